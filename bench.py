@@ -21,9 +21,12 @@ stated as a GoalError, captured in a HIP graph); `--step-mode generic` times the
 error function as arbitrary torch code instead.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--rays R] [--no-cpu-baseline]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  `--dump-outputs DIR` also writes what the last of the K timed steps
+returned to its caller (step error, parameters after the update, the traced ray sets; rank 0's
+shard with several ranks) as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -212,6 +215,54 @@ def spawn_ranks(n, argv):
 
 
 MIN_TIMED_SECONDS = 0.2
+DUMP_ROWS_MAX = 65_536         # rows kept of a larger ray set (a fixed, seeded sample)
+DUMP_BYTES_MAX = 64_000_000
+
+
+def snapshot_outputs(error, parameters, eng):
+    """What the step just run returned to its caller, copied on the device (later steps reuse
+    the buffers): the step error, the parameters after the step's update, the ray counts per pass
+    and every field of the ray sets of the step's trace.  dump_outputs writes it."""
+    snap = {"error": error, "ray_counts": [np.asarray(c) for c in eng.last_trace["counts"]]}
+    for name, p in parameters.items():
+        snap[name] = p.detach().clone()
+    for cls in ("finished", "active", "stopped", "dead"):
+        rays = getattr(eng, cls + "_rays")
+        if rays:
+            snap[cls] = {k: v.detach().clone() for k, v in rays.items()}
+    return snap
+
+
+def dump_outputs(out_dir, snap):
+    """--dump-outputs: a snapshot_outputs() as DIR/<name>.npy in float32 / float64 (ray set
+    fields as <set>_<field>).  A ray set of more than DUMP_ROWS_MAX rays is cut to a sample of rows
+    drawn with a fixed seed from its row count (`<set>_rows.npy` holds their indices).  Returns
+    {name: shape}."""
+    arrays = {"error": np.asarray(snap["error"], dtype=np.float64),
+              "ray_counts": np.stack(snap["ray_counts"])}
+    for name, v in snap.items():
+        if isinstance(v, torch.Tensor):
+            arrays[name] = v.cpu().numpy()
+    for cls in ("finished", "active", "stopped", "dead"):
+        if cls not in snap:
+            continue
+        fields = {k: v.cpu().numpy() for k, v in snap[cls].items()}
+        n = next(iter(fields.values())).shape[0]
+        if n > DUMP_ROWS_MAX:
+            rows = np.sort(np.random.default_rng(0).choice(n, DUMP_ROWS_MAX, replace=False))
+            fields = {k: v[rows] for k, v in fields.items()}
+            arrays[cls + "_rows"] = rows
+        for k, v in fields.items():
+            arrays[f"{cls}_{k}"] = v
+    arrays = {k: v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)
+              for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than {DUMP_BYTES_MAX}")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
 
 
 def main(argv=None):
@@ -248,7 +299,12 @@ def main(argv=None):
                     help="several ranks: capture the RCCL all-reduce inside the step's graph "
                          "(FusedStep.capture_collective; default: called between two graphs -- the "
                          "captured form has only been replayed with a one-rank group so far)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned to its caller "
+                         "(error, parameters, ray sets: float32 / float64 .npy, at most 64 MB) to DIR")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under torchrun: one process cannot stand for N ranks
@@ -259,6 +315,8 @@ def main(argv=None):
     if args.config != "cfg4":
         if args.gpus != 1:
             raise SystemExit("--config other than cfg4 is a single-GPU measurement")
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the headline workload's outputs (cfg4) only")
         import bench_configs
         bench_configs.run(args.config, args)
         return
@@ -295,14 +353,15 @@ def main(argv=None):
             return _timed_leg(*a, **kw)
 
     def _timed_leg(global_rays, trace_mode, step_mode, dtype, profile=False, random_rays=False,
-                  coherent="auto", exact_steps=False):
+                  coherent="auto", exact_steps=False, dump_dir=None):
         """Build the scene with `global_rays` source rays (each rank traces its contiguous
         shard), run warmup steps, then time optimiser steps between barriers: EXACTLY --steps of
         them with `exact_steps` (the headline leg: the contract's K), else at least
         MIN_TIMED_SECONDS worth (side legs).  The headline leg then runs a second, longer loop
         (`steady`: >= MIN_TIMED_SECONDS, reported beside the line, never `value`).  Returns a dict:
         seconds (max over ranks), tests (sum over ranks), per-launch ms of the hot kernels (only
-        with `profile`, which needs eagerly launched kernels), pass counts, faces, mode."""
+        with `profile`, which needs eagerly launched kernels), pass counts, faces, mode; with
+        `dump_dir`, rank 0 writes the last timed step's outputs there (dump_outputs)."""
         ray_dtype = torch.float32 if dtype == "f32" else torch.float64
         eng, system, params = build_scene(global_rays, args.k_front, args.k_back, ray_dtype,
                                           accelerate=trace_mode, random_rays=random_rays,
@@ -320,17 +379,20 @@ def main(argv=None):
         fs = opt._fused_step
         barrier()
 
-        def run(n_steps):
+        def run(n_steps, keep_error=False):
             tests0 = int(fs.tests_total.item()) if fs is not None else 0
             tests_local = 0
             barrier()
             t0 = time.perf_counter()
             for _ in range(n_steps):
-                opt.single_step(None)
+                # (dropped before the next step: a step copies out an error value still referenced)
+                err = None
+                err = opt.single_step(None)
                 if fs is None:
                     tests_local += eng.last_trace["n_tests"]
             barrier()
             dt = time.perf_counter() - t0
+            run.error = float(err) if keep_error else None
             if fs is not None:
                 tests_local = int(fs.tests_total.item()) - tests0
             tests_total = float(tests_local)
@@ -358,7 +420,12 @@ def main(argv=None):
         steps = args.steps if exact_steps else enough_steps()
         if profile:
             lib.tfrt_profile_enable(1)
-        dt, tests_total = run(steps)
+        dt, tests_total = run(steps, keep_error=dump_dir is not None)
+        snap = None
+        if dump_dir is not None and rank == 0:
+            # (copied now, written after the steady loop: no idle gap on the device before it)
+            snap = snapshot_outputs(run.error, {"front_parameters": params[0],
+                                                "back_parameters": params[1]}, eng)
         per_rank_ms = [t / steps * 1e3 for t in run.per_rank_s]
         kernel_ms = []
         if profile:
@@ -375,6 +442,7 @@ def main(argv=None):
             dt2, tests2 = run(n2)
             steady = {"steps": n2, "seconds": dt2, "ms_per_step": dt2 / n2 * 1e3,
                       "tests_per_s": tests2 / dt2}
+        dumped = dump_outputs(dump_dir, snap) if snap is not None else None
         # work the in-place trace executed in its last step (rank 0's shard)
         executed = None
         st = fs._state if fs is not None else None
@@ -395,6 +463,7 @@ def main(argv=None):
                    in_place=bool(fs.in_place) if fs is not None else False, executed=executed,
                    graph_replays=fs.graph_replays if fs is not None else 0,
                    collective_in_graph=bool(fs.collective_in_graph) if fs is not None else None,
+                   dumped=dumped,
                    capture_error=repr(fs.capture_error) if fs is not None and fs.capture_error
                    else None)
         del eng, system, params, opt
@@ -403,7 +472,8 @@ def main(argv=None):
 
     per_rank = args.scaling == "weak"
     global_rays = args.rays * world if per_rank else args.rays
-    main_leg = timed_leg(global_rays, args.trace_mode, args.step_mode, args.dtype, exact_steps=True)
+    main_leg = timed_leg(global_rays, args.trace_mode, args.step_mode, args.dtype, exact_steps=True,
+                         dump_dir=args.dump_outputs)
     side = {}
     if world > 1 and not args.no_extra_legs:
         # the other scaling convention, separately reported (never `value`)
@@ -635,6 +705,8 @@ def main(argv=None):
         % (step_bytes / 1e6))
     if main_leg["capture_error"]:
         line["config"]["graph_capture_error"] = main_leg["capture_error"]
+    if main_leg["dumped"] is not None:
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": main_leg["dumped"]}
     line.update(side)
     if world == 1 and not args.no_extra_legs:
         # separately reported legs (never `value`); results are identical in every trace mode

@@ -12,6 +12,7 @@ The fixture holds data only.  tests/test_reference_golden.py then checks the ora
 HIP entry points (GPU) against it.  What this pins and what not: the reference's operation ORDER,
 masking and formulas as written in its source; not TensorFlow's own kernels (the stand-in supplies
 the arithmetic), so the evidence is "restatement transcribed correctly", not "TensorFlow ran".
+sin / cos / asin / atan2 are the C library's (tests/host_libm.py), as in the oracle's checks.
 """
 import importlib.util
 import os
@@ -21,6 +22,9 @@ import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+from host_libm import host_libm  # noqa: E402
+
 REF = "/root/reference/tfrt/geometry.py"
 PI = np.pi
 
@@ -108,6 +112,7 @@ if __name__ == "__main__":
         raise SystemExit("the reference is not present here: fixtures can only be made in the build container")
     mod = load_reference()
     d = inputs()
-    out = run(mod, d)
+    with host_libm():
+        out = run(mod, d)
     np.savez_compressed(os.path.join(HERE, "reference_geometry.npz"), **d, **out)
     print({k: v.shape for k, v in out.items() if hasattr(v, "shape")})

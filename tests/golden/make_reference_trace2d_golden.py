@@ -21,6 +21,8 @@ boundary entry such a ray touched up to and including the reflecting one.  Scene
 mirror polyline); ``gtir`` arcs of alternating radius sign: total internal reflection near the
 ends of the negative ones; ``prism`` acrylic bodies of segments: 45-degree total internal
 reflection in a prism, plain refraction through a slab.
+
+sin / cos / asin / atan2 are the C library's (tests/host_libm.py), as in the oracle's checks.
 """
 import os
 import sys
@@ -41,6 +43,7 @@ import tfrt.engine as ref_engine        # noqa: E402  (the reference's modules)
 import tfrt.materials as ref_materials  # noqa: E402
 import tfrt.operation as ref_operation  # noqa: E402
 from test_gpu_trace2d import _scene     # noqa: E402  (scene generator shared with the GPU tests)
+from host_libm import host_libm         # noqa: E402
 
 GEO = ("x_start", "y_start", "x_end", "y_end")
 
@@ -195,4 +198,5 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    with host_libm():
+        main()

@@ -12,6 +12,13 @@ import torch
 PI = math.pi
 
 
+@pytest.fixture
+def on_host(monkeypatch):
+    """New scene tensors on the CPU even where a GPU is visible (config picks the GPU then)."""
+    import tensorflowraytrace_amd.config as config
+    monkeypatch.setattr(config, "_device", torch.device("cpu"))
+
+
 def test_update_order_and_frozen():
     from tensorflowraytrace_amd.update import RecursivelyUpdatable
     log = []
@@ -118,7 +125,7 @@ def test_distributions_and_sources_dense_undense(cpu_backend):
         sources.AperatureSource(3, a, distributions.StaticUniformCircle(5, 1.0), [575.0], dense=False)
 
 
-def test_quaternion_helpers():
+def test_quaternion_helpers(on_host):
     import tensorflowraytrace_amd.distributions as d
     q = d.get_rotation_quaternion_from_u_to_v((1.0, 0, 0), (0, 1.0, 0))
     v = d.rotate_vector_by_quaternion(q, torch.tensor([[1.0, 0, 0], [0, 0, 1.0]], dtype=torch.float64))
@@ -520,7 +527,7 @@ def test_planar_interpolated_remesh_reproduces_a_plane_and_a_paraboloid():
 # ------------------------------------------------------------------------------------------
 # analysis helpers (tfrt/analyze.py)
 
-def test_histogram2d_matches_numpy_and_clips_outliers_into_edge_bins():
+def test_histogram2d_matches_numpy_and_clips_outliers_into_edge_bins(on_host):
     import tfrt.analyze as analyze
     rng = np.random.default_rng(5)
     x, y = rng.uniform(-1, 1, 5000), rng.uniform(-2, 2, 5000)

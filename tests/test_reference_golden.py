@@ -6,7 +6,9 @@ raw_line_triangle_intersect, raw_line_circle_intersect, angle_in_interval, snell
 snells_law_3D (tfrt/geometry.py:96-802).
 
 * the oracle restatement reproduces every output BIT FOR BIT (same formulas, same order, same
-  masking, same arithmetic): a transcription error in oracle/geom.py would show here;
+  masking, same arithmetic): a transcription error in oracle/geom.py would show here.  Both sides
+  take sin / cos / asin / atan2 from the C library (tests/host_libm.py): torch's own kernels for
+  them differ in the last bit from one CPU model to another;
 * on the GPU the HIP entry points reproduce the algebraic outputs (line x line, line x triangle,
   Snell 3-D) bit for bit and the outputs that go through atan2 / sin / cos / asin (device libm vs
   host libm) to 1e-12; valid masks identical.
@@ -17,6 +19,7 @@ import numpy as np
 import pytest
 import torch
 
+from host_libm import host_libm
 from oracle import geom
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_geometry.npz")
@@ -27,11 +30,18 @@ def g():
     return np.load(GOLD)
 
 
+@pytest.fixture
+def libm():
+    """The elementary functions the reference fixtures were made with (tests/host_libm.py)."""
+    with host_libm():
+        yield
+
+
 def _t(a, dev="cpu"):
     return torch.tensor(np.ascontiguousarray(a), dtype=torch.float64, device=dev)
 
 
-def test_oracle_reproduces_the_reference_source_bit_for_bit(g):
+def test_oracle_reproduces_the_reference_source_bit_for_bit(g, libm):
     eps = 1e-10
     x, y, valid, u, v = geom.raw_line_intersect(*[_t(r) for r in g["li"]], eps)
     assert np.array_equal(valid.numpy(), g["li_valid"]) and 0 < (~g["li_valid"]).sum() < 300
@@ -182,7 +192,7 @@ def _oracle_2d(g, tag, bug_compatible=False):
 
 
 @pytest.mark.parametrize("tag", ["arc", "seg", "both"])
-def test_oracle_2d_trace_reproduces_the_reference_engine_bit_for_bit(tag):
+def test_oracle_2d_trace_reproduces_the_reference_engine_bit_for_bit(tag, libm):
     """Unmixed scenes: plain oracle.  The mixed scene: the reference pairs the reacting rays
     [segment hits, arc hits] with boundary data ordered [arc, segment] (engine.py:1958-1965); the
     oracle reproduces that output exactly with ``bug_compatible=True``."""
@@ -259,7 +269,7 @@ def _check_grad(got, want, tag, key, rtol, scale=None):
 
 
 @pytest.mark.parametrize("tag", GRAD2D_TAGS)
-def test_oracle_2d_gradients_reproduce_the_reference_tape(tag):
+def test_oracle_2d_gradients_reproduce_the_reference_tape(tag, libm):
     """torch.autograd through the oracle == torch.autograd through the reference's own source
     (the fixture), field by field, NaN for NaN: grefr / arc / seg have no total internal
     reflection (all finite); prism and gtir do (the entries the reflected rays touched are NaN,

@@ -672,3 +672,86 @@ def test_full_size_coherent_gradients_against_oracle_autograd(full, dtype, tol):
     _, nat_g = _loss_and_grads(nat, scene, list(nat_p))
     for a, b in zip(whole, nat_g):
         assert float((a - b).abs().max()) <= (1e-10 if dtype == torch.float64 else 2e-6) * float(b.abs().max())
+
+
+@pytest.fixture(scope="module")
+def full_inplace(full):
+    """cfg4's 1M-ray source sorted (ops.ray_order) and traced in place over the 3 passes
+    (tfrt_scene3d.in_place: one launch, 64-ray wavefronts at this size), the sets restored to the
+    reference's order by ops.restore_order."""
+    from tensorflowraytrace_amd import ops
+    from test_gpu_inplace import assert_in_place
+    sc, src, fv = full["sc"], full["src"], full["fv"].detach()
+    order = ops.ray_order(src)
+    p64 = order.long()
+    args = ops.Scene3DArgs(fv, sc.catagory, mat_in=sc.mat_in, mat_out=sc.mat_out,
+                           n_table=sc.n_table[:, p64].contiguous(), face_grad_mask=sc.face_grad_mask,
+                           cluster_order=sc.cluster_order, coherent_rays=True)
+    args.coherent_only = args.in_place = True
+    assert_in_place(args, fv, N_FULL, PASSES)
+    raw = ops.trace3d(src[:, p64].contiguous(), fv, args, max_passes=PASSES, flags=full["flags"])
+    assert raw["left_over"] == 0
+    return ops.restore_order(raw, order)
+
+
+def test_full_size_in_place_trace_equals_the_natural_order_trace(full, full_inplace):
+    out, got = full["out"], full_inplace
+    assert np.array_equal(got["counts"], out["counts"]) and got["n_tests"] == out["n_tests"]
+    for cls in ("finished", "active", "stopped", "dead", "unfinished"):
+        assert torch.equal(got[cls + "_id"], out[cls + "_id"]), cls
+        if cls != "unfinished":
+            assert torch.equal(got[cls + "_face"], out[cls + "_face"]), cls
+        assert torch.equal(got[cls].detach(), out[cls].detach()), cls
+
+
+def test_full_size_in_place_sample_against_the_oracle(full, full_inplace):
+    """test_full_size_sample_against_the_oracle's 256 rays, read from the in-place trace."""
+    test_full_size_sample_against_the_oracle(dict(full, out=full_inplace))
+
+
+@pytest.mark.parametrize("dtype,tol", [(torch.float32, 2e-6), (torch.float64, 1e-10)])
+def test_cfg4_in_place_fused_step_against_the_generic_step(dtype, tol):
+    """The step bench.py times, on its own cfg4 scene (bench.build_scene: 1M rays, 10,574 faces,
+    3 passes) and with its optimiser: once the engine traces the sorted source in place, the fused
+    step runs the in-place goal chain with 64-ray wavefronts (k_backward_chain recomputing the
+    finished rows from the tape).  Its gradient, read from the parameter change, against the
+    generic natural-order step (ops.trace3d + torch.autograd, the path the 512-ray oracle slices
+    of test_full_size_coherent_gradients_against_oracle_autograd pin) at the same parameters.
+    (The clip is opened so that the parameter change is the gradient; the warm-up steps take
+    lr_scale = 0 so the lens stays where the second system is built, the measured one a larger
+    scale so that the change stands well above the parameters' rounding.)"""
+    import bench
+    import tfrt.optimizer as optimizer
+    eng, system, params = bench.build_scene(N_FULL, K_FRONT, K_BACK, dtype)
+    opt = optimizer.SGD_Optimizer(eng, params, bench.make_error_function(), trace_depth=3,
+                                  learning_rate=1e-6, grad_clip=1e9, fused="auto", graph="auto",
+                                  speculative=False)
+    opt.suppress_warnings = True
+    for _ in range(10):
+        opt.single_step(None, lr_scale=0.0)
+        fs = opt._fused_step
+        if fs is not None and fs.in_place and fs.folded_backward:
+            break
+    assert fs.in_place and fs.folded_backward
+    used = [p.detach().clone() for p in params]
+    lr_scale = 100.0
+    opt.single_step(None, lr_scale=lr_scale)
+    assert fs.in_place and fs.folded_backward
+    assert fs.capture_error is None, fs.capture_error
+    scale = opt.sgd_learning_rate * opt.learning_rate * lr_scale
+    got = [(u - p.detach()) / scale for u, p in zip(used, params)]
+
+    eng2, system2, params2 = bench.build_scene(N_FULL, K_FRONT, K_BACK, dtype, coherent=False)
+    with torch.no_grad():
+        for p2, u in zip(params2, used):
+            p2.copy_(u)
+    opt2 = optimizer.SGD_Optimizer(eng2, params2, bench.make_error_function(), trace_depth=3,
+                                   learning_rate=1e-6, grad_clip=1e9, fused=False, speculative=False)
+    opt2.suppress_warnings = True
+    want, _, n_terms = opt2.raw_gradient()
+    assert getattr(eng2, "_order_cache", None) is None          # (natural order)
+    assert int(float(opt.last_error_terms)) == int(n_terms) > 1_500_000
+    for g, w in zip(got, want):
+        assert float(w.abs().max()) > 0
+        rel = float((g - w).abs().max() / w.abs().max())
+        assert rel <= tol, f"gradient rel err {rel:.2e}"

@@ -247,3 +247,46 @@ def test_fused_step_in_coherent_order_equals_the_generic_path():
     for f, v in fin.items():
         np.testing.assert_allclose(v.cpu().numpy(), eng2.finished_rays[f].detach().cpu().numpy(),
                                    rtol=0, atol=1e-8, err_msg=f)
+
+
+@pytest.mark.parametrize("mode", ["eager", "graph"])
+@pytest.mark.parametrize("ray_dtype,tol", [(torch.float32, 1e-5), (torch.float64, 1e-8)])
+def test_in_place_fused_step_gradient_against_oracle_autograd(mode, ray_dtype, tol):
+    """The step bench.py times: 8,192 rays (the engine sorts them, and once a trace has left no
+    wavefront over it traces them in place), the GoalError folded into the reverse sweep, which
+    recomputes every finished row from the in-place tape (input ray + hit parameter, rounded to the
+    ray state) instead of reading it back.  (p_before - p_after) / (0.01 * scale) against
+    torch.autograd through the oracle at p_before, eagerly and under graph replay."""
+    opt, eng, system, lens, target, source, _ = _make(8192, mode, ray_dtype=ray_dtype)
+    for _ in range(8):                                   # order, visit-all note, graph capture
+        opt.single_step(None)
+    fs = opt._fused_step
+    assert getattr(eng, "_visit_all_key", None) is not None
+    replays = fs.graph_replays
+    system.update()                                      # constraints settle the parameters
+    used = _params(lens)
+    err = float(opt.single_step(None))
+    after = _params(lens)
+    assert fs.in_place and fs.folded_backward            # the step just measured
+    if mode == "graph":
+        assert fs.capture_error is None, fs.capture_error
+        assert fs.graph_replays == replays + 1 >= 2
+    else:
+        assert fs.graph_replays == 0
+    scale = 0.01 * opt.learning_rate
+    q = [u.clone().requires_grad_(True) for u in used]
+    osys, src = _oracle_for(system, lens, target, source, q)
+    if ray_dtype == torch.float32:
+        for k in ("x_start", "y_start", "z_start", "x_end", "y_end", "z_end"):
+            src[k] = src[k].float().double()
+    ref = tracer.ray_trace(osys, src, max_iterations=3, inherit=("wavelength", "object_coords"))
+    rf = ref["finished"]
+    rerr = (torch.stack([rf["y_end"], rf["z_end"]], 1) + rf["object_coords"][:, 1:]) ** 2
+    rg = torch.autograd.grad(rerr.sum(), q)
+    assert rf["y_end"].shape[0] > 6000
+    assert abs(err - float(rerr.mean().detach())) <= tol * float(rerr.mean().detach())
+    assert int(float(opt.last_error_terms)) == rerr.numel()
+    for k in range(2):
+        g = (used[k] - after[k]) / scale
+        rel = float((g - rg[k]).abs().max() / rg[k].abs().max())
+        assert rel < tol, f"surface {k}: gradient rel err {rel:.2e}"

@@ -19,6 +19,7 @@ import pytest
 import torch
 
 import test_gpu_stress as st
+from test_gpu_inplace import assert_in_place
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -70,6 +71,7 @@ def test_in_place_and_hierarchy_traces_equal_the_all_pairs_trace(seed):
                                        **base)
                 args.eps = eps
                 args.coherent_only = args.in_place = True
+                assert_in_place(args, fv, r.shape[1], passes)
                 raw = ops.trace3d(r[:, order.long()].contiguous(), fv, args,
                                   **(dict(kw, perm=order) if by_slot else kw))
                 out = raw if by_slot else ops.restore_order(raw, order)

@@ -39,6 +39,16 @@ def _same(out, ref, tag):
             assert torch.equal(out[cls + "_face"], ref[cls + "_face"]), (tag, cls)
 
 
+def assert_in_place(args, fv, n_rays, passes):
+    """The trace about to run with ``args`` takes the in-place route.  inplace_trace()
+    (tfrt_trace3d.hip) falls back to the per-pass path without a word -- fewer than 64 rays or
+    64 faces, no cluster_order, deterministic, coherent_rays unset -- and ops.trace3d does not say
+    which path ran: an in-place test that skips this may be testing the per-pass path."""
+    from tensorflowraytrace_amd import _lib
+    assert _lib.lib().tfrt_trace3d_in_place(ctypes.byref(args.struct(fv)), n_rays, passes) == 1, \
+        ("not an in-place trace", n_rays, passes)
+
+
 def _lens_args(sc, fv, order, in_place, eps=None):
     from tensorflowraytrace_amd import ops
     a = ops.Scene3DArgs(fv, sc.catagory, mat_in=sc.mat_in, mat_out=sc.mat_out,
@@ -66,8 +76,10 @@ def test_in_place_trace_equals_the_per_pass_trace_on_lens_scenes(n_rays, dtype, 
     rays = src[:, order.long()].contiguous()
     outs = {}
     for in_place in (False, True):
-        outs[in_place] = ops.trace3d(rays, fv, _lens_args(sc, fv, order, in_place),
-                                     max_passes=passes, flags=_flags())
+        args = _lens_args(sc, fv, order, in_place)
+        if in_place:
+            assert_in_place(args, fv, n_rays, passes)
+        outs[in_place] = ops.trace3d(rays, fv, args, max_passes=passes, flags=_flags())
     assert int(outs[False]["counts"][:, 1].sum()) > (0.5 * n_rays if n_rays >= 1000 else 0)   # most rays finish
     _same(outs[True], outs[False], (n_rays, dtype, passes))
     # ... and, restored, the natural-order trace (the reference's order)
@@ -99,6 +111,7 @@ def test_in_place_trace_on_adversarial_soups(seed):
                                coherent_rays=True, **base)
         args.eps = eps
         args.coherent_only = args.in_place = True
+        assert_in_place(args, fv, r.shape[1], 4)
         raw = ops.trace3d(r[:, order.long()].contiguous(), fv, args, max_passes=4, flags=_flags(),
                           new_ray_length=sc0["L"], dead_ray_length=0.5 if seed % 2 else None)
         _same(ops.restore_order(raw, order), ref, (seed, dtype))
@@ -118,8 +131,10 @@ def test_in_place_gradients_equal_the_per_pass_gradients(dtype):
     for in_place in (False, True):
         fv = fv0.detach().clone().requires_grad_(True)
         rays = rays0.detach().clone().requires_grad_(True)
-        out = ops.trace3d(rays, fv, _lens_args(sc, fv.detach(), order, in_place), max_passes=3,
-                          flags=_flags())
+        args = _lens_args(sc, fv.detach(), order, in_place)
+        if in_place:
+            assert_in_place(args, fv.detach(), rays.shape[1], 3)
+        out = ops.trace3d(rays, fv, args, max_passes=3, flags=_flags())
         w = torch.linspace(0.5, 1.5, out["finished"].shape[1], device=DEV, dtype=torch.float64)
         err = (w * (out["finished"][4].double() ** 2 + out["finished"][5].double() ** 2)).sum()
         err = err + (out["active"][3].double() * out["active"][0].double()).sum() * 1e-3
@@ -145,6 +160,7 @@ def test_compact_entry_fills_the_sets_a_forward_call_without_outputs_left_out():
     rays = src[:, order.long()].contiguous()
     args = _lens_args(sc, fv, order, True)
     P, N, M = 4, rays.shape[1], fv.shape[0]
+    assert_in_place(args, fv, N, P)
     ref = ops.trace3d(rays, fv, args, max_passes=P, flags=_flags())
     wsb = L.tfrt_trace3d_workspace_bytes(N, M, P, _lib.F32)
     ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
@@ -227,8 +243,10 @@ def test_in_place_trace_hands_the_sets_back_in_the_callers_order(n_rays, dtype, 
     grads = {}
     for in_place in (True, False):
         fv = fv0.detach().clone().requires_grad_(True)
-        out = ops.trace3d(rays, fv, _lens_args(sc, fv.detach(), order, in_place), max_passes=passes,
-                          flags=_flags(), perm=order)
+        args = _lens_args(sc, fv.detach(), order, in_place)
+        if in_place:
+            assert_in_place(args, fv.detach(), n_rays, passes)
+        out = ops.trace3d(rays, fv, args, max_passes=passes, flags=_flags(), perm=order)
         _same(out, ref, ("own order", in_place, n_rays, dtype))
         w = torch.linspace(0.5, 1.5, out["finished"].shape[1], device=DEV, dtype=torch.float64)
         err = (w * (out["finished"][4].double() ** 2 + out["finished"][5].double() ** 2)).sum()

@@ -182,12 +182,14 @@ def test_value_mode_matches_index_mode():
     np.testing.assert_allclose(a["finished"].detach().cpu().numpy(), b["finished"].detach().cpu().numpy(), atol=1e-12)
 
 
-@pytest.mark.parametrize("coherent", [False, True])
+@pytest.mark.parametrize("coherent", [False, True, "in_place"])
 def test_value_mode_gradient_with_respect_to_the_refractive_indices(coherent):
     """StandardReaction('value') reads n_in / n_out as ordinary tensors (operation.py:268-272), so
     a tape can differentiate an error w.r.t. them: the reverse sweep accumulates d error /
     d n_in[face], d n_out[face] (tfrt_scene3d.grad_n_in / grad_n_out) -- against torch.autograd
-    through the oracle, per-face indices drawn at random around the acrylic value."""
+    through the oracle, per-face indices drawn at random around the acrylic value.  "in_place": the
+    rays sorted, traced in place (k_backward_chain with the index terms, on the in-place tape),
+    handed back in their own order through perm=."""
     from tensorflowraytrace_amd import ops
     scene = scene_util.lens_scene(6000, k_front=4, k_back=3)
     src, fv, sc, _ = _gpu_scene(scene, torch.float64, cluster="group")
@@ -199,8 +201,15 @@ def test_value_mode_gradient_with_respect_to_the_refractive_indices(coherent):
     n_in = torch.tensor(n_in_np, device=fv.device, requires_grad=True)
     n_out = torch.tensor(n_out_np, device=fv.device, requires_grad=True)
     sv = ops.Scene3DArgs(fv.detach(), sc.catagory, n_in=n_in, n_out=n_out,
-                         cluster_order=sc.cluster_order, coherent_rays=coherent)
-    out = ops.trace3d(src, fv.detach(), sv, max_passes=4)
+                         cluster_order=sc.cluster_order, coherent_rays=bool(coherent))
+    if coherent == "in_place":
+        from test_gpu_inplace import assert_in_place
+        order = ops.ray_order(src)
+        sv.coherent_only = sv.in_place = True
+        assert_in_place(sv, fv.detach(), src.shape[1], 4)
+        out = ops.trace3d(src[:, order.long()].contiguous(), fv.detach(), sv, max_passes=4, perm=order)
+    else:
+        out = ops.trace3d(src, fv.detach(), sv, max_passes=4)
     goal = torch.tensor(scene["goal"], dtype=torch.float64, device=fv.device)[out["finished_id"].long()]
     fin = out["finished"]
     loss = ((fin[4] - goal[:, 0]) ** 2 + (fin[5] - goal[:, 1]) ** 2).sum()

@@ -128,35 +128,67 @@ def test_oracle_trace_reproduces_the_reference_engine_bit_for_bit():
         assert np.abs(got - want).max() <= 1e-13 * np.abs(want).max()
 
 
+# How the GPU traces a fixture's rays: the two-level filter ("group"), every ray against every face
+# ("all-pairs"), or in place (tfrt_scene3d.in_place: the rays sorted by ops.ray_order, all passes in
+# one launch, the sets compacted from the tape) with the sets brought back to the reference's order
+# by ops.restore_order ("in-place-restored") or compacted in it through perm= ("in-place-perm")
+TRACE_MODES = ["group", "all-pairs", "in-place-restored", "in-place-perm"]
+
+
+def _in_place_trace(src, fv, args, order, passes, mode, **kw):
+    """trace3d of `src` in place over the order `order` (ops.ray_order; `args`: the scene of the
+    SORTED rays); the outputs in the reference's order, gradients flowing back through the
+    permutation."""
+    from tensorflowraytrace_amd import ops
+    from test_gpu_inplace import assert_in_place
+    rays = src[:, order.long()].contiguous()
+    args.coherent_rays = True
+    args.coherent_only = args.in_place = True
+    assert_in_place(args, fv.detach(), rays.shape[1], passes)
+    if mode == "in-place-perm":
+        return ops.trace3d(rays, fv, args, max_passes=passes, perm=order, **kw)
+    assert mode == "in-place-restored", mode
+    return ops.restore_order(ops.trace3d(rays, fv, args, max_passes=passes, **kw), order)
+
+
 @pytest.mark.gpu
+@pytest.mark.parametrize("mode", TRACE_MODES)
 @pytest.mark.parametrize("dtype,tol", [(torch.float64, 0.0), (torch.float32, 1e-5)])
-def test_hip_trace_reproduces_the_reference_engine(dtype, tol):
+def test_hip_trace_reproduces_the_reference_engine(dtype, tol, mode):
     """float64 ray state: classes, order and every coordinate of the finished and active sets equal
-    the reference engine's output bit for bit; gradients to 1e-8.  float32 state: 1e-5."""
+    the reference engine's output bit for bit; gradients to 1e-8.  float32 state: 1e-5.  In every
+    trace mode, the in-place trace and its reverse sweep included."""
     from tensorflowraytrace_amd import ops, _lib
     from test_gpu_trace3d import _gpu_scene
     g = np.load(TRACE)
     scene = {k: g[k] for k in g.files}
-    for cluster in ("group", False):
-        src, fv, sc, (p_f, p_b) = _gpu_scene(scene, dtype, cluster=cluster)
-        flags = _lib.COMPILE_ACTIVE | _lib.COMPILE_FINISHED | _lib.COMPILE_DEAD | _lib.COMPILE_STOPPED
+    src, fv, sc, (p_f, p_b) = _gpu_scene(scene, dtype, cluster=mode != "all-pairs" and "group")
+    flags = _lib.COMPILE_ACTIVE | _lib.COMPILE_FINISHED | _lib.COMPILE_DEAD | _lib.COMPILE_STOPPED
+    if mode.startswith("in-place"):
+        # (n(lambda) per ray: the table's columns follow the sorted rays, as the engine keeps it)
+        order = ops.ray_order(src)
+        args = ops.Scene3DArgs(fv.detach(), sc.catagory, mat_in=sc.mat_in, mat_out=sc.mat_out,
+                               n_table=sc.n_table[:, order.long()].contiguous(),
+                               face_grad_mask=sc.face_grad_mask, cluster_order=sc.cluster_order)
+        out = _in_place_trace(src, fv, args, order, int(g["passes"]), mode, flags=flags)
+    else:
         out = ops.trace3d(src, fv, sc, max_passes=int(g["passes"]), flags=flags)
-        assert out["dead"].shape[1] == 0 and out["stopped"].shape[1] == 0
-        for cls in ("finished", "active"):
-            assert np.array_equal(out[cls + "_id"].cpu().numpy().astype(np.int64), g[cls + "_id"]), cls
-            got = out[cls].detach().cpu().double().numpy()
-            if tol == 0.0:
-                assert np.array_equal(got, g[cls]), (cls, cluster)
-            else:
-                assert np.abs(got - g[cls]).max() / max(1.0, np.abs(g[cls]).max()) <= tol
-        fin = out["finished"]
-        goal = torch.tensor(g["goal"], device=fin.device)[out["finished_id"].long()]
-        loss = ((fin[4].double() - goal[:, 0]) ** 2 + (fin[5].double() - goal[:, 1]) ** 2).sum()
-        g_f, g_b = torch.autograd.grad(loss, [p_f, p_b])
-        gtol = 1e-8 if tol == 0.0 else tol
-        assert abs(float(loss.detach()) - float(g["loss"])) <= max(gtol, 1e-12) * float(g["loss"])
-        for got, want in ((g_f.cpu().numpy(), g["grad_front"]), (g_b.cpu().numpy(), g["grad_back"])):
-            assert np.abs(got - want).max() <= gtol * np.abs(want).max()
+    assert out["dead"].shape[1] == 0 and out["stopped"].shape[1] == 0
+    for cls in ("finished", "active"):
+        assert np.array_equal(out[cls + "_id"].cpu().numpy().astype(np.int64), g[cls + "_id"]), cls
+        got = out[cls].detach().cpu().double().numpy()
+        if tol == 0.0:
+            assert np.array_equal(got, g[cls]), (cls, mode)
+        else:
+            assert np.abs(got - g[cls]).max() / max(1.0, np.abs(g[cls]).max()) <= tol
+    fin = out["finished"]
+    goal = torch.tensor(g["goal"], device=fin.device)[out["finished_id"].long()]
+    loss = ((fin[4].double() - goal[:, 0]) ** 2 + (fin[5].double() - goal[:, 1]) ** 2).sum()
+    g_f, g_b = torch.autograd.grad(loss, [p_f, p_b])
+    gtol = 1e-8 if tol == 0.0 else tol
+    assert abs(float(loss.detach()) - float(g["loss"])) <= max(gtol, 1e-12) * float(g["loss"])
+    for got, want in ((g_f.cpu().numpy(), g["grad_front"]), (g_b.cpu().numpy(), g["grad_back"])):
+        assert np.abs(got - want).max() <= gtol * np.abs(want).max()
 
 
 # ---------------------------------------------------------------------------------------------
@@ -455,34 +487,42 @@ def test_oracle_reproduces_the_reference_engine_on_adversarial_soups(tag):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("mode", TRACE_MODES)
 @pytest.mark.parametrize("tag", ["plain", "deadlen"])
-def test_hip_reproduces_the_reference_engine_on_adversarial_soups(tag):
-    """float64 ray state, hierarchy and all-pairs modes: every class holds the reference engine's
-    rays, in its order, with every coordinate bit equal (coplanar ties, stops, dead rays cut to
-    dead_ray_length, rays still travelling after the last pass)."""
+def test_hip_reproduces_the_reference_engine_on_adversarial_soups(tag, mode):
+    """float64 ray state, hierarchy, all-pairs and in-place modes: every class holds the reference
+    engine's rays, in its order, with every coordinate bit equal (coplanar ties, stops, dead rays
+    cut to dead_ray_length, rays still travelling after the last pass); the reverse sweep -- in
+    place: class gradients read through rec_slot, stopped and dead classes included -- against the
+    reference-source gradient."""
     from tensorflowraytrace_amd import ops, _lib
     g = np.load(SOUP)
     dev = "cuda:0"
     flags = _lib.COMPILE_ACTIVE | _lib.COMPILE_FINISHED | _lib.COMPILE_DEAD | _lib.COMPILE_STOPPED
+    # (every fixture soup -- 700 rays or more, 300 faces or more -- goes in place: _in_place_trace
+    # asserts it before it traces)
     for seed in g["seeds"]:
         sc = _soup_case(g, seed)
         fv = sc["P"].to(dev).requires_grad_(tag == "plain")
-        for clustered in (True, False):
-            args = ops.Scene3DArgs(fv.detach(), sc["cat"].int().to(dev), n_in=sc["n_in"].to(dev),
-                                   n_out=sc["n_out"].to(dev),
-                                   cluster_order=ops.cluster_order(fv.detach()) if clustered else None)
-            out = ops.trace3d(sc["rays"].to(dev), fv, args, max_passes=int(g["passes"]), flags=flags,
-                              new_ray_length=sc["L"],
-                              dead_ray_length=sc["dead"] if tag == "deadlen" else None)
-            for cls in CLASSES:
-                want, want_id = g[f"s{seed}__{tag}__{cls}"], g[f"s{seed}__{tag}__{cls}_id"]
-                got = out[cls].detach().cpu().numpy()
-                assert got.shape[1] == want.shape[1], (seed, cls, clustered)
-                assert np.array_equal(out[cls + "_id"].cpu().numpy().astype(np.int64), want_id), \
-                    (seed, cls, clustered)
-                assert np.array_equal(got, want), (seed, cls, clustered)
-            if tag == "plain":
-                # the reverse sweep against the reference-source gradient of the same scalar
-                loss = _soup_loss(out["finished"], out["active"], out["stopped"], sc["L"])
-                (gP,) = torch.autograd.grad(loss, [fv])
-                _check_grad(gP.cpu().numpy(), g[f"s{seed}__plain__grad_P"], f"soup {seed}", "P", 1e-8)
+        args = ops.Scene3DArgs(fv.detach(), sc["cat"].int().to(dev), n_in=sc["n_in"].to(dev),
+                               n_out=sc["n_out"].to(dev),
+                               cluster_order=ops.cluster_order(fv.detach()) if mode != "all-pairs" else None)
+        kw = dict(flags=flags, new_ray_length=sc["L"],
+                  dead_ray_length=sc["dead"] if tag == "deadlen" else None)
+        rays = sc["rays"].to(dev)
+        if mode.startswith("in-place"):
+            out = _in_place_trace(rays, fv, args, ops.ray_order(rays), int(g["passes"]), mode, **kw)
+        else:
+            out = ops.trace3d(rays, fv, args, max_passes=int(g["passes"]), **kw)
+        for cls in CLASSES:
+            want, want_id = g[f"s{seed}__{tag}__{cls}"], g[f"s{seed}__{tag}__{cls}_id"]
+            got = out[cls].detach().cpu().numpy()
+            assert got.shape[1] == want.shape[1], (seed, cls, mode)
+            assert np.array_equal(out[cls + "_id"].cpu().numpy().astype(np.int64), want_id), \
+                (seed, cls, mode)
+            assert np.array_equal(got, want), (seed, cls, mode)
+        if tag == "plain":
+            # the reverse sweep against the reference-source gradient of the same scalar
+            loss = _soup_loss(out["finished"], out["active"], out["stopped"], sc["L"])
+            (gP,) = torch.autograd.grad(loss, [fv])
+            _check_grad(gP.cpu().numpy(), g[f"s{seed}__plain__grad_P"], f"soup {seed}", "P", 1e-8)

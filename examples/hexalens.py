@@ -11,7 +11,13 @@ mesh_parametrization_tools, smoother from mesh_smoothing_tool, a phase schedule 
 per-step work (trace, error gradient) runs in the HIP kernels and the loop is driven by
 SGD_Optimizer.training_routine instead of a hand-written tf.GradientTape loop.  No GUI.
 
-    python examples/hexalens.py [--rays 20000] [--steps 30] [--edge 0.12]
+    python examples/hexalens.py [--rays 20000] [--steps 30] [--edge 0.12] [--momentum]
+
+``--momentum`` runs the reference's own schedule (dev/hexalens.py:244-300): Nesterov SGD with
+the momentum raised phase by phase, 0.6 -> 0.9 -> 0.95 -> 0.98, the phases' lengths and learning
+rates in the reference's proportions, accumulator in the first phase, smoother in the first two.
+The reference ran 225 such steps; in a run of a few dozen the error falls fastest in the first two
+phases and then oscillates under momentum 0.95 and 0.98 (the rays are re-drawn every step).
 """
 import argparse
 import os
@@ -122,14 +128,40 @@ def save_meshes(lens, directory):
     lens.surfaces[1].save(os.path.join(directory, "hexalens_second.stl"))
 
 
+# dev/hexalens.py:244-300: (steps, learning rate relative to the first phase, momentum,
+# accumulator, smoother) of each phase
+MOMENTUM_PHASES = ((50, 1.0, 0.6, True, True), (25, 2.0, 0.9, False, True),
+                   (50, 4.5, 0.95, False, False), (100, 1.0, 0.98, False, False))
+
+
+def momentum_routine(steps, lr_scale, accumulator, smoother):
+    """The reference's momentum schedule scaled to ``steps`` steps in all (one per phase at
+    least)."""
+    total = sum(ph[0] for ph in MOMENTUM_PHASES)
+    routine = []
+    for n, lr, m, acc, smooth in MOMENTUM_PHASES:
+        routine.append({"steps": max(round(steps * n / total), 1), "learning_rate": lr_scale * lr,
+                        "momentum": m, "accumulators": accumulator if acc else None,
+                        "smoothers": smoother if smooth else None})
+    return routine
+
+
 def run(ray_count=20000, steps=30, lens_res_scale=0.12, verbose=True, history_file=None,
-        resume_from=None, generic_step=False):
+        resume_from=None, generic_step=False, momentum=False):
     s = build(ray_count, lens_res_scale, generic_step=generic_step)
     parameter_history = []
     if resume_from:
         parameter_history = load_parameters(s["lens"], s["system"], resume_from)
-    opt = optimizer.SGD_Optimizer(s["engine"], s["lens"].parameters, s["error_function"], 3,
-                                  learning_rate=2e-5 * (20000 / ray_count), grad_clip=1.0)
+    learning_rate = 2e-5 * (20000 / ray_count)
+    if momentum:
+        # (momentum 0.6 multiplies the steady-state step by 1 / (1 - 0.6): the first phase moves
+        # as fast as the plain schedule; the clip caps a step at 1e-3, as the reference's does)
+        opt = optimizer.SGD_Optimizer(s["engine"], s["lens"].parameters, s["error_function"], 3,
+                                      learning_rate=(1 - 0.6) * learning_rate, grad_clip=0.1,
+                                      apply_momentum=True, nesterov=True)
+    else:
+        opt = optimizer.SGD_Optimizer(s["engine"], s["lens"].parameters, s["error_function"], 3,
+                                      learning_rate=learning_rate, grad_clip=1.0)
     opt.suppress_warnings = True
     errors = []
 
@@ -146,12 +178,15 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, verbose=True, history_fi
         return opt.last_error
 
     opt.single_step = single_step
-    routine = [
+    if momentum:
+        routine = momentum_routine(steps, 1.0, s["accumulator"], s["smoother"])
+    else:
+        routine = [
         {"steps": max(steps // 2, 1), "learning_rate": 1.0, "accumulators": s["accumulator"],
          "smoothers": s["smoother"]},
         {"steps": max(steps - steps // 2, 1), "learning_rate": (1.0, 0.5), "accumulators": None,
          "smoothers": None},
-    ]
+        ]
     opt.training_routine(routine, post_step=record, report_frequency=5 if verbose else 0,
                          show_time=verbose)
     if history_file:
@@ -170,9 +205,11 @@ if __name__ == "__main__":
     ap.add_argument("--stl-dir", default=None, help="write both optimised surfaces as STL here")
     ap.add_argument("--generic-step", action="store_true",
                     help="error function as torch code (the reference's form) instead of a GoalError")
+    ap.add_argument("--momentum", action="store_true",
+                    help="the reference's Nesterov-momentum phase schedule (0.6 -> 0.98)")
     a = ap.parse_args()
     errs, state = run(a.rays, a.steps, a.edge, history_file=a.history, resume_from=a.resume,
-                      generic_step=a.generic_step)
+                      generic_step=a.generic_step, momentum=a.momentum)
     if a.stl_dir:
         save_meshes(state["lens"], a.stl_dir)
     print(f"mean squared image error: first {errs[0]:.6g} -> last {errs[-1]:.6g}")

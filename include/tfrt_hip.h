@@ -199,6 +199,27 @@ int tfrt_sgd_process_multi_finish(int32_t n_tensors, const void* const* grad,
                                   const double* hyper, const tfrt_goal_pending* pending,
                                   void* stream);
 
+/* tfrt_sgd_process_multi with the Keras SGD momentum rule (optimizer.py:128-132 with momentum
+ * assigned): `hyper` holds {scale, clip, sgd_learning_rate, momentum, nesterov} per tensor,
+ * 5 * n_tensors float64 on the device, and velocity[k] is a persistent float64 buffer of n[k]
+ * elements per tensor (zero before the first step).  Per element, after the processing above,
+ *     if momentum == 0:  param[i] -= sgd_learning_rate * g        (velocity[i] NOT written)
+ *     else:              v = momentum * velocity[i] - sgd_learning_rate * g;  velocity[i] = v
+ *                        param[i] += momentum * v - sgd_learning_rate * g     (nesterov != 0)
+ *                        param[i] += v                                        (nesterov == 0)
+ * every product and difference rounded on its own (no fused multiply-add).  `processed` and its
+ * entries may be NULL; `param`, `velocity` and their entries (for n[k] > 0) may not.  `processed`
+ * may alias `grad`; `velocity` aliases neither `grad` nor `param`. */
+int tfrt_sgd_momentum_multi(int32_t n_tensors, const void* const* grad, void* const* processed,
+                            void* const* param, void* const* velocity, const int64_t* n,
+                            const double* hyper, void* stream);
+
+/* ... and finishes a pending error sum in one more workgroup of the same launch. */
+int tfrt_sgd_momentum_multi_finish(int32_t n_tensors, const void* const* grad,
+                                   void* const* processed, void* const* param,
+                                   void* const* velocity, const int64_t* n, const double* hyper,
+                                   const tfrt_goal_pending* pending, void* stream);
+
 /* y = A x, A in CSR form (int64 indices, f64 values): the accumulator (optimizer.py:250-255)
  * and smoother (optimizer.py:277-282) products for the sparse matrices the mesh tools
  * produce (mesh_tools.py:221-421).  x and y must not alias. */

@@ -3,6 +3,7 @@
 // k_sgd_process : non-finite -> 0, scale, clip of one gradient tensor and, optionally, the
 //                 Keras-SGD apply `param -= sgd_lr * processed` in the same launch: the host
 //                 path of the reference is six eager ops per parameter per step.
+// k_sgd_momentum_multi : the same with the Keras momentum / Nesterov rule and a velocity buffer.
 // k_csr_matvec  : y = A x for a CSR matrix: the accumulator / smoother products
 //                 (optimizer.py:250-255, 277-282).  The matrices the mesh tools build
 //                 (mesh_tools.py:221-421) have a handful of non-zeros per row, a dense (P,P)
@@ -71,6 +72,51 @@ __global__ __launch_bounds__(BLOCK) void k_sgd_process_multi(SgdBatch b,
   g = g < -clip ? -clip : (g > clip ? clip : g);
   if (b.processed[k] != nullptr) b.processed[k][i] = g;
   if (b.param[k] != nullptr) b.param[k][i] = b.param[k][i] - sgd_lr * g;
+}
+
+// The same with the Keras SGD momentum rule (optimizer.py:128-132 with momentum assigned, the
+// generic path's SGD_Optimizer.apply_gradients): a persistent velocity per parameter element and
+// two more scalars per tensor, {scale, clip, sgd_lr, momentum, nesterov} (5 float64).
+//   v  = m*v - lr*g;   p += nesterov ? m*v - lr*g : v
+// and, while m == 0, plain `p -= lr*g` with v left unwritten.  m is read on the device, so a
+// captured launch graph replays across momentum phases.
+struct SgdMomentumBatch {
+  const double* grad[SGD_BATCH];
+  double* processed[SGD_BATCH];
+  double* param[SGD_BATCH];
+  double* velocity[SGD_BATCH];
+  int64_t n[SGD_BATCH];
+  int32_t first_block[SGD_BATCH + 1];
+  int32_t count;
+};
+
+__global__ __launch_bounds__(BLOCK) void k_sgd_momentum_multi(SgdMomentumBatch b,
+                                                              const double* __restrict__ hyper,
+                                                              tfrt_goal_pending goal) {
+  if ((int)blockIdx.x == b.first_block[SGD_BATCH]) {
+    goal_finish_block(goal);
+    return;
+  }
+  int k = 0;
+  while (k + 1 < b.count && (int)blockIdx.x >= b.first_block[k + 1]) ++k;  // block-uniform
+  const int64_t i = (int64_t)((int)blockIdx.x - b.first_block[k]) * BLOCK + threadIdx.x;
+  if (i >= b.n[k]) return;
+  const double* h = hyper + 5 * k;
+  const double scale = h[0], clip = h[1], sgd_lr = h[2], m = h[3];
+  const bool nesterov = h[4] != 0.0;
+  double g = b.grad[k][i];
+  g = isfinite(g) ? g : 0.0;
+  g = g * scale;
+  g = g < -clip ? -clip : (g > clip ? clip : g);
+  if (b.processed[k] != nullptr) b.processed[k][i] = g;
+  double* p = b.param[k];
+  if (m == 0.0) {  // optimizer.py: momentum off for this phase -- v keeps its value
+    p[i] = p[i] - sgd_lr * g;
+    return;
+  }
+  const double v = m * b.velocity[k][i] - sgd_lr * g;
+  b.velocity[k][i] = v;
+  p[i] = nesterov ? p[i] + (m * v - sgd_lr * g) : p[i] + v;
 }
 
 // one wave per row; lanes stride over the row's non-zeros, butterfly-sum at the end
@@ -171,6 +217,57 @@ int tfrt_sgd_process_multi_finish(int32_t n_tensors, const void* const* grad,
                                   void* stream) {
   if (!pending) return TFRT_E_BADARG;
   return sgd_multi_launch(n_tensors, grad, processed, param, n, hyper, pending, stream);
+}
+
+static int sgd_momentum_launch(int32_t n_tensors, const void* const* grad,
+                               void* const* processed, void* const* param, void* const* velocity,
+                               const int64_t* n, const double* hyper,
+                               const tfrt_goal_pending* pending, void* stream) {
+  if (n_tensors < 0 || n_tensors > SGD_BATCH ||
+      (n_tensors > 0 && (!grad || !param || !velocity || !n || !hyper)))
+    return TFRT_E_BADARG;
+  if (pending != nullptr &&
+      (!pending->partial || (!pending->n_finished && !pending->partial_counts) ||
+       !pending->error_out || pending->n_partial < 0))
+    return TFRT_E_BADARG;
+  SgdMomentumBatch b;
+  int blocks = 0;
+  for (int k = 0; k < SGD_BATCH; ++k) {
+    const bool on = k < n_tensors;
+    if (on && (n[k] < 0 || (n[k] > 0 && (!grad[k] || !param[k] || !velocity[k]))))
+      return TFRT_E_BADARG;
+    b.grad[k] = on ? static_cast<const double*>(grad[k]) : nullptr;
+    b.processed[k] = (on && processed) ? static_cast<double*>(processed[k]) : nullptr;
+    b.param[k] = on ? static_cast<double*>(param[k]) : nullptr;
+    b.velocity[k] = on ? static_cast<double*>(velocity[k]) : nullptr;
+    b.n[k] = on ? n[k] : 0;
+    b.first_block[k] = blocks;
+    if (on) blocks += cdiv(n[k], BLOCK);
+  }
+  b.first_block[SGD_BATCH] = blocks;
+  b.count = n_tensors;
+  const int grid = blocks + (pending != nullptr ? 1 : 0);
+  if (grid == 0) return 0;
+  hipLaunchKernelGGL(k_sgd_momentum_multi, dim3(grid), dim3(BLOCK), 0,
+                     static_cast<hipStream_t>(stream), b, hyper,
+                     pending != nullptr ? *pending : tfrt_goal_pending{});
+  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+}
+
+int tfrt_sgd_momentum_multi(int32_t n_tensors, const void* const* grad, void* const* processed,
+                            void* const* param, void* const* velocity, const int64_t* n,
+                            const double* hyper, void* stream) {
+  return sgd_momentum_launch(n_tensors, grad, processed, param, velocity, n, hyper, nullptr,
+                             stream);
+}
+
+int tfrt_sgd_momentum_multi_finish(int32_t n_tensors, const void* const* grad,
+                                   void* const* processed, void* const* param,
+                                   void* const* velocity, const int64_t* n, const double* hyper,
+                                   const tfrt_goal_pending* pending, void* stream) {
+  if (!pending) return TFRT_E_BADARG;
+  return sgd_momentum_launch(n_tensors, grad, processed, param, velocity, n, hyper, pending,
+                             stream);
 }
 
 int tfrt_csr_matvec(const int64_t* crow_indices, const int64_t* col_indices, const double* values,

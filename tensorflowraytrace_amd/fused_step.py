@@ -23,6 +23,7 @@ states that form declaratively; an optimiser given a ``GoalError`` runs ``FusedS
     autograd through update()           -> d error / d parameters           (tfrt_param_faces_backward ...)
     [one all-reduce over ray shards]
     tfrt_sgd_process_dev / tfrt_csr_matvec   non-finite -> 0, scale, clip, accumulate, SGD apply
+                                        (tfrt_sgd_momentum_multi with apply_momentum=True)
 
 Every launch has step-independent arguments (learning-rate dependent scalars live in a small
 device table), so after a few eager steps the sequence is captured once in a HIP graph
@@ -168,12 +169,15 @@ class _RowFields:
 
 
 class _HyperTable:
-    """(n_parameters, 3) float64 {scale, clip, sgd_learning_rate} on the device, refreshed through
-    a ring of pinned host buffers only when a value changes."""
+    """(n_parameters, 3) float64 {scale, clip, sgd_learning_rate} on the device -- (n_parameters, 5)
+    with {momentum, nesterov} appended for the momentum rule -- refreshed through a ring of pinned
+    host buffers only when a value changes."""
 
-    def __init__(self, n, device, slots=8):
-        self.dev = torch.zeros((n, 3), dtype=torch.float64, device=device)
-        self._host = [torch.zeros((n, 3), dtype=torch.float64).pin_memory() for _ in range(slots)]
+    def __init__(self, n, device, slots=8, width=3):
+        self.width = width
+        self.dev = torch.zeros((n, width), dtype=torch.float64, device=device)
+        self._host = [torch.zeros((n, width), dtype=torch.float64).pin_memory()
+                      for _ in range(slots)]
         self._events = [None] * slots
         self._at = 0
         self._current = None
@@ -234,8 +238,6 @@ class FusedStep:
         if isinstance(optimizer.error_function, RowwiseError) and not FusedStep.rowwise_ready(eng):
             return False
         if eng.dimension != 3 or not bool(eng.optical_system):
-            return False
-        if optimizer.apply_momentum and optimizer.momentum > 0.0:
             return False
         try:
             eng._reaction()
@@ -605,6 +607,8 @@ class FusedStep:
         opt = self.opt
         L = _lib.lib()
         k = len(grads)
+        if opt.apply_momentum:
+            return self._enqueue_apply_momentum(grads, accumulators)
         if 1 < k <= 8 and all(a is None for a in accumulators) and \
                 len({ops._stream(p).value for p in opt.parameters}) == 1:
             # plain SGD on every parameter tensor: one launch for all of them (the device table
@@ -647,6 +651,54 @@ class FusedStep:
                     check(L.tfrt_sgd_process_dev(ops._p(acc.contiguous()), None, ops._p(p),
                                                  acc.numel(), _lib.F64, apply_row, stream),
                           "tfrt_sgd_process_dev")
+
+    def _enqueue_apply_momentum(self, grads, accumulators):
+        """_enqueue_apply with the momentum rule (tfrt_sgd_momentum_multi): rows of five scalars
+        {scale, clip, sgd_learning_rate, momentum, nesterov}, the optimizer's velocity buffers."""
+        opt = self.opt
+        L = _lib.lib()
+        k = len(grads)
+        vel = opt._velocity
+        hyper = self._hyper.dev.data_ptr()
+
+        def arr(ts, ctype=ctypes.c_void_p):
+            return (ctype * len(ts))(*ts)
+        pending, self._goal_pending = getattr(self, "_goal_pending", None), None
+        stream = ops._stream(opt.parameters[0])
+        with torch.no_grad():
+            if k <= 8 and all(a is None for a in accumulators) and \
+                    len({ops._stream(p).value for p in opt.parameters}) == 1:
+                # every parameter tensor in one launch, which also finishes the error sum
+                args = (k, arr([g.data_ptr() for g in grads]), None,
+                        arr([p.data_ptr() for p in opt.parameters]),
+                        arr([v.data_ptr() for v in vel]),
+                        arr([g.numel() for g in grads], ctypes.c_int64), ctypes.c_void_p(hyper))
+                if pending is not None and pending[1].value == stream.value:
+                    check(L.tfrt_sgd_momentum_multi_finish(*args, ctypes.byref(pending[0]), stream),
+                          "tfrt_sgd_momentum_multi_finish")
+                    return
+                if pending is not None:
+                    check(L.tfrt_goal_finish(ctypes.byref(pending[0]), pending[1]),
+                          "tfrt_goal_finish")
+                check(L.tfrt_sgd_momentum_multi(*args, stream), "tfrt_sgd_momentum_multi")
+                return
+            if pending is not None:
+                check(L.tfrt_goal_finish(ctypes.byref(pending[0]), pending[1]), "tfrt_goal_finish")
+            for i, (g, p) in enumerate(zip(grads, opt.parameters)):
+                stream = ops._stream(p)
+                row = ctypes.c_void_p(hyper + 40 * i)
+                if accumulators[i] is not None:
+                    # (the row's first three scalars: tfrt_sgd_process_dev reads no further)
+                    processed = torch.empty_like(g)
+                    check(L.tfrt_sgd_process_dev(ops._p(g), ops._p(processed), None, g.numel(),
+                                                 _lib.F64, row, stream), "tfrt_sgd_process_dev")
+                    g = opt._matrix_product(opt._acc_cache, i, accumulators[i],
+                                            processed).contiguous()
+                    row = ctypes.c_void_p(self._hyper_apply.dev.data_ptr() + 40 * i)
+                check(L.tfrt_sgd_momentum_multi(1, arr([g.data_ptr()]), None, arr([p.data_ptr()]),
+                                                arr([vel[i].data_ptr()]),
+                                                arr([g.numel()], ctypes.c_int64), row, stream),
+                      "tfrt_sgd_momentum_multi")
 
     def _fix_grads(self, grads):
         opt = self.opt
@@ -711,12 +763,15 @@ class FusedStep:
     def _hyper_rows(self, lr_scale):
         opt = self.opt
         rows, apply_rows = [], []
+        # (momentum rule: the phase's momentum rides in the table, so a phase change replays)
+        extra = ((float(opt.momentum), 1.0 if opt.nesterov else 0.0) if opt.apply_momentum
+                 else ())
         for i in range(len(opt.parameters)):
             scale = float(lr_scale * opt.individual_lr[i] * opt.learning_rate)
             clip = float(opt.grad_clip if opt.clip_mode == "common" else
                          opt.individual_lr[i] * opt.clip_scale * opt.learning_rate * lr_scale)
-            rows.append((scale, clip, float(opt.sgd_learning_rate)))
-            apply_rows.append((1.0, float("inf"), float(opt.sgd_learning_rate)))
+            rows.append((scale, clip, float(opt.sgd_learning_rate)) + extra)
+            apply_rows.append((1.0, float("inf"), float(opt.sgd_learning_rate)) + extra)
         return tuple(rows), tuple(apply_rows)
 
     def _signature(self, accumulators):
@@ -734,16 +789,23 @@ class FusedStep:
                 getattr(opt.error_function, "fields", None),
                 tdist.world_size(), eng.optical_system.scene_signature(), bool(eng.deterministic),
                 id((getattr(eng, "_order_cache", None) or (None, None, None))[2]),
-                getattr(eng, "_visit_all_key", None) is not None, eng.in_place)
+                getattr(eng, "_visit_all_key", None) is not None, eng.in_place,
+                bool(opt.apply_momentum),
+                tuple(v.data_ptr() for v in opt._velocity) if opt.apply_momentum else ())
 
     def step(self, accumulators, lr_scale):
         """One optimiser step.  Returns the error tensor {sum, n_terms, mean} (device)."""
         opt = self.opt
         dev = opt.parameters[0].device
         world = 2 if tdist.is_distributed() else 1      # > 1: the collective splits the sequence
-        if getattr(self, "_hyper", None) is None:
-            self._hyper = _HyperTable(len(opt.parameters), dev)
-            self._hyper_apply = _HyperTable(len(opt.parameters), dev)
+        width = 5 if opt.apply_momentum else 3
+        if getattr(self, "_hyper", None) is None or self._hyper.width != width:
+            # (a captured graph reads the table it was captured with: a new one invalidates it)
+            self._graphs = None
+            self._hyper = _HyperTable(len(opt.parameters), dev, width=width)
+            self._hyper_apply = _HyperTable(len(opt.parameters), dev, width=width)
+        if opt.apply_momentum:
+            opt._velocities()        # allocated before the first capture, updated in place after
         rows, apply_rows = self._hyper_rows(lr_scale)
         self._hyper.set(rows)
         self._hyper_apply.set(apply_rows)

@@ -486,6 +486,37 @@ def sgd_process(grad, scale, clip, param=None, sgd_learning_rate=0.0):
     return out
 
 
+def sgd_momentum(grads, params, velocities, rows, processed=None):
+    """optimizer.py:223-247 and the Keras SGD momentum apply for float64 tensors, up to eight per
+    launch (tfrt_sgd_momentum_multi): ``rows[k] = (scale, clip, sgd_learning_rate, momentum,
+    nesterov)``.  Updates ``params`` and ``velocities`` in place (``velocities`` untouched while
+    momentum is 0); writes the processed gradients into ``processed`` if given."""
+    k = len(grads)
+    if not (k == len(params) == len(velocities) == len(rows)) or \
+            (processed is not None and len(processed) != k):
+        raise TfrtError("sgd_momentum: one gradient, parameter, velocity and row per tensor")
+    if k == 0:
+        return
+    _need_gpu(*grads, *params, *velocities)
+    for i, (g, p, v) in enumerate(zip(grads, params, velocities)):
+        outs = (g, p, v) if processed is None else (g, p, v, processed[i])
+        if any(t.dtype != torch.float64 or not t.is_contiguous() or t.shape != g.shape
+               for t in outs):
+            raise TfrtError("sgd_momentum: contiguous float64 tensors of one shape per parameter")
+    hyper = torch.tensor(rows, dtype=torch.float64).to(grads[0].device)
+    L = _lib.lib()
+    stream = _stream(params[0])
+    for lo in range(0, k, 8):
+        hi = min(lo + 8, k)
+
+        def ptrs(ts):
+            return (ctypes.c_void_p * (hi - lo))(*[t.data_ptr() for t in ts[lo:hi]])
+        check(L.tfrt_sgd_momentum_multi(
+            hi - lo, ptrs(grads), None if processed is None else ptrs(processed), ptrs(params),
+            ptrs(velocities), (ctypes.c_int64 * (hi - lo))(*[g.numel() for g in grads[lo:hi]]),
+            ctypes.c_void_p(hyper.data_ptr() + 40 * lo), stream), "tfrt_sgd_momentum_multi")
+
+
 class CsrMatrix:
     """A square accumulator / smoother matrix held in CSR form on the device
     (optimizer.py:250-255, 277-282 multiply dense (P,P) matrices whose rows hold a few

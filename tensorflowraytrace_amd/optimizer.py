@@ -11,7 +11,15 @@ the Keras defaults (learning rate 0.01, momentum 0.0) and later only *assigns* `
 (optimizer.py:103,128-132); in Keras OptimizerV2 the momentum branch is chosen at
 construction, so the step is plain ``p -= 0.01 * processed_grad``.  That is the default here
 (``sgd_learning_rate=0.01``, ``apply_momentum=False``); ``apply_momentum=True`` enables the
-Nesterov rule the constructor presumably intended.
+Nesterov rule the constructor presumably intended, per element
+
+    v = m*v - lr*g;   p += m*v - lr*g   (``nesterov=True``, the default)  |  p += v
+
+with ``m`` the step's ``momentum`` and one persistent velocity buffer per parameter, updated in
+place; while ``m == 0`` the step is plain ``p -= lr*g`` and the velocity keeps its value.  The
+fused step (fused_step.FusedStep) and, on the GPU, the generic path run it in the parameter-update
+kernel (tfrt_sgd_momentum_multi); both share the velocity buffers, so an optimizer can switch
+between them mid-run.
 """
 import time
 import weakref
@@ -116,7 +124,7 @@ class SGD_Optimizer:
     def __init__(self, engine, parameters, error_function, trace_depth, momentum=0.0,
                  learning_rate=1.0, individual_lr=None, grad_clip="default", clip_mode="common",
                  clip_scale=10.0, sgd_learning_rate=0.01, apply_momentum=False, speculative=False,
-                 fused="auto", graph="auto"):
+                 fused="auto", graph="auto", nesterov=True):
         self.engine = engine
         if type(parameters) is list or type(parameters) is tuple:
             self.parameters = parameters
@@ -126,6 +134,7 @@ class SGD_Optimizer:
         self.trace_depth = trace_depth
         self.sgd_learning_rate = sgd_learning_rate
         self.apply_momentum = apply_momentum
+        self.nesterov = bool(nesterov)      # (momentum rule; the reference builds nesterov=True)
         # ``speculative=True`` (opt-in) overlaps host and device on the generic path: the per-class
         # ray counts of the trace are guessed from the previous step and verified after the
         # gradient has been enqueued.  On a wrong guess the error function has ALREADY run once on
@@ -187,6 +196,25 @@ class SGD_Optimizer:
                 "SGD_Optimizer: individual_lr must have as many elements as there are "
                 "parameters.") from e
         self._individual_lr = val
+
+    def _velocities(self):
+        """The velocity buffers of the momentum rule: zero-initialised once per parameter and
+        updated in place from then on (a captured launch graph keeps their addresses)."""
+        for i, p in enumerate(self.parameters):
+            v = self._velocity[i]
+            if v is None or v.shape != p.shape or v.dtype != p.dtype or v.device != p.device:
+                self._velocity[i] = torch.zeros(p.shape, dtype=p.dtype, device=p.device)
+        return self._velocity
+
+    def _momentum_kernel(self, p, g):
+        """Whether the momentum update of ``p`` by ``g`` runs in tfrt_sgd_momentum_multi (float64
+        on the device) rather than as eager torch ops."""
+        return (p.is_cuda and p.dtype == torch.float64 and g.dtype == torch.float64
+                and p.is_contiguous() and p.shape == g.shape)
+
+    def _momentum_row(self, scale, clip):
+        return (float(scale), float(clip), float(self.sgd_learning_rate), float(self._momentum),
+                1.0 if self.nesterov else 0.0)
 
     def convert_to_plist(self, data):
         p_count = len(self.parameters)
@@ -283,6 +311,7 @@ class SGD_Optimizer:
         self.last_error_terms = n_terms
         processed, applied = [], []
         plain_sgd = not (self.apply_momentum and self._momentum > 0.0)
+        batch = []      # momentum updates processed and applied in one launch after the loop
         for i, grad in enumerate(grads):
             scale = lr_scale * self.individual_lr[i] * self.learning_rate
             if self.clip_mode == "common":
@@ -292,6 +321,13 @@ class SGD_Optimizer:
             p = self.parameters[i]
             fuse = (apply and plain_sgd and accumulators[i] is None and p.is_contiguous()
                     and p.dtype == grad.dtype and p.shape == grad.shape)
+            if (apply and not plain_sgd and accumulators[i] is None
+                    and self._momentum_kernel(p, grad)):
+                grad = grad.contiguous()
+                batch.append((i, grad, torch.empty_like(grad), self._momentum_row(scale, clp)))
+                processed.append(batch[-1][2])
+                applied.append(True)
+                continue
             with torch.no_grad():
                 grad = ops.sgd_process(grad, scale, clp, param=p if fuse else None,
                                        sgd_learning_rate=self.sgd_learning_rate)
@@ -299,6 +335,12 @@ class SGD_Optimizer:
             if accumulators[i] is not None:
                 grad = self._matrix_product(self._acc_cache, i, accumulators[i], grad)
             processed.append(grad)
+        if batch:
+            vel = self._velocities()
+            with torch.no_grad():
+                ops.sgd_momentum([b[1] for b in batch], [self.parameters[b[0]] for b in batch],
+                                 [vel[b[0]] for b in batch], [b[3] for b in batch],
+                                 processed=[b[2] for b in batch])
         # (tf.reduce_mean, optimizer.py:257: the mean of no error terms is NaN)
         if isinstance(n_terms, torch.Tensor):
             mean = torch.where(n_terms > 0, error_sum / torch.clamp(n_terms, min=1.0),
@@ -324,20 +366,28 @@ class SGD_Optimizer:
                 parameters.copy_(entry[1].matvec(parameters.detach()))
 
     def apply_gradients(self, grads, skip=None):
+        momentum = self.apply_momentum and self._momentum > 0.0
+        vel = self._velocities() if momentum else None
+        batch = []      # (device float64: one tfrt_sgd_momentum_multi launch, rows {1, inf, ...})
         with torch.no_grad():
             for i, (g, p) in enumerate(zip(grads, self.parameters)):
                 if skip is not None and skip[i]:
                     continue  # already applied by the fused processing kernel
                 lr = self.sgd_learning_rate
-                if self.apply_momentum and self._momentum > 0.0:
-                    v = self._velocity[i]
-                    if v is None:
-                        v = torch.zeros_like(p)
-                    v = self._momentum * v - lr * g
-                    self._velocity[i] = v
-                    p.add_(self._momentum * v - lr * g)  # Nesterov form used by Keras
+                if momentum:
+                    if self._momentum_kernel(p, g):
+                        batch.append((i, g.contiguous()))
+                        continue
+                    m, v = self._momentum, vel[i]
+                    v.copy_(m * v - lr * g)
+                    # Nesterov form used by Keras, or the classical one
+                    p.add_(m * v - lr * g if self.nesterov else v)
                 else:
                     p.add_(g, alpha=-lr)
+            if batch:
+                row = self._momentum_row(1.0, float("inf"))
+                ops.sgd_momentum([g for _, g in batch], [self.parameters[i] for i, _ in batch],
+                                 [vel[i] for i, _ in batch], [row] * len(batch))
 
     def single_step(self, accumulators, *args, lr_scale=1.0, momentum=0.0, verbose=False,
                     **kwargs):

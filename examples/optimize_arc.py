@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""
+Counterpart of the reference's dev/optimize_single_arc.py: one acrylic arc whose centre and
+radius are the SAME parameter (``arc["x_center"] = parameter; arc["radius"] = parameter``) is
+shaped by gradient descent so that a beam focuses on a target wall at x = 10
+(error = finished["y_end"] ** 2).
+
+The reference's error is a GoalError (goal: y_end = 0), so on the GPU SGD_Optimizer runs the fused
+2-D step -- update, tfrt_trace2d_forward, tfrt_trace2d_backward_goal, parameter update -- captured
+in one HIP graph after a few eager steps.  The reference's optimiser is Keras SGD with learning
+rate 1, Nesterov momentum 0.8 and the gradient clipped to 0.1; ``--momentum`` runs that rule
+(without it: plain SGD).  ``--generic`` forces the generic path (user error function, autograd)
+for comparison.  No GUI.
+
+    python examples/optimize_arc.py [--rays 10] [--steps 30] [--momentum] [--generic]
+"""
+import argparse
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import tfrt.boundaries as boundaries          # noqa: E402
+import tfrt.distributions as distributions    # noqa: E402
+import tfrt.drawing as drawing                # noqa: E402
+import tfrt.engine as engine                  # noqa: E402
+import tfrt.materials as materials            # noqa: E402
+import tfrt.operation as operation            # noqa: E402
+import tfrt.optimizer as optimizer            # noqa: E402
+import tfrt.sources as sources                # noqa: E402
+
+PI = math.pi
+
+
+def build(ray_count=10, ray_dtype=torch.float64, device="cuda:0"):
+    parameter = torch.tensor([5.0], dtype=torch.float64, device=device, requires_grad=True)
+    arc = boundaries.ManualArcBoundary()
+    arc["x_center"] = parameter
+    arc["y_center"] = np.array([0.0])
+    arc["angle_start"] = np.array([3 * PI / 4])
+    arc["angle_end"] = np.array([5 * PI / 4])
+    arc["radius"] = parameter
+    engine.annotation_helper(arc, "mat_in", 1, "x_center", dtype=torch.int64)
+    engine.annotation_helper(arc, "mat_out", 0, "x_center", dtype=torch.int64)
+
+    target = boundaries.ManualSegmentBoundary()
+    target.feed_segments(np.array([[10, -5, 10, 5]], dtype=np.float64))
+    target.frozen = True
+
+    beam_points = distributions.StaticUniformBeam(-1.5, 1.5, ray_count)
+    angles = distributions.StaticUniformAngularDistribution(0, 0, 1)
+    source = sources.AngularSource(2, (-1.0, 0.0), 0.0, angles, beam_points, drawing.RAINBOW_6)
+    source.frozen = True
+
+    system = engine.OpticalSystem2D()
+    system.optical_arcs = [arc]
+    system.sources = [source]
+    system.target_segments = [target]
+    system.materials = [{"n": materials.vacuum}, {"n": materials.acrylic}]
+
+    trace_engine = engine.OpticalEngine(2, [operation.StandardReaction()],
+                                        simple_ray_inheritance={"wavelength"},
+                                        ray_dtype=ray_dtype)
+    trace_engine.optical_system = system
+    system.update()
+    trace_engine.validate_system()
+    return dict(parameter=parameter, arc=arc, system=system, engine=trace_engine)
+
+
+def make_optimizer(scene, momentum=False, generic=False):
+    n = scene["system"].sources["x_start"].shape[0]
+    goal = torch.zeros(n, dtype=torch.float64, device=scene["parameter"].device)
+    erf = optimizer.GoalError(("y_end",), goal)
+    # Keras SGD(learning_rate=1.0, momentum=0.8, nesterov=True) of the reference, gradient clipped
+    # to 0.1 before it is applied
+    return optimizer.SGD_Optimizer(scene["engine"], [scene["parameter"]], erf, 2,
+                                   learning_rate=1.0, grad_clip=0.1, sgd_learning_rate=1.0,
+                                   apply_momentum=momentum, fused=not generic)
+
+
+def run(ray_count=10, steps=30, momentum=False, generic=False, verbose=True):
+    scene = build(ray_count)
+    opt = make_optimizer(scene, momentum, generic)
+    errors = []
+    for i in range(steps):
+        # the reference's schedule: 30 steps at learning rate 1, then 0.1 (its momentum stays 0.8:
+        # the script's set_momentum call is commented out)
+        err = opt.single_step(None, lr_scale=0.1 if i >= 30 else 1.0,
+                              momentum=0.8 if momentum else 0.0)
+        errors.append(float(err))
+        if verbose:
+            print(f"step {i + 1}: error {errors[-1]:.6e}  parameter {float(scene['parameter']):.6f}")
+    return errors, dict(scene, optimizer=opt)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--rays", type=int, default=10,
+                    help="beam points (the reference's 10); each is traced at six wavelengths")
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--momentum", action="store_true",
+                    help="the reference's Nesterov momentum 0.8")
+    ap.add_argument("--generic", action="store_true",
+                    help="force the generic optimiser step (for comparison)")
+    a = ap.parse_args()
+    errors, s = run(a.rays, a.steps, a.momentum, a.generic)
+    fs = s["optimizer"]._fused_step
+    path = ("generic" if fs is None else
+            f"fused, {fs.graph_replays} of {fs.steps} steps replayed from a HIP graph")
+    print(f"error {errors[0]:.6e} -> {errors[-1]:.6e} ({path})")
+
+
+if __name__ == "__main__":
+    main()

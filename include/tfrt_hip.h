@@ -683,6 +683,35 @@ int tfrt_trace2d_backward(const void* src_rays, int64_t src_stride, int64_t n_ra
                           double* grad_arc, double* grad_src_rays, const int32_t* counts,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* The built-in goal error (tfrt_goal_error3d's form) folded into the 2-D reverse sweep: ONE
+ * launch for the error, its seed 2 (output - goal) and the whole sweep of every pass, in place of
+ * tfrt_goal_error3d + max_passes launches of tfrt_trace2d_backward's kernel.  One lane per source
+ * ray walks the ray's chain through the tape; a chain that finishes forms its residuals from the
+ * row stored in `finished` (state dtype) and leaves their squares in per-wavefront partial sums
+ * (a fixed order: the error is bit-identical from run to run).  Any max_passes.
+ *   src_rays .. state_dtype, counts, workspace  as for tfrt_trace2d_forward (same call's tape)
+ *   finished        the finished-ray block that forward call wrote (rays + capacity; ids unused)
+ *   fields[c]       row of the 4-row block (0..3 = x_start, y_start, x_end, y_end), n_fields 1..4
+ *   goal            as for tfrt_goal_error3d, rows indexed by the source ray
+ *   goal_workspace  tfrt_trace2d_backward_goal_workspace_bytes(n_rays) bytes (the partial sums)
+ *   pending         filled in like tfrt_goal_error3d_deferred's: finish with
+ *                   tfrt_sgd_process_multi_finish or tfrt_goal_finish ({sum, terms, mean} with
+ *                   terms = finished rays x n_fields; tests_total gets the trace's test count)
+ *   grad_seg (Ms,4), grad_arc (Ma,5) f64, ACCUMULATED into (caller zeroes), either may be NULL;
+ *   lanes that share a primitive are summed inside the wavefront before the global atomic.
+ * No class gradients besides the goal's and no source-ray gradient. */
+size_t tfrt_trace2d_backward_goal_workspace_bytes(int64_t n_rays);
+int tfrt_trace2d_backward_goal(const void* src_rays, int64_t src_stride, int64_t n_rays,
+                               const tfrt_scene2d* scene, double new_ray_length,
+                               int32_t max_passes, int32_t state_dtype,
+                               const tfrt_ray_out* finished, const int32_t* fields,
+                               int32_t n_fields, const double* goal, int64_t goal_stride,
+                               int64_t goal_ray_stride, double* error_out, int64_t* tests_total,
+                               void* goal_workspace, size_t goal_workspace_bytes,
+                               tfrt_goal_pending* pending, double* grad_seg, double* grad_arc,
+                               const int32_t* counts, void* workspace, size_t workspace_bytes,
+                               void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Ray order.  The reference's ray sets are ORDERED: every class lists, pass after pass, its rays
  * in the order of the source set (OpticalEngine.ray_trace / single_pass own both: tfrt/engine.py:

@@ -362,6 +362,7 @@ class BoundaryBase(RecursivelyUpdatable):
 
 class _Manual2D(BoundaryBase):
     _shape_field = None
+    _geometry_fields = ()
 
     @property
     def dimension(self):
@@ -369,6 +370,26 @@ class _Manual2D(BoundaryBase):
 
     def __setitem__(self, key, item):
         self._fields[key] = _as_field(item, config.get_device())
+
+    def __getitem__(self, key):
+        # A parameter written straight into a field (dev/optimize_single_arc.py:
+        # arc["x_center"] = parameter; arc["radius"] = parameter) is read through an alias while
+        # a collect_taps() block is open (a fused optimiser step's update()), like the parameters
+        # of the generated boundaries: the merged geometry then reaches it through tap().
+        # Everywhere else, and for the fields a parametric boundary computes, the field itself.
+        value = self._fields[key]
+        if _tap_log is not None and isinstance(value, torch.Tensor) and value.is_leaf:
+            return tap(value)
+        return value
+
+    def field_signature(self):
+        """Identity and shape of every geometry field the caller gave (none for a boundary that
+        computes its fields in update()): a field the caller replaces is a changed scene to a
+        captured launch sequence, one whose values change in place is not."""
+        if type(self)._update is not _Manual2D._update:
+            return ()
+        return tuple((f, id(self._fields[f]), tuple(self._fields[f].shape))
+                     for f in self._geometry_fields if f in self._fields)
 
     def update_materials(self):
         if self._shape_field in self._fields:
@@ -384,6 +405,7 @@ class _Manual2D(BoundaryBase):
 
 class ArcBoundaryBase(_Manual2D):
     _shape_field = "x_center"
+    _geometry_fields = ("x_center", "y_center", "angle_start", "angle_end", "radius")
 
 
 class ManualArcBoundary(ArcBoundaryBase):
@@ -392,6 +414,7 @@ class ManualArcBoundary(ArcBoundaryBase):
 
 class SegmentBoundaryBase(_Manual2D):
     _shape_field = "x_start"
+    _geometry_fields = ("x_start", "y_start", "x_end", "y_end")
 
 
 class ManualSegmentBoundary(SegmentBoundaryBase):

@@ -11,6 +11,7 @@
 // pass emits, per class, segment-hit rays first and arc-hit rays second (engine.py:1955-1981),
 // hence 7 compaction bins: {active, finished, stopped} x {segment, arc} + dead.
 #include "tfrt_common.h"
+#include "goal_finish.h"
 #include "trace_math2d.h"
 
 namespace tfrt {
@@ -941,6 +942,211 @@ static int trace2d_backward_t(const void* src_rays, int64_t src_stride, int64_t 
   return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
 }
 
+// ---------------------------------------------------------------------------------------
+// The goal error folded into the reverse sweep (tfrt_trace2d_backward_goal).
+//
+// A 2-D trace keeps its rays in natural order, so lane i IS source ray i (and goal row i) and
+// walks its chain forward through the tape: an ACTIVE ray's rec_slot is its child's index in
+// the next pass's input, every other class's rec_slot is the global slot in that class's block
+// (k_react2d).  A chain that finishes reads its output row at that slot, forms r = out - goal,
+// seeds 2 r and runs the chain's adjoint from the last link back to pass 0 -- the very calls of
+// adjoint2d k_backward2d makes for this ray, link by link, including the parent links of chains
+// that do not finish (their zero child gradient still carries the NaN of a totally reflected
+// link, geometry.py:640-646, as it does there).  The chain's indices live in an LDS ring of
+// CHAIN2 links per lane; a chain longer than that re-walks the tape from pass 0 for every
+// further CHAIN2 links (one code path for any max_passes).
+//
+// The links of a wave are processed in lockstep (link k of every lane together), so that the
+// primitive gradients can be combined inside the wave before the global atomics: in a scene of
+// few primitives (dev/optimize_single_arc.py: one arc) every lane adds into the same row.
+constexpr int CHAIN2 = 16;
+
+struct ChainGoal2 {
+  GoalFields gf;
+  const double* goal;
+  int64_t goal_stride, goal_ray_stride;
+};
+
+// Adds the gradient rows of the lanes with `has` set into g_seg / g_arc: one atomic per entry
+// and distinct primitive of the wave (a wave-wide sum over the lanes that share the primitive;
+// a primitive only one lane touched is added by that lane directly).  Called by all 64 lanes.
+__device__ __forceinline__ void add_prim_grads(bool has, int prim, const double gp[5], int Ms,
+                                               double* __restrict__ g_seg,
+                                               double* __restrict__ g_arc) {
+  unsigned long long todo = __ballot(has);
+  while (todo) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const int key = __shfl(prim, leader, 64);
+    const bool mine = has && prim == key;
+    const unsigned long long grp = __ballot(mine);
+    const bool is_arc = key >= Ms;
+    double* row = is_arc ? (g_arc ? g_arc + (int64_t)(key - Ms) * 5 : nullptr)
+                         : (g_seg ? g_seg + (int64_t)key * 4 : nullptr);
+    if (row != nullptr) {
+      // (adjoint2d leaves an arc's angle columns 2, 3 at zero: they only feed comparisons)
+      constexpr int seg_q[4] = {0, 1, 2, 3};
+      constexpr int arc_q[3] = {0, 1, 4};
+      const int nq = is_arc ? 3 : 4;
+      if (__popcll(grp) == 1) {
+        if (mine)
+          for (int k = 0; k < nq; ++k) {
+            const int q = is_arc ? arc_q[k] : seg_q[k];
+            if (gp[q] != 0.0) unsafeAtomicAdd(row + q, gp[q]);
+          }
+      } else {
+        for (int k = 0; k < nq; ++k) {
+          const int q = is_arc ? arc_q[k] : seg_q[k];
+          double v = mine ? gp[q] : 0.0;
+#pragma unroll
+          for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+          if ((int)lane_id() == leader && v != 0.0) unsafeAtomicAdd(row + q, v);
+        }
+      }
+    }
+    has = has && !mine;
+    todo &= ~grp;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_backward2d_goal(
+    const T* __restrict__ src, int64_t src_stride, int N, const T* __restrict__ rays_ws,
+    int64_t n, const int32_t* __restrict__ rec_prim, const double* __restrict__ rec_u,
+    const uint8_t* __restrict__ rec_bin, const int32_t* __restrict__ rec_slot, int P,
+    tfrt_scene2d sc, double L, tfrt_ray_out fin, ChainGoal2 cg, double* __restrict__ partial,
+    double* __restrict__ g_seg, double* __restrict__ g_arc) {
+  __shared__ int32_t chain[CHAIN2 * BLOCK];
+  const int tid = threadIdx.x;
+  const int i = blockIdx.x * BLOCK + tid;
+  const bool lane_ok = i < N;
+  const int Ms = (int)sc.n_segments;
+  auto link_at = [&](int p) -> int32_t& { return chain[(p % CHAIN2) * BLOCK + tid]; };
+
+  // walk forward: every link's index into its pass's input (the last CHAIN2 kept), the end class
+  int top = -1, end_cls = -1, end_slot = 0;
+  if (lane_ok) {
+    int idx = i;
+    for (int p = 0; p < P; ++p) {
+      link_at(p) = idx;
+      top = p;
+      const int bin = rec_bin[(size_t)p * n + idx];
+      const int slot = rec_slot[(size_t)p * n + idx];
+      const int cls = (bin == BIN_DEAD) ? CLS_DEAD : (bin >> 1);
+      if (cls != CLS_ACTIVE) {
+        end_cls = cls;
+        end_slot = slot;
+        break;
+      }
+      idx = slot;
+    }
+  }
+  // the residuals of a finished chain, and its seed (rows 0, 1 -> start, rows 2, 3 -> hit)
+  double acc = 0.0;
+  double sd[4] = {0.0, 0.0, 0.0, 0.0};
+  if (end_cls == CLS_FINISHED && end_slot < fin.capacity) {
+    // the reference's squared_difference and reduce_sum are separate ops: no contraction (the
+    // adjoint's own arithmetic is compiled as in k_backward2d)
+#pragma clang fp contract(off)
+    const T* out = static_cast<const T*>(fin.rays);
+    for (int c = 0; c < cg.gf.n; ++c) {
+      const int row = cg.gf.row[c];
+      const double r = ldd(out, (int64_t)row * fin.capacity + end_slot) -
+                       cg.goal[(int64_t)c * cg.goal_stride + (int64_t)i * cg.goal_ray_stride];
+      sd[row] = 2.0 * r;
+      acc += r * r;
+    }
+  }
+  // per-wavefront partial sum, lanes in a fixed butterfly order
+  {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d, 64);
+  }
+  const int64_t wave_g = ((int64_t)blockIdx.x * BLOCK + tid) >> 6;
+  if (lane_id() == 0 && wave_g * 64 < N) partial[wave_g] = acc;
+
+  // reverse: link `top` is the chain's end (seeded when finished, no child), every link below it
+  // is an active parent whose child gradient is (gc_s, gc_e)
+  int p = top;
+  int lo = top - CHAIN2 + 1;          // links [max(lo, 0), top] are in the ring
+  double gc_s[2] = {0.0, 0.0}, gc_e[2] = {0.0, 0.0};
+  while (__any(p >= 0)) {
+    bool has = false;
+    int prim = -1;
+    double gp[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    if (p >= 0) {
+      if (p < lo) {                   // past the ring: re-walk the tape for links [lo, p]
+        lo = max(0, p - CHAIN2 + 1);
+        int idx = i;
+        for (int q = 0; q < lo; ++q) idx = rec_slot[(size_t)q * n + idx];
+        for (int q = lo; q <= p; ++q) {
+          link_at(q) = idx;
+          idx = rec_slot[(size_t)q * n + idx];
+        }
+      }
+      const int idx = link_at(p);
+      const bool has_child = p < top;
+      double g_s[2] = {0, 0}, g_h[2] = {0, 0}, g_ce[2] = {0, 0};
+      if (has_child) {
+        // (k_backward2d: g_h, g_ce start at zero and the child's gradient is added)
+        for (int k = 0; k < 2; ++k) {
+          g_h[k] += gc_s[k];
+          g_ce[k] += gc_e[k];
+        }
+      } else if (end_cls == CLS_FINISHED) {
+        for (int k = 0; k < 2; ++k) {
+          g_s[k] += sd[k];
+          g_h[k] += sd[2 + k];
+        }
+      }
+      bool nz = has_child;
+      for (int k = 0; k < 2; ++k) nz = nz || g_s[k] != 0.0 || g_h[k] != 0.0;
+      double gs[2] = {0, 0}, ge[2] = {0, 0};
+      if (nz) {
+        double s[2], e[2];
+        if (p == 0) load_ray2(src, src_stride, idx, s, e);
+        else load_ray2(rays_ws + (size_t)(p - 1) * 4 * n, n, idx, s, e);
+        prim = rec_prim[(size_t)p * n + idx];
+        const bool is_arc = prim >= Ms;
+        double n_in = 1.0, n_out = 1.0;
+        if (has_child) prim_indices(sc, prim, i, &n_in, &n_out);
+        const double* pp = is_arc ? sc.arc + (int64_t)(prim - Ms) * 5 : sc.seg + (int64_t)prim * 4;
+        adjoint2d(s, e, pp, is_arc, rec_u[(size_t)p * n + idx], has_child, n_in, n_out, L, g_s,
+                  g_h, g_ce, gs, ge, gp, sc.finite_tir_gradient != 0);
+        has = true;
+      }
+      for (int k = 0; k < 2; ++k) {
+        gc_s[k] = gs[k];
+        gc_e[k] = ge[k];
+      }
+      --p;
+    }
+    add_prim_grads(has, prim, gp, Ms, g_seg, g_arc);
+  }
+}
+
+template <typename T>
+static int trace2d_backward_goal_t(const void* src_rays, int64_t src_stride, int64_t N,
+                                   const tfrt_scene2d* sc, double L, int P, int dtype,
+                                   const tfrt_ray_out& fin, const ChainGoal2& cg, double* partial,
+                                   double* g_seg, double* g_arc, void* workspace,
+                                   size_t workspace_bytes, hipStream_t st) {
+  const Layout2 lay = make_layout2(N, P, dtype);
+  if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
+  if (N == 0) return 0;
+  char* ws = static_cast<char*>(workspace);
+  const size_t n = N;
+  hipLaunchKernelGGL((k_backward2d_goal<T>), dim3(cdiv(N, BLOCK)), dim3(BLOCK), 0, st,
+                     static_cast<const T*>(src_rays), src_stride, (int)N,
+                     reinterpret_cast<const T*>(ws + lay.rays), (int64_t)n,
+                     reinterpret_cast<const int32_t*>(ws + lay.rec_prim),
+                     reinterpret_cast<const double*>(ws + lay.rec_u),
+                     reinterpret_cast<const uint8_t*>(ws + lay.rec_bin),
+                     reinterpret_cast<const int32_t*>(ws + lay.rec_slot), P, *sc, L, fin, cg,
+                     partial, g_seg, g_arc);
+  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+}
+
 template <bool ARC>
 static int seam2d(const void* rays, int64_t stride, int64_t n_rays, int32_t dtype,
                   const double* prim, int64_t M, double ei, double es, double er, double* x,
@@ -1062,6 +1268,72 @@ int tfrt_trace2d_backward(const void* src_rays, int64_t src_stride, int64_t n_ra
                                       cap_stopped, grad_dead, cap_dead, grad_seg, grad_arc,
                                       grad_src_rays, counts, workspace, workspace_bytes, st);
   return TFRT_E_UNSUPPORTED;
+}
+
+size_t tfrt_trace2d_backward_goal_workspace_bytes(int64_t n_rays) {
+  if (n_rays < 0) return 0;
+  // one partial error sum per 64 rays
+  return align_up((size_t)cdiv(n_rays > 0 ? n_rays : 1, 64) * sizeof(double));
+}
+
+int tfrt_trace2d_backward_goal(const void* src_rays, int64_t src_stride, int64_t n_rays,
+                               const tfrt_scene2d* scene, double new_ray_length,
+                               int32_t max_passes, int32_t state_dtype,
+                               const tfrt_ray_out* finished, const int32_t* fields,
+                               int32_t n_fields, const double* goal, int64_t goal_stride,
+                               int64_t goal_ray_stride, double* error_out, int64_t* tests_total,
+                               void* goal_workspace, size_t goal_workspace_bytes,
+                               tfrt_goal_pending* pending, double* grad_seg, double* grad_arc,
+                               const int32_t* counts, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+  if (!scene2_ok(scene) || n_rays < 0 || n_rays >= (1ll << 31) - 4096 || max_passes < 0 ||
+      !counts || !workspace || !finished || !fields || n_fields < 1 || n_fields > 4 ||
+      !error_out || !pending || !goal_workspace || goal_stride < 0 || goal_ray_stride < 0 ||
+      goal_workspace_bytes < tfrt_trace2d_backward_goal_workspace_bytes(n_rays))
+    return TFRT_E_BADARG;
+  // (a forward compiled without finished rays left nothing to compare with the goal)
+  if (n_rays > 0 && (!src_rays || src_stride < n_rays || !goal || !finished->rays ||
+                     finished->capacity <= 0))
+    return TFRT_E_BADARG;
+  if (state_dtype != TFRT_F32 && state_dtype != TFRT_F64 && state_dtype != TFRT_F16)
+    return TFRT_E_UNSUPPORTED;
+  ChainGoal2 cg;
+  cg.gf.n = n_fields;
+  for (int c = 0; c < 6; ++c) {
+    cg.gf.row[c] = c < n_fields ? fields[c] : 0;
+    if (cg.gf.row[c] < 0 || cg.gf.row[c] > 3) return TFRT_E_BADARG;
+  }
+  cg.goal = goal;
+  cg.goal_stride = goal_stride;
+  cg.goal_ray_stride = goal_ray_stride;
+  double* partial = static_cast<double*>(goal_workspace);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int rc;
+  if (state_dtype == TFRT_F32)
+    rc = trace2d_backward_goal_t<float>(src_rays, src_stride, n_rays, scene, new_ray_length,
+                                        max_passes, state_dtype, *finished, cg, partial, grad_seg,
+                                        grad_arc, workspace, workspace_bytes, st);
+  else if (state_dtype == TFRT_F64)
+    rc = trace2d_backward_goal_t<double>(src_rays, src_stride, n_rays, scene, new_ray_length,
+                                         max_passes, state_dtype, *finished, cg, partial,
+                                         grad_seg, grad_arc, workspace, workspace_bytes, st);
+  else
+    rc = trace2d_backward_goal_t<_Float16>(src_rays, src_stride, n_rays, scene, new_ray_length,
+                                           max_passes, state_dtype, *finished, cg, partial,
+                                           grad_seg, grad_arc, workspace, workspace_bytes, st);
+  if (rc != 0) return rc;
+  // trailing counters of the trace: {total_active, total_finished, ..., n_tests_lo, n_tests_hi}
+  const int32_t* tail = counts + (size_t)max_passes * TFRT_COUNTS_PER_PASS;
+  tfrt_goal_pending g = {};
+  g.partial = partial;
+  g.n_partial = n_rays > 0 ? cdiv(n_rays, 64) : 0;
+  g.n_finished = tail + 1;
+  g.n_fields = n_fields;
+  g.error_out = error_out;
+  g.tests_lo_hi = tail + 4;
+  g.tests_total = tests_total;
+  *pending = g;
+  return 0;
 }
 
 }  // extern "C"

@@ -147,10 +147,18 @@ def annotation_helper(parent, field, value, valid_shape_field, dtype=torch.float
             shape = parent[valid_shape_field].shape
             parent[field] = value(shape, dtype)
     else:
+        made = []     # (the column last made: kept while nobody replaced it and the shape holds)
+
         def f():
             ref = parent[valid_shape_field]
+            if made and parent[field] is made[0] and made[0].shape == ref.shape \
+                    and made[0].device == ref.device:
+                # (a constant: a new tensor every update would look like a changed scene to a
+                # captured optimiser step, and its host->device copy cannot be captured)
+                return
             parent[field] = torch.as_tensor(value, dtype=dtype, device=ref.device).expand(
                 ref.shape).clone()
+            made[:] = [parent[field]]
     parent.post_update_handles.append(f)
 
 
@@ -530,6 +538,23 @@ class OpticalSystem2D(OpticalSystemBase):
     @property
     def dimension(self):
         return 2
+
+    def scene_signature(self):
+        """What a captured launch sequence of a fused step has baked in about the scene besides
+        the merged geometry: which boundaries (identity and primitive count), the fields the
+        caller gave the manual ones (identity and shape: the capture reads them by address, their
+        values may change in place; a boundary that computes its fields -- material columns
+        included -- does so inside the captured update()), the epsilons and the material list.
+        Cheap (no tensor work): checked before every graph replay."""
+        sig = []
+        for name in self._boundary_sets:
+            for b in getattr(self, "_" + name):
+                shape = getattr(b, "_shape_field", None)
+                count = tuple(b._fields[shape].shape) if shape in getattr(b, "_fields", {}) else ()
+                fs = getattr(b, "field_signature", None)
+                sig.append((name, id(b), count, fs() if fs is not None else ()))
+        return (tuple(sig), self.intersect_epsilion, self.size_epsilion,
+                self.ray_start_epsilion, tuple(id(m) for m in self.materials))
 
     def _merge_kind(self, kind, geo):
         sets = [(getattr(self, f"_amalgamated_{c}_{kind}"), cat) for c, cat in

@@ -25,6 +25,10 @@ states that form declaratively; an optimiser given a ``GoalError`` runs ``FusedS
     tfrt_sgd_process_dev / tfrt_csr_matvec   non-finite -> 0, scale, clip, accumulate, SGD apply
                                         (tfrt_sgd_momentum_multi with apply_momentum=True)
 
+A 2-D engine (one process, no ray shards) runs ``_enqueue_gradient2d`` instead:
+``tfrt_trace2d_forward``, then ``tfrt_trace2d_backward_goal`` -- error, seed and the reverse sweep of
+every pass in ONE launch -- and autograd from the merged segments and arcs to the parameters.
+
 Every launch has step-independent arguments (learning-rate dependent scalars live in a small
 device table), so after a few eager steps the sequence is captured once in a HIP graph
 (``torch.cuda.CUDAGraph``) and replayed: one graph launch per step.  With ray shards over several
@@ -44,6 +48,7 @@ from . import distributed as tdist
 from ._lib import RayOut, check
 
 _GEO3 = ("x_start", "y_start", "z_start", "x_end", "y_end", "z_end")
+_GEO2 = ("x_start", "y_start", "x_end", "y_end")
 _CLASS_FLAGS = (("finished", _lib.COMPILE_FINISHED), ("active", _lib.COMPILE_ACTIVE),
                 ("stopped", _lib.COMPILE_STOPPED), ("dead", _lib.COMPILE_DEAD))
 
@@ -64,6 +69,9 @@ class GoalError:
     Example (dev/hexalens.py:154-157, magnification m)::
 
         erf = GoalError(("y_end", "z_end"), lambda src: -m * src["object_coords"][:, 1:])
+
+    On a 2-D engine the fields come from ``x_start, y_start, x_end, y_end`` (``rows_for(2)``);
+    dev/optimize_single_arc.py's error is ``GoalError(("y_end",), zeros)``.
     """
 
     def __init__(self, fields=("y_end", "z_end"), goal=None, rowwise=False):
@@ -84,6 +92,17 @@ class GoalError:
         self.rows = [_GEO3.index(f) for f in self.fields]
         self.goal = goal
         self._cache = None
+
+    def rows_for(self, dimension):
+        """Rows of the ray block of a ``dimension``-D trace that the fields are read from (a 3-D
+        block is x_start .. z_end, a 2-D one x_start, y_start, x_end, y_end)."""
+        if dimension == 3:
+            return self.rows
+        bad = [f for f in self.fields if f not in _GEO2]
+        if bad:
+            raise ValueError(f"GoalError: field(s) {bad} do not exist on a {dimension}-D engine "
+                             f"(fields of its rays: {_GEO2})")
+        return [_GEO2.index(f) for f in self.fields]
 
     def table(self, src, by_ray=False):
         """(len(fields), N) contiguous float64 goal table of the source set ``src``; with
@@ -114,6 +133,7 @@ class GoalError:
 
     def __call__(self, engine):
         """The same error through the generic path (arbitrary-error-function contract)."""
+        self.rows_for(engine.dimension)
         fin = engine.finished_rays
         if not bool(fin):
             return torch.zeros((0, len(self.fields)), dtype=torch.float64)
@@ -198,8 +218,9 @@ class _HyperTable:
 
 
 class FusedStep:
-    """Runs ``SGD_Optimizer.single_step`` for a ``GoalError`` as a fixed launch sequence; see the
-    module docstring.  One instance per optimizer."""
+    """Runs ``SGD_Optimizer.single_step`` for a ``GoalError`` as a fixed launch sequence, on 3-D
+    engines (also for a ``RowwiseError``) and on 2-D ones (one process); see the module docstring.
+    One instance per optimizer."""
 
     # coherent rays: error, gradient seed and reverse sweep as ONE launch (tfrt_trace3d_backward_goal);
     # False: tfrt_goal_error3d + tfrt_trace3d_backward (what a trace in natural order always runs)
@@ -237,7 +258,9 @@ class FusedStep:
             return False
         if isinstance(optimizer.error_function, RowwiseError) and not FusedStep.rowwise_ready(eng):
             return False
-        if eng.dimension != 3 or not bool(eng.optical_system):
+        if not bool(eng.optical_system):
+            return False
+        if eng.dimension == 2 and not FusedStep.eligible2d(optimizer):
             return False
         try:
             eng._reaction()
@@ -245,6 +268,22 @@ class FusedStep:
             return False
         return all(isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.float64
                    and p.is_contiguous() for p in optimizer.parameters)
+
+    @staticmethod
+    def eligible2d(optimizer):
+        """A 2-D engine takes the fused step with a GoalError over fields its rays have, in one
+        process without ray shards, and with the projection in the kernels (no operation with a
+        main() of its own); everything else keeps the generic path."""
+        eng, erf = optimizer.engine, optimizer.error_function
+        if not isinstance(erf, GoalError) or tdist.is_distributed() or eng._custom_ops():
+            return False
+        if eng.ray_shard not in (None, "auto"):
+            return False
+        try:
+            erf.rows_for(2)
+        except ValueError:
+            return False
+        return True
 
     @staticmethod
     def rowwise_ready(eng):
@@ -307,6 +346,8 @@ class FusedStep:
         """update -> trace -> error -> reverse sweep -> parameter gradients.  Returns
         (grads, error tensor {sum, terms, mean}).  Nothing here waits for the device."""
         opt, eng = self.opt, self.opt.engine
+        if eng.dimension == 2:
+            return self._enqueue_gradient2d()
         system = eng.optical_system
         eng.clear_ray_history()
         from . import boundaries
@@ -429,15 +470,16 @@ class FusedStep:
                     ops._p(st["g_fin"]), st["capN"], None, 0, None, 0, None, 0, ops._p(st["g_fv"]),
                     None, ops._p(st["counts"]), ops._p(st["ws"]), st["wsb"], stream),
                     "tfrt_trace3d_backward")
-            grads = self._parameter_gradients(fv, st, tap_log)
+            grads = self._parameter_gradients([fv], [st["g_fv"]], tap_log)
         self._publish_lazily(st, src, P, flags, perm, (block, float(eng.dead_ray_length or 0.0))
                              if inplace else None)
         # (publish() inverts `perm` when it runs: a replayed graph re-orders a re-drawn source into
         # the same tensor behind Python's back)
         return grads, st["err"]
 
-    def _parameter_gradients(self, fv, st, tap_log):
-        """d error / d parameters from d error / d faces (st["g_fv"]) through update()'s graph."""
+    def _parameter_gradients(self, outs, g_outs, tap_log):
+        """d error / d parameters from d error / d geometry (``g_outs``: the faces' gradient in 3-D,
+        the merged segments' and arcs' in 2-D) through update()'s graph."""
         opt = self.opt
         grads = [None] * len(opt.parameters)
         if True:
@@ -460,8 +502,7 @@ class FusedStep:
                     inputs.extend(taps + [p])
                     owner.extend([i] * len(taps) + [-1 - i])
             with torch.autograd.set_multithreading_enabled(False):
-                got = torch.autograd.grad([fv], inputs, grad_outputs=[st["g_fv"]],
-                                          allow_unused=True)
+                got = torch.autograd.grad(outs, inputs, grad_outputs=g_outs, allow_unused=True)
             total = {}
             for i, g in zip(owner, got):
                 if g is None:
@@ -567,13 +608,131 @@ class FusedStep:
                     float(eng.dead_ray_length or 0.0), P, dt, ops._p(g64), g64.shape[1], None, 0,
                     None, 0, None, 0, ops._p(st["g_fv"]), None, ops._p(st["counts"]),
                     ops._p(st["ws"]), st["wsb"], stream), "tfrt_trace3d_backward")
-                grads = self._parameter_gradients(fv, st, tap_log)
+                grads = self._parameter_gradients([fv], [st["g_fv"]], tap_log)
         finally:
             sc.in_place = 1 if scene.in_place else 0      # (the struct is cached by the scene)
             sc.clear_buffer, sc.clear_count = None, 0
         self._goal_pending = None
         self._publish_lazily(st, src, P, flags, perm, (block, float(eng.dead_ray_length or 0.0)))
         return grads, st["err"]
+
+    # ------------------------------------------------------------------------------ 2-D
+    def _buffers2d(self, block, seg, arc, P, flags, dt, rows):
+        """Persistent outputs / tape / gradient blocks of a 2-D trace for this (N, Ms, Ma, P,
+        dtype, flags, fields)."""
+        N = block.shape[1]
+        Ms = 0 if seg is None else seg.shape[0]
+        Ma = 0 if arc is None else arc.shape[0]
+        sig = (2, N, Ms, Ma, P, dt, flags, str(block.device), tuple(rows))
+        st = self._state
+        if st is not None and st["sig"] == sig:
+            return st
+        dev = block.device
+        L = _lib.lib()
+        wsb = L.tfrt_trace2d_workspace_bytes(N, Ms, Ma, P, dt)
+        capN = max(N, 1)
+        ints = ops._IntPool(dev, True, _lib.COUNTS_PER_PASS * (P + 1), flags, capN, P)
+        caps = {"finished": capN, "active": capN * max(P, 1), "stopped": capN, "dead": capN}
+        full, aux, outs = {}, {"counts": ints.counts}, {}
+        for name, flag in _CLASS_FLAGS:
+            if flags & flag:
+                rays = torch.empty((4, caps[name]), dtype=block.dtype, device=dev)
+                ids, faces = ints.take(caps[name]), ints.take(caps[name])
+                full[name], aux[name + "_id"], aux[name + "_face"] = rays, ids, faces
+                outs[name] = ops._ray_out(rays, ids, faces)
+            else:
+                aux[name + "_id"] = aux[name + "_face"] = None
+                outs[name] = ops._ray_out(None, None, None)
+        aux["unfinished"] = torch.empty((4, 0), dtype=block.dtype, device=dev)
+        aux["unfinished_id"] = torch.empty(0, dtype=torch.int32, device=dev)
+        gws = L.tfrt_trace2d_backward_goal_workspace_bytes(N)
+        # (segment and arc gradients in one block: one clearing launch per step)
+        g_prim = torch.zeros(max(4 * Ms + 5 * Ma, 1), dtype=torch.float64, device=dev)
+        st = dict(
+            sig=sig, dim=2, N=N, Ms=Ms, Ma=Ma, P=P, dt=dt, flags=flags, capN=capN, full=full,
+            aux=aux, outs=outs, ws=torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev),
+            wsb=wsb, counts=ints.counts, ints=ints, g_prim=g_prim,
+            g_seg=g_prim[:4 * Ms].view(Ms, 4), g_arc=g_prim[4 * Ms:4 * Ms + 5 * Ma].view(Ma, 5),
+            err=torch.zeros(3, dtype=torch.float64, device=dev),
+            goal_ws=torch.zeros(max(gws, 1), dtype=torch.uint8, device=dev), gws=gws,
+            fields=(ctypes.c_int32 * 4)(*(list(rows) + [0] * 4)[:4]),
+        )
+        self._state = st
+        self._graphs = None
+        if self.tests_total is None or self.tests_total.device != dev:
+            self.tests_total = torch.zeros(1, dtype=torch.int64, device=dev)
+        return st
+
+    def _enqueue_gradient2d(self):
+        """_enqueue_gradient of a 2-D engine: update -> tfrt_trace2d_forward ->
+        tfrt_trace2d_backward_goal (error, seed and the reverse sweep of every pass in one
+        launch) -> parameter gradients through update()'s graph from the merged segments and
+        arcs.  One process, rays in natural order."""
+        opt, eng = self.opt, self.opt.engine
+        system = eng.optical_system
+        eng.clear_ray_history()
+        from . import boundaries
+        with boundaries.collect_taps() as tap_log:
+            system.update()
+        src = eng._source_set()
+        if not src:
+            raise RuntimeError("FusedStep: the optical system has no source rays")
+        erf = opt.error_function
+        rows = erf.rows_for(2)
+        block, scene, _ = eng._trace_inputs(src)
+        goal = erf.table(src)
+        P, flags = int(opt.trace_depth), eng._flags() | _lib.COMPILE_FINISHED
+        dt = ops._DT[block.dtype]
+        geo = [None if k is None else k["geo"] for k in (scene.segments, scene.arcs)]
+        det = [None if g is None else g.detach() for g in geo]
+        if any(g is not None and (g.dtype != torch.float64 or not g.is_contiguous()) for g in det):
+            raise RuntimeError("FusedStep: merged segments / arcs must be contiguous float64")
+        st = self._buffers2d(block, det[0], det[1], P, flags, dt, rows)
+        L = _lib.lib()
+        stream = ops._stream(block)
+        sc = scene.struct(det[0], det[1])
+        o = st["outs"]
+        check(L.tfrt_trace2d_forward(
+            ops._p(block), block.shape[1], st["N"], ctypes.byref(sc), float(eng.new_ray_length),
+            float(eng.dead_ray_length or 0.0), P, dt, flags, ctypes.byref(o["finished"]),
+            ctypes.byref(o["active"]), ctypes.byref(o["stopped"]), ctypes.byref(o["dead"]),
+            None, None,      # (the rays still active after the last pass are not copied out)
+            ops._p(st["counts"]), ops._p(st["ws"]), st["wsb"], stream), "tfrt_trace2d_forward")
+        back = [(g, grad) for g, grad in zip(geo, (st["g_seg"], st["g_arc"]))
+                if g is not None and g.requires_grad and g.shape[0] > 0]
+        if back:
+            st["g_prim"].zero_()
+        pending = _lib.GoalPending()
+        check(L.tfrt_trace2d_backward_goal(
+            ops._p(block), block.shape[1], st["N"], ctypes.byref(sc), float(eng.new_ray_length),
+            P, dt, ctypes.byref(o["finished"]), st["fields"], len(rows), ops._p(goal),
+            goal.shape[1], 1, ops._p(st["err"]), ops._p(self.tests_total), ops._p(st["goal_ws"]),
+            st["gws"], ctypes.byref(pending),
+            ops._p(st["g_seg"]) if back and st["Ms"] else None,
+            ops._p(st["g_arc"]) if back and st["Ma"] else None,
+            ops._p(st["counts"]), ops._p(st["ws"]), st["wsb"], stream),
+            "tfrt_trace2d_backward_goal")
+        # (nothing on the device waits for the error sum: the parameter update's launch finishes it)
+        self._goal_pending = (pending, stream)
+        self.folded_backward, self.in_place = True, False
+        grads = [None] * len(opt.parameters)
+        if back:
+            grads = self._parameter_gradients([b[0] for b in back], [b[1] for b in back], tap_log)
+        self._publish_lazily2d(st, src)
+        return grads, st["err"]
+
+    def _publish_lazily2d(self, st, src):
+        eng = self.opt.engine
+        eng._trace_src = src
+        eng._trace_sig = (src.n_rays if hasattr(src, "n_rays") else src["x_start"].shape[0],
+                          st["P"], st["flags"])
+        self._last_perm, self._last_inplace = None, None
+
+        def publish():
+            out = ops._finish_trace(dict(st["full"]), dict(st["aux"]), st["P"], None)
+            out["n_segments"] = st["Ms"]
+            return out
+        eng._pending_trace = publish
 
     def _publish_lazily(self, st, src, P, flags, perm=None, inplace=None):
         eng = self.opt.engine
@@ -781,7 +940,7 @@ class FusedStep:
         if src and hasattr(src, "identity"):
             src_id = src.identity        # (rays re-drawn in place: the buffers stay)
         else:
-            src_id = tuple(id(src[f]) for f in _GEO3) if src else ()
+            src_id = tuple(id(src[f]) for f in (_GEO3 if eng.dimension == 3 else _GEO2)) if src else ()
         return (tuple(id(a) for a in accumulators), tuple(p.data_ptr() for p in opt.parameters),
                 src_id, int(opt.trace_depth),
                 eng._flags(), eng.new_ray_length, eng.dead_ray_length, eng._trace_mode(),
@@ -858,6 +1017,9 @@ class FusedStep:
         st = self._state
         eng = self.opt.engine
         eng.clear_ray_history()
+        if st.get("dim") == 2:
+            self._publish_lazily2d(st, eng._trace_src)
+            return
         self._publish_lazily(st, eng._trace_src, st["P"], st["flags"],
                              getattr(self, "_last_perm", None), getattr(self, "_last_inplace", None))
 

@@ -159,7 +159,8 @@ class SGD_Optimizer:
         self._acc_cache = {}
         # ``fused``: run a step whose error function is a ``GoalError`` as one fixed launch
         # sequence (fused_step.FusedStep: no host read of the ray counts, built-in error and seed
-        # kernel); ``graph``: replay that sequence from a captured HIP graph after a few steps.
+        # kernel -- on 3-D engines, and on 2-D ones in a single process); ``graph``: replay that
+        # sequence from a captured HIP graph after a few steps.
         # "auto" = whenever possible; False = always the generic path.
         self.fused = fused
         self.graph = graph

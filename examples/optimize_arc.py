@@ -9,10 +9,13 @@ The reference's error is a GoalError (goal: y_end = 0), so on the GPU SGD_Optimi
 2-D step -- update, tfrt_trace2d_forward, tfrt_trace2d_backward_goal, parameter update -- captured
 in one HIP graph after a few eager steps.  The reference's optimiser is Keras SGD with learning
 rate 1, Nesterov momentum 0.8 and the gradient clipped to 0.1; ``--momentum`` runs that rule
-(without it: plain SGD).  ``--generic`` forces the generic path (user error function, autograd)
-for comparison.  No GUI.
+(without it: plain SGD).  ``--rowwise`` states the same error as
+``RowwiseError(lambda r: r["y_end"] ** 2)``, any element-wise torch function's form: the fused step
+then evaluates it on fixed-shape columns (tfrt_trace2d_rows, tfrt_trace2d_backward_rows) inside
+the same graph.  ``--generic`` forces the generic path (user error function, autograd) for
+comparison.  No GUI.
 
-    python examples/optimize_arc.py [--rays 10] [--steps 30] [--momentum] [--generic]
+    python examples/optimize_arc.py [--rays 10] [--steps 30] [--momentum] [--rowwise] [--generic]
 """
 import argparse
 import math
@@ -71,10 +74,13 @@ def build(ray_count=10, ray_dtype=torch.float64, device="cuda:0"):
     return dict(parameter=parameter, arc=arc, system=system, engine=trace_engine)
 
 
-def make_optimizer(scene, momentum=False, generic=False):
-    n = scene["system"].sources["x_start"].shape[0]
-    goal = torch.zeros(n, dtype=torch.float64, device=scene["parameter"].device)
-    erf = optimizer.GoalError(("y_end",), goal)
+def make_optimizer(scene, momentum=False, generic=False, rowwise=False):
+    if rowwise:
+        erf = optimizer.RowwiseError(lambda r: r["y_end"] ** 2)
+    else:
+        n = scene["system"].sources["x_start"].shape[0]
+        goal = torch.zeros(n, dtype=torch.float64, device=scene["parameter"].device)
+        erf = optimizer.GoalError(("y_end",), goal)
     # Keras SGD(learning_rate=1.0, momentum=0.8, nesterov=True) of the reference, gradient clipped
     # to 0.1 before it is applied
     return optimizer.SGD_Optimizer(scene["engine"], [scene["parameter"]], erf, 2,
@@ -82,9 +88,9 @@ def make_optimizer(scene, momentum=False, generic=False):
                                    apply_momentum=momentum, fused=not generic)
 
 
-def run(ray_count=10, steps=30, momentum=False, generic=False, verbose=True):
+def run(ray_count=10, steps=30, momentum=False, generic=False, verbose=True, rowwise=False):
     scene = build(ray_count)
-    opt = make_optimizer(scene, momentum, generic)
+    opt = make_optimizer(scene, momentum, generic, rowwise)
     errors = []
     for i in range(steps):
         # the reference's schedule: 30 steps at learning rate 1, then 0.1 (its momentum stays 0.8:
@@ -104,10 +110,12 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--momentum", action="store_true",
                     help="the reference's Nesterov momentum 0.8")
+    ap.add_argument("--rowwise", action="store_true",
+                    help="the same error as a RowwiseError (any element-wise error function)")
     ap.add_argument("--generic", action="store_true",
                     help="force the generic optimiser step (for comparison)")
     a = ap.parse_args()
-    errors, s = run(a.rays, a.steps, a.momentum, a.generic)
+    errors, s = run(a.rays, a.steps, a.momentum, a.generic, rowwise=a.rowwise)
     fs = s["optimizer"]._fused_step
     path = ("generic" if fs is None else
             f"fused, {fs.graph_replays} of {fs.steps} steps replayed from a HIP graph")

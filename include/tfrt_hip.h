@@ -712,6 +712,45 @@ int tfrt_trace2d_backward_goal(const void* src_rays, int64_t src_stride, int64_t
                                const int32_t* counts, void* workspace, size_t workspace_bytes,
                                void* stream);
 
+/* Any row-wise error over the same chains (fused_step.RowwiseError on a 2-D engine): the finished
+ * rays as FIXED-SHAPE columns, one per source ray, then the reverse sweep of
+ * tfrt_trace2d_backward_goal seeded from the error's gradient with respect to those columns.
+ * Between the two calls the caller evaluates the error terms and their gradient (torch autograd,
+ * element-wise); no ray count is read on the host, so the sequence can be captured in a graph.
+ *   src_rays .. state_dtype, counts, workspace, finished   as for tfrt_trace2d_backward_goal
+ * tfrt_trace2d_rows:
+ *   rows (4 rows of rows_stride >= n_rays, state dtype)  column i = the row of `finished` source ray
+ *                   i's chain ended in, bit for bit; a chain that did not finish gets a finite
+ *                   stand-in, source ray i itself
+ *   row_face (n_rays) int32  the finished ray's primitive (segment index, Ms + arc index), -1 for
+ *                   a chain that did not finish: the mask
+ *   Every column is written exactly once: nothing to clear before.
+ * tfrt_trace2d_backward_rows:
+ *   err_terms       f64, term c of ray i at c * err_stride + i * err_ray_stride, n_terms >= 1;
+ *                   summed over the chains that finished in per-wavefront partials (a fixed order)
+ *   grad_rows (4 rows of grad_stride >= n_rays, f64)  d error / d rows, or NULL (zero); rows 0, 1
+ *                   seed the start gradient and rows 2, 3 the hit gradient of the chain's last
+ *                   link, where tfrt_trace2d_backward_goal puts 2 (out - goal)
+ *   Both are read only for chains that finished: masked columns may hold NaN or inf.
+ *   error_out, tests_total, goal_workspace, pending  as for tfrt_trace2d_backward_goal (terms =
+ *                   finished rays x n_terms; tests_total gets the trace's test count when the
+ *                   pending sum is finished)
+ *   grad_seg (Ms,4), grad_arc (Ma,5) f64, ACCUMULATED into (caller zeroes), either may be NULL. */
+int tfrt_trace2d_rows(const void* src_rays, int64_t src_stride, int64_t n_rays,
+                      int32_t max_passes, int32_t state_dtype, const tfrt_ray_out* finished,
+                      void* rows, int64_t rows_stride, int32_t* row_face, const int32_t* counts,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int tfrt_trace2d_backward_rows(const void* src_rays, int64_t src_stride, int64_t n_rays,
+                               const tfrt_scene2d* scene, double new_ray_length,
+                               int32_t max_passes, int32_t state_dtype,
+                               const tfrt_ray_out* finished, const double* err_terms,
+                               int32_t n_terms, int64_t err_stride, int64_t err_ray_stride,
+                               const double* grad_rows, int64_t grad_stride, double* error_out,
+                               int64_t* tests_total, void* goal_workspace,
+                               size_t goal_workspace_bytes, tfrt_goal_pending* pending,
+                               double* grad_seg, double* grad_arc, const int32_t* counts,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Ray order.  The reference's ray sets are ORDERED: every class lists, pass after pass, its rays
  * in the order of the source set (OpticalEngine.ray_trace / single_pass own both: tfrt/engine.py:

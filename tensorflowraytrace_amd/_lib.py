@@ -183,6 +183,14 @@ SIGNATURES = {
         c_vp, c_i64, c_i64, _P(Scene2D), c_f64, c_i32, c_i32,           # rays, scene, length, P, dtype
         c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp,   # goal
         c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "tfrt_trace2d_rows": (c_i32, [
+        c_vp, c_i64, c_i64, c_i32, c_i32, _P(RayOut),                   # rays, P, dtype, finished
+        c_vp, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "tfrt_trace2d_backward_rows": (c_i32, [
+        c_vp, c_i64, c_i64, _P(Scene2D), c_f64, c_i32, c_i32, _P(RayOut),
+        c_vp, c_i32, c_i64, c_i64, c_vp, c_i64,                         # error terms, seeds
+        c_vp, c_vp, c_vp, c_sz, c_vp,                                   # the pending error sum
+        c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "tfrt_ray_order_workspace_bytes": (c_sz, [c_i64]),
     "tfrt_ray_order": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz,
                                c_vp]),

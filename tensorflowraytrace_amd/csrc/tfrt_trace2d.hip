@@ -959,12 +959,104 @@ static int trace2d_backward_t(const void* src_rays, int64_t src_stride, int64_t 
 // The links of a wave are processed in lockstep (link k of every lane together), so that the
 // primitive gradients can be combined inside the wave before the global atomics: in a scene of
 // few primitives (dev/optimize_single_arc.py: one arc) every lane adds into the same row.
+//
+// The seed is a template parameter of the kernel: SeedGoal2 forms it from the goal (and sums the
+// error), SeedRows2 reads it from a buffer of row gradients (tfrt_trace2d_backward_rows: the
+// gradient of any row-wise error over the columns tfrt_trace2d_rows made).
 constexpr int CHAIN2 = 16;
 
 struct ChainGoal2 {
   GoalFields gf;
   const double* goal;
   int64_t goal_stride, goal_ray_stride;
+};
+
+// Walks source ray i's chain forward through the tape.  keep(p, idx) is told every link's index
+// into its pass's input; returns the last link's pass (-1: P == 0) and leaves how the chain ended
+// in end_cls / end_slot (-1 / 0 while it is still active after pass P-1) and that last link's
+// index in `last`.
+template <typename Keep>
+__device__ __forceinline__ int walk_chain2(int i, const uint8_t* __restrict__ rec_bin,
+                                           const int32_t* __restrict__ rec_slot, int64_t n, int P,
+                                           Keep keep, int& end_cls, int& end_slot, int& last) {
+  int top = -1;
+  int idx = i;
+  for (int p = 0; p < P; ++p) {
+    keep(p, idx);
+    top = p;
+    last = idx;
+    const int bin = rec_bin[(size_t)p * n + idx];
+    const int slot = rec_slot[(size_t)p * n + idx];
+    const int cls = (bin == BIN_DEAD) ? CLS_DEAD : (bin >> 1);
+    if (cls != CLS_ACTIVE) {
+      end_cls = cls;
+      end_slot = slot;
+      break;
+    }
+    idx = slot;
+  }
+  return top;
+}
+
+// Per-wavefront partial sum of `acc`, lanes in a fixed butterfly order (called by all 64 lanes).
+__device__ __forceinline__ void wave_partial(double acc, int N, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d, 64);
+  const int64_t wave_g = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
+  if (lane_id() == 0 && wave_g * 64 < N) partial[wave_g] = acc;
+}
+
+// The goal residual: seeds 2 (out - goal) on the goal's rows and returns the squared residuals'
+// sum; sum() leaves the wave's partial error sum.
+struct SeedGoal2 {
+  ChainGoal2 cg;
+  double* partial;
+
+  template <typename T>
+  __device__ __forceinline__ double seed(const tfrt_ray_out& fin, int end_slot, int i,
+                                         double sd[4]) const {
+    // the reference's squared_difference and reduce_sum are separate ops: no contraction (the
+    // adjoint's own arithmetic is compiled as in k_backward2d)
+#pragma clang fp contract(off)
+    double acc = 0.0;
+    const T* out = static_cast<const T*>(fin.rays);
+    for (int c = 0; c < cg.gf.n; ++c) {
+      const int row = cg.gf.row[c];
+      const double r = ldd(out, (int64_t)row * fin.capacity + end_slot) -
+                       cg.goal[(int64_t)c * cg.goal_stride + (int64_t)i * cg.goal_ray_stride];
+      sd[row] = 2.0 * r;
+      acc += r * r;
+    }
+    return acc;
+  }
+
+  __device__ __forceinline__ void sum(double acc, int N) const { wave_partial(acc, N, partial); }
+};
+
+// Row gradients d error / d (x_start, y_start, x_end, y_end) of source ray i's column, rows
+// `stride` apart (NULL: zero), and ray i's n_terms error terms, summed like SeedGoal2's.
+struct SeedRows2 {
+  const double* g;
+  int64_t stride;
+  const double* err;
+  int64_t err_stride, err_ray_stride;
+  int n_terms;
+  double* partial;
+
+  template <typename T>
+  __device__ __forceinline__ double seed(const tfrt_ray_out&, int, int i, double sd[4]) const {
+#pragma clang fp contract(off)
+    if (g != nullptr)
+      for (int r = 0; r < 4; ++r) sd[r] = g[(int64_t)r * stride + i];
+    double acc = 0.0;
+    for (int c = 0; c < n_terms; ++c) acc += err[(int64_t)c * err_stride + (int64_t)i * err_ray_stride];
+    return acc;
+  }
+
+  __device__ __forceinline__ void sum(double acc, int N) const {
+    wave_partial(acc, N, partial);
+  }
 };
 
 // Adds the gradient rows of the lanes with `has` set into g_seg / g_arc: one atomic per entry
@@ -1008,13 +1100,13 @@ __device__ __forceinline__ void add_prim_grads(bool has, int prim, const double 
   }
 }
 
-template <typename T>
+template <typename T, typename Seed>
 __global__ __launch_bounds__(BLOCK) void k_backward2d_goal(
     const T* __restrict__ src, int64_t src_stride, int N, const T* __restrict__ rays_ws,
     int64_t n, const int32_t* __restrict__ rec_prim, const double* __restrict__ rec_u,
     const uint8_t* __restrict__ rec_bin, const int32_t* __restrict__ rec_slot, int P,
-    tfrt_scene2d sc, double L, tfrt_ray_out fin, ChainGoal2 cg, double* __restrict__ partial,
-    double* __restrict__ g_seg, double* __restrict__ g_arc) {
+    tfrt_scene2d sc, double L, tfrt_ray_out fin, Seed seed, double* __restrict__ g_seg,
+    double* __restrict__ g_arc) {
   __shared__ int32_t chain[CHAIN2 * BLOCK];
   const int tid = threadIdx.x;
   const int i = blockIdx.x * BLOCK + tid;
@@ -1023,47 +1115,16 @@ __global__ __launch_bounds__(BLOCK) void k_backward2d_goal(
   auto link_at = [&](int p) -> int32_t& { return chain[(p % CHAIN2) * BLOCK + tid]; };
 
   // walk forward: every link's index into its pass's input (the last CHAIN2 kept), the end class
-  int top = -1, end_cls = -1, end_slot = 0;
-  if (lane_ok) {
-    int idx = i;
-    for (int p = 0; p < P; ++p) {
-      link_at(p) = idx;
-      top = p;
-      const int bin = rec_bin[(size_t)p * n + idx];
-      const int slot = rec_slot[(size_t)p * n + idx];
-      const int cls = (bin == BIN_DEAD) ? CLS_DEAD : (bin >> 1);
-      if (cls != CLS_ACTIVE) {
-        end_cls = cls;
-        end_slot = slot;
-        break;
-      }
-      idx = slot;
-    }
-  }
-  // the residuals of a finished chain, and its seed (rows 0, 1 -> start, rows 2, 3 -> hit)
+  int top = -1, end_cls = -1, end_slot = 0, last = 0;
+  if (lane_ok)
+    top = walk_chain2(i, rec_bin, rec_slot, n, P, [&](int p, int idx) { link_at(p) = idx; },
+                      end_cls, end_slot, last);
+  // the seed of a finished chain (rows 0, 1 -> start, rows 2, 3 -> hit), read for no other chain
   double acc = 0.0;
   double sd[4] = {0.0, 0.0, 0.0, 0.0};
-  if (end_cls == CLS_FINISHED && end_slot < fin.capacity) {
-    // the reference's squared_difference and reduce_sum are separate ops: no contraction (the
-    // adjoint's own arithmetic is compiled as in k_backward2d)
-#pragma clang fp contract(off)
-    const T* out = static_cast<const T*>(fin.rays);
-    for (int c = 0; c < cg.gf.n; ++c) {
-      const int row = cg.gf.row[c];
-      const double r = ldd(out, (int64_t)row * fin.capacity + end_slot) -
-                       cg.goal[(int64_t)c * cg.goal_stride + (int64_t)i * cg.goal_ray_stride];
-      sd[row] = 2.0 * r;
-      acc += r * r;
-    }
-  }
-  // per-wavefront partial sum, lanes in a fixed butterfly order
-  {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d, 64);
-  }
-  const int64_t wave_g = ((int64_t)blockIdx.x * BLOCK + tid) >> 6;
-  if (lane_id() == 0 && wave_g * 64 < N) partial[wave_g] = acc;
+  if (end_cls == CLS_FINISHED && end_slot < fin.capacity)
+    acc = seed.template seed<T>(fin, end_slot, i, sd);
+  seed.sum(acc, N);
 
   // reverse: link `top` is the chain's end (seeded when finished, no child), every link below it
   // is an active parent whose child gradient is (gc_s, gc_e)
@@ -1125,26 +1186,90 @@ __global__ __launch_bounds__(BLOCK) void k_backward2d_goal(
   }
 }
 
-template <typename T>
+template <typename T, typename Seed>
 static int trace2d_backward_goal_t(const void* src_rays, int64_t src_stride, int64_t N,
                                    const tfrt_scene2d* sc, double L, int P, int dtype,
-                                   const tfrt_ray_out& fin, const ChainGoal2& cg, double* partial,
-                                   double* g_seg, double* g_arc, void* workspace,
-                                   size_t workspace_bytes, hipStream_t st) {
+                                   const tfrt_ray_out& fin, const Seed& seed, double* g_seg,
+                                   double* g_arc, void* workspace, size_t workspace_bytes,
+                                   hipStream_t st) {
   const Layout2 lay = make_layout2(N, P, dtype);
   if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
   if (N == 0) return 0;
   char* ws = static_cast<char*>(workspace);
   const size_t n = N;
-  hipLaunchKernelGGL((k_backward2d_goal<T>), dim3(cdiv(N, BLOCK)), dim3(BLOCK), 0, st,
+  hipLaunchKernelGGL((k_backward2d_goal<T, Seed>), dim3(cdiv(N, BLOCK)), dim3(BLOCK), 0, st,
                      static_cast<const T*>(src_rays), src_stride, (int)N,
                      reinterpret_cast<const T*>(ws + lay.rays), (int64_t)n,
                      reinterpret_cast<const int32_t*>(ws + lay.rec_prim),
                      reinterpret_cast<const double*>(ws + lay.rec_u),
                      reinterpret_cast<const uint8_t*>(ws + lay.rec_bin),
-                     reinterpret_cast<const int32_t*>(ws + lay.rec_slot), P, *sc, L, fin, cg,
-                     partial, g_seg, g_arc);
+                     reinterpret_cast<const int32_t*>(ws + lay.rec_slot), P, *sc, L, fin, seed,
+                     g_seg, g_arc);
   return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+}
+
+// tfrt_trace2d_rows: every source ray's column of fixed-shape rows.  Lane i walks ray i's chain
+// as k_backward2d_goal does; a chain that finished copies its row of the `finished` block (the
+// state dtype, bit for bit) and its primitive, any other chain the source ray itself and -1.
+// Every column is written once.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_rows2d(
+    const T* __restrict__ src, int64_t src_stride, int N, int64_t n,
+    const int32_t* __restrict__ rec_prim, const uint8_t* __restrict__ rec_bin,
+    const int32_t* __restrict__ rec_slot, int P, tfrt_ray_out fin, T* __restrict__ rows,
+    int64_t rows_stride, int32_t* __restrict__ row_face) {
+  const int i = blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= N) return;
+  int end_cls = -1, end_slot = 0, last = 0;
+  const int top = walk_chain2(i, rec_bin, rec_slot, n, P, [](int, int) {}, end_cls, end_slot,
+                              last);
+  const T* from = src;
+  int64_t stride = src_stride, col = i;
+  int face = -1;
+  if (end_cls == CLS_FINISHED && end_slot < fin.capacity) {
+    from = static_cast<const T*>(fin.rays);
+    stride = fin.capacity;
+    col = end_slot;
+    face = rec_prim[(size_t)top * n + last];
+  }
+  for (int r = 0; r < 4; ++r) rows[r * rows_stride + i] = from[r * stride + col];
+  row_face[i] = face;
+}
+
+template <typename T>
+static int trace2d_rows_t(const void* src_rays, int64_t src_stride, int64_t N, int P, int dtype,
+                          const tfrt_ray_out& fin, void* rows, int64_t rows_stride,
+                          int32_t* row_face, void* workspace, size_t workspace_bytes,
+                          hipStream_t st) {
+  const Layout2 lay = make_layout2(N, P, dtype);
+  if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
+  if (N == 0) return 0;
+  char* ws = static_cast<char*>(workspace);
+  hipLaunchKernelGGL((k_rows2d<T>), dim3(cdiv(N, BLOCK)), dim3(BLOCK), 0, st,
+                     static_cast<const T*>(src_rays), src_stride, (int)N, (int64_t)N,
+                     reinterpret_cast<const int32_t*>(ws + lay.rec_prim),
+                     reinterpret_cast<const uint8_t*>(ws + lay.rec_bin),
+                     reinterpret_cast<const int32_t*>(ws + lay.rec_slot), P, fin,
+                     static_cast<T*>(rows), rows_stride, row_face);
+  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+}
+
+// The second stage of a 2-D error sum (per-wavefront partials): {sum, terms = finished rays x
+// n_terms, mean} and the trace's test count, from the trailing counters of the trace
+// {total_active, total_finished, ..., n_tests_lo, n_tests_hi}.
+static tfrt_goal_pending goal_pending2(double* partial, int64_t n_rays, const int32_t* counts,
+                                       int max_passes, int n_terms, double* error_out,
+                                       int64_t* tests_total) {
+  const int32_t* tail = counts + (size_t)max_passes * TFRT_COUNTS_PER_PASS;
+  tfrt_goal_pending g = {};
+  g.partial = partial;
+  g.n_partial = n_rays > 0 ? cdiv(n_rays, 64) : 0;
+  g.n_finished = tail + 1;
+  g.n_fields = n_terms;
+  g.error_out = error_out;
+  g.tests_lo_hi = tail + 4;
+  g.tests_total = tests_total;
+  return g;
 }
 
 template <bool ARC>
@@ -1307,32 +1432,91 @@ int tfrt_trace2d_backward_goal(const void* src_rays, int64_t src_stride, int64_t
   cg.goal_stride = goal_stride;
   cg.goal_ray_stride = goal_ray_stride;
   double* partial = static_cast<double*>(goal_workspace);
+  const SeedGoal2 seed = {cg, partial};
   hipStream_t st = static_cast<hipStream_t>(stream);
   int rc;
   if (state_dtype == TFRT_F32)
     rc = trace2d_backward_goal_t<float>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                        max_passes, state_dtype, *finished, cg, partial, grad_seg,
+                                        max_passes, state_dtype, *finished, seed, grad_seg,
                                         grad_arc, workspace, workspace_bytes, st);
   else if (state_dtype == TFRT_F64)
     rc = trace2d_backward_goal_t<double>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                         max_passes, state_dtype, *finished, cg, partial,
-                                         grad_seg, grad_arc, workspace, workspace_bytes, st);
+                                         max_passes, state_dtype, *finished, seed, grad_seg,
+                                         grad_arc, workspace, workspace_bytes, st);
   else
     rc = trace2d_backward_goal_t<_Float16>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                           max_passes, state_dtype, *finished, cg, partial,
-                                           grad_seg, grad_arc, workspace, workspace_bytes, st);
+                                           max_passes, state_dtype, *finished, seed, grad_seg,
+                                           grad_arc, workspace, workspace_bytes, st);
   if (rc != 0) return rc;
-  // trailing counters of the trace: {total_active, total_finished, ..., n_tests_lo, n_tests_hi}
-  const int32_t* tail = counts + (size_t)max_passes * TFRT_COUNTS_PER_PASS;
-  tfrt_goal_pending g = {};
-  g.partial = partial;
-  g.n_partial = n_rays > 0 ? cdiv(n_rays, 64) : 0;
-  g.n_finished = tail + 1;
-  g.n_fields = n_fields;
-  g.error_out = error_out;
-  g.tests_lo_hi = tail + 4;
-  g.tests_total = tests_total;
-  *pending = g;
+  *pending = goal_pending2(partial, n_rays, counts, max_passes, n_fields, error_out, tests_total);
+  return 0;
+}
+
+int tfrt_trace2d_rows(const void* src_rays, int64_t src_stride, int64_t n_rays,
+                      int32_t max_passes, int32_t state_dtype, const tfrt_ray_out* finished,
+                      void* rows, int64_t rows_stride, int32_t* row_face, const int32_t* counts,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+  if (n_rays < 0 || n_rays >= (1ll << 31) - 4096 || max_passes < 0 || !counts || !workspace ||
+      !finished)
+    return TFRT_E_BADARG;
+  if (n_rays > 0 && (!src_rays || src_stride < n_rays || !rows || rows_stride < n_rays ||
+                     !row_face || !finished->rays || finished->capacity <= 0))
+    return TFRT_E_BADARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (state_dtype == TFRT_F32)
+    return trace2d_rows_t<float>(src_rays, src_stride, n_rays, max_passes, state_dtype, *finished,
+                                 rows, rows_stride, row_face, workspace, workspace_bytes, st);
+  if (state_dtype == TFRT_F64)
+    return trace2d_rows_t<double>(src_rays, src_stride, n_rays, max_passes, state_dtype,
+                                  *finished, rows, rows_stride, row_face, workspace,
+                                  workspace_bytes, st);
+  if (state_dtype == TFRT_F16)
+    return trace2d_rows_t<_Float16>(src_rays, src_stride, n_rays, max_passes, state_dtype,
+                                    *finished, rows, rows_stride, row_face, workspace,
+                                    workspace_bytes, st);
+  return TFRT_E_UNSUPPORTED;
+}
+
+int tfrt_trace2d_backward_rows(const void* src_rays, int64_t src_stride, int64_t n_rays,
+                               const tfrt_scene2d* scene, double new_ray_length,
+                               int32_t max_passes, int32_t state_dtype,
+                               const tfrt_ray_out* finished, const double* err_terms,
+                               int32_t n_terms, int64_t err_stride, int64_t err_ray_stride,
+                               const double* grad_rows, int64_t grad_stride, double* error_out,
+                               int64_t* tests_total, void* goal_workspace,
+                               size_t goal_workspace_bytes, tfrt_goal_pending* pending,
+                               double* grad_seg, double* grad_arc, const int32_t* counts,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  if (!scene2_ok(scene) || n_rays < 0 || n_rays >= (1ll << 31) - 4096 || max_passes < 0 ||
+      !counts || !workspace || !finished || n_terms < 1 || err_stride < 0 ||
+      err_ray_stride < 0 || !error_out || !pending || !goal_workspace ||
+      goal_workspace_bytes < tfrt_trace2d_backward_goal_workspace_bytes(n_rays))
+    return TFRT_E_BADARG;
+  if (n_rays > 0 && (!src_rays || src_stride < n_rays || !err_terms ||
+                     (grad_rows && grad_stride < n_rays) || !finished->rays ||
+                     finished->capacity <= 0))
+    return TFRT_E_BADARG;
+  double* partial = static_cast<double*>(goal_workspace);
+  const SeedRows2 seed = {grad_rows, grad_stride, err_terms, err_stride, err_ray_stride, n_terms,
+                          partial};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int rc;
+  if (state_dtype == TFRT_F32)
+    rc = trace2d_backward_goal_t<float>(src_rays, src_stride, n_rays, scene, new_ray_length,
+                                        max_passes, state_dtype, *finished, seed, grad_seg,
+                                        grad_arc, workspace, workspace_bytes, st);
+  else if (state_dtype == TFRT_F64)
+    rc = trace2d_backward_goal_t<double>(src_rays, src_stride, n_rays, scene, new_ray_length,
+                                         max_passes, state_dtype, *finished, seed, grad_seg,
+                                         grad_arc, workspace, workspace_bytes, st);
+  else if (state_dtype == TFRT_F16)
+    rc = trace2d_backward_goal_t<_Float16>(src_rays, src_stride, n_rays, scene, new_ray_length,
+                                           max_passes, state_dtype, *finished, seed, grad_seg,
+                                           grad_arc, workspace, workspace_bytes, st);
+  else
+    return TFRT_E_UNSUPPORTED;
+  if (rc != 0) return rc;
+  *pending = goal_pending2(partial, n_rays, counts, max_passes, n_terms, error_out, tests_total);
   return 0;
 }
 

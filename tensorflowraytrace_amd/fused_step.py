@@ -27,7 +27,9 @@ states that form declaratively; an optimiser given a ``GoalError`` runs ``FusedS
 
 A 2-D engine (one process, no ray shards) runs ``_enqueue_gradient2d`` instead:
 ``tfrt_trace2d_forward``, then ``tfrt_trace2d_backward_goal`` -- error, seed and the reverse sweep of
-every pass in ONE launch -- and autograd from the merged segments and arcs to the parameters.
+every pass in ONE launch -- and autograd from the merged segments and arcs to the parameters.  With a
+``RowwiseError`` the error comes from ``tfrt_trace2d_rows`` (every source ray's fixed-shape column),
+``fn`` and its autograd, and ``tfrt_trace2d_backward_rows`` sweeps from that gradient.
 
 Every launch has step-independent arguments (learning-rate dependent scalars live in a small
 device table), so after a few eager steps the sequence is captured once in a HIP graph
@@ -157,7 +159,8 @@ class RowwiseError:
     launches, ``fn``'s own torch kernels and their autograd included, are captured in one HIP graph
     like a ``GoalError``'s (fused_step.FusedStep).  Columns of rays that did not finish hold finite
     stand-in values (the source ray); their error terms are masked out of the sum and their
-    gradients are never read."""
+    gradients are never read.  On 2-D engines the same holds with one process and no ray shards
+    (tfrt_trace2d_rows / tfrt_trace2d_backward_rows; 2-D traces keep the source's order)."""
 
     def __init__(self, fn):
         if not callable(fn):
@@ -218,8 +221,8 @@ class _HyperTable:
 
 
 class FusedStep:
-    """Runs ``SGD_Optimizer.single_step`` for a ``GoalError`` as a fixed launch sequence, on 3-D
-    engines (also for a ``RowwiseError``) and on 2-D ones (one process); see the module docstring.
+    """Runs ``SGD_Optimizer.single_step`` for a ``GoalError`` or a ``RowwiseError`` as a fixed
+    launch sequence, on 3-D engines and on 2-D ones (one process); see the module docstring.
     One instance per optimizer."""
 
     # coherent rays: error, gradient seed and reverse sweep as ONE launch (tfrt_trace3d_backward_goal);
@@ -256,7 +259,8 @@ class FusedStep:
         eng = optimizer.engine
         if not isinstance(optimizer.error_function, (GoalError, RowwiseError)) or args or kwargs:
             return False
-        if isinstance(optimizer.error_function, RowwiseError) and not FusedStep.rowwise_ready(eng):
+        if (isinstance(optimizer.error_function, RowwiseError) and eng.dimension == 3
+                and not FusedStep.rowwise_ready(eng)):
             return False
         if not bool(eng.optical_system):
             return False
@@ -271,14 +275,17 @@ class FusedStep:
 
     @staticmethod
     def eligible2d(optimizer):
-        """A 2-D engine takes the fused step with a GoalError over fields its rays have, in one
-        process without ray shards, and with the projection in the kernels (no operation with a
-        main() of its own); everything else keeps the generic path."""
+        """A 2-D engine takes the fused step with a GoalError over fields its rays have or with a
+        RowwiseError, in one process without ray shards, and with the projection in the kernels
+        (no operation with a main() of its own); everything else keeps the generic path."""
         eng, erf = optimizer.engine, optimizer.error_function
-        if not isinstance(erf, GoalError) or tdist.is_distributed() or eng._custom_ops():
+        if not isinstance(erf, (GoalError, RowwiseError)) or tdist.is_distributed() \
+                or eng._custom_ops():
             return False
         if eng.ray_shard not in (None, "auto"):
             return False
+        if isinstance(erf, RowwiseError):
+            return True
         try:
             erf.rows_for(2)
         except ValueError:
@@ -617,13 +624,13 @@ class FusedStep:
         return grads, st["err"]
 
     # ------------------------------------------------------------------------------ 2-D
-    def _buffers2d(self, block, seg, arc, P, flags, dt, rows):
+    def _buffers2d(self, block, seg, arc, P, flags, dt, rows, rowwise=False):
         """Persistent outputs / tape / gradient blocks of a 2-D trace for this (N, Ms, Ma, P,
-        dtype, flags, fields)."""
+        dtype, flags, fields); with ``rowwise`` also the fixed-shape columns of a RowwiseError."""
         N = block.shape[1]
         Ms = 0 if seg is None else seg.shape[0]
         Ma = 0 if arc is None else arc.shape[0]
-        sig = (2, N, Ms, Ma, P, dt, flags, str(block.device), tuple(rows))
+        sig = (2, N, Ms, Ma, P, dt, flags, str(block.device), tuple(rows), bool(rowwise))
         st = self._state
         if st is not None and st["sig"] == sig:
             return st
@@ -657,6 +664,10 @@ class FusedStep:
             goal_ws=torch.zeros(max(gws, 1), dtype=torch.uint8, device=dev), gws=gws,
             fields=(ctypes.c_int32 * 4)(*(list(rows) + [0] * 4)[:4]),
         )
+        if rowwise:
+            # (every column is written by each step's tfrt_trace2d_rows: no clearing)
+            st["rows"] = torch.empty((4, capN), dtype=block.dtype, device=dev)
+            st["row_face"] = torch.empty(capN, dtype=torch.int32, device=dev)
         self._state = st
         self._graphs = None
         if self.tests_total is None or self.tests_total.device != dev:
@@ -678,15 +689,14 @@ class FusedStep:
         if not src:
             raise RuntimeError("FusedStep: the optical system has no source rays")
         erf = opt.error_function
+        if isinstance(erf, RowwiseError):
+            return self._enqueue_rowwise2d(erf, src, tap_log)
         rows = erf.rows_for(2)
         block, scene, _ = eng._trace_inputs(src)
         goal = erf.table(src)
         P, flags = int(opt.trace_depth), eng._flags() | _lib.COMPILE_FINISHED
         dt = ops._DT[block.dtype]
-        geo = [None if k is None else k["geo"] for k in (scene.segments, scene.arcs)]
-        det = [None if g is None else g.detach() for g in geo]
-        if any(g is not None and (g.dtype != torch.float64 or not g.is_contiguous()) for g in det):
-            raise RuntimeError("FusedStep: merged segments / arcs must be contiguous float64")
+        geo, det = self._geometry2d(scene)
         st = self._buffers2d(block, det[0], det[1], P, flags, dt, rows)
         L = _lib.lib()
         stream = ops._stream(block)
@@ -717,6 +727,87 @@ class FusedStep:
         self.folded_backward, self.in_place = True, False
         grads = [None] * len(opt.parameters)
         if back:
+            grads = self._parameter_gradients([b[0] for b in back], [b[1] for b in back], tap_log)
+        self._publish_lazily2d(st, src)
+        return grads, st["err"]
+
+    @staticmethod
+    def _geometry2d(scene):
+        """The merged segments and arcs (None where the scene has none) and their detached views."""
+        geo = [None if k is None else k["geo"] for k in (scene.segments, scene.arcs)]
+        det = [None if g is None else g.detach() for g in geo]
+        if any(g is not None and (g.dtype != torch.float64 or not g.is_contiguous()) for g in det):
+            raise RuntimeError("FusedStep: merged segments / arcs must be contiguous float64")
+        return geo, det
+
+    def _enqueue_rowwise2d(self, erf, src, tap_log):
+        """_enqueue_gradient2d for a RowwiseError: update (done) -> tfrt_trace2d_forward ->
+        tfrt_trace2d_rows (every source ray's column, a mask for the rays that finished) ->
+        ``erf.fn`` on those columns + its autograd (torch) -> tfrt_trace2d_backward_rows seeded
+        with the columns' gradient -> parameter gradients.  No ray count is read; everything is
+        capturable."""
+        opt, eng = self.opt, self.opt.engine
+        block, scene, _ = eng._trace_inputs(src)
+        P, flags = int(opt.trace_depth), eng._flags() | _lib.COMPILE_FINISHED
+        dt = ops._DT[block.dtype]
+        geo, det = self._geometry2d(scene)
+        st = self._buffers2d(block, det[0], det[1], P, flags, dt, (), rowwise=True)
+        N = st["N"]
+        L = _lib.lib()
+        stream = ops._stream(block)
+        sc = scene.struct(det[0], det[1])
+        o = st["outs"]
+        check(L.tfrt_trace2d_forward(
+            ops._p(block), block.shape[1], N, ctypes.byref(sc), float(eng.new_ray_length),
+            float(eng.dead_ray_length or 0.0), P, dt, flags, ctypes.byref(o["finished"]),
+            ctypes.byref(o["active"]), ctypes.byref(o["stopped"]), ctypes.byref(o["dead"]),
+            None, None,      # (the rays still active after the last pass are not copied out)
+            ops._p(st["counts"]), ops._p(st["ws"]), st["wsb"], stream), "tfrt_trace2d_forward")
+        # the finished rows at their source rays' columns
+        check(L.tfrt_trace2d_rows(
+            ops._p(block), block.shape[1], N, P, dt, ctypes.byref(o["finished"]),
+            ops._p(st["rows"]), st["rows"].shape[1], ops._p(st["row_face"]), ops._p(st["counts"]),
+            ops._p(st["ws"]), st["wsb"], stream), "tfrt_trace2d_rows")
+        # the user's error function, row by row on every source ray's column (natural order:
+        # column i is source ray i, whose own fields are the inherited ones)
+        leaf = st["rows"].detach().requires_grad_(True)
+        e = erf.fn(_RowFields({name: leaf[k] for k, name in enumerate(_GEO2)},
+                              lambda key: src[key]))
+        if e.dim() == 1:
+            e = e.reshape(-1, 1)
+        if e.dim() != 2 or e.shape[0] != N:
+            raise RuntimeError(f"RowwiseError: fn returned {tuple(e.shape)}, expected one row "
+                               f"per ray ({N})")
+        e = e.double()
+        # No reduction over the rays in torch (a sum over a million entries inside a replayed graph
+        # is not reliable): the gradient of the masked sum is the mask itself, and the sum is
+        # formed by the sweep's launch and finished by the parameter update's, as for a GoalError
+        back = [(g, grad) for g, grad in zip(geo, (st["g_seg"], st["g_arc"]))
+                if g is not None and g.requires_grad and g.shape[0] > 0]
+        g64 = None
+        if back and e.requires_grad:
+            mask = (st["row_face"][:N] >= 0).unsqueeze(1).expand_as(e).double()
+            with torch.autograd.set_multithreading_enabled(False):
+                g_rows, = torch.autograd.grad(e, [leaf], grad_outputs=mask)
+            g64 = g_rows.to(torch.float64).contiguous()
+            st["g_prim"].zero_()
+        e = e.detach().contiguous()
+        pending = _lib.GoalPending()
+        check(L.tfrt_trace2d_backward_rows(
+            ops._p(block), block.shape[1], N, ctypes.byref(sc), float(eng.new_ray_length), P, dt,
+            ctypes.byref(o["finished"]), ops._p(e), e.shape[1], 1, e.shape[1],
+            None if g64 is None else ops._p(g64), 0 if g64 is None else g64.shape[1],
+            ops._p(st["err"]), ops._p(self.tests_total), ops._p(st["goal_ws"]), st["gws"],
+            ctypes.byref(pending),
+            ops._p(st["g_seg"]) if g64 is not None and st["Ms"] else None,
+            ops._p(st["g_arc"]) if g64 is not None and st["Ma"] else None,
+            ops._p(st["counts"]), ops._p(st["ws"]), st["wsb"], stream),
+            "tfrt_trace2d_backward_rows")
+        # (nothing on the device waits for the error sum: the parameter update's launch finishes it)
+        self._goal_pending = (pending, stream)
+        self.folded_backward, self.in_place = False, False
+        grads = [None] * len(opt.parameters)
+        if g64 is not None:
             grads = self._parameter_gradients([b[0] for b in back], [b[1] for b in back], tap_log)
         self._publish_lazily2d(st, src)
         return grads, st["err"]

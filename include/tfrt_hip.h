@@ -636,6 +636,17 @@ typedef struct tfrt_scene2d {
    * up to the reflecting one; tfrt_sgd_process zeroes such entries (optimizer.py:226-229).
    * 1: the reflect branch's own finite gradient (new_angle = norm + theta1 + pi) instead. */
   int32_t finite_tir_gradient;
+  /* Reverse sweeps only (tfrt_trace2d_backward, tfrt_trace2d_backward_goal,
+   * tfrt_trace2d_backward_rows), "value" mode (n_table NULL, *_n_in / *_n_out given): f64,
+   * ACCUMULATED into, or NULL (not asked) -- d error / d seg_n_in[k], seg_n_out[k] (Ms each) and
+   * d error / d arc_n_in[k], arc_n_out[k] (Ma each), the 2-D counterpart of
+   * tfrt_scene3d.grad_n_in / grad_n_out (tfrt/operation.py:255-307 reads the two fields as
+   * ordinary tensors).  An index that is 0 (the "safe" ratio replaced it by 1) gets 0.  Ignored in
+   * "index" mode and by tfrt_trace2d_forward. */
+  double* grad_seg_n_in;
+  double* grad_seg_n_out;
+  double* grad_arc_n_in;
+  double* grad_arc_n_out;
 } tfrt_scene2d;
 
 /* OpticalSystem2D._segment_intersection, tfrt/engine.py:688-749 (rays: 4 x stride block). */
@@ -672,7 +683,8 @@ int tfrt_trace2d_forward(const void* src_rays, int64_t src_stride, int64_t n_ray
  * 2-D system, e.g. dev/optimize_single_arc.py where the variable is an arc's centre/radius).
  *   grad_seg (Ms,4) f64 and grad_arc (Ma,5) f64 are ACCUMULATED into (caller zeroes); the
  *   angle_start/angle_end columns of grad_arc stay zero (they only feed comparisons).
- *   grad_src_rays 4 x n_rays f64 or NULL. */
+ *   grad_src_rays 4 x n_rays f64 or NULL.
+ *   scene->grad_{seg,arc}_n_{in,out}: the per-primitive index gradients, when given. */
 int tfrt_trace2d_backward(const void* src_rays, int64_t src_stride, int64_t n_rays,
                           const tfrt_scene2d* scene, double new_ray_length,
                           double dead_ray_length, int32_t max_passes, int32_t state_dtype,
@@ -699,6 +711,8 @@ int tfrt_trace2d_backward(const void* src_rays, int64_t src_stride, int64_t n_ra
  *                   terms = finished rays x n_fields; tests_total gets the trace's test count)
  *   grad_seg (Ms,4), grad_arc (Ma,5) f64, ACCUMULATED into (caller zeroes), either may be NULL;
  *   lanes that share a primitive are summed inside the wavefront before the global atomic.
+ *   scene->grad_{seg,arc}_n_{in,out}: the per-primitive index gradients, when given (summed
+ *   inside the wavefront the same way).
  * No class gradients besides the goal's and no source-ray gradient. */
 size_t tfrt_trace2d_backward_goal_workspace_bytes(int64_t n_rays);
 int tfrt_trace2d_backward_goal(const void* src_rays, int64_t src_stride, int64_t n_rays,
@@ -735,7 +749,8 @@ int tfrt_trace2d_backward_goal(const void* src_rays, int64_t src_stride, int64_t
  *   error_out, tests_total, goal_workspace, pending  as for tfrt_trace2d_backward_goal (terms =
  *                   finished rays x n_terms; tests_total gets the trace's test count when the
  *                   pending sum is finished)
- *   grad_seg (Ms,4), grad_arc (Ma,5) f64, ACCUMULATED into (caller zeroes), either may be NULL. */
+ *   grad_seg (Ms,4), grad_arc (Ma,5) f64, ACCUMULATED into (caller zeroes), either may be NULL;
+ *   scene->grad_{seg,arc}_n_{in,out} as for tfrt_trace2d_backward_goal. */
 int tfrt_trace2d_rows(const void* src_rays, int64_t src_stride, int64_t n_rays,
                       int32_t max_passes, int32_t state_dtype, const tfrt_ray_out* finished,
                       void* rows, int64_t rows_stride, int32_t* row_face, const int32_t* counts,

@@ -46,6 +46,8 @@ class Scene2D(ctypes.Structure):
         ("n_table", c_vp), ("n_table_stride", c_i64), ("n_materials", c_i32),
         ("intersect_epsilion", c_f64), ("size_epsilion", c_f64), ("ray_start_epsilion", c_f64),
         ("finite_tir_gradient", c_i32),
+        ("grad_seg_n_in", c_vp), ("grad_seg_n_out", c_vp),
+        ("grad_arc_n_in", c_vp), ("grad_arc_n_out", c_vp),
     ]
 
 

@@ -646,7 +646,20 @@ __device__ __forceinline__ void add4(const double* g, int64_t cap, int64_t slot,
   }
 }
 
-template <typename T>
+// Index gradient of one link ("value" mode): adds gn = {d / d n_in, d / d n_out} into the link's
+// primitive's rows of tfrt_scene2d.grad_{seg,arc}_n_{in,out} (those given).
+__device__ __forceinline__ void add_index_grads(const tfrt_scene2d& sc, int prim, const double gn[2]) {
+  const int Ms = (int)sc.n_segments;
+  const bool is_arc = prim >= Ms;
+  const int k = is_arc ? prim - Ms : prim;
+  double* gi = is_arc ? sc.grad_arc_n_in : sc.grad_seg_n_in;
+  double* go = is_arc ? sc.grad_arc_n_out : sc.grad_seg_n_out;
+  if (gi != nullptr && gn[0] != 0.0) unsafeAtomicAdd(gi + k, gn[0]);
+  if (go != nullptr && gn[1] != 0.0) unsafeAtomicAdd(go + k, gn[1]);
+}
+
+// GN: the index gradients are asked for (index_grads2d(sc)); false compiles none of their terms.
+template <typename T, bool GN>
 __global__ __launch_bounds__(BLOCK) void k_backward2d(
     const T* __restrict__ rays_in, int64_t stride_in, const int32_t* __restrict__ n_ptr,
     const int32_t* __restrict__ ray_id_in, const int32_t* __restrict__ rec_prim,
@@ -703,8 +716,10 @@ __global__ __launch_bounds__(BLOCK) void k_backward2d(
       double n_in = 1.0, n_out = 1.0, gp[5];
       if (has_child) prim_indices(sc, prim, rid, &n_in, &n_out);
       const double* pp = is_arc ? sc.arc + (int64_t)(prim - Ms) * 5 : sc.seg + (int64_t)prim * 4;
+      double gn[2];
       adjoint2d(s, e, pp, is_arc, rec_u[i], has_child, n_in, n_out, L, g_s, g_h, g_ce, gs, ge, gp,
-                sc.finite_tir_gradient != 0);
+                sc.finite_tir_gradient != 0, GN ? gn : nullptr);
+      if (GN && has_child) add_index_grads(sc, prim, gn);
       if (is_arc) {
         if (g_arc != nullptr)
           for (int q = 0; q < 5; ++q)
@@ -839,6 +854,14 @@ static bool scene2_ok(const tfrt_scene2d* sc) {
   return true;
 }
 
+// The reverse sweeps compile the index terms in only when a gradient of the per-primitive indices
+// is asked for, in "value" mode (n_table NULL): tfrt_scene2d.grad_{seg,arc}_n_{in,out}.
+static bool index_grads2d(const tfrt_scene2d* sc) {
+  if (sc->n_table != nullptr) return false;
+  return (sc->n_segments > 0 && (sc->grad_seg_n_in || sc->grad_seg_n_out)) ||
+         (sc->n_arcs > 0 && (sc->grad_arc_n_in || sc->grad_arc_n_out));
+}
+
 template <typename T>
 static int trace2d_forward_t(const void* src_rays, int64_t src_stride, int64_t N,
                              const tfrt_scene2d* sc, double L, double dead_len, int P, int dtype,
@@ -925,6 +948,7 @@ static int trace2d_backward_t(const void* src_rays, int64_t src_stride, int64_t 
   const uint8_t* rec_bin = reinterpret_cast<uint8_t*>(ws + lay.rec_bin);
   double* gbuf = reinterpret_cast<double*>(ws + lay.gbuf);
   const size_t n = N > 0 ? N : 1;
+  const bool gn = index_grads2d(sc);
   for (int p = P - 1; p >= 0; --p) {
     const T* rin = p == 0 ? static_cast<const T*>(src_rays) : rays_ws + (size_t)(p - 1) * 4 * n;
     const int64_t sin = p == 0 ? src_stride : (int64_t)n;
@@ -932,12 +956,15 @@ static int trace2d_backward_t(const void* src_rays, int64_t src_stride, int64_t 
     const double* g_child = (p == P - 1) ? nullptr : gbuf + (size_t)((p + 1) & 1) * 4 * n;
     double* g_out = (p == 0 && g_src != nullptr) ? g_src : gbuf + (size_t)(p & 1) * 4 * n;
     const int64_t out_stride = (p == 0 && g_src != nullptr) ? N : (int64_t)n;
-    hipLaunchKernelGGL((k_backward2d<T>), dim3(lay.nblk), dim3(BLOCK), 0, st, rin, sin, nrays + p,
-                       idin, rec_prim + (size_t)p * n, rec_u + (size_t)p * n,
-                       rec_bin + (size_t)p * n, rec_slot + (size_t)p * n,
-                       counts + (size_t)p * TFRT_COUNTS_PER_PASS, *sc, L, dead_len, g_child,
-                       (int64_t)n, g_fin, cap_fin, g_act, cap_act, g_stp, cap_stp, g_dead, cap_dead,
-                       g_out, out_stride, g_seg, g_arc);
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(lay.nblk), dim3(BLOCK), 0, st, rin, sin, nrays + p, idin,
+                         rec_prim + (size_t)p * n, rec_u + (size_t)p * n, rec_bin + (size_t)p * n,
+                         rec_slot + (size_t)p * n, counts + (size_t)p * TFRT_COUNTS_PER_PASS, *sc,
+                         L, dead_len, g_child, (int64_t)n, g_fin, cap_fin, g_act, cap_act, g_stp,
+                         cap_stp, g_dead, cap_dead, g_out, out_stride, g_seg, g_arc);
+    };
+    if (gn) launch(k_backward2d<T, true>);
+    else launch(k_backward2d<T, false>);
   }
   return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
 }
@@ -1100,7 +1127,39 @@ __device__ __forceinline__ void add_prim_grads(bool has, int prim, const double 
   }
 }
 
-template <typename T, typename Seed>
+// add_prim_grads for the index gradients gn = {d / d n_in, d / d n_out} of the lanes with `has`
+// set (tfrt_scene2d.grad_{seg,arc}_n_{in,out}, those given).  Called by all 64 lanes.
+__device__ __forceinline__ void add_prim_index_grads(bool has, int prim, const double gn[2],
+                                                     const tfrt_scene2d& sc) {
+  const int Ms = (int)sc.n_segments;
+  unsigned long long todo = __ballot(has);
+  while (todo) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const int key = __shfl(prim, leader, 64);
+    const bool mine = has && prim == key;
+    const unsigned long long grp = __ballot(mine);
+    const bool is_arc = key >= Ms;
+    const int k = is_arc ? key - Ms : key;
+    double* const rows[2] = {is_arc ? sc.grad_arc_n_in : sc.grad_seg_n_in,
+                             is_arc ? sc.grad_arc_n_out : sc.grad_seg_n_out};
+    const bool single = __popcll(grp) == 1;
+    for (int q = 0; q < 2; ++q) {
+      if (rows[q] == nullptr) continue;
+      if (single) {
+        if (mine && gn[q] != 0.0) unsafeAtomicAdd(rows[q] + k, gn[q]);
+      } else {
+        double v = mine ? gn[q] : 0.0;
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+        if ((int)lane_id() == leader && v != 0.0) unsafeAtomicAdd(rows[q] + k, v);
+      }
+    }
+    has = has && !mine;
+    todo &= ~grp;
+  }
+}
+
+template <typename T, typename Seed, bool GN>
 __global__ __launch_bounds__(BLOCK) void k_backward2d_goal(
     const T* __restrict__ src, int64_t src_stride, int N, const T* __restrict__ rays_ws,
     int64_t n, const int32_t* __restrict__ rec_prim, const double* __restrict__ rec_u,
@@ -1135,6 +1194,7 @@ __global__ __launch_bounds__(BLOCK) void k_backward2d_goal(
     bool has = false;
     int prim = -1;
     double gp[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    double gn[2] = {0.0, 0.0};
     if (p >= 0) {
       if (p < lo) {                   // past the ring: re-walk the tape for links [lo, p]
         lo = max(0, p - CHAIN2 + 1);
@@ -1173,7 +1233,7 @@ __global__ __launch_bounds__(BLOCK) void k_backward2d_goal(
         if (has_child) prim_indices(sc, prim, i, &n_in, &n_out);
         const double* pp = is_arc ? sc.arc + (int64_t)(prim - Ms) * 5 : sc.seg + (int64_t)prim * 4;
         adjoint2d(s, e, pp, is_arc, rec_u[(size_t)p * n + idx], has_child, n_in, n_out, L, g_s,
-                  g_h, g_ce, gs, ge, gp, sc.finite_tir_gradient != 0);
+                  g_h, g_ce, gs, ge, gp, sc.finite_tir_gradient != 0, GN ? gn : nullptr);
         has = true;
       }
       for (int k = 0; k < 2; ++k) {
@@ -1183,6 +1243,7 @@ __global__ __launch_bounds__(BLOCK) void k_backward2d_goal(
       --p;
     }
     add_prim_grads(has, prim, gp, Ms, g_seg, g_arc);
+    if (GN) add_prim_index_grads(has, prim, gn, sc);
   }
 }
 
@@ -1197,14 +1258,18 @@ static int trace2d_backward_goal_t(const void* src_rays, int64_t src_stride, int
   if (N == 0) return 0;
   char* ws = static_cast<char*>(workspace);
   const size_t n = N;
-  hipLaunchKernelGGL((k_backward2d_goal<T, Seed>), dim3(cdiv(N, BLOCK)), dim3(BLOCK), 0, st,
-                     static_cast<const T*>(src_rays), src_stride, (int)N,
-                     reinterpret_cast<const T*>(ws + lay.rays), (int64_t)n,
-                     reinterpret_cast<const int32_t*>(ws + lay.rec_prim),
-                     reinterpret_cast<const double*>(ws + lay.rec_u),
-                     reinterpret_cast<const uint8_t*>(ws + lay.rec_bin),
-                     reinterpret_cast<const int32_t*>(ws + lay.rec_slot), P, *sc, L, fin, seed,
-                     g_seg, g_arc);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(cdiv(N, BLOCK)), dim3(BLOCK), 0, st,
+                       static_cast<const T*>(src_rays), src_stride, (int)N,
+                       reinterpret_cast<const T*>(ws + lay.rays), (int64_t)n,
+                       reinterpret_cast<const int32_t*>(ws + lay.rec_prim),
+                       reinterpret_cast<const double*>(ws + lay.rec_u),
+                       reinterpret_cast<const uint8_t*>(ws + lay.rec_bin),
+                       reinterpret_cast<const int32_t*>(ws + lay.rec_slot), P, *sc, L, fin, seed,
+                       g_seg, g_arc);
+  };
+  if (index_grads2d(sc)) launch(k_backward2d_goal<T, Seed, true>);
+  else launch(k_backward2d_goal<T, Seed, false>);
   return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
 }
 

@@ -180,15 +180,22 @@ TFRT_HD double segment_norm(const double seg[4]) {
 // whatever the upstream gradient (zero included), so theta1 -- i.e. the norm angle and the ray
 // angle -- receive NaN and with them the boundary entries and the parent ray.  Reproduced unless
 // finite_tir (tfrt_scene2d.finite_tir_gradient): then the reflect branch's own gradient.
+//   gn (optional, "value" mode): {d / d n_in, d / d n_out} of the link's primitive.  The refract
+// branch gives d newa / d n = -sin(th1e) / sqrt(1 - th2^2), carried through the "safe" ratio
+// n = n_in / n_out (internal) or n_out / n_in (external); an index that is zero was replaced by
+// 1 there and gets nothing.  Reflect / mirror: 0, or NaN as above.  NULL: not asked for (the
+// arithmetic of every other output is the same either way).
 TFRT_HD void adjoint2d(const double s[2], const double e[2], const double* prim, bool is_arc,
                        double u, bool has_child, double n_in, double n_out, double L,
                        const double g_s[2], const double g_h[2], const double g_ce[2],
-                       double gs[2], double ge[2], double gprim[5], bool finite_tir = false) {
+                       double gs[2], double ge[2], double gprim[5], bool finite_tir = false,
+                       double* gn = nullptr) {
   const double d[2] = {e[0] - s[0], e[1] - s[1]};
   const double h[2] = {s[0] + u * d[0], s[1] + u * d[1]};
   double hb[2] = {g_h[0], g_h[1]};
   double sb[2] = {g_s[0], g_s[1]};
   for (int i = 0; i < 5; ++i) gprim[i] = 0.0;
+  if (gn != nullptr) gn[0] = gn[1] = 0.0;
   double normb = 0.0;  // gradient on the surface-normal angle
 
   if (has_child) {
@@ -228,6 +235,21 @@ TFRT_HD void adjoint2d(const double s[2], const double e[2], const double* prim,
     } else {  // (mirror, n == 0: theta2 = 0 and asin's unselected gradient is a plain 0)
       normb = newb * 2.0;
       rab = -newb;
+    }
+    if (gn != nullptr) {
+      // d error / d n (snells_law_2D: new_angle = norm - asin(n sin(theta1)) when refracted)
+      double nb = 0.0;
+      if (refr) nb = -newb / sqrt(1.0 - th2 * th2) * sin(th1e);
+      else if (fabs(th2) > 1.0 && !finite_tir) nb = __builtin_nan("");
+      if (internal) {          // n = n_in / n_out, 0 when n_out == 0
+        if (out_safe) {
+          if (in_safe) gn[0] = nb / nos;
+          gn[1] = -nb * (n / nos);
+        }
+      } else if (in_safe) {    // n = n_out / n_in, 0 when n_in == 0
+        if (out_safe) gn[1] = nb / nis;
+        gn[0] = -nb * (n / nis);
+      }
     }
     // ray_angle = atan2(s.y - h.y, s.x - h.x)
     const double qx = s[0] - h[0], qy = s[1] - h[1];

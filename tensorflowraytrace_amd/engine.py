@@ -313,6 +313,21 @@ def _prop(name):
     return property(lambda self: self._get_set(name), lambda self, new: self._set_set(name, new))
 
 
+def _live(v):
+    """A material field that takes a gradient (a refractive index being optimised)."""
+    return isinstance(v, torch.Tensor) and v.requires_grad
+
+
+def _field_key(v):
+    """A material field in the keys of the merged columns and of a captured step: identity and
+    version; a field that takes a gradient changes in place every step -- identity only --, or is
+    made by every update() from a parameter (a scalar broadcast) -- nothing: it is merged again by
+    every update() anyway."""
+    if not _live(v):
+        return (id(v), v._version)
+    return (id(v) if v.is_leaf else None, None)
+
+
 class OpticalSystem3D(OpticalSystemBase):
     """engine.py:871-1166."""
 
@@ -378,25 +393,35 @@ class OpticalSystem3D(OpticalSystemBase):
         else:
             self._merged_face_verts = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
         self._merged = _MergedTriangles(self)
+        # (a material field that takes a gradient -- a refractive index of StandardReaction("value")
+        # being optimised -- changes in place every step: it is keyed by identity alone and merged
+        # again by every update(), into the same column, see below)
         key = tuple((c, n, id(b)) + tuple(
-            (id(b[f]), b[f]._version) for f in ("mat_in", "mat_out", "n_in", "n_out") if f in b)
+            _field_key(b[f]) for f in ("mat_in", "mat_out", "n_in", "n_out") if f in b)
             for c, n, b in cats) + (tuple(grads),)
-        if self._scene_cache is None or self._scene_cache[0] != key:
-            dev = self._merged_face_verts.device
-            catagory = torch.cat([torch.full((n,), c, dtype=torch.int32) for c, n, _ in cats]).to(dev)
+        dev = self._merged_face_verts.device
+        from . import boundaries
 
-            def col(field, dtype):
-                if not any(c == OPTICAL and field in b for c, n, b in cats):
-                    return None
-                out = []
-                for c, n, b in cats:
-                    if c == OPTICAL and field in b:
-                        out.append(b[field].to(device=dev, dtype=dtype).reshape(-1))
-                    elif c == OPTICAL:
-                        raise KeyError(f"optical boundary lacks field {field}")
-                    else:
-                        out.append(torch.zeros(n, dtype=dtype, device=dev))
-                return torch.cat(out).contiguous()
+        def col(field, dtype):
+            if not any(c == OPTICAL and field in b for c, n, b in cats):
+                return None
+            out = []
+            for c, n, b in cats:
+                if c == OPTICAL and field in b:
+                    v = b[field]
+                    # (read through boundaries.tap inside a fused step's update())
+                    v = boundaries.tap(v) if _live(v) and v.is_leaf else v
+                    out.append(v.to(device=dev, dtype=dtype).reshape(-1))
+                elif c == OPTICAL:
+                    raise KeyError(f"optical boundary lacks field {field}")
+                else:
+                    out.append(torch.zeros(n, dtype=dtype, device=dev))
+            return torch.cat(out).contiguous()
+
+        live = [f for f in ("n_in", "n_out")
+                if any(c == OPTICAL and f in b and _live(b[f]) for c, n, b in cats)]
+        if self._scene_cache is None or self._scene_cache[0] != key:
+            catagory = torch.cat([torch.full((n,), c, dtype=torch.int32) for c, n, _ in cats]).to(dev)
 
             gmask = torch.cat([torch.full((n,), 1 if g else 0, dtype=torch.uint8)
                                for (c, n, _), g in zip(cats, grads)]).to(dev)
@@ -408,6 +433,17 @@ class OpticalSystem3D(OpticalSystemBase):
                 catagory=catagory, mat_in=col("mat_in", torch.int32),
                 mat_out=col("mat_out", torch.int32), n_in=col("n_in", torch.float64),
                 n_out=col("n_out", torch.float64), face_grad_mask=gmask), held)
+            for f in live:     # the kernels read a column that stays put; autograd reads `live`
+                self._scene_cache[1][f] = self._scene_cache[1][f].detach().clone()
+        # The merged index columns that take a gradient, made from the current values: copied into
+        # the cached column (inside a captured update() too) and kept for autograd (Scene3DArgs.
+        # n_in_arg / n_out_arg) -- d error / d index reaches the parameter through them.
+        self._live_index = {}
+        for f in live:
+            merged = col(f, torch.float64)
+            with torch.no_grad():
+                self._scene_cache[1][f].copy_(merged)
+            self._live_index[f] = merged
 
     def scene_signature(self):
         """What a captured launch sequence has baked in about the scene besides the face tensor:
@@ -417,8 +453,7 @@ class OpticalSystem3D(OpticalSystemBase):
         for name in ("_optical", "_stop", "_target"):
             for b in getattr(self, name):
                 sig.append((id(b),) + tuple(
-                    (id(b[f]), b[f]._version) for f in ("mat_in", "mat_out", "n_in", "n_out")
-                    if f in b))
+                    _field_key(b[f]) for f in ("mat_in", "mat_out", "n_in", "n_out") if f in b))
         return (tuple(sig), self.intersect_epsilion, self.size_epsilion,
                 self.ray_start_epsilion, tuple(id(m) for m in self.materials))
 
@@ -446,10 +481,16 @@ class OpticalSystem3D(OpticalSystemBase):
                     self.intersect_epsilion, self.size_epsilion, self.ray_start_epsilion)
         memo = getattr(self, "_scene_args_memo", None)
         if memo is not None and memo[0] == memo_key:
-            memo[1].face_verts = self._merged_face_verts
-            return memo[1]
-        args = self._build_scene_args(s, n_table, index_mode, ghost, kw)
-        self._scene_args_memo = (memo_key, args, s, n_table, order)  # keep the ids alive
+            args = memo[1]
+            args.face_verts = self._merged_face_verts
+        else:
+            args = self._build_scene_args(s, n_table, index_mode, ghost, kw)
+            self._scene_args_memo = (memo_key, args, s, n_table, order)  # keep the ids alive
+        if not (ghost or index_mode):
+            # "value" mode: the indices that take a gradient as this update() merged them
+            live = getattr(self, "_live_index", {})
+            args.n_in_arg = live.get("n_in", s["n_in"])
+            args.n_out_arg = live.get("n_out", s["n_out"])
         return args
 
     def _build_scene_args(self, s, n_table, index_mode, ghost, kw):

@@ -302,12 +302,14 @@ class FusedStep:
                 and not getattr(eng, "_rowwise_off", False))
 
     # -------------------------------------------------------------------------- buffers
-    def _buffers(self, block, fv, P, flags, dt):
-        """Persistent outputs / tape / seeds of the trace for this (N, M, P, dtype, flags)."""
+    def _buffers(self, block, fv, P, flags, dt, index=False):
+        """Persistent outputs / tape / seeds of the trace for this (N, M, P, dtype, flags);
+        ``index``: the (2, M) block of d error / d (n_in, n_out) too."""
         N, M = block.shape[1], fv.shape[0]
         # (the error function's rows are baked into `fields` and into which rows of g_fin are
         # ever written: another GoalError gets fresh, zeroed buffers)
-        sig = (N, M, P, dt, flags, str(block.device), tuple(self.opt.error_function.rows))
+        sig = (N, M, P, dt, flags, str(block.device), tuple(self.opt.error_function.rows),
+               bool(index))
         st = self._state
         if st is not None and st["sig"] == sig:
             return st
@@ -337,6 +339,7 @@ class FusedStep:
             counts=ints.counts, ints=ints,
             g_fin=torch.zeros((6, capN), dtype=torch.float64, device=dev),
             g_fv=torch.zeros((max(M, 1), 9), dtype=torch.float64, device=dev),
+            g_n=torch.zeros((2, max(M, 1)), dtype=torch.float64, device=dev) if index else None,
             err=torch.zeros(3, dtype=torch.float64, device=dev),
             goal_ws=torch.zeros(max(gws, 1), dtype=torch.uint8, device=dev), gws=gws,
             fields=(ctypes.c_int32 * 6)(*(self.opt.error_function.rows + [0] * 6)[:6]),
@@ -394,7 +397,8 @@ class FusedStep:
         fvc = fv.detach()
         if fvc.dtype != torch.float64 or not fvc.is_contiguous():
             raise RuntimeError("FusedStep: merged faces must be contiguous float64")
-        st = self._buffers(block, fvc, P, flags, dt)
+        index = self._index3d(scene, fvc)
+        st = self._buffers(block, fvc, P, flags, dt, any(n is not None for n in index))
         sink = getattr(self, "_err_sink", None)
         if tdist.is_distributed() and sink is not None and st["err"].data_ptr() != sink.data_ptr():
             st["err"] = sink             # (the error sums land in the collective's buffer)
@@ -402,7 +406,9 @@ class FusedStep:
         stream = ops._stream(block)
         sc = scene.struct(fvc)
         o = st["outs"]
-        need_back = bool(fv.requires_grad and st["M"] > 0)
+        # (the reverse sweep runs for the faces or the indices; it is given the face-gradient block
+        # either way: the in-place chain sums its face terms per wavefront into it)
+        need_back = bool((fv.requires_grad or st["g_n"] is not None) and st["M"] > 0)
         # coherent rays: error, gradient seed and the whole reverse sweep are ONE launch
         # (tfrt_trace3d_backward_goal); the face-gradient block it accumulates into is cleared by
         # the trace's set-up launch
@@ -443,6 +449,22 @@ class FusedStep:
             st["g_fv"].numel() if need_back else 0, ops._p(self.tests_total),
             ops._p(st["goal_ws"]), st["gws"])
         self._goal_pending = None
+        self._set_index_grads3d(sc, st, need_back)
+        try:
+            grads = self._backward3d(st, sc, block, goal, goal_by_ray, goal_args, folded, need_back,
+                                     erf, P, dt, stream, L, eng, fv, index, tap_log)
+        finally:
+            self._set_index_grads3d(sc, st, False)
+        self._publish_lazily(st, src, P, flags, perm, (block, float(eng.dead_ray_length or 0.0))
+                             if inplace else None)
+        # (publish() inverts `perm` when it runs: a replayed graph re-orders a re-drawn source into
+        # the same tensor behind Python's back)
+        return grads, st["err"]
+
+    def _backward3d(self, st, sc, block, goal, goal_by_ray, goal_args, folded, need_back, erf, P,
+                    dt, stream, L, eng, fv, index, tap_log):
+        """Error, seed and reverse sweep of _enqueue_gradient, then the parameter gradients."""
+        o = st["outs"]
         if folded:
             if "chain_ws" not in st:
                 cwb = L.tfrt_trace3d_backward_goal_workspace_bytes(st["N"])
@@ -468,7 +490,7 @@ class FusedStep:
             check(L.tfrt_goal_error3d_deferred(*goal_args, ctypes.byref(pending), stream),
                   "tfrt_goal_error3d_deferred")
             self._goal_pending = (pending, stream)
-        grads = [None] * len(opt.parameters)
+        grads = [None] * len(self.opt.parameters)
         if need_back:
             if not folded:
                 check(L.tfrt_trace3d_backward(
@@ -477,12 +499,38 @@ class FusedStep:
                     ops._p(st["g_fin"]), st["capN"], None, 0, None, 0, None, 0, ops._p(st["g_fv"]),
                     None, ops._p(st["counts"]), ops._p(st["ws"]), st["wsb"], stream),
                     "tfrt_trace3d_backward")
-            grads = self._parameter_gradients([fv], [st["g_fv"]], tap_log)
-        self._publish_lazily(st, src, P, flags, perm, (block, float(eng.dead_ray_length or 0.0))
-                             if inplace else None)
-        # (publish() inverts `perm` when it runs: a replayed graph re-orders a re-drawn source into
-        # the same tensor behind Python's back)
-        return grads, st["err"]
+            grads = self._parameter_gradients(*self._outs3d(fv, st, index), tap_log)
+        return grads
+
+    @staticmethod
+    def _index3d(scene, fvc):
+        """(n_in, n_out) of "value" mode when they take a gradient (the merged columns update()
+        made, Scene3DArgs.n_in_arg / n_out_arg), None where not."""
+        if scene.n_table is not None or fvc.shape[0] == 0:
+            return (None, None)
+        return tuple(n if isinstance(n, torch.Tensor) and n.requires_grad else None
+                     for n in (scene.n_in_arg, scene.n_out_arg))
+
+    @staticmethod
+    def _outs3d(fv, st, index):
+        """What the parameter gradients are taken from: the faces and the indices that take one."""
+        outs, g_outs = ([fv], [st["g_fv"]]) if fv.requires_grad else ([], [])
+        for k, n in enumerate(index):
+            if n is not None:
+                outs.append(n)
+                g_outs.append(st["g_n"][k, :n.shape[0]])
+        return outs, g_outs
+
+    @staticmethod
+    def _set_index_grads3d(sc, st, on):
+        """Points tfrt_scene3d.grad_n_in / grad_n_out at the step's index block (cleared here, in
+        the captured sequence) or clears them: the struct is cached by the scene."""
+        g = st["g_n"]
+        if on and g is not None:
+            g.zero_()
+            sc.grad_n_in, sc.grad_n_out = g[0].data_ptr(), g[1].data_ptr()
+        else:
+            sc.grad_n_in = sc.grad_n_out = None
 
     def _parameter_gradients(self, outs, g_outs, tap_log):
         """d error / d parameters from d error / d geometry (``g_outs``: the faces' gradient in 3-D,
@@ -548,7 +596,8 @@ class FusedStep:
         fvc = fv.detach()
         if fvc.dtype != torch.float64 or not fvc.is_contiguous():
             raise RuntimeError("FusedStep: merged faces must be contiguous float64")
-        st = self._buffers(block, fvc, P, flags, dt)
+        index = self._index3d(scene, fvc)
+        st = self._buffers(block, fvc, P, flags, dt, any(n is not None for n in index))
         N, M, dev = st["N"], st["M"], block.device
         L = _lib.lib()
         stream = ops._stream(block)
@@ -562,7 +611,7 @@ class FusedStep:
             st["row_face"] = torch.full((st["capN"],), -1, dtype=torch.int32, device=dev)
             st["row_passes"] = torch.zeros(st["capN"], dtype=torch.int32, device=dev)
             st["row_out"] = ops._ray_out(st["rows"], st["row_passes"], st["row_face"])
-        need_back = bool(fv.requires_grad and M > 0)
+        need_back = bool((fv.requires_grad or st["g_n"] is not None) and M > 0)
         self.folded_backward, self.in_place = False, True
         sc.in_place = 2
         if need_back:
@@ -610,27 +659,31 @@ class FusedStep:
                 with torch.autograd.set_multithreading_enabled(False):
                     g_rows, = torch.autograd.grad(err_sum, [leaf])
                 g64 = g_rows.to(torch.float64).contiguous()
+                self._set_index_grads3d(sc, st, True)
                 check(L.tfrt_trace3d_backward(
                     ops._p(block), block.shape[1], N, ctypes.byref(sc), float(eng.new_ray_length),
                     float(eng.dead_ray_length or 0.0), P, dt, ops._p(g64), g64.shape[1], None, 0,
                     None, 0, None, 0, ops._p(st["g_fv"]), None, ops._p(st["counts"]),
                     ops._p(st["ws"]), st["wsb"], stream), "tfrt_trace3d_backward")
-                grads = self._parameter_gradients([fv], [st["g_fv"]], tap_log)
+                grads = self._parameter_gradients(*self._outs3d(fv, st, index), tap_log)
         finally:
             sc.in_place = 1 if scene.in_place else 0      # (the struct is cached by the scene)
             sc.clear_buffer, sc.clear_count = None, 0
+            self._set_index_grads3d(sc, st, False)
         self._goal_pending = None
         self._publish_lazily(st, src, P, flags, perm, (block, float(eng.dead_ray_length or 0.0)))
         return grads, st["err"]
 
     # ------------------------------------------------------------------------------ 2-D
-    def _buffers2d(self, block, seg, arc, P, flags, dt, rows, rowwise=False):
+    def _buffers2d(self, block, seg, arc, P, flags, dt, rows, rowwise=False, index=()):
         """Persistent outputs / tape / gradient blocks of a 2-D trace for this (N, Ms, Ma, P,
-        dtype, flags, fields); with ``rowwise`` also the fixed-shape columns of a RowwiseError."""
+        dtype, flags, fields); with ``rowwise`` also the fixed-shape columns of a RowwiseError.
+        ``index``: which of (seg_n_in, seg_n_out, arc_n_in, arc_n_out) take a gradient."""
         N = block.shape[1]
         Ms = 0 if seg is None else seg.shape[0]
         Ma = 0 if arc is None else arc.shape[0]
-        sig = (2, N, Ms, Ma, P, dt, flags, str(block.device), tuple(rows), bool(rowwise))
+        index = tuple(bool(i) for i in index) or (False,) * 4
+        sig = (2, N, Ms, Ma, P, dt, flags, str(block.device), tuple(rows), bool(rowwise), index)
         st = self._state
         if st is not None and st["sig"] == sig:
             return st
@@ -653,12 +706,20 @@ class FusedStep:
         aux["unfinished"] = torch.empty((4, 0), dtype=block.dtype, device=dev)
         aux["unfinished_id"] = torch.empty(0, dtype=torch.int32, device=dev)
         gws = L.tfrt_trace2d_backward_goal_workspace_bytes(N)
-        # (segment and arc gradients in one block: one clearing launch per step)
-        g_prim = torch.zeros(max(4 * Ms + 5 * Ma, 1), dtype=torch.float64, device=dev)
+        # (segment and arc gradients in one block, the index gradients asked for behind them: one
+        # clearing launch per step)
+        n_index = 2 * (Ms + Ma) if any(index) else 0
+        at = 4 * Ms + 5 * Ma
+        g_prim = torch.zeros(max(at + n_index, 1), dtype=torch.float64, device=dev)
+        g_index = [None] * 4
+        if n_index:
+            g_index = [g_prim[at:at + Ms], g_prim[at + Ms:at + 2 * Ms],
+                       g_prim[at + 2 * Ms:at + 2 * Ms + Ma], g_prim[at + 2 * Ms + Ma:at + n_index]]
+            g_index = [g if want else None for g, want in zip(g_index, index)]
         st = dict(
             sig=sig, dim=2, N=N, Ms=Ms, Ma=Ma, P=P, dt=dt, flags=flags, capN=capN, full=full,
             aux=aux, outs=outs, ws=torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev),
-            wsb=wsb, counts=ints.counts, ints=ints, g_prim=g_prim,
+            wsb=wsb, counts=ints.counts, ints=ints, g_prim=g_prim, g_index=g_index,
             g_seg=g_prim[:4 * Ms].view(Ms, 4), g_arc=g_prim[4 * Ms:4 * Ms + 5 * Ma].view(Ma, 5),
             err=torch.zeros(3, dtype=torch.float64, device=dev),
             goal_ws=torch.zeros(max(gws, 1), dtype=torch.uint8, device=dev), gws=gws,
@@ -697,7 +758,9 @@ class FusedStep:
         P, flags = int(opt.trace_depth), eng._flags() | _lib.COMPILE_FINISHED
         dt = ops._DT[block.dtype]
         geo, det = self._geometry2d(scene)
-        st = self._buffers2d(block, det[0], det[1], P, flags, dt, rows)
+        index = self._index2d(scene)
+        st = self._buffers2d(block, det[0], det[1], P, flags, dt, rows,
+                             index=[i is not None for i in index])
         L = _lib.lib()
         stream = ops._stream(block)
         sc = scene.struct(det[0], det[1])
@@ -710,18 +773,23 @@ class FusedStep:
             ops._p(st["counts"]), ops._p(st["ws"]), st["wsb"], stream), "tfrt_trace2d_forward")
         back = [(g, grad) for g, grad in zip(geo, (st["g_seg"], st["g_arc"]))
                 if g is not None and g.requires_grad and g.shape[0] > 0]
+        back += [(n, g) for n, g in zip(index, st["g_index"]) if n is not None]
         if back:
             st["g_prim"].zero_()
         pending = _lib.GoalPending()
-        check(L.tfrt_trace2d_backward_goal(
-            ops._p(block), block.shape[1], st["N"], ctypes.byref(sc), float(eng.new_ray_length),
-            P, dt, ctypes.byref(o["finished"]), st["fields"], len(rows), ops._p(goal),
-            goal.shape[1], 1, ops._p(st["err"]), ops._p(self.tests_total), ops._p(st["goal_ws"]),
-            st["gws"], ctypes.byref(pending),
-            ops._p(st["g_seg"]) if back and st["Ms"] else None,
-            ops._p(st["g_arc"]) if back and st["Ma"] else None,
-            ops._p(st["counts"]), ops._p(st["ws"]), st["wsb"], stream),
-            "tfrt_trace2d_backward_goal")
+        self._set_index_grads(sc, st, bool(back))
+        try:
+            check(L.tfrt_trace2d_backward_goal(
+                ops._p(block), block.shape[1], st["N"], ctypes.byref(sc), float(eng.new_ray_length),
+                P, dt, ctypes.byref(o["finished"]), st["fields"], len(rows), ops._p(goal),
+                goal.shape[1], 1, ops._p(st["err"]), ops._p(self.tests_total),
+                ops._p(st["goal_ws"]), st["gws"], ctypes.byref(pending),
+                ops._p(st["g_seg"]) if back and st["Ms"] else None,
+                ops._p(st["g_arc"]) if back and st["Ma"] else None,
+                ops._p(st["counts"]), ops._p(st["ws"]), st["wsb"], stream),
+                "tfrt_trace2d_backward_goal")
+        finally:
+            self._set_index_grads(sc, st, False)
         # (nothing on the device waits for the error sum: the parameter update's launch finishes it)
         self._goal_pending = (pending, stream)
         self.folded_backward, self.in_place = True, False
@@ -730,6 +798,19 @@ class FusedStep:
             grads = self._parameter_gradients([b[0] for b in back], [b[1] for b in back], tap_log)
         self._publish_lazily2d(st, src)
         return grads, st["err"]
+
+    @staticmethod
+    def _index2d(scene):
+        """The per-primitive indices of "value" mode that take a gradient (seg_n_in, seg_n_out,
+        arc_n_in, arc_n_out; None where not), as merged by update() from the boundaries' fields."""
+        return [n if isinstance(n, torch.Tensor) and n.requires_grad and n.shape[0] > 0 else None
+                for n in scene.index_args()]
+
+    @staticmethod
+    def _set_index_grads(sc, st, on):
+        """Points the 2-D scene struct's index-gradient fields at this step's blocks (or clears them)."""
+        for name, g in zip(ops._GRAD_INDEX_2D, st["g_index"]):
+            setattr(sc, name, g.data_ptr() if (on and g is not None) else None)
 
     @staticmethod
     def _geometry2d(scene):
@@ -751,7 +832,9 @@ class FusedStep:
         P, flags = int(opt.trace_depth), eng._flags() | _lib.COMPILE_FINISHED
         dt = ops._DT[block.dtype]
         geo, det = self._geometry2d(scene)
-        st = self._buffers2d(block, det[0], det[1], P, flags, dt, (), rowwise=True)
+        index = self._index2d(scene)
+        st = self._buffers2d(block, det[0], det[1], P, flags, dt, (), rowwise=True,
+                             index=[i is not None for i in index])
         N = st["N"]
         L = _lib.lib()
         stream = ops._stream(block)
@@ -784,6 +867,7 @@ class FusedStep:
         # formed by the sweep's launch and finished by the parameter update's, as for a GoalError
         back = [(g, grad) for g, grad in zip(geo, (st["g_seg"], st["g_arc"]))
                 if g is not None and g.requires_grad and g.shape[0] > 0]
+        back += [(n, g) for n, g in zip(index, st["g_index"]) if n is not None]
         g64 = None
         if back and e.requires_grad:
             mask = (st["row_face"][:N] >= 0).unsqueeze(1).expand_as(e).double()
@@ -793,16 +877,20 @@ class FusedStep:
             st["g_prim"].zero_()
         e = e.detach().contiguous()
         pending = _lib.GoalPending()
-        check(L.tfrt_trace2d_backward_rows(
-            ops._p(block), block.shape[1], N, ctypes.byref(sc), float(eng.new_ray_length), P, dt,
-            ctypes.byref(o["finished"]), ops._p(e), e.shape[1], 1, e.shape[1],
-            None if g64 is None else ops._p(g64), 0 if g64 is None else g64.shape[1],
-            ops._p(st["err"]), ops._p(self.tests_total), ops._p(st["goal_ws"]), st["gws"],
-            ctypes.byref(pending),
-            ops._p(st["g_seg"]) if g64 is not None and st["Ms"] else None,
-            ops._p(st["g_arc"]) if g64 is not None and st["Ma"] else None,
-            ops._p(st["counts"]), ops._p(st["ws"]), st["wsb"], stream),
-            "tfrt_trace2d_backward_rows")
+        self._set_index_grads(sc, st, g64 is not None)
+        try:
+            check(L.tfrt_trace2d_backward_rows(
+                ops._p(block), block.shape[1], N, ctypes.byref(sc), float(eng.new_ray_length), P,
+                dt, ctypes.byref(o["finished"]), ops._p(e), e.shape[1], 1, e.shape[1],
+                None if g64 is None else ops._p(g64), 0 if g64 is None else g64.shape[1],
+                ops._p(st["err"]), ops._p(self.tests_total), ops._p(st["goal_ws"]), st["gws"],
+                ctypes.byref(pending),
+                ops._p(st["g_seg"]) if g64 is not None and st["Ms"] else None,
+                ops._p(st["g_arc"]) if g64 is not None and st["Ma"] else None,
+                ops._p(st["counts"]), ops._p(st["ws"]), st["wsb"], stream),
+                "tfrt_trace2d_backward_rows")
+        finally:
+            self._set_index_grads(sc, st, False)
         # (nothing on the device waits for the error sum: the parameter update's launch finishes it)
         self._goal_pending = (pending, stream)
         self.folded_backward, self.in_place = False, False
@@ -1041,7 +1129,25 @@ class FusedStep:
                 id((getattr(eng, "_order_cache", None) or (None, None, None))[2]),
                 getattr(eng, "_visit_all_key", None) is not None, eng.in_place,
                 bool(opt.apply_momentum),
-                tuple(v.data_ptr() for v in opt._velocity) if opt.apply_momentum else ())
+                tuple(v.data_ptr() for v in opt._velocity) if opt.apply_momentum else (),
+                self._index_signature())
+
+    def _index_signature(self):
+        """The refractive-index fields that take a gradient (boundary, field, identity of a tensor
+        the caller gave).  Their values change in place every step -- a captured update() merges
+        them by address --; another tensor, or an index that starts or stops taking a gradient,
+        changes the sequence.  (A field update() computes, e.g. a scalar broadcast from a
+        material_dict entry, is made inside the captured update(): its identity does not count.)"""
+        system = self.opt.engine.optical_system
+        sig = []
+        for name in system._boundary_sets:
+            for b in getattr(system, "_" + name):
+                fields = getattr(b, "_fields", {})
+                for f in ("n_in", "n_out"):
+                    v = fields.get(f)
+                    if isinstance(v, torch.Tensor) and v.requires_grad:
+                        sig.append((id(b), f, id(v) if v.is_leaf else None))
+        return tuple(sig)
 
     def step(self, accumulators, lr_scale):
         """One optimiser step.  Returns the error tensor {sum, n_terms, mean} (device)."""

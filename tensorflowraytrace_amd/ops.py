@@ -1421,6 +1421,7 @@ class Scene2DArgs:
 
         fill("seg", self.segments, seg_geo, "n_segments")
         fill("arc", self.arcs, arc_geo, "n_arcs")
+        sc.grad_seg_n_in = sc.grad_seg_n_out = sc.grad_arc_n_in = sc.grad_arc_n_out = None
         if self.n_table is not None and self.n_table.numel() and self.index_mode and not self.ghost:
             sc.n_table = self.n_table.data_ptr()
             sc.n_table_stride = self.n_table.shape[1]
@@ -1431,10 +1432,23 @@ class Scene2DArgs:
         sc.finite_tir_gradient = 1 if self.finite_tir_gradient else 0
         return sc
 
+    def index_args(self):
+        """"value" mode: the per-primitive indices as handed in (seg_n_in, seg_n_out, arc_n_in,
+        arc_n_out; they may require grad: d error / d index), None where absent or not read."""
+        if self.ghost or self.index_mode:
+            return (None,) * 4
+        return tuple(None if info is None else info.get(f) for info in (self.segments, self.arcs)
+                     for f in ("n_in", "n_out"))
+
+
+_GRAD_INDEX_2D = ("grad_seg_n_in", "grad_seg_n_out", "grad_arc_n_in", "grad_arc_n_out")
+
 
 class _Trace2D(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, src, seg_geo, arc_geo, scene, opts):
+    def forward(ctx, src, seg_geo, arc_geo, seg_n_in, seg_n_out, arc_n_in, arc_n_out, scene, opts):
+        # (the index tensors: the per-primitive indices of "value" mode when they require grad --
+        # the values are read through `scene`; listing them here gives their gradients a place to go)
         _need_gpu(src, seg_geo, arc_geo)
         dev = src.device
         if src.dtype not in _DT:
@@ -1503,16 +1517,25 @@ class _Trace2D(torch.autograd.Function):
         g_src = torch.zeros((4, t.src.shape[1]), dtype=torch.float64, device=dev) if need_src else None
         gs = _class_grads(ctx.present, t.caps, 4, dev, grads)
         sc = t.scene.struct(t.seg, t.arc)
-        check(_lib.lib().tfrt_trace2d_backward(
-            _p(t.src), t.src.shape[1], t.src.shape[1], ctypes.byref(sc),
-            float(t.opts["new_ray_length"]), float(t.opts["dead_ray_length"] or 0.0),
-            int(t.opts["max_passes"]), t.dt,
-            _p(gs[0]), t.caps[0], _p(gs[1]), t.caps[1], _p(gs[2]), t.caps[2], _p(gs[3]), t.caps[3],
-            _p(g_seg), _p(g_arc), _p(g_src), _p(t.counts), _p(t.ws), t.wsb, _stream(t.src)),
-            "tfrt_trace2d_backward")
+        sizes = [0 if g is None else g.shape[0] for g in (t.seg, t.seg, t.arc, t.arc)]
+        g_n = [torch.zeros(m, dtype=torch.float64, device=dev) if ctx.needs_input_grad[3 + k] and m
+               else None for k, m in enumerate(sizes)]
+        for name, g in zip(_GRAD_INDEX_2D, g_n):
+            setattr(sc, name, None if g is None else g.data_ptr())
+        try:
+            check(_lib.lib().tfrt_trace2d_backward(
+                _p(t.src), t.src.shape[1], t.src.shape[1], ctypes.byref(sc),
+                float(t.opts["new_ray_length"]), float(t.opts["dead_ray_length"] or 0.0),
+                int(t.opts["max_passes"]), t.dt,
+                _p(gs[0]), t.caps[0], _p(gs[1]), t.caps[1], _p(gs[2]), t.caps[2], _p(gs[3]),
+                t.caps[3], _p(g_seg), _p(g_arc), _p(g_src), _p(t.counts), _p(t.ws), t.wsb,
+                _stream(t.src)), "tfrt_trace2d_backward")
+        finally:
+            for name in _GRAD_INDEX_2D:
+                setattr(sc, name, None)
         if g_src is not None:
             g_src = g_src.to(t.src.dtype)
-        return g_src, g_seg, g_arc, None, None
+        return (g_src, g_seg, g_arc, *g_n, None, None)
 
 
 def trace2d(src, scene, max_passes, new_ray_length=1.0, dead_ray_length=None,
@@ -1524,7 +1547,9 @@ def trace2d(src, scene, max_passes, new_ray_length=1.0, dead_ray_length=None,
                 zero_init=predicted_counts is not None)
     seg_geo = None if scene.segments is None else scene.segments["geo"]
     arc_geo = None if scene.arcs is None else scene.arcs["geo"]
-    outs = _Trace2D.apply(src, seg_geo, arc_geo, scene, opts)
+    index = [n if isinstance(n, torch.Tensor) and n.requires_grad else None
+             for n in scene.index_args()]
+    outs = _Trace2D.apply(src, seg_geo, arc_geo, *index, scene, opts)
     aux = opts.pop("_aux")
     blocks, rows = _split_rows(outs, [aux[name + "_id"] is not None for name in _CLASS_NAMES], 4)
     full = dict(zip(_CLASS_NAMES, blocks))

@@ -13,9 +13,12 @@ rate 1, Nesterov momentum 0.8 and the gradient clipped to 0.1; ``--momentum`` ru
 ``RowwiseError(lambda r: r["y_end"] ** 2)``, any element-wise torch function's form: the fused step
 then evaluates it on fixed-shape columns (tfrt_trace2d_rows, tfrt_trace2d_backward_rows) inside
 the same graph.  ``--generic`` forces the generic path (user error function, autograd) for
-comparison.  No GUI.
+comparison.  ``--deterministic`` sums the reverse sweep's gradients in an order-independent way
+(``OpticalEngine(deterministic=True)``): the whole run is bit-identical from one run to the next.
+No GUI.
 
     python examples/optimize_arc.py [--rays 10] [--steps 30] [--momentum] [--rowwise] [--generic]
+                                    [--deterministic]
 """
 import argparse
 import math
@@ -39,7 +42,7 @@ import tfrt.sources as sources                # noqa: E402
 PI = math.pi
 
 
-def build(ray_count=10, ray_dtype=torch.float64, device="cuda:0"):
+def build(ray_count=10, ray_dtype=torch.float64, device="cuda:0", deterministic=False):
     parameter = torch.tensor([5.0], dtype=torch.float64, device=device, requires_grad=True)
     arc = boundaries.ManualArcBoundary()
     arc["x_center"] = parameter
@@ -67,7 +70,7 @@ def build(ray_count=10, ray_dtype=torch.float64, device="cuda:0"):
 
     trace_engine = engine.OpticalEngine(2, [operation.StandardReaction()],
                                         simple_ray_inheritance={"wavelength"},
-                                        ray_dtype=ray_dtype)
+                                        ray_dtype=ray_dtype, deterministic=deterministic)
     trace_engine.optical_system = system
     system.update()
     trace_engine.validate_system()
@@ -88,8 +91,9 @@ def make_optimizer(scene, momentum=False, generic=False, rowwise=False):
                                    apply_momentum=momentum, fused=not generic)
 
 
-def run(ray_count=10, steps=30, momentum=False, generic=False, verbose=True, rowwise=False):
-    scene = build(ray_count)
+def run(ray_count=10, steps=30, momentum=False, generic=False, verbose=True, rowwise=False,
+        deterministic=False):
+    scene = build(ray_count, deterministic=deterministic)
     opt = make_optimizer(scene, momentum, generic, rowwise)
     errors = []
     for i in range(steps):
@@ -114,8 +118,11 @@ def main():
                     help="the same error as a RowwiseError (any element-wise error function)")
     ap.add_argument("--generic", action="store_true",
                     help="force the generic optimiser step (for comparison)")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="bit-reproducible gradients (ordered reverse-sweep sums)")
     a = ap.parse_args()
-    errors, s = run(a.rays, a.steps, a.momentum, a.generic, rowwise=a.rowwise)
+    errors, s = run(a.rays, a.steps, a.momentum, a.generic, rowwise=a.rowwise,
+                    deterministic=a.deterministic)
     fs = s["optimizer"]._fused_step
     path = ("generic" if fs is None else
             f"fused, {fs.graph_replays} of {fs.steps} steps replayed from a HIP graph")

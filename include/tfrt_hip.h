@@ -636,6 +636,8 @@ typedef struct tfrt_scene2d {
    * up to the reflecting one; tfrt_sgd_process zeroes such entries (optimizer.py:226-229).
    * 1: the reflect branch's own finite gradient (new_angle = norm + theta1 + pi) instead. */
   int32_t finite_tir_gradient;
+  /* Bit-reproducible reverse sweeps: `deterministic`, the struct's last field (appended there to
+   * keep every other offset); the entries this rule makes NaN are NaN in both of its modes. */
   /* Reverse sweeps only (tfrt_trace2d_backward, tfrt_trace2d_backward_goal,
    * tfrt_trace2d_backward_rows), "value" mode (n_table NULL, *_n_in / *_n_out given): f64,
    * ACCUMULATED into, or NULL (not asked) -- d error / d seg_n_in[k], seg_n_out[k] (Ms each) and
@@ -647,6 +649,20 @@ typedef struct tfrt_scene2d {
   double* grad_seg_n_out;
   double* grad_arc_n_in;
   double* grad_arc_n_out;
+  /* Reverse sweeps only (tfrt_trace2d_backward, tfrt_trace2d_backward_goal,
+   * tfrt_trace2d_backward_rows), the 2-D counterpart of tfrt_scene3d.deterministic.  0 (default):
+   * grad_seg, grad_arc and the four grad_*_n_* blocks are summed with float64 atomics, whose last
+   * bits depend on the order in which they arrive.  1: ordered mode -- the sweep runs twice; the
+   * first run finds every output entry's largest finite term, the second rounds each term to a
+   * 64-bit integer at a power-of-two scale taken from that maximum (2^-40 of it while an entry
+   * receives at most 2^22 terms -- rays x passes of the call, per pass for tfrt_trace2d_backward --
+   * one bit coarser per doubling beyond, so that no sum can overflow), sums the integers (exact,
+   * hence order-independent) and adds sum / scale into the output: bit-identical results on every
+   * run and for any order of the source rays.  A non-finite term makes its entry NaN, as its float
+   * sum would be (the TIR rule of finite_tir_gradient is unchanged).  The forward pass and the
+   * built-in goal's error sum are bit-reproducible in either mode.  Needs the workspace
+   * tfrt_trace2d_workspace_bytes reports for the scene's n_segments and n_arcs. */
+  int32_t deterministic;
 } tfrt_scene2d;
 
 /* OpticalSystem2D._segment_intersection, tfrt/engine.py:688-749 (rays: 4 x stride block). */
@@ -664,6 +680,8 @@ int tfrt_arc_intersection(const void* rays, int64_t stride, int64_t n_rays, int3
                           uint8_t* valid, double* ray_u, double* arc_u, int32_t* gather_arc,
                           void* stream);
 
+/* Workspace of one 2-D trace and its reverse sweeps; n_segments and n_arcs size only the
+ * accumulators of the ordered sweeps (tfrt_scene2d.deterministic, 17 B per output entry). */
 size_t tfrt_trace2d_workspace_bytes(int64_t n_rays, int64_t n_segments, int64_t n_arcs,
                                     int32_t max_passes, int32_t state_dtype);
 

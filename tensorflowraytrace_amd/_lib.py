@@ -48,6 +48,7 @@ class Scene2D(ctypes.Structure):
         ("finite_tir_gradient", c_i32),
         ("grad_seg_n_in", c_vp), ("grad_seg_n_out", c_vp),
         ("grad_arc_n_in", c_vp), ("grad_arc_n_out", c_vp),
+        ("deterministic", c_i32),
     ]
 
 

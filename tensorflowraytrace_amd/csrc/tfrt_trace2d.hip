@@ -658,8 +658,119 @@ __device__ __forceinline__ void add_index_grads(const tfrt_scene2d& sc, int prim
   if (go != nullptr && gn[1] != 0.0) unsafeAtomicAdd(go + k, gn[1]);
 }
 
+// ---- ordered (deterministic) accumulation: tfrt_scene2d.deterministic
+// The 3-D rule (tfrt_trace3d.hip, k_face_accumulate_fixed) carried over to every 2-D sweep, with
+// one scale per output entry instead of one per pass.  A sweep runs twice: ORD_MAX only reduces
+// the largest finite |term| of every entry (integer atomicMax on the bit pattern), ORD_ACC rounds
+// each term to round(term * scale) in 64 bits -- scale = 2^(bits - e), the entry's largest term
+// = f 2^e, f in [0.5, 1) -- and sums those integers (in the wavefront, then with integer
+// atomics): exact, hence independent of the order and of which rays share a wavefront.  A
+// non-finite term flags its entry instead.  k_fixed_finish2 then adds sum / scale (NaN where
+// flagged) into the outputs in entry order and clears the accumulators.
+//
+// Headroom: every term is at most 2^bits after rounding, and an entry receives at most `terms`
+// of them (rays per launch x passes per launch), so bits = min(40, 62 - ceil(log2 terms)) keeps
+// every sum below 2^62 (fixed_bits2).  40 bits (2^-40 of the entry's largest term) up to 2^22
+// terms per entry, one bit less for every doubling beyond.
+//
+// Entries (6 Ms + 7 Ma): grad_seg (Ms,4), grad_arc (Ma,5), then grad_seg_n_in, grad_seg_n_out,
+// grad_arc_n_in, grad_arc_n_out.
+constexpr int ORD_NONE = 0, ORD_MAX = 1, ORD_ACC = 2;
+constexpr int FIXED_BITS2 = 40;
+
+struct Fixed2 {
+  unsigned long long* maxbits;  // per entry: bit pattern of the largest finite |term|
+  unsigned long long* acc;      // per entry: two's complement sum of the rounded terms
+  uint8_t* flag;                // per entry: a non-finite term was seen
+  int bits;
+};
+
+static int fixed_bits2(int64_t terms) {
+  int lg = 0;
+  while (lg < 62 && (int64_t(1) << lg) < terms) ++lg;
+  return min(FIXED_BITS2, 62 - lg);
+}
+
+__device__ __forceinline__ double fixed_scale2(unsigned long long maxbits, int bits) {
+  if (maxbits == 0ull) return 0.0;
+  int e;
+  (void)frexp(__longlong_as_double((long long)maxbits), &e);
+  // (an entry whose largest term lies below 2^-960 would need a scale beyond the float64 range:
+  // its terms round to zero)
+  int shift = bits - e;
+  if (shift > 1000) shift = 1000;
+  return ldexp(1.0, shift);
+}
+
+__device__ __forceinline__ int64_t geo_entry2(int prim, int q, int Ms) {
+  return prim < Ms ? 4 * (int64_t)prim + q : 4 * (int64_t)Ms + 5 * (int64_t)(prim - Ms) + q;
+}
+
+// q = 0: d / d n_in, 1: d / d n_out
+__device__ __forceinline__ int64_t index_entry2(int prim, int q, int Ms, int Ma) {
+  const int64_t base = 4 * (int64_t)Ms + 5 * (int64_t)Ma;
+  return prim < Ms ? base + (q ? Ms : 0) + prim
+                   : base + 2 * (int64_t)Ms + (q ? Ma : 0) + (prim - Ms);
+}
+
+// One lane's term x of entry `at`.
+template <int ORD>
+__device__ __forceinline__ void fixed_term(const Fixed2& fx, int64_t at, double x) {
+  const double a = fabs(x);
+  if (ORD == ORD_MAX) {
+    // non-negative doubles order like their bit patterns; NaN compares false
+    if (a > 0.0 && a < INFINITY) atomicMax(fx.maxbits + at, (unsigned long long)__double_as_longlong(a));
+  } else if (!(a < INFINITY)) {
+    fx.flag[at] = 1;
+  } else {
+    const long long q = llrint(x * fixed_scale2(fx.maxbits[at], fx.bits));
+    if (q != 0) atomicAdd(fx.acc + at, (unsigned long long)q);  // two's complement
+  }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_fixed_finish2(Fixed2 fx, int Ms, int Ma,
+                                                         double* __restrict__ g_seg,
+                                                         double* __restrict__ g_arc,
+                                                         tfrt_scene2d sc) {
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  const int64_t s4 = 4 * (int64_t)Ms, a5 = 5 * (int64_t)Ma;
+  if (i >= s4 + a5 + 2 * (int64_t)(Ms + Ma)) return;
+  double* out;
+  if (i < s4) {
+    out = g_seg ? g_seg + i : nullptr;
+  } else if (i < s4 + a5) {
+    out = g_arc ? g_arc + (i - s4) : nullptr;
+  } else {
+    int64_t j = i - s4 - a5;
+    double* g;
+    if (j < Ms) {
+      g = sc.grad_seg_n_in;
+    } else if (j < 2 * (int64_t)Ms) {
+      g = sc.grad_seg_n_out;
+      j -= Ms;
+    } else if (j < 2 * (int64_t)Ms + Ma) {
+      g = sc.grad_arc_n_in;
+      j -= 2 * (int64_t)Ms;
+    } else {
+      g = sc.grad_arc_n_out;
+      j -= 2 * (int64_t)Ms + Ma;
+    }
+    out = g ? g + j : nullptr;
+  }
+  const long long q = (long long)fx.acc[i];
+  if (out != nullptr) {
+    if (fx.flag[i] != 0) *out = __builtin_nan("");
+    else if (q != 0) *out += (double)q / fixed_scale2(fx.maxbits[i], fx.bits);
+  }
+  fx.acc[i] = 0ull;
+  fx.flag[i] = 0;
+  fx.maxbits[i] = 0ull;
+}
+
 // GN: the index gradients are asked for (index_grads2d(sc)); false compiles none of their terms.
-template <typename T, bool GN>
+// ORD: ORD_NONE float64 atomics; ORD_MAX / ORD_ACC the two launches of the ordered sum (ORD_MAX
+// writes no ray gradient).
+template <typename T, bool GN, int ORD = ORD_NONE>
 __global__ __launch_bounds__(BLOCK) void k_backward2d(
     const T* __restrict__ rays_in, int64_t stride_in, const int32_t* __restrict__ n_ptr,
     const int32_t* __restrict__ ray_id_in, const int32_t* __restrict__ rec_prim,
@@ -670,7 +781,7 @@ __global__ __launch_bounds__(BLOCK) void k_backward2d(
     const double* __restrict__ g_act, int64_t cap_act, const double* __restrict__ g_stp,
     int64_t cap_stp, const double* __restrict__ g_dead, int64_t cap_dead,
     double* __restrict__ g_out, int64_t out_stride, double* __restrict__ g_seg,
-    double* __restrict__ g_arc) {
+    double* __restrict__ g_arc, Fixed2 fx) {
   const int n = *n_ptr;
   const int i = blockIdx.x * BLOCK + threadIdx.x;
   if (i >= n) return;
@@ -719,17 +830,30 @@ __global__ __launch_bounds__(BLOCK) void k_backward2d(
       double gn[2];
       adjoint2d(s, e, pp, is_arc, rec_u[i], has_child, n_in, n_out, L, g_s, g_h, g_ce, gs, ge, gp,
                 sc.finite_tir_gradient != 0, GN ? gn : nullptr);
-      if (GN && has_child) add_index_grads(sc, prim, gn);
-      if (is_arc) {
-        if (g_arc != nullptr)
-          for (int q = 0; q < 5; ++q)
-            if (gp[q] != 0.0) unsafeAtomicAdd(g_arc + (int64_t)(prim - Ms) * 5 + q, gp[q]);
-      } else if (g_seg != nullptr) {
-        for (int q = 0; q < 4; ++q)
-          if (gp[q] != 0.0) unsafeAtomicAdd(g_seg + (int64_t)prim * 4 + q, gp[q]);
+      if constexpr (ORD == ORD_NONE) {
+        if (GN && has_child) add_index_grads(sc, prim, gn);
+        if (is_arc) {
+          if (g_arc != nullptr)
+            for (int q = 0; q < 5; ++q)
+              if (gp[q] != 0.0) unsafeAtomicAdd(g_arc + (int64_t)(prim - Ms) * 5 + q, gp[q]);
+        } else if (g_seg != nullptr) {
+          for (int q = 0; q < 4; ++q)
+            if (gp[q] != 0.0) unsafeAtomicAdd(g_seg + (int64_t)prim * 4 + q, gp[q]);
+        }
+      } else {
+        const int Ma = (int)sc.n_arcs;
+        if (GN && has_child) {
+          if ((is_arc ? sc.grad_arc_n_in : sc.grad_seg_n_in) != nullptr)
+            fixed_term<ORD>(fx, index_entry2(prim, 0, Ms, Ma), gn[0]);
+          if ((is_arc ? sc.grad_arc_n_out : sc.grad_seg_n_out) != nullptr)
+            fixed_term<ORD>(fx, index_entry2(prim, 1, Ms, Ma), gn[1]);
+        }
+        if (is_arc ? g_arc != nullptr : g_seg != nullptr)
+          for (int q = 0; q < (is_arc ? 5 : 4); ++q) fixed_term<ORD>(fx, geo_entry2(prim, q, Ms), gp[q]);
       }
     }
   }
+  if (ORD == ORD_MAX) return;
   for (int k = 0; k < 2; ++k) {
     g_out[k * out_stride + i] = gs[k];
     g_out[(2 + k) * out_stride + i] = ge[k];
@@ -805,10 +929,15 @@ __global__ __launch_bounds__(BLOCK) void k_seam2d(const T* __restrict__ rays, in
 struct Layout2 {
   size_t nrays, blockcnt, blockoff, rowtot, rowbase, ticket, bincnt, rays, rayid, lastprim, rec_prim, rec_slot, rec_u,
       rec_aux, rec_bin, gbuf, total;
+  // ordered reverse sweeps (tfrt_scene2d.deterministic) only: per-entry accumulators behind the
+  // rest, O(primitives); total_ordered covers them
+  size_t fix_max, fix_acc, fix_flag, total_ordered;
   int nblk;
 };
 
-static Layout2 make_layout2(int64_t N, int P, int dtype) {
+// (Ms, Ma size only the ordered sweeps' region at the end: every other offset is the same
+// whatever they are)
+static Layout2 make_layout2(int64_t N, int P, int dtype, int64_t Ms = 0, int64_t Ma = 0) {
   Layout2 L;
   const size_t esz = dtype == TFRT_F64 ? 8 : (dtype == TFRT_F16 ? 2 : 4);
   const size_t n = N > 0 ? N : 1;
@@ -836,7 +965,24 @@ static Layout2 make_layout2(int64_t N, int P, int dtype) {
   L.rec_bin = take((size_t)P * n);
   L.gbuf = take((size_t)2 * 4 * n * sizeof(double));
   L.total = o;
+  const size_t E = (size_t)(6 * Ms + 7 * Ma);
+  L.fix_max = take(E * sizeof(unsigned long long));
+  L.fix_acc = take(E * sizeof(unsigned long long));
+  L.fix_flag = take(E);
+  L.total_ordered = o;
   return L;
+}
+
+// The ordered sweeps' accumulators in the workspace, cleared (inside the call, so that a captured
+// sequence replays correctly); bits for at most `terms` terms per entry.
+static Fixed2 fixed_region2(const Layout2& lay, char* ws, int64_t terms, hipStream_t st) {
+  Fixed2 fx;
+  fx.maxbits = reinterpret_cast<unsigned long long*>(ws + lay.fix_max);
+  fx.acc = reinterpret_cast<unsigned long long*>(ws + lay.fix_acc);
+  fx.flag = reinterpret_cast<uint8_t*>(ws + lay.fix_flag);
+  fx.bits = fixed_bits2(terms > 0 ? terms : 1);
+  (void)hipMemsetAsync(ws + lay.fix_max, 0, lay.total_ordered - lay.fix_max, st);
+  return fx;
 }
 
 static bool scene2_ok(const tfrt_scene2d* sc) {
@@ -936,7 +1082,8 @@ static int trace2d_backward_t(const void* src_rays, int64_t src_stride, int64_t 
                               const double* g_dead, int64_t cap_dead, double* g_seg, double* g_arc,
                               double* g_src, const int32_t* counts, void* workspace,
                               size_t workspace_bytes, hipStream_t st) {
-  const Layout2 lay = make_layout2(N, P, dtype);
+  const int Ms = (int)sc->n_segments, Ma = (int)sc->n_arcs;
+  const Layout2 lay = make_layout2(N, P, dtype, Ms, Ma);
   if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
   char* ws = static_cast<char*>(workspace);
   const int32_t* nrays = reinterpret_cast<int32_t*>(ws + lay.nrays);
@@ -949,6 +1096,14 @@ static int trace2d_backward_t(const void* src_rays, int64_t src_stride, int64_t 
   double* gbuf = reinterpret_cast<double*>(ws + lay.gbuf);
   const size_t n = N > 0 ? N : 1;
   const bool gn = index_grads2d(sc);
+  // ordered: per pass ORD_MAX, ORD_ACC and k_fixed_finish2 (the pass's sums are added into the
+  // outputs pass by pass, last pass first); at most one term per ray and entry in a pass
+  const bool ordered = sc->deterministic != 0 && Ms + Ma > 0 && (g_seg || g_arc || gn);
+  Fixed2 fx = {nullptr, nullptr, nullptr, 0};
+  if (ordered) {
+    if (workspace_bytes < lay.total_ordered) return TFRT_E_WORKSPACE;
+    fx = fixed_region2(lay, ws, N, st);
+  }
   for (int p = P - 1; p >= 0; --p) {
     const T* rin = p == 0 ? static_cast<const T*>(src_rays) : rays_ws + (size_t)(p - 1) * 4 * n;
     const int64_t sin = p == 0 ? src_stride : (int64_t)n;
@@ -961,10 +1116,22 @@ static int trace2d_backward_t(const void* src_rays, int64_t src_stride, int64_t 
                          rec_prim + (size_t)p * n, rec_u + (size_t)p * n, rec_bin + (size_t)p * n,
                          rec_slot + (size_t)p * n, counts + (size_t)p * TFRT_COUNTS_PER_PASS, *sc,
                          L, dead_len, g_child, (int64_t)n, g_fin, cap_fin, g_act, cap_act, g_stp,
-                         cap_stp, g_dead, cap_dead, g_out, out_stride, g_seg, g_arc);
+                         cap_stp, g_dead, cap_dead, g_out, out_stride, g_seg, g_arc, fx);
     };
-    if (gn) launch(k_backward2d<T, true>);
-    else launch(k_backward2d<T, false>);
+    if (!ordered) {
+      if (gn) launch(k_backward2d<T, true>);
+      else launch(k_backward2d<T, false>);
+      continue;
+    }
+    if (gn) {
+      launch(k_backward2d<T, true, ORD_MAX>);
+      launch(k_backward2d<T, true, ORD_ACC>);
+    } else {
+      launch(k_backward2d<T, false, ORD_MAX>);
+      launch(k_backward2d<T, false, ORD_ACC>);
+    }
+    hipLaunchKernelGGL(k_fixed_finish2, dim3(cdiv(6 * (int64_t)Ms + 7 * (int64_t)Ma, BLOCK)),
+                       dim3(BLOCK), 0, st, fx, Ms, Ma, g_seg, g_arc, *sc);
   }
   return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
 }
@@ -1159,13 +1326,80 @@ __device__ __forceinline__ void add_prim_index_grads(bool has, int prim, const d
   }
 }
 
-template <typename T, typename Seed, bool GN>
+// The terms x of the lanes with `mine` set into entry `at` (wave-uniform), ORD_MAX or ORD_ACC:
+// one atomic per entry and wavefront.  The rounded terms are summed as integers, so the result
+// does not depend on which lanes share the wavefront.  Called by all 64 lanes.
+template <int ORD>
+__device__ __forceinline__ void fixed_group(const Fixed2& fx, int64_t at, bool mine, bool single,
+                                            int leader, double x) {
+  if (single) {
+    if (mine) fixed_term<ORD>(fx, at, x);
+    return;
+  }
+  const double a = fabs(x);
+  if (ORD == ORD_MAX) {
+    double m = (mine && a < INFINITY) ? a : 0.0;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) m = fmax(m, __shfl_xor(m, d, 64));
+    if ((int)lane_id() == leader && m > 0.0)
+      atomicMax(fx.maxbits + at, (unsigned long long)__double_as_longlong(m));
+  } else {
+    const double scale = fixed_scale2(fx.maxbits[at], fx.bits);
+    unsigned long long q = 0ull;
+    if (mine) {
+      if (a < INFINITY) q = (unsigned long long)llrint(x * scale);
+      else fx.flag[at] = 1;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) q += __shfl_xor(q, d, 64);  // (two's complement)
+    if ((int)lane_id() == leader && q != 0ull) atomicAdd(fx.acc + at, q);
+  }
+}
+
+// add_prim_grads + add_prim_index_grads of the ordered sweep.  Called by all 64 lanes.
+template <int ORD, bool GN>
+__device__ __forceinline__ void add_prim_grads_fixed(bool has, int prim, const double gp[5],
+                                                     const double gn[2], const tfrt_scene2d& sc,
+                                                     double* g_seg, double* g_arc,
+                                                     const Fixed2& fx) {
+  const int Ms = (int)sc.n_segments, Ma = (int)sc.n_arcs;
+  unsigned long long todo = __ballot(has);
+  while (todo) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const int key = __shfl(prim, leader, 64);
+    const bool mine = has && prim == key;
+    const unsigned long long grp = __ballot(mine);
+    const bool single = __popcll(grp) == 1;
+    const bool is_arc = key >= Ms;
+    if (is_arc ? g_arc != nullptr : g_seg != nullptr) {
+      // (adjoint2d leaves an arc's angle columns 2, 3 at zero: they only feed comparisons)
+      constexpr int seg_q[4] = {0, 1, 2, 3};
+      constexpr int arc_q[3] = {0, 1, 4};
+      const int nq = is_arc ? 3 : 4;
+      for (int k = 0; k < nq; ++k) {
+        const int q = is_arc ? arc_q[k] : seg_q[k];
+        fixed_group<ORD>(fx, geo_entry2(key, q, Ms), mine, single, leader, gp[q]);
+      }
+    }
+    if (GN) {
+      double* const rows[2] = {is_arc ? sc.grad_arc_n_in : sc.grad_seg_n_in,
+                               is_arc ? sc.grad_arc_n_out : sc.grad_seg_n_out};
+      for (int q = 0; q < 2; ++q)
+        if (rows[q] != nullptr)
+          fixed_group<ORD>(fx, index_entry2(key, q, Ms, Ma), mine, single, leader, gn[q]);
+    }
+    has = has && !mine;
+    todo &= ~grp;
+  }
+}
+
+template <typename T, typename Seed, bool GN, int ORD = ORD_NONE>
 __global__ __launch_bounds__(BLOCK) void k_backward2d_goal(
     const T* __restrict__ src, int64_t src_stride, int N, const T* __restrict__ rays_ws,
     int64_t n, const int32_t* __restrict__ rec_prim, const double* __restrict__ rec_u,
     const uint8_t* __restrict__ rec_bin, const int32_t* __restrict__ rec_slot, int P,
     tfrt_scene2d sc, double L, tfrt_ray_out fin, Seed seed, double* __restrict__ g_seg,
-    double* __restrict__ g_arc) {
+    double* __restrict__ g_arc, Fixed2 fx) {
   __shared__ int32_t chain[CHAIN2 * BLOCK];
   const int tid = threadIdx.x;
   const int i = blockIdx.x * BLOCK + tid;
@@ -1183,7 +1417,7 @@ __global__ __launch_bounds__(BLOCK) void k_backward2d_goal(
   double sd[4] = {0.0, 0.0, 0.0, 0.0};
   if (end_cls == CLS_FINISHED && end_slot < fin.capacity)
     acc = seed.template seed<T>(fin, end_slot, i, sd);
-  seed.sum(acc, N);
+  if (ORD != ORD_MAX) seed.sum(acc, N);  // (the ordered sweep's first launch leaves the error)
 
   // reverse: link `top` is the chain's end (seeded when finished, no child), every link below it
   // is an active parent whose child gradient is (gc_s, gc_e)
@@ -1242,8 +1476,12 @@ __global__ __launch_bounds__(BLOCK) void k_backward2d_goal(
       }
       --p;
     }
-    add_prim_grads(has, prim, gp, Ms, g_seg, g_arc);
-    if (GN) add_prim_index_grads(has, prim, gn, sc);
+    if constexpr (ORD == ORD_NONE) {
+      add_prim_grads(has, prim, gp, Ms, g_seg, g_arc);
+      if (GN) add_prim_index_grads(has, prim, gn, sc);
+    } else {
+      add_prim_grads_fixed<ORD, GN>(has, prim, gp, gn, sc, g_seg, g_arc, fx);
+    }
   }
 }
 
@@ -1253,11 +1491,19 @@ static int trace2d_backward_goal_t(const void* src_rays, int64_t src_stride, int
                                    const tfrt_ray_out& fin, const Seed& seed, double* g_seg,
                                    double* g_arc, void* workspace, size_t workspace_bytes,
                                    hipStream_t st) {
-  const Layout2 lay = make_layout2(N, P, dtype);
+  const int Ms = (int)sc->n_segments, Ma = (int)sc->n_arcs;
+  const Layout2 lay = make_layout2(N, P, dtype, Ms, Ma);
   if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
+  const bool gn = index_grads2d(sc);
+  // ordered: ORD_MAX, ORD_ACC over all passes, then k_fixed_finish2; at most one term per ray,
+  // pass and entry
+  const bool ordered = sc->deterministic != 0 && Ms + Ma > 0 && (g_seg || g_arc || gn);
+  if (ordered && workspace_bytes < lay.total_ordered) return TFRT_E_WORKSPACE;
   if (N == 0) return 0;
   char* ws = static_cast<char*>(workspace);
   const size_t n = N;
+  Fixed2 fx = {nullptr, nullptr, nullptr, 0};
+  if (ordered) fx = fixed_region2(lay, ws, N * (int64_t)(P > 0 ? P : 1), st);
   auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(cdiv(N, BLOCK)), dim3(BLOCK), 0, st,
                        static_cast<const T*>(src_rays), src_stride, (int)N,
@@ -1266,10 +1512,22 @@ static int trace2d_backward_goal_t(const void* src_rays, int64_t src_stride, int
                        reinterpret_cast<const double*>(ws + lay.rec_u),
                        reinterpret_cast<const uint8_t*>(ws + lay.rec_bin),
                        reinterpret_cast<const int32_t*>(ws + lay.rec_slot), P, *sc, L, fin, seed,
-                       g_seg, g_arc);
+                       g_seg, g_arc, fx);
   };
-  if (index_grads2d(sc)) launch(k_backward2d_goal<T, Seed, true>);
-  else launch(k_backward2d_goal<T, Seed, false>);
+  if (!ordered) {
+    if (gn) launch(k_backward2d_goal<T, Seed, true>);
+    else launch(k_backward2d_goal<T, Seed, false>);
+    return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  }
+  if (gn) {
+    launch(k_backward2d_goal<T, Seed, true, ORD_MAX>);
+    launch(k_backward2d_goal<T, Seed, true, ORD_ACC>);
+  } else {
+    launch(k_backward2d_goal<T, Seed, false, ORD_MAX>);
+    launch(k_backward2d_goal<T, Seed, false, ORD_ACC>);
+  }
+  hipLaunchKernelGGL(k_fixed_finish2, dim3(cdiv(6 * (int64_t)Ms + 7 * (int64_t)Ma, BLOCK)),
+                     dim3(BLOCK), 0, st, fx, Ms, Ma, g_seg, g_arc, *sc);
   return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
 }
 
@@ -1395,7 +1653,8 @@ int tfrt_arc_intersection(const void* rays, int64_t stride, int64_t n_rays, int3
 size_t tfrt_trace2d_workspace_bytes(int64_t n_rays, int64_t n_segments, int64_t n_arcs,
                                     int32_t max_passes, int32_t state_dtype) {
   if (n_rays < 0 || n_segments < 0 || n_arcs < 0 || max_passes < 0) return 0;
-  return make_layout2(n_rays, max_passes, state_dtype).total;
+  // (the segments and arcs size the ordered reverse sweeps' accumulators)
+  return make_layout2(n_rays, max_passes, state_dtype, n_segments, n_arcs).total_ordered;
 }
 
 int tfrt_trace2d_forward(const void* src_rays, int64_t src_stride, int64_t n_rays,

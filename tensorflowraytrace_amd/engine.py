@@ -629,10 +629,12 @@ class OpticalSystem2D(OpticalSystemBase):
         self._merged_arcs = self._merge_kind(
             "arcs", ("x_center", "y_center", "angle_start", "angle_end", "radius"))
 
-    def scene_args(self, n_table, index_mode, ghost=False, finite_tir_gradient=False):
+    def scene_args(self, n_table, index_mode, ghost=False, finite_tir_gradient=False,
+                   deterministic=False):
         return ops.Scene2DArgs(self._merged_segments, self._merged_arcs, n_table, index_mode,
                                ghost, self.intersect_epsilion, self.size_epsilion,
-                               self.ray_start_epsilion, finite_tir_gradient=finite_tir_gradient)
+                               self.ray_start_epsilion, finite_tir_gradient=finite_tir_gradient,
+                               deterministic=deterministic)
 
     @staticmethod
     def _segment_intersection(rx1, ry1, rx2, ry2, sx1, sy1, sx2, sy2, intersect_epsilion,
@@ -702,7 +704,8 @@ class OpticalEngine:
             raise ValueError(f"OpticalEngine: unknown accelerate mode {accelerate!r}")
         self.accelerate = accelerate
         # True: the reverse sweep sums face gradients in an order-independent way (scaled 64-bit
-        # integers): gradients are bit-identical from run to run (tfrt_scene3d.deterministic);
+        # integers): gradients are bit-identical from run to run (tfrt_scene3d.deterministic; in
+        # 2-D tfrt_scene2d.deterministic, also for any order of the source rays);
         # default False: float64 atomics, whose last bits depend on the arrival order.
         self.deterministic = bool(deterministic)
         # 3-D hierarchy mode: trace the rays in a coherent order (ops.ray_order: a Hilbert-curve
@@ -1036,7 +1039,8 @@ class OpticalEngine:
             if block is None:
                 block = rays.ray_block(dt)
             scene = system.scene_args(n_table, index_mode, ghost,
-                                      finite_tir_gradient=self.finite_tir_gradient)
+                                      finite_tir_gradient=self.finite_tir_gradient,
+                                      deterministic=self.deterministic)
         fv = None
         if self.dimension == 3:
             fv = system._merged_face_verts

@@ -892,6 +892,16 @@ typedef struct tfrt_points_program {
 #define TFRT_SRC_APERTURE 0 /* start = a[i], end = b[i]                                      sources.py:918-1095 */
 #define TFRT_SRC_POINT 1    /* start = center, end = center + L rot(b[i])                    sources.py:464-675 */
 #define TFRT_SRC_ANGULAR 2  /* start = center + rot(a[i]), end = start + L rot(b[i])         sources.py:678-915 */
+/* A stored pool of rays, re-sampled with replacement and jittered at every update (PrecompiledSource,
+ * tfrt/sources.py:1099-1358): ray i at epoch e is pool row
+ *   row = pool_downsample ? min(floor(u0 * pool_count), pool_count - 1) : i,
+ * u0 the first number of Philox(pool_seed, pool_stream, e, i) -- the product in float64 wherever the
+ * program is evaluated, so that the order's float32 keys belong to the very rays that are traced --,
+ * plus sigma_start / sigma_end times standard normals: Box-Muller, sqrt(-2 log(1 - u)) (cos, sin)(2 pi v),
+ * on the pair (u, v) of stream pool_stream + 1 + axis, which gives the axis's (start, end) normals.
+ * An axis whose sigma is 0 is not touched: the coordinate is the stored one bit for bit.  `a`, `b`,
+ * center, quat, ray_length and swap are unused. */
+#define TFRT_SRC_POOL 3
 typedef struct tfrt_source3d_program {
   int32_t kind;          /* TFRT_SRC_* */
   int32_t swap;          /* start and end exchanged (start_on_center / start_on_base false) */
@@ -902,6 +912,14 @@ typedef struct tfrt_source3d_program {
   int32_t has_quat, reserved0;
   double ray_length;
   int64_t n_rays;        /* every input has 1 or n_rays samples */
+  /* TFRT_SRC_POOL only (zero otherwise) */
+  const double* pool;    /* (pool_count, 6) f64 ROW-major: one 48-byte record x_start ... z_end per stored ray */
+  int64_t pool_count;    /* 1 ... INT32_MAX */
+  double sigma_start[3], sigma_end[3]; /* standard deviations of the jitter per axis, >= 0 */
+  int32_t pool_downsample; /* 0: ray i is row i (n_rays == pool_count) */
+  int32_t pool_stream;   /* streams pool_stream ... pool_stream + 3 of the seed */
+  uint64_t pool_seed;
+  const int64_t* pool_epoch; /* device counter; may be NULL when nothing is sampled or jittered */
 } tfrt_source3d_program;
 
 /* tfrt_ray_order for rays first .. first + n_rays of a source program, without the rays ever being
@@ -946,6 +964,12 @@ int tfrt_points_generate(const tfrt_points_program* program, const int32_t* inde
 int tfrt_source3d_generate(const tfrt_source3d_program* program, const int32_t* index,
                            int64_t first, int64_t n, int32_t state_dtype, void* rays, int64_t stride, double* fields,
                            int64_t field_stride, void* stream);
+
+/* TFRT_SRC_POOL: rows[j] = the pool row of ray first + index[j] (NULL: first + j), j < n, at the
+ * current epoch -- the row tfrt_source3d_generate and the order's keys read for that ray (the same
+ * device function), so that a caller can gather every stored field that is not geometry. */
+int tfrt_source3d_pool_rows(const tfrt_source3d_program* program, const int32_t* index,
+                            int64_t first, int64_t n, int32_t* rows, void* stream);
 
 #ifdef __cplusplus
 }

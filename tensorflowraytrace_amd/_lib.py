@@ -99,11 +99,14 @@ class Source3DProgram(ctypes.Structure):
     """tfrt_source3d_program (include/tfrt_hip.h)."""
     _fields_ = [("kind", c_i32), ("swap", c_i32), ("a", PointsProgram), ("b", PointsProgram),
                 ("center", c_f64 * 3), ("quat", c_f64 * 4), ("has_quat", c_i32),
-                ("reserved0", c_i32), ("ray_length", c_f64), ("n_rays", c_i64)]
+                ("reserved0", c_i32), ("ray_length", c_f64), ("n_rays", c_i64),
+                ("pool", c_vp), ("pool_count", c_i64), ("sigma_start", c_f64 * 3),
+                ("sigma_end", c_f64 * 3), ("pool_downsample", c_i32), ("pool_stream", c_i32),
+                ("pool_seed", ctypes.c_uint64), ("pool_epoch", c_vp)]
 
 
 PTS_TABLE, PTS_CIRCLE, PTS_SQUARE, PTS_SPHERE_UNIFORM, PTS_SPHERE_LAMBERT = 0, 1, 2, 3, 4
-SRC_APERTURE, SRC_POINT, SRC_ANGULAR = 0, 1, 2
+SRC_APERTURE, SRC_POINT, SRC_ANGULAR, SRC_POOL = 0, 1, 2, 3
 
 _P = ctypes.POINTER
 
@@ -214,6 +217,7 @@ SIGNATURES = {
                                      c_vp]),
     "tfrt_source3d_generate": (c_i32, [_P(Source3DProgram), c_vp, c_i64, c_i64, c_i32, c_vp, c_i64,
                                        c_vp, c_i64, c_vp]),
+    "tfrt_source3d_pool_rows": (c_i32, [_P(Source3DProgram), c_vp, c_i64, c_i64, c_vp, c_vp]),
 }
 
 _lib = None

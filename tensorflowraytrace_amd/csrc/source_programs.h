@@ -2,6 +2,8 @@
 // csrc/tfrt_source.hip (rays and points into the caller's buffers) and csrc/tfrt_order.hip (the
 // coherent order of a program's rays without ever writing them in source order).
 #pragma once
+#include <cfloat>
+#include <cstdint>
 #include "tfrt_common.h"
 
 namespace tfrt {
@@ -48,6 +50,8 @@ __device__ __forceinline__ void m_sincos(double x, double* s, double* c) { sinco
 __device__ __forceinline__ void m_sincos(float x, float* s, float* c) { sincosf(x, s, c); }
 __device__ __forceinline__ void m_sincospi(double x, double* s, double* c) { sincospi(x, s, c); }
 __device__ __forceinline__ void m_sincospi(float x, float* s, float* c) { sincospif(x, s, c); }
+__device__ __forceinline__ double m_log(double x) { return log(x); }
+__device__ __forceinline__ float m_log(float x) { return logf(x); }
 
 template <typename F>
 __device__ __forceinline__ void quat_rotate(const double qd[4], F v[3]) {
@@ -145,10 +149,62 @@ __device__ __forceinline__ void eval_points(const tfrt_points_program& pg, int64
   out[2] = p[2];
 }
 
-// ray i of the source (natural numbering)
+// TFRT_SRC_POOL: the stored row ray i is made from at `epoch`.  Float64 whatever the caller
+// evaluates in: a float32 product could name another row than the one that is traced.
+__device__ __forceinline__ int64_t pool_row(const tfrt_source3d_program& sp, int64_t i,
+                                            uint64_t epoch) {
+  const int64_t last = sp.pool_count - 1;
+  int64_t row = i;
+  if (sp.pool_downsample) {
+    double u0, u1;
+    uniform2(sp.pool_seed, (uint32_t)sp.pool_stream, epoch, (uint64_t)i, &u0, &u1);
+    row = (int64_t)floor(u0 * (double)sp.pool_count);
+  }
+  return row < 0 ? 0 : (row > last ? last : row);   // (never outside the pool, whatever `i` is)
+}
+
+__device__ __forceinline__ bool pool_perturbs(const tfrt_source3d_program& sp) {
+  return sp.sigma_start[0] > 0.0 || sp.sigma_start[1] > 0.0 || sp.sigma_start[2] > 0.0 ||
+         sp.sigma_end[0] > 0.0 || sp.sigma_end[1] > 0.0 || sp.sigma_end[2] > 0.0;
+}
+
+// ray i of a pool: the 48-byte record of its row, every axis with a sigma moved by sigma * z
 template <typename F>
+__device__ __forceinline__ void eval_pool(const tfrt_source3d_program& sp, int64_t i, F s[3],
+                                          F e[3]) {
+  const bool jitter = pool_perturbs(sp);
+  const uint64_t epoch = (sp.pool_downsample || jitter) ? (uint64_t)*sp.pool_epoch : 0;
+  const double* rec = sp.pool + 6 * pool_row(sp, i, epoch);
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    s[q] = (F)rec[q];
+    e[q] = (F)rec[3 + q];
+  }
+  if (!jitter) return;
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    if (!(sp.sigma_start[q] > 0.0 || sp.sigma_end[q] > 0.0)) continue;
+    double u, v;
+    uniform2(sp.pool_seed, (uint32_t)(sp.pool_stream + 1 + q), epoch, (uint64_t)i, &u, &v);
+    // (1 - u in (0, 1] in float64: the logarithm stays finite, |z| <= sqrt(106 log 2) = 8.57)
+    const F r = m_sqrt((F)-2 * m_log((F)(1.0 - u)));
+    F sn, cs;
+    m_sincospi((F)(2.0 * v), &sn, &cs);
+    if (sp.sigma_start[q] > 0.0) s[q] += (F)sp.sigma_start[q] * (r * cs);
+    if (sp.sigma_end[q] > 0.0) e[q] += (F)sp.sigma_end[q] * (r * sn);
+  }
+}
+
+// ray i of the source (natural numbering).  POOL: the program is a TFRT_SRC_POOL one -- the host
+// picks the instantiation by the program's kind, so that the kernels of the procedural kinds carry
+// nothing of the pool's code or registers, and the pool's nothing of theirs.
+template <bool POOL = false, typename F>
 __device__ __forceinline__ void eval_ray(const tfrt_source3d_program& sp, int64_t i, F s[3],
                                          F e[3]) {
+  if constexpr (POOL) {
+    eval_pool<F>(sp, i, s, e);
+    return;
+  }
   F a[3] = {(F)0, (F)0, (F)0}, b[3] = {(F)0, (F)0, (F)0}, aux[2];
   const int64_t ia = sp.a.count == 1 ? 0 : i, ib = sp.b.count == 1 ? 0 : i;
   if (sp.kind == TFRT_SRC_APERTURE) {
@@ -185,8 +241,23 @@ inline bool points_program_ok(const tfrt_points_program* pg) {
   return pg->epoch != nullptr;
 }
 
+// a pool program: the pool and its size, the widths, the counter whenever a kernel reads it
+inline bool pool_program_ok(const tfrt_source3d_program* sp) {
+  if (sp->pool == nullptr || sp->pool_count <= 0 || sp->pool_count > (int64_t)INT32_MAX)
+    return false;
+  bool jitter = false;
+  for (int q = 0; q < 3; ++q) {
+    const double a = sp->sigma_start[q], b = sp->sigma_end[q];
+    if (!(a >= 0.0 && a <= DBL_MAX && b >= 0.0 && b <= DBL_MAX)) return false;   // (negative, inf, NaN)
+    jitter = jitter || a > 0.0 || b > 0.0;
+  }
+  if ((sp->pool_downsample || jitter) && sp->pool_epoch == nullptr) return false;
+  return sp->pool_downsample || sp->n_rays == sp->pool_count;
+}
+
 inline bool source_program_ok(const tfrt_source3d_program* sp) {
   if (!sp || sp->n_rays < 0) return false;
+  if (sp->kind == TFRT_SRC_POOL) return pool_program_ok(sp);
   if (sp->kind < TFRT_SRC_APERTURE || sp->kind > TFRT_SRC_ANGULAR) return false;
   if (!points_program_ok(&sp->b)) return false;
   if (sp->kind != TFRT_SRC_POINT && !points_program_ok(&sp->a)) return false;

@@ -35,18 +35,22 @@ struct BlockRays {
     load_ray3(rays, stride, i, s, e);
   }
 };
-struct ProgramRays {
+// (POOL: a TFRT_SRC_POOL program; its own instantiation of the kernels, see eval_ray)
+template <bool POOL>
+struct ProgramRaysT {
   static constexpr bool HAS_F32 = true;
   tfrt_source3d_program sp;
   int64_t first;
   __device__ __forceinline__ void load(int64_t i, double s[3], double e[3]) const {
-    eval_ray(sp, first + i, s, e);
+    eval_ray<POOL>(sp, first + i, s, e);
   }
-  // (float32 evaluation: enough for the order's keys, a fraction of the float64 one's time)
+  // (float32 evaluation: enough for the order's keys, a fraction of the float64 one's time; a
+  // pool's row is chosen in float64 all the same: the keys are those of the rays that are traced)
   __device__ __forceinline__ void load_f(int64_t i, float s[3], float e[3]) const {
-    eval_ray<float>(sp, first + i, s, e);
+    eval_ray<POOL>(sp, first + i, s, e);
   }
 };
+using ProgramRays = ProgramRaysT<false>;
 
 // ------------------------------------------------------------------------------ order keys
 
@@ -381,8 +385,8 @@ __global__ __launch_bounds__(BLOCK) void k_order_key(const float2* __restrict__ 
 // outside them lands in an edge cell --, so nothing has to pass over all rays before the keys are
 // made.  Also leaves the histogram of the low digits per sort tile -- of the HIGH digits when HIGH
 // (tfrt_source3d_order_cells: the scatter by the high digit comes first, see k_bucket_sort).
-template <int ITEMS, bool HIGH>
-__global__ __launch_bounds__(BLOCK) void k_order_pkey(const ProgramRays src, int n,
+template <int ITEMS, bool HIGH, typename R>
+__global__ __launch_bounds__(BLOCK) void k_order_pkey(const R src, int n,
                                                       const double* __restrict__ fverts, int M,
                                                       double ax0, double ax1, double ax2,
                                                       int has_axis, int bits,
@@ -396,7 +400,7 @@ __global__ __launch_bounds__(BLOCK) void k_order_pkey(const ProgramRays src, int
   const int bins = 1 << bits;
   for (int d = tid; d < bins; d += BLOCK) h_lds[d] = 0u;
   float sf[3] = {0.f, 0.f, 0.f}, ef[3] = {0.f, 0.f, 0.f};
-  block_frame<ProgramRays, true>(src, n, fverts, M, ax0, ax1, ax2, has_axis, red, &fr, sf, ef);
+  block_frame<R, true>(src, n, fverts, M, ax0, ax1, ax2, has_axis, red, &fr, sf, ef);
   __syncthreads();
   float xlo, xhi, ylo, yhi;
   {
@@ -1260,8 +1264,8 @@ static int ray_order_t(const R& src, int64_t N, const double* fverts, int64_t M,
       const dim3 cgrid(cdiv(bins, BLOCK), L.nseg);
 #define TFRT_ORDER_MSD(I)                                                                          \
   {                                                                                                \
-    hipLaunchKernelGGL((k_order_pkey<I, true>), dim3(L.nblk), dim3(BLOCK), hl, st, src, n, fverts, \
-                       (int)M, a0, a1, a2, axis ? 1 : 0, L.bits, keys, hist, L.nblk);              \
+    hipLaunchKernelGGL((k_order_pkey<I, true, R>), dim3(L.nblk), dim3(BLOCK), hl, st, src, n,      \
+                       fverts, (int)M, a0, a1, a2, axis ? 1 : 0, L.bits, keys, hist, L.nblk);      \
     hipLaunchKernelGGL(k_colscan_rows, cgrid, dim3(BLOCK), 0, st, hist, L.nblk, bins, seg);        \
     hipLaunchKernelGGL(k_colscan_segs, dim3(cgrid.x), dim3(BLOCK), 0, st, seg, L.nseg, bins,       \
                        dtotal);                                                                    \
@@ -1280,7 +1284,7 @@ static int ray_order_t(const R& src, int64_t N, const double* fverts, int64_t M,
 #define TFRT_ORDER_ITEMS(I)                                                                       \
   {                                                                                               \
     if constexpr (R::HAS_F32)   /* a program's rays: frame, extents and keys in one launch */     \
-      hipLaunchKernelGGL((k_order_pkey<I, false>), dim3(L.nblk), dim3(BLOCK), hl, st, src, n,     \
+      hipLaunchKernelGGL((k_order_pkey<I, false, R>), dim3(L.nblk), dim3(BLOCK), hl, st, src, n,  \
                          fverts, (int)M, a0, a1, a2, axis ? 1 : 0, L.bits, keys, hist, L.nblk);    \
     else                                                                                          \
       hipLaunchKernelGGL((k_order_key<I>), dim3(L.nblk), dim3(BLOCK), hl, st, xy, n, mm, L.bits,  \
@@ -1418,12 +1422,15 @@ static int source3d_order(const tfrt_source3d_program* program, int64_t first, i
   if (!perm || !workspace) return TFRT_E_BADARG;
   const OrderLayout L = order_layout(n_rays);
   if (workspace_bytes < L.total) return TFRT_E_WORKSPACE;
-  ProgramRays src;
-  src.sp = *program;
-  src.first = first;
-  const int rc = ray_order_t(src, n_rays, face_verts, n_faces, axis, perm, keys_out,
-                             static_cast<char*>(workspace), L, static_cast<hipStream_t>(stream),
-                             cells);
+  char* ws = static_cast<char*>(workspace);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int rc;
+  if (program->kind == TFRT_SRC_POOL)
+    rc = ray_order_t(ProgramRaysT<true>{*program, first}, n_rays, face_verts, n_faces, axis, perm,
+                     keys_out, ws, L, st, cells);
+  else
+    rc = ray_order_t(ProgramRays{*program, first}, n_rays, face_verts, n_faces, axis, perm,
+                     keys_out, ws, L, st, cells);
   if (rc != 0) return rc;
   return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
 }

@@ -15,6 +15,10 @@
 //                    transformation (lift to 3-D, scale, quaternion, translation)
 //   source program   AperatureSource / PointSource / AngularSource assembly of two of those
 //                    (tfrt/sources.py:464-1095, undense: sample i of each input makes ray i)
+//   pool program     PrecompiledSource (tfrt/sources.py:1099-1358): a stored set of rays as 48-byte
+//                    records, ray i = a row drawn with replacement (one Philox number) plus a
+//                    normal jitter of the end points (Box-Muller on three more draws); the row is
+//                    also handed out (tfrt_source3d_pool_rows) for the fields that are not geometry
 //
 // Rays and points are functions of (program, epoch, i): they are written into the caller's
 // persistent buffers by one launch, any subset of them can be made again later (the sorted copy of
@@ -49,7 +53,7 @@ __global__ __launch_bounds__(BLOCK) void k_points(tfrt_points_program pg, const 
   if (aux1 != nullptr) aux1[j] = aux[1];
 }
 
-template <typename T>
+template <typename T, bool POOL>
 __global__ __launch_bounds__(BLOCK) void k_source3d(tfrt_source3d_program sp,
                                                     const int32_t* __restrict__ index,
                                                     int64_t first, int64_t n,
@@ -60,9 +64,21 @@ __global__ __launch_bounds__(BLOCK) void k_source3d(tfrt_source3d_program sp,
   if (j >= n) return;
   const int64_t i = first + (index != nullptr ? index[j] : j);
   double s[3], e[3];
-  eval_ray(sp, i, s, e);
+  eval_ray<POOL>(sp, i, s, e);
   if (rays != nullptr) store_ray3(rays, stride, j, s, e);
   if (fields != nullptr) store_ray3(fields, fstride, j, s, e);
+}
+
+// TFRT_SRC_POOL: the row every ray is made from (eval_pool's own pool_row)
+__global__ __launch_bounds__(BLOCK) void k_pool_rows(tfrt_source3d_program sp,
+                                                     const int32_t* __restrict__ index,
+                                                     int64_t first, int64_t n,
+                                                     int32_t* __restrict__ rows) {
+  const int64_t j = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (j >= n) return;
+  const int64_t i = first + (index != nullptr ? index[j] : j);
+  const uint64_t epoch = sp.pool_downsample ? (uint64_t)*sp.pool_epoch : 0;
+  rows[j] = (int32_t)pool_row(sp, i, epoch);
 }
 
 __global__ void k_epoch_advance(int64_t* p0, int64_t* p1, int64_t* p2, int64_t* p3, int64_t* p4,
@@ -114,22 +130,41 @@ int tfrt_source3d_generate(const tfrt_source3d_program* program, const int32_t* 
   if (n == 0) return 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(cdiv(n, BLOCK));
+  const bool pool = program->kind == TFRT_SRC_POOL;
+#define TFRT_SOURCE3D(T)                                                                          \
+  {                                                                                               \
+    if (pool)                                                                                     \
+      hipLaunchKernelGGL((k_source3d<T, true>), grid, dim3(BLOCK), 0, st, *program, index, first, \
+                         n, static_cast<T*>(rays), stride, fields, field_stride);                 \
+    else                                                                                          \
+      hipLaunchKernelGGL((k_source3d<T, false>), grid, dim3(BLOCK), 0, st, *program, index,       \
+                         first, n, static_cast<T*>(rays), stride, fields, field_stride);          \
+  }
   switch (state_dtype) {
     case TFRT_F32:
-      hipLaunchKernelGGL((k_source3d<float>), grid, dim3(BLOCK), 0, st, *program, index, first, n,
-                         static_cast<float*>(rays), stride, fields, field_stride);
+      TFRT_SOURCE3D(float)
       break;
     case TFRT_F64:
-      hipLaunchKernelGGL((k_source3d<double>), grid, dim3(BLOCK), 0, st, *program, index, first, n,
-                         static_cast<double*>(rays), stride, fields, field_stride);
+      TFRT_SOURCE3D(double)
       break;
     case TFRT_F16:
-      hipLaunchKernelGGL((k_source3d<_Float16>), grid, dim3(BLOCK), 0, st, *program, index, first, n,
-                         static_cast<_Float16*>(rays), stride, fields, field_stride);
+      TFRT_SOURCE3D(_Float16)
       break;
     default:
       return TFRT_E_BADARG;
   }
+#undef TFRT_SOURCE3D
+  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+}
+
+int tfrt_source3d_pool_rows(const tfrt_source3d_program* program, const int32_t* index,
+                            int64_t first, int64_t n, int32_t* rows, void* stream) {
+  if (n < 0 || !source_program_ok(program) || program->kind != TFRT_SRC_POOL) return TFRT_E_BADARG;
+  if (first < 0 || (index == nullptr && first + n > program->n_rays)) return TFRT_E_BADARG;
+  if (n == 0) return 0;
+  if (rows == nullptr) return TFRT_E_BADARG;
+  hipLaunchKernelGGL(k_pool_rows, dim3(cdiv(n, BLOCK)), dim3(BLOCK), 0,
+                     static_cast<hipStream_t>(stream), *program, index, first, n, rows);
   return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
 }
 

@@ -1222,17 +1222,19 @@ def restore_order(out, perm):
 
 
 def source3d_order(program, n, first=0, face_verts=None, axis=None, out=None, device=None,
-                   stable=True):
+                   stable=True, return_keys=False):
     """``ray_order`` of rays ``first .. first + n`` of a source program (tfrt_source3d_order): the
     rays are never written in source order.  ``stable=False``: the same order up to ties, most
     significant digit first (tfrt_source3d_order_cells) -- fewer launches; rays with the same key may
-    land in an order that varies from run to run."""
+    land in an order that varies from run to run.  ``return_keys``: also the uint32 keys the
+    program's float32 evaluation made (natural order, as int32 bits)."""
     n = int(n)
     dev = device if device is not None else (out.device if out is not None else face_verts.device)
     perm = out if out is not None else torch.empty(n, dtype=torch.int32, device=dev)
     if perm.dtype != torch.int32 or perm.numel() != n or not perm.is_contiguous():
         raise TfrtError("source3d_order: `out` must be a contiguous int32 tensor of n entries")
     _need_gpu(perm, face_verts)
+    keys = torch.empty(n, dtype=torch.int32, device=perm.device) if return_keys else None
     if n:
         L = _lib.lib()
         fv = None if face_verts is None else _c(face_verts.detach(), torch.float64)
@@ -1241,8 +1243,8 @@ def source3d_order(program, n, first=0, face_verts=None, axis=None, out=None, de
         ax = None if axis is None else (ctypes.c_double * 3)(*[float(v) for v in axis])
         fn = L.tfrt_source3d_order if stable else L.tfrt_source3d_order_cells
         check(fn(ctypes.byref(program), int(first), n, _p(fv), 0 if fv is None else fv.shape[0], ax,
-                 _p(perm), None, _p(ws), wsb, _stream(perm)), "tfrt_source3d_order")
-    return perm
+                 _p(perm), _p(keys), _p(ws), wsb, _stream(perm)), "tfrt_source3d_order")
+    return (perm, keys) if return_keys else perm
 
 
 def epoch_advance(counters):
@@ -1297,6 +1299,27 @@ def source3d_generate(program, n, dtype=None, first=0, index=None, rays_out=None
             rays.stride(0) if rays is not None else 0, _p(fl), n if fl is not None else 0,
             _stream(ref)), "tfrt_source3d_generate")
     return rays, fl
+
+
+def source3d_pool_rows(program, n, first=0, index=None, out=None, device=None):
+    """The pool rows the rays ``first + index[j]`` (``first + j``) of a TFRT_SRC_POOL program are made
+    from at its current epoch (tfrt_source3d_pool_rows): (n,) int32 -- what every stored field that
+    is not geometry is gathered through."""
+    n = int(n)
+    dev = device if device is not None else (index.device if index is not None else
+                                             (out.device if out is not None else None))
+    rows = out if out is not None else torch.empty(n, dtype=torch.int32, device=dev)
+    if rows.dtype != torch.int32 or rows.numel() != n or not rows.is_contiguous():
+        raise TfrtError("source3d_pool_rows: `out` must be a contiguous int32 tensor of n entries")
+    if index is not None and (index.dtype != torch.int32 or index.numel() != n
+                              or not index.is_contiguous()):
+        raise TfrtError("source3d_pool_rows: `index` must be a contiguous int32 tensor of n entries")
+    if n:
+        _need_gpu(rows, index)
+        check(_lib.lib().tfrt_source3d_pool_rows(ctypes.byref(program), _p(index), int(first), n,
+                                                 _p(rows), _stream(rows)),
+              "tfrt_source3d_pool_rows")
+    return rows
 
 
 def morton_order(face_verts):

@@ -38,6 +38,13 @@ def _lib_kinds():
 _GEO3 = ("x_start", "y_start", "z_start", "x_end", "y_end", "z_end")
 
 
+def _host_array(value):
+    """A field column as a numpy array on the host (tensors are detached and copied back)."""
+    if isinstance(value, torch.Tensor):
+        return value.detach().cpu().numpy()
+    return np.asarray(value)
+
+
 class DeviceRaySet:
     """The field set of a source whose rays are made by a device program (csrc/tfrt_source.hip):
     a read-only mapping like the reference's source dict (``x_start`` ... ``z_end``,
@@ -147,7 +154,83 @@ class DeviceRaySet:
         return self._src._device_rays(self._first, self._n, self._index, dtype)[0]
 
 
-class SourceBase(RecursivelyUpdatable, ABC):
+class PoolRaySet(DeviceRaySet):
+    """The field set of a device-made ``PrecompiledSource``: geometry from the pool program
+    (TFRT_SRC_POOL: a stored row per ray, re-drawn and jittered every update), every other stored
+    field gathered through the rows the program drew (tfrt_source3d_pool_rows: the same device
+    function, so rows and rays are one draw) -- on first use, memoised until the next update."""
+
+    def keys(self):
+        return list(_GEO3) + [f for f in self._src._pool_fields if f not in _GEO3]
+
+    def rows(self):
+        """(n,) int32: the pool row of every ray of the set, in the set's order."""
+        from . import ops
+        src = self._src
+        return self._memo("__rows__", lambda: ops.source3d_pool_rows(
+            src._dev_program[1], self._n, first=self._first, index=self._index,
+            device=src._dev_device))
+
+    def __getitem__(self, key):
+        src = self._src
+        if key in _GEO3:
+            return DeviceRaySet.__getitem__(self, key)
+        if key not in src._pool_fields:
+            raise KeyError(key)
+        column = src._pool_fields[key]
+        if key in src._pool_uniform:        # one value for every stored ray: an expanded scalar
+            return self._memo_static(key, lambda: column.expand(self._n, *column.shape[1:]))
+        return self._memo(key, lambda: column.index_select(0, self.rows()))
+
+    def _memo_static(self, name, make):
+        """Kept across updates (the engine keys its n(lambda) table by the column's memory)."""
+        cache = self._src._dev_static
+        k = (self._n, name)
+        if k not in cache:
+            cache[k] = make()
+        return cache[k]
+
+
+class _DeviceMade:
+    """What a source whose rays are made by a device program keeps for its ray sets: the views
+    (one per shard / order) and the persistent ray blocks, filled once per update."""
+
+    _ray_set = DeviceRaySet
+
+    def _device_view(self, first, n, index):
+        views = self.__dict__.setdefault("_dev_views", {})
+        k = (first, n, None if index is None else id(index))
+        v = views.get(k)
+        if v is None or (index is not None and v._index is not index):
+            if len(views) > 16:
+                views.clear()
+            v = views[k] = self._ray_set(self, first, n, index)
+        return v
+
+    def _device_rays(self, first, n, index, dtype, fields=False):
+        """Generate (once per update and destination) the ray block of ``dtype`` and / or the
+        float64 field columns of rays ``first + index[j]``."""
+        from . import ops
+        sp = self._dev_program[1]
+        bufs = self.__dict__.setdefault("_dev_buffers", {})
+        ik = None if index is None else (id(index), index._version)
+        rays = fl = None
+        if dtype is not None:
+            bk = (first, n, None if index is None else "index", dtype)
+            ent = bufs.get(bk)
+            if ent is None or ent[0].device != self._dev_device:
+                ent = bufs[bk] = [torch.empty((6, n), dtype=dtype, device=self._dev_device), None, None]
+            if ent[1] != (self._dev_epoch, ik):
+                ops.source3d_generate(sp, n, first=first, index=index, rays_out=ent[0])
+                ent[1], ent[2] = (self._dev_epoch, ik), index
+            rays = ent[0]
+        if fields:
+            _, fl = ops.source3d_generate(sp, n, first=first, index=index, fields=True,
+                                          device=self._dev_device)
+        return rays, fl
+
+
+class SourceBase(_DeviceMade, RecursivelyUpdatable, ABC):
     def __init__(self, extra_fields={}, standard_domains=set(), dense=True,
                  always_resize=False, **kwargs):
         self.extra_fields = extra_fields
@@ -411,38 +494,6 @@ class SourceBase(RecursivelyUpdatable, ABC):
             for d in self._dev_program[3]:
                 d._drawn = {}
                 d.epoch = d.__dict__.get("epoch", 0) + 1
-
-    def _device_view(self, first, n, index):
-        views = self.__dict__.setdefault("_dev_views", {})
-        k = (first, n, None if index is None else id(index))
-        v = views.get(k)
-        if v is None or (index is not None and v._index is not index):
-            if len(views) > 16:
-                views.clear()
-            v = views[k] = DeviceRaySet(self, first, n, index)
-        return v
-
-    def _device_rays(self, first, n, index, dtype, fields=False):
-        """Generate (once per update and destination) the ray block of ``dtype`` and / or the
-        float64 field columns of rays ``first + index[j]``."""
-        from . import ops
-        sp = self._dev_program[1]
-        bufs = self.__dict__.setdefault("_dev_buffers", {})
-        ik = None if index is None else (id(index), index._version)
-        rays = fl = None
-        if dtype is not None:
-            bk = (first, n, None if index is None else "index", dtype)
-            ent = bufs.get(bk)
-            if ent is None or ent[0].device != self._dev_device:
-                ent = bufs[bk] = [torch.empty((6, n), dtype=dtype, device=self._dev_device), None, None]
-            if ent[1] != (self._dev_epoch, ik):
-                ops.source3d_generate(sp, n, first=first, index=index, rays_out=ent[0])
-                ent[1], ent[2] = (self._dev_epoch, ik), index
-            rays = ent[0]
-        if fields:
-            _, fl = ops.source3d_generate(sp, n, first=first, index=index, fields=True,
-                                          device=self._dev_device)
-        return rays, fl
 
     def _wavelength_column(self):
         w = self._wavelengths
@@ -803,10 +854,29 @@ class AperatureSource(SourceBase):
     end_point_distribution = property(lambda self: self._end_point_distribution)
 
 
-class PrecompiledSource(RecursivelyUpdatable):
+class PrecompiledSource(_DeviceMade, RecursivelyUpdatable):
     """A stored ray set, optionally re-sampled / perturbed at each update
     (sources.py:1099-1358).  File format: pickle of
-    ``{"dimension", "standard_domains", "fields": {name: ndarray}}`` (sources.py:1174-1181)."""
+    ``{"dimension", "standard_domains", "fields": {name: ndarray}}`` (sources.py:1174-1181).
+
+    On a HIP device (3-D, ``distributions.set_device_random`` on, a pool that holds the six
+    geometry fields) the source is a device program like the Random* sources
+    (csrc/tfrt_source.hip, TFRT_SRC_POOL): the pool is uploaded once, ``update()`` only steps a
+    device counter, and the rays -- row indices and normal perturbations from the counter-based
+    generator -- are written straight into persistent buffers, in any order (``PoolRaySet``).
+    Elsewhere (CPU, 2-D, ``set_device_random(False)``) the rows are drawn and the pool indexed on
+    the host.  The source takes its four generator streams when it first enters device mode and
+    keeps them; like the Random* distributions among themselves, distributions made after a later
+    ``distributions.seed()`` (which starts the stream numbers again) may then share stream numbers
+    with a source that is still alive -- the seed itself is part of the program, so re-seeding
+    re-draws.
+
+    Two repairs of the host path relative to the parent of this change: the perturbations are drawn
+    from the per-device generator of ``distributions`` (the code named a ``_generator`` that does not
+    exist and raised AttributeError as soon as a perturbation was set), and an empty pool with a
+    perturbation set updates to an empty source instead of raising KeyError."""
+
+    _ray_set = PoolRaySet
 
     def __init__(self, arg, sample_count=100, do_downsample=True, start_perturbation=None,
                  end_perturbation=None, **kwargs):
@@ -819,7 +889,7 @@ class PrecompiledSource(RecursivelyUpdatable):
         elif type(arg) is not int:
             self._dimension = arg._dimension
             self._standard_domains = arg._standard_domains
-            self._full_fields = {k: v.detach().cpu().numpy() for k, v in arg._fields.items()}
+            self._full_fields = {k: _host_array(arg._fields[k]) for k in arg._fields.keys()}
         else:
             self._dimension = arg
             self._standard_domains = set()
@@ -827,6 +897,8 @@ class PrecompiledSource(RecursivelyUpdatable):
         self.start_perturbation = start_perturbation
         self.end_perturbation = end_perturbation
         self._fields = {}
+        self._pool_key, self._pool_records = None, None
+        self._pool_fields, self._pool_uniform = {}, set()
         self.sample_count = sample_count
         self.do_downsample = do_downsample
         RecursivelyUpdatable.__init__(self, **kwargs)
@@ -836,13 +908,174 @@ class PrecompiledSource(RecursivelyUpdatable):
         f = self._full_fields.get("x_start")
         return 0 if f is None else f.shape[0]
 
+    @property
+    def sample_count(self):
+        return self._sample_count
+
+    @sample_count.setter
+    def sample_count(self, val):
+        if isinstance(val, bool) or not isinstance(val, (int, np.integer)):
+            raise ValueError("PrecompiledSource: sample_count must be of integer type.")
+        if val <= 0:
+            raise ValueError("PrecompiledSource: sample_count must be > 0.")
+        self._sample_count = int(val)
+
+    def _perturbation(self, val, which):
+        if val is None:
+            return None
+        try:
+            if isinstance(val, torch.Tensor):
+                val = val.detach().cpu().numpy()
+            p = np.array(np.broadcast_to(np.asarray(val, dtype=np.float64), (self._dimension,)))
+        except (TypeError, ValueError):
+            raise ValueError(f"PrecompiledSource: {which} must be None, scalar, or must have one "
+                             "entry per dimension.") from None
+        if not (np.isfinite(p).all() and (p >= 0.0).all()):
+            raise ValueError(f"PrecompiledSource: {which} holds standard deviations: finite and "
+                             "not negative.")
+        return p
+
+    @property
+    def start_perturbation(self):
+        return self._start_perturbation
+
+    @start_perturbation.setter
+    def start_perturbation(self, val):
+        self._start_perturbation = self._perturbation(val, "start_perturbation")
+
+    @property
+    def end_perturbation(self):
+        return self._end_perturbation
+
+    @end_perturbation.setter
+    def end_perturbation(self, val):
+        self._end_perturbation = self._perturbation(val, "end_perturbation")
+
     def save(self, filename):
         out = {"dimension": self._dimension, "standard_domains": self._standard_domains,
-               "fields": {k: v.detach().cpu().numpy() for k, v in self._fields.items()}}
+               "fields": {k: _host_array(self._fields[k]) for k in self._fields.keys()}}
         with open(filename, "wb") as f:
             pickle.dump(out, f, pickle.HIGHEST_PROTOCOL)
 
+    def from_samples(self, samples):
+        """Fill the pool from a list of field mappings (source snapshots, engine ray sets such as
+        ``engine.finished_rays``, plain dicts): every field is the concatenation, in list order,
+        of the samples' columns; the earlier pool is replaced (sources.py:1254-1269)."""
+        lists = {}
+        for sample in samples:
+            for field in sample.keys():
+                lists.setdefault(field, []).append(_host_array(sample[field]))
+        self._full_fields = {f: np.concatenate(parts, axis=0) for f, parts in lists.items()}
+        self._drop_pool()
+        self._fields = {}
+        self.update()
+
+    def clear(self):
+        """Empty the pool and the fields (sources.py:1271-1273): the source is falsy until filled."""
+        self._full_fields = {}
+        self._fields = {}
+        self._drop_pool()
+
+    def _drop_pool(self):
+        """Forget the uploaded pool and everything made from it: the records and field columns,
+        the program that points at them, the views and their persistent ray blocks."""
+        self._pool_key, self._pool_records = None, None
+        self._pool_fields, self._pool_uniform = {}, set()
+        for name in ("_pool_held", "_dev_program", "_dev_views", "_dev_buffers"):
+            self.__dict__.pop(name, None)
+        self._dev_cache, self._dev_static = {}, {}
+
+    # ------------------------------------------------------------------ device program
+    def _device_mode(self):
+        ff = self._full_fields
+        return (self._dimension == 3 and dist._device_random
+                and config.get_device().type == "cuda" and all(g in ff for g in _GEO3)
+                and self.sampling_domain_size > 0)
+
+    def _upload_pool(self, dev):
+        """Records and field columns of the pool on ``dev``, once per pool (``from_samples`` /
+        ``clear`` / another ``_full_fields`` end it)."""
+        ff = self._full_fields
+        key = (id(ff), tuple((f, id(v)) for f, v in ff.items()), str(dev))
+        if self._pool_key == key:
+            return
+        n = self.sampling_domain_size
+        rec = np.empty((n, 6), dtype=np.float64)       # one 48-byte record per stored ray
+        for k, g in enumerate(_GEO3):
+            rec[:, k] = np.asarray(ff[g], dtype=np.float64).reshape(n)
+        self._pool_records = torch.from_numpy(rec).to(dev)
+        self._pool_fields, self._pool_uniform = {}, set()
+        for f, v in ff.items():
+            if f in _GEO3:
+                self._pool_fields[f] = None            # (made by the program)
+                continue
+            v = np.ascontiguousarray(v)
+            if f == "wavelength" and v.ndim == 1 and n > 1 and bool((v == v[0]).all()):
+                v = v[:1]
+                self._pool_uniform.add(f)
+            self._pool_fields[f] = torch.from_numpy(v).to(dev)
+        self._pool_key = key
+        self._pool_held = (ff, list(ff.values()))      # (the keyed ids stay their own)
+        self._dev_static = {}
+
+    def _enter_device(self):
+        from . import _lib, ops
+        dev = config.get_device()
+        self._upload_pool(dev)
+        ep = self.__dict__.get("_epoch_dev")
+        if ep is None or ep.device != self._pool_records.device:
+            self._epoch_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+            # (the rows draw on one stream of the seed, the normals of the three axes on the next three)
+            self._stream_id = dist._streams[0] + 1
+            dist._streams[0] += 4
+        down = bool(self.do_downsample)
+        n = int(self._sample_count) if down else self.sampling_domain_size
+        sig = [tuple(float(v) for v in (np.zeros(3) if p is None else p))
+               for p in (self._start_perturbation, self._end_perturbation)]
+        key = ("pool", self._pool_records.data_ptr(), self.sampling_domain_size, n, down, sig[0],
+               sig[1], dist._seed, self._stream_id, self._epoch_dev.data_ptr())
+        cached = self.__dict__.get("_dev_program")
+        fresh = cached is None or cached[0] != key
+        if fresh:
+            sp = _lib.Source3DProgram()
+            sp.kind = _lib.SRC_POOL
+            sp.n_rays = n
+            sp.pool = self._pool_records.data_ptr()
+            sp.pool_count = self.sampling_domain_size
+            for k in range(3):
+                sp.sigma_start[k], sp.sigma_end[k] = sig[0][k], sig[1][k]
+            sp.pool_downsample = 1 if down else 0
+            sp.pool_stream = self._stream_id
+            sp.pool_seed = dist._seed & 0xFFFFFFFFFFFFFFFF
+            sp.pool_epoch = self._epoch_dev.data_ptr()
+            self._dev_program = (key, sp, [self._pool_records, self._epoch_dev], [])
+        redrawn = down or any(v > 0.0 for v in sig[0] + sig[1])
+        if redrawn:
+            ops.epoch_advance([self._epoch_dev])       # (captured with the step's update())
+        if redrawn or fresh or not isinstance(self._fields, DeviceRaySet):
+            self._dev_epoch = self.__dict__.get("_dev_epoch", 0) + 1
+            self._dev_cache = {}
+        self._dev_n, self._dev_program_key, self._dev_device = n, key, dev
+        self._fields = self._device_view(0, n, None)
+
+    @property
+    def device_mode(self):
+        """True while the rays are made by the device program (see the class comment)."""
+        return isinstance(self._fields, DeviceRaySet)
+
+    def note_external_update(self):
+        """The epoch counter was stepped without Python (a replayed launch graph of an optimiser
+        step): forget what was materialised for earlier draws."""
+        if isinstance(self._fields, DeviceRaySet):
+            self._dev_epoch += 1
+            self._dev_cache = {}
+
     def _update(self):
+        if self._device_mode():
+            self._enter_device()
+            return
+        if isinstance(self._fields, DeviceRaySet):
+            self._fields = {}
         dev = config.get_device()
         n = self.sampling_domain_size
         if self.do_downsample and n > 0:
@@ -857,15 +1090,18 @@ class PrecompiledSource(RecursivelyUpdatable):
                 continue
             p = np.broadcast_to(np.asarray(pert, dtype=np.float64), (self._dimension,))
             for a, sd in zip("xyz"[: self._dimension], p):
-                f = self._fields[a + suffix]
-                noise = torch.randn(f.shape, dtype=torch.float64, generator=dist._generator
-                                    if dist._generator is not None else None).to(dev)
+                f = self._fields.get(a + suffix)
+                if f is None:                # (an empty pool, to be filled by from_samples)
+                    continue
+                gen, gdev = dist._generator_for(dev)
+                noise = torch.randn(f.shape, dtype=torch.float64, generator=gen, device=gdev)
                 self._fields[a + suffix] = f + float(sd) * noise
 
     def _generate_update_handles(self):
         return []
 
     dimension = property(lambda self: self._dimension)
+    standard_domains = property(lambda self: self._standard_domains)
 
     def __getitem__(self, key):
         return self._fields[key]

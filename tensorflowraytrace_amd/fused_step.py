@@ -19,17 +19,23 @@ states that form declaratively; an optimiser given a ``GoalError`` runs ``FusedS
     system.update()                     constraints, parameters -> faces   (torch + tfrt_param_faces_*)
     tfrt_trace3d_forward                into persistent buffers, counts stay on the device
     tfrt_goal_error3d                   error sum (fixed order) + gradient seed 2 (output - goal)
-    tfrt_trace3d_backward               -> d error / d faces
+    tfrt_trace3d_backward               -> d error / d faces   (coherent rays: both as ONE launch,
+                                        tfrt_trace3d_backward_goal)
     autograd through update()           -> d error / d parameters           (tfrt_param_faces_backward ...)
     [one all-reduce over ray shards]
     tfrt_sgd_process_dev / tfrt_csr_matvec   non-finite -> 0, scale, clip, accumulate, SGD apply
                                         (tfrt_sgd_momentum_multi with apply_momentum=True)
 
-A 2-D engine (one process, no ray shards) runs ``_enqueue_gradient2d`` instead:
+A 2-D engine (one process, no ray shards) runs ``FusedStep._goal2d`` instead of ``_goal3d``:
 ``tfrt_trace2d_forward``, then ``tfrt_trace2d_backward_goal`` -- error, seed and the reverse sweep of
 every pass in ONE launch -- and autograd from the merged segments and arcs to the parameters.  With a
-``RowwiseError`` the error comes from ``tfrt_trace2d_rows`` (every source ray's fixed-shape column),
-``fn`` and its autograd, and ``tfrt_trace2d_backward_rows`` sweeps from that gradient.
+``RowwiseError`` (``_rowwise2d``) the error comes from ``tfrt_trace2d_rows`` (every source ray's
+fixed-shape column), ``fn`` and its autograd, and ``tfrt_trace2d_backward_rows`` sweeps from that
+gradient; ``_rowwise3d`` does the same on a 3-D engine with an in-place trace that leaves the
+finished rows at the rays' own columns.
+
+The four bodies share one skeleton: ``_enqueue_gradient`` does what comes before the trace, the
+body its launches over a ``_StepState``, ``_publish_lazily`` and ``_enqueue_apply`` what comes after.
 
 Every launch has step-independent arguments (learning-rate dependent scalars live in a small
 device table), so after a few eager steps the sequence is captured once in a HIP graph
@@ -220,6 +226,87 @@ class _HyperTable:
         self._current = rows
 
 
+
+class _Override:
+    """``with _override(sc, field=value, ...)``: sets fields of a scene struct for the span of the
+    block and puts back the values they had, also when the block raises.  The struct is cached by
+    the scene and shared with every other trace of it: whatever a step points it at (its gradient
+    blocks, the block the trace's set-up launch clears, the in-place mode of this trace) must be
+    gone when the step's launches are enqueued."""
+    __slots__ = ("_sc", "_new", "_old")
+
+    def __init__(self, sc, fields):
+        self._sc, self._new = sc, fields
+
+    def __enter__(self):
+        sc = self._sc
+        self._old = [(name, getattr(sc, name)) for name in self._new]
+        for name, value in self._new.items():
+            setattr(sc, name, value)
+        return sc
+
+    def __exit__(self, *exc):
+        for name, value in self._old:
+            setattr(self._sc, name, value)
+        return False
+
+
+def _override(sc, **fields):
+    return _Override(sc, fields)
+
+
+class _StepState:
+    """The persistent buffers of one signature -- outputs, tape, seeds and gradient blocks of the
+    trace -- and what the last enqueued step left for publishing its ray sets."""
+    __slots__ = (
+        "sig", "dim", "N", "M", "Ms", "Ma", "P", "dt", "flags", "capN",
+        "full", "aux", "outs", "no_outs", "counts", "ints", "ws", "wsb",
+        "err", "goal_ws", "gws", "fields",
+        "g_fin", "g_fv", "g_n",                              # 3-D gradient blocks
+        "g_prim", "g_seg", "g_arc", "g_index",               # 2-D: one block, views into it
+        "rows", "row_face", "row_passes", "row_outs",        # a RowwiseError's fixed-shape columns
+        "chain_ws", "inherited",                             # made on first use
+        "block", "stream", "perm", "inplace")                # of the last enqueued step
+
+    def __init__(self, sig, block, dim, P, flags, fields, workspace_bytes):
+        """What 2-D and 3-D share, for ray blocks of ``2 * dim`` rows.  ``fields``: the rows the
+        error is read from; ``workspace_bytes``: (of the trace, of the error sum)."""
+        for name in self.__slots__:
+            setattr(self, name, None)
+        n_rows, dev = 2 * dim, block.device
+        N = block.shape[1]
+        capN = max(N, 1)
+        self.sig, self.dim, self.N, self.P, self.flags, self.capN = sig, dim, N, P, flags, capN
+        self.dt = ops._DT[block.dtype]
+        ints = ops._IntPool(dev, True, _lib.COUNTS_PER_PASS * (P + 1), flags, capN, P)
+        caps = {"finished": capN, "active": capN * max(P, 1), "stopped": capN, "dead": capN}
+        full, aux, outs = {}, {"counts": ints.counts}, {}
+        for name, flag in _CLASS_FLAGS:
+            if flags & flag:
+                rays = torch.empty((n_rows, caps[name]), dtype=block.dtype, device=dev)
+                ids, faces = ints.take(caps[name]), ints.take(caps[name])
+                full[name], aux[name + "_id"], aux[name + "_face"] = rays, ids, faces
+                outs[name] = ops._ray_out(rays, ids, faces)
+            else:
+                aux[name + "_id"] = aux[name + "_face"] = None
+                outs[name] = ops._ray_out(None, None, None)
+        # the rays still active after the last pass are not copied out by a fused step
+        aux["unfinished"] = torch.empty((n_rows, 0), dtype=block.dtype, device=dev)
+        aux["unfinished_id"] = torch.empty(0, dtype=torch.int32, device=dev)
+        self.full, self.aux, self.outs = full, aux, outs
+        self.no_outs = {name: ops._ray_out(None, None, None) for name, _ in _CLASS_FLAGS}
+        self.counts, self.ints = ints.counts, ints
+        wsb, gws = workspace_bytes
+        self.ws, self.wsb = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev), wsb
+        self.err = torch.zeros(3, dtype=torch.float64, device=dev)
+        self.goal_ws, self.gws = torch.zeros(max(gws, 1), dtype=torch.uint8, device=dev), gws
+        self.fields = (ctypes.c_int32 * n_rows)(*(list(fields) + [0] * n_rows)[:n_rows])
+
+    def __getitem__(self, name):
+        """``state["N"]``: the fields by name, as bench.py and the tests read them."""
+        return getattr(self, name)
+
+
 class FusedStep:
     """Runs ``SGD_Optimizer.single_step`` for a ``GoalError`` or a ``RowwiseError`` as a fixed
     launch sequence, on 3-D engines and on 2-D ones (one process); see the module docstring.
@@ -243,15 +330,25 @@ class FusedStep:
         self.opt = optimizer
         self.graph_mode = graph           # "auto" / True: capture after the warm-up; False: never
         self.graph_warmup = int(graph_warmup)
-        self._state = None                # persistent buffers of the current signature
-        self._graphs = None               # (signature, graph A, graph B or None)
+        self._state = None                # _StepState of the current signature
+        self._graphs = None               # (signature, graph A, graph B or None, grads)
+        self._stream = None               # the side stream steps are captured on
+        self._last_sig = None             # signature of the last eager step
         self._eager_steps = 0
         self.tests_total = None           # device int64: ray-face tests of all fused steps
         self.steps = 0
         self.graph_replays = 0
         self.capture_error = None
+        self.collective_capture_error = None
         self.untapped = False             # a parameter reached the faces without boundaries.tap
         self._tap_checks = 0              # eager steps that compared leaf and alias gradients
+        self._goal_perm = None            # the goal rows in the trace's (coherent) order, keyed
+        self._goal_pending = None         # (error sum left to the update's launch, its stream)
+        self._hyper = self._hyper_apply = None    # _HyperTable of the update / of an accumulated one
+        self._err_view = None             # {sum, terms, mean} of the last step
+        # several ranks: [gradients, error sums] as the collective reduces them
+        self._flat_buf = self._flat = self._err_sink = None
+        self._flat_views = False
 
     # ------------------------------------------------------------------------ eligibility
     @staticmethod
@@ -302,205 +399,246 @@ class FusedStep:
                 and not getattr(eng, "_rowwise_off", False))
 
     # -------------------------------------------------------------------------- buffers
-    def _buffers(self, block, fv, P, flags, dt, index=False):
-        """Persistent outputs / tape / seeds of the trace for this (N, M, P, dtype, flags);
-        ``index``: the (2, M) block of d error / d (n_in, n_out) too."""
+    def _buffers(self, block, fv, P, flags, index=False):
+        """The state of a 3-D trace for this (N, M, P, dtype, flags), made when the signature
+        changes; ``index``: with the (2, M) block of d error / d (n_in, n_out) too."""
         N, M = block.shape[1], fv.shape[0]
+        dt = ops._DT[block.dtype]
         # (the error function's rows are baked into `fields` and into which rows of g_fin are
         # ever written: another GoalError gets fresh, zeroed buffers)
-        sig = (N, M, P, dt, flags, str(block.device), tuple(self.opt.error_function.rows),
-               bool(index))
+        rows = self.opt.error_function.rows
+        sig = (N, M, P, dt, flags, str(block.device), tuple(rows), bool(index))
         st = self._state
-        if st is not None and st["sig"] == sig:
-            return st
-        dev = block.device
-        L = _lib.lib()
-        wsb = L.tfrt_trace3d_workspace_bytes(N, M, P, dt)
-        capN = max(N, 1)
-        ints = ops._IntPool(dev, True, _lib.COUNTS_PER_PASS * (P + 1), flags, capN, P)
-        caps = {"finished": capN, "active": capN * max(P, 1), "stopped": capN, "dead": capN}
-        full, aux, outs = {}, {"counts": ints.counts}, {}
-        for name, flag in _CLASS_FLAGS:
-            if flags & flag:
-                rays = torch.empty((6, caps[name]), dtype=block.dtype, device=dev)
-                ids, faces = ints.take(caps[name]), ints.take(caps[name])
-                full[name], aux[name + "_id"], aux[name + "_face"] = rays, ids, faces
-                outs[name] = ops._ray_out(rays, ids, faces)
-            else:
-                aux[name + "_id"] = aux[name + "_face"] = None
-                outs[name] = ops._ray_out(None, None, None)
-        # the rays still active after the last pass are not copied out by a fused step
-        aux["unfinished"] = torch.empty((6, 0), dtype=block.dtype, device=dev)
-        aux["unfinished_id"] = torch.empty(0, dtype=torch.int32, device=dev)
-        gws = L.tfrt_goal_error3d_workspace_bytes(capN)
-        st = dict(
-            sig=sig, N=N, M=M, P=P, dt=dt, flags=flags, capN=capN, full=full, aux=aux, outs=outs,
-            ws=torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev), wsb=wsb,
-            counts=ints.counts, ints=ints,
-            g_fin=torch.zeros((6, capN), dtype=torch.float64, device=dev),
-            g_fv=torch.zeros((max(M, 1), 9), dtype=torch.float64, device=dev),
-            g_n=torch.zeros((2, max(M, 1)), dtype=torch.float64, device=dev) if index else None,
-            err=torch.zeros(3, dtype=torch.float64, device=dev),
-            goal_ws=torch.zeros(max(gws, 1), dtype=torch.uint8, device=dev), gws=gws,
-            fields=(ctypes.c_int32 * 6)(*(self.opt.error_function.rows + [0] * 6)[:6]),
-            no_outs={name: ops._ray_out(None, None, None) for name, _ in _CLASS_FLAGS},
-        )
+        if st is None or st.sig != sig:
+            L = _lib.lib()
+            st = _StepState(sig, block, 3, P, flags, rows,
+                            (L.tfrt_trace3d_workspace_bytes(N, M, P, dt),
+                             L.tfrt_goal_error3d_workspace_bytes(max(N, 1))))
+            dev = block.device
+            st.M = M
+            st.g_fin = torch.zeros((6, st.capN), dtype=torch.float64, device=dev)
+            st.g_fv = torch.zeros((max(M, 1), 9), dtype=torch.float64, device=dev)
+            if index:
+                st.g_n = torch.zeros((2, max(M, 1)), dtype=torch.float64, device=dev)
+            self._install(st)
+        st.block, st.stream = block, ops._stream(block)
+        return st
+
+    def _buffers2d(self, block, det, P, flags, rows, index):
+        """The state of a 2-D trace over the (detached) merged segments and arcs ``det`` for this
+        (N, Ms, Ma, P, dtype, flags, fields).  ``rows``: the ray-block rows of a GoalError's
+        fields, None for a RowwiseError (which gets its fixed-shape columns); ``index``: which of
+        (seg_n_in, seg_n_out, arc_n_in, arc_n_out) take a gradient."""
+        N = block.shape[1]
+        Ms, Ma = (0 if g is None else g.shape[0] for g in det)
+        dt = ops._DT[block.dtype]
+        index = tuple(i is not None for i in index)
+        sig = (2, N, Ms, Ma, P, dt, flags, str(block.device), tuple(rows or ()), rows is None,
+               index)
+        st = self._state
+        if st is None or st.sig != sig:
+            L = _lib.lib()
+            st = _StepState(sig, block, 2, P, flags, rows or (),
+                            (L.tfrt_trace2d_workspace_bytes(N, Ms, Ma, P, dt),
+                             L.tfrt_trace2d_backward_goal_workspace_bytes(N)))
+            dev = block.device
+            st.Ms, st.Ma = Ms, Ma
+            # (segment and arc gradients in one block, the index gradients asked for behind them:
+            # one clearing launch per step)
+            n_index = 2 * (Ms + Ma) if any(index) else 0
+            at = 4 * Ms + 5 * Ma
+            g = st.g_prim = torch.zeros(max(at + n_index, 1), dtype=torch.float64, device=dev)
+            st.g_seg, st.g_arc = g[:4 * Ms].view(Ms, 4), g[4 * Ms:at].view(Ma, 5)
+            st.g_index = [None] * 4
+            if n_index:
+                cuts = (at, at + Ms, at + 2 * Ms, at + 2 * Ms + Ma, at + n_index)
+                st.g_index = [g[a:b] if want else None
+                              for a, b, want in zip(cuts, cuts[1:], index)]
+            if rows is None:
+                # (every column is written by each step's tfrt_trace2d_rows: no clearing)
+                st.rows = torch.empty((4, st.capN), dtype=block.dtype, device=dev)
+                st.row_face = torch.empty(st.capN, dtype=torch.int32, device=dev)
+            self._install(st)
+        st.block, st.stream = block, ops._stream(block)
+        return st
+
+    def _install(self, st):
+        """New buffers: whatever was captured wrote into the old ones."""
         self._state = st
         self._graphs = None
+        dev = st.err.device
         if self.tests_total is None or self.tests_total.device != dev:
             self.tests_total = torch.zeros(1, dtype=torch.int64, device=dev)
-        return st
+
+    # ------------------------------------------------------- the C-ABI entries called twice
+    def _lengths(self):
+        eng = self.opt.engine
+        return float(eng.new_ray_length), float(eng.dead_ray_length or 0.0)
+
+    def _trace_forward(self, st, sc, outs):
+        """tfrt_trace3d_forward / tfrt_trace2d_forward (one argument list) of the step's rays into
+        the ray sets ``outs``; counts and tape stay on the device."""
+        name = "tfrt_trace3d_forward" if st.dim == 3 else "tfrt_trace2d_forward"
+        block = st.block
+        check(getattr(_lib.lib(), name)(
+            ops._p(block), block.shape[1], st.N, ctypes.byref(sc), *self._lengths(), st.P, st.dt,
+            st.flags, ctypes.byref(outs["finished"]), ctypes.byref(outs["active"]),
+            ctypes.byref(outs["stopped"]), ctypes.byref(outs["dead"]),
+            None, None,      # (the rays still active after the last pass are not copied out)
+            ops._p(st.counts), ops._p(st.ws), st.wsb, st.stream), name)
+
+    def _trace3d_backward(self, st, sc, seeds, capacity):
+        """tfrt_trace3d_backward from the finished rays' gradient ``seeds`` (6, capacity) into the
+        face-gradient block (and the index block the struct points at)."""
+        block = st.block
+        check(_lib.lib().tfrt_trace3d_backward(
+            ops._p(block), block.shape[1], st.N, ctypes.byref(sc), *self._lengths(), st.P, st.dt,
+            ops._p(seeds), capacity, None, 0, None, 0, None, 0, ops._p(st.g_fv), None,
+            ops._p(st.counts), ops._p(st.ws), st.wsb, st.stream), "tfrt_trace3d_backward")
+
+    @staticmethod
+    def _goal_finish(pending, stream):
+        """The second stage of an error sum (the launch tfrt_goal_error3d would have made)."""
+        check(_lib.lib().tfrt_goal_finish(ctypes.byref(pending), stream), "tfrt_goal_finish")
 
     # ---------------------------------------------------------------- the launch sequence
     def _enqueue_gradient(self):
         """update -> trace -> error -> reverse sweep -> parameter gradients.  Returns
         (grads, error tensor {sum, terms, mean}).  Nothing here waits for the device."""
         opt, eng = self.opt, self.opt.engine
-        if eng.dimension == 2:
-            return self._enqueue_gradient2d()
-        system = eng.optical_system
         eng.clear_ray_history()
         from . import boundaries
         with boundaries.collect_taps() as tap_log:
-            system.update()
+            eng.optical_system.update()
         src = eng._source_set()
         if not src:
             raise RuntimeError("FusedStep: the optical system has no source rays")
-        erf = opt.error_function
-        block, scene, fv = eng._trace_inputs(src)
-        perm = eng._trace_perm
-        if isinstance(erf, RowwiseError):
-            return self._enqueue_rowwise(erf, src, block, scene, fv, perm, tap_log)
-        goal_by_ray = False       # (N, fields) rows instead of (fields, N) columns
-        if perm is None:
-            goal = erf.table(src)
-        else:
-            # coherent order: the trace runs over src[perm] (its ray ids are positions in that
-            # order), so the goal rows go along; the ray sets are restored when somebody asks
-            # (keyed by the goal TABLE, not by the geometry the order was made from: a goal may
-            # read any source field, and erf.table() is itself cached by the versions of all of
-            # them -- a field changed in place re-evaluates it and, through the key, re-gathers)
-            rowwise = bool(erf.rowwise and callable(erf.goal) and hasattr(src, "permuted"))
-            base = None if rowwise else erf.table(src)
-            gkey = (id(erf), src.cache_key if rowwise else id(base), id(perm), rowwise)
-            cached = getattr(self, "_goal_perm", None)
-            if cached is None or cached[0] != gkey:
-                if rowwise:
-                    # made in the trace's order, left in the layout the callable returns
-                    rows, by_ray = erf.table(src.permuted(perm), by_ray=True), True
-                else:
-                    rows, by_ray = ops.gather_rows(base, perm), False
-                cached = self._goal_perm = (gkey, rows, perm, by_ray, base)   # (holds `base`: its id stays its own)
-            goal, goal_by_ray = cached[1], cached[3]
+        inputs = eng._trace_inputs(src)
         P, flags = int(opt.trace_depth), eng._flags() | _lib.COMPILE_FINISHED
-        dt = ops._DT[block.dtype]
-        fvc = fv.detach()
-        if fvc.dtype != torch.float64 or not fvc.is_contiguous():
-            raise RuntimeError("FusedStep: merged faces must be contiguous float64")
+        rowwise = isinstance(opt.error_function, RowwiseError)
+        if eng.dimension == 2:
+            body = self._rowwise2d if rowwise else self._goal2d
+        else:
+            body = self._rowwise3d if rowwise else self._goal3d
+        grads, st = body(src, inputs, tap_log, P, flags)
+        self._publish_lazily(st, src)
+        return ([None] * len(opt.parameters) if grads is None else grads), st.err
+
+    # ------------------------------------------------------------------------------ 3-D
+    def _goal3d(self, src, inputs, tap_log, P, flags):
+        """tfrt_trace3d_forward -> error + gradient seed -> reverse sweep; coherent rays: the last
+        two as one launch, and from 64 rays on the trace in place."""
+        erf = self.opt.error_function
+        block, scene, fv = inputs
+        perm = self.opt.engine._trace_perm
+        goal, goal_by_ray = self._goal_rows(erf, src, perm)
+        fvc = self._faces(fv)
         index = self._index3d(scene, fvc)
-        st = self._buffers(block, fvc, P, flags, dt, any(n is not None for n in index))
-        sink = getattr(self, "_err_sink", None)
-        if tdist.is_distributed() and sink is not None and st["err"].data_ptr() != sink.data_ptr():
-            st["err"] = sink             # (the error sums land in the collective's buffer)
-        L = _lib.lib()
-        stream = ops._stream(block)
+        st = self._buffers(block, fvc, P, flags, any(n is not None for n in index))
+        sink = self._err_sink
+        if tdist.is_distributed() and sink is not None and st.err.data_ptr() != sink.data_ptr():
+            st.err = sink               # (the error sums land in the collective's buffer)
         sc = scene.struct(fvc)
-        o = st["outs"]
         # (the reverse sweep runs for the faces or the indices; it is given the face-gradient block
         # either way: the in-place chain sums its face terms per wavefront into it)
-        need_back = bool((fv.requires_grad or st["g_n"] is not None) and st["M"] > 0)
+        need_back = bool((fv.requires_grad or st.g_n is not None) and st.M > 0)
         # coherent rays: error, gradient seed and the whole reverse sweep are ONE launch
         # (tfrt_trace3d_backward_goal); the face-gradient block it accumulates into is cleared by
         # the trace's set-up launch
         folded = bool(self.fold_backward and need_back and sc.coherent_rays
                       and not sc.deterministic and 1 <= P <= 8)
-        self.folded_backward = folded
         # all passes in one launch, rays in place (tfrt_scene3d.in_place): the folded reverse sweep
         # needs no ray set, so none is compacted here -- _publish_lazily does it if somebody asks
-        inplace = bool(folded and sc.in_place and st["N"] >= 64 and P >= 1)
-        self.in_place = inplace
-        if not inplace:
-            sc.in_place = 0
-        if folded:
-            sc.clear_buffer, sc.clear_count = st["g_fv"].data_ptr(), st["g_fv"].numel()
-        fo = st["no_outs"] if inplace else o
-        try:
-            check(L.tfrt_trace3d_forward(
-                ops._p(block), block.shape[1], st["N"], ctypes.byref(sc), float(eng.new_ray_length),
-                float(eng.dead_ray_length or 0.0), P, dt, flags, ctypes.byref(fo["finished"]),
-                ctypes.byref(fo["active"]), ctypes.byref(fo["stopped"]), ctypes.byref(fo["dead"]),
-                None, None,      # (the rays still active after the last pass are not copied out)
-                ops._p(st["counts"]), ops._p(st["ws"]), st["wsb"], stream), "tfrt_trace3d_forward")
-        finally:
-            # (the struct is cached by the scene: nobody else's trace clears our block)
-            sc.clear_buffer, sc.clear_count = None, 0
-        fin = st["full"]["finished"]
-        # error + gradient seed; the same launch clears the face-gradient block the reverse sweep
-        # accumulates into and adds the trace's test count to the running total
-        # (one rank: nothing on the device waits for the error sum, so its second stage is left
-        # to the parameter update's launch -- _enqueue_apply --; with several ranks the sum goes
-        # into the collective and is finished here)
-        goal_args = (
-            ops._p(fin), st["capN"], ops._p(st["aux"]["finished_id"]), dt, ops._p(st["counts"]), P,
-            st["fields"], len(erf.rows), ops._p(goal),
-            1 if goal_by_ray else goal.shape[1], goal.shape[1] if goal_by_ray else 1,
-            ops._p(st["g_fin"]),
-            ops._p(st["err"]), ops._p(st["g_fv"]) if need_back else None,
-            st["g_fv"].numel() if need_back else 0, ops._p(self.tests_total),
-            ops._p(st["goal_ws"]), st["gws"])
-        self._goal_pending = None
-        self._set_index_grads3d(sc, st, need_back)
-        try:
-            grads = self._backward3d(st, sc, block, goal, goal_by_ray, goal_args, folded, need_back,
-                                     erf, P, dt, stream, L, eng, fv, index, tap_log)
-        finally:
-            self._set_index_grads3d(sc, st, False)
-        self._publish_lazily(st, src, P, flags, perm, (block, float(eng.dead_ray_length or 0.0))
-                             if inplace else None)
-        # (publish() inverts `perm` when it runs: a replayed graph re-orders a re-drawn source into
-        # the same tensor behind Python's back)
-        return grads, st["err"]
+        inplace = bool(folded and sc.in_place and st.N >= 64 and P >= 1)
+        self.folded_backward, self.in_place = folded, inplace
+        st.perm = perm
+        st.inplace = (block, self._lengths()[1]) if inplace else None
+        clear = {"clear_buffer": st.g_fv.data_ptr(), "clear_count": st.g_fv.numel()} if folded \
+            else {}
+        # (in_place: the reverse sweep is given the same value as the forward)
+        with _override(sc, in_place=1 if inplace else 0):
+            with _override(sc, **clear):
+                self._trace_forward(st, sc, st.no_outs if inplace else st.outs)
+            with self._index_grads3d(sc, st, need_back):
+                self._goal_backward3d(st, sc, (goal, goal_by_ray), folded, need_back)
+        if not need_back:
+            return None, st
+        return self._parameter_gradients(*self._outs3d(fv, st, index), tap_log), st
 
-    def _backward3d(self, st, sc, block, goal, goal_by_ray, goal_args, folded, need_back, erf, P,
-                    dt, stream, L, eng, fv, index, tap_log):
-        """Error, seed and reverse sweep of _enqueue_gradient, then the parameter gradients."""
-        o = st["outs"]
-        if folded:
-            if "chain_ws" not in st:
-                cwb = L.tfrt_trace3d_backward_goal_workspace_bytes(st["N"])
-                st["chain_ws"] = (torch.zeros(max(cwb, 1), dtype=torch.uint8, device=block.device), cwb)
-            pending = _lib.GoalPending()
-            check(L.tfrt_trace3d_backward_goal(
-                ops._p(block), block.shape[1], st["N"], ctypes.byref(sc),
-                float(eng.new_ray_length), float(eng.dead_ray_length or 0.0), P, dt,
-                ctypes.byref(o["finished"]), st["fields"], len(erf.rows), ops._p(goal),
-                1 if goal_by_ray else goal.shape[1], goal.shape[1] if goal_by_ray else 1,
-                ops._p(st["err"]), ops._p(self.tests_total), ops._p(st["chain_ws"][0]),
-                st["chain_ws"][1], ctypes.byref(pending), None, 0, None, 0, None, 0,
-                ops._p(st["g_fv"]), None, ops._p(st["counts"]), ops._p(st["ws"]), st["wsb"],
-                stream), "tfrt_trace3d_backward_goal")
-            if tdist.is_distributed():      # (the sum goes into the collective: finished here)
-                check(L.tfrt_goal_finish(ctypes.byref(pending), stream), "tfrt_goal_finish")
+    def _goal_rows(self, erf, src, perm):
+        """The goal table of the step's rays and whether it is (N, fields) rows instead of
+        (fields, N) columns."""
+        if perm is None:
+            return erf.table(src), False
+        # coherent order: the trace runs over src[perm] (its ray ids are positions in that
+        # order), so the goal rows go along; the ray sets are restored when somebody asks
+        # (keyed by the goal TABLE, not by the geometry the order was made from: a goal may
+        # read any source field, and erf.table() is itself cached by the versions of all of
+        # them -- a field changed in place re-evaluates it and, through the key, re-gathers)
+        rowwise = bool(erf.rowwise and callable(erf.goal) and hasattr(src, "permuted"))
+        base = None if rowwise else erf.table(src)
+        gkey = (id(erf), src.cache_key if rowwise else id(base), id(perm), rowwise)
+        cached = self._goal_perm
+        if cached is None or cached[0] != gkey:
+            if rowwise:
+                # made in the trace's order, left in the layout the callable returns
+                rows, by_ray = erf.table(src.permuted(perm), by_ray=True), True
             else:
-                self._goal_pending = (pending, stream)
-        elif tdist.is_distributed():
-            check(L.tfrt_goal_error3d(*goal_args, stream), "tfrt_goal_error3d")
+                rows, by_ray = ops.gather_rows(base, perm), False
+            cached = self._goal_perm = (gkey, rows, perm, by_ray, base)   # (holds `base`: its id stays its own)
+        return cached[1], cached[3]
+
+    def _goal_backward3d(self, st, sc, goal_rows, folded, need_back):
+        """Error, gradient seed and reverse sweep of _goal3d.  One rank: nothing on the device
+        waits for the error sum, so its second stage is left to the parameter update's launch
+        (_enqueue_apply); with several ranks the sum goes into the collective and is finished
+        here."""
+        L = _lib.lib()
+        goal, by_ray = goal_rows
+        n_fields = len(self.opt.error_function.rows)
+        strides = (1, goal.shape[1]) if by_ray else (goal.shape[1], 1)
+        block, stream = st.block, st.stream
+        several = tdist.is_distributed()
+        pending = _lib.GoalPending()
+        self._goal_pending = None
+        if folded:
+            if st.chain_ws is None:
+                cwb = L.tfrt_trace3d_backward_goal_workspace_bytes(st.N)
+                st.chain_ws = (torch.zeros(max(cwb, 1), dtype=torch.uint8, device=block.device), cwb)
+            check(L.tfrt_trace3d_backward_goal(
+                ops._p(block), block.shape[1], st.N, ctypes.byref(sc), *self._lengths(), st.P,
+                st.dt, ctypes.byref(st.outs["finished"]), st.fields, n_fields, ops._p(goal),
+                *strides, ops._p(st.err), ops._p(self.tests_total), ops._p(st.chain_ws[0]),
+                st.chain_ws[1], ctypes.byref(pending), None, 0, None, 0, None, 0,
+                ops._p(st.g_fv), None, ops._p(st.counts), ops._p(st.ws), st.wsb, stream),
+                "tfrt_trace3d_backward_goal")
+            if several:
+                self._goal_finish(pending, stream)
         else:
-            pending = _lib.GoalPending()
-            check(L.tfrt_goal_error3d_deferred(*goal_args, ctypes.byref(pending), stream),
-                  "tfrt_goal_error3d_deferred")
+            # error + gradient seed; the same launch clears the face-gradient block the reverse
+            # sweep accumulates into and adds the trace's test count to the running total
+            goal_args = (
+                ops._p(st.full["finished"]), st.capN, ops._p(st.aux["finished_id"]), st.dt,
+                ops._p(st.counts), st.P, st.fields, n_fields, ops._p(goal), *strides,
+                ops._p(st.g_fin), ops._p(st.err), ops._p(st.g_fv) if need_back else None,
+                st.g_fv.numel() if need_back else 0, ops._p(self.tests_total),
+                ops._p(st.goal_ws), st.gws)
+            if several:
+                check(L.tfrt_goal_error3d(*goal_args, stream), "tfrt_goal_error3d")
+            else:
+                check(L.tfrt_goal_error3d_deferred(*goal_args, ctypes.byref(pending), stream),
+                      "tfrt_goal_error3d_deferred")
+        if not several:
             self._goal_pending = (pending, stream)
-        grads = [None] * len(self.opt.parameters)
-        if need_back:
-            if not folded:
-                check(L.tfrt_trace3d_backward(
-                    ops._p(block), block.shape[1], st["N"], ctypes.byref(sc),
-                    float(eng.new_ray_length), float(eng.dead_ray_length or 0.0), P, dt,
-                    ops._p(st["g_fin"]), st["capN"], None, 0, None, 0, None, 0, ops._p(st["g_fv"]),
-                    None, ops._p(st["counts"]), ops._p(st["ws"]), st["wsb"], stream),
-                    "tfrt_trace3d_backward")
-            grads = self._parameter_gradients(*self._outs3d(fv, st, index), tap_log)
-        return grads
+        if need_back and not folded:
+            self._trace3d_backward(st, sc, st.g_fin, st.capN)
+
+    @staticmethod
+    def _faces(fv):
+        fvc = fv.detach()
+        if fvc.dtype != torch.float64 or not fvc.is_contiguous():
+            raise RuntimeError("FusedStep: merged faces must be contiguous float64")
+        return fvc
 
     @staticmethod
     def _index3d(scene, fvc):
@@ -514,411 +652,276 @@ class FusedStep:
     @staticmethod
     def _outs3d(fv, st, index):
         """What the parameter gradients are taken from: the faces and the indices that take one."""
-        outs, g_outs = ([fv], [st["g_fv"]]) if fv.requires_grad else ([], [])
+        outs, g_outs = ([fv], [st.g_fv]) if fv.requires_grad else ([], [])
         for k, n in enumerate(index):
             if n is not None:
                 outs.append(n)
-                g_outs.append(st["g_n"][k, :n.shape[0]])
+                g_outs.append(st.g_n[k, :n.shape[0]])
         return outs, g_outs
 
     @staticmethod
-    def _set_index_grads3d(sc, st, on):
-        """Points tfrt_scene3d.grad_n_in / grad_n_out at the step's index block (cleared here, in
-        the captured sequence) or clears them: the struct is cached by the scene."""
-        g = st["g_n"]
-        if on and g is not None:
-            g.zero_()
-            sc.grad_n_in, sc.grad_n_out = g[0].data_ptr(), g[1].data_ptr()
-        else:
-            sc.grad_n_in = sc.grad_n_out = None
+    def _index_grads3d(sc, st, on):
+        """Scope in which tfrt_scene3d.grad_n_in / grad_n_out point at the step's index block
+        (cleared here, in the captured sequence)."""
+        g = st.g_n
+        if not on or g is None:
+            return _override(sc)
+        g.zero_()
+        return _override(sc, grad_n_in=g[0].data_ptr(), grad_n_out=g[1].data_ptr())
+
+    def _rowwise3d(self, src, inputs, tap_log, P, flags):
+        """In-place trace with the finished rows at the rays' own columns -> ``erf.fn`` on
+        fixed-shape tensors + its autograd (torch) -> reverse sweep.  No ray count is read;
+        everything is capturable."""
+        eng = self.opt.engine
+        block, scene, fv = inputs
+        perm = eng._trace_perm
+        fvc = self._faces(fv)
+        index = self._index3d(scene, fvc)
+        st = self._buffers(block, fvc, P, flags, any(n is not None for n in index))
+        N, M, dev = st.N, st.M, block.device
+        sc = scene.struct(fvc)
+        if not (scene.in_place and sc.coherent_rays
+                and _lib.lib().tfrt_trace3d_in_place(ctypes.byref(sc), N, P) == 1):
+            eng._rowwise_off = True      # (this source is not traced in place: generic path)
+            raise _NotInPlace()
+        if st.rows is None:
+            st.rows = torch.zeros((6, st.capN), dtype=block.dtype, device=dev)
+            st.row_face = torch.full((st.capN,), -1, dtype=torch.int32, device=dev)
+            st.row_passes = torch.zeros(st.capN, dtype=torch.int32, device=dev)
+            st.row_outs = dict(st.no_outs,
+                               finished=ops._ray_out(st.rows, st.row_passes, st.row_face))
+        need_back = bool((fv.requires_grad or st.g_n is not None) and M > 0)
+        self.folded_backward, self.in_place = False, True
+        self._goal_pending = None
+        st.perm, st.inplace = perm, (block, self._lengths()[1])
+        clear = {"clear_buffer": st.g_fv.data_ptr(), "clear_count": st.g_fv.numel()} if need_back \
+            else {}
+        grads = None
+        # (in_place == 2: the finished rows at the rays' own columns; the reverse sweep is given
+        # the same value as the forward)
+        with _override(sc, in_place=2, **clear):
+            self._trace_forward(st, sc, st.row_outs)
+            if perm is None:
+                inherited = src.__getitem__
+            else:
+                if st.inherited is None:
+                    st.inherited = {}
+                cache = st.inherited
+
+                def inherited(key):
+                    v = src[key]
+                    hit = cache.get(key)
+                    if hit is None or hit[0] is not v or hit[1] is not perm or hit[2] != v._version:
+                        hit = cache[key] = (v, perm, v._version, v.index_select(0, perm.long()))
+                    return hit[3]
+            leaf, e = self._rowwise_terms(st, _GEO3, inherited)
+            mask = st.row_face[:N] >= 0
+            err_sum = torch.where(mask.unsqueeze(1), e.double(), torch.zeros((), dtype=torch.float64,
+                                                                           device=dev)).sum()
+            terms = mask.sum().double() * e.shape[1]
+            with torch.no_grad():
+                st.err[0] = err_sum.detach()
+                st.err[1] = terms
+                st.err[2] = torch.where(terms > 0, err_sum.detach() / torch.clamp(terms, min=1.0),
+                                        torch.full_like(terms, float("nan")))
+                self.tests_total += st.row_passes[:N].sum() * M
+            if need_back and err_sum.requires_grad:
+                with torch.autograd.set_multithreading_enabled(False):
+                    g_rows, = torch.autograd.grad(err_sum, [leaf])
+                g64 = g_rows.to(torch.float64).contiguous()
+                with self._index_grads3d(sc, st, True):
+                    self._trace3d_backward(st, sc, g64, g64.shape[1])
+                grads = self._parameter_gradients(*self._outs3d(fv, st, index), tap_log)
+        return grads, st
+
+    def _rowwise_terms(self, st, names, inherited):
+        """The user's error function, row by row on every source ray's column: ``st.rows`` (a leaf
+        of its own autograd graph) under the geometry ``names``, every other field through
+        ``inherited``.  Returns the leaf and the error terms as (N, k)."""
+        leaf = st.rows.detach().requires_grad_(True)
+        geo = {name: leaf[k] for k, name in enumerate(names)}
+        e = self.opt.error_function.fn(_RowFields(geo, inherited))
+        if e.dim() == 1:
+            e = e.reshape(-1, 1)
+        # (3-D has always taken terms of more than two dimensions -- it sums them all and counts
+        # e.shape[1] per ray --; 2-D hands the terms to a kernel as a matrix and refuses them.
+        # Both behaviours are kept.)
+        if e.shape[0] != st.N or (st.dim == 2 and e.dim() != 2):
+            raise RuntimeError(f"RowwiseError: fn returned {tuple(e.shape)}, expected one row "
+                               f"per ray ({st.N})")
+        return leaf, e
 
     def _parameter_gradients(self, outs, g_outs, tap_log):
         """d error / d parameters from d error / d geometry (``g_outs``: the faces' gradient in 3-D,
         the merged segments' and arcs' in 2-D) through update()'s graph."""
         opt = self.opt
         grads = [None] * len(opt.parameters)
-        if True:
-            # Inside a graph capture: differentiate w.r.t. the aliases update() read the parameters
-            # through (see boundaries.tap), never w.r.t. the leaves.  Outside a capture the leaf is
-            # differentiated too -- its gradient is the total whatever route update() took -- and
-            # the first eager steps compare the two: a parameter that reaches the faces (partly)
-            # without an alias (a custom _update reading the leaf) must never be captured.
-            capturing = torch.cuda.is_current_stream_capturing()
-            inputs, owner = [], []
-            for i, p in enumerate(opt.parameters):
-                taps = tap_log.get(id(p), [])
-                if not taps:
-                    self.untapped = True
-                checked = self._tap_checks >= self.graph_warmup and not self.untapped
-                if (capturing or checked) and taps:
-                    inputs.extend(taps)
-                    owner.extend([i] * len(taps))
-                else:
-                    inputs.extend(taps + [p])
-                    owner.extend([i] * len(taps) + [-1 - i])
-            with torch.autograd.set_multithreading_enabled(False):
-                got = torch.autograd.grad(outs, inputs, grad_outputs=g_outs, allow_unused=True)
-            total = {}
-            for i, g in zip(owner, got):
-                if g is None:
-                    continue
-                if i < 0:
-                    total[-1 - i] = g
-                else:
-                    grads[i] = g if grads[i] is None else grads[i] + g
-            for i, g in total.items():
-                if not self.untapped and self._tap_checks < self.graph_warmup:
-                    # (one host read per parameter, first steps only.  Relative to the gradient's
-                    # largest entry: the aliases are summed in another order than autograd's own
-                    # accumulation, entries near zero may differ by more than any relative bound)
-                    same = grads[i] is not None and bool(
-                        torch.isfinite(g).eq(torch.isfinite(grads[i])).all()) and float(
-                        (torch.nan_to_num(grads[i] - g, nan=0.0, posinf=0.0, neginf=0.0)).abs().max()
-                    ) <= 1e-9 * float(torch.nan_to_num(g, nan=0.0, posinf=0.0, neginf=0.0).abs().max())
-                    if not same:
-                        self.untapped = True
-                        self.capture_error = RuntimeError(
-                            f"FusedStep: parameter {i} reaches the faces without boundaries.tap "
-                            "(its leaf gradient differs from the sum over its aliases): the step "
-                            "is never captured in a launch graph")
-                grads[i] = g
-            if not capturing:
-                self._tap_checks += 1
+        # Inside a graph capture: differentiate w.r.t. the aliases update() read the parameters
+        # through (see boundaries.tap), never w.r.t. the leaves.  Outside a capture the leaf is
+        # differentiated too -- its gradient is the total whatever route update() took -- and
+        # the first eager steps compare the two: a parameter that reaches the faces (partly)
+        # without an alias (a custom _update reading the leaf) must never be captured.
+        capturing = torch.cuda.is_current_stream_capturing()
+        inputs, owner = [], []
+        for i, p in enumerate(opt.parameters):
+            taps = tap_log.get(id(p), [])
+            if not taps:
+                self.untapped = True
+            checked = self._tap_checks >= self.graph_warmup and not self.untapped
+            if (capturing or checked) and taps:
+                inputs.extend(taps)
+                owner.extend([i] * len(taps))
+            else:
+                inputs.extend(taps + [p])
+                owner.extend([i] * len(taps) + [-1 - i])
+        with torch.autograd.set_multithreading_enabled(False):
+            got = torch.autograd.grad(outs, inputs, grad_outputs=g_outs, allow_unused=True)
+        total = {}
+        for i, g in zip(owner, got):
+            if g is None:
+                continue
+            if i < 0:
+                total[-1 - i] = g
+            else:
+                grads[i] = g if grads[i] is None else grads[i] + g
+        for i, g in total.items():
+            if (not self.untapped and self._tap_checks < self.graph_warmup
+                    and not self._same_gradient(grads[i], g)):
+                self.untapped = True
+                self.capture_error = RuntimeError(
+                    f"FusedStep: parameter {i} reaches the faces without boundaries.tap "
+                    "(its leaf gradient differs from the sum over its aliases): the step "
+                    "is never captured in a launch graph")
+            grads[i] = g
+        if not capturing:
+            self._tap_checks += 1
         return grads
 
-    def _enqueue_rowwise(self, erf, src, block, scene, fv, perm, tap_log):
-        """update (done) -> in-place trace with the finished rows at the rays' own columns ->
-        ``erf.fn`` on fixed-shape tensors + its autograd (torch) -> reverse sweep -> parameter
-        gradients.  No ray count is read; everything is capturable."""
-        opt, eng = self.opt, self.opt.engine
-        P, flags = int(opt.trace_depth), eng._flags() | _lib.COMPILE_FINISHED
-        dt = ops._DT[block.dtype]
-        fvc = fv.detach()
-        if fvc.dtype != torch.float64 or not fvc.is_contiguous():
-            raise RuntimeError("FusedStep: merged faces must be contiguous float64")
-        index = self._index3d(scene, fvc)
-        st = self._buffers(block, fvc, P, flags, dt, any(n is not None for n in index))
-        N, M, dev = st["N"], st["M"], block.device
-        L = _lib.lib()
-        stream = ops._stream(block)
-        sc = scene.struct(fvc)
-        if not (scene.in_place and sc.coherent_rays
-                and L.tfrt_trace3d_in_place(ctypes.byref(sc), N, P) == 1):
-            eng._rowwise_off = True      # (this source is not traced in place: generic path)
-            raise _NotInPlace()
-        if "rows" not in st:
-            st["rows"] = torch.zeros((6, st["capN"]), dtype=block.dtype, device=dev)
-            st["row_face"] = torch.full((st["capN"],), -1, dtype=torch.int32, device=dev)
-            st["row_passes"] = torch.zeros(st["capN"], dtype=torch.int32, device=dev)
-            st["row_out"] = ops._ray_out(st["rows"], st["row_passes"], st["row_face"])
-        need_back = bool((fv.requires_grad or st["g_n"] is not None) and M > 0)
-        self.folded_backward, self.in_place = False, True
-        sc.in_place = 2
-        if need_back:
-            sc.clear_buffer, sc.clear_count = st["g_fv"].data_ptr(), st["g_fv"].numel()
-        no = st["no_outs"]
-        try:
-            check(L.tfrt_trace3d_forward(
-                ops._p(block), block.shape[1], N, ctypes.byref(sc), float(eng.new_ray_length),
-                float(eng.dead_ray_length or 0.0), P, dt, flags, ctypes.byref(st["row_out"]),
-                ctypes.byref(no["active"]), ctypes.byref(no["stopped"]), ctypes.byref(no["dead"]),
-                None, None, ops._p(st["counts"]), ops._p(st["ws"]), st["wsb"], stream),
-                "tfrt_trace3d_forward")
-            # the user's error function, row by row on every source ray's column
-            leaf = st["rows"].detach().requires_grad_(True)
-            geo = {name: leaf[k] for k, name in enumerate(_GEO3)}
-            if perm is None:
-                inherited = lambda key: src[key]                       # noqa: E731
-            else:
-                cache = st.setdefault("inherited", {})
-
-                def inherited(key, cache=cache):
-                    v = src[key]
-                    hit = cache.get(key)
-                    if hit is None or hit[0] is not v or hit[1] is not perm or hit[2] != v._version:
-                        hit = cache[key] = (v, perm, v._version, v.index_select(0, perm.long()))
-                    return hit[3]
-            e = erf.fn(_RowFields(geo, inherited))
-            if e.dim() == 1:
-                e = e.reshape(-1, 1)
-            if e.shape[0] != N:
-                raise RuntimeError(f"RowwiseError: fn returned {tuple(e.shape)}, expected one row "
-                                   f"per ray ({N})")
-            mask = st["row_face"][:N] >= 0
-            err_sum = torch.where(mask.unsqueeze(1), e.double(), torch.zeros((), dtype=torch.float64,
-                                                                           device=dev)).sum()
-            terms = mask.sum().double() * e.shape[1]
-            with torch.no_grad():
-                st["err"][0] = err_sum.detach()
-                st["err"][1] = terms
-                st["err"][2] = torch.where(terms > 0, err_sum.detach() / torch.clamp(terms, min=1.0),
-                                           torch.full_like(terms, float("nan")))
-                self.tests_total += st["row_passes"][:N].sum() * M
-            grads = [None] * len(opt.parameters)
-            if need_back and err_sum.requires_grad:
-                with torch.autograd.set_multithreading_enabled(False):
-                    g_rows, = torch.autograd.grad(err_sum, [leaf])
-                g64 = g_rows.to(torch.float64).contiguous()
-                self._set_index_grads3d(sc, st, True)
-                check(L.tfrt_trace3d_backward(
-                    ops._p(block), block.shape[1], N, ctypes.byref(sc), float(eng.new_ray_length),
-                    float(eng.dead_ray_length or 0.0), P, dt, ops._p(g64), g64.shape[1], None, 0,
-                    None, 0, None, 0, ops._p(st["g_fv"]), None, ops._p(st["counts"]),
-                    ops._p(st["ws"]), st["wsb"], stream), "tfrt_trace3d_backward")
-                grads = self._parameter_gradients(*self._outs3d(fv, st, index), tap_log)
-        finally:
-            sc.in_place = 1 if scene.in_place else 0      # (the struct is cached by the scene)
-            sc.clear_buffer, sc.clear_count = None, 0
-            self._set_index_grads3d(sc, st, False)
-        self._goal_pending = None
-        self._publish_lazily(st, src, P, flags, perm, (block, float(eng.dead_ray_length or 0.0)))
-        return grads, st["err"]
+    @staticmethod
+    def _same_gradient(aliases, leaf):
+        """Whether the sum over a parameter's aliases is its leaf gradient (one host read per
+        parameter, first steps only).  Relative to the gradient's largest entry: the aliases are
+        summed in another order than autograd's own accumulation, entries near zero may differ by
+        more than any relative bound."""
+        if aliases is None or not bool(torch.isfinite(leaf).eq(torch.isfinite(aliases)).all()):
+            return False
+        finite = dict(nan=0.0, posinf=0.0, neginf=0.0)
+        return float(torch.nan_to_num(aliases - leaf, **finite).abs().max()) \
+            <= 1e-9 * float(torch.nan_to_num(leaf, **finite).abs().max())
 
     # ------------------------------------------------------------------------------ 2-D
-    def _buffers2d(self, block, seg, arc, P, flags, dt, rows, rowwise=False, index=()):
-        """Persistent outputs / tape / gradient blocks of a 2-D trace for this (N, Ms, Ma, P,
-        dtype, flags, fields); with ``rowwise`` also the fixed-shape columns of a RowwiseError.
-        ``index``: which of (seg_n_in, seg_n_out, arc_n_in, arc_n_out) take a gradient."""
-        N = block.shape[1]
-        Ms = 0 if seg is None else seg.shape[0]
-        Ma = 0 if arc is None else arc.shape[0]
-        index = tuple(bool(i) for i in index) or (False,) * 4
-        sig = (2, N, Ms, Ma, P, dt, flags, str(block.device), tuple(rows), bool(rowwise), index)
-        st = self._state
-        if st is not None and st["sig"] == sig:
-            return st
-        dev = block.device
-        L = _lib.lib()
-        wsb = L.tfrt_trace2d_workspace_bytes(N, Ms, Ma, P, dt)
-        capN = max(N, 1)
-        ints = ops._IntPool(dev, True, _lib.COUNTS_PER_PASS * (P + 1), flags, capN, P)
-        caps = {"finished": capN, "active": capN * max(P, 1), "stopped": capN, "dead": capN}
-        full, aux, outs = {}, {"counts": ints.counts}, {}
-        for name, flag in _CLASS_FLAGS:
-            if flags & flag:
-                rays = torch.empty((4, caps[name]), dtype=block.dtype, device=dev)
-                ids, faces = ints.take(caps[name]), ints.take(caps[name])
-                full[name], aux[name + "_id"], aux[name + "_face"] = rays, ids, faces
-                outs[name] = ops._ray_out(rays, ids, faces)
-            else:
-                aux[name + "_id"] = aux[name + "_face"] = None
-                outs[name] = ops._ray_out(None, None, None)
-        aux["unfinished"] = torch.empty((4, 0), dtype=block.dtype, device=dev)
-        aux["unfinished_id"] = torch.empty(0, dtype=torch.int32, device=dev)
-        gws = L.tfrt_trace2d_backward_goal_workspace_bytes(N)
-        # (segment and arc gradients in one block, the index gradients asked for behind them: one
-        # clearing launch per step)
-        n_index = 2 * (Ms + Ma) if any(index) else 0
-        at = 4 * Ms + 5 * Ma
-        g_prim = torch.zeros(max(at + n_index, 1), dtype=torch.float64, device=dev)
-        g_index = [None] * 4
-        if n_index:
-            g_index = [g_prim[at:at + Ms], g_prim[at + Ms:at + 2 * Ms],
-                       g_prim[at + 2 * Ms:at + 2 * Ms + Ma], g_prim[at + 2 * Ms + Ma:at + n_index]]
-            g_index = [g if want else None for g, want in zip(g_index, index)]
-        st = dict(
-            sig=sig, dim=2, N=N, Ms=Ms, Ma=Ma, P=P, dt=dt, flags=flags, capN=capN, full=full,
-            aux=aux, outs=outs, ws=torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev),
-            wsb=wsb, counts=ints.counts, ints=ints, g_prim=g_prim, g_index=g_index,
-            g_seg=g_prim[:4 * Ms].view(Ms, 4), g_arc=g_prim[4 * Ms:4 * Ms + 5 * Ma].view(Ma, 5),
-            err=torch.zeros(3, dtype=torch.float64, device=dev),
-            goal_ws=torch.zeros(max(gws, 1), dtype=torch.uint8, device=dev), gws=gws,
-            fields=(ctypes.c_int32 * 4)(*(list(rows) + [0] * 4)[:4]),
-        )
-        if rowwise:
-            # (every column is written by each step's tfrt_trace2d_rows: no clearing)
-            st["rows"] = torch.empty((4, capN), dtype=block.dtype, device=dev)
-            st["row_face"] = torch.empty(capN, dtype=torch.int32, device=dev)
-        self._state = st
-        self._graphs = None
-        if self.tests_total is None or self.tests_total.device != dev:
-            self.tests_total = torch.zeros(1, dtype=torch.int64, device=dev)
-        return st
-
-    def _enqueue_gradient2d(self):
-        """_enqueue_gradient of a 2-D engine: update -> tfrt_trace2d_forward ->
-        tfrt_trace2d_backward_goal (error, seed and the reverse sweep of every pass in one
-        launch) -> parameter gradients through update()'s graph from the merged segments and
-        arcs.  One process, rays in natural order."""
-        opt, eng = self.opt, self.opt.engine
-        system = eng.optical_system
-        eng.clear_ray_history()
-        from . import boundaries
-        with boundaries.collect_taps() as tap_log:
-            system.update()
-        src = eng._source_set()
-        if not src:
-            raise RuntimeError("FusedStep: the optical system has no source rays")
-        erf = opt.error_function
-        if isinstance(erf, RowwiseError):
-            return self._enqueue_rowwise2d(erf, src, tap_log)
-        rows = erf.rows_for(2)
-        block, scene, _ = eng._trace_inputs(src)
-        goal = erf.table(src)
-        P, flags = int(opt.trace_depth), eng._flags() | _lib.COMPILE_FINISHED
-        dt = ops._DT[block.dtype]
-        geo, det = self._geometry2d(scene)
-        index = self._index2d(scene)
-        st = self._buffers2d(block, det[0], det[1], P, flags, dt, rows,
-                             index=[i is not None for i in index])
-        L = _lib.lib()
-        stream = ops._stream(block)
-        sc = scene.struct(det[0], det[1])
-        o = st["outs"]
-        check(L.tfrt_trace2d_forward(
-            ops._p(block), block.shape[1], st["N"], ctypes.byref(sc), float(eng.new_ray_length),
-            float(eng.dead_ray_length or 0.0), P, dt, flags, ctypes.byref(o["finished"]),
-            ctypes.byref(o["active"]), ctypes.byref(o["stopped"]), ctypes.byref(o["dead"]),
-            None, None,      # (the rays still active after the last pass are not copied out)
-            ops._p(st["counts"]), ops._p(st["ws"]), st["wsb"], stream), "tfrt_trace2d_forward")
-        back = [(g, grad) for g, grad in zip(geo, (st["g_seg"], st["g_arc"]))
-                if g is not None and g.requires_grad and g.shape[0] > 0]
-        back += [(n, g) for n, g in zip(index, st["g_index"]) if n is not None]
-        if back:
-            st["g_prim"].zero_()
-        pending = _lib.GoalPending()
-        self._set_index_grads(sc, st, bool(back))
-        try:
-            check(L.tfrt_trace2d_backward_goal(
-                ops._p(block), block.shape[1], st["N"], ctypes.byref(sc), float(eng.new_ray_length),
-                P, dt, ctypes.byref(o["finished"]), st["fields"], len(rows), ops._p(goal),
-                goal.shape[1], 1, ops._p(st["err"]), ops._p(self.tests_total),
-                ops._p(st["goal_ws"]), st["gws"], ctypes.byref(pending),
-                ops._p(st["g_seg"]) if back and st["Ms"] else None,
-                ops._p(st["g_arc"]) if back and st["Ma"] else None,
-                ops._p(st["counts"]), ops._p(st["ws"]), st["wsb"], stream),
-                "tfrt_trace2d_backward_goal")
-        finally:
-            self._set_index_grads(sc, st, False)
-        # (nothing on the device waits for the error sum: the parameter update's launch finishes it)
-        self._goal_pending = (pending, stream)
-        self.folded_backward, self.in_place = True, False
-        grads = [None] * len(opt.parameters)
-        if back:
-            grads = self._parameter_gradients([b[0] for b in back], [b[1] for b in back], tap_log)
-        self._publish_lazily2d(st, src)
-        return grads, st["err"]
-
-    @staticmethod
-    def _index2d(scene):
-        """The per-primitive indices of "value" mode that take a gradient (seg_n_in, seg_n_out,
-        arc_n_in, arc_n_out; None where not), as merged by update() from the boundaries' fields."""
-        return [n if isinstance(n, torch.Tensor) and n.requires_grad and n.shape[0] > 0 else None
-                for n in scene.index_args()]
-
-    @staticmethod
-    def _set_index_grads(sc, st, on):
-        """Points the 2-D scene struct's index-gradient fields at this step's blocks (or clears them)."""
-        for name, g in zip(ops._GRAD_INDEX_2D, st["g_index"]):
-            setattr(sc, name, g.data_ptr() if (on and g is not None) else None)
-
-    @staticmethod
-    def _geometry2d(scene):
-        """The merged segments and arcs (None where the scene has none) and their detached views."""
+    def _setup2d(self, inputs, P, flags, rows):
+        """State, scene struct and what the reverse sweep differentiates of a 2-D step: the
+        (tensor, gradient block) pairs of the merged segments, arcs and indices that take one."""
+        block, scene, _ = inputs
         geo = [None if k is None else k["geo"] for k in (scene.segments, scene.arcs)]
         det = [None if g is None else g.detach() for g in geo]
         if any(g is not None and (g.dtype != torch.float64 or not g.is_contiguous()) for g in det):
             raise RuntimeError("FusedStep: merged segments / arcs must be contiguous float64")
-        return geo, det
+        # the per-primitive indices of "value" mode that take a gradient (seg_n_in, seg_n_out,
+        # arc_n_in, arc_n_out; None where not), as merged by update() from the boundaries' fields
+        index = [n if isinstance(n, torch.Tensor) and n.requires_grad and n.shape[0] > 0 else None
+                 for n in scene.index_args()]
+        st = self._buffers2d(block, det, P, flags, rows, index)
+        st.perm = st.inplace = None       # (2-D traces keep the source's order and compact)
+        back = [(g, grad) for g, grad in zip(geo, (st.g_seg, st.g_arc))
+                if g is not None and g.requires_grad and g.shape[0] > 0]
+        back += [(n, g) for n, g in zip(index, st.g_index) if n is not None]
+        return st, scene.struct(det[0], det[1]), back
 
-    def _enqueue_rowwise2d(self, erf, src, tap_log):
-        """_enqueue_gradient2d for a RowwiseError: update (done) -> tfrt_trace2d_forward ->
-        tfrt_trace2d_rows (every source ray's column, a mask for the rays that finished) ->
-        ``erf.fn`` on those columns + its autograd (torch) -> tfrt_trace2d_backward_rows seeded
-        with the columns' gradient -> parameter gradients.  No ray count is read; everything is
-        capturable."""
-        opt, eng = self.opt, self.opt.engine
-        block, scene, _ = eng._trace_inputs(src)
-        P, flags = int(opt.trace_depth), eng._flags() | _lib.COMPILE_FINISHED
-        dt = ops._DT[block.dtype]
-        geo, det = self._geometry2d(scene)
-        index = self._index2d(scene)
-        st = self._buffers2d(block, det[0], det[1], P, flags, dt, (), rowwise=True,
-                             index=[i is not None for i in index])
-        N = st["N"]
+    @staticmethod
+    def _index_grads2d(sc, st, on):
+        """Scope in which the 2-D scene struct's index-gradient fields point at the step's blocks."""
+        return _override(sc, **{name: g.data_ptr() for name, g in zip(ops._GRAD_INDEX_2D, st.g_index)
+                                if on and g is not None})
+
+    def _goal2d(self, src, inputs, tap_log, P, flags):
+        """tfrt_trace2d_forward -> tfrt_trace2d_backward_goal (error, seed and the reverse sweep of
+        every pass in one launch); the parameter gradients come through update()'s graph from the
+        merged segments and arcs.  One process, rays in natural order."""
+        erf = self.opt.error_function
+        rows = erf.rows_for(2)
+        goal = erf.table(src)
+        st, sc, back = self._setup2d(inputs, P, flags, rows)
+        block = st.block
+        self._trace_forward(st, sc, st.outs)
+        if back:
+            st.g_prim.zero_()
+        pending = _lib.GoalPending()
+        with self._index_grads2d(sc, st, bool(back)):
+            check(_lib.lib().tfrt_trace2d_backward_goal(
+                ops._p(block), block.shape[1], st.N, ctypes.byref(sc), self._lengths()[0],
+                P, st.dt, ctypes.byref(st.outs["finished"]), st.fields, len(rows), ops._p(goal),
+                goal.shape[1], 1, ops._p(st.err), ops._p(self.tests_total),
+                ops._p(st.goal_ws), st.gws, ctypes.byref(pending),
+                ops._p(st.g_seg) if back and st.Ms else None,
+                ops._p(st.g_arc) if back and st.Ma else None,
+                ops._p(st.counts), ops._p(st.ws), st.wsb, st.stream),
+                "tfrt_trace2d_backward_goal")
+        # (nothing on the device waits for the error sum: the parameter update's launch finishes it)
+        self._goal_pending = (pending, st.stream)
+        self.folded_backward, self.in_place = True, False
+        if not back:
+            return None, st
+        return self._parameter_gradients([b[0] for b in back], [b[1] for b in back], tap_log), st
+
+    def _rowwise2d(self, src, inputs, tap_log, P, flags):
+        """_goal2d for a RowwiseError: tfrt_trace2d_forward -> tfrt_trace2d_rows (every source
+        ray's column, a mask for the rays that finished) -> ``erf.fn`` on those columns + its
+        autograd (torch) -> tfrt_trace2d_backward_rows seeded with the columns' gradient.  No ray
+        count is read; everything is capturable."""
+        st, sc, back = self._setup2d(inputs, P, flags, None)
+        block, N = st.block, st.N
         L = _lib.lib()
-        stream = ops._stream(block)
-        sc = scene.struct(det[0], det[1])
-        o = st["outs"]
-        check(L.tfrt_trace2d_forward(
-            ops._p(block), block.shape[1], N, ctypes.byref(sc), float(eng.new_ray_length),
-            float(eng.dead_ray_length or 0.0), P, dt, flags, ctypes.byref(o["finished"]),
-            ctypes.byref(o["active"]), ctypes.byref(o["stopped"]), ctypes.byref(o["dead"]),
-            None, None,      # (the rays still active after the last pass are not copied out)
-            ops._p(st["counts"]), ops._p(st["ws"]), st["wsb"], stream), "tfrt_trace2d_forward")
+        finished = ctypes.byref(st.outs["finished"])
+        self._trace_forward(st, sc, st.outs)
         # the finished rows at their source rays' columns
         check(L.tfrt_trace2d_rows(
-            ops._p(block), block.shape[1], N, P, dt, ctypes.byref(o["finished"]),
-            ops._p(st["rows"]), st["rows"].shape[1], ops._p(st["row_face"]), ops._p(st["counts"]),
-            ops._p(st["ws"]), st["wsb"], stream), "tfrt_trace2d_rows")
-        # the user's error function, row by row on every source ray's column (natural order:
-        # column i is source ray i, whose own fields are the inherited ones)
-        leaf = st["rows"].detach().requires_grad_(True)
-        e = erf.fn(_RowFields({name: leaf[k] for k, name in enumerate(_GEO2)},
-                              lambda key: src[key]))
-        if e.dim() == 1:
-            e = e.reshape(-1, 1)
-        if e.dim() != 2 or e.shape[0] != N:
-            raise RuntimeError(f"RowwiseError: fn returned {tuple(e.shape)}, expected one row "
-                               f"per ray ({N})")
+            ops._p(block), block.shape[1], N, P, st.dt, finished,
+            ops._p(st.rows), st.rows.shape[1], ops._p(st.row_face), ops._p(st.counts),
+            ops._p(st.ws), st.wsb, st.stream), "tfrt_trace2d_rows")
+        # (natural order: column i is source ray i, whose own fields are the inherited ones)
+        leaf, e = self._rowwise_terms(st, _GEO2, src.__getitem__)
         e = e.double()
         # No reduction over the rays in torch (a sum over a million entries inside a replayed graph
         # is not reliable): the gradient of the masked sum is the mask itself, and the sum is
         # formed by the sweep's launch and finished by the parameter update's, as for a GoalError
-        back = [(g, grad) for g, grad in zip(geo, (st["g_seg"], st["g_arc"]))
-                if g is not None and g.requires_grad and g.shape[0] > 0]
-        back += [(n, g) for n, g in zip(index, st["g_index"]) if n is not None]
         g64 = None
         if back and e.requires_grad:
-            mask = (st["row_face"][:N] >= 0).unsqueeze(1).expand_as(e).double()
+            mask = (st.row_face[:N] >= 0).unsqueeze(1).expand_as(e).double()
             with torch.autograd.set_multithreading_enabled(False):
                 g_rows, = torch.autograd.grad(e, [leaf], grad_outputs=mask)
             g64 = g_rows.to(torch.float64).contiguous()
-            st["g_prim"].zero_()
+            st.g_prim.zero_()
         e = e.detach().contiguous()
         pending = _lib.GoalPending()
-        self._set_index_grads(sc, st, g64 is not None)
-        try:
+        with self._index_grads2d(sc, st, g64 is not None):
             check(L.tfrt_trace2d_backward_rows(
-                ops._p(block), block.shape[1], N, ctypes.byref(sc), float(eng.new_ray_length), P,
-                dt, ctypes.byref(o["finished"]), ops._p(e), e.shape[1], 1, e.shape[1],
+                ops._p(block), block.shape[1], N, ctypes.byref(sc), self._lengths()[0], P,
+                st.dt, finished, ops._p(e), e.shape[1], 1, e.shape[1],
                 None if g64 is None else ops._p(g64), 0 if g64 is None else g64.shape[1],
-                ops._p(st["err"]), ops._p(self.tests_total), ops._p(st["goal_ws"]), st["gws"],
+                ops._p(st.err), ops._p(self.tests_total), ops._p(st.goal_ws), st.gws,
                 ctypes.byref(pending),
-                ops._p(st["g_seg"]) if g64 is not None and st["Ms"] else None,
-                ops._p(st["g_arc"]) if g64 is not None and st["Ma"] else None,
-                ops._p(st["counts"]), ops._p(st["ws"]), st["wsb"], stream),
+                ops._p(st.g_seg) if g64 is not None and st.Ms else None,
+                ops._p(st.g_arc) if g64 is not None and st.Ma else None,
+                ops._p(st.counts), ops._p(st.ws), st.wsb, st.stream),
                 "tfrt_trace2d_backward_rows")
-        finally:
-            self._set_index_grads(sc, st, False)
         # (nothing on the device waits for the error sum: the parameter update's launch finishes it)
-        self._goal_pending = (pending, stream)
+        self._goal_pending = (pending, st.stream)
         self.folded_backward, self.in_place = False, False
-        grads = [None] * len(opt.parameters)
-        if g64 is not None:
-            grads = self._parameter_gradients([b[0] for b in back], [b[1] for b in back], tap_log)
-        self._publish_lazily2d(st, src)
-        return grads, st["err"]
+        if g64 is None:
+            return None, st
+        return self._parameter_gradients([b[0] for b in back], [b[1] for b in back], tap_log), st
 
-    def _publish_lazily2d(self, st, src):
+    # ------------------------------------------------------------------------ publishing
+    def _publish_lazily(self, st, src):
+        """Leaves the engine a function that cuts the ray sets of the step ``st`` last enqueued
+        (or a replayed graph last ran) when somebody asks for them."""
         eng = self.opt.engine
-        eng._trace_src = src
-        eng._trace_sig = (src.n_rays if hasattr(src, "n_rays") else src["x_start"].shape[0],
-                          st["P"], st["flags"])
-        self._last_perm, self._last_inplace = None, None
-
-        def publish():
-            out = ops._finish_trace(dict(st["full"]), dict(st["aux"]), st["P"], None)
-            out["n_segments"] = st["Ms"]
-            return out
-        eng._pending_trace = publish
-
-    def _publish_lazily(self, st, src, P, flags, perm=None, inplace=None):
-        eng = self.opt.engine
+        P, flags, perm, inplace = st.P, st.flags, st.perm, st.inplace
         eng._trace_src = src
         eng._trace_sig = (src.n_rays if hasattr(src, "n_rays") else src["x_start"].shape[0], P, flags)
-        full, aux = st["full"], st["aux"]
-        self._last_perm, self._last_inplace = perm, inplace
 
         def publish():
             if inplace is not None:
@@ -926,105 +929,66 @@ class FusedStep:
                 # tape now, into the reference's (per-pass, stable) order of the traced rays
                 # (with a coherent order: in the SOURCE's order, through the inverse of the order)
                 block, dead_len = inplace
-                o = st["outs"]
+                o = st.outs
+                # (`perm` is inverted now, not when the step was enqueued: a replayed graph
+                # re-orders a re-drawn source into the same tensor behind Python's back)
                 check(_lib.lib().tfrt_trace3d_compact(
-                    ops._p(block), block.shape[1], st["N"], dead_len, P, st["dt"], flags,
+                    ops._p(block), block.shape[1], st.N, dead_len, P, st.dt, flags,
                     ctypes.byref(o["finished"]), ctypes.byref(o["active"]),
                     ctypes.byref(o["stopped"]), ctypes.byref(o["dead"]), None, None,
-                    ops._p(st["counts"]), st["M"],
-                    None if perm is None else ops._p(ops.inverse_order(perm)), ops._p(st["ws"]),
-                    st["wsb"], ops._stream(block)), "tfrt_trace3d_compact")
-                return ops._finish_trace(dict(full), dict(aux), P, None)
-            out = ops._finish_trace(dict(full), dict(aux), P, None)
+                    ops._p(st.counts), st.M,
+                    None if perm is None else ops._p(ops.inverse_order(perm)), ops._p(st.ws),
+                    st.wsb, ops._stream(block)), "tfrt_trace3d_compact")
+                return ops._finish_trace(dict(st.full), dict(st.aux), P, None)
+            out = ops._finish_trace(dict(st.full), dict(st.aux), P, None)
+            if st.dim == 2:
+                out["n_segments"] = st.Ms
             return out if perm is None else ops.restore_order(out, perm)
         eng._pending_trace = publish
 
+    # ------------------------------------------------------------------------ the update
     def _enqueue_apply(self, grads, accumulators):
         """non-finite -> 0, scale, clip, accumulate, SGD apply (optimizer.py:223-257, 316) with
-        the step-dependent scalars read from the device table."""
+        the step-dependent scalars read from the device table: rows of {scale, clip,
+        sgd_learning_rate}, with {momentum, nesterov} appended for the momentum rule
+        (tfrt_sgd_momentum_multi, the optimizer's velocity buffers)."""
         opt = self.opt
         L = _lib.lib()
         k = len(grads)
-        if opt.apply_momentum:
-            return self._enqueue_apply_momentum(grads, accumulators)
-        if 1 < k <= 8 and all(a is None for a in accumulators) and \
-                len({ops._stream(p).value for p in opt.parameters}) == 1:
-            # plain SGD on every parameter tensor: one launch for all of them (the device table
-            # holds the three scalars of parameter i at offset 3 i)
-            gp = (ctypes.c_void_p * k)(*[g.data_ptr() for g in grads])
-            pp = (ctypes.c_void_p * k)(*[p.data_ptr() for p in opt.parameters])
-            nn = (ctypes.c_int64 * k)(*[g.numel() for g in grads])
-            pending, self._goal_pending = getattr(self, "_goal_pending", None), None
-            with torch.no_grad():
-                if pending is not None and pending[1].value == ops._stream(opt.parameters[0]).value:
-                    check(L.tfrt_sgd_process_multi_finish(
-                        k, gp, None, pp, nn, ctypes.c_void_p(self._hyper.dev.data_ptr()),
-                        ctypes.byref(pending[0]), ops._stream(opt.parameters[0])),
-                        "tfrt_sgd_process_multi_finish")
-                else:
-                    if pending is not None:
-                        check(L.tfrt_goal_finish(ctypes.byref(pending[0]), pending[1]),
-                              "tfrt_goal_finish")
-                    check(L.tfrt_sgd_process_multi(k, gp, None, pp, nn,
-                                                   ctypes.c_void_p(self._hyper.dev.data_ptr()),
-                                                   ops._stream(opt.parameters[0])),
-                          "tfrt_sgd_process_multi")
-            return
-        pending, self._goal_pending = getattr(self, "_goal_pending", None), None
-        if pending is not None:      # (other update paths: the launch tfrt_goal_error3d would have made)
-            check(L.tfrt_goal_finish(ctypes.byref(pending[0]), pending[1]), "tfrt_goal_finish")
-        for i, (g, p) in enumerate(zip(grads, opt.parameters)):
-            hyper = ctypes.c_void_p(self._hyper.dev.data_ptr() + 24 * i)
-            stream = ops._stream(p)
-            with torch.no_grad():
-                if accumulators[i] is None:
-                    check(L.tfrt_sgd_process_dev(ops._p(g), None, ops._p(p), g.numel(), _lib.F64,
-                                                 hyper, stream), "tfrt_sgd_process_dev")
-                else:
-                    processed = torch.empty_like(g)
-                    check(L.tfrt_sgd_process_dev(ops._p(g), ops._p(processed), None, g.numel(),
-                                                 _lib.F64, hyper, stream), "tfrt_sgd_process_dev")
-                    acc = opt._matrix_product(opt._acc_cache, i, accumulators[i], processed)
-                    apply_row = ctypes.c_void_p(self._hyper_apply.dev.data_ptr() + 24 * i)
-                    check(L.tfrt_sgd_process_dev(ops._p(acc.contiguous()), None, ops._p(p),
-                                                 acc.numel(), _lib.F64, apply_row, stream),
-                          "tfrt_sgd_process_dev")
-
-    def _enqueue_apply_momentum(self, grads, accumulators):
-        """_enqueue_apply with the momentum rule (tfrt_sgd_momentum_multi): rows of five scalars
-        {scale, clip, sgd_learning_rate, momentum, nesterov}, the optimizer's velocity buffers."""
-        opt = self.opt
-        L = _lib.lib()
-        k = len(grads)
-        vel = opt._velocity
-        hyper = self._hyper.dev.data_ptr()
+        momentum = bool(opt.apply_momentum)
+        # (the plain rule takes one launch for all parameter tensors from two of them on, the
+        # momentum rule from one on)
+        batched = (k > (0 if momentum else 1) and k <= 8 and all(a is None for a in accumulators)
+                   and len({ops._stream(p).value for p in opt.parameters}) == 1)
+        pending, self._goal_pending = self._goal_pending, None
 
         def arr(ts, ctype=ctypes.c_void_p):
             return (ctype * len(ts))(*ts)
-        pending, self._goal_pending = getattr(self, "_goal_pending", None), None
-        stream = ops._stream(opt.parameters[0])
+        hyper, row_bytes = self._hyper.dev.data_ptr(), 8 * self._hyper.width
         with torch.no_grad():
-            if k <= 8 and all(a is None for a in accumulators) and \
-                    len({ops._stream(p).value for p in opt.parameters}) == 1:
-                # every parameter tensor in one launch, which also finishes the error sum
-                args = (k, arr([g.data_ptr() for g in grads]), None,
+            if batched:
+                # every parameter tensor in one launch (the device table holds the scalars of
+                # parameter i in row i), which also finishes the error sum left on its stream
+                stream = ops._stream(opt.parameters[0])
+                name = "tfrt_sgd_momentum_multi" if momentum else "tfrt_sgd_process_multi"
+                args = [k, arr([g.data_ptr() for g in grads]), None,
                         arr([p.data_ptr() for p in opt.parameters]),
-                        arr([v.data_ptr() for v in vel]),
-                        arr([g.numel() for g in grads], ctypes.c_int64), ctypes.c_void_p(hyper))
+                        arr([g.numel() for g in grads], ctypes.c_int64), ctypes.c_void_p(hyper)]
+                if momentum:
+                    args.insert(4, arr([v.data_ptr() for v in opt._velocity]))
                 if pending is not None and pending[1].value == stream.value:
-                    check(L.tfrt_sgd_momentum_multi_finish(*args, ctypes.byref(pending[0]), stream),
-                          "tfrt_sgd_momentum_multi_finish")
+                    check(getattr(L, name + "_finish")(*args, ctypes.byref(pending[0]), stream),
+                          name + "_finish")
                     return
-                if pending is not None:
-                    check(L.tfrt_goal_finish(ctypes.byref(pending[0]), pending[1]),
-                          "tfrt_goal_finish")
-                check(L.tfrt_sgd_momentum_multi(*args, stream), "tfrt_sgd_momentum_multi")
+                if pending is not None:      # (recorded on another stream: finished on its own)
+                    self._goal_finish(*pending)
+                check(getattr(L, name)(*args, stream), name)
                 return
             if pending is not None:
-                check(L.tfrt_goal_finish(ctypes.byref(pending[0]), pending[1]), "tfrt_goal_finish")
+                self._goal_finish(*pending)
             for i, (g, p) in enumerate(zip(grads, opt.parameters)):
                 stream = ops._stream(p)
-                row = ctypes.c_void_p(hyper + 40 * i)
+                row = ctypes.c_void_p(hyper + row_bytes * i)
                 if accumulators[i] is not None:
                     # (the row's first three scalars: tfrt_sgd_process_dev reads no further)
                     processed = torch.empty_like(g)
@@ -1032,11 +996,15 @@ class FusedStep:
                                                  _lib.F64, row, stream), "tfrt_sgd_process_dev")
                     g = opt._matrix_product(opt._acc_cache, i, accumulators[i],
                                             processed).contiguous()
-                    row = ctypes.c_void_p(self._hyper_apply.dev.data_ptr() + 40 * i)
-                check(L.tfrt_sgd_momentum_multi(1, arr([g.data_ptr()]), None, arr([p.data_ptr()]),
-                                                arr([vel[i].data_ptr()]),
-                                                arr([g.numel()], ctypes.c_int64), row, stream),
-                      "tfrt_sgd_momentum_multi")
+                    row = ctypes.c_void_p(self._hyper_apply.dev.data_ptr() + row_bytes * i)
+                if momentum:
+                    check(L.tfrt_sgd_momentum_multi(
+                        1, arr([g.data_ptr()]), None, arr([p.data_ptr()]),
+                        arr([opt._velocity[i].data_ptr()]), arr([g.numel()], ctypes.c_int64), row,
+                        stream), "tfrt_sgd_momentum_multi")
+                else:
+                    check(L.tfrt_sgd_process_dev(ops._p(g), None, ops._p(p), g.numel(), _lib.F64,
+                                                 row, stream), "tfrt_sgd_process_dev")
 
     def _fix_grads(self, grads):
         opt = self.opt
@@ -1062,7 +1030,7 @@ class FusedStep:
             # no slicing after
             opt = self.opt
             n = sum(p.numel() for p in opt.parameters)
-            flat = getattr(self, "_flat_buf", None)
+            flat = self._flat_buf
             if flat is None or flat.numel() != n + 3 or flat.device != opt.parameters[0].device:
                 flat = self._flat_buf = torch.zeros(n + 3, dtype=torch.float64,
                                                     device=opt.parameters[0].device)
@@ -1155,7 +1123,7 @@ class FusedStep:
         dev = opt.parameters[0].device
         world = 2 if tdist.is_distributed() else 1      # > 1: the collective splits the sequence
         width = 5 if opt.apply_momentum else 3
-        if getattr(self, "_hyper", None) is None or self._hyper.width != width:
+        if self._hyper is None or self._hyper.width != width:
             # (a captured graph reads the table it was captured with: a new one invalidates it)
             self._graphs = None
             self._hyper = _HyperTable(len(opt.parameters), dev, width=width)
@@ -1181,7 +1149,7 @@ class FusedStep:
                 and getattr(opt.engine, "_trace_perm", None) is not None):
             # (ONE host read, early on: did the sorted source leave wavefronts to the grouped
             # kernel?  Many: coherent="auto" goes back to natural order for this source)
-            opt.engine._note_left_over(int(self._state["counts"][-1]), self._state["P"])
+            opt.engine._note_left_over(int(self._state.counts[-1]), self._state.P)
             self._last_sig = self._signature(accumulators)   # (what the note changes is no instability)
         return self._err_view
 
@@ -1208,17 +1176,12 @@ class FusedStep:
         return self._err_view
 
     def _stable(self, sig):
-        return getattr(self, "_last_sig", None) == sig
+        return self._last_sig == sig
 
     def _republish(self):
-        st = self._state
         eng = self.opt.engine
         eng.clear_ray_history()
-        if st.get("dim") == 2:
-            self._publish_lazily2d(st, eng._trace_src)
-            return
-        self._publish_lazily(st, eng._trace_src, st["P"], st["flags"],
-                             getattr(self, "_last_perm", None), getattr(self, "_last_inplace", None))
+        self._publish_lazily(self._state, eng._trace_src)
 
     def _capture(self, sig, accumulators, world):
         """Run THIS step eagerly on the capture stream, then capture the sequence there (capturing
@@ -1227,7 +1190,7 @@ class FusedStep:
         the caller's stream would make the backward inside the capture fork to that stream, and
         ending the capture then crashes inside the HIP runtime."""
         dev = self.opt.parameters[0].device
-        if getattr(self, "_stream", None) is None:
+        if self._stream is None:
             self._stream = torch.cuda.Stream(dev)
         side, cur = self._stream, torch.cuda.current_stream(dev)
         side.wait_stream(cur)
@@ -1252,7 +1215,7 @@ class FusedStep:
             # (the device is idle: one read tells whether the visiting-order trace of the step just
             # run left wavefronts to the grouped kernel; if not, the captured sequence omits it)
             if self._state is not None:
-                self.opt.engine._note_left_over(int(self._state["counts"][-1]), self._state["P"])
+                self.opt.engine._note_left_over(int(self._state.counts[-1]), self._state.P)
             sig = self._signature(accumulators)
             pool = torch.cuda.graph_pool_handle()
             ga, gb, grads = None, None, None

@@ -15,10 +15,15 @@ then evaluates it on fixed-shape columns (tfrt_trace2d_rows, tfrt_trace2d_backwa
 the same graph.  ``--generic`` forces the generic path (user error function, autograd) for
 comparison.  ``--deterministic`` sums the reverse sweep's gradients in an order-independent way
 (``OpticalEngine(deterministic=True)``): the whole run is bit-identical from one run to the next.
+``--random-source`` shapes the same lens over a beam that is re-drawn at every step (a
+``RandomUniformBeam``, one wavelength, one ray per beam point: stochastic gradient descent proper).
+On the GPU the source is a device program -- ``update()`` steps a counter, one launch writes the
+rays of the new draw into the same buffers --, so the step is captured like the static one; the
+run prints whether it was, and the mean step time by device events after ``--warmup`` steps.
 No GUI.
 
     python examples/optimize_arc.py [--rays 10] [--steps 30] [--momentum] [--rowwise] [--generic]
-                                    [--deterministic]
+                                    [--deterministic] [--random-source [--warmup 5]]
 """
 import argparse
 import math
@@ -42,7 +47,8 @@ import tfrt.sources as sources                # noqa: E402
 PI = math.pi
 
 
-def build(ray_count=10, ray_dtype=torch.float64, device="cuda:0", deterministic=False):
+def build(ray_count=10, ray_dtype=torch.float64, device="cuda:0", deterministic=False,
+          random_source=False):
     parameter = torch.tensor([5.0], dtype=torch.float64, device=device, requires_grad=True)
     arc = boundaries.ManualArcBoundary()
     arc["x_center"] = parameter
@@ -57,10 +63,16 @@ def build(ray_count=10, ray_dtype=torch.float64, device="cuda:0", deterministic=
     target.feed_segments(np.array([[10, -5, 10, 5]], dtype=np.float64))
     target.frozen = True
 
-    beam_points = distributions.StaticUniformBeam(-1.5, 1.5, ray_count)
     angles = distributions.StaticUniformAngularDistribution(0, 0, 1)
-    source = sources.AngularSource(2, (-1.0, 0.0), 0.0, angles, beam_points, drawing.RAINBOW_6)
-    source.frozen = True
+    if random_source:
+        # re-drawn by every update(): one ray per beam point (an undense source), one wavelength
+        beam_points = distributions.RandomUniformBeam(-1.5, 1.5, ray_count)
+        source = sources.AngularSource(2, (-1.0, 0.0), 0.0, angles, beam_points,
+                                       drawing.RAINBOW_6[3:4], dense=False)
+    else:
+        beam_points = distributions.StaticUniformBeam(-1.5, 1.5, ray_count)
+        source = sources.AngularSource(2, (-1.0, 0.0), 0.0, angles, beam_points, drawing.RAINBOW_6)
+        source.frozen = True
 
     system = engine.OpticalSystem2D()
     system.optical_arcs = [arc]
@@ -74,7 +86,7 @@ def build(ray_count=10, ray_dtype=torch.float64, device="cuda:0", deterministic=
     trace_engine.optical_system = system
     system.update()
     trace_engine.validate_system()
-    return dict(parameter=parameter, arc=arc, system=system, engine=trace_engine)
+    return dict(parameter=parameter, arc=arc, system=system, engine=trace_engine, source=source)
 
 
 def make_optimizer(scene, momentum=False, generic=False, rowwise=False):
@@ -92,10 +104,23 @@ def make_optimizer(scene, momentum=False, generic=False, rowwise=False):
 
 
 def run(ray_count=10, steps=30, momentum=False, generic=False, verbose=True, rowwise=False,
-        deterministic=False):
-    scene = build(ray_count, deterministic=deterministic)
+        deterministic=False, random_source=False, warmup=0):
+    """``warmup`` > 0: that many untimed steps first; the mean time of the ``steps`` after them (device
+    events around the loop, no host read inside it) is returned as ``ms_per_step``."""
+    scene = build(ray_count, deterministic=deterministic, random_source=random_source)
     opt = make_optimizer(scene, momentum, generic, rowwise)
     errors = []
+    if warmup > 0:
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for i in range(warmup + steps):
+            if i == warmup:
+                t0.record()
+            err = opt.single_step(None, momentum=0.8 if momentum else 0.0)
+            if i == 0 or i == warmup + steps - 1:
+                errors.append(float(err))
+        t1.record()
+        torch.cuda.synchronize()
+        return errors, dict(scene, optimizer=opt, ms_per_step=t0.elapsed_time(t1) / max(steps, 1))
     for i in range(steps):
         # the reference's schedule: 30 steps at learning rate 1, then 0.1 (its momentum stays 0.8:
         # the script's set_momentum call is commented out)
@@ -120,13 +145,24 @@ def main():
                     help="force the generic optimiser step (for comparison)")
     ap.add_argument("--deterministic", action="store_true",
                     help="bit-reproducible gradients (ordered reverse-sweep sums)")
+    ap.add_argument("--random-source", action="store_true",
+                    help="re-draw the beam at every step (RandomUniformBeam) and time the steps")
+    ap.add_argument("--warmup", type=int, default=5,
+                    help="untimed steps before the timed ones (--random-source)")
     a = ap.parse_args()
     errors, s = run(a.rays, a.steps, a.momentum, a.generic, rowwise=a.rowwise,
-                    deterministic=a.deterministic)
+                    deterministic=a.deterministic, random_source=a.random_source,
+                    warmup=max(a.warmup, 1) if a.random_source else 0, verbose=not a.random_source)
     fs = s["optimizer"]._fused_step
     path = ("generic" if fs is None else
             f"fused, {fs.graph_replays} of {fs.steps} steps replayed from a HIP graph")
     print(f"error {errors[0]:.6e} -> {errors[-1]:.6e} ({path})")
+    if a.random_source:
+        captured = fs is not None and fs.graph_replays > 0 and fs.capture_error is None
+        made = "device program" if hasattr(s["source"]._fields, "ray_block") else \
+            "host draw (torch)"
+        print(f"random source: {made}; step captured: {'yes' if captured else 'no'}; "
+              f"mean step {s['ms_per_step']:.3f} ms over {a.steps} steps")
 
 
 if __name__ == "__main__":

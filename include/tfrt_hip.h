@@ -971,6 +971,73 @@ int tfrt_source3d_generate(const tfrt_source3d_program* program, const int32_t* 
 int tfrt_source3d_pool_rows(const tfrt_source3d_program* program, const int32_t* index,
                             int64_t first, int64_t n, int32_t* rows, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 2-D sources made on the device.  Replaces, for 2-D sources that re-draw their rays at every
+ * update (dev/light_guide.py:45-49): the _update of RandomUniformAngularDistribution,
+ * RandomLambertianAngularDistribution, RandomUniformBeam and RandomUniformAperaturePoints
+ * (tfrt/distributions.py: tf.random.uniform pushed through the distribution's formula) and the
+ * 2-D branches of AperatureSource / PointSource / AngularSource._update (tfrt/sources.py:464-1095,
+ * undense sources).  The generator, the epoch counters and their meaning are those of the 3-D
+ * programs above; as there, parity with the reference is the distribution, not the sequence.
+ *
+ * A samples program is a 1-D distribution: sample i is made of ONE uniform number u, the first of
+ * Philox4x32-10(seed, stream, epoch, i) (the second is unused), as v = lo + (hi - lo) u, in
+ * float64.  It yields a value -- an angle (one column) or a point (two columns) -- and a rank. */
+#define TFRT_SMP_TABLE 0          /* value = row i of `table`; no rank (0) */
+#define TFRT_SMP_UNIFORM_ANGLE 1  /* angle = v in [lo, hi]; rank = angle / rank_scale,
+                                     rank_scale = max(|lo|, |hi|, 1e-300) */
+#define TFRT_SMP_LAMBERT_ANGLE 2  /* rank = v, lo = sin(min_angle), hi = sin(max_angle); angle = asin(rank) */
+#define TFRT_SMP_BEAM 3           /* rank = v in [r0, r1] = [lo, hi]; point = p0 * rank (p0: the beam's endpoint) */
+#define TFRT_SMP_APERTURE_POINTS 4 /* rank = u (lo = 0, hi = 1); point = p0 + rank * (p1 - p0) */
+typedef struct tfrt_samples_program {
+  int32_t kind;          /* TFRT_SMP_* */
+  int32_t stream;        /* distinguishes the distributions that share a seed */
+  int64_t count;         /* samples of the distribution */
+  const double* table;   /* TFRT_SMP_TABLE: (count, columns) f64 rows */
+  int32_t columns;       /* TFRT_SMP_TABLE: 1 (angles) or 2 (points); the other kinds have their own */
+  int32_t reserved0;
+  double lo, hi;         /* limits of the uniform draw, lo <= hi */
+  double rank_scale;     /* TFRT_SMP_UNIFORM_ANGLE */
+  double p0[2], p1[2];   /* TFRT_SMP_BEAM: endpoint, -; TFRT_SMP_APERTURE_POINTS: start, end */
+  uint64_t seed;
+  const int64_t* epoch;  /* device counter (one int64): the number of updates so far */
+} tfrt_samples_program;
+
+/* TFRT_SRC_APERTURE: start = a[i], end = b[i] (both point-valued);
+ * TFRT_SRC_POINT:    start = center, end = start + L (cos t, sin t), t = b[i] + central_angle;
+ * TFRT_SRC_ANGULAR:  start = center + R(central_angle) a[i], end as for TFRT_SRC_POINT
+ * (a point-valued, b angle-valued; `swap` exchanges start and end).  TFRT_SRC_POOL has no 2-D form. */
+typedef struct tfrt_source2d_program {
+  int32_t kind;          /* TFRT_SRC_APERTURE / TFRT_SRC_POINT / TFRT_SRC_ANGULAR */
+  int32_t swap;          /* start and end exchanged (start_on_center / start_on_base false) */
+  tfrt_samples_program a; /* start points / base points (unused by TFRT_SRC_POINT) */
+  tfrt_samples_program b; /* end points / angles */
+  double center[2];
+  double central_angle;
+  double rot[2];         /* cos, sin of central_angle, made on the host: R(central_angle) turns the
+                            base points of TFRT_SRC_ANGULAR (the same for every ray) */
+  double ray_length;
+  int64_t n_rays;        /* every input has 1 or n_rays samples */
+} tfrt_source2d_program;
+
+/* Samples first + index[j] (NULL: first + j), j < n, of one 1-D distribution at its current epoch:
+ * `values` (n, value_columns) f64 rows -- value_columns must be the program's own (1: angles, 2:
+ * points) -- and / or `ranks` (n) f64; either may be NULL.  Refused with TFRT_E_BADARG before any
+ * launch: a kind out of range, a random kind without an epoch counter, lo > hi (or a NaN limit),
+ * a table without storage or with columns other than 1 or 2. */
+int tfrt_samples_generate(const tfrt_samples_program* program, const int32_t* index,
+                          int64_t first, int64_t n, double* values, int32_t value_columns,
+                          double* ranks, void* stream);
+
+/* Rays first + index[j] (NULL: first + j), j < n, of a 2-D source at the current epochs of its
+ * distributions: `rays` a 4 x stride block of the state dtype and / or `fields` a 4 x field_stride
+ * f64 block (x_start, y_start, x_end, y_end); either may be NULL.  The block is the float64 result
+ * rounded once to the state dtype.  Refused like tfrt_samples_generate, and when an input is not
+ * point- / angle-valued as the kind needs, or has neither one sample nor n_rays. */
+int tfrt_source2d_generate(const tfrt_source2d_program* program, const int32_t* index,
+                           int64_t first, int64_t n, int32_t state_dtype, void* rays, int64_t stride,
+                           double* fields, int64_t field_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

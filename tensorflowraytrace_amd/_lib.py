@@ -105,8 +105,25 @@ class Source3DProgram(ctypes.Structure):
                 ("pool_seed", ctypes.c_uint64), ("pool_epoch", c_vp)]
 
 
+class SamplesProgram(ctypes.Structure):
+    """tfrt_samples_program (include/tfrt_hip.h)."""
+    _fields_ = [("kind", c_i32), ("stream", c_i32), ("count", c_i64), ("table", c_vp),
+                ("columns", c_i32), ("reserved0", c_i32), ("lo", c_f64), ("hi", c_f64),
+                ("rank_scale", c_f64), ("p0", c_f64 * 2), ("p1", c_f64 * 2),
+                ("seed", ctypes.c_uint64), ("epoch", c_vp)]
+
+
+class Source2DProgram(ctypes.Structure):
+    """tfrt_source2d_program (include/tfrt_hip.h)."""
+    _fields_ = [("kind", c_i32), ("swap", c_i32), ("a", SamplesProgram), ("b", SamplesProgram),
+                ("center", c_f64 * 2), ("central_angle", c_f64), ("rot", c_f64 * 2),
+                ("ray_length", c_f64),
+                ("n_rays", c_i64)]
+
+
 PTS_TABLE, PTS_CIRCLE, PTS_SQUARE, PTS_SPHERE_UNIFORM, PTS_SPHERE_LAMBERT = 0, 1, 2, 3, 4
 SRC_APERTURE, SRC_POINT, SRC_ANGULAR, SRC_POOL = 0, 1, 2, 3
+SMP_TABLE, SMP_UNIFORM_ANGLE, SMP_LAMBERT_ANGLE, SMP_BEAM, SMP_APERTURE_POINTS = 0, 1, 2, 3, 4
 
 _P = ctypes.POINTER
 
@@ -218,6 +235,10 @@ SIGNATURES = {
     "tfrt_source3d_generate": (c_i32, [_P(Source3DProgram), c_vp, c_i64, c_i64, c_i32, c_vp, c_i64,
                                        c_vp, c_i64, c_vp]),
     "tfrt_source3d_pool_rows": (c_i32, [_P(Source3DProgram), c_vp, c_i64, c_i64, c_vp, c_vp]),
+    "tfrt_samples_generate": (c_i32, [_P(SamplesProgram), c_vp, c_i64, c_i64, c_vp, c_i32, c_vp,
+                                      c_vp]),
+    "tfrt_source2d_generate": (c_i32, [_P(Source2DProgram), c_vp, c_i64, c_i64, c_i32, c_vp, c_i64,
+                                       c_vp, c_i64, c_vp]),
 }
 
 _lib = None

@@ -231,6 +231,69 @@ __device__ __forceinline__ void eval_ray(const tfrt_source3d_program& sp, int64_
   }
 }
 
+// ------------------------------------------------------------------------------------ 2-D
+// Sample `i` of a 1-D samples program, in float64: its value (v[0] an angle, or v[0], v[1] a point)
+// and its rank.  One Philox call per sample: the first number only (distributions.py: _uniform's
+// low + (high - low) * u, then the distribution's own formula).
+__device__ __forceinline__ void eval_sample(const tfrt_samples_program& pg, int64_t i, double v[2],
+                                            double* rank) {
+  v[0] = v[1] = 0.0;
+  *rank = 0.0;
+  if (pg.kind == TFRT_SMP_TABLE) {
+    // (never outside the table, whatever an `index` entry says; count >= 1 when anything is launched)
+    const int64_t r = i < 0 ? 0 : (i >= pg.count ? pg.count - 1 : i);
+    const double* row = pg.table + pg.columns * r;
+    v[0] = row[0];
+    if (pg.columns == 2) v[1] = row[1];
+    return;
+  }
+  double u, unused;
+  uniform2(pg.seed, (uint32_t)pg.stream, (uint64_t)*pg.epoch, (uint64_t)i, &u, &unused);
+  const double d = pg.lo + (pg.hi - pg.lo) * u;
+  if (pg.kind == TFRT_SMP_UNIFORM_ANGLE) {
+    v[0] = d;
+    *rank = d / pg.rank_scale;
+  } else if (pg.kind == TFRT_SMP_LAMBERT_ANGLE) {
+    v[0] = asin(d);
+    *rank = d;
+  } else if (pg.kind == TFRT_SMP_BEAM) {
+    v[0] = pg.p0[0] * d;
+    v[1] = pg.p0[1] * d;
+    *rank = d;
+  } else {                                       // TFRT_SMP_APERTURE_POINTS (lo = 0, hi = 1: d = u)
+    v[0] = pg.p0[0] + d * (pg.p1[0] - pg.p0[0]);
+    v[1] = pg.p0[1] + d * (pg.p1[1] - pg.p0[1]);
+    *rank = d;
+  }
+}
+
+// ray i of a 2-D source (the 2-D branches of sources.py's _internal_update): s, e = (x, y)
+__device__ __forceinline__ void eval_ray2(const tfrt_source2d_program& sp, int64_t i, double s[2],
+                                          double e[2]) {
+  const int64_t ia = sp.a.count == 1 ? 0 : i, ib = sp.b.count == 1 ? 0 : i;
+  double rank;
+  if (sp.kind == TFRT_SRC_APERTURE) {
+    eval_sample(sp.a, ia, s, &rank);
+    eval_sample(sp.b, ib, e, &rank);
+    return;
+  }
+  double ang[2], st[2] = {sp.center[0], sp.center[1]};
+  eval_sample(sp.b, ib, ang, &rank);
+  if (sp.kind == TFRT_SRC_ANGULAR) {
+    double base[2];
+    eval_sample(sp.a, ia, base, &rank);
+    st[0] += sp.rot[0] * base[0] - sp.rot[1] * base[1];   // (cos, sin from the host: uniform)
+    st[1] += sp.rot[1] * base[0] + sp.rot[0] * base[1];
+  }
+  double sn, cs;
+  sincos(ang[0] + sp.central_angle, &sn, &cs);
+  const double en[2] = {st[0] + sp.ray_length * cs, st[1] + sp.ray_length * sn};
+  s[0] = sp.swap ? en[0] : st[0];
+  s[1] = sp.swap ? en[1] : st[1];
+  e[0] = sp.swap ? st[0] : en[0];
+  e[1] = sp.swap ? st[1] : en[1];
+}
+
 // Host-side validity of the programs: everything a kernel dereferences or indexes by
 // (tfrt_points_generate, tfrt_source3d_generate and tfrt_source3d_order refuse what fails here with
 // TFRT_E_BADARG instead of launching on it).
@@ -262,6 +325,28 @@ inline bool source_program_ok(const tfrt_source3d_program* sp) {
   if (!points_program_ok(&sp->b)) return false;
   if (sp->kind != TFRT_SRC_POINT && !points_program_ok(&sp->a)) return false;
   // (undense: every input has one sample or one per ray)
+  const int64_t ca = sp->kind == TFRT_SRC_POINT ? 1 : sp->a.count, cb = sp->b.count;
+  return (ca == 1 || ca == sp->n_rays) && (cb == 1 || cb == sp->n_rays);
+}
+
+// columns of a samples program's value: 1 (an angle), 2 (a point), 0: not a valid program
+inline int samples_program_columns(const tfrt_samples_program* pg) {
+  if (!pg || pg->count < 0) return 0;
+  if (pg->kind == TFRT_SMP_TABLE) {
+    if (pg->columns != 1 && pg->columns != 2) return 0;
+    return (pg->count == 0 || pg->table != nullptr) ? pg->columns : 0;
+  }
+  if (pg->kind < TFRT_SMP_TABLE || pg->kind > TFRT_SMP_APERTURE_POINTS) return 0;
+  if (pg->epoch == nullptr || !(pg->lo <= pg->hi)) return 0;     // (a NaN limit fails too)
+  return pg->kind <= TFRT_SMP_LAMBERT_ANGLE ? 1 : 2;
+}
+
+inline bool source2d_program_ok(const tfrt_source2d_program* sp) {
+  if (!sp || sp->n_rays < 0) return false;
+  if (sp->kind < TFRT_SRC_APERTURE || sp->kind > TFRT_SRC_ANGULAR) return false;
+  // aperture: two point sets; point / angular: angles, and base points for the latter
+  if (samples_program_columns(&sp->b) != (sp->kind == TFRT_SRC_APERTURE ? 2 : 1)) return false;
+  if (sp->kind != TFRT_SRC_POINT && samples_program_columns(&sp->a) != 2) return false;
   const int64_t ca = sp->kind == TFRT_SRC_POINT ? 1 : sp->a.count, cb = sp->b.count;
   return (ca == 1 || ca == sp->n_rays) && (cb == 1 || cb == sp->n_rays);
 }

@@ -19,6 +19,11 @@
 //                    records, ray i = a row drawn with replacement (one Philox number) plus a
 //                    normal jitter of the end points (Box-Muller on three more draws); the row is
 //                    also handed out (tfrt_source3d_pool_rows) for the fields that are not geometry
+//   samples program  a 1-D distribution of a 2-D source (a random angle in a fan, uniform or
+//                    Lambertian; a random point on a beam or between two points; a table): ONE
+//                    uniform number per sample (distributions.py:350-377, 458-501)
+//   2-D source       the 2-D branches of the same three sources over two samples programs, a
+//                    centre and a scalar central angle (tfrt_source2d_program)
 //
 // Rays and points are functions of (program, epoch, i): they are written into the caller's
 // persistent buffers by one launch, any subset of them can be made again later (the sorted copy of
@@ -79,6 +84,55 @@ __global__ __launch_bounds__(BLOCK) void k_pool_rows(tfrt_source3d_program sp,
   const int64_t i = first + (index != nullptr ? index[j] : j);
   const uint64_t epoch = sp.pool_downsample ? (uint64_t)*sp.pool_epoch : 0;
   rows[j] = (int32_t)pool_row(sp, i, epoch);
+}
+
+// One lane per ray / sample, nothing shared: store-bound (4 state columns and / or 4 float64 columns
+// per ray, every column written by consecutive lanes).
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_source2d(tfrt_source2d_program sp,
+                                                    const int32_t* __restrict__ index,
+                                                    int64_t first, int64_t n,
+                                                    T* __restrict__ rays, int64_t stride,
+                                                    double* __restrict__ fields,
+                                                    int64_t fstride) {
+  const int64_t j = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (j >= n) return;
+  const int64_t i = first + (index != nullptr ? index[j] : j);
+  double s[2], e[2];
+  eval_ray2(sp, i, s, e);
+  if (rays != nullptr) {           // the float64 result rounded once
+    rays[j] = static_cast<T>(s[0]);
+    rays[stride + j] = static_cast<T>(s[1]);
+    rays[2 * stride + j] = static_cast<T>(e[0]);
+    rays[3 * stride + j] = static_cast<T>(e[1]);
+  }
+  if (fields != nullptr) {
+    fields[j] = s[0];
+    fields[fstride + j] = s[1];
+    fields[2 * fstride + j] = e[0];
+    fields[3 * fstride + j] = e[1];
+  }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_samples(tfrt_samples_program pg,
+                                                   const int32_t* __restrict__ index,
+                                                   int64_t first, int64_t n,
+                                                   double* __restrict__ values, int32_t cols,
+                                                   double* __restrict__ ranks) {
+  const int64_t j = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (j >= n) return;
+  const int64_t i = first + (index != nullptr ? index[j] : j);
+  double v[2], rank;
+  eval_sample(pg, i, v, &rank);
+  if (values != nullptr) {
+    if (cols == 2) {               // (n, 2) rows, as the distributions' `points`
+      values[2 * j] = v[0];
+      values[2 * j + 1] = v[1];
+    } else {
+      values[j] = v[0];
+    }
+  }
+  if (ranks != nullptr) ranks[j] = rank;
 }
 
 __global__ void k_epoch_advance(int64_t* p0, int64_t* p1, int64_t* p2, int64_t* p3, int64_t* p4,
@@ -165,6 +219,51 @@ int tfrt_source3d_pool_rows(const tfrt_source3d_program* program, const int32_t*
   if (rows == nullptr) return TFRT_E_BADARG;
   hipLaunchKernelGGL(k_pool_rows, dim3(cdiv(n, BLOCK)), dim3(BLOCK), 0,
                      static_cast<hipStream_t>(stream), *program, index, first, n, rows);
+  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+}
+
+int tfrt_samples_generate(const tfrt_samples_program* program, const int32_t* index,
+                          int64_t first, int64_t n, double* values, int32_t value_columns,
+                          double* ranks, void* stream) {
+  const int cols = samples_program_columns(program);
+  if (cols == 0 || n < 0 || value_columns != cols) return TFRT_E_BADARG;
+  if (first < 0 || (index == nullptr && first + n > program->count)) return TFRT_E_BADARG;
+  if (n == 0) return 0;
+  if (program->count == 0) return TFRT_E_BADARG;
+  hipLaunchKernelGGL(k_samples, dim3(cdiv(n, BLOCK)), dim3(BLOCK), 0,
+                     static_cast<hipStream_t>(stream), *program, index, first, n, values, cols,
+                     ranks);
+  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+}
+
+int tfrt_source2d_generate(const tfrt_source2d_program* program, const int32_t* index,
+                           int64_t first, int64_t n, int32_t state_dtype, void* rays, int64_t stride,
+                           double* fields, int64_t field_stride, void* stream) {
+  if (n < 0 || !source2d_program_ok(program)) return TFRT_E_BADARG;
+  if (first < 0 || (index == nullptr && first + n > program->n_rays)) return TFRT_E_BADARG;
+  if ((rays != nullptr && stride < n) || (fields != nullptr && field_stride < n))
+    return TFRT_E_BADARG;
+  if (state_dtype != TFRT_F32 && state_dtype != TFRT_F64 && state_dtype != TFRT_F16)
+    return TFRT_E_BADARG;
+  if (n == 0) return 0;
+  if (program->n_rays == 0) return TFRT_E_BADARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid(cdiv(n, BLOCK));
+#define TFRT_SOURCE2D(T)                                                                      \
+  hipLaunchKernelGGL((k_source2d<T>), grid, dim3(BLOCK), 0, st, *program, index, first, n,    \
+                     static_cast<T*>(rays), stride, fields, field_stride);
+  switch (state_dtype) {
+    case TFRT_F32:
+      TFRT_SOURCE2D(float)
+      break;
+    case TFRT_F64:
+      TFRT_SOURCE2D(double)
+      break;
+    default:
+      TFRT_SOURCE2D(_Float16)
+      break;
+  }
+#undef TFRT_SOURCE2D
   return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
 }
 

@@ -67,6 +67,8 @@ def _f64(x):
 # are made by one kernel when somebody asks, and a source made of such distributions writes its
 # rays straight into persistent buffers (sources.DeviceRaySet), in any order.  The numbers differ
 # from the torch generator's stream; the distributions are the same (tests/test_gpu_source_programs.py).
+# The 1-D distributions of 2-D sources (random angles, beams, aperture points) are programs of the
+# same kind (tfrt_samples_program, sources.DeviceRaySet2D; tests/test_gpu_source2d_programs.py).
 
 _device_random = True
 _streams = [0]
@@ -102,7 +104,43 @@ class _Drawn:
         obj.__dict__[self.name] = val
 
 
-class _DeviceRandom:
+class _DeviceDrawn:
+    """What the device-made distributions share: the epoch counter on the device, the stream of the
+    seed, and the samples materialised since the last update."""
+
+    def _device_update(self):
+        dev = config.get_device()
+        ep = self.__dict__.get("_epoch_dev")
+        if ep is None or ep.device != dev:
+            self._epoch_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+            _streams[0] += 1
+            self._stream_id = _streams[0]
+        self._device_active = True
+        # (the device counter is stepped when somebody draws -- a source does it for all of its
+        # distributions in one launch)
+        self._epoch_pending = self.__dict__.get("_epoch_pending", 0) + 1
+        self.epoch = self.__dict__.get("epoch", 0) + 1
+        self._drawn = {}
+        # (a transformation takes effect with the update after it was attached, like the
+        # reference's post-update handle)
+        self._active_transformations = list(self.__dict__.get("_transformations", ()))
+
+    def _leave_device_mode(self):
+        self.__dict__["_device_active"] = False
+
+    def pending_epochs(self):
+        """[(device counter, steps it is behind)] -- consumed by whoever flushes."""
+        n, self._epoch_pending = self.__dict__.get("_epoch_pending", 0), 0
+        return [(self._epoch_dev, n)] if n else []
+
+    def flush_epoch(self):
+        from . import ops
+        for counter, n in self.pending_epochs():
+            for _ in range(n):
+                ops.epoch_advance([counter])
+
+
+class _DeviceRandom(_DeviceDrawn):
     """Mixin of the Random* base point / direction distributions (see above)."""
 
     _kind = None          # _lib.PTS_*
@@ -121,37 +159,9 @@ class _DeviceRandom:
 
     def _device_update(self):
         from . import _lib
-        dev = config.get_device()
-        ep = self.__dict__.get("_epoch_dev")
-        if ep is None or ep.device != dev:
-            self._epoch_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-            _streams[0] += 1
-            self._stream_id = _streams[0]
-        self._device_active = True
-        # (the device counter is stepped when somebody draws -- a source does it for all of its
-        # distributions in one launch)
-        self._epoch_pending = self.__dict__.get("_epoch_pending", 0) + 1
-        self.epoch = self.__dict__.get("epoch", 0) + 1
-        self._drawn = {}
-        # (a transformation takes effect with the update after it was attached, like the
-        # reference's post-update handle)
-        self._active_transformations = list(self.__dict__.get("_transformations", ()))
+        super()._device_update()
         assert self._kind in (_lib.PTS_CIRCLE, _lib.PTS_SQUARE, _lib.PTS_SPHERE_UNIFORM,
                               _lib.PTS_SPHERE_LAMBERT)
-
-    def _leave_device_mode(self):
-        self.__dict__["_device_active"] = False
-
-    def pending_epochs(self):
-        """[(device counter, steps it is behind)] -- consumed by whoever flushes."""
-        n, self._epoch_pending = self.__dict__.get("_epoch_pending", 0), 0
-        return [(self._epoch_dev, n)] if n else []
-
-    def flush_epoch(self):
-        from . import ops
-        for counter, n in self.pending_epochs():
-            for _ in range(n):
-                ops.epoch_advance([counter])
 
     def _program_parameters(self):
         raise NotImplementedError
@@ -217,6 +227,70 @@ class _DeviceRandom:
             pts, a0, a1 = ops.points_generate(self.program(), self._sample_total(), columns=cols,
                                               want_aux=True, device=self._epoch_dev.device)
             d["points"], d["aux0"], d["aux1"] = pts, a0, a1
+        return d[what]
+
+
+class _DeviceRandom1D(_DeviceDrawn):
+    """Mixin of the 2-D sources' random distributions -- an angle in a fan, a point on a beam or
+    between two points --: a tfrt_samples_program, ONE uniform number per sample pushed through
+    the formulas of the torch path below.  ``angles`` / ``points`` / ``ranks`` are made by one
+    launch on first use after every update (tfrt_samples_generate)."""
+
+    _kind = None          # _lib.SMP_*
+
+    def _device_mode(self):
+        # (the limits and end points are baked into the program as numbers: when one of them
+        # requires grad the torch formulas run, so that autograd still reaches it; so they do
+        # with a BasePointTransformation, which a samples program has no room for)
+        baked = [self.__dict__.get(name) for name in
+                 ("min_angle", "max_angle", "_start_point", "_end_point")]
+        if any(isinstance(t, torch.Tensor) and t.requires_grad for t in baked):
+            return False
+        return (_device_random and config.get_device().type == "cuda"
+                and not self.__dict__.get("_transformations"))
+
+    def _sample_total(self):
+        return int(self.sample_count)
+
+    def _program_key(self):
+        """What the program's numbers depend on (cheap: no read-back)."""
+        raise NotImplementedError
+
+    def _program_numbers(self):
+        """(lo, hi, rank_scale, p0, p1) of tfrt_samples_program."""
+        raise NotImplementedError
+
+    def program(self):
+        """The distribution as a tfrt_samples_program.  Built once per set of parameters (reading
+        a point tensor back costs a host sync, which a captured launch sequence must not
+        contain)."""
+        from . import _lib
+        key = (self._kind, self._stream_id, self._sample_total(), self._program_key(), _seed,
+               self._epoch_dev.data_ptr())
+        cached = self.__dict__.get("_program_cache")
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        lo, hi, rank_scale, p0, p1 = self._program_numbers()
+        pg = _lib.SamplesProgram()
+        pg.kind, pg.stream, pg.count = self._kind, self._stream_id, self._sample_total()
+        pg.table, pg.columns = None, 0
+        pg.lo, pg.hi, pg.rank_scale = float(lo), float(hi), float(rank_scale)
+        for k in range(2):
+            pg.p0[k], pg.p1[k] = float(p0[k]), float(p1[k])
+        pg.seed = _seed & 0xFFFFFFFFFFFFFFFF
+        pg.epoch = self._epoch_dev.data_ptr()
+        self._program_cache = (key, pg)
+        return pg
+
+    def _draw(self, what):
+        from . import ops
+        d = self._drawn
+        if "values" not in d:
+            self.flush_epoch()
+            d["values"], d["ranks"] = ops.samples_generate(
+                self.program(), self._sample_total(), want_ranks=True,
+                device=self._epoch_dev.device)
+            d["ranks_column"] = d["ranks"].reshape(-1, 1)
         return d[what]
 
 
@@ -339,6 +413,10 @@ class ManualAngularDistribution(RecursivelyUpdatable):
 class StaticUniformAngularDistribution(AngularDistributionBase):
     """linspace(min_angle, max_angle, sample_count) (distributions.py:240-316)."""
 
+    def _static_key(self):
+        return (("StaticUniformAngularDistribution", float(self.min_angle), float(self.max_angle),
+                 int(self.sample_count)), ())
+
     def update(self):
         self.angle_limit_validation(-PI, PI)
         self._angles = torch.linspace(float(self.min_angle), float(self.max_angle),
@@ -347,9 +425,24 @@ class StaticUniformAngularDistribution(AngularDistributionBase):
         self._ranks = self._update_ranks(self._angles, self.min_angle, self.max_angle)
 
 
-class RandomUniformAngularDistribution(AngularDistributionBase):
+class RandomUniformAngularDistribution(_DeviceRandom1D, AngularDistributionBase):
+    _kind = 1     # _lib.SMP_UNIFORM_ANGLE
+    _angles = _Drawn("values")
+    _ranks = _Drawn("ranks")
+
+    def _program_key(self):
+        return (float(self.min_angle), float(self.max_angle))
+
+    def _program_numbers(self):
+        lo, hi = self._program_key()
+        return lo, hi, max(abs(lo), abs(hi), 1e-300), (0.0, 0.0), (0.0, 0.0)
+
     def update(self):
         self.angle_limit_validation(-PI, PI)
+        if self._device_mode():
+            self._device_update()
+            return
+        self._leave_device_mode()
         self._angles = _uniform(self.sample_count, float(self.min_angle), float(self.max_angle))
         self._ranks = self._update_ranks(self._angles, self.min_angle, self.max_angle)
 
@@ -357,6 +450,10 @@ class RandomUniformAngularDistribution(AngularDistributionBase):
 class StaticLambertianAngularDistribution(AngularDistributionBase):
     """Cosine-weighted fan: the rank is sin(angle), spaced evenly between sin(min_angle) and
     sin(max_angle) (distributions.py:394-470).  Limits must lie in [-pi/2, pi/2]."""
+
+    def _static_key(self):
+        return (("StaticLambertianAngularDistribution", float(self.min_angle),
+                 float(self.max_angle), int(self.sample_count)), ())
 
     def update(self):
         self.angle_limit_validation(-PI / 2.0, PI / 2.0)
@@ -366,12 +463,26 @@ class StaticLambertianAngularDistribution(AngularDistributionBase):
         self._angles = torch.asin(self._ranks)
 
 
-class RandomLambertianAngularDistribution(AngularDistributionBase):
+class RandomLambertianAngularDistribution(_DeviceRandom1D, AngularDistributionBase):
     """As above with the ranks drawn uniformly (distributions.py:473-556); re-sampled at
     every update."""
+    _kind = 2     # _lib.SMP_LAMBERT_ANGLE
+    _angles = _Drawn("values")
+    _ranks = _Drawn("ranks")
+
+    def _program_key(self):
+        return (float(self.min_angle), float(self.max_angle))
+
+    def _program_numbers(self):
+        lo, hi = self._program_key()
+        return math.sin(lo), math.sin(hi), 1.0, (0.0, 0.0), (0.0, 0.0)
 
     def update(self):
         self.angle_limit_validation(-PI / 2.0, PI / 2.0)
+        if self._device_mode():
+            self._device_update()
+            return
+        self._leave_device_mode()
         self._ranks = _uniform(self.sample_count, math.sin(float(self.min_angle)),
                                math.sin(float(self.max_angle)))
         self._angles = torch.asin(self._ranks)
@@ -429,7 +540,8 @@ class BeamPointBase(BasePointDistributionBase):
         self.central_angle = float(central_angle)
         super().__init__(**kwargs)
 
-    def _update(self):
+    def _beam_numbers(self):
+        """(start rank, end rank, the point of rank 1) after validating the parameters."""
         if self.beam_start > self.beam_end:
             raise ValueError("BeamPointBase: beam_start must be < beam_end.")
         self.sample_count_validation()
@@ -437,8 +549,12 @@ class BeamPointBase(BasePointDistributionBase):
         start_rank = self.beam_start / rank_scale
         end_rank = self.beam_end / rank_scale
         scale = self.beam_start / abs(start_rank)
-        endpoint = _f64([scale * math.cos(self.central_angle - PI / 2.0),
-                         scale * math.sin(self.central_angle - PI / 2.0)])
+        return start_rank, end_rank, (scale * math.cos(self.central_angle - PI / 2.0),
+                                      scale * math.sin(self.central_angle - PI / 2.0))
+
+    def _update(self):
+        start_rank, end_rank, endpoint = self._beam_numbers()
+        endpoint = _f64(list(endpoint))
         self._ranks = self._update_ranks(start_rank, end_rank, self.sample_count)
         self._points = endpoint.reshape(1, 2) * self._ranks.reshape(-1, 1)
 
@@ -449,13 +565,38 @@ class BeamPointBase(BasePointDistributionBase):
 
 
 class StaticUniformBeam(BeamPointBase):
+    def _static_key(self):
+        if self.post_update_handles:      # (a transformation: the points are not the formula's)
+            return None
+        return (("StaticUniformBeam", self.beam_start, self.beam_end, self.sample_count,
+                 self.central_angle), ())
+
     @staticmethod
     def _update_ranks(start_rank, end_rank, sample_count):
         return torch.linspace(start_rank, end_rank, sample_count, dtype=torch.float64,
                               device=config.get_device())
 
 
-class RandomUniformBeam(BeamPointBase):
+class RandomUniformBeam(_DeviceRandom1D, BeamPointBase):
+    _kind = 3     # _lib.SMP_BEAM
+    _points = _Drawn("values")
+    _ranks = _Drawn("ranks")
+
+    def _program_key(self):
+        return (self.beam_start, self.beam_end, self.central_angle)
+
+    def _program_numbers(self):
+        start_rank, end_rank, endpoint = self._beam_numbers()
+        return start_rank, end_rank, 1.0, endpoint, (0.0, 0.0)
+
+    def _update(self):
+        if self._device_mode():
+            self._beam_numbers()          # (the same refusals as the torch path)
+            self._device_update()
+            return
+        self._leave_device_mode()
+        super()._update()
+
     @staticmethod
     def _update_ranks(start_rank, end_rank, sample_count):
         return _uniform(sample_count, start_rank, end_rank)
@@ -489,13 +630,42 @@ class AperaturePointBase(BasePointDistributionBase):
 
 
 class StaticUniformAperaturePoints(AperaturePointBase):
+    def _static_key(self):
+        if self.post_update_handles:      # (a transformation: the points are not the formula's)
+            return None
+        ends = (self._start_point, self._end_point)
+        return (("StaticUniformAperaturePoints", tuple((id(t), t._version) for t in ends),
+                 self.sample_count), ends)
+
     @staticmethod
     def _update_ranks(sample_count):
         return torch.linspace(0.0, 1.0, sample_count, dtype=torch.float64,
                               device=config.get_device())
 
 
-class RandomUniformAperaturePoints(AperaturePointBase):
+class RandomUniformAperaturePoints(_DeviceRandom1D, AperaturePointBase):
+    _kind = 4     # _lib.SMP_APERTURE_POINTS
+    _points = _Drawn("values")
+    _ranks = _Drawn("ranks_column")
+
+    def _program_key(self):
+        return tuple((id(t), t._version) for t in (self._start_point, self._end_point))
+
+    def _program_numbers(self):
+        # (read back once per pair of tensors: program() keeps them with the key)
+        self._program_held = (self._start_point, self._end_point)
+        p0 = self._start_point.detach().cpu().reshape(-1).tolist()
+        p1 = self._end_point.detach().cpu().reshape(-1).tolist()
+        return 0.0, 1.0, 1.0, p0, p1
+
+    def _update(self):
+        if self._device_mode():
+            self.sample_count_validation()
+            self._device_update()
+            return
+        self._leave_device_mode()
+        super()._update()
+
     @staticmethod
     def _update_ranks(sample_count):
         return _uniform(sample_count)
@@ -1238,9 +1408,10 @@ class BasePointTransformation:
         self.translation = translation
         self.scale = scale
         self._base.post_update_handles.append(self._apply_transformation)
-        if isinstance(base, _DeviceRandom):
+        if isinstance(base, _DeviceDrawn):
             # the program of a device-random distribution carries ONE transformation; with a
-            # second one the distribution goes back to drawing with torch ops
+            # second one the distribution goes back to drawing with torch ops (a 1-D
+            # distribution's program carries none: it does so with the first)
             base.__dict__.setdefault("_transformations", []).append(self)
 
     def _apply_transformation(self):

@@ -1301,6 +1301,50 @@ def source3d_generate(program, n, dtype=None, first=0, index=None, rays_out=None
     return rays, fl
 
 
+def samples_generate(program, n, first=0, index=None, want_values=True, want_ranks=False,
+                     device=None):
+    """Samples of one 1-D distribution (a ``_lib.SamplesProgram``) at its current epoch
+    (tfrt_samples_generate): (values -- angles (n,) or points (n, 2) f64 -- or None, ranks (n,) f64
+    or None); ``index``: the samples ``first + index[j]`` instead of ``first + j``."""
+    dev = device if device is not None else (index.device if index is not None else None)
+    n = int(n)
+    cols = 1 if program.kind in (_lib.SMP_UNIFORM_ANGLE, _lib.SMP_LAMBERT_ANGLE) else \
+        (int(program.columns) if program.kind == _lib.SMP_TABLE else 2)
+    shape = (n,) if cols == 1 else (n, 2)
+    vals = torch.empty(shape, dtype=torch.float64, device=dev) if want_values else None
+    ranks = torch.empty(n, dtype=torch.float64, device=dev) if want_ranks else None
+    ref = vals if vals is not None else ranks
+    if n and ref is not None:
+        _need_gpu(ref, index)
+        check(_lib.lib().tfrt_samples_generate(ctypes.byref(program), _p(index), int(first), n,
+                                               _p(vals), cols, _p(ranks), _stream(ref)),
+              "tfrt_samples_generate")
+    return vals, ranks
+
+
+def source2d_generate(program, n, dtype=None, first=0, index=None, rays_out=None, fields=False,
+                      device=None):
+    """Rays of a 2-D source program (``_lib.Source2DProgram``) at the current epochs of its
+    distributions (tfrt_source2d_generate): (ray block (4, n) of ``dtype`` or None, fields (4, n)
+    f64 or None); ``index``: the rays ``first + index[j]`` instead of ``first + j``."""
+    n = int(n)
+    dev = device if device is not None else (index.device if index is not None else
+                                             (rays_out.device if rays_out is not None else None))
+    rays = rays_out
+    if rays is None and dtype is not None:
+        rays = torch.empty((4, n), dtype=dtype, device=dev)
+    fl = torch.empty((4, n), dtype=torch.float64, device=dev) if fields else None
+    ref = rays if rays is not None else fl
+    if n and ref is not None:
+        _need_gpu(ref, index)
+        dt = _DT[rays.dtype] if rays is not None else _lib.F64
+        check(_lib.lib().tfrt_source2d_generate(
+            ctypes.byref(program), _p(index), int(first), n, dt, _p(rays),
+            rays.stride(0) if rays is not None else 0, _p(fl), n if fl is not None else 0,
+            _stream(ref)), "tfrt_source2d_generate")
+    return rays, fl
+
+
 def source3d_pool_rows(program, n, first=0, index=None, out=None, device=None):
     """The pool rows the rays ``first + index[j]`` (``first + j``) of a TFRT_SRC_POOL program are made
     from at its current epoch (tfrt_source3d_pool_rows): (n,) int32 -- what every stored field that

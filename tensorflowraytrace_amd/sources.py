@@ -36,6 +36,7 @@ def _lib_kinds():
 
 
 _GEO3 = ("x_start", "y_start", "z_start", "x_end", "y_end", "z_end")
+_GEO2 = ("x_start", "y_start", "x_end", "y_end")
 
 
 def _host_array(value):
@@ -53,6 +54,8 @@ class DeviceRaySet:
     stack / cast), a field is one more launch on first use.  ``permuted(index)`` is the same set
     with ray j = ray ``index[j]`` (a coherent order), made by the same programs: an ordered copy
     of a re-drawn source costs a second launch, not a gather."""
+
+    _geo = _GEO3
 
     def __init__(self, source, first=0, count=None, index=None):
         self._src = source
@@ -88,7 +91,7 @@ class DeviceRaySet:
 
     # ------------------------------------------------------------------------- mapping
     def keys(self):
-        ks = list(_GEO3)
+        ks = list(self._geo)
         if self._src._wavelengths is not None:
             ks.append("wavelength")
         return ks + [f for f in self._src._extra_fields if f not in ks]
@@ -120,10 +123,10 @@ class DeviceRaySet:
 
     def __getitem__(self, key):
         src = self._src
-        if key in _GEO3:
+        if key in self._geo:
             block = self._memo("__fields__", lambda: src._device_rays(
                 self._first, self._n, self._index, None, fields=True)[1])
-            return block[_GEO3.index(key)]
+            return block[self._geo.index(key)]
         if key == "wavelength" and src._wavelengths is not None:
             return self._memo(key, lambda: self._cut(src._wavelength_column()))
         if key in src._extra_fields:
@@ -150,8 +153,20 @@ class DeviceRaySet:
                                   out=out, device=src._dev_device, stable=stable)
 
     def ray_block(self, dtype):
-        """(6, n) block of the ray-state dtype: a persistent buffer, filled once per update."""
+        """(6, n) block of the ray-state dtype ((4, n) in 2-D): a persistent buffer, filled once
+        per update."""
         return self._src._device_rays(self._first, self._n, self._index, dtype)[0]
+
+
+class DeviceRaySet2D(DeviceRaySet):
+    """The field set of a 2-D source made by a device program (tfrt_source2d_program): keys
+    ``x_start, y_start, x_end, y_end`` (``wavelength``, the extra fields), ``ray_block`` of shape
+    (4, n).  2-D traces keep the source's order: there is no coherent order to ask for."""
+
+    _geo = _GEO2
+
+    def order(self, face_verts=None, out=None, stable=True):
+        raise NotImplementedError("DeviceRaySet2D: 2-D rays have no coherent order")
 
 
 class PoolRaySet(DeviceRaySet):
@@ -204,7 +219,8 @@ class _DeviceMade:
         if v is None or (index is not None and v._index is not index):
             if len(views) > 16:
                 views.clear()
-            v = views[k] = self._ray_set(self, first, n, index)
+            cls = self._ray_set if self._dimension == 3 else DeviceRaySet2D
+            v = views[k] = cls(self, first, n, index)
         return v
 
     def _device_rays(self, first, n, index, dtype, fields=False):
@@ -212,6 +228,8 @@ class _DeviceMade:
         float64 field columns of rays ``first + index[j]``."""
         from . import ops
         sp = self._dev_program[1]
+        rows = 2 * self._dimension
+        generate = ops.source3d_generate if self._dimension == 3 else ops.source2d_generate
         bufs = self.__dict__.setdefault("_dev_buffers", {})
         ik = None if index is None else (id(index), index._version)
         rays = fl = None
@@ -219,14 +237,13 @@ class _DeviceMade:
             bk = (first, n, None if index is None else "index", dtype)
             ent = bufs.get(bk)
             if ent is None or ent[0].device != self._dev_device:
-                ent = bufs[bk] = [torch.empty((6, n), dtype=dtype, device=self._dev_device), None, None]
+                ent = bufs[bk] = [torch.empty((rows, n), dtype=dtype, device=self._dev_device), None, None]
             if ent[1] != (self._dev_epoch, ik):
-                ops.source3d_generate(sp, n, first=first, index=index, rays_out=ent[0])
+                generate(sp, n, first=first, index=index, rays_out=ent[0])
                 ent[1], ent[2] = (self._dev_epoch, ik), index
             rays = ent[0]
         if fields:
-            _, fl = ops.source3d_generate(sp, n, first=first, index=index, fields=True,
-                                          device=self._dev_device)
+            _, fl = generate(sp, n, first=first, index=index, fields=True, device=self._dev_device)
         return rays, fl
 
 
@@ -367,16 +384,68 @@ class SourceBase(_DeviceMade, RecursivelyUpdatable, ABC):
 
     # --------------------------------------------------------------- device programs
     def _device_inputs(self):
-        """(kind, a, b, extra) of tfrt_source3d_program for this source, ``a`` / ``b`` the input
-        distributions' point tensors or device-random distributions; None: no device form."""
+        """(kind, a, b, extra) of tfrt_source3d_program / tfrt_source2d_program for this source,
+        ``a`` / ``b`` the input distributions' point (angle) tensors or device-random
+        distributions; None: no device form."""
         return None
 
-    def _device_program(self):
-        """The source as a tfrt_source3d_program when that is possible: 3-D, undense, on a HIP
-        device, at least one input a device-random distribution (a source of static inputs keeps
-        its tensors: they are computed once anyway)."""
+    @staticmethod
+    def _static_of(distribution):
+        """(key, what the key's ids belong to) of a static distribution whose samples are a pure
+        function of its parameters (``_static_key``), else None."""
+        key = getattr(distribution, "_static_key", None)
+        return None if key is None else key()
+
+    def _table_program(self, pts, columns, static=None):
+        """A tensor input as a table program of the source's dimension: (program, the table it
+        points at, key), the table made once per tensor version; None: not a table of that form.
+        ``columns``: what the 2-D source reads from this input (1: angles, 2: points).
+        ``static``: ``_static_of`` the distribution the tensor comes from -- the static 1-D
+        distributions publish a new tensor with the same values at every update, so their table
+        is keyed by their parameters, made once, and the program (and with it a captured step's
+        signature) holds still from update to update."""
         from . import _lib
-        if (getattr(self, "_dimension", None) != 3 or self.dense or not dist._device_random
+        dim = self._dimension
+        if not isinstance(pts, torch.Tensor):
+            return None
+        if dim == 3:
+            if pts.dim() != 2 or pts.shape[1] not in (2, 3):
+                return None
+        elif (pts.dim() > 1 or pts.numel() < 1) if columns == 1 else \
+                (pts.dim() != 2 or pts.shape[1] != 2):
+            return None
+        if static is not None:
+            tkey = ("static", static[0], columns, str(pts.device))
+        else:
+            tkey = (id(pts), pts._version)
+        memo = self.__dict__.setdefault("_dev_tables", {})
+        hit = memo.get(tkey)
+        if hit is None:
+            t = _f64(pts.detach())
+            if dim == 3 and t.shape[1] == 2:
+                t = torch.cat([torch.zeros_like(t[:, :1]), t], dim=1)
+            elif dim == 2 and columns == 1:
+                t = t.reshape(-1)
+            if len(memo) > 8:
+                memo.clear()
+            # (holds what the key's ids name: they stay their own)
+            hit = memo[tkey] = (pts if static is None else static[1], t.contiguous())
+        if dim == 3:
+            pg = _lib.PointsProgram()
+            pg.kind = _lib.PTS_TABLE
+        else:
+            pg = _lib.SamplesProgram()
+            pg.kind, pg.columns = _lib.SMP_TABLE, columns
+        pg.count, pg.table = hit[1].shape[0], hit[1].data_ptr()
+        return pg, hit[1], ("table", tkey)
+
+    def _device_program(self):
+        """The source as a tfrt_source3d_program / tfrt_source2d_program when that is possible:
+        undense, on a HIP device, at least one input a device-random distribution (a source of
+        static inputs keeps its tensors: they are computed once anyway)."""
+        from . import _lib
+        dim = getattr(self, "_dimension", None)
+        if (dim not in (2, 3) or self.dense or not dist._device_random
                 or config.get_device().type != "cuda"):
             return None
         # (a program bakes center, central_angle, the wavelengths and table inputs in as numbers:
@@ -391,41 +460,37 @@ class SourceBase(_DeviceMade, RecursivelyUpdatable, ABC):
         kind, a, b, extra = spec
         if any(isinstance(d, torch.Tensor) and d.requires_grad for d in (a, b)):
             return None
-        live = [d for d in (a, b) if isinstance(d, dist._DeviceRandom)
+        random = dist._DeviceRandom if dim == 3 else dist._DeviceRandom1D
+        live = [d for d in (a, b) if isinstance(d, random)
                 and d.__dict__.get("_device_active")]
         if not live:
             return None
+        # (2-D: what the source reads from each input -- points, or angles)
+        columns = (2, 2 if kind == _lib.SRC_APERTURE else 1)
         counts, parts, keep, key = [], [], [], [kind]
-        for d in (a, b):
+        statics = extra.get("static", (None, None))
+        for d, cols, static in zip((a, b), columns, statics):
             if d is None:
                 parts.append(None)
                 key.append(None)
                 continue
-            if isinstance(d, dist._DeviceRandom) and d.__dict__.get("_device_active"):
+            if any(d is x for x in live):
                 pg = d.program()
+                if dim == 2 and (1 if pg.kind in (_lib.SMP_UNIFORM_ANGLE, _lib.SMP_LAMBERT_ANGLE)
+                                 else 2) != cols:
+                    return None
                 parts.append(pg)
                 counts.append(int(pg.count))
                 key.append(("program", id(d), id(pg)))
                 continue
-            pts = d if isinstance(d, torch.Tensor) else None
-            if pts is None or pts.dim() != 2 or pts.shape[1] not in (2, 3):
+            made = self._table_program(d, cols, static)
+            if made is None:
                 return None
-            tkey = (id(pts), pts._version)
-            memo = self.__dict__.setdefault("_dev_tables", {})
-            hit = memo.get(tkey)
-            if hit is None:
-                t = _f64(pts.detach())
-                if t.shape[1] == 2:
-                    t = torch.cat([torch.zeros_like(t[:, :1]), t], dim=1)
-                if len(memo) > 8:
-                    memo.clear()
-                hit = memo[tkey] = (pts, t.contiguous())
-            pg = _lib.PointsProgram()
-            pg.kind, pg.count, pg.table = _lib.PTS_TABLE, hit[1].shape[0], hit[1].data_ptr()
-            keep.append(hit[1])
+            pg, table, tkey = made
+            keep.append(table)
             parts.append(pg)
             counts.append(int(pg.count))
-            key.append(("table", tkey))
+            key.append(tkey)
         n = max(counts)
         if any(c not in (1, n) for c in counts):
             return None
@@ -436,19 +501,23 @@ class SourceBase(_DeviceMade, RecursivelyUpdatable, ABC):
         cached = self.__dict__.get("_dev_program")
         if cached is not None and cached[0] == key:
             return cached[1], n, key
-        sp = _lib.Source3DProgram()
+        sp = _lib.Source3DProgram() if dim == 3 else _lib.Source2DProgram()
         sp.kind = kind
         sp.swap = 1 if extra.get("swap") else 0
         if parts[0] is not None:
             sp.a = parts[0]
         sp.b = parts[1]
         c = extra.get("center")
-        for k in range(3):
+        for k in range(dim):
             sp.center[k] = 0.0 if c is None else c[k]
-        q = extra.get("quat")
-        sp.has_quat = 0 if q is None else 1
-        for k in range(4):
-            sp.quat[k] = 0.0 if q is None else q[k]
+        if dim == 3:
+            q = extra.get("quat")
+            sp.has_quat = 0 if q is None else 1
+            for k in range(4):
+                sp.quat[k] = 0.0 if q is None else q[k]
+        else:
+            sp.central_angle = float(extra.get("angle", 0.0))
+            sp.rot[0], sp.rot[1] = math.cos(sp.central_angle), math.sin(sp.central_angle)
         sp.ray_length = float(extra.get("ray_length", 1.0))
         sp.n_rays = n
         self._dev_program = (key, sp, keep, live)
@@ -515,6 +584,22 @@ class SourceBase(_DeviceMade, RecursivelyUpdatable, ABC):
             d.flush_epoch()
             return ops.points_generate(d.program(), n, first=first, index=index, columns=cols,
                                        device=self._dev_device)[0]
+        if len(items) == 3 and isinstance(items[1], dist._DeviceRandom1D) \
+                and items[1].__dict__.get("_device_active") and items[1]._sample_total() == self._dev_n \
+                and items[2] in ("ranks", "angles" if items[1]._kind <= 2 else "points"):
+            # ranks / angles / points of one of the source's own 1-D distributions: made in the
+            # asked order (tfrt_samples_generate)
+            d = items[1]
+            if index is None and first == 0 and n == self._dev_n:
+                return getattr(d, items[2])
+            d.flush_epoch()
+            ranks = items[2] == "ranks"
+            vals, rk = ops.samples_generate(d.program(), n, first=first, index=index,
+                                            want_values=not ranks, want_ranks=ranks,
+                                            device=self._dev_device)
+            if not ranks:
+                return vals
+            return rk.reshape(-1, 1) if d._kind == 4 else rk    # (aperture points: a column)
         domain, value = self._resolve_extra(items)
         value = value if isinstance(value, torch.Tensor) else torch.as_tensor(np.asarray(value))
         value = value.to(self._dev_device)
@@ -710,6 +795,13 @@ class PointSource(SourceBase, RotationBase):
 
     def _device_inputs(self):
         ad = self._angular_distribution
+        if self._dimension == 2:
+            b = ad if isinstance(ad, dist._DeviceRandom1D) else ad.angles
+            c = self._host_values("center", self._center)
+            t = self._host_values("angle", self._central_angle)[0]
+            return _lib_kinds()[1], None, b, dict(
+                static=(None, self._static_of(ad)), center=c, angle=t, ray_length=float(self.ray_length), swap=not self.start_on_center,
+                key=("point", tuple(c), t, float(self.ray_length), bool(self.start_on_center)))
         b = ad if isinstance(ad, dist._DeviceRandom) else (ad.angles if hasattr(ad, "angles") else ad.points)
         c = self._host_values("center", self._center)
         q = self._host_values("quat", self._central_angle, normalise=True)
@@ -765,6 +857,14 @@ class AngularSource(SourceBase, RotationBase):
 
     def _device_inputs(self):
         ad, bd = self._angular_distribution, self._base_point_distribution
+        if self._dimension == 2:
+            b = ad if isinstance(ad, dist._DeviceRandom1D) else ad.angles
+            a = bd if isinstance(bd, dist._DeviceRandom1D) else bd.points
+            c = self._host_values("center", self._center)
+            t = self._host_values("angle", self._central_angle)[0]
+            return _lib_kinds()[2], a, b, dict(
+                static=(self._static_of(bd), self._static_of(ad)), center=c, angle=t, ray_length=float(self.ray_length), swap=not self.start_on_base,
+                key=("angular", tuple(c), t, float(self.ray_length), bool(self.start_on_base)))
         b = ad if isinstance(ad, dist._DeviceRandom) else (ad.angles if hasattr(ad, "angles") else ad.points)
         a = bd if isinstance(bd, dist._DeviceRandom) else bd.points
         c = self._host_values("center", self._center)
@@ -818,9 +918,11 @@ class AperatureSource(SourceBase):
 
     def _device_inputs(self):
         sd, ed = self._start_point_distribution, self._end_point_distribution
-        a = sd if isinstance(sd, dist._DeviceRandom) else sd.points
-        b = ed if isinstance(ed, dist._DeviceRandom) else ed.points
-        return _lib_kinds()[0], a, b, dict(key=("aperture",))
+        random = dist._DeviceRandom if self._dimension == 3 else dist._DeviceRandom1D
+        a = sd if isinstance(sd, random) else sd.points
+        b = ed if isinstance(ed, random) else ed.points
+        static = (None, None) if self._dimension == 3 else (self._static_of(sd), self._static_of(ed))
+        return _lib_kinds()[0], a, b, dict(key=("aperture",), static=static)
 
     def axis_hint(self):
         """Direction the rays mostly share, when the programs tell (two shifted planar

@@ -1006,9 +1006,20 @@ typedef struct tfrt_samples_program {
 /* TFRT_SRC_APERTURE: start = a[i], end = b[i] (both point-valued);
  * TFRT_SRC_POINT:    start = center, end = start + L (cos t, sin t), t = b[i] + central_angle;
  * TFRT_SRC_ANGULAR:  start = center + R(central_angle) a[i], end as for TFRT_SRC_POINT
- * (a point-valued, b angle-valued; `swap` exchanges start and end).  TFRT_SRC_POOL has no 2-D form. */
+ * (a point-valued, b angle-valued; `swap` exchanges start and end).
+ * TFRT_SRC_POOL:     a stored pool of 2-D rays, re-sampled with replacement and jittered at every
+ * update (a 2-D PrecompiledSource): the draw of the 3-D pool program with two axes.  Ray i at epoch e
+ * -- e = *pool_epoch, read only when the program down-samples or has a positive sigma; otherwise 0,
+ * and the pointer may be NULL -- is pool row
+ *   row = pool_downsample ? clamp(floor(u0 * pool_count), 0, pool_count - 1) : i,
+ * u0 the first number of Philox4x32-10(pool_seed, pool_stream, e, i), the product in float64.  Every
+ * axis q in {0, 1} with a positive sigma takes the pair (u, v) of stream pool_stream + 1 + q at
+ * (e, i) and r = sqrt(-2 log(1 - u)): the start point moves by sigma_start[q] r cos(2 pi v), the end
+ * point by sigma_end[q] r sin(2 pi v).  A coordinate whose sigma is 0 is the stored one bit for bit.
+ * All of it in float64, rounded once to the state dtype.  `a`, `b`, center, central_angle, rot,
+ * ray_length and swap are unused by this kind. */
 typedef struct tfrt_source2d_program {
-  int32_t kind;          /* TFRT_SRC_APERTURE / TFRT_SRC_POINT / TFRT_SRC_ANGULAR */
+  int32_t kind;          /* TFRT_SRC_APERTURE / TFRT_SRC_POINT / TFRT_SRC_ANGULAR / TFRT_SRC_POOL */
   int32_t swap;          /* start and end exchanged (start_on_center / start_on_base false) */
   tfrt_samples_program a; /* start points / base points (unused by TFRT_SRC_POINT) */
   tfrt_samples_program b; /* end points / angles */
@@ -1018,6 +1029,14 @@ typedef struct tfrt_source2d_program {
                             base points of TFRT_SRC_ANGULAR (the same for every ray) */
   double ray_length;
   int64_t n_rays;        /* every input has 1 or n_rays samples */
+  /* TFRT_SRC_POOL only (zero otherwise) */
+  const double* pool;    /* (pool_count, 4) f64 ROW-major: one 32-byte record x_start, y_start, x_end, y_end per stored ray */
+  int64_t pool_count;    /* 1 ... INT32_MAX */
+  double sigma_start[2], sigma_end[2]; /* standard deviations of the jitter per axis, >= 0 */
+  int32_t pool_downsample; /* 0: ray i is row i (n_rays == pool_count) */
+  int32_t pool_stream;   /* streams pool_stream ... pool_stream + 2 of the seed */
+  uint64_t pool_seed;
+  const int64_t* pool_epoch; /* device counter; may be NULL when nothing is sampled or jittered */
 } tfrt_source2d_program;
 
 /* Samples first + index[j] (NULL: first + j), j < n, of one 1-D distribution at its current epoch:
@@ -1033,10 +1052,20 @@ int tfrt_samples_generate(const tfrt_samples_program* program, const int32_t* in
  * distributions: `rays` a 4 x stride block of the state dtype and / or `fields` a 4 x field_stride
  * f64 block (x_start, y_start, x_end, y_end); either may be NULL.  The block is the float64 result
  * rounded once to the state dtype.  Refused like tfrt_samples_generate, and when an input is not
- * point- / angle-valued as the kind needs, or has neither one sample nor n_rays. */
+ * point- / angle-valued as the kind needs, or has neither one sample nor n_rays.  A TFRT_SRC_POOL
+ * program is refused when `pool` is NULL, pool_count is not in 1 ... INT32_MAX, a sigma is negative
+ * or not finite, pool_epoch is NULL although the program down-samples or perturbs, or it does not
+ * down-sample and n_rays != pool_count. */
 int tfrt_source2d_generate(const tfrt_source2d_program* program, const int32_t* index,
                            int64_t first, int64_t n, int32_t state_dtype, void* rays, int64_t stride,
                            double* fields, int64_t field_stride, void* stream);
+
+/* TFRT_SRC_POOL: rows[j] = the pool row of ray first + index[j] (NULL: first + j), j < n, at the
+ * current epoch -- the row tfrt_source2d_generate reads for that ray (the same device function), so
+ * that a caller can gather every stored field that is not geometry.  Refused like
+ * tfrt_source2d_generate, and for a program of another kind. */
+int tfrt_source2d_pool_rows(const tfrt_source2d_program* program, const int32_t* index,
+                            int64_t first, int64_t n, int32_t* rows, void* stream);
 
 #ifdef __cplusplus
 }

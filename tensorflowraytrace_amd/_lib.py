@@ -118,7 +118,10 @@ class Source2DProgram(ctypes.Structure):
     _fields_ = [("kind", c_i32), ("swap", c_i32), ("a", SamplesProgram), ("b", SamplesProgram),
                 ("center", c_f64 * 2), ("central_angle", c_f64), ("rot", c_f64 * 2),
                 ("ray_length", c_f64),
-                ("n_rays", c_i64)]
+                ("n_rays", c_i64),
+                ("pool", c_vp), ("pool_count", c_i64), ("sigma_start", c_f64 * 2),
+                ("sigma_end", c_f64 * 2), ("pool_downsample", c_i32), ("pool_stream", c_i32),
+                ("pool_seed", ctypes.c_uint64), ("pool_epoch", c_vp)]
 
 
 PTS_TABLE, PTS_CIRCLE, PTS_SQUARE, PTS_SPHERE_UNIFORM, PTS_SPHERE_LAMBERT = 0, 1, 2, 3, 4
@@ -239,6 +242,7 @@ SIGNATURES = {
                                       c_vp]),
     "tfrt_source2d_generate": (c_i32, [_P(Source2DProgram), c_vp, c_i64, c_i64, c_i32, c_vp, c_i64,
                                        c_vp, c_i64, c_vp]),
+    "tfrt_source2d_pool_rows": (c_i32, [_P(Source2DProgram), c_vp, c_i64, c_i64, c_vp, c_vp]),
 }
 
 _lib = None

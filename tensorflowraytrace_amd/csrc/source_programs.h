@@ -1,4 +1,5 @@
-// Device functions of the source programs (tfrt_points_program / tfrt_source3d_program): shared by
+// Device functions of the source programs (tfrt_points_program / tfrt_source3d_program and their 2-D
+// counterparts tfrt_samples_program / tfrt_source2d_program): shared by
 // csrc/tfrt_source.hip (rays and points into the caller's buffers) and csrc/tfrt_order.hip (the
 // coherent order of a program's rays without ever writing them in source order).
 #pragma once
@@ -149,10 +150,17 @@ __device__ __forceinline__ void eval_points(const tfrt_points_program& pg, int64
   out[2] = p[2];
 }
 
-// TFRT_SRC_POOL: the stored row ray i is made from at `epoch`.  Float64 whatever the caller
-// evaluates in: a float32 product could name another row than the one that is traced.
-__device__ __forceinline__ int64_t pool_row(const tfrt_source3d_program& sp, int64_t i,
-                                            uint64_t epoch) {
+// TFRT_SRC_POOL, 3-D and 2-D alike (SP: tfrt_source3d_program / tfrt_source2d_program, whose pool
+// fields carry the same names; the axes are counted from sigma_start).
+template <typename SP>
+constexpr int pool_axes() {
+  return (int)(sizeof(SP::sigma_start) / sizeof(double));
+}
+
+// The stored row ray i is made from at `epoch`.  Float64 whatever the caller evaluates in: a
+// float32 product could name another row than the one that is traced.
+template <typename SP>
+__device__ __forceinline__ int64_t pool_row(const SP& sp, int64_t i, uint64_t epoch) {
   const int64_t last = sp.pool_count - 1;
   int64_t row = i;
   if (sp.pool_downsample) {
@@ -163,26 +171,31 @@ __device__ __forceinline__ int64_t pool_row(const tfrt_source3d_program& sp, int
   return row < 0 ? 0 : (row > last ? last : row);   // (never outside the pool, whatever `i` is)
 }
 
-__device__ __forceinline__ bool pool_perturbs(const tfrt_source3d_program& sp) {
-  return sp.sigma_start[0] > 0.0 || sp.sigma_start[1] > 0.0 || sp.sigma_start[2] > 0.0 ||
-         sp.sigma_end[0] > 0.0 || sp.sigma_end[1] > 0.0 || sp.sigma_end[2] > 0.0;
+template <typename SP>
+__device__ __forceinline__ bool pool_perturbs(const SP& sp) {
+  bool any = false;
+#pragma unroll
+  for (int q = 0; q < pool_axes<SP>(); ++q)
+    any = any || sp.sigma_start[q] > 0.0 || sp.sigma_end[q] > 0.0;
+  return any;
 }
 
-// ray i of a pool: the 48-byte record of its row, every axis with a sigma moved by sigma * z
-template <typename F>
-__device__ __forceinline__ void eval_pool(const tfrt_source3d_program& sp, int64_t i, F s[3],
-                                          F e[3]) {
+// ray i of a pool: the record of its row (48 bytes in 3-D, 32 in 2-D: the start point, then the end
+// point), every axis with a sigma moved by sigma * z
+template <typename F, typename SP>
+__device__ __forceinline__ void eval_pool(const SP& sp, int64_t i, F* s, F* e) {
+  constexpr int AXES = pool_axes<SP>();
   const bool jitter = pool_perturbs(sp);
   const uint64_t epoch = (sp.pool_downsample || jitter) ? (uint64_t)*sp.pool_epoch : 0;
-  const double* rec = sp.pool + 6 * pool_row(sp, i, epoch);
+  const double* rec = sp.pool + 2 * AXES * pool_row(sp, i, epoch);
 #pragma unroll
-  for (int q = 0; q < 3; ++q) {
+  for (int q = 0; q < AXES; ++q) {
     s[q] = (F)rec[q];
-    e[q] = (F)rec[3 + q];
+    e[q] = (F)rec[AXES + q];
   }
   if (!jitter) return;
 #pragma unroll
-  for (int q = 0; q < 3; ++q) {
+  for (int q = 0; q < AXES; ++q) {
     if (!(sp.sigma_start[q] > 0.0 || sp.sigma_end[q] > 0.0)) continue;
     double u, v;
     uniform2(sp.pool_seed, (uint32_t)(sp.pool_stream + 1 + q), epoch, (uint64_t)i, &u, &v);
@@ -267,9 +280,15 @@ __device__ __forceinline__ void eval_sample(const tfrt_samples_program& pg, int6
   }
 }
 
-// ray i of a 2-D source (the 2-D branches of sources.py's _internal_update): s, e = (x, y)
+// ray i of a 2-D source (the 2-D branches of sources.py's _internal_update): s, e = (x, y).
+// POOL: as for eval_ray -- the host picks the instantiation by the program's kind.
+template <bool POOL = false>
 __device__ __forceinline__ void eval_ray2(const tfrt_source2d_program& sp, int64_t i, double s[2],
                                           double e[2]) {
+  if constexpr (POOL) {
+    eval_pool<double>(sp, i, s, e);
+    return;
+  }
   const int64_t ia = sp.a.count == 1 ? 0 : i, ib = sp.b.count == 1 ? 0 : i;
   double rank;
   if (sp.kind == TFRT_SRC_APERTURE) {
@@ -305,11 +324,12 @@ inline bool points_program_ok(const tfrt_points_program* pg) {
 }
 
 // a pool program: the pool and its size, the widths, the counter whenever a kernel reads it
-inline bool pool_program_ok(const tfrt_source3d_program* sp) {
+template <typename SP>
+inline bool pool_program_ok(const SP* sp) {
   if (sp->pool == nullptr || sp->pool_count <= 0 || sp->pool_count > (int64_t)INT32_MAX)
     return false;
   bool jitter = false;
-  for (int q = 0; q < 3; ++q) {
+  for (int q = 0; q < pool_axes<SP>(); ++q) {
     const double a = sp->sigma_start[q], b = sp->sigma_end[q];
     if (!(a >= 0.0 && a <= DBL_MAX && b >= 0.0 && b <= DBL_MAX)) return false;   // (negative, inf, NaN)
     jitter = jitter || a > 0.0 || b > 0.0;
@@ -343,6 +363,7 @@ inline int samples_program_columns(const tfrt_samples_program* pg) {
 
 inline bool source2d_program_ok(const tfrt_source2d_program* sp) {
   if (!sp || sp->n_rays < 0) return false;
+  if (sp->kind == TFRT_SRC_POOL) return pool_program_ok(sp);
   if (sp->kind < TFRT_SRC_APERTURE || sp->kind > TFRT_SRC_ANGULAR) return false;
   // aperture: two point sets; point / angular: angles, and base points for the latter
   if (samples_program_columns(&sp->b) != (sp->kind == TFRT_SRC_APERTURE ? 2 : 1)) return false;

@@ -24,6 +24,8 @@
 //                    uniform number per sample (distributions.py:350-377, 458-501)
 //   2-D source       the 2-D branches of the same three sources over two samples programs, a
 //                    centre and a scalar central angle (tfrt_source2d_program)
+//   2-D pool         the pool program with two axes: 32-byte records, one row draw and two more
+//                    for the normals, the rows handed out by tfrt_source2d_pool_rows
 //
 // Rays and points are functions of (program, epoch, i): they are written into the caller's
 // persistent buffers by one launch, any subset of them can be made again later (the sorted copy of
@@ -74,9 +76,10 @@ __global__ __launch_bounds__(BLOCK) void k_source3d(tfrt_source3d_program sp,
   if (fields != nullptr) store_ray3(fields, fstride, j, s, e);
 }
 
-// TFRT_SRC_POOL: the row every ray is made from (eval_pool's own pool_row)
-__global__ __launch_bounds__(BLOCK) void k_pool_rows(tfrt_source3d_program sp,
-                                                     const int32_t* __restrict__ index,
+// TFRT_SRC_POOL: the row every ray is made from (eval_pool's own pool_row); SP: the 3-D or the 2-D
+// program
+template <typename SP>
+__global__ __launch_bounds__(BLOCK) void k_pool_rows(SP sp, const int32_t* __restrict__ index,
                                                      int64_t first, int64_t n,
                                                      int32_t* __restrict__ rows) {
   const int64_t j = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -87,8 +90,8 @@ __global__ __launch_bounds__(BLOCK) void k_pool_rows(tfrt_source3d_program sp,
 }
 
 // One lane per ray / sample, nothing shared: store-bound (4 state columns and / or 4 float64 columns
-// per ray, every column written by consecutive lanes).
-template <typename T>
+// per ray, every column written by consecutive lanes).  POOL: see eval_ray2.
+template <typename T, bool POOL>
 __global__ __launch_bounds__(BLOCK) void k_source2d(tfrt_source2d_program sp,
                                                     const int32_t* __restrict__ index,
                                                     int64_t first, int64_t n,
@@ -99,7 +102,7 @@ __global__ __launch_bounds__(BLOCK) void k_source2d(tfrt_source2d_program sp,
   if (j >= n) return;
   const int64_t i = first + (index != nullptr ? index[j] : j);
   double s[2], e[2];
-  eval_ray2(sp, i, s, e);
+  eval_ray2<POOL>(sp, i, s, e);
   if (rays != nullptr) {           // the float64 result rounded once
     rays[j] = static_cast<T>(s[0]);
     rays[stride + j] = static_cast<T>(s[1]);
@@ -217,7 +220,7 @@ int tfrt_source3d_pool_rows(const tfrt_source3d_program* program, const int32_t*
   if (first < 0 || (index == nullptr && first + n > program->n_rays)) return TFRT_E_BADARG;
   if (n == 0) return 0;
   if (rows == nullptr) return TFRT_E_BADARG;
-  hipLaunchKernelGGL(k_pool_rows, dim3(cdiv(n, BLOCK)), dim3(BLOCK), 0,
+  hipLaunchKernelGGL(k_pool_rows<tfrt_source3d_program>, dim3(cdiv(n, BLOCK)), dim3(BLOCK), 0,
                      static_cast<hipStream_t>(stream), *program, index, first, n, rows);
   return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
 }
@@ -249,9 +252,16 @@ int tfrt_source2d_generate(const tfrt_source2d_program* program, const int32_t* 
   if (program->n_rays == 0) return TFRT_E_BADARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(cdiv(n, BLOCK));
-#define TFRT_SOURCE2D(T)                                                                      \
-  hipLaunchKernelGGL((k_source2d<T>), grid, dim3(BLOCK), 0, st, *program, index, first, n,    \
-                     static_cast<T*>(rays), stride, fields, field_stride);
+  const bool pool = program->kind == TFRT_SRC_POOL;
+#define TFRT_SOURCE2D(T)                                                                          \
+  {                                                                                               \
+    if (pool)                                                                                     \
+      hipLaunchKernelGGL((k_source2d<T, true>), grid, dim3(BLOCK), 0, st, *program, index, first, \
+                         n, static_cast<T*>(rays), stride, fields, field_stride);                 \
+    else                                                                                          \
+      hipLaunchKernelGGL((k_source2d<T, false>), grid, dim3(BLOCK), 0, st, *program, index,       \
+                         first, n, static_cast<T*>(rays), stride, fields, field_stride);          \
+  }
   switch (state_dtype) {
     case TFRT_F32:
       TFRT_SOURCE2D(float)
@@ -264,6 +274,17 @@ int tfrt_source2d_generate(const tfrt_source2d_program* program, const int32_t* 
       break;
   }
 #undef TFRT_SOURCE2D
+  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+}
+
+int tfrt_source2d_pool_rows(const tfrt_source2d_program* program, const int32_t* index,
+                            int64_t first, int64_t n, int32_t* rows, void* stream) {
+  if (n < 0 || !source2d_program_ok(program) || program->kind != TFRT_SRC_POOL) return TFRT_E_BADARG;
+  if (first < 0 || (index == nullptr && first + n > program->n_rays)) return TFRT_E_BADARG;
+  if (n == 0) return 0;
+  if (rows == nullptr) return TFRT_E_BADARG;
+  hipLaunchKernelGGL(k_pool_rows<tfrt_source2d_program>, dim3(cdiv(n, BLOCK)), dim3(BLOCK), 0,
+                     static_cast<hipStream_t>(stream), *program, index, first, n, rows);
   return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
 }
 

@@ -1349,20 +1349,29 @@ def source3d_pool_rows(program, n, first=0, index=None, out=None, device=None):
     """The pool rows the rays ``first + index[j]`` (``first + j``) of a TFRT_SRC_POOL program are made
     from at its current epoch (tfrt_source3d_pool_rows): (n,) int32 -- what every stored field that
     is not geometry is gathered through."""
+    return _pool_rows("tfrt_source3d_pool_rows", program, n, first, index, out, device)
+
+
+def source2d_pool_rows(program, n, first=0, index=None, out=None, device=None):
+    """``source3d_pool_rows`` for a 2-D pool program (a ``_lib.Source2DProgram`` of kind
+    TFRT_SRC_POOL; tfrt_source2d_pool_rows)."""
+    return _pool_rows("tfrt_source2d_pool_rows", program, n, first, index, out, device)
+
+
+def _pool_rows(entry, program, n, first, index, out, device):
     n = int(n)
     dev = device if device is not None else (index.device if index is not None else
                                              (out.device if out is not None else None))
     rows = out if out is not None else torch.empty(n, dtype=torch.int32, device=dev)
     if rows.dtype != torch.int32 or rows.numel() != n or not rows.is_contiguous():
-        raise TfrtError("source3d_pool_rows: `out` must be a contiguous int32 tensor of n entries")
+        raise TfrtError(f"{entry[5:]}: `out` must be a contiguous int32 tensor of n entries")
     if index is not None and (index.dtype != torch.int32 or index.numel() != n
                               or not index.is_contiguous()):
-        raise TfrtError("source3d_pool_rows: `index` must be a contiguous int32 tensor of n entries")
+        raise TfrtError(f"{entry[5:]}: `index` must be a contiguous int32 tensor of n entries")
     if n:
         _need_gpu(rows, index)
-        check(_lib.lib().tfrt_source3d_pool_rows(ctypes.byref(program), _p(index), int(first), n,
-                                                 _p(rows), _stream(rows)),
-              "tfrt_source3d_pool_rows")
+        check(getattr(_lib.lib(), entry)(ctypes.byref(program), _p(index), int(first), n, _p(rows),
+                                         _stream(rows)), entry)
     return rows
 
 

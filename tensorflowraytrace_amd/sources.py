@@ -172,23 +172,36 @@ class DeviceRaySet2D(DeviceRaySet):
 class PoolRaySet(DeviceRaySet):
     """The field set of a device-made ``PrecompiledSource``: geometry from the pool program
     (TFRT_SRC_POOL: a stored row per ray, re-drawn and jittered every update), every other stored
-    field gathered through the rows the program drew (tfrt_source3d_pool_rows: the same device
-    function, so rows and rays are one draw) -- on first use, memoised until the next update."""
+    field gathered through the rows the program drew (tfrt_source3d_pool_rows /
+    tfrt_source2d_pool_rows: the same device function, so rows and rays are one draw) -- on first
+    use, memoised until the next update.  The geometry is the source's dimension's: six fields and a
+    (6, n) ``ray_block`` in 3-D, four and (4, n) in 2-D (where, as for ``DeviceRaySet2D``, there is
+    no coherent order to ask for)."""
+
+    def __init__(self, source, first=0, count=None, index=None):
+        super().__init__(source, first, count, index)
+        self._geo = _GEO3 if source._dimension == 3 else _GEO2
 
     def keys(self):
-        return list(_GEO3) + [f for f in self._src._pool_fields if f not in _GEO3]
+        return list(self._geo) + [f for f in self._src._pool_fields if f not in self._geo]
 
     def rows(self):
         """(n,) int32: the pool row of every ray of the set, in the set's order."""
         from . import ops
         src = self._src
-        return self._memo("__rows__", lambda: ops.source3d_pool_rows(
+        pool_rows = ops.source3d_pool_rows if src._dimension == 3 else ops.source2d_pool_rows
+        return self._memo("__rows__", lambda: pool_rows(
             src._dev_program[1], self._n, first=self._first, index=self._index,
             device=src._dev_device))
 
+    def order(self, face_verts=None, out=None, stable=True):
+        if self._src._dimension != 3:
+            raise NotImplementedError("PoolRaySet: 2-D rays have no coherent order")
+        return super().order(face_verts, out, stable)
+
     def __getitem__(self, key):
         src = self._src
-        if key in _GEO3:
+        if key in self._geo:
             return DeviceRaySet.__getitem__(self, key)
         if key not in src._pool_fields:
             raise KeyError(key)
@@ -210,7 +223,7 @@ class _DeviceMade:
     """What a source whose rays are made by a device program keeps for its ray sets: the views
     (one per shard / order) and the persistent ray blocks, filled once per update."""
 
-    _ray_set = DeviceRaySet
+    _ray_set, _ray_set_2d = DeviceRaySet, DeviceRaySet2D
 
     def _device_view(self, first, n, index):
         views = self.__dict__.setdefault("_dev_views", {})
@@ -219,7 +232,7 @@ class _DeviceMade:
         if v is None or (index is not None and v._index is not index):
             if len(views) > 16:
                 views.clear()
-            cls = self._ray_set if self._dimension == 3 else DeviceRaySet2D
+            cls = self._ray_set if self._dimension == 3 else self._ray_set_2d
             v = views[k] = cls(self, first, n, index)
         return v
 
@@ -961,14 +974,15 @@ class PrecompiledSource(_DeviceMade, RecursivelyUpdatable):
     (sources.py:1099-1358).  File format: pickle of
     ``{"dimension", "standard_domains", "fields": {name: ndarray}}`` (sources.py:1174-1181).
 
-    On a HIP device (3-D, ``distributions.set_device_random`` on, a pool that holds the six
-    geometry fields) the source is a device program like the Random* sources
-    (csrc/tfrt_source.hip, TFRT_SRC_POOL): the pool is uploaded once, ``update()`` only steps a
-    device counter, and the rays -- row indices and normal perturbations from the counter-based
-    generator -- are written straight into persistent buffers, in any order (``PoolRaySet``).
-    Elsewhere (CPU, 2-D, ``set_device_random(False)``) the rows are drawn and the pool indexed on
-    the host.  The source takes its four generator streams when it first enters device mode and
-    keeps them; like the Random* distributions among themselves, distributions made after a later
+    On a HIP device (``distributions.set_device_random`` on, a pool that holds the geometry
+    fields of its dimension: six in 3-D, four in 2-D) the source is a device program like the
+    Random* sources (csrc/tfrt_source.hip, TFRT_SRC_POOL): the pool is uploaded once, ``update()``
+    only steps a device counter, and the rays -- row indices and normal perturbations from the
+    counter-based generator -- are written straight into persistent buffers, in any order
+    (``PoolRaySet``).  Elsewhere (CPU, ``set_device_random(False)``, a pool without all of the
+    geometry fields) the rows are drawn and the pool indexed on the host.  The source takes its
+    generator streams (one for the rows, one per axis for the normals) when it first enters device
+    mode and keeps them; like the Random* distributions among themselves, distributions made after a later
     ``distributions.seed()`` (which starts the stream numbers again) may then share stream numbers
     with a source that is still alive -- the seed itself is part of the program, so re-seeding
     re-draws.
@@ -978,7 +992,7 @@ class PrecompiledSource(_DeviceMade, RecursivelyUpdatable):
     exist and raised AttributeError as soon as a perturbation was set), and an empty pool with a
     perturbation set updates to an empty source instead of raising KeyError."""
 
-    _ray_set = PoolRaySet
+    _ray_set = _ray_set_2d = PoolRaySet
 
     def __init__(self, arg, sample_count=100, do_downsample=True, start_perturbation=None,
                  end_perturbation=None, **kwargs):
@@ -1090,9 +1104,13 @@ class PrecompiledSource(_DeviceMade, RecursivelyUpdatable):
     # ------------------------------------------------------------------ device program
     def _device_mode(self):
         ff = self._full_fields
-        return (self._dimension == 3 and dist._device_random
-                and config.get_device().type == "cuda" and all(g in ff for g in _GEO3)
+        return (self._dimension in (2, 3) and dist._device_random
+                and config.get_device().type == "cuda" and all(g in ff for g in self._geo)
                 and self.sampling_domain_size > 0)
+
+    @property
+    def _geo(self):
+        return _GEO3 if self._dimension == 3 else _GEO2
 
     def _upload_pool(self, dev):
         """Records and field columns of the pool on ``dev``, once per pool (``from_samples`` /
@@ -1102,13 +1120,14 @@ class PrecompiledSource(_DeviceMade, RecursivelyUpdatable):
         if self._pool_key == key:
             return
         n = self.sampling_domain_size
-        rec = np.empty((n, 6), dtype=np.float64)       # one 48-byte record per stored ray
-        for k, g in enumerate(_GEO3):
+        geo = self._geo
+        rec = np.empty((n, len(geo)), dtype=np.float64)   # one 48- (3-D) or 32-byte record per stored ray
+        for k, g in enumerate(geo):
             rec[:, k] = np.asarray(ff[g], dtype=np.float64).reshape(n)
         self._pool_records = torch.from_numpy(rec).to(dev)
         self._pool_fields, self._pool_uniform = {}, set()
         for f, v in ff.items():
-            if f in _GEO3:
+            if f in geo:
                 self._pool_fields[f] = None            # (made by the program)
                 continue
             v = np.ascontiguousarray(v)
@@ -1123,28 +1142,29 @@ class PrecompiledSource(_DeviceMade, RecursivelyUpdatable):
     def _enter_device(self):
         from . import _lib, ops
         dev = config.get_device()
+        dim = self._dimension
         self._upload_pool(dev)
         ep = self.__dict__.get("_epoch_dev")
         if ep is None or ep.device != self._pool_records.device:
             self._epoch_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-            # (the rows draw on one stream of the seed, the normals of the three axes on the next three)
+            # (the rows draw on one stream of the seed, the normals of each axis on the next ones)
             self._stream_id = dist._streams[0] + 1
-            dist._streams[0] += 4
+            dist._streams[0] += 1 + dim
         down = bool(self.do_downsample)
         n = int(self._sample_count) if down else self.sampling_domain_size
-        sig = [tuple(float(v) for v in (np.zeros(3) if p is None else p))
+        sig = [tuple(float(v) for v in (np.zeros(dim) if p is None else p))
                for p in (self._start_perturbation, self._end_perturbation)]
         key = ("pool", self._pool_records.data_ptr(), self.sampling_domain_size, n, down, sig[0],
                sig[1], dist._seed, self._stream_id, self._epoch_dev.data_ptr())
         cached = self.__dict__.get("_dev_program")
         fresh = cached is None or cached[0] != key
         if fresh:
-            sp = _lib.Source3DProgram()
+            sp = _lib.Source3DProgram() if dim == 3 else _lib.Source2DProgram()
             sp.kind = _lib.SRC_POOL
             sp.n_rays = n
             sp.pool = self._pool_records.data_ptr()
             sp.pool_count = self.sampling_domain_size
-            for k in range(3):
+            for k in range(dim):
                 sp.sigma_start[k], sp.sigma_end[k] = sig[0][k], sig[1][k]
             sp.pool_downsample = 1 if down else 0
             sp.pool_stream = self._stream_id

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from oracle import sources as osources
+from source_reference import philox_uv
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -32,22 +33,8 @@ def _dist():
 # ------------------------------------------------------------------- numpy restatement
 def _philox_u(seed, stream, epoch, n):
     """First float64 of Philox4x32-10(counter = (sample, epoch), key = (seed, stream)) for samples
-    0 .. n-1: 53 bits of the first two output words, in [0, 1)."""
-    mask = np.uint64(0xFFFFFFFF)
-    s32 = np.uint64(32)
-    i = np.arange(n, dtype=np.uint64)
-    c = [i & mask, i >> s32, np.full(n, epoch & 0xFFFFFFFF, dtype=np.uint64),
-         np.full(n, epoch >> 32, dtype=np.uint64)]
-    k0, k1 = seed & 0xFFFFFFFF, ((seed >> 32) ^ stream) & 0xFFFFFFFF
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c[0]          # (32 x 32 bits: no overflow in 64)
-        p1 = np.uint64(0xCD9E8D57) * c[2]
-        n0 = (p1 >> s32) ^ c[1] ^ np.uint64(k0)
-        n2 = (p0 >> s32) ^ c[3] ^ np.uint64(k1)
-        c = [n0, p1 & mask, n2, p0 & mask]
-        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
-    a = (c[0] << s32) | c[1]
-    return (a >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+    0 .. n-1: 53 bits of the first two output words, in [0, 1) (tests/source_reference.py)."""
+    return philox_uv(seed, stream, epoch, n)[0]
 
 
 def _beam_numbers(beam_start, beam_end, central_angle):

@@ -1,0 +1,137 @@
+#!/usr/bin/env python3
+"""
+Illumination design, the workflow of the reference's dev/PCF_lens.py: "these rays start distributed
+like A and must land distributed like B".  The start points of an AperatureSource follow a two-bump
+density (ArbitraryBasePoints over an ArbitraryDistribution); their ranks -- a flat density
+evaluated at the same uniform seeds -- ride along as the extra field ``goal``
+(dev/PCF_lens.py:141-143), and a two-surface parametric acrylic lens (the one of
+examples/hexalens.py) is shaped so that every ray lands at -m times its goal: the bumps are spread
+into an even square.
+
+On a HIP device the density map is part of the source's device program: the rays are re-drawn in
+place every step, the goal rows are made in the order the rays are traced in, and the whole step is
+replayed from one HIP graph.  ``--host`` runs what there was before: scipy's interp1d on the host
+and an upload at every step, which the optimiser cannot capture.
+
+    python examples/illumination.py [--rays 20000] [--steps 30] [--edge 0.12] [--host]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import tfrt.boundaries as boundaries          # noqa: E402
+import tfrt.distributions as distributions    # noqa: E402
+import tfrt.drawing as drawing                # noqa: E402
+import tfrt.engine as engine                  # noqa: E402
+import tfrt.materials as materials            # noqa: E402
+import tfrt.mesh_tools as mt                  # noqa: E402
+import tfrt.operation as operation            # noqa: E402
+import tfrt.optimizer as optimizer            # noqa: E402
+import tfrt.sources as sources                # noqa: E402
+
+COARSEST_EDGE = 0.4        # the coarsest lens mesh the example is run with (the tests' lens)
+DENSITY_CELLS = 64
+
+
+def two_bumps(size):
+    """The source's density on [-size, size]^2: two Gaussian bumps on a faint floor."""
+    def density(gx, gy):
+        a = np.exp(-((gx + 0.4 * size) ** 2 + (gy - 0.3 * size) ** 2) / (2 * (0.25 * size) ** 2))
+        b = np.exp(-((gx - 0.5 * size) ** 2 + (gy + 0.2 * size) ** 2) / (2 * (0.18 * size) ** 2))
+        return 0.02 + a + 0.7 * b
+    return density
+
+
+def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, magnification=1.0,
+          object_size=0.2, lens_aperature=1.0, rowwise=True, **engine_kw):
+    limits = ((-object_size, object_size, DENSITY_CELLS), (-object_size, object_size, DENSITY_CELLS))
+    start_density = distributions.ArbitraryDistribution(two_bumps(object_size), limits)
+    goal_density = distributions.ArbitraryDistribution(lambda gx, gy: np.ones_like(gx), limits)
+    start_points = distributions.ArbitraryBasePoints(start_density, ray_count,
+                                                     rank_distribution=goal_density)
+    distributions.BasePointTransformation(start_points, translation=(-source_distance, 0, 0))
+    end_points = distributions.RandomUniformCircle(ray_count, 0.98 * lens_aperature)
+    distributions.BasePointTransformation(end_points)
+    source = sources.AperatureSource(
+        3, start_points, end_points, [drawing.YELLOW], dense=False,
+        extra_fields={"goal": ("start_point", start_points, "ranks")})
+
+    zero_points = mt.circular_mesh(lens_aperature, lens_res_scale)
+    zero_points.rotate_y(90)
+    zero_points.rotate_x(90)
+    top_parent = mt.get_closest_point(zero_points, (0, 0, 0))
+    vertex_update_map, accumulator = mt.mesh_parametrization_tools(zero_points, top_parent)
+
+    lens = boundaries.ParametricMultiTriangleBoundary(
+        zero_points, boundaries.FromVectorVG((1, 0, 0)),
+        [boundaries.ThicknessConstraint(0.0, "min"), boundaries.ThicknessConstraint(0.2, "min")],
+        [True, False],
+        material_list=[{"mat_in": 1, "mat_out": 0}] * 2,
+        vertex_update_map=vertex_update_map)
+    target = boundaries.ManualTriangleBoundary(mesh=mt.plane(
+        center=(source_distance * magnification, 0, 0), direction=(1, 0, 0), i_size=100, j_size=100))
+    target.frozen = True
+
+    system = engine.OpticalSystem3D()
+    system.optical = lens.surfaces
+    system.targets = [target]
+    system.sources = [source]
+    system.materials = [{"n": materials.vacuum}, {"n": materials.acrylic}]
+    system.update()
+
+    trace_engine = engine.OpticalEngine(
+        3, [operation.StandardReaction()], compile_active_rays=False,
+        simple_ray_inheritance={"wavelength", "goal"}, **engine_kw)
+    trace_engine.optical_system = system
+    trace_engine.validate_system()
+
+    m = magnification
+    error_function = optimizer.GoalError(("y_end", "z_end"), lambda s: -m * s["goal"], rowwise=rowwise)
+    return dict(engine=trace_engine, system=system, lens=lens, source=source,
+                start_points=start_points, error_function=error_function, accumulator=accumulator)
+
+
+def run(ray_count=20000, steps=30, lens_res_scale=0.12, host=False, verbose=True):
+    distributions.set_device_random(not host)
+    try:
+        s = build(ray_count, lens_res_scale)
+        opt = optimizer.SGD_Optimizer(s["engine"], s["lens"].parameters, s["error_function"], 3,
+                                      learning_rate=2e-5 * (20000 / ray_count), grad_clip=1.0)
+        opt.suppress_warnings = True
+        errors, times = [], []
+        for step in range(steps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            errors.append(float(opt.single_step(s["accumulator"] if step < steps // 2 else None)))
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+            if verbose and step % 5 == 0:
+                print(f"step {step:4d}: mean squared error {errors[-1]:.6g}  ({1e3 * times[-1]:.2f} ms)")
+        fused = opt._fused_step
+        s.update(errors=errors, times=times, device_source=s["source"]._device_program() is not None,
+                 graph_replays=0 if fused is None else fused.graph_replays)
+        return s
+    finally:
+        distributions.set_device_random(True)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rays", type=int, default=20000)
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--edge", type=float, default=0.12, help=f"lens mesh edge, up to {COARSEST_EDGE}")
+    ap.add_argument("--host", action="store_true",
+                    help="the density map on the host at every step (scipy), as before it had a program")
+    a = ap.parse_args()
+    out = run(a.rays, a.steps, a.edge, host=a.host)
+    tail = sorted(out["times"][len(out["times"]) // 2:])
+    print(f"source on the device: {out['device_source']}; steps replayed from the graph: "
+          f"{out['graph_replays']} of {a.steps}; median step of the second half: "
+          f"{1e3 * tail[len(tail) // 2]:.3f} ms")
+    print(f"mean squared illumination error: first {out['errors'][0]:.6g} -> last {out['errors'][-1]:.6g}")

@@ -873,6 +873,22 @@ int tfrt_restore_order(const int32_t* ray_id, int64_t n_rows, const int32_t* seg
 #define TFRT_PTS_SQUARE 2         /* (0, -xs + 2 xs u0, -ys + 2 ys u1) */
 #define TFRT_PTS_SPHERE_UNIFORM 3 /* phi = acos(lo + (1 - lo) u0), theta = theta_mod(pi (1 + sqrt 5) u1) */
 #define TFRT_PTS_SPHERE_LAMBERT 4 /* phi = acos(sqrt(lo + (1 - lo) u0)), lo = cos^2(angular_size) */
+/* Points that follow a 2-D density (ArbitraryBasePoints over an ArbitraryDistribution,
+ * tfrt/distributions.py:2635-2798 and :2123-2280): with p = {x_min, x_max, y_min, y_max}, x_min < x_max, y_min < y_max,
+ *   bx = x_min + (x_max - x_min) u0,  by = y_min + (y_max - y_min) u1,
+ *   x = Qx(bx),  cell = floor((x - x_min) x_count / (x_max - x_min)),  y = Qy[cell](by),
+ * the point before the transformation (0, x, y).  Q(v) over a table (xs, ys) of m knots is scipy's
+ * linear interp1d: k = clamp(first index with xs[k] >= v, 1, m - 1), the line through knots k - 1
+ * and k; xs is non-decreasing and may hold equal neighbours.  A sample whose cell is outside
+ * [0, min(x_count, y_count)) keeps y = 0 (the reference visits the x cells with range(y_count)).
+ * `density` is ONE packed f64 device buffer of 2 (x_count + 1) + 2 x_count (y_count + 1) numbers:
+ *   [Qx.xs (x_count + 1) | Qx.ys (x_count + 1) | x_count x (Qy.xs (y_count + 1) | Qy.ys (y_count + 1))]
+ * `rank_density` (or NULL) has the same layout and counts: aux0 / aux1 are rank_scale times its map
+ * of the same (bx, by); 0 without it.  Search, cell and interpolation run in float64 wherever the
+ * program is evaluated (the result is rounded to the evaluation's type at the end), so that the
+ * order's float32 keys belong to the very rays that are traced: a cell chosen in float32 could take
+ * another y curve. */
+#define TFRT_PTS_DENSITY 5
 typedef struct tfrt_points_program {
   int32_t kind;          /* TFRT_PTS_* */
   int32_t stream;        /* distinguishes the distributions that share a seed */
@@ -880,13 +896,18 @@ typedef struct tfrt_points_program {
   const double* table;   /* TFRT_PTS_TABLE: (count, 3) f64 */
   /* circle: {radius, theta_start, theta_end, -}; square: {x_size, -, -, y_size} (centre to
    * edge); spheres: {radius, theta_start, theta_end, lo}, lo = cos(angular_size) [uniform] or its
-   * square [Lambertian] */
+   * square [Lambertian]; density: {x_min, x_max, y_min, y_max} */
   double p[4];
   double scale[3], quat[4], shift[3]; /* BasePointTransformation: scale, unit quaternion (w, x, y, z), translation */
   int32_t has_scale, has_quat, has_shift;
   int32_t reserved0;
   uint64_t seed;
   const int64_t* epoch;  /* device counter (one int64): the number of updates so far */
+  /* TFRT_PTS_DENSITY only (zero otherwise) */
+  int32_t x_count, y_count; /* cells of the density grid, >= 1 */
+  const double* density; /* the packed quantile tables (see TFRT_PTS_DENSITY) */
+  const double* rank_density; /* the rank distribution's, same counts and limits; or NULL */
+  double rank_scale;
 } tfrt_points_program;
 
 #define TFRT_SRC_APERTURE 0 /* start = a[i], end = b[i]                                      sources.py:918-1095 */
@@ -952,7 +973,7 @@ int tfrt_epoch_advance(int64_t* const* epochs, int32_t n, void* stream);
  * the transformation as (n, 3) f64 rows (point_columns 3) or the distribution's own plane as
  * (n, 2) rows (point_columns 2: components y, z), and the two numbers its rank properties are made
  * of (circle: r in [0, 1] and theta; spheres: phi and theta; square: the point before the
- * transformation) -- each output may be NULL. */
+ * transformation; density: the rank point's two components) -- each output may be NULL. */
 int tfrt_points_generate(const tfrt_points_program* program, const int32_t* index,
                          int64_t first, int64_t n, double* points, int32_t point_columns, double* aux0, double* aux1,
                          void* stream);

@@ -92,7 +92,11 @@ class PointsProgram(ctypes.Structure):
     _fields_ = [("kind", c_i32), ("stream", c_i32), ("count", c_i64), ("table", c_vp),
                 ("p", c_f64 * 4), ("scale", c_f64 * 3), ("quat", c_f64 * 4), ("shift", c_f64 * 3),
                 ("has_scale", c_i32), ("has_quat", c_i32), ("has_shift", c_i32),
-                ("reserved0", c_i32), ("seed", ctypes.c_uint64), ("epoch", c_vp)]
+                ("reserved0", c_i32), ("seed", ctypes.c_uint64), ("epoch", c_vp),
+                # PTS_DENSITY only: the grid's cells, the packed quantile tables of the points'
+                # and of the ranks' density, the factor on the ranks
+                ("x_count", c_i32), ("y_count", c_i32), ("density", c_vp),
+                ("rank_density", c_vp), ("rank_scale", c_f64)]
 
 
 class Source3DProgram(ctypes.Structure):
@@ -125,6 +129,7 @@ class Source2DProgram(ctypes.Structure):
 
 
 PTS_TABLE, PTS_CIRCLE, PTS_SQUARE, PTS_SPHERE_UNIFORM, PTS_SPHERE_LAMBERT = 0, 1, 2, 3, 4
+PTS_DENSITY = 5
 SRC_APERTURE, SRC_POINT, SRC_ANGULAR, SRC_POOL = 0, 1, 2, 3
 SMP_TABLE, SMP_UNIFORM_ANGLE, SMP_LAMBERT_ANGLE, SMP_BEAM, SMP_APERTURE_POINTS = 0, 1, 2, 3, 4
 

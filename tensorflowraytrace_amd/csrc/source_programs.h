@@ -6,6 +6,7 @@
 #include <cfloat>
 #include <cstdint>
 #include "tfrt_common.h"
+#include "density_map.h"
 
 namespace tfrt {
 
@@ -69,12 +70,31 @@ __device__ __forceinline__ void quat_rotate(const double qd[4], F v[3]) {
   v[2] = r2;
 }
 
+// TFRT_PTS_DENSITY: the plane point xy and the rank point rk of the uniform pair (u0, u1), in
+// float64 whatever the caller evaluates in.
+__device__ __forceinline__ void density_point(const tfrt_points_program& pg, double u0, double u1,
+                                              double xy[2], double rk[2]) {
+  const double bx = pg.p[0] + (pg.p[1] - pg.p[0]) * u0;
+  const double by = pg.p[2] + (pg.p[3] - pg.p[2]) * u1;
+  density_map(pg.density, pg.x_count, pg.y_count, pg.p, bx, by, &xy[0], &xy[1]);
+  rk[0] = rk[1] = 0.0;
+  if (pg.rank_density != nullptr) {
+    density_map(pg.rank_density, pg.x_count, pg.y_count, pg.p, bx, by, &rk[0], &rk[1]);
+    rk[0] *= pg.rank_scale;
+    rk[1] *= pg.rank_scale;
+  }
+}
+
 constexpr double TWO_PI = 6.283185307179586476925286766559;
 constexpr double GOLDEN_TURN = 3.14159265358979323846 * (1.0 + 2.2360679774997896964);  // pi (1 + sqrt 5)
 
 // Sample `i` of a points program: the 3-D point (after the transformation) and the two numbers the
-// distribution's rank properties are made of (circle: r in [0, 1], theta; sphere: phi, theta).
-template <typename F>
+// distribution's rank properties are made of (circle: r in [0, 1], theta; sphere: phi, theta;
+// density: the rank point).  DENSITY: the program may be a TFRT_PTS_DENSITY one -- the host picks the
+// instantiation by the program's kind, as for the pool (see eval_ray): inlined into the one kernel
+// of all kinds, the two binary searches cost the order's key kernel 21 VGPRs (108 -> 129) and a
+// wavefront of occupancy whatever the kind; behind a call, 17.
+template <typename F, bool DENSITY = false>
 __device__ __forceinline__ void eval_points(const tfrt_points_program& pg, int64_t i, F out[3],
                                             F aux[2]) {
   F p[3] = {(F)0, (F)0, (F)0};
@@ -119,6 +139,13 @@ __device__ __forceinline__ void eval_points(const tfrt_points_program& pg, int64
       p[2] = -P3 + ((F)2 * P3) * u1;
       aux[0] = p[1];
       aux[1] = p[2];
+    } else if (DENSITY && pg.kind == TFRT_PTS_DENSITY) {    // p = {x_min, x_max, y_min, y_max}
+      double xy[2], rk[2];
+      density_point(pg, ud0, ud1, xy, rk);
+      p[1] = (F)xy[0];
+      p[2] = (F)xy[1];
+      aux[0] = (F)rk[0];
+      aux[1] = (F)rk[1];
     } else {                                     // p = {radius, theta_start, theta_end, lower bound}
       const F c = P3 + ((F)1 - P3) * u0;
       // cos(phi) = c (uniform cap) or sqrt(c) (Lambertian: cos^2 is uniform); sin from it
@@ -210,8 +237,9 @@ __device__ __forceinline__ void eval_pool(const SP& sp, int64_t i, F* s, F* e) {
 
 // ray i of the source (natural numbering).  POOL: the program is a TFRT_SRC_POOL one -- the host
 // picks the instantiation by the program's kind, so that the kernels of the procedural kinds carry
-// nothing of the pool's code or registers, and the pool's nothing of theirs.
-template <bool POOL = false, typename F>
+// nothing of the pool's code or registers, and the pool's nothing of theirs.  DENSITY: one of the
+// inputs is a TFRT_PTS_DENSITY program (source_program_density), in the same way.
+template <bool POOL = false, bool DENSITY = false, typename F>
 __device__ __forceinline__ void eval_ray(const tfrt_source3d_program& sp, int64_t i, F s[3],
                                          F e[3]) {
   if constexpr (POOL) {
@@ -221,14 +249,14 @@ __device__ __forceinline__ void eval_ray(const tfrt_source3d_program& sp, int64_
   F a[3] = {(F)0, (F)0, (F)0}, b[3] = {(F)0, (F)0, (F)0}, aux[2];
   const int64_t ia = sp.a.count == 1 ? 0 : i, ib = sp.b.count == 1 ? 0 : i;
   if (sp.kind == TFRT_SRC_APERTURE) {
-    eval_points<F>(sp.a, ia, s, aux);
-    eval_points<F>(sp.b, ib, e, aux);
+    eval_points<F, DENSITY>(sp.a, ia, s, aux);
+    eval_points<F, DENSITY>(sp.b, ib, e, aux);
     return;
   }
-  eval_points<F>(sp.b, ib, b, aux);   // the direction vectors
+  eval_points<F, DENSITY>(sp.b, ib, b, aux);   // the direction vectors
   if (sp.has_quat) quat_rotate<F>(sp.quat, b);
   if (sp.kind == TFRT_SRC_ANGULAR) {
-    eval_points<F>(sp.a, ia, a, aux);
+    eval_points<F, DENSITY>(sp.a, ia, a, aux);
     if (sp.has_quat) quat_rotate<F>(sp.quat, a);
   }
   F st[3], en[3];
@@ -319,7 +347,14 @@ __device__ __forceinline__ void eval_ray2(const tfrt_source2d_program& sp, int64
 inline bool points_program_ok(const tfrt_points_program* pg) {
   if (!pg || pg->count < 0) return false;
   if (pg->kind == TFRT_PTS_TABLE) return pg->count == 0 || pg->table != nullptr;
-  if (pg->kind < TFRT_PTS_TABLE || pg->kind > TFRT_PTS_SPHERE_LAMBERT) return false;
+  if (pg->kind < TFRT_PTS_TABLE || pg->kind > TFRT_PTS_DENSITY) return false;
+  if (pg->kind == TFRT_PTS_DENSITY) {
+    // the tables the searches read, their sizes, a rectangle with an inside (a NaN limit fails too)
+    if (pg->density == nullptr || pg->x_count < 1 || pg->y_count < 1) return false;
+    if (!(pg->p[0] < pg->p[1] && pg->p[2] < pg->p[3])) return false;
+    if (!(pg->p[0] >= -DBL_MAX && pg->p[1] <= DBL_MAX && pg->p[2] >= -DBL_MAX && pg->p[3] <= DBL_MAX))
+      return false;
+  }
   return pg->epoch != nullptr;
 }
 
@@ -336,6 +371,12 @@ inline bool pool_program_ok(const SP* sp) {
   }
   if ((sp->pool_downsample || jitter) && sp->pool_epoch == nullptr) return false;
   return sp->pool_downsample || sp->n_rays == sp->pool_count;
+}
+
+// a valid procedural program one of whose inputs is a TFRT_PTS_DENSITY one: the DENSITY kernels
+inline bool source_program_density(const tfrt_source3d_program* sp) {
+  return sp->kind != TFRT_SRC_POOL && (sp->b.kind == TFRT_PTS_DENSITY ||
+                                       (sp->kind != TFRT_SRC_POINT && sp->a.kind == TFRT_PTS_DENSITY));
 }
 
 inline bool source_program_ok(const tfrt_source3d_program* sp) {

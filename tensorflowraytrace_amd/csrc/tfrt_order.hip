@@ -35,19 +35,21 @@ struct BlockRays {
     load_ray3(rays, stride, i, s, e);
   }
 };
-// (POOL: a TFRT_SRC_POOL program; its own instantiation of the kernels, see eval_ray)
-template <bool POOL>
+// (POOL: a TFRT_SRC_POOL program, DENSITY: one with a TFRT_PTS_DENSITY input; their own
+// instantiations of the kernels, see eval_ray)
+template <bool POOL, bool DENSITY = false>
 struct ProgramRaysT {
   static constexpr bool HAS_F32 = true;
   tfrt_source3d_program sp;
   int64_t first;
   __device__ __forceinline__ void load(int64_t i, double s[3], double e[3]) const {
-    eval_ray<POOL>(sp, first + i, s, e);
+    eval_ray<POOL, DENSITY>(sp, first + i, s, e);
   }
   // (float32 evaluation: enough for the order's keys, a fraction of the float64 one's time; a
-  // pool's row is chosen in float64 all the same: the keys are those of the rays that are traced)
+  // pool's row and a density's cell are chosen in float64 all the same: the keys are those of the
+  // rays that are traced)
   __device__ __forceinline__ void load_f(int64_t i, float s[3], float e[3]) const {
-    eval_ray<POOL>(sp, first + i, s, e);
+    eval_ray<POOL, DENSITY>(sp, first + i, s, e);
   }
 };
 using ProgramRays = ProgramRaysT<false>;
@@ -1428,6 +1430,9 @@ static int source3d_order(const tfrt_source3d_program* program, int64_t first, i
   if (program->kind == TFRT_SRC_POOL)
     rc = ray_order_t(ProgramRaysT<true>{*program, first}, n_rays, face_verts, n_faces, axis, perm,
                      keys_out, ws, L, st, cells);
+  else if (source_program_density(program))
+    rc = ray_order_t(ProgramRaysT<false, true>{*program, first}, n_rays, face_verts, n_faces, axis,
+                     perm, keys_out, ws, L, st, cells);
   else
     rc = ray_order_t(ProgramRays{*program, first}, n_rays, face_verts, n_faces, axis, perm,
                      keys_out, ws, L, st, cells);

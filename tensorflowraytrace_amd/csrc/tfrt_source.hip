@@ -11,7 +11,8 @@
 //                    or two uniform numbers of a counter-based generator (Philox4x32-10, counter =
 //                    (sample, epoch), key = (seed, stream)) pushed through the distribution's
 //                    formula (circle / square / spherical cap, uniform or Lambertian:
-//                    distributions.py:1375-1393, 1586-1598, 1751-1775, 1814-1850) and the
+//                    distributions.py:1375-1393, 1586-1598, 1751-1775, 1814-1850; or the quantile
+//                    curves of a 2-D density, density_map.h: ArbitraryBasePoints, :2635-2798) and the
 //                    transformation (lift to 3-D, scale, quaternion, translation)
 //   source program   AperatureSource / PointSource / AngularSource assembly of two of those
 //                    (tfrt/sources.py:464-1095, undense: sample i of each input makes ray i)
@@ -36,6 +37,8 @@
 
 namespace tfrt {
 
+// DENSITY: a TFRT_PTS_DENSITY program (see eval_points)
+template <bool DENSITY>
 __global__ __launch_bounds__(BLOCK) void k_points(tfrt_points_program pg, const int32_t* index,
                                                   int64_t first, int64_t n,
                                                   double* __restrict__ points,
@@ -45,7 +48,7 @@ __global__ __launch_bounds__(BLOCK) void k_points(tfrt_points_program pg, const 
   if (j >= n) return;
   const int64_t i = first + (index != nullptr ? index[j] : j);
   double p[3], aux[2];
-  eval_points(pg, i, p, aux);
+  eval_points<double, DENSITY>(pg, i, p, aux);
   if (points != nullptr) {
     if (cols == 3) {
       points[3 * j] = p[0];
@@ -60,7 +63,7 @@ __global__ __launch_bounds__(BLOCK) void k_points(tfrt_points_program pg, const 
   if (aux1 != nullptr) aux1[j] = aux[1];
 }
 
-template <typename T, bool POOL>
+template <typename T, bool POOL, bool DENSITY>
 __global__ __launch_bounds__(BLOCK) void k_source3d(tfrt_source3d_program sp,
                                                     const int32_t* __restrict__ index,
                                                     int64_t first, int64_t n,
@@ -71,7 +74,7 @@ __global__ __launch_bounds__(BLOCK) void k_source3d(tfrt_source3d_program sp,
   if (j >= n) return;
   const int64_t i = first + (index != nullptr ? index[j] : j);
   double s[3], e[3];
-  eval_ray<POOL>(sp, i, s, e);
+  eval_ray<POOL, DENSITY>(sp, i, s, e);
   if (rays != nullptr) store_ray3(rays, stride, j, s, e);
   if (fields != nullptr) store_ray3(fields, fstride, j, s, e);
 }
@@ -171,9 +174,14 @@ int tfrt_points_generate(const tfrt_points_program* program, const int32_t* inde
     return TFRT_E_BADARG;
   if (first < 0 || (index == nullptr && first + n > program->count)) return TFRT_E_BADARG;
   if (n == 0) return 0;
-  hipLaunchKernelGGL(k_points, dim3(cdiv(n, BLOCK)), dim3(BLOCK), 0,
-                     static_cast<hipStream_t>(stream), *program, index, first, n, points, point_columns,
-                     aux0, aux1);
+  if (program->kind == TFRT_PTS_DENSITY)
+    hipLaunchKernelGGL(k_points<true>, dim3(cdiv(n, BLOCK)), dim3(BLOCK), 0,
+                       static_cast<hipStream_t>(stream), *program, index, first, n, points,
+                       point_columns, aux0, aux1);
+  else
+    hipLaunchKernelGGL(k_points<false>, dim3(cdiv(n, BLOCK)), dim3(BLOCK), 0,
+                       static_cast<hipStream_t>(stream), *program, index, first, n, points,
+                       point_columns, aux0, aux1);
   return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
 }
 
@@ -187,15 +195,18 @@ int tfrt_source3d_generate(const tfrt_source3d_program* program, const int32_t* 
   if (n == 0) return 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(cdiv(n, BLOCK));
-  const bool pool = program->kind == TFRT_SRC_POOL;
+  const bool pool = program->kind == TFRT_SRC_POOL, density = source_program_density(program);
+#define TFRT_SOURCE3D_AS(T, POOL, DENSITY)                                                        \
+  hipLaunchKernelGGL((k_source3d<T, POOL, DENSITY>), grid, dim3(BLOCK), 0, st, *program, index,   \
+                     first, n, static_cast<T*>(rays), stride, fields, field_stride)
 #define TFRT_SOURCE3D(T)                                                                          \
   {                                                                                               \
     if (pool)                                                                                     \
-      hipLaunchKernelGGL((k_source3d<T, true>), grid, dim3(BLOCK), 0, st, *program, index, first, \
-                         n, static_cast<T*>(rays), stride, fields, field_stride);                 \
+      TFRT_SOURCE3D_AS(T, true, false);                                                           \
+    else if (density)                                                                             \
+      TFRT_SOURCE3D_AS(T, false, true);                                                           \
     else                                                                                          \
-      hipLaunchKernelGGL((k_source3d<T, false>), grid, dim3(BLOCK), 0, st, *program, index,       \
-                         first, n, static_cast<T*>(rays), stride, fields, field_stride);          \
+      TFRT_SOURCE3D_AS(T, false, false);                                                          \
   }
   switch (state_dtype) {
     case TFRT_F32:
@@ -211,6 +222,7 @@ int tfrt_source3d_generate(const tfrt_source3d_program* program, const int32_t* 
       return TFRT_E_BADARG;
   }
 #undef TFRT_SOURCE3D
+#undef TFRT_SOURCE3D_AS
   return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
 }
 

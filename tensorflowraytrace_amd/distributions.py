@@ -161,10 +161,18 @@ class _DeviceRandom(_DeviceDrawn):
         from . import _lib
         super()._device_update()
         assert self._kind in (_lib.PTS_CIRCLE, _lib.PTS_SQUARE, _lib.PTS_SPHERE_UNIFORM,
-                              _lib.PTS_SPHERE_LAMBERT)
+                              _lib.PTS_SPHERE_LAMBERT, _lib.PTS_DENSITY)
 
     def _program_parameters(self):
         raise NotImplementedError
+
+    def _program_key(self):
+        """What the program depends on beyond ``_program_parameters`` (cheap: no read-back)."""
+        return ()
+
+    def _program_fill(self, pg):
+        """The fields of the program that only this kind has; returns what they point at."""
+        return None
 
     def program(self):
         """The distribution as a tfrt_points_program (with its BasePointTransformation).  Built
@@ -176,7 +184,7 @@ class _DeviceRandom(_DeviceDrawn):
         if tr:
             tensors = [tr[0].scale, tr[0].rotation, tr[0].translation]
         key = (self._kind, self._stream_id, self._sample_total(),
-               tuple(float(v) for v in self._program_parameters()), _seed,
+               tuple(float(v) for v in self._program_parameters()), self._program_key(), _seed,
                self._epoch_dev.data_ptr(),
                tuple((id(t), getattr(t, "_version", None)) for t in tensors))
         cached = self.__dict__.get("_program_cache")
@@ -211,7 +219,7 @@ class _DeviceRandom(_DeviceDrawn):
                     pg.shift[k] = sh[k]
         pg.seed = _seed & 0xFFFFFFFFFFFFFFFF
         pg.epoch = self._epoch_dev.data_ptr()
-        self._program_cache = (key, pg, tensors)
+        self._program_cache = (key, pg, tensors, self._program_fill(pg))
         return pg
 
     def _transformed(self):
@@ -1053,6 +1061,21 @@ class ArbitraryDistribution:
                 "density function.")
         return n * (n_max - n_min) / top + n_min
 
+    def evaluation_limits(self):
+        """(x_min, x_max, y_min, y_max) of the rectangle the uniform seeds are drawn from."""
+        return (float(self._x_min), float(self._x_max), float(self._y_min), float(self._y_max))
+
+    def packed_tables(self):
+        """The knots of the very interp1d objects ``__call__`` evaluates, as the one float64 array
+        of tfrt_points_program.density (include/tfrt_hip.h):
+        [Qx.xs | Qx.ys | x_count x (Qy.xs | Qy.ys)], interp1d's own sorted ``x`` and ``y``."""
+        parts = [self._x_quantile.x, self._x_quantile.y]
+        for q in self._y_quantiles:
+            parts.extend((q.x, q.y))
+        out = np.concatenate([np.asarray(a, dtype=np.float64).reshape(-1) for a in parts])
+        assert out.size == 2 * (self._x_count + 1) + 2 * self._x_count * (self._y_count + 1)
+        return out
+
     def __call__(self, x, y):
         x, y = np.asarray(_as_np(x), dtype=np.float64), np.asarray(_as_np(y), dtype=np.float64)
         x_out = self._x_quantile(x)
@@ -1176,10 +1199,18 @@ class CumulativeDensityFunction:
         return self.cdf(points)
 
 
-class ArbitraryBasePoints(BasePointDistributionBase):
+class ArbitraryBasePoints(_DeviceRandom, BasePointDistributionBase):
     """Base points following an ArbitraryDistribution, with ranks from a second one evaluated
     at the same uniform seeds (distributions.py:2635-2798); ``enforce_etendue`` rescales the
-    ranks so their mean distance from ``origin`` equals the points'."""
+    ranks so their mean distance from ``origin`` equals the points'.
+
+    On a HIP device the map runs in the points program (TFRT_PTS_DENSITY: two binary searches and
+    two interpolations per sample over the interp1d knots, uploaded once) when both distributions
+    are ArbitraryDistributions over the same rectangle and grid; otherwise, and on the CPU, it is
+    scipy on the host at every update."""
+
+    _kind = 5     # _lib.PTS_DENSITY
+    _points = _Drawn("points")
 
     def __init__(self, base_point_distribution, sample_count, rank_distribution=None,
                  auto_reroll=True, conserve_etendue=True, etendue_origin=(0, 0), **kwargs):
@@ -1200,13 +1231,84 @@ class ArbitraryBasePoints(BasePointDistributionBase):
             raise ValueError("AribitraryBasePoints: sample_count must be an integer > 0.")
         self._sample_count = int(val)
 
+    # ------------------------------------------------------------------ device program
+    def _device_mode(self):
+        b, r = self.base_point_distribution, self.rank_distribution
+        if not isinstance(b, ArbitraryDistribution):
+            return False
+        if r is not None:
+            # (the host path feeds the rank distribution the base's seeds, and scipy raises outside
+            # its range; the program has one rectangle and one grid for both sets of tables)
+            if not isinstance(r, ArbitraryDistribution) \
+                    or r.evaluation_limits() != b.evaluation_limits() \
+                    or (r._x_count, r._y_count) != (b._x_count, b._y_count):
+                return False
+        return super()._device_mode()
+
+    def _sample_total(self):
+        return self._sample_count
+
+    def _program_parameters(self):
+        return self.base_point_distribution.evaluation_limits()
+
+    def _program_key(self):
+        return (id(self.base_point_distribution), id(self.rank_distribution),
+                float(self.rank_scale_factor))
+
+    def _program_fill(self, pg):
+        b, r = self.base_point_distribution, self.rank_distribution
+        dev = self._epoch_dev.device
+        # (uploaded once per distribution and device; kept alive with the program)
+        memo = self.__dict__.setdefault("_density_tables", {})
+
+        def table(d):
+            hit = memo.get((id(d), str(dev)))
+            if hit is None:
+                hit = memo[(id(d), str(dev))] = (d, torch.from_numpy(d.packed_tables()).to(dev))
+            return hit[1]
+
+        tables = [table(b), None if r is None else table(r)]
+        pg.x_count, pg.y_count = int(b._x_count), int(b._y_count)
+        pg.density = tables[0].data_ptr()
+        pg.rank_density = None if r is None else tables[1].data_ptr()
+        pg.rank_scale = float(self.rank_scale_factor)
+        return tables
+
+    @property
+    def ranks(self):
+        if self.__dict__.get("_device_active"):
+            if self.rank_distribution is None:
+                return None
+            return torch.stack([self._draw("aux0"), self._draw("aux1")], dim=1)
+        return self._ranks
+
     def reroll(self):
+        if self.__dict__.get("_device_active"):
+            # the next draw: the counter is stepped when somebody draws (_DeviceDrawn)
+            self._epoch_pending = self.__dict__.get("_epoch_pending", 0) + 1
+            self.epoch = self.__dict__.get("epoch", 0) + 1
+            self._drawn = {}
+            return
         d = self.base_point_distribution
         self._base_x = _uniform(self._sample_count, d._x_min, d._x_max).cpu().numpy()
         self._base_y = _uniform(self._sample_count, d._y_min, d._y_max).cpu().numpy()
 
     def _update(self):
-        if self.auto_reroll or self._ranks is None:
+        if self._device_mode():
+            # (auto_reroll off: the first update draws, later ones keep the draw until reroll())
+            hold = not self.auto_reroll and self.__dict__.get("_device_active")
+            pending, epoch = self.__dict__.get("_epoch_pending", 0), self.__dict__.get("epoch", 0)
+            drawn = self.__dict__.get("_drawn")
+            active = self.__dict__.get("_active_transformations")
+            self._device_update()
+            if hold:
+                self._epoch_pending, self.epoch = pending, epoch
+                if active == self._active_transformations:
+                    self._drawn = drawn
+            return
+        was_device = self.__dict__.get("_device_active")
+        self._leave_device_mode()
+        if self.auto_reroll or self._ranks is None or was_device or "_base_x" not in self.__dict__:
             self.reroll()
         self._points = _f64(np.stack(self.base_point_distribution(self._base_x, self._base_y), 1))
         if self.rank_distribution is not None:
@@ -1216,6 +1318,17 @@ class ArbitraryBasePoints(BasePointDistributionBase):
             self._ranks = None
 
     def enforce_etendue(self, origin=(0, 0)):
+        if self.__dict__.get("_device_active"):
+            # (one read-back, at construction; the factor is part of the program from here on)
+            ranks_now = self.ranks
+            if ranks_now is not None:
+                o = _f64(origin)
+                pts = self.points[:, -2:]
+                base = torch.linalg.norm(pts - o, dim=1).mean()
+                ranks = torch.linalg.norm(ranks_now - o, dim=1).mean()
+                self.rank_scale_factor = float(base / ranks) * float(self.rank_scale_factor)
+                self._drawn = {}
+            return
         if self._ranks is not None:
             o = _f64(origin)
             base = torch.linalg.norm(self._points - o, dim=1).mean()

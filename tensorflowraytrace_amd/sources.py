@@ -471,6 +471,10 @@ class SourceBase(_DeviceMade, RecursivelyUpdatable, ABC):
         if spec is None:
             return None
         kind, a, b, extra = spec
+        # (a density distribution that stays on the host is a table of its points, as it was
+        # before it had a program)
+        a, b = (d.points if isinstance(d, dist.ArbitraryBasePoints)
+                and not d.__dict__.get("_device_active") else d for d in (a, b))
         if any(isinstance(d, torch.Tensor) and d.requires_grad for d in (a, b)):
             return None
         random = dist._DeviceRandom if dim == 3 else dist._DeviceRandom1D
@@ -597,6 +601,19 @@ class SourceBase(_DeviceMade, RecursivelyUpdatable, ABC):
             d.flush_epoch()
             return ops.points_generate(d.program(), n, first=first, index=index, columns=cols,
                                        device=self._dev_device)[0]
+        if len(items) == 3 and items[2] == "ranks" and isinstance(items[1], dist.ArbitraryBasePoints) \
+                and items[1].__dict__.get("_device_active") and items[1]._sample_total() == self._dev_n \
+                and items[1].rank_distribution is not None:
+            # the ranks of a density distribution (the goal of an illumination design): made in the
+            # asked order by the program, not gathered from a natural-order tensor
+            d = items[1]
+            if index is None and first == 0 and n == self._dev_n:
+                return d.ranks
+            d.flush_epoch()
+            _, a0, a1 = ops.points_generate(d.program(), n, first=first, index=index,
+                                            want_points=False, want_aux=True,
+                                            device=self._dev_device)
+            return torch.stack([a0, a1], dim=1)
         if len(items) == 3 and isinstance(items[1], dist._DeviceRandom1D) \
                 and items[1].__dict__.get("_device_active") and items[1]._sample_total() == self._dev_n \
                 and items[2] in ("ranks", "angles" if items[1]._kind <= 2 else "points"):

@@ -11,13 +11,16 @@ mesh_parametrization_tools, smoother from mesh_smoothing_tool, a phase schedule 
 per-step work (trace, error gradient) runs in the HIP kernels and the loop is driven by
 SGD_Optimizer.training_routine instead of a hand-written tf.GradientTape loop.  No GUI.
 
-    python examples/hexalens.py [--rays 20000] [--steps 30] [--edge 0.12] [--momentum]
+    python examples/hexalens.py [--rays 20000] [--steps 30] [--edge 0.12] [--momentum | --adam]
 
 ``--momentum`` runs the reference's own schedule (dev/hexalens.py:244-300): Nesterov SGD with
 the momentum raised phase by phase, 0.6 -> 0.9 -> 0.95 -> 0.98, the phases' lengths and learning
 rates in the reference's proportions, accumulator in the first phase, smoother in the first two.
 The reference ran 225 such steps; in a run of a few dozen the error falls fastest in the first two
 phases and then oscillates under momentum 0.95 and 0.98 (the rays are re-drawn every step).
+``--adam`` runs the plain schedule with an ``Adam_Optimizer`` (the Keras Adam rule on the processed
+gradients, adam_learning_rate 3e-4: a vertex moves by about that much per step wherever it sits, in
+the centre or at the rim) on the same fused, graph-replayed step.
 """
 import argparse
 import os
@@ -147,7 +150,7 @@ def momentum_routine(steps, lr_scale, accumulator, smoother):
 
 
 def run(ray_count=20000, steps=30, lens_res_scale=0.12, verbose=True, history_file=None,
-        resume_from=None, generic_step=False, momentum=False):
+        resume_from=None, generic_step=False, momentum=False, adam=False):
     s = build(ray_count, lens_res_scale, generic_step=generic_step)
     parameter_history = []
     if resume_from:
@@ -159,6 +162,10 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, verbose=True, history_fi
         opt = optimizer.SGD_Optimizer(s["engine"], s["lens"].parameters, s["error_function"], 3,
                                       learning_rate=(1 - 0.6) * learning_rate, grad_clip=0.1,
                                       apply_momentum=True, nesterov=True)
+    elif adam:
+        opt = optimizer.Adam_Optimizer(s["engine"], s["lens"].parameters, s["error_function"], 3,
+                                       learning_rate=learning_rate, grad_clip=1.0,
+                                       adam_learning_rate=3e-4)
     else:
         opt = optimizer.SGD_Optimizer(s["engine"], s["lens"].parameters, s["error_function"], 3,
                                       learning_rate=learning_rate, grad_clip=1.0)
@@ -207,9 +214,11 @@ if __name__ == "__main__":
                     help="error function as torch code (the reference's form) instead of a GoalError")
     ap.add_argument("--momentum", action="store_true",
                     help="the reference's Nesterov-momentum phase schedule (0.6 -> 0.98)")
+    ap.add_argument("--adam", action="store_true",
+                    help="the Keras Adam rule (Adam_Optimizer) instead of SGD")
     a = ap.parse_args()
     errs, state = run(a.rays, a.steps, a.edge, history_file=a.history, resume_from=a.resume,
-                      generic_step=a.generic_step, momentum=a.momentum)
+                      generic_step=a.generic_step, momentum=a.momentum, adam=a.adam)
     if a.stl_dir:
         save_meshes(state["lens"], a.stl_dir)
     print(f"mean squared image error: first {errs[0]:.6g} -> last {errs[-1]:.6g}")

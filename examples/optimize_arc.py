@@ -9,7 +9,8 @@ The reference's error is a GoalError (goal: y_end = 0), so on the GPU SGD_Optimi
 2-D step -- update, tfrt_trace2d_forward, tfrt_trace2d_backward_goal, parameter update -- captured
 in one HIP graph after a few eager steps.  The reference's optimiser is Keras SGD with learning
 rate 1, Nesterov momentum 0.8 and the gradient clipped to 0.1; ``--momentum`` runs that rule
-(without it: plain SGD).  ``--rowwise`` states the same error as
+(without it: plain SGD); ``--adam`` runs an ``Adam_Optimizer`` instead (the Keras Adam rule,
+adam_learning_rate 0.05, on the same clipped gradient and the same fused step).  ``--rowwise`` states the same error as
 ``RowwiseError(lambda r: r["y_end"] ** 2)``, any element-wise torch function's form: the fused step
 then evaluates it on fixed-shape columns (tfrt_trace2d_rows, tfrt_trace2d_backward_rows) inside
 the same graph.  ``--generic`` forces the generic path (user error function, autograd) for
@@ -31,7 +32,7 @@ line: ms_per_step, graph_replays and whether the step was replayed from a graph,
 the error of the first and the last step.
 No GUI.
 
-    python examples/optimize_arc.py [--rays 10] [--steps 30] [--momentum] [--rowwise] [--generic]
+    python examples/optimize_arc.py [--rays 10] [--steps 30] [--momentum | --adam] [--rowwise] [--generic]
                                     [--deterministic] [--random-source [--warmup 5]]
                                     [--pool-source [--host] [--pool-rays 16384] [--sigma 1e-3]]
 """
@@ -144,13 +145,17 @@ def build(ray_count=10, ray_dtype=torch.float64, device="cuda:0", deterministic=
     return dict(parameter=parameter, arc=arc, system=system, engine=trace_engine, source=source)
 
 
-def make_optimizer(scene, momentum=False, generic=False, rowwise=False):
+def make_optimizer(scene, momentum=False, generic=False, rowwise=False, adam=False):
     if rowwise:
         erf = optimizer.RowwiseError(lambda r: r["y_end"] ** 2)
     else:
         n = scene["system"].sources["x_start"].shape[0]
         goal = torch.zeros(n, dtype=torch.float64, device=scene["parameter"].device)
         erf = optimizer.GoalError(("y_end",), goal)
+    if adam:
+        return optimizer.Adam_Optimizer(scene["engine"], [scene["parameter"]], erf, 2,
+                                        learning_rate=1.0, grad_clip=0.1, adam_learning_rate=0.05,
+                                        fused=not generic)
     # Keras SGD(learning_rate=1.0, momentum=0.8, nesterov=True) of the reference, gradient clipped
     # to 0.1 before it is applied
     return optimizer.SGD_Optimizer(scene["engine"], [scene["parameter"]], erf, 2,
@@ -159,11 +164,11 @@ def make_optimizer(scene, momentum=False, generic=False, rowwise=False):
 
 
 def run(ray_count=10, steps=30, momentum=False, generic=False, verbose=True, rowwise=False,
-        deterministic=False, random_source=False, warmup=0):
+        deterministic=False, random_source=False, warmup=0, adam=False):
     """``warmup`` > 0: that many untimed steps first; the mean time of the ``steps`` after them (device
     events around the loop, no host read inside it) is returned as ``ms_per_step``."""
     scene = build(ray_count, deterministic=deterministic, random_source=random_source)
-    opt = make_optimizer(scene, momentum, generic, rowwise)
+    opt = make_optimizer(scene, momentum, generic, rowwise, adam)
     errors = []
     if warmup > 0:
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -228,6 +233,8 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--momentum", action="store_true",
                     help="the reference's Nesterov momentum 0.8")
+    ap.add_argument("--adam", action="store_true",
+                    help="the Keras Adam rule (Adam_Optimizer) instead of SGD")
     ap.add_argument("--rowwise", action="store_true",
                     help="the same error as a RowwiseError (any element-wise error function)")
     ap.add_argument("--generic", action="store_true",
@@ -253,7 +260,8 @@ def main():
         return
     errors, s = run(a.rays, a.steps, a.momentum, a.generic, rowwise=a.rowwise,
                     deterministic=a.deterministic, random_source=a.random_source,
-                    warmup=max(a.warmup, 1) if a.random_source else 0, verbose=not a.random_source)
+                    warmup=max(a.warmup, 1) if a.random_source else 0, verbose=not a.random_source,
+                    adam=a.adam)
     fs = s["optimizer"]._fused_step
     path = ("generic" if fs is None else
             f"fused, {fs.graph_replays} of {fs.steps} steps replayed from a HIP graph")

@@ -220,6 +220,45 @@ int tfrt_sgd_momentum_multi_finish(int32_t n_tensors, const void* const* grad,
                                    void* const* velocity, const int64_t* n, const double* hyper,
                                    const tfrt_goal_pending* pending, void* stream);
 
+/* tfrt_sgd_process_multi with the Keras Adam rule (non-amsgrad; the reference hands its processed
+ * gradients to a Keras optimiser object, and Adam is the one its users reach for next).  `hyper`
+ * holds {scale, clip, adam_learning_rate, beta1, beta2, epsilon} per tensor, 6 * n_tensors float64
+ * on the device; m[k] and v[k] are persistent float64 buffers of n[k] elements per tensor (zero
+ * before the first step); `state` holds {t, p1, p2} per tensor, 3 * n_tensors float64 on the
+ * device, {0, 1, 1} before the first step.  One launch is one step of every tensor in it:
+ *     t  = t + 1;   p1 = p1 * beta1;   p2 = p2 * beta2      (running products, not pow(): exact
+ *                                                            IEEE products, reproducible anywhere)
+ *     lr_t = adam_learning_rate * sqrt(1 - p2) / (1 - p1)
+ * and per element, with g the gradient after the processing above (non-finite -> 0, scale, clip),
+ *     m[i] = beta1 * m[i] + (1 - beta1) * g
+ *     v[i] = beta2 * v[i] + (1 - beta2) * (g * g)
+ *     param[i] -= lr_t * m[i] / (sqrt(v[i]) + epsilon)
+ * every product, sum, difference, quotient and square root rounded on its own (no fused
+ * multiply-add; float64 sqrt and / are correctly rounded), (1 - beta) computed on the device, the
+ * expressions evaluated left to right as written.
+ *
+ * The step state: the launch reads {p1, p2} and advances {t, p1, p2} itself, so a captured graph
+ * counts its replays and every hyper value may change between them.  In each workgroup one thread
+ * reads its tensor's state before the workgroup touches an element and, once the workgroup's work is
+ * issued, adds 1 to `*ticket` (acquire-release, device scope).  The workgroup that draws the last
+ * ticket -- every other one has read the state by then -- writes the advanced state of all
+ * n_tensors tensors (tensors with n[k] == 0 included) and stores 0 to the ticket.  No workgroup can
+ * see the advanced value and nothing depends on the order workgroups run in.  `ticket` is one
+ * uint32 on the device, 0 before the first launch and left 0 by every launch; launches that may
+ * run concurrently (different streams) need a ticket each.
+ *
+ * `processed` and its entries may be NULL; `param`, `m`, `v` and their entries (for n[k] > 0),
+ * `state` and `ticket` may not.  `processed` may alias `grad`; m and v alias nothing else. */
+int tfrt_adam_multi(int32_t n_tensors, const void* const* grad, void* const* processed,
+                    void* const* param, void* const* m, void* const* v, const int64_t* n,
+                    const double* hyper, double* state, uint32_t* ticket, void* stream);
+
+/* ... and finishes a pending error sum in one more workgroup of the same launch. */
+int tfrt_adam_multi_finish(int32_t n_tensors, const void* const* grad, void* const* processed,
+                           void* const* param, void* const* m, void* const* v, const int64_t* n,
+                           const double* hyper, double* state, uint32_t* ticket,
+                           const tfrt_goal_pending* pending, void* stream);
+
 /* y = A x, A in CSR form (int64 indices, f64 values): the accumulator (optimizer.py:250-255)
  * and smoother (optimizer.py:277-282) products for the sparse matrices the mesh tools
  * produce (mesh_tools.py:221-421).  x and y must not alias. */

@@ -4,6 +4,7 @@
 //                 Keras-SGD apply `param -= sgd_lr * processed` in the same launch: the host
 //                 path of the reference is six eager ops per parameter per step.
 // k_sgd_momentum_multi : the same with the Keras momentum / Nesterov rule and a velocity buffer.
+// k_adam_multi  : the same with the Keras Adam rule, its m / v buffers and a device step state.
 // k_csr_matvec  : y = A x for a CSR matrix: the accumulator / smoother products
 //                 (optimizer.py:250-255, 277-282).  The matrices the mesh tools build
 //                 (mesh_tools.py:221-421) have a handful of non-zeros per row, a dense (P,P)
@@ -117,6 +118,83 @@ __global__ __launch_bounds__(BLOCK) void k_sgd_momentum_multi(SgdMomentumBatch b
   const double v = m * b.velocity[k][i] - sgd_lr * g;
   b.velocity[k][i] = v;
   p[i] = nesterov ? p[i] + (m * v - sgd_lr * g) : p[i] + v;
+}
+
+// The Keras Adam rule (non-amsgrad) after the same processing: persistent m and v per parameter
+// element, {scale, clip, adam_learning_rate, beta1, beta2, epsilon} per tensor (6 float64) and the
+// running state {t, p1, p2} per tensor (p1 = beta1^t, p2 = beta2^t as running products: IEEE
+// exact, unlike the device pow).  With the state of THIS step, t+1, p1*beta1, p2*beta2:
+//   lr_t = lr * sqrt(1 - p2) / (1 - p1)
+//   m = beta1*m + (1 - beta1)*g;   v = beta2*v + (1 - beta2)*(g*g);   p -= lr_t*m / (sqrt(v) + eps)
+// every operation rounded on its own.
+//
+// The state lives on the device (a replayed graph must count its steps) and this launch both
+// reads and advances it.  In a workgroup only thread 0 reads its tensor's state, before any
+// element is touched, and hands lr_t to the others through LDS; when the workgroup's work is
+// issued the same thread takes a ticket (an acquire-release add, device scope).  Whoever draws the
+// last ticket knows that every other workgroup's read is complete, writes {t+1, p1*beta1,
+// p2*beta2} of every tensor and puts the ticket back to 0 for the next launch.  Nothing depends on
+// the order in which workgroups run, and no workgroup ever sees the advanced value.
+struct AdamBatch {
+  const double* grad[SGD_BATCH];
+  double* processed[SGD_BATCH];
+  double* param[SGD_BATCH];
+  double* m[SGD_BATCH];
+  double* v[SGD_BATCH];
+  int64_t n[SGD_BATCH];
+  int32_t first_block[SGD_BATCH + 1];
+  int32_t count;
+  int32_t finish;  // the workgroup after the tensors' finishes `goal` (else it only takes a ticket)
+};
+
+__global__ __launch_bounds__(BLOCK) void k_adam_multi(AdamBatch b,
+                                                      const double* __restrict__ hyper,
+                                                      double* state, unsigned int* ticket,
+                                                      tfrt_goal_pending goal) {
+#pragma clang fp contract(off)
+  __shared__ double lr_shared;
+  if ((int)blockIdx.x >= b.first_block[SGD_BATCH]) {
+    if (b.finish) goal_finish_block(goal);
+  } else {
+    int k = 0;
+    while (k + 1 < b.count && (int)blockIdx.x >= b.first_block[k + 1]) ++k;  // block-uniform
+    const double* h = hyper + 6 * k;
+    if (threadIdx.x == 0) {
+      const double p1 = state[3 * k + 1] * h[3], p2 = state[3 * k + 2] * h[4];
+      lr_shared = h[2] * sqrt(1.0 - p2) / (1.0 - p1);
+    }
+    __syncthreads();
+    const int64_t i = (int64_t)((int)blockIdx.x - b.first_block[k]) * BLOCK + threadIdx.x;
+    if (i < b.n[k]) {
+      const double scale = h[0], clip = h[1], beta1 = h[3], beta2 = h[4], eps = h[5];
+      const double lr_t = lr_shared;
+      double g = b.grad[k][i];
+      g = isfinite(g) ? g : 0.0;
+      g = g * scale;
+      g = g < -clip ? -clip : (g > clip ? clip : g);
+      if (b.processed[k] != nullptr) b.processed[k][i] = g;
+      const double m = beta1 * b.m[k][i] + (1.0 - beta1) * g;
+      const double v = beta2 * b.v[k][i] + (1.0 - beta2) * (g * g);
+      b.m[k][i] = m;
+      b.v[k][i] = v;
+      double* p = b.param[k];
+      p[i] = p[i] - lr_t * m / (sqrt(v) + eps);
+    }
+  }
+  if (threadIdx.x != 0) return;
+  // (release: this thread's read of the state is complete before the add is visible; acquire:
+  // the writer's stores come after every other workgroup's add)
+  const unsigned int t =
+      __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+  if (t != gridDim.x - 1) return;
+  for (int k = 0; k < b.count; ++k) {
+    double* s = state + 3 * k;
+    const double t1 = s[0] + 1.0, p1 = s[1] * hyper[6 * k + 3], p2 = s[2] * hyper[6 * k + 4];
+    s[0] = t1;
+    s[1] = p1;
+    s[2] = p2;
+  }
+  __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // one wave per row; lanes stride over the row's non-zeros, butterfly-sum at the end
@@ -268,6 +346,59 @@ int tfrt_sgd_momentum_multi_finish(int32_t n_tensors, const void* const* grad,
   if (!pending) return TFRT_E_BADARG;
   return sgd_momentum_launch(n_tensors, grad, processed, param, velocity, n, hyper, pending,
                              stream);
+}
+
+static int adam_launch(int32_t n_tensors, const void* const* grad, void* const* processed,
+                       void* const* param, void* const* m, void* const* v, const int64_t* n,
+                       const double* hyper, double* state, uint32_t* ticket,
+                       const tfrt_goal_pending* pending, void* stream) {
+  if (n_tensors < 0 || n_tensors > SGD_BATCH ||
+      (n_tensors > 0 && (!grad || !param || !m || !v || !n || !hyper || !state || !ticket)))
+    return TFRT_E_BADARG;
+  if (pending != nullptr &&
+      (!pending->partial || (!pending->n_finished && !pending->partial_counts) ||
+       !pending->error_out || pending->n_partial < 0))
+    return TFRT_E_BADARG;
+  AdamBatch b;
+  int blocks = 0;
+  for (int k = 0; k < SGD_BATCH; ++k) {
+    const bool on = k < n_tensors;
+    if (on && (n[k] < 0 || (n[k] > 0 && (!grad[k] || !param[k] || !m[k] || !v[k]))))
+      return TFRT_E_BADARG;
+    b.grad[k] = on ? static_cast<const double*>(grad[k]) : nullptr;
+    b.processed[k] = (on && processed) ? static_cast<double*>(processed[k]) : nullptr;
+    b.param[k] = on ? static_cast<double*>(param[k]) : nullptr;
+    b.m[k] = on ? static_cast<double*>(m[k]) : nullptr;
+    b.v[k] = on ? static_cast<double*>(v[k]) : nullptr;
+    b.n[k] = on ? n[k] : 0;
+    b.first_block[k] = blocks;
+    if (on) blocks += cdiv(n[k], BLOCK);
+  }
+  b.first_block[SGD_BATCH] = blocks;
+  b.count = n_tensors;
+  b.finish = pending != nullptr ? 1 : 0;
+  // (tensors without elements still count the step: one workgroup that only takes the ticket)
+  const int grid = blocks + ((pending != nullptr || (blocks == 0 && n_tensors > 0)) ? 1 : 0);
+  if (grid == 0) return 0;
+  hipLaunchKernelGGL(k_adam_multi, dim3(grid), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), b,
+                     hyper, state, ticket, pending != nullptr ? *pending : tfrt_goal_pending{});
+  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+}
+
+int tfrt_adam_multi(int32_t n_tensors, const void* const* grad, void* const* processed,
+                    void* const* param, void* const* m, void* const* v, const int64_t* n,
+                    const double* hyper, double* state, uint32_t* ticket, void* stream) {
+  return adam_launch(n_tensors, grad, processed, param, m, v, n, hyper, state, ticket, nullptr,
+                     stream);
+}
+
+int tfrt_adam_multi_finish(int32_t n_tensors, const void* const* grad, void* const* processed,
+                           void* const* param, void* const* m, void* const* v, const int64_t* n,
+                           const double* hyper, double* state, uint32_t* ticket,
+                           const tfrt_goal_pending* pending, void* stream) {
+  if (!pending) return TFRT_E_BADARG;
+  return adam_launch(n_tensors, grad, processed, param, m, v, n, hyper, state, ticket, pending,
+                     stream);
 }
 
 int tfrt_csr_matvec(const int64_t* crow_indices, const int64_t* col_indices, const double* values,

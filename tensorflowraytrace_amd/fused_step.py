@@ -24,7 +24,8 @@ states that form declaratively; an optimiser given a ``GoalError`` runs ``FusedS
     autograd through update()           -> d error / d parameters           (tfrt_param_faces_backward ...)
     [one all-reduce over ray shards]
     tfrt_sgd_process_dev / tfrt_csr_matvec   non-finite -> 0, scale, clip, accumulate, SGD apply
-                                        (tfrt_sgd_momentum_multi with apply_momentum=True)
+                                        (tfrt_sgd_momentum_multi with apply_momentum=True,
+                                        tfrt_adam_multi for an Adam_Optimizer)
 
 A 2-D engine (one process, no ray shards) runs ``FusedStep._goal2d`` instead of ``_goal3d``:
 ``tfrt_trace2d_forward``, then ``tfrt_trace2d_backward_goal`` -- error, seed and the reverse sweep of
@@ -199,8 +200,9 @@ class _RowFields:
 
 class _HyperTable:
     """(n_parameters, 3) float64 {scale, clip, sgd_learning_rate} on the device -- (n_parameters, 5)
-    with {momentum, nesterov} appended for the momentum rule -- refreshed through a ring of pinned
-    host buffers only when a value changes."""
+    with {momentum, nesterov} appended for the momentum rule, (n_parameters, 6) {scale, clip,
+    adam_learning_rate, beta1, beta2, epsilon} for the Adam rule -- refreshed through a ring of
+    pinned host buffers only when a value changes."""
 
     def __init__(self, n, device, slots=8, width=3):
         self.width = width
@@ -951,14 +953,18 @@ class FusedStep:
         """non-finite -> 0, scale, clip, accumulate, SGD apply (optimizer.py:223-257, 316) with
         the step-dependent scalars read from the device table: rows of {scale, clip,
         sgd_learning_rate}, with {momentum, nesterov} appended for the momentum rule
-        (tfrt_sgd_momentum_multi, the optimizer's velocity buffers)."""
+        (tfrt_sgd_momentum_multi, the optimizer's velocity buffers), or {scale, clip,
+        adam_learning_rate, beta1, beta2, epsilon} for the Adam rule (tfrt_adam_multi, the
+        optimizer's m / v buffers and its step state, which the launch advances)."""
         opt = self.opt
         L = _lib.lib()
         k = len(grads)
-        momentum = bool(opt.apply_momentum)
+        rule = opt.update_rule
+        momentum, adam = rule == "momentum", rule == "adam"
         # (the plain rule takes one launch for all parameter tensors from two of them on, the
-        # momentum rule from one on)
-        batched = (k > (0 if momentum else 1) and k <= 8 and all(a is None for a in accumulators)
+        # momentum and Adam rules from one on)
+        batched = (k > (0 if momentum or adam else 1) and k <= 8
+                   and all(a is None for a in accumulators)
                    and len({ops._stream(p).value for p in opt.parameters}) == 1)
         pending, self._goal_pending = self._goal_pending, None
 
@@ -970,12 +976,17 @@ class FusedStep:
                 # every parameter tensor in one launch (the device table holds the scalars of
                 # parameter i in row i), which also finishes the error sum left on its stream
                 stream = ops._stream(opt.parameters[0])
-                name = "tfrt_sgd_momentum_multi" if momentum else "tfrt_sgd_process_multi"
+                name = {"sgd": "tfrt_sgd_process_multi", "momentum": "tfrt_sgd_momentum_multi",
+                        "adam": "tfrt_adam_multi"}[rule]
                 args = [k, arr([g.data_ptr() for g in grads]), None,
                         arr([p.data_ptr() for p in opt.parameters]),
                         arr([g.numel() for g in grads], ctypes.c_int64), ctypes.c_void_p(hyper)]
                 if momentum:
                     args.insert(4, arr([v.data_ptr() for v in opt._velocity]))
+                if adam:
+                    args[4:4] = [arr([m.data_ptr() for m in opt._adam_m]),
+                                 arr([v.data_ptr() for v in opt._adam_v])]
+                    args += [ops._p(opt._adam_state), ops._p(opt._adam_ticket)]
                 if pending is not None and pending[1].value == stream.value:
                     check(getattr(L, name + "_finish")(*args, ctypes.byref(pending[0]), stream),
                           name + "_finish")
@@ -1002,6 +1013,16 @@ class FusedStep:
                         1, arr([g.data_ptr()]), None, arr([p.data_ptr()]),
                         arr([opt._velocity[i].data_ptr()]), arr([g.numel()], ctypes.c_int64), row,
                         stream), "tfrt_sgd_momentum_multi")
+                elif adam:
+                    # (row i of the state and a ticket of its own: parameters may sit on
+                    # different streams)
+                    check(L.tfrt_adam_multi(
+                        1, arr([g.data_ptr()]), None, arr([p.data_ptr()]),
+                        arr([opt._adam_m[i].data_ptr()]), arr([opt._adam_v[i].data_ptr()]),
+                        arr([g.numel()], ctypes.c_int64), row,
+                        ctypes.c_void_p(opt._adam_state.data_ptr() + 24 * i),
+                        ctypes.c_void_p(opt._adam_ticket.data_ptr() + 4 * i), stream),
+                        "tfrt_adam_multi")
                 else:
                     check(L.tfrt_sgd_process_dev(ops._p(g), None, ops._p(p), g.numel(), _lib.F64,
                                                  row, stream), "tfrt_sgd_process_dev")
@@ -1070,14 +1091,19 @@ class FusedStep:
         opt = self.opt
         rows, apply_rows = [], []
         # (momentum rule: the phase's momentum rides in the table, so a phase change replays)
-        extra = ((float(opt.momentum), 1.0 if opt.nesterov else 0.0) if opt.apply_momentum
-                 else ())
+        rule = opt.update_rule
+        if rule == "adam":          # (the Adam values ride there too: reassigning them replays)
+            tail = opt._adam_tail()
+        else:
+            tail = (float(opt.sgd_learning_rate),)
+            if rule == "momentum":
+                tail += (float(opt.momentum), 1.0 if opt.nesterov else 0.0)
         for i in range(len(opt.parameters)):
             scale = float(lr_scale * opt.individual_lr[i] * opt.learning_rate)
             clip = float(opt.grad_clip if opt.clip_mode == "common" else
                          opt.individual_lr[i] * opt.clip_scale * opt.learning_rate * lr_scale)
-            rows.append((scale, clip, float(opt.sgd_learning_rate)) + extra)
-            apply_rows.append((1.0, float("inf"), float(opt.sgd_learning_rate)) + extra)
+            rows.append((scale, clip) + tail)
+            apply_rows.append((1.0, float("inf")) + tail)
         return tuple(rows), tuple(apply_rows)
 
     def _signature(self, accumulators):
@@ -1096,9 +1122,17 @@ class FusedStep:
                 tdist.world_size(), eng.optical_system.scene_signature(), bool(eng.deterministic),
                 id((getattr(eng, "_order_cache", None) or (None, None, None))[2]),
                 getattr(eng, "_visit_all_key", None) is not None, eng.in_place,
-                bool(opt.apply_momentum),
-                tuple(v.data_ptr() for v in opt._velocity) if opt.apply_momentum else (),
-                self._index_signature())
+                opt.update_rule == "momentum",
+                tuple(v.data_ptr() for v in opt._velocity) if opt.update_rule == "momentum" else (),
+                self._index_signature()) + self._rule_signature()
+
+    def _rule_signature(self):
+        """The Adam rule's part of the signature: the rule and the addresses of its state."""
+        opt = self.opt
+        if opt.update_rule != "adam":
+            return ()
+        return ("adam", tuple(t.data_ptr() for t in opt._adam_m + opt._adam_v),
+                opt._adam_state.data_ptr(), opt._adam_ticket.data_ptr())
 
     def _index_signature(self):
         """The refractive-index fields that take a gradient (boundary, field, identity of a tensor
@@ -1122,14 +1156,16 @@ class FusedStep:
         opt = self.opt
         dev = opt.parameters[0].device
         world = 2 if tdist.is_distributed() else 1      # > 1: the collective splits the sequence
-        width = 5 if opt.apply_momentum else 3
+        width = {"sgd": 3, "momentum": 5, "adam": 6}[opt.update_rule]
         if self._hyper is None or self._hyper.width != width:
             # (a captured graph reads the table it was captured with: a new one invalidates it)
             self._graphs = None
             self._hyper = _HyperTable(len(opt.parameters), dev, width=width)
             self._hyper_apply = _HyperTable(len(opt.parameters), dev, width=width)
-        if opt.apply_momentum:
+        if opt.update_rule == "momentum":
             opt._velocities()        # allocated before the first capture, updated in place after
+        elif opt.update_rule == "adam":
+            opt._adam_buffers()
         rows, apply_rows = self._hyper_rows(lr_scale)
         self._hyper.set(rows)
         self._hyper_apply.set(apply_rows)

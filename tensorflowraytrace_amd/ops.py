@@ -517,6 +517,42 @@ def sgd_momentum(grads, params, velocities, rows, processed=None):
             ctypes.c_void_p(hyper.data_ptr() + 40 * lo), stream), "tfrt_sgd_momentum_multi")
 
 
+def adam(grads, params, ms, vs, rows, state, ticket, processed=None):
+    """optimizer.py:223-247 and the Keras Adam apply for float64 tensors, up to eight per launch
+    (tfrt_adam_multi): ``rows[k] = (scale, clip, adam_learning_rate, beta1, beta2, epsilon)``,
+    ``state`` the (k, 3) float64 {t, p1, p2} of these tensors and ``ticket`` one zeroed int32, both
+    on the device.  Updates ``params``, ``ms``, ``vs`` and ``state`` in place; writes the processed
+    gradients into ``processed`` if given."""
+    k = len(grads)
+    if not (k == len(params) == len(ms) == len(vs) == len(rows)) or \
+            (processed is not None and len(processed) != k):
+        raise TfrtError("adam: one gradient, parameter, m, v and row per tensor")
+    if k == 0:
+        return
+    _need_gpu(*grads, *params, *ms, *vs, state, ticket)
+    for i, (g, p, m, v) in enumerate(zip(grads, params, ms, vs)):
+        outs = (g, p, m, v) if processed is None else (g, p, m, v, processed[i])
+        if any(t.dtype != torch.float64 or not t.is_contiguous() or t.shape != g.shape
+               for t in outs):
+            raise TfrtError("adam: contiguous float64 tensors of one shape per parameter")
+    if (state.dtype != torch.float64 or tuple(state.shape) != (k, 3) or not state.is_contiguous()
+            or ticket.dtype != torch.int32 or ticket.numel() < 1):
+        raise TfrtError("adam: state is (n_tensors, 3) float64, ticket one int32")
+    hyper = torch.tensor(rows, dtype=torch.float64).to(grads[0].device)
+    L = _lib.lib()
+    stream = _stream(params[0])
+    for lo in range(0, k, 8):
+        hi = min(lo + 8, k)
+
+        def ptrs(ts):
+            return (ctypes.c_void_p * (hi - lo))(*[t.data_ptr() for t in ts[lo:hi]])
+        check(L.tfrt_adam_multi(
+            hi - lo, ptrs(grads), None if processed is None else ptrs(processed), ptrs(params),
+            ptrs(ms), ptrs(vs), (ctypes.c_int64 * (hi - lo))(*[g.numel() for g in grads[lo:hi]]),
+            ctypes.c_void_p(hyper.data_ptr() + 48 * lo), ctypes.c_void_p(state.data_ptr() + 24 * lo),
+            _p(ticket), stream), "tfrt_adam_multi")
+
+
 class CsrMatrix:
     """A square accumulator / smoother matrix held in CSR form on the device
     (optimizer.py:250-255, 277-282 multiply dense (P,P) matrices whose rows hold a few

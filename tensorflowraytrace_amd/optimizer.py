@@ -217,6 +217,26 @@ class SGD_Optimizer:
         return (float(scale), float(clip), float(self.sgd_learning_rate), float(self._momentum),
                 1.0 if self.nesterov else 0.0)
 
+    # The update rule, as the fused step and the processing below see it: its name, whether this
+    # step is plain ``p -= lr*g`` (applied inside the processing kernel), its row of the device
+    # table and the launch that processes and applies a batch of tensors in one go.
+    @property
+    def update_rule(self):
+        return "momentum" if self.apply_momentum else "sgd"
+
+    def _plain_sgd(self):
+        return not (self.apply_momentum and self._momentum > 0.0)
+
+    _kernel_row = _momentum_row
+
+    def _kernel_apply(self, idx, grads, rows, processed=None):
+        vel = self._velocities()
+        ops.sgd_momentum(grads, [self.parameters[i] for i in idx], [vel[i] for i in idx], rows,
+                         processed=processed)
+
+    def _enter_phase(self, phase):
+        """training_routine: called with the running phase dict when a phase begins."""
+
     def convert_to_plist(self, data):
         p_count = len(self.parameters)
         if type(data) is list or type(data) is tuple:
@@ -311,8 +331,8 @@ class SGD_Optimizer:
         grads, error_sum, n_terms = self.raw_gradient(*args, **kwargs)
         self.last_error_terms = n_terms
         processed, applied = [], []
-        plain_sgd = not (self.apply_momentum and self._momentum > 0.0)
-        batch = []      # momentum updates processed and applied in one launch after the loop
+        plain_sgd = self._plain_sgd()
+        batch = []      # momentum / Adam updates processed and applied in one launch after the loop
         for i, grad in enumerate(grads):
             scale = lr_scale * self.individual_lr[i] * self.learning_rate
             if self.clip_mode == "common":
@@ -325,7 +345,7 @@ class SGD_Optimizer:
             if (apply and not plain_sgd and accumulators[i] is None
                     and self._momentum_kernel(p, grad)):
                 grad = grad.contiguous()
-                batch.append((i, grad, torch.empty_like(grad), self._momentum_row(scale, clp)))
+                batch.append((i, grad, torch.empty_like(grad), self._kernel_row(scale, clp)))
                 processed.append(batch[-1][2])
                 applied.append(True)
                 continue
@@ -337,11 +357,9 @@ class SGD_Optimizer:
                 grad = self._matrix_product(self._acc_cache, i, accumulators[i], grad)
             processed.append(grad)
         if batch:
-            vel = self._velocities()
             with torch.no_grad():
-                ops.sgd_momentum([b[1] for b in batch], [self.parameters[b[0]] for b in batch],
-                                 [vel[b[0]] for b in batch], [b[3] for b in batch],
-                                 processed=[b[2] for b in batch])
+                self._kernel_apply([b[0] for b in batch], [b[1] for b in batch],
+                                   [b[3] for b in batch], processed=[b[2] for b in batch])
         # (tf.reduce_mean, optimizer.py:257: the mean of no error terms is NaN)
         if isinstance(n_terms, torch.Tensor):
             mean = torch.where(n_terms > 0, error_sum / torch.clamp(n_terms, min=1.0),
@@ -387,8 +405,8 @@ class SGD_Optimizer:
                     p.add_(g, alpha=-lr)
             if batch:
                 row = self._momentum_row(1.0, float("inf"))
-                ops.sgd_momentum([g for _, g in batch], [self.parameters[i] for i, _ in batch],
-                                 [vel[i] for i, _ in batch], [row] * len(batch))
+                self._kernel_apply([i for i, _ in batch], [g for _, g in batch],
+                                   [row] * len(batch))
 
     def single_step(self, accumulators, *args, lr_scale=1.0, momentum=0.0, verbose=False,
                     **kwargs):
@@ -445,6 +463,7 @@ class SGD_Optimizer:
             current_phase += 1
             phase_iterations = 0
             phase.update(new_phase)
+            self._enter_phase(phase)
             phase["accumulators"] = self.convert_to_plist(phase["accumulators"])
             phase["smoothers"] = self.convert_to_plist(phase["smoothers"])
             lrs = self.convert_to_lrlist(phase["learning_rate"], phase["steps"])
@@ -467,3 +486,121 @@ class SGD_Optimizer:
         if show_time and is_rank0:
             print(f"Completed training routine.  Took {total_time} seconds.")
             print(f"Steps took an average of {total_time / max(total_iterations, 1)} seconds per step.")
+
+
+class Adam_Optimizer(SGD_Optimizer):
+    """SGD_Optimizer with the Keras ``Adam`` rule (non-amsgrad) in place of the SGD apply: the
+    gradient processing -- non-finite -> 0, scale, clip, accumulators -- is the same, and so are the
+    constructor, ``single_step``, ``training_routine`` and the fused, graph-replayed step.  Per
+    parameter tensor there is persistent float64 state, ``m`` and ``v`` of the parameter's shape
+    (zero at first) and ``{t, p1, p2}`` (``{0, 1, 1}``); a step on the processed gradient ``g`` is
+
+        t = t + 1;  p1 = p1 * beta1;  p2 = p2 * beta2          (running products, not pow())
+        lr_t = adam_learning_rate * sqrt(1 - p2) / (1 - p1)
+        m = beta1 * m + (1 - beta1) * g
+        v = beta2 * v + (1 - beta2) * (g * g)
+        param -= lr_t * m / (sqrt(v) + epsilon)
+
+    every operation rounded on its own.  ``{t, p1, p2}`` lives on the parameters' device: the update
+    launch (tfrt_adam_multi) reads and advances it, so a replayed graph counts its steps, and the
+    generic path advances the same tensor.  ``adam_learning_rate``, ``beta1``, ``beta2`` and
+    ``epsilon`` are plain attributes: assign them between steps, or give them as keys of a
+    ``training_routine`` phase.  ``sgd_learning_rate``, ``momentum``, ``apply_momentum`` and
+    ``nesterov`` are accepted and ignored."""
+
+    _PHASE_KEYS = ("adam_learning_rate", "beta1", "beta2", "epsilon")
+
+    def __init__(self, *args, adam_learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-7,
+                 **kwargs):
+        super().__init__(*args, **kwargs)
+        self.adam_learning_rate = adam_learning_rate
+        self.beta1 = beta1
+        self.beta2 = beta2
+        self.epsilon = epsilon
+        self._adam_m = [None] * len(self.parameters)
+        self._adam_v = [None] * len(self.parameters)
+        self._adam_state = None     # (n_parameters, 3) {t, p1, p2}
+        self._adam_ticket = None    # one zeroed word per parameter for the update launches
+
+    update_rule = "adam"
+
+    def _plain_sgd(self):
+        return False
+
+    def _adam_buffers(self):
+        """m, v, {t, p1, p2} and the launch tickets: made once per parameter and updated in place
+        from then on (a captured launch graph keeps their addresses)."""
+        for i, p in enumerate(self.parameters):
+            m = self._adam_m[i]
+            if m is None or m.shape != p.shape or m.dtype != p.dtype or m.device != p.device:
+                self._adam_m[i] = torch.zeros(p.shape, dtype=p.dtype, device=p.device)
+                self._adam_v[i] = torch.zeros(p.shape, dtype=p.dtype, device=p.device)
+        dev = self.parameters[0].device
+        if self._adam_state is None or self._adam_state.device != dev:
+            k = len(self.parameters)
+            self._adam_state = torch.zeros((k, 3), dtype=torch.float64, device=dev)
+            self._adam_state[:, 1:] = 1.0
+            self._adam_ticket = torch.zeros(k, dtype=torch.int32, device=dev)
+        return self._adam_m, self._adam_v, self._adam_state
+
+    def reset_state(self):
+        """Back to before the first step -- m = v = 0, {t, p1, p2} = {0, 1, 1} -- in place: the
+        buffers keep their addresses, so a captured graph goes on replaying."""
+        if self._adam_state is None:
+            return
+        with torch.no_grad():
+            for t in self._adam_m + self._adam_v:
+                if t is not None:
+                    t.zero_()
+            self._adam_state[:, 0].zero_()
+            self._adam_state[:, 1:].fill_(1.0)
+
+    def _adam_tail(self):
+        return (float(self.adam_learning_rate), float(self.beta1), float(self.beta2),
+                float(self.epsilon))
+
+    def _kernel_row(self, scale, clip):
+        return (float(scale), float(clip)) + self._adam_tail()
+
+    def _kernel_apply(self, idx, grads, rows, processed=None):
+        m, v, state = self._adam_buffers()
+        if idx == list(range(len(self.parameters))):
+            st, ticket = state, self._adam_ticket
+        else:
+            # (some of the tensors: their rows of the state, advanced, then put back)
+            st, ticket = state[idx].contiguous(), self._adam_ticket
+        ops.adam(grads, [self.parameters[i] for i in idx], [m[i] for i in idx],
+                 [v[i] for i in idx], rows, st, ticket, processed=processed)
+        if st is not state:
+            state[idx] = st
+
+    def apply_gradients(self, grads, skip=None):
+        m_all, v_all, state = self._adam_buffers()
+        lr, b1, b2, eps = self._adam_tail()
+        batch = []      # (device float64: one tfrt_adam_multi launch, rows {1, inf, ...})
+        with torch.no_grad():
+            for i, (g, p) in enumerate(zip(grads, self.parameters)):
+                if skip is not None and skip[i]:
+                    continue  # already applied by the batched launch of the processing
+                if self._momentum_kernel(p, g):
+                    batch.append((i, g.contiguous()))
+                    continue
+                # the same arithmetic as eager ops, one rounding each (no addcmul / addcdiv, and
+                # no add_(alpha=...): those may fuse the product into the sum)
+                st, m, v = state[i], m_all[i], v_all[i]
+                st[0] += 1.0
+                st[1] *= b1
+                st[2] *= b2
+                lr_t = lr * torch.sqrt(1.0 - st[2]) / (1.0 - st[1])
+                m.copy_(b1 * m + (1.0 - b1) * g)
+                v.copy_(b2 * v + (1.0 - b2) * (g * g))
+                p.sub_(lr_t * m / (torch.sqrt(v) + eps))
+            if batch:
+                row = self._kernel_row(1.0, float("inf"))
+                self._kernel_apply([i for i, _ in batch], [g for _, g in batch],
+                                   [row] * len(batch))
+
+    def _enter_phase(self, phase):
+        for key in self._PHASE_KEYS:
+            if key in phase:
+                setattr(self, key, phase[key])

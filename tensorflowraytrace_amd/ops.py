@@ -57,14 +57,34 @@ def _c(t, dtype=None):
 _corner_cache = {}
 
 
+def _check_face_indices(faces, n_vertices):
+    """Raise TfrtError unless every index of ``faces`` lies in [0, n_vertices).  One device
+    read: vertex_corners calls it once per face tensor, never on a cache hit."""
+    if faces.numel() == 0:
+        return
+    lo, hi = (int(x) for x in torch.stack(torch.aminmax(faces)).tolist())
+    if lo < 0 or hi >= int(n_vertices):
+        raise TfrtError(f"faces: vertex indices must lie in [0, {int(n_vertices)}), got "
+                        f"{lo} .. {hi}")
+
+
 def vertex_corners(faces, n_vertices):
     """(corner_start (V+1) i32, corner_list (3F) i32): the face corners ``f*3+c`` sorted by the
     vertex they reference, for the gather form of the reverse kernels (deterministic, no
-    atomics).  Built once per face tensor (mesh topology) and cached with it."""
+    atomics).  Built once per face tensor (mesh topology) and cached with it.
+
+    This is also where the host validates the face indices the kernels rely on (TfrtError for
+    an index outside [0, V)): where the table is built, so once per face tensor; a cache hit
+    costs no launch and no synchronisation.  Building reads the device (the check, bincount), so
+    the first call for a face tensor has to come outside any graph capture.  The cache is keyed
+    by the tensor itself: a caller whose faces are not int32 and contiguous already hands
+    build_faces / param_faces a fresh copy on every call and pays table and check every time --
+    keep the converted tensor, as boundaries.py does."""
     key = (faces.data_ptr(), tuple(faces.shape), int(n_vertices), faces._version)
     hit = _corner_cache.get(key)
     if hit is not None and hit[0] is faces:
         return hit[1], hit[2]
+    _check_face_indices(faces, n_vertices)
     flat = faces.reshape(-1).long()
     order = torch.argsort(flat, stable=True)
     counts = torch.bincount(flat, minlength=int(n_vertices))[:int(n_vertices)]
@@ -87,6 +107,8 @@ class _BuildFaces(torch.autograd.Function):
         _need_gpu(vertices, faces, update_mask)
         vertices = _c(vertices, torch.float64)
         F = faces.shape[0]
+        # (validates the indices, also when no gradient is wanted; outside any graph capture)
+        corners = vertex_corners(faces, vertices.shape[0]) if F > 0 else None
         fv = torch.empty((F, 9), dtype=torch.float64, device=vertices.device)
         norm = torch.empty((F, 3), dtype=torch.float64, device=vertices.device)
         check(_lib.lib().tfrt_build_faces_forward(
@@ -94,8 +116,10 @@ class _BuildFaces(torch.autograd.Function):
             "tfrt_build_faces_forward")
         ctx.save_for_backward(fv, faces, update_mask)
         ctx.n_vertices = vertices.shape[0]
-        if vertices.requires_grad and F > 0:
-            ctx.corners = vertex_corners(faces, vertices.shape[0])   # (outside any graph capture)
+        ctx.corners = corners
+        # (an output the loss does not touch arrives as None, not as zeros: a zero upstream on the
+        # NaN normal of a zero-area face would turn its vertices' gradients into NaN)
+        ctx.set_materialize_grads(False)
         return fv, norm
 
     @staticmethod
@@ -133,6 +157,7 @@ class _ParamFaces(torch.autograd.Function):
         if parameters.shape[0] != V or vectors.shape != zero_points.shape:
             raise TfrtError("param_faces: parameters (V,), zero_points (V,3) and vectors (V,3) "
                             "must describe the same vertices")
+        corners = vertex_corners(faces, V) if F > 0 else None      # (validates the indices)
         fv = torch.empty((F, 9), dtype=torch.float64, device=parameters.device)
         norm = torch.empty((F, 3), dtype=torch.float64, device=parameters.device)
         check(_lib.lib().tfrt_param_faces_forward(
@@ -140,8 +165,7 @@ class _ParamFaces(torch.autograd.Function):
             _stream(parameters)), "tfrt_param_faces_forward")
         ctx.save_for_backward(fv, faces, update_mask, vectors)
         ctx.shape = parameters.shape
-        if F > 0:
-            ctx.corners = vertex_corners(faces, V)
+        ctx.corners = corners
         ctx.set_materialize_grads(False)
         return fv, norm
 
@@ -175,8 +199,9 @@ def param_faces(parameters, zero_points, vectors, faces, update_mask=None):
 
 class _ParamFacesMulti(torch.autograd.Function):
     """Several parametric surfaces (and the fixed boundaries between them) -> ONE merged
-    face_verts block (M,9) and one norm block (sum of the parametric F,3), one launch each way
-    (tfrt_param_faces_*_multi).  ``spec``: list of entries in the order of the merged block,
+    face_verts block (M,9) and one norm tensor (F,3) per parametric surface, one launch each way
+    (tfrt_param_faces_*_multi).  The norms are separate outputs so that a surface whose normals
+    the loss does not touch receives no upstream for them (None), as with a function of its own.  ``spec``: list of entries in the order of the merged block,
     ("param", zero_points, vectors, faces, update_mask) taking the next tensor of ``parameters``,
     or ("copy", face_verts (F,9) detached)."""
 
@@ -185,11 +210,10 @@ class _ParamFacesMulti(torch.autograd.Function):
         dev = parameters[0].device if parameters else spec[0][1].device
         rows = [e[3].shape[0] if e[0] == "param" else e[1].shape[0] for e in spec]
         M = int(sum(rows))
-        n_norm = int(sum(r for e, r in zip(spec, rows) if e[0] == "param"))
         fv = torch.empty((M, 9), dtype=torch.float64, device=dev)
-        norm = torch.empty((n_norm, 3), dtype=torch.float64, device=dev)
+        norms = []
         descs, keep, pars = [], [], []
-        at = na = k = 0
+        at = k = 0
         for e, F in zip(spec, rows):
             d = _lib.FaceSurface()
             d.n_faces = F
@@ -204,10 +228,10 @@ class _ParamFacesMulti(torch.autograd.Function):
                                     "(V,3) must describe the same vertices")
                 d.zero_points, d.vectors, d.parameters = _p(zero), _p(vectors), _p(par)
                 d.faces, d.n_vertices = _p(faces), V
-                d.norm = norm.data_ptr() + na * 24
-                pars.append((at, na, F, V, faces, mask, vectors, par.shape))
+                norms.append(torch.empty((F, 3), dtype=torch.float64, device=dev))
+                d.norm = _p(norms[-1])
+                pars.append((at, F, V, faces, mask, vectors, par.shape))
                 keep.append(par)
-                na += F
             else:
                 d.copy_from = _p(e[1])
             descs.append(d)
@@ -219,18 +243,22 @@ class _ParamFacesMulti(torch.autograd.Function):
             check(_lib.lib().tfrt_param_faces_forward_multi(arr, len(chunk), stream),
                   "tfrt_param_faces_forward_multi")
         ctx.pars = pars
-        ctx.corners = [vertex_corners(f, V) if F > 0 else None for (_, _, F, V, f, _, _, _) in pars]
+        ctx.corners = [vertex_corners(f, V) if F > 0 else None for (_, F, V, f, _, _, _) in pars]
         ctx.save_for_backward(fv)
         ctx.set_materialize_grads(False)
-        return fv, norm
+        return (fv, *norms)
 
     @staticmethod
-    def backward(ctx, g_fv, g_norm):
+    def backward(ctx, g_fv, *g_norms):
         (fv,) = ctx.saved_tensors
         g_fv = _c(g_fv, torch.float64)
-        g_norm = _c(g_norm, torch.float64)
-        out, descs = [], []
-        for (at, na, F, V, faces, mask, vectors, shape), corners in zip(ctx.pars, ctx.corners):
+        out, descs, keep = [], [], []
+        for (at, F, V, faces, mask, vectors, shape), corners, g_norm in zip(ctx.pars, ctx.corners,
+                                                                            g_norms):
+            # (a surface whose normals the loss does not touch has g_norm None and skips the
+            # normal's half: a zero upstream would meet the NaN normal of a zero-area face)
+            g_norm = _c(g_norm, torch.float64)
+            keep.append(g_norm)
             if (g_fv is None and g_norm is None) or F == 0:
                 out.append(torch.zeros(shape, dtype=torch.float64, device=fv.device))
                 continue
@@ -240,7 +268,7 @@ class _ParamFacesMulti(torch.autograd.Function):
                 gp = torch.empty(shape, dtype=torch.float64, device=fv.device)
             d = _lib.FaceSurfaceGrad()
             d.grad_face_verts = g_fv.data_ptr() + at * 72 if g_fv is not None else None
-            d.grad_norm = g_norm.data_ptr() + na * 24 if g_norm is not None else None
+            d.grad_norm = _p(g_norm)
             d.face_verts = fv.data_ptr() + at * 72
             d.update_mask, d.vectors = _p(mask), _p(vectors)
             d.corner_start, d.corner_list = _p(corners[0]), _p(corners[1])
@@ -331,6 +359,8 @@ class ParamFacesBatch:
         if mask is not None:
             mask = _c(mask, torch.uint8)
         _need_gpu(parameters, zero_points, vectors, faces, mask)
+        if faces.shape[0] > 0:
+            vertex_corners(faces, zero_points.shape[0])     # (validates the indices, cached)
         self.requests.append((boundary, parameters, zero_points, vectors, faces, mask))
         boundary.__dict__["_faces_pending"] = self
 
@@ -365,17 +395,17 @@ class ParamFacesBatch:
         spec = [("param", e[1][2], e[1][3], e[1][4], e[1][5]) if e[0] == "param"
                 else ("copy", e[2]) for e in layout]
         pars = [e[1][1] for e in layout if e[0] == "param"]
-        fv, norm = _ParamFacesMulti.apply(spec, *pars)
-        at = na = 0
+        fv, *norms = _ParamFacesMulti.apply(spec, *pars)
+        at = k = 0
         rows = []
         for e in layout:
             if e[0] == "param":
                 b, F = e[1][0], e[1][4].shape[0]
                 b.__dict__["_faces_pending"] = None
                 b._face_verts = fv[at:at + F]
-                b._norm = norm[na:na + F]
+                b._norm = norms[k]
                 rows.append((b, at, at + F))
-                na += F
+                k += 1
             else:
                 F = e[2].shape[0]
                 rows.append((e[1], at, at + F))

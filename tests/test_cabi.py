@@ -122,6 +122,77 @@ def test_bad_arguments_are_rejected_before_any_launch(lib):
     assert lib.tfrt_epoch_advance(None, 9, None) == -1
 
 
+def test_face_entry_points_reject_bad_arguments_before_any_launch(lib):
+    """tfrt_build_faces_backward, tfrt_param_faces_backward, tfrt_param_faces_backward_multi,
+    tfrt_param_faces_forward and tfrt_param_faces_forward_multi: every refusal, and the empty
+    calls that return 0 without a launch."""
+    from tensorflowraytrace_amd import _lib
+    dummy = ctypes.create_string_buffer(1 << 12)
+    ptr = ctypes.cast(dummy, ctypes.c_void_p)
+
+    def build(g_fv=ptr, g_n=ptr, fv=ptr, faces=ptr, F=4, V=4, start=ptr, lst=ptr, out=ptr):
+        return lib.tfrt_build_faces_backward(g_fv, g_n, fv, faces, None, F, V, start, lst, out, None)
+
+    def param(g_fv=ptr, g_n=ptr, fv=ptr, faces=ptr, vec=ptr, F=4, V=4, start=ptr, lst=ptr, out=ptr):
+        return lib.tfrt_param_faces_backward(g_fv, g_n, fv, faces, None, vec, F, V, start, lst, out,
+                                             None)
+
+    for call in (build, param):
+        assert call(F=-1) == -1 and call(V=-1) == -1
+        assert call(g_fv=None, g_n=None) == -1               # no upstream at all
+        assert call(fv=None) == -1                           # grad_norm needs the face block
+        assert call(start=None) == -1 and call(lst=None) == -1
+        assert call(faces=None) == -1 and call(out=None) == -1
+        assert call(F=0) == 0 and call(F=0, g_fv=None, g_n=None, out=None) == 0
+    assert param(vec=None) == -1
+    assert lib.tfrt_param_faces_forward(None, ptr, ptr, 4, ptr, 4, ptr, None, None) == -1
+    assert lib.tfrt_param_faces_forward(ptr, ptr, ptr, 0, ptr, 4, ptr, None, None) == -1
+    assert lib.tfrt_param_faces_forward(None, None, None, 0, None, 0, None, None, None) == 0
+
+    def grad_surface(**kw):
+        d = _lib.FaceSurfaceGrad()
+        for k in ("grad_face_verts", "grad_norm", "face_verts", "vectors", "corner_start",
+                  "corner_list", "grad_parameters"):
+            setattr(d, k, ptr)
+        d.n_vertices = 4
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+
+    def backward_multi(*surfaces, n=None):
+        arr = (_lib.FaceSurfaceGrad * max(len(surfaces), 1))(*surfaces)
+        return lib.tfrt_param_faces_backward_multi(arr, len(surfaces) if n is None else n, None)
+
+    assert backward_multi(n=-1) == -1 and backward_multi(n=_lib.MAX_SURFACES + 1) == -1
+    assert lib.tfrt_param_faces_backward_multi(None, 1, None) == -1
+    assert lib.tfrt_param_faces_backward_multi(None, 0, None) == 0
+    for bad in (dict(n_vertices=-1), dict(grad_face_verts=None, grad_norm=None),
+                dict(face_verts=None), dict(corner_start=None), dict(corner_list=None),
+                dict(vectors=None), dict(grad_parameters=None)):
+        assert backward_multi(grad_surface(n_vertices=0), grad_surface(**bad)) == -1, bad
+    assert backward_multi(grad_surface(n_vertices=0), grad_surface(n_vertices=0)) == 0
+
+    def surface(**kw):
+        d = _lib.FaceSurface()
+        for k in ("zero_points", "vectors", "parameters", "faces", "face_verts"):
+            setattr(d, k, ptr)
+        d.n_vertices, d.n_faces = 4, 4
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+
+    def forward_multi(*surfaces, n=None):
+        arr = (_lib.FaceSurface * max(len(surfaces), 1))(*surfaces)
+        return lib.tfrt_param_faces_forward_multi(arr, len(surfaces) if n is None else n, None)
+
+    assert forward_multi(n=-1) == -1 and forward_multi(n=_lib.MAX_SURFACES + 1) == -1
+    assert lib.tfrt_param_faces_forward_multi(None, 1, None) == -1
+    for bad in (dict(n_faces=-1), dict(n_vertices=-1), dict(face_verts=None), dict(faces=None),
+                dict(parameters=None), dict(n_vertices=0)):
+        assert forward_multi(surface(n_faces=0), surface(**bad)) == -1, bad
+    assert forward_multi(surface(n_faces=0), surface(n_faces=0, face_verts=None)) == 0
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
     from tensorflowraytrace_amd import ops, _lib

@@ -14,6 +14,13 @@ replayed from one HIP graph.  ``--host`` runs what there was before: scipy's int
 and an upload at every step, which the optimiser cannot capture.
 
     python examples/illumination.py [--rays 20000] [--steps 30] [--edge 0.12] [--host]
+
+``--density-error`` optimises the same scene against the target density directly, without ranks: a
+``DensityError`` over (y_end, z_end) whose goal is the even square itself, on a grid of ``--bins``
+bins per axis -- no transport map is needed, and rays that are lost or stopped simply do not count.
+``--generic`` forces the generic path (``fused=False``) for comparison.
+
+    python examples/illumination.py --density-error [--bins 64] [--generic]
 """
 import argparse
 import os
@@ -37,6 +44,7 @@ import tfrt.sources as sources                # noqa: E402
 
 COARSEST_EDGE = 0.4        # the coarsest lens mesh the example is run with (the tests' lens)
 DENSITY_CELLS = 64
+DENSITY_LEARNING_RATE = 0.05
 
 
 def two_bumps(size):
@@ -48,19 +56,29 @@ def two_bumps(size):
     return density
 
 
+def even_square(size, domain_size, bins):
+    """The target of ``--density-error``: 1 on the bins whose centre lies in [-size, size]^2, 0 on
+    the margin up to ``domain_size``."""
+    centres = (np.arange(bins) + 0.5) * (2 * domain_size / bins) - domain_size
+    inside = (np.abs(centres) <= size).astype(np.float64)
+    return inside[:, None] * inside[None, :]
+
+
 def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, magnification=1.0,
-          object_size=0.2, lens_aperature=1.0, rowwise=True, **engine_kw):
+          object_size=0.2, lens_aperature=1.0, rowwise=True, density_error=False, bins=64,
+          **engine_kw):
     limits = ((-object_size, object_size, DENSITY_CELLS), (-object_size, object_size, DENSITY_CELLS))
     start_density = distributions.ArbitraryDistribution(two_bumps(object_size), limits)
     goal_density = distributions.ArbitraryDistribution(lambda gx, gy: np.ones_like(gx), limits)
-    start_points = distributions.ArbitraryBasePoints(start_density, ray_count,
-                                                     rank_distribution=goal_density)
+    # (a DensityError needs no transport map: no ranks ride along)
+    start_points = distributions.ArbitraryBasePoints(
+        start_density, ray_count, rank_distribution=None if density_error else goal_density)
     distributions.BasePointTransformation(start_points, translation=(-source_distance, 0, 0))
     end_points = distributions.RandomUniformCircle(ray_count, 0.98 * lens_aperature)
     distributions.BasePointTransformation(end_points)
     source = sources.AperatureSource(
         3, start_points, end_points, [drawing.YELLOW], dense=False,
-        extra_fields={"goal": ("start_point", start_points, "ranks")})
+        extra_fields={} if density_error else {"goal": ("start_point", start_points, "ranks")})
 
     zero_points = mt.circular_mesh(lens_aperature, lens_res_scale)
     zero_points.rotate_y(90)
@@ -87,22 +105,40 @@ def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, magnificat
 
     trace_engine = engine.OpticalEngine(
         3, [operation.StandardReaction()], compile_active_rays=False,
-        simple_ray_inheritance={"wavelength", "goal"}, **engine_kw)
+        simple_ray_inheritance={"wavelength"} if density_error else {"wavelength", "goal"},
+        **engine_kw)
     trace_engine.optical_system = system
     trace_engine.validate_system()
 
     m = magnification
-    error_function = optimizer.GoalError(("y_end", "z_end"), lambda s: -m * s["goal"], rowwise=rowwise)
+    if density_error:
+        # the even square of half-width m * object_size inside a domain with a margin of a quarter;
+        # a ray beyond the margin is pulled back by the penalty (weighted per ray: the histogram
+        # part of the error is of order 1 whatever the ray count)
+        size = abs(m) * object_size
+        half = 1.25 * size
+        error_function = optimizer.DensityError(
+            ("y_end", "z_end"), even_square(size, half, bins), ((-half, half), (-half, half)),
+            oob_weight=1.0 / (ray_count * size ** 2))
+    else:
+        error_function = optimizer.GoalError(("y_end", "z_end"), lambda s: -m * s["goal"],
+                                             rowwise=rowwise)
     return dict(engine=trace_engine, system=system, lens=lens, source=source,
                 start_points=start_points, error_function=error_function, accumulator=accumulator)
 
 
-def run(ray_count=20000, steps=30, lens_res_scale=0.12, host=False, verbose=True):
+def run(ray_count=20000, steps=30, lens_res_scale=0.12, host=False, verbose=True,
+        density_error=False, bins=64, generic=False, splat_variant=0):
     distributions.set_device_random(not host)
     try:
-        s = build(ray_count, lens_res_scale)
+        s = build(ray_count, lens_res_scale, density_error=density_error, bins=bins)
+        if density_error:
+            s["error_function"].splat_variant = splat_variant
+        # (a DensityError is one term of order 1, not a sum over the rays: its own step size)
+        lr = DENSITY_LEARNING_RATE if density_error else 2e-5 * (20000 / ray_count)
         opt = optimizer.SGD_Optimizer(s["engine"], s["lens"].parameters, s["error_function"], 3,
-                                      learning_rate=2e-5 * (20000 / ray_count), grad_clip=1.0)
+                                      learning_rate=lr, grad_clip=1.0,
+                                      fused=False if generic else "auto")
         opt.suppress_warnings = True
         errors, times = [], []
         for step in range(steps):
@@ -112,7 +148,8 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, host=False, verbose=True
             torch.cuda.synchronize()
             times.append(time.perf_counter() - t0)
             if verbose and step % 5 == 0:
-                print(f"step {step:4d}: mean squared error {errors[-1]:.6g}  ({1e3 * times[-1]:.2f} ms)")
+                name = "density error" if density_error else "mean squared error"
+                print(f"step {step:4d}: {name} {errors[-1]:.6g}  ({1e3 * times[-1]:.2f} ms)")
         fused = opt._fused_step
         s.update(errors=errors, times=times, device_source=s["source"]._device_program() is not None,
                  graph_replays=0 if fused is None else fused.graph_replays)
@@ -128,10 +165,18 @@ if __name__ == "__main__":
     ap.add_argument("--edge", type=float, default=0.12, help=f"lens mesh edge, up to {COARSEST_EDGE}")
     ap.add_argument("--host", action="store_true",
                     help="the density map on the host at every step (scipy), as before it had a program")
+    ap.add_argument("--density-error", action="store_true",
+                    help="optimise against the target density directly (DensityError), without ranks")
+    ap.add_argument("--bins", type=int, default=64, help="bins per axis of the DensityError's grid")
+    ap.add_argument("--generic", action="store_true", help="the generic path (fused=False)")
+    ap.add_argument("--splat-variant", type=int, default=0, choices=(0, 1, 2),
+                    help="tfrt_density_error's splat: 0 by the bin count, 1 LDS histogram, 2 global atomics")
     a = ap.parse_args()
-    out = run(a.rays, a.steps, a.edge, host=a.host)
+    out = run(a.rays, a.steps, a.edge, host=a.host, density_error=a.density_error, bins=a.bins,
+              generic=a.generic, splat_variant=a.splat_variant)
     tail = sorted(out["times"][len(out["times"]) // 2:])
     print(f"source on the device: {out['device_source']}; steps replayed from the graph: "
           f"{out['graph_replays']} of {a.steps}; median step of the second half: "
           f"{1e3 * tail[len(tail) // 2]:.3f} ms")
-    print(f"mean squared illumination error: first {out['errors'][0]:.6g} -> last {out['errors'][-1]:.6g}")
+    name = "density error" if a.density_error else "mean squared illumination error"
+    print(f"{name}: first {out['errors'][0]:.6g} -> last {out['errors'][-1]:.6g}")

@@ -511,6 +511,49 @@ int tfrt_goal_error3d_deferred(const void* finished_rays, int64_t capacity,
                                tfrt_goal_pending* pending, void* stream);
 int tfrt_goal_finish(const tfrt_goal_pending* pending, void* stream);
 
+/* DensityError: the columns that count, taken together, must land with the density `goal` on an
+ * (ny x nx) grid of bins over the domain [x0, x1] x [y0, y1] -- the soft-histogram form of
+ * tfrt/analyze.py:134-290 (DistributionDifferential), which bins hard and has no gradient.  Three
+ * launches behind a memset of `hq`, no host read, no allocation: captured with the rest of a step.
+ *
+ * A column i counts if mask is NULL or mask[i] >= 0 (tfrt_ray_out.face of an in-place trace with
+ * the finished rows at the rays' own columns) and its coordinates x = rows[row_x], y = rows[row_y]
+ * (converted to f64) are finite.  Every operation below is rounded on its own (no contraction).
+ *   outside the closed domain on any axis: nothing goes to the histogram; the error gains
+ *     oob_weight * (ex^2 + ey^2), ex = max(x0 - x, 0) + max(x - x1, 0), and the gradient is the
+ *     derivative of that expression;
+ *   inside: u = (x - x0) * sx - 0.5, i0 = floor(u), t = u - i0; weight 1 - t goes to column
+ *     clamp(i0, 0, nx - 1), weight t to column clamp(i0 + 1, 0, nx - 1) (the outer half bin piles
+ *     onto the edge bin); y alike, the four weights are the products (two weights without y).
+ *   Each weight w is added to its bin as the integer rint(w * 2^32), half to even, in the int64
+ *   histogram hq: the sum does not depend on the order of the atomics.  H = hq / 2^32, s = ||H||;
+ *   s == 0: E_hist = sum g^2 and every pull is 0; else h = H / s, r = h - g, E_hist = sum r^2 and
+ *   the pull on bin b is D_b = (2 / s) (r_b - h_b sum_c h_c r_c).  A counting ray inside gets
+ *     d/dx = sx [(1 - ty)(D[j0,i1] - D[j0,i0]) + ty (D[j1,i1] - D[j1,i0])], d/dy symmetric
+ *   (clamped indices; quantisation treated as the identity).  error = E_hist + penalties; all of
+ *   its sums have a fixed shape and order: two runs give the same bits.
+ *
+ *   rows, stride    ray block in the state dtype, entry (row, i) at rows[row * stride + i], n columns
+ *   row_x, row_y    rows (0..5) of x and y; row_y = -1: one field (then ny must be 1)
+ *   goal            (ny, nx) f64, non-negative, L2-normalised by the caller
+ *   sx, sy          nx / (x1 - x0), ny / (y1 - y0), computed by the caller in f64
+ *   grad            f64 block, entry (row, i) at grad[row * grad_stride + i]: rows row_x and row_y
+ *                   are written for EVERY column (0 where a ray does not count); no other row is
+ *   error_out       3 f64 {error, 1, error}: one error term, the mean is the sum
+ *   hq              nx * ny int64, cleared and filled by this call
+ *   splat_variant   0: the per-workgroup LDS histogram up to 4,096 bins, global 64-bit atomics
+ *                   above; 1 / 2 force one of them (1 with more than 4,096 bins: TFRT_E_BADARG)
+ *   workspace       tfrt_density_error_workspace_bytes(n, nx, ny) bytes (0: bad arguments)
+ * nx, ny >= 1, nx * ny <= 65,536, 0 <= n < 2^31 (n == 0 is legal: error = sum g^2).
+ */
+size_t tfrt_density_error_workspace_bytes(int64_t n, int32_t nx, int32_t ny);
+int tfrt_density_error(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                       const int32_t* mask, int32_t row_x, int32_t row_y, const double* goal,
+                       int32_t nx, int32_t ny, double x0, double x1, double sx, double y0,
+                       double y1, double sy, double oob_weight, double* grad, int64_t grad_stride,
+                       double* error_out, int64_t* hq, int32_t splat_variant, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* tfrt_goal_error3d_deferred and tfrt_trace3d_backward in ONE launch, for a trace over coherent
  * rays (tfrt_scene3d.coherent_rays, not deterministic, max_passes <= 8; TFRT_E_UNSUPPORTED
  * otherwise -- call the two entry points instead): the lane that walks a finished ray's chain of

@@ -1,0 +1,327 @@
+// DensityError: the finished rays, taken together, must land with a given density on the target.
+//
+// The rays' end points are spread bilinearly over the centres of an (ny x nx) grid of bins -- a
+// soft histogram H --, both H and the goal are L2-normalised, and the error is the sum of squared
+// differences (tfrt/analyze.py:134-290, DistributionDifferential, is the same on hard bins: it has
+// no gradient).  The definition, operation by operation, is in include/tfrt_hip.h at
+// tfrt_density_error; tests/density_error_reference.py restates it in numpy.
+//
+// Bit-reproducible by construction: every weight w is added to its bin as the INTEGER
+// rint(w * 2^32) (int64; n < 2^31 rays of total weight 1 each stay below 2^63).  Integer addition
+// is associative, so the histogram does not depend on the order in which the atomics land; every
+// floating-point reduction has a fixed shape and order.  No float atomics anywhere.
+//
+// Three launches (the int64 histogram is cleared by a memset node in front of them):
+//
+//   k_density_splat   one lane per column (a fixed grid for n, grid-stride): weights -> Hq, and the
+//                     out-of-domain penalty as one partial sum per workgroup.  Two variants:
+//                     <true>  bins <= DENSITY_LDS_BINS: a per-workgroup int64 histogram in LDS
+//                             (ds_add_u64; 8 B per bin, at most 32 KiB of the CU's 160 KiB: with
+//                             the 32 B of the penalty sum four workgroups -- 4 waves per SIMD --
+//                             still fit a CU), flushed with one global atomic per non-zero bin.
+//                             Many rays hit few bins: the contention stays in LDS.
+//                     <false> more bins: global 64-bit atomics (global_atomic_add_x2) per weight.
+//   k_density_bins    ONE workgroup of 1024: s = ||H||, E_hist, the pull D on every bin (up to
+//                     65,536 of them), the penalty partials in index order, {sum, terms, mean}.
+//   k_density_seed    one lane per column: both gradient rows of EVERY column (zeros where a ray
+//                     does not count) from D and the same classification as the splat.
+//
+// The penalty is summed where the rays are first classified (the splat) and finished by the one
+// workgroup that runs anyway (the bins): a sum formed by the seed would need a fourth, dependent
+// launch (~4.5 us) or a "last workgroup finishes" fence (what that costs: tfrt_error.hip).
+#include "tfrt_common.h"
+
+namespace tfrt {
+
+constexpr int DENSITY_LDS_BINS = 4096;   // 32 KiB of int64 per workgroup
+constexpr int DENSITY_MAX_BINS = 65536;
+constexpr int DENSITY_MAX_GRID = 512;    // workgroups of the splat (two per CU of a 256-CU chip)
+constexpr int DENSITY_RAYS_PER_BLOCK = 4 * BLOCK;
+constexpr int BINS_BLOCK = 1024;
+constexpr int BINS_WAVES = BINS_BLOCK / 64;
+
+struct DensityGrid {
+  double x0, x1, sx, y0, y1, sy, oob;
+  int32_t nx, ny, row_x, row_y;
+};
+
+// What one column does.  kind 0: does not count (masked, or a non-finite coordinate); 1: inside
+// the closed domain, spread over (ja|jb, ia|ib) with tx, ty; 2: outside, ex / ey and their signs.
+struct DensityRay {
+  int kind;
+  int ia, ib, ja, jb;
+  double tx, ty;     // kind 1: the upper weights; kind 2: ex, ey
+  double dx, dy;     // kind 2: d ex / d x, d ey / d y (-1, 0, +1)
+};
+
+__device__ __forceinline__ void density_axis(double v, double lo, double scale, int nb, int& a,
+                                             int& b, double& t) {
+#pragma clang fp contract(off)
+  const double u = (v - lo) * scale - 0.5;
+  const double f = floor(u);
+  t = u - f;
+  // (f lies in [-1, nb]: v is inside the closed domain)
+  const int i0 = (int)f;
+  a = min(max(i0, 0), nb - 1);
+  b = min(max(i0 + 1, 0), nb - 1);
+}
+
+template <typename T>
+__device__ __forceinline__ DensityRay density_classify(const T* __restrict__ rows, int64_t stride,
+                                                       const int32_t* __restrict__ mask, int64_t i,
+                                                       const DensityGrid& g) {
+#pragma clang fp contract(off)
+  DensityRay r;
+  r.kind = 0;
+  r.ia = r.ib = r.ja = r.jb = 0;
+  r.tx = r.ty = r.dx = r.dy = 0.0;
+  if (mask != nullptr && mask[i] < 0) return r;
+  const bool two = g.row_y >= 0;
+  const double x = ldd(rows, (int64_t)g.row_x * stride + i);
+  const double y = two ? ldd(rows, (int64_t)g.row_y * stride + i) : 0.0;
+  if (!isfinite(x) || !isfinite(y)) return r;
+  const bool out = x < g.x0 || x > g.x1 || (two && (y < g.y0 || y > g.y1));
+  if (out) {
+    r.kind = 2;
+    r.tx = fmax(g.x0 - x, 0.0) + fmax(x - g.x1, 0.0);
+    r.dx = x < g.x0 ? -1.0 : (x > g.x1 ? 1.0 : 0.0);
+    if (two) {
+      r.ty = fmax(g.y0 - y, 0.0) + fmax(y - g.y1, 0.0);
+      r.dy = y < g.y0 ? -1.0 : (y > g.y1 ? 1.0 : 0.0);
+    }
+    return r;
+  }
+  r.kind = 1;
+  density_axis(x, g.x0, g.sx, g.nx, r.ia, r.ib, r.tx);
+  if (two) density_axis(y, g.y0, g.sy, g.ny, r.ja, r.jb, r.ty);
+  return r;
+}
+
+__device__ __forceinline__ unsigned long long density_fixed(double w) {
+#pragma clang fp contract(off)
+  // round half to even (v_rndne_f64); w in [0, 1], so the product is exact and at most 2^32
+  return (unsigned long long)(long long)rint(w * 4294967296.0);
+}
+
+// fixed-shape sum over a workgroup of NW waves: xor butterflies inside the wave, waves in index
+// order; every thread of the workgroup must call it.  `wsum` is reused: a barrier at the end.
+template <int NW>
+__device__ __forceinline__ double density_block_sum(double v, double* wsum) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+  if (lane_id() == 0) wsum[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int w = 0; w < NW; ++w) s += wsum[w];
+  __syncthreads();
+  return s;
+}
+
+template <typename T, bool LDS>
+__global__ __launch_bounds__(BLOCK) void k_density_splat(
+    const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
+    DensityGrid g, unsigned long long* __restrict__ hq, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+  extern __shared__ unsigned long long hist[];
+  __shared__ double wsum[WAVES];
+  const int bins = g.nx * g.ny;
+  if (LDS) {
+    for (int b = threadIdx.x; b < bins; b += BLOCK) hist[b] = 0ull;
+    __syncthreads();
+  }
+  unsigned long long* dst = LDS ? hist : hq;
+  double pen = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * BLOCK) {
+    const DensityRay r = density_classify(rows, stride, mask, i, g);
+    if (r.kind == 2) {
+      pen += g.oob * (r.tx * r.tx + r.ty * r.ty);
+    } else if (r.kind == 1) {
+      const double wx0 = 1.0 - r.tx, wx1 = r.tx;
+      if (g.row_y >= 0) {
+        const double wy0 = 1.0 - r.ty, wy1 = r.ty;
+        atomicAdd(&dst[r.ja * g.nx + r.ia], density_fixed(wy0 * wx0));
+        atomicAdd(&dst[r.ja * g.nx + r.ib], density_fixed(wy0 * wx1));
+        atomicAdd(&dst[r.jb * g.nx + r.ia], density_fixed(wy1 * wx0));
+        atomicAdd(&dst[r.jb * g.nx + r.ib], density_fixed(wy1 * wx1));
+      } else {
+        atomicAdd(&dst[r.ia], density_fixed(wx0));
+        atomicAdd(&dst[r.ib], density_fixed(wx1));
+      }
+    }
+  }
+  if (LDS) {
+    __syncthreads();
+    for (int b = threadIdx.x; b < bins; b += BLOCK) {
+      const unsigned long long v = hist[b];
+      if (v != 0ull) atomicAdd(&hq[b], v);
+    }
+  }
+  const double s = density_block_sum<WAVES>(pen, wsum);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// One workgroup.  Thread t owns bins t, t + 1024, ... (summed in that order), then the fixed-shape
+// workgroup sum: the same bits on every run.
+__global__ __launch_bounds__(BINS_BLOCK) void k_density_bins(
+    const long long* __restrict__ hq, const double* __restrict__ goal, int bins,
+    const double* __restrict__ partial, int n_partial, double* __restrict__ pull,
+    double* __restrict__ error_out) {
+#pragma clang fp contract(off)
+  __shared__ double wsum[BINS_WAVES];
+  const int t = threadIdx.x;
+  double hh = 0.0, gg = 0.0, pen = 0.0;
+  for (int b = t; b < bins; b += BINS_BLOCK) {
+    const double H = (double)hq[b] / 4294967296.0;
+    const double gb = goal[b];
+    hh += H * H;
+    gg += gb * gb;
+  }
+  for (int b = t; b < n_partial; b += BINS_BLOCK) pen += partial[b];
+  hh = density_block_sum<BINS_WAVES>(hh, wsum);
+  gg = density_block_sum<BINS_WAVES>(gg, wsum);
+  pen = density_block_sum<BINS_WAVES>(pen, wsum);
+  const double s = sqrt(hh);
+  double e_hist;
+  if (s == 0.0) {
+    for (int b = t; b < bins; b += BINS_BLOCK) pull[b] = 0.0;
+    e_hist = gg;
+  } else {
+    double rr = 0.0, hr = 0.0;
+    for (int b = t; b < bins; b += BINS_BLOCK) {
+      const double h = ((double)hq[b] / 4294967296.0) / s;
+      const double r = h - goal[b];
+      rr += r * r;
+      hr += h * r;
+    }
+    rr = density_block_sum<BINS_WAVES>(rr, wsum);
+    hr = density_block_sum<BINS_WAVES>(hr, wsum);
+    const double k = 2.0 / s;
+    for (int b = t; b < bins; b += BINS_BLOCK) {
+      const double h = ((double)hq[b] / 4294967296.0) / s;
+      const double r = h - goal[b];
+      pull[b] = k * (r - h * hr);
+    }
+    e_hist = rr;
+  }
+  if (t == 0) {
+    const double e = e_hist + pen;
+    error_out[0] = e;
+    error_out[1] = 1.0;   // one error term: the reported mean is the sum
+    error_out[2] = e;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_density_seed(
+    const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
+    DensityGrid g, const double* __restrict__ pull, double* __restrict__ grad,
+    int64_t grad_stride) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const DensityRay r = density_classify(rows, stride, mask, i, g);
+  const bool two = g.row_y >= 0;
+  double gx = 0.0, gy = 0.0;
+  if (r.kind == 2) {
+    gx = g.oob * (2.0 * r.tx) * r.dx;
+    gy = g.oob * (2.0 * r.ty) * r.dy;
+  } else if (r.kind == 1) {
+    if (two) {
+      const double d00 = pull[r.ja * g.nx + r.ia], d01 = pull[r.ja * g.nx + r.ib];
+      const double d10 = pull[r.jb * g.nx + r.ia], d11 = pull[r.jb * g.nx + r.ib];
+      gx = g.sx * ((1.0 - r.ty) * (d01 - d00) + r.ty * (d11 - d10));
+      gy = g.sy * ((1.0 - r.tx) * (d10 - d00) + r.tx * (d11 - d01));
+    } else {
+      gx = g.sx * (pull[r.ib] - pull[r.ia]);
+    }
+  }
+  grad[(int64_t)g.row_x * grad_stride + i] = gx;
+  if (two) grad[(int64_t)g.row_y * grad_stride + i] = gy;
+}
+
+static int density_grid(int64_t n) {
+  if (n <= 0) return 0;
+  const int64_t want = (n + DENSITY_RAYS_PER_BLOCK - 1) / DENSITY_RAYS_PER_BLOCK;
+  return (int)(want < DENSITY_MAX_GRID ? want : DENSITY_MAX_GRID);
+}
+
+}  // namespace tfrt
+
+using namespace tfrt;
+
+extern "C" {
+
+size_t tfrt_density_error_workspace_bytes(int64_t n, int32_t nx, int32_t ny) {
+  if (n < 0 || nx < 1 || ny < 1 || (int64_t)nx * ny > DENSITY_MAX_BINS) return 0;
+  return align_up((size_t)nx * ny * sizeof(double)) + align_up(DENSITY_MAX_GRID * sizeof(double));
+}
+
+int tfrt_density_error(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                       const int32_t* mask, int32_t row_x, int32_t row_y, const double* goal,
+                       int32_t nx, int32_t ny, double x0, double x1, double sx, double y0,
+                       double y1, double sy, double oob_weight, double* grad, int64_t grad_stride,
+                       double* error_out, int64_t* hq, int32_t splat_variant, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  if (n < 0 || n > INT32_MAX || nx < 1 || ny < 1 || (int64_t)nx * ny > DENSITY_MAX_BINS ||
+      row_x < 0 || row_x > 5 || row_y < -1 || row_y > 5 || row_x == row_y || !goal || !error_out ||
+      !hq || !workspace || (row_y < 0 && ny != 1) || splat_variant < 0 || splat_variant > 2)
+    return TFRT_E_BADARG;
+  if (!(x1 > x0) || !(sx > 0.0) || !isfinite(sx) || !(oob_weight >= 0.0) || !isfinite(oob_weight) ||
+      !isfinite(x0) || !isfinite(x1))
+    return TFRT_E_BADARG;
+  if (row_y >= 0 && (!(y1 > y0) || !(sy > 0.0) || !isfinite(sy) || !isfinite(y0) || !isfinite(y1)))
+    return TFRT_E_BADARG;
+  if (n > 0 && (!rows || !grad || stride < n || grad_stride < n)) return TFRT_E_BADARG;
+  if (state_dtype != TFRT_F32 && state_dtype != TFRT_F64 && state_dtype != TFRT_F16)
+    return TFRT_E_BADARG;
+  const int bins = nx * ny;
+  if (splat_variant == 1 && bins > DENSITY_LDS_BINS) return TFRT_E_BADARG;
+  if (workspace_bytes < tfrt_density_error_workspace_bytes(n, nx, ny)) return TFRT_E_WORKSPACE;
+  const bool lds = splat_variant == 1 || (splat_variant == 0 && bins <= DENSITY_LDS_BINS);
+
+  DensityGrid g;
+  g.x0 = x0, g.x1 = x1, g.sx = sx, g.oob = oob_weight;
+  g.y0 = row_y >= 0 ? y0 : 0.0, g.y1 = row_y >= 0 ? y1 : 0.0, g.sy = row_y >= 0 ? sy : 0.0;
+  g.nx = nx, g.ny = ny, g.row_x = row_x, g.row_y = row_y;
+  double* pull = static_cast<double*>(workspace);
+  double* partial = reinterpret_cast<double*>(static_cast<char*>(workspace) +
+                                              align_up((size_t)bins * sizeof(double)));
+  unsigned long long* hqu = reinterpret_cast<unsigned long long*>(hq);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int grid = density_grid(n);
+  const int nblk = cdiv(n, BLOCK);
+
+  (void)hipMemsetAsync(hq, 0, (size_t)bins * sizeof(int64_t), st);
+#define TFRT_DENSITY(T)                                                                          \
+  do {                                                                                           \
+    const T* r = static_cast<const T*>(rows);                                                    \
+    if (grid > 0) {                                                                              \
+      if (lds)                                                                                   \
+        hipLaunchKernelGGL((k_density_splat<T, true>), dim3(grid), dim3(BLOCK),                  \
+                           (size_t)bins * sizeof(unsigned long long), st, r, stride, n, mask, g, \
+                           hqu, partial);                                                        \
+      else                                                                                       \
+        hipLaunchKernelGGL((k_density_splat<T, false>), dim3(grid), dim3(BLOCK), 0, st, r,       \
+                           stride, n, mask, g, hqu, partial);                                    \
+    }                                                                                            \
+    hipLaunchKernelGGL(k_density_bins, dim3(1), dim3(BINS_BLOCK), 0, st,                         \
+                       reinterpret_cast<const long long*>(hq), goal, bins, partial, grid, pull,  \
+                       error_out);                                                               \
+    if (nblk > 0)                                                                                \
+      hipLaunchKernelGGL((k_density_seed<T>), dim3(nblk), dim3(BLOCK), 0, st, r, stride, n,      \
+                         mask, g, pull, grad, grad_stride);                                      \
+  } while (0)
+  if (state_dtype == TFRT_F32) {
+    TFRT_DENSITY(float);
+  } else if (state_dtype == TFRT_F64) {
+    TFRT_DENSITY(double);
+  } else {
+    TFRT_DENSITY(_Float16);
+  }
+#undef TFRT_DENSITY
+  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+}
+
+}  // extern "C"

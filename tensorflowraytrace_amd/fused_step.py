@@ -33,7 +33,9 @@ every pass in ONE launch -- and autograd from the merged segments and arcs to th
 ``RowwiseError`` (``_rowwise2d``) the error comes from ``tfrt_trace2d_rows`` (every source ray's
 fixed-shape column), ``fn`` and its autograd, and ``tfrt_trace2d_backward_rows`` sweeps from that
 gradient; ``_rowwise3d`` does the same on a 3-D engine with an in-place trace that leaves the
-finished rows at the rays' own columns.
+finished rows at the rays' own columns.  A ``DensityError`` -- the finished rays, taken together,
+must land with a given density -- takes ``_rowwise3d`` too, with ``tfrt_density_error`` (a memset and
+three launches: splat, bins, seed) in the place of ``fn`` and its autograd.
 
 The four bodies share one skeleton: ``_enqueue_gradient`` does what comes before the trace, the
 body its launches over a ``_StepState``, ``_publish_lazily`` and ``_enqueue_apply`` what comes after.
@@ -179,6 +181,165 @@ class RowwiseError:
         return self.fn(engine.finished_rays)
 
 
+class DensityError:
+    """The finished rays, taken together, must land with the density ``goal`` on the target: a
+    soft (bilinear) histogram of the rays against the goal, both L2-normalised, summed squared
+    difference -- ``analyze.DistributionDifferential`` (tfrt/analyze.py:134-290) with a gradient.
+
+    ``fields``: one or two geometry fields of a finished ray, x and (if present) y, e.g.
+    ``("y_end", "z_end")``.  ``goal``: a non-negative array, shape (ny, nx) for two fields -- the
+    second field is the FIRST index, as ``analyze.histogram2D`` returns it -- or (nx,) for one; or a
+    callable, evaluated once at the bin centres exactly as ``DistributionDifferential`` does (the
+    bin counts then come from ``bins``: nx, or (nx, ny)).  It is kept L2-normalised in float64 on
+    the device as ``goal`` (``g`` below); an all-zero goal is a ValueError.  ``domain``:
+    ``((x0, x1), (y0, y1))``, or ``((x0, x1),)`` for one field.  At least one bin per axis, at most
+    65,536 bins.  ``sx = nx / (x1 - x0)`` (and ``sy``) are computed once, in float64, on the host.
+
+    For every finished ray of the trace, coordinates converted to float64, every operation
+    rounded on its own:
+
+    * a ray with a non-finite coordinate contributes nothing and gets zero gradient;
+    * a ray outside the closed domain on any axis contributes nothing to the histogram and adds
+      ``oob_weight * (ex**2 + ey**2)`` to the error, ``ex = max(x0 - x, 0) + max(x - x1, 0)``; its
+      gradient is the derivative of that expression;
+    * a ray inside is spread bilinearly over bin centres: ``u = (x - x0) * sx - 0.5``,
+      ``i0 = floor(u)``, ``t = u - i0``; weight ``1 - t`` goes to column ``clamp(i0, 0, nx - 1)``
+      and ``t`` to column ``clamp(i0 + 1, 0, nx - 1)`` (the outer half bin piles onto the edge bin:
+      total weight 1, derivative 0 there); y alike, the four weights are the products; one field:
+      two weights;
+    * each weight ``w`` is added to its bin as the integer ``rint(w * 2**32)`` (half to even) in an
+      int64 histogram ``Hq`` -- integer addition is associative, so ``Hq`` does not depend on the
+      order of the atomics; ``H = Hq / 2**32``;
+    * ``s = ||H||``; ``s == 0``: the histogram part is ``sum(g**2)`` and every pull is 0; otherwise
+      ``h = H / s``, ``r = h - g``, ``E_hist = sum(r**2)`` and the pull on bin b is
+      ``D_b = (2 / s) * (r_b - h_b * sum_c(h_c * r_c))``;
+    * gradient of a ray inside (quantisation treated as the identity):
+      ``dE/dx = sx * ((1 - ty) * (D[j0, i1] - D[j0, i0]) + ty * (D[j1, i1] - D[j1, i0]))`` with
+      the clamped indices, ``dE/dy`` symmetric;
+    * ``error = E_hist + sum of the penalties``: ONE error term, so the reported mean is the sum.
+      Every reduction has a fixed shape and order: two runs give the same bits.
+
+    It is an ordinary ``error_function(engine)`` (the generic path: ``ops.density_error`` over the
+    finished rays' columns under a ``torch.autograd.Function``), which also serves sources that
+    are not traced in place, ``deterministic=True`` and 2-D engines.  On a 3-D engine that traces
+    its source in place the optimiser runs it on the fused, graph-replayed step under the
+    conditions of a ``RowwiseError`` (``FusedStep._rowwise3d`` with ``tfrt_density_error`` in the
+    place of ``fn`` and its autograd).  The fused 2-D step does not take it
+    (``FusedStep.eligible2d`` is false): 2-D engines use the generic path.  One process: the
+    histogram couples the rays, ray shards would each normalise their own.
+
+    ``goal`` may be overwritten in place between steps (a replayed graph reads the buffer);
+    ``last_hq`` is the int64 histogram of the last evaluation.  ``splat_variant`` (0: by the number
+    of bins; 1: histogram in LDS; 2: global atomics) is tfrt_density_error's, for measuring."""
+
+    splat_variant = 0
+
+    def __init__(self, fields, goal, domain, oob_weight=0.0, bins=None):
+        from . import config
+        self.fields = (fields,) if isinstance(fields, str) else tuple(fields)
+        if len(self.fields) not in (1, 2) or any(f not in _GEO3 for f in self.fields) \
+                or len(set(self.fields)) != len(self.fields):
+            raise ValueError(f"DensityError: one or two distinct fields out of {_GEO3}, got {fields!r}")
+        self.rows = [_GEO3.index(f) for f in self.fields]
+        k = len(self.fields)
+        try:
+            domain = tuple((float(d[0]), float(d[1])) for d in domain)
+        except (IndexError, TypeError) as e:
+            raise ValueError("DensityError: domain must be ((x0, x1), (y0, y1)) or ((x0, x1),)") from e
+        if len(domain) != k or any(not (np.isfinite(a) and np.isfinite(b) and b > a) for a, b in domain):
+            raise ValueError(f"DensityError: domain needs one finite (lo, hi), lo < hi, per field; got {domain!r}")
+        self.domain = domain
+        self.oob_weight = float(oob_weight)
+        if not (self.oob_weight >= 0.0 and np.isfinite(self.oob_weight)):
+            raise ValueError("DensityError: oob_weight must be finite and >= 0")
+        dev = config.get_device()
+        if callable(goal):
+            if bins is None:
+                raise ValueError("DensityError: a callable goal needs bins=nx or bins=(nx, ny)")
+            counts = (int(bins),) * k if np.ndim(bins) == 0 else tuple(int(b) for b in bins)
+            if len(counts) != k or any(c < 1 for c in counts):
+                raise ValueError(f"DensityError: bins must give one count >= 1 per field, got {bins!r}")
+            centres = []
+            for (lo, hi), c in zip(domain, counts):
+                edges = torch.linspace(lo, hi, c + 1, dtype=torch.float64, device=dev)
+                centres.append((edges[:-1] + edges[1:]) / 2.0)
+            if k == 2:
+                goal = goal(*torch.meshgrid(centres[0], centres[1], indexing="xy"))
+            else:
+                goal = goal(centres[0])
+        g = config.as_f64(goal, dev).detach()
+        if g.dim() != k or g.numel() < 1 or g.numel() > ops.DENSITY_MAX_BINS:
+            raise ValueError(f"DensityError: goal must have {k} dimension(s) and between 1 and "
+                             f"{ops.DENSITY_MAX_BINS} bins, got shape {tuple(g.shape)}")
+        if not bool(torch.isfinite(g).all()) or bool((g < 0).any()):
+            raise ValueError("DensityError: goal must be finite and non-negative")
+        norm = float(torch.linalg.norm(g))
+        if norm == 0.0:
+            raise ValueError("DensityError: goal is zero everywhere")
+        self.goal = (g / norm).contiguous()
+        nx = self.goal.shape[-1]
+        self.grid = ops.density_grid(domain, nx, self.goal.shape[0] if k == 2 else None)
+        self.last_hq = None
+
+    @property
+    def g(self):
+        return self.goal
+
+    def rows_for(self, dimension):
+        """Rows of the ray block of a ``dimension``-D trace that the fields are read from."""
+        if dimension == 3:
+            return self.rows
+        bad = [f for f in self.fields if f not in _GEO2]
+        if bad:
+            raise ValueError(f"DensityError: field(s) {bad} do not exist on a {dimension}-D engine "
+                             f"(fields of its rays: {_GEO2})")
+        return [_GEO2.index(f) for f in self.fields]
+
+    def goal_on(self, device):
+        """The goal buffer on ``device`` (moved once; a new buffer re-captures a graph)."""
+        if self.goal.device != device:
+            self.goal = self.goal.to(device)
+        return self.goal
+
+    def graph_key(self):
+        """What a captured step has baked in: the goal buffer's address and the constants."""
+        return (self.goal.data_ptr(), tuple(self.goal.shape), self.grid, self.oob_weight,
+                self.splat_variant)
+
+    def evaluate(self, rows, row_x, row_y, mask=None, **buffers):
+        """``ops.density_error`` of the columns of ``rows`` with this goal, domain and weight."""
+        out = ops.density_error(rows, row_x, row_y, self.goal_on(rows.device), self.grid,
+                                self.oob_weight, mask=mask, variant=self.splat_variant, **buffers)
+        self.last_hq = out[2]
+        return out
+
+    def __call__(self, engine):
+        """The error as a (1,) tensor through the generic path; the gradient rows come back in
+        ``backward``."""
+        self.rows_for(engine.dimension)
+        fin = engine.finished_rays
+        if not bool(fin):
+            return (self.goal * self.goal).sum().reshape(1)
+        return _DensityTerms.apply(torch.stack([fin[f] for f in self.fields], dim=0), self)
+
+
+class _DensityTerms(torch.autograd.Function):
+    """DensityError over the (k, n) field columns of the finished rays, no mask."""
+
+    @staticmethod
+    def forward(ctx, columns, erf):
+        block = columns.detach().contiguous()
+        err, grad, _ = erf.evaluate(block, 0, 1 if block.shape[0] == 2 else -1)
+        ctx.save_for_backward(grad)
+        ctx.dtype = columns.dtype
+        return err[:1].clone()
+
+    @staticmethod
+    def backward(ctx, upstream):
+        grad, = ctx.saved_tensors
+        return (upstream * grad).to(ctx.dtype), None
+
+
 class _RowFields:
     """Field mapping handed to a RowwiseError on the fixed-shape path: geometry = the rows of the
     in-place finished block, everything else = the source's own fields in the trace's order."""
@@ -267,6 +428,7 @@ class _StepState:
         "g_fin", "g_fv", "g_n",                              # 3-D gradient blocks
         "g_prim", "g_seg", "g_arc", "g_index",               # 2-D: one block, views into it
         "rows", "row_face", "row_passes", "row_outs",        # a RowwiseError's fixed-shape columns
+        "density_ws", "hq",                                  # a DensityError's workspace and histogram
         "chain_ws", "inherited",                             # made on first use
         "block", "stream", "perm", "inplace")                # of the last enqueued step
 
@@ -311,7 +473,8 @@ class _StepState:
 
 class FusedStep:
     """Runs ``SGD_Optimizer.single_step`` for a ``GoalError`` or a ``RowwiseError`` as a fixed
-    launch sequence, on 3-D engines and on 2-D ones (one process); see the module docstring.
+    launch sequence, on 3-D engines and on 2-D ones (one process), and for a ``DensityError`` on
+    3-D engines; see the module docstring.
     One instance per optimizer."""
 
     # coherent rays: error, gradient seed and reverse sweep as ONE launch (tfrt_trace3d_backward_goal);
@@ -356,11 +519,14 @@ class FusedStep:
     @staticmethod
     def eligible(optimizer, args, kwargs):
         eng = optimizer.engine
-        if not isinstance(optimizer.error_function, (GoalError, RowwiseError)) or args or kwargs:
+        erf = optimizer.error_function
+        if not isinstance(erf, (GoalError, RowwiseError, DensityError)) or args or kwargs:
             return False
-        if (isinstance(optimizer.error_function, RowwiseError) and eng.dimension == 3
+        if (isinstance(erf, (RowwiseError, DensityError)) and eng.dimension == 3
                 and not FusedStep.rowwise_ready(eng)):
             return False
+        if isinstance(erf, DensityError) and tdist.is_distributed():
+            return False            # (the histogram couples the rays: one process)
         if not bool(eng.optical_system):
             return False
         if eng.dimension == 2 and not FusedStep.eligible2d(optimizer):
@@ -517,7 +683,7 @@ class FusedStep:
             raise RuntimeError("FusedStep: the optical system has no source rays")
         inputs = eng._trace_inputs(src)
         P, flags = int(opt.trace_depth), eng._flags() | _lib.COMPILE_FINISHED
-        rowwise = isinstance(opt.error_function, RowwiseError)
+        rowwise = isinstance(opt.error_function, (RowwiseError, DensityError))
         if eng.dimension == 2:
             body = self._rowwise2d if rowwise else self._goal2d
         else:
@@ -673,8 +839,8 @@ class FusedStep:
 
     def _rowwise3d(self, src, inputs, tap_log, P, flags):
         """In-place trace with the finished rows at the rays' own columns -> ``erf.fn`` on
-        fixed-shape tensors + its autograd (torch) -> reverse sweep.  No ray count is read;
-        everything is capturable."""
+        fixed-shape tensors + its autograd (torch), or a DensityError's three launches
+        (tfrt_density_error) -> reverse sweep.  No ray count is read; everything is capturable."""
         eng = self.opt.engine
         block, scene, fv = inputs
         perm = eng._trace_perm
@@ -704,38 +870,72 @@ class FusedStep:
         # the same value as the forward)
         with _override(sc, in_place=2, **clear):
             self._trace_forward(st, sc, st.row_outs)
-            if perm is None:
-                inherited = src.__getitem__
+            if isinstance(self.opt.error_function, DensityError):
+                g64 = self._density_seeds3d(st)
+                if not need_back:
+                    g64 = None
             else:
-                if st.inherited is None:
-                    st.inherited = {}
-                cache = st.inherited
-
-                def inherited(key):
-                    v = src[key]
-                    hit = cache.get(key)
-                    if hit is None or hit[0] is not v or hit[1] is not perm or hit[2] != v._version:
-                        hit = cache[key] = (v, perm, v._version, v.index_select(0, perm.long()))
-                    return hit[3]
-            leaf, e = self._rowwise_terms(st, _GEO3, inherited)
-            mask = st.row_face[:N] >= 0
-            err_sum = torch.where(mask.unsqueeze(1), e.double(), torch.zeros((), dtype=torch.float64,
-                                                                           device=dev)).sum()
-            terms = mask.sum().double() * e.shape[1]
-            with torch.no_grad():
-                st.err[0] = err_sum.detach()
-                st.err[1] = terms
-                st.err[2] = torch.where(terms > 0, err_sum.detach() / torch.clamp(terms, min=1.0),
-                                        torch.full_like(terms, float("nan")))
-                self.tests_total += st.row_passes[:N].sum() * M
-            if need_back and err_sum.requires_grad:
-                with torch.autograd.set_multithreading_enabled(False):
-                    g_rows, = torch.autograd.grad(err_sum, [leaf])
-                g64 = g_rows.to(torch.float64).contiguous()
+                g64 = self._rowwise_seeds3d(st, src, perm, need_back)
+            if g64 is not None:
                 with self._index_grads3d(sc, st, True):
                     self._trace3d_backward(st, sc, g64, g64.shape[1])
                 grads = self._parameter_gradients(*self._outs3d(fv, st, index), tap_log)
         return grads, st
+
+    def _density_seeds3d(self, st):
+        """A DensityError on the fixed-shape columns: tfrt_density_error reads ``st.rows`` and the
+        mask ``st.row_face`` and writes its two rows of the persistent seed block (the other rows
+        were zeroed when the state was made) for every column, the error into ``st.err`` and the
+        histogram into ``st.hq``.  Returns the (6, capN) seed block."""
+        erf = self.opt.error_function
+        dev = st.rows.device
+        goal = erf.goal_on(dev)
+        if st.hq is None or st.hq.shape != goal.shape:
+            nx, ny = goal.shape[-1], (goal.shape[0] if goal.dim() == 2 else 1)
+            wsb = _lib.lib().tfrt_density_error_workspace_bytes(st.N, nx, ny)
+            st.density_ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+            st.hq = torch.zeros(goal.shape, dtype=torch.int64, device=dev)
+        rows = erf.rows
+        erf.evaluate(st.rows[:, :st.N], rows[0], rows[1] if len(rows) == 2 else -1,
+                     mask=st.row_face, grad=st.g_fin, err=st.err, hq=st.hq,
+                     workspace=st.density_ws)
+        with torch.no_grad():
+            self.tests_total += st.row_passes[:st.N].sum() * st.M
+        return st.g_fin
+
+    def _rowwise_seeds3d(self, st, src, perm, need_back):
+        """A RowwiseError on the fixed-shape columns: ``fn`` and its autograd (torch), the masked
+        error sum into ``st.err``.  Returns the columns' float64 gradient, None without one."""
+        N, M, dev = st.N, st.M, st.rows.device
+        if perm is None:
+            inherited = src.__getitem__
+        else:
+            if st.inherited is None:
+                st.inherited = {}
+            cache = st.inherited
+
+            def inherited(key):
+                v = src[key]
+                hit = cache.get(key)
+                if hit is None or hit[0] is not v or hit[1] is not perm or hit[2] != v._version:
+                    hit = cache[key] = (v, perm, v._version, v.index_select(0, perm.long()))
+                return hit[3]
+        leaf, e = self._rowwise_terms(st, _GEO3, inherited)
+        mask = st.row_face[:N] >= 0
+        err_sum = torch.where(mask.unsqueeze(1), e.double(), torch.zeros((), dtype=torch.float64,
+                                                                       device=dev)).sum()
+        terms = mask.sum().double() * e.shape[1]
+        with torch.no_grad():
+            st.err[0] = err_sum.detach()
+            st.err[1] = terms
+            st.err[2] = torch.where(terms > 0, err_sum.detach() / torch.clamp(terms, min=1.0),
+                                    torch.full_like(terms, float("nan")))
+            self.tests_total += st.row_passes[:N].sum() * M
+        if need_back and err_sum.requires_grad:
+            with torch.autograd.set_multithreading_enabled(False):
+                g_rows, = torch.autograd.grad(err_sum, [leaf])
+            return g_rows.to(torch.float64).contiguous()
+        return None
 
     def _rowwise_terms(self, st, names, inherited):
         """The user's error function, row by row on every source ray's column: ``st.rows`` (a leaf
@@ -1124,7 +1324,7 @@ class FusedStep:
                 getattr(eng, "_visit_all_key", None) is not None, eng.in_place,
                 opt.update_rule == "momentum",
                 tuple(v.data_ptr() for v in opt._velocity) if opt.update_rule == "momentum" else (),
-                self._index_signature()) + self._rule_signature()
+                self._index_signature()) + self._rule_signature() + self._density_signature()
 
     def _rule_signature(self):
         """The Adam rule's part of the signature: the rule and the addresses of its state."""
@@ -1133,6 +1333,12 @@ class FusedStep:
             return ()
         return ("adam", tuple(t.data_ptr() for t in opt._adam_m + opt._adam_v),
                 opt._adam_state.data_ptr(), opt._adam_ticket.data_ptr())
+
+    def _density_signature(self):
+        """A DensityError's part of the signature: the goal buffer's address (overwriting the goal
+        in place is seen by replays, another buffer re-captures), its shape and the constants."""
+        erf = self.opt.error_function
+        return erf.graph_key() if isinstance(erf, DensityError) else ()
 
     def _index_signature(self):
         """The refractive-index fields that take a gradient (boundary, field, identity of a tensor

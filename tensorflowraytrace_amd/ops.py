@@ -1218,6 +1218,139 @@ def gather_rows(src, index, n_valid=None, out=None):
     return out.reshape(-1) if (one and out.dim() == 2) else out
 
 
+DENSITY_FIXED_ONE = 4294967296.0      # 2^32: one ray's total weight in the int64 histogram
+DENSITY_MAX_BINS = 65536
+
+
+def density_grid(domain, nx, ny=None):
+    """The domain constants tfrt_density_error takes, (x0, x1, sx, y0, y1, sy) in float64 with
+    sx = nx / (x1 - x0) computed once here; one axis: the y constants are 0."""
+    (x0, x1) = (float(v) for v in domain[0])
+    sx = float(np.float64(nx) / (np.float64(x1) - np.float64(x0)))
+    if ny is None:
+        return (x0, x1, sx, 0.0, 0.0, 0.0)
+    (y0, y1) = (float(v) for v in domain[1])
+    return (x0, x1, sx, y0, y1, float(np.float64(ny) / (np.float64(y1) - np.float64(y0))))
+
+
+def density_error(rows, row_x, row_y, goal, grid, oob_weight=0.0, mask=None, grad=None, err=None,
+                  hq=None, workspace=None, variant=0):
+    """tfrt_density_error: the DensityError of the columns of ``rows`` (k, n), x in row ``row_x``
+    and y in row ``row_y`` (-1: one field), against the L2-normalised float64 ``goal`` (ny, nx) or
+    (nx,); ``grid`` from ``density_grid``; ``mask``: optional int32, column i counts if
+    mask[i] >= 0.  Returns (err {sum, 1, mean}, grad (k, n) float64, hq int64 of the goal's
+    shape): rows ``row_x`` / ``row_y`` of ``grad`` are written for every column, other rows only
+    when ``grad`` is made here (zeros).  ``grad``, ``err``, ``hq``, ``workspace`` (uint8): buffers
+    to reuse -- with all four given a CUDA call allocates nothing.
+
+    CUDA tensors run the kernels.  CPU tensors run a torch restatement with the same int64
+    fixed-point histogram and the same operation order per ray (``hq`` and the per-ray quantities
+    agree bit for bit; the sums over bins are torch's and agree to rounding)."""
+    two = row_y >= 0
+    nx = goal.shape[-1]
+    ny = goal.shape[0] if goal.dim() == 2 else 1
+    if goal.dtype != torch.float64 or not goal.is_contiguous() or goal.dim() != (2 if two else 1):
+        raise ValueError("density_error: goal must be contiguous float64, (ny, nx) for two fields "
+                         "and (nx,) for one")
+    if nx * ny > DENSITY_MAX_BINS:
+        raise ValueError(f"density_error: more than {DENSITY_MAX_BINS} bins")
+    k, n = rows.shape
+    dev = rows.device
+    if grad is None:
+        grad = torch.zeros((k, n), dtype=torch.float64, device=dev)
+    if err is None:
+        err = torch.empty(3, dtype=torch.float64, device=dev)
+    if hq is None:
+        hq = torch.empty(goal.shape, dtype=torch.int64, device=dev)
+    x0, x1, sx, y0, y1, sy = grid
+    if not rows.is_cuda:
+        _density_error_cpu(rows, row_x, row_y, goal, grid, float(oob_weight), mask, grad, err, hq)
+        return err, grad, hq
+    _need_gpu(rows, goal, mask, grad, err, hq)
+    if rows.stride(1) != 1 or grad.stride(1) != 1:
+        raise ValueError("density_error: rows and grad must have contiguous columns")
+    L = _lib.lib()
+    wsb = L.tfrt_density_error_workspace_bytes(n, nx, ny)
+    if workspace is None:
+        workspace = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    check(L.tfrt_density_error(
+        _p(rows), rows.stride(0), n, _DT[rows.dtype], _p(mask), row_x, row_y, _p(goal), nx, ny,
+        x0, x1, sx, y0, y1, sy, float(oob_weight), _p(grad), grad.stride(0), _p(err), _p(hq),
+        int(variant), _p(workspace), workspace.numel(), _stream(rows)), "tfrt_density_error")
+    return err, grad, hq
+
+
+def _density_axis(v, lo, scale, nb):
+    u = (v - lo) * scale - 0.5
+    f = torch.floor(u)
+    i0 = f.long()
+    return i0.clamp(0, nb - 1), (i0 + 1).clamp(0, nb - 1), u - f
+
+
+def _density_error_cpu(rows, row_x, row_y, goal, grid, oob, mask, grad, err, hq):
+    """The CPU path of ``density_error`` (every torch op rounds on its own, as the kernels do)."""
+    x0, x1, sx, y0, y1, sy = grid
+    two = row_y >= 0
+    nx = goal.shape[-1]
+    n = rows.shape[1]
+    x = rows[row_x].double()
+    y = rows[row_y].double() if two else torch.zeros_like(x)
+    counts = torch.isfinite(x) & torch.isfinite(y)
+    if mask is not None:
+        counts &= mask >= 0
+    out = (x < x0) | (x > x1)
+    if two:
+        out |= (y < y0) | (y > y1)
+    inside, outside = counts & ~out, counts & out
+    zero = torch.zeros((), dtype=torch.float64)
+    # outside: the penalty and its derivative
+    ex = torch.maximum(x0 - x, zero) + torch.maximum(x - x1, zero)
+    ey = (torch.maximum(y0 - y, zero) + torch.maximum(y - y1, zero)) if two else torch.zeros_like(x)
+    pen = (oob * (ex * ex + ey * ey))[outside].sum()
+    gx = torch.where(outside, oob * (2.0 * ex) * ((x > x1).double() - (x < x0).double()), zero)
+    gy = torch.where(outside, oob * (2.0 * ey) * ((y > y1).double() - (y < y0).double()), zero) \
+        if two else None
+    # inside: the fixed-point histogram
+    xi, yi = x[inside], y[inside]
+    ia, ib, tx = _density_axis(xi, x0, sx, nx)
+    flat = hq.view(-1)
+    flat.zero_()
+
+    def splat(index, w):
+        flat.index_add_(0, index, torch.round(w * DENSITY_FIXED_ONE).long())
+    if two:
+        ja, jb, ty = _density_axis(yi, y0, sy, goal.shape[0])
+        wx0, wx1, wy0, wy1 = 1.0 - tx, tx, 1.0 - ty, ty
+        splat(ja * nx + ia, wy0 * wx0)
+        splat(ja * nx + ib, wy0 * wx1)
+        splat(jb * nx + ia, wy1 * wx0)
+        splat(jb * nx + ib, wy1 * wx1)
+    else:
+        splat(ia, 1.0 - tx)
+        splat(ib, tx)
+    H = flat.double() / DENSITY_FIXED_ONE
+    g = goal.reshape(-1)
+    s = torch.sqrt((H * H).sum())
+    if float(s) == 0.0:
+        e_hist, D = (g * g).sum(), torch.zeros_like(H)
+    else:
+        h = H / s
+        r = h - g
+        e_hist = (r * r).sum()
+        D = (2.0 / s) * (r - h * (h * r).sum())
+    if two:
+        d00, d01, d10, d11 = D[ja * nx + ia], D[ja * nx + ib], D[jb * nx + ia], D[jb * nx + ib]
+        gx[inside] = sx * ((1.0 - ty) * (d01 - d00) + ty * (d11 - d10))
+        gy[inside] = sy * ((1.0 - tx) * (d10 - d00) + tx * (d11 - d01))
+    else:
+        gx[inside] = sx * (D[ib] - D[ia])
+    grad[row_x, :n] = gx
+    if two:
+        grad[row_y, :n] = gy
+    e = e_hist + pen
+    err[0], err[1], err[2] = e, 1.0, e
+
+
 def restore_plan(ids, counts_dev, P, cls_col, perm, n_src, n_rows=None, total=None, zero=False):
     """(inv, dest_of, original ids) of one output class of a trace over permuted rays
     (tfrt_restore_order): row j of the class in the reference's order = row ``inv[j]`` of the

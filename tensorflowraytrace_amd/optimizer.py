@@ -29,7 +29,8 @@ import torch
 
 from . import distributed as tdist
 from . import ops
-from .fused_step import FusedStep, GoalError, RowwiseError, _NotInPlace  # noqa: F401  (GoalError, RowwiseError: public API)
+# (GoalError, RowwiseError, DensityError: public API)
+from .fused_step import FusedStep, GoalError, RowwiseError, DensityError, _NotInPlace  # noqa: F401
 
 
 class DeferredScalar:

@@ -7,6 +7,7 @@ kernel wrapper is not on a HIP device, the call raises.  Build the library with
 """
 import ctypes
 import os
+import typing
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TFRT_LIB_PATH") or os.path.join(HERE, "libtfrt_hip.so")
@@ -257,6 +258,29 @@ SIGNATURES = {
                                        c_vp, c_i64, c_vp]),
     "tfrt_source2d_pool_rows": (c_i32, [_P(Source2DProgram), c_vp, c_i64, c_i64, c_vp, c_vp]),
 }
+
+
+class UpdateRule(typing.NamedTuple):
+    """An update rule of the batched parameter-update launch (tfrt_update.hip), as its callers see
+    it: ``entry(n, grad, processed, param, *states, n_elements, rows, *extras, stream)``, a
+    tensor's row of the device table being {scale, clip} + ``tail``."""
+    name: str           # SGD_Optimizer.update_rule
+    entry: str          # the C entry; entry + "_finish" also finishes a pending error sum
+    tail: tuple         # optimiser attributes whose values follow {scale, clip} in a row
+    states: tuple       # optimiser attributes with one state tensor per parameter, in ABI order
+    extras: tuple       # (optimiser attribute, bytes per parameter) of the trailing device arguments
+    min_batch: int      # fewest parameter tensors the fused step gives the batched launch
+
+    @property
+    def width(self):
+        return 2 + len(self.tail)
+
+
+SGD = UpdateRule("sgd", "tfrt_sgd_process_multi", ("sgd_learning_rate",), (), (), 2)
+MOMENTUM = UpdateRule("momentum", "tfrt_sgd_momentum_multi",
+                      ("sgd_learning_rate", "momentum", "nesterov"), ("_velocity",), (), 1)
+ADAM = UpdateRule("adam", "tfrt_adam_multi", ("adam_learning_rate", "beta1", "beta2", "epsilon"),
+                  ("_adam_m", "_adam_v"), (("_adam_state", 24), ("_adam_ticket", 4)), 1)
 
 _lib = None
 

@@ -12,13 +12,27 @@
 //
 // All of it is HBM/latency bound (tens of KB per launch); one thread per element / one wave per
 // row, coalesced loads, nothing else to tune.
+#include <array>
+
 #include "tfrt_common.h"
 #include "goal_finish.h"
 
 namespace tfrt {
 
-// the reference runs these as separate multiply / subtract ops: keep them unfused
+// the reference runs these as separate multiply / subtract ops: keep them unfused.  (Everything
+// below that does arithmetic, the shared processing included, is compiled under this pragma.)
 #pragma clang fp contract(off)
+
+// optimizer.py:226-229 (tf.where(is_finite(g), g, 0)), :233 scale, :236-247 clip_by_value; the
+// processed value is also written to processed[i] where the caller wants it
+template <typename T>
+__device__ __forceinline__ T process_gradient(T g, T scale, T clip, T* processed, int64_t i) {
+  g = isfinite(g) ? g : T(0);
+  g = g * scale;
+  g = g < -clip ? -clip : (g > clip ? clip : g);
+  if (processed != nullptr) processed[i] = g;
+  return g;
+}
 
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void k_sgd_process(const T* __restrict__ grad,
@@ -33,90 +47,82 @@ __global__ __launch_bounds__(BLOCK) void k_sgd_process(const T* __restrict__ gra
     clip = static_cast<T>(hyper[1]);
     sgd_lr = static_cast<T>(hyper[2]);
   }
-  T g = grad[i];
-  // optimizer.py:226-229 (tf.where(is_finite(g), g, 0)), :233 scale, :236-247 clip_by_value
-  g = isfinite(g) ? g : T(0);
-  g = g * scale;
-  g = g < -clip ? -clip : (g > clip ? clip : g);
-  if (processed != nullptr) processed[i] = g;
+  const T g = process_gradient(grad[i], scale, clip, processed, i);
   if (param != nullptr) param[i] = param[i] - sgd_lr * g;
 }
 
 // The same for up to SGD_BATCH tensors in one launch (an optimiser with several parameter
-// tensors -- the two surfaces of a lens -- otherwise pays one ~4 us launch each per step).
+// tensors -- the two surfaces of a lens -- otherwise pays one ~4 us launch each per step), under
+// one of three update rules.  The rules share the batch, the way a thread finds its tensor and
+// element, the processing and the host launcher; a rule is a __global__ function of its own (the
+// plain one pays for no other's LDS, barrier or ticket) with its per-element apply, STATES arrays
+// of persistent per-element state and its row of `hyper`, {scale, clip, ...}, per tensor.
 constexpr int SGD_BATCH = 8;
-struct SgdBatch {
+template <int STATES>
+struct UpdateBatch {
   const double* grad[SGD_BATCH];
   double* processed[SGD_BATCH];
   double* param[SGD_BATCH];
+  double* state[STATES][SGD_BATCH];  // none | velocity | m, v
   int64_t n[SGD_BATCH];
   int32_t first_block[SGD_BATCH + 1];
   int32_t count;
 };
+// (the plain rule's kernel-argument block carries no other rule's arrays)
+static_assert(sizeof(UpdateBatch<0>) == 4 * 8 * SGD_BATCH + 4 * (SGD_BATCH + 2));
 
-__global__ __launch_bounds__(BLOCK) void k_sgd_process_multi(SgdBatch b,
-                                                             const double* __restrict__ hyper,
-                                                             tfrt_goal_pending goal) {
-  // (one workgroup more than the tensors need, when the step's error sum is still to be finished)
-  if ((int)blockIdx.x == b.first_block[SGD_BATCH]) {
-    goal_finish_block(goal);
-    return;
+// The tensor this workgroup works on (block-uniform) and, in `i`, the thread's element of it,
+// which may lie past the tensor's end; -1 in the workgroup behind the tensors' (one more than
+// they need), which finishes the step's error sum here when one is pending.
+template <int STATES>
+__device__ __forceinline__ int locate(const UpdateBatch<STATES>& b, const tfrt_goal_pending& goal,
+                                      int64_t& i) {
+  if ((int)blockIdx.x >= b.first_block[SGD_BATCH]) {
+    if (goal.partial != nullptr) goal_finish_block(goal);
+    return -1;
   }
   int k = 0;
   while (k + 1 < b.count && (int)blockIdx.x >= b.first_block[k + 1]) ++k;  // block-uniform
-  const int64_t i = (int64_t)((int)blockIdx.x - b.first_block[k]) * BLOCK + threadIdx.x;
-  if (i >= b.n[k]) return;
-  const double scale = hyper[3 * k], clip = hyper[3 * k + 1], sgd_lr = hyper[3 * k + 2];
-  double g = b.grad[k][i];
-  g = isfinite(g) ? g : 0.0;
-  g = g * scale;
-  g = g < -clip ? -clip : (g > clip ? clip : g);
-  if (b.processed[k] != nullptr) b.processed[k][i] = g;
-  if (b.param[k] != nullptr) b.param[k][i] = b.param[k][i] - sgd_lr * g;
+  i = (int64_t)((int)blockIdx.x - b.first_block[k]) * BLOCK + threadIdx.x;
+  return k;
 }
 
-// The same with the Keras SGD momentum rule (optimizer.py:128-132 with momentum assigned, the
-// generic path's SGD_Optimizer.apply_gradients): a persistent velocity per parameter element and
-// two more scalars per tensor, {scale, clip, sgd_lr, momentum, nesterov} (5 float64).
+// Plain SGD, {scale, clip, sgd_lr} per tensor: p -= lr*g (a null param: processing only).
+__global__ __launch_bounds__(BLOCK) void k_sgd_process_multi(UpdateBatch<0> b,
+                                                             const double* __restrict__ hyper,
+                                                             tfrt_goal_pending goal) {
+  int64_t i;
+  const int k = locate(b, goal, i);
+  if (k < 0 || i >= b.n[k]) return;
+  const double* h = hyper + 3 * k;
+  const double g = process_gradient(b.grad[k][i], h[0], h[1], b.processed[k], i);
+  if (b.param[k] != nullptr) b.param[k][i] = b.param[k][i] - h[2] * g;
+}
+
+// The Keras SGD momentum rule (optimizer.py:128-132 with momentum assigned, the generic path's
+// SGD_Optimizer.apply_gradients): a persistent velocity per parameter element and two more
+// scalars per tensor, {scale, clip, sgd_lr, momentum, nesterov} (5 float64).
 //   v  = m*v - lr*g;   p += nesterov ? m*v - lr*g : v
 // and, while m == 0, plain `p -= lr*g` with v left unwritten.  m is read on the device, so a
 // captured launch graph replays across momentum phases.
-struct SgdMomentumBatch {
-  const double* grad[SGD_BATCH];
-  double* processed[SGD_BATCH];
-  double* param[SGD_BATCH];
-  double* velocity[SGD_BATCH];
-  int64_t n[SGD_BATCH];
-  int32_t first_block[SGD_BATCH + 1];
-  int32_t count;
-};
-
-__global__ __launch_bounds__(BLOCK) void k_sgd_momentum_multi(SgdMomentumBatch b,
+__global__ __launch_bounds__(BLOCK) void k_sgd_momentum_multi(UpdateBatch<1> b,
                                                               const double* __restrict__ hyper,
                                                               tfrt_goal_pending goal) {
-  if ((int)blockIdx.x == b.first_block[SGD_BATCH]) {
-    goal_finish_block(goal);
-    return;
-  }
-  int k = 0;
-  while (k + 1 < b.count && (int)blockIdx.x >= b.first_block[k + 1]) ++k;  // block-uniform
-  const int64_t i = (int64_t)((int)blockIdx.x - b.first_block[k]) * BLOCK + threadIdx.x;
-  if (i >= b.n[k]) return;
+  int64_t i;
+  const int k = locate(b, goal, i);
+  if (k < 0 || i >= b.n[k]) return;
   const double* h = hyper + 5 * k;
-  const double scale = h[0], clip = h[1], sgd_lr = h[2], m = h[3];
+  const double sgd_lr = h[2], m = h[3];
   const bool nesterov = h[4] != 0.0;
-  double g = b.grad[k][i];
-  g = isfinite(g) ? g : 0.0;
-  g = g * scale;
-  g = g < -clip ? -clip : (g > clip ? clip : g);
-  if (b.processed[k] != nullptr) b.processed[k][i] = g;
+  const double g = process_gradient(b.grad[k][i], h[0], h[1], b.processed[k], i);
   double* p = b.param[k];
   if (m == 0.0) {  // optimizer.py: momentum off for this phase -- v keeps its value
     p[i] = p[i] - sgd_lr * g;
     return;
   }
-  const double v = m * b.velocity[k][i] - sgd_lr * g;
-  b.velocity[k][i] = v;
+  double* velocity = b.state[0][k];
+  const double v = m * velocity[i] - sgd_lr * g;
+  velocity[i] = v;
   p[i] = nesterov ? p[i] + (m * v - sgd_lr * g) : p[i] + v;
 }
 
@@ -134,49 +140,31 @@ __global__ __launch_bounds__(BLOCK) void k_sgd_momentum_multi(SgdMomentumBatch b
 // issued the same thread takes a ticket (an acquire-release add, device scope).  Whoever draws the
 // last ticket knows that every other workgroup's read is complete, writes {t+1, p1*beta1,
 // p2*beta2} of every tensor and puts the ticket back to 0 for the next launch.  Nothing depends on
-// the order in which workgroups run, and no workgroup ever sees the advanced value.
-struct AdamBatch {
-  const double* grad[SGD_BATCH];
-  double* processed[SGD_BATCH];
-  double* param[SGD_BATCH];
-  double* m[SGD_BATCH];
-  double* v[SGD_BATCH];
-  int64_t n[SGD_BATCH];
-  int32_t first_block[SGD_BATCH + 1];
-  int32_t count;
-  int32_t finish;  // the workgroup after the tensors' finishes `goal` (else it only takes a ticket)
-};
-
-__global__ __launch_bounds__(BLOCK) void k_adam_multi(AdamBatch b,
+// the order in which workgroups run, and no workgroup ever sees the advanced value.  (The
+// workgroup behind the tensors' takes a ticket too, also when it has no error sum to finish: it
+// is then the only one of a batch whose tensors have no elements, which still counts the step.)
+__global__ __launch_bounds__(BLOCK) void k_adam_multi(UpdateBatch<2> b,
                                                       const double* __restrict__ hyper,
-                                                      double* state, unsigned int* ticket,
-                                                      tfrt_goal_pending goal) {
-#pragma clang fp contract(off)
+                                                      tfrt_goal_pending goal, double* state,
+                                                      unsigned int* ticket) {
   __shared__ double lr_shared;
-  if ((int)blockIdx.x >= b.first_block[SGD_BATCH]) {
-    if (b.finish) goal_finish_block(goal);
-  } else {
-    int k = 0;
-    while (k + 1 < b.count && (int)blockIdx.x >= b.first_block[k + 1]) ++k;  // block-uniform
+  int64_t i;
+  const int k = locate(b, goal, i);
+  if (k >= 0) {
     const double* h = hyper + 6 * k;
     if (threadIdx.x == 0) {
       const double p1 = state[3 * k + 1] * h[3], p2 = state[3 * k + 2] * h[4];
       lr_shared = h[2] * sqrt(1.0 - p2) / (1.0 - p1);
     }
     __syncthreads();
-    const int64_t i = (int64_t)((int)blockIdx.x - b.first_block[k]) * BLOCK + threadIdx.x;
     if (i < b.n[k]) {
-      const double scale = h[0], clip = h[1], beta1 = h[3], beta2 = h[4], eps = h[5];
+      const double beta1 = h[3], beta2 = h[4], eps = h[5];
       const double lr_t = lr_shared;
-      double g = b.grad[k][i];
-      g = isfinite(g) ? g : 0.0;
-      g = g * scale;
-      g = g < -clip ? -clip : (g > clip ? clip : g);
-      if (b.processed[k] != nullptr) b.processed[k][i] = g;
-      const double m = beta1 * b.m[k][i] + (1.0 - beta1) * g;
-      const double v = beta2 * b.v[k][i] + (1.0 - beta2) * (g * g);
-      b.m[k][i] = m;
-      b.v[k][i] = v;
+      const double g = process_gradient(b.grad[k][i], h[0], h[1], b.processed[k], i);
+      const double m = beta1 * b.state[0][k][i] + (1.0 - beta1) * g;
+      const double v = beta2 * b.state[1][k][i] + (1.0 - beta2) * (g * g);
+      b.state[0][k][i] = m;
+      b.state[1][k][i] = v;
       double* p = b.param[k];
       p[i] = p[i] - lr_t * m / (sqrt(v) + eps);
     }
@@ -187,9 +175,9 @@ __global__ __launch_bounds__(BLOCK) void k_adam_multi(AdamBatch b,
   const unsigned int t =
       __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
   if (t != gridDim.x - 1) return;
-  for (int k = 0; k < b.count; ++k) {
-    double* s = state + 3 * k;
-    const double t1 = s[0] + 1.0, p1 = s[1] * hyper[6 * k + 3], p2 = s[2] * hyper[6 * k + 4];
+  for (int j = 0; j < b.count; ++j) {
+    double* s = state + 3 * j;
+    const double t1 = s[0] + 1.0, p1 = s[1] * hyper[6 * j + 3], p2 = s[2] * hyper[6 * j + 4];
     s[0] = t1;
     s[1] = p1;
     s[2] = p2;
@@ -216,6 +204,54 @@ __global__ __launch_bounds__(BLOCK) void k_csr_matvec(const int64_t* __restrict_
 }  // namespace tfrt
 
 using namespace tfrt;
+
+static bool pending_ok(const tfrt_goal_pending* p) {
+  return p == nullptr || (p->partial && (p->n_finished || p->partial_counts) && p->error_out &&
+                          p->n_partial >= 0);
+}
+
+// Validates, fills the batch and launches a rule's kernel over it, with one more workgroup when
+// `pending` is to be finished.  A rule with state arrays needs its parameters (the plain one may
+// only process); `extra` are a rule's further device arguments, Adam's step state and ticket.
+template <int STATES, typename... Extra>
+static int update_launch(void (*kernel)(UpdateBatch<STATES>, const double*, tfrt_goal_pending,
+                                        Extra...),
+                         int32_t n_tensors, const void* const* grad, void* const* processed,
+                         void* const* param, std::array<void* const*, STATES> state,
+                         const int64_t* n, const double* hyper, const tfrt_goal_pending* pending,
+                         void* stream, Extra... extra) {
+  bool have = grad && n && hyper && (STATES == 0 || param) && (... && (extra != nullptr));
+  for (void* const* s : state) have = have && s;
+  if (n_tensors < 0 || n_tensors > SGD_BATCH || (n_tensors > 0 && !have) || !pending_ok(pending))
+    return TFRT_E_BADARG;
+  UpdateBatch<STATES> b;
+  int blocks = 0;
+  for (int k = 0; k < SGD_BATCH; ++k) {
+    const bool on = k < n_tensors;
+    bool ok = !on || n[k] == 0 || (n[k] > 0 && grad[k] && (STATES == 0 || param[k]));
+    b.grad[k] = on ? static_cast<const double*>(grad[k]) : nullptr;
+    b.processed[k] = (on && processed) ? static_cast<double*>(processed[k]) : nullptr;
+    b.param[k] = (on && param) ? static_cast<double*>(param[k]) : nullptr;
+    for (int s = 0; s < STATES; ++s) {
+      b.state[s][k] = on ? static_cast<double*>(state[s][k]) : nullptr;
+      ok = ok && (!on || n[k] == 0 || b.state[s][k]);
+    }
+    if (!ok) return TFRT_E_BADARG;
+    b.n[k] = on ? n[k] : 0;
+    b.first_block[k] = blocks;
+    if (on) blocks += cdiv(n[k], BLOCK);
+  }
+  b.first_block[SGD_BATCH] = blocks;
+  b.count = n_tensors;
+  // (Adam: tensors without elements still count the step, in one workgroup that only takes the
+  // ticket)
+  const bool ticket_only = sizeof...(Extra) > 0 && blocks == 0 && n_tensors > 0;
+  const int grid = blocks + ((pending != nullptr || ticket_only) ? 1 : 0);
+  if (grid == 0) return 0;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), b,
+                     hyper, pending != nullptr ? *pending : tfrt_goal_pending{}, extra...);
+  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+}
 
 extern "C" {
 
@@ -252,41 +288,11 @@ int tfrt_sgd_process_dev(const void* grad, void* processed, void* param, int64_t
   return sgd_process_launch(grad, processed, param, n, dtype, 0.0, 0.0, 0.0, hyper, stream);
 }
 
-static int sgd_multi_launch(int32_t n_tensors, const void* const* grad, void* const* processed,
-                            void* const* param, const int64_t* n, const double* hyper,
-                            const tfrt_goal_pending* pending, void* stream) {
-  if (n_tensors < 0 || n_tensors > SGD_BATCH || (n_tensors > 0 && (!grad || !n || !hyper)))
-    return TFRT_E_BADARG;
-  if (pending != nullptr && (!pending->partial || (!pending->n_finished && !pending->partial_counts) ||
-      !pending->error_out ||
-                             pending->n_partial < 0))
-    return TFRT_E_BADARG;
-  SgdBatch b;
-  int blocks = 0;
-  for (int k = 0; k < SGD_BATCH; ++k) {
-    const bool on = k < n_tensors;
-    if (on && (n[k] < 0 || (n[k] > 0 && !grad[k]))) return TFRT_E_BADARG;
-    b.grad[k] = on ? static_cast<const double*>(grad[k]) : nullptr;
-    b.processed[k] = (on && processed) ? static_cast<double*>(processed[k]) : nullptr;
-    b.param[k] = (on && param) ? static_cast<double*>(param[k]) : nullptr;
-    b.n[k] = on ? n[k] : 0;
-    b.first_block[k] = blocks;
-    if (on) blocks += cdiv(n[k], BLOCK);
-  }
-  b.first_block[SGD_BATCH] = blocks;
-  b.count = n_tensors;
-  const int grid = blocks + (pending != nullptr ? 1 : 0);
-  if (grid == 0) return 0;
-  hipLaunchKernelGGL(k_sgd_process_multi, dim3(grid), dim3(BLOCK), 0,
-                     static_cast<hipStream_t>(stream), b, hyper,
-                     pending != nullptr ? *pending : tfrt_goal_pending{});
-  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
-}
-
 int tfrt_sgd_process_multi(int32_t n_tensors, const void* const* grad, void* const* processed,
                            void* const* param, const int64_t* n, const double* hyper,
                            void* stream) {
-  return sgd_multi_launch(n_tensors, grad, processed, param, n, hyper, nullptr, stream);
+  return update_launch<0>(k_sgd_process_multi, n_tensors, grad, processed, param, {}, n, hyper,
+                          nullptr, stream);
 }
 
 int tfrt_sgd_process_multi_finish(int32_t n_tensors, const void* const* grad,
@@ -294,49 +300,15 @@ int tfrt_sgd_process_multi_finish(int32_t n_tensors, const void* const* grad,
                                   const double* hyper, const tfrt_goal_pending* pending,
                                   void* stream) {
   if (!pending) return TFRT_E_BADARG;
-  return sgd_multi_launch(n_tensors, grad, processed, param, n, hyper, pending, stream);
-}
-
-static int sgd_momentum_launch(int32_t n_tensors, const void* const* grad,
-                               void* const* processed, void* const* param, void* const* velocity,
-                               const int64_t* n, const double* hyper,
-                               const tfrt_goal_pending* pending, void* stream) {
-  if (n_tensors < 0 || n_tensors > SGD_BATCH ||
-      (n_tensors > 0 && (!grad || !param || !velocity || !n || !hyper)))
-    return TFRT_E_BADARG;
-  if (pending != nullptr &&
-      (!pending->partial || (!pending->n_finished && !pending->partial_counts) ||
-       !pending->error_out || pending->n_partial < 0))
-    return TFRT_E_BADARG;
-  SgdMomentumBatch b;
-  int blocks = 0;
-  for (int k = 0; k < SGD_BATCH; ++k) {
-    const bool on = k < n_tensors;
-    if (on && (n[k] < 0 || (n[k] > 0 && (!grad[k] || !param[k] || !velocity[k]))))
-      return TFRT_E_BADARG;
-    b.grad[k] = on ? static_cast<const double*>(grad[k]) : nullptr;
-    b.processed[k] = (on && processed) ? static_cast<double*>(processed[k]) : nullptr;
-    b.param[k] = on ? static_cast<double*>(param[k]) : nullptr;
-    b.velocity[k] = on ? static_cast<double*>(velocity[k]) : nullptr;
-    b.n[k] = on ? n[k] : 0;
-    b.first_block[k] = blocks;
-    if (on) blocks += cdiv(n[k], BLOCK);
-  }
-  b.first_block[SGD_BATCH] = blocks;
-  b.count = n_tensors;
-  const int grid = blocks + (pending != nullptr ? 1 : 0);
-  if (grid == 0) return 0;
-  hipLaunchKernelGGL(k_sgd_momentum_multi, dim3(grid), dim3(BLOCK), 0,
-                     static_cast<hipStream_t>(stream), b, hyper,
-                     pending != nullptr ? *pending : tfrt_goal_pending{});
-  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  return update_launch<0>(k_sgd_process_multi, n_tensors, grad, processed, param, {}, n, hyper,
+                          pending, stream);
 }
 
 int tfrt_sgd_momentum_multi(int32_t n_tensors, const void* const* grad, void* const* processed,
                             void* const* param, void* const* velocity, const int64_t* n,
                             const double* hyper, void* stream) {
-  return sgd_momentum_launch(n_tensors, grad, processed, param, velocity, n, hyper, nullptr,
-                             stream);
+  return update_launch<1>(k_sgd_momentum_multi, n_tensors, grad, processed, param, {velocity}, n,
+                          hyper, nullptr, stream);
 }
 
 int tfrt_sgd_momentum_multi_finish(int32_t n_tensors, const void* const* grad,
@@ -344,52 +316,15 @@ int tfrt_sgd_momentum_multi_finish(int32_t n_tensors, const void* const* grad,
                                    void* const* velocity, const int64_t* n, const double* hyper,
                                    const tfrt_goal_pending* pending, void* stream) {
   if (!pending) return TFRT_E_BADARG;
-  return sgd_momentum_launch(n_tensors, grad, processed, param, velocity, n, hyper, pending,
-                             stream);
-}
-
-static int adam_launch(int32_t n_tensors, const void* const* grad, void* const* processed,
-                       void* const* param, void* const* m, void* const* v, const int64_t* n,
-                       const double* hyper, double* state, uint32_t* ticket,
-                       const tfrt_goal_pending* pending, void* stream) {
-  if (n_tensors < 0 || n_tensors > SGD_BATCH ||
-      (n_tensors > 0 && (!grad || !param || !m || !v || !n || !hyper || !state || !ticket)))
-    return TFRT_E_BADARG;
-  if (pending != nullptr &&
-      (!pending->partial || (!pending->n_finished && !pending->partial_counts) ||
-       !pending->error_out || pending->n_partial < 0))
-    return TFRT_E_BADARG;
-  AdamBatch b;
-  int blocks = 0;
-  for (int k = 0; k < SGD_BATCH; ++k) {
-    const bool on = k < n_tensors;
-    if (on && (n[k] < 0 || (n[k] > 0 && (!grad[k] || !param[k] || !m[k] || !v[k]))))
-      return TFRT_E_BADARG;
-    b.grad[k] = on ? static_cast<const double*>(grad[k]) : nullptr;
-    b.processed[k] = (on && processed) ? static_cast<double*>(processed[k]) : nullptr;
-    b.param[k] = on ? static_cast<double*>(param[k]) : nullptr;
-    b.m[k] = on ? static_cast<double*>(m[k]) : nullptr;
-    b.v[k] = on ? static_cast<double*>(v[k]) : nullptr;
-    b.n[k] = on ? n[k] : 0;
-    b.first_block[k] = blocks;
-    if (on) blocks += cdiv(n[k], BLOCK);
-  }
-  b.first_block[SGD_BATCH] = blocks;
-  b.count = n_tensors;
-  b.finish = pending != nullptr ? 1 : 0;
-  // (tensors without elements still count the step: one workgroup that only takes the ticket)
-  const int grid = blocks + ((pending != nullptr || (blocks == 0 && n_tensors > 0)) ? 1 : 0);
-  if (grid == 0) return 0;
-  hipLaunchKernelGGL(k_adam_multi, dim3(grid), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), b,
-                     hyper, state, ticket, pending != nullptr ? *pending : tfrt_goal_pending{});
-  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  return update_launch<1>(k_sgd_momentum_multi, n_tensors, grad, processed, param, {velocity}, n,
+                          hyper, pending, stream);
 }
 
 int tfrt_adam_multi(int32_t n_tensors, const void* const* grad, void* const* processed,
                     void* const* param, void* const* m, void* const* v, const int64_t* n,
                     const double* hyper, double* state, uint32_t* ticket, void* stream) {
-  return adam_launch(n_tensors, grad, processed, param, m, v, n, hyper, state, ticket, nullptr,
-                     stream);
+  return update_launch<2>(k_adam_multi, n_tensors, grad, processed, param, {m, v}, n, hyper,
+                          nullptr, stream, state, ticket);
 }
 
 int tfrt_adam_multi_finish(int32_t n_tensors, const void* const* grad, void* const* processed,
@@ -397,8 +332,8 @@ int tfrt_adam_multi_finish(int32_t n_tensors, const void* const* grad, void* con
                            const double* hyper, double* state, uint32_t* ticket,
                            const tfrt_goal_pending* pending, void* stream) {
   if (!pending) return TFRT_E_BADARG;
-  return adam_launch(n_tensors, grad, processed, param, m, v, n, hyper, state, ticket, pending,
-                     stream);
+  return update_launch<2>(k_adam_multi, n_tensors, grad, processed, param, {m, v}, n, hyper,
+                          pending, stream, state, ticket);
 }
 
 int tfrt_csr_matvec(const int64_t* crow_indices, const int64_t* col_indices, const double* values,

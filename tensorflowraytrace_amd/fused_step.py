@@ -1159,73 +1159,60 @@ class FusedStep:
         opt = self.opt
         L = _lib.lib()
         k = len(grads)
-        rule = opt.update_rule
-        momentum, adam = rule == "momentum", rule == "adam"
-        # (the plain rule takes one launch for all parameter tensors from two of them on, the
-        # momentum and Adam rules from one on)
-        batched = (k > (0 if momentum or adam else 1) and k <= 8
-                   and all(a is None for a in accumulators)
+        rule = opt._rule
+        batched = (rule.min_batch <= k <= 8 and all(a is None for a in accumulators)
                    and len({ops._stream(p).value for p in opt.parameters}) == 1)
         pending, self._goal_pending = self._goal_pending, None
 
         def arr(ts, ctype=ctypes.c_void_p):
             return (ctype * len(ts))(*ts)
+
+        def launch(idx, gs, row, stream, *finish):
+            """The rule's entry over parameters ``idx`` (consecutive ones) with gradients ``gs``;
+            ``row``: address of the first one's row; ``finish``: the pending sum to finish."""
+            name = rule.entry + ("_finish" if finish else "")
+            check(getattr(L, name)(
+                len(gs), arr([g.data_ptr() for g in gs]), None,
+                arr([opt.parameters[i].data_ptr() for i in idx]),
+                *[arr([getattr(opt, a)[i].data_ptr() for i in idx]) for a in rule.states],
+                arr([g.numel() for g in gs], ctypes.c_int64), ctypes.c_void_p(row),
+                *[ctypes.c_void_p(getattr(opt, a).data_ptr() + stride * idx[0])
+                  for a, stride in rule.extras], *finish, stream), name)
         hyper, row_bytes = self._hyper.dev.data_ptr(), 8 * self._hyper.width
         with torch.no_grad():
             if batched:
                 # every parameter tensor in one launch (the device table holds the scalars of
                 # parameter i in row i), which also finishes the error sum left on its stream
                 stream = ops._stream(opt.parameters[0])
-                name = {"sgd": "tfrt_sgd_process_multi", "momentum": "tfrt_sgd_momentum_multi",
-                        "adam": "tfrt_adam_multi"}[rule]
-                args = [k, arr([g.data_ptr() for g in grads]), None,
-                        arr([p.data_ptr() for p in opt.parameters]),
-                        arr([g.numel() for g in grads], ctypes.c_int64), ctypes.c_void_p(hyper)]
-                if momentum:
-                    args.insert(4, arr([v.data_ptr() for v in opt._velocity]))
-                if adam:
-                    args[4:4] = [arr([m.data_ptr() for m in opt._adam_m]),
-                                 arr([v.data_ptr() for v in opt._adam_v])]
-                    args += [ops._p(opt._adam_state), ops._p(opt._adam_ticket)]
                 if pending is not None and pending[1].value == stream.value:
-                    check(getattr(L, name + "_finish")(*args, ctypes.byref(pending[0]), stream),
-                          name + "_finish")
+                    launch(range(k), grads, hyper, stream, ctypes.byref(pending[0]))
                     return
                 if pending is not None:      # (recorded on another stream: finished on its own)
                     self._goal_finish(*pending)
-                check(getattr(L, name)(*args, stream), name)
+                launch(range(k), grads, hyper, stream)
                 return
             if pending is not None:
                 self._goal_finish(*pending)
             for i, (g, p) in enumerate(zip(grads, opt.parameters)):
                 stream = ops._stream(p)
-                row = ctypes.c_void_p(hyper + row_bytes * i)
+                row = hyper + row_bytes * i
                 if accumulators[i] is not None:
                     # (the row's first three scalars: tfrt_sgd_process_dev reads no further)
                     processed = torch.empty_like(g)
                     check(L.tfrt_sgd_process_dev(ops._p(g), ops._p(processed), None, g.numel(),
-                                                 _lib.F64, row, stream), "tfrt_sgd_process_dev")
+                                                 _lib.F64, ctypes.c_void_p(row), stream),
+                          "tfrt_sgd_process_dev")
                     g = opt._matrix_product(opt._acc_cache, i, accumulators[i],
                                             processed).contiguous()
-                    row = ctypes.c_void_p(self._hyper_apply.dev.data_ptr() + row_bytes * i)
-                if momentum:
-                    check(L.tfrt_sgd_momentum_multi(
-                        1, arr([g.data_ptr()]), None, arr([p.data_ptr()]),
-                        arr([opt._velocity[i].data_ptr()]), arr([g.numel()], ctypes.c_int64), row,
-                        stream), "tfrt_sgd_momentum_multi")
-                elif adam:
-                    # (row i of the state and a ticket of its own: parameters may sit on
-                    # different streams)
-                    check(L.tfrt_adam_multi(
-                        1, arr([g.data_ptr()]), None, arr([p.data_ptr()]),
-                        arr([opt._adam_m[i].data_ptr()]), arr([opt._adam_v[i].data_ptr()]),
-                        arr([g.numel()], ctypes.c_int64), row,
-                        ctypes.c_void_p(opt._adam_state.data_ptr() + 24 * i),
-                        ctypes.c_void_p(opt._adam_ticket.data_ptr() + 4 * i), stream),
-                        "tfrt_adam_multi")
-                else:
+                    row = self._hyper_apply.dev.data_ptr() + row_bytes * i
+                if rule is _lib.SGD:
                     check(L.tfrt_sgd_process_dev(ops._p(g), None, ops._p(p), g.numel(), _lib.F64,
-                                                 row, stream), "tfrt_sgd_process_dev")
+                                                 ctypes.c_void_p(row), stream),
+                          "tfrt_sgd_process_dev")
+                else:
+                    # (a one-tensor batch; its row of the rule's state and a ticket of its own:
+                    # parameters may sit on different streams)
+                    launch([i], [g], row, stream)
 
     def _fix_grads(self, grads):
         opt = self.opt
@@ -1288,22 +1275,16 @@ class FusedStep:
 
     # ------------------------------------------------------------------------------ step
     def _hyper_rows(self, lr_scale):
+        # (the rule's own values -- the phase's momentum, the Adam rates -- ride in the table too:
+        # a phase change or a reassignment replays)
         opt = self.opt
         rows, apply_rows = [], []
-        # (momentum rule: the phase's momentum rides in the table, so a phase change replays)
-        rule = opt.update_rule
-        if rule == "adam":          # (the Adam values ride there too: reassigning them replays)
-            tail = opt._adam_tail()
-        else:
-            tail = (float(opt.sgd_learning_rate),)
-            if rule == "momentum":
-                tail += (float(opt.momentum), 1.0 if opt.nesterov else 0.0)
         for i in range(len(opt.parameters)):
             scale = float(lr_scale * opt.individual_lr[i] * opt.learning_rate)
             clip = float(opt.grad_clip if opt.clip_mode == "common" else
                          opt.individual_lr[i] * opt.clip_scale * opt.learning_rate * lr_scale)
-            rows.append((scale, clip) + tail)
-            apply_rows.append((1.0, float("inf")) + tail)
+            rows.append(opt._kernel_row(scale, clip))
+            apply_rows.append(opt._kernel_row(1.0, float("inf")))
         return tuple(rows), tuple(apply_rows)
 
     def _signature(self, accumulators):
@@ -1322,17 +1303,13 @@ class FusedStep:
                 tdist.world_size(), eng.optical_system.scene_signature(), bool(eng.deterministic),
                 id((getattr(eng, "_order_cache", None) or (None, None, None))[2]),
                 getattr(eng, "_visit_all_key", None) is not None, eng.in_place,
-                opt.update_rule == "momentum",
-                tuple(v.data_ptr() for v in opt._velocity) if opt.update_rule == "momentum" else (),
                 self._index_signature()) + self._rule_signature() + self._density_signature()
 
     def _rule_signature(self):
-        """The Adam rule's part of the signature: the rule and the addresses of its state."""
-        opt = self.opt
-        if opt.update_rule != "adam":
-            return ()
-        return ("adam", tuple(t.data_ptr() for t in opt._adam_m + opt._adam_v),
-                opt._adam_state.data_ptr(), opt._adam_ticket.data_ptr())
+        """The update rule's part of the signature: the rule and the addresses of its state."""
+        opt, rule = self.opt, self.opt._rule
+        return (rule.name, tuple(t.data_ptr() for a in rule.states for t in getattr(opt, a)),
+                tuple(getattr(opt, a).data_ptr() for a, _ in rule.extras))
 
     def _density_signature(self):
         """A DensityError's part of the signature: the goal buffer's address (overwriting the goal
@@ -1362,16 +1339,13 @@ class FusedStep:
         opt = self.opt
         dev = opt.parameters[0].device
         world = 2 if tdist.is_distributed() else 1      # > 1: the collective splits the sequence
-        width = {"sgd": 3, "momentum": 5, "adam": 6}[opt.update_rule]
+        width = opt._rule.width
         if self._hyper is None or self._hyper.width != width:
             # (a captured graph reads the table it was captured with: a new one invalidates it)
             self._graphs = None
             self._hyper = _HyperTable(len(opt.parameters), dev, width=width)
             self._hyper_apply = _HyperTable(len(opt.parameters), dev, width=width)
-        if opt.update_rule == "momentum":
-            opt._velocities()        # allocated before the first capture, updated in place after
-        elif opt.update_rule == "adam":
-            opt._adam_buffers()
+        opt._state_buffers()         # allocated before the first capture, updated in place after
         rows, apply_rows = self._hyper_rows(lr_scale)
         self._hyper.set(rows)
         self._hyper_apply.set(apply_rows)

@@ -516,35 +516,41 @@ def sgd_process(grad, scale, clip, param=None, sgd_learning_rate=0.0):
     return out
 
 
+def _update(rule, fn, what, grads, params, states, rows, processed, extras=(), extras_error=None):
+    """``rule``'s launch (an _lib.UpdateRule) over any number of float64 tensors, eight at a time.
+    ``extras``: (tensor, bytes per tensor) of its trailing device arguments."""
+    k = len(grads)
+    lists = [grads, params, *states] + ([] if processed is None else [processed])
+    if any(len(ts) != k for ts in lists + [rows]):
+        raise TfrtError(f"{fn}: one gradient, parameter, {what} and row per tensor")
+    if k == 0:
+        return
+    _need_gpu(*grads, *params, *[t for ts in states for t in ts], *[t for t, _ in extras])
+    for per_tensor in zip(*lists):
+        if any(t.dtype != torch.float64 or not t.is_contiguous() or t.shape != per_tensor[0].shape
+               for t in per_tensor):
+            raise TfrtError(f"{fn}: contiguous float64 tensors of one shape per parameter")
+    if extras_error is not None:
+        raise TfrtError(extras_error)
+    hyper = torch.tensor(rows, dtype=torch.float64).to(grads[0].device)
+    entry = getattr(_lib.lib(), rule.entry)
+    stream = _stream(params[0])
+    for lo in range(0, k, 8):
+        g, p, *more = [_ptr_array(ts[lo:lo + 8])[1] for ts in lists]
+        done = None if processed is None else more.pop()
+        n = [t.numel() for t in grads[lo:lo + 8]]
+        check(entry(len(n), g, done, p, *more, (ctypes.c_int64 * len(n))(*n),
+                    ctypes.c_void_p(hyper.data_ptr() + 8 * rule.width * lo),
+                    *[ctypes.c_void_p(t.data_ptr() + stride * lo) for t, stride in extras], stream),
+              rule.entry)
+
+
 def sgd_momentum(grads, params, velocities, rows, processed=None):
     """optimizer.py:223-247 and the Keras SGD momentum apply for float64 tensors, up to eight per
     launch (tfrt_sgd_momentum_multi): ``rows[k] = (scale, clip, sgd_learning_rate, momentum,
     nesterov)``.  Updates ``params`` and ``velocities`` in place (``velocities`` untouched while
     momentum is 0); writes the processed gradients into ``processed`` if given."""
-    k = len(grads)
-    if not (k == len(params) == len(velocities) == len(rows)) or \
-            (processed is not None and len(processed) != k):
-        raise TfrtError("sgd_momentum: one gradient, parameter, velocity and row per tensor")
-    if k == 0:
-        return
-    _need_gpu(*grads, *params, *velocities)
-    for i, (g, p, v) in enumerate(zip(grads, params, velocities)):
-        outs = (g, p, v) if processed is None else (g, p, v, processed[i])
-        if any(t.dtype != torch.float64 or not t.is_contiguous() or t.shape != g.shape
-               for t in outs):
-            raise TfrtError("sgd_momentum: contiguous float64 tensors of one shape per parameter")
-    hyper = torch.tensor(rows, dtype=torch.float64).to(grads[0].device)
-    L = _lib.lib()
-    stream = _stream(params[0])
-    for lo in range(0, k, 8):
-        hi = min(lo + 8, k)
-
-        def ptrs(ts):
-            return (ctypes.c_void_p * (hi - lo))(*[t.data_ptr() for t in ts[lo:hi]])
-        check(L.tfrt_sgd_momentum_multi(
-            hi - lo, ptrs(grads), None if processed is None else ptrs(processed), ptrs(params),
-            ptrs(velocities), (ctypes.c_int64 * (hi - lo))(*[g.numel() for g in grads[lo:hi]]),
-            ctypes.c_void_p(hyper.data_ptr() + 40 * lo), stream), "tfrt_sgd_momentum_multi")
+    _update(_lib.MOMENTUM, "sgd_momentum", "velocity", grads, params, [velocities], rows, processed)
 
 
 def adam(grads, params, ms, vs, rows, state, ticket, processed=None):
@@ -553,34 +559,12 @@ def adam(grads, params, ms, vs, rows, state, ticket, processed=None):
     ``state`` the (k, 3) float64 {t, p1, p2} of these tensors and ``ticket`` one zeroed int32, both
     on the device.  Updates ``params``, ``ms``, ``vs`` and ``state`` in place; writes the processed
     gradients into ``processed`` if given."""
-    k = len(grads)
-    if not (k == len(params) == len(ms) == len(vs) == len(rows)) or \
-            (processed is not None and len(processed) != k):
-        raise TfrtError("adam: one gradient, parameter, m, v and row per tensor")
-    if k == 0:
-        return
-    _need_gpu(*grads, *params, *ms, *vs, state, ticket)
-    for i, (g, p, m, v) in enumerate(zip(grads, params, ms, vs)):
-        outs = (g, p, m, v) if processed is None else (g, p, m, v, processed[i])
-        if any(t.dtype != torch.float64 or not t.is_contiguous() or t.shape != g.shape
-               for t in outs):
-            raise TfrtError("adam: contiguous float64 tensors of one shape per parameter")
-    if (state.dtype != torch.float64 or tuple(state.shape) != (k, 3) or not state.is_contiguous()
-            or ticket.dtype != torch.int32 or ticket.numel() < 1):
-        raise TfrtError("adam: state is (n_tensors, 3) float64, ticket one int32")
-    hyper = torch.tensor(rows, dtype=torch.float64).to(grads[0].device)
-    L = _lib.lib()
-    stream = _stream(params[0])
-    for lo in range(0, k, 8):
-        hi = min(lo + 8, k)
-
-        def ptrs(ts):
-            return (ctypes.c_void_p * (hi - lo))(*[t.data_ptr() for t in ts[lo:hi]])
-        check(L.tfrt_adam_multi(
-            hi - lo, ptrs(grads), None if processed is None else ptrs(processed), ptrs(params),
-            ptrs(ms), ptrs(vs), (ctypes.c_int64 * (hi - lo))(*[g.numel() for g in grads[lo:hi]]),
-            ctypes.c_void_p(hyper.data_ptr() + 48 * lo), ctypes.c_void_p(state.data_ptr() + 24 * lo),
-            _p(ticket), stream), "tfrt_adam_multi")
+    ok = (state.dtype == torch.float64 and tuple(state.shape) == (len(grads), 3)
+          and state.is_contiguous() and ticket.dtype == torch.int32 and ticket.numel() >= 1)
+    # (the launches of one call run one after the other on one stream: one ticket word for all)
+    _update(_lib.ADAM, "adam", "m, v", grads, params, [ms, vs], rows, processed,
+            extras=((state, _lib.ADAM.extras[0][1]), (ticket, 0)),
+            extras_error=None if ok else "adam: state is (n_tensors, 3) float64, ticket one int32")
 
 
 class CsrMatrix:

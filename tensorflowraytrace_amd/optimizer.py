@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import distributed as tdist
-from . import ops
+from . import _lib, ops
 # (GoalError, RowwiseError, DensityError: public API)
 from .fused_step import FusedStep, GoalError, RowwiseError, DensityError, _NotInPlace  # noqa: F401
 
@@ -199,41 +199,47 @@ class SGD_Optimizer:
                 "parameters.") from e
         self._individual_lr = val
 
-    def _velocities(self):
+    def _state_buffers(self):
         """The velocity buffers of the momentum rule: zero-initialised once per parameter and
         updated in place from then on (a captured launch graph keeps their addresses)."""
+        if not self.apply_momentum:
+            return
         for i, p in enumerate(self.parameters):
             v = self._velocity[i]
             if v is None or v.shape != p.shape or v.dtype != p.dtype or v.device != p.device:
                 self._velocity[i] = torch.zeros(p.shape, dtype=p.dtype, device=p.device)
-        return self._velocity
 
-    def _momentum_kernel(self, p, g):
-        """Whether the momentum update of ``p`` by ``g`` runs in tfrt_sgd_momentum_multi (float64
-        on the device) rather than as eager torch ops."""
+    def _in_kernel(self, p, g):
+        """Whether the update of ``p`` by ``g`` runs in the rule's batched launch (float64 on the
+        device) rather than as eager torch ops."""
         return (p.is_cuda and p.dtype == torch.float64 and g.dtype == torch.float64
                 and p.is_contiguous() and p.shape == g.shape)
 
-    def _momentum_row(self, scale, clip):
-        return (float(scale), float(clip), float(self.sgd_learning_rate), float(self._momentum),
-                1.0 if self.nesterov else 0.0)
+    # The update rule, as the fused step and the processing below see it: its description (name,
+    # C entry, layout of its row of the device table and of its state), whether this step is plain
+    # ``p -= lr*g`` (applied inside the processing kernel), a tensor's row and the launch that
+    # processes and applies a batch of tensors in one go.
+    @property
+    def _rule(self):
+        return _lib.MOMENTUM if self.apply_momentum else _lib.SGD
 
-    # The update rule, as the fused step and the processing below see it: its name, whether this
-    # step is plain ``p -= lr*g`` (applied inside the processing kernel), its row of the device
-    # table and the launch that processes and applies a batch of tensors in one go.
     @property
     def update_rule(self):
-        return "momentum" if self.apply_momentum else "sgd"
+        return self._rule.name
 
     def _plain_sgd(self):
         return not (self.apply_momentum and self._momentum > 0.0)
 
-    _kernel_row = _momentum_row
+    def _rule_tail(self):
+        return tuple(float(getattr(self, a)) for a in self._rule.tail)
+
+    def _kernel_row(self, scale, clip):
+        return (float(scale), float(clip)) + self._rule_tail()
 
     def _kernel_apply(self, idx, grads, rows, processed=None):
-        vel = self._velocities()
-        ops.sgd_momentum(grads, [self.parameters[i] for i in idx], [vel[i] for i in idx], rows,
-                         processed=processed)
+        self._state_buffers()
+        ops.sgd_momentum(grads, [self.parameters[i] for i in idx],
+                         [self._velocity[i] for i in idx], rows, processed=processed)
 
     def _enter_phase(self, phase):
         """training_routine: called with the running phase dict when a phase begins."""
@@ -344,7 +350,7 @@ class SGD_Optimizer:
             fuse = (apply and plain_sgd and accumulators[i] is None and p.is_contiguous()
                     and p.dtype == grad.dtype and p.shape == grad.shape)
             if (apply and not plain_sgd and accumulators[i] is None
-                    and self._momentum_kernel(p, grad)):
+                    and self._in_kernel(p, grad)):
                 grad = grad.contiguous()
                 batch.append((i, grad, torch.empty_like(grad), self._kernel_row(scale, clp)))
                 processed.append(batch[-1][2])
@@ -386,28 +392,30 @@ class SGD_Optimizer:
                 parameters.copy_(entry[1].matvec(parameters.detach()))
 
     def apply_gradients(self, grads, skip=None):
-        momentum = self.apply_momentum and self._momentum > 0.0
-        vel = self._velocities() if momentum else None
-        batch = []      # (device float64: one tfrt_sgd_momentum_multi launch, rows {1, inf, ...})
+        plain = self._plain_sgd()
+        if not plain:
+            self._state_buffers()
+        batch = []      # (device float64: one launch of the rule's kernel, rows {1, inf, ...})
         with torch.no_grad():
             for i, (g, p) in enumerate(zip(grads, self.parameters)):
                 if skip is not None and skip[i]:
-                    continue  # already applied by the fused processing kernel
-                lr = self.sgd_learning_rate
-                if momentum:
-                    if self._momentum_kernel(p, g):
-                        batch.append((i, g.contiguous()))
-                        continue
-                    m, v = self._momentum, vel[i]
-                    v.copy_(m * v - lr * g)
-                    # Nesterov form used by Keras, or the classical one
-                    p.add_(m * v - lr * g if self.nesterov else v)
+                    continue  # already applied by the launch of the processing
+                if plain:
+                    p.add_(g, alpha=-self.sgd_learning_rate)
+                elif self._in_kernel(p, g):
+                    batch.append((i, g.contiguous()))
                 else:
-                    p.add_(g, alpha=-lr)
+                    self._eager_apply(i, g, p)
             if batch:
-                row = self._momentum_row(1.0, float("inf"))
+                row = self._kernel_row(1.0, float("inf"))
                 self._kernel_apply([i for i, _ in batch], [g for _, g in batch],
                                    [row] * len(batch))
+
+    def _eager_apply(self, i, g, p):
+        lr, m, v = self.sgd_learning_rate, self._momentum, self._velocity[i]
+        v.copy_(m * v - lr * g)
+        # Nesterov form used by Keras, or the classical one
+        p.add_(m * v - lr * g if self.nesterov else v)
 
     def single_step(self, accumulators, *args, lr_scale=1.0, momentum=0.0, verbose=False,
                     **kwargs):
@@ -523,12 +531,12 @@ class Adam_Optimizer(SGD_Optimizer):
         self._adam_state = None     # (n_parameters, 3) {t, p1, p2}
         self._adam_ticket = None    # one zeroed word per parameter for the update launches
 
-    update_rule = "adam"
+    _rule = _lib.ADAM
 
     def _plain_sgd(self):
         return False
 
-    def _adam_buffers(self):
+    def _state_buffers(self):
         """m, v, {t, p1, p2} and the launch tickets: made once per parameter and updated in place
         from then on (a captured launch graph keeps their addresses)."""
         for i, p in enumerate(self.parameters):
@@ -542,7 +550,6 @@ class Adam_Optimizer(SGD_Optimizer):
             self._adam_state = torch.zeros((k, 3), dtype=torch.float64, device=dev)
             self._adam_state[:, 1:] = 1.0
             self._adam_ticket = torch.zeros(k, dtype=torch.int32, device=dev)
-        return self._adam_m, self._adam_v, self._adam_state
 
     def reset_state(self):
         """Back to before the first step -- m = v = 0, {t, p1, p2} = {0, 1, 1} -- in place: the
@@ -556,50 +563,28 @@ class Adam_Optimizer(SGD_Optimizer):
             self._adam_state[:, 0].zero_()
             self._adam_state[:, 1:].fill_(1.0)
 
-    def _adam_tail(self):
-        return (float(self.adam_learning_rate), float(self.beta1), float(self.beta2),
-                float(self.epsilon))
-
-    def _kernel_row(self, scale, clip):
-        return (float(scale), float(clip)) + self._adam_tail()
-
     def _kernel_apply(self, idx, grads, rows, processed=None):
-        m, v, state = self._adam_buffers()
-        if idx == list(range(len(self.parameters))):
-            st, ticket = state, self._adam_ticket
-        else:
-            # (some of the tensors: their rows of the state, advanced, then put back)
-            st, ticket = state[idx].contiguous(), self._adam_ticket
+        self._state_buffers()
+        m, v, state = self._adam_m, self._adam_v, self._adam_state
+        # (some of the tensors: their rows of the state, advanced, then put back)
+        st = state if idx == list(range(len(self.parameters))) else state[idx].contiguous()
         ops.adam(grads, [self.parameters[i] for i in idx], [m[i] for i in idx],
-                 [v[i] for i in idx], rows, st, ticket, processed=processed)
+                 [v[i] for i in idx], rows, st, self._adam_ticket, processed=processed)
         if st is not state:
             state[idx] = st
 
-    def apply_gradients(self, grads, skip=None):
-        m_all, v_all, state = self._adam_buffers()
-        lr, b1, b2, eps = self._adam_tail()
-        batch = []      # (device float64: one tfrt_adam_multi launch, rows {1, inf, ...})
-        with torch.no_grad():
-            for i, (g, p) in enumerate(zip(grads, self.parameters)):
-                if skip is not None and skip[i]:
-                    continue  # already applied by the batched launch of the processing
-                if self._momentum_kernel(p, g):
-                    batch.append((i, g.contiguous()))
-                    continue
-                # the same arithmetic as eager ops, one rounding each (no addcmul / addcdiv, and
-                # no add_(alpha=...): those may fuse the product into the sum)
-                st, m, v = state[i], m_all[i], v_all[i]
-                st[0] += 1.0
-                st[1] *= b1
-                st[2] *= b2
-                lr_t = lr * torch.sqrt(1.0 - st[2]) / (1.0 - st[1])
-                m.copy_(b1 * m + (1.0 - b1) * g)
-                v.copy_(b2 * v + (1.0 - b2) * (g * g))
-                p.sub_(lr_t * m / (torch.sqrt(v) + eps))
-            if batch:
-                row = self._kernel_row(1.0, float("inf"))
-                self._kernel_apply([i for i, _ in batch], [g for _, g in batch],
-                                   [row] * len(batch))
+    def _eager_apply(self, i, g, p):
+        # the kernel's arithmetic as eager ops, one rounding each (no addcmul / addcdiv, and no
+        # add_(alpha=...): those may fuse the product into the sum)
+        lr, b1, b2, eps = self._rule_tail()
+        st, m, v = self._adam_state[i], self._adam_m[i], self._adam_v[i]
+        st[0] += 1.0
+        st[1] *= b1
+        st[2] *= b2
+        lr_t = lr * torch.sqrt(1.0 - st[2]) / (1.0 - st[1])
+        m.copy_(b1 * m + (1.0 - b1) * g)
+        v.copy_(b2 * v + (1.0 - b2) * (g * g))
+        p.sub_(lr_t * m / (torch.sqrt(v) + eps))
 
     def _enter_phase(self, phase):
         for key in self._PHASE_KEYS:

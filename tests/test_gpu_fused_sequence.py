@@ -67,12 +67,19 @@ def _lens3d(n_rays, k=3, coherent=None, in_place=None, **kw):
     return opt, acc
 
 
-def _optimizer2d(make, momentum=False):
+def _optimizer2d(make, momentum=False, adam=False):
     import torch
-    from tfrt.optimizer import SGD_Optimizer
+    from tfrt.optimizer import Adam_Optimizer, SGD_Optimizer
     eng, params, erf = make(torch.float64)
-    return SGD_Optimizer(eng, params, erf, 4, learning_rate=0.02, grad_clip=0.05,
-                         sgd_learning_rate=1.0, apply_momentum=momentum, fused=True, graph=False)
+    cls = Adam_Optimizer if adam else SGD_Optimizer
+    return cls(eng, params, erf, 4, learning_rate=0.02, grad_clip=0.05,
+               sgd_learning_rate=1.0, apply_momentum=momentum, fused=True, graph=False)
+
+
+def _lens3d_adam(n_rays, **kw):
+    from test_gpu_adam import _make
+    opt, _eng, _lens, acc = _make(n_rays, "eager", **kw)
+    return opt, acc
 
 
 def _index2d(error):
@@ -116,6 +123,12 @@ def _case(name):
         return _lens3d(2000, accumulators=True) + (6, {})
     if name == "apply_accumulator_momentum":
         return _lens3d(2000, accumulators=True, apply_momentum=True) + (6, {"momentum": 0.9})
+    if name == "apply_one_parameter_adam":
+        return _optimizer2d(SCENES["single_arc"], adam=True), None, 6, {}
+    if name == "apply_two_parameters_adam":
+        return _lens3d_adam(2000) + (6, {})
+    if name == "apply_accumulator_adam":
+        return _lens3d_adam(2000, accumulators=True) + (6, {})
     raise KeyError(name)
 
 
@@ -155,6 +168,12 @@ EXPECTED = {
     "apply_accumulator_momentum": _UNFOLDED3D + ["tfrt_goal_finish", "tfrt_sgd_process_dev",
                                                  "tfrt_csr_matvec", "tfrt_sgd_momentum_multi",
                                                  "tfrt_sgd_momentum_multi"],
+    # the Adam rule on the same scenes: one launch from one parameter on, like momentum
+    "apply_one_parameter_adam": _GOAL2D + ["tfrt_adam_multi_finish"],
+    "apply_two_parameters_adam": _UNFOLDED3D + ["tfrt_adam_multi_finish"],
+    "apply_accumulator_adam": _UNFOLDED3D + ["tfrt_goal_finish", "tfrt_sgd_process_dev",
+                                             "tfrt_csr_matvec", "tfrt_adam_multi",
+                                             "tfrt_adam_multi"],
 }
 # (folded reverse sweep, in-place trace) of the recorded step
 MODES = {

@@ -60,6 +60,129 @@ __device__ __forceinline__ void wave_fence() {
 inline int cdiv(int64_t a, int64_t b) { return static_cast<int>((a + b - 1) / b); }
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
+// The element type of a ray block, chosen by a `state_dtype` code: fn gets a state_tag<T> for
+// TFRT_F32 / TFRT_F64 / TFRT_F16 (`[&](auto tag) { using T = typename decltype(tag)::type; ... }`)
+// and its result is returned; any other code returns `miss` without calling fn.
+template <typename T>
+struct state_tag {
+  using type = T;
+};
+template <typename F>
+inline int dispatch_state(int state_dtype, int miss, F&& fn) {
+  switch (state_dtype) {
+    case TFRT_F32: return fn(state_tag<float>{});
+    case TFRT_F64: return fn(state_tag<double>{});
+    case TFRT_F16: return fn(state_tag<_Float16>{});
+    default: return miss;
+  }
+}
+inline bool state_dtype_ok(int dtype) {
+  return dtype == TFRT_F32 || dtype == TFRT_F64 || dtype == TFRT_F16;
+}
+// (an unknown code sizes like float32: the workspace sizing entries take any code)
+inline size_t state_bytes(int dtype) { return dtype == TFRT_F64 ? 8 : (dtype == TFRT_F16 ? 2 : 4); }
+
+// One pass's input rays: the source for pass 0, the previous pass's output otherwise.
+template <typename T>
+struct PassIn {
+  const T* rays;
+  int64_t stride;
+  const int32_t* ids;    // source-ray index of a slot, or null: the slot itself
+  const int32_t* last;   // the face (2-D: primitive) the ray left, or null: none
+};
+
+// What a forward entry (tfrt_trace3d_forward, tfrt_trace3d_compact, tfrt_trace2d_forward) hands
+// its typed function, validated: the arguments of the C entry under the names used below it.
+template <typename Scene>
+struct TraceCall {
+  const void* src;
+  int64_t src_stride, N;
+  const Scene* sc;
+  double L, dead_len;
+  int P, dtype;
+  uint32_t flags;
+  const tfrt_ray_out *fin, *act, *stp, *dead;
+  void* unfinished;
+  int32_t* unfinished_id;
+  int32_t* counts;
+  void* workspace;
+  size_t workspace_bytes;
+  hipStream_t st;
+};
+
+// The counters a trace without a set-up launch starts from: the first pass's ray count, the
+// trailing totals and the grid scan's ticket (when there is one).  (A template only so that the
+// files that launch it are the ones that carry it.)
+template <typename = void>
+__global__ void k_init(int32_t* nrays0, int n, int32_t* tail8, unsigned int* scan_ticket) {
+  if (threadIdx.x == 0) *nrays0 = n;
+  if (threadIdx.x < 8) tail8[threadIdx.x] = 0;
+  if (threadIdx.x == 0 && scan_ticket != nullptr) *scan_ticket = 0u;
+}
+
+// The first *n_ptr rays of a SoA block of ROWS rows, and their ids (their positions when the
+// input has none).
+template <typename T, int ROWS>
+__global__ __launch_bounds__(BLOCK) void k_copy_rays(const T* __restrict__ in, int64_t sin,
+                                                     const int32_t* __restrict__ id_in,
+                                                     const int32_t* __restrict__ n_ptr,
+                                                     T* __restrict__ out, int64_t sout,
+                                                     int32_t* __restrict__ id_out) {
+  const int n = *n_ptr;
+  const int i = blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  for (int k = 0; k < ROWS; ++k) out[k * sout + i] = in[k * sin + i];
+  if (id_out) id_out[i] = id_in ? id_in[i] : i;
+}
+
+// scan_rows_grid's single-workgroup sibling (1024 threads, up to SCAN_GRID_MIN_ROWS rows): every
+// thread takes a run of consecutive rows.  `off` receives global offsets (the consumer gets no
+// rowbase), `total` (LDS, NB ints) the column sums, visible to every thread on return.
+template <int NB>
+__device__ __forceinline__ void scan_rows_one(const int32_t* __restrict__ cnt,
+                                              int32_t* __restrict__ off, int nrows, int* total) {
+  const int per = (nrows + 1023) / 1024;
+  const int b0 = min(nrows, (int)threadIdx.x * per), b1 = min(nrows, b0 + per);
+  int loc[NB];
+#pragma unroll
+  for (int c = 0; c < NB; ++c) loc[c] = 0;
+  for (int b = b0; b < b1; ++b)
+    for (int c = 0; c < NB; ++c) loc[c] += cnt[b * NB + c];
+  __shared__ int wsum[16][NB];
+  __shared__ int wbase[16][NB];
+  const int lane = lane_id(), wave = threadIdx.x >> 6;
+  int pre[NB];
+#pragma unroll
+  for (int c = 0; c < NB; ++c) {
+    int v = loc[c];
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int o = __shfl_up(v, d, 64);
+      if (lane >= d) v += o;
+    }
+    pre[c] = v - loc[c];  // exclusive within the wave
+    if (lane == 63) wsum[wave][c] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < NB) {
+    int run = 0;
+    for (int w = 0; w < 16; ++w) {
+      wbase[w][threadIdx.x] = run;
+      run += wsum[w][threadIdx.x];
+    }
+    total[threadIdx.x] = run;
+  }
+  __syncthreads();
+  int run[NB];
+#pragma unroll
+  for (int c = 0; c < NB; ++c) run[c] = wbase[wave][c] + pre[c];
+  for (int b = b0; b < b1; ++b)
+    for (int c = 0; c < NB; ++c) {
+      off[b * NB + c] = run[c];
+      run[c] += cnt[b * NB + c];
+    }
+}
+
 // Exclusive scan of per-ray-block histograms (rows of NB counters, NB = 4 or 8) over a grid of
 // 1024-thread workgroups, one row per thread: coalesced int4 loads and stores, a wave scan by
 // shuffles and one exchange through LDS.  `off` receives the offsets *within the row's

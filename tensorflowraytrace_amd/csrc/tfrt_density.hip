@@ -274,8 +274,7 @@ int tfrt_density_error(const void* rows, int64_t stride, int64_t n, int32_t stat
   if (row_y >= 0 && (!(y1 > y0) || !(sy > 0.0) || !isfinite(sy) || !isfinite(y0) || !isfinite(y1)))
     return TFRT_E_BADARG;
   if (n > 0 && (!rows || !grad || stride < n || grad_stride < n)) return TFRT_E_BADARG;
-  if (state_dtype != TFRT_F32 && state_dtype != TFRT_F64 && state_dtype != TFRT_F16)
-    return TFRT_E_BADARG;
+  if (!state_dtype_ok(state_dtype)) return TFRT_E_BADARG;
   const int bins = nx * ny;
   if (splat_variant == 1 && bins > DENSITY_LDS_BINS) return TFRT_E_BADARG;
   if (workspace_bytes < tfrt_density_error_workspace_bytes(n, nx, ny)) return TFRT_E_WORKSPACE;
@@ -294,34 +293,26 @@ int tfrt_density_error(const void* rows, int64_t stride, int64_t n, int32_t stat
   const int nblk = cdiv(n, BLOCK);
 
   (void)hipMemsetAsync(hq, 0, (size_t)bins * sizeof(int64_t), st);
-#define TFRT_DENSITY(T)                                                                          \
-  do {                                                                                           \
-    const T* r = static_cast<const T*>(rows);                                                    \
-    if (grid > 0) {                                                                              \
-      if (lds)                                                                                   \
-        hipLaunchKernelGGL((k_density_splat<T, true>), dim3(grid), dim3(BLOCK),                  \
-                           (size_t)bins * sizeof(unsigned long long), st, r, stride, n, mask, g, \
-                           hqu, partial);                                                        \
-      else                                                                                       \
-        hipLaunchKernelGGL((k_density_splat<T, false>), dim3(grid), dim3(BLOCK), 0, st, r,       \
-                           stride, n, mask, g, hqu, partial);                                    \
-    }                                                                                            \
-    hipLaunchKernelGGL(k_density_bins, dim3(1), dim3(BINS_BLOCK), 0, st,                         \
-                       reinterpret_cast<const long long*>(hq), goal, bins, partial, grid, pull,  \
-                       error_out);                                                               \
-    if (nblk > 0)                                                                                \
-      hipLaunchKernelGGL((k_density_seed<T>), dim3(nblk), dim3(BLOCK), 0, st, r, stride, n,      \
-                         mask, g, pull, grad, grad_stride);                                      \
-  } while (0)
-  if (state_dtype == TFRT_F32) {
-    TFRT_DENSITY(float);
-  } else if (state_dtype == TFRT_F64) {
-    TFRT_DENSITY(double);
-  } else {
-    TFRT_DENSITY(_Float16);
-  }
-#undef TFRT_DENSITY
-  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  return dispatch_state(state_dtype, TFRT_E_BADARG, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const T* r = static_cast<const T*>(rows);
+    if (grid > 0) {
+      if (lds)
+        hipLaunchKernelGGL((k_density_splat<T, true>), dim3(grid), dim3(BLOCK),
+                           (size_t)bins * sizeof(unsigned long long), st, r, stride, n, mask, g,
+                           hqu, partial);
+      else
+        hipLaunchKernelGGL((k_density_splat<T, false>), dim3(grid), dim3(BLOCK), 0, st, r, stride,
+                           n, mask, g, hqu, partial);
+    }
+    hipLaunchKernelGGL(k_density_bins, dim3(1), dim3(BINS_BLOCK), 0, st,
+                       reinterpret_cast<const long long*>(hq), goal, bins, partial, grid, pull,
+                       error_out);
+    if (nblk > 0)
+      hipLaunchKernelGGL((k_density_seed<T>), dim3(nblk), dim3(BLOCK), 0, st, r, stride, n, mask,
+                         g, pull, grad, grad_stride);
+    return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  });
 }
 
 }  // extern "C"

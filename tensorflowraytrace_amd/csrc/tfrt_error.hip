@@ -104,21 +104,15 @@ static int goal_error_launch(const void* finished_rays, int64_t capacity,
   double* partial = static_cast<double*>(workspace);
   const int nblk = cdiv(capacity > 0 ? capacity : 1, BLOCK);
   hipStream_t st = static_cast<hipStream_t>(stream);
-#define TFRT_GOAL(T)                                                                           \
-  hipLaunchKernelGGL((k_goal_error<T>), dim3(nblk), dim3(BLOCK), 0, st,                        \
-                     static_cast<const T*>(finished_rays), capacity, finished_id, n_finished,  \
-                     gf, goal, goal_stride, goal_ray_stride, grad_finished, partial, zero_buffer,   \
-                     zero_count)
-  if (state_dtype == TFRT_F32) {
-    TFRT_GOAL(float);
-  } else if (state_dtype == TFRT_F64) {
-    TFRT_GOAL(double);
-  } else if (state_dtype == TFRT_F16) {
-    TFRT_GOAL(_Float16);
-  } else {
-    return TFRT_E_BADARG;
-  }
-#undef TFRT_GOAL
+  const int rc = dispatch_state(state_dtype, TFRT_E_BADARG, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((k_goal_error<T>), dim3(nblk), dim3(BLOCK), 0, st,
+                       static_cast<const T*>(finished_rays), capacity, finished_id, n_finished, gf,
+                       goal, goal_stride, goal_ray_stride, grad_finished, partial, zero_buffer,
+                       zero_count);
+    return 0;
+  });
+  if (rc != 0) return rc;
   tfrt_goal_pending g = {};
   g.partial = partial;
   g.n_partial = nblk;

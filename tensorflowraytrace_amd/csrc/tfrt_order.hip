@@ -1391,25 +1391,13 @@ int tfrt_ray_order(const void* rays, int64_t stride, int64_t n_rays, int32_t sta
   if (workspace_bytes < L.total) return TFRT_E_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   char* ws = static_cast<char*>(workspace);
-  int rc;
-  switch (state_dtype) {
-    case TFRT_F32:
-      rc = ray_order_t(BlockRays<float>{static_cast<const float*>(rays), stride}, n_rays,
-                       face_verts, n_faces, axis, perm, keys_out, ws, L, st);
-      break;
-    case TFRT_F64:
-      rc = ray_order_t(BlockRays<double>{static_cast<const double*>(rays), stride}, n_rays,
-                       face_verts, n_faces, axis, perm, keys_out, ws, L, st);
-      break;
-    case TFRT_F16:
-      rc = ray_order_t(BlockRays<_Float16>{static_cast<const _Float16*>(rays), stride}, n_rays,
-                       face_verts, n_faces, axis, perm, keys_out, ws, L, st);
-      break;
-    default:
-      return TFRT_E_BADARG;
-  }
-  if (rc != 0) return rc;
-  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  return dispatch_state(state_dtype, TFRT_E_BADARG, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const int rc = ray_order_t(BlockRays<T>{static_cast<const T*>(rays), stride}, n_rays,
+                               face_verts, n_faces, axis, perm, keys_out, ws, L, st);
+    if (rc != 0) return rc;
+    return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  });
 }
 
 static int source3d_order(const tfrt_source3d_program* program, int64_t first, int64_t n_rays,
@@ -1457,8 +1445,7 @@ int tfrt_source3d_order_cells(const tfrt_source3d_program* program, int64_t firs
 }
 
 size_t tfrt_permute_rays_workspace_bytes(int64_t n_rays, int32_t state_dtype) {
-  const size_t esz = state_dtype == TFRT_F64 ? 8 : (state_dtype == TFRT_F16 ? 2 : 4);
-  return align_up((size_t)(n_rays > 0 ? n_rays : 1) * 8 * esz);
+  return align_up((size_t)(n_rays > 0 ? n_rays : 1) * 8 * state_bytes(state_dtype));
 }
 
 int tfrt_permute_rays(const void* src_rays, int64_t src_stride, int64_t n_rays,
@@ -1471,20 +1458,11 @@ int tfrt_permute_rays(const void* src_rays, int64_t src_stride, int64_t n_rays,
   if (workspace_bytes < tfrt_permute_rays_workspace_bytes(n_rays, state_dtype))
     return TFRT_E_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (state_dtype) {
-    case TFRT_F32:
-      permute_rays_t<float>(src_rays, src_stride, n_rays, index, dst_rays, dst_stride, workspace, st);
-      break;
-    case TFRT_F64:
-      permute_rays_t<double>(src_rays, src_stride, n_rays, index, dst_rays, dst_stride, workspace, st);
-      break;
-    case TFRT_F16:
-      permute_rays_t<_Float16>(src_rays, src_stride, n_rays, index, dst_rays, dst_stride, workspace, st);
-      break;
-    default:
-      return TFRT_E_BADARG;
-  }
-  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  return dispatch_state(state_dtype, TFRT_E_BADARG, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    permute_rays_t<T>(src_rays, src_stride, n_rays, index, dst_rays, dst_stride, workspace, st);
+    return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  });
 }
 
 int tfrt_gather_rows(const void* src, int64_t src_stride, int32_t n_rows, int32_t elem_bytes,

@@ -196,34 +196,17 @@ int tfrt_source3d_generate(const tfrt_source3d_program* program, const int32_t* 
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(cdiv(n, BLOCK));
   const bool pool = program->kind == TFRT_SRC_POOL, density = source_program_density(program);
-#define TFRT_SOURCE3D_AS(T, POOL, DENSITY)                                                        \
-  hipLaunchKernelGGL((k_source3d<T, POOL, DENSITY>), grid, dim3(BLOCK), 0, st, *program, index,   \
-                     first, n, static_cast<T*>(rays), stride, fields, field_stride)
-#define TFRT_SOURCE3D(T)                                                                          \
-  {                                                                                               \
-    if (pool)                                                                                     \
-      TFRT_SOURCE3D_AS(T, true, false);                                                           \
-    else if (density)                                                                             \
-      TFRT_SOURCE3D_AS(T, false, true);                                                           \
-    else                                                                                          \
-      TFRT_SOURCE3D_AS(T, false, false);                                                          \
-  }
-  switch (state_dtype) {
-    case TFRT_F32:
-      TFRT_SOURCE3D(float)
-      break;
-    case TFRT_F64:
-      TFRT_SOURCE3D(double)
-      break;
-    case TFRT_F16:
-      TFRT_SOURCE3D(_Float16)
-      break;
-    default:
-      return TFRT_E_BADARG;
-  }
-#undef TFRT_SOURCE3D
-#undef TFRT_SOURCE3D_AS
-  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  return dispatch_state(state_dtype, TFRT_E_BADARG, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, dim3(BLOCK), 0, st, *program, index, first, n,
+                         static_cast<T*>(rays), stride, fields, field_stride);
+    };
+    if (pool) launch(k_source3d<T, true, false>);
+    else if (density) launch(k_source3d<T, false, true>);
+    else launch(k_source3d<T, false, false>);
+    return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  });
 }
 
 int tfrt_source3d_pool_rows(const tfrt_source3d_program* program, const int32_t* index,
@@ -258,35 +241,22 @@ int tfrt_source2d_generate(const tfrt_source2d_program* program, const int32_t* 
   if (first < 0 || (index == nullptr && first + n > program->n_rays)) return TFRT_E_BADARG;
   if ((rays != nullptr && stride < n) || (fields != nullptr && field_stride < n))
     return TFRT_E_BADARG;
-  if (state_dtype != TFRT_F32 && state_dtype != TFRT_F64 && state_dtype != TFRT_F16)
-    return TFRT_E_BADARG;
+  if (!state_dtype_ok(state_dtype)) return TFRT_E_BADARG;
   if (n == 0) return 0;
   if (program->n_rays == 0) return TFRT_E_BADARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(cdiv(n, BLOCK));
   const bool pool = program->kind == TFRT_SRC_POOL;
-#define TFRT_SOURCE2D(T)                                                                          \
-  {                                                                                               \
-    if (pool)                                                                                     \
-      hipLaunchKernelGGL((k_source2d<T, true>), grid, dim3(BLOCK), 0, st, *program, index, first, \
-                         n, static_cast<T*>(rays), stride, fields, field_stride);                 \
-    else                                                                                          \
-      hipLaunchKernelGGL((k_source2d<T, false>), grid, dim3(BLOCK), 0, st, *program, index,       \
-                         first, n, static_cast<T*>(rays), stride, fields, field_stride);          \
-  }
-  switch (state_dtype) {
-    case TFRT_F32:
-      TFRT_SOURCE2D(float)
-      break;
-    case TFRT_F64:
-      TFRT_SOURCE2D(double)
-      break;
-    default:
-      TFRT_SOURCE2D(_Float16)
-      break;
-  }
-#undef TFRT_SOURCE2D
-  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  return dispatch_state(state_dtype, TFRT_E_BADARG, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, dim3(BLOCK), 0, st, *program, index, first, n,
+                         static_cast<T*>(rays), stride, fields, field_stride);
+    };
+    if (pool) launch(k_source2d<T, true>);
+    else launch(k_source2d<T, false>);
+    return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  });
 }
 
 int tfrt_source2d_pool_rows(const tfrt_source2d_program* program, const int32_t* index,

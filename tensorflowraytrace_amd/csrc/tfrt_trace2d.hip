@@ -444,47 +444,8 @@ __global__ __launch_bounds__(1024) void k_scan2d_one(const int32_t* __restrict__
                                                  int M) {
   const int n = *n_ptr;
   const int nblk = (n + BLOCK - 1) / BLOCK;
-  const int per = (nblk + 1023) / 1024;
-  const int b0 = min(nblk, (int)threadIdx.x * per), b1 = min(nblk, b0 + per);
-  int loc[NBIN];
-#pragma unroll
-  for (int c = 0; c < NBIN; ++c) loc[c] = 0;
-  for (int b = b0; b < b1; ++b)
-    for (int c = 0; c < NBIN; ++c) loc[c] += blockcnt[b * NBIN + c];
-  __shared__ int wsum[16][NBIN];
-  __shared__ int wbase[16][NBIN];
   __shared__ int total[NBIN];
-  const int lane = lane_id(), wave = threadIdx.x >> 6;
-  int pre[NBIN];
-#pragma unroll
-  for (int c = 0; c < NBIN; ++c) {
-    int v = loc[c];
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(v, d, 64);
-      if (lane >= d) v += o;
-    }
-    pre[c] = v - loc[c];
-    if (lane == 63) wsum[wave][c] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < NBIN) {
-    int run = 0;
-    for (int w = 0; w < 16; ++w) {
-      wbase[w][threadIdx.x] = run;
-      run += wsum[w][threadIdx.x];
-    }
-    total[threadIdx.x] = run;
-  }
-  __syncthreads();
-  int run[NBIN];
-#pragma unroll
-  for (int c = 0; c < NBIN; ++c) run[c] = wbase[wave][c] + pre[c];
-  for (int b = b0; b < b1; ++b)
-    for (int c = 0; c < NBIN; ++c) {
-      blockoff[b * NBIN + c] = run[c];
-      run[c] += blockcnt[b * NBIN + c];
-    }
+  scan_rows_one<NBIN>(blockcnt, blockoff, nblk, total);
   if (threadIdx.x < NBIN) bin_counts[threadIdx.x] = total[threadIdx.x];
   if (threadIdx.x < 4) {
     const int c = threadIdx.x;
@@ -860,25 +821,6 @@ __global__ __launch_bounds__(BLOCK) void k_backward2d(
   }
 }
 
-__global__ void k_init2(int32_t* nrays0, int n, int32_t* tail8, unsigned int* scan_ticket) {
-  if (threadIdx.x == 0) *nrays0 = n;
-  if (threadIdx.x < 8) tail8[threadIdx.x] = 0;
-  if (threadIdx.x == 0) *scan_ticket = 0u;
-}
-
-template <typename T>
-__global__ __launch_bounds__(BLOCK) void k_copy_rays2(const T* __restrict__ in, int64_t sin,
-                                                      const int32_t* __restrict__ id_in,
-                                                      const int32_t* __restrict__ n_ptr,
-                                                      T* __restrict__ out, int64_t sout,
-                                                      int32_t* __restrict__ id_out) {
-  const int n = *n_ptr;
-  const int i = blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= n) return;
-  for (int k = 0; k < 4; ++k) out[k * sout + i] = in[k * sin + i];
-  if (id_out) id_out[i] = id_in ? id_in[i] : i;
-}
-
 // seam kernels: one primitive kind, nearest per ray
 template <typename T, bool ARC>
 __global__ __launch_bounds__(BLOCK) void k_seam2d(const T* __restrict__ rays, int64_t stride, int n,
@@ -939,7 +881,7 @@ struct Layout2 {
 // whatever they are)
 static Layout2 make_layout2(int64_t N, int P, int dtype, int64_t Ms = 0, int64_t Ma = 0) {
   Layout2 L;
-  const size_t esz = dtype == TFRT_F64 ? 8 : (dtype == TFRT_F16 ? 2 : 4);
+  const size_t esz = state_bytes(dtype);
   const size_t n = N > 0 ? N : 1;
   L.nblk = cdiv(n, BLOCK);
   size_t o = 0;
@@ -972,6 +914,38 @@ static Layout2 make_layout2(int64_t N, int P, int dtype, int64_t Ms = 0, int64_t
   L.total_ordered = o;
   return L;
 }
+
+// Typed view of the record a 2-D trace leaves in its workspace (Layout2), per-pass rows `n` slots
+// apart: the forward writes it through a Tape2<T>, the sweeps and tfrt_trace2d_rows read it
+// through a Tape2<const T>.
+template <typename T>
+struct Tape2 {
+  template <typename U>
+  using as = std::conditional_t<std::is_const_v<T>, const U, U>;
+  using E = std::remove_const_t<T>;
+  as<char>* ws;
+  const Layout2& lay;
+  size_t n;
+  template <typename U>
+  as<U>* at(size_t offset) const { return reinterpret_cast<as<U>*>(ws + offset); }
+  Tape2(as<void>* workspace, const Layout2& layout, int64_t N)
+      : ws(static_cast<as<char>*>(workspace)), lay(layout), n(N > 0 ? N : 1) {}
+
+  as<int32_t>* nrays = at<int32_t>(lay.nrays);   // rays entering pass 1..P, and P + 1
+  // pass p's output rays, their ids and last primitives; its records
+  T* rays_out(int p) const { return at<E>(lay.rays) + (size_t)p * 4 * n; }
+  as<int32_t>* ids(int p) const { return at<int32_t>(lay.rayid) + (size_t)p * n; }
+  as<int32_t>* last(int p) const { return at<int32_t>(lay.lastprim) + (size_t)p * n; }
+  as<int32_t>* rec_prim(int p) const { return at<int32_t>(lay.rec_prim) + (size_t)p * n; }
+  as<int32_t>* rec_slot(int p) const { return at<int32_t>(lay.rec_slot) + (size_t)p * n; }
+  as<double>* rec_u(int p) const { return at<double>(lay.rec_u) + (size_t)p * n; }
+  as<double>* rec_aux(int p) const { return at<double>(lay.rec_aux) + (size_t)p * n; }
+  as<uint8_t>* rec_bin(int p) const { return at<uint8_t>(lay.rec_bin) + (size_t)p * n; }
+  PassIn<E> input(int p, const void* src, int64_t src_stride) const {
+    if (p == 0) return {static_cast<const E*>(src), src_stride, nullptr, nullptr};
+    return {rays_out(p - 1), (int64_t)n, ids(p - 1), last(p - 1)};
+  }
+};
 
 // The ordered sweeps' accumulators in the workspace, cleared (inside the call, so that a captured
 // sequence replays correctly); bits for at most `terms` terms per entry.
@@ -1008,115 +982,116 @@ static bool index_grads2d(const tfrt_scene2d* sc) {
          (sc->n_arcs > 0 && (sc->grad_arc_n_in || sc->grad_arc_n_out));
 }
 
+// What the 2-D reverse sweeps hand on (tfrt_trace2d_backward: the class gradients; the goal and
+// rows sweeps: the forward's finished block, their seed apart).
+struct SweepCall2 {
+  const void* src;
+  int64_t src_stride, N;
+  const tfrt_scene2d* sc;
+  double L, dead_len;
+  int P, dtype;
+  const int32_t* counts;
+  void* workspace;
+  size_t workspace_bytes;
+  hipStream_t st;
+  // what differs between them, set by name (null / 0 where an entry has none)
+  const double *g_fin, *g_act, *g_stp, *g_dead;
+  int64_t cap_fin, cap_act, cap_stp, cap_dead;
+  double *g_seg, *g_arc, *g_src;
+  const tfrt_ray_out* fin;   // goal and rows sweeps only
+};
+
 template <typename T>
-static int trace2d_forward_t(const void* src_rays, int64_t src_stride, int64_t N,
-                             const tfrt_scene2d* sc, double L, double dead_len, int P, int dtype,
-                             uint32_t flags, tfrt_ray_out* fin, tfrt_ray_out* act,
-                             tfrt_ray_out* stp, tfrt_ray_out* dead, void* unfinished,
-                             int32_t* unfinished_id, int32_t* counts, void* workspace,
-                             size_t workspace_bytes, hipStream_t st) {
-  const Layout2 lay = make_layout2(N, P, dtype);
-  if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
-  char* ws = static_cast<char*>(workspace);
-  int32_t* nrays = reinterpret_cast<int32_t*>(ws + lay.nrays);
+static int trace2d_forward_t(const TraceCall<tfrt_scene2d>& c) {
+  const tfrt_scene2d* sc = c.sc;
+  const int64_t N = c.N;
+  const int P = c.P;
+  hipStream_t st = c.st;
+  const Layout2 lay = make_layout2(N, P, c.dtype);
+  if (c.workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
+  const Tape2<T> tape(c.workspace, lay, N);
+  // (the forward's own regions: nobody else reads them)
+  char* ws = static_cast<char*>(c.workspace);
   int32_t* blockcnt = reinterpret_cast<int32_t*>(ws + lay.blockcnt);
   int32_t* blockoff = reinterpret_cast<int32_t*>(ws + lay.blockoff);
   int32_t* rowtot = reinterpret_cast<int32_t*>(ws + lay.rowtot);
   int32_t* rowbase = reinterpret_cast<int32_t*>(ws + lay.rowbase);
   unsigned int* ticket = reinterpret_cast<unsigned int*>(ws + lay.ticket);
-  int32_t* bincnt = reinterpret_cast<int32_t*>(ws + lay.bincnt);
-  T* rays_ws = reinterpret_cast<T*>(ws + lay.rays);
-  int32_t* rayid = reinterpret_cast<int32_t*>(ws + lay.rayid);
-  int32_t* lastprim = reinterpret_cast<int32_t*>(ws + lay.lastprim);
-  int32_t* rec_prim = reinterpret_cast<int32_t*>(ws + lay.rec_prim);
-  int32_t* rec_slot = reinterpret_cast<int32_t*>(ws + lay.rec_slot);
-  double* rec_u = reinterpret_cast<double*>(ws + lay.rec_u);
-  double* rec_aux = reinterpret_cast<double*>(ws + lay.rec_aux);
-  uint8_t* rec_bin = reinterpret_cast<uint8_t*>(ws + lay.rec_bin);
-  int32_t* tail = counts + (size_t)P * TFRT_COUNTS_PER_PASS;
-  const size_t n = N > 0 ? N : 1;
+  int32_t* bincnt_all = reinterpret_cast<int32_t*>(ws + lay.bincnt);
+  int32_t* nrays = tape.nrays;
+  int32_t* tail = c.counts + (size_t)P * TFRT_COUNTS_PER_PASS;
+  const int64_t n = (int64_t)tape.n;
   const int M = (int)(sc->n_segments + sc->n_arcs);
-  hipLaunchKernelGGL(k_init2, dim3(1), dim3(64), 0, st, nrays, (int)N, tail, ticket);
+  hipLaunchKernelGGL(k_init<>, dim3(1), dim3(64), 0, st, nrays, (int)N, tail, ticket);
   const tfrt_ray_out none = {nullptr, nullptr, nullptr, 0};
   for (int p = 0; p < P; ++p) {
-    const T* rin = p == 0 ? static_cast<const T*>(src_rays) : rays_ws + (size_t)(p - 1) * 4 * n;
-    const int64_t sin = p == 0 ? src_stride : (int64_t)n;
-    const int32_t* idin = p == 0 ? nullptr : rayid + (size_t)(p - 1) * n;
-    const int32_t* lpin = p == 0 ? nullptr : lastprim + (size_t)(p - 1) * n;
-    hipLaunchKernelGGL((k_intersect2d<T>), dim3(lay.nblk), dim3(BLOCK), 0, st, rin, sin, nrays + p,
-                       lpin, *sc, rec_prim + (size_t)p * n, rec_u + (size_t)p * n,
-                       rec_aux + (size_t)p * n, rec_bin + (size_t)p * n, blockcnt);
+    const PassIn<T> in = tape.input(p, c.src, c.src_stride);
+    int32_t* pass_counts = c.counts + (size_t)p * TFRT_COUNTS_PER_PASS;
+    int32_t* bincnt = bincnt_all + (size_t)p * NBIN;
+    hipLaunchKernelGGL((k_intersect2d<T>), dim3(lay.nblk), dim3(BLOCK), 0, st, in.rays, in.stride,
+                       nrays + p, in.last, *sc, tape.rec_prim(p), tape.rec_u(p), tape.rec_aux(p),
+                       tape.rec_bin(p), blockcnt);
     const bool grid_scan = lay.nblk >= SCAN_GRID_MIN_ROWS;
     if (grid_scan)
       hipLaunchKernelGGL(k_scan2d, dim3(cdiv(lay.nblk, 1024)), dim3(1024), 0, st, nrays + p,
-                         blockcnt, blockoff, rowtot, rowbase, ticket,
-                         counts + (size_t)p * TFRT_COUNTS_PER_PASS, bincnt + (size_t)p * NBIN, tail,
-                         nrays + p + 1, reinterpret_cast<unsigned long long*>(tail + 4), M);
+                         blockcnt, blockoff, rowtot, rowbase, ticket, pass_counts,
+                         bincnt, tail, nrays + p + 1,
+                         reinterpret_cast<unsigned long long*>(tail + 4), M);
     else
-      hipLaunchKernelGGL(k_scan2d_one, dim3(1), dim3(1024), 0, st, nrays + p, blockcnt, blockoff,
-                         counts + (size_t)p * TFRT_COUNTS_PER_PASS, bincnt + (size_t)p * NBIN, tail,
-                         nrays + p + 1, reinterpret_cast<unsigned long long*>(tail + 4), M);
-    hipLaunchKernelGGL((k_react2d<T>), dim3(lay.nblk), dim3(BLOCK), 0, st, rin, sin, nrays + p,
-                       idin, rec_prim + (size_t)p * n, rec_u + (size_t)p * n,
-                       rec_aux + (size_t)p * n, rec_bin + (size_t)p * n, blockoff,
-                       grid_scan ? rowbase : static_cast<int32_t*>(nullptr),
-                       counts + (size_t)p * TFRT_COUNTS_PER_PASS, bincnt + (size_t)p * NBIN, *sc, L,
-                       dead_len, flags, rays_ws + (size_t)p * 4 * n, (int64_t)n,
-                       rayid + (size_t)p * n, lastprim + (size_t)p * n, rec_slot + (size_t)p * n,
-                       fin ? *fin : none, act ? *act : none, stp ? *stp : none,
-                       dead ? *dead : none, tail + 6);
+      hipLaunchKernelGGL(k_scan2d_one, dim3(1), dim3(1024), 0, st, nrays + p, blockcnt,
+                         blockoff, pass_counts, bincnt, tail, nrays + p + 1,
+                         reinterpret_cast<unsigned long long*>(tail + 4), M);
+    hipLaunchKernelGGL((k_react2d<T>), dim3(lay.nblk), dim3(BLOCK), 0, st, in.rays, in.stride,
+                       nrays + p, in.ids, tape.rec_prim(p), tape.rec_u(p), tape.rec_aux(p),
+                       tape.rec_bin(p), blockoff,
+                       grid_scan ? rowbase : static_cast<int32_t*>(nullptr), pass_counts, bincnt,
+                       *sc, c.L, c.dead_len, c.flags, tape.rays_out(p), n, tape.ids(p),
+                       tape.last(p), tape.rec_slot(p), c.fin ? *c.fin : none,
+                       c.act ? *c.act : none, c.stp ? *c.stp : none, c.dead ? *c.dead : none,
+                       tail + 6);
   }
-  if (unfinished != nullptr && P > 0) {
-    hipLaunchKernelGGL((k_copy_rays2<T>), dim3(lay.nblk), dim3(BLOCK), 0, st,
-                       rays_ws + (size_t)(P - 1) * 4 * n, (int64_t)n, rayid + (size_t)(P - 1) * n,
-                       nrays + P, static_cast<T*>(unfinished), (int64_t)N, unfinished_id);
+  if (c.unfinished != nullptr && P > 0) {
+    hipLaunchKernelGGL((k_copy_rays<T, 4>), dim3(lay.nblk), dim3(BLOCK), 0, st, tape.rays_out(P - 1),
+                       n, tape.ids(P - 1), nrays + P, static_cast<T*>(c.unfinished), (int64_t)N,
+                       c.unfinished_id);
   }
   return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
 }
 
 template <typename T>
-static int trace2d_backward_t(const void* src_rays, int64_t src_stride, int64_t N,
-                              const tfrt_scene2d* sc, double L, double dead_len, int P, int dtype,
-                              const double* g_fin, int64_t cap_fin, const double* g_act,
-                              int64_t cap_act, const double* g_stp, int64_t cap_stp,
-                              const double* g_dead, int64_t cap_dead, double* g_seg, double* g_arc,
-                              double* g_src, const int32_t* counts, void* workspace,
-                              size_t workspace_bytes, hipStream_t st) {
+static int trace2d_backward_t(const SweepCall2& c) {
+  const tfrt_scene2d* sc = c.sc;
+  const int64_t N = c.N;
+  const int P = c.P;
+  double *g_seg = c.g_seg, *g_arc = c.g_arc;
+  hipStream_t st = c.st;
   const int Ms = (int)sc->n_segments, Ma = (int)sc->n_arcs;
-  const Layout2 lay = make_layout2(N, P, dtype, Ms, Ma);
-  if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
-  char* ws = static_cast<char*>(workspace);
-  const int32_t* nrays = reinterpret_cast<int32_t*>(ws + lay.nrays);
-  const T* rays_ws = reinterpret_cast<T*>(ws + lay.rays);
-  const int32_t* rayid = reinterpret_cast<int32_t*>(ws + lay.rayid);
-  const int32_t* rec_prim = reinterpret_cast<int32_t*>(ws + lay.rec_prim);
-  const int32_t* rec_slot = reinterpret_cast<int32_t*>(ws + lay.rec_slot);
-  const double* rec_u = reinterpret_cast<double*>(ws + lay.rec_u);
-  const uint8_t* rec_bin = reinterpret_cast<uint8_t*>(ws + lay.rec_bin);
-  double* gbuf = reinterpret_cast<double*>(ws + lay.gbuf);
-  const size_t n = N > 0 ? N : 1;
+  const Layout2 lay = make_layout2(N, P, c.dtype, Ms, Ma);
+  if (c.workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
+  const Tape2<const T> tape(c.workspace, lay, N);
+  char* ws = static_cast<char*>(c.workspace);
+  double* gbuf = reinterpret_cast<double*>(ws + lay.gbuf);   // (the sweep's own)
+  const int64_t n = (int64_t)tape.n;
   const bool gn = index_grads2d(sc);
   // ordered: per pass ORD_MAX, ORD_ACC and k_fixed_finish2 (the pass's sums are added into the
   // outputs pass by pass, last pass first); at most one term per ray and entry in a pass
   const bool ordered = sc->deterministic != 0 && Ms + Ma > 0 && (g_seg || g_arc || gn);
   Fixed2 fx = {nullptr, nullptr, nullptr, 0};
   if (ordered) {
-    if (workspace_bytes < lay.total_ordered) return TFRT_E_WORKSPACE;
+    if (c.workspace_bytes < lay.total_ordered) return TFRT_E_WORKSPACE;
     fx = fixed_region2(lay, ws, N, st);
   }
   for (int p = P - 1; p >= 0; --p) {
-    const T* rin = p == 0 ? static_cast<const T*>(src_rays) : rays_ws + (size_t)(p - 1) * 4 * n;
-    const int64_t sin = p == 0 ? src_stride : (int64_t)n;
-    const int32_t* idin = p == 0 ? nullptr : rayid + (size_t)(p - 1) * n;
+    const PassIn<T> in = tape.input(p, c.src, c.src_stride);
     const double* g_child = (p == P - 1) ? nullptr : gbuf + (size_t)((p + 1) & 1) * 4 * n;
-    double* g_out = (p == 0 && g_src != nullptr) ? g_src : gbuf + (size_t)(p & 1) * 4 * n;
-    const int64_t out_stride = (p == 0 && g_src != nullptr) ? N : (int64_t)n;
+    double* g_out = (p == 0 && c.g_src != nullptr) ? c.g_src : gbuf + (size_t)(p & 1) * 4 * n;
+    const int64_t out_stride = (p == 0 && c.g_src != nullptr) ? N : n;
     auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(lay.nblk), dim3(BLOCK), 0, st, rin, sin, nrays + p, idin,
-                         rec_prim + (size_t)p * n, rec_u + (size_t)p * n, rec_bin + (size_t)p * n,
-                         rec_slot + (size_t)p * n, counts + (size_t)p * TFRT_COUNTS_PER_PASS, *sc,
-                         L, dead_len, g_child, (int64_t)n, g_fin, cap_fin, g_act, cap_act, g_stp,
-                         cap_stp, g_dead, cap_dead, g_out, out_stride, g_seg, g_arc, fx);
+      hipLaunchKernelGGL(kernel, dim3(lay.nblk), dim3(BLOCK), 0, st, in.rays, in.stride,
+                         tape.nrays + p, in.ids, tape.rec_prim(p), tape.rec_u(p), tape.rec_bin(p),
+                         tape.rec_slot(p), c.counts + (size_t)p * TFRT_COUNTS_PER_PASS, *sc, c.L,
+                         c.dead_len, g_child, n, c.g_fin, c.cap_fin, c.g_act, c.cap_act, c.g_stp,
+                         c.cap_stp, c.g_dead, c.cap_dead, g_out, out_stride, g_seg, g_arc, fx);
     };
     if (!ordered) {
       if (gn) launch(k_backward2d<T, true>);
@@ -1486,33 +1461,30 @@ __global__ __launch_bounds__(BLOCK) void k_backward2d_goal(
 }
 
 template <typename T, typename Seed>
-static int trace2d_backward_goal_t(const void* src_rays, int64_t src_stride, int64_t N,
-                                   const tfrt_scene2d* sc, double L, int P, int dtype,
-                                   const tfrt_ray_out& fin, const Seed& seed, double* g_seg,
-                                   double* g_arc, void* workspace, size_t workspace_bytes,
-                                   hipStream_t st) {
+static int trace2d_backward_goal_t(const SweepCall2& c, const Seed& seed) {
+  const tfrt_scene2d* sc = c.sc;
+  const int64_t N = c.N;
+  const int P = c.P;
+  double *g_seg = c.g_seg, *g_arc = c.g_arc;
+  hipStream_t st = c.st;
   const int Ms = (int)sc->n_segments, Ma = (int)sc->n_arcs;
-  const Layout2 lay = make_layout2(N, P, dtype, Ms, Ma);
-  if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
+  const Layout2 lay = make_layout2(N, P, c.dtype, Ms, Ma);
+  if (c.workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
   const bool gn = index_grads2d(sc);
   // ordered: ORD_MAX, ORD_ACC over all passes, then k_fixed_finish2; at most one term per ray,
   // pass and entry
   const bool ordered = sc->deterministic != 0 && Ms + Ma > 0 && (g_seg || g_arc || gn);
-  if (ordered && workspace_bytes < lay.total_ordered) return TFRT_E_WORKSPACE;
+  if (ordered && c.workspace_bytes < lay.total_ordered) return TFRT_E_WORKSPACE;
   if (N == 0) return 0;
-  char* ws = static_cast<char*>(workspace);
-  const size_t n = N;
+  const Tape2<const T> tape(c.workspace, lay, N);
   Fixed2 fx = {nullptr, nullptr, nullptr, 0};
-  if (ordered) fx = fixed_region2(lay, ws, N * (int64_t)(P > 0 ? P : 1), st);
+  if (ordered)
+    fx = fixed_region2(lay, static_cast<char*>(c.workspace), N * (int64_t)(P > 0 ? P : 1), st);
   auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(cdiv(N, BLOCK)), dim3(BLOCK), 0, st,
-                       static_cast<const T*>(src_rays), src_stride, (int)N,
-                       reinterpret_cast<const T*>(ws + lay.rays), (int64_t)n,
-                       reinterpret_cast<const int32_t*>(ws + lay.rec_prim),
-                       reinterpret_cast<const double*>(ws + lay.rec_u),
-                       reinterpret_cast<const uint8_t*>(ws + lay.rec_bin),
-                       reinterpret_cast<const int32_t*>(ws + lay.rec_slot), P, *sc, L, fin, seed,
-                       g_seg, g_arc, fx);
+                       static_cast<const T*>(c.src), c.src_stride, (int)N, tape.rays_out(0),
+                       (int64_t)tape.n, tape.rec_prim(0), tape.rec_u(0), tape.rec_bin(0),
+                       tape.rec_slot(0), P, *sc, c.L, *c.fin, seed, g_seg, g_arc, fx);
   };
   if (!ordered) {
     if (gn) launch(k_backward2d_goal<T, Seed, true>);
@@ -1567,12 +1539,10 @@ static int trace2d_rows_t(const void* src_rays, int64_t src_stride, int64_t N, i
   const Layout2 lay = make_layout2(N, P, dtype);
   if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
   if (N == 0) return 0;
-  char* ws = static_cast<char*>(workspace);
+  const Tape2<const T> tape(workspace, lay, N);
   hipLaunchKernelGGL((k_rows2d<T>), dim3(cdiv(N, BLOCK)), dim3(BLOCK), 0, st,
-                     static_cast<const T*>(src_rays), src_stride, (int)N, (int64_t)N,
-                     reinterpret_cast<const int32_t*>(ws + lay.rec_prim),
-                     reinterpret_cast<const uint8_t*>(ws + lay.rec_bin),
-                     reinterpret_cast<const int32_t*>(ws + lay.rec_slot), P, fin,
+                     static_cast<const T*>(src_rays), src_stride, (int)N, (int64_t)tape.n,
+                     tape.rec_prim(0), tape.rec_bin(0), tape.rec_slot(0), P, fin,
                      static_cast<T*>(rows), rows_stride, row_face);
   return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
 }
@@ -1605,22 +1575,13 @@ static int seam2d(const void* rays, int64_t stride, int64_t n_rays, int32_t dtyp
   if (!rays || !x || !y || !valid || !ray_u || !prim_u || !gather) return TFRT_E_BADARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(cdiv(n_rays, BLOCK));
-  if (dtype == TFRT_F32) {
-    hipLaunchKernelGGL((k_seam2d<float, ARC>), grid, dim3(BLOCK), 0, st,
-                       static_cast<const float*>(rays), stride, (int)n_rays, prim, (int)M, ei, es,
-                       er, x, y, valid, ray_u, prim_u, gather);
-  } else if (dtype == TFRT_F64) {
-    hipLaunchKernelGGL((k_seam2d<double, ARC>), grid, dim3(BLOCK), 0, st,
-                       static_cast<const double*>(rays), stride, (int)n_rays, prim, (int)M, ei, es,
-                       er, x, y, valid, ray_u, prim_u, gather);
-  } else if (dtype == TFRT_F16) {
-    hipLaunchKernelGGL((k_seam2d<_Float16, ARC>), grid, dim3(BLOCK), 0, st,
-                       static_cast<const _Float16*>(rays), stride, (int)n_rays, prim, (int)M, ei,
-                       es, er, x, y, valid, ray_u, prim_u, gather);
-  } else {
-    return TFRT_E_UNSUPPORTED;
-  }
-  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  return dispatch_state(dtype, TFRT_E_UNSUPPORTED, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((k_seam2d<T, ARC>), grid, dim3(BLOCK), 0, st, static_cast<const T*>(rays),
+                       stride, (int)n_rays, prim, (int)M, ei, es, er, x, y, valid, ray_u, prim_u,
+                       gather);
+    return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  });
 }
 
 }  // namespace tfrt
@@ -1667,23 +1628,13 @@ int tfrt_trace2d_forward(const void* src_rays, int64_t src_stride, int64_t n_ray
   if (!scene2_ok(scene) || n_rays < 0 || n_rays >= (1ll << 31) - 4096 || max_passes < 0 ||
       !counts || !workspace || (n_rays > 0 && !src_rays) || src_stride < n_rays)
     return TFRT_E_BADARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (state_dtype == TFRT_F32)
-    return trace2d_forward_t<float>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                    dead_ray_length, max_passes, state_dtype, flags, finished,
-                                    active, stopped, dead, unfinished, unfinished_id, counts,
-                                    workspace, workspace_bytes, st);
-  if (state_dtype == TFRT_F64)
-    return trace2d_forward_t<double>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                     dead_ray_length, max_passes, state_dtype, flags, finished,
-                                     active, stopped, dead, unfinished, unfinished_id, counts,
-                                     workspace, workspace_bytes, st);
-  if (state_dtype == TFRT_F16)
-    return trace2d_forward_t<_Float16>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                     dead_ray_length, max_passes, state_dtype, flags, finished,
-                                     active, stopped, dead, unfinished, unfinished_id, counts,
-                                     workspace, workspace_bytes, st);
-  return TFRT_E_UNSUPPORTED;
+  const TraceCall<tfrt_scene2d> c = {
+      src_rays, src_stride, n_rays, scene, new_ray_length, dead_ray_length, max_passes,
+      state_dtype, flags, finished, active, stopped, dead, unfinished, unfinished_id, counts,
+      workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+  return dispatch_state(state_dtype, TFRT_E_UNSUPPORTED, [&](auto tag) {
+    return trace2d_forward_t<typename decltype(tag)::type>(c);
+  });
 }
 
 int tfrt_trace2d_backward(const void* src_rays, int64_t src_stride, int64_t n_rays,
@@ -1697,26 +1648,17 @@ int tfrt_trace2d_backward(const void* src_rays, int64_t src_stride, int64_t n_ra
                           void* workspace, size_t workspace_bytes, void* stream) {
   if (!scene2_ok(scene) || n_rays < 0 || max_passes < 0 || !counts || !workspace)
     return TFRT_E_BADARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (state_dtype == TFRT_F32)
-    return trace2d_backward_t<float>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                     dead_ray_length, max_passes, state_dtype, grad_finished,
-                                     cap_finished, grad_active, cap_active, grad_stopped,
-                                     cap_stopped, grad_dead, cap_dead, grad_seg, grad_arc,
-                                     grad_src_rays, counts, workspace, workspace_bytes, st);
-  if (state_dtype == TFRT_F64)
-    return trace2d_backward_t<double>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                      dead_ray_length, max_passes, state_dtype, grad_finished,
-                                      cap_finished, grad_active, cap_active, grad_stopped,
-                                      cap_stopped, grad_dead, cap_dead, grad_seg, grad_arc,
-                                      grad_src_rays, counts, workspace, workspace_bytes, st);
-  if (state_dtype == TFRT_F16)
-    return trace2d_backward_t<_Float16>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                      dead_ray_length, max_passes, state_dtype, grad_finished,
-                                      cap_finished, grad_active, cap_active, grad_stopped,
-                                      cap_stopped, grad_dead, cap_dead, grad_seg, grad_arc,
-                                      grad_src_rays, counts, workspace, workspace_bytes, st);
-  return TFRT_E_UNSUPPORTED;
+  SweepCall2 c = {src_rays, src_stride, n_rays, scene, new_ray_length, dead_ray_length,
+                  max_passes, state_dtype, counts, workspace, workspace_bytes,
+                  static_cast<hipStream_t>(stream)};
+  c.g_fin = grad_finished, c.cap_fin = cap_finished;
+  c.g_act = grad_active, c.cap_act = cap_active;
+  c.g_stp = grad_stopped, c.cap_stp = cap_stopped;
+  c.g_dead = grad_dead, c.cap_dead = cap_dead;
+  c.g_seg = grad_seg, c.g_arc = grad_arc, c.g_src = grad_src_rays;
+  return dispatch_state(state_dtype, TFRT_E_UNSUPPORTED, [&](auto tag) {
+    return trace2d_backward_t<typename decltype(tag)::type>(c);
+  });
 }
 
 size_t tfrt_trace2d_backward_goal_workspace_bytes(int64_t n_rays) {
@@ -1744,8 +1686,7 @@ int tfrt_trace2d_backward_goal(const void* src_rays, int64_t src_stride, int64_t
   if (n_rays > 0 && (!src_rays || src_stride < n_rays || !goal || !finished->rays ||
                      finished->capacity <= 0))
     return TFRT_E_BADARG;
-  if (state_dtype != TFRT_F32 && state_dtype != TFRT_F64 && state_dtype != TFRT_F16)
-    return TFRT_E_UNSUPPORTED;
+  if (!state_dtype_ok(state_dtype)) return TFRT_E_UNSUPPORTED;
   ChainGoal2 cg;
   cg.gf.n = n_fields;
   for (int c = 0; c < 6; ++c) {
@@ -1757,20 +1698,13 @@ int tfrt_trace2d_backward_goal(const void* src_rays, int64_t src_stride, int64_t
   cg.goal_ray_stride = goal_ray_stride;
   double* partial = static_cast<double*>(goal_workspace);
   const SeedGoal2 seed = {cg, partial};
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc;
-  if (state_dtype == TFRT_F32)
-    rc = trace2d_backward_goal_t<float>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                        max_passes, state_dtype, *finished, seed, grad_seg,
-                                        grad_arc, workspace, workspace_bytes, st);
-  else if (state_dtype == TFRT_F64)
-    rc = trace2d_backward_goal_t<double>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                         max_passes, state_dtype, *finished, seed, grad_seg,
-                                         grad_arc, workspace, workspace_bytes, st);
-  else
-    rc = trace2d_backward_goal_t<_Float16>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                           max_passes, state_dtype, *finished, seed, grad_seg,
-                                           grad_arc, workspace, workspace_bytes, st);
+  SweepCall2 c = {src_rays, src_stride, n_rays, scene, new_ray_length, /*dead_len=*/0.0,
+                  max_passes, state_dtype, counts, workspace, workspace_bytes,
+                  static_cast<hipStream_t>(stream)};
+  c.g_seg = grad_seg, c.g_arc = grad_arc, c.fin = finished;
+  const int rc = dispatch_state(state_dtype, TFRT_E_UNSUPPORTED, [&](auto tag) {
+    return trace2d_backward_goal_t<typename decltype(tag)::type>(c, seed);
+  });
   if (rc != 0) return rc;
   *pending = goal_pending2(partial, n_rays, counts, max_passes, n_fields, error_out, tests_total);
   return 0;
@@ -1786,19 +1720,11 @@ int tfrt_trace2d_rows(const void* src_rays, int64_t src_stride, int64_t n_rays,
   if (n_rays > 0 && (!src_rays || src_stride < n_rays || !rows || rows_stride < n_rays ||
                      !row_face || !finished->rays || finished->capacity <= 0))
     return TFRT_E_BADARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (state_dtype == TFRT_F32)
-    return trace2d_rows_t<float>(src_rays, src_stride, n_rays, max_passes, state_dtype, *finished,
-                                 rows, rows_stride, row_face, workspace, workspace_bytes, st);
-  if (state_dtype == TFRT_F64)
-    return trace2d_rows_t<double>(src_rays, src_stride, n_rays, max_passes, state_dtype,
-                                  *finished, rows, rows_stride, row_face, workspace,
-                                  workspace_bytes, st);
-  if (state_dtype == TFRT_F16)
-    return trace2d_rows_t<_Float16>(src_rays, src_stride, n_rays, max_passes, state_dtype,
-                                    *finished, rows, rows_stride, row_face, workspace,
-                                    workspace_bytes, st);
-  return TFRT_E_UNSUPPORTED;
+  return dispatch_state(state_dtype, TFRT_E_UNSUPPORTED, [&](auto tag) {
+    return trace2d_rows_t<typename decltype(tag)::type>(
+        src_rays, src_stride, n_rays, max_passes, state_dtype, *finished, rows, rows_stride,
+        row_face, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+  });
 }
 
 int tfrt_trace2d_backward_rows(const void* src_rays, int64_t src_stride, int64_t n_rays,
@@ -1823,22 +1749,13 @@ int tfrt_trace2d_backward_rows(const void* src_rays, int64_t src_stride, int64_t
   double* partial = static_cast<double*>(goal_workspace);
   const SeedRows2 seed = {grad_rows, grad_stride, err_terms, err_stride, err_ray_stride, n_terms,
                           partial};
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc;
-  if (state_dtype == TFRT_F32)
-    rc = trace2d_backward_goal_t<float>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                        max_passes, state_dtype, *finished, seed, grad_seg,
-                                        grad_arc, workspace, workspace_bytes, st);
-  else if (state_dtype == TFRT_F64)
-    rc = trace2d_backward_goal_t<double>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                         max_passes, state_dtype, *finished, seed, grad_seg,
-                                         grad_arc, workspace, workspace_bytes, st);
-  else if (state_dtype == TFRT_F16)
-    rc = trace2d_backward_goal_t<_Float16>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                           max_passes, state_dtype, *finished, seed, grad_seg,
-                                           grad_arc, workspace, workspace_bytes, st);
-  else
-    return TFRT_E_UNSUPPORTED;
+  SweepCall2 c = {src_rays, src_stride, n_rays, scene, new_ray_length, /*dead_len=*/0.0,
+                  max_passes, state_dtype, counts, workspace, workspace_bytes,
+                  static_cast<hipStream_t>(stream)};
+  c.g_seg = grad_seg, c.g_arc = grad_arc, c.fin = finished;
+  const int rc = dispatch_state(state_dtype, TFRT_E_UNSUPPORTED, [&](auto tag) {
+    return trace2d_backward_goal_t<typename decltype(tag)::type>(c, seed);
+  });
   if (rc != 0) return rc;
   *pending = goal_pending2(partial, n_rays, counts, max_passes, n_terms, error_out, tests_total);
   return 0;

@@ -2267,46 +2267,8 @@ __global__ __launch_bounds__(1024) void k_scan3d_one(const int32_t* __restrict__
                                                  int M) {
   const int n = *n_ptr;
   const int nblk = (n + BLOCK - 1) / BLOCK;
-  const int per = (nblk + 1023) / 1024;
-  const int b0 = min(nblk, (int)threadIdx.x * per), b1 = min(nblk, b0 + per);
-  int loc[4] = {0, 0, 0, 0};
-  for (int b = b0; b < b1; ++b)
-    for (int c = 0; c < 4; ++c) loc[c] += blockcnt[b * 4 + c];
-
-  __shared__ int wsum[16][4];
-  __shared__ int wbase[16][4];
   __shared__ int total[4];
-  const int lane = lane_id(), wave = threadIdx.x >> 6;
-  int pre[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    int v = loc[c];
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(v, d, 64);
-      if (lane >= d) v += o;
-    }
-    pre[c] = v - loc[c];  // exclusive within the wave
-    if (lane == 63) wsum[wave][c] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    int run = 0;
-    for (int w = 0; w < 16; ++w) {
-      wbase[w][threadIdx.x] = run;
-      run += wsum[w][threadIdx.x];
-    }
-    total[threadIdx.x] = run;
-  }
-  __syncthreads();
-  int run[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) run[c] = wbase[wave][c] + pre[c];
-  for (int b = b0; b < b1; ++b)
-    for (int c = 0; c < 4; ++c) {
-      blockoff[b * 4 + c] = run[c];
-      run[c] += blockcnt[b * 4 + c];
-    }
+  scan_rows_one<4>(blockcnt, blockoff, nblk, total);
   if (threadIdx.x < 4) {
     const int c = threadIdx.x;
     pass_counts[c] = total[c];
@@ -2624,20 +2586,6 @@ __device__ __forceinline__ void trace_inplace(const InplaceArgs<T>& a, const Bea
     beam_pass<T, RT>(W, g, lane, a.bundle, active, skip, p == 0, /*coherent_only=*/1, TFRT_WI_ARG,
                      work);
     wave_fence();
-#ifdef TFRT_BURN   // (tuning experiment: extra independent float32 FMAs per pass -- does the launch notice?)
-    {
-      float x0 = (float)lane, x1 = x0 + 1.f, x2 = x0 + 2.f, x3 = x0 + 3.f;
-#pragma unroll
-      for (int k = 0; k < TFRT_BURN; ++k) {
-        x0 = fmaf(x0, 1.0001f, 0.5f);
-        x1 = fmaf(x1, 1.0001f, 0.5f);
-        x2 = fmaf(x2, 1.0001f, 0.5f);
-        x3 = fmaf(x3, 1.0001f, 0.5f);
-        __asm__ volatile("" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3));
-      }
-      if (x0 + x1 + x2 + x3 == 12345.678f) W.best_i[lane] = -2;
-    }
-#endif
     TFRT_TICK_INIT;
     // (the struct waits in ONE vector register, a word per lane, and is unpacked here, pass by
     // pass: the register is made opaque first, so that the unpacking stays below the walk instead
@@ -3688,25 +3636,6 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
 
 // ------------------------------------------------------------------------------ misc
 
-__global__ void k_init(int32_t* nrays0, int n, int32_t* tail8, unsigned int* scan_ticket) {
-  if (threadIdx.x == 0) *nrays0 = n;
-  if (threadIdx.x < 8) tail8[threadIdx.x] = 0;
-  if (threadIdx.x == 0 && scan_ticket != nullptr) *scan_ticket = 0u;
-}
-
-template <typename T>
-__global__ __launch_bounds__(BLOCK) void k_copy_rays(const T* __restrict__ in, int64_t sin,
-                                                     const int32_t* __restrict__ id_in,
-                                                     const int32_t* __restrict__ n_ptr,
-                                                     T* __restrict__ out, int64_t sout,
-                                                     int32_t* __restrict__ id_out) {
-  const int n = *n_ptr;
-  const int i = blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= n) return;
-  for (int k = 0; k < 6; ++k) out[k * sout + i] = in[k * sin + i];
-  if (id_out) id_out[i] = id_in ? id_in[i] : i;
-}
-
 // finalize for the seam-level tfrt_intersect3d
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void k_finalize_seam(
@@ -3808,7 +3737,7 @@ struct Layout3 {
 
 static Layout3 make_layout(int64_t N, int64_t M, int P, int dtype, const Plan3& pl) {
   Layout3 L;
-  const size_t esz = dtype == TFRT_F64 ? 8 : (dtype == TFRT_F16 ? 2 : 4);
+  const size_t esz = state_bytes(dtype);
   const size_t n = N > 0 ? N : 1, m = M > 0 ? M : 1;
   size_t o = 0;
   auto take = [&](size_t bytes) {
@@ -3862,6 +3791,42 @@ static Layout3 make_layout(int64_t N, int64_t M, int P, int dtype, const Plan3& 
   L.total = o;
   return L;
 }
+
+// Typed view of the record a trace leaves in its workspace (Layout3), per-pass rows `n` slots
+// apart: the forward and the gather write it through a Tape3<T>, the sweeps read it through a
+// Tape3<const T> (T = const void where only the count rows are read).
+template <typename T>
+struct Tape3 {
+  template <typename U>
+  using as = std::conditional_t<std::is_const_v<T>, const U, U>;
+  using E = std::remove_const_t<T>;
+  as<char>* ws;
+  const Layout3& lay;
+  size_t n;
+  template <typename U>
+  as<U>* at(size_t offset) const { return reinterpret_cast<as<U>*>(ws + offset); }
+  Tape3(as<void>* workspace, const Layout3& layout, int64_t N)
+      : ws(static_cast<as<char>*>(workspace)), lay(layout), n(N > 0 ? N : 1) {}
+
+  as<int32_t>* nrays = at<int32_t>(lay.nrays);   // rays entering pass 1..P, and P + 1
+  as<double>* fnorm = at<double>(lay.fnorm);     // FaceTables
+  as<double>* feta = at<double>(lay.feta);
+  as<uint32_t>* wcount = at<uint32_t>(lay.wcount);   // in-place traces: see make_layout
+  as<int4>* wbase = at<int4>(lay.wbase);
+  as<InplaceTape>* tape_args = at<InplaceTape>(lay.tape_args);
+  // pass p's output rays, their ids and last faces; its records
+  T* rays_out(int p) const { return at<E>(lay.rays) + (size_t)p * 6 * n; }
+  as<int32_t>* ids(int p) const { return at<int32_t>(lay.rayid) + (size_t)p * n; }
+  as<int32_t>* last(int p) const { return at<int32_t>(lay.lasttri) + (size_t)p * n; }
+  as<int32_t>* rec_tri(int p) const { return at<int32_t>(lay.rec_tri) + (size_t)p * n; }
+  as<int32_t>* rec_slot(int p) const { return at<int32_t>(lay.rec_slot) + (size_t)p * n; }
+  as<double>* rec_t(int p) const { return at<double>(lay.rec_t) + (size_t)p * n; }
+  as<uint8_t>* rec_cls(int p) const { return at<uint8_t>(lay.rec_cls) + (size_t)p * n; }
+  PassIn<E> input(int p, const void* src, int64_t src_stride) const {
+    if (p == 0) return {static_cast<const E*>(src), src_stride, nullptr, nullptr};
+    return {rays_out(p - 1), (int64_t)n, ids(p - 1), last(p - 1)};
+  }
+};
 
 // ---- optional per-launch timing of the hot kernels (benchmark use only; see tfrt_profile_*)
 struct ProfRec {
@@ -3981,289 +3946,25 @@ static bool scene_ok(const tfrt_scene3d* sc) {
   return sc->n_faces == 0 || index_mode || value_mode;
 }
 
+// does this scene get the hierarchy (the grouped filter's clusters)?
+// (the grouped kernel packs member slot and ray slot into 32 bits: member slots < 2^24)
+static bool has_hierarchy(const tfrt_scene3d* sc, int64_t M) {
+  return M >= 4 * CLUSTER && M < (1 << 24) - CLUSTER && sc->cluster_order != nullptr;
+}
+
+// are the indices per face -- FaceTables.feta, which the forward's set-up launch fills and the
+// chain sweep reads?  (the indices of a face do not depend on the ray: one table column, or
+// "value" mode)
+static bool per_face_indices(const tfrt_scene3d* sc) {
+  const bool index_mode = sc->n_table != nullptr && sc->mat_in != nullptr;
+  return index_mode ? sc->n_table_uniform != 0 : (sc->n_in != nullptr && sc->n_out != nullptr);
+}
+
 // does this trace take the in-place route (tfrt_scene3d.in_place)?  The same test in the forward,
 // the reverse sweep and tfrt_trace3d_compact.
 static bool inplace_trace(const tfrt_scene3d* sc, int64_t N, int64_t M, int P) {
-  const bool hierarchy = M >= 4 * CLUSTER && M < (1 << 24) - CLUSTER && sc->cluster_order != nullptr;
-  return sc->in_place != 0 && sc->coherent_rays != 0 && sc->deterministic == 0 && hierarchy &&
-         N >= 64 && P >= 1;
-}
-
-template <typename T>
-static int inplace_gather_t(const void* src_rays, int64_t src_stride, int64_t N, int64_t M,
-                            const int32_t* ray_slot, double dead_len, int P, uint32_t flags, const tfrt_ray_out* fin, const tfrt_ray_out* act,
-                            const tfrt_ray_out* stp, const tfrt_ray_out* dead, void* unfinished,
-                            int32_t* unfinished_id, int32_t* counts, char* ws, const Layout3& lay,
-                            hipStream_t st) {
-  const tfrt_ray_out none = {nullptr, nullptr, nullptr, 0};
-  const size_t n = N > 0 ? N : 1;
-  GatherArgs<T> a;
-  a.src = static_cast<const T*>(src_rays);
-  a.src_stride = src_stride;
-  a.N = (int32_t)N;
-  a.P = P;
-  a.bundle = inplace_bundle(N);
-  a.nwaves = cdiv(N, a.bundle);
-  a.rays_ws = reinterpret_cast<const T*>(ws + lay.rays);
-  a.rec_tri = reinterpret_cast<const int32_t*>(ws + lay.rec_tri);
-  a.rec_t = reinterpret_cast<const double*>(ws + lay.rec_t);
-  a.rec_cls = reinterpret_cast<const uint8_t*>(ws + lay.rec_cls);
-  a.rec_slot = reinterpret_cast<int32_t*>(ws + lay.rec_slot);
-  a.n = (int64_t)n;
-  a.wbase = reinterpret_cast<const int4*>(ws + lay.wbase);
-  a.wstride = (int32_t)inplace_wstride(N);
-  a.counts = counts;
-  a.flags = flags;
-  a.dead_len = dead_len;
-  a.fin = fin ? *fin : none;
-  a.act = act ? *act : none;
-  a.stp = stp ? *stp : none;
-  a.dead = dead ? *dead : none;
-  a.unfinished = static_cast<T*>(unfinished);
-  a.unfinished_id = unfinished_id;
-  a.err = counts + (size_t)P * TFRT_COUNTS_PER_PASS + 6;
-  a.slot_of = ray_slot;
-  const uint32_t* wcount = reinterpret_cast<const uint32_t*>(ws + lay.wcount);
-  if (ray_slot != nullptr) {
-    // the caller's numbering: wavefronts of 64 of ITS consecutive rays, counted from the tape
-    // (their rows: behind the trace's own count rows and the two work rows)
-    a.bundle = 64;
-    a.nwaves = cdiv(N, 64);
-    uint32_t* wnat = reinterpret_cast<uint32_t*>(ws + lay.wcount) + (size_t)(P + 2) * a.wstride;
-    hipLaunchKernelGGL(k_inplace_count, dim3(a.nwaves), dim3(64), 0, st, a.rec_cls, a.n, (int)N, P,
-                       ray_slot, wnat, a.wstride);
-    wcount = wnat;
-  }
-  // the counts (per pass and class, bases, totals, tests) and every wavefront's bases, then the rows
-  hipLaunchKernelGGL(k_inplace_scan, dim3(P), dim3(1024), 0, st, wcount, a.nwaves, a.wstride, P,
-                     (int)N, (int)M, reinterpret_cast<int4*>(ws + lay.wbase), counts);
-  hipLaunchKernelGGL((k_inplace_gather<T>), dim3(a.nwaves), dim3(64), 0, st, a);
-  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
-}
-
-template <typename T>
-static int trace3d_forward_t(const void* src_rays, int64_t src_stride, int64_t N,
-                             const tfrt_scene3d* sc, double L, double dead_len, int P,
-                             int dtype, uint32_t flags, tfrt_ray_out* fin, tfrt_ray_out* act,
-                             tfrt_ray_out* stp, tfrt_ray_out* dead, void* unfinished,
-                             int32_t* unfinished_id, int32_t* counts, void* workspace,
-                             size_t workspace_bytes, hipStream_t st) {
-  const int M = (int)sc->n_faces;
-  Plan3 pl = make_plan(N, M);
-  const Layout3 lay = make_layout(N, M, P, dtype, pl);
-  if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
-  char* ws = static_cast<char*>(workspace);
-  double* c0 = reinterpret_cast<double*>(ws + lay.c0);
-  float4* sphere = reinterpret_cast<float4*>(ws + lay.sphere);
-  int32_t* nrays = reinterpret_cast<int32_t*>(ws + lay.nrays);
-  int32_t* blockcnt = reinterpret_cast<int32_t*>(ws + lay.blockcnt);
-  int32_t* blockoff = reinterpret_cast<int32_t*>(ws + lay.blockoff);
-  int32_t* rowtot = reinterpret_cast<int32_t*>(ws + lay.rowtot);
-  int32_t* rowbase = reinterpret_cast<int32_t*>(ws + lay.rowbase);
-  unsigned int* ticket = reinterpret_cast<unsigned int*>(ws + lay.ticket);
-  double* part_t = reinterpret_cast<double*>(ws + lay.part_t);
-  int32_t* part_i = reinterpret_cast<int32_t*>(ws + lay.part_i);
-  float* prep = reinterpret_cast<float*>(ws + lay.prep);
-  T* rays_ws = reinterpret_cast<T*>(ws + lay.rays);
-  int32_t* rayid = reinterpret_cast<int32_t*>(ws + lay.rayid);
-  int32_t* lasttri = reinterpret_cast<int32_t*>(ws + lay.lasttri);
-  int32_t* rec_tri = reinterpret_cast<int32_t*>(ws + lay.rec_tri);
-  int32_t* rec_slot = reinterpret_cast<int32_t*>(ws + lay.rec_slot);
-  double* rec_t = reinterpret_cast<double*>(ws + lay.rec_t);
-  uint8_t* rec_cls = reinterpret_cast<uint8_t*>(ws + lay.rec_cls);
-  FaceTables ft;
-  ft.fnorm = reinterpret_cast<double*>(ws + lay.fnorm);
-  // (the indices of a face do not depend on the ray: one table column, or "value" mode)
-  const bool index_mode = sc->n_table != nullptr && sc->mat_in != nullptr;
-  if (index_mode ? sc->n_table_uniform != 0 : (sc->n_in != nullptr && sc->n_out != nullptr))
-    ft.feta = reinterpret_cast<double*>(ws + lay.feta);
-  ft.mat_in = sc->mat_in;
-  ft.mat_out = sc->mat_out;
-  ft.n_table = sc->n_table;
-  ft.n_table_stride = sc->n_table_stride;
-  ft.n_in = sc->n_in;
-  ft.n_out = sc->n_out;
-  int32_t* tail = counts + (size_t)P * TFRT_COUNTS_PER_PASS;
-  const size_t n = N > 0 ? N : 1;
-
-  if (M <= 0) hipLaunchKernelGGL(k_init, dim3(1), dim3(64), 0, st, nrays, (int)N, tail, ticket);
-  if (M <= 0 && sc->clear_buffer != nullptr && sc->clear_count > 0)   // (no set-up launch to do it)
-    (void)hipMemsetAsync(sc->clear_buffer, 0, (size_t)sc->clear_count * sizeof(double), st);
-  Accel3 ac;
-  // (the grouped kernel packs member slot and ray slot into 32 bits: member slots < 2^24)
-  ac.order = (M >= 4 * CLUSTER && M < (1 << 24) - CLUSTER) ? sc->cluster_order : nullptr;
-  ac.n_clusters = cdiv(M > 0 ? M : 1, CLUSTER);
-  ac.csphere = reinterpret_cast<float4*>(ws + lay.csphere);
-  ac.cface = reinterpret_cast<int32_t*>(ws + lay.cface);
-  ac.clsphere = reinterpret_cast<float4*>(ws + lay.clsphere);
-  ac.susphere = reinterpret_cast<float4*>(ws + lay.susphere);
-  ac.crec = reinterpret_cast<float4*>(ws + lay.crec);
-  // Coherent rays: wavefronts take k_intersect_beam's shared walk first; one cluster chunk,
-  // classification in the kernels' epilogues
-  const bool coherent = sc->coherent_rays != 0 && ac.order != nullptr && N >= 64;
-  int32_t* hist_ab[2] = {reinterpret_cast<int32_t*>(ws + lay.hist_a),
-                         reinterpret_cast<int32_t*>(ws + lay.hist_b)};
-  if (coherent) {
-    pl.g_blocks = cdiv(N, (int64_t)BLOCK);
-    pl.g_chunks = 1;
-    pl.g_chunk_clusters = (ac.n_clusters + 7) / 8 * 8;
-  }
-  const bool inplace = inplace_trace(sc, N, M, P);
-  const bool rows_in_place = inplace && sc->in_place == 2;
-  InplaceTape tape = {};
-  if (inplace) {
-    tape.rays_ws = rays_ws;
-    tape.rec_tri = rec_tri;
-    tape.rec_t = rec_t;
-    tape.rec_cls = rec_cls;
-    tape.n = (int64_t)n;
-    tape.wcount = reinterpret_cast<uint32_t*>(ws + lay.wcount);
-    tape.wstride = (int64_t)inplace_wstride(N);
-    tape.catagory = sc->catagory;
-    tape.fnorm = ft.fnorm;
-    tape.feta = ft.feta;
-    tape.n_table = sc->n_table;
-    tape.mat_in = sc->mat_in;
-    tape.mat_out = sc->mat_out;
-    tape.n_table_stride = sc->n_table_stride;
-    tape.L = L;
-    if (rows_in_place) {
-      // the finished rows at the rays' own columns: nothing is compacted, nothing else is written
-      if (!fin || !fin->rays || !fin->face || !fin->ray_id || fin->capacity < N ||
-          (act && act->rays) || (stp && stp->rays) || (dead && dead->rays) || unfinished != nullptr)
-        return TFRT_E_BADARG;
-      tape.fin_rows = fin->rays;
-      tape.fin_cap = fin->capacity;
-      tape.fin_face = fin->face;
-      tape.fin_passes = fin->ray_id;
-    }
-  }
-  if (M > 0) {
-    if (ac.order != nullptr) {  // (the hierarchy kernel also does k_center's work)
-      const int cl_blocks = cdiv((int64_t)ac.n_clusters * CLUSTER, BLOCK);
-      const int n_super = cdiv(ac.n_clusters, SUPER);
-      hipLaunchKernelGGL(k_hierarchy_spheres, dim3(n_super + cl_blocks), dim3(BLOCK), 0, st,
-                         sc->face_verts, M, ac.order, c0, sc->size_epsilion, ac.n_clusters,
-                         n_super, ac.csphere, ac.cface, ac.clsphere, ac.crec, ac.susphere, nrays,
-                         (int)N, tail, ticket, hist_ab[0],
-                         (coherent && !inplace) ? pl.nblk * 4 + 1 : 0, ft,
-                         sc->clear_buffer, sc->clear_buffer ? sc->clear_count : 0, tape,
-                         inplace ? reinterpret_cast<InplaceTape*>(ws + lay.tape_args) : nullptr);
-    } else {
-      hipLaunchKernelGGL(k_center, dim3(1), dim3(BLOCK), 0, st, sc->face_verts, M, c0, nrays,
-                         (int)N, tail, ticket);
-      hipLaunchKernelGGL(k_spheres, dim3(cdiv(M, BLOCK)), dim3(BLOCK), 0, st, sc->face_verts, M,
-                         c0, sc->size_epsilion, sphere, ft, sc->clear_buffer,
-                         sc->clear_buffer ? sc->clear_count : 0);
-    }
-  }
-  const tfrt_ray_out none = {nullptr, nullptr, nullptr, 0};
-  if (inplace) {
-    // every pass in one launch, rays in place; then the counts, then (only if asked) the ray sets
-    InplaceArgs<T> a;
-    a.src = static_cast<const T*>(src_rays);
-    a.src_stride = src_stride;
-    a.N = (int32_t)N;
-    a.P = P;
-    a.bundle = inplace_bundle(N);
-    a.nwaves = cdiv(N, a.bundle);
-    a.tape = reinterpret_cast<const InplaceTape*>(ws + lay.tape_args);
-    const BeamScene bs = {ac.susphere, ac.clsphere, ac.csphere, ac.crec, sc->face_verts, c0,
-                          ac.n_clusters, cdiv(ac.n_clusters, SUPER), sc->intersect_epsilion,
-                          sc->size_epsilion, sc->ray_start_epsilion};
-    {
-      ProfScope prof(TFRT_PROF_INTERSECT, st);
-      if (rows_in_place)
-        hipLaunchKernelGGL((k_trace_inplace_rows<T>), dim3(a.nwaves), dim3(64), 0, st, a, bs);
-      else
-        hipLaunchKernelGGL((k_trace_inplace<T>), dim3(a.nwaves), dim3(64), 0, st, a, bs);
-    }
-    // (no room for ray sets: no scan either -- tfrt_trace3d_compact makes counts and sets later)
-    const bool want_rows = !rows_in_place &&
-                           ((fin && fin->rays) || (act && act->rays) || (stp && stp->rays) ||
-                            (dead && dead->rays) || unfinished != nullptr);
-    if (want_rows)
-      return inplace_gather_t<T>(src_rays, src_stride, N, M, sc->ray_slot, dead_len, P, flags, fin,
-                                 act, stp, dead, unfinished, unfinished_id, counts, ws, lay, st);
-    return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
-  }
-  const int chunks_used = ac.order == nullptr ? pl.chunks : pl.g_chunks;
-  for (int p = 0; p < P; ++p) {
-    const T* rin = p == 0 ? static_cast<const T*>(src_rays) : rays_ws + (size_t)(p - 1) * 6 * n;
-    const int64_t sin = p == 0 ? src_stride : (int64_t)n;
-    const int32_t* idin = p == 0 ? nullptr : rayid + (size_t)(p - 1) * n;
-    const int32_t* ltin = p == 0 ? nullptr : lasttri + (size_t)(p - 1) * n;
-    T* rout = rays_ws + (size_t)p * 6 * n;
-    Classify3 fz;
-    fz.catagory = sc->catagory;
-    fz.rec_tri = rec_tri + (size_t)p * n;
-    fz.rec_t = rec_t + (size_t)p * n;
-    fz.rec_cls = rec_cls + (size_t)p * n;
-    fz.blockcnt = blockcnt;
-    bool classified = false;
-    Ordered3 od;
-    if (coherent) {
-      od.nq = (int)N;
-      od.hist = hist_ab[p & 1];
-      od.left_list = reinterpret_cast<int32_t*>(ws + lay.left_list);
-      od.left_count = od.hist + (size_t)pl.nblk * 4;
-      od.left_total = tail + 7;
-      od.coherent_only = sc->coherent_only != 0;
-      od.n_super = cdiv(ac.n_clusters, SUPER);
-      fz.blockcnt = od.hist;
-    }
-    if (launch_intersect<T>(pl, st, rin, sin, nrays + p, ltin, sphere, sc->face_verts, c0, prep,
-                            (int64_t)n, M, sc->intersect_epsilion, sc->size_epsilion,
-                            sc->ray_start_epsilion, part_t, part_i, (int64_t)n, &ac,
-                            /*prep_ready=*/p > 0, &fz, &classified,
-                            coherent ? &od : nullptr) != 0)
-      return TFRT_E_LAUNCH;
-    int32_t* blockcnt_p = coherent ? od.hist : blockcnt;
-    if (!classified)
-      hipLaunchKernelGGL(k_classify3d, dim3(pl.nblk), dim3(BLOCK), 0, st, nrays + p, chunks_used,
-                         part_t, part_i, (int64_t)n, sc->catagory, rec_tri + (size_t)p * n,
-                         rec_t + (size_t)p * n, rec_cls + (size_t)p * n, blockcnt_p);
-    const bool grid_scan = pl.nblk >= SCAN_GRID_MIN_ROWS;
-    SelfScan ss;
-    if (coherent) {
-      ss.hist_next = hist_ab[(p + 1) & 1];
-      ss.hist_rows = pl.nblk;
-    }
-    if (pl.nblk <= SELF_SCAN_MAX_BLOCKS) {
-      ss.blockcnt = blockcnt_p;
-      ss.prev_counts = p > 0 ? counts + (size_t)(p - 1) * TFRT_COUNTS_PER_PASS : nullptr;
-      ss.counts_row = counts + (size_t)p * TFRT_COUNTS_PER_PASS;
-      ss.totals = tail;
-      ss.n_next = nrays + p + 1;
-      ss.n_tests = reinterpret_cast<unsigned long long*>(tail + 4);
-      ss.M = M;
-    } else if (grid_scan)
-      hipLaunchKernelGGL(k_scan3d, dim3(cdiv(pl.nblk, 1024)), dim3(1024), 0, st, nrays + p,
-                         blockcnt_p, blockoff, rowtot, rowbase, ticket,
-                         counts + (size_t)p * TFRT_COUNTS_PER_PASS, tail, nrays + p + 1,
-                         reinterpret_cast<unsigned long long*>(tail + 4), M);
-    else
-      hipLaunchKernelGGL(k_scan3d_one, dim3(1), dim3(1024), 0, st, nrays + p, blockcnt_p, blockoff,
-                         counts + (size_t)p * TFRT_COUNTS_PER_PASS, tail, nrays + p + 1,
-                         reinterpret_cast<unsigned long long*>(tail + 4), M);
-    ProfScope prof_react(TFRT_PROF_REACT, st);
-    hipLaunchKernelGGL((k_react3d<T>), dim3(pl.nblk), dim3(BLOCK), 0, st, rin, sin, nrays + p,
-                       idin, rec_tri + (size_t)p * n, rec_t + (size_t)p * n,
-                       rec_cls + (size_t)p * n, blockoff,
-                       grid_scan ? rowbase : static_cast<int32_t*>(nullptr),
-                       counts + (size_t)p * TFRT_COUNTS_PER_PASS, *sc, L, dead_len, flags, rout,
-                       (int64_t)n, rayid + (size_t)p * n, lasttri + (size_t)p * n,
-                       rec_slot + (size_t)p * n, fin ? *fin : none, act ? *act : none,
-                       stp ? *stp : none, dead ? *dead : none, tail + 6,
-                       (p + 1 < P && !coherent) ? prep : nullptr,
-                       (int64_t)n, c0, ss, ft.fnorm, ft.feta);
-  }
-  if (unfinished != nullptr && P > 0) {
-    hipLaunchKernelGGL((k_copy_rays<T>), dim3(pl.nblk), dim3(BLOCK), 0, st,
-                       rays_ws + (size_t)(P - 1) * 6 * n, (int64_t)n, rayid + (size_t)(P - 1) * n,
-                       nrays + P, static_cast<T*>(unfinished), (int64_t)N, unfinished_id);
-  }
-  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  return sc->in_place != 0 && sc->coherent_rays != 0 && sc->deterministic == 0 &&
+         has_hierarchy(sc, M) && N >= 64 && P >= 1;
 }
 
 // the built-in goal error folded into the sweep (tfrt_trace3d_backward_goal)
@@ -4277,46 +3978,317 @@ struct ChainGoal {
   int32_t* partial_cnt;
 };
 
+// What tfrt_trace3d_backward and tfrt_trace3d_backward_goal hand on.
+struct SweepCall3 {
+  const void* src;
+  int64_t src_stride, N;
+  const tfrt_scene3d* sc;
+  double L, dead_len;
+  int P, dtype;
+  const int32_t* counts;
+  void* workspace;
+  size_t workspace_bytes;
+  hipStream_t st;
+  // what differs between the two, set by name (null / 0 where an entry has none)
+  const double *g_fin, *g_act, *g_stp, *g_dead;
+  int64_t cap_fin, cap_act, cap_stp, cap_dead;
+  double *g_fverts, *g_src;
+  const ChainGoal* goal;
+};
+
 template <typename T>
-static int trace3d_backward_t(const void* src_rays, int64_t src_stride, int64_t N,
-                              const tfrt_scene3d* sc, double L, double dead_len, int P, int dtype,
-                              const double* g_fin, int64_t cap_fin, const double* g_act,
-                              int64_t cap_act, const double* g_stp, int64_t cap_stp,
-                              const double* g_dead, int64_t cap_dead, double* g_fverts,
-                              double* g_src, const int32_t* counts, void* workspace,
-                              size_t workspace_bytes, hipStream_t st,
-                              const ChainGoal* goal = nullptr) {
+static int inplace_gather_t(const TraceCall<tfrt_scene3d>& c, int64_t M, const int32_t* ray_slot,
+                            const Layout3& lay) {
+  const tfrt_ray_out none = {nullptr, nullptr, nullptr, 0};
+  const int64_t N = c.N;
+  const int P = c.P;
+  hipStream_t st = c.st;
+  const Tape3<T> tape(c.workspace, lay, N);
+  GatherArgs<T> a;
+  a.src = static_cast<const T*>(c.src);
+  a.src_stride = c.src_stride;
+  a.N = (int32_t)N;
+  a.P = P;
+  a.bundle = inplace_bundle(N);
+  a.nwaves = cdiv(N, a.bundle);
+  a.rays_ws = tape.rays_out(0);
+  a.rec_tri = tape.rec_tri(0);
+  a.rec_t = tape.rec_t(0);
+  a.rec_cls = tape.rec_cls(0);
+  a.rec_slot = tape.rec_slot(0);
+  a.n = (int64_t)tape.n;
+  a.wbase = tape.wbase;
+  a.wstride = (int32_t)inplace_wstride(N);
+  a.counts = c.counts;
+  a.flags = c.flags;
+  a.dead_len = c.dead_len;
+  a.fin = c.fin ? *c.fin : none;
+  a.act = c.act ? *c.act : none;
+  a.stp = c.stp ? *c.stp : none;
+  a.dead = c.dead ? *c.dead : none;
+  a.unfinished = static_cast<T*>(c.unfinished);
+  a.unfinished_id = c.unfinished_id;
+  a.err = c.counts + (size_t)P * TFRT_COUNTS_PER_PASS + 6;
+  a.slot_of = ray_slot;
+  const uint32_t* wcount = tape.wcount;
+  if (ray_slot != nullptr) {
+    // the caller's numbering: wavefronts of 64 of ITS consecutive rays, counted from the tape
+    // (their rows: behind the trace's own count rows and the two work rows)
+    a.bundle = 64;
+    a.nwaves = cdiv(N, 64);
+    uint32_t* wnat = tape.wcount + (size_t)(P + 2) * a.wstride;
+    hipLaunchKernelGGL(k_inplace_count, dim3(a.nwaves), dim3(64), 0, st, a.rec_cls, a.n, (int)N, P,
+                       ray_slot, wnat, a.wstride);
+    wcount = wnat;
+  }
+  // the counts (per pass and class, bases, totals, tests) and every wavefront's bases, then the rows
+  hipLaunchKernelGGL(k_inplace_scan, dim3(P), dim3(1024), 0, st, wcount, a.nwaves, a.wstride, P,
+                     (int)N, (int)M, tape.wbase, c.counts);
+  hipLaunchKernelGGL((k_inplace_gather<T>), dim3(a.nwaves), dim3(64), 0, st, a);
+  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+}
+
+template <typename T>
+static int trace3d_forward_t(const TraceCall<tfrt_scene3d>& c) {
+  const tfrt_scene3d* sc = c.sc;
+  const int64_t N = c.N;
+  const int P = c.P;
+  hipStream_t st = c.st;
+  const int M = (int)sc->n_faces;
+  Plan3 pl = make_plan(N, M);
+  const Layout3 lay = make_layout(N, M, P, c.dtype, pl);
+  if (c.workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
+  const Tape3<T> tape(c.workspace, lay, N);
+  // (the forward's own regions: nobody else reads them)
+  char* ws = static_cast<char*>(c.workspace);
+  double* c0 = reinterpret_cast<double*>(ws + lay.c0);
+  float4* sphere = reinterpret_cast<float4*>(ws + lay.sphere);
+  int32_t* blockcnt = reinterpret_cast<int32_t*>(ws + lay.blockcnt);
+  int32_t* blockoff = reinterpret_cast<int32_t*>(ws + lay.blockoff);
+  int32_t* rowtot = reinterpret_cast<int32_t*>(ws + lay.rowtot);
+  int32_t* rowbase = reinterpret_cast<int32_t*>(ws + lay.rowbase);
+  unsigned int* ticket = reinterpret_cast<unsigned int*>(ws + lay.ticket);
+  double* part_t = reinterpret_cast<double*>(ws + lay.part_t);
+  int32_t* part_i = reinterpret_cast<int32_t*>(ws + lay.part_i);
+  float* prep = reinterpret_cast<float*>(ws + lay.prep);
+  int32_t* hist_ab[2] = {reinterpret_cast<int32_t*>(ws + lay.hist_a),
+                         reinterpret_cast<int32_t*>(ws + lay.hist_b)};
+  int32_t* left_list = reinterpret_cast<int32_t*>(ws + lay.left_list);
+  int32_t* nrays = tape.nrays;
+  FaceTables ft;
+  ft.fnorm = tape.fnorm;
+  if (per_face_indices(sc)) ft.feta = tape.feta;
+  ft.mat_in = sc->mat_in;
+  ft.mat_out = sc->mat_out;
+  ft.n_table = sc->n_table;
+  ft.n_table_stride = sc->n_table_stride;
+  ft.n_in = sc->n_in;
+  ft.n_out = sc->n_out;
+  int32_t* tail = c.counts + (size_t)P * TFRT_COUNTS_PER_PASS;
+  const int64_t n = (int64_t)tape.n;
+
+  if (M <= 0) hipLaunchKernelGGL(k_init<>, dim3(1), dim3(64), 0, st, nrays, (int)N, tail, ticket);
+  if (M <= 0 && sc->clear_buffer != nullptr && sc->clear_count > 0)   // (no set-up launch to do it)
+    (void)hipMemsetAsync(sc->clear_buffer, 0, (size_t)sc->clear_count * sizeof(double), st);
+  const Accel3 ac = {has_hierarchy(sc, M) ? sc->cluster_order : nullptr,
+                     cdiv(M > 0 ? M : 1, CLUSTER),
+                     reinterpret_cast<float4*>(ws + lay.csphere),
+                     reinterpret_cast<int32_t*>(ws + lay.cface),
+                     reinterpret_cast<float4*>(ws + lay.clsphere),
+                     reinterpret_cast<float4*>(ws + lay.susphere),
+                     reinterpret_cast<float4*>(ws + lay.crec)};
+  // Coherent rays: wavefronts take k_intersect_beam's shared walk first; one cluster chunk,
+  // classification in the kernels' epilogues
+  const bool coherent = sc->coherent_rays != 0 && ac.order != nullptr && N >= 64;
+  if (coherent) {
+    pl.g_blocks = cdiv(N, (int64_t)BLOCK);
+    pl.g_chunks = 1;
+    pl.g_chunk_clusters = (ac.n_clusters + 7) / 8 * 8;
+  }
+  const bool inplace = inplace_trace(sc, N, M, P);
+  const bool rows_in_place = inplace && sc->in_place == 2;
+  InplaceTape it = {};
+  if (inplace) {
+    it.rays_ws = tape.rays_out(0);
+    it.rec_tri = tape.rec_tri(0);
+    it.rec_t = tape.rec_t(0);
+    it.rec_cls = tape.rec_cls(0);
+    it.n = n;
+    it.wcount = tape.wcount;
+    it.wstride = (int64_t)inplace_wstride(N);
+    it.catagory = sc->catagory;
+    it.fnorm = ft.fnorm;
+    it.feta = ft.feta;
+    it.n_table = sc->n_table;
+    it.mat_in = sc->mat_in;
+    it.mat_out = sc->mat_out;
+    it.n_table_stride = sc->n_table_stride;
+    it.L = c.L;
+    if (rows_in_place) {
+      // the finished rows at the rays' own columns: nothing is compacted, nothing else is written
+      if (!c.fin || !c.fin->rays || !c.fin->face || !c.fin->ray_id || c.fin->capacity < N ||
+          (c.act && c.act->rays) || (c.stp && c.stp->rays) || (c.dead && c.dead->rays) ||
+          c.unfinished != nullptr)
+        return TFRT_E_BADARG;
+      it.fin_rows = c.fin->rays;
+      it.fin_cap = c.fin->capacity;
+      it.fin_face = c.fin->face;
+      it.fin_passes = c.fin->ray_id;
+    }
+  }
+  if (M > 0) {
+    if (ac.order != nullptr) {  // (the hierarchy kernel also does k_center's work)
+      const int cl_blocks = cdiv((int64_t)ac.n_clusters * CLUSTER, BLOCK);
+      const int n_super = cdiv(ac.n_clusters, SUPER);
+      hipLaunchKernelGGL(k_hierarchy_spheres, dim3(n_super + cl_blocks), dim3(BLOCK), 0, st,
+                         sc->face_verts, M, ac.order, c0, sc->size_epsilion, ac.n_clusters,
+                         n_super, ac.csphere, ac.cface, ac.clsphere, ac.crec, ac.susphere, nrays,
+                         (int)N, tail, ticket, hist_ab[0],
+                         (coherent && !inplace) ? pl.nblk * 4 + 1 : 0, ft,
+                         sc->clear_buffer, sc->clear_buffer ? sc->clear_count : 0, it,
+                         inplace ? tape.tape_args : nullptr);
+    } else {
+      hipLaunchKernelGGL(k_center, dim3(1), dim3(BLOCK), 0, st, sc->face_verts, M, c0, nrays,
+                         (int)N, tail, ticket);
+      hipLaunchKernelGGL(k_spheres, dim3(cdiv(M, BLOCK)), dim3(BLOCK), 0, st, sc->face_verts, M,
+                         c0, sc->size_epsilion, sphere, ft, sc->clear_buffer,
+                         sc->clear_buffer ? sc->clear_count : 0);
+    }
+  }
+  const tfrt_ray_out none = {nullptr, nullptr, nullptr, 0};
+  if (inplace) {
+    // every pass in one launch, rays in place; then the counts, then (only if asked) the ray sets
+    InplaceArgs<T> a;
+    a.src = static_cast<const T*>(c.src);
+    a.src_stride = c.src_stride;
+    a.N = (int32_t)N;
+    a.P = P;
+    a.bundle = inplace_bundle(N);
+    a.nwaves = cdiv(N, a.bundle);
+    a.tape = tape.tape_args;
+    const BeamScene bs = {ac.susphere, ac.clsphere, ac.csphere, ac.crec, sc->face_verts, c0,
+                          ac.n_clusters, cdiv(ac.n_clusters, SUPER), sc->intersect_epsilion,
+                          sc->size_epsilion, sc->ray_start_epsilion};
+    {
+      ProfScope prof(TFRT_PROF_INTERSECT, st);
+      if (rows_in_place)
+        hipLaunchKernelGGL((k_trace_inplace_rows<T>), dim3(a.nwaves), dim3(64), 0, st, a, bs);
+      else
+        hipLaunchKernelGGL((k_trace_inplace<T>), dim3(a.nwaves), dim3(64), 0, st, a, bs);
+    }
+    // (no room for ray sets: no scan either -- tfrt_trace3d_compact makes counts and sets later)
+    const bool want_rows = !rows_in_place &&
+                           ((c.fin && c.fin->rays) || (c.act && c.act->rays) ||
+                            (c.stp && c.stp->rays) || (c.dead && c.dead->rays) ||
+                            c.unfinished != nullptr);
+    if (want_rows) return inplace_gather_t<T>(c, M, sc->ray_slot, lay);
+    return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  }
+  const int chunks_used = ac.order == nullptr ? pl.chunks : pl.g_chunks;
+  for (int p = 0; p < P; ++p) {
+    const PassIn<T> in = tape.input(p, c.src, c.src_stride);
+    int32_t* pass_counts = c.counts + (size_t)p * TFRT_COUNTS_PER_PASS;
+    Classify3 fz;
+    fz.catagory = sc->catagory;
+    fz.rec_tri = tape.rec_tri(p);
+    fz.rec_t = tape.rec_t(p);
+    fz.rec_cls = tape.rec_cls(p);
+    fz.blockcnt = blockcnt;
+    bool classified = false;
+    Ordered3 od;
+    if (coherent) {
+      od.nq = (int)N;
+      od.hist = hist_ab[p & 1];
+      od.left_list = left_list;
+      od.left_count = od.hist + (size_t)pl.nblk * 4;
+      od.left_total = tail + 7;
+      od.coherent_only = sc->coherent_only != 0;
+      od.n_super = cdiv(ac.n_clusters, SUPER);
+      fz.blockcnt = od.hist;
+    }
+    if (launch_intersect<T>(pl, st, in.rays, in.stride, nrays + p, in.last, sphere,
+                            sc->face_verts, c0, prep, n, M, sc->intersect_epsilion,
+                            sc->size_epsilion, sc->ray_start_epsilion, part_t, part_i, n, &ac,
+                            /*prep_ready=*/p > 0, &fz, &classified,
+                            coherent ? &od : nullptr) != 0)
+      return TFRT_E_LAUNCH;
+    int32_t* blockcnt_p = coherent ? od.hist : blockcnt;
+    if (!classified)
+      hipLaunchKernelGGL(k_classify3d, dim3(pl.nblk), dim3(BLOCK), 0, st, nrays + p, chunks_used,
+                         part_t, part_i, n, sc->catagory, tape.rec_tri(p), tape.rec_t(p),
+                         tape.rec_cls(p), blockcnt_p);
+    const bool grid_scan = pl.nblk >= SCAN_GRID_MIN_ROWS;
+    SelfScan ss;
+    if (coherent) {
+      ss.hist_next = hist_ab[(p + 1) & 1];
+      ss.hist_rows = pl.nblk;
+    }
+    if (pl.nblk <= SELF_SCAN_MAX_BLOCKS) {
+      ss.blockcnt = blockcnt_p;
+      ss.prev_counts = p > 0 ? c.counts + (size_t)(p - 1) * TFRT_COUNTS_PER_PASS : nullptr;
+      ss.counts_row = pass_counts;
+      ss.totals = tail;
+      ss.n_next = nrays + p + 1;
+      ss.n_tests = reinterpret_cast<unsigned long long*>(tail + 4);
+      ss.M = M;
+    } else if (grid_scan)
+      hipLaunchKernelGGL(k_scan3d, dim3(cdiv(pl.nblk, 1024)), dim3(1024), 0, st, nrays + p,
+                         blockcnt_p, blockoff, rowtot, rowbase, ticket, pass_counts,
+                         tail, nrays + p + 1, reinterpret_cast<unsigned long long*>(tail + 4), M);
+    else
+      hipLaunchKernelGGL(k_scan3d_one, dim3(1), dim3(1024), 0, st, nrays + p, blockcnt_p,
+                         blockoff, pass_counts, tail, nrays + p + 1,
+                         reinterpret_cast<unsigned long long*>(tail + 4), M);
+    ProfScope prof_react(TFRT_PROF_REACT, st);
+    hipLaunchKernelGGL((k_react3d<T>), dim3(pl.nblk), dim3(BLOCK), 0, st, in.rays, in.stride,
+                       nrays + p, in.ids, tape.rec_tri(p), tape.rec_t(p), tape.rec_cls(p),
+                       blockoff, grid_scan ? rowbase : static_cast<int32_t*>(nullptr),
+                       pass_counts, *sc, c.L, c.dead_len, c.flags, tape.rays_out(p), n, tape.ids(p),
+                       tape.last(p), tape.rec_slot(p), c.fin ? *c.fin : none,
+                       c.act ? *c.act : none, c.stp ? *c.stp : none, c.dead ? *c.dead : none, tail + 6,
+                       (p + 1 < P && !coherent) ? prep : nullptr, n, c0, ss, ft.fnorm, ft.feta);
+  }
+  if (c.unfinished != nullptr && P > 0) {
+    hipLaunchKernelGGL((k_copy_rays<T, 6>), dim3(pl.nblk), dim3(BLOCK), 0, st, tape.rays_out(P - 1),
+                       n, tape.ids(P - 1), nrays + P, static_cast<T*>(c.unfinished), (int64_t)N,
+                       c.unfinished_id);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+}
+
+template <typename T>
+static int trace3d_backward_t(const SweepCall3& c) {
+  const tfrt_scene3d* sc = c.sc;
+  const int64_t N = c.N;
+  const int P = c.P;
+  hipStream_t st = c.st;
   const int M = (int)sc->n_faces;
   const Plan3 pl = make_plan(N, M);
-  const Layout3 lay = make_layout(N, M, P, dtype, pl);
-  if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
-  char* ws = static_cast<char*>(workspace);
-  const int32_t* nrays = reinterpret_cast<int32_t*>(ws + lay.nrays);
-  const T* rays_ws = reinterpret_cast<T*>(ws + lay.rays);
-  const int32_t* rayid = reinterpret_cast<int32_t*>(ws + lay.rayid);
-  const int32_t* rec_tri = reinterpret_cast<int32_t*>(ws + lay.rec_tri);
-  const int32_t* rec_slot = reinterpret_cast<int32_t*>(ws + lay.rec_slot);
-  const double* rec_t = reinterpret_cast<double*>(ws + lay.rec_t);
-  const uint8_t* rec_cls = reinterpret_cast<uint8_t*>(ws + lay.rec_cls);
+  const Layout3 lay = make_layout(N, M, P, c.dtype, pl);
+  if (c.workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
+  const Tape3<const T> tape(c.workspace, lay, N);
+  // (the sweep's own regions)
+  char* ws = static_cast<char*>(c.workspace);
+  const int32_t* nrays = tape.nrays;
   using G = typename SweepStore<T>::type;  // (the regions are sized for float64)
   G* gbuf = reinterpret_cast<G*>(ws + lay.gbuf);
-  const size_t n = N > 0 ? N : 1;
+  G* stash_g_all = reinterpret_cast<G*>(ws + lay.stash_g);
+  int32_t* stash_face_all = reinterpret_cast<int32_t*>(ws + lay.stash_face);
+  unsigned long long* fix_acc = reinterpret_cast<unsigned long long*>(ws + lay.fix_acc);
+  uint8_t* fix_flag = reinterpret_cast<uint8_t*>(ws + lay.fix_flag);
+  unsigned long long* fix_max = reinterpret_cast<unsigned long long*>(ws + lay.fix_max);
+  const int64_t n = (int64_t)tape.n;
   // Windowed LDS accumulation of the face gradients (k_face_accumulate): every window block
   // scans its chunk's face ids, so it is used while the windows are few; beyond that (and for
   // small ray counts) k_backward3d adds straight into g_fverts with float64 atomics -- faces are
   // then so many that they see little contention.
   const int windows = cdiv(M > 0 ? M : 1, FACE_WINDOW);
-  const bool ordered = sc->deterministic != 0 && M > 0 && g_fverts != nullptr;
+  const bool ordered = sc->deterministic != 0 && M > 0 && c.g_fverts != nullptr;
   // (coherent rays: the wavefront's rays hit few faces; k_backward3d sums them itself)
-  const bool wave_sums = !ordered && sc->coherent_rays != 0 && M > 0 && g_fverts != nullptr;
+  const bool wave_sums = !ordered && sc->coherent_rays != 0 && M > 0 && c.g_fverts != nullptr;
   const bool stash = ordered || (!wave_sums && M > 0 && N >= 16384 && windows <= 32);
-  unsigned long long* fix_acc = reinterpret_cast<unsigned long long*>(ws + lay.fix_acc);
-  uint8_t* fix_flag = reinterpret_cast<uint8_t*>(ws + lay.fix_flag);
-  unsigned long long* fix_max = reinterpret_cast<unsigned long long*>(ws + lay.fix_max);
   if (ordered)  // (fix_acc, fix_flag and fix_max are adjacent: one clear)
     (void)hipMemsetAsync(fix_acc, 0, lay.total - lay.fix_acc, st);
-  G* stash_g_all = reinterpret_cast<G*>(ws + lay.stash_g);
-  int32_t* stash_face_all = reinterpret_cast<int32_t*>(ws + lay.stash_face);
   // ray slots per accumulate block, measured at 1M rays x 11 windows (us for the three passes,
   // target pass first): 2048 -> 37/50/54, 4096 -> 21/33/38, 8192 -> 15/37/34, 16384 -> 12/49/36.
   // Every block zeroes and flushes its window, so big chunks win while the blocks still fill
@@ -4327,44 +4299,45 @@ static int trace3d_backward_t(const void* src_rays, int64_t src_stride, int64_t 
   while (acc_chunk > 1024 && (int64_t)cdiv(N, acc_chunk) * windows < 256) acc_chunk /= 2;
   const bool inplace = inplace_trace(sc, N, M, P);
   if (inplace && !wave_sums) return TFRT_E_UNSUPPORTED;   // (deterministic: not with in_place)
-  if ((wave_sums && P >= 1 && (P <= CHAIN_MAXP || inplace)) || goal != nullptr) {
+  if ((wave_sums && P >= 1 && (P <= CHAIN_MAXP || inplace)) || c.goal != nullptr) {
     // coherent rays: the whole sweep in one launch (k_backward_chain)
     if (!(wave_sums && P >= 1 && (P <= CHAIN_MAXP || inplace))) return TFRT_E_UNSUPPORTED;
     ChainArgs<T> a;
-    a.src = static_cast<const T*>(src_rays);
-    a.src_stride = src_stride;
-    a.rays_ws = rays_ws;
+    a.src = static_cast<const T*>(c.src);
+    a.src_stride = c.src_stride;
+    a.rays_ws = tape.rays_out(0);
     a.nrays = nrays;
-    a.rayid = rayid;
-    a.rec_tri = rec_tri;
-    a.rec_slot = rec_slot;
-    a.rec_t = rec_t;
-    a.rec_cls = rec_cls;
-    a.counts = counts;
-    a.n = (int64_t)n;
+    a.rayid = tape.ids(0);
+    a.rec_tri = tape.rec_tri(0);
+    a.rec_slot = tape.rec_slot(0);
+    a.rec_t = tape.rec_t(0);
+    a.rec_cls = tape.rec_cls(0);
+    a.counts = c.counts;
+    a.n = n;
     a.P = P;
-    a.L = L;
-    a.dead_len = dead_len;
-    a.g_fin = g_fin;
-    a.g_act = g_act;
-    a.g_stp = g_stp;
-    a.g_dead = g_dead;
-    a.cap_fin = cap_fin;
-    a.cap_act = cap_act;
-    a.cap_stp = cap_stp;
-    a.cap_dead = cap_dead;
-    a.g_src = g_src;
+    a.L = c.L;
+    a.dead_len = c.dead_len;
+    a.g_fin = c.g_fin;
+    a.g_act = c.g_act;
+    a.g_stp = c.g_stp;
+    a.g_dead = c.g_dead;
+    a.cap_fin = c.cap_fin;
+    a.cap_act = c.cap_act;
+    a.cap_stp = c.cap_stp;
+    a.cap_dead = c.cap_dead;
+    a.g_src = c.g_src;
     a.N = N;
-    a.g_fverts = g_fverts;
+    a.g_fverts = c.g_fverts;
     // (in-place tape: class gradients are read through rec_slot, which k_inplace_gather fills;
     // a sweep that is handed none but the built-in goal's never reads it)
     // 3 (tfrt_scene3d.in_place == 2): the finished rows' gradient sits at the rays' own columns,
     // no other class carries one -- like 2, rec_slot is never read
-    if (inplace && sc->in_place == 2 && (g_act || g_stp || g_dead || goal != nullptr || cap_fin < N))
+    if (inplace && sc->in_place == 2 &&
+        (c.g_act || c.g_stp || c.g_dead || c.goal != nullptr || c.cap_fin < N))
       return TFRT_E_BADARG;
     a.inplace = !inplace ? 0
                 : (sc->in_place == 2 ? 3
-                   : ((g_fin || g_act || g_stp || g_dead || goal == nullptr) ? 1 : 2));
+                   : ((c.g_fin || c.g_act || c.g_stp || c.g_dead || c.goal == nullptr) ? 1 : 2));
     a.chain_in_lds = P <= CHAIN_MAXP ? 1 : 0;
     a.fin_rays = nullptr;
     a.fin_cap = 0;
@@ -4373,23 +4346,18 @@ static int trace3d_backward_t(const void* src_rays, int64_t src_stride, int64_t 
     a.goal_stride = a.goal_ray_stride = 0;
     a.partial = nullptr;
     a.partial_cnt = nullptr;
-    {  // (the per-face indices the forward's set-up launch left, under the same condition)
-      const bool index_mode = sc->n_table != nullptr && sc->mat_in != nullptr;
-      const bool per_face = index_mode ? sc->n_table_uniform != 0
-                                       : (sc->n_in != nullptr && sc->n_out != nullptr);
-      a.feta = per_face ? reinterpret_cast<const double*>(ws + lay.feta) : nullptr;
-    }
+    a.feta = per_face_indices(sc) ? tape.feta : nullptr;
     const size_t chain_lds = a.chain_in_lds ? (size_t)P * 64 * sizeof(int4) : 0;
     ProfScope prof_bwd(TFRT_PROF_BACKWARD, st);
-    if (goal != nullptr) {
-      a.fin_rays = static_cast<const T*>(goal->fin_rays);
-      a.fin_cap = goal->fin_cap;
-      a.gf = goal->gf;
-      a.goal = goal->goal;
-      a.goal_stride = goal->goal_stride;
-      a.goal_ray_stride = goal->goal_ray_stride;
-      a.partial = goal->partial;
-      a.partial_cnt = goal->partial_cnt;
+    if (c.goal != nullptr) {
+      a.fin_rays = static_cast<const T*>(c.goal->fin_rays);
+      a.fin_cap = c.goal->fin_cap;
+      a.gf = c.goal->gf;
+      a.goal = c.goal->goal;
+      a.goal_stride = c.goal->goal_stride;
+      a.goal_ray_stride = c.goal->goal_ray_stride;
+      a.partial = c.goal->partial;
+      a.partial_cnt = c.goal->partial_cnt;
       if (N > 0 && sc->grad_n_in != nullptr)
         hipLaunchKernelGGL((k_backward_chain<T, 1, true, true>), dim3(cdiv(N, 64)), dim3(64),
                            chain_lds, st, a, *sc);
@@ -4406,25 +4374,22 @@ static int trace3d_backward_t(const void* src_rays, int64_t src_stride, int64_t 
     return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
   }
   for (int p = P - 1; p >= 0; --p) {
-    const T* rin = p == 0 ? static_cast<const T*>(src_rays) : rays_ws + (size_t)(p - 1) * 6 * n;
-    const int64_t sin = p == 0 ? src_stride : (int64_t)n;
-    const int32_t* idin = p == 0 ? nullptr : rayid + (size_t)(p - 1) * n;
+    const PassIn<T> in = tape.input(p, c.src, c.src_stride);
     const G* g_child = (p == P - 1) ? nullptr : gbuf + (size_t)((p + 1) & 1) * 6 * n;
     // (the first pass's ray gradient goes to the caller's g_src, or nowhere)
     G* g_out = p == 0 ? nullptr : gbuf + (size_t)(p & 1) * 6 * n;
-    double* g_src_out = p == 0 ? g_src : nullptr;
-    const int64_t out_stride = p == 0 ? N : (int64_t)n;
+    double* g_src_out = p == 0 ? c.g_src : nullptr;
+    const int64_t out_stride = p == 0 ? N : n;
     G* stash_g = stash_g_all + (size_t)p * 9 * n;
     int32_t* stash_face = stash_face_all + (size_t)p * n;
     ProfScope prof_bwd(TFRT_PROF_BACKWARD, st);
     constexpr int BWD_BW = 1;
     hipLaunchKernelGGL((k_backward3d<T, BWD_BW>), dim3(cdiv(N, 64 * BWD_BW)), dim3(64 * BWD_BW), 0,
-                       st, rin, sin, nrays + p,
-                       idin, rec_tri + (size_t)p * n, rec_t + (size_t)p * n,
-                       rec_cls + (size_t)p * n, rec_slot + (size_t)p * n,
-                       counts + (size_t)p * TFRT_COUNTS_PER_PASS, *sc, L, dead_len, g_child,
-                       (int64_t)n, g_fin, cap_fin, g_act, cap_act, g_stp, cap_stp, g_dead,
-                       cap_dead, g_out, g_src_out, out_stride, g_fverts,
+                       st, in.rays, in.stride, nrays + p, in.ids, tape.rec_tri(p), tape.rec_t(p),
+                       tape.rec_cls(p), tape.rec_slot(p),
+                       c.counts + (size_t)p * TFRT_COUNTS_PER_PASS, *sc, c.L, c.dead_len, g_child,
+                       n, c.g_fin, c.cap_fin, c.g_act, c.cap_act, c.g_stp, c.cap_stp,
+                       c.g_dead, c.cap_dead, g_out, g_src_out, out_stride, c.g_fverts,
                        stash ? stash_g : nullptr, stash ? stash_face : nullptr, wave_sums ? 1 : 0);
     if (ordered) {
       // two-entry scale buffer, alternating per pass (each pass's conversion clears the other)
@@ -4434,14 +4399,14 @@ static int trace3d_backward_t(const void* src_rays, int64_t src_stride, int64_t 
       hipLaunchKernelGGL((k_face_accumulate_fixed<G>), dim3(pl.nblk), dim3(BLOCK), 0, st, nrays + p,
                          stash_face, stash_g, mx, fix_acc, fix_flag);
       hipLaunchKernelGGL(k_fixed_finish, dim3(cdiv((int64_t)M * 9, BLOCK)), dim3(BLOCK), 0, st,
-                         (int64_t)M * 9, mx, fix_max + (((P - 1 - p) & 1) ^ 1), fix_acc, fix_flag,
-                         g_fverts);
+                         (int64_t)M * 9, mx, fix_max + (((P - 1 - p) & 1) ^ 1), fix_acc,
+                         fix_flag, c.g_fverts);
     }
   }
   if (stash && !ordered && P > 0) {
     ProfScope prof_acc(TFRT_PROF_ACCUMULATE, st);
     hipLaunchKernelGGL((k_face_accumulate<G>), dim3(cdiv(N, acc_chunk), windows), dim3(1024), 0, st,
-                       nrays, P, (int64_t)n, stash_face_all, stash_g_all, acc_chunk, M, g_fverts);
+                       nrays, P, n, stash_face_all, stash_g_all, acc_chunk, M, c.g_fverts);
   }
   return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
 }
@@ -4470,23 +4435,13 @@ int tfrt_trace3d_forward(const void* src_rays, int64_t src_stride, int64_t n_ray
   if (!scene_ok(scene) || n_rays < 0 || n_rays >= (1ll << 31) - 4096 || max_passes < 0 ||
       !counts || !workspace || (n_rays > 0 && !src_rays) || src_stride < n_rays)
     return TFRT_E_BADARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (state_dtype == TFRT_F32)
-    return trace3d_forward_t<float>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                    dead_ray_length, max_passes, state_dtype, flags, finished,
-                                    active, stopped, dead, unfinished, unfinished_id, counts,
-                                    workspace, workspace_bytes, st);
-  if (state_dtype == TFRT_F64)
-    return trace3d_forward_t<double>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                     dead_ray_length, max_passes, state_dtype, flags, finished,
-                                     active, stopped, dead, unfinished, unfinished_id, counts,
-                                     workspace, workspace_bytes, st);
-  if (state_dtype == TFRT_F16)
-    return trace3d_forward_t<_Float16>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                     dead_ray_length, max_passes, state_dtype, flags, finished,
-                                     active, stopped, dead, unfinished, unfinished_id, counts,
-                                     workspace, workspace_bytes, st);
-  return TFRT_E_UNSUPPORTED;
+  const TraceCall<tfrt_scene3d> c = {
+      src_rays, src_stride, n_rays, scene, new_ray_length, dead_ray_length, max_passes,
+      state_dtype, flags, finished, active, stopped, dead, unfinished, unfinished_id, counts,
+      workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+  return dispatch_state(state_dtype, TFRT_E_UNSUPPORTED, [&](auto tag) {
+    return trace3d_forward_t<typename decltype(tag)::type>(c);
+  });
 }
 
 int tfrt_trace3d_in_place(const tfrt_scene3d* scene, int64_t n_rays, int32_t max_passes) {
@@ -4502,8 +4457,7 @@ int tfrt_trace3d_executed(int64_t n_rays, int64_t n_faces, int32_t max_passes, i
   const Layout3 lay = make_layout(n_rays, n_faces, max_passes, state_dtype, pl);
   if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
   const int wstride = (int)inplace_wstride(n_rays);
-  const uint32_t* rows = reinterpret_cast<const uint32_t*>(static_cast<const char*>(workspace) +
-                                                           lay.wcount) + (size_t)max_passes * wstride;
+  const uint32_t* rows = Tape3<const void>(workspace, lay, n_rays).wcount + (size_t)max_passes * wstride;
   hipLaunchKernelGGL(k_inplace_work, dim3(2), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), rows,
                      cdiv(n_rays, inplace_bundle(n_rays)), wstride,
                      reinterpret_cast<unsigned long long*>(executed));
@@ -4523,21 +4477,14 @@ int tfrt_trace3d_compact(const void* src_rays, int64_t src_stride, int64_t n_ray
   const Plan3 pl = make_plan(n_rays, n_faces);
   const Layout3 lay = make_layout(n_rays, n_faces, max_passes, state_dtype, pl);
   if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  char* ws = static_cast<char*>(workspace);
-  if (state_dtype == TFRT_F32)
-    return inplace_gather_t<float>(src_rays, src_stride, n_rays, n_faces, ray_slot, dead_ray_length, max_passes, flags,
-                                   finished, active, stopped, dead, unfinished, unfinished_id,
-                                   counts, ws, lay, st);
-  if (state_dtype == TFRT_F64)
-    return inplace_gather_t<double>(src_rays, src_stride, n_rays, n_faces, ray_slot, dead_ray_length, max_passes,
-                                    flags, finished, active, stopped, dead, unfinished,
-                                    unfinished_id, counts, ws, lay, st);
-  if (state_dtype == TFRT_F16)
-    return inplace_gather_t<_Float16>(src_rays, src_stride, n_rays, n_faces, ray_slot, dead_ray_length, max_passes,
-                                      flags, finished, active, stopped, dead, unfinished,
-                                      unfinished_id, counts, ws, lay, st);
-  return TFRT_E_UNSUPPORTED;
+  // (no scene and no new-ray length: the gather reads neither)
+  const TraceCall<tfrt_scene3d> c = {
+      src_rays, src_stride, n_rays, nullptr, 0.0, dead_ray_length, max_passes, state_dtype, flags,
+      finished, active, stopped, dead, unfinished, unfinished_id, counts, workspace,
+      workspace_bytes, static_cast<hipStream_t>(stream)};
+  return dispatch_state(state_dtype, TFRT_E_UNSUPPORTED, [&](auto tag) {
+    return inplace_gather_t<typename decltype(tag)::type>(c, n_faces, ray_slot, lay);
+  });
 }
 
 int tfrt_trace3d_backward(const void* src_rays, int64_t src_stride, int64_t n_rays,
@@ -4552,26 +4499,17 @@ int tfrt_trace3d_backward(const void* src_rays, int64_t src_stride, int64_t n_ra
   if (!scene_ok(scene) || n_rays < 0 || max_passes < 0 || !counts || !workspace ||
       !grad_face_verts)
     return TFRT_E_BADARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (state_dtype == TFRT_F32)
-    return trace3d_backward_t<float>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                     dead_ray_length, max_passes, state_dtype, grad_finished,
-                                     cap_finished, grad_active, cap_active, grad_stopped,
-                                     cap_stopped, grad_dead, cap_dead, grad_face_verts,
-                                     grad_src_rays, counts, workspace, workspace_bytes, st);
-  if (state_dtype == TFRT_F64)
-    return trace3d_backward_t<double>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                      dead_ray_length, max_passes, state_dtype, grad_finished,
-                                      cap_finished, grad_active, cap_active, grad_stopped,
-                                      cap_stopped, grad_dead, cap_dead, grad_face_verts,
-                                      grad_src_rays, counts, workspace, workspace_bytes, st);
-  if (state_dtype == TFRT_F16)
-    return trace3d_backward_t<_Float16>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                      dead_ray_length, max_passes, state_dtype, grad_finished,
-                                      cap_finished, grad_active, cap_active, grad_stopped,
-                                      cap_stopped, grad_dead, cap_dead, grad_face_verts,
-                                      grad_src_rays, counts, workspace, workspace_bytes, st);
-  return TFRT_E_UNSUPPORTED;
+  SweepCall3 c = {src_rays, src_stride, n_rays, scene, new_ray_length, dead_ray_length,
+                  max_passes, state_dtype, counts, workspace, workspace_bytes,
+                  static_cast<hipStream_t>(stream)};
+  c.g_fin = grad_finished, c.cap_fin = cap_finished;
+  c.g_act = grad_active, c.cap_act = cap_active;
+  c.g_stp = grad_stopped, c.cap_stp = cap_stopped;
+  c.g_dead = grad_dead, c.cap_dead = cap_dead;
+  c.g_fverts = grad_face_verts, c.g_src = grad_src_rays;
+  return dispatch_state(state_dtype, TFRT_E_UNSUPPORTED, [&](auto tag) {
+    return trace3d_backward_t<typename decltype(tag)::type>(c);
+  });
 }
 
 size_t tfrt_trace3d_backward_goal_workspace_bytes(int64_t n_rays) {
@@ -4622,26 +4560,17 @@ int tfrt_trace3d_backward_goal(const void* src_rays, int64_t src_stride, int64_t
                                                    align_up((size_t)cdiv(n_rays > 0 ? n_rays : 1, 64) *
                                                             sizeof(double)))
                       : nullptr;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = TFRT_E_UNSUPPORTED;
-  if (state_dtype == TFRT_F32)
-    rc = trace3d_backward_t<float>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                   dead_ray_length, max_passes, state_dtype, nullptr, 0,
-                                   grad_active, cap_active, grad_stopped, cap_stopped, grad_dead,
-                                   cap_dead, grad_face_verts, grad_src_rays, counts, workspace,
-                                   workspace_bytes, st, &g);
-  else if (state_dtype == TFRT_F64)
-    rc = trace3d_backward_t<double>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                    dead_ray_length, max_passes, state_dtype, nullptr, 0,
-                                    grad_active, cap_active, grad_stopped, cap_stopped, grad_dead,
-                                    cap_dead, grad_face_verts, grad_src_rays, counts, workspace,
-                                    workspace_bytes, st, &g);
-  else if (state_dtype == TFRT_F16)
-    rc = trace3d_backward_t<_Float16>(src_rays, src_stride, n_rays, scene, new_ray_length,
-                                      dead_ray_length, max_passes, state_dtype, nullptr, 0,
-                                      grad_active, cap_active, grad_stopped, cap_stopped,
-                                      grad_dead, cap_dead, grad_face_verts, grad_src_rays, counts,
-                                      workspace, workspace_bytes, st, &g);
+  SweepCall3 c = {src_rays, src_stride, n_rays, scene, new_ray_length, dead_ray_length,
+                  max_passes, state_dtype, counts, workspace, workspace_bytes,
+                  static_cast<hipStream_t>(stream)};
+  c.g_act = grad_active, c.cap_act = cap_active;
+  c.g_stp = grad_stopped, c.cap_stp = cap_stopped;
+  c.g_dead = grad_dead, c.cap_dead = cap_dead;
+  c.g_fverts = grad_face_verts, c.g_src = grad_src_rays;
+  c.goal = &g;
+  const int rc = dispatch_state(state_dtype, TFRT_E_UNSUPPORTED, [&](auto tag) {
+    return trace3d_backward_t<typename decltype(tag)::type>(c);
+  });
   if (rc != 0) return rc;
   // trailing counters of the trace: {total_active, total_finished, ..., n_tests_lo, n_tests_hi}
   const int32_t* tail = counts + (size_t)max_passes * TFRT_COUNTS_PER_PASS;
@@ -4696,7 +4625,7 @@ int tfrt_intersect3d(const void* rays, int64_t stride, int64_t n_rays, int32_t s
   o += align_up((size_t)pl.chunks * n * sizeof(int32_t));
   float* prep = reinterpret_cast<float*>(ws + o);
   if (M <= 0)
-    hipLaunchKernelGGL(k_init, dim3(1), dim3(64), 0, st, nptr, (int)n_rays, nptr + 8,
+    hipLaunchKernelGGL(k_init<>, dim3(1), dim3(64), 0, st, nptr, (int)n_rays, nptr + 8,
                        (unsigned int*)nullptr);
   if (M > 0) {
     hipLaunchKernelGGL(k_center, dim3(1), dim3(BLOCK), 0, st, face_verts, M, c0, nptr, (int)n_rays,
@@ -4705,25 +4634,17 @@ int tfrt_intersect3d(const void* rays, int64_t stride, int64_t n_rays, int32_t s
                        size_epsilion, sphere, FaceTables(), static_cast<double*>(nullptr),
                        (int64_t)0);
   }
-#define TFRT_SEAM(TT)                                                                          \
-  launch_intersect<TT>(pl, st, static_cast<const TT*>(rays), stride, nptr, nullptr, sphere,    \
-                       face_verts, c0, prep, (int64_t)n, M, intersect_epsilion, size_epsilion, \
-                       ray_start_epsilion, part_t, part_i, (int64_t)n, nullptr);               \
-  hipLaunchKernelGGL((k_finalize_seam<TT>), dim3(pl.nblk), dim3(BLOCK), 0, st,                 \
-                     static_cast<const TT*>(rays), stride, (int)n_rays, pl.chunks, part_t,     \
-                     part_i, (int64_t)n, face_verts, M, intersect_epsilion, size_epsilion,     \
-                     ray_start_epsilion, x, y, z, valid, ray_u, trig_u, trig_v, gather_trig)
-  if (state_dtype == TFRT_F32) {
-    TFRT_SEAM(float);
-  } else if (state_dtype == TFRT_F64) {
-    TFRT_SEAM(double);
-  } else if (state_dtype == TFRT_F16) {
-    TFRT_SEAM(_Float16);
-  } else {
-    return TFRT_E_UNSUPPORTED;
-  }
-#undef TFRT_SEAM
-  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  return dispatch_state(state_dtype, TFRT_E_UNSUPPORTED, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    launch_intersect<T>(pl, st, static_cast<const T*>(rays), stride, nptr, nullptr, sphere,
+                        face_verts, c0, prep, (int64_t)n, M, intersect_epsilion, size_epsilion,
+                        ray_start_epsilion, part_t, part_i, (int64_t)n, nullptr);
+    hipLaunchKernelGGL((k_finalize_seam<T>), dim3(pl.nblk), dim3(BLOCK), 0, st,
+                       static_cast<const T*>(rays), stride, (int)n_rays, pl.chunks, part_t, part_i,
+                       (int64_t)n, face_verts, M, intersect_epsilion, size_epsilion,
+                       ray_start_epsilion, x, y, z, valid, ray_u, trig_u, trig_v, gather_trig);
+    return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  });
 }
 
 int tfrt_profile_enable(int enable) {

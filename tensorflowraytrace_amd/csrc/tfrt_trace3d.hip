@@ -3388,7 +3388,8 @@ __device__ __forceinline__ int backward_core(
     for (int k = 0; k < 3; ++k) nz = nz || g_s[k] != 0.0 || g_h[k] != 0.0;
     if (nz) {
       if (!early) {
-        tri = rec_tri[i];
+        // (a caller that handed the record's face over, hit or none, has read this very value)
+        if (tri_known < -1) tri = rec_tri[i];
         load_face(has_child);
       }
       double gn[2];
@@ -3630,6 +3631,153 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
         a.partial_cnt[2 * (i0 >> 6)] = n_fin;
         a.partial_cnt[2 * (i0 >> 6) + 1] = n_entered;
       }
+    }
+  }
+}
+
+// The sweep of the optimiser's steady-state step, with what its dispatch knows made compile-time
+// facts: an in-place tape (a ray keeps its slot, rec_slot is never read), no gradient but the
+// built-in goal's (ChainArgs.inplace == 2), the chain's records in LDS (P <= CHAIN_MAXP), the
+// indices per face (feta) and no gradient with respect to them.  It is
+// k_backward_chain<T, 1, true, false> on that path -- the same arithmetic in the same order, the
+// same atomics -- without the run-time branches of the other paths and with an argument block of
+// what this path reads: ChainArgs plus tfrt_scene3d are ~60 scalars, which left the general
+// kernel 38 spilled scalar registers on this very path.
+template <typename T>
+struct ChainGoalArgs {
+  const T* src;            // source rays (inputs of pass 1)
+  int64_t src_stride;
+  const T* rays_ws;        // inputs of pass 2..P, (P - 1) blocks of 6 x n
+  const int32_t* nrays;    // rays entering pass 1
+  const int32_t* rec_tri;
+  const double* rec_t;
+  const uint8_t* rec_cls;
+  int64_t n;               // slot stride of the per-pass arrays
+  int32_t P;
+  double L;
+  double* g_src;           // (6 x N) or null
+  int64_t N;
+  double* g_fverts;
+  GoalFields gf;
+  const double* goal;
+  int64_t goal_stride, goal_ray_stride;
+  double* partial;         // one partial error sum per wavefront of the launch
+  int32_t* partial_cnt;    // ... and {finished rays, passes entered} per wavefront, or null
+  const double* feta;      // per-face indices (FaceTables), never null here
+  const double* face_verts;        // of tfrt_scene3d: what backward_core reads on this path
+  const uint8_t* face_grad_mask;
+};
+
+template <typename T>
+__global__ __launch_bounds__(64)
+__attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_backward_chain_goal_inplace(
+    ChainGoalArgs<T> a) {
+  // the reference's squared_difference and reduce_sum are separate ops: no contraction
+#pragma clang fp contract(off)
+  const int n0 = a.nrays[0];
+  const int i0 = blockIdx.x * 64 + threadIdx.x;
+  const int lane = threadIdx.x;
+  if ((i0 & ~63) >= n0) {  // (whole wave)
+    if (lane == 0) {
+      a.partial[i0 >> 6] = 0.0;
+      if (a.partial_cnt != nullptr) a.partial_cnt[2 * (i0 >> 6)] = a.partial_cnt[2 * (i0 >> 6) + 1] = 0;
+    }
+    return;
+  }
+  __builtin_assume(a.feta != nullptr);
+  __shared__ double wacc[WSUM_CELLS];
+  __shared__ int32_t wface[WSUM_SLOTS];
+  extern __shared__ int2 chain_goal_lds[];   // [pass][lane]: tape byte, face
+  int2* chain = chain_goal_lds;
+  const int P = a.P;
+  // (of the scene only these two fields are read below: the rest folds away)
+  tfrt_scene3d sc = {};
+  sc.face_verts = a.face_verts;
+  sc.face_grad_mask = a.face_grad_mask;
+  int last = -1;
+  if (i0 < n0) {
+    for (int p = 0; p < P; ++p) {
+      const size_t at = (size_t)p * a.n + i0;
+      const int tape = a.rec_cls[at], tri = a.rec_tri[at];
+      chain[p * 64 + lane] = make_int2(tape, tri);
+      last = p;
+      if ((tape & 3) != CLS_ACTIVE) break;
+    }
+  }
+  // (wave-uniform bound of the walk back)
+  int top = last;
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) top = max(top, __shfl_xor(top, d, 64));
+  // (every lane holds the same value now; said so, the pass counter and the per-pass base
+  // addresses made of it live in scalar registers)
+  top = __builtin_amdgcn_readfirstlane(top);
+  double child[6] = {0, 0, 0, 0, 0, 0};
+  double err = 0.0;
+  int n_fin = 0, n_entered = 0;   // (wave-uniform) finished rays, passes the wavefront's rays entered
+  for (int p = top; p >= 0; --p) {
+    double gP[9];
+    int tri = -1;
+    bool fin_here = false;
+    if (p <= last) {
+      const int2 rec = chain[p * 64 + lane];
+      const int tape = rec.x;
+      const size_t off = (size_t)p * a.n;
+      const T* rin = p == 0 ? a.src : a.rays_ws + (size_t)(p - 1) * 6 * a.n;
+      const int64_t sin = p == 0 ? a.src_stride : a.n;
+      double seed[6] = {0, 0, 0, 0, 0, 0};
+      if (p == last && (tape & 3) == CLS_FINISHED) {
+        fin_here = true;
+        // the finished row as k_inplace_gather would store it, recomputed from the tape
+        // (k_backward_chain: the same terms in the same order)
+        double fin_row[6], s0[3], e0[3], h0[3];
+        load_ray3(rin, sin, i0, s0, e0);
+        hit_point(s0, e0, a.rec_t[off + i0], h0);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          fin_row[k] = s0[k];
+          fin_row[3 + k] = static_cast<double>(static_cast<T>(h0[k]));
+        }
+        for (int c = 0; c < a.gf.n; ++c) {
+          const int row = a.gf.row[c];
+          double out_c = 0.0;
+#pragma unroll
+          for (int k = 0; k < 6; ++k)   // (no dynamic register index)
+            if (k == row) out_c = fin_row[k];
+          const double r = out_c -
+                           a.goal[(int64_t)c * a.goal_stride + (int64_t)i0 * a.goal_ray_stride];
+          const double g = 2.0 * r;
+#pragma unroll
+          for (int q = 0; q < 6; ++q)   // (no dynamic register index)
+            if (q == row) seed[q] = g;
+          err += r * r;
+        }
+      }
+      double gs[3], ge[3];
+      tri = backward_core<T, false>(i0, tape, i0, rin, sin, nullptr, a.rec_tri + off, a.rec_t + off,
+                                    nullptr, sc, a.L, 0.0, p < P - 1, child, seed, nullptr, 0,
+                                    nullptr, 0, nullptr, 0, nullptr, 0, gs, ge, gP,
+                                    max(rec.y, -1),   // (a record is a face or -1: no re-read)
+                                    a.feta, true);
+      for (int k = 0; k < 3; ++k) {
+        child[k] = gs[k];
+        child[3 + k] = ge[k];
+      }
+    }
+    n_fin += __popcll(__ballot(fin_here));
+    n_entered += __popcll(__ballot(p <= last));
+    wave_face_sums(tri, gP, wacc, wface, a.g_fverts);
+  }
+  if (a.g_src != nullptr && i0 < n0) {
+    for (int k = 0; k < 6; ++k) a.g_src[k * a.N + i0] = child[k];
+  }
+  // fixed-shape reduction: xor butterflies inside the wave (k_goal_finish sums the partials)
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) err += __shfl_xor(err, d, 64);
+  if (lane == 0) {
+    a.partial[i0 >> 6] = err;
+    if (a.partial_cnt != nullptr) {
+      a.partial_cnt[2 * (i0 >> 6)] = n_fin;
+      a.partial_cnt[2 * (i0 >> 6) + 1] = n_entered;
     }
   }
 }
@@ -4358,7 +4506,35 @@ static int trace3d_backward_t(const SweepCall3& c) {
       a.goal_ray_stride = c.goal->goal_ray_stride;
       a.partial = c.goal->partial;
       a.partial_cnt = c.goal->partial_cnt;
-      if (N > 0 && sc->grad_n_in != nullptr)
+      if (N > 0 && a.inplace == 2 && a.chain_in_lds && a.feta != nullptr &&
+          sc->grad_n_in == nullptr) {
+        // the optimiser's steady-state step: its own kernel (k_backward_chain_goal_inplace)
+        ChainGoalArgs<T> g;
+        g.src = a.src;
+        g.src_stride = a.src_stride;
+        g.rays_ws = a.rays_ws;
+        g.nrays = a.nrays;
+        g.rec_tri = a.rec_tri;
+        g.rec_t = a.rec_t;
+        g.rec_cls = a.rec_cls;
+        g.n = a.n;
+        g.P = a.P;
+        g.L = a.L;
+        g.g_src = a.g_src;
+        g.N = a.N;
+        g.g_fverts = a.g_fverts;
+        g.gf = a.gf;
+        g.goal = a.goal;
+        g.goal_stride = a.goal_stride;
+        g.goal_ray_stride = a.goal_ray_stride;
+        g.partial = a.partial;
+        g.partial_cnt = a.partial_cnt;
+        g.feta = a.feta;
+        g.face_verts = sc->face_verts;
+        g.face_grad_mask = sc->face_grad_mask;
+        hipLaunchKernelGGL((k_backward_chain_goal_inplace<T>), dim3(cdiv(N, 64)), dim3(64),
+                           (size_t)P * 64 * sizeof(int2), st, g);
+      } else if (N > 0 && sc->grad_n_in != nullptr)
         hipLaunchKernelGGL((k_backward_chain<T, 1, true, true>), dim3(cdiv(N, 64)), dim3(64),
                            chain_lds, st, a, *sc);
       else if (N > 0)

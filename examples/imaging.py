@@ -1,0 +1,156 @@
+#!/usr/bin/env python3
+"""
+Imaging without a target in advance: a two-surface parametric acrylic lens is shaped so that the
+rays of every object point meet in ONE point on the target plane -- wherever that point is.
+
+The scene of the reference's dev/image_quality_3d.py (which can only LOOK at the result, as a
+histogram of the target plane): P object points on a plane at x = -10 -- a small "F" --, from each
+of them A rays in random directions inside a cone towards the lens (a non-dense ``AngularSource``
+over a ``ManualBasePointDistribution`` of the points, tiled A times, and a
+``RandomUniformSphere``), the lens of examples/hexalens.py, a target plane at x = +10.  The merit
+function is the RMS spot size, ``optimizer.SpotError``: the rays carry the label of their object
+point, and the error is the summed squared distance of every finished ray to the centroid of its
+own label.  Magnification, distortion and field curvature are left to the lens.
+
+The directions are re-drawn at every step; the labels stay (ray i is object point i mod P).  With a
+``SpotError`` the optimiser runs the step as one fixed launch sequence replayed from a HIP graph
+once the engine traces the source in place; ``--generic`` keeps the generic path (the same
+kernels under torch.autograd).
+
+    python examples/imaging.py [--rays 20000] [--steps 30] [--generic] [--adam]
+"""
+import argparse
+import math
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import tfrt.boundaries as boundaries          # noqa: E402
+import tfrt.distributions as distributions    # noqa: E402
+import tfrt.drawing as drawing                # noqa: E402
+import tfrt.engine as engine                  # noqa: E402
+import tfrt.materials as materials            # noqa: E402
+import tfrt.mesh_tools as mt                  # noqa: E402
+import tfrt.operation as operation            # noqa: E402
+import tfrt.optimizer as optimizer            # noqa: E402
+import tfrt.sources as sources                # noqa: E402
+
+LEARNING_RATE = 2e-5     # at 20,000 rays
+HALF_DOMAIN = 3.0        # the target region: the unfocused cone of a ray bundle has radius ~1.6
+
+
+def letter_f(size=0.2):
+    """The object points: an "F" of height 2 * size in the (y, z) plane, (P, 3) with x = 0 --
+    a backbone of 15 points, a top bar of 8 and a middle bar of 5."""
+    backbone = [(-0.5 * size, z) for z in np.linspace(-size, size, 15)]
+    top = [(y, size) for y in np.linspace(-0.5 * size, 0.75 * size, 9)[1:]]
+    middle = [(y, 0.0) for y in np.linspace(-0.5 * size, 0.4 * size, 6)[1:]]
+    yz = np.array(backbone + top + middle, dtype=np.float64)
+    return np.concatenate([np.zeros((yz.shape[0], 1)), yz], axis=1)
+
+
+def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, target_distance=10.0,
+          object_size=0.2, lens_aperature=1.0):
+    points = letter_f(object_size)
+    P = points.shape[0]
+    A = max(ray_count // P, 2)
+    n_rays = P * A
+    # ray i leaves object point i mod P: the points tiled A times, one random direction each
+    base_points = distributions.ManualBasePointDistribution(3, points=np.tile(points, (A, 1)))
+    # (the cone that just fills the lens from the farthest object point)
+    cone = math.atan((0.95 * lens_aperature - 1.25 * object_size) / source_distance)
+    directions = distributions.RandomUniformSphere(cone, n_rays)
+    source = sources.AngularSource(3, (-source_distance, 0.0, 0.0), (1.0, 0.0, 0.0), directions,
+                                   base_points, [drawing.YELLOW], dense=False)
+    labels = np.arange(n_rays) % P
+
+    zero_points = mt.circular_mesh(lens_aperature, lens_res_scale)
+    zero_points.rotate_y(90)
+    zero_points.rotate_x(90)
+    top_parent = mt.get_closest_point(zero_points, (0, 0, 0))
+    vertex_update_map, accumulator = mt.mesh_parametrization_tools(zero_points, top_parent)
+    lens = boundaries.ParametricMultiTriangleBoundary(
+        zero_points, boundaries.FromVectorVG((1, 0, 0)),
+        [boundaries.ThicknessConstraint(0.0, "min"), boundaries.ThicknessConstraint(0.2, "min")],
+        [True, False],
+        material_list=[{"mat_in": 1, "mat_out": 0}] * 2,
+        vertex_update_map=vertex_update_map)
+    target = boundaries.ManualTriangleBoundary(mesh=mt.plane(
+        center=(target_distance, 0, 0), direction=(1, 0, 0), i_size=100, j_size=100))
+    target.frozen = True
+
+    system = engine.OpticalSystem3D()
+    system.optical = lens.surfaces
+    system.targets = [target]
+    system.sources = [source]
+    system.materials = [{"n": materials.vacuum}, {"n": materials.acrylic}]
+    system.update()
+
+    trace_engine = engine.OpticalEngine(
+        3, [operation.StandardReaction()], compile_active_rays=False,
+        simple_ray_inheritance={"wavelength"})
+    trace_engine.optical_system = system
+    trace_engine.validate_system()
+
+    # a ray that leaves the target region is pulled back instead of dragging its spot along
+    error_function = optimizer.SpotError(
+        ("y_end", "z_end"), labels, ((-HALF_DOMAIN, HALF_DOMAIN), (-HALF_DOMAIN, HALF_DOMAIN)),
+        oob_weight=1.0)
+    return dict(engine=trace_engine, system=system, lens=lens, source=source, n_rays=n_rays,
+                n_points=P, error_function=error_function, accumulator=accumulator)
+
+
+def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=False, verbose=True,
+        learning_rate=None):
+    s = build(ray_count, lens_res_scale)
+    erf = s["error_function"]
+    if learning_rate is None:
+        # (the error is a sum over the rays: the step size goes with 1 / rays)
+        learning_rate = LEARNING_RATE * (20000 / s["n_rays"])
+    kw = dict(learning_rate=learning_rate, grad_clip=1.0, fused=False if generic else "auto")
+    if adam:
+        opt = optimizer.Adam_Optimizer(s["engine"], s["lens"].parameters, erf, 3,
+                                       adam_learning_rate=3e-4, **kw)
+    else:
+        opt = optimizer.SGD_Optimizer(s["engine"], s["lens"].parameters, erf, 3, **kw)
+    opt.suppress_warnings = True
+    rms, times = [], []
+    for step in range(steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        mean = float(opt.single_step(s["accumulator"] if step < steps // 2 else None))
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+        inside = int(erf.last_acc[:, 0].sum())
+        error_sum = mean * float(opt.last_error_terms)
+        rms.append(math.sqrt(error_sum / inside) if inside else float("nan"))
+        if verbose and (step % 5 == 0 or step == steps - 1):
+            print(f"step {step:4d}: rms spot {rms[-1]:.6g}  ({inside} rays inside, "
+                  f"{1e3 * times[-1]:.2f} ms)")
+    fused = opt._fused_step
+    s.update(rms=rms, times=times, graph_replays=0 if fused is None else fused.graph_replays,
+             centroids=erf.centroids())
+    return s
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rays", type=int, default=20000)
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--edge", type=float, default=0.12, help="lens mesh edge")
+    ap.add_argument("--generic", action="store_true", help="the generic path (fused=False)")
+    ap.add_argument("--adam", action="store_true", help="an Adam_Optimizer instead of plain SGD")
+    ap.add_argument("--lr", type=float, default=None,
+                    help=f"learning rate (default {LEARNING_RATE} * 20000 / rays)")
+    a = ap.parse_args()
+    out = run(a.rays, a.steps, a.edge, generic=a.generic, adam=a.adam, learning_rate=a.lr)
+    tail = sorted(out["times"][len(out["times"]) // 2:])
+    print(f"{out['n_points']} object points, {out['n_rays']} rays; steps replayed from the graph: "
+          f"{out['graph_replays']} of {a.steps}; median step of the second half: "
+          f"{1e3 * tail[len(tail) // 2]:.3f} ms")
+    print(f"rms spot: first {out['rms'][0]:.6g} last {out['rms'][-1]:.6g}")

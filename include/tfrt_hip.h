@@ -554,6 +554,60 @@ int tfrt_density_error(const void* rows, int64_t stride, int64_t n, int32_t stat
                        double* error_out, int64_t* hq, int32_t splat_variant, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* SpotError: the columns that carry the same group label must meet in one point -- the sum over
+ * the rays of the squared distance to the CENTROID of their own group (the squared RMS spot size
+ * times the ray count), wherever the centroids lie.  Four launches (clear `acc`, accumulate, seed,
+ * finish), no host read, no allocation: captured with the rest of a step.
+ *
+ * With k the number of fields (1 or 2), a column i COUNTS if mask is NULL or mask[i] >= 0
+ * (tfrt_ray_out.face of an in-place trace with the finished rows at the rays' own columns), and
+ * terms = k * (number of counting columns).  Coordinates x = rows[row_x], y = rows[row_y] are
+ * converted to f64; every operation below is an IEEE f64 operation rounded on its own (no
+ * contraction).  A counting column goes to exactly one of four cases, tried in this order:
+ *   a coordinate is non-finite: no error, gradient 0;
+ *   no spot: s = perm ? perm[i] : i, label = group[s]; s outside [0, n_source) or label outside
+ *     [0, n_groups): no error, gradient 0 (the label -1 excludes a ray; nothing is read out of
+ *     bounds, whatever perm and group hold);
+ *   outside the closed domain on any axis: nothing goes to `acc`; the error gains
+ *     oob_weight * (ex^2 + ey^2), ex = max(x0 - x, 0) + max(x - x1, 0), and the gradient is the
+ *     derivative of that expression (as tfrt_density_error);
+ *   inside: qx = (int64) min(max(rint((x - x0) * qsx), 0), 2^qbits), half to even, qy alike;
+ *     {1, qx, qy} is added to record `label` of `acc` with 64-bit integer atomics: the sums do not
+ *     depend on the order of the atomics.
+ * Once every column is in, a group with count > 0 has cx = x0 + ((double) Sx / (double) count) / qsx
+ * and cy alike.  An inside ray has dx = x - cx, the terms dx * dx and dy * dy and the gradient rows
+ * 2 * dx and 2 * dy: exact without a derivative of the centroid, because the residuals of a group
+ * sum to zero (up to the quantisation, half a step of 1 / qsx).  error = the sum of the inside
+ * terms + the sum of the penalties; all sums have a fixed shape and order: two runs give the same
+ * bits.
+ *
+ *   rows, stride    ray block in the state dtype, entry (row, i) at rows[row * stride + i], n columns
+ *   row_x, row_y    rows (0..5) of x and y; row_y = -1: one field (qy = 0, Sy stays 0)
+ *   group           n_source int32 labels, one per SOURCE ray
+ *   perm            n int32, the source ray of column i; or NULL: column i is source ray i
+ *   n_groups        G, 1 <= G <= 2^20
+ *   qbits           1..52; the caller uses min(52, 62 - bit_length(n_source)).  n >= 2^(62 - qbits)
+ *                   is refused: n * 2^qbits < 2^62, no sum overflows
+ *   qsx, qsy        ldexp(1, qbits) / (x1 - x0) and / (y1 - y0), computed by the caller in f64
+ *   grad            f64 block, entry (row, i) at grad[row * grad_stride + i]: rows row_x and row_y
+ *                   are written for EVERY column (0 where a ray does not count); no other row is
+ *   error_out       3 f64 {error, terms, terms > 0 ? error / terms : NaN}
+ *   acc             n_groups records of four int64 {count, Sx, Sy, 0} (32 B: the adds of one ray
+ *                   fall into one sector), cleared and filled by this call
+ *   variant         0: a per-workgroup table in LDS up to 1,024 groups, global 64-bit atomics
+ *                   above; 1 / 2 force one of them (1 with more than 1,024 groups: TFRT_E_BADARG)
+ *   workspace       tfrt_spot_error_workspace_bytes(n, n_groups) bytes (0: bad arguments)
+ * 0 <= n < 2^31 (n == 0 is legal: {0, 0, NaN}), 0 <= n_source < 2^31.
+ */
+size_t tfrt_spot_error_workspace_bytes(int64_t n, int32_t n_groups);
+int tfrt_spot_error(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                    const int32_t* mask, int32_t row_x, int32_t row_y, const int32_t* group,
+                    int64_t n_source, const int32_t* perm, int32_t n_groups, double x0, double x1,
+                    double qsx, double y0, double y1, double qsy, int32_t qbits,
+                    double oob_weight, double* grad, int64_t grad_stride, double* error_out,
+                    int64_t* acc, int32_t variant, void* workspace, size_t workspace_bytes,
+                    void* stream);
+
 /* tfrt_goal_error3d_deferred and tfrt_trace3d_backward in ONE launch, for a trace over coherent
  * rays (tfrt_scene3d.coherent_rays, not deterministic, max_passes <= 8; TFRT_E_UNSUPPORTED
  * otherwise -- call the two entry points instead): the lane that walks a finished ray's chain of

@@ -35,7 +35,9 @@ fixed-shape column), ``fn`` and its autograd, and ``tfrt_trace2d_backward_rows``
 gradient; ``_rowwise3d`` does the same on a 3-D engine with an in-place trace that leaves the
 finished rows at the rays' own columns.  A ``DensityError`` -- the finished rays, taken together,
 must land with a given density -- takes ``_rowwise3d`` too, with ``tfrt_density_error`` (a memset and
-three launches: splat, bins, seed) in the place of ``fn`` and its autograd.
+three launches: splat, bins, seed) in the place of ``fn`` and its autograd; a ``SpotError`` -- rays
+of one group must meet in one point -- likewise with ``tfrt_spot_error`` (clear, accumulate, seed,
+finish).
 
 The four bodies share one skeleton: ``_enqueue_gradient`` does what comes before the trace, the
 body its launches over a ``_StepState``, ``_publish_lazily`` and ``_enqueue_apply`` what comes after.
@@ -340,6 +342,221 @@ class _DensityTerms(torch.autograd.Function):
         return (upstream * grad).to(ctx.dtype), None
 
 
+class SpotError:
+    """Rays that left the same object point must meet in one point -- wherever that is: the sum
+    over the finished rays of the squared distance to the CENTROID of their own group, the squared
+    RMS spot size times the ray count.  Where the spots lie (magnification, distortion, field
+    curvature) is left to the lens; no target is needed in advance.
+
+    ``fields``: one or two geometry fields of a finished ray, e.g. ``("y_end", "z_end")``.
+    ``groups``: an integer tensor or array of shape (N,), one label per SOURCE ray in the source's
+    own order -- finished rays look theirs up through the source-ray index the trace carries --, or
+    a callable on the source's field dict that returns such labels (evaluated and cached as
+    ``GoalError.table`` is; it then needs ``n_groups``).  The labels are kept as int32 on the
+    device (``labels``) and may be overwritten in place between steps (a replayed graph reads the
+    buffer).  Labels outside ``[0, n_groups)`` -- ``-1`` -- exclude a ray.  ``n_groups``: G, by
+    default ``max + 1`` of a tensor, read once here; at most 2**20.  ``domain``:
+    ``((x0, x1), (y0, y1))``, or ``((x0, x1),)`` for one field: rays outside it take a penalty
+    instead of pulling their spot.
+
+    For every finished ray of the trace, coordinates converted to float64, every operation rounded
+    on its own, the first case that applies:
+
+    * a non-finite coordinate: no error, zero gradient;
+    * a label outside ``[0, n_groups)``: no error, zero gradient;
+    * outside the closed domain on any axis: the ray is in no spot and adds
+      ``oob_weight * (ex**2 + ey**2)``, ``ex = max(x0 - x, 0) + max(x - x1, 0)``; its gradient is
+      the derivative of that expression;
+    * inside: ``qx = min(max(rint((x - x0) * qsx), 0), 2**qbits)`` (half to even),
+      ``qsx = 2**qbits / (x1 - x0)``, ``qbits = min(52, 62 - bit_length(N))``; ``{1, qx, qy}`` is
+      added to the ray's group in an int64 table -- integer addition is associative, so the table
+      does not depend on the order of the atomics.
+
+    A group with rays has the centroid ``cx = x0 + (Sx / count) / qsx``; a ray inside has
+    ``dx = x - cx``, the error terms ``dx**2`` and ``dy**2`` and the gradient ``2 * dx``, ``2 * dy``.
+    That gradient is exact without differentiating through the centroid, because the residuals of
+    a group sum to zero (up to the quantisation: at most half a step ``1 / qsx`` per centroid).
+    ``error = sum of the terms + sum of the penalties`` over ``len(fields) * n_finished`` terms;
+    every sum has a fixed shape and order: two runs give the same bits.
+
+    It is an ordinary ``error_function(engine)`` (the generic path: ``ops.spot_error`` over the
+    finished rays' columns under a ``torch.autograd.Function``), which also serves sources that are
+    not traced in place, ``deterministic=True``, fewer than 4,096 rays and 2-D engines
+    (``FusedStep.eligible2d`` is false).  Its ``backward`` returns ``upstream * gradient``: exact
+    when ``upstream`` is constant within a group (the optimiser passes ones); weights that differ
+    inside a group would move the centroid, which this does not follow.  On a 3-D engine that traces
+    its source in place the optimiser runs it on the fused, graph-replayed step under the
+    conditions of a ``RowwiseError`` (``FusedStep._rowwise3d`` with ``tfrt_spot_error`` in the
+    place of ``fn`` and its autograd), with the same kernels and the same ``qbits``.  One process:
+    with ray shards over several ranks the generic path runs and each shard forms the centroids of
+    its own rays.
+
+    ``last_acc`` is the (G, 4) int64 table ``{count, Sx, Sy, 0}`` of the last evaluation,
+    ``centroids()`` the (G, k) float64 centroids made from it (NaN for a group without rays).
+    ``splat_variant`` (0: by G; 1: table in LDS; 2: global atomics) is tfrt_spot_error's, for
+    measuring."""
+
+    splat_variant = 0
+
+    def __init__(self, fields, groups, domain, oob_weight=0.0, n_groups=None):
+        from . import config
+        self.fields = (fields,) if isinstance(fields, str) else tuple(fields)
+        if len(self.fields) not in (1, 2) or any(f not in _GEO3 for f in self.fields) \
+                or len(set(self.fields)) != len(self.fields):
+            raise ValueError(f"SpotError: one or two distinct fields out of {_GEO3}, got {fields!r}")
+        self.rows = [_GEO3.index(f) for f in self.fields]
+        k = len(self.fields)
+        try:
+            domain = tuple((float(d[0]), float(d[1])) for d in domain)
+        except (IndexError, TypeError) as e:
+            raise ValueError("SpotError: domain must be ((x0, x1), (y0, y1)) or ((x0, x1),)") from e
+        if len(domain) != k or any(not (np.isfinite(a) and np.isfinite(b) and b > a) for a, b in domain):
+            raise ValueError(f"SpotError: domain needs one finite (lo, hi), lo < hi, per field; got {domain!r}")
+        self.domain = domain
+        self.oob_weight = float(oob_weight)
+        if not (self.oob_weight >= 0.0 and np.isfinite(self.oob_weight)):
+            raise ValueError("SpotError: oob_weight must be finite and >= 0")
+        self.groups = groups
+        self.labels = None
+        self._cache = None
+        if callable(groups):
+            if n_groups is None:
+                raise ValueError("SpotError: callable groups need n_groups")
+        else:
+            self.labels = self._as_labels(groups, config.get_device())
+            if n_groups is None:
+                if self.labels.numel() == 0:
+                    raise ValueError("SpotError: no labels and no n_groups")
+                n_groups = int(self.labels.max()) + 1
+        try:
+            self.n_groups = int(n_groups)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"SpotError: n_groups must be an integer, got {n_groups!r}") from e
+        if not 1 <= self.n_groups <= ops.SPOT_MAX_GROUPS:
+            raise ValueError(f"SpotError: n_groups must lie in 1 .. {ops.SPOT_MAX_GROUPS}, got "
+                             f"{n_groups!r}")
+        self._grids = {}
+        self.last_acc = None
+        self.last_grid = None
+
+    @staticmethod
+    def _as_labels(groups, device):
+        g = groups if isinstance(groups, torch.Tensor) else torch.as_tensor(np.asarray(groups))
+        if g.dim() != 1 or g.dtype.is_floating_point or g.dtype.is_complex or g.dtype == torch.bool:
+            raise ValueError("SpotError: groups must be integers of shape (N,), one label per "
+                             f"source ray; got shape {tuple(g.shape)}, {g.dtype}")
+        return g.detach().to(device=device, dtype=torch.int32).contiguous()
+
+    def rows_for(self, dimension):
+        """Rows of the ray block of a ``dimension``-D trace that the fields are read from."""
+        if dimension == 3:
+            return self.rows
+        bad = [f for f in self.fields if f not in _GEO2]
+        if bad:
+            raise ValueError(f"SpotError: field(s) {bad} do not exist on a {dimension}-D engine "
+                             f"(fields of its rays: {_GEO2})")
+        return [_GEO2.index(f) for f in self.fields]
+
+    def labels_of(self, src):
+        """The int32 label buffer of the source set ``src`` on its device, one label per source
+        ray: the tensor given (moved once; a new buffer re-captures a graph), or the callable's
+        result, cached by the versions of the source's fields as ``GoalError.table`` is."""
+        if hasattr(src, "n_rays"):
+            n, dev = src.n_rays, src.device
+        else:
+            n, dev = src["x_start"].shape[0], src["x_start"].device
+        if callable(self.groups):
+            if hasattr(src, "cache_key"):      # rays made in place (sources.DeviceRaySet)
+                vals, key = [src], src.cache_key
+            else:
+                vals = list(src.values()) if hasattr(src, "values") else [src[k] for k in src.keys()]
+                key = tuple((id(v), getattr(v, "_version", None)) for v in vals)
+            if self._cache is None or self._cache[0] != key:
+                self.labels = self._as_labels(self.groups(src), dev)
+                self._cache = (key, vals)        # the keyed tensors stay alive with the key
+        elif self.labels.device != dev:
+            self.labels = self.labels.to(dev)
+        if self.labels.numel() != n:
+            raise ValueError(f"SpotError: {self.labels.numel()} labels for {n} source rays -- one "
+                             "label per source ray")
+        return self.labels
+
+    def grid_for(self, n_source):
+        """(qbits, grid constants) for a source of ``n_source`` rays: both paths of a step use the
+        source's ray count, so the fused and the generic step quantise alike."""
+        hit = self._grids.get(n_source)
+        if hit is None:
+            qbits = ops.spot_qbits(n_source)
+            hit = self._grids[n_source] = (qbits, ops.spot_grid(self.domain, qbits))
+        return hit
+
+    def graph_key(self):
+        """What a captured step has baked in: the label buffer's address and the constants."""
+        lab = self.labels
+        return (None if lab is None else (lab.data_ptr(), tuple(lab.shape)), self.n_groups,
+                self.domain, self.oob_weight, self.splat_variant)
+
+    def evaluate(self, rows, row_x, row_y, labels, mask=None, perm=None, **buffers):
+        """``ops.spot_error`` of the columns of ``rows`` with these labels, domain and weight."""
+        qbits, grid = self.grid_for(labels.numel())
+        out = ops.spot_error(rows, row_x, row_y, labels, self.n_groups, grid, self.oob_weight,
+                             mask=mask, perm=perm, variant=self.splat_variant, qbits=qbits,
+                             **buffers)
+        self.last_acc, self.last_grid = out[2], grid
+        return out
+
+    def centroids(self):
+        """(G, k) float64 centroids of the last evaluation, NaN for a group without rays."""
+        if self.last_acc is None:
+            raise RuntimeError("SpotError: no evaluation yet")
+        return ops.spot_centroids(self.last_acc, self.last_grid, len(self.fields))
+
+    def __call__(self, engine):
+        """The (n_finished, k) error terms through the generic path; the gradient rows come back
+        in ``backward``."""
+        self.rows_for(engine.dimension)
+        fin = engine.finished_rays
+        if not bool(fin):
+            return torch.zeros((0, len(self.fields)), dtype=torch.float64)
+        ids = engine.last_trace["finished_id"]
+        labels = self.labels_of(engine._trace_src)
+        columns = torch.stack([fin[f] for f in self.fields], dim=0)
+        return _SpotTerms.apply(columns, self, labels, ids.to(torch.int32).contiguous())
+
+
+class _SpotTerms(torch.autograd.Function):
+    """SpotError over the (k, n) field columns of the finished rays, no mask; ``ids``: the source
+    ray of every column.  Returns the (n, k) terms: an inside ray's are (gradient / 2)**2 -- the
+    kernel's own dx * dx, the halving is exact --, a penalised ray's ``oob_weight * ex**2`` per
+    field."""
+
+    @staticmethod
+    def forward(ctx, columns, erf, labels, ids):
+        block = columns.detach().contiguous()
+        k = block.shape[0]
+        err, grad, _ = erf.evaluate(block, 0, 1 if k == 2 else -1, labels, perm=ids)
+        ctx.save_for_backward(grad)
+        ctx.dtype = columns.dtype
+        v = block.double()
+        lo = torch.tensor([d[0] for d in erf.domain], dtype=torch.float64, device=v.device)[:, None]
+        hi = torch.tensor([d[1] for d in erf.domain], dtype=torch.float64, device=v.device)[:, None]
+        zero = torch.zeros((), dtype=torch.float64, device=v.device)
+        ex = torch.maximum(lo - v, zero) + torch.maximum(v - hi, zero)
+        out = ((v < lo) | (v > hi)).any(dim=0, keepdim=True)
+        # (a ray that does not count has a zero gradient and, outside, no penalty either: its
+        # label decides, which the kernel has looked up)
+        lab = labels[ids.long().clamp(0, labels.numel() - 1)]
+        spot = ((lab >= 0) & (lab < erf.n_groups) & torch.isfinite(v).all(dim=0))[None, :]
+        half = 0.5 * grad
+        terms = torch.where(out, erf.oob_weight * (ex * ex), half * half)
+        return torch.where(spot, terms, zero).t().contiguous()
+
+    @staticmethod
+    def backward(ctx, upstream):
+        grad, = ctx.saved_tensors
+        return (upstream.t() * grad).to(ctx.dtype), None, None, None
+
+
 class _RowFields:
     """Field mapping handed to a RowwiseError on the fixed-shape path: geometry = the rows of the
     in-place finished block, everything else = the source's own fields in the trace's order."""
@@ -429,6 +646,7 @@ class _StepState:
         "g_prim", "g_seg", "g_arc", "g_index",               # 2-D: one block, views into it
         "rows", "row_face", "row_passes", "row_outs",        # a RowwiseError's fixed-shape columns
         "density_ws", "hq",                                  # a DensityError's workspace and histogram
+        "spot_ws", "acc",                                    # a SpotError's workspace and group records
         "chain_ws", "inherited",                             # made on first use
         "block", "stream", "perm", "inplace")                # of the last enqueued step
 
@@ -473,8 +691,8 @@ class _StepState:
 
 class FusedStep:
     """Runs ``SGD_Optimizer.single_step`` for a ``GoalError`` or a ``RowwiseError`` as a fixed
-    launch sequence, on 3-D engines and on 2-D ones (one process), and for a ``DensityError`` on
-    3-D engines; see the module docstring.
+    launch sequence, on 3-D engines and on 2-D ones (one process), and for a ``DensityError`` or a
+    ``SpotError`` on 3-D engines; see the module docstring.
     One instance per optimizer."""
 
     # coherent rays: error, gradient seed and reverse sweep as ONE launch (tfrt_trace3d_backward_goal);
@@ -520,13 +738,13 @@ class FusedStep:
     def eligible(optimizer, args, kwargs):
         eng = optimizer.engine
         erf = optimizer.error_function
-        if not isinstance(erf, (GoalError, RowwiseError, DensityError)) or args or kwargs:
+        if not isinstance(erf, (GoalError, RowwiseError, DensityError, SpotError)) or args or kwargs:
             return False
-        if (isinstance(erf, (RowwiseError, DensityError)) and eng.dimension == 3
+        if (isinstance(erf, (RowwiseError, DensityError, SpotError)) and eng.dimension == 3
                 and not FusedStep.rowwise_ready(eng)):
             return False
-        if isinstance(erf, DensityError) and tdist.is_distributed():
-            return False            # (the histogram couples the rays: one process)
+        if isinstance(erf, (DensityError, SpotError)) and tdist.is_distributed():
+            return False            # (the histogram / the centroids couple the rays: one process)
         if not bool(eng.optical_system):
             return False
         if eng.dimension == 2 and not FusedStep.eligible2d(optimizer):
@@ -683,7 +901,7 @@ class FusedStep:
             raise RuntimeError("FusedStep: the optical system has no source rays")
         inputs = eng._trace_inputs(src)
         P, flags = int(opt.trace_depth), eng._flags() | _lib.COMPILE_FINISHED
-        rowwise = isinstance(opt.error_function, (RowwiseError, DensityError))
+        rowwise = isinstance(opt.error_function, (RowwiseError, DensityError, SpotError))
         if eng.dimension == 2:
             body = self._rowwise2d if rowwise else self._goal2d
         else:
@@ -839,8 +1057,8 @@ class FusedStep:
 
     def _rowwise3d(self, src, inputs, tap_log, P, flags):
         """In-place trace with the finished rows at the rays' own columns -> ``erf.fn`` on
-        fixed-shape tensors + its autograd (torch), or a DensityError's three launches
-        (tfrt_density_error) -> reverse sweep.  No ray count is read; everything is capturable."""
+        fixed-shape tensors + its autograd (torch), or a DensityError's / a SpotError's three
+        launches (tfrt_density_error, tfrt_spot_error) -> reverse sweep.  No ray count is read; everything is capturable."""
         eng = self.opt.engine
         block, scene, fv = inputs
         perm = eng._trace_perm
@@ -870,8 +1088,11 @@ class FusedStep:
         # the same value as the forward)
         with _override(sc, in_place=2, **clear):
             self._trace_forward(st, sc, st.row_outs)
-            if isinstance(self.opt.error_function, DensityError):
-                g64 = self._density_seeds3d(st)
+            if isinstance(self.opt.error_function, (DensityError, SpotError)):
+                if isinstance(self.opt.error_function, DensityError):
+                    g64 = self._density_seeds3d(st)
+                else:
+                    g64 = self._spot_seeds3d(st, src, perm)
                 if not need_back:
                     g64 = None
             else:
@@ -899,6 +1120,28 @@ class FusedStep:
         erf.evaluate(st.rows[:, :st.N], rows[0], rows[1] if len(rows) == 2 else -1,
                      mask=st.row_face, grad=st.g_fin, err=st.err, hq=st.hq,
                      workspace=st.density_ws)
+        with torch.no_grad():
+            self.tests_total += st.row_passes[:st.N].sum() * st.M
+        return st.g_fin
+
+    def _spot_seeds3d(self, st, src, perm):
+        """A SpotError on the fixed-shape columns: tfrt_spot_error reads ``st.rows``, the mask
+        ``st.row_face``, the source's label buffer and the trace's order ``perm`` -- the kernel
+        looks a column's label up itself, so no permuted copy can go stale when a source is
+        re-drawn and re-ordered inside the graph -- and writes its two rows of the persistent seed
+        block (the other rows were zeroed when the state was made) for every column, the error
+        into ``st.err`` and the group records into ``st.acc``.  Returns the (6, capN) seed block."""
+        erf = self.opt.error_function
+        dev = st.rows.device
+        labels = erf.labels_of(src)
+        if st.acc is None or st.acc.shape[0] != erf.n_groups:
+            wsb = _lib.lib().tfrt_spot_error_workspace_bytes(st.N, erf.n_groups)
+            st.spot_ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+            st.acc = torch.zeros((erf.n_groups, 4), dtype=torch.int64, device=dev)
+        rows = erf.rows
+        erf.evaluate(st.rows[:, :st.N], rows[0], rows[1] if len(rows) == 2 else -1, labels,
+                     mask=st.row_face, perm=perm, grad=st.g_fin, err=st.err, acc=st.acc,
+                     workspace=st.spot_ws)
         with torch.no_grad():
             self.tests_total += st.row_passes[:st.N].sum() * st.M
         return st.g_fin
@@ -1313,9 +1556,10 @@ class FusedStep:
 
     def _density_signature(self):
         """A DensityError's part of the signature: the goal buffer's address (overwriting the goal
-        in place is seen by replays, another buffer re-captures), its shape and the constants."""
+        in place is seen by replays, another buffer re-captures), its shape and the constants; a
+        SpotError's: the label buffer's address and shape, G and the constants."""
         erf = self.opt.error_function
-        return erf.graph_key() if isinstance(erf, DensityError) else ()
+        return erf.graph_key() if isinstance(erf, (DensityError, SpotError)) else ()
 
     def _index_signature(self):
         """The refractive-index fields that take a gradient (boundary, field, identity of a tensor

@@ -1335,6 +1335,149 @@ def _density_error_cpu(rows, row_x, row_y, goal, grid, oob, mask, grad, err, hq)
     err[0], err[1], err[2] = e, 1.0, e
 
 
+SPOT_MAX_GROUPS = 1 << 20
+SPOT_LDS_GROUPS = 1024
+
+
+def spot_qbits(n_source):
+    """Fraction bits of tfrt_spot_error's fixed point for a source of ``n_source`` rays:
+    n_source * 2^qbits < 2^62, at most 52."""
+    return min(52, 62 - int(n_source).bit_length())
+
+
+def spot_grid(domain, qbits):
+    """The domain constants tfrt_spot_error takes, (x0, x1, qsx, y0, y1, qsy) in float64 with
+    qsx = 2^qbits / (x1 - x0) computed once here; one axis: the y constants are 0."""
+    one = float(np.ldexp(1.0, int(qbits)))
+    (x0, x1) = (float(v) for v in domain[0])
+    qsx = float(np.float64(one) / (np.float64(x1) - np.float64(x0)))
+    if len(domain) == 1:
+        return (x0, x1, qsx, 0.0, 0.0, 0.0)
+    (y0, y1) = (float(v) for v in domain[1])
+    return (x0, x1, qsx, y0, y1, float(np.float64(one) / (np.float64(y1) - np.float64(y0))))
+
+
+def spot_error(rows, row_x, row_y, group, n_groups, grid, oob_weight=0.0, mask=None, perm=None,
+               grad=None, err=None, acc=None, variant=0, workspace=None, qbits=None):
+    """tfrt_spot_error: the SpotError of the columns of ``rows`` (k, n), x in row ``row_x`` and y
+    in row ``row_y`` (-1: one field).  ``group``: contiguous int32 labels, one per SOURCE ray;
+    ``perm``: optional int32 (n,), the source ray of column i (None: column i is source ray i);
+    ``n_groups``: G, labels outside [0, G) belong to no spot; ``grid`` from ``spot_grid`` with the
+    same ``qbits`` (None: ``spot_qbits(group.numel())``); ``mask``: optional int32, column i
+    counts if mask[i] >= 0.  Returns (err {sum, terms, mean}, grad (k, n) float64, acc (G, 4)
+    int64 {count, Sx, Sy, 0}): rows ``row_x`` / ``row_y`` of ``grad`` are written for every column,
+    other rows only when ``grad`` is made here (zeros).  ``grad``, ``err``, ``acc``, ``workspace``
+    (uint8): buffers to reuse -- with all four given a CUDA call allocates nothing.
+
+    CUDA tensors run the kernels.  CPU tensors run a torch restatement with the same int64 fixed
+    point and the same operations per ray, each rounded on its own (``acc`` and the gradient rows
+    agree bit for bit; the error sums are torch's and agree to rounding)."""
+    n_groups = int(n_groups)
+    if group.dtype != torch.int32 or group.dim() != 1 or not group.is_contiguous():
+        raise ValueError("spot_error: group must be a contiguous int32 vector, one label per "
+                         "source ray")
+    if not 1 <= n_groups <= SPOT_MAX_GROUPS:
+        raise ValueError(f"spot_error: n_groups must lie in 1 .. {SPOT_MAX_GROUPS}")
+    k, n = rows.shape
+    if perm is not None and (perm.dtype != torch.int32 or perm.numel() < n
+                             or not perm.is_contiguous()):
+        raise ValueError("spot_error: perm must be contiguous int32, one entry per column")
+    if qbits is None:
+        qbits = spot_qbits(group.numel())
+    dev = rows.device
+    if grad is None:
+        grad = torch.zeros((k, n), dtype=torch.float64, device=dev)
+    if err is None:
+        err = torch.empty(3, dtype=torch.float64, device=dev)
+    if acc is None:
+        acc = torch.empty((n_groups, 4), dtype=torch.int64, device=dev)
+    if tuple(acc.shape) != (n_groups, 4) or acc.dtype != torch.int64 or not acc.is_contiguous():
+        raise ValueError("spot_error: acc must be contiguous int64 of shape (n_groups, 4)")
+    x0, x1, qsx, y0, y1, qsy = grid
+    if not rows.is_cuda:
+        if not 1 <= qbits <= 52 or n >= 1 << (62 - qbits):
+            raise ValueError("spot_error: qbits must lie in 1 .. 52 with n < 2^(62 - qbits)")
+        _spot_error_cpu(rows, row_x, row_y, group, n_groups, grid, float(oob_weight), mask, perm,
+                        grad, err, acc, int(qbits))
+        return err, grad, acc
+    _need_gpu(rows, group, mask, perm, grad, err, acc)
+    if rows.stride(1) != 1 or grad.stride(1) != 1:
+        raise ValueError("spot_error: rows and grad must have contiguous columns")
+    L = _lib.lib()
+    wsb = L.tfrt_spot_error_workspace_bytes(n, n_groups)
+    if workspace is None:
+        workspace = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    check(L.tfrt_spot_error(
+        _p(rows), rows.stride(0), n, _DT[rows.dtype], _p(mask), row_x, row_y, _p(group),
+        group.numel(), _p(perm), n_groups, x0, x1, qsx, y0, y1, qsy, int(qbits),
+        float(oob_weight), _p(grad), grad.stride(0), _p(err), _p(acc), int(variant),
+        _p(workspace), workspace.numel(), _stream(rows)), "tfrt_spot_error")
+    return err, grad, acc
+
+
+def spot_centroids(acc, grid, fields=2):
+    """The (G, fields) float64 centroids of a tfrt_spot_error record table:
+    ``x0 + (Sx / count) / qsx``, NaN for a group without rays."""
+    x0, _, qsx, y0, _, qsy = grid
+    cnt = acc[:, 0].double()
+    cnt = torch.where(cnt > 0, cnt, torch.full_like(cnt, float("nan")))
+    cols = [x0 + (acc[:, 1].double() / cnt) / qsx]
+    if fields == 2:
+        cols.append(y0 + (acc[:, 2].double() / cnt) / qsy)
+    return torch.stack(cols, dim=1)
+
+
+def _spot_error_cpu(rows, row_x, row_y, group, n_groups, grid, oob, mask, perm, grad, err, acc,
+                    qbits):
+    """The CPU path of ``spot_error`` (every torch op rounds on its own, as the kernels do)."""
+    x0, x1, qsx, y0, y1, qsy = grid
+    two = row_y >= 0
+    n = rows.shape[1]
+    qmax = float(np.ldexp(1.0, qbits))
+    x = rows[row_x].double()
+    y = rows[row_y].double() if two else torch.zeros_like(x)
+    counting = torch.ones(n, dtype=torch.bool) if mask is None else (mask[:n] >= 0)
+    finite = torch.isfinite(x) & torch.isfinite(y)
+    s = torch.arange(n, dtype=torch.int64) if perm is None else perm[:n].long()
+    s_ok = (s >= 0) & (s < group.numel())
+    label = torch.full((n,), -1, dtype=torch.int64)
+    label[s_ok] = group[s[s_ok]].long()
+    spot = counting & finite & s_ok & (label >= 0) & (label < n_groups)
+    out = (x < x0) | (x > x1)
+    if two:
+        out |= (y < y0) | (y > y1)
+    inside, outside = spot & ~out, spot & out
+    zero = torch.zeros((), dtype=torch.float64)
+    # outside: the penalty and its derivative
+    ex = torch.maximum(x0 - x, zero) + torch.maximum(x - x1, zero)
+    ey = (torch.maximum(y0 - y, zero) + torch.maximum(y - y1, zero)) if two else torch.zeros_like(x)
+    pen = (oob * (ex * ex + ey * ey))[outside].sum()
+    gx = torch.where(outside, oob * (2.0 * ex) * ((x > x1).double() - (x < x0).double()), zero)
+    gy = torch.where(outside, oob * (2.0 * ey) * ((y > y1).double() - (y < y0).double()), zero)
+    # inside: the fixed-point records
+    xi, yi, li = x[inside], y[inside], label[inside]
+    acc.zero_()
+    acc[:, 0].index_add_(0, li, torch.ones_like(li))
+    acc[:, 1].index_add_(0, li, torch.round((xi - x0) * qsx).clamp(0.0, qmax).long())
+    if two:
+        acc[:, 2].index_add_(0, li, torch.round((yi - y0) * qsy).clamp(0.0, qmax).long())
+    cnt = acc[li, 0].double()
+    dx = xi - (x0 + (acc[li, 1].double() / cnt) / qsx)
+    gx[inside] = 2.0 * dx
+    terms = dx * dx
+    if two:
+        dy = yi - (y0 + (acc[li, 2].double() / cnt) / qsy)
+        gy[inside] = 2.0 * dy
+        terms = terms + dy * dy
+    grad[row_x, :n] = gx
+    if two:
+        grad[row_y, :n] = gy
+    e = terms.sum() + pen
+    n_terms = float(int(counting.sum()) * (2 if two else 1))
+    err[0], err[1] = e, n_terms
+    err[2] = e / n_terms if n_terms > 0 else float("nan")
+
+
 def restore_plan(ids, counts_dev, P, cls_col, perm, n_src, n_rows=None, total=None, zero=False):
     """(inv, dest_of, original ids) of one output class of a trace over permuted rays
     (tfrt_restore_order): row j of the class in the reference's order = row ``inv[j]`` of the

@@ -29,8 +29,9 @@ import torch
 
 from . import distributed as tdist
 from . import _lib, ops
-# (GoalError, RowwiseError, DensityError: public API)
-from .fused_step import FusedStep, GoalError, RowwiseError, DensityError, _NotInPlace  # noqa: F401
+# (GoalError, RowwiseError, DensityError, SpotError: public API)
+from .fused_step import (FusedStep, GoalError, RowwiseError, DensityError, SpotError,  # noqa: F401
+                         _NotInPlace)
 
 
 class DeferredScalar:

@@ -368,6 +368,17 @@ typedef struct tfrt_scene3d {
    * (tfrt/engine.py:2069-2111, 1379-1403), and class gradients are read in that order by the
    * reverse sweep -- no tfrt_restore_order afterwards.  NULL: the order of src_rays. */
   const int32_t* ray_slot;
+  /* With in_place, optional: (ceil(n_rays / 64)) i32, a permutation of the GROUPS of 64 consecutive
+   * columns of src_rays -- the order in which k_trace_inplace and the folded goal sweep of an
+   * in-place trace (tfrt_trace3d_backward_goal's steady-state kernel) take them: workgroup b works
+   * on group wave_schedule[b], the expensive groups first (tfrt_trace3d_wave_schedule makes one).
+   * A hint about time only: every group is traced and swept exactly as without it, and whatever is
+   * stored per wavefront is stored at the wavefront's own index, so outputs, counts and the error
+   * sum are the same bit for bit (the face gradient's atomics were unordered before).  It MUST be
+   * a permutation: a group that is missing is not traced.  Read by the device when the launch
+   * runs, so a captured launch sees later contents.  NULL: index order.  No reference counterpart
+   * (the reference has no wavefronts). */
+  const int32_t* wave_schedule;
 } tfrt_scene3d;
 
 /* One class of output rays (finished / active history / stopped / dead), compacted stably in
@@ -444,6 +455,28 @@ int tfrt_trace3d_in_place(const tfrt_scene3d* scene, int64_t n_rays, int32_t max
 int tfrt_trace3d_executed(int64_t n_rays, int64_t n_faces, int32_t max_passes, int32_t state_dtype,
                           const void* workspace, size_t workspace_bytes, int64_t* executed,
                           void* stream);
+
+/* The wavefront schedule for the NEXT in-place traces of these rays in this order
+ * (tfrt_scene3d.wave_schedule), from the work the trace whose tape is in `workspace` recorded per
+ * wavefront: schedule_out receives ceil(n_rays / 64) i32, the groups of 64 rays listed by cost
+ * class (passes entered, candidate faces tested), the heaviest class first, ascending inside a
+ * class; equal costs give 0, 1, 2, ...  One small launch on `stream`; meant to run when a step's
+ * launch sequence is set up, not inside it.  Same n_rays / n_faces / max_passes / state_dtype as
+ * the forward call.  No reference counterpart. */
+int tfrt_trace3d_wave_schedule(int64_t n_rays, int64_t n_faces, int32_t max_passes,
+                               int32_t state_dtype, const void* workspace, size_t workspace_bytes,
+                               int32_t* schedule_out, void* stream);
+
+/* What tfrt_trace3d_wave_schedule reads (measurement and tests; no reference counterpart): the
+ * count rows the in-place trace whose tape is in `workspace` left per wavefront, copied densely
+ * into rows_out, (max_passes + 2) x W u32 -- rows 0 .. max_passes-1 the four class counts of each
+ * pass, one byte each (non-zero: the wavefront entered the pass), then the (ray, face) pairs that
+ * reached the exact test and the candidate faces tested against the bundle.  Returns W > 0, the
+ * trace's wavefronts (of 64 rays, or of 32: then two to a group of the schedule), or < 0 on bad
+ * arguments; rows_out NULL: only W. */
+int tfrt_trace3d_wave_rows(int64_t n_rays, int64_t n_faces, int32_t max_passes, int32_t state_dtype,
+                           const void* workspace, size_t workspace_bytes, uint32_t* rows_out,
+                           void* stream);
 
 /* Reverse sweep over the tape left in `workspace` by tfrt_trace3d_forward with the same
  * arguments.  Replaces the ray-dependent part of tape.gradient in

@@ -43,6 +43,7 @@
 #include <type_traits>
 #include "tfrt_common.h"
 #include "goal_finish.h"
+#include "wave_schedule.h"
 
 namespace tfrt {
 
@@ -2550,6 +2551,10 @@ struct InplaceArgs {
   int64_t src_stride;
   int32_t N, P, bundle, nwaves;
   const InplaceTape* tape;   // (device memory: see InplaceTape)
+  // tfrt_scene3d.wave_schedule (wave_schedule.h) or null: workgroup b takes wavefront
+  // (sched[b >> gshift] << gshift) + (b & ((1 << gshift) - 1)), of ngroups groups of 64 rays
+  const int32_t* sched;
+  int32_t ngroups, gshift;
 };
 
 // Wavefronts per SIMD: five for the plain kernel (96 registers, no scratch; with the 8 KB of LDS a
@@ -2565,7 +2570,16 @@ struct InplaceArgs {
 template <typename T, bool ROWS>
 __device__ __forceinline__ void trace_inplace(const InplaceArgs<T>& a, const BeamScene& g) {
   using RT = std::conditional_t<sizeof(T) <= 4, float, double>;
-  const int lane = threadIdx.x, qwave = blockIdx.x;
+  const int lane = threadIdx.x;
+  // (one wave-uniform load at entry: the index lives in a scalar register like blockIdx.x did, and
+  // everything indexed by wavefront -- rays, tape, count rows -- follows it)
+  int qwave = blockIdx.x;
+  if (a.sched != nullptr) {
+    const int g = __builtin_amdgcn_readfirstlane(a.sched[blockIdx.x >> a.gshift]);
+    if ((unsigned)g >= (unsigned)a.ngroups) return;
+    qwave = (g << a.gshift) + ((int)blockIdx.x & ((1 << a.gshift) - 1));
+    if (qwave >= a.nwaves) return;   // (the last group of a 32-ray trace may hold one wavefront)
+  }
   const int q = qwave * a.bundle + lane;
   const bool has = lane < a.bundle && q < a.N;
   const int64_t i = has ? q : 0;
@@ -2848,6 +2862,72 @@ __global__ __launch_bounds__(BLOCK) void k_inplace_work(const uint32_t* __restri
     unsigned long long t = 0ull;
     for (int w = 0; w < WAVES; ++w) t += part[w];
     out[blockIdx.x] = t;
+  }
+}
+
+// The wavefront schedule of wave_schedule.h from the count rows of the trace before: one
+// workgroup -- the cost range, a class histogram in LDS, its scan (heaviest class first), then a
+// stable scatter, 1024 groups at a time (ballot ranks inside a wavefront, the wavefronts' counts
+// through LDS).  It runs when a step's launch sequence is set up, never inside it.
+__global__ __launch_bounds__(1024) void k_wave_schedule(const uint32_t* __restrict__ wcount,
+                                                        int wstride, int P, int nwaves, int per,
+                                                        int G, int32_t* __restrict__ sched) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ uint32_t lo, hi;
+  __shared__ int base[WAVE_SCHED_CLASSES];
+  __shared__ int wcnt[16][WAVE_SCHED_CLASSES];
+  if (tid == 0) {
+    lo = 0xFFFFFFFFu;
+    hi = 0u;
+  }
+  if (tid < WAVE_SCHED_CLASSES) base[tid] = 0;
+  __syncthreads();
+  uint32_t mn = 0xFFFFFFFFu, mx = 0u;
+  for (int g = tid; g < G; g += 1024) {
+    const uint32_t c = wave_group_cost(wcount, (size_t)wstride, P, nwaves, per, g);
+    mn = min(mn, c);
+    mx = max(mx, c);
+  }
+  atomicMin(&lo, mn);
+  atomicMax(&hi, mx);
+  __syncthreads();
+  const uint32_t cmin = lo, cmax = hi;
+  for (int g = tid; g < G; g += 1024)
+    atomicAdd(&base[wave_class(wave_group_cost(wcount, (size_t)wstride, P, nwaves, per, g), cmin, cmax)], 1);
+  __syncthreads();
+  if (tid == 0) {   // where every class begins: the heaviest first
+    int run = 0;
+    for (int c = WAVE_SCHED_CLASSES - 1; c >= 0; --c) {
+      const int n = base[c];
+      base[c] = run;
+      run += n;
+    }
+  }
+  __syncthreads();
+  for (int g0 = 0; g0 < G; g0 += 1024) {
+    const int g = g0 + tid;
+    const int cls =
+        g < G ? wave_class(wave_group_cost(wcount, (size_t)wstride, P, nwaves, per, g), cmin, cmax) : -1;
+    int rank = 0;
+#pragma unroll
+    for (int c = 0; c < WAVE_SCHED_CLASSES; ++c) {
+      const unsigned long long m = __ballot(cls == c);
+      if (cls == c) rank = rank_below(m);
+      if (lane == 0) wcnt[wave][c] = __popcll(m);
+    }
+    __syncthreads();
+    if (cls >= 0) {
+      int at = base[cls] + rank;
+      for (int w = 0; w < wave; ++w) at += wcnt[w][cls];
+      if (at < G) sched[at] = g;   // (always: the classes' sizes sum to G)
+    }
+    __syncthreads();
+    if (tid < WAVE_SCHED_CLASSES) {
+      int t = 0;
+      for (int w = 0; w < 16; ++w) t += wcnt[w][tid];
+      base[tid] += t;
+    }
+    __syncthreads();
   }
 }
 
@@ -3666,6 +3746,8 @@ struct ChainGoalArgs {
   const double* feta;      // per-face indices (FaceTables), never null here
   const double* face_verts;        // of tfrt_scene3d: what backward_core reads on this path
   const uint8_t* face_grad_mask;
+  const int32_t* sched;    // tfrt_scene3d.wave_schedule or null: workgroup b takes wavefront sched[b]
+  int32_t ngroups;
 };
 
 template <typename T>
@@ -3675,7 +3757,14 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
   // the reference's squared_difference and reduce_sum are separate ops: no contraction
 #pragma clang fp contract(off)
   const int n0 = a.nrays[0];
-  const int i0 = blockIdx.x * 64 + threadIdx.x;
+  // (the wavefront's index, scalar: rays, tape, partial and partial_cnt follow it, so the error
+  // sum's fixed order does not depend on the schedule)
+  int wave = blockIdx.x;
+  if (a.sched != nullptr) {
+    wave = __builtin_amdgcn_readfirstlane(a.sched[blockIdx.x]);
+    if ((unsigned)wave >= (unsigned)a.ngroups) return;
+  }
+  const int i0 = wave * 64 + threadIdx.x;
   const int lane = threadIdx.x;
   if ((i0 & ~63) >= n0) {  // (whole wave)
     if (lane == 0) {
@@ -4314,15 +4403,20 @@ static int trace3d_forward_t(const TraceCall<tfrt_scene3d>& c) {
     a.bundle = inplace_bundle(N);
     a.nwaves = cdiv(N, a.bundle);
     a.tape = tape.tape_args;
+    a.sched = sc->wave_schedule;
+    a.ngroups = cdiv(N, 64);
+    a.gshift = a.bundle == 64 ? 0 : 1;
+    // (with a schedule every group's wavefronts get a workgroup, the missing last one returns)
+    const int n_groups_waves = a.sched != nullptr ? a.ngroups << a.gshift : a.nwaves;
     const BeamScene bs = {ac.susphere, ac.clsphere, ac.csphere, ac.crec, sc->face_verts, c0,
                           ac.n_clusters, cdiv(ac.n_clusters, SUPER), sc->intersect_epsilion,
                           sc->size_epsilion, sc->ray_start_epsilion};
     {
       ProfScope prof(TFRT_PROF_INTERSECT, st);
       if (rows_in_place)
-        hipLaunchKernelGGL((k_trace_inplace_rows<T>), dim3(a.nwaves), dim3(64), 0, st, a, bs);
+        hipLaunchKernelGGL((k_trace_inplace_rows<T>), dim3(n_groups_waves), dim3(64), 0, st, a, bs);
       else
-        hipLaunchKernelGGL((k_trace_inplace<T>), dim3(a.nwaves), dim3(64), 0, st, a, bs);
+        hipLaunchKernelGGL((k_trace_inplace<T>), dim3(n_groups_waves), dim3(64), 0, st, a, bs);
     }
     // (no room for ray sets: no scan either -- tfrt_trace3d_compact makes counts and sets later)
     const bool want_rows = !rows_in_place &&
@@ -4532,6 +4626,8 @@ static int trace3d_backward_t(const SweepCall3& c) {
         g.feta = a.feta;
         g.face_verts = sc->face_verts;
         g.face_grad_mask = sc->face_grad_mask;
+        g.sched = sc->wave_schedule;
+        g.ngroups = cdiv(N, 64);
         hipLaunchKernelGGL((k_backward_chain_goal_inplace<T>), dim3(cdiv(N, 64)), dim3(64),
                            (size_t)P * 64 * sizeof(int2), st, g);
       } else if (N > 0 && sc->grad_n_in != nullptr)
@@ -4638,6 +4734,42 @@ int tfrt_trace3d_executed(int64_t n_rays, int64_t n_faces, int32_t max_passes, i
                      cdiv(n_rays, inplace_bundle(n_rays)), wstride,
                      reinterpret_cast<unsigned long long*>(executed));
   return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+}
+
+int tfrt_trace3d_wave_schedule(int64_t n_rays, int64_t n_faces, int32_t max_passes,
+                               int32_t state_dtype, const void* workspace, size_t workspace_bytes,
+                               int32_t* schedule_out, void* stream) {
+  if (n_rays < 64 || n_rays >= (1ll << 31) - 4096 || n_faces < 0 || max_passes < 1 || !workspace ||
+      !schedule_out)
+    return TFRT_E_BADARG;
+  const Plan3 pl = make_plan(n_rays, n_faces);
+  const Layout3 lay = make_layout(n_rays, n_faces, max_passes, state_dtype, pl);
+  if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
+  const int bundle = inplace_bundle(n_rays);
+  hipLaunchKernelGGL(k_wave_schedule, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream),
+                     Tape3<const void>(workspace, lay, n_rays).wcount, (int)inplace_wstride(n_rays),
+                     (int)max_passes, cdiv(n_rays, bundle), 64 / bundle, cdiv(n_rays, 64),
+                     schedule_out);
+  return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+}
+
+int tfrt_trace3d_wave_rows(int64_t n_rays, int64_t n_faces, int32_t max_passes, int32_t state_dtype,
+                           const void* workspace, size_t workspace_bytes, uint32_t* rows_out,
+                           void* stream) {
+  if (n_rays < 64 || n_rays >= (1ll << 31) - 4096 || n_faces < 0 || max_passes < 1 || !workspace)
+    return TFRT_E_BADARG;
+  const Plan3 pl = make_plan(n_rays, n_faces);
+  const Layout3 lay = make_layout(n_rays, n_faces, max_passes, state_dtype, pl);
+  if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
+  const int nwaves = cdiv(n_rays, inplace_bundle(n_rays));
+  if (rows_out != nullptr &&
+      hipMemcpy2DAsync(rows_out, (size_t)nwaves * sizeof(uint32_t),
+                       Tape3<const void>(workspace, lay, n_rays).wcount,
+                       inplace_wstride(n_rays) * sizeof(uint32_t), (size_t)nwaves * sizeof(uint32_t),
+                       (size_t)max_passes + 2, hipMemcpyDeviceToDevice,
+                       static_cast<hipStream_t>(stream)) != hipSuccess)
+    return TFRT_E_LAUNCH;
+  return nwaves;
 }
 
 int tfrt_trace3d_compact(const void* src_rays, int64_t src_stride, int64_t n_rays,

@@ -730,6 +730,14 @@ class OpticalEngine:
         if in_place not in ("auto", True, False):
             raise ValueError(f"OpticalEngine: in_place must be 'auto', True or False, got {in_place!r}")
         self.in_place = in_place
+        # In-place traces of the fused optimiser step only: the order in which the trace and its
+        # reverse sweep hand their wavefronts out (tfrt_scene3d.wave_schedule).  "auto": the step
+        # makes a schedule from the work its first in-place trace records per wavefront -- the
+        # expensive wavefronts first -- when the launch has more wavefronts than the chip holds at
+        # once, and makes it again when the ray order, the scene's topology or the trace's shape
+        # change.  False: index order.  An int32 device tensor: this permutation of the groups of
+        # 64 rays (ops.check_wave_schedule).  A hint about time: results do not depend on it.
+        self.wave_schedule = "auto"
         # 2-D only.  False (default, the reference): a totally reflected ray has a NaN gradient
         # (tf.asin in the unselected tf.where branch, geometry.py:640-646) which poisons every
         # boundary entry it touched; SGD_Optimizer zeroes those (optimizer.py:226-229).  True:

@@ -648,6 +648,7 @@ class _StepState:
         "density_ws", "hq",                                  # a DensityError's workspace and histogram
         "spot_ws", "acc",                                    # a SpotError's workspace and group records
         "chain_ws", "inherited",                             # made on first use
+        "sched", "sched_key", "sched_checked",               # the in-place trace's wavefront schedule
         "block", "stream", "perm", "inplace")                # of the last enqueued step
 
     def __init__(self, sig, block, dim, P, flags, fields, workspace_bytes):
@@ -708,6 +709,10 @@ class FusedStep:
     # per step.  True: always try (bench.py --collective-in-graph).
     capture_collective = "auto"
     collective_in_graph = False
+    # engine.wave_schedule == "auto": a schedule is made when the step has more groups of 64 rays
+    # than this (None: the wavefronts the chip holds of k_trace_inplace, 4 SIMDs x 5 per CU -- a
+    # launch that is resident all at once has no order to gain from)
+    schedule_min_waves = None
 
     def __init__(self, optimizer, graph="auto", graph_warmup=3):
         self.opt = optimizer
@@ -941,15 +946,61 @@ class FusedStep:
         st.inplace = (block, self._lengths()[1]) if inplace else None
         clear = {"clear_buffer": st.g_fv.data_ptr(), "clear_count": st.g_fv.numel()} if folded \
             else {}
-        # (in_place: the reverse sweep is given the same value as the forward)
-        with _override(sc, in_place=1 if inplace else 0):
+        sched = self._wave_schedule(st) if inplace else None
+        # (in_place, wave_schedule: the reverse sweep is given the same values as the forward)
+        with _override(sc, in_place=1 if inplace else 0,
+                       wave_schedule=None if sched is None else sched.data_ptr()):
             with _override(sc, **clear):
                 self._trace_forward(st, sc, st.no_outs if inplace else st.outs)
             with self._index_grads3d(sc, st, need_back):
                 self._goal_backward3d(st, sc, (goal, goal_by_ray), folded, need_back)
+        if inplace:
+            self._make_wave_schedule(st, perm)
         if not need_back:
             return None, st
         return self._parameter_gradients(*self._outs3d(fv, st, index), tap_log), st
+
+    def _wave_schedule(self, st):
+        """The wavefront schedule this in-place step runs with (engine.wave_schedule), or None:
+        the caller's tensor, checked once per version, or the one _make_wave_schedule left."""
+        given = self.opt.engine.wave_schedule
+        if isinstance(given, torch.Tensor):
+            key = (id(given), given._version)
+            if st.sched_checked != key:
+                if given.device != st.block.device:
+                    raise RuntimeError("FusedStep: wave_schedule must be on the rays' device")
+                ops.check_wave_schedule(given, st.N)
+                st.sched_checked = key
+            return given
+        if given != "auto":
+            if given is not False:
+                raise ValueError("OpticalEngine.wave_schedule must be 'auto', False or an int32 "
+                                 f"tensor, got {given!r}")
+            return None
+        return st.sched if st.sched_key is not None else None
+
+    def _make_wave_schedule(self, st, perm):
+        """engine.wave_schedule == "auto": after the first in-place step of these rays in this
+        order over this scene (what the key holds; N, M and P are the state's own), one launch
+        behind the trace that has just left its work rows turns them into the schedule of the
+        steps that follow.  The buffer is persistent and read by address: a later build -- another
+        order, another topology -- needs no new capture.  Never inside a capture, never per step:
+        a source re-drawn in place keeps its wavefronts' places on the key grid, and a schedule
+        gone stale costs time, not correctness."""
+        eng = self.opt.engine
+        if not isinstance(eng.wave_schedule, str) or eng.wave_schedule != "auto":
+            return
+        G = ops.wave_groups(st.N)
+        least = self.schedule_min_waves
+        if least is None:
+            least = 20 * torch.cuda.get_device_properties(st.block.device).multi_processor_count
+        key = (id(perm), eng.optical_system.scene_signature())
+        if G <= least or st.sched_key == key or torch.cuda.is_current_stream_capturing():
+            return
+        if st.sched is None:
+            st.sched = torch.empty(G, dtype=torch.int32, device=st.block.device)
+        ops.wave_schedule(st.N, st.M, st.P, st.block.dtype, st.ws, out=st.sched)
+        st.sched_key = key
 
     def _goal_rows(self, erf, src, perm):
         """The goal table of the step's rays and whether it is (N, fields) rows instead of
@@ -1546,6 +1597,8 @@ class FusedStep:
                 tdist.world_size(), eng.optical_system.scene_signature(), bool(eng.deterministic),
                 id((getattr(eng, "_order_cache", None) or (None, None, None))[2]),
                 getattr(eng, "_visit_all_key", None) is not None, eng.in_place,
+                id(eng.wave_schedule) if isinstance(eng.wave_schedule, torch.Tensor)
+                else eng.wave_schedule,
                 self._index_signature()) + self._rule_signature() + self._density_signature()
 
     def _rule_signature(self):

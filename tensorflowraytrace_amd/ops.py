@@ -1162,6 +1162,61 @@ def inverse_order(perm):
     return inv
 
 
+def wave_groups(n_rays):
+    """Entries of a wavefront schedule for ``n_rays`` rays: the groups of 64 consecutive rays."""
+    return (int(n_rays) + 63) // 64
+
+
+def wave_schedule(n_rays, n_faces, max_passes, state_dtype, workspace, out=None):
+    """The wavefront schedule for the next in-place traces of the rays whose trace left its tape in
+    ``workspace`` (tfrt_trace3d_wave_schedule; tfrt_scene3d.wave_schedule): int32, the groups of 64
+    rays by cost class, the heaviest class first.  ``state_dtype``: the ray block's torch dtype;
+    ``out``: an int32 tensor of ``wave_groups(n_rays)`` entries to write into."""
+    _need_gpu(workspace, out)
+    G = wave_groups(n_rays)
+    if out is None:
+        out = torch.empty(G, dtype=torch.int32, device=workspace.device)
+    if out.dtype != torch.int32 or out.numel() != G or not out.is_contiguous():
+        raise TfrtError("wave_schedule: `out` must be a contiguous int32 tensor of ceil(N / 64) entries")
+    check(_lib.lib().tfrt_trace3d_wave_schedule(
+        n_rays, n_faces, max_passes, _DT[state_dtype], _p(workspace), workspace.numel(), _p(out),
+        _stream(workspace)), "tfrt_trace3d_wave_schedule")
+    return out
+
+
+def wave_rows(n_rays, n_faces, max_passes, state_dtype, workspace):
+    """The per-wavefront count rows ``wave_schedule`` reads (tfrt_trace3d_wave_rows): int32 tensor
+    (max_passes + 2, W) of uint32 bits, W the wavefronts of the trace."""
+    _need_gpu(workspace)
+    L = _lib.lib()
+    args = (n_rays, n_faces, max_passes, _DT[state_dtype], _p(workspace), workspace.numel())
+    W = L.tfrt_trace3d_wave_rows(*args, None, None)
+    if W < 0:
+        check(W, "tfrt_trace3d_wave_rows")
+    rows = torch.empty((max_passes + 2, W), dtype=torch.int32, device=workspace.device)
+    code = L.tfrt_trace3d_wave_rows(*args, _p(rows), _stream(workspace))
+    if code < 0:
+        check(code, "tfrt_trace3d_wave_rows")
+    return rows
+
+
+def check_wave_schedule(schedule, n_rays):
+    """Refuses a caller's wavefront schedule unless it is a contiguous int32 device tensor holding a
+    permutation of ``range(wave_groups(n_rays))`` -- a group that is missing would not be traced.
+    Checked by sorting (one host read), before anything is launched with it."""
+    G = wave_groups(n_rays)
+    if not isinstance(schedule, torch.Tensor) or schedule.dtype != torch.int32:
+        raise TfrtError("wave_schedule must be an int32 tensor")
+    _need_gpu(schedule)
+    if schedule.dim() != 1 or schedule.numel() != G or not schedule.is_contiguous():
+        raise TfrtError(f"wave_schedule must hold {G} entries (one per 64 rays), "
+                        f"got shape {tuple(schedule.shape)}")
+    want = torch.arange(G, dtype=torch.int32, device=schedule.device)
+    if not torch.equal(torch.sort(schedule).values, want):
+        raise TfrtError(f"wave_schedule must be a permutation of range({G})")
+    return schedule
+
+
 def permute_rays(rays, index, out=None):
     """``rays[:, index]`` of a (6, N) ray block (tfrt_permute_rays)."""
     _need_gpu(rays, index)

@@ -3487,6 +3487,46 @@ __device__ __forceinline__ int backward_core(
   return face_out;
 }
 
+// backward_core for a caller that holds everything the slot reads in registers already
+// (k_backward_chain_goal_inplace asks for all of a pass's loads together): the same decisions and
+// the same arithmetic in the same order, no access to memory.  Of backward_core's cases only
+// those of that path are here: no class gradient but the finished row's `seed`, per-face indices
+// (n_in = n_out = 1 unless the slot has a child), no gradient with respect to them.
+// face_wanted: the face's byte of tfrt_scene3d.face_grad_mask is set, or there is no mask.
+__device__ __forceinline__ int backward_core_loaded(
+    int tape, int tri, bool child_pass, const double s[3], const double e[3], const double P[9],
+    double t_rec, double n_in, double n_out, bool face_wanted, double L, const double child[6],
+    const double seed[6], double gs[3], double ge[3], double gP[9]) {
+  int face_out = -1;
+  const int cls = tape & 3;
+  for (int k = 0; k < 3; ++k) gs[k] = ge[k] = 0.0;
+  if (cls != CLS_DEAD) {
+    double g_s[3] = {0, 0, 0}, g_h[3] = {0, 0, 0}, g_ce[3] = {0, 0, 0};
+    bool has_child = false;
+    if (cls == CLS_FINISHED) {
+      for (int k = 0; k < 3; ++k) {
+        g_s[k] += seed[k];
+        g_h[k] += seed[3 + k];
+      }
+    } else if (cls == CLS_ACTIVE && child_pass) {
+      has_child = true;
+      for (int k = 0; k < 3; ++k) {
+        g_h[k] += child[k];
+        g_ce[k] += child[3 + k];
+      }
+    }
+    bool nz = has_child;
+    for (int k = 0; k < 3; ++k) nz = nz || g_s[k] != 0.0 || g_h[k] != 0.0;
+    if (nz) {
+      const int branch = ((tape & TAPE_INTERNAL) ? 1 : 0) | ((tape & TAPE_REFLECT) ? 2 : 0);
+      adjoint3d(s, e, P, t_rec, has_child, n_in, n_out, L, g_s, g_h, g_ce, gs, ge, gP, nullptr,
+                branch, false);
+      if (face_wanted) face_out = tri;
+    }
+  }
+  return face_out;
+}
+
 // The same with the child's gradient read from, and the slot's own written to, the sweep's
 // per-pass buffers (k_backward3d).  The first pass writes to the caller's g_src, or nowhere.
 template <typename T>
@@ -3722,7 +3762,9 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
 // k_backward_chain<T, 1, true, false> on that path -- the same arithmetic in the same order, the
 // same atomics -- without the run-time branches of the other paths and with an argument block of
 // what this path reads: ChainArgs plus tfrt_scene3d are ~60 scalars, which left the general
-// kernel 38 spilled scalar registers on this very path.
+// kernel 38 spilled scalar registers on this very path.  With the path fixed,
+// what a lane reads in a pass is known from its record alone, so the pass asks for all of it at
+// once and computes from registers (backward_core_loaded).
 template <typename T>
 struct ChainGoalArgs {
   const T* src;            // source rays (inputs of pass 1)
@@ -3744,7 +3786,7 @@ struct ChainGoalArgs {
   double* partial;         // one partial error sum per wavefront of the launch
   int32_t* partial_cnt;    // ... and {finished rays, passes entered} per wavefront, or null
   const double* feta;      // per-face indices (FaceTables), never null here
-  const double* face_verts;        // of tfrt_scene3d: what backward_core reads on this path
+  const double* face_verts;        // of tfrt_scene3d: what the sweep reads of it on this path
   const uint8_t* face_grad_mask;
   const int32_t* sched;    // tfrt_scene3d.wave_schedule or null: workgroup b takes wavefront sched[b]
   int32_t ngroups;
@@ -3779,10 +3821,6 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
   extern __shared__ int2 chain_goal_lds[];   // [pass][lane]: tape byte, face
   int2* chain = chain_goal_lds;
   const int P = a.P;
-  // (of the scene only these two fields are read below: the rest folds away)
-  tfrt_scene3d sc = {};
-  sc.face_verts = a.face_verts;
-  sc.face_grad_mask = a.face_grad_mask;
   int last = -1;
   if (i0 < n0) {
     for (int p = 0; p < P; ++p) {
@@ -3809,31 +3847,86 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
     bool fin_here = false;
     if (p <= last) {
       const int2 rec = chain[p * 64 + lane];
-      const int tape = rec.x;
+      const int tape = rec.x, cls = tape & 3;
+      const int face = max(rec.y, -1);   // (a record is a face or -1)
       const size_t off = (size_t)p * a.n;
       const T* rin = p == 0 ? a.src : a.rays_ws + (size_t)(p - 1) * 6 * a.n;
       const int64_t sin = p == 0 ? a.src_stride : a.n;
+      const bool child_pass = p < P - 1;
+      fin_here = p == last && cls == CLS_FINISHED;
+      // Every load of the pass is asked for here, before the first of them is waited for: one
+      // round trip to memory per pass.  (Left inside the finished arm, its run-time loop over the
+      // goal's columns and backward_core, the compiler cannot move a load out of a divergent
+      // branch or a loop: ray, hit parameter, one goal column after the other, then the face --
+      // five dependent trips on the finished arm, two on the other.)  Each lane asks for what
+      // backward_core and the finished arm read for it and for nothing else; the one exception
+      // is the mask byte of a finished lane whose residuals are all exactly zero, which carries
+      // no gradient and is not known before the goal has arrived -- its own face's byte.
+      const bool on_face = face >= 0 && cls != CLS_DEAD;
+      const bool with_child = on_face && child_pass && cls == CLS_ACTIVE;
+      // (the lane's ray index through an empty statement the compiler cannot see past: the
+      // per-lane addresses below are then formed in the pass that uses them -- moved out of the
+      // loop they stay in 16 vector registers for the whole walk, which the adjoint needs)
+      int iv = i0;
+      __asm__ volatile("" : "+v"(iv));
+      T ray_w[6];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) ray_w[k] = rin[k * sin + iv];
+      double t_rec = 0.0;
+      if (fin_here || on_face) t_rec = a.rec_t[off + iv];
+      double goal_w[6];
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        goal_w[c] = 0.0;
+        if (fin_here && c < a.gf.n)
+          goal_w[c] = a.goal[(int64_t)c * a.goal_stride + (int64_t)iv * a.goal_ray_stride];
+      }
+      double Pf[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, n_in = 1.0, n_out = 1.0;
+      uint8_t mask_w = 1;
+      if (on_face) {
+        const double* fp = a.face_verts + 9 * (int64_t)face;
+#pragma unroll
+        for (int q = 0; q < 9; ++q) Pf[q] = fp[q];
+        if (a.face_grad_mask != nullptr && (with_child || cls == CLS_FINISHED))
+          mask_w = a.face_grad_mask[face];
+      }
+      if (with_child) {
+        n_in = a.feta[4 * (int64_t)face + 2];
+        n_out = a.feta[4 * (int64_t)face + 3];
+      }
+      double s0[3], e0[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        s0[k] = static_cast<double>(ray_w[k]);
+        e0[k] = static_cast<double>(ray_w[3 + k]);
+      }
+      // (the byte as loaded, opaque until here: tested where it is asked for, the test and its
+      // wait for everything in flight would sit in front of the loads that follow it)
+      int mask_i = mask_w;
+      __asm__ volatile("" : "+v"(mask_i));
       double seed[6] = {0, 0, 0, 0, 0, 0};
-      if (p == last && (tape & 3) == CLS_FINISHED) {
-        fin_here = true;
+      if (fin_here) {
         // the finished row as k_inplace_gather would store it, recomputed from the tape
         // (k_backward_chain: the same terms in the same order)
-        double fin_row[6], s0[3], e0[3], h0[3];
-        load_ray3(rin, sin, i0, s0, e0);
-        hit_point(s0, e0, a.rec_t[off + i0], h0);
+        double fin_row[6], h0[3];
+        hit_point(s0, e0, t_rec, h0);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
           fin_row[k] = s0[k];
           fin_row[3 + k] = static_cast<double>(static_cast<T>(h0[k]));
         }
+        // (a run-time loop: unrolled, its 36 tests of a column's row against a constant leave
+        // the loop and take 72 scalar registers with them)
+#pragma nounroll
         for (int c = 0; c < a.gf.n; ++c) {
           const int row = a.gf.row[c];
-          double out_c = 0.0;
+          double out_c = 0.0, goal_c = 0.0;
 #pragma unroll
-          for (int k = 0; k < 6; ++k)   // (no dynamic register index)
+          for (int k = 0; k < 6; ++k) {   // (no dynamic register index)
             if (k == row) out_c = fin_row[k];
-          const double r = out_c -
-                           a.goal[(int64_t)c * a.goal_stride + (int64_t)i0 * a.goal_ray_stride];
+            if (k == c) goal_c = goal_w[k];
+          }
+          const double r = out_c - goal_c;
           const double g = 2.0 * r;
 #pragma unroll
           for (int q = 0; q < 6; ++q)   // (no dynamic register index)
@@ -3842,11 +3935,8 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
         }
       }
       double gs[3], ge[3];
-      tri = backward_core<T, false>(i0, tape, i0, rin, sin, nullptr, a.rec_tri + off, a.rec_t + off,
-                                    nullptr, sc, a.L, 0.0, p < P - 1, child, seed, nullptr, 0,
-                                    nullptr, 0, nullptr, 0, nullptr, 0, gs, ge, gP,
-                                    max(rec.y, -1),   // (a record is a face or -1: no re-read)
-                                    a.feta, true);
+      tri = backward_core_loaded(tape, face, child_pass, s0, e0, Pf, t_rec, n_in, n_out,
+                                 mask_i != 0, a.L, child, seed, gs, ge, gP);
       for (int k = 0; k < 3; ++k) {
         child[k] = gs[k];
         child[3 + k] = ge[k];

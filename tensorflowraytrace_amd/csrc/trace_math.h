@@ -292,7 +292,10 @@ TFRT_HD void adjoint3d(const double s[3], const double e[3], const double P[9], 
 
   double hb[3] = {g_h[0], g_h[1], g_h[2]};
   double sb[3] = {g_s[0], g_s[1], g_s[2]};
-  for (int i = 0; i < 9; ++i) gP[i] = 0.0;
+  // gradient w.r.t. C that comes back through the child's normal (zero without a child): the
+  // reverse of C = E1 x E2 is linear in it, so it joins the hit parameter's below and the pair
+  // of cross products runs once
+  double Cn[3] = {0.0, 0.0, 0.0};
 
   if (has_child) {
     // Forward quantities recomputed for the reverse step.  They need not reproduce the forward
@@ -378,17 +381,7 @@ TFRT_HD void adjoint3d(const double s[3], const double e[3], const double P[9], 
     }
     // n = l2_normalize(N), N = C/|C|  ->  dC = (nb - n (n.nb)) / |C|   (|N| = 1)
     const double nn = dot3(n, nb);
-    double Cb[3];
-    for (int i = 0; i < 3; ++i) Cb[i] = (nb[i] - n[i] * nn) * inv_c;
-    // C = E1 x E2
-    double E1b[3], E2b[3];
-    cross3(E2, Cb, E1b);
-    cross3(Cb, E1, E2b);
-    for (int i = 0; i < 3; ++i) {
-      gP[3 + i] += E1b[i];
-      gP[6 + i] += E2b[i];
-      gP[i] -= E1b[i] + E2b[i];
-    }
+    for (int i = 0; i < 3; ++i) Cn[i] = (nb[i] - n[i] * nn) * inv_c;
   }
 
   // h = s + t d
@@ -405,18 +398,18 @@ TFRT_HD void adjoint3d(const double s[3], const double e[3], const double P[9], 
   const double denb = -numb * t;
   double Cb[3];
   for (int i = 0; i < 3; ++i) {
-    gP[i] += numb * C[i];
     sb[i] -= numb * C[i];
-    Cb[i] = numb * (P[i] - s[i]) + denb * d[i];
+    Cb[i] = Cn[i] + (numb * (P[i] - s[i]) + denb * d[i]);
     db[i] += denb * C[i];
   }
+  // C = E1 x E2
   double E1b[3], E2b[3];
   cross3(E2, Cb, E1b);
   cross3(Cb, E1, E2b);
   for (int i = 0; i < 3; ++i) {
-    gP[3 + i] += E1b[i];
-    gP[6 + i] += E2b[i];
-    gP[i] -= E1b[i] + E2b[i];
+    gP[3 + i] = E1b[i];
+    gP[6 + i] = E2b[i];
+    gP[i] = numb * C[i] - (E1b[i] + E2b[i]);
     ge[i] = db[i];
     gs[i] = sb[i] - db[i];
   }

@@ -3116,7 +3116,51 @@ __device__ __forceinline__ double dpp_f64(const double v) {
 // are served one after the other -- with a single copy a third of this kernel's time -- and
 // neighbouring lanes are the ones that share a face.  Eight copies for up to 8 faces, four for
 // up to 16, two for up to 32: sparse rays share a face with few lanes anyway)
+// Layout: the copies outermost -- copy c of cell k = slot * 9 + term at wacc[c * stride + k],
+// stride = wsum_stride(copies).  A lane then folds ITS cell's copies in registers: neighbouring
+// lanes read neighbouring doubles at a constant stride, nothing crosses lanes, and up to seven
+// faces take one step.  (The strides are the tier's cells padded to 2 mod 4 doubles: the copies
+// of one cell, which the lanes of an eight take together, lie in different LDS banks.)
+// -DTFRT_SWEEP_COPY_MAJOR=0 builds the earlier layout, copies innermost and folded across lanes
+// with DPP (tuning builds: scratch/build_variants.py).
+#ifndef TFRT_SWEEP_COPY_MAJOR
+#define TFRT_SWEEP_COPY_MAJOR 1
+#endif
+#if TFRT_SWEEP_COPY_MAJOR
+constexpr int WSUM_SLOTS = 32, WSUM_CELLS = 592;
+__device__ __forceinline__ constexpr int wsum_stride(int copies) {
+  return WSUM_SLOTS * 9 * 2 / copies + 2;   // 8: 74, 4: 146, 2: 290
+}
+static_assert(8 * wsum_stride(8) <= WSUM_CELLS && 4 * wsum_stride(4) <= WSUM_CELLS &&
+              2 * wsum_stride(2) <= WSUM_CELLS, "wacc holds every tier");
+
+// wacc is all zero between two calls of wave_face_sums: the kernel clears it once ...
+__device__ __forceinline__ void wsum_clear(double* wacc) {
+  for (int k = 2 * (threadIdx.x & 63); k < WSUM_CELLS; k += 128)
+    *reinterpret_cast<double2*>(wacc + k) = make_double2(0.0, 0.0);
+  wave_fence();
+}
+// ... and the fold leaves zeros where it read.  One lane per (face, term): the copies of its
+// cell summed in registers, then ONE atomic to memory.
+template <int COPIES>
+__device__ __forceinline__ void wsum_fold(double* wacc, const int32_t* wface, int K, int lane,
+                                          double* __restrict__ g_fverts) {
+  for (int k = lane; k < K; k += 64) {
+    double* w = wacc + k;
+    double v = w[0];
+#pragma unroll
+    for (int c = 1; c < COPIES; ++c) v += w[c * wsum_stride(COPIES)];
+#pragma unroll
+    for (int c = 0; c < COPIES; ++c) w[c * wsum_stride(COPIES)] = 0.0;
+    if (v != 0.0) {
+      const int f = k / 9;
+      unsafeAtomicAdd(g_fverts + 9 * (int64_t)wface[f] + (k - 9 * f), v);
+    }
+  }
+}
+#else
 constexpr int WSUM_SLOTS = 32, WSUM_CELLS = 576;
+#endif
 __device__ __forceinline__ void wave_face_sums(int tri, const double gP[9], double* wacc,
                                                int32_t* wface, double* __restrict__ g_fverts) {
   const int lane = threadIdx.x & 63;
@@ -3132,6 +3176,27 @@ __device__ __forceinline__ void wave_face_sums(int tri, const double gP[9], doub
     ++ns;
     todo &= ~__ballot(mine);
   }
+#if TFRT_SWEEP_COPY_MAJOR
+  const int copies = ns <= 8 ? 8 : (ns <= 16 ? 4 : 2);
+  if (tri >= 0) {
+    if (slot >= 0) {
+      double* w = &wacc[(lane & (copies - 1)) * wsum_stride(copies) + slot * 9];
+#pragma unroll
+      for (int c = 0; c < 9; ++c)
+        if (gP[c] != 0.0) unsafeAtomicAdd(w + c, gP[c]);
+    } else {  // (more distinct faces than slots: rays that are not coherent after all)
+      double* gp = g_fverts + 9 * (int64_t)tri;
+#pragma unroll
+      for (int c = 0; c < 9; ++c)
+        if (gP[c] != 0.0) unsafeAtomicAdd(gp + c, gP[c]);
+    }
+  }
+  wave_fence();
+  if (copies == 8) wsum_fold<8>(wacc, wface, ns * 9, lane, g_fverts);
+  else if (copies == 4) wsum_fold<4>(wacc, wface, ns * 9, lane, g_fverts);
+  else wsum_fold<2>(wacc, wface, ns * 9, lane, g_fverts);
+  wave_fence();  // (the next use of wacc / wface must not overtake these reads and zeros)
+#else
   const int copies = ns <= 8 ? 8 : (ns <= 16 ? 4 : 2);
   const int cells = ns * 9 * copies;
   for (int k = lane; k < cells; k += 64) wacc[k] = 0.0;
@@ -3164,6 +3229,7 @@ __device__ __forceinline__ void wave_face_sums(int tri, const double gP[9], doub
     }
   }
   wave_fence();  // (the next use of wacc / wface must not overtake these reads)
+#endif
 }
 
 // BW wavefronts per workgroup (the wavefronts share nothing: see k_intersect_beam)
@@ -3187,9 +3253,12 @@ __global__ __launch_bounds__(64 * BW) void k_backward3d(
   const int i = q0;
   if (wave_sums) {
     if ((q0 & ~63) >= n) return;  // (whole wave; the sums: wave_face_sums)
-    __shared__ double wacc[BW][WSUM_CELLS];  // [slot][term][copy]
+    __shared__ __align__(16) double wacc[BW][WSUM_CELLS];  // (layout: wave_face_sums)
     __shared__ int32_t wface[BW][WSUM_SLOTS];
     const int wave = threadIdx.x >> 6;
+#if TFRT_SWEEP_COPY_MAJOR
+    wsum_clear(wacc[wave]);
+#endif
     double gP[9];
     int tri = -1;
     if (i < n)
@@ -3492,10 +3561,24 @@ __device__ __forceinline__ int backward_core(
 // the same arithmetic in the same order, no access to memory.  Of backward_core's cases only
 // those of that path are here: no class gradient but the finished row's `seed`, per-face indices
 // (n_in = n_out = 1 unless the slot has a child), no gradient with respect to them.
-// face_wanted: the face's byte of tfrt_scene3d.face_grad_mask is set, or there is no mask.
+// face_wanted: the face's byte of tfrt_scene3d.face_grad_mask is set, or there is no mask; the
+// adjoint forms no face terms for a face nobody differentiates.
+// (n_a, n_b): the face's two index ratios as the set-up launch stored them (feta[4f], feta[4f + 1]
+// = snell_ratios) -- the adjoint picks one where it used to divide n_in and n_out again.
+// -DTFRT_SWEEP_SKIP_FROZEN=0 / -DTFRT_SWEEP_ETA_TABLE=0 build the earlier forms (all face terms
+// computed and dropped; (n_a, n_b) = (n_in, n_out) and divided): tuning builds.
+#ifndef TFRT_SWEEP_SKIP_FROZEN
+#define TFRT_SWEEP_SKIP_FROZEN 1
+#endif
+#ifndef TFRT_SWEEP_ETA_TABLE
+#define TFRT_SWEEP_ETA_TABLE 1
+#endif
+// FIN / CHILD: false where the caller knows that no lane of the wavefront finishes in this pass /
+// has a child ray in it -- the arm is not compiled in (k_backward_chain_goal_inplace's roles).
+template <bool FIN = true, bool CHILD = true>
 __device__ __forceinline__ int backward_core_loaded(
     int tape, int tri, bool child_pass, const double s[3], const double e[3], const double P[9],
-    double t_rec, double n_in, double n_out, bool face_wanted, double L, const double child[6],
+    double t_rec, double n_a, double n_b, bool face_wanted, double L, const double child[6],
     const double seed[6], double gs[3], double ge[3], double gP[9]) {
   int face_out = -1;
   const int cls = tape & 3;
@@ -3503,12 +3586,12 @@ __device__ __forceinline__ int backward_core_loaded(
   if (cls != CLS_DEAD) {
     double g_s[3] = {0, 0, 0}, g_h[3] = {0, 0, 0}, g_ce[3] = {0, 0, 0};
     bool has_child = false;
-    if (cls == CLS_FINISHED) {
+    if (FIN && cls == CLS_FINISHED) {
       for (int k = 0; k < 3; ++k) {
         g_s[k] += seed[k];
         g_h[k] += seed[3 + k];
       }
-    } else if (cls == CLS_ACTIVE && child_pass) {
+    } else if (CHILD && cls == CLS_ACTIVE && child_pass) {
       has_child = true;
       for (int k = 0; k < 3; ++k) {
         g_h[k] += child[k];
@@ -3519,8 +3602,15 @@ __device__ __forceinline__ int backward_core_loaded(
     for (int k = 0; k < 3; ++k) nz = nz || g_s[k] != 0.0 || g_h[k] != 0.0;
     if (nz) {
       const int branch = ((tape & TAPE_INTERNAL) ? 1 : 0) | ((tape & TAPE_REFLECT) ? 2 : 0);
-      adjoint3d(s, e, P, t_rec, has_child, n_in, n_out, L, g_s, g_h, g_ce, gs, ge, gP, nullptr,
-                branch, false);
+      const bool face_terms = TFRT_SWEEP_SKIP_FROZEN ? face_wanted : true;
+#if TFRT_SWEEP_ETA_TABLE
+      const double ratios[2] = {n_a, n_b};
+      adjoint3d(s, e, P, t_rec, has_child, 1.0, 1.0, L, g_s, g_h, g_ce, gs, ge, gP, nullptr,
+                branch, false, face_terms, ratios);
+#else
+      adjoint3d(s, e, P, t_rec, has_child, n_a, n_b, L, g_s, g_h, g_ce, gs, ge, gP, nullptr,
+                branch, false, face_terms);
+#endif
       if (face_wanted) face_out = tri;
     }
   }
@@ -3636,12 +3726,15 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
     }
     return;
   }
-  __shared__ double wacc[BW][WSUM_CELLS];
+  __shared__ __align__(16) double wacc[BW][WSUM_CELLS];
   __shared__ int32_t wface[BW][WSUM_SLOTS];
   extern __shared__ int4 chain_lds[];   // [wave][pass][lane]: slot, tape byte, output slot, face
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int P = a.P;
   int4* chain = chain_lds + (size_t)wave * P * 64;
+#if TFRT_SWEEP_COPY_MAJOR
+  wsum_clear(wacc[wave]);
+#endif
   // forward: the slots of this ray's chain and the pass it ends in; what the walk back needs of
   // every slot's record is read here, three independent loads per pass
   int last = -1;
@@ -3790,7 +3883,200 @@ struct ChainGoalArgs {
   const uint8_t* face_grad_mask;
   const int32_t* sched;    // tfrt_scene3d.wave_schedule or null: workgroup b takes wavefront sched[b]
   int32_t ngroups;
+  // the goal's columns as the pass reads them (chain_goal_columns)
+  int32_t goal_col[6];     // the column whose value a finished lane loads into register j, or -1
+  uint32_t rows_packed;    // gf.row[c] in bits 4c .. 4c + 2
+  int32_t rows_ascending;  // gf.row strictly ascending: register j is ROW j's (its column or none)
 };
+
+// -DTFRT_SWEEP_ROLES=0: one pass body for every wavefront, per-lane 64-bit addresses;
+// -DTFRT_SWEEP_GOAL_ROWS=0: the run-time loop over the goal's columns for every order of rows
+// (tuning builds: scratch/build_variants.py)
+#ifndef TFRT_SWEEP_ROLES
+#define TFRT_SWEEP_ROLES 1
+#endif
+#ifndef TFRT_SWEEP_GOAL_ROWS
+#define TFRT_SWEEP_GOAL_ROWS 1
+#endif
+
+// Strictly ascending rows (("y_end", "z_end"): the usual goal) need no run-time loop: register j
+// of the pass holds row j's goal value and an unrolled loop over the six rows, scalar branches on
+// "this row has a column", takes the residuals in ascending row order -- the column order, so the
+// error sum keeps its bits.  Any other order (a field twice included) keeps the loop over the
+// columns, with register c column c's value and the rows in one scalar.
+template <typename T>
+static void chain_goal_columns(ChainGoalArgs<T>& g) {
+  bool asc = TFRT_SWEEP_GOAL_ROWS != 0;
+  for (int c = 1; c < g.gf.n; ++c) asc = asc && g.gf.row[c] > g.gf.row[c - 1];
+  g.rows_ascending = asc ? 1 : 0;
+  g.rows_packed = 0;
+  for (int j = 0; j < 6; ++j) g.goal_col[j] = (!asc && j < g.gf.n) ? j : -1;
+  for (int c = 0; c < g.gf.n; ++c) {
+    g.rows_packed |= (uint32_t)(g.gf.row[c] & 7) << (4 * c);
+    if (asc) g.goal_col[g.gf.row[c]] = c;
+  }
+}
+
+// base[i] for a wave-uniform base and a lane's small index: the address is a scalar register pair
+// plus one 32-bit byte offset per lane (global_load's saddr form), no 64-bit vector arithmetic
+// (the base through an empty statement that pins it to scalar registers: left to itself the
+// compiler folds the lane's offset into the first row's address and derives the others from that
+// 64-bit vector; the statement also keeps the bases of all passes from waiting outside the loop.
+// The address comes back from an integer, so it is said to be global memory's: a generic pointer
+// would load with flat instructions.)
+template <typename U>
+__device__ __forceinline__ U ld_scalar_base(const U* base, unsigned long long byte_offset) {
+  unsigned long long v = reinterpret_cast<unsigned long long>(base);
+  __asm__ volatile("" : "+s"(v));
+  typedef const U __attribute__((address_space(1))) G;
+  return *reinterpret_cast<G*>(v + byte_offset);
+}
+template <typename U>
+__device__ __forceinline__ U ld_lane(const U* base, uint32_t i) {
+  return ld_scalar_base(base, (unsigned long long)(i * (uint32_t)sizeof(U)));
+}
+
+// One pass of one lane of k_backward_chain_goal_inplace (below): `child` is the gradient w.r.t.
+// the lane's ray as the later pass left it and receives this pass's.  FIN / CHILD: false where no
+// lane of the wavefront finishes in this pass / no lane has a child ray in it; then the goal's
+// loads, the finished row, the seed and the columns' loop / the child's arm, the index ratios,
+// Snell's reverse and the normal's way back do not exist.  One source for both roles.
+template <typename T, bool FIN, bool CHILD>
+__device__ __forceinline__ int chain_goal_pass(const ChainGoalArgs<T>& a, int p, int wave, int lane,
+                                               int tape, int face, bool fin_lane, double child[6],
+                                               double& err, double gP[9]) {
+  // the reference's squared_difference and reduce_sum are separate ops: no contraction
+#pragma clang fp contract(off)
+  const int cls = tape & 3;
+  const size_t off = (size_t)p * a.n;
+  const T* rin = p == 0 ? a.src : a.rays_ws + (size_t)(p - 1) * 6 * a.n;
+  const int64_t sin = p == 0 ? a.src_stride : a.n;
+  const bool child_pass = CHILD && p < a.P - 1;
+  const bool fin_here = FIN && fin_lane;
+  // Every load of the pass is asked for here, before the first of them is waited for: one
+  // round trip to memory per pass.  (Left inside the finished arm, its run-time loop over the
+  // goal's columns and backward_core, the compiler cannot move a load out of a divergent
+  // branch or a loop: ray, hit parameter, one goal column after the other, then the face --
+  // five dependent trips on the finished arm, two on the other.)  Each lane asks for what
+  // backward_core and the finished arm read for it and for nothing else; the one exception
+  // is the mask byte of a finished lane whose residuals are all exactly zero, which carries
+  // no gradient and is not known before the goal has arrived -- its own face's byte.
+  const bool on_face = face >= 0 && cls != CLS_DEAD;
+  const bool with_child = on_face && child_pass && cls == CLS_ACTIVE;
+  T ray_w[6];
+  double t_rec = 0.0;
+  double goal_w[6] = {0, 0, 0, 0, 0, 0};
+#if TFRT_SWEEP_ROLES
+  // (the lane through an empty statement the compiler cannot see past: what is made of it is
+  // made in the pass that uses it and does not wait in vector registers through the whole walk,
+  // which the adjoint needs.)  The wavefront's rows start at scalar addresses.
+  uint32_t lv = lane;
+  __asm__ volatile("" : "+v"(lv));
+  const size_t w0 = (size_t)wave * 64;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) ray_w[k] = ld_lane(rin + k * sin + w0, lv);
+  if (fin_here || on_face) t_rec = ld_lane(a.rec_t + off + w0, lv);
+  if (FIN) {
+    const int64_t gl = (int64_t)lv * a.goal_ray_stride;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      int cj = a.goal_col[j];
+      __asm__ volatile("" : "+s"(cj));   // (a scalar branch per register, decided in the pass)
+      if (cj >= 0) {
+        const double* gb = a.goal + (int64_t)cj * a.goal_stride + (int64_t)w0 * a.goal_ray_stride;
+        if (fin_here) goal_w[j] = ld_scalar_base(gb, (unsigned long long)gl * sizeof(double));
+      }
+    }
+  }
+#else
+  // (the lane's ray index through an empty statement the compiler cannot see past: the
+  // per-lane addresses below are then formed in the pass that uses them -- moved out of the
+  // loop they stay in 16 vector registers for the whole walk, which the adjoint needs)
+  int iv = wave * 64 + lane;
+  __asm__ volatile("" : "+v"(iv));
+#pragma unroll
+  for (int k = 0; k < 6; ++k) ray_w[k] = rin[k * sin + iv];
+  if (fin_here || on_face) t_rec = a.rec_t[off + iv];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    const int cj = a.goal_col[j];
+    if (FIN && cj >= 0 && fin_here)
+      goal_w[j] = a.goal[(int64_t)cj * a.goal_stride + (int64_t)iv * a.goal_ray_stride];
+  }
+#endif
+  double Pf[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, n_a = 1.0, n_b = 1.0;   // (backward_core_loaded)
+  uint8_t mask_w = 1;
+  if (on_face) {
+    const double* fp = a.face_verts + 9 * (int64_t)face;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) Pf[q] = fp[q];
+    if (a.face_grad_mask != nullptr && (with_child || (FIN && cls == CLS_FINISHED)))
+      mask_w = a.face_grad_mask[face];
+  }
+  if (with_child) {
+    n_a = a.feta[4 * (int64_t)face + (TFRT_SWEEP_ETA_TABLE ? 0 : 2)];
+    n_b = a.feta[4 * (int64_t)face + (TFRT_SWEEP_ETA_TABLE ? 1 : 3)];
+  }
+  double s0[3], e0[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    s0[k] = static_cast<double>(ray_w[k]);
+    e0[k] = static_cast<double>(ray_w[3 + k]);
+  }
+  // (the byte as loaded, opaque until here: tested where it is asked for, the test and its
+  // wait for everything in flight would sit in front of the loads that follow it)
+  int mask_i = mask_w;
+  __asm__ volatile("" : "+v"(mask_i));
+  double seed[6] = {0, 0, 0, 0, 0, 0};
+  if (fin_here) {
+    // the finished row as k_inplace_gather would store it, recomputed from the tape
+    // (k_backward_chain: the same terms in the same order)
+    double fin_row[6], h0[3];
+    hit_point(s0, e0, t_rec, h0);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      fin_row[k] = s0[k];
+      fin_row[3 + k] = static_cast<double>(static_cast<T>(h0[k]));
+    }
+    if (a.rows_ascending) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        if (a.goal_col[k] >= 0) {   // (scalar)
+          const double r = fin_row[k] - goal_w[k];
+          seed[k] = 2.0 * r;
+          err += r * r;
+        }
+      }
+    } else {
+      // (a run-time loop: unrolled, its 36 tests of a column's row against a constant leave
+      // the loop and take 72 scalar registers with them)
+#pragma nounroll
+      for (int c = 0; c < a.gf.n; ++c) {
+        const int row = (a.rows_packed >> (4 * c)) & 7;
+        double out_c = 0.0, goal_c = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {   // (no dynamic register index)
+          if (k == row) out_c = fin_row[k];
+          if (k == c) goal_c = goal_w[k];
+        }
+        const double r = out_c - goal_c;
+        const double g = 2.0 * r;
+#pragma unroll
+        for (int q = 0; q < 6; ++q)   // (no dynamic register index)
+          if (q == row) seed[q] = g;
+        err += r * r;
+      }
+    }
+  }
+  double gs[3], ge[3];
+  const int tri = backward_core_loaded<FIN, CHILD>(tape, face, child_pass, s0, e0, Pf, t_rec, n_a,
+                                                   n_b, mask_i != 0, a.L, child, seed, gs, ge, gP);
+  for (int k = 0; k < 3; ++k) {
+    child[k] = gs[k];
+    child[3 + k] = ge[k];
+  }
+  return tri;
+}
 
 template <typename T>
 __global__ __launch_bounds__(64)
@@ -3816,10 +4102,13 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
     return;
   }
   __builtin_assume(a.feta != nullptr);
-  __shared__ double wacc[WSUM_CELLS];
+  __shared__ __align__(16) double wacc[WSUM_CELLS];
   __shared__ int32_t wface[WSUM_SLOTS];
   extern __shared__ int2 chain_goal_lds[];   // [pass][lane]: tape byte, face
   int2* chain = chain_goal_lds;
+#if TFRT_SWEEP_COPY_MAJOR
+  wsum_clear(wacc);
+#endif
   const int P = a.P;
   int last = -1;
   if (i0 < n0) {
@@ -3844,106 +4133,30 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
   for (int p = top; p >= 0; --p) {
     double gP[9];
     int tri = -1;
-    bool fin_here = false;
-    if (p <= last) {
+    const bool here = p <= last;
+    int tape = CLS_DEAD, face = -1;
+    if (here) {
       const int2 rec = chain[p * 64 + lane];
-      const int tape = rec.x, cls = tape & 3;
-      const int face = max(rec.y, -1);   // (a record is a face or -1)
-      const size_t off = (size_t)p * a.n;
-      const T* rin = p == 0 ? a.src : a.rays_ws + (size_t)(p - 1) * 6 * a.n;
-      const int64_t sin = p == 0 ? a.src_stride : a.n;
-      const bool child_pass = p < P - 1;
-      fin_here = p == last && cls == CLS_FINISHED;
-      // Every load of the pass is asked for here, before the first of them is waited for: one
-      // round trip to memory per pass.  (Left inside the finished arm, its run-time loop over the
-      // goal's columns and backward_core, the compiler cannot move a load out of a divergent
-      // branch or a loop: ray, hit parameter, one goal column after the other, then the face --
-      // five dependent trips on the finished arm, two on the other.)  Each lane asks for what
-      // backward_core and the finished arm read for it and for nothing else; the one exception
-      // is the mask byte of a finished lane whose residuals are all exactly zero, which carries
-      // no gradient and is not known before the goal has arrived -- its own face's byte.
-      const bool on_face = face >= 0 && cls != CLS_DEAD;
-      const bool with_child = on_face && child_pass && cls == CLS_ACTIVE;
-      // (the lane's ray index through an empty statement the compiler cannot see past: the
-      // per-lane addresses below are then formed in the pass that uses them -- moved out of the
-      // loop they stay in 16 vector registers for the whole walk, which the adjoint needs)
-      int iv = i0;
-      __asm__ volatile("" : "+v"(iv));
-      T ray_w[6];
-#pragma unroll
-      for (int k = 0; k < 6; ++k) ray_w[k] = rin[k * sin + iv];
-      double t_rec = 0.0;
-      if (fin_here || on_face) t_rec = a.rec_t[off + iv];
-      double goal_w[6];
-#pragma unroll
-      for (int c = 0; c < 6; ++c) {
-        goal_w[c] = 0.0;
-        if (fin_here && c < a.gf.n)
-          goal_w[c] = a.goal[(int64_t)c * a.goal_stride + (int64_t)iv * a.goal_ray_stride];
-      }
-      double Pf[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, n_in = 1.0, n_out = 1.0;
-      uint8_t mask_w = 1;
-      if (on_face) {
-        const double* fp = a.face_verts + 9 * (int64_t)face;
-#pragma unroll
-        for (int q = 0; q < 9; ++q) Pf[q] = fp[q];
-        if (a.face_grad_mask != nullptr && (with_child || cls == CLS_FINISHED))
-          mask_w = a.face_grad_mask[face];
-      }
-      if (with_child) {
-        n_in = a.feta[4 * (int64_t)face + 2];
-        n_out = a.feta[4 * (int64_t)face + 3];
-      }
-      double s0[3], e0[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        s0[k] = static_cast<double>(ray_w[k]);
-        e0[k] = static_cast<double>(ray_w[3 + k]);
-      }
-      // (the byte as loaded, opaque until here: tested where it is asked for, the test and its
-      // wait for everything in flight would sit in front of the loads that follow it)
-      int mask_i = mask_w;
-      __asm__ volatile("" : "+v"(mask_i));
-      double seed[6] = {0, 0, 0, 0, 0, 0};
-      if (fin_here) {
-        // the finished row as k_inplace_gather would store it, recomputed from the tape
-        // (k_backward_chain: the same terms in the same order)
-        double fin_row[6], h0[3];
-        hit_point(s0, e0, t_rec, h0);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          fin_row[k] = s0[k];
-          fin_row[3 + k] = static_cast<double>(static_cast<T>(h0[k]));
-        }
-        // (a run-time loop: unrolled, its 36 tests of a column's row against a constant leave
-        // the loop and take 72 scalar registers with them)
-#pragma nounroll
-        for (int c = 0; c < a.gf.n; ++c) {
-          const int row = a.gf.row[c];
-          double out_c = 0.0, goal_c = 0.0;
-#pragma unroll
-          for (int k = 0; k < 6; ++k) {   // (no dynamic register index)
-            if (k == row) out_c = fin_row[k];
-            if (k == c) goal_c = goal_w[k];
-          }
-          const double r = out_c - goal_c;
-          const double g = 2.0 * r;
-#pragma unroll
-          for (int q = 0; q < 6; ++q)   // (no dynamic register index)
-            if (q == row) seed[q] = g;
-          err += r * r;
-        }
-      }
-      double gs[3], ge[3];
-      tri = backward_core_loaded(tape, face, child_pass, s0, e0, Pf, t_rec, n_in, n_out,
-                                 mask_i != 0, a.L, child, seed, gs, ge, gP);
-      for (int k = 0; k < 3; ++k) {
-        child[k] = gs[k];
-        child[3 + k] = ge[k];
-      }
+      tape = rec.x;
+      face = max(rec.y, -1);   // (a record is a face or -1)
     }
-    n_fin += __popcll(__ballot(fin_here));
-    n_entered += __popcll(__ballot(p <= last));
+    const bool fin_here = here && p == last && (tape & 3) == CLS_FINISHED;
+    const unsigned long long fin_m = __ballot(fin_here);
+#if TFRT_SWEEP_ROLES
+    // The wavefronts of a coherent trace are nearly all of one role in a pass: nobody finishes
+    // here, or everybody who is here finishes and nobody has a child -- one of the two bodies
+    // runs (chain_goal_pass).  A mixed wavefront runs both, each with its own lanes.
+    const bool fin_role = here && fin_m != 0ull && !(p < P - 1 && (tape & 3) == CLS_ACTIVE);
+    if (fin_role)
+      tri = chain_goal_pass<T, true, false>(a, p, wave, lane, tape, face, fin_here, child, err, gP);
+    if (here && !fin_role)
+      tri = chain_goal_pass<T, false, true>(a, p, wave, lane, tape, face, false, child, err, gP);
+#else
+    if (here)
+      tri = chain_goal_pass<T, true, true>(a, p, wave, lane, tape, face, fin_here, child, err, gP);
+#endif
+    n_fin += __popcll(fin_m);
+    n_entered += __popcll(__ballot(here));
     wave_face_sums(tri, gP, wacc, wface, a.g_fverts);
   }
   if (a.g_src != nullptr && i0 < n0) {
@@ -4718,6 +4931,7 @@ static int trace3d_backward_t(const SweepCall3& c) {
         g.face_grad_mask = sc->face_grad_mask;
         g.sched = sc->wave_schedule;
         g.ngroups = cdiv(N, 64);
+        chain_goal_columns(g);
         hipLaunchKernelGGL((k_backward_chain_goal_inplace<T>), dim3(cdiv(N, 64)), dim3(64),
                            (size_t)P * 64 * sizeof(int2), st, g);
       } else if (N > 0 && sc->grad_n_in != nullptr)

@@ -255,6 +255,30 @@ TFRT_HD double adj_rsqrt(double x) {
 #endif
 }
 
+// Dot and cross products for the REVERSE sweep only, under the same licence: on the device fused
+// multiply-adds (3 and 6 instructions instead of the 5 and 9 of dot3 / cross3, whose separately
+// rounded products the forward's decisions need), on the host dot3 / cross3 themselves.
+// -DTFRT_ADJ_CONTRACT=0 builds the device code on dot3 / cross3 too (tuning builds).
+#ifndef TFRT_ADJ_CONTRACT
+#define TFRT_ADJ_CONTRACT 1
+#endif
+TFRT_HD double adj_dot3(const double a[3], const double b[3]) {
+#if defined(__HIP_DEVICE_COMPILE__) && TFRT_ADJ_CONTRACT
+  return __builtin_fma(a[2], b[2], __builtin_fma(a[1], b[1], a[0] * b[0]));
+#else
+  return dot3(a, b);
+#endif
+}
+TFRT_HD void adj_cross3(const double a[3], const double b[3], double o[3]) {
+#if defined(__HIP_DEVICE_COMPILE__) && TFRT_ADJ_CONTRACT
+  o[0] = __builtin_fma(a[1], b[2], -(a[2] * b[1]));
+  o[1] = __builtin_fma(a[2], b[0], -(a[0] * b[2]));
+  o[2] = __builtin_fma(a[0], b[1], -(a[1] * b[0]));
+#else
+  cross3(a, b, o);
+#endif
+}
+
 // ------------------------------------------------------------------------------------------
 // Reverse-mode of one ray through one pass.
 //
@@ -271,11 +295,19 @@ TFRT_HD double adj_rsqrt(double x) {
 //          gn[2] (optional: wrt n_in, n_out of the reaction -- "value" mode reads them as ordinary
 //          tensors, operation.py:268-272; zero for a mirror / total internal reflection, whose
 //          direction does not depend on the ratio, geometry.py:735-747).
+// face_terms = false: nobody reads the face's gradient (a frozen surface): gP is left untouched
+//          and what only it needs is skipped -- the normal's way back to C, the gradient w.r.t. C
+//          and the two cross products; gs and ge are the same bits either way.
+// ratios:  snell_ratios(n_in, n_out) where the caller holds them already (the per-face table of
+//          the trace's set-up launch): the index ratio is then picked, not divided -- the same
+//          operands and safe-value rules, hence the same bits.  Needs the forward's branches
+//          (branch >= 0) and no gn: n_in and n_out are not read then.
 TFRT_HD void adjoint3d(const double s[3], const double e[3], const double P[9], double ray_u,
                        bool has_child, double n_in, double n_out, double L,
                        const double g_s[3], const double g_h[3], const double g_ce[3],
                        double gs[3], double ge[3], double gP[9], double* gn = nullptr,
-                       int branch = -1, bool gn_wanted = true) {
+                       int branch = -1, bool gn_wanted = true, bool face_terms = true,
+                       const double* ratios = nullptr) {
   // branch: -1 = re-derive the forward's branches here; else bit 0 = the ray met the face from
   // the inside (n.u > 0), bit 1 = it was reflected (mirror or total internal reflection), as the
   // forward pass decided them
@@ -286,7 +318,7 @@ TFRT_HD void adjoint3d(const double s[3], const double e[3], const double P[9], 
   const double E1[3] = {P[3] - P[0], P[4] - P[1], P[5] - P[2]};
   const double E2[3] = {P[6] - P[0], P[7] - P[1], P[8] - P[2]};
   double C[3];
-  cross3(E1, E2, C);
+  adj_cross3(E1, E2, C);
   const double t = ray_u;
   double h[3] = {s[0] + t * d[0], s[1] + t * d[1], s[2] + t * d[2]};
 
@@ -304,18 +336,20 @@ TFRT_HD void adjoint3d(const double s[3], const double e[3], const double P[9], 
     // the forward's second normalisation of an already-unit vector, and only the index ratio
     // that is used is formed: 5 float64 divisions and 3 square roots instead of 14 and 5
     // (a float64 division is ~30 instructions; the kernel is bound by float64 VALU issue).
-    const double inv_c = adj_rsqrt(dot3(C, C));
+    const double inv_c = adj_rsqrt(adj_dot3(C, C));
     const double n[3] = {C[0] * inv_c, C[1] * inv_c, C[2] * inv_c};
     const double r[3] = {h[0] - s[0], h[1] - s[1], h[2] - s[2]};
-    const double rsq = dot3(r, r);
+    const double rsq = adj_dot3(r, r);
     const bool clamped = rsq < 1e-12;               // l2_normalize's max(sum x^2, 1e-12)
     const double inv_r = clamped ? 1e6 : adj_rsqrt(rsq);
     const double u[3] = {r[0] * inv_r, r[1] * inv_r, r[2] * inv_r};
-    const double nu = dot3(n, u);
+    const double nu = adj_dot3(n, u);
     const bool in_safe = n_in != 0.0, out_safe = n_out != 0.0;
     const double nis = in_safe ? n_in : 1.0, nos = out_safe ? n_out : 1.0;
     const bool internal = branch >= 0 ? (branch & 1) != 0 : nu > 0.0;
-    const double eta = internal ? (out_safe ? nis / nos : 0.0) : (in_safe ? nos / nis : 0.0);
+    const double eta = ratios != nullptr
+                           ? (internal ? ratios[0] : ratios[1])
+                           : (internal ? (out_safe ? nis / nos : 0.0) : (in_safe ? nos / nis : 0.0));
     const double nu_eta = eta * nu;
     double k = 1.0 - eta * eta + nu_eta * nu_eta;
     const bool reflect = branch >= 0 ? (branch & 2) != 0 : ((k < 0.0) || (n_in == 0.0));
@@ -329,7 +363,7 @@ TFRT_HD void adjoint3d(const double s[3], const double e[3], const double P[9], 
     }
     double nub;
     if (reflect) {
-      nub = -2.0 * dot3(wb, n);
+      nub = -2.0 * adj_dot3(wb, n);
       for (int i = 0; i < 3; ++i) {
         ub[i] = wb[i];
         nb[i] = -2.0 * nu * wb[i];
@@ -341,11 +375,11 @@ TFRT_HD void adjoint3d(const double s[3], const double e[3], const double P[9], 
       const double irk = k > 0.0 ? adj_rsqrt(k) : INFINITY;
       const double rk = k > 0.0 ? k * irk : 0.0;
       const double alpha = sg * rk - nu_eta;
-      const double ab = dot3(wb, n);
+      const double ab = adj_dot3(wb, n);
       nub = ab * (sg * eta * nu_eta * irk - eta);
       if (gn != nullptr && gn_wanted) {
         // w = alpha n + eta u, alpha = sg sqrt(1 - eta^2 + eta^2 nu^2) - eta nu
-        const double etab = dot3(wb, u) + ab * (sg * eta * (nu * nu - 1.0) * irk - nu);
+        const double etab = adj_dot3(wb, u) + ab * (sg * eta * (nu * nu - 1.0) * irk - nu);
         if (internal) {            // eta = n_in / n_out
           if (out_safe) {
             gn[0] = in_safe ? etab / nos : 0.0;
@@ -367,7 +401,7 @@ TFRT_HD void adjoint3d(const double s[3], const double e[3], const double P[9], 
     }
     // u = l2_normalize(h - s)
     if (!clamped) {
-      const double uu = dot3(u, ub);
+      const double uu = adj_dot3(u, ub);
       for (int i = 0; i < 3; ++i) {
         const double rb = (ub[i] - u[i] * uu) * inv_r;
         hb[i] += rb;
@@ -380,8 +414,10 @@ TFRT_HD void adjoint3d(const double s[3], const double e[3], const double P[9], 
       }
     }
     // n = l2_normalize(N), N = C/|C|  ->  dC = (nb - n (n.nb)) / |C|   (|N| = 1)
-    const double nn = dot3(n, nb);
-    for (int i = 0; i < 3; ++i) Cn[i] = (nb[i] - n[i] * nn) * inv_c;
+    if (face_terms) {
+      const double nn = adj_dot3(n, nb);
+      for (int i = 0; i < 3; ++i) Cn[i] = (nb[i] - n[i] * nn) * inv_c;
+    }
   }
 
   // h = s + t d
@@ -393,23 +429,25 @@ TFRT_HD void adjoint3d(const double s[3], const double e[3], const double P[9], 
     db[i] = t * hb[i];
   }
   // t = num / den, num = (P0 - s).C, den = d.C
-  const double den = dot3(d, C);
+  const double den = adj_dot3(d, C);
   const double numb = tb * adj_rcp(den);
   const double denb = -numb * t;
-  double Cb[3];
+  if (face_terms) {
+    double Cb[3];
+    for (int i = 0; i < 3; ++i) Cb[i] = Cn[i] + (numb * (P[i] - s[i]) + denb * d[i]);
+    // C = E1 x E2
+    double E1b[3], E2b[3];
+    adj_cross3(E2, Cb, E1b);
+    adj_cross3(Cb, E1, E2b);
+    for (int i = 0; i < 3; ++i) {
+      gP[3 + i] = E1b[i];
+      gP[6 + i] = E2b[i];
+      gP[i] = numb * C[i] - (E1b[i] + E2b[i]);
+    }
+  }
   for (int i = 0; i < 3; ++i) {
     sb[i] -= numb * C[i];
-    Cb[i] = Cn[i] + (numb * (P[i] - s[i]) + denb * d[i]);
     db[i] += denb * C[i];
-  }
-  // C = E1 x E2
-  double E1b[3], E2b[3];
-  cross3(E2, Cb, E1b);
-  cross3(Cb, E1, E2b);
-  for (int i = 0; i < 3; ++i) {
-    gP[3 + i] = E1b[i];
-    gP[6 + i] = E2b[i];
-    gP[i] = numb * C[i] - (E1b[i] + E2b[i]);
     ge[i] = db[i];
     gs[i] = sb[i] - db[i];
   }

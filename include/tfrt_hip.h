@@ -546,8 +546,9 @@ int tfrt_goal_finish(const tfrt_goal_pending* pending, void* stream);
 
 /* DensityError: the columns that count, taken together, must land with the density `goal` on an
  * (ny x nx) grid of bins over the domain [x0, x1] x [y0, y1] -- the soft-histogram form of
- * tfrt/analyze.py:134-290 (DistributionDifferential), which bins hard and has no gradient.  Three
- * launches behind a memset of `hq`, no host read, no allocation: captured with the rest of a step.
+ * tfrt/analyze.py:134-290 (DistributionDifferential), which bins hard and has no gradient.  Four
+ * launches (clear `hq`, splat, bins, seed), no host read, no allocation: captured with the rest of
+ * a step.
  *
  * A column i counts if mask is NULL or mask[i] >= 0 (tfrt_ray_out.face of an in-place trace with
  * the finished rows at the rays' own columns) and its coordinates x = rows[row_x], y = rows[row_y]
@@ -586,6 +587,52 @@ int tfrt_density_error(const void* rows, int64_t stride, int64_t n, int32_t stat
                        double y1, double sy, double oob_weight, double* grad, int64_t grad_stride,
                        double* error_out, int64_t* hq, int32_t splat_variant, void* workspace,
                        size_t workspace_bytes, void* stream);
+
+/* tfrt_density_error with FIELD CODES in the place of rows: a field is a row of the ray block or a
+ * direction cosine of the finished ray's last link (far-field intensity: a density over the
+ * outgoing direction).  The same launches and the same workspace as tfrt_density_error; no
+ * direction block in memory -- the splat and the seed each recompute the direction from the rows
+ * they stream.
+ *
+ * `rows` is the geometry block of a `dimension`-D trace (d = dimension, 2 or 3): 2d rows, 0..d-1
+ * the start of the last link (x, y[, z]), d..2d-1 its end.  Field codes:
+ *   c < 2d           block row c
+ *   2d <= c < 3d     d_(c - 2d), the direction cosine on axis c - 2d
+ * (3-D: x_dir, y_dir, z_dir = 6, 7, 8; 2-D: x_dir, y_dir = 4, 5).  A position and a direction may
+ * be mixed (phase space); the two codes must differ.  For a column, every operation an IEEE f64
+ * operation rounded on its own, no contraction:
+ *   e_a = (double) end_a - (double) start_a                a = x, y[, z]
+ *   q   = e_x*e_x + e_y*e_y [+ e_z*e_z]                    summed left to right
+ *   L   = sqrt(q),  d_a = e_a / L
+ * With at least one direction field, a column with any non-finite geometry row, or with L not
+ * finite or not > 0, is a column whose coordinates are not finite: it does not count.  The value
+ * v_k of field k then goes through exactly the expressions of tfrt_density_error (domain test,
+ * penalty, bilinear weights, histogram, pulls), which also give gv_k = d error / d v_k, there
+ * written to the gradient rows.  Here, with a direction field:
+ *   t   = the sum over the direction fields k, in field order, of gv_k * d_(a_k)
+ *   G_b = ((gv_k of the direction field of axis b, else 0.0) - t * d_b) / L         every axis b
+ *   grad[end_b]   =  G_b   (+ gv_k of a position field that names that row, added last)
+ *   grad[start_b] = -G_b   (+ likewise)
+ * and ALL 2d rows of `grad` are written for every column, 0.0 where a column does not count.
+ * With position fields only (both codes < 2d) the rows written and every bit are
+ * tfrt_density_error's.
+ *
+ * With rows in float32 the subtraction end - start cancels: a direction is good to about
+ * eps32 * max|coordinate| / L, not to eps32.
+ *
+ *   dimension          2 or 3; rows has 2 * dimension rows of `stride`
+ *   field_x, field_y   codes in [0, 3 * dimension); field_y = -1: one field (then ny must be 1);
+ *                      field_x != field_y
+ *   grad               f64 block of 2 * dimension rows of `grad_stride`
+ * Everything else as for tfrt_density_error.
+ */
+int tfrt_density_error_fields(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                              int32_t dimension, const int32_t* mask, int32_t field_x,
+                              int32_t field_y, const double* goal, int32_t nx, int32_t ny,
+                              double x0, double x1, double sx, double y0, double y1, double sy,
+                              double oob_weight, double* grad, int64_t grad_stride,
+                              double* error_out, int64_t* hq, int32_t splat_variant,
+                              void* workspace, size_t workspace_bytes, void* stream);
 
 /* SpotError: the columns that carry the same group label must meet in one point -- the sum over
  * the rays of the squared distance to the CENTROID of their own group (the squared RMS spot size
@@ -640,6 +687,29 @@ int tfrt_spot_error(const void* rows, int64_t stride, int64_t n, int32_t state_d
                     double oob_weight, double* grad, int64_t grad_stride, double* error_out,
                     int64_t* acc, int32_t variant, void* workspace, size_t workspace_bytes,
                     void* stream);
+
+/* tfrt_spot_error with FIELD CODES in the place of rows (collimation: the rays of one group must
+ * leave parallel -- a spot in direction space; the centroids are then mean direction cosines).
+ * The fields, their codes, the column's direction (e, q, L, d), the chain rule from
+ * gv_k = d error / d v_k to the 2 * dimension rows of `grad` and the float32 caveat are those of
+ * tfrt_density_error_fields, with tfrt_spot_error's expressions for v_k -> {acc, error, gv_k}.
+ * With at least one direction field a column with a non-finite geometry row, or with L not finite
+ * or not > 0, takes the first of tfrt_spot_error's four cases ("a coordinate is non-finite": no
+ * error, gradient 0, counted in `terms`).  The same launches and the same workspace as
+ * tfrt_spot_error; with position fields only the rows written and every bit are its.
+ *
+ *   dimension          2 or 3; rows has 2 * dimension rows of `stride`
+ *   field_x, field_y   codes in [0, 3 * dimension); field_y = -1: one field; field_x != field_y
+ *   grad               f64 block of 2 * dimension rows of `grad_stride`
+ * Everything else as for tfrt_spot_error.
+ */
+int tfrt_spot_error_fields(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                           int32_t dimension, const int32_t* mask, int32_t field_x,
+                           int32_t field_y, const int32_t* group, int64_t n_source,
+                           const int32_t* perm, int32_t n_groups, double x0, double x1, double qsx,
+                           double y0, double y1, double qsy, int32_t qbits, double oob_weight,
+                           double* grad, int64_t grad_stride, double* error_out, int64_t* acc,
+                           int32_t variant, void* workspace, size_t workspace_bytes, void* stream);
 
 /* tfrt_goal_error3d_deferred and tfrt_trace3d_backward in ONE launch, for a trace over coherent
  * rays (tfrt_scene3d.coherent_rays, not deterministic, max_passes <= 8; TFRT_E_UNSUPPORTED

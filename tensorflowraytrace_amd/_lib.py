@@ -194,11 +194,20 @@ SIGNATURES = {
         c_vp, c_i64, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32,    # columns, mask, rows, goal
         c_f64, c_f64, c_f64, c_f64, c_f64, c_f64, c_f64,                      # domain, oob_weight
         c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]),
+    "tfrt_density_error_fields": (c_i32, [
+        c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32,   # + dimension
+        c_f64, c_f64, c_f64, c_f64, c_f64, c_f64, c_f64,
+        c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]),
     "tfrt_spot_error_workspace_bytes": (c_sz, [c_i64, c_i32]),
     "tfrt_spot_error": (c_i32, [
         c_vp, c_i64, c_i64, c_i32, c_vp, c_i32, c_i32,                        # columns, mask, rows
         c_vp, c_i64, c_vp, c_i32,                                             # group, perm, G
         c_f64, c_f64, c_f64, c_f64, c_f64, c_f64, c_i32, c_f64,               # domain, qbits, oob_weight
+        c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]),
+    "tfrt_spot_error_fields": (c_i32, [
+        c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_i32, c_i32,                 # + dimension
+        c_vp, c_i64, c_vp, c_i32,
+        c_f64, c_f64, c_f64, c_f64, c_f64, c_f64, c_i32, c_f64,
         c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]),
     "tfrt_trace3d_backward_goal_workspace_bytes": (c_sz, [c_i64]),
     "tfrt_trace3d_backward_goal": (c_i32, [

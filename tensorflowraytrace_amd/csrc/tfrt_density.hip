@@ -11,8 +11,13 @@
 // is associative, so the histogram does not depend on the order in which the atomics land; every
 // floating-point reduction has a fixed shape and order.  No float atomics anywhere.
 //
-// Three launches (the int64 histogram is cleared by a memset node in front of them):
+// Four launches:
 //
+//   k_density_clear   zeroes Hq.  A launch, not a memset node, as in tfrt_spot.hip: replayed inside
+//                     a step's graph behind a source that is re-drawn in the graph, the memset
+//                     node left every bin of the examples' histograms with a stale 2^46 (16,384
+//                     rays' worth) under the weights added; a kernel node in the same place clears
+//                     them.  The cause is not known; the node costs what a memset node costs.
 //   k_density_splat   one lane per column (a fixed grid for n, grid-stride): weights -> Hq, and the
 //                     out-of-domain penalty as one partial sum per workgroup.  Two variants:
 //                     <true>  bins <= DENSITY_LDS_BINS: a per-workgroup int64 histogram in LDS
@@ -26,10 +31,17 @@
 //   k_density_seed    one lane per column: both gradient rows of EVERY column (zeros where a ray
 //                     does not count) from D and the same classification as the splat.
 //
+// A field is a row of the ray block or a direction cosine of the finished ray's last link
+// (tfrt_density_error_fields; the codes, the direction and the chain rule of its gradient:
+// direction_fields.h).  The splat and the seed are templated on "has a direction field": without
+// one they are the kernels of position fields, load for load; with one they recompute the
+// direction from the rows they stream, and the seed writes EVERY row of the column.
+//
 // The penalty is summed where the rays are first classified (the splat) and finished by the one
 // workgroup that runs anyway (the bins): a sum formed by the seed would need a fourth, dependent
 // launch (~4.5 us) or a "last workgroup finishes" fence (what that costs: tfrt_error.hip).
 #include "tfrt_common.h"
+#include "direction_fields.h"
 
 namespace tfrt {
 
@@ -42,7 +54,7 @@ constexpr int BINS_WAVES = BINS_BLOCK / 64;
 
 struct DensityGrid {
   double x0, x1, sx, y0, y1, sy, oob;
-  int32_t nx, ny, row_x, row_y;
+  int32_t nx, ny, row_x, row_y;   // row_x, row_y: field codes (direction_fields.h)
 };
 
 // What one column does.  kind 0: does not count (masked, or a non-finite coordinate); 1: inside
@@ -66,10 +78,10 @@ __device__ __forceinline__ void density_axis(double v, double lo, double scale, 
   b = min(max(i0 + 1, 0), nb - 1);
 }
 
-template <typename T>
+template <typename T, int DIM>
 __device__ __forceinline__ DensityRay density_classify(const T* __restrict__ rows, int64_t stride,
                                                        const int32_t* __restrict__ mask, int64_t i,
-                                                       const DensityGrid& g) {
+                                                       const DensityGrid& g, LinkDir<DIM>& link) {
 #pragma clang fp contract(off)
   DensityRay r;
   r.kind = 0;
@@ -77,8 +89,8 @@ __device__ __forceinline__ DensityRay density_classify(const T* __restrict__ row
   r.tx = r.ty = r.dx = r.dy = 0.0;
   if (mask != nullptr && mask[i] < 0) return r;
   const bool two = g.row_y >= 0;
-  const double x = ldd(rows, (int64_t)g.row_x * stride + i);
-  const double y = two ? ldd(rows, (int64_t)g.row_y * stride + i) : 0.0;
+  double x, y;
+  read_fields<T, DIM>(rows, stride, i, g.row_x, g.row_y, x, y, link);
   if (!isfinite(x) || !isfinite(y)) return r;
   const bool out = x < g.x0 || x > g.x1 || (two && (y < g.y0 || y > g.y1));
   if (out) {
@@ -118,7 +130,14 @@ __device__ __forceinline__ double density_block_sum(double v, double* wsum) {
   return s;
 }
 
-template <typename T, bool LDS>
+// The histogram, cleared in front of the adds.
+__global__ __launch_bounds__(BLOCK) void k_density_clear(unsigned long long* __restrict__ hq,
+                                                         int bins) {
+  const int b = blockIdx.x * BLOCK + threadIdx.x;
+  if (b < bins) hq[b] = 0ull;
+}
+
+template <typename T, bool LDS, int DIM>
 __global__ __launch_bounds__(BLOCK) void k_density_splat(
     const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
     DensityGrid g, unsigned long long* __restrict__ hq, double* __restrict__ partial) {
@@ -134,7 +153,8 @@ __global__ __launch_bounds__(BLOCK) void k_density_splat(
   double pen = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * BLOCK) {
-    const DensityRay r = density_classify(rows, stride, mask, i, g);
+    LinkDir<DIM> link;
+    const DensityRay r = density_classify<T, DIM>(rows, stride, mask, i, g, link);
     if (r.kind == 2) {
       pen += g.oob * (r.tx * r.tx + r.ty * r.ty);
     } else if (r.kind == 1) {
@@ -213,7 +233,7 @@ __global__ __launch_bounds__(BINS_BLOCK) void k_density_bins(
   }
 }
 
-template <typename T>
+template <typename T, int DIM>
 __global__ __launch_bounds__(BLOCK) void k_density_seed(
     const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
     DensityGrid g, const double* __restrict__ pull, double* __restrict__ grad,
@@ -221,7 +241,8 @@ __global__ __launch_bounds__(BLOCK) void k_density_seed(
 #pragma clang fp contract(off)
   const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
   if (i >= n) return;
-  const DensityRay r = density_classify(rows, stride, mask, i, g);
+  LinkDir<DIM> link;
+  const DensityRay r = density_classify<T, DIM>(rows, stride, mask, i, g, link);
   const bool two = g.row_y >= 0;
   double gx = 0.0, gy = 0.0;
   if (r.kind == 2) {
@@ -237,8 +258,13 @@ __global__ __launch_bounds__(BLOCK) void k_density_seed(
       gx = g.sx * (pull[r.ib] - pull[r.ia]);
     }
   }
-  grad[(int64_t)g.row_x * grad_stride + i] = gx;
-  if (two) grad[(int64_t)g.row_y * grad_stride + i] = gy;
+  if constexpr (DIM != 0) {
+    // (every row of the column: a direction pulls on the start and on the end of the link)
+    chain_fields<DIM>(link, r.kind != 0, g.row_x, g.row_y, gx, gy, grad, grad_stride, i);
+  } else {
+    grad[(int64_t)g.row_x * grad_stride + i] = gx;
+    if (two) grad[(int64_t)g.row_y * grad_stride + i] = gy;
+  }
 }
 
 static int density_grid(int64_t n) {
@@ -250,6 +276,86 @@ static int density_grid(int64_t n) {
 }  // namespace tfrt
 
 using namespace tfrt;
+
+extern "C" size_t tfrt_density_error_workspace_bytes(int64_t n, int32_t nx, int32_t ny);
+
+// The launches of both entries.  `dim` and the codes have been checked by the caller.
+template <typename T, int DIM>
+static void density_launch(const T* r, int64_t stride, int64_t n, const int32_t* mask,
+                           const DensityGrid& g, bool lds, int bins, int grid, int nblk,
+                           unsigned long long* hqu, const double* goal, double* pull,
+                           double* partial, double* grad, int64_t grad_stride, double* error_out,
+                           hipStream_t st) {
+  if (grid > 0) {
+    if (lds)
+      hipLaunchKernelGGL((k_density_splat<T, true, DIM>), dim3(grid), dim3(BLOCK),
+                         (size_t)bins * sizeof(unsigned long long), st, r, stride, n, mask, g, hqu,
+                         partial);
+    else
+      hipLaunchKernelGGL((k_density_splat<T, false, DIM>), dim3(grid), dim3(BLOCK), 0, st, r,
+                         stride, n, mask, g, hqu, partial);
+  }
+  hipLaunchKernelGGL(k_density_bins, dim3(1), dim3(BINS_BLOCK), 0, st,
+                     reinterpret_cast<const long long*>(hqu), goal, bins, partial, grid, pull,
+                     error_out);
+  if (nblk > 0)
+    hipLaunchKernelGGL((k_density_seed<T, DIM>), dim3(nblk), dim3(BLOCK), 0, st, r, stride, n,
+                       mask, g, pull, grad, grad_stride);
+}
+
+// Both entries behind their own checks of the rows / codes: `dim` 2 or 3, codes below 3 * dim.
+static int density_error_run(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                             int32_t dim, const int32_t* mask, int32_t row_x, int32_t row_y,
+                             const double* goal, int32_t nx, int32_t ny, double x0, double x1,
+                             double sx, double y0, double y1, double sy, double oob_weight,
+                             double* grad, int64_t grad_stride, double* error_out, int64_t* hq,
+                             int32_t splat_variant, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+  if (n < 0 || n > INT32_MAX || nx < 1 || ny < 1 || (int64_t)nx * ny > DENSITY_MAX_BINS ||
+      row_x == row_y || !goal || !error_out || !hq || !workspace || (row_y < 0 && ny != 1) ||
+      splat_variant < 0 || splat_variant > 2)
+    return TFRT_E_BADARG;
+  if (!(x1 > x0) || !(sx > 0.0) || !isfinite(sx) || !(oob_weight >= 0.0) || !isfinite(oob_weight) ||
+      !isfinite(x0) || !isfinite(x1))
+    return TFRT_E_BADARG;
+  if (row_y >= 0 && (!(y1 > y0) || !(sy > 0.0) || !isfinite(sy) || !isfinite(y0) || !isfinite(y1)))
+    return TFRT_E_BADARG;
+  if (n > 0 && (!rows || !grad || stride < n || grad_stride < n)) return TFRT_E_BADARG;
+  if (!state_dtype_ok(state_dtype)) return TFRT_E_BADARG;
+  const int bins = nx * ny;
+  if (splat_variant == 1 && bins > DENSITY_LDS_BINS) return TFRT_E_BADARG;
+  if (workspace_bytes < tfrt_density_error_workspace_bytes(n, nx, ny)) return TFRT_E_WORKSPACE;
+  const bool lds = splat_variant == 1 || (splat_variant == 0 && bins <= DENSITY_LDS_BINS);
+  const bool dir = row_x >= 2 * dim || row_y >= 2 * dim;
+
+  DensityGrid g;
+  g.x0 = x0, g.x1 = x1, g.sx = sx, g.oob = oob_weight;
+  g.y0 = row_y >= 0 ? y0 : 0.0, g.y1 = row_y >= 0 ? y1 : 0.0, g.sy = row_y >= 0 ? sy : 0.0;
+  g.nx = nx, g.ny = ny, g.row_x = row_x, g.row_y = row_y;
+  double* pull = static_cast<double*>(workspace);
+  double* partial = reinterpret_cast<double*>(static_cast<char*>(workspace) +
+                                              align_up((size_t)bins * sizeof(double)));
+  unsigned long long* hqu = reinterpret_cast<unsigned long long*>(hq);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int grid = density_grid(n);
+  const int nblk = cdiv(n, BLOCK);
+
+  hipLaunchKernelGGL(k_density_clear, dim3(cdiv(bins, BLOCK)), dim3(BLOCK), 0, st, hqu, bins);
+  return dispatch_state(state_dtype, TFRT_E_BADARG, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const T* r = static_cast<const T*>(rows);
+    if (!dir)
+      density_launch<T, 0>(r, stride, n, mask, g, lds, bins, grid, nblk, hqu, goal, pull, partial,
+                           grad, grad_stride, error_out, st);
+    else if (dim == 3)
+      density_launch<T, 3>(r, stride, n, mask, g, lds, bins, grid, nblk, hqu, goal, pull, partial,
+                           grad, grad_stride, error_out, st);
+    else
+      density_launch<T, 2>(r, stride, n, mask, g, lds, bins, grid, nblk, hqu, goal, pull, partial,
+                           grad, grad_stride, error_out, st);
+    return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
+  });
+}
 
 extern "C" {
 
@@ -264,55 +370,25 @@ int tfrt_density_error(const void* rows, int64_t stride, int64_t n, int32_t stat
                        double y1, double sy, double oob_weight, double* grad, int64_t grad_stride,
                        double* error_out, int64_t* hq, int32_t splat_variant, void* workspace,
                        size_t workspace_bytes, void* stream) {
-  if (n < 0 || n > INT32_MAX || nx < 1 || ny < 1 || (int64_t)nx * ny > DENSITY_MAX_BINS ||
-      row_x < 0 || row_x > 5 || row_y < -1 || row_y > 5 || row_x == row_y || !goal || !error_out ||
-      !hq || !workspace || (row_y < 0 && ny != 1) || splat_variant < 0 || splat_variant > 2)
-    return TFRT_E_BADARG;
-  if (!(x1 > x0) || !(sx > 0.0) || !isfinite(sx) || !(oob_weight >= 0.0) || !isfinite(oob_weight) ||
-      !isfinite(x0) || !isfinite(x1))
-    return TFRT_E_BADARG;
-  if (row_y >= 0 && (!(y1 > y0) || !(sy > 0.0) || !isfinite(sy) || !isfinite(y0) || !isfinite(y1)))
-    return TFRT_E_BADARG;
-  if (n > 0 && (!rows || !grad || stride < n || grad_stride < n)) return TFRT_E_BADARG;
-  if (!state_dtype_ok(state_dtype)) return TFRT_E_BADARG;
-  const int bins = nx * ny;
-  if (splat_variant == 1 && bins > DENSITY_LDS_BINS) return TFRT_E_BADARG;
-  if (workspace_bytes < tfrt_density_error_workspace_bytes(n, nx, ny)) return TFRT_E_WORKSPACE;
-  const bool lds = splat_variant == 1 || (splat_variant == 0 && bins <= DENSITY_LDS_BINS);
+  if (row_x < 0 || row_x > 5 || row_y < -1 || row_y > 5) return TFRT_E_BADARG;
+  return density_error_run(rows, stride, n, state_dtype, 3, mask, row_x, row_y, goal, nx, ny, x0,
+                           x1, sx, y0, y1, sy, oob_weight, grad, grad_stride, error_out, hq,
+                           splat_variant, workspace, workspace_bytes, stream);
+}
 
-  DensityGrid g;
-  g.x0 = x0, g.x1 = x1, g.sx = sx, g.oob = oob_weight;
-  g.y0 = row_y >= 0 ? y0 : 0.0, g.y1 = row_y >= 0 ? y1 : 0.0, g.sy = row_y >= 0 ? sy : 0.0;
-  g.nx = nx, g.ny = ny, g.row_x = row_x, g.row_y = row_y;
-  double* pull = static_cast<double*>(workspace);
-  double* partial = reinterpret_cast<double*>(static_cast<char*>(workspace) +
-                                              align_up((size_t)bins * sizeof(double)));
-  unsigned long long* hqu = reinterpret_cast<unsigned long long*>(hq);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int grid = density_grid(n);
-  const int nblk = cdiv(n, BLOCK);
-
-  (void)hipMemsetAsync(hq, 0, (size_t)bins * sizeof(int64_t), st);
-  return dispatch_state(state_dtype, TFRT_E_BADARG, [&](auto tag) {
-    using T = typename decltype(tag)::type;
-    const T* r = static_cast<const T*>(rows);
-    if (grid > 0) {
-      if (lds)
-        hipLaunchKernelGGL((k_density_splat<T, true>), dim3(grid), dim3(BLOCK),
-                           (size_t)bins * sizeof(unsigned long long), st, r, stride, n, mask, g,
-                           hqu, partial);
-      else
-        hipLaunchKernelGGL((k_density_splat<T, false>), dim3(grid), dim3(BLOCK), 0, st, r, stride,
-                           n, mask, g, hqu, partial);
-    }
-    hipLaunchKernelGGL(k_density_bins, dim3(1), dim3(BINS_BLOCK), 0, st,
-                       reinterpret_cast<const long long*>(hq), goal, bins, partial, grid, pull,
-                       error_out);
-    if (nblk > 0)
-      hipLaunchKernelGGL((k_density_seed<T>), dim3(nblk), dim3(BLOCK), 0, st, r, stride, n, mask,
-                         g, pull, grad, grad_stride);
-    return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
-  });
+int tfrt_density_error_fields(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                              int32_t dimension, const int32_t* mask, int32_t field_x,
+                              int32_t field_y, const double* goal, int32_t nx, int32_t ny,
+                              double x0, double x1, double sx, double y0, double y1, double sy,
+                              double oob_weight, double* grad, int64_t grad_stride,
+                              double* error_out, int64_t* hq, int32_t splat_variant,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  if (dimension < 2 || dimension > 3 || field_x < 0 || field_x >= 3 * dimension || field_y < -1 ||
+      field_y >= 3 * dimension)
+    return TFRT_E_BADARG;
+  return density_error_run(rows, stride, n, state_dtype, dimension, mask, field_x, field_y, goal,
+                           nx, ny, x0, x1, sx, y0, y1, sy, oob_weight, grad, grad_stride,
+                           error_out, hq, splat_variant, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

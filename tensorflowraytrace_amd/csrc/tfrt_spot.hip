@@ -37,7 +37,15 @@
 //                      gradient rows of EVERY column (zeros where a ray does not count), the inside
 //                      terms as one partial per workgroup.
 //   k_spot_finish      ONE workgroup: the partials in index order, {sum, terms, mean}.
+//
+// A field is a row of the ray block or a direction cosine of the finished ray's last link
+// (tfrt_spot_error_fields: rays of one group must leave PARALLEL; the codes, the direction and the
+// chain rule of its gradient: direction_fields.h).  The accumulate and the seed are templated on
+// "has a direction field": without one they are the kernels of position fields, load for load;
+// with one they recompute the direction from the rows they stream, and the seed writes EVERY row
+// of the column.
 #include "tfrt_common.h"
+#include "direction_fields.h"
 
 namespace tfrt {
 
@@ -52,7 +60,7 @@ constexpr int FINISH_WAVES = FINISH_BLOCK / 64;
 struct SpotGrid {
   double x0, x1, qsx, y0, y1, qsy, oob, qmax;
   int64_t n_source;
-  int32_t n_groups, row_x, row_y;
+  int32_t n_groups, row_x, row_y;   // row_x, row_y: field codes (direction_fields.h)
 };
 
 // What one column does.  kind 0: masked off; 3: counts, but contributes nothing (a non-finite
@@ -64,12 +72,12 @@ struct SpotRay {
   double dx, dy;     // kind 2: d ex / d x, d ey / d y (-1, 0, +1)
 };
 
-template <typename T>
+template <typename T, int DIM>
 __device__ __forceinline__ SpotRay spot_classify(const T* __restrict__ rows, int64_t stride,
                                                  const int32_t* __restrict__ mask,
                                                  const int32_t* __restrict__ group,
                                                  const int32_t* __restrict__ perm, int64_t i,
-                                                 const SpotGrid& g) {
+                                                 const SpotGrid& g, LinkDir<DIM>& link) {
 #pragma clang fp contract(off)
   SpotRay r;
   r.kind = 0;
@@ -78,8 +86,8 @@ __device__ __forceinline__ SpotRay spot_classify(const T* __restrict__ rows, int
   if (mask != nullptr && mask[i] < 0) return r;
   r.kind = 3;
   const bool two = g.row_y >= 0;
-  const double x = ldd(rows, (int64_t)g.row_x * stride + i);
-  const double y = two ? ldd(rows, (int64_t)g.row_y * stride + i) : 0.0;
+  double x, y;
+  read_fields<T, DIM>(rows, stride, i, g.row_x, g.row_y, x, y, link);
   if (!isfinite(x) || !isfinite(y)) return r;
   // (nothing is read out of bounds, whatever perm and group hold)
   const int64_t s = perm != nullptr ? (int64_t)perm[i] : i;
@@ -145,7 +153,7 @@ __global__ __launch_bounds__(BLOCK) void k_spot_clear(unsigned long long* __rest
   if (e < entries) acc[e] = 0ull;
 }
 
-template <typename T, bool LDS>
+template <typename T, bool LDS, int DIM>
 __global__ __launch_bounds__(BLOCK) void k_spot_accumulate(
     const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
     const int32_t* __restrict__ group, const int32_t* __restrict__ perm, SpotGrid g,
@@ -165,7 +173,8 @@ __global__ __launch_bounds__(BLOCK) void k_spot_accumulate(
   long long counting = 0;
   for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * BLOCK) {
-    const SpotRay r = spot_classify(rows, stride, mask, group, perm, i, g);
+    LinkDir<DIM> link;
+    const SpotRay r = spot_classify<T, DIM>(rows, stride, mask, group, perm, i, g, link);
     counting += r.kind != 0 ? 1 : 0;
     if (r.kind == 2) {
       pen += g.oob * (r.x * r.x + r.y * r.y);
@@ -200,7 +209,7 @@ __global__ __launch_bounds__(BLOCK) void k_spot_accumulate(
   }
 }
 
-template <typename T>
+template <typename T, int DIM>
 __global__ __launch_bounds__(BLOCK) void k_spot_seed(
     const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
     const int32_t* __restrict__ group, const int32_t* __restrict__ perm, SpotGrid g,
@@ -212,7 +221,8 @@ __global__ __launch_bounds__(BLOCK) void k_spot_seed(
   double terms = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * BLOCK) {
-    const SpotRay r = spot_classify(rows, stride, mask, group, perm, i, g);
+    LinkDir<DIM> link;
+    const SpotRay r = spot_classify<T, DIM>(rows, stride, mask, group, perm, i, g, link);
     double gx = 0.0, gy = 0.0;
     if (r.kind == 2) {
       gx = g.oob * (2.0 * r.x) * r.dx;
@@ -233,8 +243,14 @@ __global__ __launch_bounds__(BLOCK) void k_spot_seed(
       }
       terms += t;
     }
-    grad[(int64_t)g.row_x * grad_stride + i] = gx;
-    if (two) grad[(int64_t)g.row_y * grad_stride + i] = gy;
+    if constexpr (DIM != 0) {
+      // (every row of the column: a direction pulls on the start and on the end of the link)
+      chain_fields<DIM>(link, r.kind == 1 || r.kind == 2, g.row_x, g.row_y, gx, gy, grad,
+                   grad_stride, i);
+    } else {
+      grad[(int64_t)g.row_x * grad_stride + i] = gx;
+      if (two) grad[(int64_t)g.row_y * grad_stride + i] = gy;
+    }
   }
   const double s = spot_block_sum<WAVES>(terms, wsum);
   if (threadIdx.x == 0) term_partial[blockIdx.x] = s;
@@ -285,25 +301,38 @@ static int spot_seed_grid(int64_t n) {
 
 using namespace tfrt;
 
-extern "C" {
+extern "C" size_t tfrt_spot_error_workspace_bytes(int64_t n, int32_t n_groups);
 
-size_t tfrt_spot_error_workspace_bytes(int64_t n, int32_t n_groups) {
-  if (n < 0 || n > INT32_MAX || n_groups < 1 || n_groups > SPOT_MAX_GROUPS) return 0;
-  return 2 * align_up(SPOT_MAX_GRID * sizeof(double)) +
-         align_up(SPOT_SEED_MAX_GRID * sizeof(double));
+// The accumulate and seed launches of both entries.
+template <typename T, int DIM>
+static void spot_launch(const T* r, int64_t stride, int64_t n, const int32_t* mask,
+                        const int32_t* group, const int32_t* perm, const SpotGrid& g, bool lds,
+                        int grid, int sgrid, unsigned long long* accu, double* pen_partial,
+                        long long* cnt_partial, double* term_partial, double* grad,
+                        int64_t grad_stride, hipStream_t st) {
+  if (lds)
+    hipLaunchKernelGGL((k_spot_accumulate<T, true, DIM>), dim3(grid), dim3(BLOCK),
+                       (size_t)g.n_groups * 3 * sizeof(unsigned long long), st, r, stride, n, mask,
+                       group, perm, g, accu, pen_partial, cnt_partial);
+  else
+    hipLaunchKernelGGL((k_spot_accumulate<T, false, DIM>), dim3(grid), dim3(BLOCK), 0, st, r,
+                       stride, n, mask, group, perm, g, accu, pen_partial, cnt_partial);
+  hipLaunchKernelGGL((k_spot_seed<T, DIM>), dim3(sgrid), dim3(BLOCK), 0, st, r, stride, n, mask,
+                     group, perm, g, reinterpret_cast<const long long*>(accu), grad, grad_stride,
+                     term_partial);
 }
 
-int tfrt_spot_error(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
-                    const int32_t* mask, int32_t row_x, int32_t row_y, const int32_t* group,
-                    int64_t n_source, const int32_t* perm, int32_t n_groups, double x0, double x1,
-                    double qsx, double y0, double y1, double qsy, int32_t qbits,
-                    double oob_weight, double* grad, int64_t grad_stride, double* error_out,
-                    int64_t* acc, int32_t variant, void* workspace, size_t workspace_bytes,
-                    void* stream) {
+// Both entries behind their own checks of the rows / codes: `dim` 2 or 3, codes below 3 * dim.
+static int spot_error_run(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                          int32_t dim, const int32_t* mask, int32_t row_x, int32_t row_y,
+                          const int32_t* group, int64_t n_source, const int32_t* perm,
+                          int32_t n_groups, double x0, double x1, double qsx, double y0, double y1,
+                          double qsy, int32_t qbits, double oob_weight, double* grad,
+                          int64_t grad_stride, double* error_out, int64_t* acc, int32_t variant,
+                          void* workspace, size_t workspace_bytes, void* stream) {
   if (n < 0 || n > INT32_MAX || n_source < 0 || n_source > INT32_MAX || n_groups < 1 ||
-      n_groups > SPOT_MAX_GROUPS || qbits < 1 || qbits > 52 || row_x < 0 || row_x > 5 ||
-      row_y < -1 || row_y > 5 || row_x == row_y || !group || !error_out || !acc || !workspace ||
-      variant < 0 || variant > 2)
+      n_groups > SPOT_MAX_GROUPS || qbits < 1 || qbits > 52 || row_x == row_y || !group ||
+      !error_out || !acc || !workspace || variant < 0 || variant > 2)
     return TFRT_E_BADARG;
   if (n >= ((int64_t)1 << (62 - qbits))) return TFRT_E_BADARG;   // n * 2^qbits must stay below 2^62
   if (!(x1 > x0) || !(qsx > 0.0) || !isfinite(qsx) || !(oob_weight >= 0.0) ||
@@ -316,6 +345,7 @@ int tfrt_spot_error(const void* rows, int64_t stride, int64_t n, int32_t state_d
   if (variant == 1 && n_groups > SPOT_LDS_GROUPS) return TFRT_E_BADARG;
   if (workspace_bytes < tfrt_spot_error_workspace_bytes(n, n_groups)) return TFRT_E_WORKSPACE;
   const bool lds = variant == 1 || (variant == 0 && n_groups <= SPOT_LDS_GROUPS);
+  const bool dir = row_x >= 2 * dim || row_y >= 2 * dim;
 
   SpotGrid g;
   g.x0 = x0, g.x1 = x1, g.qsx = qsx, g.oob = oob_weight;
@@ -339,21 +369,57 @@ int tfrt_spot_error(const void* rows, int64_t stride, int64_t n, int32_t state_d
     using T = typename decltype(tag)::type;
     const T* r = static_cast<const T*>(rows);
     if (grid > 0) {
-      if (lds)
-        hipLaunchKernelGGL((k_spot_accumulate<T, true>), dim3(grid), dim3(BLOCK),
-                           (size_t)n_groups * 3 * sizeof(unsigned long long), st, r, stride, n,
-                           mask, group, perm, g, accu, pen_partial, cnt_partial);
+      if (!dir)
+        spot_launch<T, 0>(r, stride, n, mask, group, perm, g, lds, grid, sgrid, accu, pen_partial,
+                          cnt_partial, term_partial, grad, grad_stride, st);
+      else if (dim == 3)
+        spot_launch<T, 3>(r, stride, n, mask, group, perm, g, lds, grid, sgrid, accu, pen_partial,
+                          cnt_partial, term_partial, grad, grad_stride, st);
       else
-        hipLaunchKernelGGL((k_spot_accumulate<T, false>), dim3(grid), dim3(BLOCK), 0, st, r,
-                           stride, n, mask, group, perm, g, accu, pen_partial, cnt_partial);
-      hipLaunchKernelGGL((k_spot_seed<T>), dim3(sgrid), dim3(BLOCK), 0, st, r, stride, n, mask,
-                         group, perm, g, reinterpret_cast<const long long*>(acc), grad,
-                         grad_stride, term_partial);
+        spot_launch<T, 2>(r, stride, n, mask, group, perm, g, lds, grid, sgrid, accu, pen_partial,
+                          cnt_partial, term_partial, grad, grad_stride, st);
     }
     hipLaunchKernelGGL(k_spot_finish, dim3(1), dim3(FINISH_BLOCK), 0, st, pen_partial, cnt_partial,
                        grid, term_partial, sgrid, row_y >= 0 ? 2 : 1, error_out);
     return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
   });
+}
+
+extern "C" {
+
+size_t tfrt_spot_error_workspace_bytes(int64_t n, int32_t n_groups) {
+  if (n < 0 || n > INT32_MAX || n_groups < 1 || n_groups > SPOT_MAX_GROUPS) return 0;
+  return 2 * align_up(SPOT_MAX_GRID * sizeof(double)) +
+         align_up(SPOT_SEED_MAX_GRID * sizeof(double));
+}
+
+int tfrt_spot_error(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                    const int32_t* mask, int32_t row_x, int32_t row_y, const int32_t* group,
+                    int64_t n_source, const int32_t* perm, int32_t n_groups, double x0, double x1,
+                    double qsx, double y0, double y1, double qsy, int32_t qbits,
+                    double oob_weight, double* grad, int64_t grad_stride, double* error_out,
+                    int64_t* acc, int32_t variant, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+  if (row_x < 0 || row_x > 5 || row_y < -1 || row_y > 5) return TFRT_E_BADARG;
+  return spot_error_run(rows, stride, n, state_dtype, 3, mask, row_x, row_y, group, n_source, perm,
+                        n_groups, x0, x1, qsx, y0, y1, qsy, qbits, oob_weight, grad, grad_stride,
+                        error_out, acc, variant, workspace, workspace_bytes, stream);
+}
+
+int tfrt_spot_error_fields(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                           int32_t dimension, const int32_t* mask, int32_t field_x,
+                           int32_t field_y, const int32_t* group, int64_t n_source,
+                           const int32_t* perm, int32_t n_groups, double x0, double x1, double qsx,
+                           double y0, double y1, double qsy, int32_t qbits, double oob_weight,
+                           double* grad, int64_t grad_stride, double* error_out, int64_t* acc,
+                           int32_t variant, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+  if (dimension < 2 || dimension > 3 || field_x < 0 || field_x >= 3 * dimension || field_y < -1 ||
+      field_y >= 3 * dimension)
+    return TFRT_E_BADARG;
+  return spot_error_run(rows, stride, n, state_dtype, dimension, mask, field_x, field_y, group,
+                        n_source, perm, n_groups, x0, x1, qsx, y0, y1, qsy, qbits, oob_weight, grad,
+                        grad_stride, error_out, acc, variant, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -34,8 +34,8 @@ every pass in ONE launch -- and autograd from the merged segments and arcs to th
 fixed-shape column), ``fn`` and its autograd, and ``tfrt_trace2d_backward_rows`` sweeps from that
 gradient; ``_rowwise3d`` does the same on a 3-D engine with an in-place trace that leaves the
 finished rows at the rays' own columns.  A ``DensityError`` -- the finished rays, taken together,
-must land with a given density -- takes ``_rowwise3d`` too, with ``tfrt_density_error`` (a memset and
-three launches: splat, bins, seed) in the place of ``fn`` and its autograd; a ``SpotError`` -- rays
+must land with a given density -- takes ``_rowwise3d`` too, with ``tfrt_density_error`` (four
+launches: clear, splat, bins, seed) in the place of ``fn`` and its autograd; a ``SpotError`` -- rays
 of one group must meet in one point -- likewise with ``tfrt_spot_error`` (clear, accumulate, seed,
 finish).
 
@@ -62,6 +62,12 @@ from ._lib import RayOut, check
 
 _GEO3 = ("x_start", "y_start", "z_start", "x_end", "y_end", "z_end")
 _GEO2 = ("x_start", "y_start", "x_end", "y_end")
+# the fields of the coupled errors (DensityError, SpotError): a row of the geometry block or a
+# direction cosine of the finished ray's last link; the index is the field code of
+# tfrt_density_error_fields / tfrt_spot_error_fields
+_FIELDS3 = _GEO3 + ("x_dir", "y_dir", "z_dir")
+_FIELDS2 = _GEO2 + ("x_dir", "y_dir")
+
 _CLASS_FLAGS = (("finished", _lib.COMPILE_FINISHED), ("active", _lib.COMPILE_ACTIVE),
                 ("stopped", _lib.COMPILE_STOPPED), ("dead", _lib.COMPILE_DEAD))
 
@@ -183,13 +189,39 @@ class RowwiseError:
         return self.fn(engine.finished_rays)
 
 
+def _field_codes(what, fields, dimension):
+    """The field codes of ``fields`` on a ``dimension``-D engine."""
+    names = _FIELDS3 if dimension == 3 else _FIELDS2
+    bad = [f for f in fields if f not in names]
+    if bad:
+        raise ValueError(f"{what}: field(s) {bad} do not exist on a {dimension}-D engine "
+                         f"(fields of its rays: {names})")
+    return [names.index(f) for f in fields]
+
+
+def _geometry_block(engine, fin):
+    """(dimension, the (2 * dimension, n) block of the finished rays' geometry fields)."""
+    dim = engine.dimension
+    return dim, torch.stack([fin[f] for f in (_GEO3 if dim == 3 else _GEO2)], dim=0)
+
+
 class DensityError:
     """The finished rays, taken together, must land with the density ``goal`` on the target: a
     soft (bilinear) histogram of the rays against the goal, both L2-normalised, summed squared
     difference -- ``analyze.DistributionDifferential`` (tfrt/analyze.py:134-290) with a gradient.
 
-    ``fields``: one or two geometry fields of a finished ray, x and (if present) y, e.g.
-    ``("y_end", "z_end")``.  ``goal``: a non-negative array, shape (ny, nx) for two fields -- the
+    ``fields``: one or two fields of a finished ray, x and (if present) y, e.g.
+    ``("y_end", "z_end")``: geometry fields, or the direction cosines ``x_dir``, ``y_dir``,
+    ``z_dir`` of the ray's last link -- ``("y_dir", "z_dir")`` is a far-field intensity, a position
+    with a direction a phase-space density.  For a ray, in float64 and every operation rounded on
+    its own: ``e = end - start``, ``L = sqrt(e_x*e_x + e_y*e_y + e_z*e_z)`` (summed left to right),
+    ``d = e / L``; a ray with a non-finite coordinate or without a length (``L`` not finite or not
+    ``> 0``) counts as one with a non-finite coordinate.  The gradient of a direction field goes
+    back onto the start and the end of the link:
+    ``G_b = ((gv of the field of axis b, else 0) - t * d_b) / L`` with ``t = sum_k gv_k * d_(a_k)``,
+    ``+G`` on the end rows and ``-G`` on the start rows.  With float32 ray state the subtraction
+    cancels: a direction is good to about ``eps32 * max|coordinate| / L``, not to ``eps32``.
+    ``goal``: a non-negative array, shape (ny, nx) for two fields -- the
     second field is the FIRST index, as ``analyze.histogram2D`` returns it -- or (nx,) for one; or a
     callable, evaluated once at the bin centres exactly as ``DistributionDifferential`` does (the
     bin counts then come from ``bins``: nx, or (nx, ny)).  It is kept L2-normalised in float64 on
@@ -239,10 +271,11 @@ class DensityError:
     def __init__(self, fields, goal, domain, oob_weight=0.0, bins=None):
         from . import config
         self.fields = (fields,) if isinstance(fields, str) else tuple(fields)
-        if len(self.fields) not in (1, 2) or any(f not in _GEO3 for f in self.fields) \
+        if len(self.fields) not in (1, 2) or any(f not in _FIELDS3 for f in self.fields) \
                 or len(set(self.fields)) != len(self.fields):
-            raise ValueError(f"DensityError: one or two distinct fields out of {_GEO3}, got {fields!r}")
-        self.rows = [_GEO3.index(f) for f in self.fields]
+            raise ValueError(f"DensityError: one or two distinct fields out of {_FIELDS3}, got {fields!r}")
+        self.rows = [_FIELDS3.index(f) for f in self.fields]
+        self.has_direction = any(f.endswith("_dir") for f in self.fields)
         k = len(self.fields)
         try:
             domain = tuple((float(d[0]), float(d[1])) for d in domain)
@@ -288,14 +321,11 @@ class DensityError:
         return self.goal
 
     def rows_for(self, dimension):
-        """Rows of the ray block of a ``dimension``-D trace that the fields are read from."""
+        """Field codes on a ``dimension``-D trace: the row of the ray block a geometry field is
+        read from, ``2 * dimension + axis`` for a direction cosine."""
         if dimension == 3:
             return self.rows
-        bad = [f for f in self.fields if f not in _GEO2]
-        if bad:
-            raise ValueError(f"DensityError: field(s) {bad} do not exist on a {dimension}-D engine "
-                             f"(fields of its rays: {_GEO2})")
-        return [_GEO2.index(f) for f in self.fields]
+        return _field_codes("DensityError", self.fields, dimension)
 
     def goal_on(self, device):
         """The goal buffer on ``device`` (moved once; a new buffer re-captures a graph)."""
@@ -308,20 +338,25 @@ class DensityError:
         return (self.goal.data_ptr(), tuple(self.goal.shape), self.grid, self.oob_weight,
                 self.splat_variant)
 
-    def evaluate(self, rows, row_x, row_y, mask=None, **buffers):
-        """``ops.density_error`` of the columns of ``rows`` with this goal, domain and weight."""
+    def evaluate(self, rows, row_x, row_y, mask=None, dimension=None, **buffers):
+        """``ops.density_error`` of the columns of ``rows`` with this goal, domain and weight
+        (``dimension`` given: ``rows`` is the geometry block, ``row_x`` / ``row_y`` field codes)."""
         out = ops.density_error(rows, row_x, row_y, self.goal_on(rows.device), self.grid,
-                                self.oob_weight, mask=mask, variant=self.splat_variant, **buffers)
+                                self.oob_weight, mask=mask, variant=self.splat_variant,
+                                dimension=dimension, **buffers)
         self.last_hq = out[2]
         return out
 
     def __call__(self, engine):
         """The error as a (1,) tensor through the generic path; the gradient rows come back in
         ``backward``."""
-        self.rows_for(engine.dimension)
+        codes = self.rows_for(engine.dimension)
         fin = engine.finished_rays
         if not bool(fin):
             return (self.goal * self.goal).sum().reshape(1)
+        if self.has_direction:
+            dim, block = _geometry_block(engine, fin)
+            return _DensityFieldTerms.apply(block, self, dim, tuple(codes))
         return _DensityTerms.apply(torch.stack([fin[f] for f in self.fields], dim=0), self)
 
 
@@ -342,13 +377,38 @@ class _DensityTerms(torch.autograd.Function):
         return (upstream * grad).to(ctx.dtype), None
 
 
+class _DensityFieldTerms(torch.autograd.Function):
+    """DensityError with a direction field over the (2 * dimension, n) geometry block of the
+    finished rays, no mask; ``codes``: the field codes."""
+
+    @staticmethod
+    def forward(ctx, block, erf, dimension, codes):
+        rows = block.detach().contiguous()
+        err, grad, _ = erf.evaluate(rows, codes[0], codes[1] if len(codes) == 2 else -1,
+                                    dimension=dimension)
+        ctx.save_for_backward(grad)
+        ctx.dtype = block.dtype
+        return err[:1].clone()
+
+    @staticmethod
+    def backward(ctx, upstream):
+        grad, = ctx.saved_tensors
+        return (upstream * grad).to(ctx.dtype), None, None, None
+
+
 class SpotError:
     """Rays that left the same object point must meet in one point -- wherever that is: the sum
     over the finished rays of the squared distance to the CENTROID of their own group, the squared
     RMS spot size times the ray count.  Where the spots lie (magnification, distortion, field
     curvature) is left to the lens; no target is needed in advance.
 
-    ``fields``: one or two geometry fields of a finished ray, e.g. ``("y_end", "z_end")``.
+    ``fields``: one or two fields of a finished ray, e.g. ``("y_end", "z_end")``: geometry
+    fields, or the direction cosines ``x_dir``, ``y_dir``, ``z_dir`` of the ray's last link --
+    ``("y_dir", "z_dir")`` asks the rays of one object point to leave PARALLEL (collimation, afocal
+    systems: a spot in direction space; ``centroids()`` are then mean direction cosines).  The
+    direction, its non-finite case, the chain rule back onto the start and end rows and the
+    float32 caveat (a direction is good to about ``eps32 * max|coordinate| / L``) are
+    ``DensityError``'s.
     ``groups``: an integer tensor or array of shape (N,), one label per SOURCE ray in the source's
     own order -- finished rays look theirs up through the source-ray index the trace carries --, or
     a callable on the source's field dict that returns such labels (evaluated and cached as
@@ -384,7 +444,9 @@ class SpotError:
     not traced in place, ``deterministic=True``, fewer than 4,096 rays and 2-D engines
     (``FusedStep.eligible2d`` is false).  Its ``backward`` returns ``upstream * gradient``: exact
     when ``upstream`` is constant within a group (the optimiser passes ones); weights that differ
-    inside a group would move the centroid, which this does not follow.  On a 3-D engine that traces
+    inside a group would move the centroid, which this does not follow; with a direction field the
+    two fields of a ray must also carry the same weight (a ``ValueError`` otherwise), because the
+    kernel's chain rule sums both into the geometry rows.  On a 3-D engine that traces
     its source in place the optimiser runs it on the fused, graph-replayed step under the
     conditions of a ``RowwiseError`` (``FusedStep._rowwise3d`` with ``tfrt_spot_error`` in the
     place of ``fn`` and its autograd), with the same kernels and the same ``qbits``.  One process:
@@ -401,10 +463,11 @@ class SpotError:
     def __init__(self, fields, groups, domain, oob_weight=0.0, n_groups=None):
         from . import config
         self.fields = (fields,) if isinstance(fields, str) else tuple(fields)
-        if len(self.fields) not in (1, 2) or any(f not in _GEO3 for f in self.fields) \
+        if len(self.fields) not in (1, 2) or any(f not in _FIELDS3 for f in self.fields) \
                 or len(set(self.fields)) != len(self.fields):
-            raise ValueError(f"SpotError: one or two distinct fields out of {_GEO3}, got {fields!r}")
-        self.rows = [_GEO3.index(f) for f in self.fields]
+            raise ValueError(f"SpotError: one or two distinct fields out of {_FIELDS3}, got {fields!r}")
+        self.rows = [_FIELDS3.index(f) for f in self.fields]
+        self.has_direction = any(f.endswith("_dir") for f in self.fields)
         k = len(self.fields)
         try:
             domain = tuple((float(d[0]), float(d[1])) for d in domain)
@@ -448,14 +511,11 @@ class SpotError:
         return g.detach().to(device=device, dtype=torch.int32).contiguous()
 
     def rows_for(self, dimension):
-        """Rows of the ray block of a ``dimension``-D trace that the fields are read from."""
+        """Field codes on a ``dimension``-D trace: the row of the ray block a geometry field is
+        read from, ``2 * dimension + axis`` for a direction cosine."""
         if dimension == 3:
             return self.rows
-        bad = [f for f in self.fields if f not in _GEO2]
-        if bad:
-            raise ValueError(f"SpotError: field(s) {bad} do not exist on a {dimension}-D engine "
-                             f"(fields of its rays: {_GEO2})")
-        return [_GEO2.index(f) for f in self.fields]
+        return _field_codes("SpotError", self.fields, dimension)
 
     def labels_of(self, src):
         """The int32 label buffer of the source set ``src`` on its device, one label per source
@@ -496,12 +556,14 @@ class SpotError:
         return (None if lab is None else (lab.data_ptr(), tuple(lab.shape)), self.n_groups,
                 self.domain, self.oob_weight, self.splat_variant)
 
-    def evaluate(self, rows, row_x, row_y, labels, mask=None, perm=None, **buffers):
-        """``ops.spot_error`` of the columns of ``rows`` with these labels, domain and weight."""
+    def evaluate(self, rows, row_x, row_y, labels, mask=None, perm=None, dimension=None,
+                 **buffers):
+        """``ops.spot_error`` of the columns of ``rows`` with these labels, domain and weight
+        (``dimension`` given: ``rows`` is the geometry block, ``row_x`` / ``row_y`` field codes)."""
         qbits, grid = self.grid_for(labels.numel())
         out = ops.spot_error(rows, row_x, row_y, labels, self.n_groups, grid, self.oob_weight,
                              mask=mask, perm=perm, variant=self.splat_variant, qbits=qbits,
-                             **buffers)
+                             dimension=dimension, **buffers)
         self.last_acc, self.last_grid = out[2], grid
         return out
 
@@ -514,12 +576,16 @@ class SpotError:
     def __call__(self, engine):
         """The (n_finished, k) error terms through the generic path; the gradient rows come back
         in ``backward``."""
-        self.rows_for(engine.dimension)
+        codes = self.rows_for(engine.dimension)
         fin = engine.finished_rays
         if not bool(fin):
             return torch.zeros((0, len(self.fields)), dtype=torch.float64)
         ids = engine.last_trace["finished_id"]
         labels = self.labels_of(engine._trace_src)
+        if self.has_direction:
+            dim, block = _geometry_block(engine, fin)
+            return _SpotFieldTerms.apply(block, self, labels, ids.to(torch.int32).contiguous(),
+                                         dim, tuple(codes))
         columns = torch.stack([fin[f] for f in self.fields], dim=0)
         return _SpotTerms.apply(columns, self, labels, ids.to(torch.int32).contiguous())
 
@@ -555,6 +621,45 @@ class _SpotTerms(torch.autograd.Function):
     def backward(ctx, upstream):
         grad, = ctx.saved_tensors
         return (upstream.t() * grad).to(ctx.dtype), None, None, None
+
+
+class _SpotFieldTerms(torch.autograd.Function):
+    """SpotError with a direction field over the (2 * dimension, n) geometry block of the finished
+    rays, no mask; ``ids``: the source ray of every column, ``codes``: the field codes.  Returns
+    the (n, k) terms: an inside ray's squared distances to its group's centroid (from the records
+    of the evaluation), a penalised ray's ``oob_weight * ex**2`` per field."""
+
+    @staticmethod
+    def forward(ctx, block, erf, labels, ids, dimension, codes):
+        rows = block.detach().contiguous()
+        k = len(codes)
+        err, grad, acc = erf.evaluate(rows, codes[0], codes[1] if k == 2 else -1, labels,
+                                      perm=ids, dimension=dimension)
+        ctx.save_for_backward(grad)
+        ctx.dtype = block.dtype
+        link = ops._link_torch(rows, dimension)
+        v = torch.stack([ops._link_field_torch(link, c, dimension) for c in codes], dim=0)
+        lo = torch.tensor([d[0] for d in erf.domain], dtype=torch.float64, device=v.device)[:, None]
+        hi = torch.tensor([d[1] for d in erf.domain], dtype=torch.float64, device=v.device)[:, None]
+        zero = torch.zeros((), dtype=torch.float64, device=v.device)
+        ex = torch.maximum(lo - v, zero) + torch.maximum(v - hi, zero)
+        out = ((v < lo) | (v > hi)).any(dim=0, keepdim=True)
+        lab = labels[ids.long().clamp(0, labels.numel() - 1)]
+        spot = (lab >= 0) & (lab < erf.n_groups) & torch.isfinite(v).all(dim=0)
+        centre = ops.spot_centroids(acc, erf.last_grid, k).t()[:, lab.long().clamp(0, erf.n_groups - 1)]
+        dv = v - centre
+        terms = torch.where(out, erf.oob_weight * (ex * ex), dv * dv)
+        return torch.where(spot[None, :], terms, zero).t().contiguous()
+
+    @staticmethod
+    def backward(ctx, upstream):
+        # the kernel's chain rule has summed both fields' gradients into the rows: one weight per
+        # ray is all that can be applied afterwards (the optimiser passes ones)
+        if upstream.shape[1] == 2 and not torch.equal(upstream[:, 0], upstream[:, 1]):
+            raise ValueError("SpotError with a direction field: the upstream gradient must weigh "
+                             "both fields of a ray alike")
+        grad, = ctx.saved_tensors
+        return (upstream[:, 0] * grad).to(ctx.dtype), None, None, None, None, None
 
 
 class _RowFields:
@@ -1156,9 +1261,10 @@ class FusedStep:
 
     def _density_seeds3d(self, st):
         """A DensityError on the fixed-shape columns: tfrt_density_error reads ``st.rows`` and the
-        mask ``st.row_face`` and writes its two rows of the persistent seed block (the other rows
-        were zeroed when the state was made) for every column, the error into ``st.err`` and the
-        histogram into ``st.hq``.  Returns the (6, capN) seed block."""
+        mask ``st.row_face`` and writes its rows of the persistent seed block for every column --
+        the two rows of position fields (the other rows were zeroed when the state was made, and
+        the field codes are part of its signature), all six with a direction field --, the error
+        into ``st.err`` and the histogram into ``st.hq``.  Returns the (6, capN) seed block."""
         erf = self.opt.error_function
         dev = st.rows.device
         goal = erf.goal_on(dev)
@@ -1169,7 +1275,7 @@ class FusedStep:
             st.hq = torch.zeros(goal.shape, dtype=torch.int64, device=dev)
         rows = erf.rows
         erf.evaluate(st.rows[:, :st.N], rows[0], rows[1] if len(rows) == 2 else -1,
-                     mask=st.row_face, grad=st.g_fin, err=st.err, hq=st.hq,
+                     mask=st.row_face, dimension=3, grad=st.g_fin, err=st.err, hq=st.hq,
                      workspace=st.density_ws)
         with torch.no_grad():
             self.tests_total += st.row_passes[:st.N].sum() * st.M
@@ -1179,9 +1285,10 @@ class FusedStep:
         """A SpotError on the fixed-shape columns: tfrt_spot_error reads ``st.rows``, the mask
         ``st.row_face``, the source's label buffer and the trace's order ``perm`` -- the kernel
         looks a column's label up itself, so no permuted copy can go stale when a source is
-        re-drawn and re-ordered inside the graph -- and writes its two rows of the persistent seed
-        block (the other rows were zeroed when the state was made) for every column, the error
-        into ``st.err`` and the group records into ``st.acc``.  Returns the (6, capN) seed block."""
+        re-drawn and re-ordered inside the graph -- and writes its rows of the persistent seed
+        block for every column (two for position fields, the others zeroed when the state was
+        made; all six with a direction field), the error into ``st.err`` and the group records
+        into ``st.acc``.  Returns the (6, capN) seed block."""
         erf = self.opt.error_function
         dev = st.rows.device
         labels = erf.labels_of(src)
@@ -1191,8 +1298,8 @@ class FusedStep:
             st.acc = torch.zeros((erf.n_groups, 4), dtype=torch.int64, device=dev)
         rows = erf.rows
         erf.evaluate(st.rows[:, :st.N], rows[0], rows[1] if len(rows) == 2 else -1, labels,
-                     mask=st.row_face, perm=perm, grad=st.g_fin, err=st.err, acc=st.acc,
-                     workspace=st.spot_ws)
+                     mask=st.row_face, perm=perm, dimension=3, grad=st.g_fin, err=st.err,
+                     acc=st.acc, workspace=st.spot_ws)
         with torch.no_grad():
             self.tests_total += st.row_passes[:st.N].sum() * st.M
         return st.g_fin

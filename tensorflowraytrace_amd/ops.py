@@ -1257,6 +1257,68 @@ def gather_rows(src, index, n_valid=None, out=None):
     return out.reshape(-1) if (one and out.dim() == 2) else out
 
 
+def _check_field_codes(what, rows, row_x, row_y, dimension):
+    """``dimension`` given: ``rows`` is the (2 * dimension, n) geometry block and ``row_x`` /
+    ``row_y`` are field codes (tfrt_density_error_fields)."""
+    if dimension not in (2, 3):
+        raise ValueError(f"{what}: dimension must be None, 2 or 3, got {dimension!r}")
+    if rows.shape[0] != 2 * dimension:
+        raise ValueError(f"{what}: a {dimension}-D geometry block has {2 * dimension} rows, got "
+                         f"{rows.shape[0]}")
+    top = 3 * dimension
+    if not (0 <= row_x < top and -1 <= row_y < top and row_x != row_y):
+        raise ValueError(f"{what}: field codes must be distinct and lie in [0, {top}), got "
+                         f"{row_x}, {row_y}")
+
+
+def _link_torch(rows, dim):
+    """(start, end, d, L, ok) of the columns' last links, the operations of
+    tfrt_density_error_fields one by one."""
+    s, e = rows[:dim].double(), rows[dim:2 * dim].double()
+    v = e - s
+    q = v[0] * v[0] + v[1] * v[1]
+    if dim == 3:
+        q = q + v[2] * v[2]
+    # (numpy's sqrt on the CPU, as tests/direction_fields_reference.py uses: torch 2.10's CPU sqrt
+    # differed from it in the last bit of 11 of the 1,000 lengths of that file's ``rays(1000)``,
+    # and L has to agree with the kernels' bit for bit)
+    L = torch.sqrt(q) if q.is_cuda else torch.from_numpy(np.sqrt(q.numpy()))
+    ok = torch.isfinite(s).all(dim=0) & torch.isfinite(e).all(dim=0) & torch.isfinite(L) & (L > 0)
+    return s, e, v / L, L, ok
+
+
+def _link_field_torch(link, code, dim):
+    s, e, d, _, ok = link
+    v = s[code] if code < dim else (e[code - dim] if code < 2 * dim else d[code - 2 * dim])
+    return torch.where(ok, v, torch.full((), float("nan"), dtype=torch.float64))
+
+
+def _chain_cpu(grad, n, dim, row_x, row_y, gx, gy, link, counts):
+    """All 2 * dim rows of ``grad`` from gx, gy (the chain rule of tfrt_density_error_fields, in
+    its operation order); zeros where ``counts`` is false."""
+    _, _, d, L, _ = link
+    two = row_y >= 0
+    ax, ay = row_x - 2 * dim, (row_y - 2 * dim if two else -1)
+    t = gx * d[ax] if ax >= 0 else None
+    if ay >= 0:
+        t = gy * d[ay] if t is None else t + gy * d[ay]
+    zero = torch.zeros((), dtype=torch.float64)
+    for b in range(dim):
+        gvb = gx if ax == b else (gy if ay == b else torch.zeros_like(gx))
+        G = (gvb - t * d[b]) / L
+        start, end = -G, G
+        if row_x == b:
+            start = start + gx
+        if two and row_y == b:
+            start = start + gy
+        if row_x == dim + b:
+            end = end + gx
+        if two and row_y == dim + b:
+            end = end + gy
+        grad[b, :n] = torch.where(counts, start, zero)
+        grad[dim + b, :n] = torch.where(counts, end, zero)
+
+
 DENSITY_FIXED_ONE = 4294967296.0      # 2^32: one ray's total weight in the int64 histogram
 DENSITY_MAX_BINS = 65536
 
@@ -1273,7 +1335,7 @@ def density_grid(domain, nx, ny=None):
 
 
 def density_error(rows, row_x, row_y, goal, grid, oob_weight=0.0, mask=None, grad=None, err=None,
-                  hq=None, workspace=None, variant=0):
+                  hq=None, workspace=None, variant=0, dimension=None):
     """tfrt_density_error: the DensityError of the columns of ``rows`` (k, n), x in row ``row_x``
     and y in row ``row_y`` (-1: one field), against the L2-normalised float64 ``goal`` (ny, nx) or
     (nx,); ``grid`` from ``density_grid``; ``mask``: optional int32, column i counts if
@@ -1281,6 +1343,12 @@ def density_error(rows, row_x, row_y, goal, grid, oob_weight=0.0, mask=None, gra
     shape): rows ``row_x`` / ``row_y`` of ``grad`` are written for every column, other rows only
     when ``grad`` is made here (zeros).  ``grad``, ``err``, ``hq``, ``workspace`` (uint8): buffers
     to reuse -- with all four given a CUDA call allocates nothing.
+
+    ``dimension`` 2 or 3 (tfrt_density_error_fields): ``rows`` is the (2 * dimension, n) geometry
+    block of the finished rays (start rows, then end rows) and ``row_x`` / ``row_y`` are FIELD
+    CODES: below 2 * dimension a row of the block, from there on the direction cosines of the last
+    link (3-D: x_dir, y_dir, z_dir = 6, 7, 8; 2-D: x_dir, y_dir = 4, 5).  With a direction field
+    all 2 * dimension rows of ``grad`` are written (the chain rule back onto start and end).
 
     CUDA tensors run the kernels.  CPU tensors run a torch restatement with the same int64
     fixed-point histogram and the same operation order per ray (``hq`` and the per-ray quantities
@@ -1294,16 +1362,21 @@ def density_error(rows, row_x, row_y, goal, grid, oob_weight=0.0, mask=None, gra
     if nx * ny > DENSITY_MAX_BINS:
         raise ValueError(f"density_error: more than {DENSITY_MAX_BINS} bins")
     k, n = rows.shape
+    if dimension is not None:
+        _check_field_codes("density_error", rows, row_x, row_y, dimension)
     dev = rows.device
     if grad is None:
         grad = torch.zeros((k, n), dtype=torch.float64, device=dev)
+    if dimension is not None and grad.shape[0] != k:
+        raise ValueError(f"density_error: grad needs {k} rows")
     if err is None:
         err = torch.empty(3, dtype=torch.float64, device=dev)
     if hq is None:
         hq = torch.empty(goal.shape, dtype=torch.int64, device=dev)
     x0, x1, sx, y0, y1, sy = grid
     if not rows.is_cuda:
-        _density_error_cpu(rows, row_x, row_y, goal, grid, float(oob_weight), mask, grad, err, hq)
+        _density_error_cpu(rows, row_x, row_y, goal, grid, float(oob_weight), mask, grad, err, hq,
+                           dimension)
         return err, grad, hq
     _need_gpu(rows, goal, mask, grad, err, hq)
     if rows.stride(1) != 1 or grad.stride(1) != 1:
@@ -1312,6 +1385,13 @@ def density_error(rows, row_x, row_y, goal, grid, oob_weight=0.0, mask=None, gra
     wsb = L.tfrt_density_error_workspace_bytes(n, nx, ny)
     if workspace is None:
         workspace = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    if dimension is not None:
+        check(L.tfrt_density_error_fields(
+            _p(rows), rows.stride(0), n, _DT[rows.dtype], int(dimension), _p(mask), row_x, row_y,
+            _p(goal), nx, ny, x0, x1, sx, y0, y1, sy, float(oob_weight), _p(grad), grad.stride(0),
+            _p(err), _p(hq), int(variant), _p(workspace), workspace.numel(), _stream(rows)),
+            "tfrt_density_error_fields")
+        return err, grad, hq
     check(L.tfrt_density_error(
         _p(rows), rows.stride(0), n, _DT[rows.dtype], _p(mask), row_x, row_y, _p(goal), nx, ny,
         x0, x1, sx, y0, y1, sy, float(oob_weight), _p(grad), grad.stride(0), _p(err), _p(hq),
@@ -1326,14 +1406,20 @@ def _density_axis(v, lo, scale, nb):
     return i0.clamp(0, nb - 1), (i0 + 1).clamp(0, nb - 1), u - f
 
 
-def _density_error_cpu(rows, row_x, row_y, goal, grid, oob, mask, grad, err, hq):
+def _density_error_cpu(rows, row_x, row_y, goal, grid, oob, mask, grad, err, hq, dimension=None):
     """The CPU path of ``density_error`` (every torch op rounds on its own, as the kernels do)."""
     x0, x1, sx, y0, y1, sy = grid
     two = row_y >= 0
     nx = goal.shape[-1]
     n = rows.shape[1]
-    x = rows[row_x].double()
-    y = rows[row_y].double() if two else torch.zeros_like(x)
+    link = None
+    if dimension is not None and max(row_x, row_y) >= 2 * dimension:
+        link = _link_torch(rows, dimension)
+        x = _link_field_torch(link, row_x, dimension)
+        y = _link_field_torch(link, row_y, dimension) if two else torch.zeros_like(x)
+    else:
+        x = rows[row_x].double()
+        y = rows[row_y].double() if two else torch.zeros_like(x)
     counts = torch.isfinite(x) & torch.isfinite(y)
     if mask is not None:
         counts &= mask >= 0
@@ -1383,9 +1469,12 @@ def _density_error_cpu(rows, row_x, row_y, goal, grid, oob, mask, grad, err, hq)
         gy[inside] = sy * ((1.0 - tx) * (d10 - d00) + tx * (d11 - d01))
     else:
         gx[inside] = sx * (D[ib] - D[ia])
-    grad[row_x, :n] = gx
-    if two:
-        grad[row_y, :n] = gy
+    if link is not None:
+        _chain_cpu(grad, n, dimension, row_x, row_y, gx, gy, link, counts)
+    else:
+        grad[row_x, :n] = gx
+        if two:
+            grad[row_y, :n] = gy
     e = e_hist + pen
     err[0], err[1], err[2] = e, 1.0, e
 
@@ -1413,7 +1502,8 @@ def spot_grid(domain, qbits):
 
 
 def spot_error(rows, row_x, row_y, group, n_groups, grid, oob_weight=0.0, mask=None, perm=None,
-               grad=None, err=None, acc=None, variant=0, workspace=None, qbits=None):
+               grad=None, err=None, acc=None, variant=0, workspace=None, qbits=None,
+               dimension=None):
     """tfrt_spot_error: the SpotError of the columns of ``rows`` (k, n), x in row ``row_x`` and y
     in row ``row_y`` (-1: one field).  ``group``: contiguous int32 labels, one per SOURCE ray;
     ``perm``: optional int32 (n,), the source ray of column i (None: column i is source ray i);
@@ -1423,6 +1513,11 @@ def spot_error(rows, row_x, row_y, group, n_groups, grid, oob_weight=0.0, mask=N
     int64 {count, Sx, Sy, 0}): rows ``row_x`` / ``row_y`` of ``grad`` are written for every column,
     other rows only when ``grad`` is made here (zeros).  ``grad``, ``err``, ``acc``, ``workspace``
     (uint8): buffers to reuse -- with all four given a CUDA call allocates nothing.
+
+    ``dimension`` 2 or 3 (tfrt_spot_error_fields): ``rows`` is the (2 * dimension, n) geometry
+    block and ``row_x`` / ``row_y`` are FIELD CODES, as for ``density_error``; with a direction
+    field all 2 * dimension rows of ``grad`` are written and the centroids are mean direction
+    cosines.
 
     CUDA tensors run the kernels.  CPU tensors run a torch restatement with the same int64 fixed
     point and the same operations per ray, each rounded on its own (``acc`` and the gradient rows
@@ -1434,6 +1529,8 @@ def spot_error(rows, row_x, row_y, group, n_groups, grid, oob_weight=0.0, mask=N
     if not 1 <= n_groups <= SPOT_MAX_GROUPS:
         raise ValueError(f"spot_error: n_groups must lie in 1 .. {SPOT_MAX_GROUPS}")
     k, n = rows.shape
+    if dimension is not None:
+        _check_field_codes("spot_error", rows, row_x, row_y, dimension)
     if perm is not None and (perm.dtype != torch.int32 or perm.numel() < n
                              or not perm.is_contiguous()):
         raise ValueError("spot_error: perm must be contiguous int32, one entry per column")
@@ -1442,6 +1539,8 @@ def spot_error(rows, row_x, row_y, group, n_groups, grid, oob_weight=0.0, mask=N
     dev = rows.device
     if grad is None:
         grad = torch.zeros((k, n), dtype=torch.float64, device=dev)
+    if dimension is not None and grad.shape[0] != k:
+        raise ValueError(f"spot_error: grad needs {k} rows")
     if err is None:
         err = torch.empty(3, dtype=torch.float64, device=dev)
     if acc is None:
@@ -1453,7 +1552,7 @@ def spot_error(rows, row_x, row_y, group, n_groups, grid, oob_weight=0.0, mask=N
         if not 1 <= qbits <= 52 or n >= 1 << (62 - qbits):
             raise ValueError("spot_error: qbits must lie in 1 .. 52 with n < 2^(62 - qbits)")
         _spot_error_cpu(rows, row_x, row_y, group, n_groups, grid, float(oob_weight), mask, perm,
-                        grad, err, acc, int(qbits))
+                        grad, err, acc, int(qbits), dimension)
         return err, grad, acc
     _need_gpu(rows, group, mask, perm, grad, err, acc)
     if rows.stride(1) != 1 or grad.stride(1) != 1:
@@ -1462,6 +1561,13 @@ def spot_error(rows, row_x, row_y, group, n_groups, grid, oob_weight=0.0, mask=N
     wsb = L.tfrt_spot_error_workspace_bytes(n, n_groups)
     if workspace is None:
         workspace = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    if dimension is not None:
+        check(L.tfrt_spot_error_fields(
+            _p(rows), rows.stride(0), n, _DT[rows.dtype], int(dimension), _p(mask), row_x, row_y,
+            _p(group), group.numel(), _p(perm), n_groups, x0, x1, qsx, y0, y1, qsy, int(qbits),
+            float(oob_weight), _p(grad), grad.stride(0), _p(err), _p(acc), int(variant),
+            _p(workspace), workspace.numel(), _stream(rows)), "tfrt_spot_error_fields")
+        return err, grad, acc
     check(L.tfrt_spot_error(
         _p(rows), rows.stride(0), n, _DT[rows.dtype], _p(mask), row_x, row_y, _p(group),
         group.numel(), _p(perm), n_groups, x0, x1, qsx, y0, y1, qsy, int(qbits),
@@ -1483,14 +1589,20 @@ def spot_centroids(acc, grid, fields=2):
 
 
 def _spot_error_cpu(rows, row_x, row_y, group, n_groups, grid, oob, mask, perm, grad, err, acc,
-                    qbits):
+                    qbits, dimension=None):
     """The CPU path of ``spot_error`` (every torch op rounds on its own, as the kernels do)."""
     x0, x1, qsx, y0, y1, qsy = grid
     two = row_y >= 0
     n = rows.shape[1]
     qmax = float(np.ldexp(1.0, qbits))
-    x = rows[row_x].double()
-    y = rows[row_y].double() if two else torch.zeros_like(x)
+    link = None
+    if dimension is not None and max(row_x, row_y) >= 2 * dimension:
+        link = _link_torch(rows, dimension)
+        x = _link_field_torch(link, row_x, dimension)
+        y = _link_field_torch(link, row_y, dimension) if two else torch.zeros_like(x)
+    else:
+        x = rows[row_x].double()
+        y = rows[row_y].double() if two else torch.zeros_like(x)
     counting = torch.ones(n, dtype=torch.bool) if mask is None else (mask[:n] >= 0)
     finite = torch.isfinite(x) & torch.isfinite(y)
     s = torch.arange(n, dtype=torch.int64) if perm is None else perm[:n].long()
@@ -1524,9 +1636,12 @@ def _spot_error_cpu(rows, row_x, row_y, group, n_groups, grid, oob, mask, perm, 
         dy = yi - (y0 + (acc[li, 2].double() / cnt) / qsy)
         gy[inside] = 2.0 * dy
         terms = terms + dy * dy
-    grad[row_x, :n] = gx
-    if two:
-        grad[row_y, :n] = gy
+    if link is not None:
+        _chain_cpu(grad, n, dimension, row_x, row_y, gx, gy, link, spot)
+    else:
+        grad[row_x, :n] = gx
+        if two:
+            grad[row_y, :n] = gy
     e = terms.sum() + pen
     n_terms = float(int(counting.sum()) * (2 if two else 1))
     err[0], err[1] = e, n_terms

@@ -13,6 +13,7 @@
 #include "tfrt_common.h"
 #include "goal_finish.h"
 #include "trace_math2d.h"
+#include "trace_filter2d.h"
 
 namespace tfrt {
 
@@ -113,104 +114,11 @@ __device__ __forceinline__ int nearest2d(const double s[2], const double e[2],
 }
 
 // ---------------------------------------------------------------------------------------
-// Filtered nearest hit (the trace kernels; the seams keep the plain loop above).
-//
-// As in 3-D, throughput and decisions are separated: every primitive gets a bounding circle
-// (segment: midpoint, half length; arc: the whole circle, or the circle on its chord when it
-// spans less than pi), every ray the unit normal n of its line and the offset s.n; the line can
-// touch the primitive only if (c.n - s.n)^2 <= r_eff^2 -- 6 float32 ops against ~60 float64 ops
-// (two atan2 for an arc) of the exact test.  Survivors (a handful out of hundreds) go to a
-// per-lane LDS queue and are decided exactly, in ascending primitive order, by a wave-uniform
-// flush.  Conservative: r_eff = r (1 + 1e-5) + 64 * 2^-24 (|c| + r), segments are extended by
-// size_eps at both ends (engine.py:722-724), and the reference's tangent snap `|rad| < eps -> 0`
-// (geometry.py:480-483), which lets a line MISS a circle of radius R by up to
-// d = eps R^3 / (8 |ray|^2), is covered by (r + d)^2 <= r^2 + 2 w R^4 + w^2 R^6, w = eps / (8 |ray|^2).
-constexpr int KQ2 = 16;  // queue slots per lane
-
-__device__ __forceinline__ float round_up2(double x) {
-  float f = static_cast<float>(x);
-  f = nextafterf(f, INFINITY);
-  return nextafterf(f, INFINITY);
-}
-
-// filter entry (cx, cy, r_eff^2, R^2) of a segment
-__device__ __forceinline__ float4 filter_segment(const double* g, double es) {
-  const double cx = 0.5 * (g[0] + g[2]), cy = 0.5 * (g[1] + g[3]);
-  const double len = sqrt((g[2] - g[0]) * (g[2] - g[0]) + (g[3] - g[1]) * (g[3] - g[1]));
-  double r = 0.5 * len + (es > 0.0 ? es * len : 0.0);
-  r = r * (1.0 + 1e-5) + 64.0 * 5.9604644775390625e-08 * (sqrt(cx * cx + cy * cy) + r);
-  if (!(r == r) || r > 1e18) return make_float4(0.f, 0.f, INFINITY, 0.f);  // always a candidate
-  return make_float4((float)cx, (float)cy, round_up2(r * r), 0.f);
-}
-
-__device__ __forceinline__ float4 filter_arc(const double* g) {
-  const double R = fabs(g[4]);
-  double span = g[3] - g[2];
-  if (span < 0.0) span += 2 * PI_D;  // angle_in_interval: geometry.py:790-802
-  double cx = g[0], cy = g[1], r = R;
-  const double h = 0.5 * span;
-  if (h < 0.5 * PI_D) {  // less than a half circle: the circle on the chord contains the arc
-    const double tm = g[2] + h;
-    cx += R * cos(h) * cos(tm);
-    cy += R * cos(h) * sin(tm);
-    r = R * sin(h) + 1e-9 * R;  // + slack for the rounding of cos / sin
-  }
-  r = r * (1.0 + 1e-5) + 64.0 * 5.9604644775390625e-08 * (sqrt(cx * cx + cy * cy) + r);
-  if (!(r == r) || !(R == R) || r > 1e18 || R > 1e9)
-    return make_float4(0.f, 0.f, INFINITY, 0.f);  // always a candidate
-  return make_float4((float)cx, (float)cy, round_up2(r * r), round_up2(R * R));
-}
-
-// Two levels (round 4): the primitives of a tile, in the caller's order, form clusters of G2 = 8
-// consecutive ones -- the segments of a polyline and the arcs of a lens array are neighbours in
-// the tables the reference builds (boundaries.py: one row per segment along the curve) -- under a
-// bounding circle of their bounding circles.  A lane first collects the clusters its line touches
-// (Ms / 8 + Ma / 8 tests instead of Ms + Ma), then tests the members of ITS clusters, cluster by
-// cluster in ascending order: primitives still reach the exact test in ascending index, so ties
-// fall as before.  A line that passes a member's circle passes the cluster's:
-// |t_C - t_m| <= |C - c_m|, hence |t_C| <= |C - c_m| + r_m + sqrt(s_m) <= R_C + q, with
-// s_m = R_m^4 (2 w + w^2 R_m^2) the arc's tangent-snap term and
-// q = Rq sqrt(w1) + Rq^1.5 sqrt(w2) >= sqrt(s_max)   (Rq = the largest R^2 of the cluster).
-// Measured on cfg5b (4M rays x 320 primitives, random rays): 5,340 -> VALU instructions per
-// wavefront, k_intersect2d 627 us per pass -> see DESIGN.md 5.
-constexpr int G2 = 8;                     // primitives per cluster
+// Filtered nearest hit (the trace kernels; the seams keep the plain loop above).  The filter's
+// arithmetic -- the bounding circles of primitives and clusters, the ray's float32 state and
+// the two predicates, with their derivation -- is trace_filter2d.h; here are the tiling, the LDS
+// staging, the per-lane queues and the wave-uniform flushes around it.
 constexpr int NC2 = TILE2 / G2;           // clusters per tile
-
-// bounding circle (cx, cy, R, Rq) and Rq^1.5 of the filter entries f[0..G2) (z < 0: padding)
-__device__ __forceinline__ float4 cluster_filter(const float4* f, float* rq15) {
-  float sx = 0.f, sy = 0.f, rq = 0.f;
-  int m = 0;
-  bool always = false;
-#pragma unroll
-  for (int g = 0; g < G2; ++g) {
-    const float4 v = f[g];
-    if (v.z < 0.f) continue;
-    always = always || !(v.z < INFINITY);
-    sx += v.x;
-    sy += v.y;
-    rq = fmaxf(rq, v.w);
-    ++m;
-  }
-  *rq15 = 0.f;
-  if (m == 0) return make_float4(0.f, 0.f, -1.f, 0.f);          // never touched
-  if (always || !(rq < 1e30f)) return make_float4(0.f, 0.f, INFINITY, 0.f);  // always a candidate
-  const float cx = sx / (float)m, cy = sy / (float)m;
-  float R = 0.f;
-#pragma unroll
-  for (int g = 0; g < G2; ++g) {
-    const float4 v = f[g];
-    if (v.z < 0.f) continue;
-    const float dx = v.x - cx, dy = v.y - cy;
-    const float d = sqrtf(dx * dx + dy * dy) * (1.f + 1e-6f);
-    const float r = sqrtf(v.z) * (1.f + 1e-6f);
-    R = fmaxf(R, d + r);
-  }
-  // (the same allowance for the float32 evaluation of the line's offset as the members have)
-  R = R * (1.f + 1e-5f) + 64.f * 5.9604644775390625e-08f * (sqrtf(cx * cx + cy * cy) + R);
-  if (!(R < INFINITY)) return make_float4(0.f, 0.f, INFINITY, 0.f);
-  *rq15 = rq * sqrtf(rq) * (1.f + 1e-6f);
-  return make_float4(cx, cy, R, rq);
-}
 
 template <int STATE_BITS>
 __device__ __forceinline__ int nearest2d_filtered(const double s[2], const double e[2],
@@ -220,34 +128,8 @@ __device__ __forceinline__ int nearest2d_filtered(const double s[2], const doubl
                                                   double* lds, float4* filt, int32_t* queue,
                                                   float4* cfilt, float* crq15, uint8_t* cqueue,
                                                   bool active, double* out_u, double* out_aux) {
-  // float32 state of this lane's ray
-  // sn = NaN: a lane without a (valid) ray never passes the test, whatever the radius
-  float nx = 0.f, ny = 0.f, sn = __builtin_nanf(""), w1 = 0.f, w2 = 0.f, k1 = 0.f, kw = 0.f;
-  {
-    const double dx = e[0] - s[0], dy = e[1] - s[1];
-    const double l2 = dx * dx + dy * dy;
-    if (active && l2 > 0.0 && l2 < INFINITY) {
-      const double inv = 1.0 / sqrt(l2);
-      const double ux = -dy * inv, uy = dx * inv;
-      nx = (float)ux;
-      ny = (float)uy;
-      sn = (float)(s[0] * ux + s[1] * uy);
-      const double w = (ei > 0.0 ? ei : 0.0) / (8.0 * l2);
-      w1 = round_up2(2.0 * w * (1.0 + 1e-5));
-      w2 = round_up2(w * w * (1.0 + 1e-5));
-      k1 = round_up2(sqrt((double)w1) * (1.0 + 1e-6));
-      kw = round_up2(sqrt((double)w2) * (1.0 + 1e-6));
-    }
-  }
-  auto touches = [&](const float4 f) {
-    const float t = fmaf(f.x, nx, fmaf(f.y, ny, -sn));
-    const float lim = fmaf(f.w * f.w, fmaf(w2, f.w, w1), f.z);
-    return t * t <= lim;
-  };
-  auto touches_cluster = [&](const float4 c, const float rq15) {
-    const float t = fmaf(c.x, nx, fmaf(c.y, ny, -sn));
-    return fabsf(t) <= c.z + fmaf(c.w, k1, rq15 * kw);
-  };
+  // float32 state of this lane's ray (a lane without a valid ray never passes the test)
+  const RayFilter2 rf = ray_filter2(s, e, ei, active);
   const int tid = threadIdx.x;
   int cnt = 0;
   double su = INFINITY, au = INFINITY, aang = 0.0;
@@ -264,7 +146,7 @@ __device__ __forceinline__ int nearest2d_filtered(const double s[2], const doubl
     int cc = 0;
     for (int c = 0; c < nc; ++c) {
       cqueue[cc * BLOCK + tid] = (uint8_t)c;
-      cc += touches_cluster(cfilt[c], crq15[c]) ? 1 : 0;
+      cc += touches_cluster(rf, cfilt[c], crq15[c]) ? 1 : 0;
     }
     return cc;
   };
@@ -276,7 +158,7 @@ __device__ __forceinline__ int nearest2d_filtered(const double s[2], const doubl
     for (int k = tid; k < nt * 4; k += BLOCK) lds[k] = seg[(int64_t)t0 * 4 + k];
     __syncthreads();
     for (int k = tid; k < nt8; k += BLOCK)
-      filt[k] = k < nt ? filter_segment(lds + 4 * k, es) : make_float4(0.f, 0.f, -1.f, 0.f);
+      filt[k] = k < nt ? filter_segment(lds + 4 * k, es) : filter_padding();
     __syncthreads();
     const int nc = build_clusters(nt);
     __syncthreads();
@@ -299,7 +181,7 @@ __device__ __forceinline__ int nearest2d_filtered(const double s[2], const doubl
 #pragma unroll
         for (int g = 0; g < G2; ++g) {
           queue[cnt * BLOCK + tid] = j0 + g;
-          cnt += touches(filt[j0 + g]) ? 1 : 0;
+          cnt += touches(rf, filt[j0 + g]) ? 1 : 0;
         }
       }
       if (__any(cnt > KQ2 - G2)) flush();
@@ -313,7 +195,7 @@ __device__ __forceinline__ int nearest2d_filtered(const double s[2], const doubl
     for (int k = tid; k < nt * 5; k += BLOCK) lds[k] = arc[(int64_t)t0 * 5 + k];
     __syncthreads();
     for (int k = tid; k < nt8; k += BLOCK)
-      filt[k] = k < nt ? filter_arc(lds + 5 * k) : make_float4(0.f, 0.f, -1.f, 0.f);
+      filt[k] = k < nt ? filter_arc(lds + 5 * k) : filter_padding();
     __syncthreads();
     const int nc = build_clusters(nt);
     __syncthreads();
@@ -344,7 +226,7 @@ __device__ __forceinline__ int nearest2d_filtered(const double s[2], const doubl
 #pragma unroll
         for (int g = 0; g < G2; ++g) {
           queue[cnt * BLOCK + tid] = j0 + g;
-          cnt += touches(filt[j0 + g]) ? 1 : 0;
+          cnt += touches(rf, filt[j0 + g]) ? 1 : 0;
         }
       }
       if (__any(cnt > KQ2 - G2)) flush();

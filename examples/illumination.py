@@ -20,7 +20,12 @@ and an upload at every step, which the optimiser cannot capture.
 bins per axis -- no transport map is needed, and rays that are lost or stopped simply do not count.
 ``--generic`` forces the generic path (``fused=False``) for comparison.
 
-    python examples/illumination.py --density-error [--bins 64] [--generic]
+``--lambertian-weights`` (with ``--density-error``) treats the start plane as a Lambertian emitter:
+the aperture source samples its rays evenly over the lens, and every ray carries ``cos theta`` of
+its start direction to the emitter's normal as its radiant power -- the ``weights`` of the
+``DensityError``, a callable on the source's fields, evaluated again whenever the rays are re-drawn.
+
+    python examples/illumination.py --density-error [--bins 64] [--generic] [--lambertian-weights]
 """
 import argparse
 import os
@@ -64,9 +69,16 @@ def even_square(size, domain_size, bins):
     return inside[:, None] * inside[None, :]
 
 
+def lambertian(src):
+    """cos theta of a source ray's start direction to the emitter's normal (1, 0, 0): the weights
+    of ``--lambertian-weights``, a callable on the source's field dict."""
+    d = [src[a + "_end"].double() - src[a + "_start"].double() for a in "xyz"]
+    return d[0].abs() / torch.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+
+
 def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, magnification=1.0,
           object_size=0.2, lens_aperature=1.0, rowwise=True, density_error=False, bins=64,
-          **engine_kw):
+          lambertian_weights=False, **engine_kw):
     limits = ((-object_size, object_size, DENSITY_CELLS), (-object_size, object_size, DENSITY_CELLS))
     start_density = distributions.ArbitraryDistribution(two_bumps(object_size), limits)
     goal_density = distributions.ArbitraryDistribution(lambda gx, gy: np.ones_like(gx), limits)
@@ -119,7 +131,8 @@ def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, magnificat
         half = 1.25 * size
         error_function = optimizer.DensityError(
             ("y_end", "z_end"), even_square(size, half, bins), ((-half, half), (-half, half)),
-            oob_weight=1.0 / (ray_count * size ** 2))
+            oob_weight=1.0 / (ray_count * size ** 2),
+            weights=lambertian if lambertian_weights else None)
     else:
         error_function = optimizer.GoalError(("y_end", "z_end"), lambda s: -m * s["goal"],
                                              rowwise=rowwise)
@@ -128,10 +141,13 @@ def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, magnificat
 
 
 def run(ray_count=20000, steps=30, lens_res_scale=0.12, host=False, verbose=True,
-        density_error=False, bins=64, generic=False, splat_variant=0):
+        density_error=False, bins=64, generic=False, splat_variant=0, lambertian_weights=False):
+    if lambertian_weights and not density_error:
+        raise ValueError("--lambertian-weights weighs a DensityError: it needs --density-error")
     distributions.set_device_random(not host)
     try:
-        s = build(ray_count, lens_res_scale, density_error=density_error, bins=bins)
+        s = build(ray_count, lens_res_scale, density_error=density_error, bins=bins,
+                  lambertian_weights=lambertian_weights)
         if density_error:
             s["error_function"].splat_variant = splat_variant
         # (a DensityError is one term of order 1, not a sum over the rays: its own step size)
@@ -171,9 +187,12 @@ if __name__ == "__main__":
     ap.add_argument("--generic", action="store_true", help="the generic path (fused=False)")
     ap.add_argument("--splat-variant", type=int, default=0, choices=(0, 1, 2),
                     help="tfrt_density_error's splat: 0 by the bin count, 1 LDS histogram, 2 global atomics")
+    ap.add_argument("--lambertian-weights", action="store_true",
+                    help="with --density-error: every ray carries cos theta of its start direction")
     a = ap.parse_args()
     out = run(a.rays, a.steps, a.edge, host=a.host, density_error=a.density_error, bins=a.bins,
-              generic=a.generic, splat_variant=a.splat_variant)
+              generic=a.generic, splat_variant=a.splat_variant,
+              lambertian_weights=a.lambertian_weights)
     tail = sorted(out["times"][len(out["times"]) // 2:])
     print(f"source on the device: {out['device_source']}; steps replayed from the graph: "
           f"{out['graph_replays']} of {a.steps}; median step of the second half: "

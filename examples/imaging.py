@@ -17,7 +17,13 @@ The directions are re-drawn at every step; the labels stay (ray i is object poin
 once the engine traces the source in place; ``--generic`` keeps the generic path (the same
 kernels under torch.autograd).
 
-    python examples/imaging.py [--rays 20000] [--steps 30] [--generic] [--adam]
+``--apodize SIGMA`` weighs the rays by a Gaussian pupil: a ray that leaves its object point at the
+angle theta to the axis carries ``exp(-(sin theta / (SIGMA * sin cone))**2 / 2)`` -- ``SIGMA`` in
+units of the cone that fills the lens --, given to the ``SpotError`` as a callable on the source's
+fields (the directions are re-drawn at every step, so are the weights).  The spot is then the
+weighted one: centroid, RMS size and gradient.
+
+    python examples/imaging.py [--rays 20000] [--steps 30] [--generic] [--adam] [--apodize SIGMA]
 """
 import argparse
 import math
@@ -54,8 +60,19 @@ def letter_f(size=0.2):
     return np.concatenate([np.zeros((yz.shape[0], 1)), yz], axis=1)
 
 
+def gaussian_pupil(sigma, cone):
+    """The weights of ``--apodize``: a callable on the source's field dict."""
+    scale = sigma * math.sin(cone)
+
+    def weights(src):
+        d = [src[a + "_end"].double() - src[a + "_start"].double() for a in "xyz"]
+        sin2 = (d[1] * d[1] + d[2] * d[2]) / (d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+        return torch.exp(-0.5 * sin2 / (scale * scale))
+    return weights
+
+
 def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, target_distance=10.0,
-          object_size=0.2, lens_aperature=1.0):
+          object_size=0.2, lens_aperature=1.0, apodize=None):
     points = letter_f(object_size)
     P = points.shape[0]
     A = max(ray_count // P, 2)
@@ -100,14 +117,14 @@ def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, target_dis
     # a ray that leaves the target region is pulled back instead of dragging its spot along
     error_function = optimizer.SpotError(
         ("y_end", "z_end"), labels, ((-HALF_DOMAIN, HALF_DOMAIN), (-HALF_DOMAIN, HALF_DOMAIN)),
-        oob_weight=1.0)
+        oob_weight=1.0, weights=None if apodize is None else gaussian_pupil(apodize, cone))
     return dict(engine=trace_engine, system=system, lens=lens, source=source, n_rays=n_rays,
                 n_points=P, error_function=error_function, accumulator=accumulator)
 
 
 def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=False, verbose=True,
-        learning_rate=None):
-    s = build(ray_count, lens_res_scale)
+        learning_rate=None, apodize=None):
+    s = build(ray_count, lens_res_scale, apodize=apodize)
     erf = s["error_function"]
     if learning_rate is None:
         # (the error is a sum over the rays: the step size goes with 1 / rays)
@@ -126,9 +143,14 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=Fals
         mean = float(opt.single_step(s["accumulator"] if step < steps // 2 else None))
         torch.cuda.synchronize()
         times.append(time.perf_counter() - t0)
-        inside = int(erf.last_acc[:, 0].sum())
+        if apodize is None:
+            inside = light = int(erf.last_acc[:, 0].sum())
+        else:
+            # (weighted records: W = sum wq in units of 2^-wbits, the ray count in slot 5)
+            inside = int(erf.last_acc[:, 5].sum())
+            light = math.ldexp(int(erf.last_acc[:, 0].sum()), -erf.graph_key()[-1])
         error_sum = mean * float(opt.last_error_terms)
-        rms.append(math.sqrt(error_sum / inside) if inside else float("nan"))
+        rms.append(math.sqrt(error_sum / light) if inside else float("nan"))
         if verbose and (step % 5 == 0 or step == steps - 1):
             print(f"step {step:4d}: rms spot {rms[-1]:.6g}  ({inside} rays inside, "
                   f"{1e3 * times[-1]:.2f} ms)")
@@ -147,8 +169,11 @@ if __name__ == "__main__":
     ap.add_argument("--adam", action="store_true", help="an Adam_Optimizer instead of plain SGD")
     ap.add_argument("--lr", type=float, default=None,
                     help=f"learning rate (default {LEARNING_RATE} * 20000 / rays)")
+    ap.add_argument("--apodize", type=float, default=None, metavar="SIGMA",
+                    help="Gaussian pupil weights, SIGMA in units of the cone that fills the lens")
     a = ap.parse_args()
-    out = run(a.rays, a.steps, a.edge, generic=a.generic, adam=a.adam, learning_rate=a.lr)
+    out = run(a.rays, a.steps, a.edge, generic=a.generic, adam=a.adam, learning_rate=a.lr,
+              apodize=a.apodize)
     tail = sorted(out["times"][len(out["times"]) // 2:])
     print(f"{out['n_points']} object points, {out['n_rays']} rays; steps replayed from the graph: "
           f"{out['graph_replays']} of {a.steps}; median step of the second half: "

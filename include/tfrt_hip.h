@@ -711,6 +711,86 @@ int tfrt_spot_error_fields(const void* rows, int64_t stride, int64_t n, int32_t 
                            double* grad, int64_t grad_stride, double* error_out, int64_t* acc,
                            int32_t variant, void* workspace, size_t workspace_bytes, void* stream);
 
+/* tfrt_density_error_fields with a radiant power per SOURCE ray (a Lambertian emitter sampled
+ * uniformly in angle, a spectrum, an apodised pupil, a measured ray file): `weight` holds n_source
+ * f64 in [0, 1] -- only ratios matter, the caller divides by the maximum.  The same four launches
+ * and the same workspace (tfrt_density_error_workspace_bytes), no host read, no allocation.
+ *
+ * For a counting column i -- after the case "a coordinate is non-finite", before the domain test --
+ *   s = perm ? perm[i] : i;  s outside [0, n_source), or w = weight[s] not finite or not in [0, 1]:
+ *     the column does not count: no error, gradient 0 (nothing is read out of bounds, whatever
+ *     perm holds).
+ * Otherwise everything is tfrt_density_error_fields' with, every operation an IEEE f64 operation
+ * rounded on its own:
+ *   inside: a bilinear weight b (bx * by; bx with one field) enters its bin as the integer
+ *     rint((b * w) * 2^32), half to even (w <= 1: the int64 bins overflow no sooner); the gradient
+ *     gv_k is the unweighted expression multiplied by w last;
+ *   outside: the penalty oob_weight * (ex^2 + ey^2) and its gradient, each multiplied by w last.
+ * s, E_hist and the pulls come from the weighted histogram exactly as in tfrt_density_error.  With
+ * a direction field gv_k carries w when it enters the chain rule.  On return the first nx * ny f64
+ * of `workspace` hold the pulls D_b (row-major, as `goal`): what a ray made of them can be checked
+ * bit for bit, although their own sums over the bins are only reproducible, not portable.
+ *
+ *   weight      n_source f64, one per SOURCE ray; NULL: TFRT_E_BADARG
+ *   n_source    0 <= n_source < 2^31
+ *   perm        n int32, the source ray of column i; or NULL: column i is source ray i
+ * Everything else as for tfrt_density_error_fields.
+ */
+int tfrt_density_error_weighted(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                                int32_t dimension, const int32_t* mask, int32_t field_x,
+                                int32_t field_y, const double* goal, const double* weight,
+                                int64_t n_source, const int32_t* perm, int32_t nx, int32_t ny,
+                                double x0, double x1, double sx, double y0, double y1, double sy,
+                                double oob_weight, double* grad, int64_t grad_stride,
+                                double* error_out, int64_t* hq, int32_t splat_variant,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
+/* tfrt_spot_error_fields with a radiant power per SOURCE ray: the centroid of a group is the
+ * WEIGHTED mean of its rays and the error the weighted sum of squared distances to it.  `weight`
+ * holds n_source f64 in [0, 1] (only ratios matter, the caller divides by the maximum).  The same
+ * four launches, no host read, no allocation.
+ *
+ * The four cases of tfrt_spot_error, with the second one wider.  For a counting column with finite
+ * coordinates, s = perm ? perm[i] : i:
+ *   no spot: s outside [0, n_source); or w = weight[s] not finite or not in [0, 1]; or
+ *     wq = rint(w * 2^wbits) (half to even) == 0; or the label group[s] outside [0, n_groups): no
+ *     error, gradient 0.  The weight is read once, behind the index check the label needs.
+ * wr = (double) wq * 2^-wbits is exact, and it is the weight used everywhere below: the weighted
+ * residuals of a group sum to zero in the quantised quantities.  Every operation an IEEE f64
+ * operation rounded on its own:
+ *   outside the closed domain: the penalty oob_weight * (ex^2 + ey^2) and its gradient, each
+ *     multiplied by wr last;
+ *   inside: qx as in tfrt_spot_error; with h = qbits / 2 (rounded down) the product wq * qx goes
+ *     into two limbs, so that a position keeps its full qbits: Xhi += wq * (qx >> h),
+ *     Xlo += wq * (qx & (2^h - 1)); Yhi, Ylo alike; W += wq; count += 1 (64-bit integer atomics).
+ * Every sum stays below n * 2^wbits * 2^ceil(qbits / 2): n >= 2^(62 - wbits - ceil(qbits / 2)) is
+ * refused (the bound n < 2^(62 - qbits) of tfrt_spot_error is not asked for here).  A group with
+ * W > 0 has
+ *   X = ldexp((double) Xhi, h) + (double) Xlo,   cx = x0 + (X / (double) W) / qsx,   cy alike.
+ * An inside ray has dx = x - cx, the terms wr * (dx * dx) and wr * (dy * dy) (added in that order)
+ * and the gradient rows (2 * dx) * wr and (2 * dy) * wr.  error_out stays
+ * {error, k * counting columns, error / terms}.
+ *
+ *   weight      n_source f64, one per SOURCE ray; NULL: TFRT_E_BADARG
+ *   wbits       1..20; the caller uses min(20, 62 - bit_length(n_source) - ceil(qbits / 2))
+ *   acc         n_groups records of eight int64 {W, Xhi, Xlo, Yhi, Ylo, count, 0, 0} (64 B: the
+ *               adds of one ray fall into one line), cleared and filled by this call
+ *   variant     0: a per-workgroup table in LDS (six planes of G int64) up to 512 groups -- the
+ *               24 KiB of tfrt_spot_error's table at 1,024 --, global 64-bit atomics above; 1 / 2
+ *               force one of them (1 with more than 512 groups: TFRT_E_BADARG)
+ *   workspace   tfrt_spot_error_weighted_workspace_bytes(n, n_groups) bytes (0: bad arguments)
+ * Everything else as for tfrt_spot_error_fields.
+ */
+size_t tfrt_spot_error_weighted_workspace_bytes(int64_t n, int32_t n_groups);
+int tfrt_spot_error_weighted(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                             int32_t dimension, const int32_t* mask, int32_t field_x,
+                             int32_t field_y, const int32_t* group, const double* weight,
+                             int32_t wbits, int64_t n_source, const int32_t* perm,
+                             int32_t n_groups, double x0, double x1, double qsx, double y0,
+                             double y1, double qsy, int32_t qbits, double oob_weight, double* grad,
+                             int64_t grad_stride, double* error_out, int64_t* acc, int32_t variant,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* tfrt_goal_error3d_deferred and tfrt_trace3d_backward in ONE launch, for a trace over coherent
  * rays (tfrt_scene3d.coherent_rays, not deterministic, max_passes <= 8; TFRT_E_UNSUPPORTED
  * otherwise -- call the two entry points instead): the lane that walks a finished ray's chain of

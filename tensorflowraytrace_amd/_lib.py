@@ -209,6 +209,17 @@ SIGNATURES = {
         c_vp, c_i64, c_vp, c_i32,
         c_f64, c_f64, c_f64, c_f64, c_f64, c_f64, c_i32, c_f64,
         c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]),
+    "tfrt_density_error_weighted": (c_i32, [
+        c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp,           # ... goal
+        c_vp, c_i64, c_vp, c_i32, c_i32,                                      # weight, perm, nx, ny
+        c_f64, c_f64, c_f64, c_f64, c_f64, c_f64, c_f64,
+        c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]),
+    "tfrt_spot_error_weighted_workspace_bytes": (c_sz, [c_i64, c_i32]),
+    "tfrt_spot_error_weighted": (c_i32, [
+        c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_i32, c_i32,
+        c_vp, c_vp, c_i32, c_i64, c_vp, c_i32,                                # group, weight, wbits
+        c_f64, c_f64, c_f64, c_f64, c_f64, c_f64, c_i32, c_f64,
+        c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]),
     "tfrt_trace3d_backward_goal_workspace_bytes": (c_sz, [c_i64]),
     "tfrt_trace3d_backward_goal": (c_i32, [
         c_vp, c_i64, c_i64, c_vp, c_f64, c_f64, c_i32, c_i32,          # rays, scene, lengths, P, dtype

@@ -40,6 +40,13 @@
 // The penalty is summed where the rays are first classified (the splat) and finished by the one
 // workgroup that runs anyway (the bins): a sum formed by the seed would need a fourth, dependent
 // launch (~4.5 us) or a "last workgroup finishes" fence (what that costs: tfrt_error.hip).
+//
+// Weighted (tfrt_density_error_weighted): every source ray carries a radiant power w in [0, 1],
+// looked up once per column through `perm`; a bilinear weight enters its bin as
+// rint((b * w) * 2^32), gradient and penalty are multiplied by w last, and the bins launch is the
+// unweighted one on the weighted histogram.  The splat and the seed are sibling kernels
+// (k_density_splat_weighted, k_density_seed_weighted) with the weights as one more argument; the
+// unweighted kernels are untouched.
 #include "tfrt_common.h"
 #include "direction_fields.h"
 
@@ -55,6 +62,14 @@ constexpr int BINS_WAVES = BINS_BLOCK / 64;
 struct DensityGrid {
   double x0, x1, sx, y0, y1, sy, oob;
   int32_t nx, ny, row_x, row_y;   // row_x, row_y: field codes (direction_fields.h)
+};
+
+// The weights of tfrt_density_error_weighted: one f64 in [0, 1] per SOURCE ray; column i is
+// source ray perm[i] (perm null: i).
+struct DensityWeights {
+  const double* weight;
+  const int32_t* perm;
+  int64_t n_source;
 };
 
 // What one column does.  kind 0: does not count (masked, or a non-finite coordinate); 1: inside
@@ -106,6 +121,26 @@ __device__ __forceinline__ DensityRay density_classify(const T* __restrict__ row
   r.kind = 1;
   density_axis(x, g.x0, g.sx, g.nx, r.ia, r.ib, r.tx);
   if (two) density_axis(y, g.y0, g.sy, g.ny, r.ja, r.jb, r.ty);
+  return r;
+}
+
+// The same for tfrt_density_error_weighted: a column that counts (kinds 1 and 2) without a source
+// ray or with a weight outside [0, 1] does not count (kind 0 -- "does not count" ends alike
+// wherever it is found, so the order of the checks does not show).  Nothing is read out of bounds,
+// whatever perm holds.
+template <typename T, int DIM>
+__device__ __forceinline__ DensityRay density_classify_weighted(
+    const T* __restrict__ rows, int64_t stride, const int32_t* __restrict__ mask, int64_t i,
+    const DensityGrid& g, const DensityWeights& wt, LinkDir<DIM>& link, double& w) {
+  DensityRay r = density_classify<T, DIM>(rows, stride, mask, i, g, link);
+  w = 0.0;
+  if (r.kind != 0) {
+    const int64_t s = wt.perm != nullptr ? (int64_t)wt.perm[i] : i;
+    const bool has = s >= 0 && s < wt.n_source;
+    // (a NaN fails both comparisons)
+    if (has) w = wt.weight[s];
+    if (!has || !(w >= 0.0 && w <= 1.0)) r.kind = 0;
+  }
   return r;
 }
 
@@ -168,6 +203,54 @@ __global__ __launch_bounds__(BLOCK) void k_density_splat(
       } else {
         atomicAdd(&dst[r.ia], density_fixed(wx0));
         atomicAdd(&dst[r.ib], density_fixed(wx1));
+      }
+    }
+  }
+  if (LDS) {
+    __syncthreads();
+    for (int b = threadIdx.x; b < bins; b += BLOCK) {
+      const unsigned long long v = hist[b];
+      if (v != 0ull) atomicAdd(&hq[b], v);
+    }
+  }
+  const double s = density_block_sum<WAVES>(pen, wsum);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// tfrt_density_error_weighted's splat: every bilinear weight and the penalty times w last.
+template <typename T, bool LDS, int DIM>
+__global__ __launch_bounds__(BLOCK) void k_density_splat_weighted(
+    const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
+    DensityGrid g, DensityWeights wt, unsigned long long* __restrict__ hq,
+    double* __restrict__ partial) {
+#pragma clang fp contract(off)
+  extern __shared__ unsigned long long hist[];
+  __shared__ double wsum[WAVES];
+  const int bins = g.nx * g.ny;
+  if (LDS) {
+    for (int b = threadIdx.x; b < bins; b += BLOCK) hist[b] = 0ull;
+    __syncthreads();
+  }
+  unsigned long long* dst = LDS ? hist : hq;
+  double pen = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * BLOCK) {
+    LinkDir<DIM> link;
+    double w;
+    const DensityRay r = density_classify_weighted<T, DIM>(rows, stride, mask, i, g, wt, link, w);
+    if (r.kind == 2) {
+      pen += (g.oob * (r.tx * r.tx + r.ty * r.ty)) * w;
+    } else if (r.kind == 1) {
+      const double wx0 = 1.0 - r.tx, wx1 = r.tx;
+      if (g.row_y >= 0) {
+        const double wy0 = 1.0 - r.ty, wy1 = r.ty;
+        atomicAdd(&dst[r.ja * g.nx + r.ia], density_fixed((wy0 * wx0) * w));
+        atomicAdd(&dst[r.ja * g.nx + r.ib], density_fixed((wy0 * wx1) * w));
+        atomicAdd(&dst[r.jb * g.nx + r.ia], density_fixed((wy1 * wx0) * w));
+        atomicAdd(&dst[r.jb * g.nx + r.ib], density_fixed((wy1 * wx1) * w));
+      } else {
+        atomicAdd(&dst[r.ia], density_fixed(wx0 * w));
+        atomicAdd(&dst[r.ib], density_fixed(wx1 * w));
       }
     }
   }
@@ -267,6 +350,41 @@ __global__ __launch_bounds__(BLOCK) void k_density_seed(
   }
 }
 
+// tfrt_density_error_weighted's seed: gx, gy times w last, in front of the chain rule.
+template <typename T, int DIM>
+__global__ __launch_bounds__(BLOCK) void k_density_seed_weighted(
+    const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
+    DensityGrid g, DensityWeights wt, const double* __restrict__ pull, double* __restrict__ grad,
+    int64_t grad_stride) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  LinkDir<DIM> link;
+  double w;
+  const DensityRay r = density_classify_weighted<T, DIM>(rows, stride, mask, i, g, wt, link, w);
+  const bool two = g.row_y >= 0;
+  double gx = 0.0, gy = 0.0;
+  if (r.kind == 2) {
+    gx = (g.oob * (2.0 * r.tx) * r.dx) * w;
+    gy = (g.oob * (2.0 * r.ty) * r.dy) * w;
+  } else if (r.kind == 1) {
+    if (two) {
+      const double d00 = pull[r.ja * g.nx + r.ia], d01 = pull[r.ja * g.nx + r.ib];
+      const double d10 = pull[r.jb * g.nx + r.ia], d11 = pull[r.jb * g.nx + r.ib];
+      gx = (g.sx * ((1.0 - r.ty) * (d01 - d00) + r.ty * (d11 - d10))) * w;
+      gy = (g.sy * ((1.0 - r.tx) * (d10 - d00) + r.tx * (d11 - d01))) * w;
+    } else {
+      gx = (g.sx * (pull[r.ib] - pull[r.ia])) * w;
+    }
+  }
+  if constexpr (DIM != 0) {
+    chain_fields<DIM>(link, r.kind != 0, g.row_x, g.row_y, gx, gy, grad, grad_stride, i);
+  } else {
+    grad[(int64_t)g.row_x * grad_stride + i] = gx;
+    if (two) grad[(int64_t)g.row_y * grad_stride + i] = gy;
+  }
+}
+
 static int density_grid(int64_t n) {
   if (n <= 0) return 0;
   const int64_t want = (n + DENSITY_RAYS_PER_BLOCK - 1) / DENSITY_RAYS_PER_BLOCK;
@@ -279,14 +397,24 @@ using namespace tfrt;
 
 extern "C" size_t tfrt_density_error_workspace_bytes(int64_t n, int32_t nx, int32_t ny);
 
-// The launches of both entries.  `dim` and the codes have been checked by the caller.
+// The launches of every entry (`wt` null: unweighted).  `dim` and the codes have been checked by
+// the caller.
 template <typename T, int DIM>
 static void density_launch(const T* r, int64_t stride, int64_t n, const int32_t* mask,
-                           const DensityGrid& g, bool lds, int bins, int grid, int nblk,
+                           const DensityGrid& g, const DensityWeights* wt, bool lds, int bins,
+                           int grid, int nblk,
                            unsigned long long* hqu, const double* goal, double* pull,
                            double* partial, double* grad, int64_t grad_stride, double* error_out,
                            hipStream_t st) {
-  if (grid > 0) {
+  if (grid > 0 && wt != nullptr) {
+    if (lds)
+      hipLaunchKernelGGL((k_density_splat_weighted<T, true, DIM>), dim3(grid), dim3(BLOCK),
+                         (size_t)bins * sizeof(unsigned long long), st, r, stride, n, mask, g, *wt,
+                         hqu, partial);
+    else
+      hipLaunchKernelGGL((k_density_splat_weighted<T, false, DIM>), dim3(grid), dim3(BLOCK), 0, st,
+                         r, stride, n, mask, g, *wt, hqu, partial);
+  } else if (grid > 0) {
     if (lds)
       hipLaunchKernelGGL((k_density_splat<T, true, DIM>), dim3(grid), dim3(BLOCK),
                          (size_t)bins * sizeof(unsigned long long), st, r, stride, n, mask, g, hqu,
@@ -298,19 +426,23 @@ static void density_launch(const T* r, int64_t stride, int64_t n, const int32_t*
   hipLaunchKernelGGL(k_density_bins, dim3(1), dim3(BINS_BLOCK), 0, st,
                      reinterpret_cast<const long long*>(hqu), goal, bins, partial, grid, pull,
                      error_out);
-  if (nblk > 0)
+  if (nblk > 0 && wt != nullptr)
+    hipLaunchKernelGGL((k_density_seed_weighted<T, DIM>), dim3(nblk), dim3(BLOCK), 0, st, r,
+                       stride, n, mask, g, *wt, pull, grad, grad_stride);
+  else if (nblk > 0)
     hipLaunchKernelGGL((k_density_seed<T, DIM>), dim3(nblk), dim3(BLOCK), 0, st, r, stride, n,
                        mask, g, pull, grad, grad_stride);
 }
 
-// Both entries behind their own checks of the rows / codes: `dim` 2 or 3, codes below 3 * dim.
+// Every entry behind its own checks of the rows / codes: `dim` 2 or 3, codes below 3 * dim.
+// `wt` null: unweighted.
 static int density_error_run(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
                              int32_t dim, const int32_t* mask, int32_t row_x, int32_t row_y,
                              const double* goal, int32_t nx, int32_t ny, double x0, double x1,
                              double sx, double y0, double y1, double sy, double oob_weight,
                              double* grad, int64_t grad_stride, double* error_out, int64_t* hq,
                              int32_t splat_variant, void* workspace, size_t workspace_bytes,
-                             void* stream) {
+                             void* stream, const DensityWeights* wt = nullptr) {
   if (n < 0 || n > INT32_MAX || nx < 1 || ny < 1 || (int64_t)nx * ny > DENSITY_MAX_BINS ||
       row_x == row_y || !goal || !error_out || !hq || !workspace || (row_y < 0 && ny != 1) ||
       splat_variant < 0 || splat_variant > 2)
@@ -345,14 +477,14 @@ static int density_error_run(const void* rows, int64_t stride, int64_t n, int32_
     using T = typename decltype(tag)::type;
     const T* r = static_cast<const T*>(rows);
     if (!dir)
-      density_launch<T, 0>(r, stride, n, mask, g, lds, bins, grid, nblk, hqu, goal, pull, partial,
-                           grad, grad_stride, error_out, st);
+      density_launch<T, 0>(r, stride, n, mask, g, wt, lds, bins, grid, nblk, hqu, goal, pull,
+                           partial, grad, grad_stride, error_out, st);
     else if (dim == 3)
-      density_launch<T, 3>(r, stride, n, mask, g, lds, bins, grid, nblk, hqu, goal, pull, partial,
-                           grad, grad_stride, error_out, st);
+      density_launch<T, 3>(r, stride, n, mask, g, wt, lds, bins, grid, nblk, hqu, goal, pull,
+                           partial, grad, grad_stride, error_out, st);
     else
-      density_launch<T, 2>(r, stride, n, mask, g, lds, bins, grid, nblk, hqu, goal, pull, partial,
-                           grad, grad_stride, error_out, st);
+      density_launch<T, 2>(r, stride, n, mask, g, wt, lds, bins, grid, nblk, hqu, goal, pull,
+                           partial, grad, grad_stride, error_out, st);
     return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
   });
 }
@@ -389,6 +521,24 @@ int tfrt_density_error_fields(const void* rows, int64_t stride, int64_t n, int32
   return density_error_run(rows, stride, n, state_dtype, dimension, mask, field_x, field_y, goal,
                            nx, ny, x0, x1, sx, y0, y1, sy, oob_weight, grad, grad_stride,
                            error_out, hq, splat_variant, workspace, workspace_bytes, stream);
+}
+
+int tfrt_density_error_weighted(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                                int32_t dimension, const int32_t* mask, int32_t field_x,
+                                int32_t field_y, const double* goal, const double* weight,
+                                int64_t n_source, const int32_t* perm, int32_t nx, int32_t ny,
+                                double x0, double x1, double sx, double y0, double y1, double sy,
+                                double oob_weight, double* grad, int64_t grad_stride,
+                                double* error_out, int64_t* hq, int32_t splat_variant,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+  if (dimension < 2 || dimension > 3 || field_x < 0 || field_x >= 3 * dimension || field_y < -1 ||
+      field_y >= 3 * dimension || !weight || n_source < 0 || n_source > INT32_MAX)
+    return TFRT_E_BADARG;
+  DensityWeights wt;
+  wt.weight = weight, wt.perm = perm, wt.n_source = n_source;
+  return density_error_run(rows, stride, n, state_dtype, dimension, mask, field_x, field_y, goal,
+                           nx, ny, x0, x1, sx, y0, y1, sy, oob_weight, grad, grad_stride,
+                           error_out, hq, splat_variant, workspace, workspace_bytes, stream, &wt);
 }
 
 }  // extern "C"

@@ -44,12 +44,28 @@
 // "has a direction field": without one they are the kernels of position fields, load for load;
 // with one they recompute the direction from the rows they stream, and the seed writes EVERY row
 // of the column.
+//
+// Weighted (tfrt_spot_error_weighted): every source ray carries a radiant power w in [0, 1], which
+// enters as the INTEGER wq = rint(w * 2^wbits); wr = wq * 2^-wbits is the weight everywhere, so the
+// weighted residuals of a group sum to zero in the quantised quantities.  The product wq * qx is
+// kept in two limbs (wq * (qx >> h) and wq * (qx & (2^h - 1)), h = qbits / 2) so that the position
+// keeps its full qbits; a record is one 64-byte line of eight int64
+// {W, Xhi, Xlo, Yhi, Ylo, count, 0, 0}.  The accumulate and the seed are sibling kernels
+// (k_spot_accumulate_weighted, k_spot_seed_weighted) with the weights as one more argument; the
+// unweighted kernels are untouched.  The weight is read once per column through `perm`, behind
+// the index check that the label lookup needs anyway.  The table in LDS has six planes of G
+// int64: SPOT_WEIGHTED_LDS_GROUPS = 512 keeps it at the 24 KiB of the unweighted table at 1,024
+// groups -- six workgroups, 24 waves, share a CU's 160 KiB; twice the table would leave three, too
+// few to hide the latency of the ds_add_u64 behind other waves' loads.  More groups: six global
+// 64-bit atomics, all in the ray's one line.
 #include "tfrt_common.h"
 #include "direction_fields.h"
 
 namespace tfrt {
 
 constexpr int SPOT_LDS_GROUPS = 1024;      // 3 planes of int64: 24 KiB per workgroup
+constexpr int SPOT_WEIGHTED_LDS_GROUPS = 512;   // weighted, 6 planes of int64: 24 KiB
+constexpr int SPOT_MAX_WBITS = 20;
 constexpr int SPOT_MAX_GROUPS = 1 << 20;
 constexpr int SPOT_MAX_GRID = 512;         // workgroups of the accumulate launch
 constexpr int SPOT_RAYS_PER_BLOCK = 4 * BLOCK;
@@ -61,6 +77,13 @@ struct SpotGrid {
   double x0, x1, qsx, y0, y1, qsy, oob, qmax;
   int64_t n_source;
   int32_t n_groups, row_x, row_y;   // row_x, row_y: field codes (direction_fields.h)
+};
+
+// The weights of tfrt_spot_error_weighted: one f64 in [0, 1] per SOURCE ray.
+struct SpotWeights {
+  const double* weight;
+  double one, inv;           // 2^wbits, 2^-wbits
+  int32_t h;                 // qbits / 2: the low limb's bits
 };
 
 // What one column does.  kind 0: masked off; 3: counts, but contributes nothing (a non-finite
@@ -109,6 +132,29 @@ __device__ __forceinline__ SpotRay spot_classify(const T* __restrict__ rows, int
   r.kind = 1;
   r.x = x;
   r.y = y;
+  return r;
+}
+
+// The same for tfrt_spot_error_weighted: a column with a spot (kinds 1 and 2) whose weight does not
+// count or quantises to 0 is in no spot (kind 3 -- every "no spot" case ends alike, so the order of
+// the checks does not show).  s has passed spot_classify's index check; the read of perm is the one
+// that served the label.  wq = rint(w * 2^wbits) > 0, wr = wq * 2^-wbits.
+template <typename T, int DIM>
+__device__ __forceinline__ SpotRay spot_classify_weighted(
+    const T* __restrict__ rows, int64_t stride, const int32_t* __restrict__ mask,
+    const int32_t* __restrict__ group, const int32_t* __restrict__ perm, int64_t i,
+    const SpotGrid& g, const SpotWeights& wt, LinkDir<DIM>& link, double& wq, double& wr) {
+#pragma clang fp contract(off)
+  SpotRay r = spot_classify<T, DIM>(rows, stride, mask, group, perm, i, g, link);
+  wq = wr = 0.0;
+  if (r.kind == 1 || r.kind == 2) {
+    const int64_t s = perm != nullptr ? (int64_t)perm[i] : i;
+    // (a NaN fails both comparisons; the product with a power of two is exact)
+    const double w = wt.weight[s];
+    wq = w >= 0.0 && w <= 1.0 ? rint(w * wt.one) : 0.0;
+    wr = wq * wt.inv;
+    if (wq == 0.0) r.kind = 3;
+  }
   return r;
 }
 
@@ -209,6 +255,78 @@ __global__ __launch_bounds__(BLOCK) void k_spot_accumulate(
   }
 }
 
+// tfrt_spot_error_weighted's accumulate: the planes W | Xhi | Xlo | Yhi | Ylo | count of G each in
+// LDS -- the order of a record of eight int64 --, or six global atomics in the ray's one line.
+template <typename T, bool LDS, int DIM>
+__global__ __launch_bounds__(BLOCK) void k_spot_accumulate_weighted(
+    const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
+    const int32_t* __restrict__ group, const int32_t* __restrict__ perm, SpotGrid g,
+    SpotWeights wt, unsigned long long* __restrict__ acc, double* __restrict__ pen_partial,
+    long long* __restrict__ cnt_partial) {
+#pragma clang fp contract(off)
+  extern __shared__ unsigned long long table[];
+  __shared__ double wsum[WAVES];
+  __shared__ long long wcnt[WAVES];
+  const int G = g.n_groups;
+  const bool two = g.row_y >= 0;
+  const unsigned long long low = (1ull << wt.h) - 1ull;
+  if (LDS) {
+    for (int e = threadIdx.x; e < 6 * G; e += BLOCK) table[e] = 0ull;
+    __syncthreads();
+  }
+  double pen = 0.0;
+  long long counting = 0;
+  for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * BLOCK) {
+    LinkDir<DIM> link;
+    double wq, wr;
+    const SpotRay r =
+        spot_classify_weighted<T, DIM>(rows, stride, mask, group, perm, i, g, wt, link, wq, wr);
+    counting += r.kind != 0 ? 1 : 0;
+    if (r.kind == 2) {
+      pen += (g.oob * (r.x * r.x + r.y * r.y)) * wr;
+    } else if (r.kind == 1) {
+      const unsigned long long q = (unsigned long long)(long long)wq;
+      const unsigned long long qx = spot_fixed(r.x, g.x0, g.qsx, g.qmax);
+      const unsigned long long qy = two ? spot_fixed(r.y, g.y0, g.qsy, g.qmax) : 0ull;
+      if (LDS) {
+        atomicAdd(&table[r.label], q);
+        atomicAdd(&table[G + r.label], q * (qx >> wt.h));
+        atomicAdd(&table[2 * G + r.label], q * (qx & low));
+        if (two) {
+          atomicAdd(&table[3 * G + r.label], q * (qy >> wt.h));
+          atomicAdd(&table[4 * G + r.label], q * (qy & low));
+        }
+        atomicAdd(&table[5 * G + r.label], 1ull);
+      } else {
+        unsigned long long* rec = acc + 8 * (int64_t)r.label;
+        atomicAdd(&rec[0], q);
+        atomicAdd(&rec[1], q * (qx >> wt.h));
+        atomicAdd(&rec[2], q * (qx & low));
+        if (two) {
+          atomicAdd(&rec[3], q * (qy >> wt.h));
+          atomicAdd(&rec[4], q * (qy & low));
+        }
+        atomicAdd(&rec[5], 1ull);
+      }
+    }
+  }
+  if (LDS) {
+    __syncthreads();
+    for (int e = threadIdx.x; e < 6 * G; e += BLOCK) {
+      const unsigned long long v = table[e];
+      const int plane = e / G, label = e - plane * G;
+      if (v != 0ull) atomicAdd(&acc[8 * (int64_t)label + plane], v);
+    }
+  }
+  const double s = spot_block_sum<WAVES>(pen, wsum);
+  const long long c = spot_block_count<WAVES>(counting, wcnt);
+  if (threadIdx.x == 0) {
+    pen_partial[blockIdx.x] = s;
+    cnt_partial[blockIdx.x] = c;
+  }
+}
+
 template <typename T, int DIM>
 __global__ __launch_bounds__(BLOCK) void k_spot_seed(
     const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
@@ -245,6 +363,57 @@ __global__ __launch_bounds__(BLOCK) void k_spot_seed(
     }
     if constexpr (DIM != 0) {
       // (every row of the column: a direction pulls on the start and on the end of the link)
+      chain_fields<DIM>(link, r.kind == 1 || r.kind == 2, g.row_x, g.row_y, gx, gy, grad,
+                   grad_stride, i);
+    } else {
+      grad[(int64_t)g.row_x * grad_stride + i] = gx;
+      if (two) grad[(int64_t)g.row_y * grad_stride + i] = gy;
+    }
+  }
+  const double s = spot_block_sum<WAVES>(terms, wsum);
+  if (threadIdx.x == 0) term_partial[blockIdx.x] = s;
+}
+
+// tfrt_spot_error_weighted's seed: the centroid from the two limbs, everything times wr last.
+template <typename T, int DIM>
+__global__ __launch_bounds__(BLOCK) void k_spot_seed_weighted(
+    const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
+    const int32_t* __restrict__ group, const int32_t* __restrict__ perm, SpotGrid g,
+    SpotWeights wt, const long long* __restrict__ acc, double* __restrict__ grad,
+    int64_t grad_stride, double* __restrict__ term_partial) {
+#pragma clang fp contract(off)
+  __shared__ double wsum[WAVES];
+  const bool two = g.row_y >= 0;
+  double terms = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * BLOCK) {
+    LinkDir<DIM> link;
+    double wq, wr;
+    const SpotRay r =
+        spot_classify_weighted<T, DIM>(rows, stride, mask, group, perm, i, g, wt, link, wq, wr);
+    double gx = 0.0, gy = 0.0;
+    if (r.kind == 2) {
+      gx = (g.oob * (2.0 * r.x) * r.dx) * wr;
+      gy = (g.oob * (2.0 * r.y) * r.dy) * wr;
+    } else if (r.kind == 1) {
+      // (this ray is in its own group's record: W >= wq >= 1)
+      const long long* rec = acc + 8 * (int64_t)r.label;
+      const double W = (double)rec[0];
+      const double X = ldexp((double)rec[1], wt.h) + (double)rec[2];
+      const double cx = g.x0 + (X / W) / g.qsx;
+      const double dx = r.x - cx;
+      gx = (2.0 * dx) * wr;
+      double t = wr * (dx * dx);
+      if (two) {
+        const double Y = ldexp((double)rec[3], wt.h) + (double)rec[4];
+        const double cy = g.y0 + (Y / W) / g.qsy;
+        const double dy = r.y - cy;
+        gy = (2.0 * dy) * wr;
+        t = t + wr * (dy * dy);
+      }
+      terms += t;
+    }
+    if constexpr (DIM != 0) {
       chain_fields<DIM>(link, r.kind == 1 || r.kind == 2, g.row_x, g.row_y, gx, gy, grad,
                    grad_stride, i);
     } else {
@@ -303,13 +472,27 @@ using namespace tfrt;
 
 extern "C" size_t tfrt_spot_error_workspace_bytes(int64_t n, int32_t n_groups);
 
-// The accumulate and seed launches of both entries.
+// The accumulate and seed launches of every entry (`wt` null: unweighted).
 template <typename T, int DIM>
 static void spot_launch(const T* r, int64_t stride, int64_t n, const int32_t* mask,
-                        const int32_t* group, const int32_t* perm, const SpotGrid& g, bool lds,
-                        int grid, int sgrid, unsigned long long* accu, double* pen_partial,
-                        long long* cnt_partial, double* term_partial, double* grad,
-                        int64_t grad_stride, hipStream_t st) {
+                        const int32_t* group, const int32_t* perm, const SpotGrid& g,
+                        const SpotWeights* wt, bool lds, int grid, int sgrid,
+                        unsigned long long* accu, double* pen_partial, long long* cnt_partial,
+                        double* term_partial, double* grad, int64_t grad_stride, hipStream_t st) {
+  const long long* acc = reinterpret_cast<const long long*>(accu);
+  if (wt != nullptr) {
+    if (lds)
+      hipLaunchKernelGGL((k_spot_accumulate_weighted<T, true, DIM>), dim3(grid), dim3(BLOCK),
+                         (size_t)g.n_groups * 6 * sizeof(unsigned long long), st, r, stride, n,
+                         mask, group, perm, g, *wt, accu, pen_partial, cnt_partial);
+    else
+      hipLaunchKernelGGL((k_spot_accumulate_weighted<T, false, DIM>), dim3(grid), dim3(BLOCK), 0,
+                         st, r, stride, n, mask, group, perm, g, *wt, accu, pen_partial,
+                         cnt_partial);
+    hipLaunchKernelGGL((k_spot_seed_weighted<T, DIM>), dim3(sgrid), dim3(BLOCK), 0, st, r, stride,
+                       n, mask, group, perm, g, *wt, acc, grad, grad_stride, term_partial);
+    return;
+  }
   if (lds)
     hipLaunchKernelGGL((k_spot_accumulate<T, true, DIM>), dim3(grid), dim3(BLOCK),
                        (size_t)g.n_groups * 3 * sizeof(unsigned long long), st, r, stride, n, mask,
@@ -318,23 +501,32 @@ static void spot_launch(const T* r, int64_t stride, int64_t n, const int32_t* ma
     hipLaunchKernelGGL((k_spot_accumulate<T, false, DIM>), dim3(grid), dim3(BLOCK), 0, st, r,
                        stride, n, mask, group, perm, g, accu, pen_partial, cnt_partial);
   hipLaunchKernelGGL((k_spot_seed<T, DIM>), dim3(sgrid), dim3(BLOCK), 0, st, r, stride, n, mask,
-                     group, perm, g, reinterpret_cast<const long long*>(accu), grad, grad_stride,
-                     term_partial);
+                     group, perm, g, acc, grad, grad_stride, term_partial);
 }
 
-// Both entries behind their own checks of the rows / codes: `dim` 2 or 3, codes below 3 * dim.
+// Every entry behind its own checks of the rows / codes: `dim` 2 or 3, codes below 3 * dim.
+// `weight` null: records of four int64 and n * 2^qbits < 2^62; else records of eight, `wbits`
+// and n * 2^wbits * 2^ceil(qbits / 2) < 2^62.
 static int spot_error_run(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
                           int32_t dim, const int32_t* mask, int32_t row_x, int32_t row_y,
                           const int32_t* group, int64_t n_source, const int32_t* perm,
                           int32_t n_groups, double x0, double x1, double qsx, double y0, double y1,
                           double qsy, int32_t qbits, double oob_weight, double* grad,
                           int64_t grad_stride, double* error_out, int64_t* acc, int32_t variant,
-                          void* workspace, size_t workspace_bytes, void* stream) {
+                          void* workspace, size_t workspace_bytes, void* stream,
+                          const double* weight = nullptr, int32_t wbits = 0) {
+  const bool weighted = weight != nullptr;
   if (n < 0 || n > INT32_MAX || n_source < 0 || n_source > INT32_MAX || n_groups < 1 ||
       n_groups > SPOT_MAX_GROUPS || qbits < 1 || qbits > 52 || row_x == row_y || !group ||
       !error_out || !acc || !workspace || variant < 0 || variant > 2)
     return TFRT_E_BADARG;
-  if (n >= ((int64_t)1 << (62 - qbits))) return TFRT_E_BADARG;   // n * 2^qbits must stay below 2^62
+  if (weighted) {
+    // every sum stays below n * 2^wbits * 2^ceil(qbits / 2) < 2^62
+    if (wbits < 1 || wbits > SPOT_MAX_WBITS) return TFRT_E_BADARG;
+    if (n >= ((int64_t)1 << (62 - wbits - (qbits + 1) / 2))) return TFRT_E_BADARG;
+  } else if (n >= ((int64_t)1 << (62 - qbits))) {
+    return TFRT_E_BADARG;   // n * 2^qbits must stay below 2^62
+  }
   if (!(x1 > x0) || !(qsx > 0.0) || !isfinite(qsx) || !(oob_weight >= 0.0) ||
       !isfinite(oob_weight) || !isfinite(x0) || !isfinite(x1))
     return TFRT_E_BADARG;
@@ -342,9 +534,10 @@ static int spot_error_run(const void* rows, int64_t stride, int64_t n, int32_t s
     return TFRT_E_BADARG;
   if (n > 0 && (!rows || !grad || stride < n || grad_stride < n)) return TFRT_E_BADARG;
   if (!state_dtype_ok(state_dtype)) return TFRT_E_BADARG;
-  if (variant == 1 && n_groups > SPOT_LDS_GROUPS) return TFRT_E_BADARG;
+  const int lds_groups = weighted ? SPOT_WEIGHTED_LDS_GROUPS : SPOT_LDS_GROUPS;
+  if (variant == 1 && n_groups > lds_groups) return TFRT_E_BADARG;
   if (workspace_bytes < tfrt_spot_error_workspace_bytes(n, n_groups)) return TFRT_E_WORKSPACE;
-  const bool lds = variant == 1 || (variant == 0 && n_groups <= SPOT_LDS_GROUPS);
+  const bool lds = variant == 1 || (variant == 0 && n_groups <= lds_groups);
   const bool dir = row_x >= 2 * dim || row_y >= 2 * dim;
 
   SpotGrid g;
@@ -352,6 +545,10 @@ static int spot_error_run(const void* rows, int64_t stride, int64_t n, int32_t s
   g.y0 = row_y >= 0 ? y0 : 0.0, g.y1 = row_y >= 0 ? y1 : 0.0, g.qsy = row_y >= 0 ? qsy : 0.0;
   g.qmax = ldexp(1.0, qbits);
   g.n_source = n_source, g.n_groups = n_groups, g.row_x = row_x, g.row_y = row_y;
+  SpotWeights w;
+  w.weight = weight, w.one = ldexp(1.0, wbits), w.inv = ldexp(1.0, -wbits), w.h = qbits / 2;
+  const SpotWeights* wt = weighted ? &w : nullptr;
+  const int record = weighted ? 8 : 4;
   char* ws = static_cast<char*>(workspace);
   double* pen_partial = reinterpret_cast<double*>(ws);
   long long* cnt_partial =
@@ -363,21 +560,21 @@ static int spot_error_run(const void* rows, int64_t stride, int64_t n, int32_t s
   const int grid = spot_grid(n);
   const int sgrid = spot_seed_grid(n);
 
-  hipLaunchKernelGGL(k_spot_clear, dim3(cdiv(4 * (int64_t)n_groups, BLOCK)), dim3(BLOCK), 0, st,
-                     accu, 4 * n_groups);
+  hipLaunchKernelGGL(k_spot_clear, dim3(cdiv(record * (int64_t)n_groups, BLOCK)), dim3(BLOCK), 0,
+                     st, accu, record * n_groups);
   return dispatch_state(state_dtype, TFRT_E_BADARG, [&](auto tag) {
     using T = typename decltype(tag)::type;
     const T* r = static_cast<const T*>(rows);
     if (grid > 0) {
       if (!dir)
-        spot_launch<T, 0>(r, stride, n, mask, group, perm, g, lds, grid, sgrid, accu, pen_partial,
-                          cnt_partial, term_partial, grad, grad_stride, st);
+        spot_launch<T, 0>(r, stride, n, mask, group, perm, g, wt, lds, grid, sgrid, accu,
+                          pen_partial, cnt_partial, term_partial, grad, grad_stride, st);
       else if (dim == 3)
-        spot_launch<T, 3>(r, stride, n, mask, group, perm, g, lds, grid, sgrid, accu, pen_partial,
-                          cnt_partial, term_partial, grad, grad_stride, st);
+        spot_launch<T, 3>(r, stride, n, mask, group, perm, g, wt, lds, grid, sgrid, accu,
+                          pen_partial, cnt_partial, term_partial, grad, grad_stride, st);
       else
-        spot_launch<T, 2>(r, stride, n, mask, group, perm, g, lds, grid, sgrid, accu, pen_partial,
-                          cnt_partial, term_partial, grad, grad_stride, st);
+        spot_launch<T, 2>(r, stride, n, mask, group, perm, g, wt, lds, grid, sgrid, accu,
+                          pen_partial, cnt_partial, term_partial, grad, grad_stride, st);
     }
     hipLaunchKernelGGL(k_spot_finish, dim3(1), dim3(FINISH_BLOCK), 0, st, pen_partial, cnt_partial,
                        grid, term_partial, sgrid, row_y >= 0 ? 2 : 1, error_out);
@@ -420,6 +617,27 @@ int tfrt_spot_error_fields(const void* rows, int64_t stride, int64_t n, int32_t 
   return spot_error_run(rows, stride, n, state_dtype, dimension, mask, field_x, field_y, group,
                         n_source, perm, n_groups, x0, x1, qsx, y0, y1, qsy, qbits, oob_weight, grad,
                         grad_stride, error_out, acc, variant, workspace, workspace_bytes, stream);
+}
+
+size_t tfrt_spot_error_weighted_workspace_bytes(int64_t n, int32_t n_groups) {
+  return tfrt_spot_error_workspace_bytes(n, n_groups);
+}
+
+int tfrt_spot_error_weighted(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                             int32_t dimension, const int32_t* mask, int32_t field_x,
+                             int32_t field_y, const int32_t* group, const double* weight,
+                             int32_t wbits, int64_t n_source, const int32_t* perm,
+                             int32_t n_groups, double x0, double x1, double qsx, double y0,
+                             double y1, double qsy, int32_t qbits, double oob_weight, double* grad,
+                             int64_t grad_stride, double* error_out, int64_t* acc, int32_t variant,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  if (dimension < 2 || dimension > 3 || field_x < 0 || field_x >= 3 * dimension || field_y < -1 ||
+      field_y >= 3 * dimension || !weight)
+    return TFRT_E_BADARG;
+  return spot_error_run(rows, stride, n, state_dtype, dimension, mask, field_x, field_y, group,
+                        n_source, perm, n_groups, x0, x1, qsx, y0, y1, qsy, qbits, oob_weight, grad,
+                        grad_stride, error_out, acc, variant, workspace, workspace_bytes, stream,
+                        weight, wbits);
 }
 
 }  // extern "C"

@@ -205,6 +205,82 @@ def _geometry_block(engine, fin):
     return dim, torch.stack([fin[f] for f in (_GEO3 if dim == 3 else _GEO2)], dim=0)
 
 
+def _source_buffer(owner, name, given, convert, src, what, noun, keep=False):
+    """``owner.<name>``, a buffer with one entry per SOURCE ray of the source set ``src``, on the
+    source's device: the tensor given (moved once; a new buffer re-captures a graph), or the
+    result of the callable ``given`` on the source's field dict, converted by ``convert(value,
+    device)`` and cached in ``owner._caches[name]`` by the versions of the source's fields as
+    ``GoalError.table`` is.  ``keep``: a new result of the callable is copied into the buffer
+    there is (same shape), so its address -- part of a step's signature -- stays and a step that
+    is being captured records the evaluation.  What ``SpotError.labels_of`` and the errors'
+    ``weights_of`` share."""
+    if hasattr(src, "n_rays"):
+        n, dev = src.n_rays, src.device
+    else:
+        n, dev = src["x_start"].shape[0], src["x_start"].device
+    value = getattr(owner, name)
+    if callable(given):
+        if hasattr(src, "cache_key"):      # rays made in place (sources.DeviceRaySet)
+            vals, key = [src], src.cache_key
+        else:
+            vals = list(src.values()) if hasattr(src, "values") else [src[k] for k in src.keys()]
+            key = tuple((id(v), getattr(v, "_version", None)) for v in vals)
+        hit = owner._caches.get(name)
+        if hit is None or hit[0] != key:
+            new = convert(given(src), dev)
+            if keep and value is not None and value.shape == new.shape \
+                    and value.device == new.device:
+                value.copy_(new)
+            else:
+                value = new
+                setattr(owner, name, value)
+            owner._caches[name] = (key, vals)        # the keyed tensors stay alive with the key
+    elif value.device != dev:
+        value = value.to(dev)
+        setattr(owner, name, value)
+    if value.numel() != n:
+        raise ValueError(f"{what}: {value.numel()} {noun}s for {n} source rays -- one {noun} per "
+                         "source ray")
+    return value
+
+
+def _as_weights(what, weights, device):
+    """The weights of ``DensityError`` / ``SpotError`` as they are kept: float64 on ``device``,
+    divided by their maximum once (only ratios matter), values in [0, 1].  While a step is being
+    captured the values cannot be read: the checks are those of the eager steps before it, and the
+    kernels leave out a ray whose weight is not finite or not in [0, 1]."""
+    w = weights if isinstance(weights, torch.Tensor) else torch.as_tensor(np.asarray(weights))
+    if w.dim() != 1 or not w.dtype.is_floating_point:
+        raise ValueError(f"{what}: weights must be floats of shape (N,), one weight per source "
+                         f"ray; got shape {tuple(w.shape)}, {w.dtype}")
+    w = w.detach().to(device=device, dtype=torch.float64)
+    if w.numel() == 0:
+        raise ValueError(f"{what}: at least one weight must be > 0")
+    if not (w.is_cuda and torch.cuda.is_current_stream_capturing()):
+        if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+            raise ValueError(f"{what}: weights must be finite and >= 0")
+        if not bool((w > 0).any()):
+            raise ValueError(f"{what}: at least one weight must be > 0")
+    return (w / w.max()).contiguous()
+
+
+def _init_weights(erf, what, weights):
+    """``erf.weights_given`` / ``erf.weights`` from the constructor's ``weights``."""
+    from . import config
+    erf.weights_given = weights
+    erf.weights = None
+    if weights is not None and not callable(weights):
+        erf.weights = _as_weights(what, weights, config.get_device())
+
+
+def _weights_key(erf):
+    """The weights' part of a ``graph_key``: the buffer's address and shape (overwriting it in
+    place is seen by replays, another buffer re-captures)."""
+    w = erf.weights
+    return (erf.weights_given is not None,
+            None if w is None else (w.data_ptr(), tuple(w.shape)))
+
+
 class DensityError:
     """The finished rays, taken together, must land with the density ``goal`` on the target: a
     soft (bilinear) histogram of the rays against the goal, both L2-normalised, summed squared
@@ -262,13 +338,34 @@ class DensityError:
     (``FusedStep.eligible2d`` is false): 2-D engines use the generic path.  One process: the
     histogram couples the rays, ray shards would each normalise their own.
 
+    ``weights``: None -- every finished ray is one unit of light --, or a radiant power per
+    SOURCE ray: a float tensor or array of shape (N,) in the source's own order, finite and
+    ``>= 0`` with at least one ``> 0`` (a ValueError otherwise), or a callable on the source's
+    field dict that returns one (``lambda src: cos`` of the start direction for a Lambertian
+    emitter sampled uniformly in angle; evaluated and cached as ``SpotError``'s ``groups``).  Only
+    ratios matter: the weights are divided by their maximum once, in float64, and kept on the
+    device as ``weights`` (values in [0, 1]); that buffer may be overwritten in place between steps
+    (a replayed graph reads it), another buffer re-captures.  A finished ray finds its weight ``w``
+    through the source-ray index the trace carries.  A ray without a source ray, or whose ``w`` is
+    not finite or not in [0, 1], counts as one with a non-finite coordinate.  Then, each product
+    rounded on its own:
+
+    * a ray inside adds ``rint(((bx * by) * w) * 2**32)`` to each of its bins (``bx * w`` with one
+      field) and its gradient is the expression above multiplied by ``w`` last;
+    * a ray outside has its penalty and its gradient multiplied by ``w`` last;
+    * ``s``, ``E_hist`` and the pulls come from the weighted histogram exactly as above; with a
+      direction field the gradient carries ``w`` when it enters the chain rule.
+
+    Weighted and unweighted run on the same paths (fused, generic, 2-D, ``deterministic=True``),
+    the weighted one with kernels of its own (tfrt_density_error_weighted).
+
     ``goal`` may be overwritten in place between steps (a replayed graph reads the buffer);
-    ``last_hq`` is the int64 histogram of the last evaluation.  ``splat_variant`` (0: by the number
+    ``last_hq`` is the int64 histogram of the last evaluation (the weighted one with weights).  ``splat_variant`` (0: by the number
     of bins; 1: histogram in LDS; 2: global atomics) is tfrt_density_error's, for measuring."""
 
     splat_variant = 0
 
-    def __init__(self, fields, goal, domain, oob_weight=0.0, bins=None):
+    def __init__(self, fields, goal, domain, oob_weight=0.0, bins=None, weights=None):
         from . import config
         self.fields = (fields,) if isinstance(fields, str) else tuple(fields)
         if len(self.fields) not in (1, 2) or any(f not in _FIELDS3 for f in self.fields) \
@@ -315,6 +412,8 @@ class DensityError:
         nx = self.goal.shape[-1]
         self.grid = ops.density_grid(domain, nx, self.goal.shape[0] if k == 2 else None)
         self.last_hq = None
+        self._caches = {}
+        _init_weights(self, "DensityError", weights)
 
     @property
     def g(self):
@@ -333,17 +432,31 @@ class DensityError:
             self.goal = self.goal.to(device)
         return self.goal
 
-    def graph_key(self):
-        """What a captured step has baked in: the goal buffer's address and the constants."""
-        return (self.goal.data_ptr(), tuple(self.goal.shape), self.grid, self.oob_weight,
-                self.splat_variant)
+    def weights_of(self, src):
+        """The float64 weight buffer of the source set ``src`` on its device, one weight in [0, 1]
+        per source ray (None without weights): the tensor given, or the callable's result,
+        normalised and cached as ``SpotError.labels_of`` caches its labels."""
+        if self.weights_given is None:
+            return None
+        return _source_buffer(self, "weights", self.weights_given,
+                              lambda v, dev: _as_weights("DensityError", v, dev), src,
+                              "DensityError", "weight", keep=True)
 
-    def evaluate(self, rows, row_x, row_y, mask=None, dimension=None, **buffers):
+    def graph_key(self):
+        """What a captured step has baked in: the goal buffer's address, the weight buffer's and
+        the constants."""
+        return (self.goal.data_ptr(), tuple(self.goal.shape), self.grid, self.oob_weight,
+                self.splat_variant) + _weights_key(self)
+
+    def evaluate(self, rows, row_x, row_y, mask=None, dimension=None, weights=None, perm=None,
+                 **buffers):
         """``ops.density_error`` of the columns of ``rows`` with this goal, domain and weight
-        (``dimension`` given: ``rows`` is the geometry block, ``row_x`` / ``row_y`` field codes)."""
+        (``dimension`` given: ``rows`` is the geometry block, ``row_x`` / ``row_y`` field codes;
+        ``weights``: the buffer of ``weights_of``, ``perm``: the source ray of every column)."""
         out = ops.density_error(rows, row_x, row_y, self.goal_on(rows.device), self.grid,
                                 self.oob_weight, mask=mask, variant=self.splat_variant,
-                                dimension=dimension, **buffers)
+                                dimension=dimension, weights=weights,
+                                perm=perm if weights is not None else None, **buffers)
         self.last_hq = out[2]
         return out
 
@@ -354,19 +467,26 @@ class DensityError:
         fin = engine.finished_rays
         if not bool(fin):
             return (self.goal * self.goal).sum().reshape(1)
+        weights = ids = None
+        if self.weights_given is not None:
+            weights = self.weights_of(engine._trace_src)
+            ids = engine.last_trace["finished_id"].to(torch.int32).contiguous()
         if self.has_direction:
             dim, block = _geometry_block(engine, fin)
-            return _DensityFieldTerms.apply(block, self, dim, tuple(codes))
-        return _DensityTerms.apply(torch.stack([fin[f] for f in self.fields], dim=0), self)
+            return _DensityFieldTerms.apply(block, self, dim, tuple(codes), weights, ids)
+        return _DensityTerms.apply(torch.stack([fin[f] for f in self.fields], dim=0), self,
+                                   weights, ids)
 
 
 class _DensityTerms(torch.autograd.Function):
-    """DensityError over the (k, n) field columns of the finished rays, no mask."""
+    """DensityError over the (k, n) field columns of the finished rays, no mask; ``weights``
+    (or None) with ``ids``, the source ray of every column."""
 
     @staticmethod
-    def forward(ctx, columns, erf):
+    def forward(ctx, columns, erf, weights=None, ids=None):
         block = columns.detach().contiguous()
-        err, grad, _ = erf.evaluate(block, 0, 1 if block.shape[0] == 2 else -1)
+        err, grad, _ = erf.evaluate(block, 0, 1 if block.shape[0] == 2 else -1, weights=weights,
+                                    perm=ids)
         ctx.save_for_backward(grad)
         ctx.dtype = columns.dtype
         return err[:1].clone()
@@ -374,18 +494,19 @@ class _DensityTerms(torch.autograd.Function):
     @staticmethod
     def backward(ctx, upstream):
         grad, = ctx.saved_tensors
-        return (upstream * grad).to(ctx.dtype), None
+        return (upstream * grad).to(ctx.dtype), None, None, None
 
 
 class _DensityFieldTerms(torch.autograd.Function):
     """DensityError with a direction field over the (2 * dimension, n) geometry block of the
-    finished rays, no mask; ``codes``: the field codes."""
+    finished rays, no mask; ``codes``: the field codes; ``weights`` (or None) with ``ids``, the
+    source ray of every column."""
 
     @staticmethod
-    def forward(ctx, block, erf, dimension, codes):
+    def forward(ctx, block, erf, dimension, codes, weights=None, ids=None):
         rows = block.detach().contiguous()
         err, grad, _ = erf.evaluate(rows, codes[0], codes[1] if len(codes) == 2 else -1,
-                                    dimension=dimension)
+                                    dimension=dimension, weights=weights, perm=ids)
         ctx.save_for_backward(grad)
         ctx.dtype = block.dtype
         return err[:1].clone()
@@ -393,7 +514,7 @@ class _DensityFieldTerms(torch.autograd.Function):
     @staticmethod
     def backward(ctx, upstream):
         grad, = ctx.saved_tensors
-        return (upstream * grad).to(ctx.dtype), None, None, None
+        return (upstream * grad).to(ctx.dtype), None, None, None, None, None
 
 
 class SpotError:
@@ -443,24 +564,51 @@ class SpotError:
     finished rays' columns under a ``torch.autograd.Function``), which also serves sources that are
     not traced in place, ``deterministic=True``, fewer than 4,096 rays and 2-D engines
     (``FusedStep.eligible2d`` is false).  Its ``backward`` returns ``upstream * gradient``: exact
-    when ``upstream`` is constant within a group (the optimiser passes ones); weights that differ
-    inside a group would move the centroid, which this does not follow; with a direction field the
-    two fields of a ray must also carry the same weight (a ``ValueError`` otherwise), because the
-    kernel's chain rule sums both into the geometry rows.  On a 3-D engine that traces
+    when ``upstream`` is constant within a group (the optimiser passes ones) -- a radiant power
+    per ray belongs in ``weights`` (below), which moves the centroid with it, not in ``upstream``;
+    with a direction field the two fields of a ray must also carry the same upstream factor (a
+    ``ValueError`` otherwise), because the kernel's chain rule sums both into the geometry rows.  On a 3-D engine that traces
     its source in place the optimiser runs it on the fused, graph-replayed step under the
     conditions of a ``RowwiseError`` (``FusedStep._rowwise3d`` with ``tfrt_spot_error`` in the
     place of ``fn`` and its autograd), with the same kernels and the same ``qbits``.  One process:
     with ray shards over several ranks the generic path runs and each shard forms the centroids of
     its own rays.
 
-    ``last_acc`` is the (G, 4) int64 table ``{count, Sx, Sy, 0}`` of the last evaluation,
-    ``centroids()`` the (G, k) float64 centroids made from it (NaN for a group without rays).
+    ``weights``: None -- every ray of a spot counts alike --, or a radiant power per SOURCE ray,
+    given, normalised (divided by the maximum, float64, values in [0, 1]), kept as ``weights`` and
+    looked up exactly as ``DensityError``'s: a tensor or array of shape (N,), or a callable on the
+    source's field dict (an apodised pupil, a spectrum).  The spot is then the WEIGHTED one.  With
+    ``wbits = min(20, 62 - bit_length(N) - ceil(qbits / 2))`` (``ops.spot_wbits(N)``) a ray's
+    weight ``w`` enters as the integer ``wq = rint(w * 2**wbits)`` (half to even), and
+    ``wr = wq * 2**-wbits`` -- exact -- is the weight used everywhere, so the weighted residuals of
+    a group sum to zero in the quantised quantities.  After the label's case above:
+
+    * no source ray, ``w`` not finite or not in [0, 1], or ``wq == 0``: the ray is in no spot, no
+      error, zero gradient;
+    * outside the domain: the penalty and its gradient are multiplied by ``wr`` last;
+    * inside: with ``h = qbits // 2`` the product ``wq * qx`` is added in two limbs, so that the
+      position keeps its full ``qbits``: ``Xhi += wq * (qx >> h)``, ``Xlo += wq * (qx & (2**h - 1))``
+      (y alike), ``W += wq``, ``count += 1`` -- a record is eight int64
+      ``{W, Xhi, Xlo, Yhi, Ylo, count, 0, 0}``, every sum below ``N * 2**wbits * 2**ceil(qbits / 2)
+      < 2**62``.
+
+    A group with ``W > 0`` has ``X = ldexp(Xhi, h) + Xlo`` and the centroid
+    ``cx = x0 + (X / W) / qsx``; a ray inside has ``dx = x - cx``, the terms ``wr * (dx * dx)`` and
+    ``wr * (dy * dy)`` and the gradient ``(2 * dx) * wr``, ``(2 * dy) * wr`` -- again exact without
+    a derivative of the centroid, because the WEIGHTED residuals of a group sum to zero.  The
+    number of terms stays ``len(fields) * n_finished``.  Weighted and unweighted run on the same
+    paths; the weighted one has kernels of its own (tfrt_spot_error_weighted: a table of six planes
+    in LDS up to ``ops.SPOT_WEIGHTED_LDS_GROUPS`` groups, global atomics above).
+
+    ``last_acc`` is the (G, 4) int64 table ``{count, Sx, Sy, 0}`` of the last evaluation -- with
+    weights the (G, 8) table above --, ``centroids()`` the (G, k) float64 centroids made from it,
+    weighted with weights (NaN for a group without rays).
     ``splat_variant`` (0: by G; 1: table in LDS; 2: global atomics) is tfrt_spot_error's, for
     measuring."""
 
     splat_variant = 0
 
-    def __init__(self, fields, groups, domain, oob_weight=0.0, n_groups=None):
+    def __init__(self, fields, groups, domain, oob_weight=0.0, n_groups=None, weights=None):
         from . import config
         self.fields = (fields,) if isinstance(fields, str) else tuple(fields)
         if len(self.fields) not in (1, 2) or any(f not in _FIELDS3 for f in self.fields) \
@@ -481,7 +629,7 @@ class SpotError:
             raise ValueError("SpotError: oob_weight must be finite and >= 0")
         self.groups = groups
         self.labels = None
-        self._cache = None
+        self._caches = {}
         if callable(groups):
             if n_groups is None:
                 raise ValueError("SpotError: callable groups need n_groups")
@@ -501,6 +649,12 @@ class SpotError:
         self._grids = {}
         self.last_acc = None
         self.last_grid = None
+        self.last_qbits = None
+        _init_weights(self, "SpotError", weights)
+        if self.weights is not None and self.labels is not None \
+                and self.weights.numel() != self.labels.numel():
+            raise ValueError(f"SpotError: {self.weights.numel()} weights for "
+                             f"{self.labels.numel()} labels -- one of each per source ray")
 
     @staticmethod
     def _as_labels(groups, device):
@@ -521,25 +675,18 @@ class SpotError:
         """The int32 label buffer of the source set ``src`` on its device, one label per source
         ray: the tensor given (moved once; a new buffer re-captures a graph), or the callable's
         result, cached by the versions of the source's fields as ``GoalError.table`` is."""
-        if hasattr(src, "n_rays"):
-            n, dev = src.n_rays, src.device
-        else:
-            n, dev = src["x_start"].shape[0], src["x_start"].device
-        if callable(self.groups):
-            if hasattr(src, "cache_key"):      # rays made in place (sources.DeviceRaySet)
-                vals, key = [src], src.cache_key
-            else:
-                vals = list(src.values()) if hasattr(src, "values") else [src[k] for k in src.keys()]
-                key = tuple((id(v), getattr(v, "_version", None)) for v in vals)
-            if self._cache is None or self._cache[0] != key:
-                self.labels = self._as_labels(self.groups(src), dev)
-                self._cache = (key, vals)        # the keyed tensors stay alive with the key
-        elif self.labels.device != dev:
-            self.labels = self.labels.to(dev)
-        if self.labels.numel() != n:
-            raise ValueError(f"SpotError: {self.labels.numel()} labels for {n} source rays -- one "
-                             "label per source ray")
-        return self.labels
+        return _source_buffer(self, "labels", self.groups, self._as_labels, src, "SpotError",
+                              "label")
+
+    def weights_of(self, src):
+        """The float64 weight buffer of the source set ``src`` on its device, one weight in [0, 1]
+        per source ray (None without weights): the tensor given, or the callable's result,
+        normalised and cached as the labels are."""
+        if self.weights_given is None:
+            return None
+        return _source_buffer(self, "weights", self.weights_given,
+                              lambda v, dev: _as_weights("SpotError", v, dev), src, "SpotError",
+                              "weight", keep=True)
 
     def grid_for(self, n_source):
         """(qbits, grid constants) for a source of ``n_source`` rays: both paths of a step use the
@@ -551,27 +698,32 @@ class SpotError:
         return hit
 
     def graph_key(self):
-        """What a captured step has baked in: the label buffer's address and the constants."""
-        lab = self.labels
+        """What a captured step has baked in: the label buffer's address, the weight buffer's
+        with ``wbits``, and the constants."""
+        lab, w = self.labels, self.weights
         return (None if lab is None else (lab.data_ptr(), tuple(lab.shape)), self.n_groups,
-                self.domain, self.oob_weight, self.splat_variant)
+                self.domain, self.oob_weight, self.splat_variant) + _weights_key(self) \
+            + (None if w is None else ops.spot_wbits(w.numel()),)
 
     def evaluate(self, rows, row_x, row_y, labels, mask=None, perm=None, dimension=None,
-                 **buffers):
+                 weights=None, **buffers):
         """``ops.spot_error`` of the columns of ``rows`` with these labels, domain and weight
-        (``dimension`` given: ``rows`` is the geometry block, ``row_x`` / ``row_y`` field codes)."""
+        (``dimension`` given: ``rows`` is the geometry block, ``row_x`` / ``row_y`` field codes;
+        ``weights``: the buffer of ``weights_of``)."""
         qbits, grid = self.grid_for(labels.numel())
         out = ops.spot_error(rows, row_x, row_y, labels, self.n_groups, grid, self.oob_weight,
                              mask=mask, perm=perm, variant=self.splat_variant, qbits=qbits,
-                             dimension=dimension, **buffers)
-        self.last_acc, self.last_grid = out[2], grid
+                             dimension=dimension, weights=weights,
+                             wbits=None if weights is None else ops.spot_wbits(labels.numel()),
+                             **buffers)
+        self.last_acc, self.last_grid, self.last_qbits = out[2], grid, qbits
         return out
 
     def centroids(self):
         """(G, k) float64 centroids of the last evaluation, NaN for a group without rays."""
         if self.last_acc is None:
             raise RuntimeError("SpotError: no evaluation yet")
-        return ops.spot_centroids(self.last_acc, self.last_grid, len(self.fields))
+        return ops.spot_centroids(self.last_acc, self.last_grid, len(self.fields), self.last_qbits)
 
     def __call__(self, engine):
         """The (n_finished, k) error terms through the generic path; the gradient rows come back
@@ -582,28 +734,66 @@ class SpotError:
             return torch.zeros((0, len(self.fields)), dtype=torch.float64)
         ids = engine.last_trace["finished_id"]
         labels = self.labels_of(engine._trace_src)
+        weights = self.weights_of(engine._trace_src)
         if self.has_direction:
             dim, block = _geometry_block(engine, fin)
             return _SpotFieldTerms.apply(block, self, labels, ids.to(torch.int32).contiguous(),
-                                         dim, tuple(codes))
+                                         dim, tuple(codes), weights)
         columns = torch.stack([fin[f] for f in self.fields], dim=0)
-        return _SpotTerms.apply(columns, self, labels, ids.to(torch.int32).contiguous())
+        return _SpotTerms.apply(columns, self, labels, ids.to(torch.int32).contiguous(), weights)
+
+
+def _spot_terms(erf, v, labels, ids, acc, weights):
+    """The (n, k) terms of a SpotError evaluation from its records: an inside ray's squared
+    distances to its group's centroid, a penalised ray's ``oob_weight * ex**2`` per field, both
+    times ``wr`` with ``weights``; zeros for a ray in no spot.  ``v``: the (k, n) float64 fields."""
+    k = v.shape[0]
+    lo = torch.tensor([d[0] for d in erf.domain], dtype=torch.float64, device=v.device)[:, None]
+    hi = torch.tensor([d[1] for d in erf.domain], dtype=torch.float64, device=v.device)[:, None]
+    zero = torch.zeros((), dtype=torch.float64, device=v.device)
+    ex = torch.maximum(lo - v, zero) + torch.maximum(v - hi, zero)
+    out = ((v < lo) | (v > hi)).any(dim=0, keepdim=True)
+    # (a ray that does not count has a zero gradient and, outside, no penalty either: its label
+    # and its weight decide, which the kernel has looked up)
+    s = ids.long()
+    s_ok = (s >= 0) & (s < labels.numel())
+    s = s.clamp(0, labels.numel() - 1)
+    lab = labels[s]
+    spot = s_ok & (lab >= 0) & (lab < erf.n_groups) & torch.isfinite(v).all(dim=0)
+    centre = ops.spot_centroids(acc, erf.last_grid, k, erf.last_qbits).t()[
+        :, lab.long().clamp(0, erf.n_groups - 1)]
+    dv = v - centre
+    if weights is None:
+        terms = torch.where(out, erf.oob_weight * (ex * ex), dv * dv)
+    else:
+        wbits = ops.spot_wbits(labels.numel())
+        w = weights[s]
+        wq = torch.where((w >= 0.0) & (w <= 1.0), torch.round(w * float(np.ldexp(1.0, wbits))),
+                         torch.zeros_like(w))
+        wr = wq * float(np.ldexp(1.0, -wbits))
+        spot = spot & (wq > 0)
+        terms = torch.where(out, (erf.oob_weight * (ex * ex)) * wr, wr * (dv * dv))
+    return torch.where(spot[None, :], terms, zero).t().contiguous()
 
 
 class _SpotTerms(torch.autograd.Function):
     """SpotError over the (k, n) field columns of the finished rays, no mask; ``ids``: the source
     ray of every column.  Returns the (n, k) terms: an inside ray's are (gradient / 2)**2 -- the
     kernel's own dx * dx, the halving is exact --, a penalised ray's ``oob_weight * ex**2`` per
-    field."""
+    field.  With ``weights`` (gradient / 2)**2 is no longer the term: the terms come from the
+    records' centroids (``_spot_terms``)."""
 
     @staticmethod
-    def forward(ctx, columns, erf, labels, ids):
+    def forward(ctx, columns, erf, labels, ids, weights=None):
         block = columns.detach().contiguous()
         k = block.shape[0]
-        err, grad, _ = erf.evaluate(block, 0, 1 if k == 2 else -1, labels, perm=ids)
+        err, grad, acc = erf.evaluate(block, 0, 1 if k == 2 else -1, labels, perm=ids,
+                                      weights=weights)
         ctx.save_for_backward(grad)
         ctx.dtype = columns.dtype
         v = block.double()
+        if weights is not None:
+            return _spot_terms(erf, v, labels, ids, acc, weights)
         lo = torch.tensor([d[0] for d in erf.domain], dtype=torch.float64, device=v.device)[:, None]
         hi = torch.tensor([d[1] for d in erf.domain], dtype=torch.float64, device=v.device)[:, None]
         zero = torch.zeros((), dtype=torch.float64, device=v.device)
@@ -620,7 +810,7 @@ class _SpotTerms(torch.autograd.Function):
     @staticmethod
     def backward(ctx, upstream):
         grad, = ctx.saved_tensors
-        return (upstream.t() * grad).to(ctx.dtype), None, None, None
+        return (upstream.t() * grad).to(ctx.dtype), None, None, None, None
 
 
 class _SpotFieldTerms(torch.autograd.Function):
@@ -630,26 +820,16 @@ class _SpotFieldTerms(torch.autograd.Function):
     of the evaluation), a penalised ray's ``oob_weight * ex**2`` per field."""
 
     @staticmethod
-    def forward(ctx, block, erf, labels, ids, dimension, codes):
+    def forward(ctx, block, erf, labels, ids, dimension, codes, weights=None):
         rows = block.detach().contiguous()
         k = len(codes)
         err, grad, acc = erf.evaluate(rows, codes[0], codes[1] if k == 2 else -1, labels,
-                                      perm=ids, dimension=dimension)
+                                      perm=ids, dimension=dimension, weights=weights)
         ctx.save_for_backward(grad)
         ctx.dtype = block.dtype
         link = ops._link_torch(rows, dimension)
         v = torch.stack([ops._link_field_torch(link, c, dimension) for c in codes], dim=0)
-        lo = torch.tensor([d[0] for d in erf.domain], dtype=torch.float64, device=v.device)[:, None]
-        hi = torch.tensor([d[1] for d in erf.domain], dtype=torch.float64, device=v.device)[:, None]
-        zero = torch.zeros((), dtype=torch.float64, device=v.device)
-        ex = torch.maximum(lo - v, zero) + torch.maximum(v - hi, zero)
-        out = ((v < lo) | (v > hi)).any(dim=0, keepdim=True)
-        lab = labels[ids.long().clamp(0, labels.numel() - 1)]
-        spot = (lab >= 0) & (lab < erf.n_groups) & torch.isfinite(v).all(dim=0)
-        centre = ops.spot_centroids(acc, erf.last_grid, k).t()[:, lab.long().clamp(0, erf.n_groups - 1)]
-        dv = v - centre
-        terms = torch.where(out, erf.oob_weight * (ex * ex), dv * dv)
-        return torch.where(spot[None, :], terms, zero).t().contiguous()
+        return _spot_terms(erf, v, labels, ids, acc, weights)
 
     @staticmethod
     def backward(ctx, upstream):
@@ -659,7 +839,7 @@ class _SpotFieldTerms(torch.autograd.Function):
             raise ValueError("SpotError with a direction field: the upstream gradient must weigh "
                              "both fields of a ray alike")
         grad, = ctx.saved_tensors
-        return (upstream[:, 0] * grad).to(ctx.dtype), None, None, None, None, None
+        return (upstream[:, 0] * grad).to(ctx.dtype), None, None, None, None, None, None
 
 
 class _RowFields:
@@ -1246,7 +1426,7 @@ class FusedStep:
             self._trace_forward(st, sc, st.row_outs)
             if isinstance(self.opt.error_function, (DensityError, SpotError)):
                 if isinstance(self.opt.error_function, DensityError):
-                    g64 = self._density_seeds3d(st)
+                    g64 = self._density_seeds3d(st, src, perm)
                 else:
                     g64 = self._spot_seeds3d(st, src, perm)
                 if not need_back:
@@ -1259,9 +1439,10 @@ class FusedStep:
                 grads = self._parameter_gradients(*self._outs3d(fv, st, index), tap_log)
         return grads, st
 
-    def _density_seeds3d(self, st):
+    def _density_seeds3d(self, st, src, perm):
         """A DensityError on the fixed-shape columns: tfrt_density_error reads ``st.rows`` and the
-        mask ``st.row_face`` and writes its rows of the persistent seed block for every column --
+        mask ``st.row_face`` -- with weights also the source's weight buffer through the trace's
+        order ``perm``, inside the kernel, as a SpotError's labels -- and writes its rows of the persistent seed block for every column --
         the two rows of position fields (the other rows were zeroed when the state was made, and
         the field codes are part of its signature), all six with a direction field --, the error
         into ``st.err`` and the histogram into ``st.hq``.  Returns the (6, capN) seed block."""
@@ -1275,8 +1456,8 @@ class FusedStep:
             st.hq = torch.zeros(goal.shape, dtype=torch.int64, device=dev)
         rows = erf.rows
         erf.evaluate(st.rows[:, :st.N], rows[0], rows[1] if len(rows) == 2 else -1,
-                     mask=st.row_face, dimension=3, grad=st.g_fin, err=st.err, hq=st.hq,
-                     workspace=st.density_ws)
+                     mask=st.row_face, dimension=3, weights=erf.weights_of(src), perm=perm,
+                     grad=st.g_fin, err=st.err, hq=st.hq, workspace=st.density_ws)
         with torch.no_grad():
             self.tests_total += st.row_passes[:st.N].sum() * st.M
         return st.g_fin
@@ -1288,18 +1469,21 @@ class FusedStep:
         re-drawn and re-ordered inside the graph -- and writes its rows of the persistent seed
         block for every column (two for position fields, the others zeroed when the state was
         made; all six with a direction field), the error into ``st.err`` and the group records
-        into ``st.acc``.  Returns the (6, capN) seed block."""
+        into ``st.acc`` ((G, 4), with weights -- looked up like the labels -- (G, 8)).  Returns
+        the (6, capN) seed block."""
         erf = self.opt.error_function
         dev = st.rows.device
         labels = erf.labels_of(src)
-        if st.acc is None or st.acc.shape[0] != erf.n_groups:
+        weights = erf.weights_of(src)
+        record = 4 if weights is None else 8
+        if st.acc is None or tuple(st.acc.shape) != (erf.n_groups, record):
             wsb = _lib.lib().tfrt_spot_error_workspace_bytes(st.N, erf.n_groups)
             st.spot_ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
-            st.acc = torch.zeros((erf.n_groups, 4), dtype=torch.int64, device=dev)
+            st.acc = torch.zeros((erf.n_groups, record), dtype=torch.int64, device=dev)
         rows = erf.rows
         erf.evaluate(st.rows[:, :st.N], rows[0], rows[1] if len(rows) == 2 else -1, labels,
-                     mask=st.row_face, perm=perm, dimension=3, grad=st.g_fin, err=st.err,
-                     acc=st.acc, workspace=st.spot_ws)
+                     mask=st.row_face, perm=perm, dimension=3, weights=weights, grad=st.g_fin,
+                     err=st.err, acc=st.acc, workspace=st.spot_ws)
         with torch.no_grad():
             self.tests_total += st.row_passes[:st.N].sum() * st.M
         return st.g_fin

@@ -1334,8 +1334,30 @@ def density_grid(domain, nx, ny=None):
     return (x0, x1, sx, y0, y1, float(np.float64(ny) / (np.float64(y1) - np.float64(y0))))
 
 
+def _check_weights(what, weights, perm, n):
+    """``weights``: contiguous float64, one per SOURCE ray; ``perm``: contiguous int32, one entry
+    per column."""
+    if weights.dtype != torch.float64 or weights.dim() != 1 or not weights.is_contiguous():
+        raise ValueError(f"{what}: weights must be a contiguous float64 vector, one weight per "
+                         "source ray")
+    if perm is not None and (perm.dtype != torch.int32 or perm.numel() < n
+                             or not perm.is_contiguous()):
+        raise ValueError(f"{what}: perm must be contiguous int32, one entry per column")
+
+
+def _source_weights(weights, perm, n):
+    """(w, ok) per column on the CPU: the weight of column i's source ray ``perm[i]`` (``i``
+    without perm) and whether it counts -- the source ray exists, w is finite and in [0, 1]."""
+    s = torch.arange(n, dtype=torch.int64) if perm is None else perm[:n].long()
+    s_ok = (s >= 0) & (s < weights.numel())
+    w = torch.zeros(n, dtype=torch.float64)
+    w[s_ok] = weights[s[s_ok]]
+    return w, s_ok & (w >= 0.0) & (w <= 1.0)
+
+
 def density_error(rows, row_x, row_y, goal, grid, oob_weight=0.0, mask=None, grad=None, err=None,
-                  hq=None, workspace=None, variant=0, dimension=None):
+                  hq=None, workspace=None, variant=0, dimension=None, weights=None, perm=None,
+                  n_source=None):
     """tfrt_density_error: the DensityError of the columns of ``rows`` (k, n), x in row ``row_x``
     and y in row ``row_y`` (-1: one field), against the L2-normalised float64 ``goal`` (ny, nx) or
     (nx,); ``grid`` from ``density_grid``; ``mask``: optional int32, column i counts if
@@ -1349,6 +1371,13 @@ def density_error(rows, row_x, row_y, goal, grid, oob_weight=0.0, mask=None, gra
     CODES: below 2 * dimension a row of the block, from there on the direction cosines of the last
     link (3-D: x_dir, y_dir, z_dir = 6, 7, 8; 2-D: x_dir, y_dir = 4, 5).  With a direction field
     all 2 * dimension rows of ``grad`` are written (the chain rule back onto start and end).
+
+    ``weights`` (tfrt_density_error_weighted): contiguous float64, one radiant power in [0, 1] per
+    SOURCE ray (``n_source`` of them, default all); ``perm``: optional int32 (n,), the source ray
+    of column i (None: column i is source ray i).  A column without a source ray, or whose weight
+    is not finite or not in [0, 1], does not count; every bilinear weight, the gradient and the
+    penalty are multiplied by the ray's weight last.  On return the first nx * ny float64 of a
+    ``workspace`` given hold the pulls D (on the CPU path too).
 
     CUDA tensors run the kernels.  CPU tensors run a torch restatement with the same int64
     fixed-point histogram and the same operation order per ray (``hq`` and the per-ray quantities
@@ -1364,6 +1393,11 @@ def density_error(rows, row_x, row_y, goal, grid, oob_weight=0.0, mask=None, gra
     k, n = rows.shape
     if dimension is not None:
         _check_field_codes("density_error", rows, row_x, row_y, dimension)
+    if weights is not None:
+        _check_weights("density_error", weights, perm, n)
+        n_source = weights.numel() if n_source is None else int(n_source)
+        if not 0 <= n_source <= weights.numel():
+            raise ValueError("density_error: n_source exceeds the weights given")
     dev = rows.device
     if grad is None:
         grad = torch.zeros((k, n), dtype=torch.float64, device=dev)
@@ -1376,15 +1410,25 @@ def density_error(rows, row_x, row_y, goal, grid, oob_weight=0.0, mask=None, gra
     x0, x1, sx, y0, y1, sy = grid
     if not rows.is_cuda:
         _density_error_cpu(rows, row_x, row_y, goal, grid, float(oob_weight), mask, grad, err, hq,
-                           dimension)
+                           dimension, None if weights is None else weights[:n_source], perm,
+                           None if workspace is None
+                           else workspace[:8 * nx * ny].view(torch.float64))
         return err, grad, hq
-    _need_gpu(rows, goal, mask, grad, err, hq)
+    _need_gpu(rows, goal, mask, grad, err, hq, weights, perm)
     if rows.stride(1) != 1 or grad.stride(1) != 1:
         raise ValueError("density_error: rows and grad must have contiguous columns")
     L = _lib.lib()
     wsb = L.tfrt_density_error_workspace_bytes(n, nx, ny)
     if workspace is None:
         workspace = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    if weights is not None:
+        # (the field-code form covers plain rows: codes below 2 * dimension are rows of the block)
+        check(L.tfrt_density_error_weighted(
+            _p(rows), rows.stride(0), n, _DT[rows.dtype], 3 if dimension is None else int(dimension),
+            _p(mask), row_x, row_y, _p(goal), _p(weights), n_source, _p(perm), nx, ny, x0, x1, sx,
+            y0, y1, sy, float(oob_weight), _p(grad), grad.stride(0), _p(err), _p(hq), int(variant),
+            _p(workspace), workspace.numel(), _stream(rows)), "tfrt_density_error_weighted")
+        return err, grad, hq
     if dimension is not None:
         check(L.tfrt_density_error_fields(
             _p(rows), rows.stride(0), n, _DT[rows.dtype], int(dimension), _p(mask), row_x, row_y,
@@ -1406,8 +1450,10 @@ def _density_axis(v, lo, scale, nb):
     return i0.clamp(0, nb - 1), (i0 + 1).clamp(0, nb - 1), u - f
 
 
-def _density_error_cpu(rows, row_x, row_y, goal, grid, oob, mask, grad, err, hq, dimension=None):
-    """The CPU path of ``density_error`` (every torch op rounds on its own, as the kernels do)."""
+def _density_error_cpu(rows, row_x, row_y, goal, grid, oob, mask, grad, err, hq, dimension=None,
+                       weights=None, perm=None, pull=None):
+    """The CPU path of ``density_error`` (every torch op rounds on its own, as the kernels do);
+    ``pull``: nx * ny float64 that receive the pulls D."""
     x0, x1, sx, y0, y1, sy = grid
     two = row_y >= 0
     nx = goal.shape[-1]
@@ -1422,27 +1468,39 @@ def _density_error_cpu(rows, row_x, row_y, goal, grid, oob, mask, grad, err, hq,
         y = rows[row_y].double() if two else torch.zeros_like(x)
     counts = torch.isfinite(x) & torch.isfinite(y)
     if mask is not None:
-        counts &= mask >= 0
+        counts &= mask[:n] >= 0
+    w = None
+    if weights is not None:
+        w, w_ok = _source_weights(weights, perm, n)
+        counts &= w_ok
     out = (x < x0) | (x > x1)
     if two:
         out |= (y < y0) | (y > y1)
     inside, outside = counts & ~out, counts & out
     zero = torch.zeros((), dtype=torch.float64)
-    # outside: the penalty and its derivative
+    # outside: the penalty and its derivative (weighted: each times w last)
     ex = torch.maximum(x0 - x, zero) + torch.maximum(x - x1, zero)
     ey = (torch.maximum(y0 - y, zero) + torch.maximum(y - y1, zero)) if two else torch.zeros_like(x)
-    pen = (oob * (ex * ex + ey * ey))[outside].sum()
-    gx = torch.where(outside, oob * (2.0 * ex) * ((x > x1).double() - (x < x0).double()), zero)
-    gy = torch.where(outside, oob * (2.0 * ey) * ((y > y1).double() - (y < y0).double()), zero) \
-        if two else None
+    pens = oob * (ex * ex + ey * ey)
+    gx = oob * (2.0 * ex) * ((x > x1).double() - (x < x0).double())
+    gy = oob * (2.0 * ey) * ((y > y1).double() - (y < y0).double()) if two else None
+    if w is not None:
+        pens, gx = pens * w, gx * w
+        gy = gy * w if two else None
+    pen = pens[outside].sum()
+    gx = torch.where(outside, gx, zero)
+    gy = torch.where(outside, gy, zero) if two else None
     # inside: the fixed-point histogram
     xi, yi = x[inside], y[inside]
+    wi = w[inside] if w is not None else None
     ia, ib, tx = _density_axis(xi, x0, sx, nx)
     flat = hq.view(-1)
     flat.zero_()
 
-    def splat(index, w):
-        flat.index_add_(0, index, torch.round(w * DENSITY_FIXED_ONE).long())
+    def splat(index, b):
+        if wi is not None:
+            b = b * wi
+        flat.index_add_(0, index, torch.round(b * DENSITY_FIXED_ONE).long())
     if two:
         ja, jb, ty = _density_axis(yi, y0, sy, goal.shape[0])
         wx0, wx1, wy0, wy1 = 1.0 - tx, tx, 1.0 - ty, ty
@@ -1463,12 +1521,16 @@ def _density_error_cpu(rows, row_x, row_y, goal, grid, oob, mask, grad, err, hq,
         r = h - g
         e_hist = (r * r).sum()
         D = (2.0 / s) * (r - h * (h * r).sum())
+    if pull is not None:
+        pull.copy_(D)
     if two:
         d00, d01, d10, d11 = D[ja * nx + ia], D[ja * nx + ib], D[jb * nx + ia], D[jb * nx + ib]
-        gx[inside] = sx * ((1.0 - ty) * (d01 - d00) + ty * (d11 - d10))
-        gy[inside] = sy * ((1.0 - tx) * (d10 - d00) + tx * (d11 - d01))
+        gxi = sx * ((1.0 - ty) * (d01 - d00) + ty * (d11 - d10))
+        gyi = sy * ((1.0 - tx) * (d10 - d00) + tx * (d11 - d01))
+        gy[inside] = gyi if wi is None else gyi * wi
     else:
-        gx[inside] = sx * (D[ib] - D[ia])
+        gxi = sx * (D[ib] - D[ia])
+    gx[inside] = gxi if wi is None else gxi * wi
     if link is not None:
         _chain_cpu(grad, n, dimension, row_x, row_y, gx, gy, link, counts)
     else:
@@ -1481,12 +1543,22 @@ def _density_error_cpu(rows, row_x, row_y, goal, grid, oob, mask, grad, err, hq,
 
 SPOT_MAX_GROUPS = 1 << 20
 SPOT_LDS_GROUPS = 1024
+SPOT_WEIGHTED_LDS_GROUPS = 512     # tfrt_spot_error_weighted: six planes, the same 24 KiB
+SPOT_MAX_WBITS = 20
 
 
 def spot_qbits(n_source):
     """Fraction bits of tfrt_spot_error's fixed point for a source of ``n_source`` rays:
     n_source * 2^qbits < 2^62, at most 52."""
     return min(52, 62 - int(n_source).bit_length())
+
+
+def spot_wbits(n_source):
+    """Fraction bits of tfrt_spot_error_weighted's quantised weight for a source of ``n_source``
+    rays: n_source * 2^wbits * 2^ceil(qbits / 2) < 2^62 with ``qbits = spot_qbits(n_source)``, at
+    most 20."""
+    qbits = spot_qbits(n_source)
+    return min(SPOT_MAX_WBITS, 62 - int(n_source).bit_length() - (qbits + 1) // 2)
 
 
 def spot_grid(domain, qbits):
@@ -1503,7 +1575,7 @@ def spot_grid(domain, qbits):
 
 def spot_error(rows, row_x, row_y, group, n_groups, grid, oob_weight=0.0, mask=None, perm=None,
                grad=None, err=None, acc=None, variant=0, workspace=None, qbits=None,
-               dimension=None):
+               dimension=None, weights=None, wbits=None):
     """tfrt_spot_error: the SpotError of the columns of ``rows`` (k, n), x in row ``row_x`` and y
     in row ``row_y`` (-1: one field).  ``group``: contiguous int32 labels, one per SOURCE ray;
     ``perm``: optional int32 (n,), the source ray of column i (None: column i is source ray i);
@@ -1518,6 +1590,12 @@ def spot_error(rows, row_x, row_y, group, n_groups, grid, oob_weight=0.0, mask=N
     block and ``row_x`` / ``row_y`` are FIELD CODES, as for ``density_error``; with a direction
     field all 2 * dimension rows of ``grad`` are written and the centroids are mean direction
     cosines.
+
+    ``weights`` (tfrt_spot_error_weighted): contiguous float64, one radiant power in [0, 1] per
+    SOURCE ray, as many as labels; ``wbits``: the fraction bits of the quantised weight
+    ``wq = rint(w * 2**wbits)`` (None: ``spot_wbits(group.numel())``).  ``acc`` is then (G, 8)
+    int64 ``{W, Xhi, Xlo, Yhi, Ylo, count, 0, 0}``, the centroids are weighted means, and terms,
+    gradient and penalty carry ``wr = wq * 2**-wbits``.
 
     CUDA tensors run the kernels.  CPU tensors run a torch restatement with the same int64 fixed
     point and the same operations per ray, each rounded on its own (``acc`` and the gradient rows
@@ -1536,6 +1614,14 @@ def spot_error(rows, row_x, row_y, group, n_groups, grid, oob_weight=0.0, mask=N
         raise ValueError("spot_error: perm must be contiguous int32, one entry per column")
     if qbits is None:
         qbits = spot_qbits(group.numel())
+    record = 4
+    if weights is not None:
+        _check_weights("spot_error", weights, None, n)
+        if weights.numel() != group.numel():
+            raise ValueError("spot_error: one weight per label")
+        if wbits is None:
+            wbits = spot_wbits(group.numel())
+        record = 8
     dev = rows.device
     if grad is None:
         grad = torch.zeros((k, n), dtype=torch.float64, device=dev)
@@ -1544,23 +1630,39 @@ def spot_error(rows, row_x, row_y, group, n_groups, grid, oob_weight=0.0, mask=N
     if err is None:
         err = torch.empty(3, dtype=torch.float64, device=dev)
     if acc is None:
-        acc = torch.empty((n_groups, 4), dtype=torch.int64, device=dev)
-    if tuple(acc.shape) != (n_groups, 4) or acc.dtype != torch.int64 or not acc.is_contiguous():
-        raise ValueError("spot_error: acc must be contiguous int64 of shape (n_groups, 4)")
+        acc = torch.empty((n_groups, record), dtype=torch.int64, device=dev)
+    if tuple(acc.shape) != (n_groups, record) or acc.dtype != torch.int64 \
+            or not acc.is_contiguous():
+        raise ValueError(f"spot_error: acc must be contiguous int64 of shape (n_groups, {record})")
     x0, x1, qsx, y0, y1, qsy = grid
     if not rows.is_cuda:
-        if not 1 <= qbits <= 52 or n >= 1 << (62 - qbits):
+        if weights is not None:
+            if not 1 <= qbits <= 52 or not 1 <= wbits <= SPOT_MAX_WBITS \
+                    or n >= 1 << (62 - wbits - (qbits + 1) // 2):
+                raise ValueError("spot_error: qbits must lie in 1 .. 52 and wbits in 1 .. 20 with "
+                                 "n < 2^(62 - wbits - ceil(qbits / 2))")
+        elif not 1 <= qbits <= 52 or n >= 1 << (62 - qbits):
             raise ValueError("spot_error: qbits must lie in 1 .. 52 with n < 2^(62 - qbits)")
         _spot_error_cpu(rows, row_x, row_y, group, n_groups, grid, float(oob_weight), mask, perm,
-                        grad, err, acc, int(qbits), dimension)
+                        grad, err, acc, int(qbits), dimension, weights,
+                        None if wbits is None else int(wbits))
         return err, grad, acc
-    _need_gpu(rows, group, mask, perm, grad, err, acc)
+    _need_gpu(rows, group, mask, perm, grad, err, acc, weights)
     if rows.stride(1) != 1 or grad.stride(1) != 1:
         raise ValueError("spot_error: rows and grad must have contiguous columns")
     L = _lib.lib()
     wsb = L.tfrt_spot_error_workspace_bytes(n, n_groups)
     if workspace is None:
         workspace = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    if weights is not None:
+        # (the field-code form covers plain rows: codes below 2 * dimension are rows of the block)
+        check(L.tfrt_spot_error_weighted(
+            _p(rows), rows.stride(0), n, _DT[rows.dtype], 3 if dimension is None else int(dimension),
+            _p(mask), row_x, row_y, _p(group), _p(weights), int(wbits), group.numel(), _p(perm),
+            n_groups, x0, x1, qsx, y0, y1, qsy, int(qbits), float(oob_weight), _p(grad),
+            grad.stride(0), _p(err), _p(acc), int(variant), _p(workspace), workspace.numel(),
+            _stream(rows)), "tfrt_spot_error_weighted")
+        return err, grad, acc
     if dimension is not None:
         check(L.tfrt_spot_error_fields(
             _p(rows), rows.stride(0), n, _DT[rows.dtype], int(dimension), _p(mask), row_x, row_y,
@@ -1576,10 +1678,22 @@ def spot_error(rows, row_x, row_y, group, n_groups, grid, oob_weight=0.0, mask=N
     return err, grad, acc
 
 
-def spot_centroids(acc, grid, fields=2):
+def spot_centroids(acc, grid, fields=2, qbits=None):
     """The (G, fields) float64 centroids of a tfrt_spot_error record table:
-    ``x0 + (Sx / count) / qsx``, NaN for a group without rays."""
+    ``x0 + (Sx / count) / qsx``, NaN for a group without rays.  A table of eight-slot records
+    (tfrt_spot_error_weighted; it needs the ``qbits`` of the evaluation for ``h = qbits // 2``):
+    ``x0 + ((ldexp(Xhi, h) + Xlo) / W) / qsx``, NaN for a group without weight."""
     x0, _, qsx, y0, _, qsy = grid
+    if acc.shape[1] == 8:
+        if qbits is None:
+            raise ValueError("spot_centroids: eight-slot records need qbits")
+        lift = float(np.ldexp(1.0, int(qbits) // 2))       # (times 2^h: exact)
+        W = acc[:, 0].double()
+        W = torch.where(W > 0, W, torch.full_like(W, float("nan")))
+        cols = [x0 + ((acc[:, 1].double() * lift + acc[:, 2].double()) / W) / qsx]
+        if fields == 2:
+            cols.append(y0 + ((acc[:, 3].double() * lift + acc[:, 4].double()) / W) / qsy)
+        return torch.stack(cols, dim=1)
     cnt = acc[:, 0].double()
     cnt = torch.where(cnt > 0, cnt, torch.full_like(cnt, float("nan")))
     cols = [x0 + (acc[:, 1].double() / cnt) / qsx]
@@ -1589,7 +1703,7 @@ def spot_centroids(acc, grid, fields=2):
 
 
 def _spot_error_cpu(rows, row_x, row_y, group, n_groups, grid, oob, mask, perm, grad, err, acc,
-                    qbits, dimension=None):
+                    qbits, dimension=None, weights=None, wbits=None):
     """The CPU path of ``spot_error`` (every torch op rounds on its own, as the kernels do)."""
     x0, x1, qsx, y0, y1, qsy = grid
     two = row_y >= 0
@@ -1610,32 +1724,68 @@ def _spot_error_cpu(rows, row_x, row_y, group, n_groups, grid, oob, mask, perm, 
     label = torch.full((n,), -1, dtype=torch.int64)
     label[s_ok] = group[s[s_ok]].long()
     spot = counting & finite & s_ok & (label >= 0) & (label < n_groups)
+    wq = wr = None
+    if weights is not None:
+        # wq = rint(w * 2^wbits), half to even; wr = wq * 2^-wbits is the weight everywhere
+        w, w_ok = _source_weights(weights, perm, n)
+        wq = torch.where(w_ok, torch.round(w * float(np.ldexp(1.0, wbits))), torch.zeros_like(w))
+        wr = wq * float(np.ldexp(1.0, -wbits))
+        spot &= wq > 0
     out = (x < x0) | (x > x1)
     if two:
         out |= (y < y0) | (y > y1)
     inside, outside = spot & ~out, spot & out
     zero = torch.zeros((), dtype=torch.float64)
-    # outside: the penalty and its derivative
+    # outside: the penalty and its derivative (weighted: each times wr last)
     ex = torch.maximum(x0 - x, zero) + torch.maximum(x - x1, zero)
     ey = (torch.maximum(y0 - y, zero) + torch.maximum(y - y1, zero)) if two else torch.zeros_like(x)
-    pen = (oob * (ex * ex + ey * ey))[outside].sum()
-    gx = torch.where(outside, oob * (2.0 * ex) * ((x > x1).double() - (x < x0).double()), zero)
-    gy = torch.where(outside, oob * (2.0 * ey) * ((y > y1).double() - (y < y0).double()), zero)
+    pens = oob * (ex * ex + ey * ey)
+    gx = oob * (2.0 * ex) * ((x > x1).double() - (x < x0).double())
+    gy = oob * (2.0 * ey) * ((y > y1).double() - (y < y0).double())
+    if wr is not None:
+        pens, gx, gy = pens * wr, gx * wr, gy * wr
+    pen = pens[outside].sum()
+    gx = torch.where(outside, gx, zero)
+    gy = torch.where(outside, gy, zero)
     # inside: the fixed-point records
     xi, yi, li = x[inside], y[inside], label[inside]
     acc.zero_()
-    acc[:, 0].index_add_(0, li, torch.ones_like(li))
-    acc[:, 1].index_add_(0, li, torch.round((xi - x0) * qsx).clamp(0.0, qmax).long())
-    if two:
-        acc[:, 2].index_add_(0, li, torch.round((yi - y0) * qsy).clamp(0.0, qmax).long())
-    cnt = acc[li, 0].double()
-    dx = xi - (x0 + (acc[li, 1].double() / cnt) / qsx)
-    gx[inside] = 2.0 * dx
-    terms = dx * dx
-    if two:
-        dy = yi - (y0 + (acc[li, 2].double() / cnt) / qsy)
-        gy[inside] = 2.0 * dy
-        terms = terms + dy * dy
+    qxi = torch.round((xi - x0) * qsx).clamp(0.0, qmax).long()
+    qyi = torch.round((yi - y0) * qsy).clamp(0.0, qmax).long() if two else None
+    if wr is not None:
+        # records {W, Xhi, Xlo, Yhi, Ylo, count, 0, 0}: wq * q in two limbs of h and qbits - h bits
+        h = qbits // 2
+        low = (1 << h) - 1
+        lift = float(np.ldexp(1.0, h))
+        wqi, wri = wq[inside].long(), wr[inside]
+        acc[:, 0].index_add_(0, li, wqi)
+        acc[:, 1].index_add_(0, li, wqi * (qxi >> h))
+        acc[:, 2].index_add_(0, li, wqi * (qxi & low))
+        if two:
+            acc[:, 3].index_add_(0, li, wqi * (qyi >> h))
+            acc[:, 4].index_add_(0, li, wqi * (qyi & low))
+        acc[:, 5].index_add_(0, li, torch.ones_like(li))
+        W = acc[li, 0].double()
+        dx = xi - (x0 + ((acc[li, 1].double() * lift + acc[li, 2].double()) / W) / qsx)
+        gx[inside] = (2.0 * dx) * wri
+        terms = wri * (dx * dx)
+        if two:
+            dy = yi - (y0 + ((acc[li, 3].double() * lift + acc[li, 4].double()) / W) / qsy)
+            gy[inside] = (2.0 * dy) * wri
+            terms = terms + wri * (dy * dy)
+    else:
+        acc[:, 0].index_add_(0, li, torch.ones_like(li))
+        acc[:, 1].index_add_(0, li, qxi)
+        if two:
+            acc[:, 2].index_add_(0, li, qyi)
+        cnt = acc[li, 0].double()
+        dx = xi - (x0 + (acc[li, 1].double() / cnt) / qsx)
+        gx[inside] = 2.0 * dx
+        terms = dx * dx
+        if two:
+            dy = yi - (y0 + (acc[li, 2].double() / cnt) / qsy)
+            gy[inside] = 2.0 * dy
+            terms = terms + dy * dy
     if link is not None:
         _chain_cpu(grad, n, dimension, row_x, row_y, gx, gy, link, spot)
     else:

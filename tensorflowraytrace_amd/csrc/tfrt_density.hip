@@ -13,11 +13,7 @@
 //
 // Four launches:
 //
-//   k_density_clear   zeroes Hq.  A launch, not a memset node, as in tfrt_spot.hip: replayed inside
-//                     a step's graph behind a source that is re-drawn in the graph, the memset
-//                     node left every bin of the examples' histograms with a stale 2^46 (16,384
-//                     rays' worth) under the weights added; a kernel node in the same place clears
-//                     them.  The cause is not known; the node costs what a memset node costs.
+//   k_error_clear     zeroes Hq.  A launch, not a memset node: why, at the kernel (error_sums.h).
 //   k_density_splat   one lane per column (a fixed grid for n, grid-stride): weights -> Hq, and the
 //                     out-of-domain penalty as one partial sum per workgroup.  Two variants:
 //                     <true>  bins <= DENSITY_LDS_BINS: a per-workgroup int64 histogram in LDS
@@ -44,11 +40,17 @@
 // Weighted (tfrt_density_error_weighted): every source ray carries a radiant power w in [0, 1],
 // looked up once per column through `perm`; a bilinear weight enters its bin as
 // rint((b * w) * 2^32), gradient and penalty are multiplied by w last, and the bins launch is the
-// unweighted one on the weighted histogram.  The splat and the seed are sibling kernels
-// (k_density_splat_weighted, k_density_seed_weighted) with the weights as one more argument; the
-// unweighted kernels are untouched.
+// unweighted one on the weighted histogram.  The splat, the seed and the classification they share
+// have a `bool WEIGHTED` template parameter: everything that touches w stands under
+// `if constexpr (WEIGHTED)`, and the weights are a base of the kernels' constants that is empty
+// without them (DensityArgs), so the unweighted instantiations neither receive nor read a weight.
+//
+// What this file shares with tfrt_spot.hip -- the fixed-shape workgroup sum, the clear kernel, the
+// out-of-domain axis, the grid size, the argument checks, the dispatch on the direction fields --
+// is in error_sums.h.
 #include "tfrt_common.h"
 #include "direction_fields.h"
+#include "error_sums.h"
 
 namespace tfrt {
 
@@ -72,8 +74,15 @@ struct DensityWeights {
   int64_t n_source;
 };
 
-// What one column does.  kind 0: does not count (masked, or a non-finite coordinate); 1: inside
-// the closed domain, spread over (ja|jb, ia|ib) with tx, ty; 2: outside, ex / ey and their signs.
+// The constants of a splat or seed launch: the grid, then (WEIGHTED) the weights.
+template <bool WEIGHTED>
+struct DensityArgs : DensityGrid, weights_base<WEIGHTED, DensityWeights> {
+  static constexpr bool weighted = WEIGHTED;
+};
+
+// What one column does.  kind 0: does not count (masked, or a non-finite coordinate; WEIGHTED: or
+// no weight that counts); 1: inside the closed domain, spread over (ja|jb, ia|ib) with tx, ty;
+// 2: outside, ex / ey and their signs.
 struct DensityRay {
   int kind;
   int ia, ib, ja, jb;
@@ -93,53 +102,46 @@ __device__ __forceinline__ void density_axis(double v, double lo, double scale, 
   b = min(max(i0 + 1, 0), nb - 1);
 }
 
-template <typename T, int DIM>
+// WEIGHTED: `w` receives the weight of the column's source ray (it is left alone without), and a
+// column that counts (kinds 1 and 2) without a source ray or with a weight outside [0, 1] does not
+// count (kind 0 -- "does not count" ends alike wherever it is found, so the order of the checks
+// does not show).  Nothing is read out of bounds, whatever perm holds.
+template <typename T, int DIM, bool WEIGHTED>
 __device__ __forceinline__ DensityRay density_classify(const T* __restrict__ rows, int64_t stride,
                                                        const int32_t* __restrict__ mask, int64_t i,
-                                                       const DensityGrid& g, LinkDir<DIM>& link) {
+                                                       const DensityArgs<WEIGHTED>& g,
+                                                       LinkDir<DIM>& link, double& w) {
 #pragma clang fp contract(off)
   DensityRay r;
   r.kind = 0;
   r.ia = r.ib = r.ja = r.jb = 0;
   r.tx = r.ty = r.dx = r.dy = 0.0;
-  if (mask != nullptr && mask[i] < 0) return r;
-  const bool two = g.row_y >= 0;
-  double x, y;
-  read_fields<T, DIM>(rows, stride, i, g.row_x, g.row_y, x, y, link);
-  if (!isfinite(x) || !isfinite(y)) return r;
-  const bool out = x < g.x0 || x > g.x1 || (two && (y < g.y0 || y > g.y1));
-  if (out) {
-    r.kind = 2;
-    r.tx = fmax(g.x0 - x, 0.0) + fmax(x - g.x1, 0.0);
-    r.dx = x < g.x0 ? -1.0 : (x > g.x1 ? 1.0 : 0.0);
-    if (two) {
-      r.ty = fmax(g.y0 - y, 0.0) + fmax(y - g.y1, 0.0);
-      r.dy = y < g.y0 ? -1.0 : (y > g.y1 ? 1.0 : 0.0);
+  if (mask == nullptr || mask[i] >= 0) {
+    const bool two = g.row_y >= 0;
+    double x, y;
+    read_fields<T, DIM>(rows, stride, i, g.row_x, g.row_y, x, y, link);
+    if (isfinite(x) && isfinite(y)) {
+      const bool out = x < g.x0 || x > g.x1 || (two && (y < g.y0 || y > g.y1));
+      if (out) {
+        r.kind = 2;
+        r.tx = outside_by(x, g.x0, g.x1), r.dx = outside_sign(x, g.x0, g.x1);
+        if (two) r.ty = outside_by(y, g.y0, g.y1), r.dy = outside_sign(y, g.y0, g.y1);
+      } else {
+        r.kind = 1;
+        density_axis(x, g.x0, g.sx, g.nx, r.ia, r.ib, r.tx);
+        if (two) density_axis(y, g.y0, g.sy, g.ny, r.ja, r.jb, r.ty);
+      }
     }
-    return r;
   }
-  r.kind = 1;
-  density_axis(x, g.x0, g.sx, g.nx, r.ia, r.ib, r.tx);
-  if (two) density_axis(y, g.y0, g.sy, g.ny, r.ja, r.jb, r.ty);
-  return r;
-}
-
-// The same for tfrt_density_error_weighted: a column that counts (kinds 1 and 2) without a source
-// ray or with a weight outside [0, 1] does not count (kind 0 -- "does not count" ends alike
-// wherever it is found, so the order of the checks does not show).  Nothing is read out of bounds,
-// whatever perm holds.
-template <typename T, int DIM>
-__device__ __forceinline__ DensityRay density_classify_weighted(
-    const T* __restrict__ rows, int64_t stride, const int32_t* __restrict__ mask, int64_t i,
-    const DensityGrid& g, const DensityWeights& wt, LinkDir<DIM>& link, double& w) {
-  DensityRay r = density_classify<T, DIM>(rows, stride, mask, i, g, link);
-  w = 0.0;
-  if (r.kind != 0) {
-    const int64_t s = wt.perm != nullptr ? (int64_t)wt.perm[i] : i;
-    const bool has = s >= 0 && s < wt.n_source;
-    // (a NaN fails both comparisons)
-    if (has) w = wt.weight[s];
-    if (!has || !(w >= 0.0 && w <= 1.0)) r.kind = 0;
+  if constexpr (WEIGHTED) {
+    w = 0.0;
+    if (r.kind != 0) {
+      const int64_t s = g.perm != nullptr ? (int64_t)g.perm[i] : i;
+      const bool has = s >= 0 && s < g.n_source;
+      // (a NaN fails both comparisons)
+      if (has) w = g.weight[s];
+      if (!has || !(w >= 0.0 && w <= 1.0)) r.kind = 0;
+    }
   }
   return r;
 }
@@ -150,32 +152,11 @@ __device__ __forceinline__ unsigned long long density_fixed(double w) {
   return (unsigned long long)(long long)rint(w * 4294967296.0);
 }
 
-// fixed-shape sum over a workgroup of NW waves: xor butterflies inside the wave, waves in index
-// order; every thread of the workgroup must call it.  `wsum` is reused: a barrier at the end.
-template <int NW>
-__device__ __forceinline__ double density_block_sum(double v, double* wsum) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-  if (lane_id() == 0) wsum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < NW; ++w) s += wsum[w];
-  __syncthreads();
-  return s;
-}
-
-// The histogram, cleared in front of the adds.
-__global__ __launch_bounds__(BLOCK) void k_density_clear(unsigned long long* __restrict__ hq,
-                                                         int bins) {
-  const int b = blockIdx.x * BLOCK + threadIdx.x;
-  if (b < bins) hq[b] = 0ull;
-}
-
-template <typename T, bool LDS, int DIM>
+// WEIGHTED: every bilinear weight and the penalty times w last.
+template <typename T, bool LDS, int DIM, bool WEIGHTED>
 __global__ __launch_bounds__(BLOCK) void k_density_splat(
     const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
-    DensityGrid g, unsigned long long* __restrict__ hq, double* __restrict__ partial) {
+    DensityArgs<WEIGHTED> g, unsigned long long* __restrict__ hq, double* __restrict__ partial) {
 #pragma clang fp contract(off)
   extern __shared__ unsigned long long hist[];
   __shared__ double wsum[WAVES];
@@ -189,20 +170,21 @@ __global__ __launch_bounds__(BLOCK) void k_density_splat(
   for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * BLOCK) {
     LinkDir<DIM> link;
-    const DensityRay r = density_classify<T, DIM>(rows, stride, mask, i, g, link);
+    double w = 0.0;
+    const DensityRay r = density_classify<T, DIM, WEIGHTED>(rows, stride, mask, i, g, link, w);
     if (r.kind == 2) {
-      pen += g.oob * (r.tx * r.tx + r.ty * r.ty);
+      pen += weighed<WEIGHTED>(g.oob * (r.tx * r.tx + r.ty * r.ty), w);
     } else if (r.kind == 1) {
       const double wx0 = 1.0 - r.tx, wx1 = r.tx;
       if (g.row_y >= 0) {
         const double wy0 = 1.0 - r.ty, wy1 = r.ty;
-        atomicAdd(&dst[r.ja * g.nx + r.ia], density_fixed(wy0 * wx0));
-        atomicAdd(&dst[r.ja * g.nx + r.ib], density_fixed(wy0 * wx1));
-        atomicAdd(&dst[r.jb * g.nx + r.ia], density_fixed(wy1 * wx0));
-        atomicAdd(&dst[r.jb * g.nx + r.ib], density_fixed(wy1 * wx1));
+        atomicAdd(&dst[r.ja * g.nx + r.ia], density_fixed(weighed<WEIGHTED>(wy0 * wx0, w)));
+        atomicAdd(&dst[r.ja * g.nx + r.ib], density_fixed(weighed<WEIGHTED>(wy0 * wx1, w)));
+        atomicAdd(&dst[r.jb * g.nx + r.ia], density_fixed(weighed<WEIGHTED>(wy1 * wx0, w)));
+        atomicAdd(&dst[r.jb * g.nx + r.ib], density_fixed(weighed<WEIGHTED>(wy1 * wx1, w)));
       } else {
-        atomicAdd(&dst[r.ia], density_fixed(wx0));
-        atomicAdd(&dst[r.ib], density_fixed(wx1));
+        atomicAdd(&dst[r.ia], density_fixed(weighed<WEIGHTED>(wx0, w)));
+        atomicAdd(&dst[r.ib], density_fixed(weighed<WEIGHTED>(wx1, w)));
       }
     }
   }
@@ -213,55 +195,7 @@ __global__ __launch_bounds__(BLOCK) void k_density_splat(
       if (v != 0ull) atomicAdd(&hq[b], v);
     }
   }
-  const double s = density_block_sum<WAVES>(pen, wsum);
-  if (threadIdx.x == 0) partial[blockIdx.x] = s;
-}
-
-// tfrt_density_error_weighted's splat: every bilinear weight and the penalty times w last.
-template <typename T, bool LDS, int DIM>
-__global__ __launch_bounds__(BLOCK) void k_density_splat_weighted(
-    const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
-    DensityGrid g, DensityWeights wt, unsigned long long* __restrict__ hq,
-    double* __restrict__ partial) {
-#pragma clang fp contract(off)
-  extern __shared__ unsigned long long hist[];
-  __shared__ double wsum[WAVES];
-  const int bins = g.nx * g.ny;
-  if (LDS) {
-    for (int b = threadIdx.x; b < bins; b += BLOCK) hist[b] = 0ull;
-    __syncthreads();
-  }
-  unsigned long long* dst = LDS ? hist : hq;
-  double pen = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * BLOCK) {
-    LinkDir<DIM> link;
-    double w;
-    const DensityRay r = density_classify_weighted<T, DIM>(rows, stride, mask, i, g, wt, link, w);
-    if (r.kind == 2) {
-      pen += (g.oob * (r.tx * r.tx + r.ty * r.ty)) * w;
-    } else if (r.kind == 1) {
-      const double wx0 = 1.0 - r.tx, wx1 = r.tx;
-      if (g.row_y >= 0) {
-        const double wy0 = 1.0 - r.ty, wy1 = r.ty;
-        atomicAdd(&dst[r.ja * g.nx + r.ia], density_fixed((wy0 * wx0) * w));
-        atomicAdd(&dst[r.ja * g.nx + r.ib], density_fixed((wy0 * wx1) * w));
-        atomicAdd(&dst[r.jb * g.nx + r.ia], density_fixed((wy1 * wx0) * w));
-        atomicAdd(&dst[r.jb * g.nx + r.ib], density_fixed((wy1 * wx1) * w));
-      } else {
-        atomicAdd(&dst[r.ia], density_fixed(wx0 * w));
-        atomicAdd(&dst[r.ib], density_fixed(wx1 * w));
-      }
-    }
-  }
-  if (LDS) {
-    __syncthreads();
-    for (int b = threadIdx.x; b < bins; b += BLOCK) {
-      const unsigned long long v = hist[b];
-      if (v != 0ull) atomicAdd(&hq[b], v);
-    }
-  }
-  const double s = density_block_sum<WAVES>(pen, wsum);
+  const double s = error_block_sum<WAVES>(pen, wsum);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -282,9 +216,9 @@ __global__ __launch_bounds__(BINS_BLOCK) void k_density_bins(
     gg += gb * gb;
   }
   for (int b = t; b < n_partial; b += BINS_BLOCK) pen += partial[b];
-  hh = density_block_sum<BINS_WAVES>(hh, wsum);
-  gg = density_block_sum<BINS_WAVES>(gg, wsum);
-  pen = density_block_sum<BINS_WAVES>(pen, wsum);
+  hh = error_block_sum<BINS_WAVES>(hh, wsum);
+  gg = error_block_sum<BINS_WAVES>(gg, wsum);
+  pen = error_block_sum<BINS_WAVES>(pen, wsum);
   const double s = sqrt(hh);
   double e_hist;
   if (s == 0.0) {
@@ -298,8 +232,8 @@ __global__ __launch_bounds__(BINS_BLOCK) void k_density_bins(
       rr += r * r;
       hr += h * r;
     }
-    rr = density_block_sum<BINS_WAVES>(rr, wsum);
-    hr = density_block_sum<BINS_WAVES>(hr, wsum);
+    rr = error_block_sum<BINS_WAVES>(rr, wsum);
+    hr = error_block_sum<BINS_WAVES>(hr, wsum);
     const double k = 2.0 / s;
     for (int b = t; b < bins; b += BINS_BLOCK) {
       const double h = ((double)hq[b] / 4294967296.0) / s;
@@ -316,29 +250,31 @@ __global__ __launch_bounds__(BINS_BLOCK) void k_density_bins(
   }
 }
 
-template <typename T, int DIM>
+// WEIGHTED: gx, gy times w last, in front of the chain rule.
+template <typename T, int DIM, bool WEIGHTED>
 __global__ __launch_bounds__(BLOCK) void k_density_seed(
     const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
-    DensityGrid g, const double* __restrict__ pull, double* __restrict__ grad,
+    DensityArgs<WEIGHTED> g, const double* __restrict__ pull, double* __restrict__ grad,
     int64_t grad_stride) {
 #pragma clang fp contract(off)
   const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
   if (i >= n) return;
   LinkDir<DIM> link;
-  const DensityRay r = density_classify<T, DIM>(rows, stride, mask, i, g, link);
+  double w = 0.0;
+  const DensityRay r = density_classify<T, DIM, WEIGHTED>(rows, stride, mask, i, g, link, w);
   const bool two = g.row_y >= 0;
   double gx = 0.0, gy = 0.0;
   if (r.kind == 2) {
-    gx = g.oob * (2.0 * r.tx) * r.dx;
-    gy = g.oob * (2.0 * r.ty) * r.dy;
+    gx = weighed<WEIGHTED>(g.oob * (2.0 * r.tx) * r.dx, w);
+    gy = weighed<WEIGHTED>(g.oob * (2.0 * r.ty) * r.dy, w);
   } else if (r.kind == 1) {
     if (two) {
       const double d00 = pull[r.ja * g.nx + r.ia], d01 = pull[r.ja * g.nx + r.ib];
       const double d10 = pull[r.jb * g.nx + r.ia], d11 = pull[r.jb * g.nx + r.ib];
-      gx = g.sx * ((1.0 - r.ty) * (d01 - d00) + r.ty * (d11 - d10));
-      gy = g.sy * ((1.0 - r.tx) * (d10 - d00) + r.tx * (d11 - d01));
+      gx = weighed<WEIGHTED>(g.sx * ((1.0 - r.ty) * (d01 - d00) + r.ty * (d11 - d10)), w);
+      gy = weighed<WEIGHTED>(g.sy * ((1.0 - r.tx) * (d10 - d00) + r.tx * (d11 - d01)), w);
     } else {
-      gx = g.sx * (pull[r.ib] - pull[r.ia]);
+      gx = weighed<WEIGHTED>(g.sx * (pull[r.ib] - pull[r.ia]), w);
     }
   }
   if constexpr (DIM != 0) {
@@ -350,89 +286,11 @@ __global__ __launch_bounds__(BLOCK) void k_density_seed(
   }
 }
 
-// tfrt_density_error_weighted's seed: gx, gy times w last, in front of the chain rule.
-template <typename T, int DIM>
-__global__ __launch_bounds__(BLOCK) void k_density_seed_weighted(
-    const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
-    DensityGrid g, DensityWeights wt, const double* __restrict__ pull, double* __restrict__ grad,
-    int64_t grad_stride) {
-#pragma clang fp contract(off)
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= n) return;
-  LinkDir<DIM> link;
-  double w;
-  const DensityRay r = density_classify_weighted<T, DIM>(rows, stride, mask, i, g, wt, link, w);
-  const bool two = g.row_y >= 0;
-  double gx = 0.0, gy = 0.0;
-  if (r.kind == 2) {
-    gx = (g.oob * (2.0 * r.tx) * r.dx) * w;
-    gy = (g.oob * (2.0 * r.ty) * r.dy) * w;
-  } else if (r.kind == 1) {
-    if (two) {
-      const double d00 = pull[r.ja * g.nx + r.ia], d01 = pull[r.ja * g.nx + r.ib];
-      const double d10 = pull[r.jb * g.nx + r.ia], d11 = pull[r.jb * g.nx + r.ib];
-      gx = (g.sx * ((1.0 - r.ty) * (d01 - d00) + r.ty * (d11 - d10))) * w;
-      gy = (g.sy * ((1.0 - r.tx) * (d10 - d00) + r.tx * (d11 - d01))) * w;
-    } else {
-      gx = (g.sx * (pull[r.ib] - pull[r.ia])) * w;
-    }
-  }
-  if constexpr (DIM != 0) {
-    chain_fields<DIM>(link, r.kind != 0, g.row_x, g.row_y, gx, gy, grad, grad_stride, i);
-  } else {
-    grad[(int64_t)g.row_x * grad_stride + i] = gx;
-    if (two) grad[(int64_t)g.row_y * grad_stride + i] = gy;
-  }
-}
-
-static int density_grid(int64_t n) {
-  if (n <= 0) return 0;
-  const int64_t want = (n + DENSITY_RAYS_PER_BLOCK - 1) / DENSITY_RAYS_PER_BLOCK;
-  return (int)(want < DENSITY_MAX_GRID ? want : DENSITY_MAX_GRID);
-}
-
 }  // namespace tfrt
 
 using namespace tfrt;
 
 extern "C" size_t tfrt_density_error_workspace_bytes(int64_t n, int32_t nx, int32_t ny);
-
-// The launches of every entry (`wt` null: unweighted).  `dim` and the codes have been checked by
-// the caller.
-template <typename T, int DIM>
-static void density_launch(const T* r, int64_t stride, int64_t n, const int32_t* mask,
-                           const DensityGrid& g, const DensityWeights* wt, bool lds, int bins,
-                           int grid, int nblk,
-                           unsigned long long* hqu, const double* goal, double* pull,
-                           double* partial, double* grad, int64_t grad_stride, double* error_out,
-                           hipStream_t st) {
-  if (grid > 0 && wt != nullptr) {
-    if (lds)
-      hipLaunchKernelGGL((k_density_splat_weighted<T, true, DIM>), dim3(grid), dim3(BLOCK),
-                         (size_t)bins * sizeof(unsigned long long), st, r, stride, n, mask, g, *wt,
-                         hqu, partial);
-    else
-      hipLaunchKernelGGL((k_density_splat_weighted<T, false, DIM>), dim3(grid), dim3(BLOCK), 0, st,
-                         r, stride, n, mask, g, *wt, hqu, partial);
-  } else if (grid > 0) {
-    if (lds)
-      hipLaunchKernelGGL((k_density_splat<T, true, DIM>), dim3(grid), dim3(BLOCK),
-                         (size_t)bins * sizeof(unsigned long long), st, r, stride, n, mask, g, hqu,
-                         partial);
-    else
-      hipLaunchKernelGGL((k_density_splat<T, false, DIM>), dim3(grid), dim3(BLOCK), 0, st, r,
-                         stride, n, mask, g, hqu, partial);
-  }
-  hipLaunchKernelGGL(k_density_bins, dim3(1), dim3(BINS_BLOCK), 0, st,
-                     reinterpret_cast<const long long*>(hqu), goal, bins, partial, grid, pull,
-                     error_out);
-  if (nblk > 0 && wt != nullptr)
-    hipLaunchKernelGGL((k_density_seed_weighted<T, DIM>), dim3(nblk), dim3(BLOCK), 0, st, r,
-                       stride, n, mask, g, *wt, pull, grad, grad_stride);
-  else if (nblk > 0)
-    hipLaunchKernelGGL((k_density_seed<T, DIM>), dim3(nblk), dim3(BLOCK), 0, st, r, stride, n,
-                       mask, g, pull, grad, grad_stride);
-}
 
 // Every entry behind its own checks of the rows / codes: `dim` 2 or 3, codes below 3 * dim.
 // `wt` null: unweighted.
@@ -443,22 +301,14 @@ static int density_error_run(const void* rows, int64_t stride, int64_t n, int32_
                              double* grad, int64_t grad_stride, double* error_out, int64_t* hq,
                              int32_t splat_variant, void* workspace, size_t workspace_bytes,
                              void* stream, const DensityWeights* wt = nullptr) {
-  if (n < 0 || n > INT32_MAX || nx < 1 || ny < 1 || (int64_t)nx * ny > DENSITY_MAX_BINS ||
-      row_x == row_y || !goal || !error_out || !hq || !workspace || (row_y < 0 && ny != 1) ||
-      splat_variant < 0 || splat_variant > 2)
+  if (nx < 1 || ny < 1 || (int64_t)nx * ny > DENSITY_MAX_BINS || !goal || (row_y < 0 && ny != 1) ||
+      !error_args_ok(rows, stride, n, state_dtype, row_x, row_y, x0, x1, sx, y0, y1, sy,
+                     oob_weight, grad, grad_stride, error_out, hq, splat_variant, workspace))
     return TFRT_E_BADARG;
-  if (!(x1 > x0) || !(sx > 0.0) || !isfinite(sx) || !(oob_weight >= 0.0) || !isfinite(oob_weight) ||
-      !isfinite(x0) || !isfinite(x1))
-    return TFRT_E_BADARG;
-  if (row_y >= 0 && (!(y1 > y0) || !(sy > 0.0) || !isfinite(sy) || !isfinite(y0) || !isfinite(y1)))
-    return TFRT_E_BADARG;
-  if (n > 0 && (!rows || !grad || stride < n || grad_stride < n)) return TFRT_E_BADARG;
-  if (!state_dtype_ok(state_dtype)) return TFRT_E_BADARG;
   const int bins = nx * ny;
   if (splat_variant == 1 && bins > DENSITY_LDS_BINS) return TFRT_E_BADARG;
   if (workspace_bytes < tfrt_density_error_workspace_bytes(n, nx, ny)) return TFRT_E_WORKSPACE;
   const bool lds = splat_variant == 1 || (splat_variant == 0 && bins <= DENSITY_LDS_BINS);
-  const bool dir = row_x >= 2 * dim || row_y >= 2 * dim;
 
   DensityGrid g;
   g.x0 = x0, g.x1 = x1, g.sx = sx, g.oob = oob_weight;
@@ -469,22 +319,38 @@ static int density_error_run(const void* rows, int64_t stride, int64_t n, int32_
                                               align_up((size_t)bins * sizeof(double)));
   unsigned long long* hqu = reinterpret_cast<unsigned long long*>(hq);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int grid = density_grid(n);
+  const int grid = error_grid(n, DENSITY_RAYS_PER_BLOCK, DENSITY_MAX_GRID);
   const int nblk = cdiv(n, BLOCK);
 
-  hipLaunchKernelGGL(k_density_clear, dim3(cdiv(bins, BLOCK)), dim3(BLOCK), 0, st, hqu, bins);
-  return dispatch_state(state_dtype, TFRT_E_BADARG, [&](auto tag) {
+  hipLaunchKernelGGL(k_error_clear<>, dim3(cdiv(bins, BLOCK)), dim3(BLOCK), 0, st, hqu, bins);
+  // the splat, the bins and the seed: rows of T, direction fields of a DIM-D block (0: none),
+  // the constants `c` with or without weights
+  auto launch = [&](auto tag, auto d, auto c) {
     using T = typename decltype(tag)::type;
+    constexpr int DIM = decltype(d)::value;
+    constexpr bool WEIGHTED = decltype(c)::weighted;
     const T* r = static_cast<const T*>(rows);
-    if (!dir)
-      density_launch<T, 0>(r, stride, n, mask, g, wt, lds, bins, grid, nblk, hqu, goal, pull,
-                           partial, grad, grad_stride, error_out, st);
-    else if (dim == 3)
-      density_launch<T, 3>(r, stride, n, mask, g, wt, lds, bins, grid, nblk, hqu, goal, pull,
-                           partial, grad, grad_stride, error_out, st);
-    else
-      density_launch<T, 2>(r, stride, n, mask, g, wt, lds, bins, grid, nblk, hqu, goal, pull,
-                           partial, grad, grad_stride, error_out, st);
+    if (grid > 0 && lds)
+      hipLaunchKernelGGL((k_density_splat<T, true, DIM, WEIGHTED>), dim3(grid), dim3(BLOCK),
+                         (size_t)bins * sizeof(unsigned long long), st, r, stride, n, mask, c, hqu,
+                         partial);
+    else if (grid > 0)
+      hipLaunchKernelGGL((k_density_splat<T, false, DIM, WEIGHTED>), dim3(grid), dim3(BLOCK), 0, st,
+                         r, stride, n, mask, c, hqu, partial);
+    hipLaunchKernelGGL(k_density_bins, dim3(1), dim3(BINS_BLOCK), 0, st,
+                       reinterpret_cast<const long long*>(hqu), goal, bins, partial, grid, pull,
+                       error_out);
+    if (nblk > 0)
+      hipLaunchKernelGGL((k_density_seed<T, DIM, WEIGHTED>), dim3(nblk), dim3(BLOCK), 0, st, r,
+                         stride, n, mask, c, pull, grad, grad_stride);
+  };
+  return dispatch_state(state_dtype, TFRT_E_BADARG, [&](auto tag) {
+    dispatch_fields(dim, row_x, row_y, [&](auto d) {
+      if (wt != nullptr)
+        launch(tag, d, DensityArgs<true>{g, *wt});
+      else
+        launch(tag, d, DensityArgs<false>{g});
+    });
     return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
   });
 }

@@ -16,11 +16,8 @@
 //
 // Four launches:
 //
-//   k_spot_clear       zeroes the records.  A launch, not a memset node: replayed inside the step's
-//                      graph, a memset node in this place left the 896 bytes of the imaging
-//                      example's 28 records uncleared (every count came back as a stale word plus the
-//                      rays added); a kernel node in the same place clears them.  The cause is not
-//                      known; the node costs what a memset node costs, one tiny launch.
+//   k_error_clear      zeroes the records.  A launch, not a memset node: why, at the kernel
+//                      (error_sums.h).
 //   k_spot_accumulate  one lane per column (a fixed grid for n, grid-stride): {1, qx, qy} -> the
 //                      record of the ray's group; the out-of-domain penalty and the number of
 //                      counting columns as one partial per workgroup.  Two variants:
@@ -50,16 +47,24 @@
 // weighted residuals of a group sum to zero in the quantised quantities.  The product wq * qx is
 // kept in two limbs (wq * (qx >> h) and wq * (qx & (2^h - 1)), h = qbits / 2) so that the position
 // keeps its full qbits; a record is one 64-byte line of eight int64
-// {W, Xhi, Xlo, Yhi, Ylo, count, 0, 0}.  The accumulate and the seed are sibling kernels
-// (k_spot_accumulate_weighted, k_spot_seed_weighted) with the weights as one more argument; the
-// unweighted kernels are untouched.  The weight is read once per column through `perm`, behind
+// {W, Xhi, Xlo, Yhi, Ylo, count, 0, 0}.  The accumulate, the seed and the classification they share
+// have a `bool WEIGHTED` template parameter: everything that touches the weight stands under
+// `if constexpr (WEIGHTED)`, the weights are a base of the kernels' constants that is empty without
+// them (SpotArgs), so the unweighted instantiations neither receive nor read a weight, and
+// SpotRecord<WEIGHTED> says once how many slots a record has and where slot p of a group lies, in
+// the LDS table and in global memory.  The weight is read once per column through `perm`, behind
 // the index check that the label lookup needs anyway.  The table in LDS has six planes of G
 // int64: SPOT_WEIGHTED_LDS_GROUPS = 512 keeps it at the 24 KiB of the unweighted table at 1,024
 // groups -- six workgroups, 24 waves, share a CU's 160 KiB; twice the table would leave three, too
 // few to hide the latency of the ds_add_u64 behind other waves' loads.  More groups: six global
 // 64-bit atomics, all in the ray's one line.
+//
+// What this file shares with tfrt_density.hip -- the fixed-shape workgroup sums, the clear kernel,
+// the out-of-domain axis, the grid sizes, the argument checks, the dispatch on the direction
+// fields -- is in error_sums.h.
 #include "tfrt_common.h"
 #include "direction_fields.h"
+#include "error_sums.h"
 
 namespace tfrt {
 
@@ -69,7 +74,7 @@ constexpr int SPOT_MAX_WBITS = 20;
 constexpr int SPOT_MAX_GROUPS = 1 << 20;
 constexpr int SPOT_MAX_GRID = 512;         // workgroups of the accumulate launch
 constexpr int SPOT_RAYS_PER_BLOCK = 4 * BLOCK;
-constexpr int SPOT_SEED_MAX_GRID = 8192;   // workgroups of the seed launch (one column per lane up to 2M)
+constexpr int SPOT_SEED_MAX_GRID = 8192;   // workgroups of the seed launch
 constexpr int FINISH_BLOCK = 1024;
 constexpr int FINISH_WAVES = FINISH_BLOCK / 64;
 
@@ -86,6 +91,42 @@ struct SpotWeights {
   int32_t h;                 // qbits / 2: the low limb's bits
 };
 
+// The constants of an accumulate or seed launch: the grid, then (WEIGHTED) the weights.
+template <bool WEIGHTED>
+struct SpotArgs : SpotGrid, weights_base<WEIGHTED, SpotWeights> {
+  static constexpr bool weighted = WEIGHTED;
+};
+
+// The record of a group: SLOTS int64 in global memory, of which the first PLANES are in use --
+// {count, Sx, Sy, 0}, or WEIGHTED one 64-byte line {W, Xhi, Xlo, Yhi, Ylo, count, 0, 0} with the
+// moments W * x in two limbs.  The table in LDS keeps the slots in use as planes of G int64 each, in
+// the record's order (consecutive labels in consecutive banks).
+template <bool WEIGHTED>
+struct SpotRecord {
+  static constexpr int PLANES = WEIGHTED ? 6 : 3;
+  static constexpr int SLOTS = WEIGHTED ? 8 : 4;
+
+  // slot p of group `label`: in the LDS table of G groups (LDS), else in the records `acc`
+  template <bool LDS>
+  static __device__ __forceinline__ unsigned long long* slot(unsigned long long* table,
+                                                             unsigned long long* acc, int G,
+                                                             int label, int p) {
+    if (LDS) return table + (p * G + label);
+    return acc + SLOTS * (int64_t)label + p;
+  }
+
+  // the sum over the group's rays of (weight x) coordinate `axis` (0: x, 1: y), as a double: what
+  // the centroid divides by the mass in slot 0
+  static __device__ __forceinline__ double moment(const long long* rec, int axis,
+                                                  const SpotArgs<WEIGHTED>& g) {
+#pragma clang fp contract(off)
+    if constexpr (WEIGHTED)
+      return ldexp((double)rec[1 + 2 * axis], g.h) + (double)rec[2 + 2 * axis];
+    else
+      return (double)rec[1 + axis];
+  }
+};
+
 // What one column does.  kind 0: masked off; 3: counts, but contributes nothing (a non-finite
 // coordinate, or no spot); 1: inside the closed domain; 2: outside, ex / ey and their signs.
 struct SpotRay {
@@ -95,65 +136,59 @@ struct SpotRay {
   double dx, dy;     // kind 2: d ex / d x, d ey / d y (-1, 0, +1)
 };
 
-template <typename T, int DIM>
+// WEIGHTED: `wq` = rint(w * 2^wbits) and `wr` = wq * 2^-wbits receive the weight of the column's
+// source ray (they are left alone without), and a column with a spot (kinds 1 and 2) whose weight
+// does not count or quantises to 0 is in no spot (kind 3 -- every "no spot" case ends alike, so
+// the order of the checks does not show).  The weight is read behind the index check that the label
+// lookup needs anyway; the read of perm is the one that served the label.
+template <typename T, int DIM, bool WEIGHTED>
 __device__ __forceinline__ SpotRay spot_classify(const T* __restrict__ rows, int64_t stride,
                                                  const int32_t* __restrict__ mask,
                                                  const int32_t* __restrict__ group,
                                                  const int32_t* __restrict__ perm, int64_t i,
-                                                 const SpotGrid& g, LinkDir<DIM>& link) {
+                                                 const SpotArgs<WEIGHTED>& g, LinkDir<DIM>& link,
+                                                 double& wq, double& wr) {
 #pragma clang fp contract(off)
   SpotRay r;
   r.kind = 0;
   r.label = 0;
   r.x = r.y = r.dx = r.dy = 0.0;
-  if (mask != nullptr && mask[i] < 0) return r;
-  r.kind = 3;
-  const bool two = g.row_y >= 0;
-  double x, y;
-  read_fields<T, DIM>(rows, stride, i, g.row_x, g.row_y, x, y, link);
-  if (!isfinite(x) || !isfinite(y)) return r;
-  // (nothing is read out of bounds, whatever perm and group hold)
-  const int64_t s = perm != nullptr ? (int64_t)perm[i] : i;
-  if (s < 0 || s >= g.n_source) return r;
-  const int label = group[s];
-  if (label < 0 || label >= g.n_groups) return r;
-  r.label = label;
-  const bool out = x < g.x0 || x > g.x1 || (two && (y < g.y0 || y > g.y1));
-  if (out) {
-    r.kind = 2;
-    r.x = fmax(g.x0 - x, 0.0) + fmax(x - g.x1, 0.0);
-    r.dx = x < g.x0 ? -1.0 : (x > g.x1 ? 1.0 : 0.0);
-    if (two) {
-      r.y = fmax(g.y0 - y, 0.0) + fmax(y - g.y1, 0.0);
-      r.dy = y < g.y0 ? -1.0 : (y > g.y1 ? 1.0 : 0.0);
+  if (mask == nullptr || mask[i] >= 0) {
+    r.kind = 3;
+    const bool two = g.row_y >= 0;
+    double x, y;
+    read_fields<T, DIM>(rows, stride, i, g.row_x, g.row_y, x, y, link);
+    if (isfinite(x) && isfinite(y)) {
+      // (nothing is read out of bounds, whatever perm and group hold)
+      const int64_t s = perm != nullptr ? (int64_t)perm[i] : i;
+      if (s >= 0 && s < g.n_source) {
+        const int label = group[s];
+        if (label >= 0 && label < g.n_groups) {
+          r.label = label;
+          const bool out = x < g.x0 || x > g.x1 || (two && (y < g.y0 || y > g.y1));
+          if (out) {
+            r.kind = 2;
+            r.x = outside_by(x, g.x0, g.x1), r.dx = outside_sign(x, g.x0, g.x1);
+            if (two) r.y = outside_by(y, g.y0, g.y1), r.dy = outside_sign(y, g.y0, g.y1);
+          } else {
+            r.kind = 1;
+            r.x = x;
+            r.y = y;
+          }
+        }
+      }
     }
-    return r;
   }
-  r.kind = 1;
-  r.x = x;
-  r.y = y;
-  return r;
-}
-
-// The same for tfrt_spot_error_weighted: a column with a spot (kinds 1 and 2) whose weight does not
-// count or quantises to 0 is in no spot (kind 3 -- every "no spot" case ends alike, so the order of
-// the checks does not show).  s has passed spot_classify's index check; the read of perm is the one
-// that served the label.  wq = rint(w * 2^wbits) > 0, wr = wq * 2^-wbits.
-template <typename T, int DIM>
-__device__ __forceinline__ SpotRay spot_classify_weighted(
-    const T* __restrict__ rows, int64_t stride, const int32_t* __restrict__ mask,
-    const int32_t* __restrict__ group, const int32_t* __restrict__ perm, int64_t i,
-    const SpotGrid& g, const SpotWeights& wt, LinkDir<DIM>& link, double& wq, double& wr) {
-#pragma clang fp contract(off)
-  SpotRay r = spot_classify<T, DIM>(rows, stride, mask, group, perm, i, g, link);
-  wq = wr = 0.0;
-  if (r.kind == 1 || r.kind == 2) {
-    const int64_t s = perm != nullptr ? (int64_t)perm[i] : i;
-    // (a NaN fails both comparisons; the product with a power of two is exact)
-    const double w = wt.weight[s];
-    wq = w >= 0.0 && w <= 1.0 ? rint(w * wt.one) : 0.0;
-    wr = wq * wt.inv;
-    if (wq == 0.0) r.kind = 3;
+  if constexpr (WEIGHTED) {
+    wq = wr = 0.0;
+    if (r.kind == 1 || r.kind == 2) {
+      const int64_t s = perm != nullptr ? (int64_t)perm[i] : i;
+      // (a NaN fails both comparisons; the product with a power of two is exact)
+      const double w = g.weight[s];
+      wq = w >= 0.0 && w <= 1.0 ? rint(w * g.one) : 0.0;
+      wr = wq * g.inv;
+      if (wq == 0.0) r.kind = 3;
+    }
   }
   return r;
 }
@@ -165,54 +200,25 @@ __device__ __forceinline__ unsigned long long spot_fixed(double v, double lo, do
   return (unsigned long long)(long long)fmin(fmax(rint((v - lo) * qs), 0.0), qmax);
 }
 
-// fixed-shape sums over a workgroup of NW waves: xor butterflies inside the wave, waves in index
-// order; every thread of the workgroup must call them.  `wsum` is reused: a barrier at the end.
-template <int NW>
-__device__ __forceinline__ double spot_block_sum(double v, double* wsum) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-  if (lane_id() == 0) wsum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < NW; ++w) s += wsum[w];
-  __syncthreads();
-  return s;
-}
-
-template <int NW>
-__device__ __forceinline__ long long spot_block_count(long long v, long long* wcnt) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-  if (lane_id() == 0) wcnt[threadIdx.x >> 6] = v;
-  __syncthreads();
-  long long s = 0;
-  for (int w = 0; w < NW; ++w) s += wcnt[w];
-  __syncthreads();
-  return s;
-}
-
-// The records of every group, cleared in front of the adds.
-__global__ __launch_bounds__(BLOCK) void k_spot_clear(unsigned long long* __restrict__ acc,
-                                                      int entries) {
-  const int e = blockIdx.x * BLOCK + threadIdx.x;
-  if (e < entries) acc[e] = 0ull;
-}
-
-template <typename T, bool LDS, int DIM>
+// {1, qx, qy} -> the record of the ray's group; WEIGHTED: {wq, wq * qx in two limbs, wq * qy in two
+// limbs, 1}, the penalty times wr last.
+template <typename T, bool LDS, int DIM, bool WEIGHTED>
 __global__ __launch_bounds__(BLOCK) void k_spot_accumulate(
     const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
-    const int32_t* __restrict__ group, const int32_t* __restrict__ perm, SpotGrid g,
+    const int32_t* __restrict__ group, const int32_t* __restrict__ perm, SpotArgs<WEIGHTED> g,
     unsigned long long* __restrict__ acc, double* __restrict__ pen_partial,
     long long* __restrict__ cnt_partial) {
 #pragma clang fp contract(off)
-  extern __shared__ unsigned long long table[];   // LDS variant: planes count | Sx | Sy of G each
+  using Record = SpotRecord<WEIGHTED>;
+  extern __shared__ unsigned long long table[];   // LDS variant: Record::PLANES planes of G each
   __shared__ double wsum[WAVES];
   __shared__ long long wcnt[WAVES];
   const int G = g.n_groups;
   const bool two = g.row_y >= 0;
+  unsigned long long low = 0ull;   // WEIGHTED: the low limb's mask
+  if constexpr (WEIGHTED) low = (1ull << g.h) - 1ull;
   if (LDS) {
-    for (int e = threadIdx.x; e < 3 * G; e += BLOCK) table[e] = 0ull;
+    for (int e = threadIdx.x; e < Record::PLANES * G; e += BLOCK) table[e] = 0ull;
     __syncthreads();
   }
   double pen = 0.0;
@@ -220,144 +226,84 @@ __global__ __launch_bounds__(BLOCK) void k_spot_accumulate(
   for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * BLOCK) {
     LinkDir<DIM> link;
-    const SpotRay r = spot_classify<T, DIM>(rows, stride, mask, group, perm, i, g, link);
-    counting += r.kind != 0 ? 1 : 0;
-    if (r.kind == 2) {
-      pen += g.oob * (r.x * r.x + r.y * r.y);
-    } else if (r.kind == 1) {
-      const unsigned long long qx = spot_fixed(r.x, g.x0, g.qsx, g.qmax);
-      const unsigned long long qy = two ? spot_fixed(r.y, g.y0, g.qsy, g.qmax) : 0ull;
-      if (LDS) {
-        atomicAdd(&table[r.label], 1ull);
-        atomicAdd(&table[G + r.label], qx);
-        if (two) atomicAdd(&table[2 * G + r.label], qy);
-      } else {
-        unsigned long long* rec = acc + 4 * (int64_t)r.label;
-        atomicAdd(&rec[0], 1ull);
-        atomicAdd(&rec[1], qx);
-        if (two) atomicAdd(&rec[2], qy);
-      }
-    }
-  }
-  if (LDS) {
-    __syncthreads();
-    for (int e = threadIdx.x; e < 3 * G; e += BLOCK) {
-      const unsigned long long v = table[e];
-      const int plane = e / G, label = e - plane * G;
-      if (v != 0ull) atomicAdd(&acc[4 * (int64_t)label + plane], v);
-    }
-  }
-  const double s = spot_block_sum<WAVES>(pen, wsum);
-  const long long c = spot_block_count<WAVES>(counting, wcnt);
-  if (threadIdx.x == 0) {
-    pen_partial[blockIdx.x] = s;
-    cnt_partial[blockIdx.x] = c;
-  }
-}
-
-// tfrt_spot_error_weighted's accumulate: the planes W | Xhi | Xlo | Yhi | Ylo | count of G each in
-// LDS -- the order of a record of eight int64 --, or six global atomics in the ray's one line.
-template <typename T, bool LDS, int DIM>
-__global__ __launch_bounds__(BLOCK) void k_spot_accumulate_weighted(
-    const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
-    const int32_t* __restrict__ group, const int32_t* __restrict__ perm, SpotGrid g,
-    SpotWeights wt, unsigned long long* __restrict__ acc, double* __restrict__ pen_partial,
-    long long* __restrict__ cnt_partial) {
-#pragma clang fp contract(off)
-  extern __shared__ unsigned long long table[];
-  __shared__ double wsum[WAVES];
-  __shared__ long long wcnt[WAVES];
-  const int G = g.n_groups;
-  const bool two = g.row_y >= 0;
-  const unsigned long long low = (1ull << wt.h) - 1ull;
-  if (LDS) {
-    for (int e = threadIdx.x; e < 6 * G; e += BLOCK) table[e] = 0ull;
-    __syncthreads();
-  }
-  double pen = 0.0;
-  long long counting = 0;
-  for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * BLOCK) {
-    LinkDir<DIM> link;
-    double wq, wr;
+    double wq = 0.0, wr = 0.0;
     const SpotRay r =
-        spot_classify_weighted<T, DIM>(rows, stride, mask, group, perm, i, g, wt, link, wq, wr);
+        spot_classify<T, DIM, WEIGHTED>(rows, stride, mask, group, perm, i, g, link, wq, wr);
     counting += r.kind != 0 ? 1 : 0;
     if (r.kind == 2) {
-      pen += (g.oob * (r.x * r.x + r.y * r.y)) * wr;
+      pen += weighed<WEIGHTED>(g.oob * (r.x * r.x + r.y * r.y), wr);
     } else if (r.kind == 1) {
-      const unsigned long long q = (unsigned long long)(long long)wq;
+      // (the weight as an integer: what a WEIGHTED record sums in the place of 1)
+      const unsigned long long q = WEIGHTED ? (unsigned long long)(long long)wq : 1ull;
       const unsigned long long qx = spot_fixed(r.x, g.x0, g.qsx, g.qmax);
       const unsigned long long qy = two ? spot_fixed(r.y, g.y0, g.qsy, g.qmax) : 0ull;
-      if (LDS) {
-        atomicAdd(&table[r.label], q);
-        atomicAdd(&table[G + r.label], q * (qx >> wt.h));
-        atomicAdd(&table[2 * G + r.label], q * (qx & low));
+      if constexpr (WEIGHTED) {
+        atomicAdd(Record::template slot<LDS>(table, acc, G, r.label, 0), q);
+        atomicAdd(Record::template slot<LDS>(table, acc, G, r.label, 1), q * (qx >> g.h));
+        atomicAdd(Record::template slot<LDS>(table, acc, G, r.label, 2), q * (qx & low));
         if (two) {
-          atomicAdd(&table[3 * G + r.label], q * (qy >> wt.h));
-          atomicAdd(&table[4 * G + r.label], q * (qy & low));
+          atomicAdd(Record::template slot<LDS>(table, acc, G, r.label, 3), q * (qy >> g.h));
+          atomicAdd(Record::template slot<LDS>(table, acc, G, r.label, 4), q * (qy & low));
         }
-        atomicAdd(&table[5 * G + r.label], 1ull);
+        atomicAdd(Record::template slot<LDS>(table, acc, G, r.label, 5), 1ull);
       } else {
-        unsigned long long* rec = acc + 8 * (int64_t)r.label;
-        atomicAdd(&rec[0], q);
-        atomicAdd(&rec[1], q * (qx >> wt.h));
-        atomicAdd(&rec[2], q * (qx & low));
-        if (two) {
-          atomicAdd(&rec[3], q * (qy >> wt.h));
-          atomicAdd(&rec[4], q * (qy & low));
-        }
-        atomicAdd(&rec[5], 1ull);
+        atomicAdd(Record::template slot<LDS>(table, acc, G, r.label, 0), q);
+        atomicAdd(Record::template slot<LDS>(table, acc, G, r.label, 1), qx);
+        if (two) atomicAdd(Record::template slot<LDS>(table, acc, G, r.label, 2), qy);
       }
     }
   }
   if (LDS) {
     __syncthreads();
-    for (int e = threadIdx.x; e < 6 * G; e += BLOCK) {
+    for (int e = threadIdx.x; e < Record::PLANES * G; e += BLOCK) {
       const unsigned long long v = table[e];
       const int plane = e / G, label = e - plane * G;
-      if (v != 0ull) atomicAdd(&acc[8 * (int64_t)label + plane], v);
+      if (v != 0ull) atomicAdd(Record::template slot<false>(table, acc, G, label, plane), v);
     }
   }
-  const double s = spot_block_sum<WAVES>(pen, wsum);
-  const long long c = spot_block_count<WAVES>(counting, wcnt);
+  const double s = error_block_sum<WAVES>(pen, wsum);
+  const long long c = error_block_sum<WAVES>(counting, wcnt);
   if (threadIdx.x == 0) {
     pen_partial[blockIdx.x] = s;
     cnt_partial[blockIdx.x] = c;
   }
 }
 
-template <typename T, int DIM>
+// WEIGHTED: the centroid from the two limbs, everything times wr last.
+template <typename T, int DIM, bool WEIGHTED>
 __global__ __launch_bounds__(BLOCK) void k_spot_seed(
     const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
-    const int32_t* __restrict__ group, const int32_t* __restrict__ perm, SpotGrid g,
+    const int32_t* __restrict__ group, const int32_t* __restrict__ perm, SpotArgs<WEIGHTED> g,
     const long long* __restrict__ acc, double* __restrict__ grad, int64_t grad_stride,
     double* __restrict__ term_partial) {
 #pragma clang fp contract(off)
+  using Record = SpotRecord<WEIGHTED>;
   __shared__ double wsum[WAVES];
   const bool two = g.row_y >= 0;
   double terms = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * BLOCK) {
     LinkDir<DIM> link;
-    const SpotRay r = spot_classify<T, DIM>(rows, stride, mask, group, perm, i, g, link);
+    double wq = 0.0, wr = 0.0;
+    const SpotRay r =
+        spot_classify<T, DIM, WEIGHTED>(rows, stride, mask, group, perm, i, g, link, wq, wr);
     double gx = 0.0, gy = 0.0;
     if (r.kind == 2) {
-      gx = g.oob * (2.0 * r.x) * r.dx;
-      gy = g.oob * (2.0 * r.y) * r.dy;
+      gx = weighed<WEIGHTED>(g.oob * (2.0 * r.x) * r.dx, wr);
+      gy = weighed<WEIGHTED>(g.oob * (2.0 * r.y) * r.dy, wr);
     } else if (r.kind == 1) {
-      // (this ray is in its own group's record: count >= 1)
-      const long long* rec = acc + 4 * (int64_t)r.label;
-      const double cnt = (double)rec[0];
-      const double cx = g.x0 + ((double)rec[1] / cnt) / g.qsx;
+      // (this ray is in its own group's record: its mass is >= 1)
+      const long long* rec = acc + Record::SLOTS * (int64_t)r.label;
+      const double mass = (double)rec[0];
+      const double cx = g.x0 + (Record::moment(rec, 0, g) / mass) / g.qsx;
       const double dx = r.x - cx;
-      gx = 2.0 * dx;
-      double t = dx * dx;
+      gx = weighed<WEIGHTED>(2.0 * dx, wr);
+      double t = weighed<WEIGHTED>(dx * dx, wr);
       if (two) {
-        const double cy = g.y0 + ((double)rec[2] / cnt) / g.qsy;
+        const double cy = g.y0 + (Record::moment(rec, 1, g) / mass) / g.qsy;
         const double dy = r.y - cy;
-        gy = 2.0 * dy;
-        t = t + dy * dy;
+        gy = weighed<WEIGHTED>(2.0 * dy, wr);
+        t = t + weighed<WEIGHTED>(dy * dy, wr);
       }
       terms += t;
     }
@@ -370,58 +316,7 @@ __global__ __launch_bounds__(BLOCK) void k_spot_seed(
       if (two) grad[(int64_t)g.row_y * grad_stride + i] = gy;
     }
   }
-  const double s = spot_block_sum<WAVES>(terms, wsum);
-  if (threadIdx.x == 0) term_partial[blockIdx.x] = s;
-}
-
-// tfrt_spot_error_weighted's seed: the centroid from the two limbs, everything times wr last.
-template <typename T, int DIM>
-__global__ __launch_bounds__(BLOCK) void k_spot_seed_weighted(
-    const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
-    const int32_t* __restrict__ group, const int32_t* __restrict__ perm, SpotGrid g,
-    SpotWeights wt, const long long* __restrict__ acc, double* __restrict__ grad,
-    int64_t grad_stride, double* __restrict__ term_partial) {
-#pragma clang fp contract(off)
-  __shared__ double wsum[WAVES];
-  const bool two = g.row_y >= 0;
-  double terms = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * BLOCK) {
-    LinkDir<DIM> link;
-    double wq, wr;
-    const SpotRay r =
-        spot_classify_weighted<T, DIM>(rows, stride, mask, group, perm, i, g, wt, link, wq, wr);
-    double gx = 0.0, gy = 0.0;
-    if (r.kind == 2) {
-      gx = (g.oob * (2.0 * r.x) * r.dx) * wr;
-      gy = (g.oob * (2.0 * r.y) * r.dy) * wr;
-    } else if (r.kind == 1) {
-      // (this ray is in its own group's record: W >= wq >= 1)
-      const long long* rec = acc + 8 * (int64_t)r.label;
-      const double W = (double)rec[0];
-      const double X = ldexp((double)rec[1], wt.h) + (double)rec[2];
-      const double cx = g.x0 + (X / W) / g.qsx;
-      const double dx = r.x - cx;
-      gx = (2.0 * dx) * wr;
-      double t = wr * (dx * dx);
-      if (two) {
-        const double Y = ldexp((double)rec[3], wt.h) + (double)rec[4];
-        const double cy = g.y0 + (Y / W) / g.qsy;
-        const double dy = r.y - cy;
-        gy = (2.0 * dy) * wr;
-        t = t + wr * (dy * dy);
-      }
-      terms += t;
-    }
-    if constexpr (DIM != 0) {
-      chain_fields<DIM>(link, r.kind == 1 || r.kind == 2, g.row_x, g.row_y, gx, gy, grad,
-                   grad_stride, i);
-    } else {
-      grad[(int64_t)g.row_x * grad_stride + i] = gx;
-      if (two) grad[(int64_t)g.row_y * grad_stride + i] = gy;
-    }
-  }
-  const double s = spot_block_sum<WAVES>(terms, wsum);
+  const double s = error_block_sum<WAVES>(terms, wsum);
   if (threadIdx.x == 0) term_partial[blockIdx.x] = s;
 }
 
@@ -442,9 +337,9 @@ __global__ __launch_bounds__(FINISH_BLOCK) void k_spot_finish(
     counting += cnt_partial[b];
   }
   for (int b = t; b < n_seed; b += FINISH_BLOCK) inside += term_partial[b];
-  inside = spot_block_sum<FINISH_WAVES>(inside, wsum);
-  pen = spot_block_sum<FINISH_WAVES>(pen, wsum);
-  counting = spot_block_count<FINISH_WAVES>(counting, wcnt);
+  inside = error_block_sum<FINISH_WAVES>(inside, wsum);
+  pen = error_block_sum<FINISH_WAVES>(pen, wsum);
+  counting = error_block_sum<FINISH_WAVES>(counting, wcnt);
   if (t == 0) {
     const double e = inside + pen;
     const double terms = (double)(counting * fields);
@@ -454,55 +349,11 @@ __global__ __launch_bounds__(FINISH_BLOCK) void k_spot_finish(
   }
 }
 
-static int spot_grid(int64_t n) {
-  if (n <= 0) return 0;
-  const int64_t want = (n + SPOT_RAYS_PER_BLOCK - 1) / SPOT_RAYS_PER_BLOCK;
-  return (int)(want < SPOT_MAX_GRID ? want : SPOT_MAX_GRID);
-}
-
-static int spot_seed_grid(int64_t n) {
-  if (n <= 0) return 0;
-  const int64_t want = (n + BLOCK - 1) / BLOCK;
-  return (int)(want < SPOT_SEED_MAX_GRID ? want : SPOT_SEED_MAX_GRID);
-}
-
 }  // namespace tfrt
 
 using namespace tfrt;
 
 extern "C" size_t tfrt_spot_error_workspace_bytes(int64_t n, int32_t n_groups);
-
-// The accumulate and seed launches of every entry (`wt` null: unweighted).
-template <typename T, int DIM>
-static void spot_launch(const T* r, int64_t stride, int64_t n, const int32_t* mask,
-                        const int32_t* group, const int32_t* perm, const SpotGrid& g,
-                        const SpotWeights* wt, bool lds, int grid, int sgrid,
-                        unsigned long long* accu, double* pen_partial, long long* cnt_partial,
-                        double* term_partial, double* grad, int64_t grad_stride, hipStream_t st) {
-  const long long* acc = reinterpret_cast<const long long*>(accu);
-  if (wt != nullptr) {
-    if (lds)
-      hipLaunchKernelGGL((k_spot_accumulate_weighted<T, true, DIM>), dim3(grid), dim3(BLOCK),
-                         (size_t)g.n_groups * 6 * sizeof(unsigned long long), st, r, stride, n,
-                         mask, group, perm, g, *wt, accu, pen_partial, cnt_partial);
-    else
-      hipLaunchKernelGGL((k_spot_accumulate_weighted<T, false, DIM>), dim3(grid), dim3(BLOCK), 0,
-                         st, r, stride, n, mask, group, perm, g, *wt, accu, pen_partial,
-                         cnt_partial);
-    hipLaunchKernelGGL((k_spot_seed_weighted<T, DIM>), dim3(sgrid), dim3(BLOCK), 0, st, r, stride,
-                       n, mask, group, perm, g, *wt, acc, grad, grad_stride, term_partial);
-    return;
-  }
-  if (lds)
-    hipLaunchKernelGGL((k_spot_accumulate<T, true, DIM>), dim3(grid), dim3(BLOCK),
-                       (size_t)g.n_groups * 3 * sizeof(unsigned long long), st, r, stride, n, mask,
-                       group, perm, g, accu, pen_partial, cnt_partial);
-  else
-    hipLaunchKernelGGL((k_spot_accumulate<T, false, DIM>), dim3(grid), dim3(BLOCK), 0, st, r,
-                       stride, n, mask, group, perm, g, accu, pen_partial, cnt_partial);
-  hipLaunchKernelGGL((k_spot_seed<T, DIM>), dim3(sgrid), dim3(BLOCK), 0, st, r, stride, n, mask,
-                     group, perm, g, acc, grad, grad_stride, term_partial);
-}
 
 // Every entry behind its own checks of the rows / codes: `dim` 2 or 3, codes below 3 * dim.
 // `weight` null: records of four int64 and n * 2^qbits < 2^62; else records of eight, `wbits`
@@ -516,9 +367,10 @@ static int spot_error_run(const void* rows, int64_t stride, int64_t n, int32_t s
                           void* workspace, size_t workspace_bytes, void* stream,
                           const double* weight = nullptr, int32_t wbits = 0) {
   const bool weighted = weight != nullptr;
-  if (n < 0 || n > INT32_MAX || n_source < 0 || n_source > INT32_MAX || n_groups < 1 ||
-      n_groups > SPOT_MAX_GROUPS || qbits < 1 || qbits > 52 || row_x == row_y || !group ||
-      !error_out || !acc || !workspace || variant < 0 || variant > 2)
+  if (n_source < 0 || n_source > INT32_MAX || n_groups < 1 || n_groups > SPOT_MAX_GROUPS ||
+      qbits < 1 || qbits > 52 || !group ||
+      !error_args_ok(rows, stride, n, state_dtype, row_x, row_y, x0, x1, qsx, y0, y1, qsy,
+                     oob_weight, grad, grad_stride, error_out, acc, variant, workspace))
     return TFRT_E_BADARG;
   if (weighted) {
     // every sum stays below n * 2^wbits * 2^ceil(qbits / 2) < 2^62
@@ -527,18 +379,10 @@ static int spot_error_run(const void* rows, int64_t stride, int64_t n, int32_t s
   } else if (n >= ((int64_t)1 << (62 - qbits))) {
     return TFRT_E_BADARG;   // n * 2^qbits must stay below 2^62
   }
-  if (!(x1 > x0) || !(qsx > 0.0) || !isfinite(qsx) || !(oob_weight >= 0.0) ||
-      !isfinite(oob_weight) || !isfinite(x0) || !isfinite(x1))
-    return TFRT_E_BADARG;
-  if (row_y >= 0 && (!(y1 > y0) || !(qsy > 0.0) || !isfinite(qsy) || !isfinite(y0) || !isfinite(y1)))
-    return TFRT_E_BADARG;
-  if (n > 0 && (!rows || !grad || stride < n || grad_stride < n)) return TFRT_E_BADARG;
-  if (!state_dtype_ok(state_dtype)) return TFRT_E_BADARG;
   const int lds_groups = weighted ? SPOT_WEIGHTED_LDS_GROUPS : SPOT_LDS_GROUPS;
   if (variant == 1 && n_groups > lds_groups) return TFRT_E_BADARG;
   if (workspace_bytes < tfrt_spot_error_workspace_bytes(n, n_groups)) return TFRT_E_WORKSPACE;
   const bool lds = variant == 1 || (variant == 0 && n_groups <= lds_groups);
-  const bool dir = row_x >= 2 * dim || row_y >= 2 * dim;
 
   SpotGrid g;
   g.x0 = x0, g.x1 = x1, g.qsx = qsx, g.oob = oob_weight;
@@ -547,8 +391,7 @@ static int spot_error_run(const void* rows, int64_t stride, int64_t n, int32_t s
   g.n_source = n_source, g.n_groups = n_groups, g.row_x = row_x, g.row_y = row_y;
   SpotWeights w;
   w.weight = weight, w.one = ldexp(1.0, wbits), w.inv = ldexp(1.0, -wbits), w.h = qbits / 2;
-  const SpotWeights* wt = weighted ? &w : nullptr;
-  const int record = weighted ? 8 : 4;
+  const int slots = weighted ? SpotRecord<true>::SLOTS : SpotRecord<false>::SLOTS;
   char* ws = static_cast<char*>(workspace);
   double* pen_partial = reinterpret_cast<double*>(ws);
   long long* cnt_partial =
@@ -557,25 +400,37 @@ static int spot_error_run(const void* rows, int64_t stride, int64_t n, int32_t s
       reinterpret_cast<double*>(ws + 2 * align_up(SPOT_MAX_GRID * sizeof(double)));
   unsigned long long* accu = reinterpret_cast<unsigned long long*>(acc);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int grid = spot_grid(n);
-  const int sgrid = spot_seed_grid(n);
+  const int grid = error_grid(n, SPOT_RAYS_PER_BLOCK, SPOT_MAX_GRID);
+  const int sgrid = error_grid(n, BLOCK, SPOT_SEED_MAX_GRID);   // one column per lane up to 2M
 
-  hipLaunchKernelGGL(k_spot_clear, dim3(cdiv(record * (int64_t)n_groups, BLOCK)), dim3(BLOCK), 0,
-                     st, accu, record * n_groups);
-  return dispatch_state(state_dtype, TFRT_E_BADARG, [&](auto tag) {
+  hipLaunchKernelGGL(k_error_clear<>, dim3(cdiv(slots * (int64_t)n_groups, BLOCK)), dim3(BLOCK), 0,
+                     st, accu, slots * n_groups);
+  // the accumulate and the seed: rows of T, direction fields of a DIM-D block (0: none), the
+  // constants `c` with or without weights
+  auto launch = [&](auto tag, auto d, auto c) {
     using T = typename decltype(tag)::type;
+    constexpr int DIM = decltype(d)::value;
+    constexpr bool WEIGHTED = decltype(c)::weighted;
     const T* r = static_cast<const T*>(rows);
-    if (grid > 0) {
-      if (!dir)
-        spot_launch<T, 0>(r, stride, n, mask, group, perm, g, wt, lds, grid, sgrid, accu,
-                          pen_partial, cnt_partial, term_partial, grad, grad_stride, st);
-      else if (dim == 3)
-        spot_launch<T, 3>(r, stride, n, mask, group, perm, g, wt, lds, grid, sgrid, accu,
-                          pen_partial, cnt_partial, term_partial, grad, grad_stride, st);
-      else
-        spot_launch<T, 2>(r, stride, n, mask, group, perm, g, wt, lds, grid, sgrid, accu,
-                          pen_partial, cnt_partial, term_partial, grad, grad_stride, st);
-    }
+    if (lds)
+      hipLaunchKernelGGL((k_spot_accumulate<T, true, DIM, WEIGHTED>), dim3(grid), dim3(BLOCK),
+                         (size_t)n_groups * SpotRecord<WEIGHTED>::PLANES * sizeof(unsigned long long),
+                         st, r, stride, n, mask, group, perm, c, accu, pen_partial, cnt_partial);
+    else
+      hipLaunchKernelGGL((k_spot_accumulate<T, false, DIM, WEIGHTED>), dim3(grid), dim3(BLOCK), 0,
+                         st, r, stride, n, mask, group, perm, c, accu, pen_partial, cnt_partial);
+    hipLaunchKernelGGL((k_spot_seed<T, DIM, WEIGHTED>), dim3(sgrid), dim3(BLOCK), 0, st, r, stride,
+                       n, mask, group, perm, c, reinterpret_cast<const long long*>(accu), grad,
+                       grad_stride, term_partial);
+  };
+  return dispatch_state(state_dtype, TFRT_E_BADARG, [&](auto tag) {
+    if (grid > 0)
+      dispatch_fields(dim, row_x, row_y, [&](auto d) {
+        if (weighted)
+          launch(tag, d, SpotArgs<true>{g, w});
+        else
+          launch(tag, d, SpotArgs<false>{g});
+      });
     hipLaunchKernelGGL(k_spot_finish, dim3(1), dim3(FINISH_BLOCK), 0, st, pen_partial, cnt_partial,
                        grid, term_partial, sgrid, row_y >= 0 ? 2 : 1, error_out);
     return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;

@@ -473,38 +473,22 @@ class DensityError:
             ids = engine.last_trace["finished_id"].to(torch.int32).contiguous()
         if self.has_direction:
             dim, block = _geometry_block(engine, fin)
-            return _DensityFieldTerms.apply(block, self, dim, tuple(codes), weights, ids)
+            return _DensityTerms.apply(block, self, weights, ids, dim, tuple(codes))
         return _DensityTerms.apply(torch.stack([fin[f] for f in self.fields], dim=0), self,
                                    weights, ids)
 
 
 class _DensityTerms(torch.autograd.Function):
-    """DensityError over the (k, n) field columns of the finished rays, no mask; ``weights``
-    (or None) with ``ids``, the source ray of every column."""
+    """DensityError over the finished rays, no mask.  ``dimension=None, codes=None``: ``block`` is
+    the (k, n) field columns; else it is the (2 * dimension, n) geometry block and ``codes`` the
+    field codes (a direction field).  ``weights`` (or None) with ``ids``, the source ray of every
+    column."""
 
     @staticmethod
-    def forward(ctx, columns, erf, weights=None, ids=None):
-        block = columns.detach().contiguous()
-        err, grad, _ = erf.evaluate(block, 0, 1 if block.shape[0] == 2 else -1, weights=weights,
-                                    perm=ids)
-        ctx.save_for_backward(grad)
-        ctx.dtype = columns.dtype
-        return err[:1].clone()
-
-    @staticmethod
-    def backward(ctx, upstream):
-        grad, = ctx.saved_tensors
-        return (upstream * grad).to(ctx.dtype), None, None, None
-
-
-class _DensityFieldTerms(torch.autograd.Function):
-    """DensityError with a direction field over the (2 * dimension, n) geometry block of the
-    finished rays, no mask; ``codes``: the field codes; ``weights`` (or None) with ``ids``, the
-    source ray of every column."""
-
-    @staticmethod
-    def forward(ctx, block, erf, dimension, codes, weights=None, ids=None):
+    def forward(ctx, block, erf, weights=None, ids=None, dimension=None, codes=None):
         rows = block.detach().contiguous()
+        if codes is None:
+            codes = (0, 1)[:rows.shape[0]]
         err, grad, _ = erf.evaluate(rows, codes[0], codes[1] if len(codes) == 2 else -1,
                                     dimension=dimension, weights=weights, perm=ids)
         ctx.save_for_backward(grad)
@@ -735,18 +719,19 @@ class SpotError:
         ids = engine.last_trace["finished_id"]
         labels = self.labels_of(engine._trace_src)
         weights = self.weights_of(engine._trace_src)
+        ids = ids.to(torch.int32).contiguous()
         if self.has_direction:
             dim, block = _geometry_block(engine, fin)
-            return _SpotFieldTerms.apply(block, self, labels, ids.to(torch.int32).contiguous(),
-                                         dim, tuple(codes), weights)
+            return _SpotTerms.apply(block, self, labels, ids, weights, dim, tuple(codes))
         columns = torch.stack([fin[f] for f in self.fields], dim=0)
-        return _SpotTerms.apply(columns, self, labels, ids.to(torch.int32).contiguous(), weights)
+        return _SpotTerms.apply(columns, self, labels, ids, weights)
 
 
-def _spot_terms(erf, v, labels, ids, acc, weights):
+def _spot_terms(erf, v, labels, ids, acc, weights, inside=None):
     """The (n, k) terms of a SpotError evaluation from its records: an inside ray's squared
-    distances to its group's centroid, a penalised ray's ``oob_weight * ex**2`` per field, both
-    times ``wr`` with ``weights``; zeros for a ray in no spot.  ``v``: the (k, n) float64 fields."""
+    distances to its group's centroid (``inside``, (k, n), where the caller has them already), a
+    penalised ray's ``oob_weight * ex**2`` per field, both times ``wr`` with ``weights``; zeros for
+    a ray in no spot.  ``v``: the (k, n) float64 fields."""
     k = v.shape[0]
     lo = torch.tensor([d[0] for d in erf.domain], dtype=torch.float64, device=v.device)[:, None]
     hi = torch.tensor([d[1] for d in erf.domain], dtype=torch.float64, device=v.device)[:, None]
@@ -760,85 +745,61 @@ def _spot_terms(erf, v, labels, ids, acc, weights):
     s = s.clamp(0, labels.numel() - 1)
     lab = labels[s]
     spot = s_ok & (lab >= 0) & (lab < erf.n_groups) & torch.isfinite(v).all(dim=0)
-    centre = ops.spot_centroids(acc, erf.last_grid, k, erf.last_qbits).t()[
-        :, lab.long().clamp(0, erf.n_groups - 1)]
-    dv = v - centre
-    if weights is None:
-        terms = torch.where(out, erf.oob_weight * (ex * ex), dv * dv)
-    else:
+    if inside is None:
+        centre = ops.spot_centroids(acc, erf.last_grid, k, erf.last_qbits).t()[
+            :, lab.long().clamp(0, erf.n_groups - 1)]
+        dv = v - centre
+        inside = dv * dv
+    penalty = erf.oob_weight * (ex * ex)
+    if weights is not None:
         wbits = ops.spot_wbits(labels.numel())
         w = weights[s]
         wq = torch.where((w >= 0.0) & (w <= 1.0), torch.round(w * float(np.ldexp(1.0, wbits))),
                          torch.zeros_like(w))
         wr = wq * float(np.ldexp(1.0, -wbits))
         spot = spot & (wq > 0)
-        terms = torch.where(out, (erf.oob_weight * (ex * ex)) * wr, wr * (dv * dv))
-    return torch.where(spot[None, :], terms, zero).t().contiguous()
+        penalty, inside = penalty * wr, wr * inside
+    return torch.where(spot[None, :], torch.where(out, penalty, inside), zero).t().contiguous()
 
 
 class _SpotTerms(torch.autograd.Function):
-    """SpotError over the (k, n) field columns of the finished rays, no mask; ``ids``: the source
-    ray of every column.  Returns the (n, k) terms: an inside ray's are (gradient / 2)**2 -- the
-    kernel's own dx * dx, the halving is exact --, a penalised ray's ``oob_weight * ex**2`` per
-    field.  With ``weights`` (gradient / 2)**2 is no longer the term: the terms come from the
-    records' centroids (``_spot_terms``)."""
+    """SpotError over the finished rays, no mask; ``ids``: the source ray of every column.
+    ``dimension=None, codes=None``: ``block`` is the (k, n) field columns; else it is the
+    (2 * dimension, n) geometry block and ``codes`` the field codes (a direction field).  Returns
+    the (n, k) terms (``_spot_terms``): a penalised ray's ``oob_weight * ex**2`` per field, an
+    inside ray's squared distances to its group's centroid.  Over plain columns without
+    ``weights`` the latter are (gradient / 2)**2 -- the kernel's own dx * dx, the halving is
+    exact --; with ``weights`` or a direction field that is no longer the term, and they come from
+    the records' centroids."""
 
     @staticmethod
-    def forward(ctx, columns, erf, labels, ids, weights=None):
-        block = columns.detach().contiguous()
-        k = block.shape[0]
-        err, grad, acc = erf.evaluate(block, 0, 1 if k == 2 else -1, labels, perm=ids,
-                                      weights=weights)
+    def forward(ctx, block, erf, labels, ids, weights=None, dimension=None, codes=None):
+        rows = block.detach().contiguous()
+        ctx.chained = codes is not None
+        if codes is None:
+            codes = (0, 1)[:rows.shape[0]]
+        err, grad, acc = erf.evaluate(rows, codes[0], codes[1] if len(codes) == 2 else -1, labels,
+                                      perm=ids, dimension=dimension, weights=weights)
         ctx.save_for_backward(grad)
-        ctx.dtype = columns.dtype
-        v = block.double()
-        if weights is not None:
+        ctx.dtype = block.dtype
+        if ctx.chained:
+            link = ops._link_torch(rows, dimension)
+            v = torch.stack([ops._link_field_torch(link, c, dimension) for c in codes], dim=0)
             return _spot_terms(erf, v, labels, ids, acc, weights)
-        lo = torch.tensor([d[0] for d in erf.domain], dtype=torch.float64, device=v.device)[:, None]
-        hi = torch.tensor([d[1] for d in erf.domain], dtype=torch.float64, device=v.device)[:, None]
-        zero = torch.zeros((), dtype=torch.float64, device=v.device)
-        ex = torch.maximum(lo - v, zero) + torch.maximum(v - hi, zero)
-        out = ((v < lo) | (v > hi)).any(dim=0, keepdim=True)
-        # (a ray that does not count has a zero gradient and, outside, no penalty either: its
-        # label decides, which the kernel has looked up)
-        lab = labels[ids.long().clamp(0, labels.numel() - 1)]
-        spot = ((lab >= 0) & (lab < erf.n_groups) & torch.isfinite(v).all(dim=0))[None, :]
         half = 0.5 * grad
-        terms = torch.where(out, erf.oob_weight * (ex * ex), half * half)
-        return torch.where(spot, terms, zero).t().contiguous()
+        return _spot_terms(erf, rows.double(), labels, ids, acc, weights,
+                           inside=half * half if weights is None else None)
 
     @staticmethod
     def backward(ctx, upstream):
         grad, = ctx.saved_tensors
-        return (upstream.t() * grad).to(ctx.dtype), None, None, None, None
-
-
-class _SpotFieldTerms(torch.autograd.Function):
-    """SpotError with a direction field over the (2 * dimension, n) geometry block of the finished
-    rays, no mask; ``ids``: the source ray of every column, ``codes``: the field codes.  Returns
-    the (n, k) terms: an inside ray's squared distances to its group's centroid (from the records
-    of the evaluation), a penalised ray's ``oob_weight * ex**2`` per field."""
-
-    @staticmethod
-    def forward(ctx, block, erf, labels, ids, dimension, codes, weights=None):
-        rows = block.detach().contiguous()
-        k = len(codes)
-        err, grad, acc = erf.evaluate(rows, codes[0], codes[1] if k == 2 else -1, labels,
-                                      perm=ids, dimension=dimension, weights=weights)
-        ctx.save_for_backward(grad)
-        ctx.dtype = block.dtype
-        link = ops._link_torch(rows, dimension)
-        v = torch.stack([ops._link_field_torch(link, c, dimension) for c in codes], dim=0)
-        return _spot_terms(erf, v, labels, ids, acc, weights)
-
-    @staticmethod
-    def backward(ctx, upstream):
+        if not ctx.chained:
+            return (upstream.t() * grad).to(ctx.dtype), None, None, None, None, None, None
         # the kernel's chain rule has summed both fields' gradients into the rows: one weight per
         # ray is all that can be applied afterwards (the optimiser passes ones)
         if upstream.shape[1] == 2 and not torch.equal(upstream[:, 0], upstream[:, 1]):
             raise ValueError("SpotError with a direction field: the upstream gradient must weigh "
                              "both fields of a ray alike")
-        grad, = ctx.saved_tensors
         return (upstream[:, 0] * grad).to(ctx.dtype), None, None, None, None, None, None
 
 

@@ -1319,6 +1319,57 @@ def _chain_cpu(grad, n, dim, row_x, row_y, gx, gy, link, counts):
         grad[dim + b, :n] = torch.where(counts, end, zero)
 
 
+def _fields_cpu(rows, row_x, row_y, dimension):
+    """(x, y, link) of the columns on the CPU: the float64 fields (y: zeros with one field) and,
+    with a direction field, the ``_link_torch`` of the block that ``_chain_cpu`` needs (else None:
+    plain rows)."""
+    two = row_y >= 0
+    if dimension is not None and max(row_x, row_y) >= 2 * dimension:
+        link = _link_torch(rows, dimension)
+        x = _link_field_torch(link, row_x, dimension)
+        y = _link_field_torch(link, row_y, dimension) if two else torch.zeros_like(x)
+        return x, y, link
+    x = rows[row_x].double()
+    return x, (rows[row_y].double() if two else torch.zeros_like(x)), None
+
+
+def _outside_cpu(x, y, two, grid, oob, counts, w):
+    """The columns of ``counts`` outside the closed domain of ``grid``: returns (inside, pen, gx,
+    gy) -- the mask of the columns inside, the sum of the penalties ``oob * (ex**2 + ey**2)`` with
+    ``ex = max(x0 - x, 0) + max(x - x1, 0)``, and their derivatives, zero where a column is not
+    outside (gy: None with one field).  ``w``: a weight per column or None; penalty and derivative
+    are multiplied by it last."""
+    x0, x1, _, y0, y1, _ = grid
+    out = (x < x0) | (x > x1)
+    if two:
+        out |= (y < y0) | (y > y1)
+    inside, outside = counts & ~out, counts & out
+    zero = torch.zeros((), dtype=torch.float64)
+    ex = torch.maximum(x0 - x, zero) + torch.maximum(x - x1, zero)
+    ey = (torch.maximum(y0 - y, zero) + torch.maximum(y - y1, zero)) if two else torch.zeros_like(x)
+    pens = oob * (ex * ex + ey * ey)
+    gx = oob * (2.0 * ex) * ((x > x1).double() - (x < x0).double())
+    gy = oob * (2.0 * ey) * ((y > y1).double() - (y < y0).double()) if two else None
+    if w is not None:
+        pens, gx = pens * w, gx * w
+        gy = gy * w if two else None
+    pen = pens[outside].sum()
+    gx = torch.where(outside, gx, zero)
+    gy = torch.where(outside, gy, zero) if two else None
+    return inside, pen, gx, gy
+
+
+def _write_grad_cpu(grad, n, dimension, row_x, row_y, gx, gy, link, counts):
+    """The gradient rows from gx, gy: the chain rule onto all 2 * dimension rows with a direction
+    field (``link`` given; zeros where ``counts`` is false), else the fields' own rows."""
+    if link is not None:
+        _chain_cpu(grad, n, dimension, row_x, row_y, gx, gy, link, counts)
+    else:
+        grad[row_x, :n] = gx
+        if row_y >= 0:
+            grad[row_y, :n] = gy
+
+
 DENSITY_FIXED_ONE = 4294967296.0      # 2^32: one ray's total weight in the int64 histogram
 DENSITY_MAX_BINS = 65536
 
@@ -1458,14 +1509,7 @@ def _density_error_cpu(rows, row_x, row_y, goal, grid, oob, mask, grad, err, hq,
     two = row_y >= 0
     nx = goal.shape[-1]
     n = rows.shape[1]
-    link = None
-    if dimension is not None and max(row_x, row_y) >= 2 * dimension:
-        link = _link_torch(rows, dimension)
-        x = _link_field_torch(link, row_x, dimension)
-        y = _link_field_torch(link, row_y, dimension) if two else torch.zeros_like(x)
-    else:
-        x = rows[row_x].double()
-        y = rows[row_y].double() if two else torch.zeros_like(x)
+    x, y, link = _fields_cpu(rows, row_x, row_y, dimension)
     counts = torch.isfinite(x) & torch.isfinite(y)
     if mask is not None:
         counts &= mask[:n] >= 0
@@ -1473,23 +1517,8 @@ def _density_error_cpu(rows, row_x, row_y, goal, grid, oob, mask, grad, err, hq,
     if weights is not None:
         w, w_ok = _source_weights(weights, perm, n)
         counts &= w_ok
-    out = (x < x0) | (x > x1)
-    if two:
-        out |= (y < y0) | (y > y1)
-    inside, outside = counts & ~out, counts & out
-    zero = torch.zeros((), dtype=torch.float64)
     # outside: the penalty and its derivative (weighted: each times w last)
-    ex = torch.maximum(x0 - x, zero) + torch.maximum(x - x1, zero)
-    ey = (torch.maximum(y0 - y, zero) + torch.maximum(y - y1, zero)) if two else torch.zeros_like(x)
-    pens = oob * (ex * ex + ey * ey)
-    gx = oob * (2.0 * ex) * ((x > x1).double() - (x < x0).double())
-    gy = oob * (2.0 * ey) * ((y > y1).double() - (y < y0).double()) if two else None
-    if w is not None:
-        pens, gx = pens * w, gx * w
-        gy = gy * w if two else None
-    pen = pens[outside].sum()
-    gx = torch.where(outside, gx, zero)
-    gy = torch.where(outside, gy, zero) if two else None
+    inside, pen, gx, gy = _outside_cpu(x, y, two, grid, oob, counts, w)
     # inside: the fixed-point histogram
     xi, yi = x[inside], y[inside]
     wi = w[inside] if w is not None else None
@@ -1531,12 +1560,7 @@ def _density_error_cpu(rows, row_x, row_y, goal, grid, oob, mask, grad, err, hq,
     else:
         gxi = sx * (D[ib] - D[ia])
     gx[inside] = gxi if wi is None else gxi * wi
-    if link is not None:
-        _chain_cpu(grad, n, dimension, row_x, row_y, gx, gy, link, counts)
-    else:
-        grad[row_x, :n] = gx
-        if two:
-            grad[row_y, :n] = gy
+    _write_grad_cpu(grad, n, dimension, row_x, row_y, gx, gy, link, counts)
     e = e_hist + pen
     err[0], err[1], err[2] = e, 1.0, e
 
@@ -1709,14 +1733,7 @@ def _spot_error_cpu(rows, row_x, row_y, group, n_groups, grid, oob, mask, perm, 
     two = row_y >= 0
     n = rows.shape[1]
     qmax = float(np.ldexp(1.0, qbits))
-    link = None
-    if dimension is not None and max(row_x, row_y) >= 2 * dimension:
-        link = _link_torch(rows, dimension)
-        x = _link_field_torch(link, row_x, dimension)
-        y = _link_field_torch(link, row_y, dimension) if two else torch.zeros_like(x)
-    else:
-        x = rows[row_x].double()
-        y = rows[row_y].double() if two else torch.zeros_like(x)
+    x, y, link = _fields_cpu(rows, row_x, row_y, dimension)
     counting = torch.ones(n, dtype=torch.bool) if mask is None else (mask[:n] >= 0)
     finite = torch.isfinite(x) & torch.isfinite(y)
     s = torch.arange(n, dtype=torch.int64) if perm is None else perm[:n].long()
@@ -1731,67 +1748,37 @@ def _spot_error_cpu(rows, row_x, row_y, group, n_groups, grid, oob, mask, perm, 
         wq = torch.where(w_ok, torch.round(w * float(np.ldexp(1.0, wbits))), torch.zeros_like(w))
         wr = wq * float(np.ldexp(1.0, -wbits))
         spot &= wq > 0
-    out = (x < x0) | (x > x1)
-    if two:
-        out |= (y < y0) | (y > y1)
-    inside, outside = spot & ~out, spot & out
-    zero = torch.zeros((), dtype=torch.float64)
     # outside: the penalty and its derivative (weighted: each times wr last)
-    ex = torch.maximum(x0 - x, zero) + torch.maximum(x - x1, zero)
-    ey = (torch.maximum(y0 - y, zero) + torch.maximum(y - y1, zero)) if two else torch.zeros_like(x)
-    pens = oob * (ex * ex + ey * ey)
-    gx = oob * (2.0 * ex) * ((x > x1).double() - (x < x0).double())
-    gy = oob * (2.0 * ey) * ((y > y1).double() - (y < y0).double())
-    if wr is not None:
-        pens, gx, gy = pens * wr, gx * wr, gy * wr
-    pen = pens[outside].sum()
-    gx = torch.where(outside, gx, zero)
-    gy = torch.where(outside, gy, zero)
-    # inside: the fixed-point records
+    inside, pen, gx, gy = _outside_cpu(x, y, two, grid, oob, spot, wr)
+    # inside: the fixed-point records, one list of slots per layout
     xi, yi, li = x[inside], y[inside], label[inside]
     acc.zero_()
     qxi = torch.round((xi - x0) * qsx).clamp(0.0, qmax).long()
     qyi = torch.round((yi - y0) * qsy).clamp(0.0, qmax).long() if two else None
-    if wr is not None:
-        # records {W, Xhi, Xlo, Yhi, Ylo, count, 0, 0}: wq * q in two limbs of h and qbits - h bits
+    ones = torch.ones_like(li)
+    if wr is None:
+        slots = [ones, qxi, qyi]                       # {count, Sx, Sy, 0}
+    else:
+        # {W, Xhi, Xlo, Yhi, Ylo, count, 0, 0}: wq * q in two limbs of h and qbits - h bits
         h = qbits // 2
         low = (1 << h) - 1
-        lift = float(np.ldexp(1.0, h))
-        wqi, wri = wq[inside].long(), wr[inside]
-        acc[:, 0].index_add_(0, li, wqi)
-        acc[:, 1].index_add_(0, li, wqi * (qxi >> h))
-        acc[:, 2].index_add_(0, li, wqi * (qxi & low))
-        if two:
-            acc[:, 3].index_add_(0, li, wqi * (qyi >> h))
-            acc[:, 4].index_add_(0, li, wqi * (qyi & low))
-        acc[:, 5].index_add_(0, li, torch.ones_like(li))
-        W = acc[li, 0].double()
-        dx = xi - (x0 + ((acc[li, 1].double() * lift + acc[li, 2].double()) / W) / qsx)
-        gx[inside] = (2.0 * dx) * wri
-        terms = wri * (dx * dx)
-        if two:
-            dy = yi - (y0 + ((acc[li, 3].double() * lift + acc[li, 4].double()) / W) / qsy)
-            gy[inside] = (2.0 * dy) * wri
-            terms = terms + wri * (dy * dy)
-    else:
-        acc[:, 0].index_add_(0, li, torch.ones_like(li))
-        acc[:, 1].index_add_(0, li, qxi)
-        if two:
-            acc[:, 2].index_add_(0, li, qyi)
-        cnt = acc[li, 0].double()
-        dx = xi - (x0 + (acc[li, 1].double() / cnt) / qsx)
-        gx[inside] = 2.0 * dx
-        terms = dx * dx
-        if two:
-            dy = yi - (y0 + (acc[li, 2].double() / cnt) / qsy)
-            gy[inside] = 2.0 * dy
-            terms = terms + dy * dy
-    if link is not None:
-        _chain_cpu(grad, n, dimension, row_x, row_y, gx, gy, link, spot)
-    else:
-        grad[row_x, :n] = gx
-        if two:
-            grad[row_y, :n] = gy
+        wqi = wq[inside].long()
+        slots = [wqi, wqi * (qxi >> h), wqi * (qxi & low)]
+        slots += [wqi * (qyi >> h), wqi * (qyi & low)] if two else [None, None]
+        slots.append(ones)
+    for p, v in enumerate(slots):
+        if v is not None:
+            acc[:, p].index_add_(0, li, v)
+    # (spot_centroids reads both layouts, group by group in the kernels' operation order)
+    centre = spot_centroids(acc, grid, 2 if two else 1, qbits)[li]
+    wri = None if wr is None else wr[inside]
+    terms = None
+    for k, (vi, g) in enumerate(((xi, gx), (yi, gy))[:2 if two else 1]):
+        d = vi - centre[:, k]
+        g[inside] = 2.0 * d if wri is None else (2.0 * d) * wri
+        t = d * d if wri is None else wri * (d * d)
+        terms = t if terms is None else terms + t
+    _write_grad_cpu(grad, n, dimension, row_x, row_y, gx, gy, link, spot)
     e = terms.sum() + pen
     n_terms = float(int(counting.sum()) * (2 if two else 1))
     err[0], err[1] = e, n_terms

@@ -1,43 +1,73 @@
 // tfrt 3-D hot path for MI355X (gfx950): ray x triangle intersection, nearest hit, stable
-// classification/compaction, Snell update, pass loop and reverse sweep.
+// classification/compaction, Snell update, pass loop and reverse sweep.  This comment is the
+// file's map; "section" names the ruler (// ---- name) under which a kernel stands.
 //
-// Structure of one pass (reference: tfrt/engine.py:2193-2302 single_pass):
+// The scheme every forward route shares.  A pair (ray, face) is first put through a
+// conservative float32 line-vs-sphere test, (c.a - s.a)^2 + (c.b - s.b)^2 <= r^2 (8 FMA-class
+// ops; (a, b) an orthonormal pair spanning the plane perpendicular to the ray, in a mesh-centred
+// frame); whatever it lets through is screened by a float32 Moeller-Trumbore evaluation with
+// error bounds (may_hit) and then decided EXACTLY in float64 with the reference's own Cramer sums
+// and epsilons (trace_math.h exact_triangle), so hit/miss and nearest-hit decisions are the
+// float64 reference's decisions; the float32 stages only remove pairs that cannot hit.
 //
-//   k_rayprep      per ray: float64 ray -> 8 float32 numbers (an orthonormal pair (a, b) spanning
-//                  the plane perpendicular to the ray, and -s.a, -s.b in a mesh-centred frame).
-//   intersect      decides every ray-face pair of the pass.  The unit of throughput is a
-//                  conservative float32 line-vs-sphere test, (c.a - s.a)^2 + (c.b - s.b)^2 <= r^2
-//                  (8 FMA-class ops); whatever it lets through is screened by a float32
-//                  Moeller-Trumbore evaluation with error bounds (may_hit) and then decided
-//                  EXACTLY in float64 with the reference's own Cramer sums and epsilons
-//                  (trace_math.h exact_triangle), so hit/miss and nearest-hit decisions are the
-//                  float64 reference's decisions; the float32 stages only remove pairs that
-//                  cannot hit.  Two kernels share that scheme, a third (rays handed over in a
-//                  coherent order) shares the walk of the hierarchy among a wavefront's rays:
-//        k_intersect_beam   (tfrt_scene3d.coherent_rays) one bundle per wavefront against the
-//                           sphere hierarchy with lane = node, the candidate faces as triangles
-//                           seen along the bundle's axis, exact float64 decisions; wavefronts
-//                           that are no narrow bundle are cut or left to k_intersect_group.
-//        k_intersect_group  (default, scenes of >= 64 faces) sphere hierarchy over k-d face
-//                           clusters: 8-cluster superclusters -> 16-face clusters -> faces;
-//                           lanes queue the clusters their rays touch, the wave drains the
-//                           queues together (member tests, screen, float64 decisions, each on
-//                           compacted full wavefronts).
-//        k_intersect3d      every pair through the sphere filter: grid (ray blocks, face
-//                           chunks), lane = R rays, spheres stream through an LDS tile.
-//   k_classify3d   min over chunks (lowest face index wins ties, like tf.argmin), boundary
-//                  catagory -> ray class, per-block class histogram.
-//   k_scan3d       one block: exclusive scan of the histograms -> stable output slots,
-//                  per-pass counts, running totals, next pass's ray count (all on device:
-//                  the host never synchronises inside a trace).
-//   k_react3d      projects the ray end onto the hit, writes finished / stopped / dead /
-//                  active-history rows at their stable slots, refracts/reflects active rays
-//                  (float64 Snell) into the next pass's ray block, records the tape.
+// Set-up, once per trace (section prep): k_hierarchy_spheres when the scene has the hierarchy
+// (has_hierarchy: 64 <= faces < 2^24 - 16 and tfrt_scene3d.cluster_order given), else k_center +
+// k_spheres; k_init (tfrt_common.h) alone when there is no face.
 //
-// Backward: k_backward3d walks the tape pass by pass in reverse, recomputes the per-ray
-// forward in float64 and applies the hand-derived adjoint (trace_math.h adjoint3d); the face
-// gradients of the rays are summed per wavefront in LDS (coherent rays) or left in a per-ray
-// stash that k_face_accumulate sums in LDS face windows (natural order).
+// Forward: four routes, chosen in trace3d_forward_t (section host-side plan).
+//   in place        inplace_trace: tfrt_scene3d.in_place != 0, coherent_rays != 0, not
+//                   deterministic, has_hierarchy, >= 64 rays, >= 1 pass.  ALL passes in one launch,
+//                   a lane keeps its ray: k_trace_inplace, or k_trace_inplace_rows when in_place
+//                   == 2 (the finished rows at the rays' own columns), wavefronts in the order of
+//                   tfrt_scene3d.wave_schedule when given (made by k_wave_schedule from an earlier
+//                   trace's work counts, which k_inplace_work sums).  The ray sets come lazily,
+//                   here or through tfrt_trace3d_compact: k_inplace_count (caller's numbering),
+//                   k_inplace_scan, k_inplace_gather.  All in section in-place trace.
+//   Otherwise a loop over the passes (tfrt/engine.py:2193-2302 single_pass), launch_intersect's
+//   choice of intersect kernels first:
+//   coherent        coherent_rays != 0, has_hierarchy, >= 64 rays: k_intersect_beam (section
+//                   coherent-wave intersect), one bundle per wavefront against the sphere
+//                   hierarchy with lane = node, exact float64 decisions; wavefronts that are no
+//                   narrow bundle are left to k_intersect_group_left (no launch with
+//                   coherent_only).
+//   grouped         has_hierarchy: k_intersect_group (section grouped intersect), 8-cluster
+//                   superclusters -> 16-face clusters -> faces; lanes queue the clusters their
+//                   rays touch, the wave drains the queues together.
+//   all pairs       else: k_rayprep + k_intersect3d (sections ray filter state, intersect), every
+//                   pair through the sphere filter, grid (ray blocks, face chunks), spheres
+//                   through an LDS tile.
+//   and the rest of the pass (sections classify, scan, react):
+//   k_classify3d    min over chunks (lowest face index wins ties, like tf.argmin), boundary
+//                   catagory -> ray class, per-block class histogram (not launched when the
+//                   grouped kernels ran as one cluster chunk: their epilogue does it).
+//   k_scan3d_one /  exclusive scan of the histograms -> stable output slots, per-pass counts,
+//   k_scan3d        running totals, next pass's ray count, all on the device (up to 4096 ray
+//                   blocks k_react3d scans for itself and neither is launched).
+//   k_react3d       projects the ray end onto the hit, writes finished / stopped / dead /
+//                   active-history rows at their stable slots, refracts/reflects active rays
+//                   (float64 Snell) into the next pass's ray block, records the tape.
+//   k_copy_rays (tfrt_common.h) hands back the rays still active after the last pass.
+//
+// Backward: three sweeps over the tape, chosen in trace3d_backward_t (section host-side plan);
+// the kernels are in section backward.  wave_sums = coherent_rays != 0, not deterministic, faces
+// and a face-gradient block present.
+//   chain           wave_sums, >= 1 pass and (at most CHAIN_MAXP = 8 passes or an in-place tape):
+//                   k_backward_chain, the whole sweep in one launch, a lane follows its ray's
+//                   chain of slots and walks back with the gradient in registers; the face
+//                   gradients of a wavefront are summed in LDS (wave_face_sums).
+//   chain, goal,    chain, called through tfrt_trace3d_backward_goal with no class gradient, an
+//   in place        in-place tape of in_place == 1 and at most 8 passes, per-face indices
+//                   (per_face_indices) and no gradient w.r.t. them: k_backward_chain_goal_inplace,
+//                   the optimiser's steady-state step.
+//   per pass        else (tfrt_trace3d_backward only): k_backward3d pass by pass in reverse (float64
+//                   recomputation, trace_math.h adjoint3d); face gradients by wave_face_sums
+//                   (wave_sums), by atomics, or left in a per-ray stash that k_face_accumulate
+//                   sums in LDS face windows -- deterministic: k_stash_absmax,
+//                   k_face_accumulate_fixed, k_fixed_finish (integer sums in face order).
+//
+// tfrt_intersect3d, the seam-level entry, runs set-up, launch_intersect (all pairs) and
+// k_finalize_seam (section misc); plan, workspace layout, the typed view of the tape and the typed
+// drivers of the C entries are in section host-side plan.
 #include <vector>
 
 #include <type_traits>
@@ -3099,14 +3129,6 @@ __device__ __forceinline__ int backward_ray(
 // (106 VGPRs = 4 waves per SIMD; the kernel is bound by float64 VALU issue -- ~2,000 executed
 // instructions per ray, 28 of them divisions -- and forcing 5 or 6 waves with
 // amdgpu_waves_per_eu spills: 55/66 us for the lens passes became 62/74 and 89/103)
-// a float64 from another lane of the row (DPP control word CTRL), both halves
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(const double v) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xFFFFFFFFll), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xF, 0xF, false);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
 
 // Coherent rays (tfrt_scene3d.coherent_rays): the 64 rays of a wavefront hit a handful of
 // faces.  Their terms are summed per face in LDS first (one slot per distinct face of the
@@ -3121,12 +3143,6 @@ __device__ __forceinline__ double dpp_f64(const double v) {
 // lanes read neighbouring doubles at a constant stride, nothing crosses lanes, and up to seven
 // faces take one step.  (The strides are the tier's cells padded to 2 mod 4 doubles: the copies
 // of one cell, which the lanes of an eight take together, lie in different LDS banks.)
-// -DTFRT_SWEEP_COPY_MAJOR=0 builds the earlier layout, copies innermost and folded across lanes
-// with DPP (tuning builds: scratch/build_variants.py).
-#ifndef TFRT_SWEEP_COPY_MAJOR
-#define TFRT_SWEEP_COPY_MAJOR 1
-#endif
-#if TFRT_SWEEP_COPY_MAJOR
 constexpr int WSUM_SLOTS = 32, WSUM_CELLS = 592;
 __device__ __forceinline__ constexpr int wsum_stride(int copies) {
   return WSUM_SLOTS * 9 * 2 / copies + 2;   // 8: 74, 4: 146, 2: 290
@@ -3158,9 +3174,6 @@ __device__ __forceinline__ void wsum_fold(double* wacc, const int32_t* wface, in
     }
   }
 }
-#else
-constexpr int WSUM_SLOTS = 32, WSUM_CELLS = 576;
-#endif
 __device__ __forceinline__ void wave_face_sums(int tri, const double gP[9], double* wacc,
                                                int32_t* wface, double* __restrict__ g_fverts) {
   const int lane = threadIdx.x & 63;
@@ -3176,7 +3189,6 @@ __device__ __forceinline__ void wave_face_sums(int tri, const double gP[9], doub
     ++ns;
     todo &= ~__ballot(mine);
   }
-#if TFRT_SWEEP_COPY_MAJOR
   const int copies = ns <= 8 ? 8 : (ns <= 16 ? 4 : 2);
   if (tri >= 0) {
     if (slot >= 0) {
@@ -3196,40 +3208,6 @@ __device__ __forceinline__ void wave_face_sums(int tri, const double gP[9], doub
   else if (copies == 4) wsum_fold<4>(wacc, wface, ns * 9, lane, g_fverts);
   else wsum_fold<2>(wacc, wface, ns * 9, lane, g_fverts);
   wave_fence();  // (the next use of wacc / wface must not overtake these reads and zeros)
-#else
-  const int copies = ns <= 8 ? 8 : (ns <= 16 ? 4 : 2);
-  const int cells = ns * 9 * copies;
-  for (int k = lane; k < cells; k += 64) wacc[k] = 0.0;
-  wave_fence();
-  if (tri >= 0) {
-    if (slot >= 0) {
-      double* w = &wacc[slot * 9 * copies + (lane & (copies - 1))];
-#pragma unroll
-      for (int c = 0; c < 9; ++c)
-        if (gP[c] != 0.0) unsafeAtomicAdd(w + c * copies, gP[c]);
-    } else {  // (more distinct faces than slots: rays that are not coherent after all)
-      double* gp = g_fverts + 9 * (int64_t)tri;
-#pragma unroll
-      for (int c = 0; c < 9; ++c)
-        if (gP[c] != 0.0) unsafeAtomicAdd(gp + c, gP[c]);
-    }
-  }
-  wave_fence();
-  // the copies of a sum lie in neighbouring lanes now: folded with DPP, then ONE atomic per
-  // (face, term) of the wavefront goes to memory
-  for (int k0 = 0; k0 < cells; k0 += 64) {
-    const int k = k0 + lane;
-    double v = k < cells ? wacc[k] : 0.0;
-    v += dpp_f64<0xB1>(v);                    // quad_perm [1,0,3,2]
-    if (copies >= 4) v += dpp_f64<0x4E>(v);   // quad_perm [2,3,0,1]
-    if (copies >= 8) v += dpp_f64<0x141>(v);  // row_half_mirror: the other quad of the eight
-    if ((lane & (copies - 1)) == 0 && k < cells && v != 0.0) {
-      const int term = k / copies;
-      unsafeAtomicAdd(g_fverts + 9 * (int64_t)wface[term / 9] + (term % 9), v);
-    }
-  }
-  wave_fence();  // (the next use of wacc / wface must not overtake these reads)
-#endif
 }
 
 // BW wavefronts per workgroup (the wavefronts share nothing: see k_intersect_beam)
@@ -3256,9 +3234,7 @@ __global__ __launch_bounds__(64 * BW) void k_backward3d(
     __shared__ __align__(16) double wacc[BW][WSUM_CELLS];  // (layout: wave_face_sums)
     __shared__ int32_t wface[BW][WSUM_SLOTS];
     const int wave = threadIdx.x >> 6;
-#if TFRT_SWEEP_COPY_MAJOR
     wsum_clear(wacc[wave]);
-#endif
     double gP[9];
     int tri = -1;
     if (i < n)
@@ -3565,14 +3541,6 @@ __device__ __forceinline__ int backward_core(
 // adjoint forms no face terms for a face nobody differentiates.
 // (n_a, n_b): the face's two index ratios as the set-up launch stored them (feta[4f], feta[4f + 1]
 // = snell_ratios) -- the adjoint picks one where it used to divide n_in and n_out again.
-// -DTFRT_SWEEP_SKIP_FROZEN=0 / -DTFRT_SWEEP_ETA_TABLE=0 build the earlier forms (all face terms
-// computed and dropped; (n_a, n_b) = (n_in, n_out) and divided): tuning builds.
-#ifndef TFRT_SWEEP_SKIP_FROZEN
-#define TFRT_SWEEP_SKIP_FROZEN 1
-#endif
-#ifndef TFRT_SWEEP_ETA_TABLE
-#define TFRT_SWEEP_ETA_TABLE 1
-#endif
 // FIN / CHILD: false where the caller knows that no lane of the wavefront finishes in this pass /
 // has a child ray in it -- the arm is not compiled in (k_backward_chain_goal_inplace's roles).
 template <bool FIN = true, bool CHILD = true>
@@ -3602,15 +3570,9 @@ __device__ __forceinline__ int backward_core_loaded(
     for (int k = 0; k < 3; ++k) nz = nz || g_s[k] != 0.0 || g_h[k] != 0.0;
     if (nz) {
       const int branch = ((tape & TAPE_INTERNAL) ? 1 : 0) | ((tape & TAPE_REFLECT) ? 2 : 0);
-      const bool face_terms = TFRT_SWEEP_SKIP_FROZEN ? face_wanted : true;
-#if TFRT_SWEEP_ETA_TABLE
       const double ratios[2] = {n_a, n_b};
       adjoint3d(s, e, P, t_rec, has_child, 1.0, 1.0, L, g_s, g_h, g_ce, gs, ge, gP, nullptr,
-                branch, false, face_terms, ratios);
-#else
-      adjoint3d(s, e, P, t_rec, has_child, n_a, n_b, L, g_s, g_h, g_ce, gs, ge, gP, nullptr,
-                branch, false, face_terms);
-#endif
+                branch, false, face_wanted, ratios);
       if (face_wanted) face_out = tri;
     }
   }
@@ -3732,9 +3694,7 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int P = a.P;
   int4* chain = chain_lds + (size_t)wave * P * 64;
-#if TFRT_SWEEP_COPY_MAJOR
   wsum_clear(wacc[wave]);
-#endif
   // forward: the slots of this ray's chain and the pass it ends in; what the walk back needs of
   // every slot's record is read here, three independent loads per pass
   int last = -1;
@@ -3889,16 +3849,6 @@ struct ChainGoalArgs {
   int32_t rows_ascending;  // gf.row strictly ascending: register j is ROW j's (its column or none)
 };
 
-// -DTFRT_SWEEP_ROLES=0: one pass body for every wavefront, per-lane 64-bit addresses;
-// -DTFRT_SWEEP_GOAL_ROWS=0: the run-time loop over the goal's columns for every order of rows
-// (tuning builds: scratch/build_variants.py)
-#ifndef TFRT_SWEEP_ROLES
-#define TFRT_SWEEP_ROLES 1
-#endif
-#ifndef TFRT_SWEEP_GOAL_ROWS
-#define TFRT_SWEEP_GOAL_ROWS 1
-#endif
-
 // Strictly ascending rows (("y_end", "z_end"): the usual goal) need no run-time loop: register j
 // of the pass holds row j's goal value and an unrolled loop over the six rows, scalar branches on
 // "this row has a column", takes the residuals in ascending row order -- the column order, so the
@@ -3906,7 +3856,7 @@ struct ChainGoalArgs {
 // columns, with register c column c's value and the rows in one scalar.
 template <typename T>
 static void chain_goal_columns(ChainGoalArgs<T>& g) {
-  bool asc = TFRT_SWEEP_GOAL_ROWS != 0;
+  bool asc = true;
   for (int c = 1; c < g.gf.n; ++c) asc = asc && g.gf.row[c] > g.gf.row[c - 1];
   g.rows_ascending = asc ? 1 : 0;
   g.rows_packed = 0;
@@ -3966,7 +3916,6 @@ __device__ __forceinline__ int chain_goal_pass(const ChainGoalArgs<T>& a, int p,
   T ray_w[6];
   double t_rec = 0.0;
   double goal_w[6] = {0, 0, 0, 0, 0, 0};
-#if TFRT_SWEEP_ROLES
   // (the lane through an empty statement the compiler cannot see past: what is made of it is
   // made in the pass that uses it and does not wait in vector registers through the whole walk,
   // which the adjoint needs.)  The wavefront's rows start at scalar addresses.
@@ -3988,22 +3937,6 @@ __device__ __forceinline__ int chain_goal_pass(const ChainGoalArgs<T>& a, int p,
       }
     }
   }
-#else
-  // (the lane's ray index through an empty statement the compiler cannot see past: the
-  // per-lane addresses below are then formed in the pass that uses them -- moved out of the
-  // loop they stay in 16 vector registers for the whole walk, which the adjoint needs)
-  int iv = wave * 64 + lane;
-  __asm__ volatile("" : "+v"(iv));
-#pragma unroll
-  for (int k = 0; k < 6; ++k) ray_w[k] = rin[k * sin + iv];
-  if (fin_here || on_face) t_rec = a.rec_t[off + iv];
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    const int cj = a.goal_col[j];
-    if (FIN && cj >= 0 && fin_here)
-      goal_w[j] = a.goal[(int64_t)cj * a.goal_stride + (int64_t)iv * a.goal_ray_stride];
-  }
-#endif
   double Pf[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, n_a = 1.0, n_b = 1.0;   // (backward_core_loaded)
   uint8_t mask_w = 1;
   if (on_face) {
@@ -4014,8 +3947,8 @@ __device__ __forceinline__ int chain_goal_pass(const ChainGoalArgs<T>& a, int p,
       mask_w = a.face_grad_mask[face];
   }
   if (with_child) {
-    n_a = a.feta[4 * (int64_t)face + (TFRT_SWEEP_ETA_TABLE ? 0 : 2)];
-    n_b = a.feta[4 * (int64_t)face + (TFRT_SWEEP_ETA_TABLE ? 1 : 3)];
+    n_a = a.feta[4 * (int64_t)face];
+    n_b = a.feta[4 * (int64_t)face + 1];
   }
   double s0[3], e0[3];
 #pragma unroll
@@ -4106,9 +4039,7 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
   __shared__ int32_t wface[WSUM_SLOTS];
   extern __shared__ int2 chain_goal_lds[];   // [pass][lane]: tape byte, face
   int2* chain = chain_goal_lds;
-#if TFRT_SWEEP_COPY_MAJOR
   wsum_clear(wacc);
-#endif
   const int P = a.P;
   int last = -1;
   if (i0 < n0) {
@@ -4142,7 +4073,6 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
     }
     const bool fin_here = here && p == last && (tape & 3) == CLS_FINISHED;
     const unsigned long long fin_m = __ballot(fin_here);
-#if TFRT_SWEEP_ROLES
     // The wavefronts of a coherent trace are nearly all of one role in a pass: nobody finishes
     // here, or everybody who is here finishes and nobody has a child -- one of the two bodies
     // runs (chain_goal_pass).  A mixed wavefront runs both, each with its own lanes.
@@ -4151,10 +4081,6 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
       tri = chain_goal_pass<T, true, false>(a, p, wave, lane, tape, face, fin_here, child, err, gP);
     if (here && !fin_role)
       tri = chain_goal_pass<T, false, true>(a, p, wave, lane, tape, face, false, child, err, gP);
-#else
-    if (here)
-      tri = chain_goal_pass<T, true, true>(a, p, wave, lane, tape, face, fin_here, child, err, gP);
-#endif
     n_fin += __popcll(fin_m);
     n_entered += __popcll(__ballot(here));
     wave_face_sums(tri, gP, wacc, wface, a.g_fverts);
@@ -4275,16 +4201,21 @@ struct Layout3 {
       fix_flag, fix_max, total;
 };
 
+// Hands out the regions of a workspace one behind the other, each on an aligned offset.
+struct Carver {
+  size_t o = 0;
+  size_t operator()(size_t bytes) {
+    const size_t at = o;
+    o = align_up(o + bytes);
+    return at;
+  }
+};
+
 static Layout3 make_layout(int64_t N, int64_t M, int P, int dtype, const Plan3& pl) {
   Layout3 L;
   const size_t esz = state_bytes(dtype);
   const size_t n = N > 0 ? N : 1, m = M > 0 ? M : 1;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    size_t at = o;
-    o = align_up(o + bytes);
-    return at;
-  };
+  Carver take;
   L.c0 = take(4 * sizeof(double));
   L.sphere = take(m * sizeof(float4));
   L.nrays = take((P + 2) * sizeof(int32_t));
@@ -4328,9 +4259,34 @@ static Layout3 make_layout(int64_t N, int64_t M, int P, int dtype, const Plan3& 
   L.fix_acc = take((size_t)9 * m * sizeof(unsigned long long));  // ordered accumulation
   L.fix_flag = take((size_t)9 * m);
   L.fix_max = take(2 * sizeof(unsigned long long));
-  L.total = o;
+  L.total = take.o;
   return L;
 }
+
+// Plan and layout of a trace of N rays over M faces in P passes: what every 3-D entry starts from.
+struct Frame3 {
+  Plan3 pl;
+  Layout3 lay;
+  Frame3(int64_t N, int64_t M, int P, int dtype)
+      : pl(make_plan(N, M)), lay(make_layout(N, M, P, dtype, pl)) {}
+  int check(size_t workspace_bytes) const { return workspace_bytes < lay.total ? TFRT_E_WORKSPACE : 0; }
+};
+
+// The workspace of the seam-level tfrt_intersect3d: sized and carved from this one description.
+struct SeamLayout3 {
+  size_t c0, sphere, nptr, part_t, part_i, prep, total;
+  SeamLayout3(int64_t N, int64_t M, const Plan3& pl) {
+    const size_t n = N > 0 ? N : 1, m = M > 0 ? M : 1;
+    Carver take;
+    c0 = take(4 * sizeof(double));
+    sphere = take(m * sizeof(float4));
+    nptr = take(64);   // the ray count and, 8 ints on, the eight trailing counters
+    part_t = take((size_t)pl.chunks * n * sizeof(double));
+    part_i = take((size_t)pl.chunks * n * sizeof(int32_t));
+    prep = take((size_t)8 * n * sizeof(float));
+    total = take.o;
+  }
+};
 
 // Typed view of the record a trace leaves in its workspace (Layout3), per-pass rows `n` slots
 // apart: the forward and the gather write it through a Tape3<T>, the sweeps read it through a
@@ -4351,7 +4307,7 @@ struct Tape3 {
   as<int32_t>* nrays = at<int32_t>(lay.nrays);   // rays entering pass 1..P, and P + 1
   as<double>* fnorm = at<double>(lay.fnorm);     // FaceTables
   as<double>* feta = at<double>(lay.feta);
-  as<uint32_t>* wcount = at<uint32_t>(lay.wcount);   // in-place traces: see make_layout
+  as<uint32_t>* wcount = at<uint32_t>(lay.wcount);   // in-place traces: see Layout3's wcount
   as<int4>* wbase = at<int4>(lay.wbase);
   as<InplaceTape>* tape_args = at<InplaceTape>(lay.tape_args);
   // pass p's output rays, their ids and last faces; its records
@@ -4415,24 +4371,49 @@ struct Ordered3 {
   int n_super = 0;
 };
 
+// What stays the same through a trace ...
+struct Intersect3 {
+  const Plan3& pl;
+  hipStream_t st;
+  const Accel3* ac;          // the hierarchy; null or without `order`: all pairs (k_intersect3d)
+  const float4* sphere;      // per-face spheres of the all-pairs filter
+  const double* fverts;
+  const double* c0;
+  int M;
+  double ei, es, er;         // intersect, size and ray-start epsilon
+  float* prep;               // scratch: the rays' filter state, ...
+  double* part_t;            // ... every chunk's nearest hit
+  int32_t* part_i;
+  int64_t n;                 // row stride of the three
+};
+// ... and what changes from pass to pass.
 template <typename T>
-static int launch_intersect(const Plan3& pl, hipStream_t st, const T* rays, int64_t stride,
-                            const int32_t* n_ptr, const int32_t* last_tri, const float4* sphere,
-                            const double* fverts, const double* c0, float* prep, int64_t pstride,
-                            int M, double ei, double es, double er, double* part_t,
-                            int32_t* part_i, int64_t part_stride, const Accel3* ac,
-                            bool prep_ready = false, const Classify3* classify = nullptr,
-                            bool* classified = nullptr, const Ordered3* od = nullptr) {
+struct IntersectPass3 {
+  const T* rays;
+  int64_t stride;
+  const int32_t* n_ptr;
+  const int32_t* last_tri;
+  bool prep_ready;             // `prep` holds this pass's filter state (k_react3d left it)
+  const Classify3* classify;   // or null
+  const Ordered3* od;          // or null: no coherent-ray trace
+};
+
+// Returns whether the pass's hit records are classified already (the grouped kernels' epilogue).
+template <typename T>
+static bool launch_intersect(const Intersect3& tr, const IntersectPass3<T>& ps) {
+  const Plan3& pl = tr.pl;
+  hipStream_t st = tr.st;
+  const Accel3* ac = tr.ac;
+  const Ordered3* od = ps.od;
   const bool grouped = ac != nullptr && ac->order != nullptr;
   Classify3 fz;
-  if (grouped && pl.g_chunks == 1 && classify != nullptr && classify->rec_cls != nullptr)
-    fz = *classify;
-  if (classified != nullptr) *classified = fz.rec_cls != nullptr;
+  if (grouped && pl.g_chunks == 1 && ps.classify != nullptr && ps.classify->rec_cls != nullptr)
+    fz = *ps.classify;
   // (the grouped kernel forms the filter state of a trace's first pass itself: prep = nullptr)
-  const bool prep_inline = grouped && !prep_ready;
-  if (!prep_ready && !prep_inline)
-    hipLaunchKernelGGL((k_rayprep<T>), dim3(pl.nblk), dim3(BLOCK), 0, st, rays, stride, n_ptr, c0,
-                       prep, pstride);
+  const bool prep_inline = grouped && !ps.prep_ready;
+  if (!ps.prep_ready && !prep_inline)
+    hipLaunchKernelGGL((k_rayprep<T>), dim3(pl.nblk), dim3(BLOCK), 0, st, ps.rays, ps.stride,
+                       ps.n_ptr, tr.c0, tr.prep, tr.n);
   dim3 grid(pl.ray_blocks, pl.chunks);
   if (grouped) grid = dim3(pl.g_blocks, pl.g_chunks);
   ProfScope prof(TFRT_PROF_INTERSECT, st);
@@ -4442,40 +4423,41 @@ static int launch_intersect(const Plan3& pl, hipStream_t st, const T* rays, int6
     int bundle = 64;
     if (od->coherent_only && od->nq <= 160 * 1024) bundle = 32;  // (125k rays: 0.191 against 0.200 ms per step; 250k: 0.223 against 0.211)
     constexpr int BEAM_BW = 1;
-    const BeamScene bs = {ac->susphere, ac->clsphere, ac->csphere, ac->crec, fverts, c0,
-                          ac->n_clusters, od->n_super, ei, es, er};
+    const BeamScene bs = {ac->susphere, ac->clsphere, ac->csphere, ac->crec, tr.fverts, tr.c0,
+                          ac->n_clusters, od->n_super, tr.ei, tr.es, tr.er};
     hipLaunchKernelGGL((k_intersect_beam<T, BEAM_BW>), dim3(cdiv(od->nq, BEAM_BW * bundle)),
-                       dim3(64 * BEAM_BW), 0, st, rays, stride, n_ptr, last_tri, bs, fz.catagory,
-                       fz.rec_tri, fz.rec_t, fz.rec_cls, od->hist, od->left_list,
+                       dim3(64 * BEAM_BW), 0, st, ps.rays, ps.stride, ps.n_ptr, ps.last_tri, bs,
+                       fz.catagory, fz.rec_tri, fz.rec_t, fz.rec_cls, od->hist, od->left_list,
                        od->left_count, od->left_total, od->coherent_only, bundle);
     // (enough workgroups to fill the chip when every wavefront is left over; they loop)
     grid = dim3(min(cdiv(od->nq, BLOCK), 1280), 1);
-  }
-  if (grouped && od != nullptr) {
-    // (every wavefront was finished by k_intersect_beam: no launch)
+    // (coherent_only: every wavefront was finished by k_intersect_beam, no launch)
     if (!od->coherent_only)
-      hipLaunchKernelGGL((k_intersect_group_left<T>), grid, dim3(BLOCK), 0, st, rays, stride, n_ptr,
-                         last_tri, ac->susphere, ac->clsphere, ac->csphere, ac->crec, ac->cface,
-                         fverts, c0, ac->n_clusters, pl.g_chunk_clusters, ei, es, er, fz.catagory,
-                         fz.rec_tri, fz.rec_t, fz.rec_cls, od->left_list, od->left_count, od->hist);
+      hipLaunchKernelGGL((k_intersect_group_left<T>), grid, dim3(BLOCK), 0, st, ps.rays, ps.stride,
+                         ps.n_ptr, ps.last_tri, ac->susphere, ac->clsphere, ac->csphere, ac->crec,
+                         ac->cface, tr.fverts, tr.c0, ac->n_clusters, pl.g_chunk_clusters, tr.ei,
+                         tr.es, tr.er, fz.catagory, fz.rec_tri, fz.rec_t, fz.rec_cls, od->left_list,
+                         od->left_count, od->hist);
   } else if (grouped) {
-    hipLaunchKernelGGL((k_intersect_group<T>), grid, dim3(BLOCK), 0, st, rays, stride, n_ptr,
-                       last_tri, ac->susphere, ac->clsphere, ac->csphere, ac->crec, ac->cface,
-                       fverts, c0, prep_inline ? nullptr : prep, pstride, ac->n_clusters,
-                       pl.g_chunk_clusters, ei, es, er, part_t, part_i, part_stride, fz.catagory,
-                       fz.rec_tri, fz.rec_t, fz.rec_cls, fz.blockcnt);
+    hipLaunchKernelGGL((k_intersect_group<T>), grid, dim3(BLOCK), 0, st, ps.rays, ps.stride,
+                       ps.n_ptr, ps.last_tri, ac->susphere, ac->clsphere, ac->csphere, ac->crec,
+                       ac->cface, tr.fverts, tr.c0, prep_inline ? nullptr : tr.prep, tr.n,
+                       ac->n_clusters, pl.g_chunk_clusters, tr.ei, tr.es, tr.er, tr.part_t,
+                       tr.part_i, tr.n, fz.catagory, fz.rec_tri, fz.rec_t, fz.rec_cls, fz.blockcnt);
   } else {
-#define TFRT_LAUNCH_R(RR)                                                                      \
-    hipLaunchKernelGGL((k_intersect3d<T, RR>), grid, dim3(BLOCK), 0, st, rays, stride, n_ptr,  \
-                       last_tri, sphere, fverts, prep, pstride, M, pl.chunk_faces, ei, es, er, \
-                       part_t, part_i, part_stride)
+#define TFRT_LAUNCH_R(RR)                                                                     \
+    hipLaunchKernelGGL((k_intersect3d<T, RR>), grid, dim3(BLOCK), 0, st, ps.rays, ps.stride,  \
+                       ps.n_ptr, ps.last_tri, tr.sphere, tr.fverts, tr.prep, tr.n, tr.M,      \
+                       pl.chunk_faces, tr.ei, tr.es, tr.er, tr.part_t, tr.part_i, tr.n)
     if (pl.R == 1) { TFRT_LAUNCH_R(1); }
     else if (pl.R == 4) { TFRT_LAUNCH_R(4); }
     else { TFRT_LAUNCH_R(2); }
 #undef TFRT_LAUNCH_R
   }
-  return 0;
+  return fz.rec_cls != nullptr;
 }
+
+constexpr tfrt_ray_out NO_RAYS = {nullptr, nullptr, nullptr, 0};   // a ray set nobody asked for
 
 static bool scene_ok(const tfrt_scene3d* sc) {
   if (!sc || sc->n_faces < 0) return false;
@@ -4507,6 +4489,22 @@ static bool inplace_trace(const tfrt_scene3d* sc, int64_t N, int64_t M, int P) {
          has_hierarchy(sc, M) && N >= 64 && P >= 1;
 }
 
+// How an in-place trace of N rays is cut into wavefronts: `bundle` rays each, `nwaves` of them,
+// count rows `wstride` words apart; the wave schedule orders `ngroups` groups of 64 rays, each
+// 1 << gshift wavefronts.
+struct InplaceWaves {
+  int32_t bundle, nwaves, wstride, ngroups, gshift;
+};
+static InplaceWaves inplace_waves(int64_t N) {
+  InplaceWaves w;
+  w.bundle = inplace_bundle(N);
+  w.nwaves = cdiv(N, w.bundle);
+  w.wstride = (int32_t)inplace_wstride(N);
+  w.ngroups = cdiv(N, 64);
+  w.gshift = w.bundle == 64 ? 0 : 1;
+  return w;
+}
+
 // the built-in goal error folded into the sweep (tfrt_trace3d_backward_goal)
 struct ChainGoal {
   const void* fin_rays;
@@ -4536,46 +4534,143 @@ struct SweepCall3 {
   const ChainGoal* goal;
 };
 
+// ------------------------------------------------- kernel arguments, each made in one place
+
+template <typename T>
+static FaceTables face_tables_of(const Tape3<T>& tape, const tfrt_scene3d* sc) {
+  FaceTables ft;
+  ft.fnorm = tape.fnorm;
+  if (per_face_indices(sc)) ft.feta = tape.feta;
+  ft.mat_in = sc->mat_in, ft.mat_out = sc->mat_out;
+  ft.n_table = sc->n_table, ft.n_table_stride = sc->n_table_stride;
+  ft.n_in = sc->n_in, ft.n_out = sc->n_out;
+  return ft;
+}
+
+// fin_rows: the finished set of a tfrt_scene3d.in_place == 2 trace (every ray's finished row at
+// the ray's own column), or null
+template <typename T>
+static InplaceTape inplace_tape_of(const Tape3<T>& tape, const tfrt_scene3d* sc,
+                                   const FaceTables& ft, double L, const InplaceWaves& w,
+                                   const tfrt_ray_out* fin_rows) {
+  InplaceTape it = {};
+  it.rays_ws = tape.rays_out(0), it.n = (int64_t)tape.n;
+  it.rec_tri = tape.rec_tri(0), it.rec_t = tape.rec_t(0), it.rec_cls = tape.rec_cls(0);
+  it.wcount = tape.wcount, it.wstride = w.wstride;
+  it.catagory = sc->catagory;
+  it.fnorm = ft.fnorm, it.feta = ft.feta;
+  it.n_table = sc->n_table, it.n_table_stride = sc->n_table_stride;
+  it.mat_in = sc->mat_in, it.mat_out = sc->mat_out;
+  it.L = L;
+  if (fin_rows != nullptr) {
+    it.fin_rows = fin_rows->rays, it.fin_cap = fin_rows->capacity;
+    it.fin_face = fin_rows->face, it.fin_passes = fin_rows->ray_id;
+  }
+  return it;
+}
+
+template <typename T>
+static InplaceArgs<T> inplace_args_of(const TraceCall<tfrt_scene3d>& c, const Tape3<T>& tape,
+                                      const InplaceWaves& w) {
+  InplaceArgs<T> a;
+  a.src = static_cast<const T*>(c.src), a.src_stride = c.src_stride;
+  a.N = (int32_t)c.N, a.P = c.P;
+  a.bundle = w.bundle, a.nwaves = w.nwaves;
+  a.tape = tape.tape_args;
+  a.sched = c.sc->wave_schedule, a.ngroups = w.ngroups, a.gshift = w.gshift;
+  return a;
+}
+
+// ray_slot (tfrt_scene3d.ray_slot) or null: with it the sets come out in the caller's numbering,
+// wavefronts of 64 of ITS consecutive rays (GatherArgs.slot_of)
+template <typename T>
+static GatherArgs<T> gather_args_of(const TraceCall<tfrt_scene3d>& c, const Tape3<T>& tape,
+                                    const InplaceWaves& w, const int32_t* ray_slot) {
+  GatherArgs<T> a;
+  a.src = static_cast<const T*>(c.src), a.src_stride = c.src_stride;
+  a.N = (int32_t)c.N, a.P = c.P;
+  a.bundle = ray_slot != nullptr ? 64 : w.bundle;
+  a.nwaves = ray_slot != nullptr ? w.ngroups : w.nwaves;
+  a.rays_ws = tape.rays_out(0), a.n = (int64_t)tape.n;
+  a.rec_tri = tape.rec_tri(0), a.rec_t = tape.rec_t(0), a.rec_cls = tape.rec_cls(0);
+  a.rec_slot = tape.rec_slot(0);
+  a.wbase = tape.wbase, a.wstride = w.wstride;
+  a.counts = c.counts, a.flags = c.flags, a.dead_len = c.dead_len;
+  a.fin = c.fin ? *c.fin : NO_RAYS, a.act = c.act ? *c.act : NO_RAYS;
+  a.stp = c.stp ? *c.stp : NO_RAYS, a.dead = c.dead ? *c.dead : NO_RAYS;
+  a.unfinished = static_cast<T*>(c.unfinished), a.unfinished_id = c.unfinished_id;
+  a.err = c.counts + (size_t)c.P * TFRT_COUNTS_PER_PASS + 6;
+  a.slot_of = ray_slot;
+  return a;
+}
+
+// tape_mode: ChainArgs.inplace
+template <typename T>
+static ChainArgs<T> chain_args_of(const SweepCall3& c, const Tape3<const T>& tape, int tape_mode) {
+  ChainArgs<T> a;
+  a.src = static_cast<const T*>(c.src), a.src_stride = c.src_stride;
+  a.rays_ws = tape.rays_out(0), a.n = (int64_t)tape.n;
+  a.nrays = tape.nrays, a.rayid = tape.ids(0);
+  a.rec_tri = tape.rec_tri(0), a.rec_slot = tape.rec_slot(0);
+  a.rec_t = tape.rec_t(0), a.rec_cls = tape.rec_cls(0);
+  a.counts = c.counts;
+  a.P = c.P, a.L = c.L, a.dead_len = c.dead_len;
+  a.g_fin = c.g_fin, a.cap_fin = c.cap_fin;
+  a.g_act = c.g_act, a.cap_act = c.cap_act;
+  a.g_stp = c.g_stp, a.cap_stp = c.cap_stp;
+  a.g_dead = c.g_dead, a.cap_dead = c.cap_dead;
+  a.g_src = c.g_src, a.N = c.N;
+  a.g_fverts = c.g_fverts;
+  const ChainGoal no_goal = {};   // (no fields, null pointers)
+  const ChainGoal& g = c.goal != nullptr ? *c.goal : no_goal;
+  a.fin_rays = static_cast<const T*>(g.fin_rays), a.fin_cap = g.fin_cap;
+  a.gf = g.gf;
+  a.goal = g.goal, a.goal_stride = g.goal_stride, a.goal_ray_stride = g.goal_ray_stride;
+  a.partial = g.partial, a.partial_cnt = g.partial_cnt;
+  a.feta = per_face_indices(c.sc) ? tape.feta : nullptr;
+  a.inplace = tape_mode;
+  a.chain_in_lds = c.P <= CHAIN_MAXP ? 1 : 0;
+  return a;
+}
+
+// k_backward_chain_goal_inplace reads a part of what k_backward_chain reads, and two fields of the
+// scene
+template <typename T>
+static ChainGoalArgs<T> chain_goal_args_of(const ChainArgs<T>& a, const tfrt_scene3d* sc) {
+  ChainGoalArgs<T> g;
+  g.src = a.src, g.src_stride = a.src_stride;
+  g.rays_ws = a.rays_ws, g.n = a.n;
+  g.nrays = a.nrays;
+  g.rec_tri = a.rec_tri, g.rec_t = a.rec_t, g.rec_cls = a.rec_cls;
+  g.P = a.P, g.L = a.L;
+  g.g_src = a.g_src, g.N = a.N;
+  g.g_fverts = a.g_fverts;
+  g.gf = a.gf;
+  g.goal = a.goal, g.goal_stride = a.goal_stride, g.goal_ray_stride = a.goal_ray_stride;
+  g.partial = a.partial, g.partial_cnt = a.partial_cnt;
+  g.feta = a.feta;
+  g.face_verts = sc->face_verts, g.face_grad_mask = sc->face_grad_mask;
+  g.sched = sc->wave_schedule, g.ngroups = cdiv(a.N, 64);
+  chain_goal_columns(g);
+  return g;
+}
+
+// ------------------------------------------------------------------------- the three drivers
+
+// The ray sets (and counts) of an in-place trace from its tape: tfrt_trace3d_forward when a set
+// was asked for, tfrt_trace3d_compact later.
 template <typename T>
 static int inplace_gather_t(const TraceCall<tfrt_scene3d>& c, int64_t M, const int32_t* ray_slot,
                             const Layout3& lay) {
-  const tfrt_ray_out none = {nullptr, nullptr, nullptr, 0};
   const int64_t N = c.N;
   const int P = c.P;
   hipStream_t st = c.st;
   const Tape3<T> tape(c.workspace, lay, N);
-  GatherArgs<T> a;
-  a.src = static_cast<const T*>(c.src);
-  a.src_stride = c.src_stride;
-  a.N = (int32_t)N;
-  a.P = P;
-  a.bundle = inplace_bundle(N);
-  a.nwaves = cdiv(N, a.bundle);
-  a.rays_ws = tape.rays_out(0);
-  a.rec_tri = tape.rec_tri(0);
-  a.rec_t = tape.rec_t(0);
-  a.rec_cls = tape.rec_cls(0);
-  a.rec_slot = tape.rec_slot(0);
-  a.n = (int64_t)tape.n;
-  a.wbase = tape.wbase;
-  a.wstride = (int32_t)inplace_wstride(N);
-  a.counts = c.counts;
-  a.flags = c.flags;
-  a.dead_len = c.dead_len;
-  a.fin = c.fin ? *c.fin : none;
-  a.act = c.act ? *c.act : none;
-  a.stp = c.stp ? *c.stp : none;
-  a.dead = c.dead ? *c.dead : none;
-  a.unfinished = static_cast<T*>(c.unfinished);
-  a.unfinished_id = c.unfinished_id;
-  a.err = c.counts + (size_t)P * TFRT_COUNTS_PER_PASS + 6;
-  a.slot_of = ray_slot;
+  const GatherArgs<T> a = gather_args_of<T>(c, tape, inplace_waves(N), ray_slot);
   const uint32_t* wcount = tape.wcount;
   if (ray_slot != nullptr) {
-    // the caller's numbering: wavefronts of 64 of ITS consecutive rays, counted from the tape
-    // (their rows: behind the trace's own count rows and the two work rows)
-    a.bundle = 64;
-    a.nwaves = cdiv(N, 64);
+    // the caller's numbering: its wavefronts counted from the tape (their rows: behind the
+    // trace's own count rows and the two work rows)
     uint32_t* wnat = tape.wcount + (size_t)(P + 2) * a.wstride;
     hipLaunchKernelGGL(k_inplace_count, dim3(a.nwaves), dim3(64), 0, st, a.rec_cls, a.n, (int)N, P,
                        ray_slot, wnat, a.wstride);
@@ -4595,35 +4690,23 @@ static int trace3d_forward_t(const TraceCall<tfrt_scene3d>& c) {
   const int P = c.P;
   hipStream_t st = c.st;
   const int M = (int)sc->n_faces;
-  Plan3 pl = make_plan(N, M);
-  const Layout3 lay = make_layout(N, M, P, c.dtype, pl);
-  if (c.workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
+  const Frame3 fr(N, M, P, c.dtype);
+  if (fr.check(c.workspace_bytes)) return TFRT_E_WORKSPACE;
+  const Layout3& lay = fr.lay;
+  Plan3 pl = fr.pl;
   const Tape3<T> tape(c.workspace, lay, N);
   // (the forward's own regions: nobody else reads them)
-  char* ws = static_cast<char*>(c.workspace);
-  double* c0 = reinterpret_cast<double*>(ws + lay.c0);
-  float4* sphere = reinterpret_cast<float4*>(ws + lay.sphere);
-  int32_t* blockcnt = reinterpret_cast<int32_t*>(ws + lay.blockcnt);
-  int32_t* blockoff = reinterpret_cast<int32_t*>(ws + lay.blockoff);
-  int32_t* rowtot = reinterpret_cast<int32_t*>(ws + lay.rowtot);
-  int32_t* rowbase = reinterpret_cast<int32_t*>(ws + lay.rowbase);
-  unsigned int* ticket = reinterpret_cast<unsigned int*>(ws + lay.ticket);
-  double* part_t = reinterpret_cast<double*>(ws + lay.part_t);
-  int32_t* part_i = reinterpret_cast<int32_t*>(ws + lay.part_i);
-  float* prep = reinterpret_cast<float*>(ws + lay.prep);
-  int32_t* hist_ab[2] = {reinterpret_cast<int32_t*>(ws + lay.hist_a),
-                         reinterpret_cast<int32_t*>(ws + lay.hist_b)};
-  int32_t* left_list = reinterpret_cast<int32_t*>(ws + lay.left_list);
+  auto i32 = [&](size_t at) { return tape.template at<int32_t>(at); };
+  auto f4 = [&](size_t at) { return tape.template at<float4>(at); };
+  double* c0 = tape.template at<double>(lay.c0);
+  float4* sphere = f4(lay.sphere);
+  int32_t *blockcnt = i32(lay.blockcnt), *blockoff = i32(lay.blockoff);
+  int32_t *rowtot = i32(lay.rowtot), *rowbase = i32(lay.rowbase);
+  unsigned int* ticket = tape.template at<unsigned int>(lay.ticket);
+  int32_t* hist_ab[2] = {i32(lay.hist_a), i32(lay.hist_b)};
+  int32_t* left_list = i32(lay.left_list);
   int32_t* nrays = tape.nrays;
-  FaceTables ft;
-  ft.fnorm = tape.fnorm;
-  if (per_face_indices(sc)) ft.feta = tape.feta;
-  ft.mat_in = sc->mat_in;
-  ft.mat_out = sc->mat_out;
-  ft.n_table = sc->n_table;
-  ft.n_table_stride = sc->n_table_stride;
-  ft.n_in = sc->n_in;
-  ft.n_out = sc->n_out;
+  const FaceTables ft = face_tables_of(tape, sc);
   int32_t* tail = c.counts + (size_t)P * TFRT_COUNTS_PER_PASS;
   const int64_t n = (int64_t)tape.n;
 
@@ -4631,12 +4714,8 @@ static int trace3d_forward_t(const TraceCall<tfrt_scene3d>& c) {
   if (M <= 0 && sc->clear_buffer != nullptr && sc->clear_count > 0)   // (no set-up launch to do it)
     (void)hipMemsetAsync(sc->clear_buffer, 0, (size_t)sc->clear_count * sizeof(double), st);
   const Accel3 ac = {has_hierarchy(sc, M) ? sc->cluster_order : nullptr,
-                     cdiv(M > 0 ? M : 1, CLUSTER),
-                     reinterpret_cast<float4*>(ws + lay.csphere),
-                     reinterpret_cast<int32_t*>(ws + lay.cface),
-                     reinterpret_cast<float4*>(ws + lay.clsphere),
-                     reinterpret_cast<float4*>(ws + lay.susphere),
-                     reinterpret_cast<float4*>(ws + lay.crec)};
+                     cdiv(M > 0 ? M : 1, CLUSTER), f4(lay.csphere), i32(lay.cface),
+                     f4(lay.clsphere), f4(lay.susphere), f4(lay.crec)};
   // Coherent rays: wavefronts take k_intersect_beam's shared walk first; one cluster chunk,
   // classification in the kernels' epilogues
   const bool coherent = sc->coherent_rays != 0 && ac.order != nullptr && N >= 64;
@@ -4647,35 +4726,16 @@ static int trace3d_forward_t(const TraceCall<tfrt_scene3d>& c) {
   }
   const bool inplace = inplace_trace(sc, N, M, P);
   const bool rows_in_place = inplace && sc->in_place == 2;
-  InplaceTape it = {};
-  if (inplace) {
-    it.rays_ws = tape.rays_out(0);
-    it.rec_tri = tape.rec_tri(0);
-    it.rec_t = tape.rec_t(0);
-    it.rec_cls = tape.rec_cls(0);
-    it.n = n;
-    it.wcount = tape.wcount;
-    it.wstride = (int64_t)inplace_wstride(N);
-    it.catagory = sc->catagory;
-    it.fnorm = ft.fnorm;
-    it.feta = ft.feta;
-    it.n_table = sc->n_table;
-    it.mat_in = sc->mat_in;
-    it.mat_out = sc->mat_out;
-    it.n_table_stride = sc->n_table_stride;
-    it.L = c.L;
-    if (rows_in_place) {
-      // the finished rows at the rays' own columns: nothing is compacted, nothing else is written
-      if (!c.fin || !c.fin->rays || !c.fin->face || !c.fin->ray_id || c.fin->capacity < N ||
-          (c.act && c.act->rays) || (c.stp && c.stp->rays) || (c.dead && c.dead->rays) ||
-          c.unfinished != nullptr)
-        return TFRT_E_BADARG;
-      it.fin_rows = c.fin->rays;
-      it.fin_cap = c.fin->capacity;
-      it.fin_face = c.fin->face;
-      it.fin_passes = c.fin->ray_id;
-    }
-  }
+  const bool other_sets = (c.act && c.act->rays) || (c.stp && c.stp->rays) ||
+                          (c.dead && c.dead->rays) || c.unfinished != nullptr;
+  // the finished rows at the rays' own columns: nothing is compacted, nothing else is written
+  if (rows_in_place && (!c.fin || !c.fin->rays || !c.fin->face || !c.fin->ray_id ||
+                        c.fin->capacity < N || other_sets))
+    return TFRT_E_BADARG;
+  const InplaceWaves waves = inplace_waves(N);
+  const InplaceTape it =
+      inplace ? inplace_tape_of(tape, sc, ft, c.L, waves, rows_in_place ? c.fin : nullptr)
+              : InplaceTape{};
   if (M > 0) {
     if (ac.order != nullptr) {  // (the hierarchy kernel also does k_center's work)
       const int cl_blocks = cdiv((int64_t)ac.n_clusters * CLUSTER, BLOCK);
@@ -4695,20 +4755,9 @@ static int trace3d_forward_t(const TraceCall<tfrt_scene3d>& c) {
                          sc->clear_buffer ? sc->clear_count : 0);
     }
   }
-  const tfrt_ray_out none = {nullptr, nullptr, nullptr, 0};
   if (inplace) {
     // every pass in one launch, rays in place; then the counts, then (only if asked) the ray sets
-    InplaceArgs<T> a;
-    a.src = static_cast<const T*>(c.src);
-    a.src_stride = c.src_stride;
-    a.N = (int32_t)N;
-    a.P = P;
-    a.bundle = inplace_bundle(N);
-    a.nwaves = cdiv(N, a.bundle);
-    a.tape = tape.tape_args;
-    a.sched = sc->wave_schedule;
-    a.ngroups = cdiv(N, 64);
-    a.gshift = a.bundle == 64 ? 0 : 1;
+    const InplaceArgs<T> a = inplace_args_of<T>(c, tape, waves);
     // (with a schedule every group's wavefronts get a workgroup, the missing last one returns)
     const int n_groups_waves = a.sched != nullptr ? a.ngroups << a.gshift : a.nwaves;
     const BeamScene bs = {ac.susphere, ac.clsphere, ac.csphere, ac.crec, sc->face_verts, c0,
@@ -4722,46 +4771,37 @@ static int trace3d_forward_t(const TraceCall<tfrt_scene3d>& c) {
         hipLaunchKernelGGL((k_trace_inplace<T>), dim3(n_groups_waves), dim3(64), 0, st, a, bs);
     }
     // (no room for ray sets: no scan either -- tfrt_trace3d_compact makes counts and sets later)
-    const bool want_rows = !rows_in_place &&
-                           ((c.fin && c.fin->rays) || (c.act && c.act->rays) ||
-                            (c.stp && c.stp->rays) || (c.dead && c.dead->rays) ||
-                            c.unfinished != nullptr);
+    const bool want_rows = !rows_in_place && ((c.fin && c.fin->rays) || other_sets);
     if (want_rows) return inplace_gather_t<T>(c, M, sc->ray_slot, lay);
     return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
   }
   const int chunks_used = ac.order == nullptr ? pl.chunks : pl.g_chunks;
+  float* prep = tape.template at<float>(lay.prep);
+  const Intersect3 isect = {pl, st, &ac, sphere, sc->face_verts, c0, M, sc->intersect_epsilion,
+                            sc->size_epsilion, sc->ray_start_epsilion, prep,
+                            tape.template at<double>(lay.part_t), i32(lay.part_i), n};
   for (int p = 0; p < P; ++p) {
     const PassIn<T> in = tape.input(p, c.src, c.src_stride);
     int32_t* pass_counts = c.counts + (size_t)p * TFRT_COUNTS_PER_PASS;
-    Classify3 fz;
-    fz.catagory = sc->catagory;
-    fz.rec_tri = tape.rec_tri(p);
-    fz.rec_t = tape.rec_t(p);
-    fz.rec_cls = tape.rec_cls(p);
-    fz.blockcnt = blockcnt;
-    bool classified = false;
+    Classify3 fz = {sc->catagory, tape.rec_tri(p), tape.rec_t(p), tape.rec_cls(p), blockcnt};
     Ordered3 od;
     if (coherent) {
       od.nq = (int)N;
       od.hist = hist_ab[p & 1];
-      od.left_list = left_list;
-      od.left_count = od.hist + (size_t)pl.nblk * 4;
+      od.left_list = left_list, od.left_count = od.hist + (size_t)pl.nblk * 4;
       od.left_total = tail + 7;
       od.coherent_only = sc->coherent_only != 0;
       od.n_super = cdiv(ac.n_clusters, SUPER);
       fz.blockcnt = od.hist;
     }
-    if (launch_intersect<T>(pl, st, in.rays, in.stride, nrays + p, in.last, sphere,
-                            sc->face_verts, c0, prep, n, M, sc->intersect_epsilion,
-                            sc->size_epsilion, sc->ray_start_epsilion, part_t, part_i, n, &ac,
-                            /*prep_ready=*/p > 0, &fz, &classified,
-                            coherent ? &od : nullptr) != 0)
-      return TFRT_E_LAUNCH;
+    const IntersectPass3<T> pass = {in.rays, in.stride, nrays + p, in.last, /*prep_ready=*/p > 0,
+                                    &fz, coherent ? &od : nullptr};
+    const bool classified = launch_intersect<T>(isect, pass);
     int32_t* blockcnt_p = coherent ? od.hist : blockcnt;
     if (!classified)
       hipLaunchKernelGGL(k_classify3d, dim3(pl.nblk), dim3(BLOCK), 0, st, nrays + p, chunks_used,
-                         part_t, part_i, n, sc->catagory, tape.rec_tri(p), tape.rec_t(p),
-                         tape.rec_cls(p), blockcnt_p);
+                         isect.part_t, isect.part_i, n, sc->catagory, tape.rec_tri(p),
+                         tape.rec_t(p), tape.rec_cls(p), blockcnt_p);
     const bool grid_scan = pl.nblk >= SCAN_GRID_MIN_ROWS;
     SelfScan ss;
     if (coherent) {
@@ -4789,8 +4829,9 @@ static int trace3d_forward_t(const TraceCall<tfrt_scene3d>& c) {
                        nrays + p, in.ids, tape.rec_tri(p), tape.rec_t(p), tape.rec_cls(p),
                        blockoff, grid_scan ? rowbase : static_cast<int32_t*>(nullptr),
                        pass_counts, *sc, c.L, c.dead_len, c.flags, tape.rays_out(p), n, tape.ids(p),
-                       tape.last(p), tape.rec_slot(p), c.fin ? *c.fin : none,
-                       c.act ? *c.act : none, c.stp ? *c.stp : none, c.dead ? *c.dead : none, tail + 6,
+                       tape.last(p), tape.rec_slot(p), c.fin ? *c.fin : NO_RAYS,
+                       c.act ? *c.act : NO_RAYS, c.stp ? *c.stp : NO_RAYS,
+                       c.dead ? *c.dead : NO_RAYS, tail + 6,
                        (p + 1 < P && !coherent) ? prep : nullptr, n, c0, ss, ft.fnorm, ft.feta);
   }
   if (c.unfinished != nullptr && P > 0) {
@@ -4808,20 +4849,20 @@ static int trace3d_backward_t(const SweepCall3& c) {
   const int P = c.P;
   hipStream_t st = c.st;
   const int M = (int)sc->n_faces;
-  const Plan3 pl = make_plan(N, M);
-  const Layout3 lay = make_layout(N, M, P, c.dtype, pl);
-  if (c.workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
-  const Tape3<const T> tape(c.workspace, lay, N);
-  // (the sweep's own regions)
-  char* ws = static_cast<char*>(c.workspace);
+  const Frame3 fr(N, M, P, c.dtype);
+  if (fr.check(c.workspace_bytes)) return TFRT_E_WORKSPACE;
+  const Layout3& lay = fr.lay;
+  const Plan3& pl = fr.pl;
+  const Tape3<const T> tape(c.workspace, lay, N);   // the forward's record: read
+  const Tape3<T> own(c.workspace, lay, N);          // the sweep's own regions: written
   const int32_t* nrays = tape.nrays;
   using G = typename SweepStore<T>::type;  // (the regions are sized for float64)
-  G* gbuf = reinterpret_cast<G*>(ws + lay.gbuf);
-  G* stash_g_all = reinterpret_cast<G*>(ws + lay.stash_g);
-  int32_t* stash_face_all = reinterpret_cast<int32_t*>(ws + lay.stash_face);
-  unsigned long long* fix_acc = reinterpret_cast<unsigned long long*>(ws + lay.fix_acc);
-  uint8_t* fix_flag = reinterpret_cast<uint8_t*>(ws + lay.fix_flag);
-  unsigned long long* fix_max = reinterpret_cast<unsigned long long*>(ws + lay.fix_max);
+  G* gbuf = own.template at<G>(lay.gbuf);
+  G* stash_g_all = own.template at<G>(lay.stash_g);
+  int32_t* stash_face_all = own.template at<int32_t>(lay.stash_face);
+  unsigned long long* fix_acc = own.template at<unsigned long long>(lay.fix_acc);
+  uint8_t* fix_flag = own.template at<uint8_t>(lay.fix_flag);
+  unsigned long long* fix_max = own.template at<unsigned long long>(lay.fix_max);
   const int64_t n = (int64_t)tape.n;
   // Windowed LDS accumulation of the face gradients (k_face_accumulate): every window block
   // scans its chunk's face ids, so it is used while the windows are few; beyond that (and for
@@ -4842,110 +4883,41 @@ static int trace3d_backward_t(const SweepCall3& c) {
   // (one launch sums all passes now: a block per CU is enough -- 125k rays x 11 windows, step time
   // with 1024 / 2048 / 4096 / 8192 slots per block: 0.302 / 0.278 / 0.265 / 0.268 ms)
   while (acc_chunk > 1024 && (int64_t)cdiv(N, acc_chunk) * windows < 256) acc_chunk /= 2;
+
+  // ---- the route.  An in-place tape's mode (ChainArgs.inplace): class gradients are read through
+  // rec_slot, which k_inplace_gather fills (1); a sweep that is handed none but the built-in
+  // goal's never reads it (2); tfrt_scene3d.in_place == 2, the finished rows' gradient sits at
+  // the rays' own columns and no other class carries one -- like 2, rec_slot is never read (3)
   const bool inplace = inplace_trace(sc, N, M, P);
+  const bool class_grads = c.g_fin || c.g_act || c.g_stp || c.g_dead;
+  const int tape_mode = !inplace ? 0
+                        : (sc->in_place == 2 ? 3 : ((class_grads || c.goal == nullptr) ? 1 : 2));
+  // Three sweeps.  chain: coherent rays, the whole sweep in one launch along every ray's chain of
+  // slots (k_backward_chain); goal_inplace: the same for the optimiser's steady-state step, which
+  // has its own kernel (k_backward_chain_goal_inplace); neither: pass by pass (k_backward3d)
+  const bool chain = wave_sums && P >= 1 && (P <= CHAIN_MAXP || inplace);
+  const bool goal_inplace = chain && c.goal != nullptr && tape_mode == 2 && P <= CHAIN_MAXP &&
+                            per_face_indices(sc) && sc->grad_n_in == nullptr;
   if (inplace && !wave_sums) return TFRT_E_UNSUPPORTED;   // (deterministic: not with in_place)
-  if ((wave_sums && P >= 1 && (P <= CHAIN_MAXP || inplace)) || c.goal != nullptr) {
-    // coherent rays: the whole sweep in one launch (k_backward_chain)
-    if (!(wave_sums && P >= 1 && (P <= CHAIN_MAXP || inplace))) return TFRT_E_UNSUPPORTED;
-    ChainArgs<T> a;
-    a.src = static_cast<const T*>(c.src);
-    a.src_stride = c.src_stride;
-    a.rays_ws = tape.rays_out(0);
-    a.nrays = nrays;
-    a.rayid = tape.ids(0);
-    a.rec_tri = tape.rec_tri(0);
-    a.rec_slot = tape.rec_slot(0);
-    a.rec_t = tape.rec_t(0);
-    a.rec_cls = tape.rec_cls(0);
-    a.counts = c.counts;
-    a.n = n;
-    a.P = P;
-    a.L = c.L;
-    a.dead_len = c.dead_len;
-    a.g_fin = c.g_fin;
-    a.g_act = c.g_act;
-    a.g_stp = c.g_stp;
-    a.g_dead = c.g_dead;
-    a.cap_fin = c.cap_fin;
-    a.cap_act = c.cap_act;
-    a.cap_stp = c.cap_stp;
-    a.cap_dead = c.cap_dead;
-    a.g_src = c.g_src;
-    a.N = N;
-    a.g_fverts = c.g_fverts;
-    // (in-place tape: class gradients are read through rec_slot, which k_inplace_gather fills;
-    // a sweep that is handed none but the built-in goal's never reads it)
-    // 3 (tfrt_scene3d.in_place == 2): the finished rows' gradient sits at the rays' own columns,
-    // no other class carries one -- like 2, rec_slot is never read
-    if (inplace && sc->in_place == 2 &&
-        (c.g_act || c.g_stp || c.g_dead || c.goal != nullptr || c.cap_fin < N))
-      return TFRT_E_BADARG;
-    a.inplace = !inplace ? 0
-                : (sc->in_place == 2 ? 3
-                   : ((c.g_fin || c.g_act || c.g_stp || c.g_dead || c.goal == nullptr) ? 1 : 2));
-    a.chain_in_lds = P <= CHAIN_MAXP ? 1 : 0;
-    a.fin_rays = nullptr;
-    a.fin_cap = 0;
-    a.gf.n = 0;
-    a.goal = nullptr;
-    a.goal_stride = a.goal_ray_stride = 0;
-    a.partial = nullptr;
-    a.partial_cnt = nullptr;
-    a.feta = per_face_indices(sc) ? tape.feta : nullptr;
-    const size_t chain_lds = a.chain_in_lds ? (size_t)P * 64 * sizeof(int4) : 0;
+  if (c.goal != nullptr && !chain) return TFRT_E_UNSUPPORTED;
+  if (chain && tape_mode == 3 &&
+      (c.g_act || c.g_stp || c.g_dead || c.goal != nullptr || c.cap_fin < N))
+    return TFRT_E_BADARG;
+
+  if (chain) {
+    const ChainArgs<T> a = chain_args_of<T>(c, tape, tape_mode);
     ProfScope prof_bwd(TFRT_PROF_BACKWARD, st);
-    if (c.goal != nullptr) {
-      a.fin_rays = static_cast<const T*>(c.goal->fin_rays);
-      a.fin_cap = c.goal->fin_cap;
-      a.gf = c.goal->gf;
-      a.goal = c.goal->goal;
-      a.goal_stride = c.goal->goal_stride;
-      a.goal_ray_stride = c.goal->goal_ray_stride;
-      a.partial = c.goal->partial;
-      a.partial_cnt = c.goal->partial_cnt;
-      if (N > 0 && a.inplace == 2 && a.chain_in_lds && a.feta != nullptr &&
-          sc->grad_n_in == nullptr) {
-        // the optimiser's steady-state step: its own kernel (k_backward_chain_goal_inplace)
-        ChainGoalArgs<T> g;
-        g.src = a.src;
-        g.src_stride = a.src_stride;
-        g.rays_ws = a.rays_ws;
-        g.nrays = a.nrays;
-        g.rec_tri = a.rec_tri;
-        g.rec_t = a.rec_t;
-        g.rec_cls = a.rec_cls;
-        g.n = a.n;
-        g.P = a.P;
-        g.L = a.L;
-        g.g_src = a.g_src;
-        g.N = a.N;
-        g.g_fverts = a.g_fverts;
-        g.gf = a.gf;
-        g.goal = a.goal;
-        g.goal_stride = a.goal_stride;
-        g.goal_ray_stride = a.goal_ray_stride;
-        g.partial = a.partial;
-        g.partial_cnt = a.partial_cnt;
-        g.feta = a.feta;
-        g.face_verts = sc->face_verts;
-        g.face_grad_mask = sc->face_grad_mask;
-        g.sched = sc->wave_schedule;
-        g.ngroups = cdiv(N, 64);
-        chain_goal_columns(g);
-        hipLaunchKernelGGL((k_backward_chain_goal_inplace<T>), dim3(cdiv(N, 64)), dim3(64),
-                           (size_t)P * 64 * sizeof(int2), st, g);
-      } else if (N > 0 && sc->grad_n_in != nullptr)
-        hipLaunchKernelGGL((k_backward_chain<T, 1, true, true>), dim3(cdiv(N, 64)), dim3(64),
-                           chain_lds, st, a, *sc);
-      else if (N > 0)
-        hipLaunchKernelGGL((k_backward_chain<T, 1, true, false>), dim3(cdiv(N, 64)), dim3(64),
-                           chain_lds, st, a, *sc);
-    } else if (N > 0 && sc->grad_n_in != nullptr) {
-      hipLaunchKernelGGL((k_backward_chain<T, 1, false, true>), dim3(cdiv(N, 64)), dim3(64),
-                         chain_lds, st, a, *sc);
+    if (N > 0 && goal_inplace) {
+      hipLaunchKernelGGL((k_backward_chain_goal_inplace<T>), dim3(cdiv(N, 64)), dim3(64),
+                         (size_t)P * 64 * sizeof(int2), st, chain_goal_args_of(a, sc));
     } else if (N > 0) {
-      hipLaunchKernelGGL((k_backward_chain<T, 1, false, false>), dim3(cdiv(N, 64)), dim3(64),
-                         chain_lds, st, a, *sc);
+      using Kernel = void (*)(ChainArgs<T>, tfrt_scene3d);
+      const Kernel kernel[2][2] = {   // [GOAL][GN]
+          {k_backward_chain<T, 1, false, false>, k_backward_chain<T, 1, false, true>},
+          {k_backward_chain<T, 1, true, false>, k_backward_chain<T, 1, true, true>}};
+      const size_t chain_lds = a.chain_in_lds ? (size_t)P * 64 * sizeof(int4) : 0;
+      hipLaunchKernelGGL(kernel[c.goal != nullptr][sc->grad_n_in != nullptr], dim3(cdiv(N, 64)),
+                         dim3(64), chain_lds, st, a, *sc);
     }
     return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
   }
@@ -4997,8 +4969,7 @@ extern "C" {
 size_t tfrt_trace3d_workspace_bytes(int64_t n_rays, int64_t n_faces, int32_t max_passes,
                                     int32_t state_dtype) {
   if (n_rays < 0 || n_faces < 0 || max_passes < 0) return 0;
-  const Plan3 pl = make_plan(n_rays, n_faces);
-  return make_layout(n_rays, n_faces, max_passes, state_dtype, pl).total;
+  return Frame3(n_rays, n_faces, max_passes, state_dtype).lay.total;
 }
 
 int tfrt_trace3d_forward(const void* src_rays, int64_t src_stride, int64_t n_rays,
@@ -5029,14 +5000,13 @@ int tfrt_trace3d_executed(int64_t n_rays, int64_t n_faces, int32_t max_passes, i
                           const void* workspace, size_t workspace_bytes, int64_t* executed,
                           void* stream) {
   if (n_rays < 64 || n_faces < 0 || max_passes < 1 || !workspace || !executed) return TFRT_E_BADARG;
-  const Plan3 pl = make_plan(n_rays, n_faces);
-  const Layout3 lay = make_layout(n_rays, n_faces, max_passes, state_dtype, pl);
-  if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
-  const int wstride = (int)inplace_wstride(n_rays);
-  const uint32_t* rows = Tape3<const void>(workspace, lay, n_rays).wcount + (size_t)max_passes * wstride;
+  const Frame3 fr(n_rays, n_faces, max_passes, state_dtype);
+  if (fr.check(workspace_bytes)) return TFRT_E_WORKSPACE;
+  const InplaceWaves w = inplace_waves(n_rays);
+  const uint32_t* rows =
+      Tape3<const void>(workspace, fr.lay, n_rays).wcount + (size_t)max_passes * w.wstride;
   hipLaunchKernelGGL(k_inplace_work, dim3(2), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), rows,
-                     cdiv(n_rays, inplace_bundle(n_rays)), wstride,
-                     reinterpret_cast<unsigned long long*>(executed));
+                     w.nwaves, w.wstride, reinterpret_cast<unsigned long long*>(executed));
   return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
 }
 
@@ -5046,14 +5016,12 @@ int tfrt_trace3d_wave_schedule(int64_t n_rays, int64_t n_faces, int32_t max_pass
   if (n_rays < 64 || n_rays >= (1ll << 31) - 4096 || n_faces < 0 || max_passes < 1 || !workspace ||
       !schedule_out)
     return TFRT_E_BADARG;
-  const Plan3 pl = make_plan(n_rays, n_faces);
-  const Layout3 lay = make_layout(n_rays, n_faces, max_passes, state_dtype, pl);
-  if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
-  const int bundle = inplace_bundle(n_rays);
+  const Frame3 fr(n_rays, n_faces, max_passes, state_dtype);
+  if (fr.check(workspace_bytes)) return TFRT_E_WORKSPACE;
+  const InplaceWaves w = inplace_waves(n_rays);
   hipLaunchKernelGGL(k_wave_schedule, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream),
-                     Tape3<const void>(workspace, lay, n_rays).wcount, (int)inplace_wstride(n_rays),
-                     (int)max_passes, cdiv(n_rays, bundle), 64 / bundle, cdiv(n_rays, 64),
-                     schedule_out);
+                     Tape3<const void>(workspace, fr.lay, n_rays).wcount, w.wstride,
+                     (int)max_passes, w.nwaves, 64 / w.bundle, w.ngroups, schedule_out);
   return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
 }
 
@@ -5062,18 +5030,17 @@ int tfrt_trace3d_wave_rows(int64_t n_rays, int64_t n_faces, int32_t max_passes, 
                            void* stream) {
   if (n_rays < 64 || n_rays >= (1ll << 31) - 4096 || n_faces < 0 || max_passes < 1 || !workspace)
     return TFRT_E_BADARG;
-  const Plan3 pl = make_plan(n_rays, n_faces);
-  const Layout3 lay = make_layout(n_rays, n_faces, max_passes, state_dtype, pl);
-  if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
-  const int nwaves = cdiv(n_rays, inplace_bundle(n_rays));
+  const Frame3 fr(n_rays, n_faces, max_passes, state_dtype);
+  if (fr.check(workspace_bytes)) return TFRT_E_WORKSPACE;
+  const InplaceWaves w = inplace_waves(n_rays);
   if (rows_out != nullptr &&
-      hipMemcpy2DAsync(rows_out, (size_t)nwaves * sizeof(uint32_t),
-                       Tape3<const void>(workspace, lay, n_rays).wcount,
-                       inplace_wstride(n_rays) * sizeof(uint32_t), (size_t)nwaves * sizeof(uint32_t),
+      hipMemcpy2DAsync(rows_out, (size_t)w.nwaves * sizeof(uint32_t),
+                       Tape3<const void>(workspace, fr.lay, n_rays).wcount,
+                       (size_t)w.wstride * sizeof(uint32_t), (size_t)w.nwaves * sizeof(uint32_t),
                        (size_t)max_passes + 2, hipMemcpyDeviceToDevice,
                        static_cast<hipStream_t>(stream)) != hipSuccess)
     return TFRT_E_LAUNCH;
-  return nwaves;
+  return w.nwaves;
 }
 
 int tfrt_trace3d_compact(const void* src_rays, int64_t src_stride, int64_t n_rays,
@@ -5086,16 +5053,15 @@ int tfrt_trace3d_compact(const void* src_rays, int64_t src_stride, int64_t n_ray
   if (n_rays < 64 || n_rays >= (1ll << 31) - 4096 || max_passes < 1 || !counts || !workspace ||
       !src_rays || src_stride < n_rays || n_faces < 0)
     return TFRT_E_BADARG;
-  const Plan3 pl = make_plan(n_rays, n_faces);
-  const Layout3 lay = make_layout(n_rays, n_faces, max_passes, state_dtype, pl);
-  if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
+  const Frame3 fr(n_rays, n_faces, max_passes, state_dtype);
+  if (fr.check(workspace_bytes)) return TFRT_E_WORKSPACE;
   // (no scene and no new-ray length: the gather reads neither)
   const TraceCall<tfrt_scene3d> c = {
       src_rays, src_stride, n_rays, nullptr, 0.0, dead_ray_length, max_passes, state_dtype, flags,
       finished, active, stopped, dead, unfinished, unfinished_id, counts, workspace,
       workspace_bytes, static_cast<hipStream_t>(stream)};
   return dispatch_state(state_dtype, TFRT_E_UNSUPPORTED, [&](auto tag) {
-    return inplace_gather_t<typename decltype(tag)::type>(c, n_faces, ray_slot, lay);
+    return inplace_gather_t<typename decltype(tag)::type>(c, n_faces, ray_slot, fr.lay);
   });
 }
 
@@ -5201,11 +5167,7 @@ int tfrt_trace3d_backward_goal(const void* src_rays, int64_t src_stride, int64_t
 
 size_t tfrt_intersect3d_workspace_bytes(int64_t n_rays, int64_t n_faces) {
   if (n_rays < 0 || n_faces < 0) return 0;
-  const Plan3 pl = make_plan(n_rays, n_faces);
-  const size_t n = n_rays > 0 ? n_rays : 1, m = n_faces > 0 ? n_faces : 1;
-  return align_up(4 * sizeof(double)) + align_up(m * sizeof(float4)) + align_up(64) +
-         align_up((size_t)pl.chunks * n * sizeof(double)) +
-         align_up((size_t)pl.chunks * n * sizeof(int32_t)) + align_up((size_t)8 * n * sizeof(float));
+  return SeamLayout3(n_rays, n_faces, make_plan(n_rays, n_faces)).total;
 }
 
 int tfrt_intersect3d(const void* rays, int64_t stride, int64_t n_rays, int32_t state_dtype,
@@ -5217,25 +5179,22 @@ int tfrt_intersect3d(const void* rays, int64_t stride, int64_t n_rays, int32_t s
   if (n_rays < 0 || n_faces < 0 || n_faces >= (1ll << 29) || stride < n_rays || !workspace ||
       (n_faces > 0 && !face_verts))
     return TFRT_E_BADARG;
-  if (workspace_bytes < tfrt_intersect3d_workspace_bytes(n_rays, n_faces)) return TFRT_E_WORKSPACE;
+  const Plan3 pl = make_plan(n_rays, n_faces);
+  const SeamLayout3 lay(n_rays, n_faces, pl);
+  if (workspace_bytes < lay.total) return TFRT_E_WORKSPACE;
   if (n_rays == 0) return 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int M = (int)n_faces;
-  const Plan3 pl = make_plan(n_rays, n_faces);
-  const size_t n = n_rays, m = n_faces > 0 ? n_faces : 1;
+  const int64_t n = n_rays;
   char* ws = static_cast<char*>(workspace);
-  size_t o = 0;
-  double* c0 = reinterpret_cast<double*>(ws + o);
-  o += align_up(4 * sizeof(double));
-  float4* sphere = reinterpret_cast<float4*>(ws + o);
-  o += align_up(m * sizeof(float4));
-  int32_t* nptr = reinterpret_cast<int32_t*>(ws + o);
-  o += align_up(64);
-  double* part_t = reinterpret_cast<double*>(ws + o);
-  o += align_up((size_t)pl.chunks * n * sizeof(double));
-  int32_t* part_i = reinterpret_cast<int32_t*>(ws + o);
-  o += align_up((size_t)pl.chunks * n * sizeof(int32_t));
-  float* prep = reinterpret_cast<float*>(ws + o);
+  double* c0 = reinterpret_cast<double*>(ws + lay.c0);
+  float4* sphere = reinterpret_cast<float4*>(ws + lay.sphere);
+  int32_t* nptr = reinterpret_cast<int32_t*>(ws + lay.nptr);
+  const Intersect3 isect = {pl, st, nullptr, sphere, face_verts, c0, M, intersect_epsilion,
+                            size_epsilion, ray_start_epsilion,
+                            reinterpret_cast<float*>(ws + lay.prep),
+                            reinterpret_cast<double*>(ws + lay.part_t),
+                            reinterpret_cast<int32_t*>(ws + lay.part_i), n};
   if (M <= 0)
     hipLaunchKernelGGL(k_init<>, dim3(1), dim3(64), 0, st, nptr, (int)n_rays, nptr + 8,
                        (unsigned int*)nullptr);
@@ -5248,12 +5207,12 @@ int tfrt_intersect3d(const void* rays, int64_t stride, int64_t n_rays, int32_t s
   }
   return dispatch_state(state_dtype, TFRT_E_UNSUPPORTED, [&](auto tag) {
     using T = typename decltype(tag)::type;
-    launch_intersect<T>(pl, st, static_cast<const T*>(rays), stride, nptr, nullptr, sphere,
-                        face_verts, c0, prep, (int64_t)n, M, intersect_epsilion, size_epsilion,
-                        ray_start_epsilion, part_t, part_i, (int64_t)n, nullptr);
-    hipLaunchKernelGGL((k_finalize_seam<T>), dim3(pl.nblk), dim3(BLOCK), 0, st,
-                       static_cast<const T*>(rays), stride, (int)n_rays, pl.chunks, part_t, part_i,
-                       (int64_t)n, face_verts, M, intersect_epsilion, size_epsilion,
+    const IntersectPass3<T> pass = {static_cast<const T*>(rays), stride, nptr, nullptr,
+                                    /*prep_ready=*/false, nullptr, nullptr};
+    launch_intersect<T>(isect, pass);
+    hipLaunchKernelGGL((k_finalize_seam<T>), dim3(pl.nblk), dim3(BLOCK), 0, st, pass.rays, stride,
+                       (int)n_rays, pl.chunks, isect.part_t, isect.part_i, n, face_verts, M,
+                       intersect_epsilion, size_epsilion,
                        ray_start_epsilion, x, y, z, valid, ray_u, trig_u, trig_v, gather_trig);
     return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
   });

@@ -258,19 +258,15 @@ TFRT_HD double adj_rsqrt(double x) {
 // Dot and cross products for the REVERSE sweep only, under the same licence: on the device fused
 // multiply-adds (3 and 6 instructions instead of the 5 and 9 of dot3 / cross3, whose separately
 // rounded products the forward's decisions need), on the host dot3 / cross3 themselves.
-// -DTFRT_ADJ_CONTRACT=0 builds the device code on dot3 / cross3 too (tuning builds).
-#ifndef TFRT_ADJ_CONTRACT
-#define TFRT_ADJ_CONTRACT 1
-#endif
 TFRT_HD double adj_dot3(const double a[3], const double b[3]) {
-#if defined(__HIP_DEVICE_COMPILE__) && TFRT_ADJ_CONTRACT
+#if defined(__HIP_DEVICE_COMPILE__)
   return __builtin_fma(a[2], b[2], __builtin_fma(a[1], b[1], a[0] * b[0]));
 #else
   return dot3(a, b);
 #endif
 }
 TFRT_HD void adj_cross3(const double a[3], const double b[3], double o[3]) {
-#if defined(__HIP_DEVICE_COMPILE__) && TFRT_ADJ_CONTRACT
+#if defined(__HIP_DEVICE_COMPILE__)
   o[0] = __builtin_fma(a[1], b[2], -(a[2] * b[1]));
   o[1] = __builtin_fma(a[2], b[0], -(a[0] * b[2]));
   o[2] = __builtin_fma(a[0], b[1], -(a[1] * b[0]));

@@ -136,6 +136,11 @@ typedef struct tfrt_face_surface_grad {
   const int32_t* corner_list;     /* face * 3 + corner, grouped by vertex */
   int64_t n_vertices;
   double* grad_parameters;        /* (V,) out (overwritten) */
+  /* (F,9) rows or NULL: the faces' four sums (tfrt_scene3d.face_sums: the first four doubles of
+   * every row; the other five are not read) in place of grad_face_verts -- expanded per face
+   * through face_verts (required then), the normal's half added as before.
+   * Both given: TFRT_E_BADARG, like all three upstreams NULL. */
+  const double* grad_face_sums;
 } tfrt_face_surface_grad;
 int tfrt_param_faces_forward_multi(const tfrt_face_surface* surfaces, int32_t n_surfaces,
                                    void* stream);
@@ -379,6 +384,20 @@ typedef struct tfrt_scene3d {
    * runs, so a captured launch sees later contents.  NULL: index order.  No reference counterpart
    * (the reference has no wavefronts). */
   const int32_t* wave_schedule;
+  /* Reverse sweep only.  0 (default): grad_face_verts is the (M,9) block of face-vertex gradients.
+   * 1: the four-sum form -- the first FOUR doubles of a face's row of that (M,9) block receive
+   * the sums, over the rays that hit the face, of the gradient w.r.t. C = (P1 - P0) x (P2 - P0)
+   * (three) and w.r.t. the hit parameter's numerator (one); the row's other five doubles are not
+   * written.  A face's nine vertex gradients are linear in these four with coefficients of the
+   * face alone, so the sweep neither forms nor sums the nine per ray; whoever reads the block
+   * expands once per face (tfrt_face_surface_grad.grad_face_sums does; csrc/trace_math.h
+   * face_sums_expand).  The rows stay where they are, so a face's row is its own in either form
+   * (frozen faces' rows stay zero) and clear_buffer / clear_count are what they were.  Honoured
+   * by the one-launch sweeps of coherent rays (k_backward_chain, k_backward_chain_goal_inplace);
+   * a call that would take any other route (deterministic, rays that are not coherent, more
+   * passes than the chain holds without in_place) returns TFRT_E_UNSUPPORTED before it launches
+   * anything and never writes the other form.  Pass the same value to the forward. */
+  int32_t face_sums;
 } tfrt_scene3d;
 
 /* One class of output rays (finished / active history / stopped / dead), compacted stably in
@@ -484,7 +503,8 @@ int tfrt_trace3d_wave_rows(int64_t n_rays, int64_t n_faces, int32_t max_passes, 
  *
  *   grad_finished/active/stopped/dead : 6 x capacity f64 blocks (row stride = the matching
  *              tfrt_ray_out.capacity of the forward call) or NULL
- *   grad_face_verts (M,9) f64, ACCUMULATED into (caller zeroes)
+ *   grad_face_verts (M,9) f64, ACCUMULATED into (caller zeroes); with tfrt_scene3d.face_sums only
+ *                   the first four doubles of every row (the faces' four sums)
  *   grad_src_rays   6 x n_rays f64 or NULL
  */
 int tfrt_trace3d_backward(const void* src_rays, int64_t src_stride, int64_t n_rays,
@@ -805,7 +825,8 @@ int tfrt_spot_error_weighted(const void* rows, int64_t stride, int64_t n, int32_
  *   goal_workspace  tfrt_trace3d_backward_goal_workspace_bytes(n_rays) bytes (the partial sums)
  *   pending         filled in like tfrt_goal_error3d_deferred's: finish with
  *                   tfrt_sgd_process_multi_finish or tfrt_goal_finish
- *   grad_face_verts (M,9) f64, ACCUMULATED into (cleared beforehand: tfrt_scene3d.clear_buffer)
+ *   grad_face_verts (M,9) f64, ACCUMULATED into (cleared beforehand: tfrt_scene3d.clear_buffer);
+ *                   the four sums with tfrt_scene3d.face_sums, as for tfrt_trace3d_backward
  * Everything else as for tfrt_trace3d_backward (grad_active / grad_stopped / grad_dead may be
  * given as well; the finished rows' gradient is the goal's). */
 size_t tfrt_trace3d_backward_goal_workspace_bytes(int64_t n_rays);

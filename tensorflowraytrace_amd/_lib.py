@@ -34,6 +34,7 @@ class Scene3D(ctypes.Structure):
         ("deterministic", c_i32), ("coherent_rays", c_i32), ("coherent_only", c_i32),
         ("grad_n_in", c_vp), ("grad_n_out", c_vp), ("clear_buffer", c_vp), ("clear_count", c_i64),
         ("in_place", c_i32), ("ray_slot", c_vp), ("wave_schedule", c_vp),
+        ("face_sums", c_i32),
     ]
 
 
@@ -71,7 +72,7 @@ class FaceSurfaceGrad(ctypes.Structure):
                 ("face_verts", ctypes.c_void_p), ("update_mask", ctypes.c_void_p),
                 ("vectors", ctypes.c_void_p), ("corner_start", ctypes.c_void_p),
                 ("corner_list", ctypes.c_void_p), ("n_vertices", ctypes.c_int64),
-                ("grad_parameters", ctypes.c_void_p)]
+                ("grad_parameters", ctypes.c_void_p), ("grad_face_sums", ctypes.c_void_p)]
 
 
 class GoalPending(ctypes.Structure):

@@ -114,11 +114,25 @@ __global__ __launch_bounds__(BLOCK) void k_param_faces(
 
 // shared by the two reverse kernels: gradient of the 9 face coordinates including the part
 // that arrives through the unit normal
+// g_fsums: the faces' four sums (tfrt_scene3d.face_sums: the first four doubles of the (F,9)
+// rows) in place of g_fverts -- expanded
+// here, once per face, by the formulas the sweep's nine-term form applies per ray
+// (trace_math.h face_sums_expand); only the multi-surface gather is handed them
 __device__ inline void face_grad(const double* __restrict__ g_fverts,
                                  const double* __restrict__ g_norm,
-                                 const double* __restrict__ fverts, int64_t f, double g[9]) {
+                                 const double* __restrict__ fverts, int64_t f, double g[9],
+                                 const double* __restrict__ g_fsums = nullptr) {
+  if (g_fsums != nullptr) {
+    double P[9], S[4];
 #pragma unroll
-  for (int q = 0; q < 9; ++q) g[q] = g_fverts ? g_fverts[9 * f + q] : 0.0;
+    for (int q = 0; q < 9; ++q) P[q] = fverts[9 * f + q];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) S[q] = g_fsums[9 * f + q];
+    face_sums_expand(P, S, g);
+  } else {
+#pragma unroll
+    for (int q = 0; q < 9; ++q) g[q] = g_fverts ? g_fverts[9 * f + q] : 0.0;
+  }
   if (g_norm != nullptr) {
     // N = C/|C|, C = A x B, A = P1-P0, B = P2-P1
     double P[9], N[3], C[3], clen;
@@ -290,7 +304,7 @@ __global__ __launch_bounds__(BLOCK) void k_param_faces_bwd_gather_multi(FaceSurf
       const int fc = u.corner_list[q], f = fc / 3, c = fc - 3 * f;
       if (u.update_mask != nullptr && u.update_mask[fc] == 0) continue;
       double g[9];
-      face_grad(u.grad_face_verts, u.grad_norm, u.face_verts, f, g);
+      face_grad(u.grad_face_verts, u.grad_norm, u.face_verts, f, g, u.grad_face_sums);
       acc += g[3 * c] * u.vectors[3 * v] + g[3 * c + 1] * u.vectors[3 * v + 1] +
              g[3 * c + 2] * u.vectors[3 * v + 2];
     }
@@ -487,7 +501,9 @@ int tfrt_param_faces_backward_multi(const tfrt_face_surface_grad* surfaces, int3
     if (u.n_vertices < 0) return TFRT_E_BADARG;
     if (u.n_vertices > 0 &&
         (!u.vectors || !u.grad_parameters || !u.corner_start || !u.corner_list ||
-         (!u.grad_face_verts && !u.grad_norm) || (u.grad_norm && !u.face_verts)))
+         (!u.grad_face_verts && !u.grad_norm && !u.grad_face_sums) ||
+         (u.grad_face_verts && u.grad_face_sums) ||
+         ((u.grad_norm || u.grad_face_sums) && !u.face_verts)))
       return TFRT_E_BADARG;
     b.s[k] = u;
     blocks += cdiv(u.n_vertices * GATHER_LANES, BLOCK);

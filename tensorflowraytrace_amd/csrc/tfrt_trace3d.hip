@@ -3143,37 +3143,62 @@ __device__ __forceinline__ int backward_ray(
 // lanes read neighbouring doubles at a constant stride, nothing crosses lanes, and up to seven
 // faces take one step.  (The strides are the tier's cells padded to 2 mod 4 doubles: the copies
 // of one cell, which the lanes of an eight take together, lie in different LDS banks.)
-constexpr int WSUM_SLOTS = 32, WSUM_CELLS = 592;
-__device__ __forceinline__ constexpr int wsum_stride(int copies) {
-  return WSUM_SLOTS * 9 * 2 / copies + 2;   // 8: 74, 4: 146, 2: 290
+// TERMS: what a hit leaves per face -- the nine face-vertex terms, or the four sums they are
+// linear in (tfrt_scene3d.face_sums: adjoint3d hands back (Cb, numb), a face's sums go to the
+// first four doubles of its row of g_fverts and the parameter gather expands once per face).  The
+// tiers are the same; the four-sum cells are 4 / 9 of the nine-term ones, a face's memory atomics
+// 32 consecutive bytes.  Either way face f's row starts at g_fverts + WSUM_ROW * f.
+constexpr int WSUM_SLOTS = 32, WSUM_ROW = 9;
+template <int TERMS>
+constexpr int wsum_stride(int copies) {
+  return WSUM_SLOTS * TERMS * 2 / copies + 2;   // nine terms: 8: 74, 4: 146, 2: 290; four: 34, 66, 130
 }
-static_assert(8 * wsum_stride(8) <= WSUM_CELLS && 4 * wsum_stride(4) <= WSUM_CELLS &&
-              2 * wsum_stride(2) <= WSUM_CELLS, "wacc holds every tier");
+template <int TERMS>
+constexpr int wsum_cells() {
+  return 8 * wsum_stride<TERMS>(8);             // 592 / 272: the eight-copy tier is the widest
+}
+template <int TERMS>
+struct WsumCheck {
+  static_assert(TERMS == 9 || TERMS == 4, "nine face-vertex terms or the four sums");
+  static_assert(4 * wsum_stride<TERMS>(4) <= wsum_cells<TERMS>() &&
+                    2 * wsum_stride<TERMS>(2) <= wsum_cells<TERMS>(),
+                "wacc holds every tier");
+  static_assert(wsum_stride<TERMS>(8) % 4 == 2 && wsum_stride<TERMS>(4) % 4 == 2 &&
+                    wsum_stride<TERMS>(2) % 4 == 2,
+                "the copies of one cell lie in different LDS banks");
+  static_assert(wsum_cells<TERMS>() % 2 == 0, "cleared two cells at a time");
+  static constexpr bool ok = true;
+};
+constexpr int WSUM_CELLS = wsum_cells<9>();
+static_assert(WSUM_CELLS == 592 && wsum_cells<4>() == 272 && WsumCheck<9>::ok && WsumCheck<4>::ok,
+              "the tiers of wave_face_sums");
 
 // wacc is all zero between two calls of wave_face_sums: the kernel clears it once ...
+template <int TERMS>
 __device__ __forceinline__ void wsum_clear(double* wacc) {
-  for (int k = 2 * (threadIdx.x & 63); k < WSUM_CELLS; k += 128)
+  for (int k = 2 * (threadIdx.x & 63); k < wsum_cells<TERMS>(); k += 128)
     *reinterpret_cast<double2*>(wacc + k) = make_double2(0.0, 0.0);
   wave_fence();
 }
 // ... and the fold leaves zeros where it read.  One lane per (face, term): the copies of its
 // cell summed in registers, then ONE atomic to memory.
-template <int COPIES>
+template <int COPIES, int TERMS>
 __device__ __forceinline__ void wsum_fold(double* wacc, const int32_t* wface, int K, int lane,
                                           double* __restrict__ g_fverts) {
   for (int k = lane; k < K; k += 64) {
     double* w = wacc + k;
     double v = w[0];
 #pragma unroll
-    for (int c = 1; c < COPIES; ++c) v += w[c * wsum_stride(COPIES)];
+    for (int c = 1; c < COPIES; ++c) v += w[c * wsum_stride<TERMS>(COPIES)];
 #pragma unroll
-    for (int c = 0; c < COPIES; ++c) w[c * wsum_stride(COPIES)] = 0.0;
+    for (int c = 0; c < COPIES; ++c) w[c * wsum_stride<TERMS>(COPIES)] = 0.0;
     if (v != 0.0) {
-      const int f = k / 9;
-      unsafeAtomicAdd(g_fverts + 9 * (int64_t)wface[f] + (k - 9 * f), v);
+      const int f = k / TERMS;
+      unsafeAtomicAdd(g_fverts + WSUM_ROW * (int64_t)wface[f] + (k - TERMS * f), v);
     }
   }
 }
+template <int TERMS>
 __device__ __forceinline__ void wave_face_sums(int tri, const double gP[9], double* wacc,
                                                int32_t* wface, double* __restrict__ g_fverts) {
   const int lane = threadIdx.x & 63;
@@ -3192,21 +3217,21 @@ __device__ __forceinline__ void wave_face_sums(int tri, const double gP[9], doub
   const int copies = ns <= 8 ? 8 : (ns <= 16 ? 4 : 2);
   if (tri >= 0) {
     if (slot >= 0) {
-      double* w = &wacc[(lane & (copies - 1)) * wsum_stride(copies) + slot * 9];
+      double* w = &wacc[(lane & (copies - 1)) * wsum_stride<TERMS>(copies) + slot * TERMS];
 #pragma unroll
-      for (int c = 0; c < 9; ++c)
+      for (int c = 0; c < TERMS; ++c)
         if (gP[c] != 0.0) unsafeAtomicAdd(w + c, gP[c]);
     } else {  // (more distinct faces than slots: rays that are not coherent after all)
-      double* gp = g_fverts + 9 * (int64_t)tri;
+      double* gp = g_fverts + WSUM_ROW * (int64_t)tri;
 #pragma unroll
-      for (int c = 0; c < 9; ++c)
+      for (int c = 0; c < TERMS; ++c)
         if (gP[c] != 0.0) unsafeAtomicAdd(gp + c, gP[c]);
     }
   }
   wave_fence();
-  if (copies == 8) wsum_fold<8>(wacc, wface, ns * 9, lane, g_fverts);
-  else if (copies == 4) wsum_fold<4>(wacc, wface, ns * 9, lane, g_fverts);
-  else wsum_fold<2>(wacc, wface, ns * 9, lane, g_fverts);
+  if (copies == 8) wsum_fold<8, TERMS>(wacc, wface, ns * TERMS, lane, g_fverts);
+  else if (copies == 4) wsum_fold<4, TERMS>(wacc, wface, ns * TERMS, lane, g_fverts);
+  else wsum_fold<2, TERMS>(wacc, wface, ns * TERMS, lane, g_fverts);
   wave_fence();  // (the next use of wacc / wface must not overtake these reads and zeros)
 }
 
@@ -3234,7 +3259,7 @@ __global__ __launch_bounds__(64 * BW) void k_backward3d(
     __shared__ __align__(16) double wacc[BW][WSUM_CELLS];  // (layout: wave_face_sums)
     __shared__ int32_t wface[BW][WSUM_SLOTS];
     const int wave = threadIdx.x >> 6;
-    wsum_clear(wacc[wave]);
+    wsum_clear<9>(wacc[wave]);
     double gP[9];
     int tri = -1;
     if (i < n)
@@ -3242,7 +3267,7 @@ __global__ __launch_bounds__(64 * BW) void k_backward3d(
                             pass_counts, sc, L, dead_len, g_child, child_stride, g_fin, cap_fin,
                             g_act, cap_act, g_stp, cap_stp, g_dead, cap_dead, g_out, g_src_out,
                             out_stride, gP);
-    wave_face_sums(tri, gP, wacc[wave], wface[wave], g_fverts);
+    wave_face_sums<9>(tri, gP, wacc[wave], wface[wave], g_fverts);
     return;
   }
   if (i >= n) return;
@@ -3432,7 +3457,9 @@ __global__ __launch_bounds__(BLOCK) void k_fixed_finish(int64_t m9,
 // Reverse of one ray slot of one pass, in registers: `child` holds the gradient w.r.t. the slot's
 // child ray (start, end) when it has one; gs / ge receive the gradient w.r.t. the slot's input
 // ray.  Returns the face whose gradient gP must be accumulated (-1: none).
-template <typename T, bool GN = true>   // GN: the caller may want d error / d (per-face indices)
+// TERMS: 9 = gP receives the nine face-vertex terms; 4 = gP[0..3] the four sums' addends
+// (adjoint3d, face_sums)
+template <typename T, bool GN = true, int TERMS = 9>   // GN: the caller may want d error / d (per-face indices)
 __device__ __forceinline__ int backward_core(
     int i, int tape, int slot, const T* __restrict__ rays_in, int64_t stride_in,
     const int32_t* __restrict__ ray_id_in, const int32_t* __restrict__ rec_tri,
@@ -3521,7 +3548,7 @@ __device__ __forceinline__ int backward_core(
       const bool want_n = GN && has_child && sc.grad_n_in != nullptr && sc.n_table == nullptr;
       const int branch = ((tape & TAPE_INTERNAL) ? 1 : 0) | ((tape & TAPE_REFLECT) ? 2 : 0);
       adjoint3d(s, e, P, t_rec, has_child, n_in, n_out, L, g_s, g_h, g_ce, gs, ge, gP, gn, branch,
-                want_n);
+                want_n, /*face_terms=*/true, /*ratios=*/nullptr, /*face_sums=*/TERMS == 4);
       if (want_n) {  // "value" mode: d error / d (per-face refractive indices)
         if (gn[0] != 0.0) unsafeAtomicAdd(sc.grad_n_in + tri, gn[0]);
         if (gn[1] != 0.0) unsafeAtomicAdd(sc.grad_n_out + tri, gn[1]);
@@ -3543,7 +3570,7 @@ __device__ __forceinline__ int backward_core(
 // = snell_ratios) -- the adjoint picks one where it used to divide n_in and n_out again.
 // FIN / CHILD: false where the caller knows that no lane of the wavefront finishes in this pass /
 // has a child ray in it -- the arm is not compiled in (k_backward_chain_goal_inplace's roles).
-template <bool FIN = true, bool CHILD = true>
+template <bool FIN = true, bool CHILD = true, int TERMS = 9>
 __device__ __forceinline__ int backward_core_loaded(
     int tape, int tri, bool child_pass, const double s[3], const double e[3], const double P[9],
     double t_rec, double n_a, double n_b, bool face_wanted, double L, const double child[6],
@@ -3572,7 +3599,7 @@ __device__ __forceinline__ int backward_core_loaded(
       const int branch = ((tape & TAPE_INTERNAL) ? 1 : 0) | ((tape & TAPE_REFLECT) ? 2 : 0);
       const double ratios[2] = {n_a, n_b};
       adjoint3d(s, e, P, t_rec, has_child, 1.0, 1.0, L, g_s, g_h, g_ce, gs, ge, gP, nullptr,
-                branch, false, face_wanted, ratios);
+                branch, false, face_wanted, ratios, TERMS == 4);
       if (face_wanted) face_out = tri;
     }
   }
@@ -3673,7 +3700,8 @@ struct ChainArgs {
 #endif
 // GN = false: no gradient with respect to the per-face indices is asked for (tfrt_scene3d.grad_n_in
 // null -- the usual case; the adjoint's index terms and the two atomics are not compiled in)
-template <typename T, int BW, bool GOAL, bool GN>
+// TERMS: nine face-vertex terms per face, or the four sums (tfrt_scene3d.face_sums)
+template <typename T, int BW, bool GOAL, bool GN, int TERMS>
 __global__ __launch_bounds__(64 * BW)
 __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_backward_chain(
     ChainArgs<T> a, tfrt_scene3d sc) {
@@ -3688,13 +3716,13 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
     }
     return;
   }
-  __shared__ __align__(16) double wacc[BW][WSUM_CELLS];
+  __shared__ __align__(16) double wacc[BW][wsum_cells<TERMS>()];
   __shared__ int32_t wface[BW][WSUM_SLOTS];
   extern __shared__ int4 chain_lds[];   // [wave][pass][lane]: slot, tape byte, output slot, face
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int P = a.P;
   int4* chain = chain_lds + (size_t)wave * P * 64;
-  wsum_clear(wacc[wave]);
+  wsum_clear<TERMS>(wacc[wave]);
   // forward: the slots of this ray's chain and the pass it ends in; what the walk back needs of
   // every slot's record is read here, three independent loads per pass
   int last = -1;
@@ -3774,7 +3802,7 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
         }
       }
       double gs[3], ge[3];
-      tri = backward_core<T, GN>(j, tape, slot, rin, sin, idin, a.rec_tri + off, a.rec_t + off,
+      tri = backward_core<T, GN, TERMS>(j, tape, slot, rin, sin, idin, a.rec_tri + off, a.rec_t + off,
                                  a.counts + (size_t)p * TFRT_COUNTS_PER_PASS, sc, a.L, a.dead_len,
                                  p < P - 1, child, GOAL ? seed : nullptr, a.g_fin, a.cap_fin, a.g_act,
                              a.cap_act, a.g_stp, a.cap_stp, a.g_dead, a.cap_dead, gs, ge, gP,
@@ -3788,7 +3816,7 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
       n_fin += __popcll(__ballot(fin_here));
       n_entered += __popcll(__ballot(p <= last));
     }
-    wave_face_sums(tri, gP, wacc[wave], wface[wave], a.g_fverts);
+    wave_face_sums<TERMS>(tri, gP, wacc[wave], wface[wave], a.g_fverts);
   }
   if (a.g_src != nullptr && i0 < n0) {
     // (a ray without a chain cannot be: every source ray enters pass 1 when P > 0)
@@ -3891,7 +3919,7 @@ __device__ __forceinline__ U ld_lane(const U* base, uint32_t i) {
 // lane of the wavefront finishes in this pass / no lane has a child ray in it; then the goal's
 // loads, the finished row, the seed and the columns' loop / the child's arm, the index ratios,
 // Snell's reverse and the normal's way back do not exist.  One source for both roles.
-template <typename T, bool FIN, bool CHILD>
+template <typename T, bool FIN, bool CHILD, int TERMS>
 __device__ __forceinline__ int chain_goal_pass(const ChainGoalArgs<T>& a, int p, int wave, int lane,
                                                int tape, int face, bool fin_lane, double child[6],
                                                double& err, double gP[9]) {
@@ -4002,7 +4030,7 @@ __device__ __forceinline__ int chain_goal_pass(const ChainGoalArgs<T>& a, int p,
     }
   }
   double gs[3], ge[3];
-  const int tri = backward_core_loaded<FIN, CHILD>(tape, face, child_pass, s0, e0, Pf, t_rec, n_a,
+  const int tri = backward_core_loaded<FIN, CHILD, TERMS>(tape, face, child_pass, s0, e0, Pf, t_rec, n_a,
                                                    n_b, mask_i != 0, a.L, child, seed, gs, ge, gP);
   for (int k = 0; k < 3; ++k) {
     child[k] = gs[k];
@@ -4011,7 +4039,7 @@ __device__ __forceinline__ int chain_goal_pass(const ChainGoalArgs<T>& a, int p,
   return tri;
 }
 
-template <typename T>
+template <typename T, int TERMS>
 __global__ __launch_bounds__(64)
 __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_backward_chain_goal_inplace(
     ChainGoalArgs<T> a) {
@@ -4035,11 +4063,11 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
     return;
   }
   __builtin_assume(a.feta != nullptr);
-  __shared__ __align__(16) double wacc[WSUM_CELLS];
+  __shared__ __align__(16) double wacc[wsum_cells<TERMS>()];
   __shared__ int32_t wface[WSUM_SLOTS];
   extern __shared__ int2 chain_goal_lds[];   // [pass][lane]: tape byte, face
   int2* chain = chain_goal_lds;
-  wsum_clear(wacc);
+  wsum_clear<TERMS>(wacc);
   const int P = a.P;
   int last = -1;
   if (i0 < n0) {
@@ -4078,12 +4106,12 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
     // runs (chain_goal_pass).  A mixed wavefront runs both, each with its own lanes.
     const bool fin_role = here && fin_m != 0ull && !(p < P - 1 && (tape & 3) == CLS_ACTIVE);
     if (fin_role)
-      tri = chain_goal_pass<T, true, false>(a, p, wave, lane, tape, face, fin_here, child, err, gP);
+      tri = chain_goal_pass<T, true, false, TERMS>(a, p, wave, lane, tape, face, fin_here, child, err, gP);
     if (here && !fin_role)
-      tri = chain_goal_pass<T, false, true>(a, p, wave, lane, tape, face, false, child, err, gP);
+      tri = chain_goal_pass<T, false, true, TERMS>(a, p, wave, lane, tape, face, false, child, err, gP);
     n_fin += __popcll(fin_m);
     n_entered += __popcll(__ballot(here));
-    wave_face_sums(tri, gP, wacc, wface, a.g_fverts);
+    wave_face_sums<TERMS>(tri, gP, wacc, wface, a.g_fverts);
   }
   if (a.g_src != nullptr && i0 < n0) {
     for (int k = 0; k < 6; ++k) a.g_src[k * a.N + i0] = child[k];
@@ -4873,8 +4901,6 @@ static int trace3d_backward_t(const SweepCall3& c) {
   // (coherent rays: the wavefront's rays hit few faces; k_backward3d sums them itself)
   const bool wave_sums = !ordered && sc->coherent_rays != 0 && M > 0 && c.g_fverts != nullptr;
   const bool stash = ordered || (!wave_sums && M > 0 && N >= 16384 && windows <= 32);
-  if (ordered)  // (fix_acc, fix_flag and fix_max are adjacent: one clear)
-    (void)hipMemsetAsync(fix_acc, 0, lay.total - lay.fix_acc, st);
   // ray slots per accumulate block, measured at 1M rays x 11 windows (us for the three passes,
   // target pass first): 2048 -> 37/50/54, 4096 -> 21/33/38, 8192 -> 15/37/34, 16384 -> 12/49/36.
   // Every block zeroes and flushes its window, so big chunks win while the blocks still fill
@@ -4903,21 +4929,34 @@ static int trace3d_backward_t(const SweepCall3& c) {
   if (chain && tape_mode == 3 &&
       (c.g_act || c.g_stp || c.g_dead || c.goal != nullptr || c.cap_fin < N))
     return TFRT_E_BADARG;
+  // tfrt_scene3d.face_sums: the rows of g_fverts receive the faces' four sums.  Only the two
+  // chain kernels write that form; every other route (the stash and k_face_accumulate, the
+  // ordered sums, k_backward3d's own sums and atomics) is refused before anything is launched --
+  // one buffer holds one form per step.
+  const bool four_sums = sc->face_sums != 0;
+  if (four_sums && !chain) return TFRT_E_UNSUPPORTED;
+  if (ordered)  // (fix_acc, fix_flag and fix_max are adjacent: one clear)
+    (void)hipMemsetAsync(fix_acc, 0, lay.total - lay.fix_acc, st);
 
   if (chain) {
     const ChainArgs<T> a = chain_args_of<T>(c, tape, tape_mode);
     ProfScope prof_bwd(TFRT_PROF_BACKWARD, st);
     if (N > 0 && goal_inplace) {
-      hipLaunchKernelGGL((k_backward_chain_goal_inplace<T>), dim3(cdiv(N, 64)), dim3(64),
+      using Kernel = void (*)(ChainGoalArgs<T>);
+      const Kernel kernel[2] = {k_backward_chain_goal_inplace<T, 9>,   // [four sums]
+                                k_backward_chain_goal_inplace<T, 4>};
+      hipLaunchKernelGGL(kernel[four_sums], dim3(cdiv(N, 64)), dim3(64),
                          (size_t)P * 64 * sizeof(int2), st, chain_goal_args_of(a, sc));
     } else if (N > 0) {
       using Kernel = void (*)(ChainArgs<T>, tfrt_scene3d);
-      const Kernel kernel[2][2] = {   // [GOAL][GN]
-          {k_backward_chain<T, 1, false, false>, k_backward_chain<T, 1, false, true>},
-          {k_backward_chain<T, 1, true, false>, k_backward_chain<T, 1, true, true>}};
+      const Kernel kernel[2][2][2] = {   // [GOAL][GN][four sums]
+          {{k_backward_chain<T, 1, false, false, 9>, k_backward_chain<T, 1, false, false, 4>},
+           {k_backward_chain<T, 1, false, true, 9>, k_backward_chain<T, 1, false, true, 4>}},
+          {{k_backward_chain<T, 1, true, false, 9>, k_backward_chain<T, 1, true, false, 4>},
+           {k_backward_chain<T, 1, true, true, 9>, k_backward_chain<T, 1, true, true, 4>}}};
       const size_t chain_lds = a.chain_in_lds ? (size_t)P * 64 * sizeof(int4) : 0;
-      hipLaunchKernelGGL(kernel[c.goal != nullptr][sc->grad_n_in != nullptr], dim3(cdiv(N, 64)),
-                         dim3(64), chain_lds, st, a, *sc);
+      hipLaunchKernelGGL(kernel[c.goal != nullptr][sc->grad_n_in != nullptr][four_sums],
+                         dim3(cdiv(N, 64)), dim3(64), chain_lds, st, a, *sc);
     }
     return hipGetLastError() == hipSuccess ? 0 : TFRT_E_LAUNCH;
   }

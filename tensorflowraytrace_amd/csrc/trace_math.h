@@ -276,6 +276,33 @@ TFRT_HD void adj_cross3(const double a[3], const double b[3], double o[3]) {
 }
 
 // ------------------------------------------------------------------------------------------
+// The reverse of C = E1 x E2 and of num = (P0 - s).C onto the face's vertices: the nine
+// face-vertex gradients from the gradient w.r.t. C (Cb) and w.r.t. num (numb).  E1, E2 and C
+// belong to the face alone, so the nine are linear in the four (Cb, numb).
+TFRT_HD void face_terms_of(const double E1[3], const double E2[3], const double C[3],
+                           const double Cb[3], double numb, double g[9]) {
+  double E1b[3], E2b[3];
+  adj_cross3(E2, Cb, E1b);
+  adj_cross3(Cb, E1, E2b);
+  for (int i = 0; i < 3; ++i) {
+    g[3 + i] = E1b[i];
+    g[6 + i] = E2b[i];
+    g[i] = numb * C[i] - (E1b[i] + E2b[i]);
+  }
+}
+
+// A face's vertices P and its four sums S = (sum Cb[0..2], sum numb) over the rays that hit it
+// (adjoint3d, face_sums = true) -> the nine face-vertex gradients, by the formulas of the
+// nine-term form: what that form sums per ray, taken once per face.
+TFRT_HD void face_sums_expand(const double P[9], const double S[4], double g[9]) {
+  const double E1[3] = {P[3] - P[0], P[4] - P[1], P[5] - P[2]};
+  const double E2[3] = {P[6] - P[0], P[7] - P[1], P[8] - P[2]};
+  double C[3];
+  adj_cross3(E1, E2, C);
+  face_terms_of(E1, E2, C, S, S[3], g);
+}
+
+// ------------------------------------------------------------------------------------------
 // Reverse-mode of one ray through one pass.
 //
 // Forward (per ray):   d = e - s ; C = (P1-P0) x (P2-P0) ; t = ((P0-s).C)/(d.C) ; h = s + t d
@@ -298,12 +325,16 @@ TFRT_HD void adj_cross3(const double a[3], const double b[3], double o[3]) {
 //          the trace's set-up launch): the index ratio is then picked, not divided -- the same
 //          operands and safe-value rules, hence the same bits.  Needs the forward's branches
 //          (branch >= 0) and no gn: n_in and n_out are not read then.
+// face_sums = true (with face_terms): gP[0..2] receives the gradient w.r.t. C, gP[3] the one
+//          w.r.t. the hit parameter's numerator, gP[4..8] are left untouched -- the four numbers
+//          the nine terms are linear in; nothing of the two cross products or their combination
+//          is formed (face_sums_expand does it once per face).  gs and ge: the same bits.
 TFRT_HD void adjoint3d(const double s[3], const double e[3], const double P[9], double ray_u,
                        bool has_child, double n_in, double n_out, double L,
                        const double g_s[3], const double g_h[3], const double g_ce[3],
                        double gs[3], double ge[3], double gP[9], double* gn = nullptr,
                        int branch = -1, bool gn_wanted = true, bool face_terms = true,
-                       const double* ratios = nullptr) {
+                       const double* ratios = nullptr, bool face_sums = false) {
   // branch: -1 = re-derive the forward's branches here; else bit 0 = the ray met the face from
   // the inside (n.u > 0), bit 1 = it was reflected (mirror or total internal reflection), as the
   // forward pass decided them
@@ -431,14 +462,13 @@ TFRT_HD void adjoint3d(const double s[3], const double e[3], const double P[9], 
   if (face_terms) {
     double Cb[3];
     for (int i = 0; i < 3; ++i) Cb[i] = Cn[i] + (numb * (P[i] - s[i]) + denb * d[i]);
-    // C = E1 x E2
-    double E1b[3], E2b[3];
-    adj_cross3(E2, Cb, E1b);
-    adj_cross3(Cb, E1, E2b);
-    for (int i = 0; i < 3; ++i) {
-      gP[3 + i] = E1b[i];
-      gP[6 + i] = E2b[i];
-      gP[i] = numb * C[i] - (E1b[i] + E2b[i]);
+    if (face_sums) {
+      // the nine terms are linear in (Cb, numb) with coefficients of the face alone: the caller
+      // sums these four per face and somebody expands once per face (face_sums_expand)
+      for (int i = 0; i < 3; ++i) gP[i] = Cb[i];
+      gP[3] = numb;
+    } else {
+      face_terms_of(E1, E2, C, Cb, numb, gP);
     }
   }
   for (int i = 0; i < 3; ++i) {

@@ -50,6 +50,7 @@ processes the collective splits it in two graphs (RCCL is called eagerly between
 ``GoalError`` is also an ordinary error function (``__call__(engine)``): the generic path gives
 the same numbers, which is what the parity tests compare.
 """
+import contextlib
 import ctypes
 import gc
 
@@ -947,6 +948,7 @@ class FusedStep:
     fold_backward = True
     folded_backward = False           # what the last enqueued step did
     in_place = False                  # ... its trace ran all passes in one launch, rays in place
+    face_sums = False                 # ... its sweep left four sums per face (tfrt_scene3d.face_sums)
     # Several ranks: capture the RCCL all-reduce inside the step's graph (one graph per step) instead
     # of calling it eagerly between two graphs.  "auto": only with a one-rank group -- the form has
     # been replayed with a one-rank RCCL group (tests/test_gpu_zz_rccl.py), never yet with several
@@ -1190,11 +1192,14 @@ class FusedStep:
         self.folded_backward, self.in_place = folded, inplace
         st.perm = perm
         st.inplace = (block, self._lengths()[1]) if inplace else None
+        # (the folded sweep is one of the two chain kernels, which write the four-sum form)
+        four = self.face_sums = self._four_sums(fv, sc, folded)
         clear = {"clear_buffer": st.g_fv.data_ptr(), "clear_count": st.g_fv.numel()} if folded \
             else {}
         sched = self._wave_schedule(st) if inplace else None
-        # (in_place, wave_schedule: the reverse sweep is given the same values as the forward)
-        with _override(sc, in_place=1 if inplace else 0,
+        # (in_place, wave_schedule, face_sums: the reverse sweep is given the same values as the
+        # forward)
+        with _override(sc, in_place=1 if inplace else 0, face_sums=1 if four else 0,
                        wave_schedule=None if sched is None else sched.data_ptr()):
             with _override(sc, **clear):
                 self._trace_forward(st, sc, st.no_outs if inplace else st.outs)
@@ -1204,7 +1209,18 @@ class FusedStep:
             self._make_wave_schedule(st, perm)
         if not need_back:
             return None, st
-        return self._parameter_gradients(*self._outs3d(fv, st, index), tap_log), st
+        with ops.FaceSums() if four else contextlib.nullcontext():
+            return self._parameter_gradients(*self._outs3d(fv, st, index), tap_log), st
+
+    @staticmethod
+    def _four_sums(fv, sc, chain_sweep):
+        """Whether this step's reverse sweep leaves the faces' four sums (tfrt_scene3d.face_sums)
+        instead of their nine vertex gradients: the sweep is one of the two chain kernels, not
+        ``deterministic``, and the merged faces come straight from the parametric update whose
+        gather expands the sums -- a vertex-parametrised boundary, a custom ``_update`` or
+        anything else between the update and the faces reads a true (M, 9) gradient."""
+        return bool(chain_sweep and not sc.deterministic and sc.coherent_rays
+                    and fv.requires_grad and ops.faces_from_param_update(fv))
 
     def _wave_schedule(self, st):
         """The wavefront schedule this in-place step runs with (engine.wave_schedule), or None:
@@ -1378,12 +1394,14 @@ class FusedStep:
         self.folded_backward, self.in_place = False, True
         self._goal_pending = None
         st.perm, st.inplace = perm, (block, self._lengths()[1])
+        # (an in-place tape is swept by k_backward_chain, which writes the four-sum form)
+        four = self.face_sums = self._four_sums(fv, sc, need_back)
         clear = {"clear_buffer": st.g_fv.data_ptr(), "clear_count": st.g_fv.numel()} if need_back \
             else {}
         grads = None
         # (in_place == 2: the finished rows at the rays' own columns; the reverse sweep is given
-        # the same value as the forward)
-        with _override(sc, in_place=2, **clear):
+        # the same values as the forward)
+        with _override(sc, in_place=2, face_sums=1 if four else 0, **clear):
             self._trace_forward(st, sc, st.row_outs)
             if isinstance(self.opt.error_function, (DensityError, SpotError)):
                 if isinstance(self.opt.error_function, DensityError):
@@ -1397,7 +1415,8 @@ class FusedStep:
             if g64 is not None:
                 with self._index_grads3d(sc, st, True):
                     self._trace3d_backward(st, sc, g64, g64.shape[1])
-                grads = self._parameter_gradients(*self._outs3d(fv, st, index), tap_log)
+                with ops.FaceSums() if four else contextlib.nullcontext():
+                    grads = self._parameter_gradients(*self._outs3d(fv, st, index), tap_log)
         return grads, st
 
     def _density_seeds3d(self, st, src, perm):

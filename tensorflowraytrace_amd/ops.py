@@ -267,7 +267,12 @@ class _ParamFacesMulti(torch.autograd.Function):
             if gp is None:
                 gp = torch.empty(shape, dtype=torch.float64, device=fv.device)
             d = _lib.FaceSurfaceGrad()
-            d.grad_face_verts = g_fv.data_ptr() + at * 72 if g_fv is not None else None
+            if g_fv is not None and FaceSums._active is not None:
+                # (the upstream keeps its (M, 9) shape for autograd; the first four doubles of a
+                # row are the face's four sums, expanded inside the gather)
+                d.grad_face_sums = g_fv.data_ptr() + at * 72
+            else:
+                d.grad_face_verts = g_fv.data_ptr() + at * 72 if g_fv is not None else None
             d.grad_norm = _p(g_norm)
             d.face_verts = fv.data_ptr() + at * 72
             d.update_mask, d.vectors = _p(mask), _p(vectors)
@@ -320,6 +325,32 @@ class GradSink:
     def holds(self, t):
         """True if ``t`` is one of the slices handed out (same memory, same size)."""
         return any(v.data_ptr() == t.data_ptr() and v.numel() == t.numel() for v in self.taken)
+
+
+class FaceSums:
+    """While active (``with FaceSums():``) the face gradient handed to the merged face update's
+    reverse (_ParamFacesMulti) is in the four-sum form of tfrt_scene3d.face_sums: a reverse sweep
+    wrote, per face, the four sums its nine vertex gradients are linear in into the first four
+    doubles of the face's row of the (M, 9) block, and the gather expands them once per face
+    (tfrt_face_surface_grad.grad_face_sums).  Opened by the fused step around its parameter
+    gradients, and only when the merged faces come straight from that update."""
+
+    _active = None
+
+    def __enter__(self):
+        self._prev, FaceSums._active = FaceSums._active, self
+        return self
+
+    def __exit__(self, *exc):
+        FaceSums._active = self._prev
+        return False
+
+
+def faces_from_param_update(fv):
+    """Whether ``fv`` is the merged face block as _ParamFacesMulti returned it: its gradient then
+    reaches that update's reverse untouched by any other node."""
+    fn = getattr(fv, "grad_fn", None)
+    return fn is not None and getattr(fn, "_forward_cls", None) is _ParamFacesMulti
 
 
 def current_faces_batch():

@@ -26,6 +26,13 @@ its start direction to the emitter's normal as its radiant power -- the ``weight
 ``DensityError``, a callable on the source's fields, evaluated again whenever the rays are re-drawn.
 
     python examples/illumination.py --density-error [--bins 64] [--generic] [--lambertian-weights]
+
+``--transport-error`` optimises the same scene and the same goal by sliced optimal transport
+instead: a ``TransportError`` over (y_end, z_end) with ``--directions`` projection directions pulls
+every ray towards the goal's quantile at its own rank, so the step has a signal even where the
+landing pattern and the goal do not overlap.  ``--generic`` as above.
+
+    python examples/illumination.py --transport-error [--directions 8] [--bins 64] [--generic]
 """
 import argparse
 import os
@@ -78,7 +85,8 @@ def lambertian(src):
 
 def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, magnification=1.0,
           object_size=0.2, lens_aperature=1.0, rowwise=True, density_error=False, bins=64,
-          lambertian_weights=False, **engine_kw):
+          lambertian_weights=False, transport_error=False, directions=8, **engine_kw):
+    density_error = density_error or transport_error      # (the same scene: no ranks ride along)
     limits = ((-object_size, object_size, DENSITY_CELLS), (-object_size, object_size, DENSITY_CELLS))
     start_density = distributions.ArbitraryDistribution(two_bumps(object_size), limits)
     goal_density = distributions.ArbitraryDistribution(lambda gx, gy: np.ones_like(gx), limits)
@@ -123,7 +131,15 @@ def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, magnificat
     trace_engine.validate_system()
 
     m = magnification
-    if density_error:
+    if transport_error:
+        # the goal and the domain of --density-error; rays beyond the margin need no penalty,
+        # their rank pulls them in
+        size = abs(m) * object_size
+        half = 1.25 * size
+        error_function = optimizer.TransportError(
+            ("y_end", "z_end"), even_square(size, half, bins), ((-half, half), (-half, half)),
+            directions=directions)
+    elif density_error:
         # the even square of half-width m * object_size inside a domain with a margin of a quarter;
         # a ray beyond the margin is pulled back by the penalty (weighted per ray: the histogram
         # part of the error is of order 1 whatever the ray count)
@@ -141,17 +157,27 @@ def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, magnificat
 
 
 def run(ray_count=20000, steps=30, lens_res_scale=0.12, host=False, verbose=True,
-        density_error=False, bins=64, generic=False, splat_variant=0, lambertian_weights=False):
-    if lambertian_weights and not density_error:
+        density_error=False, bins=64, generic=False, splat_variant=0, lambertian_weights=False,
+        transport_error=False, directions=8):
+    if lambertian_weights and (transport_error or not density_error):
         raise ValueError("--lambertian-weights weighs a DensityError: it needs --density-error")
+    if transport_error and density_error:
+        raise ValueError("--transport-error and --density-error are two objectives: choose one")
     distributions.set_device_random(not host)
     try:
         s = build(ray_count, lens_res_scale, density_error=density_error, bins=bins,
-                  lambertian_weights=lambertian_weights)
+                  lambertian_weights=lambertian_weights, transport_error=transport_error,
+                  directions=directions)
         if density_error:
             s["error_function"].splat_variant = splat_variant
         # (a DensityError is one term of order 1, not a sum over the rays: its own step size)
         lr = DENSITY_LEARNING_RATE if density_error else 2e-5 * (20000 / ray_count)
+        if transport_error:
+            # a sum over the rays like the GoalError's, of K terms per ray in units of the domain's
+            # width w: a ray's gradient is K / w**2 times that of a squared distance
+            erf = s["error_function"]
+            width = erf.domain[0][1] - erf.domain[0][0]
+            lr *= width ** 2 / erf.n_directions
         opt = optimizer.SGD_Optimizer(s["engine"], s["lens"].parameters, s["error_function"], 3,
                                       learning_rate=lr, grad_clip=1.0,
                                       fused=False if generic else "auto")
@@ -164,7 +190,8 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, host=False, verbose=True
             torch.cuda.synchronize()
             times.append(time.perf_counter() - t0)
             if verbose and step % 5 == 0:
-                name = "density error" if density_error else "mean squared error"
+                name = "transport error" if transport_error else \
+                    "density error" if density_error else "mean squared error"
                 print(f"step {step:4d}: {name} {errors[-1]:.6g}  ({1e3 * times[-1]:.2f} ms)")
         fused = opt._fused_step
         s.update(errors=errors, times=times, device_source=s["source"]._device_program() is not None,
@@ -184,6 +211,10 @@ if __name__ == "__main__":
     ap.add_argument("--density-error", action="store_true",
                     help="optimise against the target density directly (DensityError), without ranks")
     ap.add_argument("--bins", type=int, default=64, help="bins per axis of the DensityError's grid")
+    ap.add_argument("--transport-error", action="store_true",
+                    help="optimise against the target density by sliced optimal transport (TransportError)")
+    ap.add_argument("--directions", type=int, default=8,
+                    help="projection directions of the TransportError")
     ap.add_argument("--generic", action="store_true", help="the generic path (fused=False)")
     ap.add_argument("--splat-variant", type=int, default=0, choices=(0, 1, 2),
                     help="tfrt_density_error's splat: 0 by the bin count, 1 LDS histogram, 2 global atomics")
@@ -192,10 +223,12 @@ if __name__ == "__main__":
     a = ap.parse_args()
     out = run(a.rays, a.steps, a.edge, host=a.host, density_error=a.density_error, bins=a.bins,
               generic=a.generic, splat_variant=a.splat_variant,
-              lambertian_weights=a.lambertian_weights)
+              lambertian_weights=a.lambertian_weights, transport_error=a.transport_error,
+              directions=a.directions)
     tail = sorted(out["times"][len(out["times"]) // 2:])
     print(f"source on the device: {out['device_source']}; steps replayed from the graph: "
           f"{out['graph_replays']} of {a.steps}; median step of the second half: "
           f"{1e3 * tail[len(tail) // 2]:.3f} ms")
-    name = "density error" if a.density_error else "mean squared illumination error"
+    name = "transport error" if a.transport_error else \
+        "density error" if a.density_error else "mean squared illumination error"
     print(f"{name}: first {out['errors'][0]:.6g} -> last {out['errors'][-1]:.6g}")

@@ -811,6 +811,59 @@ int tfrt_spot_error_weighted(const void* rows, int64_t stride, int64_t n, int32_
                              int64_t grad_stride, double* error_out, int64_t* acc, int32_t variant,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* TransportError: sliced optimal transport (Wasserstein-2) of the columns to a target density.
+ * Along each of K directions the columns' projections are sorted, the column of mid-rank r among
+ * the n_valid that count belongs at the goal's quantile r / n_valid, and the error is the sum of
+ * the squared distances to those targets.  The goal enters as one quantile table per direction,
+ * built on the host.  No transport map, no overlap of pattern and goal needed; columns that do
+ * not count simply take no part.
+ *
+ * For column i and direction k (c_k, s_k = cos, sin of its angle), coordinates converted to f64,
+ * every operation rounded on its own:
+ *   - the column counts if mask[i] >= 0 (mask given) and both coordinates are finite;
+ *   - xi = (x - x0) * ix, eta = (y - y0) * iy;  p = c * xi + s * eta (two products, one sum; one
+ *     field: p = xi);
+ *   - key: a = min(0, c) + min(0, s), b = max(0, c) + max(0, s), lo = a - (b - a),
+ *     scale = 2^26 / (3 * (b - a)), q = clamp(floor((p - lo) * scale), 0, 2^26 - 2) (a NaN: 0);
+ *     a column that does not count has q = 2^26 - 1;
+ *   - rank among the n_valid columns that count: first = keys smaller than q, count = keys equal
+ *     to q, rank2 = 2 * first + count (-1 for a column that does not count),
+ *     u = (first + count * 0.5) / n_valid: ties share the mid-rank, so nothing depends on the
+ *     order of the columns;
+ *   - target: z = u * Q, m = min(floor(z), Q - 1), f = z - m, t = T_k[m] + f * (T_k[m+1] - T_k[m]);
+ *     d = p - t, the term is d * d;
+ *   - gradient, summed over k = 0 .. K-1 in that order from 0: gx += ((2 * d) * c) * ix,
+ *     gy += ((2 * d) * s) * iy (the targets are constants); zeros for a column that does not count;
+ *   - err = {sum of all terms, K * n_valid, sum / terms (NaN without terms)}: per column the terms
+ *     are added over k, per lane over its columns, then a fixed-shape workgroup sum and the
+ *     workgroups' partial sums in index order -- two runs give the same bits.
+ *
+ *   rows, stride, n   the columns: element (r, i) at rows[r * stride + i]; 0 <= n <= 2^30
+ *   state_dtype       TFRT_F32 / TFRT_F64 / TFRT_F16
+ *   dimension         2 or 3: rows is a (2 * dimension)-row geometry block
+ *   mask              n int32 or NULL
+ *   row_x, row_y      rows of the block, distinct; row_y = -1: one field, and n_directions must be 1
+ *                     (its direction is (1, 0) whatever angles_cs holds)
+ *   x0, ix, y0, iy    the domain's lower ends and 1 / width, finite, ix, iy > 0
+ *   angles_cs         (K, 2) f64 on the device: c_k, s_k
+ *   tables            (K, Q + 1) f64 on the device, each row non-decreasing
+ *   n_knots           Q, 2 .. 65,536;  n_directions: K, 1 .. 64
+ *   grad, grad_stride rows row_x (and row_y) are written for EVERY column, f64
+ *   err               3 f64
+ *   rank2             (K, n) int32, contiguous
+ *   workspace         tfrt_transport_error_workspace_bytes(n, n_directions) bytes (0: bad arguments)
+ * 11 K + 2 launches (per direction: keys, the eight of the radix sort, sorted keys, ranks; then
+ * the seed and the error), nothing cleared, no atomics, no host read, no allocation: capturable.
+ * Bad arguments are refused with TFRT_E_BADARG / TFRT_E_WORKSPACE before any launch.
+ */
+size_t tfrt_transport_error_workspace_bytes(int64_t n, int32_t n_directions);
+int tfrt_transport_error(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                         int32_t dimension, const int32_t* mask, int32_t row_x, int32_t row_y,
+                         double x0, double ix, double y0, double iy, const double* angles_cs,
+                         const double* tables, int32_t n_knots, int32_t n_directions,
+                         double* grad, int64_t grad_stride, double* err, int32_t* rank2,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* tfrt_goal_error3d_deferred and tfrt_trace3d_backward in ONE launch, for a trace over coherent
  * rays (tfrt_scene3d.coherent_rays, not deterministic, max_passes <= 8; TFRT_E_UNSUPPORTED
  * otherwise -- call the two entry points instead): the lane that walks a finished ray's chain of

@@ -221,6 +221,11 @@ SIGNATURES = {
         c_vp, c_vp, c_i32, c_i64, c_vp, c_i32,                                # group, weight, wbits
         c_f64, c_f64, c_f64, c_f64, c_f64, c_f64, c_i32, c_f64,
         c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]),
+    "tfrt_transport_error_workspace_bytes": (c_sz, [c_i64, c_i32]),
+    "tfrt_transport_error": (c_i32, [
+        c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_i32, c_i32,                 # columns, mask, rows
+        c_f64, c_f64, c_f64, c_f64, c_vp, c_vp, c_i32, c_i32,                 # domain, cs, tables, Q, K
+        c_vp, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "tfrt_trace3d_backward_goal_workspace_bytes": (c_sz, [c_i64]),
     "tfrt_trace3d_backward_goal": (c_i32, [
         c_vp, c_i64, c_i64, c_vp, c_f64, c_f64, c_i32, c_i32,          # rays, scene, lengths, P, dtype

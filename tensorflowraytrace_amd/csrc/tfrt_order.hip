@@ -20,6 +20,7 @@
 // calls can be captured into the graph of an optimiser step (a source re-drawn every step is
 // ordered every step).
 #include "tfrt_common.h"
+#include "order_sort.h"
 #include "source_programs.h"
 
 namespace tfrt {
@@ -1232,6 +1233,12 @@ static int sort_keys(const OrderLayout& L, char* ws, int n, unsigned* keys, int3
   }
   hipLaunchKernelGGL((k_sort_hist_keys<8>), dim3(L.nblk), dim3(BLOCK), hl, st, keys, n, L.bits, hist);
   return sort_passes<8>(L, ws, n, perm, keys, st);
+}
+
+// (order_sort.h: the sort for the other files of the library)
+size_t sort_keys26_workspace_bytes(int64_t n) { return order_layout(n, 13).total; }
+int sort_keys26(void* ws, int n, unsigned* keys, int32_t* perm, hipStream_t st) {
+  return sort_keys(order_layout(n, 13), static_cast<char*>(ws), n, keys, perm, st);
 }
 
 template <typename R>

@@ -37,7 +37,8 @@ finished rows at the rays' own columns.  A ``DensityError`` -- the finished rays
 must land with a given density -- takes ``_rowwise3d`` too, with ``tfrt_density_error`` (four
 launches: clear, splat, bins, seed) in the place of ``fn`` and its autograd; a ``SpotError`` -- rays
 of one group must meet in one point -- likewise with ``tfrt_spot_error`` (clear, accumulate, seed,
-finish).
+finish); a ``TransportError`` -- the same target density by sliced optimal transport -- with
+``tfrt_transport_error`` (per direction keys, radix sort, sorted keys, ranks; then seed and finish).
 
 The four bodies share one skeleton: ``_enqueue_gradient`` does what comes before the trace, the
 body its launches over a ``_StepState``, ``_publish_lazily`` and ``_enqueue_apply`` what comes after.
@@ -282,6 +283,55 @@ def _weights_key(erf):
             None if w is None else (w.data_ptr(), tuple(w.shape)))
 
 
+def _fields_and_domain(what, fields, domain):
+    """(fields, domain) of a DensityError or TransportError as they are kept: one or two distinct
+    field names, one finite (lo, hi) per field."""
+    names = (fields,) if isinstance(fields, str) else tuple(fields)
+    if len(names) not in (1, 2) or any(f not in _FIELDS3 for f in names) \
+            or len(set(names)) != len(names):
+        raise ValueError(f"{what}: one or two distinct fields out of {_FIELDS3}, got {fields!r}")
+    try:
+        domain = tuple((float(d[0]), float(d[1])) for d in domain)
+    except (IndexError, TypeError) as e:
+        raise ValueError(f"{what}: domain must be ((x0, x1), (y0, y1)) or ((x0, x1),)") from e
+    if len(domain) != len(names) \
+            or any(not (np.isfinite(a) and np.isfinite(b) and b > a) for a, b in domain):
+        raise ValueError(f"{what}: domain needs one finite (lo, hi), lo < hi, per field; got {domain!r}")
+    return names, domain
+
+
+def _goal_bins(what, goal, domain, bins, dev):
+    """(g, ||g||) of a goal given as an array -- (ny, nx), or (nx,) for one field -- or as a
+    callable evaluated at the centres of ``bins`` bins: float64 on ``dev``, finite, non-negative,
+    not all zero."""
+    from . import config
+    k = len(domain)
+    if callable(goal):
+        if bins is None:
+            raise ValueError(f"{what}: a callable goal needs bins=nx or bins=(nx, ny)")
+        counts = (int(bins),) * k if np.ndim(bins) == 0 else tuple(int(b) for b in bins)
+        if len(counts) != k or any(c < 1 for c in counts):
+            raise ValueError(f"{what}: bins must give one count >= 1 per field, got {bins!r}")
+        centres = []
+        for (lo, hi), c in zip(domain, counts):
+            edges = torch.linspace(lo, hi, c + 1, dtype=torch.float64, device=dev)
+            centres.append((edges[:-1] + edges[1:]) / 2.0)
+        if k == 2:
+            goal = goal(*torch.meshgrid(centres[0], centres[1], indexing="xy"))
+        else:
+            goal = goal(centres[0])
+    g = config.as_f64(goal, dev).detach()
+    if g.dim() != k or g.numel() < 1 or g.numel() > ops.DENSITY_MAX_BINS:
+        raise ValueError(f"{what}: goal must have {k} dimension(s) and between 1 and "
+                         f"{ops.DENSITY_MAX_BINS} bins, got shape {tuple(g.shape)}")
+    if not bool(torch.isfinite(g).all()) or bool((g < 0).any()):
+        raise ValueError(f"{what}: goal must be finite and non-negative")
+    norm = float(torch.linalg.norm(g))
+    if norm == 0.0:
+        raise ValueError(f"{what}: goal is zero everywhere")
+    return g, norm
+
+
 class DensityError:
     """The finished rays, taken together, must land with the density ``goal`` on the target: a
     soft (bilinear) histogram of the rays against the goal, both L2-normalised, summed squared
@@ -368,47 +418,15 @@ class DensityError:
 
     def __init__(self, fields, goal, domain, oob_weight=0.0, bins=None, weights=None):
         from . import config
-        self.fields = (fields,) if isinstance(fields, str) else tuple(fields)
-        if len(self.fields) not in (1, 2) or any(f not in _FIELDS3 for f in self.fields) \
-                or len(set(self.fields)) != len(self.fields):
-            raise ValueError(f"DensityError: one or two distinct fields out of {_FIELDS3}, got {fields!r}")
+        self.fields, self.domain = _fields_and_domain("DensityError", fields, domain)
         self.rows = [_FIELDS3.index(f) for f in self.fields]
         self.has_direction = any(f.endswith("_dir") for f in self.fields)
         k = len(self.fields)
-        try:
-            domain = tuple((float(d[0]), float(d[1])) for d in domain)
-        except (IndexError, TypeError) as e:
-            raise ValueError("DensityError: domain must be ((x0, x1), (y0, y1)) or ((x0, x1),)") from e
-        if len(domain) != k or any(not (np.isfinite(a) and np.isfinite(b) and b > a) for a, b in domain):
-            raise ValueError(f"DensityError: domain needs one finite (lo, hi), lo < hi, per field; got {domain!r}")
-        self.domain = domain
         self.oob_weight = float(oob_weight)
         if not (self.oob_weight >= 0.0 and np.isfinite(self.oob_weight)):
             raise ValueError("DensityError: oob_weight must be finite and >= 0")
         dev = config.get_device()
-        if callable(goal):
-            if bins is None:
-                raise ValueError("DensityError: a callable goal needs bins=nx or bins=(nx, ny)")
-            counts = (int(bins),) * k if np.ndim(bins) == 0 else tuple(int(b) for b in bins)
-            if len(counts) != k or any(c < 1 for c in counts):
-                raise ValueError(f"DensityError: bins must give one count >= 1 per field, got {bins!r}")
-            centres = []
-            for (lo, hi), c in zip(domain, counts):
-                edges = torch.linspace(lo, hi, c + 1, dtype=torch.float64, device=dev)
-                centres.append((edges[:-1] + edges[1:]) / 2.0)
-            if k == 2:
-                goal = goal(*torch.meshgrid(centres[0], centres[1], indexing="xy"))
-            else:
-                goal = goal(centres[0])
-        g = config.as_f64(goal, dev).detach()
-        if g.dim() != k or g.numel() < 1 or g.numel() > ops.DENSITY_MAX_BINS:
-            raise ValueError(f"DensityError: goal must have {k} dimension(s) and between 1 and "
-                             f"{ops.DENSITY_MAX_BINS} bins, got shape {tuple(g.shape)}")
-        if not bool(torch.isfinite(g).all()) or bool((g < 0).any()):
-            raise ValueError("DensityError: goal must be finite and non-negative")
-        norm = float(torch.linalg.norm(g))
-        if norm == 0.0:
-            raise ValueError("DensityError: goal is zero everywhere")
+        g, norm = _goal_bins("DensityError", goal, self.domain, bins, dev)
         self.goal = (g / norm).contiguous()
         nx = self.goal.shape[-1]
         self.grid = ops.density_grid(domain, nx, self.goal.shape[0] if k == 2 else None)
@@ -500,6 +518,215 @@ class _DensityTerms(torch.autograd.Function):
     def backward(ctx, upstream):
         grad, = ctx.saved_tensors
         return (upstream * grad).to(ctx.dtype), None, None, None, None, None
+
+
+class TransportError:
+    """The finished rays, taken together, must land with the density ``goal`` on the target --
+    measured by sliced optimal transport (sliced Wasserstein-2) from the rays that actually arrive:
+    along each of K directions the landing points are sorted, the ray of rank r belongs at the
+    goal's quantile (r + 1/2) / n, and the error is the squared distance to that target.  In one
+    dimension this IS the optimal transport, and its gradient is exact almost everywhere because
+    the assignment is locally constant; in two it is averaged over the directions.  Unlike
+    ``DensityError``, whose gradient comes from a ray's four neighbouring bins, the pull is global:
+    a beam that starts beside the target, a lens that over-focuses into one spot, a goal with
+    empty stretches all have a signal.  It needs no transport map (``GoalError`` with ranks does);
+    lost rays simply take no part.
+
+    ``fields``, ``goal``, ``domain``, ``bins``: as for ``DensityError`` -- one or two geometry
+    fields of a finished ray, e.g. ``("y_end", "z_end")``; ``goal`` a non-negative array of shape
+    (ny, nx), the second field the FIRST index, or (nx,) for one field, or a callable evaluated at
+    the centres of ``bins`` bins; ``domain`` one finite ``(lo, hi)`` per field; the same
+    ValueErrors.  Direction fields (``x_dir`` ...) and ``weights=`` are refused with a ValueError:
+    weighted quantiles and the chain rule of a direction are not built yet.
+    ``directions``: with two fields K angles -- an int K means ``theta_k = pi * k / K``,
+    k = 0 .. K-1 (default 8), an array gives them --, 1 <= K <= 64; one field: K = 1, the axis
+    itself.  ``c_k = cos(theta_k)``, ``s_k = sin(theta_k)`` are computed once on the host in
+    float64.  ``knots``: Q, the intervals of a quantile table, 2 <= Q <= 65,536.
+
+    The quantile tables ``tables``, (K, Q + 1) float64 on the device, are built on the host
+    (``ops.transport_tables``): every goal bin is split into 4 x 4 sub-points at the sub-cells'
+    centres, in normalised coordinates xi, eta in [0, 1], each with the bin's mass; empty ones are
+    dropped; per direction ``p = c * xi + s * eta`` (one field: ``p = xi``) is sorted stably,
+    ``cm = (cumsum(w) - w / 2) / sum(w)`` and ``T_k = np.interp(arange(Q + 1) / Q, cm, p_sorted)``:
+    non-decreasing by construction.
+
+    For every finished ray and direction, coordinates converted to float64, every operation
+    rounded on its own:
+
+    * a ray counts if both coordinates are finite (and, on the fused step, it has finished);
+    * ``xi = (x - x0) * ix`` with ``ix = 1 / (x1 - x0)`` computed once on the host, ``eta`` alike;
+      ``p = c * xi + s * eta`` (two products, one sum);
+    * its sort key: ``a = min(0, c) + min(0, s)``, ``b = max(0, c) + max(0, s)``,
+      ``lo = a - (b - a)``, ``scale = 2**26 / (3 * (b - a))``,
+      ``q = clamp(floor((p - lo) * scale), 0, 2**26 - 2)``; a ray that does not count has
+      ``q = 2**26 - 1`` (the width 26 is ``ops.TRANSPORT_KEY_BITS``: two 13-bit digits of the
+      radix sort) -- a ray up to one domain width outside still has a key of its own, farther out
+      the keys clamp and the rays tie;
+    * its rank among the n_valid rays that count: ``first`` keys are smaller than q, ``count`` are
+      equal to q, ``rank2 = 2 * first + count`` (int32; -1 for a ray that does not count) and
+      ``u = (first + count * 0.5) / n_valid``.  Ties share the mid-rank on purpose: the result
+      does not depend on the order of the rays, so the fused step (coherent order) and the generic
+      path (finished order) give every ray the same bits;
+    * target and residual: ``z = u * Q``, ``m = min(floor(z), Q - 1)``, ``f = z - m``,
+      ``t = T[m] + f * (T[m + 1] - T[m])``, ``d = p - t``; the term is ``d * d``;
+    * gradient, accumulated from zero in the order k = 0 .. K-1:
+      ``gx += ((2 * d) * c) * ix``, ``gy += ((2 * d) * s) * iy``; zeros for a ray that does not
+      count.  The targets are constants, as ``SpotError``'s centroids are;
+    * ``error = {sum of all terms, K * n_valid, sum / terms}`` -- the sum convention of
+      ``GoalError`` and ``SpotError``; the mean of no terms is NaN.  The sum has a fixed shape and
+      order: two runs give the same bits in the error, the gradient and ``rank2``.
+
+    It is an ordinary ``error_function(engine)`` (the generic path: ``ops.transport_error`` over
+    the finished rays' columns under a ``torch.autograd.Function``, which returns the
+    (n_finished, K) terms), which also serves 2-D engines, ``deterministic=True``, fewer than 4,096
+    rays and sources that are not traced in place.  On a 3-D engine that traces its source in
+    place the optimiser runs it on the fused, graph-replayed step under the conditions of a
+    ``DensityError`` (``FusedStep._rowwise3d`` with ``tfrt_transport_error``: 11 K + 2 launches,
+    n_valid stays on the device).  One process: the ranks couple all rays.
+
+    ``set_goal(goal)`` rebuilds the tables into the same device buffer, so a replayed graph sees
+    the new goal; another shape is a ValueError.  ``last_rank2`` is the (K, n) int32 ``rank2`` of
+    the last evaluation, ``last_count`` its n_valid (read from the device when asked for)."""
+
+    def __init__(self, fields, goal, domain, directions=None, knots=1024, bins=None,
+                 weights=None):
+        from . import config
+        self.fields, self.domain = _fields_and_domain("TransportError", fields, domain)
+        if any(f.endswith("_dir") for f in self.fields):
+            raise ValueError("TransportError: direction fields (x_dir, y_dir, z_dir) are not "
+                             f"supported, only geometry fields; got {fields!r}")
+        if weights is not None:
+            raise ValueError("TransportError: weights= is not supported (weighted quantiles are "
+                             "not built yet)")
+        self.rows = [_FIELDS3.index(f) for f in self.fields]
+        k = len(self.fields)
+        try:
+            self.knots = int(knots)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"TransportError: knots must be an integer, got {knots!r}") from e
+        if self.knots != knots or not 2 <= self.knots <= ops.TRANSPORT_MAX_KNOTS:
+            raise ValueError(f"TransportError: knots must lie in 2 .. {ops.TRANSPORT_MAX_KNOTS}, "
+                             f"got {knots!r}")
+        try:
+            cs = ops.transport_directions(8 if directions is None else directions, k)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"TransportError: directions must be a count in 1 .. "
+                             f"{ops.TRANSPORT_MAX_DIRECTIONS} or as many finite angles, got "
+                             f"{directions!r}") from e
+        self.directions = cs                       # (K, 2) numpy: cos, sin
+        self.bins = bins
+        dev = config.get_device()
+        g, _ = _goal_bins("TransportError", goal, self.domain, bins, dev)
+        self.goal_shape = tuple(g.shape)
+        self.angles = torch.as_tensor(cs, dtype=torch.float64).contiguous().to(dev)
+        self.tables = torch.as_tensor(
+            ops.transport_tables(g.cpu().numpy(), self.domain, cs, self.knots)).contiguous().to(dev)
+        self.grid = ops.transport_grid(self.domain)
+        self.last_rank2 = None
+
+    @property
+    def n_directions(self):
+        return self.tables.shape[0]
+
+    @property
+    def last_count(self):
+        """n_valid of the last evaluation (a device read)."""
+        if self.last_rank2 is None:
+            raise RuntimeError("TransportError: no evaluation yet")
+        return int((self.last_rank2[0] >= 0).sum()) if self.last_rank2.shape[1] else 0
+
+    def set_goal(self, goal):
+        """Another goal of the same shape: the tables are rebuilt on the host and copied into the
+        device buffer there is."""
+        g, _ = _goal_bins("TransportError", goal, self.domain, self.bins, torch.device("cpu"))
+        if tuple(g.shape) != self.goal_shape:
+            raise ValueError(f"TransportError: set_goal needs a goal of shape {self.goal_shape}, "
+                             f"got {tuple(g.shape)}")
+        new = ops.transport_tables(g.numpy(), self.domain, self.directions, self.knots)
+        self.tables.copy_(torch.as_tensor(new))
+
+    def rows_for(self, dimension):
+        """The rows of a ``dimension``-D geometry block the fields are read from."""
+        if dimension == 3:
+            return self.rows
+        return _field_codes("TransportError", self.fields, dimension)
+
+    def tables_on(self, device):
+        """(tables, angles) on ``device`` (moved once; new buffers re-capture a graph)."""
+        if self.tables.device != device:
+            self.tables, self.angles = self.tables.to(device), self.angles.to(device)
+        return self.tables, self.angles
+
+    def graph_key(self):
+        """What a captured step has baked in: the table buffer's address, K, Q, the directions'
+        buffer and the domain."""
+        return (self.tables.data_ptr(), self.n_directions, self.knots, self.angles.data_ptr(),
+                self.domain)
+
+    def evaluate(self, rows, row_x, row_y, mask=None, dimension=None, **buffers):
+        """``ops.transport_error`` of the columns of ``rows`` with these tables and this domain
+        (``dimension`` given: ``rows`` is the geometry block)."""
+        tables, angles = self.tables_on(rows.device)
+        out = ops.transport_error(rows, row_x, row_y, tables, self.grid, angles, mask=mask,
+                                  dimension=dimension, **buffers)
+        self.last_rank2 = out[2]
+        return out
+
+    def __call__(self, engine):
+        """The (n_finished, K) error terms through the generic path; the gradient rows come back
+        in ``backward``."""
+        self.rows_for(engine.dimension)           # (a field the engine's rays do not have)
+        fin = engine.finished_rays
+        if not bool(fin):
+            return torch.zeros((0, self.n_directions), dtype=torch.float64)
+        return _TransportTerms.apply(torch.stack([fin[f] for f in self.fields], dim=0), self)
+
+
+def _transport_terms(erf, v, rank2):
+    """The (n, K) terms of a TransportError evaluation from its ranks, the definition's operations
+    as torch ops; ``v``: the (k, n) float64 fields.  Zeros for a ray that does not count."""
+    tables, angles = erf.tables_on(v.device)
+    x0, ix, y0, iy = erf.grid
+    two = v.shape[0] == 2
+    Q = erf.knots
+    xi = (v[0] - x0) * ix
+    eta = (v[1] - y0) * iy if two else None
+    counts = rank2[0] >= 0
+    nv = counts.sum().double()
+    terms = []
+    for k in range(tables.shape[0]):
+        p = erf.directions[k, 0] * xi + erf.directions[k, 1] * eta if two else xi
+        z = ((rank2[k].double() * 0.5) / nv) * float(Q)
+        fm = torch.clamp(torch.floor(torch.where(counts, z, torch.zeros_like(z))),
+                         min=0.0, max=float(Q - 1))
+        m = fm.long()
+        t0 = tables[k][m]
+        d = p - (t0 + (z - fm) * (tables[k][m + 1] - t0))
+        terms.append(torch.where(counts, d * d, torch.zeros_like(d)))
+    return torch.stack(terms, dim=1).contiguous()
+
+
+class _TransportTerms(torch.autograd.Function):
+    """TransportError over the (k, n) field columns of the finished rays, no mask.  Returns the
+    (n, K) terms; the gradient has summed the K directions into a ray's rows, so one weight per
+    ray is all that can be applied afterwards (the optimiser passes ones)."""
+
+    @staticmethod
+    def forward(ctx, columns, erf):
+        rows = columns.detach().contiguous()
+        _, grad, rank2 = erf.evaluate(rows, 0, 1 if rows.shape[0] == 2 else -1)
+        ctx.save_for_backward(grad)
+        ctx.dtype = columns.dtype
+        return _transport_terms(erf, rows.double(), rank2)
+
+    @staticmethod
+    def backward(ctx, upstream):
+        grad, = ctx.saved_tensors
+        if upstream.shape[1] > 1 and not torch.equal(upstream,
+                                                     upstream[:, :1].expand_as(upstream)):
+            raise ValueError("TransportError: the upstream gradient must weigh the K terms of a "
+                             "ray alike")
+        return (upstream[:, 0] * grad).to(ctx.dtype), None
 
 
 class SpotError:
@@ -804,6 +1031,10 @@ class _SpotTerms(torch.autograd.Function):
         return (upstream[:, 0] * grad).to(ctx.dtype), None, None, None, None, None, None
 
 
+# the coupled errors: all finished rays of a step enter one evaluation (one process)
+_COUPLED = (DensityError, SpotError, TransportError)
+
+
 class _RowFields:
     """Field mapping handed to a RowwiseError on the fixed-shape path: geometry = the rows of the
     in-place finished block, everything else = the source's own fields in the trace's order."""
@@ -894,6 +1125,7 @@ class _StepState:
         "rows", "row_face", "row_passes", "row_outs",        # a RowwiseError's fixed-shape columns
         "density_ws", "hq",                                  # a DensityError's workspace and histogram
         "spot_ws", "acc",                                    # a SpotError's workspace and group records
+        "transport_ws", "rank2",                             # a TransportError's workspace and ranks
         "chain_ws", "inherited",                             # made on first use
         "sched", "sched_key", "sched_checked",               # the in-place trace's wavefront schedule
         "block", "stream", "perm", "inplace")                # of the last enqueued step
@@ -939,8 +1171,8 @@ class _StepState:
 
 class FusedStep:
     """Runs ``SGD_Optimizer.single_step`` for a ``GoalError`` or a ``RowwiseError`` as a fixed
-    launch sequence, on 3-D engines and on 2-D ones (one process), and for a ``DensityError`` or a
-    ``SpotError`` on 3-D engines; see the module docstring.
+    launch sequence, on 3-D engines and on 2-D ones (one process), and for a ``DensityError``, a
+    ``SpotError`` or a ``TransportError`` on 3-D engines; see the module docstring.
     One instance per optimizer."""
 
     # coherent rays: error, gradient seed and reverse sweep as ONE launch (tfrt_trace3d_backward_goal);
@@ -991,13 +1223,13 @@ class FusedStep:
     def eligible(optimizer, args, kwargs):
         eng = optimizer.engine
         erf = optimizer.error_function
-        if not isinstance(erf, (GoalError, RowwiseError, DensityError, SpotError)) or args or kwargs:
+        if not isinstance(erf, (GoalError, RowwiseError) + _COUPLED) or args or kwargs:
             return False
-        if (isinstance(erf, (RowwiseError, DensityError, SpotError)) and eng.dimension == 3
+        if (isinstance(erf, (RowwiseError,) + _COUPLED) and eng.dimension == 3
                 and not FusedStep.rowwise_ready(eng)):
             return False
-        if isinstance(erf, (DensityError, SpotError)) and tdist.is_distributed():
-            return False            # (the histogram / the centroids couple the rays: one process)
+        if isinstance(erf, _COUPLED) and tdist.is_distributed():
+            return False            # (the histogram / the centroids / the ranks couple the rays: one process)
         if not bool(eng.optical_system):
             return False
         if eng.dimension == 2 and not FusedStep.eligible2d(optimizer):
@@ -1154,7 +1386,7 @@ class FusedStep:
             raise RuntimeError("FusedStep: the optical system has no source rays")
         inputs = eng._trace_inputs(src)
         P, flags = int(opt.trace_depth), eng._flags() | _lib.COMPILE_FINISHED
-        rowwise = isinstance(opt.error_function, (RowwiseError, DensityError, SpotError))
+        rowwise = isinstance(opt.error_function, (RowwiseError,) + _COUPLED)
         if eng.dimension == 2:
             body = self._rowwise2d if rowwise else self._goal2d
         else:
@@ -1370,8 +1602,9 @@ class FusedStep:
 
     def _rowwise3d(self, src, inputs, tap_log, P, flags):
         """In-place trace with the finished rows at the rays' own columns -> ``erf.fn`` on
-        fixed-shape tensors + its autograd (torch), or a DensityError's / a SpotError's three
-        launches (tfrt_density_error, tfrt_spot_error) -> reverse sweep.  No ray count is read; everything is capturable."""
+        fixed-shape tensors + its autograd (torch), or a DensityError's / a SpotError's / a
+        TransportError's launches (tfrt_density_error, tfrt_spot_error, tfrt_transport_error) ->
+        reverse sweep.  No ray count is read; everything is capturable."""
         eng = self.opt.engine
         block, scene, fv = inputs
         perm = eng._trace_perm
@@ -1403,9 +1636,11 @@ class FusedStep:
         # the same values as the forward)
         with _override(sc, in_place=2, face_sums=1 if four else 0, **clear):
             self._trace_forward(st, sc, st.row_outs)
-            if isinstance(self.opt.error_function, (DensityError, SpotError)):
+            if isinstance(self.opt.error_function, _COUPLED):
                 if isinstance(self.opt.error_function, DensityError):
                     g64 = self._density_seeds3d(st, src, perm)
+                elif isinstance(self.opt.error_function, TransportError):
+                    g64 = self._transport_seeds3d(st)
                 else:
                     g64 = self._spot_seeds3d(st, src, perm)
                 if not need_back:
@@ -1438,6 +1673,27 @@ class FusedStep:
         erf.evaluate(st.rows[:, :st.N], rows[0], rows[1] if len(rows) == 2 else -1,
                      mask=st.row_face, dimension=3, weights=erf.weights_of(src), perm=perm,
                      grad=st.g_fin, err=st.err, hq=st.hq, workspace=st.density_ws)
+        with torch.no_grad():
+            self.tests_total += st.row_passes[:st.N].sum() * st.M
+        return st.g_fin
+
+    def _transport_seeds3d(self, st):
+        """A TransportError on the fixed-shape columns: tfrt_transport_error reads ``st.rows`` and
+        the mask ``st.row_face`` and writes its two rows of the persistent seed block for every
+        column (the other rows were zeroed when the state was made), the error into ``st.err`` and
+        the ranks into ``st.rank2``; n_valid never leaves the device.  Returns the (6, capN) seed
+        block."""
+        erf = self.opt.error_function
+        dev = st.rows.device
+        K = erf.n_directions
+        if st.rank2 is None or tuple(st.rank2.shape) != (K, st.N):
+            wsb = _lib.lib().tfrt_transport_error_workspace_bytes(st.N, K)
+            st.transport_ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+            st.rank2 = torch.zeros((K, st.N), dtype=torch.int32, device=dev)
+        rows = erf.rows
+        erf.evaluate(st.rows[:, :st.N], rows[0], rows[1] if len(rows) == 2 else -1,
+                     mask=st.row_face, dimension=3, grad=st.g_fin, err=st.err, rank2=st.rank2,
+                     workspace=st.transport_ws)
         with torch.no_grad():
             self.tests_total += st.row_passes[:st.N].sum() * st.M
         return st.g_fin
@@ -1883,7 +2139,7 @@ class FusedStep:
         in place is seen by replays, another buffer re-captures), its shape and the constants; a
         SpotError's: the label buffer's address and shape, G and the constants."""
         erf = self.opt.error_function
-        return erf.graph_key() if isinstance(erf, (DensityError, SpotError)) else ()
+        return erf.graph_key() if isinstance(erf, _COUPLED) else ()
 
     def _index_signature(self):
         """The refractive-index fields that take a gradient (boundary, field, identity of a tensor

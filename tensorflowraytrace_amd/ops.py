@@ -1596,6 +1596,216 @@ def _density_error_cpu(rows, row_x, row_y, goal, grid, oob, mask, grad, err, hq,
     err[0], err[1], err[2] = e, 1.0, e
 
 
+TRANSPORT_KEY_BITS = 26               # transport_math.h: two 13-bit digits of the radix sort
+TRANSPORT_KEY_INVALID = (1 << TRANSPORT_KEY_BITS) - 1
+TRANSPORT_MAX_DIRECTIONS = 64
+TRANSPORT_MAX_KNOTS = 65536
+TRANSPORT_SUBCELLS = 4                # sub-points per goal bin and axis of the quantile tables
+
+
+def transport_directions(directions, n_fields=2):
+    """The (K, 2) float64 array of (cos, sin) of a TransportError's projection angles, computed
+    once here: an int K means the angles pi * k / K, k = 0 .. K-1; an array gives them.  One field:
+    the single direction (1, 0)."""
+    if n_fields == 1:
+        return np.array([[1.0, 0.0]], dtype=np.float64)
+    if np.ndim(directions) == 0:
+        if isinstance(directions, (bool, np.bool_)) or int(directions) != directions:
+            raise ValueError(f"transport_directions: a direction count must be an integer, got "
+                             f"{directions!r}")
+        k = int(directions)
+        if not 1 <= k <= TRANSPORT_MAX_DIRECTIONS:
+            raise ValueError(f"transport_directions: 1 .. {TRANSPORT_MAX_DIRECTIONS} directions, "
+                             f"got {k}")
+        theta = np.pi * np.arange(k, dtype=np.float64) / np.float64(k)
+    else:
+        theta = np.asarray(directions, dtype=np.float64)
+        if theta.ndim != 1 or not 1 <= theta.size <= TRANSPORT_MAX_DIRECTIONS \
+                or not np.isfinite(theta).all():
+            raise ValueError(f"transport_directions: 1 .. {TRANSPORT_MAX_DIRECTIONS} finite "
+                             f"angles, got {directions!r}")
+    return np.stack([np.cos(theta), np.sin(theta)], axis=1)
+
+
+def transport_tables(goal, domain, angles, knots):
+    """The quantile tables of a TransportError, (K, Q + 1) numpy float64, in the normalised
+    coordinates of ``domain`` (whose extents therefore do not enter: only one (lo, hi) per field
+    is asked for).  ``goal``: non-negative (ny, nx) or (nx,); ``angles``: the (K, 2) (cos, sin) of
+    ``transport_directions``; ``knots``: Q.  Every bin is split into 4 x 4 sub-points (4 with one
+    field) at the sub-cells' centres, each with the bin's mass; empty ones are dropped; per
+    direction the projections ``p = c * xi + s * eta`` (one field: ``xi``) are sorted stably,
+    ``cm = (cumsum(w) - w / 2) / sum(w)``, and ``T = np.interp(arange(Q + 1) / Q, cm, p_sorted)``:
+    non-decreasing by construction."""
+    g = np.asarray(goal, dtype=np.float64)
+    cs = np.asarray(angles, dtype=np.float64).reshape(-1, 2)
+    q = int(knots)
+    if g.ndim not in (1, 2) or g.ndim != len(domain):
+        raise ValueError("transport_tables: goal must be (ny, nx) with two domain axes or (nx,) "
+                         "with one")
+    if not 2 <= q <= TRANSPORT_MAX_KNOTS:
+        raise ValueError(f"transport_tables: 2 .. {TRANSPORT_MAX_KNOTS} knots, got {knots!r}")
+    if not np.isfinite(g).all() or (g < 0).any() or not (g > 0).any():
+        raise ValueError("transport_tables: goal must be finite, non-negative and not all zero")
+    sub = TRANSPORT_SUBCELLS
+    nx = g.shape[-1]
+    xi = (np.arange(nx * sub, dtype=np.float64) + 0.5) / np.float64(nx * sub)
+    if g.ndim == 2:
+        ny = g.shape[0]
+        eta = (np.arange(ny * sub, dtype=np.float64) + 0.5) / np.float64(ny * sub)
+        w = np.repeat(np.repeat(g, sub, axis=0), sub, axis=1).reshape(-1)
+        xi, eta = np.tile(xi, ny * sub), np.repeat(eta, nx * sub)
+    else:
+        w = np.repeat(g, sub)
+        eta = np.zeros_like(xi)
+        cs = np.array([[1.0, 0.0]])
+    keep = w > 0
+    xi, eta, w = xi[keep], eta[keep], w[keep]
+    at = np.arange(q + 1, dtype=np.float64) / np.float64(q)
+    tables = np.empty((cs.shape[0], q + 1), dtype=np.float64)
+    for k, (c, s) in enumerate(cs):
+        p = c * xi + s * eta if g.ndim == 2 else xi
+        order = np.argsort(p, kind="stable")
+        ws = w[order]
+        cm = (np.cumsum(ws) - ws / 2.0) / ws.sum()
+        tables[k] = np.interp(at, cm, p[order])
+    return tables
+
+
+def transport_grid(domain):
+    """The domain constants tfrt_transport_error takes, (x0, ix, y0, iy) in float64 with
+    ix = 1 / (x1 - x0) computed once here; one axis: the y constants are 0."""
+    (x0, x1) = (float(v) for v in domain[0])
+    ix = float(np.float64(1.0) / (np.float64(x1) - np.float64(x0)))
+    if len(domain) == 1:
+        return (x0, ix, 0.0, 0.0)
+    (y0, y1) = (float(v) for v in domain[1])
+    return (x0, ix, y0, float(np.float64(1.0) / (np.float64(y1) - np.float64(y0))))
+
+
+def transport_error(rows, row_x, row_y, tables, grid, angles, mask=None, dimension=None,
+                    grad=None, err=None, rank2=None, workspace=None):
+    """tfrt_transport_error: the TransportError of the columns of ``rows`` (k, n), x in row
+    ``row_x`` and y in row ``row_y`` (-1: one field, one direction).  ``tables``: contiguous
+    float64 (K, Q + 1) from ``transport_tables``; ``grid`` from ``transport_grid``; ``angles``:
+    contiguous float64 (K, 2), the (cos, sin) of ``transport_directions``; both on the device of
+    ``rows``.  ``mask``: optional int32, column i counts if mask[i] >= 0.  ``dimension`` 2 or 3:
+    ``rows`` is the (2 * dimension, n) geometry block (position rows only); None: any block of up
+    to six rows.  Returns (err {sum, K * n_valid, mean}, grad (k, n) float64, rank2 (K, n) int32:
+    2 * first + count of every column, -1 where it does not count): rows ``row_x`` / ``row_y`` of
+    ``grad`` are written for every column, other rows only when ``grad`` is made here (zeros).
+    ``grad``, ``err``, ``rank2``, ``workspace`` (uint8): buffers to reuse -- with all four given a
+    CUDA call allocates nothing.
+
+    CUDA tensors run the kernels.  CPU tensors run a torch restatement with the same keys, the
+    same ranks and the same operation order per ray (``rank2`` and the gradient agree bit for
+    bit; the error sum is torch's and agrees to rounding)."""
+    two = row_y >= 0
+    if tables.dtype != torch.float64 or tables.dim() != 2 or not tables.is_contiguous() \
+            or angles.dtype != torch.float64 or tuple(angles.shape) != (tables.shape[0], 2) \
+            or not angles.is_contiguous():
+        raise ValueError("transport_error: tables must be contiguous float64 (K, Q + 1) and "
+                         "angles contiguous float64 (K, 2)")
+    K, Q = tables.shape[0], tables.shape[1] - 1
+    if not (1 <= K <= TRANSPORT_MAX_DIRECTIONS and 2 <= Q <= TRANSPORT_MAX_KNOTS) \
+            or (not two and K != 1):
+        raise ValueError(f"transport_error: 1 .. {TRANSPORT_MAX_DIRECTIONS} directions (one with "
+                         f"one field) and 2 .. {TRANSPORT_MAX_KNOTS} knots, got {K} and {Q}")
+    k, n = rows.shape
+    top = k if dimension is None else 2 * dimension
+    if dimension is not None and (dimension not in (2, 3) or k != 2 * dimension):
+        raise ValueError(f"transport_error: dimension must be None, 2 or 3 with a block of "
+                         f"2 * dimension rows, got {dimension!r} and {k} rows")
+    if k > 6 or not (0 <= row_x < top and -1 <= row_y < top and row_x != row_y):
+        raise ValueError(f"transport_error: rows must be distinct position rows in [0, {top}), "
+                         f"got {row_x}, {row_y}")
+    dev = rows.device
+    if grad is None:
+        grad = torch.zeros((k, n), dtype=torch.float64, device=dev)
+    if err is None:
+        err = torch.empty(3, dtype=torch.float64, device=dev)
+    if rank2 is None:
+        rank2 = torch.empty((K, n), dtype=torch.int32, device=dev)
+    if rank2.dtype != torch.int32 or tuple(rank2.shape) != (K, n) or not rank2.is_contiguous():
+        raise ValueError(f"transport_error: rank2 must be contiguous int32 ({K}, {n})")
+    if grad.dtype != torch.float64 or grad.dim() != 2 or grad.shape[0] != k or grad.shape[1] < n:
+        raise ValueError(f"transport_error: grad must be float64 ({k}, {n})")
+    if mask is not None and (mask.dtype != torch.int32 or mask.numel() < n
+                             or not mask.is_contiguous()):
+        raise ValueError("transport_error: mask must be contiguous int32, one entry per column")
+    if not rows.is_cuda:
+        _transport_error_cpu(rows, row_x, row_y, tables, grid, angles, mask, grad, err, rank2)
+        return err, grad, rank2
+    _need_gpu(rows, tables, angles, mask, grad, err, rank2)
+    if rows.stride(1) != 1 or grad.stride(1) != 1:
+        raise ValueError("transport_error: rows and grad must have contiguous columns")
+    L = _lib.lib()
+    wsb = L.tfrt_transport_error_workspace_bytes(n, K)
+    if workspace is None:
+        workspace = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    x0, ix, y0, iy = grid
+    check(L.tfrt_transport_error(
+        _p(rows), rows.stride(0), n, _DT[rows.dtype], 3 if dimension is None else int(dimension),
+        _p(mask), row_x, row_y, x0, ix, y0, iy, _p(angles), _p(tables), Q, K, _p(grad),
+        grad.stride(0), _p(err), _p(rank2), _p(workspace), workspace.numel(), _stream(rows)),
+        "tfrt_transport_error")
+    return err, grad, rank2
+
+
+def _transport_error_cpu(rows, row_x, row_y, tables, grid, angles, mask, grad, err, rank2):
+    """The CPU path of ``transport_error`` (every torch op rounds on its own, as the kernels
+    do)."""
+    x0, ix, y0, iy = grid
+    two = row_y >= 0
+    n = rows.shape[1]
+    K, Q = tables.shape[0], tables.shape[1] - 1
+    x = rows[row_x].double()
+    y = rows[row_y].double() if two else torch.zeros_like(x)
+    counts = torch.isfinite(x) & torch.isfinite(y)
+    if mask is not None:
+        counts &= mask[:n] >= 0
+    nv = int(counts.sum())
+    xi = (x - x0) * ix
+    eta = (y - y0) * iy if two else torch.zeros_like(x)
+    zero = torch.zeros((), dtype=torch.float64)
+    top = float(TRANSPORT_KEY_INVALID - 1)
+    gx, gy = torch.zeros_like(x), torch.zeros_like(x)
+    total = torch.zeros((), dtype=torch.float64)
+    for k in range(K):
+        c, s = (float(v) for v in angles[k]) if two else (1.0, 0.0)
+        a, b = min(0.0, c) + min(0.0, s), max(0.0, c) + max(0.0, s)
+        lo = a - (b - a)
+        scale = float(1 << TRANSPORT_KEY_BITS) / (3.0 * (b - a))
+        p = c * xi + s * eta if two else xi
+        v = torch.floor((p - lo) * scale)
+        key = torch.where(v >= 0.0, torch.clamp(v, max=top), zero).long()
+        key = torch.where(counts, key, torch.full_like(key, TRANSPORT_KEY_INVALID))
+        sk = torch.sort(key).values
+        first = torch.searchsorted(sk, key, right=False)
+        last = torch.searchsorted(sk, key, right=True)
+        r2 = torch.where(counts, first + last, torch.full_like(first, -1))
+        rank2[k] = r2.to(torch.int32)
+        if nv == 0:
+            continue
+        u = (r2.double() * 0.5) / float(nv)
+        z = u * float(Q)
+        fm = torch.clamp(torch.floor(z), min=0.0, max=float(Q - 1))
+        m = fm.long()
+        f = z - fm
+        T = tables[k]
+        t0 = T[m]
+        t = t0 + f * (T[m + 1] - t0)
+        d = torch.where(counts, p - t, zero)
+        total = total + (d * d).sum()
+        gx = gx + ((2.0 * d) * c) * ix
+        gy = gy + ((2.0 * d) * s) * iy
+    grad[row_x, :n] = gx
+    if two:
+        grad[row_y, :n] = gy
+    terms = float(K * nv)
+    err[0], err[1] = total, terms
+    err[2] = total / terms if terms > 0 else float("nan")
+
+
 SPOT_MAX_GROUPS = 1 << 20
 SPOT_LDS_GROUPS = 1024
 SPOT_WEIGHTED_LDS_GROUPS = 512     # tfrt_spot_error_weighted: six planes, the same 24 KiB

@@ -29,9 +29,9 @@ import torch
 
 from . import distributed as tdist
 from . import _lib, ops
-# (GoalError, RowwiseError, DensityError, SpotError: public API)
+# (GoalError, RowwiseError, DensityError, SpotError, TransportError: public API)
 from .fused_step import (FusedStep, GoalError, RowwiseError, DensityError, SpotError,  # noqa: F401
-                         _NotInPlace)
+                         TransportError, _NotInPlace)
 
 
 class DeferredScalar:

@@ -1480,8 +1480,8 @@ __global__ __launch_bounds__(BLOCK) void k_intersect_group_left(
 //              bundle (no per-ray work at all), survivors compacted into the next level's list.
 //   faces      LANE = FACE: the candidate faces (a dozen for a coherent wave) as TRIANGLES, seen
 //              along the axis, against the bundle (face_frame below); those left are ordered by
-//              depth and taken two at a time, LANE = RAY: the faces' records travel in scalar
-//              registers (v_readlane), a ray keeps a face if its image lies within the face's
+//              depth and taken two at a time, LANE = RAY: the faces' records reach the lanes as
+//              DPP operands (face_edges), a ray keeps a face if its image lies within the face's
 //              (a dozen instructions); the pairs kept queue for the exact float64 decision, one
 //              (ray, face) per lane, nearest hit per ray by 64-bit ds_min -- the same function
 //              as in the grouped kernel.  The walk ends when every ray has a decided hit nearer
@@ -1650,6 +1650,64 @@ __device__ __forceinline__ void wave_max3_min(float& a, float& b, float& c, floa
   d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d), 63));
 }
 
+// two sums and a maximum (three values: a register is read three instructions after it was written)
+#define TFRT_DPP_STEP3(OPA, OPB, OPC, CTRL) \
+  OPA " %0, %0, %0 " CTRL "\n\t" OPB " %1, %1, %1 " CTRL "\n\t" OPC " %2, %2, %2 " CTRL "\n\t"
+#define TFRT_DPP_ALL3(OPA, OPB, OPC)                                        \
+  "s_nop 1\n\t"                                                             \
+  TFRT_DPP_STEP3(OPA, OPB, OPC, "quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf") \
+  TFRT_DPP_STEP3(OPA, OPB, OPC, "quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf") \
+  TFRT_DPP_STEP3(OPA, OPB, OPC, "row_half_mirror row_mask:0xf bank_mask:0xf")     \
+  TFRT_DPP_STEP3(OPA, OPB, OPC, "row_mirror row_mask:0xf bank_mask:0xf")          \
+  TFRT_DPP_STEP3(OPA, OPB, OPC, "row_bcast:15 row_mask:0xa bank_mask:0xf")        \
+  TFRT_DPP_STEP3(OPA, OPB, OPC, "row_bcast:31 row_mask:0xc bank_mask:0xf")
+__device__ __forceinline__ void wave_sum2_max(float& a, float& b, float& c) {
+  __asm__ volatile(TFRT_DPP_ALL3("v_add_f32_dpp", "v_add_f32_dpp", "v_max_f32_dpp")
+                   : "+v"(a), "+v"(b), "+v"(c));
+  a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a), 63));
+  b = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(b), 63));
+  c = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c), 63));
+}
+
+// One face record (face_frame) against every lane's ray image p(t) = A + M t: the three edge
+// values n_k . p(tc) + c_k and the room |M| h + slack + Perr + Pm |tc| they are compared with.
+// `word` holds the record's sixteen words in lanes 0..15 of EVERY row of sixteen lanes, and each
+// word reaches the arithmetic as a DPP operand (row_newbcast:k = lane k of the reader's own row):
+// no v_readlane, no scalar register.  The same products, fused multiply-adds and sums, in the same
+// order, as the plain expressions compile to.
+// EXEC: a DPP operand from a lane that is switched off reads as nothing, so this runs with every
+// lane on -- no divergent branch between the load of `word` and here (see the walk).
+// Hazards: a register written by a vector instruction is read by a DPP instruction (as any of its
+// operands) three instructions later at the earliest; the leading s_nop covers the inputs.
+#define TFRT_BCAST(K) " row_newbcast:" #K " row_mask:0xf bank_mask:0xf\n\t"
+__device__ __forceinline__ void face_edges(const float word, const float Ax, const float Ay,
+                                           const float Mx, const float My, const float Mlen,
+                                           const float Perr, const float Pm, float& room,
+                                           float& e0, float& e1, float& e2) {
+  float ix, iy;
+  __asm__ volatile(
+      "s_nop 1\n\t"
+      "v_mov_b32_dpp %3, %6" TFRT_BCAST(11)          // tc
+      "v_mov_b32_dpp %0, %6" TFRT_BCAST(13)          // slack
+      "v_fma_f32 %5, %3, %10, %8\n\t"                // iy = Ay + My tc
+      "v_fma_f32 %4, %3, %9, %7\n\t"                 // ix = Ax + Mx tc
+      "v_fmac_f32_dpp %0, %6, %11" TFRT_BCAST(12)    // room = Mlen h + slack
+      "v_mul_f32_dpp %1, %6, %5" TFRT_BCAST(1)       // e0 = n0y iy
+      "v_mul_f32_dpp %2, %6, %5" TFRT_BCAST(5)       // e1 = n1y iy
+      "v_add_f32 %0, %12, %0\n\t"                    //      ... + Perr
+      "v_fma_f32 %0, %13, |%3|, %0\n\t"              //      ... + Pm |tc|   (tc is free from here)
+      "v_fmac_f32_dpp %1, %6, %4" TFRT_BCAST(0)      // e0 += n0x ix
+      "v_fmac_f32_dpp %2, %6, %4" TFRT_BCAST(4)      // e1 += n1x ix
+      "v_mul_f32_dpp %3, %6, %5" TFRT_BCAST(9)       // e2 = n2y iy
+      "v_add_f32_dpp %1, %6, %1" TFRT_BCAST(2)       // e0 += c0
+      "v_add_f32_dpp %2, %6, %2" TFRT_BCAST(6)       // e1 += c1
+      "v_fmac_f32_dpp %3, %6, %4" TFRT_BCAST(8)      // e2 += n2x ix
+      "s_nop 1\n\t"
+      "v_add_f32_dpp %3, %6, %3" TFRT_BCAST(10)      // e2 += c2
+      : "=&v"(room), "=&v"(e0), "=&v"(e1), "=&v"(e2), "=&v"(ix), "=&v"(iy)
+      : "v"(word), "v"(Ax), "v"(Ay), "v"(Mx), "v"(My), "v"(Mlen), "v"(Perr), "v"(Pm));
+}
+
 __device__ __forceinline__ float uniform_f(float v) {  // v wave-uniform: into a scalar register
   return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
@@ -1660,8 +1718,8 @@ __device__ __forceinline__ float bcast_f(float v, int src_lane) {  // src_lane w
 // The exact float64 test of k_intersect_beam, one (ray, face) pair per lane; nearest hit per ray
 // by 64-bit min on an order-preserving key of ray_u, ties to the lower face index (tf.argmin's
 // first index).  x_pair[k] = face << 6 | ray slot, rt[6][64] = the wavefront's rays as stored.
-// (A function of its own, not inlined: the four places that call it share one copy, and its
-// registers -- nine float64 vertices, the six-term sums -- are not added to the caller's.)
+// (Inlined into beam_pass, which runs it in ONE place -- the walk's flush loop -- so that its
+// registers, nine float64 vertices and the six-term sums, are not multiplied by call sites.)
 template <typename U>
 using LdsPtr = __attribute__((address_space(3))) U*;
 
@@ -1716,7 +1774,8 @@ struct BeamLds {
   uint16_t clist[BEAM_CLIST];
   uint32_t flist[BEAM_FLIST];
   uint32_t x_pair[192];  // face << 6 | lane of the ray (faces < 2^24)
-  float4 ftab[64][4];    // records of a chunk's faces, nearest first (face_frame)
+  float4 ftab[65][4];    // records of a chunk's faces, nearest first (face_frame); a round loads two
+                         // (the second, behind the chunk's last face, is read and not used)
   RT rtab[6][64];        // the wave's rays as stored (the exact test reads them by slot)
   unsigned long long best_k[64];
   int32_t best_i[64];
@@ -1836,9 +1895,10 @@ __device__ __forceinline__ bool beam_pass(BeamLds<RT>& W, const BeamScene& g, co
       // ---- the bundle
       float swx = sel ? ux : 0.f, swy = sel ? uy : 0.f, swz = sel ? uz : 0.f;
       float sox = sel ? sx : 0.f, soy = sel ? sy : 0.f, soz = sel ? sz : 0.f;
-      float pad0 = 0.f, pad1 = 0.f;
+      // (Lw does not depend on the sums: its maximum rides in the second call)
+      float Lw = sel ? rabs : 0.f;
       wave_sum4(swx, swy, swz, sox);
-      wave_sum4(soy, soz, pad0, pad1);
+      wave_sum2_max(soy, soz, Lw);
       const float wl2 = swx * swx + swy * swy + swz * swz;
       narrow = wl2 > 0.49f * cnt * cnt;  // (NaN: false)
       spread = !narrow;
@@ -1883,8 +1943,7 @@ __device__ __forceinline__ bool beam_pass(BeamLds<RT>& W, const BeamScene& g, co
       // (offset and slope of the ray's line from the axis are those of its image: e1, e2, w are
       // orthonormal to rounding, which the inflation below covers many times over)
       float R0 = sel ? __builtin_amdgcn_sqrtf(Ax * Ax + Ay * Ay) : 0.f, S = sel ? Mlen : 0.f;
-      float Lw = sel ? rabs : 0.f, tmin = sel ? ts : INFINITY;
-      wave_max3_min(R0, S, Lw, tmin);
+      float tmin = sel ? ts : INFINITY;
       Lw += fabsf(bm.ox) + fabsf(bm.oy) + fabsf(bm.oz);
       // A second anchor of the same bound: R0 + S |t| is tight near the plane where R0 was taken
       // and loosens with the distance from it, because S is the largest slope, not the spread.
@@ -1901,7 +1960,7 @@ __device__ __forceinline__ bool beam_pass(BeamLds<RT>& W, const BeamScene& g, co
         const float bx = Ax + Mx * tb, by = Ay + My * tb;
         R0b = __builtin_amdgcn_sqrtf(bx * bx + by * by);
       }
-      R0b = wave_max_f(R0b);
+      wave_max3_min(R0, S, R0b, tmin);
       // bounds inflated far beyond their float32 rounding (offsets ~ 2^-23 Lw, slopes ~ 2^-23)
       bm.R0 = R0 * 1.001f + 4e-6f * Lw;
       bm.S = S * 1.001f + 2e-6f;
@@ -2046,7 +2105,7 @@ __device__ __forceinline__ bool beam_pass(BeamLds<RT>& W, const BeamScene& g, co
     // upper bound of the axial coordinate of this ray's nearest hit so far (inf: none)
     auto reach_now = [&]() {
       const double best = dkey_inv(W.best_k[lane]);
-      const float bu = nextafterf((float)best, INFINITY) * ray_dt;  // (d . w > 0: cos > 0.7)
+      const float bu = next_up_f((float)best) * ray_dt;  // (d . w > 0: cos > 0.7)
       return ray_t + bu + 1e-5f * fabsf(bu) + ray_terr;
     };
     float myreach = reach_now();
@@ -2104,29 +2163,32 @@ __device__ __forceinline__ bool beam_pass(BeamLds<RT>& W, const BeamScene& g, co
       TFRT_STAT(27, nt);
       TFRT_TICK(6);
       float span = -INFINITY;  // farthest axial coordinate of the faces taken so far
-      // one face of the record table against this lane's ray: the record's sixteen words have been
-      // read by sixteen lanes (from lane `b` on) and are handed round with v_readlane -- scalar
-      // operands; sixty-four lanes reading ONE LDS address would be served one after the other
-      auto on_face = [&](const float word, const int b, int* j, float* thi) {
-        const float tn = bcast_f(word, b + 3), tc = bcast_f(word, b + 11);
-        *thi = bcast_f(word, b + 7);
-        *j = __float_as_int(bcast_f(word, b + 14));
-        const float ix = Ax + Mx * tc, iy = Ay + My * tc;
-        const float room = Mlen * bcast_f(word, b + 12) + bcast_f(word, b + 13) + Perr + Pm * fabsf(tc);
+      // one face of the record table against this lane's ray.  The record's sixteen words have been
+      // read by the sixteen lanes of every row (sixty-four lanes reading ONE LDS address would be
+      // served one after the other) and reach the edge tests as DPP operands (face_edges); only
+      // what feeds scalar control flow and the pair word -- tn, thi, the face index -- is handed
+      // round with v_readlane.  Straight-line, every lane on: the three edges are always computed
+      // and the booleans combined at the end (`&`, not `&&`: a short-circuit would put face_edges
+      // behind a divergent branch, where lanes 0..15 of a row may be off and their words unreadable).
+      auto on_face = [&](const float word, int* j, float* thi) {
+        const float tn = bcast_f(word, 3);
+        *thi = bcast_f(word, 7);
+        *j = __float_as_int(bcast_f(word, 14));
+        float room, e0, e1, e2;
+        face_edges(word, Ax, Ay, Mx, My, Mlen, Perr, Pm, room, e0, e1, e2);
         // (valid hits lie ahead of the start -- where bm.tmin says so --, and nearer than the
         // ray's nearest hit so far)
-        return sel && *j != skip && !(myreach < tn) &&
-               !(bm.tmin > -INFINITY && *thi < ray_t - ray_terr) &&
-               !(bcast_f(word, b) * ix + bcast_f(word, b + 1) * iy + bcast_f(word, b + 2) > room) &&
-               !(bcast_f(word, b + 4) * ix + bcast_f(word, b + 5) * iy + bcast_f(word, b + 6) > room) &&
-               !(bcast_f(word, b + 8) * ix + bcast_f(word, b + 9) * iy + bcast_f(word, b + 10) > room);
+        const bool behind = bm.tmin > -INFINITY && *thi < ray_t - ray_terr;
+        return (sel & (*j != skip) & !(myreach < tn) & !behind) &
+               (!(e0 > room) & !(e1 > room) & !(e2 > room));
       };
       // two faces per round (the rounds' scalar bookkeeping and branches cost as much as a face)
       for (int c = 0;; c += 2) {
         const bool end = c >= nt;  // (behind the chunk's last face: only decisions, if any)
         const bool two = c + 1 < nt;
-        const float word =
-            reinterpret_cast<const float*>(&W.ftab[end ? 0 : c][0])[lane & (two ? 31 : 15)];
+        // (the round's two records, 64 bytes apart: one ds_read2_b32)
+        const float* recs = reinterpret_cast<const float*>(&W.ftab[end ? 0 : c][0]) + (lane & 15);
+        const float word = recs[0], word2 = recs[16];
         const float tn = end ? INFINITY : bcast_f(word, 3);
         // decide what is queued: full batches; or at a gap in depth when every ray has a hit or
         // a candidate (the walk may end here); or at the very end
@@ -2160,9 +2222,9 @@ __device__ __forceinline__ bool beam_pass(BeamLds<RT>& W, const BeamScene& g, co
         TFRT_WAVE_NOTE(2, two ? 2 : 1);
         int ja, jb = -1;
         float thia, thib = -INFINITY;
-        const bool keepa = on_face(word, 0, &ja, &thia);
+        const bool keepa = on_face(word, &ja, &thia);
         bool keepb = false;
-        if (two) keepb = on_face(word, 16, &jb, &thib);
+        if (two) keepb = on_face(word2, &jb, &thib);
         span = fmaxf(span, fmaxf(thia, thib));
         const unsigned long long kma = __ballot(keepa), kmb = __ballot(keepb);
         const int na = __popcll(kma);

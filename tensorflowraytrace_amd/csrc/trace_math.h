@@ -64,6 +64,20 @@ TFRT_HD TriHit exact_triangle(const double s[3], const double e[3], const double
   return o;
 }
 
+// nextafterf(x, +infinity) for every float, bit for bit, without the library's case analysis: the
+// neighbouring float is the neighbouring integer -- one up for a non-negative value, one down for
+// a negative one (x + 0 first: -0 counts as +0, whose neighbour is the smallest subnormal);
+// +infinity and NaN (neither is < infinity) stay what they are.
+TFRT_HD float next_up_f(float x) {
+  x += 0.0f;
+  unsigned b;
+  __builtin_memcpy(&b, &x, 4);
+  const unsigned up = b + (unsigned)(((int)b >> 31) | 1);   // (unsigned: a NaN may wrap around)
+  float y;
+  __builtin_memcpy(&y, &up, 4);
+  return x < INFINITY ? y : x;
+}
+
 // hit point = r1 - ray_u * (r1 - r2)      geometry.py:316-318
 TFRT_HD void hit_point(const double s[3], const double e[3], double ray_u, double h[3]) {
 #pragma clang fp contract(off)

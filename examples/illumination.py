@@ -33,6 +33,15 @@ every ray towards the goal's quantile at its own rank, so the step has a signal 
 landing pattern and the goal do not overlap.  ``--generic`` as above.
 
     python examples/illumination.py --transport-error [--directions 8] [--bins 64] [--generic]
+
+``--combined`` runs both objectives as the two terms of one step, ``SumError([TransportError,
+DensityError])``: transport first -- it still points home where the histogram's gradient vanishes
+--, density for the detail.  ``set_weights`` moves the balance from the one to the other as the run
+goes; the weights live in a device buffer, so the replayed graph sees them without a re-capture.
+One trace, two error evaluations, one combination and one reverse sweep per step; both terms'
+own errors are printed.
+
+    python examples/illumination.py --combined [--directions 8] [--bins 64] [--generic]
 """
 import argparse
 import os
@@ -85,8 +94,10 @@ def lambertian(src):
 
 def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, magnification=1.0,
           object_size=0.2, lens_aperature=1.0, rowwise=True, density_error=False, bins=64,
-          lambertian_weights=False, transport_error=False, directions=8, **engine_kw):
-    density_error = density_error or transport_error      # (the same scene: no ranks ride along)
+          lambertian_weights=False, transport_error=False, directions=8, combined=False,
+          **engine_kw):
+    # (the same scene: no ranks ride along)
+    density_error = density_error or transport_error or combined
     limits = ((-object_size, object_size, DENSITY_CELLS), (-object_size, object_size, DENSITY_CELLS))
     start_density = distributions.ArbitraryDistribution(two_bumps(object_size), limits)
     goal_density = distributions.ArbitraryDistribution(lambda gx, gy: np.ones_like(gx), limits)
@@ -131,7 +142,16 @@ def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, magnificat
     trace_engine.validate_system()
 
     m = magnification
-    if transport_error:
+    if combined:
+        # both objectives of the flags below, over the same goal and domain
+        size = abs(m) * object_size
+        half = 1.25 * size
+        goal, domain = even_square(size, half, bins), ((-half, half), (-half, half))
+        error_function = optimizer.SumError([
+            optimizer.TransportError(("y_end", "z_end"), goal, domain, directions=directions),
+            optimizer.DensityError(("y_end", "z_end"), goal, domain,
+                                   oob_weight=1.0 / (ray_count * size ** 2))])
+    elif transport_error:
         # the goal and the domain of --density-error; rays beyond the margin need no penalty,
         # their rank pulls them in
         size = abs(m) * object_size
@@ -158,7 +178,11 @@ def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, magnificat
 
 def run(ray_count=20000, steps=30, lens_res_scale=0.12, host=False, verbose=True,
         density_error=False, bins=64, generic=False, splat_variant=0, lambertian_weights=False,
-        transport_error=False, directions=8):
+        transport_error=False, directions=8, combined=False):
+    if combined:
+        if density_error or transport_error or lambertian_weights or host:
+            raise ValueError("--combined runs both objectives itself: no other objective flag")
+        return run_combined(ray_count, steps, lens_res_scale, verbose, bins, generic, directions)
     if lambertian_weights and (transport_error or not density_error):
         raise ValueError("--lambertian-weights weighs a DensityError: it needs --density-error")
     if transport_error and density_error:
@@ -201,6 +225,50 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, host=False, verbose=True
         distributions.set_device_random(True)
 
 
+def transport_weight(erf, ray_count):
+    """The weight that gives a TransportError, as a term beside a DensityError stepped with
+    DENSITY_LEARNING_RATE, the step it takes alone in ``run``."""
+    width = erf.domain[0][1] - erf.domain[0][0]
+    alone = 2e-5 * (20000 / ray_count) * width ** 2 / erf.n_directions
+    return alone / DENSITY_LEARNING_RATE
+
+
+def run_combined(ray_count=20000, steps=30, lens_res_scale=0.12, verbose=True, bins=64,
+                 generic=False, directions=8):
+    """``--combined``: SumError([TransportError, DensityError]), the balance moved from transport
+    (nine tenths of its own step, a tenth of the density's) to density (the reverse) across the
+    run."""
+    s = build(ray_count, lens_res_scale, bins=bins, directions=directions, combined=True)
+    erf = s["error_function"]
+    w_t = transport_weight(erf.terms[0], ray_count)
+    opt = optimizer.SGD_Optimizer(s["engine"], s["lens"].parameters, erf, 3,
+                                  learning_rate=DENSITY_LEARNING_RATE, grad_clip=1.0,
+                                  fused=False if generic else "auto")
+    opt.suppress_warnings = True
+    errors, times, transport, density, merit = [], [], [], [], []
+    for step in range(steps):
+        a = step / (steps - 1) if steps > 1 else 0.0
+        erf.set_weights([w_t * (1.0 - 0.9 * a), 0.1 + 0.9 * a])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        errors.append(float(opt.single_step(s["accumulator"] if step < steps // 2 else None)))
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+        last = erf.last_errors.cpu()
+        transport.append(float(last[0, 2]))
+        density.append(float(last[1, 0]))
+        # one number for the run, whatever the balance was: both terms at their full weights
+        merit.append(w_t * float(last[0, 0]) + float(last[1, 0]))
+        if verbose and (step % 5 == 0 or step == steps - 1):
+            print(f"step {step:4d}: transport error (mean term) {transport[-1]:.6g}  density error "
+                  f"{density[-1]:.6g}  weighted sum {errors[-1]:.6g}  ({1e3 * times[-1]:.2f} ms)")
+    fused = opt._fused_step
+    s.update(errors=errors, times=times, transport=transport, density=density, merit=merit,
+             device_source=s["source"]._device_program() is not None,
+             graph_replays=0 if fused is None else fused.graph_replays)
+    return s
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--rays", type=int, default=20000)
@@ -220,15 +288,24 @@ if __name__ == "__main__":
                     help="tfrt_density_error's splat: 0 by the bin count, 1 LDS histogram, 2 global atomics")
     ap.add_argument("--lambertian-weights", action="store_true",
                     help="with --density-error: every ray carries cos theta of its start direction")
+    ap.add_argument("--combined", action="store_true",
+                    help="both objectives on one step: SumError([TransportError, DensityError])")
     a = ap.parse_args()
     out = run(a.rays, a.steps, a.edge, host=a.host, density_error=a.density_error, bins=a.bins,
               generic=a.generic, splat_variant=a.splat_variant,
               lambertian_weights=a.lambertian_weights, transport_error=a.transport_error,
-              directions=a.directions)
+              directions=a.directions, combined=a.combined)
     tail = sorted(out["times"][len(out["times"]) // 2:])
     print(f"source on the device: {out['device_source']}; steps replayed from the graph: "
           f"{out['graph_replays']} of {a.steps}; median step of the second half: "
           f"{1e3 * tail[len(tail) // 2]:.3f} ms")
+    if a.combined:
+        print(f"transport error (mean term): first {out['transport'][0]:.6g} -> last "
+              f"{out['transport'][-1]:.6g}")
+        print(f"density error: first {out['density'][0]:.6g} -> last {out['density'][-1]:.6g}")
+        print(f"combined error at full weights: first {out['merit'][0]:.6g} -> last "
+              f"{out['merit'][-1]:.6g}")
+        sys.exit(0)
     name = "transport error" if a.transport_error else \
         "density error" if a.density_error else "mean squared illumination error"
     print(f"{name}: first {out['errors'][0]:.6g} -> last {out['errors'][-1]:.6g}")

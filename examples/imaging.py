@@ -24,6 +24,15 @@ fields (the directions are re-drawn at every step, so are the weights).  The spo
 weighted one: centroid, RMS size and gradient.
 
     python examples/imaging.py [--rays 20000] [--steps 30] [--generic] [--adam] [--apodize SIGMA]
+
+``--magnification M`` pins what the ``SpotError`` leaves to the lens: the image of an object point
+at (y, z) must lie at (-M y, -M z).  The error is then a ``SumError`` of two terms on one step,
+``SumError([SpotError, GoalError(("y_end", "z_end"), -M * object_coords)], reduce="mean")`` -- the
+mean squared spot radius plus the mean squared distance to the image point, the error of the
+reference's dev/hexalens.py --, one trace, two error evaluations, one combination and one reverse
+sweep, replayed from the same graph.
+
+    python examples/imaging.py --magnification 1.0 [--rays 20000] [--steps 30] [--generic]
 """
 import argparse
 import math
@@ -47,6 +56,8 @@ import tfrt.optimizer as optimizer            # noqa: E402
 import tfrt.sources as sources                # noqa: E402
 
 LEARNING_RATE = 2e-5     # at 20,000 rays
+MEAN_LEARNING_RATE = 0.4  # --magnification: LEARNING_RATE * 20,000 rays * 2 terms per ray, halved
+                          # because two terms pull
 HALF_DOMAIN = 3.0        # the target region: the unfocused cone of a ray bundle has radius ~1.6
 
 
@@ -72,7 +83,7 @@ def gaussian_pupil(sigma, cone):
 
 
 def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, target_distance=10.0,
-          object_size=0.2, lens_aperature=1.0, apodize=None):
+          object_size=0.2, lens_aperature=1.0, apodize=None, magnification=None):
     points = letter_f(object_size)
     P = points.shape[0]
     A = max(ray_count // P, 2)
@@ -118,25 +129,37 @@ def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, target_dis
     error_function = optimizer.SpotError(
         ("y_end", "z_end"), labels, ((-HALF_DOMAIN, HALF_DOMAIN), (-HALF_DOMAIN, HALF_DOMAIN)),
         oob_weight=1.0, weights=None if apodize is None else gaussian_pupil(apodize, cone))
+    spot = error_function
+    if magnification is not None:
+        # ray i leaves object point i mod P whatever direction is drawn for it: the image points
+        # are a fixed table with one row per source ray
+        image = -float(magnification) * np.tile(points, (A, 1))[:, 1:]
+        error_function = optimizer.SumError(
+            [spot, optimizer.GoalError(("y_end", "z_end"),
+                                       torch.as_tensor(image).to(lens.parameters[0].device))],
+            reduce="mean")
     return dict(engine=trace_engine, system=system, lens=lens, source=source, n_rays=n_rays,
-                n_points=P, error_function=error_function, accumulator=accumulator)
+                n_points=P, error_function=error_function, spot=spot, accumulator=accumulator)
 
 
 def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=False, verbose=True,
-        learning_rate=None, apodize=None):
-    s = build(ray_count, lens_res_scale, apodize=apodize)
-    erf = s["error_function"]
+        learning_rate=None, apodize=None, magnification=None):
+    s = build(ray_count, lens_res_scale, apodize=apodize, magnification=magnification)
+    combined, erf = s["error_function"], s["spot"]
     if learning_rate is None:
         # (the error is a sum over the rays: the step size goes with 1 / rays)
         learning_rate = LEARNING_RATE * (20000 / s["n_rays"])
+        if magnification is not None:
+            # (a mean over two terms per ray: the same step per ray as the sum's)
+            learning_rate = MEAN_LEARNING_RATE
     kw = dict(learning_rate=learning_rate, grad_clip=1.0, fused=False if generic else "auto")
     if adam:
-        opt = optimizer.Adam_Optimizer(s["engine"], s["lens"].parameters, erf, 3,
+        opt = optimizer.Adam_Optimizer(s["engine"], s["lens"].parameters, combined, 3,
                                        adam_learning_rate=3e-4, **kw)
     else:
-        opt = optimizer.SGD_Optimizer(s["engine"], s["lens"].parameters, erf, 3, **kw)
+        opt = optimizer.SGD_Optimizer(s["engine"], s["lens"].parameters, combined, 3, **kw)
     opt.suppress_warnings = True
-    rms, times = [], []
+    rms, times, errors, place = [], [], [], []
     for step in range(steps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -149,14 +172,22 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=Fals
             # (weighted records: W = sum wq in units of 2^-wbits, the ray count in slot 5)
             inside = int(erf.last_acc[:, 5].sum())
             light = math.ldexp(int(erf.last_acc[:, 0].sum()), -erf.graph_key()[-1])
-        error_sum = mean * float(opt.last_error_terms)
+        errors.append(mean)
+        if magnification is None:
+            error_sum = mean * float(opt.last_error_terms)
+        else:
+            # (the terms' own triples {sum, terms, mean} of the step)
+            error_sum = float(combined.last_errors[0, 0])
+            place.append(float(combined.last_errors[1, 2]))
         rms.append(math.sqrt(error_sum / light) if inside else float("nan"))
         if verbose and (step % 5 == 0 or step == steps - 1):
-            print(f"step {step:4d}: rms spot {rms[-1]:.6g}  ({inside} rays inside, "
+            extra = "" if magnification is None else \
+                f"  mean squared image distance {place[-1]:.6g}  combined {mean:.6g}"
+            print(f"step {step:4d}: rms spot {rms[-1]:.6g}{extra}  ({inside} rays inside, "
                   f"{1e3 * times[-1]:.2f} ms)")
     fused = opt._fused_step
-    s.update(rms=rms, times=times, graph_replays=0 if fused is None else fused.graph_replays,
-             centroids=erf.centroids())
+    s.update(rms=rms, times=times, errors=errors, place=place,
+             graph_replays=0 if fused is None else fused.graph_replays, centroids=erf.centroids())
     return s
 
 
@@ -171,11 +202,17 @@ if __name__ == "__main__":
                     help=f"learning rate (default {LEARNING_RATE} * 20000 / rays)")
     ap.add_argument("--apodize", type=float, default=None, metavar="SIGMA",
                     help="Gaussian pupil weights, SIGMA in units of the cone that fills the lens")
+    ap.add_argument("--magnification", type=float, default=None, metavar="M",
+                    help="pin the image of (y, z) to (-M y, -M z): SumError([SpotError, GoalError])")
     a = ap.parse_args()
     out = run(a.rays, a.steps, a.edge, generic=a.generic, adam=a.adam, learning_rate=a.lr,
-              apodize=a.apodize)
+              apodize=a.apodize, magnification=a.magnification)
     tail = sorted(out["times"][len(out["times"]) // 2:])
     print(f"{out['n_points']} object points, {out['n_rays']} rays; steps replayed from the graph: "
           f"{out['graph_replays']} of {a.steps}; median step of the second half: "
           f"{1e3 * tail[len(tail) // 2]:.3f} ms")
     print(f"rms spot: first {out['rms'][0]:.6g} last {out['rms'][-1]:.6g}")
+    if a.magnification is not None:
+        print(f"mean squared image distance: first {out['place'][0]:.6g} last "
+              f"{out['place'][-1]:.6g}")
+        print(f"combined error: first {out['errors'][0]:.6g} last {out['errors'][-1]:.6g}")

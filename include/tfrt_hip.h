@@ -864,6 +864,88 @@ int tfrt_transport_error(const void* rows, int64_t stride, int64_t n, int32_t st
                          double* grad, int64_t grad_stride, double* err, int32_t* rank2,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* GoalError on the fixed-shape columns of an in-place trace (tfrt_scene3d.in_place == 2: the
+ * finished rows at the rays' own columns, a mask in the place of a ray count) -- the form that can
+ * be added to a coupled error of the same step (tfrt_error_combine).  Two launches (the columns,
+ * the sum), no host read, no allocation, no atomics: captured with the rest of a step.
+ *
+ * A column i COUNTS if mask is NULL or mask[i] >= 0, and its source ray s = perm ? perm[i] : i lies
+ * inside [0, n_source); a column whose s lies outside does not count and nothing is read out of
+ * bounds, whatever perm holds.  For a counting column and each field c, every operation an IEEE
+ * f64 operation rounded on its own (no contraction):
+ *   o = (double) rows[fields[c]][i],  d = o - goal(c, s),  the error term is d * d,
+ *   grad[fields[c]][i] = 2 * d
+ * with goal(c, s) = goal[c * goal_stride + s * goal_ray_stride] (both layouts of
+ * tfrt_goal_error3d).  The rows named by `fields` are written for EVERY column, 0.0 where a column
+ * does not count; no other row is written.
+ *   error_out = {sum, terms, terms > 0 ? sum / terms : NaN},  terms = n_fields * counting columns.
+ * The sum has a fixed shape and order -- per lane over its columns (grid-stride), a fixed-shape
+ * workgroup sum, then one workgroup over the workgroups' partial sums in index order --: two runs
+ * give the same bits.
+ *
+ *   rows, stride, n   the ray block in the state dtype (TFRT_F32 / TFRT_F64 / TFRT_F16), entry
+ *                     (row, i) at rows[row * stride + i]; 0 <= n < 2^31 (n == 0 is legal:
+ *                     {0, 0, NaN})
+ *   n_rows            4 or 6: the rows of the block (2-D / 3-D geometry)
+ *   mask              n int32 or NULL (tfrt_ray_out.face of the in-place trace)
+ *   perm, n_source    n int32, the source ray of column i, or NULL: column i is source ray i;
+ *                     0 <= n_source < 2^31, as for tfrt_spot_error
+ *   fields, n_fields  1 .. n_rows distinct rows in [0, n_rows), passed as tfrt_goal_error3d
+ *                     passes them
+ *   goal              f64 table with one entry per field and SOURCE ray
+ *   grad, grad_stride f64 block, entry (row, i) at grad[row * grad_stride + i]
+ *   workspace         tfrt_goal_error_columns_workspace_bytes(n) bytes (0: bad arguments)
+ * Bad arguments are refused with TFRT_E_BADARG / TFRT_E_WORKSPACE before any launch.
+ */
+size_t tfrt_goal_error_columns_workspace_bytes(int64_t n);
+int tfrt_goal_error_columns(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                            int32_t n_rows, const int32_t* mask, const int32_t* perm,
+                            int64_t n_source, const int32_t* fields, int32_t n_fields,
+                            const double* goal, int64_t goal_stride, int64_t goal_ray_stride,
+                            double* grad, int64_t grad_stride, double* error_out, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
+/* SumError: the weighted sum of K error terms of one step, 1 <= K <= 8, in ONE launch.  Every term
+ * has left a gradient seed block on the same columns and its error triple on the device; the
+ * reverse sweep is linear in its seed, so the combined seed block and the combined error are all
+ * a step of the sum needs.  The descriptors are a host array copied into the kernel arguments.
+ *
+ *   c_k = weights[k]                                          reduce == 0 (sum)
+ *   c_k = terms_k > 0 ? weights[k] / terms_k : 0.0            reduce == 1 (mean),
+ * terms_k = terms[k].error[1] read on the device: no ray count ever reaches the host.
+ * Gradients, for every row r < n_rows and column i < n: the terms whose row_mask has bit r, in
+ * index order, acc = c_k * g_k[r][i] for the first, acc = acc + c_k * g_k[r][i] for every later
+ * one, every product and every sum rounded on its own; a row named by no term is written 0.0.
+ * The first product is not added to a zero: one term with weight 1.0 comes back with its own
+ * bits, signed zeros included.
+ * Error: E = c_0 * e_0[0], then E = E + c_k * e_k[0] in index order; error_out = {E, 1, E} -- one
+ * error term, as tfrt_density_error reports itself.  coeff_out[k] = c_k.  One thread of the
+ * launch writes error_out and coeff_out; they depend only on what earlier launches wrote.
+ *
+ *   terms[k].grad      f64 block, entry (row, i) at grad[row * stride + i]; NULL in EVERY term (or
+ *                      n == 0): only the errors are combined -- the step without a reverse sweep
+ *   terms[k].stride    n <= stride < 2^31
+ *   terms[k].row_mask  bit r: the term has written row r of its block (no bit at n_rows or above)
+ *   terms[k].error     the term's 3 f64 {sum, terms, mean} on the device
+ *   weights            n_terms f64 on the device; reduce: 0 = sum, 1 = mean
+ *   n, n_rows          0 <= n < 2^31 columns, 4 or 6 rows
+ *   grad_out           f64 block of n_rows rows of out_stride; it must not overlap a term's block
+ *                      (n_rows rows of its stride): TFRT_E_BADARG
+ *   error_out          3 f64;  coeff_out: n_terms f64
+ * A lane takes two neighbouring columns with one 16-byte access per term and row where every
+ * block is 16-byte aligned and every stride even, one column otherwise; the bits do not depend on
+ * which.  (sum_k rows_k + n_rows) * 8 B * n of traffic, no LDS, no atomics, no host read.
+ */
+typedef struct tfrt_combine_term {
+  const double* grad;
+  int64_t stride;
+  uint32_t row_mask;
+  const double* error;
+} tfrt_combine_term;
+int tfrt_error_combine(const tfrt_combine_term* terms, int32_t n_terms, const double* weights,
+                       int32_t reduce, int64_t n, int32_t n_rows, double* grad_out,
+                       int64_t out_stride, double* error_out, double* coeff_out, void* stream);
+
 /* tfrt_goal_error3d_deferred and tfrt_trace3d_backward in ONE launch, for a trace over coherent
  * rays (tfrt_scene3d.coherent_rays, not deterministic, max_passes <= 8; TFRT_E_UNSUPPORTED
  * otherwise -- call the two entry points instead): the lane that walks a finished ray's chain of

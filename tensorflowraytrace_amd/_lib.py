@@ -84,6 +84,15 @@ class GoalPending(ctypes.Structure):
                 ("n_faces", ctypes.c_int64), ("counts_tail", ctypes.c_void_p)]
 
 
+COMBINE_MAX_TERMS = 8
+
+
+class CombineTerm(ctypes.Structure):
+    """tfrt_combine_term (include/tfrt_hip.h)."""
+    _fields_ = [("grad", ctypes.c_void_p), ("stride", ctypes.c_int64),
+                ("row_mask", ctypes.c_uint32), ("error", ctypes.c_void_p)]
+
+
 class RayOut(ctypes.Structure):
     """struct tfrt_ray_out"""
     _fields_ = [("rays", c_vp), ("ray_id", c_vp), ("face", c_vp), ("capacity", c_i64)]
@@ -226,6 +235,13 @@ SIGNATURES = {
         c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_i32, c_i32,                 # columns, mask, rows
         c_f64, c_f64, c_f64, c_f64, c_vp, c_vp, c_i32, c_i32,                 # domain, cs, tables, Q, K
         c_vp, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "tfrt_goal_error_columns_workspace_bytes": (c_sz, [c_i64]),
+    "tfrt_goal_error_columns": (c_i32, [
+        c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64,                  # columns, mask, perm
+        c_vp, c_i32, c_vp, c_i64, c_i64,                                      # fields, goal
+        c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "tfrt_error_combine": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp,
+                                   c_vp]),
     "tfrt_trace3d_backward_goal_workspace_bytes": (c_sz, [c_i64]),
     "tfrt_trace3d_backward_goal": (c_i32, [
         c_vp, c_i64, c_i64, c_vp, c_f64, c_f64, c_i32, c_i32,          # rays, scene, lengths, P, dtype

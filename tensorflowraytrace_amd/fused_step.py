@@ -39,6 +39,9 @@ launches: clear, splat, bins, seed) in the place of ``fn`` and its autograd; a `
 of one group must meet in one point -- likewise with ``tfrt_spot_error`` (clear, accumulate, seed,
 finish); a ``TransportError`` -- the same target density by sliced optimal transport -- with
 ``tfrt_transport_error`` (per direction keys, radix sort, sorted keys, ranks; then seed and finish).
+A ``SumError`` -- a weighted sum of such terms and of ``GoalError``s -- takes ``_rowwise3d`` as well:
+every term's launches into a seed block of its own (a ``GoalError`` through
+``tfrt_goal_error_columns``), then ONE ``tfrt_error_combine`` for the step's seed block and error.
 
 The four bodies share one skeleton: ``_enqueue_gradient`` does what comes before the trace, the
 body its launches over a ``_StepState``, ``_publish_lazily`` and ``_enqueue_apply`` what comes after.
@@ -1035,6 +1038,137 @@ class _SpotTerms(torch.autograd.Function):
 _COUPLED = (DensityError, SpotError, TransportError)
 
 
+class SumError:
+    """A weighted sum of error terms on ONE step: ``error = sum_k c_k * term_k``.  A real design
+    is never one term: transport to find the target and density for the detail, a spot size with
+    a magnification pinned by a goal, a near field and a far field at once.  Every term reads the
+    same finished rays of one trace and the reverse sweep is linear in its seed, so the combined
+    step is one trace, K error evaluations, one combination and one reverse sweep.
+
+    ``terms``: 1 to 8 distinct instances of ``GoalError``, ``DensityError``, ``SpotError`` or
+    ``TransportError``; a ``RowwiseError``, a nested ``SumError`` or the same object twice is a
+    ValueError.  ``weights``: K finite values >= 0, default all ones, kept as the (K,) float64
+    device tensor ``weights``; ``set_weights(values)`` validates on the host and overwrites that
+    buffer in place, so a replayed graph sees the new values without a re-capture (as
+    ``TransportError.set_goal``).  A weight of 0 switches a term off for a phase; the term is
+    still evaluated.  ``reduce``: ``"sum"``, ``c_k = w_k`` and ``term_k`` the term's error sum; or
+    ``"mean"``, ``c_k = w_k / terms_k`` with ``terms_k`` the term's own count of error terms
+    (0.0 for a term without any), read on the device.  Every product and every sum is rounded on
+    its own, the terms in index order (tfrt_error_combine); the sum reports itself as ONE error
+    term, ``{E, 1, E}``, as a ``DensityError`` does.
+
+    After an evaluation ``last_errors`` is the (K, 3) tensor of the terms' own triples {sum, terms,
+    mean} and ``last_coefficients`` the (K,) ``c_k``; each term keeps its own ``last_hq`` /
+    ``centroids()`` / ``last_rank2`` as when it runs alone.
+
+    It is an ordinary ``error_function(engine)`` -- the generic path returns the (1,) tensor
+    ``sum_k c_k * term_k(engine).sum()`` (``terms_k = numel``) under torch autograd, which serves
+    2-D engines, fewer than 4,096 rays, ``deterministic=True`` and sources not traced in place.
+    On a 3-D engine that traces its source in place the optimiser runs it on the fused,
+    graph-replayed step under the conditions of a ``DensityError``: every term evaluates into a
+    seed block of its own (a ``GoalError`` through tfrt_goal_error_columns, its goal row looked up
+    through the trace's order inside the kernel), and one tfrt_error_combine launch writes the
+    step's seed block and error.  One process."""
+
+    def __init__(self, terms, weights=None, reduce="sum"):
+        from . import config
+        try:
+            terms = tuple(terms)
+        except TypeError as e:
+            raise ValueError("SumError: terms must be a sequence of error terms") from e
+        if not 1 <= len(terms) <= ops.COMBINE_MAX_TERMS:
+            raise ValueError(f"SumError: 1 .. {ops.COMBINE_MAX_TERMS} terms, got {len(terms)}")
+        for t in terms:
+            if isinstance(t, SumError):
+                raise ValueError("SumError: a nested SumError is not supported -- list its terms "
+                                 "(and multiply the weights) instead")
+            if isinstance(t, RowwiseError):
+                raise ValueError("SumError: a RowwiseError cannot be a term (its error is torch "
+                                 "code of its own); state it as a GoalError")
+            if not isinstance(t, (GoalError,) + _COUPLED):
+                raise ValueError("SumError: terms must be GoalError, DensityError, SpotError or "
+                                 f"TransportError instances, got {type(t).__name__}")
+        if len(set(id(t) for t in terms)) != len(terms):
+            raise ValueError("SumError: the same term object is listed twice (a term keeps the "
+                             "buffers of its last evaluation); make a second instance")
+        if reduce not in ("sum", "mean"):
+            raise ValueError(f"SumError: reduce must be 'sum' or 'mean', got {reduce!r}")
+        self.terms, self.reduce = terms, reduce
+        values = self._as_values(len(terms), [1.0] * len(terms) if weights is None else weights)
+        self.weights = torch.as_tensor(values).to(config.get_device())
+        # every term's rows, in term order: a step's buffers are keyed on them
+        self.rows = [r for t in terms for r in t.rows]
+        self.fields = tuple(t.fields for t in terms)
+        self.last_errors = self.last_coefficients = None
+
+    @staticmethod
+    def _as_values(K, weights):
+        try:
+            w = np.asarray(weights.detach().cpu() if isinstance(weights, torch.Tensor)
+                           else weights, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"SumError: weights must be {K} numbers, got {weights!r}") from e
+        if w.shape != (K,):
+            raise ValueError(f"SumError: {K} weights for {K} terms, got shape {w.shape}")
+        if not np.isfinite(w).all() or (w < 0).any():
+            raise ValueError(f"SumError: weights must be finite and >= 0, got {w.tolist()}")
+        return np.ascontiguousarray(w)
+
+    def set_weights(self, values):
+        """Other weights, checked on the host and copied into the device buffer there is."""
+        self.weights.copy_(torch.as_tensor(self._as_values(len(self.terms), values)))
+
+    def weights_on(self, device):
+        """The weight buffer on ``device`` (moved once; a new buffer re-captures a graph)."""
+        if self.weights.device != device:
+            self.weights = self.weights.to(device)
+        return self.weights
+
+    def rows_for(self, dimension):
+        return [r for t in self.terms for r in t.rows_for(dimension)]
+
+    def graph_key(self):
+        """What a captured step has baked in: the terms' keys, the weight buffer's address and
+        ``reduce``."""
+        return (tuple((id(t), t.graph_key() if isinstance(t, _COUPLED)
+                       else (id(t.goal), t.fields, t.rowwise)) for t in self.terms),
+                self.weights.data_ptr(), self.reduce)
+
+    def __call__(self, engine):
+        """The error as a (1,) tensor through the generic path: the terms called one by one, then
+        tfrt_error_combine's operations in its order as torch ops."""
+        total, triples, coeffs = None, [], []
+        for k, term in enumerate(self.terms):
+            e = term(engine)
+            s = e.sum().double()
+            w = self.weights_on(s.device)[k]
+            if self.reduce == "sum":
+                c = w
+            else:
+                c = w / float(e.numel()) if e.numel() > 0 else torch.zeros_like(w)
+            p = c * s
+            total = p if total is None else total + p
+            with torch.no_grad():
+                n = torch.full_like(w, float(e.numel()))
+                triples.append(torch.stack([s.detach(), n, s.detach() / n if e.numel() > 0
+                                            else torch.full_like(w, float("nan"))]))
+                coeffs.append(c.detach())
+        self.last_errors, self.last_coefficients = torch.stack(triples), torch.stack(coeffs)
+        return total.reshape(1)
+
+
+class _TermState:
+    """What one term of a SumError owns in a step's state: its seed block and error triple, and
+    the buffers its kind of error keeps (the names a ``_StepState`` has for a single error)."""
+    __slots__ = ("g_fin", "err", "row_mask", "density_ws", "hq", "spot_ws", "acc", "transport_ws",
+                 "rank2", "goal_ws")
+
+    def __init__(self, g_fin, err, row_mask):
+        for name in self.__slots__:
+            setattr(self, name, None)
+        self.g_fin, self.err, self.row_mask = g_fin, err, row_mask
+
+
 class _RowFields:
     """Field mapping handed to a RowwiseError on the fixed-shape path: geometry = the rows of the
     in-place finished block, everything else = the source's own fields in the trace's order."""
@@ -1126,6 +1260,7 @@ class _StepState:
         "density_ws", "hq",                                  # a DensityError's workspace and histogram
         "spot_ws", "acc",                                    # a SpotError's workspace and group records
         "transport_ws", "rank2",                             # a TransportError's workspace and ranks
+        "terms", "terms_key", "term_errs", "coeff",          # a SumError's per-term states
         "chain_ws", "inherited",                             # made on first use
         "sched", "sched_key", "sched_checked",               # the in-place trace's wavefront schedule
         "block", "stream", "perm", "inplace")                # of the last enqueued step
@@ -1172,7 +1307,8 @@ class _StepState:
 class FusedStep:
     """Runs ``SGD_Optimizer.single_step`` for a ``GoalError`` or a ``RowwiseError`` as a fixed
     launch sequence, on 3-D engines and on 2-D ones (one process), and for a ``DensityError``, a
-    ``SpotError`` or a ``TransportError`` on 3-D engines; see the module docstring.
+    ``SpotError``, a ``TransportError`` or a ``SumError`` of them on 3-D engines; see the module
+    docstring.
     One instance per optimizer."""
 
     # coherent rays: error, gradient seed and reverse sweep as ONE launch (tfrt_trace3d_backward_goal);
@@ -1223,12 +1359,14 @@ class FusedStep:
     def eligible(optimizer, args, kwargs):
         eng = optimizer.engine
         erf = optimizer.error_function
-        if not isinstance(erf, (GoalError, RowwiseError) + _COUPLED) or args or kwargs:
+        if not isinstance(erf, (GoalError, RowwiseError, SumError) + _COUPLED) or args or kwargs:
             return False
-        if (isinstance(erf, (RowwiseError,) + _COUPLED) and eng.dimension == 3
+        if isinstance(erf, SumError) and eng.dimension != 3:
+            return False            # (a sum of terms takes the generic path on a 2-D engine)
+        if (isinstance(erf, (RowwiseError, SumError) + _COUPLED) and eng.dimension == 3
                 and not FusedStep.rowwise_ready(eng)):
             return False
-        if isinstance(erf, _COUPLED) and tdist.is_distributed():
+        if isinstance(erf, (SumError,) + _COUPLED) and tdist.is_distributed():
             return False            # (the histogram / the centroids / the ranks couple the rays: one process)
         if not bool(eng.optical_system):
             return False
@@ -1386,7 +1524,7 @@ class FusedStep:
             raise RuntimeError("FusedStep: the optical system has no source rays")
         inputs = eng._trace_inputs(src)
         P, flags = int(opt.trace_depth), eng._flags() | _lib.COMPILE_FINISHED
-        rowwise = isinstance(opt.error_function, (RowwiseError,) + _COUPLED)
+        rowwise = isinstance(opt.error_function, (RowwiseError, SumError) + _COUPLED)
         if eng.dimension == 2:
             body = self._rowwise2d if rowwise else self._goal2d
         else:
@@ -1603,8 +1741,9 @@ class FusedStep:
     def _rowwise3d(self, src, inputs, tap_log, P, flags):
         """In-place trace with the finished rows at the rays' own columns -> ``erf.fn`` on
         fixed-shape tensors + its autograd (torch), or a DensityError's / a SpotError's / a
-        TransportError's launches (tfrt_density_error, tfrt_spot_error, tfrt_transport_error) ->
-        reverse sweep.  No ray count is read; everything is capturable."""
+        TransportError's launches (tfrt_density_error, tfrt_spot_error, tfrt_transport_error), or
+        a SumError's terms and tfrt_error_combine -> reverse sweep.  No ray count is read;
+        everything is capturable."""
         eng = self.opt.engine
         block, scene, fv = inputs
         perm = eng._trace_perm
@@ -1636,13 +1775,14 @@ class FusedStep:
         # the same values as the forward)
         with _override(sc, in_place=2, face_sums=1 if four else 0, **clear):
             self._trace_forward(st, sc, st.row_outs)
-            if isinstance(self.opt.error_function, _COUPLED):
-                if isinstance(self.opt.error_function, DensityError):
-                    g64 = self._density_seeds3d(st, src, perm)
-                elif isinstance(self.opt.error_function, TransportError):
-                    g64 = self._transport_seeds3d(st)
+            erf = self.opt.error_function
+            if isinstance(erf, (SumError,) + _COUPLED):
+                if isinstance(erf, SumError):
+                    g64 = self._sum_seeds3d(st, src, perm, erf, need_back)
                 else:
-                    g64 = self._spot_seeds3d(st, src, perm)
+                    g64 = self._term_seeds3d(st, src, perm, erf, st)
+                with torch.no_grad():
+                    self.tests_total += st.row_passes[:st.N].sum() * st.M
                 if not need_back:
                     g64 = None
             else:
@@ -1654,75 +1794,124 @@ class FusedStep:
                     grads = self._parameter_gradients(*self._outs3d(fv, st, index), tap_log)
         return grads, st
 
-    def _density_seeds3d(self, st, src, perm):
+    def _term_seeds3d(self, st, src, perm, erf, hold):
+        """The launches of one built-in error ``erf`` on the fixed-shape columns of ``st``, into
+        the seed block, the error triple and the buffers of ``hold``: the step's state itself for
+        a single error, a ``_TermState`` for a term of a SumError.  Returns the seed block."""
+        if isinstance(erf, DensityError):
+            return self._density_seeds3d(st, src, perm, erf, hold)
+        if isinstance(erf, TransportError):
+            return self._transport_seeds3d(st, erf, hold)
+        if isinstance(erf, SpotError):
+            return self._spot_seeds3d(st, src, perm, erf, hold)
+        return self._goal_seeds3d(st, src, perm, erf, hold)
+
+    def _sum_seeds3d(self, st, src, perm, erf, need_back):
+        """A SumError on the fixed-shape columns: every term evaluates into a private, once-zeroed
+        (6, capN) seed block and its own triple -- coupled terms through their ``evaluate`` with
+        buffers of their own, GoalError terms through tfrt_goal_error_columns --, then ONE
+        tfrt_error_combine writes the step's seed block ``st.g_fin`` (all six rows, every column)
+        and ``st.err``; without a reverse sweep only the errors are combined.  Nothing is read
+        back: the coefficients of ``reduce="mean"`` come from the triples on the device."""
+        dev = st.rows.device
+        key = tuple(id(t) for t in erf.terms)
+        if st.terms is None or st.terms_key != key:
+            K = len(erf.terms)
+            st.term_errs = torch.zeros((K, 3), dtype=torch.float64, device=dev)
+            st.coeff = torch.zeros(K, dtype=torch.float64, device=dev)
+            st.terms = []
+            for k, t in enumerate(erf.terms):
+                mask = 0x3f if getattr(t, "has_direction", False) \
+                    else sum(1 << r for r in t.rows)
+                st.terms.append(_TermState(
+                    torch.zeros((6, st.capN), dtype=torch.float64, device=dev), st.term_errs[k],
+                    mask))
+            st.terms_key = key
+            self._graphs = None
+        for t, hold in zip(erf.terms, st.terms):
+            self._term_seeds3d(st, src, perm, t, hold)
+        ops.error_combine(
+            [(h.g_fin if need_back else None, h.row_mask, h.err) for h in st.terms],
+            erf.weights_on(dev), erf.reduce, n=st.N, n_rows=6, out=st.g_fin, err=st.err,
+            coeff=st.coeff)
+        erf.last_errors, erf.last_coefficients = st.term_errs, st.coeff
+        return st.g_fin
+
+    def _goal_seeds3d(self, st, src, perm, erf, hold):
+        """A GoalError term on the fixed-shape columns: tfrt_goal_error_columns reads ``st.rows``,
+        the mask ``st.row_face`` and the goal table in the source's order, which it looks up
+        through the trace's order ``perm`` itself (no permuted copy that could go stale when a
+        source is re-drawn and re-ordered inside the graph), and writes the fields' rows of the
+        term's seed block for every column."""
+        if hold.goal_ws is None:
+            wsb = _lib.lib().tfrt_goal_error_columns_workspace_bytes(st.N)
+            hold.goal_ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=st.rows.device)
+        # (the table in the layout the goal has: no transposed copy per step)
+        ops.goal_error_columns(st.rows[:, :st.N], erf.rows, erf.table(src, by_ray=True),
+                               mask=st.row_face, perm=perm, by_ray=True, grad=hold.g_fin,
+                               err=hold.err, workspace=hold.goal_ws)
+        return hold.g_fin
+
+    def _density_seeds3d(self, st, src, perm, erf, hold):
         """A DensityError on the fixed-shape columns: tfrt_density_error reads ``st.rows`` and the
         mask ``st.row_face`` -- with weights also the source's weight buffer through the trace's
         order ``perm``, inside the kernel, as a SpotError's labels -- and writes its rows of the persistent seed block for every column --
         the two rows of position fields (the other rows were zeroed when the state was made, and
         the field codes are part of its signature), all six with a direction field --, the error
-        into ``st.err`` and the histogram into ``st.hq``.  Returns the (6, capN) seed block."""
-        erf = self.opt.error_function
+        into ``hold.err`` and the histogram into ``hold.hq``.  Returns the (6, capN) seed block."""
         dev = st.rows.device
         goal = erf.goal_on(dev)
-        if st.hq is None or st.hq.shape != goal.shape:
+        if hold.hq is None or hold.hq.shape != goal.shape:
             nx, ny = goal.shape[-1], (goal.shape[0] if goal.dim() == 2 else 1)
             wsb = _lib.lib().tfrt_density_error_workspace_bytes(st.N, nx, ny)
-            st.density_ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
-            st.hq = torch.zeros(goal.shape, dtype=torch.int64, device=dev)
+            hold.density_ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+            hold.hq = torch.zeros(goal.shape, dtype=torch.int64, device=dev)
         rows = erf.rows
         erf.evaluate(st.rows[:, :st.N], rows[0], rows[1] if len(rows) == 2 else -1,
                      mask=st.row_face, dimension=3, weights=erf.weights_of(src), perm=perm,
-                     grad=st.g_fin, err=st.err, hq=st.hq, workspace=st.density_ws)
-        with torch.no_grad():
-            self.tests_total += st.row_passes[:st.N].sum() * st.M
-        return st.g_fin
+                     grad=hold.g_fin, err=hold.err, hq=hold.hq, workspace=hold.density_ws)
+        return hold.g_fin
 
-    def _transport_seeds3d(self, st):
+    def _transport_seeds3d(self, st, erf, hold):
         """A TransportError on the fixed-shape columns: tfrt_transport_error reads ``st.rows`` and
         the mask ``st.row_face`` and writes its two rows of the persistent seed block for every
-        column (the other rows were zeroed when the state was made), the error into ``st.err`` and
-        the ranks into ``st.rank2``; n_valid never leaves the device.  Returns the (6, capN) seed
-        block."""
-        erf = self.opt.error_function
+        column (the other rows were zeroed when the state was made), the error into ``hold.err``
+        and the ranks into ``hold.rank2``; n_valid never leaves the device.  Returns the
+        (6, capN) seed block."""
         dev = st.rows.device
         K = erf.n_directions
-        if st.rank2 is None or tuple(st.rank2.shape) != (K, st.N):
+        if hold.rank2 is None or tuple(hold.rank2.shape) != (K, st.N):
             wsb = _lib.lib().tfrt_transport_error_workspace_bytes(st.N, K)
-            st.transport_ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
-            st.rank2 = torch.zeros((K, st.N), dtype=torch.int32, device=dev)
+            hold.transport_ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+            hold.rank2 = torch.zeros((K, st.N), dtype=torch.int32, device=dev)
         rows = erf.rows
         erf.evaluate(st.rows[:, :st.N], rows[0], rows[1] if len(rows) == 2 else -1,
-                     mask=st.row_face, dimension=3, grad=st.g_fin, err=st.err, rank2=st.rank2,
-                     workspace=st.transport_ws)
-        with torch.no_grad():
-            self.tests_total += st.row_passes[:st.N].sum() * st.M
-        return st.g_fin
+                     mask=st.row_face, dimension=3, grad=hold.g_fin, err=hold.err,
+                     rank2=hold.rank2, workspace=hold.transport_ws)
+        return hold.g_fin
 
-    def _spot_seeds3d(self, st, src, perm):
+    def _spot_seeds3d(self, st, src, perm, erf, hold):
         """A SpotError on the fixed-shape columns: tfrt_spot_error reads ``st.rows``, the mask
         ``st.row_face``, the source's label buffer and the trace's order ``perm`` -- the kernel
         looks a column's label up itself, so no permuted copy can go stale when a source is
         re-drawn and re-ordered inside the graph -- and writes its rows of the persistent seed
         block for every column (two for position fields, the others zeroed when the state was
-        made; all six with a direction field), the error into ``st.err`` and the group records
-        into ``st.acc`` ((G, 4), with weights -- looked up like the labels -- (G, 8)).  Returns
+        made; all six with a direction field), the error into ``hold.err`` and the group records
+        into ``hold.acc`` ((G, 4), with weights -- looked up like the labels -- (G, 8)).  Returns
         the (6, capN) seed block."""
-        erf = self.opt.error_function
         dev = st.rows.device
         labels = erf.labels_of(src)
         weights = erf.weights_of(src)
         record = 4 if weights is None else 8
-        if st.acc is None or tuple(st.acc.shape) != (erf.n_groups, record):
+        if hold.acc is None or tuple(hold.acc.shape) != (erf.n_groups, record):
             wsb = _lib.lib().tfrt_spot_error_workspace_bytes(st.N, erf.n_groups)
-            st.spot_ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
-            st.acc = torch.zeros((erf.n_groups, record), dtype=torch.int64, device=dev)
+            hold.spot_ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+            hold.acc = torch.zeros((erf.n_groups, record), dtype=torch.int64, device=dev)
         rows = erf.rows
         erf.evaluate(st.rows[:, :st.N], rows[0], rows[1] if len(rows) == 2 else -1, labels,
-                     mask=st.row_face, perm=perm, dimension=3, weights=weights, grad=st.g_fin,
-                     err=st.err, acc=st.acc, workspace=st.spot_ws)
-        with torch.no_grad():
-            self.tests_total += st.row_passes[:st.N].sum() * st.M
-        return st.g_fin
+                     mask=st.row_face, perm=perm, dimension=3, weights=weights, grad=hold.g_fin,
+                     err=hold.err, acc=hold.acc, workspace=hold.spot_ws)
+        return hold.g_fin
 
     def _rowwise_seeds3d(self, st, src, perm, need_back):
         """A RowwiseError on the fixed-shape columns: ``fn`` and its autograd (torch), the masked
@@ -2139,7 +2328,7 @@ class FusedStep:
         in place is seen by replays, another buffer re-captures), its shape and the constants; a
         SpotError's: the label buffer's address and shape, G and the constants."""
         erf = self.opt.error_function
-        return erf.graph_key() if isinstance(erf, _COUPLED) else ()
+        return erf.graph_key() if isinstance(erf, (SumError,) + _COUPLED) else ()
 
     def _index_signature(self):
         """The refractive-index fields that take a gradient (boundary, field, identity of a tensor

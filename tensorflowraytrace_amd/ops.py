@@ -2026,6 +2026,200 @@ def _spot_error_cpu(rows, row_x, row_y, group, n_groups, grid, oob, mask, perm, 
     err[2] = e / n_terms if n_terms > 0 else float("nan")
 
 
+# ------------------------------------------------------- a sum of error terms (SumError)
+
+COMBINE_MAX_TERMS = _lib.COMBINE_MAX_TERMS
+
+
+def goal_error_columns(rows, fields, goal, mask=None, perm=None, by_ray=False, n_source=None,
+                       grad=None, err=None, workspace=None):
+    """tfrt_goal_error_columns: GoalError on fixed-shape columns.  ``rows``: the (4 or 6, n) ray
+    block (float32 / float64 / float16, contiguous columns, any row stride); ``fields``: the
+    distinct rows compared with the goal's columns; ``goal``: contiguous float64, (len(fields),
+    n_source) or -- ``by_ray`` -- (n_source, len(fields)), one entry per field and SOURCE ray;
+    ``mask``: optional int32, column i counts if mask[i] >= 0; ``perm``: optional int32 (n,), the
+    source ray of column i (None: column i is source ray i); a column whose source ray lies
+    outside [0, n_source) does not count (``n_source``: the goal's ray count unless given
+    smaller).  Returns (err {sum, terms, mean}, grad (rows, n) float64): the rows of ``fields`` are
+    written for every column (0.0 where it does not count), other rows only when ``grad`` is made
+    here (zeros).  ``grad``, ``err``, ``workspace`` (uint8): buffers to reuse -- with all three
+    given a CUDA call allocates nothing.
+
+    CUDA tensors run the kernels.  CPU tensors run a torch restatement with the same operations
+    per column, each rounded on its own (the gradient agrees bit for bit; the error sum is torch's
+    and agrees to rounding)."""
+    k, n = rows.shape
+    fields = [int(f) for f in fields]
+    nf = len(fields)
+    if k not in (4, 6) or not 1 <= nf <= k or any(not 0 <= f < k for f in fields) \
+            or len(set(fields)) != nf:
+        raise ValueError(f"goal_error_columns: a block of 4 or 6 rows and 1 .. rows distinct "
+                         f"fields inside it, got {k} rows and fields {fields}")
+    if goal.dtype != torch.float64 or goal.dim() != 2 or not goal.is_contiguous() \
+            or goal.shape[1 if by_ray else 0] != nf:
+        raise ValueError("goal_error_columns: goal must be contiguous float64 (fields, n_source), "
+                         "or (n_source, fields) with by_ray")
+    rays = goal.shape[0 if by_ray else 1]
+    n_source = rays if n_source is None else int(n_source)
+    if not 0 <= n_source <= rays:
+        raise ValueError(f"goal_error_columns: n_source must lie in 0 .. {rays}")
+    if mask is not None and (mask.dtype != torch.int32 or mask.numel() < n
+                             or not mask.is_contiguous()):
+        raise ValueError("goal_error_columns: mask must be contiguous int32, one entry per column")
+    if perm is not None and (perm.dtype != torch.int32 or perm.numel() < n
+                             or not perm.is_contiguous()):
+        raise ValueError("goal_error_columns: perm must be contiguous int32, one entry per column")
+    dev = rows.device
+    if grad is None:
+        grad = torch.zeros((k, n), dtype=torch.float64, device=dev)
+    if err is None:
+        err = torch.empty(3, dtype=torch.float64, device=dev)
+    if grad.dtype != torch.float64 or grad.dim() != 2 or grad.shape[0] != k or grad.shape[1] < n:
+        raise ValueError(f"goal_error_columns: grad must be float64 ({k}, {n})")
+    strides = (1, nf) if by_ray else (rays, 1)
+    if not rows.is_cuda:
+        _goal_error_columns_cpu(rows, fields, goal, mask, perm, by_ray, n_source, grad, err)
+        return err, grad
+    _need_gpu(rows, goal, mask, perm, grad, err)
+    if (n > 0 and rows.stride(1) != 1) or (grad.shape[1] > 0 and grad.stride(1) != 1):
+        raise ValueError("goal_error_columns: rows and grad must have contiguous columns")
+    L = _lib.lib()
+    wsb = L.tfrt_goal_error_columns_workspace_bytes(n)
+    if workspace is None:
+        workspace = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    codes = (ctypes.c_int32 * nf)(*fields)
+    check(L.tfrt_goal_error_columns(
+        _p(rows), rows.stride(0), n, _DT[rows.dtype], k, _p(mask), _p(perm), n_source, codes, nf,
+        _p(goal), strides[0], strides[1], _p(grad), grad.stride(0), _p(err), _p(workspace),
+        workspace.numel(), _stream(rows)), "tfrt_goal_error_columns")
+    return err, grad
+
+
+def _goal_error_columns_cpu(rows, fields, goal, mask, perm, by_ray, n_source, grad, err):
+    """The CPU path of ``goal_error_columns`` (every torch op rounds on its own, as the kernels
+    do)."""
+    n = rows.shape[1]
+    counts = torch.ones(n, dtype=torch.bool)
+    if mask is not None:
+        counts &= mask[:n] >= 0
+    s = perm[:n].long() if perm is not None else torch.arange(n)
+    counts &= (s >= 0) & (s < n_source)
+    s = s.clamp(0, max(n_source - 1, 0))
+    zero = torch.zeros((), dtype=torch.float64)
+    total = torch.zeros((), dtype=torch.float64)
+    for c, f in enumerate(fields):
+        if n_source > 0:
+            g = goal[s, c] if by_ray else goal[c, s]
+            d = torch.where(counts, rows[f].double() - g, zero)
+        else:
+            d = torch.zeros(n, dtype=torch.float64)
+        total = total + (d * d).sum()
+        # (a column that does not count gets +0.0, not 2 * 0.0 with the residual's sign)
+        grad[f, :n] = torch.where(counts, 2.0 * d, zero)
+    terms = float(len(fields) * int(counts.sum()))
+    err[0], err[1] = total, terms
+    err[2] = total / terms if terms > 0 else float("nan")
+
+
+def error_combine(terms, weights, reduce="sum", n=None, n_rows=6, out=None, err=None, coeff=None):
+    """tfrt_error_combine: the weighted sum of 1 .. 8 error terms in one launch.  ``terms``: a
+    sequence of ``(grad, row_mask, error)`` -- ``grad`` a float64 seed block of ``n_rows`` rows
+    with contiguous columns (or None in EVERY term: only the errors are combined), ``row_mask``
+    the rows the term wrote (bit r for row r), ``error`` its float64 triple {sum, terms, mean}.
+    ``weights``: contiguous float64 (K,) on the terms' device; ``reduce``: "sum", c_k = w_k, or
+    "mean", c_k = w_k / terms_k (0 for a term without terms), terms_k read from the triple.
+    ``n``: the columns (default: the first block's).  Returns (err {E, 1, E}, out (n_rows, n)
+    float64 or None, coeff (K,)): row r of ``out`` is ``c_k * g_k[r]`` of the first term naming
+    it, plus ``c_k * g_k[r]`` of every later one, each product and sum rounded on its own; 0.0
+    for a row nobody names.  ``out`` (it must not overlap a term's block), ``err``, ``coeff``:
+    buffers to reuse -- with all three given a CUDA call allocates nothing.
+
+    CUDA tensors run the kernel; CPU tensors a torch restatement with the same operations in the
+    same order (every result agrees bit for bit)."""
+    terms = list(terms)
+    K = len(terms)
+    if reduce not in ("sum", "mean"):
+        raise ValueError(f"error_combine: reduce must be 'sum' or 'mean', got {reduce!r}")
+    if not 1 <= K <= COMBINE_MAX_TERMS:
+        raise ValueError(f"error_combine: 1 .. {COMBINE_MAX_TERMS} terms, got {K}")
+    if n_rows not in (4, 6):
+        raise ValueError(f"error_combine: n_rows must be 4 or 6, got {n_rows!r}")
+    if weights.dtype != torch.float64 or tuple(weights.shape) != (K,) \
+            or not weights.is_contiguous():
+        raise ValueError(f"error_combine: weights must be contiguous float64 ({K},)")
+    grads = [t[0] for t in terms]
+    with_grad = any(g is not None for g in grads)
+    if with_grad and any(g is None for g in grads):
+        raise ValueError("error_combine: every term needs a gradient block, or none has one")
+    if n is None:
+        n = grads[0].shape[1] if with_grad else 0
+    n = int(n)
+    for g, row_mask, e in terms:
+        if e.dtype != torch.float64 or e.numel() != 3 or not e.is_contiguous():
+            raise ValueError("error_combine: a term's error must be 3 contiguous float64")
+        if not 0 <= int(row_mask) < (1 << n_rows):
+            raise ValueError(f"error_combine: row_mask {row_mask!r} names a row outside the "
+                             f"{n_rows} of the block")
+        if g is not None and (g.dtype != torch.float64 or g.dim() != 2 or g.shape[0] != n_rows
+                              or g.shape[1] < n):
+            raise ValueError(f"error_combine: a term's grad must be float64 ({n_rows}, {n})")
+    dev = weights.device
+    if with_grad and n > 0:
+        if out is None:
+            out = torch.empty((n_rows, n), dtype=torch.float64, device=dev)
+        if out.dtype != torch.float64 or out.dim() != 2 or out.shape[0] != n_rows \
+                or out.shape[1] < n:
+            raise ValueError(f"error_combine: out must be float64 ({n_rows}, {n})")
+    if err is None:
+        err = torch.empty(3, dtype=torch.float64, device=dev)
+    if coeff is None:
+        coeff = torch.empty(K, dtype=torch.float64, device=dev)
+    if coeff.dtype != torch.float64 or tuple(coeff.shape) != (K,) or not coeff.is_contiguous():
+        raise ValueError(f"error_combine: coeff must be contiguous float64 ({K},)")
+    if not weights.is_cuda:
+        _error_combine_cpu(terms, weights, reduce, n if with_grad else 0, n_rows, out, err, coeff)
+        return err, out, coeff
+    _need_gpu(weights, out, err, coeff, *grads, *(t[2] for t in terms))
+    if with_grad and n > 0 and any(t.stride(1) != 1 for t in grads + [out]):
+        raise ValueError("error_combine: the blocks must have contiguous columns")
+    desc = (_lib.CombineTerm * K)()
+    for d, (g, row_mask, e) in zip(desc, terms):
+        d.grad = None if g is None else g.data_ptr()
+        d.stride = 0 if g is None else g.stride(0)
+        d.row_mask = int(row_mask)
+        d.error = e.data_ptr()
+    check(_lib.lib().tfrt_error_combine(
+        desc, K, _p(weights), 0 if reduce == "sum" else 1, n, n_rows, _p(out),
+        0 if out is None else out.stride(0), _p(err), _p(coeff), _stream(weights)),
+        "tfrt_error_combine")
+    return err, out, coeff
+
+
+def _error_combine_cpu(terms, weights, reduce, n, n_rows, out, err, coeff):
+    """The CPU path of ``error_combine`` (every torch op rounds on its own, as the kernel does)."""
+    cs = []
+    for k, (_, _, e) in enumerate(terms):
+        if reduce == "sum":
+            c = weights[k].clone()
+        else:
+            c = weights[k] / e[1] if float(e[1]) > 0.0 else torch.zeros((), dtype=torch.float64)
+        cs.append(c)
+        coeff[k] = c
+    total = cs[0] * terms[0][2][0]
+    for c, (_, _, e) in zip(cs[1:], terms[1:]):
+        total = total + c * e[0]
+    err[0], err[1], err[2] = total, 1.0, total
+    if n <= 0 or out is None:
+        return
+    for r in range(n_rows):
+        acc = None
+        for c, (g, row_mask, _) in zip(cs, terms):
+            if (int(row_mask) >> r) & 1:
+                p = c * g[r, :n]
+                acc = p if acc is None else acc + p
+        out[r, :n] = 0.0 if acc is None else acc
+
+
 def restore_plan(ids, counts_dev, P, cls_col, perm, n_src, n_rows=None, total=None, zero=False):
     """(inv, dest_of, original ids) of one output class of a trace over permuted rays
     (tfrt_restore_order): row j of the class in the reference's order = row ``inv[j]`` of the

@@ -29,9 +29,9 @@ import torch
 
 from . import distributed as tdist
 from . import _lib, ops
-# (GoalError, RowwiseError, DensityError, SpotError, TransportError: public API)
+# (GoalError, RowwiseError, DensityError, SpotError, TransportError, SumError: public API)
 from .fused_step import (FusedStep, GoalError, RowwiseError, DensityError, SpotError,  # noqa: F401
-                         TransportError, _NotInPlace)
+                         TransportError, SumError, _NotInPlace)
 
 
 class DeferredScalar:

@@ -1,0 +1,1195 @@
+"""
+The declarative error terms of the optimiser, and what the fused step (fused_step.FusedStep) asks
+of one.
+
+The error functions of the reference's optimisation scripts all have one form
+(dev/hexalens.py:144-168):  ``squared_difference(stack(finished[fields]), goal)`` with ``goal``
+a function of fields the finished rays inherit unchanged from their source rays.  ``GoalError``
+states that form declaratively.  A ``RowwiseError`` is torch code that works row by row on the
+finished rays.  The coupled errors take all finished rays of a step into one evaluation (one
+process): a ``DensityError`` -- the finished rays, taken together, must land with a given density
+-- is ``tfrt_density_error`` (four launches: clear, splat, bins, seed); a ``SpotError`` -- rays of
+one group must meet in one point -- ``tfrt_spot_error`` (clear, accumulate, seed, finish); a
+``TransportError`` -- the same target density by sliced optimal transport --
+``tfrt_transport_error`` (per direction keys, radix sort, sorted keys, ranks; then seed and
+finish).  A ``SumError`` is a weighted sum of such terms and of ``GoalError``s: every term's
+launches into a seed block of its own (a ``GoalError`` through ``tfrt_goal_error_columns``), then
+ONE ``tfrt_error_combine`` for the step's seed block and error.
+
+Each is an ordinary error function (``__call__(engine)``): the generic path gives the same
+numbers, which is what the parity tests compare.
+
+The protocol between a built-in term (``GoalError``, ``DensityError``, ``SpotError``,
+``TransportError``) and the fused 3-D step:
+
+* ``rows``, ``fields``, ``rows_for(dimension)``: the rows of the ray block (the field codes) the
+  term reads;
+* ``graph_key()``: what a captured step has baked in of the term;
+* ``seed_rows``: the bitmask of the rows of a (6, N) seed block the term writes;
+* ``seed_columns(cols, hold)``: the term's launches on the step's fixed-shape columns ``cols`` (a
+  ``_Columns``).  ``hold`` has the term's (6, capN) float64 seed block ``g_fin``, zeroed once, its
+  error triple ``err`` and a dict ``buffers`` that the term fills on first use -- and again when a
+  shape they depend on changes -- with the buffers its kind keeps, under the names its
+  ``evaluate`` takes them by.  The rows of ``seed_rows`` of ``hold.g_fin`` are written for every
+  column, and ``hold.err``; the term's ``last_hq`` / ``last_acc`` / ``last_rank2`` are those
+  buffers.  Nothing is read back.
+"""
+import collections
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+
+# What a step offers every term: the (6, N) view ``rows`` of the finished rows at the rays' own
+# columns, the int32 ``mask`` (column i counts if mask[i] >= 0), the trace's order ``perm`` (the
+# source ray of column i; None: the source's own order), the source set ``src`` and N.
+_Columns = collections.namedtuple("_Columns", "rows mask perm src n")
+
+_GEO3 = ("x_start", "y_start", "z_start", "x_end", "y_end", "z_end")
+_GEO2 = ("x_start", "y_start", "x_end", "y_end")
+# the fields of the coupled errors (DensityError, SpotError): a row of the geometry block or a
+# direction cosine of the finished ray's last link; the index is the field code of
+# tfrt_density_error_fields / tfrt_spot_error_fields
+_FIELDS3 = _GEO3 + ("x_dir", "y_dir", "z_dir")
+_FIELDS2 = _GEO2 + ("x_dir", "y_dir")
+
+
+def _source_key(src):
+    """(key, vals) of the source set ``src``: a cache key made of the versions of its fields, and
+    the tensors it is made of -- kept with the key, they stay alive and their ids stay theirs."""
+    if hasattr(src, "cache_key"):      # rays made in place (sources.DeviceRaySet): lazy fields
+        return src.cache_key, [src]
+    vals = list(src.values()) if hasattr(src, "values") else [src[k] for k in src.keys()]
+    return tuple((id(v), getattr(v, "_version", None)) for v in vals), vals
+
+
+def _source_size(src):
+    """(ray count, device) of the source set ``src``."""
+    if hasattr(src, "n_rays"):
+        return src.n_rays, src.device
+    return src["x_start"].shape[0], src["x_start"].device
+
+
+def _xy(codes):
+    """(row_x, row_y) as the column errors take them: -1 for the y of one field."""
+    return codes[0], codes[1] if len(codes) == 2 else -1
+
+
+def _workspace(n_bytes, device):
+    return torch.empty(max(n_bytes, 1), dtype=torch.uint8, device=device)
+
+
+class _Term:
+    """What the built-in terms share of the fused step's protocol (module docstring)."""
+    has_direction = False
+    # True: a step with this error alone runs on every source ray's fixed-shape column
+    # (FusedStep._rowwise3d / _rowwise2d); False: the goal steps (_goal3d / _goal2d)
+    on_columns = False
+
+    @property
+    def seed_rows(self):
+        """The bitmask of the rows of a (6, N) seed block that ``seed_columns`` writes: the
+        fields' own, all six with a direction field (the chain rule onto start and end)."""
+        return 0x3f if self.has_direction else sum(1 << r for r in self.rows)
+
+
+class GoalError(_Term):
+    """``error = squared_difference(stack([finished[f] for f in fields], axis=1), goal)``.
+
+    ``goal``: a callable taking the field dict of the SOURCE rays and returning one goal row per
+    source ray, shape (N, len(fields)) (or (N,) for a single field); or such a tensor.  Finished
+    rays look their row up through the source-ray index the trace carries, which equals
+    evaluating the same expression on the fields a finished ray inherits (engine.py:2242-2281).
+
+    Example (dev/hexalens.py:154-157, magnification m)::
+
+        erf = GoalError(("y_end", "z_end"), lambda src: -m * src["object_coords"][:, 1:])
+
+    On a 2-D engine the fields come from ``x_start, y_start, x_end, y_end`` (``rows_for(2)``);
+    dev/optimize_single_arc.py's error is ``GoalError(("y_end",), zeros)``.
+    """
+
+    def __init__(self, fields=("y_end", "z_end"), goal=None, rowwise=False):
+        self.fields = tuple(fields)
+        # ``rowwise=True`` states that a callable ``goal`` computes row i from ray i's fields alone
+        # (dev/hexalens.py:154-157 does: a multiple of the ray's object coordinates).  The fused
+        # step may then evaluate it on the source in whatever order it traces the rays, instead of
+        # permuting a table made in source order -- for a source re-drawn every step that saves a
+        # random gather per step.  Leave it False for goals that depend on a ray's POSITION in the
+        # source (a table closed over by the callable, a linspace over the rays, ...).
+        self.rowwise = bool(rowwise)
+        if not self.fields or any(f not in _GEO3 for f in self.fields):
+            raise ValueError(f"GoalError: fields must be taken from {_GEO3}, got {fields!r}")
+        if goal is None:
+            raise ValueError("GoalError: a goal (callable or tensor) is required")
+        if len(set(self.fields)) != len(self.fields):
+            raise ValueError(f"GoalError: duplicate fields in {fields!r}")
+        self.rows = [_GEO3.index(f) for f in self.fields]
+        self.goal = goal
+        self._cache = None
+
+    def rows_for(self, dimension):
+        """Rows of the ray block of a ``dimension``-D trace that the fields are read from (a 3-D
+        block is x_start .. z_end, a 2-D one x_start, y_start, x_end, y_end)."""
+        if dimension == 3:
+            return self.rows
+        bad = [f for f in self.fields if f not in _GEO2]
+        if bad:
+            raise ValueError(f"GoalError: field(s) {bad} do not exist on a {dimension}-D engine "
+                             f"(fields of its rays: {_GEO2})")
+        return [_GEO2.index(f) for f in self.fields]
+
+    def table(self, src, by_ray=False):
+        """(len(fields), N) contiguous float64 goal table of the source set ``src``; with
+        ``by_ray`` the (N, len(fields)) contiguous form the callable returns (no transposed copy:
+        tfrt_goal_error3d takes either layout)."""
+        key, vals = _source_key(src)
+        key = (key, bool(by_ray))
+        if self._cache is not None and self._cache[0] == key:
+            return self._cache[1]
+        g = self.goal(src) if callable(self.goal) else self.goal
+        n, dev = _source_size(src)
+        g = torch.as_tensor(g, dtype=torch.float64, device=dev).detach()
+        if g.dim() == 1:
+            g = g.reshape(-1, 1)
+        if tuple(g.shape) != (n, len(self.fields)):
+            raise ValueError(f"GoalError: goal has shape {tuple(g.shape)}, expected "
+                             f"({n}, {len(self.fields)}) -- one row per source ray")
+        table = g.contiguous() if by_ray else g.t().contiguous()
+        self._cache = (key, table, vals)     # the keyed tensors stay alive with the key
+        return table
+
+    def graph_key(self):
+        """What a captured step has baked in: the goal, the fields and the order the goal is
+        evaluated in."""
+        return (id(self.goal), self.fields, self.rowwise)
+
+    def seed_columns(self, cols, hold):
+        """tfrt_goal_error_columns on the step's columns: it reads the goal table in the source's
+        order and looks a column's row up through the trace's order ``cols.perm`` itself (no
+        permuted copy that could go stale when a source is re-drawn and re-ordered inside the
+        graph)."""
+        if not hold.buffers:
+            hold.buffers["workspace"] = _workspace(
+                _lib.lib().tfrt_goal_error_columns_workspace_bytes(cols.n), cols.rows.device)
+        # (the table in the layout the goal has: no transposed copy per step)
+        ops.goal_error_columns(cols.rows, self.rows, self.table(cols.src, by_ray=True),
+                               mask=cols.mask, perm=cols.perm, by_ray=True, grad=hold.g_fin,
+                               err=hold.err, **hold.buffers)
+
+    def __call__(self, engine):
+        """The same error through the generic path (arbitrary-error-function contract)."""
+        self.rows_for(engine.dimension)
+        fin = engine.finished_rays
+        if not bool(fin):
+            return torch.zeros((0, len(self.fields)), dtype=torch.float64)
+        ids = engine.last_trace["finished_id"].long()
+        table = self.table(engine._trace_src)
+        out = torch.stack([fin[f] for f in self.fields], dim=1).double()
+        return (out - table[:, ids].t()) ** 2
+
+
+class RowwiseError:
+    """An error function of the FINISHED rays that works row by row:
+    ``error = fn(rays)`` with ``rays[field]`` the fields of the finished rays (geometry and every
+    inherited source field, tfrt/engine.py:2242-2281) and the result one row of error terms per
+    ray, shape (n,) or (n, k) -- row i a function of row i of the fields alone.  That is what the
+    reference's optimisation scripts compute under their tape (dev/hexalens.py:144-168 is one
+    instance; any element-wise torch code qualifies, a mean over the rays does not).
+
+    It is an ordinary ``error_function(engine)``; stating the row-wise contract lets the optimiser
+    evaluate ``fn`` on fixed-shape tensors -- every source ray's column, a mask for the rays that
+    finished (tfrt_scene3d.in_place == 2) -- so that the step reads no ray count back and its
+    launches, ``fn``'s own torch kernels and their autograd included, are captured in one HIP graph
+    like a ``GoalError``'s (fused_step.FusedStep).  Columns of rays that did not finish hold finite
+    stand-in values (the source ray); their error terms are masked out of the sum and their
+    gradients are never read.  On 2-D engines the same holds with one process and no ray shards
+    (tfrt_trace2d_rows / tfrt_trace2d_backward_rows; 2-D traces keep the source's order)."""
+
+    on_columns = True
+
+    def __init__(self, fn):
+        if not callable(fn):
+            raise ValueError("RowwiseError: fn must be callable")
+        self.fn = fn
+        self.rows = []          # (no built-in goal kernel)
+
+    def __call__(self, engine):
+        return self.fn(engine.finished_rays)
+
+
+def _field_codes(what, fields, dimension):
+    """The field codes of ``fields`` on a ``dimension``-D engine."""
+    names = _FIELDS3 if dimension == 3 else _FIELDS2
+    bad = [f for f in fields if f not in names]
+    if bad:
+        raise ValueError(f"{what}: field(s) {bad} do not exist on a {dimension}-D engine "
+                         f"(fields of its rays: {names})")
+    return [names.index(f) for f in fields]
+
+
+def _source_buffer(owner, name, given, convert, src, what, noun, keep=False):
+    """``owner.<name>``, a buffer with one entry per SOURCE ray of the source set ``src``, on the
+    source's device: the tensor given (moved once; a new buffer re-captures a graph), or the
+    result of the callable ``given`` on the source's field dict, converted by ``convert(value,
+    device)`` and cached in ``owner._caches[name]`` by the versions of the source's fields as
+    ``GoalError.table`` is.  ``keep``: a new result of the callable is copied into the buffer
+    there is (same shape), so its address -- part of a step's signature -- stays and a step that
+    is being captured records the evaluation.  What ``SpotError.labels_of`` and the errors'
+    ``weights_of`` share."""
+    n, dev = _source_size(src)
+    value = getattr(owner, name)
+    if callable(given):
+        key, vals = _source_key(src)
+        hit = owner._caches.get(name)
+        if hit is None or hit[0] != key:
+            new = convert(given(src), dev)
+            if keep and value is not None and value.shape == new.shape \
+                    and value.device == new.device:
+                value.copy_(new)
+            else:
+                value = new
+                setattr(owner, name, value)
+            owner._caches[name] = (key, vals)        # the keyed tensors stay alive with the key
+    elif value.device != dev:
+        value = value.to(dev)
+        setattr(owner, name, value)
+    if value.numel() != n:
+        raise ValueError(f"{what}: {value.numel()} {noun}s for {n} source rays -- one {noun} per "
+                         "source ray")
+    return value
+
+
+def _as_weights(what, weights, device):
+    """The weights of ``DensityError`` / ``SpotError`` as they are kept: float64 on ``device``,
+    divided by their maximum once (only ratios matter), values in [0, 1].  While a step is being
+    captured the values cannot be read: the checks are those of the eager steps before it, and the
+    kernels leave out a ray whose weight is not finite or not in [0, 1]."""
+    w = weights if isinstance(weights, torch.Tensor) else torch.as_tensor(np.asarray(weights))
+    if w.dim() != 1 or not w.dtype.is_floating_point:
+        raise ValueError(f"{what}: weights must be floats of shape (N,), one weight per source "
+                         f"ray; got shape {tuple(w.shape)}, {w.dtype}")
+    w = w.detach().to(device=device, dtype=torch.float64)
+    if w.numel() == 0:
+        raise ValueError(f"{what}: at least one weight must be > 0")
+    if not (w.is_cuda and torch.cuda.is_current_stream_capturing()):
+        if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+            raise ValueError(f"{what}: weights must be finite and >= 0")
+        if not bool((w > 0).any()):
+            raise ValueError(f"{what}: at least one weight must be > 0")
+    return (w / w.max()).contiguous()
+
+
+def _init_weights(erf, what, weights):
+    """``erf.weights_given`` / ``erf.weights`` from the constructor's ``weights``."""
+    from . import config
+    erf.weights_given = weights
+    erf.weights = None
+    if weights is not None and not callable(weights):
+        erf.weights = _as_weights(what, weights, config.get_device())
+
+
+def _weights_key(erf):
+    """The weights' part of a ``graph_key``: the buffer's address and shape (overwriting it in
+    place is seen by replays, another buffer re-captures)."""
+    w = erf.weights
+    return (erf.weights_given is not None,
+            None if w is None else (w.data_ptr(), tuple(w.shape)))
+
+
+def _fields_and_domain(what, fields, domain):
+    """(fields, domain) of a DensityError or TransportError as they are kept: one or two distinct
+    field names, one finite (lo, hi) per field."""
+    names = (fields,) if isinstance(fields, str) else tuple(fields)
+    if len(names) not in (1, 2) or any(f not in _FIELDS3 for f in names) \
+            or len(set(names)) != len(names):
+        raise ValueError(f"{what}: one or two distinct fields out of {_FIELDS3}, got {fields!r}")
+    try:
+        domain = tuple((float(d[0]), float(d[1])) for d in domain)
+    except (IndexError, TypeError) as e:
+        raise ValueError(f"{what}: domain must be ((x0, x1), (y0, y1)) or ((x0, x1),)") from e
+    if len(domain) != len(names) \
+            or any(not (np.isfinite(a) and np.isfinite(b) and b > a) for a, b in domain):
+        raise ValueError(f"{what}: domain needs one finite (lo, hi), lo < hi, per field; got {domain!r}")
+    return names, domain
+
+
+def _goal_bins(what, goal, domain, bins, dev):
+    """(g, ||g||) of a goal given as an array -- (ny, nx), or (nx,) for one field -- or as a
+    callable evaluated at the centres of ``bins`` bins: float64 on ``dev``, finite, non-negative,
+    not all zero."""
+    from . import config
+    k = len(domain)
+    if callable(goal):
+        if bins is None:
+            raise ValueError(f"{what}: a callable goal needs bins=nx or bins=(nx, ny)")
+        counts = (int(bins),) * k if np.ndim(bins) == 0 else tuple(int(b) for b in bins)
+        if len(counts) != k or any(c < 1 for c in counts):
+            raise ValueError(f"{what}: bins must give one count >= 1 per field, got {bins!r}")
+        centres = []
+        for (lo, hi), c in zip(domain, counts):
+            edges = torch.linspace(lo, hi, c + 1, dtype=torch.float64, device=dev)
+            centres.append((edges[:-1] + edges[1:]) / 2.0)
+        if k == 2:
+            goal = goal(*torch.meshgrid(centres[0], centres[1], indexing="xy"))
+        else:
+            goal = goal(centres[0])
+    g = config.as_f64(goal, dev).detach()
+    if g.dim() != k or g.numel() < 1 or g.numel() > ops.DENSITY_MAX_BINS:
+        raise ValueError(f"{what}: goal must have {k} dimension(s) and between 1 and "
+                         f"{ops.DENSITY_MAX_BINS} bins, got shape {tuple(g.shape)}")
+    if not bool(torch.isfinite(g).all()) or bool((g < 0).any()):
+        raise ValueError(f"{what}: goal must be finite and non-negative")
+    norm = float(torch.linalg.norm(g))
+    if norm == 0.0:
+        raise ValueError(f"{what}: goal is zero everywhere")
+    return g, norm
+
+
+class _CoupledError(_Term):
+    """What the coupled errors share: all finished rays of a step enter one evaluation (one
+    process).  The class's name stands in front of its messages."""
+    on_columns = True
+    weights_given = None
+
+    def rows_for(self, dimension):
+        """Field codes on a ``dimension``-D trace: the row of the ray block a geometry field is
+        read from, ``2 * dimension + axis`` for a direction cosine."""
+        if dimension == 3:
+            return self.rows
+        return _field_codes(type(self).__name__, self.fields, dimension)
+
+    def weights_of(self, src):
+        """The float64 weight buffer of the source set ``src`` on its device, one weight in [0, 1]
+        per source ray (None without weights): the tensor given, or the callable's result,
+        normalised and cached as ``SpotError.labels_of`` caches its labels."""
+        if self.weights_given is None:
+            return None
+        what = type(self).__name__
+        return _source_buffer(self, "weights", self.weights_given,
+                              lambda v, dev: _as_weights(what, v, dev), src, what, "weight",
+                              keep=True)
+
+    def _finished_block(self, engine, fin, codes, ids=False):
+        """What the generic path hands the kernels: (block, weights, ids, dimension, codes) --
+        the (k, n) field columns of the finished rays ``fin`` with ``dimension = codes = None``,
+        or with a direction field the (2 * dimension, n) geometry block and the field codes; the
+        weight buffer (None without weights) and, with weights or ``ids``, the int32 source ray
+        of every column."""
+        weights = None if self.weights_given is None else self.weights_of(engine._trace_src)
+        ids = engine.last_trace["finished_id"].to(torch.int32).contiguous() \
+            if ids or weights is not None else None
+        if self.has_direction:
+            dim = engine.dimension
+            block = torch.stack([fin[f] for f in (_GEO3 if dim == 3 else _GEO2)], dim=0)
+            return block, weights, ids, dim, tuple(codes)
+        return torch.stack([fin[f] for f in self.fields], dim=0), weights, ids, None, None
+
+    @staticmethod
+    def _held(hold, name, shape, dtype, device, workspace_bytes):
+        """``hold.buffers`` with the zeroed buffer ``name`` of ``shape`` and a workspace of
+        ``workspace_bytes()`` bytes, and nothing else: made on first use, and again when the
+        shape changes (or the holder was another kind's)."""
+        held = hold.buffers
+        if name not in held or tuple(held[name].shape) != tuple(shape):
+            held.clear()
+            held["workspace"] = _workspace(workspace_bytes(), device)
+            held[name] = torch.zeros(tuple(shape), dtype=dtype, device=device)
+        return held
+
+
+class DensityError(_CoupledError):
+    """The finished rays, taken together, must land with the density ``goal`` on the target: a
+    soft (bilinear) histogram of the rays against the goal, both L2-normalised, summed squared
+    difference -- ``analyze.DistributionDifferential`` (tfrt/analyze.py:134-290) with a gradient.
+
+    ``fields``: one or two fields of a finished ray, x and (if present) y, e.g.
+    ``("y_end", "z_end")``: geometry fields, or the direction cosines ``x_dir``, ``y_dir``,
+    ``z_dir`` of the ray's last link -- ``("y_dir", "z_dir")`` is a far-field intensity, a position
+    with a direction a phase-space density.  For a ray, in float64 and every operation rounded on
+    its own: ``e = end - start``, ``L = sqrt(e_x*e_x + e_y*e_y + e_z*e_z)`` (summed left to right),
+    ``d = e / L``; a ray with a non-finite coordinate or without a length (``L`` not finite or not
+    ``> 0``) counts as one with a non-finite coordinate.  The gradient of a direction field goes
+    back onto the start and the end of the link:
+    ``G_b = ((gv of the field of axis b, else 0) - t * d_b) / L`` with ``t = sum_k gv_k * d_(a_k)``,
+    ``+G`` on the end rows and ``-G`` on the start rows.  With float32 ray state the subtraction
+    cancels: a direction is good to about ``eps32 * max|coordinate| / L``, not to ``eps32``.
+    ``goal``: a non-negative array, shape (ny, nx) for two fields -- the
+    second field is the FIRST index, as ``analyze.histogram2D`` returns it -- or (nx,) for one; or a
+    callable, evaluated once at the bin centres exactly as ``DistributionDifferential`` does (the
+    bin counts then come from ``bins``: nx, or (nx, ny)).  It is kept L2-normalised in float64 on
+    the device as ``goal`` (``g`` below); an all-zero goal is a ValueError.  ``domain``:
+    ``((x0, x1), (y0, y1))``, or ``((x0, x1),)`` for one field.  At least one bin per axis, at most
+    65,536 bins.  ``sx = nx / (x1 - x0)`` (and ``sy``) are computed once, in float64, on the host.
+
+    For every finished ray of the trace, coordinates converted to float64, every operation
+    rounded on its own:
+
+    * a ray with a non-finite coordinate contributes nothing and gets zero gradient;
+    * a ray outside the closed domain on any axis contributes nothing to the histogram and adds
+      ``oob_weight * (ex**2 + ey**2)`` to the error, ``ex = max(x0 - x, 0) + max(x - x1, 0)``; its
+      gradient is the derivative of that expression;
+    * a ray inside is spread bilinearly over bin centres: ``u = (x - x0) * sx - 0.5``,
+      ``i0 = floor(u)``, ``t = u - i0``; weight ``1 - t`` goes to column ``clamp(i0, 0, nx - 1)``
+      and ``t`` to column ``clamp(i0 + 1, 0, nx - 1)`` (the outer half bin piles onto the edge bin:
+      total weight 1, derivative 0 there); y alike, the four weights are the products; one field:
+      two weights;
+    * each weight ``w`` is added to its bin as the integer ``rint(w * 2**32)`` (half to even) in an
+      int64 histogram ``Hq`` -- integer addition is associative, so ``Hq`` does not depend on the
+      order of the atomics; ``H = Hq / 2**32``;
+    * ``s = ||H||``; ``s == 0``: the histogram part is ``sum(g**2)`` and every pull is 0; otherwise
+      ``h = H / s``, ``r = h - g``, ``E_hist = sum(r**2)`` and the pull on bin b is
+      ``D_b = (2 / s) * (r_b - h_b * sum_c(h_c * r_c))``;
+    * gradient of a ray inside (quantisation treated as the identity):
+      ``dE/dx = sx * ((1 - ty) * (D[j0, i1] - D[j0, i0]) + ty * (D[j1, i1] - D[j1, i0]))`` with
+      the clamped indices, ``dE/dy`` symmetric;
+    * ``error = E_hist + sum of the penalties``: ONE error term, so the reported mean is the sum.
+      Every reduction has a fixed shape and order: two runs give the same bits.
+
+    It is an ordinary ``error_function(engine)`` (the generic path: ``ops.density_error`` over the
+    finished rays' columns under a ``torch.autograd.Function``), which also serves sources that
+    are not traced in place, ``deterministic=True`` and 2-D engines.  On a 3-D engine that traces
+    its source in place the optimiser runs it on the fused, graph-replayed step under the
+    conditions of a ``RowwiseError`` (``FusedStep._rowwise3d`` with ``tfrt_density_error`` in the
+    place of ``fn`` and its autograd).  The fused 2-D step does not take it
+    (``FusedStep.eligible2d`` is false): 2-D engines use the generic path.  One process: the
+    histogram couples the rays, ray shards would each normalise their own.
+
+    ``weights``: None -- every finished ray is one unit of light --, or a radiant power per
+    SOURCE ray: a float tensor or array of shape (N,) in the source's own order, finite and
+    ``>= 0`` with at least one ``> 0`` (a ValueError otherwise), or a callable on the source's
+    field dict that returns one (``lambda src: cos`` of the start direction for a Lambertian
+    emitter sampled uniformly in angle; evaluated and cached as ``SpotError``'s ``groups``).  Only
+    ratios matter: the weights are divided by their maximum once, in float64, and kept on the
+    device as ``weights`` (values in [0, 1]); that buffer may be overwritten in place between steps
+    (a replayed graph reads it), another buffer re-captures.  A finished ray finds its weight ``w``
+    through the source-ray index the trace carries.  A ray without a source ray, or whose ``w`` is
+    not finite or not in [0, 1], counts as one with a non-finite coordinate.  Then, each product
+    rounded on its own:
+
+    * a ray inside adds ``rint(((bx * by) * w) * 2**32)`` to each of its bins (``bx * w`` with one
+      field) and its gradient is the expression above multiplied by ``w`` last;
+    * a ray outside has its penalty and its gradient multiplied by ``w`` last;
+    * ``s``, ``E_hist`` and the pulls come from the weighted histogram exactly as above; with a
+      direction field the gradient carries ``w`` when it enters the chain rule.
+
+    Weighted and unweighted run on the same paths (fused, generic, 2-D, ``deterministic=True``),
+    the weighted one with kernels of its own (tfrt_density_error_weighted).
+
+    ``goal`` may be overwritten in place between steps (a replayed graph reads the buffer);
+    ``last_hq`` is the int64 histogram of the last evaluation (the weighted one with weights).  ``splat_variant`` (0: by the number
+    of bins; 1: histogram in LDS; 2: global atomics) is tfrt_density_error's, for measuring."""
+
+    splat_variant = 0
+
+    def __init__(self, fields, goal, domain, oob_weight=0.0, bins=None, weights=None):
+        from . import config
+        self.fields, self.domain = _fields_and_domain("DensityError", fields, domain)
+        self.rows = [_FIELDS3.index(f) for f in self.fields]
+        self.has_direction = any(f.endswith("_dir") for f in self.fields)
+        k = len(self.fields)
+        self.oob_weight = float(oob_weight)
+        if not (self.oob_weight >= 0.0 and np.isfinite(self.oob_weight)):
+            raise ValueError("DensityError: oob_weight must be finite and >= 0")
+        dev = config.get_device()
+        g, norm = _goal_bins("DensityError", goal, self.domain, bins, dev)
+        self.goal = (g / norm).contiguous()
+        nx = self.goal.shape[-1]
+        self.grid = ops.density_grid(domain, nx, self.goal.shape[0] if k == 2 else None)
+        self.last_hq = None
+        self._caches = {}
+        _init_weights(self, "DensityError", weights)
+
+    @property
+    def g(self):
+        return self.goal
+
+    def goal_on(self, device):
+        """The goal buffer on ``device`` (moved once; a new buffer re-captures a graph)."""
+        if self.goal.device != device:
+            self.goal = self.goal.to(device)
+        return self.goal
+
+    def graph_key(self):
+        """What a captured step has baked in: the goal buffer's address, the weight buffer's and
+        the constants."""
+        return (self.goal.data_ptr(), tuple(self.goal.shape), self.grid, self.oob_weight,
+                self.splat_variant) + _weights_key(self)
+
+    def evaluate(self, rows, row_x, row_y, mask=None, dimension=None, weights=None, perm=None,
+                 **buffers):
+        """``ops.density_error`` of the columns of ``rows`` with this goal, domain and weight
+        (``dimension`` given: ``rows`` is the geometry block, ``row_x`` / ``row_y`` field codes;
+        ``weights``: the buffer of ``weights_of``, ``perm``: the source ray of every column)."""
+        out = ops.density_error(rows, row_x, row_y, self.goal_on(rows.device), self.grid,
+                                self.oob_weight, mask=mask, variant=self.splat_variant,
+                                dimension=dimension, weights=weights,
+                                perm=perm if weights is not None else None, **buffers)
+        self.last_hq = out[2]
+        return out
+
+    def seed_columns(self, cols, hold):
+        """tfrt_density_error on the step's columns -- with weights it reads the source's weight
+        buffer through the trace's order ``cols.perm``, inside the kernel, as a SpotError its
+        labels --: the histogram goes into ``hold.buffers["hq"]``, made anew when the goal's
+        shape changes."""
+        goal = self.goal_on(cols.rows.device)
+        nx, ny = goal.shape[-1], (goal.shape[0] if goal.dim() == 2 else 1)
+        held = self._held(hold, "hq", goal.shape, torch.int64, cols.rows.device,
+                          lambda: _lib.lib().tfrt_density_error_workspace_bytes(cols.n, nx, ny))
+        self.evaluate(cols.rows, *_xy(self.rows), mask=cols.mask, dimension=3,
+                      weights=self.weights_of(cols.src), perm=cols.perm, grad=hold.g_fin,
+                      err=hold.err, **held)
+
+    def __call__(self, engine):
+        """The error as a (1,) tensor through the generic path; the gradient rows come back in
+        ``backward``."""
+        codes = self.rows_for(engine.dimension)
+        fin = engine.finished_rays
+        if not bool(fin):
+            return (self.goal * self.goal).sum().reshape(1)
+        block, weights, ids, dim, codes = self._finished_block(engine, fin, codes)
+        return _DensityTerms.apply(block, self, weights, ids, dim, codes)
+
+
+class _DensityTerms(torch.autograd.Function):
+    """DensityError over the finished rays, no mask.  ``dimension=None, codes=None``: ``block`` is
+    the (k, n) field columns; else it is the (2 * dimension, n) geometry block and ``codes`` the
+    field codes (a direction field).  ``weights`` (or None) with ``ids``, the source ray of every
+    column."""
+
+    @staticmethod
+    def forward(ctx, block, erf, weights=None, ids=None, dimension=None, codes=None):
+        rows = block.detach().contiguous()
+        if codes is None:
+            codes = (0, 1)[:rows.shape[0]]
+        err, grad, _ = erf.evaluate(rows, *_xy(codes), dimension=dimension, weights=weights,
+                                    perm=ids)
+        ctx.save_for_backward(grad)
+        ctx.dtype = block.dtype
+        return err[:1].clone()
+
+    @staticmethod
+    def backward(ctx, upstream):
+        grad, = ctx.saved_tensors
+        return (upstream * grad).to(ctx.dtype), None, None, None, None, None
+
+
+class TransportError(_CoupledError):
+    """The finished rays, taken together, must land with the density ``goal`` on the target --
+    measured by sliced optimal transport (sliced Wasserstein-2) from the rays that actually arrive:
+    along each of K directions the landing points are sorted, the ray of rank r belongs at the
+    goal's quantile (r + 1/2) / n, and the error is the squared distance to that target.  In one
+    dimension this IS the optimal transport, and its gradient is exact almost everywhere because
+    the assignment is locally constant; in two it is averaged over the directions.  Unlike
+    ``DensityError``, whose gradient comes from a ray's four neighbouring bins, the pull is global:
+    a beam that starts beside the target, a lens that over-focuses into one spot, a goal with
+    empty stretches all have a signal.  It needs no transport map (``GoalError`` with ranks does);
+    lost rays simply take no part.
+
+    ``fields``, ``goal``, ``domain``, ``bins``: as for ``DensityError`` -- one or two geometry
+    fields of a finished ray, e.g. ``("y_end", "z_end")``; ``goal`` a non-negative array of shape
+    (ny, nx), the second field the FIRST index, or (nx,) for one field, or a callable evaluated at
+    the centres of ``bins`` bins; ``domain`` one finite ``(lo, hi)`` per field; the same
+    ValueErrors.  Direction fields (``x_dir`` ...) and ``weights=`` are refused with a ValueError:
+    weighted quantiles and the chain rule of a direction are not built yet.
+    ``directions``: with two fields K angles -- an int K means ``theta_k = pi * k / K``,
+    k = 0 .. K-1 (default 8), an array gives them --, 1 <= K <= 64; one field: K = 1, the axis
+    itself.  ``c_k = cos(theta_k)``, ``s_k = sin(theta_k)`` are computed once on the host in
+    float64.  ``knots``: Q, the intervals of a quantile table, 2 <= Q <= 65,536.
+
+    The quantile tables ``tables``, (K, Q + 1) float64 on the device, are built on the host
+    (``ops.transport_tables``): every goal bin is split into 4 x 4 sub-points at the sub-cells'
+    centres, in normalised coordinates xi, eta in [0, 1], each with the bin's mass; empty ones are
+    dropped; per direction ``p = c * xi + s * eta`` (one field: ``p = xi``) is sorted stably,
+    ``cm = (cumsum(w) - w / 2) / sum(w)`` and ``T_k = np.interp(arange(Q + 1) / Q, cm, p_sorted)``:
+    non-decreasing by construction.
+
+    For every finished ray and direction, coordinates converted to float64, every operation
+    rounded on its own:
+
+    * a ray counts if both coordinates are finite (and, on the fused step, it has finished);
+    * ``xi = (x - x0) * ix`` with ``ix = 1 / (x1 - x0)`` computed once on the host, ``eta`` alike;
+      ``p = c * xi + s * eta`` (two products, one sum);
+    * its sort key: ``a = min(0, c) + min(0, s)``, ``b = max(0, c) + max(0, s)``,
+      ``lo = a - (b - a)``, ``scale = 2**26 / (3 * (b - a))``,
+      ``q = clamp(floor((p - lo) * scale), 0, 2**26 - 2)``; a ray that does not count has
+      ``q = 2**26 - 1`` (the width 26 is ``ops.TRANSPORT_KEY_BITS``: two 13-bit digits of the
+      radix sort) -- a ray up to one domain width outside still has a key of its own, farther out
+      the keys clamp and the rays tie;
+    * its rank among the n_valid rays that count: ``first`` keys are smaller than q, ``count`` are
+      equal to q, ``rank2 = 2 * first + count`` (int32; -1 for a ray that does not count) and
+      ``u = (first + count * 0.5) / n_valid``.  Ties share the mid-rank on purpose: the result
+      does not depend on the order of the rays, so the fused step (coherent order) and the generic
+      path (finished order) give every ray the same bits;
+    * target and residual: ``z = u * Q``, ``m = min(floor(z), Q - 1)``, ``f = z - m``,
+      ``t = T[m] + f * (T[m + 1] - T[m])``, ``d = p - t``; the term is ``d * d``;
+    * gradient, accumulated from zero in the order k = 0 .. K-1:
+      ``gx += ((2 * d) * c) * ix``, ``gy += ((2 * d) * s) * iy``; zeros for a ray that does not
+      count.  The targets are constants, as ``SpotError``'s centroids are;
+    * ``error = {sum of all terms, K * n_valid, sum / terms}`` -- the sum convention of
+      ``GoalError`` and ``SpotError``; the mean of no terms is NaN.  The sum has a fixed shape and
+      order: two runs give the same bits in the error, the gradient and ``rank2``.
+
+    It is an ordinary ``error_function(engine)`` (the generic path: ``ops.transport_error`` over
+    the finished rays' columns under a ``torch.autograd.Function``, which returns the
+    (n_finished, K) terms), which also serves 2-D engines, ``deterministic=True``, fewer than 4,096
+    rays and sources that are not traced in place.  On a 3-D engine that traces its source in
+    place the optimiser runs it on the fused, graph-replayed step under the conditions of a
+    ``DensityError`` (``FusedStep._rowwise3d`` with ``tfrt_transport_error``: 11 K + 2 launches,
+    n_valid stays on the device).  One process: the ranks couple all rays.
+
+    ``set_goal(goal)`` rebuilds the tables into the same device buffer, so a replayed graph sees
+    the new goal; another shape is a ValueError.  ``last_rank2`` is the (K, n) int32 ``rank2`` of
+    the last evaluation, ``last_count`` its n_valid (read from the device when asked for)."""
+
+    def __init__(self, fields, goal, domain, directions=None, knots=1024, bins=None,
+                 weights=None):
+        from . import config
+        self.fields, self.domain = _fields_and_domain("TransportError", fields, domain)
+        if any(f.endswith("_dir") for f in self.fields):
+            raise ValueError("TransportError: direction fields (x_dir, y_dir, z_dir) are not "
+                             f"supported, only geometry fields; got {fields!r}")
+        if weights is not None:
+            raise ValueError("TransportError: weights= is not supported (weighted quantiles are "
+                             "not built yet)")
+        self.rows = [_FIELDS3.index(f) for f in self.fields]
+        k = len(self.fields)
+        try:
+            self.knots = int(knots)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"TransportError: knots must be an integer, got {knots!r}") from e
+        if self.knots != knots or not 2 <= self.knots <= ops.TRANSPORT_MAX_KNOTS:
+            raise ValueError(f"TransportError: knots must lie in 2 .. {ops.TRANSPORT_MAX_KNOTS}, "
+                             f"got {knots!r}")
+        try:
+            cs = ops.transport_directions(8 if directions is None else directions, k)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"TransportError: directions must be a count in 1 .. "
+                             f"{ops.TRANSPORT_MAX_DIRECTIONS} or as many finite angles, got "
+                             f"{directions!r}") from e
+        self.directions = cs                       # (K, 2) numpy: cos, sin
+        self.bins = bins
+        dev = config.get_device()
+        g, _ = _goal_bins("TransportError", goal, self.domain, bins, dev)
+        self.goal_shape = tuple(g.shape)
+        self.angles = torch.as_tensor(cs, dtype=torch.float64).contiguous().to(dev)
+        self.tables = torch.as_tensor(
+            ops.transport_tables(g.cpu().numpy(), self.domain, cs, self.knots)).contiguous().to(dev)
+        self.grid = ops.transport_grid(self.domain)
+        self.last_rank2 = None
+
+    @property
+    def n_directions(self):
+        return self.tables.shape[0]
+
+    @property
+    def last_count(self):
+        """n_valid of the last evaluation (a device read)."""
+        if self.last_rank2 is None:
+            raise RuntimeError("TransportError: no evaluation yet")
+        return int((self.last_rank2[0] >= 0).sum()) if self.last_rank2.shape[1] else 0
+
+    def set_goal(self, goal):
+        """Another goal of the same shape: the tables are rebuilt on the host and copied into the
+        device buffer there is."""
+        g, _ = _goal_bins("TransportError", goal, self.domain, self.bins, torch.device("cpu"))
+        if tuple(g.shape) != self.goal_shape:
+            raise ValueError(f"TransportError: set_goal needs a goal of shape {self.goal_shape}, "
+                             f"got {tuple(g.shape)}")
+        new = ops.transport_tables(g.numpy(), self.domain, self.directions, self.knots)
+        self.tables.copy_(torch.as_tensor(new))
+
+    def tables_on(self, device):
+        """(tables, angles) on ``device`` (moved once; new buffers re-capture a graph)."""
+        if self.tables.device != device:
+            self.tables, self.angles = self.tables.to(device), self.angles.to(device)
+        return self.tables, self.angles
+
+    def graph_key(self):
+        """What a captured step has baked in: the table buffer's address, K, Q, the directions'
+        buffer and the domain."""
+        return (self.tables.data_ptr(), self.n_directions, self.knots, self.angles.data_ptr(),
+                self.domain)
+
+    def evaluate(self, rows, row_x, row_y, mask=None, dimension=None, **buffers):
+        """``ops.transport_error`` of the columns of ``rows`` with these tables and this domain
+        (``dimension`` given: ``rows`` is the geometry block)."""
+        tables, angles = self.tables_on(rows.device)
+        out = ops.transport_error(rows, row_x, row_y, tables, self.grid, angles, mask=mask,
+                                  dimension=dimension, **buffers)
+        self.last_rank2 = out[2]
+        return out
+
+    def seed_columns(self, cols, hold):
+        """tfrt_transport_error on the step's columns: the ranks go into the (K, N) int32
+        ``hold.buffers["rank2"]``; n_valid never leaves the device."""
+        K = self.n_directions
+        held = self._held(hold, "rank2", (K, cols.n), torch.int32, cols.rows.device,
+                          lambda: _lib.lib().tfrt_transport_error_workspace_bytes(cols.n, K))
+        self.evaluate(cols.rows, *_xy(self.rows), mask=cols.mask, dimension=3, grad=hold.g_fin,
+                      err=hold.err, **held)
+
+    def __call__(self, engine):
+        """The (n_finished, K) error terms through the generic path; the gradient rows come back
+        in ``backward``."""
+        self.rows_for(engine.dimension)           # (a field the engine's rays do not have)
+        fin = engine.finished_rays
+        if not bool(fin):
+            return torch.zeros((0, self.n_directions), dtype=torch.float64)
+        return _TransportTerms.apply(torch.stack([fin[f] for f in self.fields], dim=0), self)
+
+
+def _transport_terms(erf, v, rank2):
+    """The (n, K) terms of a TransportError evaluation from its ranks, the definition's operations
+    as torch ops; ``v``: the (k, n) float64 fields.  Zeros for a ray that does not count."""
+    tables, angles = erf.tables_on(v.device)
+    x0, ix, y0, iy = erf.grid
+    two = v.shape[0] == 2
+    Q = erf.knots
+    xi = (v[0] - x0) * ix
+    eta = (v[1] - y0) * iy if two else None
+    counts = rank2[0] >= 0
+    nv = counts.sum().double()
+    terms = []
+    for k in range(tables.shape[0]):
+        p = erf.directions[k, 0] * xi + erf.directions[k, 1] * eta if two else xi
+        z = ((rank2[k].double() * 0.5) / nv) * float(Q)
+        fm = torch.clamp(torch.floor(torch.where(counts, z, torch.zeros_like(z))),
+                         min=0.0, max=float(Q - 1))
+        m = fm.long()
+        t0 = tables[k][m]
+        d = p - (t0 + (z - fm) * (tables[k][m + 1] - t0))
+        terms.append(torch.where(counts, d * d, torch.zeros_like(d)))
+    return torch.stack(terms, dim=1).contiguous()
+
+
+class _TransportTerms(torch.autograd.Function):
+    """TransportError over the (k, n) field columns of the finished rays, no mask.  Returns the
+    (n, K) terms; the gradient has summed the K directions into a ray's rows, so one weight per
+    ray is all that can be applied afterwards (the optimiser passes ones)."""
+
+    @staticmethod
+    def forward(ctx, columns, erf):
+        rows = columns.detach().contiguous()
+        _, grad, rank2 = erf.evaluate(rows, 0, 1 if rows.shape[0] == 2 else -1)
+        ctx.save_for_backward(grad)
+        ctx.dtype = columns.dtype
+        return _transport_terms(erf, rows.double(), rank2)
+
+    @staticmethod
+    def backward(ctx, upstream):
+        grad, = ctx.saved_tensors
+        if upstream.shape[1] > 1 and not torch.equal(upstream,
+                                                     upstream[:, :1].expand_as(upstream)):
+            raise ValueError("TransportError: the upstream gradient must weigh the K terms of a "
+                             "ray alike")
+        return (upstream[:, 0] * grad).to(ctx.dtype), None
+
+
+class SpotError(_CoupledError):
+    """Rays that left the same object point must meet in one point -- wherever that is: the sum
+    over the finished rays of the squared distance to the CENTROID of their own group, the squared
+    RMS spot size times the ray count.  Where the spots lie (magnification, distortion, field
+    curvature) is left to the lens; no target is needed in advance.
+
+    ``fields``: one or two fields of a finished ray, e.g. ``("y_end", "z_end")``: geometry
+    fields, or the direction cosines ``x_dir``, ``y_dir``, ``z_dir`` of the ray's last link --
+    ``("y_dir", "z_dir")`` asks the rays of one object point to leave PARALLEL (collimation, afocal
+    systems: a spot in direction space; ``centroids()`` are then mean direction cosines).  The
+    direction, its non-finite case, the chain rule back onto the start and end rows and the
+    float32 caveat (a direction is good to about ``eps32 * max|coordinate| / L``) are
+    ``DensityError``'s.
+    ``groups``: an integer tensor or array of shape (N,), one label per SOURCE ray in the source's
+    own order -- finished rays look theirs up through the source-ray index the trace carries --, or
+    a callable on the source's field dict that returns such labels (evaluated and cached as
+    ``GoalError.table`` is; it then needs ``n_groups``).  The labels are kept as int32 on the
+    device (``labels``) and may be overwritten in place between steps (a replayed graph reads the
+    buffer).  Labels outside ``[0, n_groups)`` -- ``-1`` -- exclude a ray.  ``n_groups``: G, by
+    default ``max + 1`` of a tensor, read once here; at most 2**20.  ``domain``:
+    ``((x0, x1), (y0, y1))``, or ``((x0, x1),)`` for one field: rays outside it take a penalty
+    instead of pulling their spot.
+
+    For every finished ray of the trace, coordinates converted to float64, every operation rounded
+    on its own, the first case that applies:
+
+    * a non-finite coordinate: no error, zero gradient;
+    * a label outside ``[0, n_groups)``: no error, zero gradient;
+    * outside the closed domain on any axis: the ray is in no spot and adds
+      ``oob_weight * (ex**2 + ey**2)``, ``ex = max(x0 - x, 0) + max(x - x1, 0)``; its gradient is
+      the derivative of that expression;
+    * inside: ``qx = min(max(rint((x - x0) * qsx), 0), 2**qbits)`` (half to even),
+      ``qsx = 2**qbits / (x1 - x0)``, ``qbits = min(52, 62 - bit_length(N))``; ``{1, qx, qy}`` is
+      added to the ray's group in an int64 table -- integer addition is associative, so the table
+      does not depend on the order of the atomics.
+
+    A group with rays has the centroid ``cx = x0 + (Sx / count) / qsx``; a ray inside has
+    ``dx = x - cx``, the error terms ``dx**2`` and ``dy**2`` and the gradient ``2 * dx``, ``2 * dy``.
+    That gradient is exact without differentiating through the centroid, because the residuals of
+    a group sum to zero (up to the quantisation: at most half a step ``1 / qsx`` per centroid).
+    ``error = sum of the terms + sum of the penalties`` over ``len(fields) * n_finished`` terms;
+    every sum has a fixed shape and order: two runs give the same bits.
+
+    It is an ordinary ``error_function(engine)`` (the generic path: ``ops.spot_error`` over the
+    finished rays' columns under a ``torch.autograd.Function``), which also serves sources that are
+    not traced in place, ``deterministic=True``, fewer than 4,096 rays and 2-D engines
+    (``FusedStep.eligible2d`` is false).  Its ``backward`` returns ``upstream * gradient``: exact
+    when ``upstream`` is constant within a group (the optimiser passes ones) -- a radiant power
+    per ray belongs in ``weights`` (below), which moves the centroid with it, not in ``upstream``;
+    with a direction field the two fields of a ray must also carry the same upstream factor (a
+    ``ValueError`` otherwise), because the kernel's chain rule sums both into the geometry rows.  On a 3-D engine that traces
+    its source in place the optimiser runs it on the fused, graph-replayed step under the
+    conditions of a ``RowwiseError`` (``FusedStep._rowwise3d`` with ``tfrt_spot_error`` in the
+    place of ``fn`` and its autograd), with the same kernels and the same ``qbits``.  One process:
+    with ray shards over several ranks the generic path runs and each shard forms the centroids of
+    its own rays.
+
+    ``weights``: None -- every ray of a spot counts alike --, or a radiant power per SOURCE ray,
+    given, normalised (divided by the maximum, float64, values in [0, 1]), kept as ``weights`` and
+    looked up exactly as ``DensityError``'s: a tensor or array of shape (N,), or a callable on the
+    source's field dict (an apodised pupil, a spectrum).  The spot is then the WEIGHTED one.  With
+    ``wbits = min(20, 62 - bit_length(N) - ceil(qbits / 2))`` (``ops.spot_wbits(N)``) a ray's
+    weight ``w`` enters as the integer ``wq = rint(w * 2**wbits)`` (half to even), and
+    ``wr = wq * 2**-wbits`` -- exact -- is the weight used everywhere, so the weighted residuals of
+    a group sum to zero in the quantised quantities.  After the label's case above:
+
+    * no source ray, ``w`` not finite or not in [0, 1], or ``wq == 0``: the ray is in no spot, no
+      error, zero gradient;
+    * outside the domain: the penalty and its gradient are multiplied by ``wr`` last;
+    * inside: with ``h = qbits // 2`` the product ``wq * qx`` is added in two limbs, so that the
+      position keeps its full ``qbits``: ``Xhi += wq * (qx >> h)``, ``Xlo += wq * (qx & (2**h - 1))``
+      (y alike), ``W += wq``, ``count += 1`` -- a record is eight int64
+      ``{W, Xhi, Xlo, Yhi, Ylo, count, 0, 0}``, every sum below ``N * 2**wbits * 2**ceil(qbits / 2)
+      < 2**62``.
+
+    A group with ``W > 0`` has ``X = ldexp(Xhi, h) + Xlo`` and the centroid
+    ``cx = x0 + (X / W) / qsx``; a ray inside has ``dx = x - cx``, the terms ``wr * (dx * dx)`` and
+    ``wr * (dy * dy)`` and the gradient ``(2 * dx) * wr``, ``(2 * dy) * wr`` -- again exact without
+    a derivative of the centroid, because the WEIGHTED residuals of a group sum to zero.  The
+    number of terms stays ``len(fields) * n_finished``.  Weighted and unweighted run on the same
+    paths; the weighted one has kernels of its own (tfrt_spot_error_weighted: a table of six planes
+    in LDS up to ``ops.SPOT_WEIGHTED_LDS_GROUPS`` groups, global atomics above).
+
+    ``last_acc`` is the (G, 4) int64 table ``{count, Sx, Sy, 0}`` of the last evaluation -- with
+    weights the (G, 8) table above --, ``centroids()`` the (G, k) float64 centroids made from it,
+    weighted with weights (NaN for a group without rays).
+    ``splat_variant`` (0: by G; 1: table in LDS; 2: global atomics) is tfrt_spot_error's, for
+    measuring."""
+
+    splat_variant = 0
+
+    def __init__(self, fields, groups, domain, oob_weight=0.0, n_groups=None, weights=None):
+        from . import config
+        self.fields, self.domain = _fields_and_domain("SpotError", fields, domain)
+        self.rows = [_FIELDS3.index(f) for f in self.fields]
+        self.has_direction = any(f.endswith("_dir") for f in self.fields)
+        self.oob_weight = float(oob_weight)
+        if not (self.oob_weight >= 0.0 and np.isfinite(self.oob_weight)):
+            raise ValueError("SpotError: oob_weight must be finite and >= 0")
+        self.groups = groups
+        self.labels = None
+        self._caches = {}
+        if callable(groups):
+            if n_groups is None:
+                raise ValueError("SpotError: callable groups need n_groups")
+        else:
+            self.labels = self._as_labels(groups, config.get_device())
+            if n_groups is None:
+                if self.labels.numel() == 0:
+                    raise ValueError("SpotError: no labels and no n_groups")
+                n_groups = int(self.labels.max()) + 1
+        try:
+            self.n_groups = int(n_groups)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"SpotError: n_groups must be an integer, got {n_groups!r}") from e
+        if not 1 <= self.n_groups <= ops.SPOT_MAX_GROUPS:
+            raise ValueError(f"SpotError: n_groups must lie in 1 .. {ops.SPOT_MAX_GROUPS}, got "
+                             f"{n_groups!r}")
+        self._grids = {}
+        self.last_acc = None
+        self.last_grid = None
+        self.last_qbits = None
+        _init_weights(self, "SpotError", weights)
+        if self.weights is not None and self.labels is not None \
+                and self.weights.numel() != self.labels.numel():
+            raise ValueError(f"SpotError: {self.weights.numel()} weights for "
+                             f"{self.labels.numel()} labels -- one of each per source ray")
+
+    @staticmethod
+    def _as_labels(groups, device):
+        g = groups if isinstance(groups, torch.Tensor) else torch.as_tensor(np.asarray(groups))
+        if g.dim() != 1 or g.dtype.is_floating_point or g.dtype.is_complex or g.dtype == torch.bool:
+            raise ValueError("SpotError: groups must be integers of shape (N,), one label per "
+                             f"source ray; got shape {tuple(g.shape)}, {g.dtype}")
+        return g.detach().to(device=device, dtype=torch.int32).contiguous()
+
+    def labels_of(self, src):
+        """The int32 label buffer of the source set ``src`` on its device, one label per source
+        ray: the tensor given (moved once; a new buffer re-captures a graph), or the callable's
+        result, cached by the versions of the source's fields as ``GoalError.table`` is."""
+        return _source_buffer(self, "labels", self.groups, self._as_labels, src, "SpotError",
+                              "label")
+
+    def grid_for(self, n_source):
+        """(qbits, grid constants) for a source of ``n_source`` rays: both paths of a step use the
+        source's ray count, so the fused and the generic step quantise alike."""
+        hit = self._grids.get(n_source)
+        if hit is None:
+            qbits = ops.spot_qbits(n_source)
+            hit = self._grids[n_source] = (qbits, ops.spot_grid(self.domain, qbits))
+        return hit
+
+    def graph_key(self):
+        """What a captured step has baked in: the label buffer's address, the weight buffer's
+        with ``wbits``, and the constants."""
+        lab, w = self.labels, self.weights
+        return (None if lab is None else (lab.data_ptr(), tuple(lab.shape)), self.n_groups,
+                self.domain, self.oob_weight, self.splat_variant) + _weights_key(self) \
+            + (None if w is None else ops.spot_wbits(w.numel()),)
+
+    def evaluate(self, rows, row_x, row_y, labels, mask=None, perm=None, dimension=None,
+                 weights=None, **buffers):
+        """``ops.spot_error`` of the columns of ``rows`` with these labels, domain and weight
+        (``dimension`` given: ``rows`` is the geometry block, ``row_x`` / ``row_y`` field codes;
+        ``weights``: the buffer of ``weights_of``)."""
+        qbits, grid = self.grid_for(labels.numel())
+        out = ops.spot_error(rows, row_x, row_y, labels, self.n_groups, grid, self.oob_weight,
+                             mask=mask, perm=perm, variant=self.splat_variant, qbits=qbits,
+                             dimension=dimension, weights=weights,
+                             wbits=None if weights is None else ops.spot_wbits(labels.numel()),
+                             **buffers)
+        self.last_acc, self.last_grid, self.last_qbits = out[2], grid, qbits
+        return out
+
+    def seed_columns(self, cols, hold):
+        """tfrt_spot_error on the step's columns: it reads the source's label buffer and the
+        trace's order ``cols.perm`` -- the kernel looks a column's label up itself, so no permuted
+        copy can go stale when a source is re-drawn and re-ordered inside the graph -- and, looked
+        up like the labels, the weights; the group records go into ``hold.buffers["acc"]``,
+        (G, 4), with weights (G, 8)."""
+        labels, weights = self.labels_of(cols.src), self.weights_of(cols.src)
+        G = self.n_groups
+        held = self._held(hold, "acc", (G, 4 if weights is None else 8), torch.int64,
+                          cols.rows.device,
+                          lambda: _lib.lib().tfrt_spot_error_workspace_bytes(cols.n, G))
+        self.evaluate(cols.rows, *_xy(self.rows), labels, mask=cols.mask, perm=cols.perm,
+                      dimension=3, weights=weights, grad=hold.g_fin, err=hold.err, **held)
+
+    def centroids(self):
+        """(G, k) float64 centroids of the last evaluation, NaN for a group without rays."""
+        if self.last_acc is None:
+            raise RuntimeError("SpotError: no evaluation yet")
+        return ops.spot_centroids(self.last_acc, self.last_grid, len(self.fields), self.last_qbits)
+
+    def __call__(self, engine):
+        """The (n_finished, k) error terms through the generic path; the gradient rows come back
+        in ``backward``."""
+        codes = self.rows_for(engine.dimension)
+        fin = engine.finished_rays
+        if not bool(fin):
+            return torch.zeros((0, len(self.fields)), dtype=torch.float64)
+        labels = self.labels_of(engine._trace_src)
+        block, weights, ids, dim, codes = self._finished_block(engine, fin, codes, ids=True)
+        return _SpotTerms.apply(block, self, labels, ids, weights, dim, codes)
+
+
+def _spot_terms(erf, v, labels, ids, acc, weights, inside=None):
+    """The (n, k) terms of a SpotError evaluation from its records: an inside ray's squared
+    distances to its group's centroid (``inside``, (k, n), where the caller has them already), a
+    penalised ray's ``oob_weight * ex**2`` per field, both times ``wr`` with ``weights``; zeros for
+    a ray in no spot.  ``v``: the (k, n) float64 fields."""
+    k = v.shape[0]
+    lo = torch.tensor([d[0] for d in erf.domain], dtype=torch.float64, device=v.device)[:, None]
+    hi = torch.tensor([d[1] for d in erf.domain], dtype=torch.float64, device=v.device)[:, None]
+    zero = torch.zeros((), dtype=torch.float64, device=v.device)
+    ex = torch.maximum(lo - v, zero) + torch.maximum(v - hi, zero)
+    out = ((v < lo) | (v > hi)).any(dim=0, keepdim=True)
+    # (a ray that does not count has a zero gradient and, outside, no penalty either: its label
+    # and its weight decide, which the kernel has looked up)
+    s = ids.long()
+    s_ok = (s >= 0) & (s < labels.numel())
+    s = s.clamp(0, labels.numel() - 1)
+    lab = labels[s]
+    spot = s_ok & (lab >= 0) & (lab < erf.n_groups) & torch.isfinite(v).all(dim=0)
+    if inside is None:
+        centre = ops.spot_centroids(acc, erf.last_grid, k, erf.last_qbits).t()[
+            :, lab.long().clamp(0, erf.n_groups - 1)]
+        dv = v - centre
+        inside = dv * dv
+    penalty = erf.oob_weight * (ex * ex)
+    if weights is not None:
+        wbits = ops.spot_wbits(labels.numel())
+        w = weights[s]
+        wq = torch.where((w >= 0.0) & (w <= 1.0), torch.round(w * float(np.ldexp(1.0, wbits))),
+                         torch.zeros_like(w))
+        wr = wq * float(np.ldexp(1.0, -wbits))
+        spot = spot & (wq > 0)
+        penalty, inside = penalty * wr, wr * inside
+    return torch.where(spot[None, :], torch.where(out, penalty, inside), zero).t().contiguous()
+
+
+class _SpotTerms(torch.autograd.Function):
+    """SpotError over the finished rays, no mask; ``ids``: the source ray of every column.
+    ``dimension=None, codes=None``: ``block`` is the (k, n) field columns; else it is the
+    (2 * dimension, n) geometry block and ``codes`` the field codes (a direction field).  Returns
+    the (n, k) terms (``_spot_terms``): a penalised ray's ``oob_weight * ex**2`` per field, an
+    inside ray's squared distances to its group's centroid.  Over plain columns without
+    ``weights`` the latter are (gradient / 2)**2 -- the kernel's own dx * dx, the halving is
+    exact --; with ``weights`` or a direction field that is no longer the term, and they come from
+    the records' centroids."""
+
+    @staticmethod
+    def forward(ctx, block, erf, labels, ids, weights=None, dimension=None, codes=None):
+        rows = block.detach().contiguous()
+        ctx.chained = codes is not None
+        if codes is None:
+            codes = (0, 1)[:rows.shape[0]]
+        err, grad, acc = erf.evaluate(rows, *_xy(codes), labels, perm=ids, dimension=dimension,
+                                      weights=weights)
+        ctx.save_for_backward(grad)
+        ctx.dtype = block.dtype
+        if ctx.chained:
+            link = ops._link_torch(rows, dimension)
+            v = torch.stack([ops._link_field_torch(link, c, dimension) for c in codes], dim=0)
+            return _spot_terms(erf, v, labels, ids, acc, weights)
+        half = 0.5 * grad
+        return _spot_terms(erf, rows.double(), labels, ids, acc, weights,
+                           inside=half * half if weights is None else None)
+
+    @staticmethod
+    def backward(ctx, upstream):
+        grad, = ctx.saved_tensors
+        if not ctx.chained:
+            return (upstream.t() * grad).to(ctx.dtype), None, None, None, None, None, None
+        # the kernel's chain rule has summed both fields' gradients into the rows: one weight per
+        # ray is all that can be applied afterwards (the optimiser passes ones)
+        if upstream.shape[1] == 2 and not torch.equal(upstream[:, 0], upstream[:, 1]):
+            raise ValueError("SpotError with a direction field: the upstream gradient must weigh "
+                             "both fields of a ray alike")
+        return (upstream[:, 0] * grad).to(ctx.dtype), None, None, None, None, None, None
+
+
+# the coupled errors: all finished rays of a step enter one evaluation (one process)
+_COUPLED = (DensityError, SpotError, TransportError)
+
+
+class SumError:
+    """A weighted sum of error terms on ONE step: ``error = sum_k c_k * term_k``.  A real design
+    is never one term: transport to find the target and density for the detail, a spot size with
+    a magnification pinned by a goal, a near field and a far field at once.  Every term reads the
+    same finished rays of one trace and the reverse sweep is linear in its seed, so the combined
+    step is one trace, K error evaluations, one combination and one reverse sweep.
+
+    ``terms``: 1 to 8 distinct instances of ``GoalError``, ``DensityError``, ``SpotError`` or
+    ``TransportError``; a ``RowwiseError``, a nested ``SumError`` or the same object twice is a
+    ValueError.  ``weights``: K finite values >= 0, default all ones, kept as the (K,) float64
+    device tensor ``weights``; ``set_weights(values)`` validates on the host and overwrites that
+    buffer in place, so a replayed graph sees the new values without a re-capture (as
+    ``TransportError.set_goal``).  A weight of 0 switches a term off for a phase; the term is
+    still evaluated.  ``reduce``: ``"sum"``, ``c_k = w_k`` and ``term_k`` the term's error sum; or
+    ``"mean"``, ``c_k = w_k / terms_k`` with ``terms_k`` the term's own count of error terms
+    (0.0 for a term without any), read on the device.  Every product and every sum is rounded on
+    its own, the terms in index order (tfrt_error_combine); the sum reports itself as ONE error
+    term, ``{E, 1, E}``, as a ``DensityError`` does.
+
+    After an evaluation ``last_errors`` is the (K, 3) tensor of the terms' own triples {sum, terms,
+    mean} and ``last_coefficients`` the (K,) ``c_k``; each term keeps its own ``last_hq`` /
+    ``centroids()`` / ``last_rank2`` as when it runs alone.
+
+    It is an ordinary ``error_function(engine)`` -- the generic path returns the (1,) tensor
+    ``sum_k c_k * term_k(engine).sum()`` (``terms_k = numel``) under torch autograd, which serves
+    2-D engines, fewer than 4,096 rays, ``deterministic=True`` and sources not traced in place.
+    On a 3-D engine that traces its source in place the optimiser runs it on the fused,
+    graph-replayed step under the conditions of a ``DensityError``: every term evaluates into a
+    seed block of its own (a ``GoalError`` through tfrt_goal_error_columns, its goal row looked up
+    through the trace's order inside the kernel), and one tfrt_error_combine launch writes the
+    step's seed block and error.  One process."""
+
+    on_columns = True
+
+    def __init__(self, terms, weights=None, reduce="sum"):
+        from . import config
+        try:
+            terms = tuple(terms)
+        except TypeError as e:
+            raise ValueError("SumError: terms must be a sequence of error terms") from e
+        if not 1 <= len(terms) <= ops.COMBINE_MAX_TERMS:
+            raise ValueError(f"SumError: 1 .. {ops.COMBINE_MAX_TERMS} terms, got {len(terms)}")
+        for t in terms:
+            if isinstance(t, SumError):
+                raise ValueError("SumError: a nested SumError is not supported -- list its terms "
+                                 "(and multiply the weights) instead")
+            if isinstance(t, RowwiseError):
+                raise ValueError("SumError: a RowwiseError cannot be a term (its error is torch "
+                                 "code of its own); state it as a GoalError")
+            if not isinstance(t, (GoalError,) + _COUPLED):
+                raise ValueError("SumError: terms must be GoalError, DensityError, SpotError or "
+                                 f"TransportError instances, got {type(t).__name__}")
+        if len(set(id(t) for t in terms)) != len(terms):
+            raise ValueError("SumError: the same term object is listed twice (a term keeps the "
+                             "buffers of its last evaluation); make a second instance")
+        if reduce not in ("sum", "mean"):
+            raise ValueError(f"SumError: reduce must be 'sum' or 'mean', got {reduce!r}")
+        self.terms, self.reduce = terms, reduce
+        values = self._as_values(len(terms), [1.0] * len(terms) if weights is None else weights)
+        self.weights = torch.as_tensor(values).to(config.get_device())
+        # every term's rows, in term order: a step's buffers are keyed on them
+        self.rows = [r for t in terms for r in t.rows]
+        self.fields = tuple(t.fields for t in terms)
+        self.last_errors = self.last_coefficients = None
+
+    @staticmethod
+    def _as_values(K, weights):
+        try:
+            w = np.asarray(weights.detach().cpu() if isinstance(weights, torch.Tensor)
+                           else weights, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"SumError: weights must be {K} numbers, got {weights!r}") from e
+        if w.shape != (K,):
+            raise ValueError(f"SumError: {K} weights for {K} terms, got shape {w.shape}")
+        if not np.isfinite(w).all() or (w < 0).any():
+            raise ValueError(f"SumError: weights must be finite and >= 0, got {w.tolist()}")
+        return np.ascontiguousarray(w)
+
+    def set_weights(self, values):
+        """Other weights, checked on the host and copied into the device buffer there is."""
+        self.weights.copy_(torch.as_tensor(self._as_values(len(self.terms), values)))
+
+    def weights_on(self, device):
+        """The weight buffer on ``device`` (moved once; a new buffer re-captures a graph)."""
+        if self.weights.device != device:
+            self.weights = self.weights.to(device)
+        return self.weights
+
+    def rows_for(self, dimension):
+        return [r for t in self.terms for r in t.rows_for(dimension)]
+
+    def graph_key(self):
+        """What a captured step has baked in: the terms' keys, the weight buffer's address and
+        ``reduce``."""
+        return (tuple((id(t), t.graph_key()) for t in self.terms), self.weights.data_ptr(),
+                self.reduce)
+
+    def __call__(self, engine):
+        """The error as a (1,) tensor through the generic path: the terms called one by one, then
+        tfrt_error_combine's operations in its order as torch ops."""
+        total, triples, coeffs = None, [], []
+        for k, term in enumerate(self.terms):
+            e = term(engine)
+            s = e.sum().double()
+            w = self.weights_on(s.device)[k]
+            if self.reduce == "sum":
+                c = w
+            else:
+                c = w / float(e.numel()) if e.numel() > 0 else torch.zeros_like(w)
+            p = c * s
+            total = p if total is None else total + p
+            with torch.no_grad():
+                n = torch.full_like(w, float(e.numel()))
+                triples.append(torch.stack([s.detach(), n, s.detach() / n if e.numel() > 0
+                                            else torch.full_like(w, float("nan"))]))
+                coeffs.append(c.detach())
+        self.last_errors, self.last_coefficients = torch.stack(triples), torch.stack(coeffs)
+        return total.reshape(1)
+

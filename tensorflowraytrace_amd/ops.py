@@ -1289,17 +1289,50 @@ def gather_rows(src, index, n_valid=None, out=None):
 
 
 def _check_field_codes(what, rows, row_x, row_y, dimension):
-    """``dimension`` given: ``rows`` is the (2 * dimension, n) geometry block and ``row_x`` /
-    ``row_y`` are field codes (tfrt_density_error_fields)."""
-    if dimension not in (2, 3):
-        raise ValueError(f"{what}: dimension must be None, 2 or 3, got {dimension!r}")
-    if rows.shape[0] != 2 * dimension:
-        raise ValueError(f"{what}: a {dimension}-D geometry block has {2 * dimension} rows, got "
-                         f"{rows.shape[0]}")
-    top = 3 * dimension
+    """``dimension`` None: ``row_x`` / ``row_y`` are rows of the (k, n) block ``rows``; given:
+    ``rows`` is the (2 * dimension, n) geometry block and they are field codes
+    (tfrt_density_error_fields).  The C entries bound a code by a constant, not by the block."""
+    top, noun = rows.shape[0], "rows"
+    if dimension is not None:
+        if dimension not in (2, 3):
+            raise ValueError(f"{what}: dimension must be None, 2 or 3, got {dimension!r}")
+        if rows.shape[0] != 2 * dimension:
+            raise ValueError(f"{what}: a {dimension}-D geometry block has {2 * dimension} rows, "
+                             f"got {rows.shape[0]}")
+        top, noun = 3 * dimension, "field codes"
     if not (0 <= row_x < top and -1 <= row_y < top and row_x != row_y):
-        raise ValueError(f"{what}: field codes must be distinct and lie in [0, {top}), got "
+        raise ValueError(f"{what}: {noun} must be distinct and lie in [0, {top}), got "
                          f"{row_x}, {row_y}")
+
+
+def _column_buffers(what, rows, grad, err, mask=None, perm=None):
+    """What the column errors (density_error, spot_error, transport_error, goal_error_columns)
+    ask of their per-column arguments, for the (k, n) block ``rows``: ``mask`` and ``perm``, where
+    given, contiguous int32 with at least n entries; ``grad`` float64 (k, at least n), zeros made
+    here by default; ``err`` three float64.  Returns (grad, err)."""
+    k, n = rows.shape
+    for name, index in (("mask", mask), ("perm", perm)):
+        if index is not None and (index.dtype != torch.int32 or index.numel() < n
+                                  or not index.is_contiguous()):
+            raise ValueError(f"{what}: {name} must be contiguous int32, one entry per column")
+    if grad is None:
+        grad = torch.zeros((k, n), dtype=torch.float64, device=rows.device)
+    elif grad.dtype != torch.float64 or grad.dim() != 2 or grad.shape[0] != k or grad.shape[1] < n:
+        raise ValueError(f"{what}: grad must be float64 ({k}, {n})")
+    if err is None:
+        err = torch.empty(3, dtype=torch.float64, device=rows.device)
+    return grad, err
+
+
+def _column_workspace(what, rows, grad, workspace, workspace_bytes, *tensors):
+    """The GPU path's share of the same: every tensor on the device, ``rows`` and ``grad`` with
+    contiguous columns, and the ``workspace`` given or one of ``workspace_bytes()`` bytes."""
+    _need_gpu(rows, grad, *tensors)
+    if (rows.shape[1] > 0 and rows.stride(1) != 1) or (grad.shape[1] > 0 and grad.stride(1) != 1):
+        raise ValueError(f"{what}: rows and grad must have contiguous columns")
+    if workspace is None:
+        workspace = torch.empty(max(workspace_bytes(), 1), dtype=torch.uint8, device=rows.device)
+    return workspace
 
 
 def _link_torch(rows, dim):
@@ -1416,15 +1449,11 @@ def density_grid(domain, nx, ny=None):
     return (x0, x1, sx, y0, y1, float(np.float64(ny) / (np.float64(y1) - np.float64(y0))))
 
 
-def _check_weights(what, weights, perm, n):
-    """``weights``: contiguous float64, one per SOURCE ray; ``perm``: contiguous int32, one entry
-    per column."""
+def _check_weights(what, weights):
+    """``weights``: contiguous float64, one per SOURCE ray."""
     if weights.dtype != torch.float64 or weights.dim() != 1 or not weights.is_contiguous():
         raise ValueError(f"{what}: weights must be a contiguous float64 vector, one weight per "
                          "source ray")
-    if perm is not None and (perm.dtype != torch.int32 or perm.numel() < n
-                             or not perm.is_contiguous()):
-        raise ValueError(f"{what}: perm must be contiguous int32, one entry per column")
 
 
 def _source_weights(weights, perm, n):
@@ -1446,7 +1475,8 @@ def density_error(rows, row_x, row_y, goal, grid, oob_weight=0.0, mask=None, gra
     mask[i] >= 0.  Returns (err {sum, 1, mean}, grad (k, n) float64, hq int64 of the goal's
     shape): rows ``row_x`` / ``row_y`` of ``grad`` are written for every column, other rows only
     when ``grad`` is made here (zeros).  ``grad``, ``err``, ``hq``, ``workspace`` (uint8): buffers
-    to reuse -- with all four given a CUDA call allocates nothing.
+    to reuse -- with all four given a CUDA call allocates nothing.  ``row_x`` / ``row_y`` must be
+    distinct rows of the block; a ValueError otherwise, before anything is launched.
 
     ``dimension`` 2 or 3 (tfrt_density_error_fields): ``rows`` is the (2 * dimension, n) geometry
     block of the finished rays (start rows, then end rows) and ``row_x`` / ``row_y`` are FIELD
@@ -1472,23 +1502,18 @@ def density_error(rows, row_x, row_y, goal, grid, oob_weight=0.0, mask=None, gra
                          "and (nx,) for one")
     if nx * ny > DENSITY_MAX_BINS:
         raise ValueError(f"density_error: more than {DENSITY_MAX_BINS} bins")
-    k, n = rows.shape
-    if dimension is not None:
-        _check_field_codes("density_error", rows, row_x, row_y, dimension)
+    n = rows.shape[1]
+    _check_field_codes("density_error", rows, row_x, row_y, dimension)
     if weights is not None:
-        _check_weights("density_error", weights, perm, n)
+        _check_weights("density_error", weights)
         n_source = weights.numel() if n_source is None else int(n_source)
         if not 0 <= n_source <= weights.numel():
             raise ValueError("density_error: n_source exceeds the weights given")
-    dev = rows.device
-    if grad is None:
-        grad = torch.zeros((k, n), dtype=torch.float64, device=dev)
-    if dimension is not None and grad.shape[0] != k:
-        raise ValueError(f"density_error: grad needs {k} rows")
-    if err is None:
-        err = torch.empty(3, dtype=torch.float64, device=dev)
+    # (the source ray of a column is looked up for its weight only)
+    grad, err = _column_buffers("density_error", rows, grad, err, mask,
+                                perm if weights is not None else None)
     if hq is None:
-        hq = torch.empty(goal.shape, dtype=torch.int64, device=dev)
+        hq = torch.empty(goal.shape, dtype=torch.int64, device=rows.device)
     x0, x1, sx, y0, y1, sy = grid
     if not rows.is_cuda:
         _density_error_cpu(rows, row_x, row_y, goal, grid, float(oob_weight), mask, grad, err, hq,
@@ -1496,13 +1521,10 @@ def density_error(rows, row_x, row_y, goal, grid, oob_weight=0.0, mask=None, gra
                            None if workspace is None
                            else workspace[:8 * nx * ny].view(torch.float64))
         return err, grad, hq
-    _need_gpu(rows, goal, mask, grad, err, hq, weights, perm)
-    if rows.stride(1) != 1 or grad.stride(1) != 1:
-        raise ValueError("density_error: rows and grad must have contiguous columns")
     L = _lib.lib()
-    wsb = L.tfrt_density_error_workspace_bytes(n, nx, ny)
-    if workspace is None:
-        workspace = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    workspace = _column_workspace(
+        "density_error", rows, grad, workspace,
+        lambda: L.tfrt_density_error_workspace_bytes(n, nx, ny), goal, mask, err, hq, weights, perm)
     if weights is not None:
         # (the field-code form covers plain rows: codes below 2 * dimension are rows of the block)
         check(L.tfrt_density_error_weighted(
@@ -1718,30 +1740,18 @@ def transport_error(rows, row_x, row_y, tables, grid, angles, mask=None, dimensi
     if k > 6 or not (0 <= row_x < top and -1 <= row_y < top and row_x != row_y):
         raise ValueError(f"transport_error: rows must be distinct position rows in [0, {top}), "
                          f"got {row_x}, {row_y}")
-    dev = rows.device
-    if grad is None:
-        grad = torch.zeros((k, n), dtype=torch.float64, device=dev)
-    if err is None:
-        err = torch.empty(3, dtype=torch.float64, device=dev)
+    grad, err = _column_buffers("transport_error", rows, grad, err, mask)
     if rank2 is None:
-        rank2 = torch.empty((K, n), dtype=torch.int32, device=dev)
+        rank2 = torch.empty((K, n), dtype=torch.int32, device=rows.device)
     if rank2.dtype != torch.int32 or tuple(rank2.shape) != (K, n) or not rank2.is_contiguous():
         raise ValueError(f"transport_error: rank2 must be contiguous int32 ({K}, {n})")
-    if grad.dtype != torch.float64 or grad.dim() != 2 or grad.shape[0] != k or grad.shape[1] < n:
-        raise ValueError(f"transport_error: grad must be float64 ({k}, {n})")
-    if mask is not None and (mask.dtype != torch.int32 or mask.numel() < n
-                             or not mask.is_contiguous()):
-        raise ValueError("transport_error: mask must be contiguous int32, one entry per column")
     if not rows.is_cuda:
         _transport_error_cpu(rows, row_x, row_y, tables, grid, angles, mask, grad, err, rank2)
         return err, grad, rank2
-    _need_gpu(rows, tables, angles, mask, grad, err, rank2)
-    if rows.stride(1) != 1 or grad.stride(1) != 1:
-        raise ValueError("transport_error: rows and grad must have contiguous columns")
     L = _lib.lib()
-    wsb = L.tfrt_transport_error_workspace_bytes(n, K)
-    if workspace is None:
-        workspace = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    workspace = _column_workspace(
+        "transport_error", rows, grad, workspace,
+        lambda: L.tfrt_transport_error_workspace_bytes(n, K), tables, angles, mask, err, rank2)
     x0, ix, y0, iy = grid
     check(L.tfrt_transport_error(
         _p(rows), rows.stride(0), n, _DT[rows.dtype], 3 if dimension is None else int(dimension),
@@ -1871,31 +1881,21 @@ def spot_error(rows, row_x, row_y, group, n_groups, grid, oob_weight=0.0, mask=N
                          "source ray")
     if not 1 <= n_groups <= SPOT_MAX_GROUPS:
         raise ValueError(f"spot_error: n_groups must lie in 1 .. {SPOT_MAX_GROUPS}")
-    k, n = rows.shape
-    if dimension is not None:
-        _check_field_codes("spot_error", rows, row_x, row_y, dimension)
-    if perm is not None and (perm.dtype != torch.int32 or perm.numel() < n
-                             or not perm.is_contiguous()):
-        raise ValueError("spot_error: perm must be contiguous int32, one entry per column")
+    n = rows.shape[1]
+    _check_field_codes("spot_error", rows, row_x, row_y, dimension)
     if qbits is None:
         qbits = spot_qbits(group.numel())
     record = 4
     if weights is not None:
-        _check_weights("spot_error", weights, None, n)
+        _check_weights("spot_error", weights)
         if weights.numel() != group.numel():
             raise ValueError("spot_error: one weight per label")
         if wbits is None:
             wbits = spot_wbits(group.numel())
         record = 8
-    dev = rows.device
-    if grad is None:
-        grad = torch.zeros((k, n), dtype=torch.float64, device=dev)
-    if dimension is not None and grad.shape[0] != k:
-        raise ValueError(f"spot_error: grad needs {k} rows")
-    if err is None:
-        err = torch.empty(3, dtype=torch.float64, device=dev)
+    grad, err = _column_buffers("spot_error", rows, grad, err, mask, perm)
     if acc is None:
-        acc = torch.empty((n_groups, record), dtype=torch.int64, device=dev)
+        acc = torch.empty((n_groups, record), dtype=torch.int64, device=rows.device)
     if tuple(acc.shape) != (n_groups, record) or acc.dtype != torch.int64 \
             or not acc.is_contiguous():
         raise ValueError(f"spot_error: acc must be contiguous int64 of shape (n_groups, {record})")
@@ -1912,13 +1912,11 @@ def spot_error(rows, row_x, row_y, group, n_groups, grid, oob_weight=0.0, mask=N
                         grad, err, acc, int(qbits), dimension, weights,
                         None if wbits is None else int(wbits))
         return err, grad, acc
-    _need_gpu(rows, group, mask, perm, grad, err, acc, weights)
-    if rows.stride(1) != 1 or grad.stride(1) != 1:
-        raise ValueError("spot_error: rows and grad must have contiguous columns")
     L = _lib.lib()
-    wsb = L.tfrt_spot_error_workspace_bytes(n, n_groups)
-    if workspace is None:
-        workspace = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    workspace = _column_workspace(
+        "spot_error", rows, grad, workspace,
+        lambda: L.tfrt_spot_error_workspace_bytes(n, n_groups), group, mask, perm, err, acc,
+        weights)
     if weights is not None:
         # (the field-code form covers plain rows: codes below 2 * dimension are rows of the block)
         check(L.tfrt_spot_error_weighted(
@@ -2063,30 +2061,15 @@ def goal_error_columns(rows, fields, goal, mask=None, perm=None, by_ray=False, n
     n_source = rays if n_source is None else int(n_source)
     if not 0 <= n_source <= rays:
         raise ValueError(f"goal_error_columns: n_source must lie in 0 .. {rays}")
-    if mask is not None and (mask.dtype != torch.int32 or mask.numel() < n
-                             or not mask.is_contiguous()):
-        raise ValueError("goal_error_columns: mask must be contiguous int32, one entry per column")
-    if perm is not None and (perm.dtype != torch.int32 or perm.numel() < n
-                             or not perm.is_contiguous()):
-        raise ValueError("goal_error_columns: perm must be contiguous int32, one entry per column")
-    dev = rows.device
-    if grad is None:
-        grad = torch.zeros((k, n), dtype=torch.float64, device=dev)
-    if err is None:
-        err = torch.empty(3, dtype=torch.float64, device=dev)
-    if grad.dtype != torch.float64 or grad.dim() != 2 or grad.shape[0] != k or grad.shape[1] < n:
-        raise ValueError(f"goal_error_columns: grad must be float64 ({k}, {n})")
+    grad, err = _column_buffers("goal_error_columns", rows, grad, err, mask, perm)
     strides = (1, nf) if by_ray else (rays, 1)
     if not rows.is_cuda:
         _goal_error_columns_cpu(rows, fields, goal, mask, perm, by_ray, n_source, grad, err)
         return err, grad
-    _need_gpu(rows, goal, mask, perm, grad, err)
-    if (n > 0 and rows.stride(1) != 1) or (grad.shape[1] > 0 and grad.stride(1) != 1):
-        raise ValueError("goal_error_columns: rows and grad must have contiguous columns")
     L = _lib.lib()
-    wsb = L.tfrt_goal_error_columns_workspace_bytes(n)
-    if workspace is None:
-        workspace = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    workspace = _column_workspace(
+        "goal_error_columns", rows, grad, workspace,
+        lambda: L.tfrt_goal_error_columns_workspace_bytes(n), goal, mask, perm, err)
     codes = (ctypes.c_int32 * nf)(*fields)
     check(L.tfrt_goal_error_columns(
         _p(rows), rows.stride(0), n, _DT[rows.dtype], k, _p(mask), _p(perm), n_source, codes, nf,

@@ -33,6 +33,18 @@ reference's dev/hexalens.py --, one trace, two error evaluations, one combinatio
 sweep, replayed from the same graph.
 
     python examples/imaging.py --magnification 1.0 [--rays 20000] [--steps 30] [--generic]
+
+``--focus`` frees the axial position too: an ``optimizer.FocusError`` over the same labels in the
+place of the ``SpotError``.  The rays of an object point, taken as lines, must pass through one
+common point of space, wherever along the beam that is; a ray counts while its end lies in a box
+around the target.  Defocus and field curvature are then no longer charged to the lens as spot
+size, and the solved foci are a read-out of the focal surface: the run ends with their spread
+along x, the field curvature.  A line includes its backward extension, so a diverging bundle has
+a (virtual) focus too: the flat starting lens reports the plate's image of the object plane, and
+the error is the lens' aberration alone.  Where the focus should lie is a second term's business
+(a ``SumError`` with a ``GoalError``, as ``--magnification`` builds for the ``SpotError``).
+
+    python examples/imaging.py --focus [--rays 20000] [--steps 30] [--generic]
 """
 import argparse
 import math
@@ -83,7 +95,7 @@ def gaussian_pupil(sigma, cone):
 
 
 def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, target_distance=10.0,
-          object_size=0.2, lens_aperature=1.0, apodize=None, magnification=None):
+          object_size=0.2, lens_aperature=1.0, apodize=None, magnification=None, focus=False):
     points = letter_f(object_size)
     P = points.shape[0]
     A = max(ray_count // P, 2)
@@ -129,6 +141,11 @@ def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, target_dis
     error_function = optimizer.SpotError(
         ("y_end", "z_end"), labels, ((-HALF_DOMAIN, HALF_DOMAIN), (-HALF_DOMAIN, HALF_DOMAIN)),
         oob_weight=1.0, weights=None if apodize is None else gaussian_pupil(apodize, cone))
+    if focus:
+        # the box contains the target plane: every ray that lands in the target region counts
+        error_function = optimizer.FocusError(
+            labels, ((target_distance - 1.0, target_distance + 1.0),
+                     (-HALF_DOMAIN, HALF_DOMAIN), (-HALF_DOMAIN, HALF_DOMAIN)), min_det=1e-9)
     spot = error_function
     if magnification is not None:
         # ray i leaves object point i mod P whatever direction is drawn for it: the image points
@@ -143,8 +160,8 @@ def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, target_dis
 
 
 def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=False, verbose=True,
-        learning_rate=None, apodize=None, magnification=None):
-    s = build(ray_count, lens_res_scale, apodize=apodize, magnification=magnification)
+        learning_rate=None, apodize=None, magnification=None, focus=False):
+    s = build(ray_count, lens_res_scale, apodize=apodize, magnification=magnification, focus=focus)
     combined, erf = s["error_function"], s["spot"]
     if learning_rate is None:
         # (the error is a sum over the rays: the step size goes with 1 / rays)
@@ -183,11 +200,13 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=Fals
         if verbose and (step % 5 == 0 or step == steps - 1):
             extra = "" if magnification is None else \
                 f"  mean squared image distance {place[-1]:.6g}  combined {mean:.6g}"
-            print(f"step {step:4d}: rms spot {rms[-1]:.6g}{extra}  ({inside} rays inside, "
+            what = "rms distance to the focus" if focus else "rms spot"
+            print(f"step {step:4d}: {what} {rms[-1]:.6g}{extra}  ({inside} rays inside, "
                   f"{1e3 * times[-1]:.2f} ms)")
     fused = opt._fused_step
     s.update(rms=rms, times=times, errors=errors, place=place,
-             graph_replays=0 if fused is None else fused.graph_replays, centroids=erf.centroids())
+             graph_replays=0 if fused is None else fused.graph_replays,
+             centroids=erf.foci() if focus else erf.centroids())
     return s
 
 
@@ -204,14 +223,26 @@ if __name__ == "__main__":
                     help="Gaussian pupil weights, SIGMA in units of the cone that fills the lens")
     ap.add_argument("--magnification", type=float, default=None, metavar="M",
                     help="pin the image of (y, z) to (-M y, -M z): SumError([SpotError, GoalError])")
+    ap.add_argument("--focus", action="store_true",
+                    help="a FocusError in the place of the SpotError: the axial position is free")
     a = ap.parse_args()
+    if a.focus and (a.apodize is not None or a.magnification is not None):
+        ap.error("--focus takes neither --apodize nor --magnification")
     out = run(a.rays, a.steps, a.edge, generic=a.generic, adam=a.adam, learning_rate=a.lr,
-              apodize=a.apodize, magnification=a.magnification)
+              apodize=a.apodize, magnification=a.magnification, focus=a.focus)
     tail = sorted(out["times"][len(out["times"]) // 2:])
     print(f"{out['n_points']} object points, {out['n_rays']} rays; steps replayed from the graph: "
           f"{out['graph_replays']} of {a.steps}; median step of the second half: "
           f"{1e3 * tail[len(tail) // 2]:.3f} ms")
-    print(f"rms spot: first {out['rms'][0]:.6g} last {out['rms'][-1]:.6g}")
+    if a.focus:
+        # (the mean squared distance of a group's focus from its rays' lines)
+        print(f"focus error: first {out['errors'][0]:.6g} last {out['errors'][-1]:.6g}")
+        x = out["centroids"][:, 0]
+        x = x[torch.isfinite(x)]
+        print(f"foci of {x.numel()} object points: x from {float(x.min()):.6g} to "
+              f"{float(x.max()):.6g}, spread {float(x.max() - x.min()):.6g} (field curvature)")
+    else:
+        print(f"rms spot: first {out['rms'][0]:.6g} last {out['rms'][-1]:.6g}")
     if a.magnification is not None:
         print(f"mean squared image distance: first {out['place'][0]:.6g} last "
               f"{out['place'][-1]:.6g}")

@@ -864,6 +864,83 @@ int tfrt_transport_error(const void* rows, int64_t stride, int64_t n, int32_t st
                          double* grad, int64_t grad_stride, double* err, int32_t* rank2,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* FocusError: the columns that carry the same group label, taken as LINES, must pass through one
+ * common point of space -- wherever along the beam that is.  The error is the sum over the rays of
+ * the squared distance of their group's FOCUS (the point nearest to all the group's lines in the
+ * least-squares sense) from the ray's own line, in the scene's units.  Five launches (clear `acc`,
+ * accumulate, solve, seed, finish), no host read, no allocation: captured with the rest of a step.
+ *
+ * `rows` is the 2d-row geometry block of a d-D trace, d = `dimension` = 2 or 3: rows 0..d-1 the
+ * start s of the finished ray's last link, rows d..2d-1 its end e, converted to f64.  Every
+ * operation below is an IEEE f64 operation rounded on its own (no contraction); a sum of products
+ * is summed left to right, x first.
+ *
+ * The line of column i (the direction of tfrt_density_error_fields):
+ *   v = e - s,  L = sqrt(v.v),  u = v / L;  the link is `ok` if every geometry row is finite and L
+ *   is finite and > 0.
+ * A column COUNTS if all of these hold (anything else has no term and gets zeros in all 2d rows of
+ * `grad`; nothing is read out of bounds, whatever perm and group hold):
+ *   mask is NULL or mask[i] >= 0;  the link is ok;  src = perm ? perm[i] : i lies in [0, n_source);
+ *   label = group[src] lies in [0, n_groups);  lo_a <= e_a <= hi_a on every axis a of the closed
+ *   box `domain`.
+ * Normalisation, the constants computed once by the entry on the host:
+ *   c_a = 0.5 * (lo_a + hi_a),  R = the largest of 0.5 * (hi_a - lo_a),  iR = 1.0 / R;
+ *   m_a = (e_a - c_a) * iR, so |m_a| <= 1.
+ * The record of a group, ten int64 {count, Pxx, Pxy, Pxz, Pyy, Pyz, Pzz, tx, ty, tz} (2-D: the z
+ * slots stay 0).  With P = I - u u^T and t = P m a counting column adds, by 64-bit integer atomics
+ * (the sums do not depend on the order of the atomics):
+ *   1;  rint(P_ab * 2^pbits) with P_aa = 1.0 - u_a * u_a and P_ab = -(u_a * u_b), a < b;
+ *   rint(t_a * 2^pbits) with w = u.m and t_a = m_a - w * u_a;  rint is half to even.
+ * The focus of a group, once every column is in: n = (double) count, a_ab = ((double) Aq_ab *
+ * 2^-pbits) / n, b_a = ((double) bq_a * 2^-pbits) / n, and
+ *   3-D:  c00 = a11*a22 - a12*a12,  c01 = a02*a12 - a01*a22,  c02 = a01*a12 - a02*a11,
+ *         c11 = a00*a22 - a02*a02,  c12 = a01*a02 - a00*a12,  c22 = a00*a11 - a01*a01,
+ *         det = a00*c00 + a01*c01 + a02*c02,
+ *         x_0 = (c00*b0 + c01*b1 + c02*b2) / det,  x_1 = (c01*b0 + c11*b1 + c12*b2) / det,
+ *         x_2 = (c02*b0 + c12*b1 + c22*b2) / det;
+ *   2-D:  det = a00*a11 - a01*a01,  x_0 = (a11*b0 - a01*b1) / det,  x_1 = (a00*b1 - a01*b0) / det.
+ * The group HAS A FOCUS if count >= 2 and det >= min_det (a definition: a collimated group has
+ * none); the real focus is c + R x.  A group without a focus leaves its rays without term and
+ * gradient.
+ * The term of a counting column whose group has a focus:
+ *   q = m - x,  a = u.q,  r_b = q_b - a * u_b,  rho_b = R * r_b,  alpha = R * a;  term = rho.rho;
+ *   lever = alpha / L,  grad[end_b] = (2.0 * rho_b) * (1.0 - lever),
+ *   grad[start_b] = (2.0 * rho_b) * lever
+ * -- the lever rule of the foot point e - alpha u along the link; exact without a derivative of x,
+ * because x minimises the group's sum (up to the quantisation, relative 2^-pbits).
+ * error_out = {sum of the terms, number of terms, sum / number (NaN without terms)}; the sums have
+ * a fixed shape and order: two runs give the same bits.
+ *
+ *   rows, stride    ray block in the state dtype, 2 * dimension rows, entry (row, i) at
+ *                   rows[row * stride + i], n columns
+ *   group           n_source int32 labels, one per SOURCE ray
+ *   perm            n int32, the source ray of column i; or NULL: column i is source ray i
+ *   n_groups        G, 1 <= G <= 2^20
+ *   x0 .. z1        the box, lo < hi and finite on every axis in use (z0, z1 are ignored in 2-D)
+ *   pbits           1..40; the caller uses min(40, 60 - bit_length(n_source)).  n >= 2^(61 - pbits)
+ *                   is refused: |t_a| < 2, so n * 2 * 2^pbits < 2^62 and no sum overflows
+ *   min_det         finite and > 0
+ *   grad            f64 block of 2 * dimension rows of `grad_stride`, every row written for EVERY
+ *                   column
+ *   acc             n_groups records of ten int64, cleared and filled by this call
+ *   foci            n_groups rows of four f64 {x_0, x_1, x_2, 1.0} in NORMALISED coordinates (2-D:
+ *                   x_2 = 0.0), {NaN, NaN, NaN, 0.0} for a group without a focus
+ *   variant         0: a per-workgroup table in LDS up to 256 groups (ten planes of G int64,
+ *                   20 KiB), global 64-bit atomics above; 1 / 2 force one of them (1 with more than
+ *                   256 groups: TFRT_E_BADARG)
+ *   workspace       tfrt_focus_error_workspace_bytes(n, n_groups) bytes (0: bad arguments)
+ * 0 <= n < 2^31 (n == 0 is legal: {0, 0, NaN}), 0 <= n_source < 2^31.  Bad arguments are refused
+ * with TFRT_E_BADARG / TFRT_E_WORKSPACE before any launch.
+ */
+size_t tfrt_focus_error_workspace_bytes(int64_t n, int32_t n_groups);
+int tfrt_focus_error(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                     int32_t dimension, const int32_t* mask, const int32_t* group,
+                     int64_t n_source, const int32_t* perm, int32_t n_groups, double x0, double x1,
+                     double y0, double y1, double z0, double z1, int32_t pbits, double min_det,
+                     double* grad, int64_t grad_stride, double* error_out, int64_t* acc,
+                     double* foci, int32_t variant, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 /* GoalError on the fixed-shape columns of an in-place trace (tfrt_scene3d.in_place == 2: the
  * finished rows at the rays' own columns, a mask in the place of a ray count) -- the form that can
  * be added to a coupled error of the same step (tfrt_error_combine).  Two launches (the columns,

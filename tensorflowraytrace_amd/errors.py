@@ -12,15 +12,17 @@ process): a ``DensityError`` -- the finished rays, taken together, must land wit
 one group must meet in one point -- ``tfrt_spot_error`` (clear, accumulate, seed, finish); a
 ``TransportError`` -- the same target density by sliced optimal transport --
 ``tfrt_transport_error`` (per direction keys, radix sort, sorted keys, ranks; then seed and
-finish).  A ``SumError`` is a weighted sum of such terms and of ``GoalError``s: every term's
-launches into a seed block of its own (a ``GoalError`` through ``tfrt_goal_error_columns``), then
-ONE ``tfrt_error_combine`` for the step's seed block and error.
+finish); a ``FocusError`` -- rays of one group, taken as lines, must pass through one point of
+space -- ``tfrt_focus_error`` (clear, accumulate, solve, seed, finish).  A ``SumError`` is a
+weighted sum of such terms and of ``GoalError``s: every term's launches into a seed block of its
+own (a ``GoalError`` through ``tfrt_goal_error_columns``), then ONE ``tfrt_error_combine`` for the
+step's seed block and error.
 
 Each is an ordinary error function (``__call__(engine)``): the generic path gives the same
 numbers, which is what the parity tests compare.
 
 The protocol between a built-in term (``GoalError``, ``DensityError``, ``SpotError``,
-``TransportError``) and the fused 3-D step:
+``TransportError``, ``FocusError``) and the fused 3-D step:
 
 * ``rows``, ``fields``, ``rows_for(dimension)``: the rows of the ray block (the field codes) the
   term reads;
@@ -345,6 +347,40 @@ def _goal_bins(what, goal, domain, bins, dev):
     if norm == 0.0:
         raise ValueError(f"{what}: goal is zero everywhere")
     return g, norm
+
+
+def _as_labels(what, groups, device):
+    """The group labels of ``SpotError`` / ``FocusError`` as they are kept: int32 on ``device``,
+    one per source ray."""
+    g = groups if isinstance(groups, torch.Tensor) else torch.as_tensor(np.asarray(groups))
+    if g.dim() != 1 or g.dtype.is_floating_point or g.dtype.is_complex or g.dtype == torch.bool:
+        raise ValueError(f"{what}: groups must be integers of shape (N,), one label per "
+                         f"source ray; got shape {tuple(g.shape)}, {g.dtype}")
+    return g.detach().to(device=device, dtype=torch.int32).contiguous()
+
+
+def _init_groups(erf, what, groups, n_groups, most):
+    """``erf.groups`` / ``erf.labels`` / ``erf.n_groups`` from the constructor's ``groups`` and
+    ``n_groups`` (default: ``max + 1`` of given labels, read once here; at most ``most``)."""
+    from . import config
+    erf.groups = groups
+    erf.labels = None
+    erf._caches = {}
+    if callable(groups):
+        if n_groups is None:
+            raise ValueError(f"{what}: callable groups need n_groups")
+    else:
+        erf.labels = _as_labels(what, groups, config.get_device())
+        if n_groups is None:
+            if erf.labels.numel() == 0:
+                raise ValueError(f"{what}: no labels and no n_groups")
+            n_groups = int(erf.labels.max()) + 1
+    try:
+        erf.n_groups = int(n_groups)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{what}: n_groups must be an integer, got {n_groups!r}") from e
+    if not 1 <= erf.n_groups <= most:
+        raise ValueError(f"{what}: n_groups must lie in 1 .. {most}, got {n_groups!r}")
 
 
 class _CoupledError(_Term):
@@ -880,32 +916,13 @@ class SpotError(_CoupledError):
     splat_variant = 0
 
     def __init__(self, fields, groups, domain, oob_weight=0.0, n_groups=None, weights=None):
-        from . import config
         self.fields, self.domain = _fields_and_domain("SpotError", fields, domain)
         self.rows = [_FIELDS3.index(f) for f in self.fields]
         self.has_direction = any(f.endswith("_dir") for f in self.fields)
         self.oob_weight = float(oob_weight)
         if not (self.oob_weight >= 0.0 and np.isfinite(self.oob_weight)):
             raise ValueError("SpotError: oob_weight must be finite and >= 0")
-        self.groups = groups
-        self.labels = None
-        self._caches = {}
-        if callable(groups):
-            if n_groups is None:
-                raise ValueError("SpotError: callable groups need n_groups")
-        else:
-            self.labels = self._as_labels(groups, config.get_device())
-            if n_groups is None:
-                if self.labels.numel() == 0:
-                    raise ValueError("SpotError: no labels and no n_groups")
-                n_groups = int(self.labels.max()) + 1
-        try:
-            self.n_groups = int(n_groups)
-        except (TypeError, ValueError) as e:
-            raise ValueError(f"SpotError: n_groups must be an integer, got {n_groups!r}") from e
-        if not 1 <= self.n_groups <= ops.SPOT_MAX_GROUPS:
-            raise ValueError(f"SpotError: n_groups must lie in 1 .. {ops.SPOT_MAX_GROUPS}, got "
-                             f"{n_groups!r}")
+        _init_groups(self, "SpotError", groups, n_groups, ops.SPOT_MAX_GROUPS)
         self._grids = {}
         self.last_acc = None
         self.last_grid = None
@@ -916,19 +933,12 @@ class SpotError(_CoupledError):
             raise ValueError(f"SpotError: {self.weights.numel()} weights for "
                              f"{self.labels.numel()} labels -- one of each per source ray")
 
-    @staticmethod
-    def _as_labels(groups, device):
-        g = groups if isinstance(groups, torch.Tensor) else torch.as_tensor(np.asarray(groups))
-        if g.dim() != 1 or g.dtype.is_floating_point or g.dtype.is_complex or g.dtype == torch.bool:
-            raise ValueError("SpotError: groups must be integers of shape (N,), one label per "
-                             f"source ray; got shape {tuple(g.shape)}, {g.dtype}")
-        return g.detach().to(device=device, dtype=torch.int32).contiguous()
-
     def labels_of(self, src):
         """The int32 label buffer of the source set ``src`` on its device, one label per source
         ray: the tensor given (moved once; a new buffer re-captures a graph), or the callable's
         result, cached by the versions of the source's fields as ``GoalError.table`` is."""
-        return _source_buffer(self, "labels", self.groups, self._as_labels, src, "SpotError",
+        return _source_buffer(self, "labels", self.groups,
+                              lambda v, dev: _as_labels("SpotError", v, dev), src, "SpotError",
                               "label")
 
     def grid_for(self, n_source):
@@ -1070,8 +1080,178 @@ class _SpotTerms(torch.autograd.Function):
         return (upstream[:, 0] * grad).to(ctx.dtype), None, None, None, None, None, None
 
 
+class FocusError(_CoupledError):
+    """Rays that left the same object point, taken as LINES, must pass through one common point
+    of space -- wherever along the beam that is: the sum over the finished rays of the squared
+    distance of their group's FOCUS from the ray's own line, in the scene's units.  A
+    ``SpotError`` asks the rays to meet in one point of the target surface and charges defocus
+    and field curvature to the lens as spot size; here the axial position is free too, and the
+    solved points (``foci()``) are a direct read-out of the focal surface.  It is also the
+    objective of concentrators and fibre coupling: everything through one small region, wherever
+    it is.
+
+    ``groups``, ``n_groups``: as for ``SpotError`` -- one integer label per SOURCE ray (a tensor
+    or array of shape (N,), kept as int32 on the device as ``labels`` and overwritable in place,
+    or a callable on the source's field dict, which needs ``n_groups``); labels outside
+    ``[0, n_groups)`` exclude a ray.  ``domain``: the closed box ``((x0, x1), (y0, y1), (z0, z1))``
+    -- ``((x0, x1), (y0, y1))`` on a 2-D engine -- that the END of a finished ray's last link must
+    lie in to count; it should contain the target.  ``min_det``: finite and > 0; a group has a
+    focus if it has at least two rays and ``det(A / count) >= min_det`` (below) -- a definition:
+    a collimated group has no focus.  Choose it well above ``2**-pbits``, the size of the
+    quantisation.  There are no ``fields`` (all ``2 * dimension`` geometry rows are read and
+    seeded) and no ``weights``.
+
+    For every finished ray of the trace, coordinates converted to float64, every operation
+    rounded on its own, sums of products left to right:
+
+    * the line: ``v = end - start``, ``L = sqrt(v . v)``, ``u = v / L`` (``DensityError``'s
+      direction); a ray counts if its link has a direction, its label lies in ``[0, n_groups)``
+      and its end lies in the box; everything else has no term and zero gradient;
+    * with ``c`` the box centre, ``R`` its largest half-width and ``iR = 1 / R`` computed once:
+      ``m = (end - c) * iR``; ``P = I - u u^T`` (``P_aa = 1 - u_a * u_a``,
+      ``P_ab = -(u_a * u_b)``), ``w = u . m``, ``t = m - w * u``;
+    * ``{1, rint(P_ab * 2**pbits) (a <= b), rint(t_a * 2**pbits)}`` (half to even) is added to the
+      ray's group in an int64 table of ten slots ``{count, Pxx, Pxy, Pxz, Pyy, Pyz, Pzz, tx, ty,
+      tz}`` (2-D: the z slots stay 0), ``pbits = min(40, 60 - bit_length(N))``
+      (``ops.focus_pbits(N)``) -- integer addition is associative, so the table does not depend on
+      the order of the atomics;
+    * a group's ``A = Aq * 2**-pbits / count``, ``b = bq * 2**-pbits / count``, the determinant
+      and ``x = A^-1 b`` by the cofactor expressions of include/tfrt_hip.h (tfrt_focus_error); its
+      focus is ``c + R * x``;
+    * a counting ray of a group with a focus: ``q = m - x``, ``a = u . q``,
+      ``rho = R * (q - a * u)``, the term ``rho . rho``; with ``lever = (R * a) / L`` the gradient
+      is ``(2 * rho) * (1 - lever)`` on the end rows and ``(2 * rho) * lever`` on the start rows:
+      the lever rule of the foot point along the link.  It is exact without a derivative of the
+      focus, because the focus minimises the group's sum (up to the quantisation, relative
+      ``2**-pbits``).  With float32 ray state the lever inherits the direction's
+      ``eps32 * max|coordinate| / L``;
+    * ``error = {sum of the terms, number of terms, sum / number}``, NaN without terms; every sum
+      has a fixed shape and order: two runs give the same bits.
+
+    It is an ordinary ``error_function(engine)`` (the generic path: ``ops.focus_error`` over the
+    finished rays' geometry block under a ``torch.autograd.Function`` that returns the
+    (n_finished, 1) terms), which also serves sources that are not traced in place,
+    ``deterministic=True``, fewer than 4,096 rays, several ranks (each shard then solves the foci
+    of its own rays) and 2-D engines.  Its ``backward`` returns ``upstream * gradient``: exact when
+    ``upstream`` is constant within a group (the optimiser passes ones).  On a 3-D engine that
+    traces its source in place the optimiser runs it on the fused, graph-replayed step under the
+    conditions of a ``DensityError`` (``FusedStep._rowwise3d`` with ``tfrt_focus_error``: clear,
+    accumulate, solve, seed, finish), and it is a legal term of a ``SumError``.
+
+    ``last_acc`` is the (G, 10) int64 table of the last evaluation, ``foci()`` the (G, d) float64
+    foci in scene coordinates made from it (NaN for a group without a focus).  ``splat_variant``
+    (0: by G; 1: table in LDS; 2: global atomics) is tfrt_focus_error's, for measuring."""
+
+    splat_variant = 0
+    has_direction = True          # (every geometry row is read and seeded)
+
+    def __init__(self, groups, domain, n_groups=None, min_det=1e-12):
+        try:
+            self.grid = ops.focus_grid(domain)
+        except ValueError as e:
+            raise ValueError(f"FocusError: domain must be ((x0, x1), (y0, y1), (z0, z1)) -- "
+                             f"((x0, x1), (y0, y1)) on a 2-D engine --, finite with lo < hi; got "
+                             f"{domain!r}") from e
+        self.domain = tuple((float(d[0]), float(d[1])) for d in domain)
+        self.dimension = len(self.domain)
+        self.fields = _GEO3 if self.dimension == 3 else _GEO2
+        self.rows = list(range(2 * self.dimension))
+        try:
+            self.min_det = float(min_det)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"FocusError: min_det must be a number, got {min_det!r}") from e
+        if not (self.min_det > 0.0 and np.isfinite(self.min_det)):
+            raise ValueError(f"FocusError: min_det must be finite and > 0, got {min_det!r}")
+        _init_groups(self, "FocusError", groups, n_groups, ops.FOCUS_MAX_GROUPS)
+        self.last_acc = None
+        self.last_foci = None
+
+    def labels_of(self, src):
+        """The int32 label buffer of the source set ``src`` on its device, one label per source
+        ray, given or computed and cached as ``SpotError.labels_of`` does."""
+        return _source_buffer(self, "labels", self.groups,
+                              lambda v, dev: _as_labels("FocusError", v, dev), src, "FocusError",
+                              "label")
+
+    def rows_for(self, dimension):
+        """All ``2 * dimension`` rows of the geometry block; the box must have the engine's
+        dimension."""
+        if dimension != self.dimension:
+            raise ValueError(f"FocusError: a {dimension}-D engine needs a domain of {dimension} "
+                             f"axes, got {self.domain!r}")
+        return self.rows
+
+    def graph_key(self):
+        """What a captured step has baked in: the label buffer's address and the constants."""
+        lab = self.labels
+        return (None if lab is None else (lab.data_ptr(), tuple(lab.shape)), self.n_groups,
+                self.grid, self.min_det, self.splat_variant)
+
+    def evaluate(self, rows, labels, mask=None, perm=None, **buffers):
+        """``ops.focus_error`` of the geometry block ``rows`` with these labels, box and
+        ``min_det``."""
+        out = ops.focus_error(rows, labels, self.n_groups, self.grid, self.min_det, mask=mask,
+                              perm=perm, dimension=self.dimension, variant=self.splat_variant,
+                              **buffers)
+        self.last_acc, self.last_foci = out[2], out[3]
+        return out
+
+    def seed_columns(self, cols, hold):
+        """tfrt_focus_error on the step's columns: it reads the source's label buffer through the
+        trace's order ``cols.perm`` inside the kernels, as a SpotError does; the records go into
+        ``hold.buffers["acc"]``, (G, 10), the solved table into ``hold.buffers["foci"]``."""
+        self.rows_for(3)
+        labels = self.labels_of(cols.src)
+        G = self.n_groups
+        held = self._held(hold, "acc", (G, ops.FOCUS_SLOTS), torch.int64, cols.rows.device,
+                          lambda: _lib.lib().tfrt_focus_error_workspace_bytes(cols.n, G))
+        if "foci" not in held:
+            held["foci"] = torch.zeros((G, 4), dtype=torch.float64, device=cols.rows.device)
+        self.evaluate(cols.rows, labels, mask=cols.mask, perm=cols.perm, grad=hold.g_fin,
+                      err=hold.err, **held)
+
+    def foci(self):
+        """(G, d) float64 foci of the last evaluation in scene coordinates, NaN for a group
+        without a focus."""
+        if self.last_foci is None:
+            raise RuntimeError("FocusError: no evaluation yet")
+        return ops.focus_points(self.last_foci, self.grid, self.dimension)
+
+    def __call__(self, engine):
+        """The (n_finished, 1) error terms through the generic path; the gradient rows come back
+        in ``backward``."""
+        self.rows_for(engine.dimension)
+        fin = engine.finished_rays
+        if not bool(fin):
+            return torch.zeros((0, 1), dtype=torch.float64)
+        labels = self.labels_of(engine._trace_src)
+        ids = engine.last_trace["finished_id"].to(torch.int32).contiguous()
+        block = torch.stack([fin[f] for f in self.fields], dim=0)
+        return _FocusTerms.apply(block, self, labels, ids)
+
+
+class _FocusTerms(torch.autograd.Function):
+    """FocusError over the (2 * dimension, n) geometry block of the finished rays, no mask;
+    ``ids``: the source ray of every column.  Returns the (n, 1) terms, made from the solved
+    table with the definition's operations as torch ops (``ops.focus_terms``)."""
+
+    @staticmethod
+    def forward(ctx, block, erf, labels, ids):
+        rows = block.detach().contiguous()
+        _, grad, _, foci = erf.evaluate(rows, labels, perm=ids)
+        ctx.save_for_backward(grad)
+        ctx.dtype = block.dtype
+        return ops.focus_terms(rows, labels, erf.n_groups, erf.grid, foci, perm=ids,
+                               dimension=erf.dimension)[:, None].contiguous()
+
+    @staticmethod
+    def backward(ctx, upstream):
+        grad, = ctx.saved_tensors
+        return (upstream[:, 0] * grad).to(ctx.dtype), None, None, None
+
+
 # the coupled errors: all finished rays of a step enter one evaluation (one process)
-_COUPLED = (DensityError, SpotError, TransportError)
+_COUPLED = (DensityError, SpotError, TransportError, FocusError)
 
 
 class SumError:
@@ -1081,9 +1261,9 @@ class SumError:
     same finished rays of one trace and the reverse sweep is linear in its seed, so the combined
     step is one trace, K error evaluations, one combination and one reverse sweep.
 
-    ``terms``: 1 to 8 distinct instances of ``GoalError``, ``DensityError``, ``SpotError`` or
-    ``TransportError``; a ``RowwiseError``, a nested ``SumError`` or the same object twice is a
-    ValueError.  ``weights``: K finite values >= 0, default all ones, kept as the (K,) float64
+    ``terms``: 1 to 8 distinct instances of ``GoalError``, ``DensityError``, ``SpotError``,
+    ``TransportError`` or ``FocusError``; a ``RowwiseError``, a nested ``SumError`` or the same
+    object twice is a ValueError.  ``weights``: K finite values >= 0, default all ones, kept as the (K,) float64
     device tensor ``weights``; ``set_weights(values)`` validates on the host and overwrites that
     buffer in place, so a replayed graph sees the new values without a re-capture (as
     ``TransportError.set_goal``).  A weight of 0 switches a term off for a phase; the term is
@@ -1095,7 +1275,7 @@ class SumError:
 
     After an evaluation ``last_errors`` is the (K, 3) tensor of the terms' own triples {sum, terms,
     mean} and ``last_coefficients`` the (K,) ``c_k``; each term keeps its own ``last_hq`` /
-    ``centroids()`` / ``last_rank2`` as when it runs alone.
+    ``centroids()`` / ``last_rank2`` / ``foci()`` as when it runs alone.
 
     It is an ordinary ``error_function(engine)`` -- the generic path returns the (1,) tensor
     ``sum_k c_k * term_k(engine).sum()`` (``terms_k = numel``) under torch autograd, which serves
@@ -1124,8 +1304,9 @@ class SumError:
                 raise ValueError("SumError: a RowwiseError cannot be a term (its error is torch "
                                  "code of its own); state it as a GoalError")
             if not isinstance(t, (GoalError,) + _COUPLED):
-                raise ValueError("SumError: terms must be GoalError, DensityError, SpotError or "
-                                 f"TransportError instances, got {type(t).__name__}")
+                raise ValueError("SumError: terms must be GoalError, DensityError, SpotError, "
+                                 "TransportError or FocusError instances, got "
+                                 f"{type(t).__name__}")
         if len(set(id(t) for t in terms)) != len(terms):
             raise ValueError("SumError: the same term object is listed twice (a term keeps the "
                              "buffers of its last evaluation); make a second instance")

@@ -2024,6 +2024,237 @@ def _spot_error_cpu(rows, row_x, row_y, group, n_groups, grid, oob, mask, perm, 
     err[2] = e / n_terms if n_terms > 0 else float("nan")
 
 
+# ------------------------------------------------------- rays of a group through one point
+FOCUS_MAX_GROUPS = 1 << 20
+FOCUS_LDS_GROUPS = 256             # tfrt_focus_error: ten planes of G int64 in LDS, 20 KiB
+FOCUS_MAX_PBITS = 40
+FOCUS_SLOTS = 10                   # {count, Pxx, Pxy, Pxz, Pyy, Pyz, Pzz, tx, ty, tz}
+_FOCUS_Z_SLOTS = (3, 5, 6, 9)
+
+
+def focus_pbits(n_source):
+    """Fraction bits of tfrt_focus_error's fixed point for a source of ``n_source`` rays:
+    ``min(40, 60 - bit_length(n_source))`` -- every entry is below 2 in absolute value, so no
+    int64 sum can overflow."""
+    return min(FOCUS_MAX_PBITS, 60 - int(n_source).bit_length())
+
+
+def focus_grid(domain):
+    """The box constants of tfrt_focus_error from ``domain`` = ((x0, x1), (y0, y1)[, (z0, z1)]):
+    ``(x0, x1, y0, y1, z0, z1, cx, cy, cz, R, iR)`` in float64 -- the box, its centre
+    ``c = 0.5 * (lo + hi)``, ``R`` the largest half-width ``0.5 * (hi - lo)`` and ``iR = 1 / R``,
+    each computed once here; a 2-D domain leaves the z entries 0."""
+    try:
+        box = [(float(d[0]), float(d[1])) for d in domain]
+    except (IndexError, TypeError) as e:
+        raise ValueError("focus_grid: domain must be ((x0, x1), (y0, y1)) or "
+                         "((x0, x1), (y0, y1), (z0, z1))") from e
+    if len(box) not in (2, 3) \
+            or any(not (np.isfinite(a) and np.isfinite(b) and b > a) for a, b in box):
+        raise ValueError("focus_grid: domain needs one finite (lo, hi), lo < hi, per axis of a "
+                         f"2-D or 3-D trace; got {domain!r}")
+    box += [(0.0, 0.0)] * (3 - len(box))
+    lo = np.array([b[0] for b in box], dtype=np.float64)
+    hi = np.array([b[1] for b in box], dtype=np.float64)
+    c = 0.5 * (lo + hi)
+    R = np.float64(max(0.5 * (hi - lo)))
+    iR = np.float64(1.0) / R
+    if not (np.isfinite(R) and np.isfinite(iR)):
+        raise ValueError(f"focus_grid: the box {domain!r} has no finite half-width")
+    return tuple(float(v) for b in box for v in b) + tuple(float(v) for v in c) \
+        + (float(R), float(iR))
+
+
+def _focus_columns(rows, group, n_groups, grid, mask, perm, dimension):
+    """(counts, label, u, m, L) of the columns of the geometry block ``rows``, the operations of
+    tfrt_focus_error one by one as torch ops (on the block's device): which columns count, their
+    group (clamped into [0, G) where a column does not count), the link's direction, the
+    normalised end point and the link's length."""
+    d = dimension
+    n = rows.shape[1]
+    dev = rows.device
+    _, e, u, L, ok = _link_torch(rows, d)
+    counts = ok if mask is None else ok & (mask[:n] >= 0)
+    s = torch.arange(n, dtype=torch.int64, device=dev) if perm is None else perm[:n].long()
+    s_ok = (s >= 0) & (s < group.numel())
+    label = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    if group.numel() > 0:
+        label = torch.where(s_ok, group[s.clamp(0, group.numel() - 1)].long(), label)
+    counts = counts & s_ok & (label >= 0) & (label < n_groups)
+    for a in range(d):
+        counts = counts & (e[a] >= grid[2 * a]) & (e[a] <= grid[2 * a + 1])
+    c = torch.tensor(grid[6:6 + d], dtype=torch.float64, device=dev)[:, None]
+    m = (e - c) * grid[10]
+    return counts, label.clamp(0, n_groups - 1), u, m, L
+
+
+def _dot_rows(v, w):
+    """v . w of two (d, n) blocks, the products summed left to right."""
+    s = v[0] * w[0] + v[1] * w[1]
+    return s + v[2] * w[2] if v.shape[0] == 3 else s
+
+
+def _focus_solve(acc, pbits, min_det, d):
+    """The (G, 4) table {x, y, z, has_focus} of a (G, 10) record table: focus_math.h's
+    focus_solve, operation by operation, over all groups at once."""
+    inv = float(np.ldexp(1.0, -int(pbits)))
+    cnt = acc[:, 0]
+    n = cnt.double()
+    a00, a01, a02, a11, a12, a22, b0, b1, b2 = (
+        (acc[:, p].double() * inv) / n for p in (1, 2, 3, 4, 5, 6, 7, 8, 9))
+    if d == 2:
+        det = a00 * a11 - a01 * a01
+        xs = [(a11 * b0 - a01 * b1) / det, (a00 * b1 - a01 * b0) / det, torch.zeros_like(det)]
+    else:
+        c00 = a11 * a22 - a12 * a12
+        c01 = a02 * a12 - a01 * a22
+        c02 = a01 * a12 - a02 * a11
+        c11 = a00 * a22 - a02 * a02
+        c12 = a01 * a02 - a00 * a12
+        c22 = a00 * a11 - a01 * a01
+        det = a00 * c00 + a01 * c01 + a02 * c02
+        xs = [(c00 * b0 + c01 * b1 + c02 * b2) / det, (c01 * b0 + c11 * b1 + c12 * b2) / det,
+              (c02 * b0 + c12 * b1 + c22 * b2) / det]
+    has = (cnt >= 2) & (det >= min_det)
+    nan = torch.full_like(det, float("nan"))
+    return torch.stack([torch.where(has, x, nan) for x in xs] + [has.double()], dim=1)
+
+
+def _focus_terms(counts, label, u, m, L, foci, R):
+    """(has, term, g_start, g_end) of the columns against the table ``foci``: focus_math.h's
+    focus_term; ``has``: the column counts and its group has a focus (the others hold garbage)."""
+    d = u.shape[0]
+    f = foci[label]
+    has = counts & (f[:, 3] != 0.0)
+    q = m - f[:, :d].t()
+    a = _dot_rows(u, q)
+    rho = R * (q - a * u)
+    lever = (R * a) / L
+    two = 2.0 * rho
+    return has, _dot_rows(rho, rho), two * lever, two * (1.0 - lever)
+
+
+def focus_terms(rows, group, n_groups, grid, foci, mask=None, perm=None, dimension=3):
+    """The (n,) float64 terms of a tfrt_focus_error evaluation from its table ``foci``, as torch
+    ops on the block's device: the squared distance of the group's focus from a ray's line, 0 for
+    a ray without a term."""
+    counts, label, u, m, L = _focus_columns(rows, group, int(n_groups), grid, mask, perm,
+                                            dimension)
+    has, term, _, _ = _focus_terms(counts, label, u, m, L, foci, grid[9])
+    return torch.where(has, term, torch.zeros_like(term))
+
+
+def focus_points(foci, grid, dimension=3):
+    """The (G, dimension) float64 foci in scene coordinates, ``c + R * x``, from the (G, 4) table
+    of tfrt_focus_error; NaN for a group without a focus."""
+    d = int(dimension)
+    c = torch.tensor(grid[6:6 + d], dtype=torch.float64, device=foci.device)
+    return c + grid[9] * foci[:, :d]
+
+
+def focus_error(rows, groups, n_groups, grid, min_det, mask=None, perm=None, dimension=3,
+                grad=None, err=None, acc=None, foci=None, workspace=None, variant=0):
+    """tfrt_focus_error: the FocusError of the columns of the (2 * dimension, n) geometry block
+    ``rows`` -- rays of one group, taken as lines, must pass through one common point.
+    ``groups``: contiguous int32 labels, one per SOURCE ray; ``perm``: optional int32 (n,), the
+    source ray of column i (None: column i is source ray i); ``n_groups``: G, labels outside
+    [0, G) have no term; ``grid`` from ``focus_grid``; ``min_det``: a group has a focus if it has
+    at least two rays and ``det(A / count) >= min_det``; ``mask``: optional int32, column i counts
+    if mask[i] >= 0.  The fixed point has ``focus_pbits(groups.numel())`` fraction bits.  Returns
+    (err {sum, terms, mean}, grad (2 * dimension, n) float64 -- every row written for every
+    column --, acc (G, 10) int64 {count, Pxx, Pxy, Pxz, Pyy, Pyz, Pzz, tx, ty, tz}, foci (G, 4)
+    float64 {x, y, z, has_focus} in normalised coordinates (``focus_points`` gives the scene's),
+    NaN for a group without a focus).  ``grad``, ``err``, ``acc``, ``foci``, ``workspace`` (uint8):
+    buffers to reuse -- with all five given a CUDA call allocates nothing.  ``variant``: 0 by G,
+    1 the table in LDS, 2 global atomics.
+
+    CUDA tensors run the kernels.  CPU tensors run a torch restatement with the same int64 fixed
+    point and the same operations, each rounded on its own (``acc``, ``foci`` and the gradient
+    agree bit for bit; the error sum is torch's and agrees to rounding)."""
+    n_groups = int(n_groups)
+    if groups.dtype != torch.int32 or groups.dim() != 1 or not groups.is_contiguous():
+        raise ValueError("focus_error: groups must be a contiguous int32 vector, one label per "
+                         "source ray")
+    if not 1 <= n_groups <= FOCUS_MAX_GROUPS:
+        raise ValueError(f"focus_error: n_groups must lie in 1 .. {FOCUS_MAX_GROUPS}")
+    if dimension not in (2, 3) or rows.dim() != 2 or rows.shape[0] != 2 * dimension:
+        raise ValueError("focus_error: rows must be the (2 * dimension, n) geometry block of a "
+                         f"2-D or 3-D trace, got dimension {dimension!r} and shape "
+                         f"{tuple(rows.shape)}")
+    if len(grid) != 11:
+        raise ValueError("focus_error: grid must come from focus_grid")
+    min_det = float(min_det)
+    if not (min_det > 0.0 and np.isfinite(min_det)):
+        raise ValueError("focus_error: min_det must be finite and > 0")
+    if variant not in (0, 1, 2) or (variant == 1 and n_groups > FOCUS_LDS_GROUPS):
+        raise ValueError(f"focus_error: variant must be 0, 1 (up to {FOCUS_LDS_GROUPS} groups) "
+                         "or 2")
+    n = rows.shape[1]
+    pbits = focus_pbits(groups.numel())
+    if n >= 1 << (61 - pbits):
+        raise ValueError("focus_error: more columns than the source's fixed point allows "
+                         "(n < 2^(61 - pbits))")
+    grad, err = _column_buffers("focus_error", rows, grad, err, mask, perm)
+    if acc is None:
+        acc = torch.empty((n_groups, FOCUS_SLOTS), dtype=torch.int64, device=rows.device)
+    if tuple(acc.shape) != (n_groups, FOCUS_SLOTS) or acc.dtype != torch.int64 \
+            or not acc.is_contiguous():
+        raise ValueError(f"focus_error: acc must be contiguous int64 of shape (n_groups, "
+                         f"{FOCUS_SLOTS})")
+    if foci is None:
+        foci = torch.empty((n_groups, 4), dtype=torch.float64, device=rows.device)
+    if tuple(foci.shape) != (n_groups, 4) or foci.dtype != torch.float64 \
+            or not foci.is_contiguous():
+        raise ValueError("focus_error: foci must be contiguous float64 of shape (n_groups, 4)")
+    if not rows.is_cuda:
+        _focus_error_cpu(rows, groups, n_groups, grid, min_det, mask, perm, dimension, grad, err,
+                         acc, foci, pbits)
+        return err, grad, acc, foci
+    L = _lib.lib()
+    workspace = _column_workspace(
+        "focus_error", rows, grad, workspace,
+        lambda: L.tfrt_focus_error_workspace_bytes(n, n_groups), groups, mask, perm, err, acc, foci)
+    check(L.tfrt_focus_error(
+        _p(rows), rows.stride(0), n, _DT[rows.dtype], int(dimension), _p(mask), _p(groups),
+        groups.numel(), _p(perm), n_groups, *grid[:6], pbits, min_det, _p(grad), grad.stride(0),
+        _p(err), _p(acc), _p(foci), int(variant), _p(workspace), workspace.numel(),
+        _stream(rows)), "tfrt_focus_error")
+    return err, grad, acc, foci
+
+
+def _focus_error_cpu(rows, groups, n_groups, grid, min_det, mask, perm, d, grad, err, acc, foci,
+                     pbits):
+    """The CPU path of ``focus_error`` (every torch op rounds on its own, as the kernels do)."""
+    n = rows.shape[1]
+    one = float(np.ldexp(1.0, pbits))
+    counts, label, u, m, L = _focus_columns(rows, groups, n_groups, grid, mask, perm, d)
+    # the records: P = I - u u^T and t = m - (u . m) u as integers
+    w = _dot_rows(u, m)
+    pairs = {1: (0, 0), 2: (0, 1), 3: (0, 2), 4: (1, 1), 5: (1, 2), 6: (2, 2)}
+    li = label[counts]
+    acc.zero_()
+    acc[:, 0].index_add_(0, li, torch.ones_like(li))
+    for p in range(1, FOCUS_SLOTS):
+        if d == 2 and p in _FOCUS_Z_SLOTS:
+            continue
+        if p < 7:
+            a, b = pairs[p]
+            v = 1.0 - u[a] * u[a] if a == b else -(u[a] * u[b])
+        else:
+            v = m[p - 7] - w * u[p - 7]
+        acc[:, p].index_add_(0, li, torch.round(v[counts] * one).long())
+    foci.copy_(_focus_solve(acc, pbits, min_det, d))
+    has, term, gs, ge = _focus_terms(counts, label, u, m, L, foci, grid[9])
+    zero = torch.zeros((), dtype=torch.float64)
+    for b in range(d):
+        grad[b, :n] = torch.where(has, gs[b], zero)
+        grad[d + b, :n] = torch.where(has, ge[b], zero)
+    n_terms = int(has.sum())
+    e = term[has].sum()
+    err[0], err[1] = e, float(n_terms)
+    err[2] = e / n_terms if n_terms > 0 else float("nan")
+
+
 # ------------------------------------------------------- a sum of error terms (SumError)
 
 COMBINE_MAX_TERMS = _lib.COMBINE_MAX_TERMS

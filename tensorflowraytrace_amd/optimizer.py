@@ -29,9 +29,10 @@ import torch
 
 from . import distributed as tdist
 from . import _lib, ops
-# (GoalError, RowwiseError, DensityError, SpotError, TransportError, SumError: public API)
+# (GoalError, RowwiseError, DensityError, SpotError, TransportError, FocusError, SumError: public
+# API)
 from .fused_step import (FusedStep, GoalError, RowwiseError, DensityError, SpotError,  # noqa: F401
-                         TransportError, SumError, _NotInPlace)
+                         TransportError, FocusError, SumError, _NotInPlace)
 
 
 class DeferredScalar:

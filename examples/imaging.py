@@ -45,6 +45,15 @@ the error is the lens' aberration alone.  Where the focus should lie is a second
 (a ``SumError`` with a ``GoalError``, as ``--magnification`` builds for the ``SpotError``).
 
     python examples/imaging.py --focus [--rays 20000] [--steps 30] [--generic]
+
+``--distortion [scale|affine]`` asks for an undistorted image without pinning its scale or place:
+``SumError([SpotError, DistortionError], reduce="mean")``.  The ``DistortionError`` fits the
+spots' centroids to ``A p + t`` over the object points p -- a free magnification (``scale``) or a
+free 2 x 2 matrix (``affine``) and a free offset -- and charges every ray the squared distance of
+its spot's centroid from the fitted image of its object point.  Every report prints the fitted
+magnification and the largest residual.
+
+    python examples/imaging.py --distortion scale [--rays 20000] [--steps 30] [--generic]
 """
 import argparse
 import math
@@ -95,7 +104,8 @@ def gaussian_pupil(sigma, cone):
 
 
 def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, target_distance=10.0,
-          object_size=0.2, lens_aperature=1.0, apodize=None, magnification=None, focus=False):
+          object_size=0.2, lens_aperature=1.0, apodize=None, magnification=None, focus=False,
+          distortion=None):
     points = letter_f(object_size)
     P = points.shape[0]
     A = max(ray_count // P, 2)
@@ -155,18 +165,27 @@ def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, target_dis
             [spot, optimizer.GoalError(("y_end", "z_end"),
                                        torch.as_tensor(image).to(lens.parameters[0].device))],
             reduce="mean")
+    distortion_term = None
+    if distortion is not None:
+        # the object points in the fields' order (y, z): one row per label
+        distortion_term = optimizer.DistortionError(
+            ("y_end", "z_end"), labels, points[:, 1:],
+            ((-HALF_DOMAIN, HALF_DOMAIN), (-HALF_DOMAIN, HALF_DOMAIN)), fit=distortion)
+        error_function = optimizer.SumError([spot, distortion_term], reduce="mean")
     return dict(engine=trace_engine, system=system, lens=lens, source=source, n_rays=n_rays,
-                n_points=P, error_function=error_function, spot=spot, accumulator=accumulator)
+                n_points=P, error_function=error_function, spot=spot, accumulator=accumulator,
+                distortion=distortion_term)
 
 
 def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=False, verbose=True,
-        learning_rate=None, apodize=None, magnification=None, focus=False):
-    s = build(ray_count, lens_res_scale, apodize=apodize, magnification=magnification, focus=focus)
+        learning_rate=None, apodize=None, magnification=None, focus=False, distortion=None):
+    s = build(ray_count, lens_res_scale, apodize=apodize, magnification=magnification, focus=focus,
+              distortion=distortion)
     combined, erf = s["error_function"], s["spot"]
     if learning_rate is None:
         # (the error is a sum over the rays: the step size goes with 1 / rays)
         learning_rate = LEARNING_RATE * (20000 / s["n_rays"])
-        if magnification is not None:
+        if magnification is not None or distortion is not None:
             # (a mean over two terms per ray: the same step per ray as the sum's)
             learning_rate = MEAN_LEARNING_RATE
     kw = dict(learning_rate=learning_rate, grad_clip=1.0, fused=False if generic else "auto")
@@ -176,7 +195,8 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=Fals
     else:
         opt = optimizer.SGD_Optimizer(s["engine"], s["lens"].parameters, combined, 3, **kw)
     opt.suppress_warnings = True
-    rms, times, errors, place = [], [], [], []
+    rms, times, errors, place, fits = [], [], [], [], []
+    summed = magnification is not None or distortion is not None
     for step in range(steps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -190,7 +210,7 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=Fals
             inside = int(erf.last_acc[:, 5].sum())
             light = math.ldexp(int(erf.last_acc[:, 0].sum()), -erf.graph_key()[-1])
         errors.append(mean)
-        if magnification is None:
+        if not summed:
             error_sum = mean * float(opt.last_error_terms)
         else:
             # (the terms' own triples {sum, terms, mean} of the step)
@@ -200,11 +220,21 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=Fals
         if verbose and (step % 5 == 0 or step == steps - 1):
             extra = "" if magnification is None else \
                 f"  mean squared image distance {place[-1]:.6g}  combined {mean:.6g}"
+            if distortion is not None:
+                fit = s["distortion"].fit_parameters()
+                r = s["distortion"].residuals()
+                worst = float(torch.linalg.norm(r[torch.isfinite(r).all(dim=1)], dim=1).max())
+                scale = fit["magnification"] if distortion == "scale" else \
+                    float(torch.linalg.det(fit["matrix"]))
+                fits.append((scale, worst))
+                extra = (f"  mean squared distortion {place[-1]:.6g}  combined {mean:.6g}  "
+                         f"{'magnification' if distortion == 'scale' else 'det A'} {scale:.6g}  "
+                         f"largest |r| {worst:.6g}")
             what = "rms distance to the focus" if focus else "rms spot"
             print(f"step {step:4d}: {what} {rms[-1]:.6g}{extra}  ({inside} rays inside, "
                   f"{1e3 * times[-1]:.2f} ms)")
     fused = opt._fused_step
-    s.update(rms=rms, times=times, errors=errors, place=place,
+    s.update(rms=rms, times=times, errors=errors, place=place, fits=fits,
              graph_replays=0 if fused is None else fused.graph_replays,
              centroids=erf.foci() if focus else erf.centroids())
     return s
@@ -225,11 +255,18 @@ if __name__ == "__main__":
                     help="pin the image of (y, z) to (-M y, -M z): SumError([SpotError, GoalError])")
     ap.add_argument("--focus", action="store_true",
                     help="a FocusError in the place of the SpotError: the axial position is free")
+    ap.add_argument("--distortion", nargs="?", const="scale", default=None,
+                    choices=("scale", "affine"),
+                    help="SumError([SpotError, DistortionError]): an undistorted image at a free "
+                         "magnification (scale) or under a free 2 x 2 matrix (affine)")
     a = ap.parse_args()
     if a.focus and (a.apodize is not None or a.magnification is not None):
         ap.error("--focus takes neither --apodize nor --magnification")
+    if a.distortion is not None and (a.focus or a.magnification is not None):
+        ap.error("--distortion takes neither --magnification nor --focus")
     out = run(a.rays, a.steps, a.edge, generic=a.generic, adam=a.adam, learning_rate=a.lr,
-              apodize=a.apodize, magnification=a.magnification, focus=a.focus)
+              apodize=a.apodize, magnification=a.magnification, focus=a.focus,
+              distortion=a.distortion)
     tail = sorted(out["times"][len(out["times"]) // 2:])
     print(f"{out['n_points']} object points, {out['n_rays']} rays; steps replayed from the graph: "
           f"{out['graph_replays']} of {a.steps}; median step of the second half: "
@@ -243,6 +280,12 @@ if __name__ == "__main__":
               f"{float(x.max()):.6g}, spread {float(x.max() - x.min()):.6g} (field curvature)")
     else:
         print(f"rms spot: first {out['rms'][0]:.6g} last {out['rms'][-1]:.6g}")
+    if a.distortion is not None:
+        print(f"mean squared distortion: first {out['place'][0]:.6g} last {out['place'][-1]:.6g}")
+        print(f"combined error: first {out['errors'][0]:.6g} last {out['errors'][-1]:.6g}")
+        scale, worst = out["fits"][-1]
+        print(f"fitted {'magnification' if a.distortion == 'scale' else 'det A'} {scale:.6g}, "
+              f"largest |r| {worst:.6g}")
     if a.magnification is not None:
         print(f"mean squared image distance: first {out['place'][0]:.6g} last "
               f"{out['place'][-1]:.6g}")

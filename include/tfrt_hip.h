@@ -941,6 +941,77 @@ int tfrt_focus_error(const void* rows, int64_t stride, int64_t n, int32_t state_
                      double* foci, int32_t variant, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* DistortionError: the centroids of the groups must be a scaled (or affine) copy of the object,
+ * at whatever magnification and offset the lens gives -- the distortion term of a lens merit
+ * function.  Every group g has an object point p_g (`points`); a weighted least-squares fit
+ * c ~ A p + t over the groups' centroids gives every group a target, and the error is the sum over
+ * the rays inside of the squared distance of their GROUP'S CENTROID from its target, plus
+ * tfrt_spot_error's penalty for rays outside the domain.  Four launches (clear `acc`,
+ * tfrt_spot_error's unweighted accumulate launch, fit, seed), no host read, no allocation, no float
+ * atomics: captured with the rest of a step.
+ *
+ * The columns, the fields and their codes, the four cases of a counting column in their order, the
+ * out-of-domain penalty and its gradient, the records {count, Sx, Sy, 0} with `qbits` and qsx, qsy,
+ * terms = k * (number of counting columns) and the chain rule of a direction field are exactly
+ * tfrt_spot_error_fields'.  Every operation below is an IEEE f64 operation rounded on its own (no
+ * contraction).  With one field the y component of every point and centroid is 0.0 and the same
+ * expressions run.
+ *
+ * A group with count > 0 is USED: w = (double) count, cx = x0 + ((double) Sx / w) / qsx, cy alike,
+ * (px, py) = its row of `points`.  Sums over the used groups:
+ *   first pass    W = sum w,  pm = (sum w * p) / W,  cm = (sum w * c) / W          (per component)
+ *   second pass   dp = p - pm, dc = c - cm;
+ *                 Sxx = sum w * (dpx * dpx), Sxy = sum w * (dpx * dpy), Syy = sum w * (dpy * dpy),
+ *                 Cxx = sum w * (dcx * dpx), Cxy = sum w * (dcx * dpy),
+ *                 Cyx = sum w * (dcy * dpx), Cyy = sum w * (dcy * dpy)
+ * The fit, with trp = Sxx + Syy:
+ *   fit_kind 0, "scale" (and fit_kind 1 with one field): M = (Cxx + Cyy) / trp, A = M I (A01 = A10
+ *     = 0.0); VALID iff at least two groups are used and trp > 0;
+ *   fit_kind 1, "affine" (two fields): det = Sxx * Syy - Sxy * Sxy, h = trp / 2.0; VALID iff
+ *     det > min_cond * (h * h) (scale-free);  A = Scp Spp^-1 by cofactors:
+ *       A00 = (Cxx * Syy - Cxy * Sxy) / det,  A01 = (Cxy * Sxx - Cxx * Sxy) / det,
+ *       A10 = (Cyx * Syy - Cyy * Sxy) / det,  A11 = (Cyy * Sxx - Cyx * Sxy) / det;
+ *   t0 = cmx - (A00 * pmx + A01 * pmy),  t1 = cmy - (A10 * pmx + A11 * pmy)      (for reporting).
+ * Third pass, for a used group with a valid fit:
+ *   rx = cx - (cmx + (A00 * dpx + A01 * dpy)),  ry = cy - (cmy + (A10 * dpx + A11 * dpy));
+ * without a valid fit rx = ry = 0.0; an unused group has rx = ry = NaN.
+ *   error = (sum w * (rx * rx) + sum w * (ry * ry)) + the sum of the penalties.
+ * A ray inside gets the gradient 2.0 * rx and 2.0 * ry of its own group (chained onto the start
+ * and end rows with a direction field, as the spot seed): exact without a derivative of the fit,
+ * because (A, t) minimises the error, and d c / d x_i = 1 / count (up to the quantisation of the
+ * records).  Without a valid fit the rays inside add no error and get a zero gradient; the
+ * penalties remain.
+ * Every sum over the groups has a fixed shape and order: thread j of the one workgroup of
+ * B = 1,024 threads takes the groups j, j + B, j + 2B, ... in ascending order, starting from 0.0
+ * and skipping unused groups; the threads are combined within each 64-lane wave by
+ * v += v[lane ^ d] for d = 32, 16, 8, 4, 2, 1, then the 16 waves in index order starting from 0.0.
+ * The penalty and count partials of the accumulate launch are summed the same way, in index order.
+ * Two runs give the same bits.
+ *
+ *   points       n_groups rows of k f64 (k = the number of fields), on the device; read by the
+ *                fit launch, so overwriting it between replays of a captured step is seen
+ *   fit_kind     0: scale, 1: affine
+ *   min_cond     finite and >= 0
+ *   fit_out      8 f64 {A00, A01, A10, A11, t0, t1, valid (1.0 / 0.0), groups used}; A and t are
+ *                NaN without a valid fit
+ *   residual     n_groups rows of two f64 {rx, ry}, 16-byte aligned
+ *   acc          n_groups records of four int64 {count, Sx, Sy, 0}, cleared and filled by this call
+ *   variant      tfrt_spot_error's
+ *   workspace    tfrt_distortion_error_workspace_bytes(n, n_groups) bytes (0: bad arguments)
+ * Everything else as for tfrt_spot_error_fields.  Bad arguments are refused with TFRT_E_BADARG /
+ * TFRT_E_WORKSPACE before any launch.
+ */
+size_t tfrt_distortion_error_workspace_bytes(int64_t n, int32_t n_groups);
+int tfrt_distortion_error(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                          int32_t dimension, const int32_t* mask, int32_t field_x,
+                          int32_t field_y, const int32_t* group, int64_t n_source,
+                          const int32_t* perm, int32_t n_groups, const double* points,
+                          int32_t fit_kind, double min_cond, double x0, double x1, double qsx,
+                          double y0, double y1, double qsy, int32_t qbits, double oob_weight,
+                          double* grad, int64_t grad_stride, double* error_out, double* fit_out,
+                          double* residual, int64_t* acc, int32_t variant, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* GoalError on the fixed-shape columns of an in-place trace (tfrt_scene3d.in_place == 2: the
  * finished rows at the rays' own columns, a mask in the place of a ray count) -- the form that can
  * be added to a coupled error of the same step (tfrt_error_combine).  Two launches (the columns,

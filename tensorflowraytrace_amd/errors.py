@@ -13,7 +13,9 @@ one group must meet in one point -- ``tfrt_spot_error`` (clear, accumulate, seed
 ``TransportError`` -- the same target density by sliced optimal transport --
 ``tfrt_transport_error`` (per direction keys, radix sort, sorted keys, ranks; then seed and
 finish); a ``FocusError`` -- rays of one group, taken as lines, must pass through one point of
-space -- ``tfrt_focus_error`` (clear, accumulate, solve, seed, finish).  A ``SumError`` is a
+space -- ``tfrt_focus_error`` (clear, accumulate, solve, seed, finish); a ``DistortionError`` --
+the groups' centroids must be a scaled or affine copy of the object points --
+``tfrt_distortion_error`` (clear, SpotError's accumulate, fit, seed).  A ``SumError`` is a
 weighted sum of such terms and of ``GoalError``s: every term's launches into a seed block of its
 own (a ``GoalError`` through ``tfrt_goal_error_columns``), then ONE ``tfrt_error_combine`` for the
 step's seed block and error.
@@ -22,7 +24,7 @@ Each is an ordinary error function (``__call__(engine)``): the generic path give
 numbers, which is what the parity tests compare.
 
 The protocol between a built-in term (``GoalError``, ``DensityError``, ``SpotError``,
-``TransportError``, ``FocusError``) and the fused 3-D step:
+``TransportError``, ``FocusError``, ``DistortionError``) and the fused 3-D step:
 
 * ``rows``, ``fields``, ``rows_for(dimension)``: the rows of the ray block (the field codes) the
   term reads;
@@ -1250,8 +1252,239 @@ class _FocusTerms(torch.autograd.Function):
         return (upstream[:, 0] * grad).to(ctx.dtype), None, None, None
 
 
+class DistortionError(_CoupledError):
+    """The image must be an undistorted copy of the object -- at whatever scale and offset the
+    lens gives: the distortion term of a lens merit function.  A ``SpotError`` makes the rays of
+    an object point meet and leaves where the spots lie to the lens; a ``GoalError`` pins them to
+    image points known in advance.  Here every group g has an object point ``p_g``, the centroids
+    ``c_g`` of the groups' finished rays are fitted by ``c ~ A p + t`` over all groups, and the
+    error is the sum over the rays inside the domain of the squared distance of their GROUP'S
+    CENTROID from its fitted target ``A p_g + t``.  Neither the magnification nor the image
+    centre is needed; both can be read afterwards (``fit_parameters()``).  It says nothing about
+    spot size: add a ``SpotError`` in a ``SumError`` for that.
+
+    ``fields``, ``groups``, ``domain``, ``oob_weight`` and ``n_groups`` are exactly
+    ``SpotError``'s: one or two fields (positions or direction cosines), one label per SOURCE ray
+    (or a callable with ``n_groups``), the label ``-1`` excludes a ray, rays outside the closed
+    domain take the penalty ``oob_weight * (ex**2 + ey**2)`` and are in no group.  There are no
+    ``weights``.  ``points``: (G, k) floats, the object coordinates of each group in the order of
+    the fields, finite (a ``ValueError`` otherwise); kept as float64 on the device (``points``)
+    and overwritable in place between steps -- a replayed graph reads the buffer.
+    ``fit``: ``"scale"`` -- a scalar magnification M, sign free, ``A = M I``, and a free offset
+    -- or ``"affine"`` -- a free k x k matrix and offset (with one field that is the scale fit).
+    ``min_cond``: finite and >= 0, the affine fit's guard (below).
+
+    For every finished ray, the four cases of ``SpotError`` in its order; a ray inside enters its
+    group's record ``{count, Sx, Sy, 0}`` with the same ``qbits`` and ``qsx``.  A group with
+    ``count > 0`` is USED: its weight ``w = count``, its centroid ``c`` as ``SpotError`` computes
+    it.  Every float64 operation is rounded on its own; with one field the y components are 0.0:
+
+    * ``W = sum w``, ``pm = (sum w p) / W``, ``cm = (sum w c) / W``;
+    * ``dp = p - pm``, ``dc = c - cm``, ``Spp = sum w dp dp^T``, ``Scp = sum w dc dp^T`` (each
+      entry ``w * (d1 * d2)``);
+    * ``"scale"``: ``M = tr(Scp) / tr(Spp)``; valid iff at least two groups are used and
+      ``tr(Spp) > 0``.  ``"affine"``: ``A = Scp Spp^-1`` by cofactors; valid iff
+      ``det(Spp) > min_cond * (tr(Spp) / 2)**2`` (scale-free: collinear object points have no
+      affine fit);
+    * ``r = c - (cm + A dp)`` per used group, ``t = cm - A pm`` for reporting;
+    * ``error = sum w rx**2 + sum w ry**2 + penalties`` over ``len(fields) * n_finished`` terms;
+      a ray inside gets the gradient ``2 rx``, ``2 ry`` of its group (chained onto start and end
+      rows with a direction field, as ``SpotError``'s).  No derivative of the fit is needed,
+      because ``(A, t)`` minimises the error (up to the quantisation of the records).  Without a
+      valid fit the rays inside add no error and get a zero gradient; the penalties remain.
+
+    Every sum over the groups has a fixed shape and order (include/tfrt_hip.h at
+    tfrt_distortion_error): two runs give the same bits.
+
+    It is an ordinary ``error_function(engine)`` (the generic path: ``ops.distortion_error`` over
+    the finished rays' columns under a ``torch.autograd.Function`` that returns the (n_finished,
+    k) terms -- a ray inside carries its group's ``rx**2``, ``ry**2``), which also serves sources
+    that are not traced in place, ``deterministic=True``, fewer than 4,096 rays, several ranks
+    (each shard then fits its own rays) and 2-D engines.  Its ``backward`` returns ``upstream *
+    gradient``, exact when ``upstream`` is constant (the optimiser passes ones); with a direction
+    field both fields of a ray must carry the same factor.  On a 3-D engine that traces its
+    source in place the optimiser runs it on the fused, graph-replayed step wherever a
+    ``SpotError`` runs there (``FusedStep._rowwise3d`` with ``tfrt_distortion_error``: clear,
+    accumulate, fit, seed), and it is a legal term of a ``SumError``.
+
+    ``last_acc`` is the (G, 4) int64 record table of the last evaluation, ``centroids()`` the
+    (G, k) centroids made from it, ``residuals()`` the (G, k) residuals (NaN for a group without
+    rays) and ``fit_parameters()`` the fit.  ``splat_variant`` is ``SpotError``'s."""
+
+    splat_variant = 0
+
+    def __init__(self, fields, groups, points, domain, fit="scale", oob_weight=0.0, n_groups=None,
+                 min_cond=1e-9):
+        from . import config
+        what = "DistortionError"
+        self.fields, self.domain = _fields_and_domain(what, fields, domain)
+        self.rows = [_FIELDS3.index(f) for f in self.fields]
+        self.has_direction = any(f.endswith("_dir") for f in self.fields)
+        self.oob_weight = float(oob_weight)
+        if not (self.oob_weight >= 0.0 and np.isfinite(self.oob_weight)):
+            raise ValueError(f"{what}: oob_weight must be finite and >= 0")
+        if fit not in ops.DISTORTION_FITS:
+            raise ValueError(f"{what}: fit must be 'scale' or 'affine', got {fit!r}")
+        self.fit = fit
+        try:
+            self.min_cond = float(min_cond)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"{what}: min_cond must be a number, got {min_cond!r}") from e
+        if not (self.min_cond >= 0.0 and np.isfinite(self.min_cond)):
+            raise ValueError(f"{what}: min_cond must be finite and >= 0, got {min_cond!r}")
+        _init_groups(self, what, groups, n_groups, ops.SPOT_MAX_GROUPS)
+        k = len(self.fields)
+        try:
+            p = points.detach().cpu().numpy() if isinstance(points, torch.Tensor) \
+                else np.asarray(points)
+            p = np.ascontiguousarray(p, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"{what}: points must be numbers of shape ({self.n_groups}, {k})") \
+                from e
+        if p.ndim == 1 and k == 1:
+            p = p[:, None]
+        if p.shape != (self.n_groups, k):
+            raise ValueError(f"{what}: points must have shape (n_groups, fields) = "
+                             f"({self.n_groups}, {k}), got {p.shape}")
+        if not np.isfinite(p).all():
+            bad = np.nonzero(~np.isfinite(p).all(axis=1))[0][:5].tolist()
+            raise ValueError(f"{what}: points must be finite; rows {bad} are not")
+        self.points = torch.as_tensor(p).to(config.get_device())
+        self._grids = {}
+        self.last_acc = self.last_grid = self.last_qbits = None
+        self.last_fit = self.last_residual = None
+
+    def labels_of(self, src):
+        """The int32 label buffer of the source set ``src`` on its device, one label per source
+        ray, given or computed and cached as ``SpotError.labels_of`` does."""
+        return _source_buffer(self, "labels", self.groups,
+                              lambda v, dev: _as_labels("DistortionError", v, dev), src,
+                              "DistortionError", "label")
+
+    grid_for = SpotError.grid_for      # (the records are SpotError's: the same qbits and grid)
+
+    def points_on(self, device):
+        """The object points on ``device`` (moved once; a new buffer re-captures a graph)."""
+        if self.points.device != device:
+            self.points = self.points.to(device)
+        return self.points
+
+    def graph_key(self):
+        """What a captured step has baked in: the addresses of the label buffer and of the
+        ``points`` buffer, and the constants."""
+        lab = self.labels
+        return (None if lab is None else (lab.data_ptr(), tuple(lab.shape)), self.n_groups,
+                self.domain, self.oob_weight, self.splat_variant, self.points.data_ptr(),
+                self.fit, self.min_cond)
+
+    def evaluate(self, rows, row_x, row_y, labels, mask=None, perm=None, dimension=None,
+                 **buffers):
+        """``ops.distortion_error`` of the columns of ``rows`` with these labels, points, domain
+        and fit (``dimension`` given: ``rows`` is the geometry block, ``row_x`` / ``row_y`` field
+        codes)."""
+        qbits, grid = self.grid_for(labels.numel())
+        out = ops.distortion_error(rows, row_x, row_y, labels, self.n_groups,
+                                   self.points_on(rows.device), grid, fit=self.fit,
+                                   min_cond=self.min_cond, oob_weight=self.oob_weight, mask=mask,
+                                   perm=perm, variant=self.splat_variant, qbits=qbits,
+                                   dimension=dimension, **buffers)
+        self.last_acc, self.last_grid, self.last_qbits = out[2], grid, qbits
+        self.last_fit, self.last_residual = out[3], out[4]
+        return out
+
+    def seed_columns(self, cols, hold):
+        """tfrt_distortion_error on the step's columns: labels through the trace's order inside
+        the kernels, as a SpotError; the records go into ``hold.buffers["acc"]``, (G, 4), the fit
+        into ``["fit_out"]``, (8,), the residual table into ``["residual"]``, (G, 2)."""
+        labels = self.labels_of(cols.src)
+        G = self.n_groups
+        dev = cols.rows.device
+        held = self._held(hold, "acc", (G, 4), torch.int64, dev,
+                          lambda: _lib.lib().tfrt_distortion_error_workspace_bytes(cols.n, G))
+        if "residual" not in held:
+            held["fit_out"] = torch.zeros(8, dtype=torch.float64, device=dev)
+            held["residual"] = torch.zeros((G, 2), dtype=torch.float64, device=dev)
+        self.evaluate(cols.rows, *_xy(self.rows), labels, mask=cols.mask, perm=cols.perm,
+                      dimension=3, grad=hold.g_fin, err=hold.err, **held)
+
+    def _last(self, name):
+        value = getattr(self, name)
+        if value is None:
+            raise RuntimeError("DistortionError: no evaluation yet")
+        return value
+
+    def centroids(self):
+        """(G, k) float64 centroids of the last evaluation, NaN for a group without rays."""
+        return ops.spot_centroids(self._last("last_acc"), self.last_grid, len(self.fields),
+                                  self.last_qbits)
+
+    def residuals(self):
+        """(G, k) float64 residuals ``c - (A p + t)`` of the last evaluation: NaN for a group
+        without rays, zeros without a valid fit."""
+        return self._last("last_residual")[:, :len(self.fields)]
+
+    def fit_parameters(self):
+        """The fit of the last evaluation, read from the device: a dict with ``matrix`` (k, k) and
+        ``offset`` (k,) float64 CPU tensors (NaN without a valid fit), ``valid``,
+        ``groups_used`` and, for ``fit="scale"``, ``magnification``."""
+        f = self._last("last_fit").detach().cpu()
+        k = len(self.fields)
+        out = dict(matrix=f[:4].reshape(2, 2)[:k, :k].clone(), offset=f[4:4 + k].clone(),
+                   valid=bool(f[6] != 0.0), groups_used=int(f[7]))
+        if self.fit == "scale":
+            out["magnification"] = float(f[0])
+        return out
+
+    def __call__(self, engine):
+        """The (n_finished, k) error terms through the generic path; the gradient rows come back
+        in ``backward``."""
+        codes = self.rows_for(engine.dimension)
+        fin = engine.finished_rays
+        if not bool(fin):
+            return torch.zeros((0, len(self.fields)), dtype=torch.float64)
+        labels = self.labels_of(engine._trace_src)
+        block, _, ids, dim, codes = self._finished_block(engine, fin, codes, ids=True)
+        return _DistortionTerms.apply(block, self, labels, ids, dim, codes)
+
+
+class _DistortionTerms(torch.autograd.Function):
+    """DistortionError over the finished rays, no mask; ``ids``: the source ray of every column;
+    ``block``, ``dimension`` and ``codes`` as for ``_SpotTerms``.  Returns the (n, k) terms: a
+    penalised ray's ``oob_weight * ex**2`` per field, an inside ray's squared residuals of its
+    GROUP (their sum over the rays is the groups' ``w * r**2``), zeros for the rest."""
+
+    @staticmethod
+    def forward(ctx, block, erf, labels, ids, dimension=None, codes=None):
+        rows = block.detach().contiguous()
+        ctx.chained = codes is not None
+        if codes is None:
+            codes = (0, 1)[:rows.shape[0]]
+        _, grad, acc, _, residual = erf.evaluate(rows, *_xy(codes), labels, perm=ids,
+                                                 dimension=dimension)
+        ctx.save_for_backward(grad)
+        ctx.dtype = block.dtype
+        if ctx.chained:
+            link = ops._link_torch(rows, dimension)
+            v = torch.stack([ops._link_field_torch(link, c, dimension) for c in codes], dim=0)
+        else:
+            v = rows.double()
+        s = ids.long().clamp(0, labels.numel() - 1)
+        r = residual[labels[s].long().clamp(0, erf.n_groups - 1), :v.shape[0]].t()
+        return _spot_terms(erf, v, labels, ids, acc, None, inside=r * r)
+
+    @staticmethod
+    def backward(ctx, upstream):
+        grad, = ctx.saved_tensors
+        if not ctx.chained:
+            return (upstream.t() * grad).to(ctx.dtype), None, None, None, None, None
+        if upstream.shape[1] == 2 and not torch.equal(upstream[:, 0], upstream[:, 1]):
+            raise ValueError("DistortionError with a direction field: the upstream gradient must "
+                             "weigh both fields of a ray alike")
+        return (upstream[:, 0] * grad).to(ctx.dtype), None, None, None, None, None
+
+
 # the coupled errors: all finished rays of a step enter one evaluation (one process)
-_COUPLED = (DensityError, SpotError, TransportError, FocusError)
+_COUPLED = (DensityError, SpotError, TransportError, FocusError, DistortionError)
 
 
 class SumError:
@@ -1262,7 +1495,7 @@ class SumError:
     step is one trace, K error evaluations, one combination and one reverse sweep.
 
     ``terms``: 1 to 8 distinct instances of ``GoalError``, ``DensityError``, ``SpotError``,
-    ``TransportError`` or ``FocusError``; a ``RowwiseError``, a nested ``SumError`` or the same
+    ``TransportError``, ``FocusError`` or ``DistortionError``; a ``RowwiseError``, a nested ``SumError`` or the same
     object twice is a ValueError.  ``weights``: K finite values >= 0, default all ones, kept as the (K,) float64
     device tensor ``weights``; ``set_weights(values)`` validates on the host and overwrites that
     buffer in place, so a replayed graph sees the new values without a re-capture (as
@@ -1275,7 +1508,7 @@ class SumError:
 
     After an evaluation ``last_errors`` is the (K, 3) tensor of the terms' own triples {sum, terms,
     mean} and ``last_coefficients`` the (K,) ``c_k``; each term keeps its own ``last_hq`` /
-    ``centroids()`` / ``last_rank2`` / ``foci()`` as when it runs alone.
+    ``centroids()`` / ``last_rank2`` / ``foci()`` / ``fit_parameters()`` as when it runs alone.
 
     It is an ordinary ``error_function(engine)`` -- the generic path returns the (1,) tensor
     ``sum_k c_k * term_k(engine).sum()`` (``terms_k = numel``) under torch autograd, which serves
@@ -1305,7 +1538,7 @@ class SumError:
                                  "code of its own); state it as a GoalError")
             if not isinstance(t, (GoalError,) + _COUPLED):
                 raise ValueError("SumError: terms must be GoalError, DensityError, SpotError, "
-                                 "TransportError or FocusError instances, got "
+                                 "TransportError, FocusError or DistortionError instances, got "
                                  f"{type(t).__name__}")
         if len(set(id(t) for t in terms)) != len(terms):
             raise ValueError("SumError: the same term object is listed twice (a term keeps the "

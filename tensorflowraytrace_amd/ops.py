@@ -2024,6 +2024,199 @@ def _spot_error_cpu(rows, row_x, row_y, group, n_groups, grid, oob, mask, perm, 
     err[2] = e / n_terms if n_terms > 0 else float("nan")
 
 
+# ------------------------------------------- group centroids as a scaled copy of the object
+DISTORTION_FITS = {"scale": 0, "affine": 1}
+DISTORTION_BLOCK = 1024            # k_distortion_fit: one workgroup of 16 waves
+
+
+def distortion_group_sum(values, used):
+    """The sum of ``values[used]`` over the groups in the fixed shape and order of
+    k_distortion_fit, as float64 torch ops on the CPU: thread j takes the groups j, j + 1024, ...
+    in ascending order from 0.0 (unused groups skipped), the 64 lanes of a wave are combined by
+    ``v += v[lane ^ d]`` for d = 32 .. 1, then the 16 waves in index order from 0.0."""
+    B = DISTORTION_BLOCK
+    G = values.numel()
+    trips = max((G + B - 1) // B, 1)
+    v = torch.zeros(trips * B, dtype=torch.float64)
+    u = torch.zeros(trips * B, dtype=torch.bool)
+    v[:G], u[:G] = values.double().cpu(), used.cpu()
+    s = torch.zeros(B, dtype=torch.float64)
+    for vt, ut in zip(v.view(trips, B), u.view(trips, B)):
+        s = torch.where(ut, s + vt, s)
+    w = s.view(B // 64, 64)
+    for d in (32, 16, 8, 4, 2, 1):
+        w = w[:, :d] + w[:, d:2 * d]
+    total = torch.zeros((), dtype=torch.float64)
+    for wave in w[:, 0]:
+        total = total + wave
+    return total
+
+
+def _distortion_fit_cpu(acc, points, grid, two, fit_kind, min_cond):
+    """(fit_out (8,), residual (G, 2)) of a record table: distortion_math.h, operation by
+    operation, over all groups at once (CPU float64 tensors)."""
+    x0, _, qsx, y0, _, qsy = grid
+    G = acc.shape[0]
+    cnt = acc[:, 0]
+    used = cnt > 0
+    w = cnt.double()
+    zeros = torch.zeros(G, dtype=torch.float64)
+    safe = torch.where(used, w, torch.ones_like(w))
+    cx = x0 + (acc[:, 1].double() / safe) / qsx
+    cy = y0 + (acc[:, 2].double() / safe) / qsy if two else zeros
+    px = points[:, 0].double()
+    py = points[:, 1].double() if two else zeros
+    gsum = lambda v: distortion_group_sum(v, used)          # noqa: E731
+    W = gsum(w)
+    pmx, pmy, cmx, cmy = (gsum(w * v) / W for v in (px, py, cx, cy))
+    n_used = int(used.sum())
+    dpx, dpy, dcx, dcy = px - pmx, py - pmy, cx - cmx, cy - cmy
+    Sxx, Sxy, Syy = gsum(w * (dpx * dpx)), gsum(w * (dpx * dpy)), gsum(w * (dpy * dpy))
+    Cxx, Cxy = gsum(w * (dcx * dpx)), gsum(w * (dcx * dpy))
+    Cyx, Cyy = gsum(w * (dcy * dpx)), gsum(w * (dcy * dpy))
+    trp = Sxx + Syy
+    nan = float("nan")
+    fit = torch.full((8,), nan, dtype=torch.float64)
+    if fit_kind == 1 and two:
+        det = Sxx * Syy - Sxy * Sxy
+        h = trp / 2.0
+        valid = bool(det > min_cond * (h * h))
+        A = ((Cxx * Syy - Cxy * Sxy) / det, (Cxy * Sxx - Cxx * Sxy) / det,
+             (Cyx * Syy - Cyy * Sxy) / det, (Cyy * Sxx - Cyx * Sxy) / det)
+    else:
+        valid = n_used >= 2 and bool(trp > 0.0)
+        M = (Cxx + Cyy) / trp
+        A = (M, zeros[0], zeros[0], M)
+    residual = torch.full((G, 2), nan, dtype=torch.float64)
+    if valid:
+        fit[0], fit[1], fit[2], fit[3] = A
+        fit[4] = cmx - (A[0] * pmx + A[1] * pmy)
+        fit[5] = cmy - (A[2] * pmx + A[3] * pmy)
+        rx = cx - (cmx + (A[0] * dpx + A[1] * dpy))
+        ry = cy - (cmy + (A[2] * dpx + A[3] * dpy))
+    else:
+        rx = ry = zeros
+    residual[:, 0] = torch.where(used, rx, residual[:, 0])
+    residual[:, 1] = torch.where(used, ry, residual[:, 1])
+    fit[6], fit[7] = float(valid), float(n_used)
+    inside = gsum(w * (residual[:, 0] * residual[:, 0])) \
+        + gsum(w * (residual[:, 1] * residual[:, 1]))
+    return fit, residual, inside
+
+
+def distortion_error(rows, row_x, row_y, group, n_groups, points, grid, fit="scale",
+                     min_cond=1e-9, oob_weight=0.0, mask=None, perm=None, grad=None, err=None,
+                     acc=None, fit_out=None, residual=None, variant=0, workspace=None, qbits=None,
+                     dimension=None):
+    """tfrt_distortion_error: the DistortionError of the columns of ``rows`` -- the centroids of
+    the groups must be a scaled (``fit="scale"``) or affine (``"affine"``) copy of the object
+    points ``points`` (G, k) float64, at whatever magnification and offset fits best.  The
+    columns, ``row_x`` / ``row_y``, ``group``, ``perm``, ``n_groups``, ``grid`` (``spot_grid``),
+    ``qbits``, ``mask``, ``oob_weight``, ``variant`` and ``dimension`` are ``spot_error``'s
+    (without ``dimension`` the rows are those of a 3-D block, as there).  Returns (err {sum,
+    terms, mean}, grad, acc (G, 4) int64 {count, Sx, Sy, 0}, fit_out (8,) float64 {A00, A01, A10,
+    A11, t0, t1, valid, groups used}, residual (G, 2) float64 -- NaN for a group without rays, 0
+    without a valid fit).  ``grad``, ``err``, ``acc``, ``fit_out``, ``residual``, ``workspace``
+    (uint8): buffers to reuse -- with all six given a CUDA call allocates nothing.
+
+    CUDA tensors run the kernels.  CPU tensors run a torch restatement with the same int64 fixed
+    point, the same operations and the same order of the sums over the groups (``acc``,
+    ``fit_out``, ``residual`` and the gradient rows agree bit for bit; the penalty sum is torch's
+    and agrees to rounding)."""
+    what = "distortion_error"
+    n_groups = int(n_groups)
+    if group.dtype != torch.int32 or group.dim() != 1 or not group.is_contiguous():
+        raise ValueError(f"{what}: group must be a contiguous int32 vector, one label per "
+                         "source ray")
+    if not 1 <= n_groups <= SPOT_MAX_GROUPS:
+        raise ValueError(f"{what}: n_groups must lie in 1 .. {SPOT_MAX_GROUPS}")
+    if fit not in DISTORTION_FITS:
+        raise ValueError(f"{what}: fit must be 'scale' or 'affine', got {fit!r}")
+    min_cond = float(min_cond)
+    if not (min_cond >= 0.0 and np.isfinite(min_cond)):
+        raise ValueError(f"{what}: min_cond must be finite and >= 0")
+    n = rows.shape[1]
+    _check_field_codes(what, rows, row_x, row_y, dimension)
+    k = 2 if row_y >= 0 else 1
+    if points.dtype != torch.float64 or tuple(points.shape) != (n_groups, k) \
+            or not points.is_contiguous() or points.device != rows.device:
+        raise ValueError(f"{what}: points must be contiguous float64 of shape (n_groups, {k}) "
+                         "on the rows' device")
+    if variant not in (0, 1, 2) or (variant == 1 and n_groups > SPOT_LDS_GROUPS):
+        raise ValueError(f"{what}: variant must be 0, 1 (up to {SPOT_LDS_GROUPS} groups) or 2")
+    if qbits is None:
+        qbits = spot_qbits(group.numel())
+    if not 1 <= qbits <= 52 or n >= 1 << (62 - qbits):
+        raise ValueError(f"{what}: qbits must lie in 1 .. 52 with n < 2^(62 - qbits)")
+    grad, err = _column_buffers(what, rows, grad, err, mask, perm)
+    dev = rows.device
+    made = dict(acc=((n_groups, 4), torch.int64), fit_out=((8,), torch.float64),
+                residual=((n_groups, 2), torch.float64))
+    given = dict(acc=acc, fit_out=fit_out, residual=residual)
+    for name, (shape, dtype) in made.items():
+        if given[name] is None:
+            given[name] = torch.empty(shape, dtype=dtype, device=dev)
+        b = given[name]
+        if tuple(b.shape) != shape or b.dtype != dtype or not b.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous {dtype} of shape {shape}")
+    acc, fit_out, residual = given["acc"], given["fit_out"], given["residual"]
+    if not rows.is_cuda:
+        _distortion_error_cpu(rows, row_x, row_y, group, n_groups, points, grid,
+                              DISTORTION_FITS[fit], min_cond, float(oob_weight), mask, perm, grad,
+                              err, acc, fit_out, residual, int(qbits), dimension)
+        return err, grad, acc, fit_out, residual
+    L = _lib.lib()
+    workspace = _column_workspace(
+        what, rows, grad, workspace,
+        lambda: L.tfrt_distortion_error_workspace_bytes(n, n_groups), group, mask, perm, err, acc,
+        fit_out, residual, points)
+    x0, x1, qsx, y0, y1, qsy = grid
+    # (the field-code form covers plain rows: codes below 2 * dimension are rows of the block)
+    check(L.tfrt_distortion_error(
+        _p(rows), rows.stride(0), n, _DT[rows.dtype], 3 if dimension is None else int(dimension),
+        _p(mask), row_x, row_y, _p(group), group.numel(), _p(perm), n_groups, _p(points),
+        DISTORTION_FITS[fit], min_cond, x0, x1, qsx, y0, y1, qsy, int(qbits), float(oob_weight),
+        _p(grad), grad.stride(0), _p(err), _p(fit_out), _p(residual), _p(acc), int(variant),
+        _p(workspace), workspace.numel(), _stream(rows)), "tfrt_distortion_error")
+    return err, grad, acc, fit_out, residual
+
+
+def _distortion_error_cpu(rows, row_x, row_y, group, n_groups, points, grid, fit_kind, min_cond,
+                          oob, mask, perm, grad, err, acc, fit_out, residual, qbits, dimension):
+    """The CPU path of ``distortion_error`` (every torch op rounds on its own, as the kernels
+    do)."""
+    x0, x1, qsx, y0, y1, qsy = grid
+    two = row_y >= 0
+    n = rows.shape[1]
+    qmax = float(np.ldexp(1.0, qbits))
+    x, y, link = _fields_cpu(rows, row_x, row_y, dimension)
+    counting = torch.ones(n, dtype=torch.bool) if mask is None else (mask[:n] >= 0)
+    finite = torch.isfinite(x) & torch.isfinite(y)
+    s = torch.arange(n, dtype=torch.int64) if perm is None else perm[:n].long()
+    s_ok = (s >= 0) & (s < group.numel())
+    label = torch.full((n,), -1, dtype=torch.int64)
+    label[s_ok] = group[s[s_ok]].long()
+    spot = counting & finite & s_ok & (label >= 0) & (label < n_groups)
+    inside, pen, gx, gy = _outside_cpu(x, y, two, grid, oob, spot, None)
+    xi, yi, li = x[inside], y[inside], label[inside]
+    acc.zero_()
+    acc[:, 0].index_add_(0, li, torch.ones_like(li))
+    acc[:, 1].index_add_(0, li, torch.round((xi - x0) * qsx).clamp(0.0, qmax).long())
+    if two:
+        acc[:, 2].index_add_(0, li, torch.round((yi - y0) * qsy).clamp(0.0, qmax).long())
+    fit, res, e_inside = _distortion_fit_cpu(acc, points, grid, two, fit_kind, min_cond)
+    fit_out.copy_(fit)
+    residual.copy_(res)
+    gx[inside] = 2.0 * res[li, 0]
+    if two:
+        gy[inside] = 2.0 * res[li, 1]
+    _write_grad_cpu(grad, n, dimension, row_x, row_y, gx, gy, link, spot)
+    e = e_inside + pen
+    n_terms = float(int(counting.sum()) * (2 if two else 1))
+    err[0], err[1] = e, n_terms
+    err[2] = e / n_terms if n_terms > 0 else float("nan")
+
+
 # ------------------------------------------------------- rays of a group through one point
 FOCUS_MAX_GROUPS = 1 << 20
 FOCUS_LDS_GROUPS = 256             # tfrt_focus_error: ten planes of G int64 in LDS, 20 KiB

@@ -46,6 +46,16 @@ the error is the lens' aberration alone.  Where the focus should lie is a second
 
     python examples/imaging.py --focus [--rays 20000] [--steps 30] [--generic]
 
+``--flat-field`` adds what a sensor asks of ``--focus``: the foci must lie in one plane across the
+axis, wherever along the axis it has to stand --
+``SumError([FocusError, FlatFieldError], reduce="mean")`` over the same labels and box, "a sharp
+image on a flat sensor".  The ``FlatFieldError`` charges every ray the squared distance of its
+object point's focus from the plane that fits the foci best (normal: the x axis; the offset is
+free), so the spread of the foci along the axis -- the field curvature that ``--focus`` only
+reports -- is now lowered.  The run prints that spread before and after, and the plane's offset.
+
+    python examples/imaging.py --flat-field [--flat-weight W] [--rays 20000] [--steps 30] [--generic]
+
 ``--distortion [scale|affine]`` asks for an undistorted image without pinning its scale or place:
 ``SumError([SpotError, DistortionError], reduce="mean")``.  The ``DistortionError`` fits the
 spots' centroids to ``A p + t`` over the object points p -- a free magnification (``scale``) or a
@@ -79,6 +89,7 @@ import tfrt.sources as sources                # noqa: E402
 LEARNING_RATE = 2e-5     # at 20,000 rays
 MEAN_LEARNING_RATE = 0.4  # --magnification: LEARNING_RATE * 20,000 rays * 2 terms per ray, halved
                           # because two terms pull
+FLAT_WEIGHT_CONES = 16.0  # --flat-field: the FlatFieldError's weight in units of sin(cone)^2
 HALF_DOMAIN = 3.0        # the target region: the unfocused cone of a ray bundle has radius ~1.6
 
 
@@ -103,9 +114,17 @@ def gaussian_pupil(sigma, cone):
     return weights
 
 
+def focus_spread(term):
+    """The spread of the foci of ``term``'s last evaluation along its axis: the largest minus the
+    smallest height of a group with a focus."""
+    h = term.heights()
+    h = h[torch.isfinite(h)]
+    return float(h.max() - h.min())
+
+
 def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, target_distance=10.0,
           object_size=0.2, lens_aperature=1.0, apodize=None, magnification=None, focus=False,
-          distortion=None):
+          distortion=None, flat_field=False, flat_weight=None):
     points = letter_f(object_size)
     P = points.shape[0]
     A = max(ray_count // P, 2)
@@ -151,12 +170,24 @@ def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, target_dis
     error_function = optimizer.SpotError(
         ("y_end", "z_end"), labels, ((-HALF_DOMAIN, HALF_DOMAIN), (-HALF_DOMAIN, HALF_DOMAIN)),
         oob_weight=1.0, weights=None if apodize is None else gaussian_pupil(apodize, cone))
-    if focus:
+    flat_term = None
+    if focus or flat_field:
         # the box contains the target plane: every ray that lands in the target region counts
-        error_function = optimizer.FocusError(
-            labels, ((target_distance - 1.0, target_distance + 1.0),
-                     (-HALF_DOMAIN, HALF_DOMAIN), (-HALF_DOMAIN, HALF_DOMAIN)), min_det=1e-9)
+        box = ((target_distance - 1.0, target_distance + 1.0),
+               (-HALF_DOMAIN, HALF_DOMAIN), (-HALF_DOMAIN, HALF_DOMAIN))
+        error_function = optimizer.FocusError(labels, box, min_det=1e-9)
     spot = error_function
+    if flat_field:
+        flat_term = optimizer.FlatFieldError(labels, box, axis=(1.0, 0.0, 0.0), min_det=1e-9)
+        if flat_weight is None:
+            # in units of sin(cone)^2: an axial distance dz blurs the image by dz * sin(cone), and
+            # a focus moves along the axis about 1 / sin(cone) times as far as the rays that make
+            # it move are displaced across -- the term is that much stiffer than the FocusError,
+            # and at weight 1 the example's step size diverges.  16 sin(cone)^2 = 0.078 lowers
+            # the spread of the foci at that step size; 4 and 1 do so more slowly
+            flat_weight = FLAT_WEIGHT_CONES * math.sin(cone) ** 2
+        error_function = optimizer.SumError([spot, flat_term], weights=[1.0, flat_weight],
+                                            reduce="mean")
     if magnification is not None:
         # ray i leaves object point i mod P whatever direction is drawn for it: the image points
         # are a fixed table with one row per source ray
@@ -174,18 +205,20 @@ def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, target_dis
         error_function = optimizer.SumError([spot, distortion_term], reduce="mean")
     return dict(engine=trace_engine, system=system, lens=lens, source=source, n_rays=n_rays,
                 n_points=P, error_function=error_function, spot=spot, accumulator=accumulator,
-                distortion=distortion_term)
+                distortion=distortion_term, flat_field=flat_term)
 
 
 def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=False, verbose=True,
-        learning_rate=None, apodize=None, magnification=None, focus=False, distortion=None):
+        learning_rate=None, apodize=None, magnification=None, focus=False, distortion=None,
+        flat_field=False, flat_weight=None):
     s = build(ray_count, lens_res_scale, apodize=apodize, magnification=magnification, focus=focus,
-              distortion=distortion)
+              distortion=distortion, flat_field=flat_field, flat_weight=flat_weight)
+    focus = focus or flat_field
     combined, erf = s["error_function"], s["spot"]
     if learning_rate is None:
         # (the error is a sum over the rays: the step size goes with 1 / rays)
         learning_rate = LEARNING_RATE * (20000 / s["n_rays"])
-        if magnification is not None or distortion is not None:
+        if magnification is not None or distortion is not None or flat_field:
             # (a mean over two terms per ray: the same step per ray as the sum's)
             learning_rate = MEAN_LEARNING_RATE
     kw = dict(learning_rate=learning_rate, grad_clip=1.0, fused=False if generic else "auto")
@@ -195,8 +228,8 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=Fals
     else:
         opt = optimizer.SGD_Optimizer(s["engine"], s["lens"].parameters, combined, 3, **kw)
     opt.suppress_warnings = True
-    rms, times, errors, place, fits = [], [], [], [], []
-    summed = magnification is not None or distortion is not None
+    rms, times, errors, place, fits, spreads = [], [], [], [], [], []
+    summed = magnification is not None or distortion is not None or flat_field
     for step in range(steps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -217,6 +250,9 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=Fals
             error_sum = float(combined.last_errors[0, 0])
             place.append(float(combined.last_errors[1, 2]))
         rms.append(math.sqrt(error_sum / light) if inside else float("nan"))
+        if flat_field:
+            # (read outside the timed part of the step)
+            spreads.append(focus_spread(s["flat_field"]))
         if verbose and (step % 5 == 0 or step == steps - 1):
             extra = "" if magnification is None else \
                 f"  mean squared image distance {place[-1]:.6g}  combined {mean:.6g}"
@@ -230,11 +266,14 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=Fals
                 extra = (f"  mean squared distortion {place[-1]:.6g}  combined {mean:.6g}  "
                          f"{'magnification' if distortion == 'scale' else 'det A'} {scale:.6g}  "
                          f"largest |r| {worst:.6g}")
+            if flat_field:
+                extra = (f"  mean squared distance to the plane {place[-1]:.6g}  combined "
+                         f"{mean:.6g}  spread of the foci {spreads[-1]:.6g}")
             what = "rms distance to the focus" if focus else "rms spot"
             print(f"step {step:4d}: {what} {rms[-1]:.6g}{extra}  ({inside} rays inside, "
                   f"{1e3 * times[-1]:.2f} ms)")
     fused = opt._fused_step
-    s.update(rms=rms, times=times, errors=errors, place=place, fits=fits,
+    s.update(rms=rms, times=times, errors=errors, place=place, fits=fits, spreads=spreads,
              graph_replays=0 if fused is None else fused.graph_replays,
              centroids=erf.foci() if focus else erf.centroids())
     return s
@@ -255,6 +294,12 @@ if __name__ == "__main__":
                     help="pin the image of (y, z) to (-M y, -M z): SumError([SpotError, GoalError])")
     ap.add_argument("--focus", action="store_true",
                     help="a FocusError in the place of the SpotError: the axial position is free")
+    ap.add_argument("--flat-field", action="store_true",
+                    help="SumError([FocusError, FlatFieldError]): a sharp image on a flat sensor, "
+                         "wherever along the axis it has to stand")
+    ap.add_argument("--flat-weight", type=float, default=None, metavar="W",
+                    help="--flat-field: the weight of the FlatFieldError beside the FocusError "
+                         f"(default {FLAT_WEIGHT_CONES} * sin(cone)^2)")
     ap.add_argument("--distortion", nargs="?", const="scale", default=None,
                     choices=("scale", "affine"),
                     help="SumError([SpotError, DistortionError]): an undistorted image at a free "
@@ -264,16 +309,30 @@ if __name__ == "__main__":
         ap.error("--focus takes neither --apodize nor --magnification")
     if a.distortion is not None and (a.focus or a.magnification is not None):
         ap.error("--distortion takes neither --magnification nor --focus")
+    if a.flat_field and (a.apodize is not None or a.magnification is not None
+                         or a.distortion is not None):
+        ap.error("--flat-field takes neither --apodize nor --magnification nor --distortion")
     out = run(a.rays, a.steps, a.edge, generic=a.generic, adam=a.adam, learning_rate=a.lr,
               apodize=a.apodize, magnification=a.magnification, focus=a.focus,
-              distortion=a.distortion)
+              distortion=a.distortion, flat_field=a.flat_field, flat_weight=a.flat_weight)
     tail = sorted(out["times"][len(out["times"]) // 2:])
     print(f"{out['n_points']} object points, {out['n_rays']} rays; steps replayed from the graph: "
           f"{out['graph_replays']} of {a.steps}; median step of the second half: "
           f"{1e3 * tail[len(tail) // 2]:.3f} ms")
-    if a.focus:
+    if a.flat_field:
+        print(f"spread of the foci along the axis: first {out['spreads'][0]:.6g} last "
+              f"{out['spreads'][-1]:.6g}")
+        plane = out["flat_field"].plane()
+        print(f"plane of the foci: offset {plane['offset']:.6g} along {plane['axis']}, "
+              f"{plane['groups_used']} object points")
+        print(f"mean squared distance to the plane: first {out['place'][0]:.6g} last "
+              f"{out['place'][-1]:.6g}")
+        print(f"combined error: first {out['errors'][0]:.6g} last {out['errors'][-1]:.6g}")
+    if a.focus or a.flat_field:
         # (the mean squared distance of a group's focus from its rays' lines)
-        print(f"focus error: first {out['errors'][0]:.6g} last {out['errors'][-1]:.6g}")
+        first, last = (out["rms"][0] ** 2, out["rms"][-1] ** 2) if a.flat_field else \
+            (out["errors"][0], out["errors"][-1])
+        print(f"focus error: first {first:.6g} last {last:.6g}")
         x = out["centroids"][:, 0]
         x = x[torch.isfinite(x)]
         print(f"foci of {x.numel()} object points: x from {float(x.min()):.6g} to "

@@ -1012,6 +1012,73 @@ int tfrt_distortion_error(const void* rows, int64_t stride, int64_t n, int32_t s
                           double* residual, int64_t* acc, int32_t variant, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* FlatFieldError: the foci of all groups must lie in ONE plane with the unit normal a = `axis` --
+ * wherever along the normal that plane has to stand.  The error is the sum, over the counting rays
+ * of the groups with a focus, of the squared distance of their group's focus from that plane, in
+ * the scene's units.  Four launches (clear `acc`, tfrt_focus_error's accumulate launch, fit, seed),
+ * no host read, no allocation, no float atomics, no finishing launch: captured with the rest of a
+ * step.
+ *
+ * Everything up to a group's focus is exactly tfrt_focus_error's: the columns and which of them
+ * COUNT, the box constants c, R, iR, m = (e - c) * iR, `pbits`, the ten-slot int64 records, a and
+ * b, the cofactors c00 .. c22 and det, "has a focus iff count >= 2 and det >= min_det", and
+ * x = A^-1 b.  Every operation below is an IEEE f64 operation rounded on its own (no contraction);
+ * a sum of products is summed left to right, x first; in 2-D the third component of every vector
+ * is 0.0 and is left out of the sums.
+ *
+ * A group is USED iff it has a focus.  With the same cofactors, y = A^-1 a:
+ *   3-D:  y_0 = (c00*a_0 + c01*a_1 + c02*a_2) / det,  y_1 = (c01*a_0 + c11*a_1 + c12*a_2) / det,
+ *         y_2 = (c02*a_0 + c12*a_1 + c22*a_2) / det;
+ *   2-D:  y_0 = (a11*a_0 - a01*a_1) / det,  y_1 = (a00*a_1 - a01*a_0) / det
+ * (a_0, a_1, a_2 the axis; a00 .. a22 the group's matrix), and
+ *   n = (double) count,  h = a.x.
+ * First pass, over the used groups:
+ *   W = sum n,  S = sum n * h,  the number of used groups,  terms = sum count (an integer);
+ *   hbar = S / W;  the plane is VALID iff at least two groups are used.
+ * Second pass, for a used group under a valid plane:
+ *   r = h - hbar,  s = R * r,  e_g = s * s,  mu_b = (2.0 * s) * y_b   (2-D: mu_2 = 0.0);
+ *   inside = sum n * e_g.
+ * Without a valid plane e_g = 0.0, mu = 0.0 and inside = 0.0.
+ *   error_out = {inside, (double) terms, inside / terms (NaN with terms == 0)}.
+ * The plane is a.p = a.c + R * hbar in the scene's coordinates; hbar is not differentiated, because
+ * it minimises the sum (sum n * r = 0).  The focus IS differentiated: d error / d x_g = 2 R^2 n r a
+ * and d x_g = A_g^-1 (1 / n) sum_i d[P_i (m_i - x_g)], so mu = 2 R r A^-1 a is the group's adjoint
+ * in the scene's units (n cancels).
+ * A counting column of a used group under a valid plane, against x and mu of its group:
+ *   q = m - x,  alpha = u.q,  lever = (R * alpha) / L,  rest = 1.0 - lever,
+ *   beta = mu.u,  k = beta / L,  and per component b:
+ *   rho_b = R * (q_b - alpha * u_b),  muP_b = mu_b - beta * u_b,  turn_b = k * rho_b,
+ *   grad[end_b] = muP_b * rest - turn_b,  grad[start_b] = muP_b * lever + turn_b
+ * -- the lever rule applied to the part of the adjoint across the ray, plus a term from turning the
+ * ray.  Every other column gets 0.0 in all 2d rows.
+ * Every sum over the groups has a fixed shape and order: thread j of the one workgroup of
+ * B = 1,024 threads takes the groups j, j + B, j + 2B, ... in ascending order, starting from 0.0
+ * and skipping unused groups; the threads are combined within each 64-lane wave by
+ * v += v[lane ^ d] for d = 32, 16, 8, 4, 2, 1, then the 16 waves in index order starting from 0.0
+ * (tfrt_distortion_error's convention).  Two runs give the same bits.
+ *
+ *   ax, ay, az      the unit normal: finite, |ax*ax + ay*ay + az*az - 1| <= 8 * 2^-52 (the caller
+ *                   divides its axis by sqrt(axis.axis) once); az is ignored in 2-D
+ *   table           n_groups rows of eight f64, 64-byte aligned: {x_0, x_1, x_2, used (1.0 / 0.0),
+ *                   mu_0, mu_1, mu_2, e_g}; x in NORMALISED coordinates (2-D: x_2 = 0.0);
+ *                   {NaN, NaN, NaN, 0, 0, 0, 0, 0} for an unused group
+ *   fit_out         8 f64 {hbar (NaN without a used group), a.c + R * hbar, W, groups used,
+ *                   valid (1.0 / 0.0), 0, 0, 0}
+ *   acc             n_groups records of ten int64, cleared and filled by this call
+ *   workspace       tfrt_flatfield_error_workspace_bytes(n, n_groups) bytes (0: bad arguments)
+ * Everything else as for tfrt_focus_error.  Bad arguments are refused with TFRT_E_BADARG /
+ * TFRT_E_WORKSPACE before any launch.
+ */
+size_t tfrt_flatfield_error_workspace_bytes(int64_t n, int32_t n_groups);
+int tfrt_flatfield_error(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                         int32_t dimension, const int32_t* mask, const int32_t* group,
+                         int64_t n_source, const int32_t* perm, int32_t n_groups, double x0,
+                         double x1, double y0, double y1, double z0, double z1, int32_t pbits,
+                         double min_det, double ax, double ay, double az, double* grad,
+                         int64_t grad_stride, double* error_out, int64_t* acc, double* table,
+                         double* fit_out, int32_t variant, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 /* GoalError on the fixed-shape columns of an in-place trace (tfrt_scene3d.in_place == 2: the
  * finished rows at the rays' own columns, a mask in the place of a ray count) -- the form that can
  * be added to a coupled error of the same step (tfrt_error_combine).  Two launches (the columns,

@@ -21,8 +21,9 @@
 // Five launches:
 //
 //   k_error_clear      zeroes the records (error_sums.h says why it is a launch).
-//   k_focus_accumulate one lane per column (a fixed grid for n, grid-stride): the ten slots of
-//                      focus_record -> the record of the ray's group.  Two variants:
+//   k_focus_accumulate focus_records.h (tfrt_flatfield.hip fills the same records): one lane per
+//                      column (a fixed grid for n, grid-stride): the ten slots of focus_record ->
+//                      the record of the ray's group.  Two variants:
 //                      <true>  G <= FOCUS_LDS_GROUPS: a per-workgroup table in LDS (ds_add_u64),
 //                              ten planes of G int64 (80 B x 256 = 20 KiB, inside the 24 KiB that
 //                              tfrt_spot.hip argues for), flushed with one global atomic per
@@ -39,81 +40,13 @@
 #include "direction_fields.h"
 #include "error_sums.h"
 #include "focus_math.h"
+#include "focus_records.h"
 
 namespace tfrt {
 
-constexpr int FOCUS_LDS_GROUPS = 256;       // 10 planes of int64: 20 KiB per workgroup
-constexpr int FOCUS_MAX_GROUPS = 1 << 20;
-constexpr int FOCUS_MAX_GRID = 512;         // workgroups of the accumulate launch
-constexpr int FOCUS_RAYS_PER_BLOCK = 4 * BLOCK;
 constexpr int FOCUS_SEED_MAX_GRID = 2048;   // workgroups of the seed launch
 constexpr int FOCUS_FINISH_BLOCK = 1024;
 constexpr int FOCUS_FINISH_WAVES = FOCUS_FINISH_BLOCK / 64;
-
-struct FocusArgs {
-  FocusBox box;
-  double one;          // 2^pbits
-  int64_t n_source;
-  int32_t n_groups;
-};
-
-// Does column i count, and for which group?  Returns the label, or -1.  `link` is set whenever
-// the mask lets the column through.
-template <typename T, int DIM>
-__device__ __forceinline__ int focus_classify(const T* __restrict__ rows, int64_t stride,
-                                              const int32_t* __restrict__ mask,
-                                              const int32_t* __restrict__ group,
-                                              const int32_t* __restrict__ perm, int64_t i,
-                                              const FocusArgs& g, LinkDir<DIM>& link) {
-  if (mask != nullptr && mask[i] < 0) return -1;
-  link = link_direction<T, DIM>(rows, stride, i);
-  if (!link.ok) return -1;
-  // (nothing is read out of bounds, whatever perm and group hold)
-  const int64_t s = perm != nullptr ? (int64_t)perm[i] : i;
-  if (s < 0 || s >= g.n_source) return -1;
-  const int label = group[s];
-  if (label < 0 || label >= g.n_groups) return -1;
-  return focus_inside<DIM>(link.e, g.box) ? label : -1;
-}
-
-template <typename T, bool LDS, int DIM>
-__global__ __launch_bounds__(BLOCK) void k_focus_accumulate(
-    const T* __restrict__ rows, int64_t stride, int64_t n, const int32_t* __restrict__ mask,
-    const int32_t* __restrict__ group, const int32_t* __restrict__ perm, FocusArgs g,
-    unsigned long long* __restrict__ acc) {
-#pragma clang fp contract(off)
-  extern __shared__ unsigned long long table[];   // LDS variant: FOCUS_SLOTS planes of G each
-  const int G = g.n_groups;
-  if (LDS) {
-    for (int e = threadIdx.x; e < FOCUS_SLOTS * G; e += BLOCK) table[e] = 0ull;
-    __syncthreads();
-  }
-  for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * BLOCK) {
-    LinkDir<DIM> link;
-    const int label = focus_classify<T, DIM>(rows, stride, mask, group, perm, i, g, link);
-    if (label < 0) continue;
-    double m[DIM];
-    int64_t q[FOCUS_SLOTS];
-    focus_normalise<DIM>(link.e, g.box, m);
-    focus_record<DIM>(link.d, m, g.one, q);
-#pragma unroll
-    for (int p = 0; p < FOCUS_SLOTS; ++p) {
-      if (DIM == 2 && (p == 3 || p == 5 || p == 6 || p == 9)) continue;   // the z slots stay 0
-      unsigned long long* at =
-          LDS ? table + (p * G + label) : acc + (FOCUS_SLOTS * (int64_t)label + p);
-      atomicAdd(at, (unsigned long long)q[p]);
-    }
-  }
-  if (LDS) {
-    __syncthreads();
-    for (int e = threadIdx.x; e < FOCUS_SLOTS * G; e += BLOCK) {
-      const unsigned long long v = table[e];
-      const int plane = e / G, label = e - plane * G;
-      if (v != 0ull) atomicAdd(acc + (FOCUS_SLOTS * (int64_t)label + plane), v);
-    }
-  }
-}
 
 template <int DIM>
 __global__ __launch_bounds__(BLOCK) void k_focus_solve(const long long* __restrict__ acc, int G,
@@ -218,32 +151,13 @@ int tfrt_focus_error(const void* rows, int64_t stride, int64_t n, int32_t state_
                      double* grad, int64_t grad_stride, double* error_out, int64_t* acc,
                      double* foci, int32_t variant, void* workspace, size_t workspace_bytes,
                      void* stream) {
-  if (dimension < 2 || dimension > 3 || n < 0 || n > INT32_MAX || n_source < 0 ||
-      n_source > INT32_MAX || n_groups < 1 || n_groups > FOCUS_MAX_GROUPS || !group ||
-      !error_out || !acc || !foci || !workspace || variant < 0 || variant > 2 || pbits < 1 ||
-      pbits > FOCUS_MAX_PBITS || !state_dtype_ok(state_dtype))
-    return TFRT_E_BADARG;
-  if (n >= ((int64_t)1 << (61 - pbits))) return TFRT_E_BADARG;   // n * 2 * 2^pbits stays below 2^62
-  if (!(min_det > 0.0) || !isfinite(min_det)) return TFRT_E_BADARG;
-  if (n > 0 && (!rows || !grad || stride < n || grad_stride < n)) return TFRT_E_BADARG;
   const double domain[6] = {x0, x1, y0, y1, z0, z1};
   FocusArgs g;
-  double half = 0.0;
-  for (int a = 0; a < 3; ++a) {
-    const bool used = a < dimension;
-    g.box.lo[a] = used ? domain[2 * a] : 0.0;
-    g.box.hi[a] = used ? domain[2 * a + 1] : 0.0;
-    if (used && (!isfinite(g.box.lo[a]) || !isfinite(g.box.hi[a]) || !(g.box.hi[a] > g.box.lo[a])))
-      return TFRT_E_BADARG;
-    g.box.c[a] = 0.5 * (g.box.lo[a] + g.box.hi[a]);
-    half = fmax(half, 0.5 * (g.box.hi[a] - g.box.lo[a]));
-  }
-  g.box.R = half, g.box.iR = 1.0 / half;
-  if (!isfinite(g.box.iR) || !isfinite(half)) return TFRT_E_BADARG;
-  if (variant == 1 && n_groups > FOCUS_LDS_GROUPS) return TFRT_E_BADARG;
+  if (focus_args(rows, stride, n, state_dtype, dimension, group, n_source, n_groups, domain, pbits,
+                 min_det, grad, grad_stride, error_out, acc, foci, variant, workspace, g) != 0)
+    return TFRT_E_BADARG;
   if (workspace_bytes < tfrt_focus_error_workspace_bytes(n, n_groups)) return TFRT_E_WORKSPACE;
   const bool lds = variant == 1 || (variant == 0 && n_groups <= FOCUS_LDS_GROUPS);
-  g.one = ldexp(1.0, pbits), g.n_source = n_source, g.n_groups = n_groups;
   const double inv = ldexp(1.0, -pbits);
 
   char* ws = static_cast<char*>(workspace);
@@ -253,25 +167,13 @@ int tfrt_focus_error(const void* rows, int64_t stride, int64_t n, int32_t state_
   unsigned long long* accu = reinterpret_cast<unsigned long long*>(acc);
   const long long* accs = reinterpret_cast<const long long*>(acc);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int grid = error_grid(n, FOCUS_RAYS_PER_BLOCK, FOCUS_MAX_GRID);
   const int sgrid = error_grid(n, BLOCK, FOCUS_SEED_MAX_GRID);
-  const int entries = FOCUS_SLOTS * n_groups;
 
-  hipLaunchKernelGGL(k_error_clear<>, dim3(cdiv(entries, BLOCK)), dim3(BLOCK), 0, st, accu,
-                     entries);
   auto launch = [&](auto tag, auto d) {
     using T = typename decltype(tag)::type;
     constexpr int DIM = decltype(d)::value;
     const T* r = static_cast<const T*>(rows);
-    if (grid > 0) {
-      if (lds)
-        hipLaunchKernelGGL((k_focus_accumulate<T, true, DIM>), dim3(grid), dim3(BLOCK),
-                           (size_t)entries * sizeof(unsigned long long), st, r, stride, n, mask,
-                           group, perm, g, accu);
-      else
-        hipLaunchKernelGGL((k_focus_accumulate<T, false, DIM>), dim3(grid), dim3(BLOCK), 0, st, r,
-                           stride, n, mask, group, perm, g, accu);
-    }
+    focus_fill_records<T, DIM>(r, stride, n, mask, group, perm, g, lds, accu, st);
     hipLaunchKernelGGL((k_focus_solve<DIM>), dim3(cdiv(n_groups, BLOCK)), dim3(BLOCK), 0, st, accs,
                        n_groups, inv, min_det, foci);
     if (sgrid > 0)

@@ -15,7 +15,9 @@ one group must meet in one point -- ``tfrt_spot_error`` (clear, accumulate, seed
 finish); a ``FocusError`` -- rays of one group, taken as lines, must pass through one point of
 space -- ``tfrt_focus_error`` (clear, accumulate, solve, seed, finish); a ``DistortionError`` --
 the groups' centroids must be a scaled or affine copy of the object points --
-``tfrt_distortion_error`` (clear, SpotError's accumulate, fit, seed).  A ``SumError`` is a
+``tfrt_distortion_error`` (clear, SpotError's accumulate, fit, seed); a ``FlatFieldError`` -- the
+foci of all groups must lie in one plane with a given normal -- ``tfrt_flatfield_error`` (clear,
+FocusError's accumulate, fit, seed).  A ``SumError`` is a
 weighted sum of such terms and of ``GoalError``s: every term's launches into a seed block of its
 own (a ``GoalError`` through ``tfrt_goal_error_columns``), then ONE ``tfrt_error_combine`` for the
 step's seed block and error.
@@ -24,7 +26,8 @@ Each is an ordinary error function (``__call__(engine)``): the generic path give
 numbers, which is what the parity tests compare.
 
 The protocol between a built-in term (``GoalError``, ``DensityError``, ``SpotError``,
-``TransportError``, ``FocusError``, ``DistortionError``) and the fused 3-D step:
+``TransportError``, ``FocusError``, ``DistortionError``, ``FlatFieldError``) and the fused 3-D
+step:
 
 * ``rows``, ``fields``, ``rows_for(dimension)``: the rows of the ray block (the field codes) the
   term reads;
@@ -1148,10 +1151,11 @@ class FocusError(_CoupledError):
     has_direction = True          # (every geometry row is read and seeded)
 
     def __init__(self, groups, domain, n_groups=None, min_det=1e-12):
+        what = type(self).__name__
         try:
             self.grid = ops.focus_grid(domain)
         except ValueError as e:
-            raise ValueError(f"FocusError: domain must be ((x0, x1), (y0, y1), (z0, z1)) -- "
+            raise ValueError(f"{what}: domain must be ((x0, x1), (y0, y1), (z0, z1)) -- "
                              f"((x0, x1), (y0, y1)) on a 2-D engine --, finite with lo < hi; got "
                              f"{domain!r}") from e
         self.domain = tuple((float(d[0]), float(d[1])) for d in domain)
@@ -1161,26 +1165,26 @@ class FocusError(_CoupledError):
         try:
             self.min_det = float(min_det)
         except (TypeError, ValueError) as e:
-            raise ValueError(f"FocusError: min_det must be a number, got {min_det!r}") from e
+            raise ValueError(f"{what}: min_det must be a number, got {min_det!r}") from e
         if not (self.min_det > 0.0 and np.isfinite(self.min_det)):
-            raise ValueError(f"FocusError: min_det must be finite and > 0, got {min_det!r}")
-        _init_groups(self, "FocusError", groups, n_groups, ops.FOCUS_MAX_GROUPS)
+            raise ValueError(f"{what}: min_det must be finite and > 0, got {min_det!r}")
+        _init_groups(self, what, groups, n_groups, ops.FOCUS_MAX_GROUPS)
         self.last_acc = None
         self.last_foci = None
 
     def labels_of(self, src):
         """The int32 label buffer of the source set ``src`` on its device, one label per source
         ray, given or computed and cached as ``SpotError.labels_of`` does."""
+        what = type(self).__name__
         return _source_buffer(self, "labels", self.groups,
-                              lambda v, dev: _as_labels("FocusError", v, dev), src, "FocusError",
-                              "label")
+                              lambda v, dev: _as_labels(what, v, dev), src, what, "label")
 
     def rows_for(self, dimension):
         """All ``2 * dimension`` rows of the geometry block; the box must have the engine's
         dimension."""
         if dimension != self.dimension:
-            raise ValueError(f"FocusError: a {dimension}-D engine needs a domain of {dimension} "
-                             f"axes, got {self.domain!r}")
+            raise ValueError(f"{type(self).__name__}: a {dimension}-D engine needs a domain of "
+                             f"{dimension} axes, got {self.domain!r}")
         return self.rows
 
     def graph_key(self):
@@ -1216,7 +1220,7 @@ class FocusError(_CoupledError):
         """(G, d) float64 foci of the last evaluation in scene coordinates, NaN for a group
         without a focus."""
         if self.last_foci is None:
-            raise RuntimeError("FocusError: no evaluation yet")
+            raise RuntimeError(f"{type(self).__name__}: no evaluation yet")
         return ops.focus_points(self.last_foci, self.grid, self.dimension)
 
     def __call__(self, engine):
@@ -1483,8 +1487,164 @@ class _DistortionTerms(torch.autograd.Function):
         return (upstream[:, 0] * grad).to(ctx.dtype), None, None, None, None, None
 
 
+class FlatFieldError(FocusError):
+    """The foci of all groups must lie in ONE plane with the normal ``axis`` -- a flat field --,
+    wherever along the normal that plane has to stand: the sum, over the finished rays that count,
+    of the squared distance of their group's focus from the plane, in the scene's units.  A
+    ``FocusError`` frees the axial position of every object point's focus, so field curvature is
+    no longer charged to the lens; a sensor is flat, and this is the term that says so:
+    ``SumError([FocusError, FlatFieldError])`` is "a sharp image on a flat sensor, wherever along
+    the axis it has to stand".
+
+    ``groups``, ``domain``, ``n_groups``, ``min_det``: a ``FocusError``'s, and everything up to a
+    group's focus ``x = A^-1 b`` is that class's, bit for bit -- which rays count, the box
+    constants, the int64 records, the cofactor solve, "a focus needs two rays and
+    ``det(A / count) >= min_det``".  ``axis``: ``dimension`` finite numbers, not all zero, default
+    ``(1, 0, 0)`` (``(1, 0)`` with a 2-D domain); ``a = axis / sqrt(axis . axis)`` is formed once.
+
+    Float64, every operation rounded on its own (include/tfrt_hip.h, tfrt_flatfield_error):
+
+    * a group with a focus is USED: ``n = count``, ``h = a . x``, and by the same cofactors
+      ``y = A^-1 a``;
+    * ``W = sum n``, ``hbar = (sum n * h) / W`` over the used groups; the plane
+      ``a . p = a . c + R * hbar`` is VALID with at least two used groups;
+    * ``r = h - hbar``, ``e_g = (R * r) * (R * r)``, ``error = {sum n * e_g, number of counting
+      rays in used groups, sum / number}``; without a valid plane the sum is 0.0 and every
+      gradient zero;
+    * the height ``hbar`` is not differentiated, because it minimises the sum; the FOCUS is: the
+      group's adjoint is ``mu = (2 * (R * r)) * y``, and a counting ray of a used group, with
+      ``focus_term``'s ``q``, ``alpha``, ``rho`` and ``lever`` and ``beta = mu . u``,
+      ``muP = mu - beta * u``, ``k = beta / L``, gets ``muP * (1 - lever) - k * rho`` on the end
+      rows and ``muP * lever + k * rho`` on the start rows -- the lever rule applied to the part
+      of the adjoint across the ray, plus a term from turning the ray;
+    * every float sum over the groups has a fixed shape and order: two runs give the same bits.
+
+    It is an ordinary ``error_function(engine)`` (the generic path: ``ops.flatfield_error`` over
+    the finished rays' geometry block under a ``torch.autograd.Function`` that returns the
+    (n_finished, 1) terms ``e_g`` of every ray's group), which serves the cases a ``FocusError``'s
+    generic path serves.  Its ``backward`` returns ``upstream * gradient``: exact when ``upstream``
+    is ONE constant (the optimiser passes ones), because the plane couples the groups.  On a 3-D
+    engine that traces its source in place the optimiser runs it on the fused, graph-replayed
+    step wherever a ``FocusError`` runs there (``tfrt_flatfield_error``: clear, accumulate, fit,
+    seed), and it is a legal term of a ``SumError``.
+
+    ``last_acc`` is the (G, 10) int64 record table of the last evaluation; ``foci()`` the (G, d)
+    foci in scene coordinates, ``heights()`` the (G,) ``a . focus``, ``residuals()`` the (G,)
+    ``R * r`` (NaN for an unused group, zeros without a plane), ``plane()`` the plane."""
+
+    def __init__(self, groups, domain, axis=None, n_groups=None, min_det=1e-12):
+        super().__init__(groups, domain, n_groups=n_groups, min_det=min_det)
+        d = self.dimension
+        if axis is None:
+            axis = (1.0, 0.0, 0.0)[:d]
+        try:
+            self.unit_axis = ops.flatfield_axis(axis, d)
+        except ValueError as e:
+            raise ValueError(f"FlatFieldError: axis must be {d} finite numbers, not all zero (the "
+                             f"domain has {d} axes); got {axis!r}") from e
+        self.axis = tuple(float(v) for v in axis)
+        self.last_table = None
+        self.last_fit = None
+
+    def graph_key(self):
+        """A ``FocusError``'s, and the axis."""
+        return super().graph_key() + (self.unit_axis,)
+
+    def evaluate(self, rows, labels, mask=None, perm=None, **buffers):
+        """``ops.flatfield_error`` of the geometry block ``rows`` with these labels, box, axis
+        and ``min_det``."""
+        out = ops.flatfield_error(rows, labels, self.n_groups, self.grid, self.axis, self.min_det,
+                                  mask=mask, perm=perm, dimension=self.dimension,
+                                  variant=self.splat_variant, **buffers)
+        self.last_acc, self.last_table, self.last_fit = out[2], out[3], out[4]
+        self.last_foci = out[3]               # (``foci()`` reads the first d entries of a row)
+        return out
+
+    def seed_columns(self, cols, hold):
+        """tfrt_flatfield_error on the step's columns, as ``FocusError.seed_columns``: the
+        records go into ``hold.buffers["acc"]``, (G, 10), the groups' table into
+        ``hold.buffers["table"]``, (G, 8), the plane into ``hold.buffers["fit_out"]``."""
+        self.rows_for(3)
+        labels = self.labels_of(cols.src)
+        G = self.n_groups
+        dev = cols.rows.device
+        held = self._held(hold, "acc", (G, ops.FOCUS_SLOTS), torch.int64, dev,
+                          lambda: _lib.lib().tfrt_flatfield_error_workspace_bytes(cols.n, G))
+        if "table" not in held:
+            held["table"] = torch.zeros((G, ops.FLATFIELD_ROW), dtype=torch.float64, device=dev)
+            held["fit_out"] = torch.zeros(8, dtype=torch.float64, device=dev)
+        self.evaluate(cols.rows, labels, mask=cols.mask, perm=cols.perm, grad=hold.g_fin,
+                      err=hold.err, **held)
+
+    def _last(self, name):
+        v = getattr(self, name)
+        if v is None:
+            raise RuntimeError("FlatFieldError: no evaluation yet")
+        return v
+
+    def heights(self):
+        """(G,) float64 ``a . focus`` of the last evaluation in scene coordinates, NaN for a group
+        without a focus."""
+        f = self.foci()
+        a = self.unit_axis
+        h = a[0] * f[:, 0] + a[1] * f[:, 1]
+        return h + a[2] * f[:, 2] if self.dimension == 3 else h
+
+    def residuals(self):
+        """(G,) float64 signed distances ``R * r`` of the foci from the plane in the scene's
+        units: NaN for an unused group, zeros without a valid plane."""
+        t, fit = self._last("last_table"), self._last("last_fit")
+        a = self.unit_axis
+        h = a[0] * t[:, 0] + a[1] * t[:, 1]
+        if self.dimension == 3:
+            h = h + a[2] * t[:, 2]
+        r = torch.where(fit[4] != 0.0, self.grid[9] * (h - fit[0]), torch.zeros_like(h))
+        return torch.where(t[:, 3] != 0.0, r, torch.full_like(r, float("nan")))
+
+    def plane(self):
+        """The plane of the last evaluation: ``axis`` (the unit normal, d floats), ``offset``
+        (``axis . p = offset`` in scene coordinates; NaN without a used group), ``valid`` (at
+        least two groups had a focus) and ``groups_used``."""
+        fit = self._last("last_fit").cpu()
+        return dict(axis=self.unit_axis[:self.dimension], offset=float(fit[1]),
+                    valid=bool(fit[4] != 0.0), groups_used=int(fit[3]))
+
+    def __call__(self, engine):
+        """The (n_finished, 1) error terms through the generic path; the gradient rows come back
+        in ``backward``."""
+        self.rows_for(engine.dimension)
+        fin = engine.finished_rays
+        if not bool(fin):
+            return torch.zeros((0, 1), dtype=torch.float64)
+        labels = self.labels_of(engine._trace_src)
+        ids = engine.last_trace["finished_id"].to(torch.int32).contiguous()
+        block = torch.stack([fin[f] for f in self.fields], dim=0)
+        return _FlatFieldTerms.apply(block, self, labels, ids)
+
+
+class _FlatFieldTerms(torch.autograd.Function):
+    """FlatFieldError over the (2 * dimension, n) geometry block of the finished rays, no mask;
+    ``ids``: the source ray of every column.  Returns the (n, 1) terms, ``e_g`` of every counting
+    ray's used group (``ops.flatfield_terms``).  ``backward`` is ``upstream * gradient``: exact
+    when ``upstream`` is one constant, because the plane couples the groups."""
+
+    @staticmethod
+    def forward(ctx, block, erf, labels, ids):
+        rows = block.detach().contiguous()
+        _, grad, _, table, _ = erf.evaluate(rows, labels, perm=ids)
+        ctx.save_for_backward(grad)
+        ctx.dtype = block.dtype
+        return ops.flatfield_terms(rows, labels, erf.n_groups, erf.grid, table, perm=ids,
+                                   dimension=erf.dimension)[:, None].contiguous()
+
+    @staticmethod
+    def backward(ctx, upstream):
+        grad, = ctx.saved_tensors
+        return (upstream[:, 0] * grad).to(ctx.dtype), None, None, None
+
+
 # the coupled errors: all finished rays of a step enter one evaluation (one process)
-_COUPLED = (DensityError, SpotError, TransportError, FocusError, DistortionError)
+_COUPLED = (DensityError, SpotError, TransportError, FocusError, DistortionError, FlatFieldError)
 
 
 class SumError:
@@ -1495,8 +1655,8 @@ class SumError:
     step is one trace, K error evaluations, one combination and one reverse sweep.
 
     ``terms``: 1 to 8 distinct instances of ``GoalError``, ``DensityError``, ``SpotError``,
-    ``TransportError``, ``FocusError`` or ``DistortionError``; a ``RowwiseError``, a nested ``SumError`` or the same
-    object twice is a ValueError.  ``weights``: K finite values >= 0, default all ones, kept as the (K,) float64
+    ``TransportError``, ``FocusError``, ``DistortionError`` or ``FlatFieldError``; a
+    ``RowwiseError``, a nested ``SumError`` or the same object twice is a ValueError.  ``weights``: K finite values >= 0, default all ones, kept as the (K,) float64
     device tensor ``weights``; ``set_weights(values)`` validates on the host and overwrites that
     buffer in place, so a replayed graph sees the new values without a re-capture (as
     ``TransportError.set_goal``).  A weight of 0 switches a term off for a phase; the term is
@@ -1508,7 +1668,8 @@ class SumError:
 
     After an evaluation ``last_errors`` is the (K, 3) tensor of the terms' own triples {sum, terms,
     mean} and ``last_coefficients`` the (K,) ``c_k``; each term keeps its own ``last_hq`` /
-    ``centroids()`` / ``last_rank2`` / ``foci()`` / ``fit_parameters()`` as when it runs alone.
+    ``centroids()`` / ``last_rank2`` / ``foci()`` / ``fit_parameters()`` / ``plane()`` as when it
+    runs alone.
 
     It is an ordinary ``error_function(engine)`` -- the generic path returns the (1,) tensor
     ``sum_k c_k * term_k(engine).sum()`` (``terms_k = numel``) under torch autograd, which serves
@@ -1538,7 +1699,8 @@ class SumError:
                                  "code of its own); state it as a GoalError")
             if not isinstance(t, (GoalError,) + _COUPLED):
                 raise ValueError("SumError: terms must be GoalError, DensityError, SpotError, "
-                                 "TransportError, FocusError or DistortionError instances, got "
+                                 "TransportError, FocusError, DistortionError or FlatFieldError "
+                                 "instances, got "
                                  f"{type(t).__name__}")
         if len(set(id(t) for t in terms)) != len(terms):
             raise ValueError("SumError: the same term object is listed twice (a term keeps the "

@@ -2419,9 +2419,24 @@ def _focus_error_cpu(rows, groups, n_groups, grid, min_det, mask, perm, d, grad,
                      pbits):
     """The CPU path of ``focus_error`` (every torch op rounds on its own, as the kernels do)."""
     n = rows.shape[1]
-    one = float(np.ldexp(1.0, pbits))
     counts, label, u, m, L = _focus_columns(rows, groups, n_groups, grid, mask, perm, d)
-    # the records: P = I - u u^T and t = m - (u . m) u as integers
+    _focus_records_cpu(acc, counts, label, u, m, pbits, d)
+    foci.copy_(_focus_solve(acc, pbits, min_det, d))
+    has, term, gs, ge = _focus_terms(counts, label, u, m, L, foci, grid[9])
+    zero = torch.zeros((), dtype=torch.float64)
+    for b in range(d):
+        grad[b, :n] = torch.where(has, gs[b], zero)
+        grad[d + b, :n] = torch.where(has, ge[b], zero)
+    n_terms = int(has.sum())
+    e = term[has].sum()
+    err[0], err[1] = e, float(n_terms)
+    err[2] = e / n_terms if n_terms > 0 else float("nan")
+
+
+def _focus_records_cpu(acc, counts, label, u, m, pbits, d):
+    """The (G, 10) records of the counting columns into ``acc``: P = I - u u^T and
+    t = m - (u . m) u as integers."""
+    one = float(np.ldexp(1.0, pbits))
     w = _dot_rows(u, m)
     pairs = {1: (0, 0), 2: (0, 1), 3: (0, 2), 4: (1, 1), 5: (1, 2), 6: (2, 2)}
     li = label[counts]
@@ -2436,16 +2451,217 @@ def _focus_error_cpu(rows, groups, n_groups, grid, min_det, mask, perm, d, grad,
         else:
             v = m[p - 7] - w * u[p - 7]
         acc[:, p].index_add_(0, li, torch.round(v[counts] * one).long())
-    foci.copy_(_focus_solve(acc, pbits, min_det, d))
-    has, term, gs, ge = _focus_terms(counts, label, u, m, L, foci, grid[9])
+
+
+# ------------------------------------------------------- the foci of all groups in one plane
+FLATFIELD_ROW = 8                  # {x0, x1, x2, used, mu0, mu1, mu2, e_g}: one 64-byte line
+FLATFIELD_BLOCK = DISTORTION_BLOCK  # k_flatfield_fit: one workgroup of 16 waves
+
+
+def flatfield_axis(axis, dimension=3):
+    """The unit normal of tfrt_flatfield_error from ``axis``, ``dimension`` numbers that are finite
+    and not all zero: ``axis / sqrt(axis . axis)`` in float64, the products summed left to right,
+    formed once here; a tuple of three floats (2-D: the third is 0.0)."""
+    d = int(dimension)
+    try:
+        a = [np.float64(v) for v in axis]
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"flatfield_axis: axis must be {d} numbers, got {axis!r}") from e
+    if len(a) != d or not all(np.isfinite(v) for v in a) or not any(v != 0.0 for v in a):
+        raise ValueError(f"flatfield_axis: axis must be {d} finite numbers, not all zero; got "
+                         f"{axis!r}")
+    s = a[0] * a[0] + a[1] * a[1]
+    if d == 3:
+        s = s + a[2] * a[2]
+    r = np.sqrt(s)
+    if not (np.isfinite(r) and r > 0.0):
+        raise ValueError(f"flatfield_axis: the length of {axis!r} is not a finite number > 0")
+    return tuple(float(v / r) for v in a) + (0.0,) * (3 - d)
+
+
+def _flatfield_fit(acc, pbits, min_det, d, a, grid):
+    """(table (G, 8), fit_out (8,), inside error, number of terms) of a (G, 10) record table on
+    the CPU: flatfield_math.h and k_flatfield_fit, operation by operation, over all groups at once,
+    the sums over the groups in the kernel's shape and order (``distortion_group_sum``)."""
+    G = acc.shape[0]
+    R = grid[9]
+    foci = _focus_solve(acc, pbits, min_det, d)
+    used = foci[:, 3] != 0.0
+    x = foci[:, :3]
+    # y = A^-1 a by the cofactors of _focus_solve
+    inv = float(np.ldexp(1.0, -int(pbits)))
+    n = acc[:, 0].double()
+    a00, a01, a02, a11, a12, a22 = ((acc[:, p].double() * inv) / n for p in (1, 2, 3, 4, 5, 6))
+    if d == 2:
+        det = a00 * a11 - a01 * a01
+        ys = [(a11 * a[0] - a01 * a[1]) / det, (a00 * a[1] - a01 * a[0]) / det]
+        h = a[0] * x[:, 0] + a[1] * x[:, 1]
+    else:
+        c00 = a11 * a22 - a12 * a12
+        c01 = a02 * a12 - a01 * a22
+        c02 = a01 * a12 - a02 * a11
+        c11 = a00 * a22 - a02 * a02
+        c12 = a01 * a02 - a00 * a12
+        c22 = a00 * a11 - a01 * a01
+        det = a00 * c00 + a01 * c01 + a02 * c02
+        ys = [(c00 * a[0] + c01 * a[1] + c02 * a[2]) / det,
+              (c01 * a[0] + c11 * a[1] + c12 * a[2]) / det,
+              (c02 * a[0] + c12 * a[1] + c22 * a[2]) / det]
+        h = a[0] * x[:, 0] + a[1] * x[:, 1] + a[2] * x[:, 2]
+    gsum = lambda v: distortion_group_sum(v, used)          # noqa: E731
+    W, S = gsum(n), gsum(n * h)
+    n_used = int(used.sum())
+    terms = int(acc[used, 0].sum())
+    hbar = S / W
+    valid = n_used >= 2
+    table = torch.zeros((G, FLATFIELD_ROW), dtype=torch.float64)
+    table[:, :3] = x                                        # (NaN without a focus)
+    table[:, 3] = used.double()
+    inside = torch.zeros((), dtype=torch.float64)
+    if valid:
+        zero = torch.zeros((), dtype=torch.float64)
+        s = R * (h - hbar)
+        two = 2.0 * s
+        e = s * s
+        for b, y in enumerate(ys):
+            table[:, 4 + b] = torch.where(used, two * y, zero)
+        table[:, 7] = torch.where(used, e, zero)
+        inside = gsum(n * e)
+    c = grid[6:9]
+    ac = a[0] * c[0] + a[1] * c[1]
+    if d == 3:
+        ac = ac + a[2] * c[2]
+    fit = torch.zeros(8, dtype=torch.float64)
+    fit[0], fit[1], fit[2] = hbar, ac + R * float(hbar), W
+    fit[3], fit[4] = float(n_used), float(valid)
+    return table, fit, inside, terms
+
+
+def _flatfield_rays(counts, label, u, m, L, table, R, valid):
+    """(has, g_start, g_end) of the columns against the table: flatfield_math.h's flatfield_ray;
+    ``has``: the column counts, its group is used and the plane is valid (the others hold
+    garbage)."""
+    d = u.shape[0]
+    f = table[label]
+    has = counts & (f[:, 3] != 0.0) & valid
+    q = m - f[:, :d].t()
+    alpha = _dot_rows(u, q)
+    lever = (R * alpha) / L
+    rest = 1.0 - lever
+    mu = f[:, 4:4 + d].t()
+    beta = _dot_rows(mu, u)
+    k = beta / L
+    rho = R * (q - alpha * u)
+    muP = mu - beta * u
+    turn = k * rho
+    return has, muP * lever + turn, muP * rest - turn
+
+
+def flatfield_terms(rows, group, n_groups, grid, table, mask=None, perm=None, dimension=3):
+    """The (n,) float64 terms of a tfrt_flatfield_error evaluation from its ``table``, as torch
+    ops on the block's device: ``e_g`` of the ray's own group -- the squared distance of the
+    group's focus from the plane -- for a counting ray of a used group, 0 for every other ray."""
+    counts, label, _, _, _ = _focus_columns(rows, group, int(n_groups), grid, mask, perm,
+                                            dimension)
+    f = table[label]
+    return torch.where(counts & (f[:, 3] != 0.0), f[:, 7], torch.zeros_like(f[:, 7]))
+
+
+def flatfield_error(rows, groups, n_groups, grid, axis, min_det, mask=None, perm=None,
+                    dimension=3, variant=0, grad=None, err=None, acc=None, table=None,
+                    fit_out=None, workspace=None):
+    """tfrt_flatfield_error: the FlatFieldError of the columns of the (2 * dimension, n) geometry
+    block ``rows`` -- the foci of all groups (``focus_error``'s, from the same records) must lie
+    in one plane with the normal ``axis``, wherever along the normal it has to stand.  ``rows``,
+    ``groups``, ``perm``, ``n_groups``, ``grid`` (``focus_grid``), ``min_det``, ``mask`` and
+    ``variant`` are ``focus_error``'s; ``axis``: ``dimension`` finite numbers, not all zero,
+    normalised once here (``flatfield_axis``).  Returns (err {sum, terms, mean}, grad
+    (2 * dimension, n) float64 -- every row written for every column --, acc (G, 10) int64, table
+    (G, 8) float64 {x0, x1, x2, used, mu0, mu1, mu2, e_g} -- the focus in normalised coordinates
+    (``focus_points`` gives the scene's), NaN and zeros for a group without a focus; mu and e_g 0
+    without a valid plane --, fit_out (8,) float64 {hbar, a . c + R * hbar, W, groups used, valid,
+    0, 0, 0}).  ``grad``, ``err``, ``acc``, ``table``, ``fit_out``, ``workspace`` (uint8): buffers
+    to reuse -- with all six given a CUDA call allocates nothing.
+
+    CUDA tensors run the kernels.  CPU tensors run a torch restatement with the same int64 fixed
+    point, the same operations and the same order of the sums over the groups: ``acc``, ``table``,
+    ``fit_out``, the gradient and the error agree bit for bit."""
+    what = "flatfield_error"
+    n_groups = int(n_groups)
+    if groups.dtype != torch.int32 or groups.dim() != 1 or not groups.is_contiguous():
+        raise ValueError(f"{what}: groups must be a contiguous int32 vector, one label per "
+                         "source ray")
+    if not 1 <= n_groups <= FOCUS_MAX_GROUPS:
+        raise ValueError(f"{what}: n_groups must lie in 1 .. {FOCUS_MAX_GROUPS}")
+    if dimension not in (2, 3) or rows.dim() != 2 or rows.shape[0] != 2 * dimension:
+        raise ValueError(f"{what}: rows must be the (2 * dimension, n) geometry block of a "
+                         f"2-D or 3-D trace, got dimension {dimension!r} and shape "
+                         f"{tuple(rows.shape)}")
+    if len(grid) != 11:
+        raise ValueError(f"{what}: grid must come from focus_grid")
+    try:
+        a = flatfield_axis(axis, dimension)
+    except ValueError as e:
+        raise ValueError(f"{what}: axis must be {dimension} finite numbers, not all zero; got "
+                         f"{axis!r}") from e
+    min_det = float(min_det)
+    if not (min_det > 0.0 and np.isfinite(min_det)):
+        raise ValueError(f"{what}: min_det must be finite and > 0")
+    if variant not in (0, 1, 2) or (variant == 1 and n_groups > FOCUS_LDS_GROUPS):
+        raise ValueError(f"{what}: variant must be 0, 1 (up to {FOCUS_LDS_GROUPS} groups) or 2")
+    n = rows.shape[1]
+    pbits = focus_pbits(groups.numel())
+    if n >= 1 << (61 - pbits):
+        raise ValueError(f"{what}: more columns than the source's fixed point allows "
+                         "(n < 2^(61 - pbits))")
+    grad, err = _column_buffers(what, rows, grad, err, mask, perm)
+    dev = rows.device
+    made = dict(acc=((n_groups, FOCUS_SLOTS), torch.int64),
+                table=((n_groups, FLATFIELD_ROW), torch.float64), fit_out=((8,), torch.float64))
+    given = dict(acc=acc, table=table, fit_out=fit_out)
+    for name, (shape, dtype) in made.items():
+        if given[name] is None:
+            given[name] = torch.empty(shape, dtype=dtype, device=dev)
+        b = given[name]
+        if tuple(b.shape) != shape or b.dtype != dtype or not b.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous {dtype} of shape {shape}")
+    acc, table, fit_out = given["acc"], given["table"], given["fit_out"]
+    if not rows.is_cuda:
+        _flatfield_error_cpu(rows, groups, n_groups, grid, a, min_det, mask, perm, dimension,
+                             grad, err, acc, table, fit_out, pbits)
+        return err, grad, acc, table, fit_out
+    if table.data_ptr() % 64 != 0:
+        raise ValueError(f"{what}: table must be 64-byte aligned")
+    L = _lib.lib()
+    workspace = _column_workspace(
+        what, rows, grad, workspace,
+        lambda: L.tfrt_flatfield_error_workspace_bytes(n, n_groups), groups, mask, perm, err, acc,
+        table, fit_out)
+    check(L.tfrt_flatfield_error(
+        _p(rows), rows.stride(0), n, _DT[rows.dtype], int(dimension), _p(mask), _p(groups),
+        groups.numel(), _p(perm), n_groups, *grid[:6], pbits, min_det, *a, _p(grad),
+        grad.stride(0), _p(err), _p(acc), _p(table), _p(fit_out), int(variant), _p(workspace),
+        workspace.numel(), _stream(rows)), "tfrt_flatfield_error")
+    return err, grad, acc, table, fit_out
+
+
+def _flatfield_error_cpu(rows, groups, n_groups, grid, a, min_det, mask, perm, d, grad, err, acc,
+                         table, fit_out, pbits):
+    """The CPU path of ``flatfield_error`` (every torch op rounds on its own, as the kernels
+    do)."""
+    n = rows.shape[1]
+    counts, label, u, m, L = _focus_columns(rows, groups, n_groups, grid, mask, perm, d)
+    _focus_records_cpu(acc, counts, label, u, m, pbits, d)
+    t, fit, inside, terms = _flatfield_fit(acc, pbits, min_det, d, a, grid)
+    table.copy_(t)
+    fit_out.copy_(fit)
+    has, gs, ge = _flatfield_rays(counts, label, u, m, L, table, grid[9], bool(fit[4] != 0.0))
     zero = torch.zeros((), dtype=torch.float64)
     for b in range(d):
         grad[b, :n] = torch.where(has, gs[b], zero)
         grad[d + b, :n] = torch.where(has, ge[b], zero)
-    n_terms = int(has.sum())
-    e = term[has].sum()
-    err[0], err[1] = e, float(n_terms)
-    err[2] = e / n_terms if n_terms > 0 else float("nan")
+    err[0], err[1] = inside, float(terms)
+    err[2] = inside / terms if terms > 0 else float("nan")
 
 
 # ------------------------------------------------------- a sum of error terms (SumError)

@@ -1747,7 +1747,7 @@ __device__ __forceinline__ void beam_decide(const int nb, const int lane, LdsPtr
     const double* fp = fverts + 9 * (int64_t)j;
 #pragma unroll
     for (int k = 0; k < 9; ++k) P[k] = fp[k];
-    const TriHit h = exact_triangle(s, e, P, eps_int, eps_size, eps_start);
+    const TriHit h = exact_triangle</*SHARED_QUOTIENTS=*/true>(s, e, P, eps_int, eps_size, eps_start);
     if (h.valid) {
       have = true;
       key = dkey(h.ray_u);
@@ -1799,13 +1799,33 @@ struct BeamScene {
 #define TFRT_WI_ARG nullptr
 #endif
 
+// c0 as the walk reads it, wave-uniform: float32 ray state needs its three float32 roundings only
+// (exact: c0 is rounded to float32), float64 state the doubles.  Constant for a launch -- the
+// set-up launch before wrote it -- so a kernel of several passes forms it once, ahead of its
+// pass loop: read per pass, the load sat behind a wait that also covered the stores of the pass
+// before.
+struct BeamCentre {
+  double c[3];
+  float cf[3];
+};
+__device__ __forceinline__ BeamCentre beam_centre(const double* __restrict__ c0) {
+  BeamCentre o;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    o.c[k] = c0[k];
+    o.cf[k] = uniform_f((float)o.c[k]);
+  }
+  return o;
+}
+
 // ONE pass of one wavefront: the rays wait in W.rtab (as stored), `live` lanes carry a ray of this
 // pass, `skip` is the face a ray starts on (-1: none).  Leaves every live ray's nearest valid hit in
 // W.best_k (order-preserving key of ray_u) / W.best_i (face, -1: none).  Returns false when the
 // wavefront is no (few) narrow bundle(s) and the caller should leave it to the grouped kernel
 // (never with coherent_only).
 template <typename T, typename RT>
-__device__ __forceinline__ bool beam_pass(BeamLds<RT>& W, const BeamScene& g, const int lane,
+__device__ __forceinline__ bool beam_pass(BeamLds<RT>& W, const BeamScene& g,
+                                          const BeamCentre& ctr, const int lane,
                                           const int bundle, const bool live, const int skip,
                                           const bool first_pass, const int coherent_only,
                                           unsigned* _wi, unsigned* work = nullptr) {
@@ -1817,15 +1837,13 @@ __device__ __forceinline__ bool beam_pass(BeamLds<RT>& W, const BeamScene& g, co
   const float4* __restrict__ csphere = g.csphere;
   const float4* __restrict__ crec = g.crec;
   const double* __restrict__ fverts = g.fverts;
-  const double* __restrict__ c0 = g.c0;
   const int n_clusters = g.n_clusters, n_super = g.n_super;
   const double eps_int = g.eps_int, eps_size = g.eps_size, eps_start = g.eps_start;
   const float4 never = make_float4(0.f, 0.f, 0.f, -1.f);
   W.best_k[lane] = dkey(INFINITY);
   W.best_i[lane] = -1;
-  const double cx = c0[0], cy = c0[1], cz = c0[2];
-  // (exact: c0 is rounded to float32)
-  const float cxf = uniform_f((float)cx), cyf = uniform_f((float)cy), czf = uniform_f((float)cz);
+  const double cx = ctr.c[0], cy = ctr.c[1], cz = ctr.c[2];
+  const float cxf = ctr.cf[0], cyf = ctr.cf[1], czf = ctr.cf[2];
   auto rel = [](const RT v, const double c, const float cf) -> float {
     if constexpr (sizeof(T) <= 4) return (float)v - cf;
     else return (float)((double)v - c);
@@ -2275,8 +2293,8 @@ __global__ __launch_bounds__(64 * BW) void k_intersect_beam(
 #pragma unroll
   for (int k = 0; k < 6; ++k) W.rtab[k][lane] = static_cast<RT>(rays[k * stride + ii]);
   const int skip = (live && last_tri != nullptr) ? last_tri[ii] : -1;
-  if (!beam_pass<T, RT>(W, g, lane, bundle, live, skip, last_tri == nullptr, coherent_only,
-                        TFRT_WI_ARG)) {
+  if (!beam_pass<T, RT>(W, g, beam_centre(g.c0), lane, bundle, live, skip, last_tri == nullptr,
+                        coherent_only, TFRT_WI_ARG)) {
     // not a wavefront of (a few) narrow bundles: the grouped kernel does it
     if (lane == 0) {
       left_list[atomicAdd(left_count, 1)] = qwave;
@@ -2687,10 +2705,13 @@ __device__ __forceinline__ void trace_inplace(const InplaceArgs<T>& a, const Bea
       reinterpret_cast<const uint32_t*>(a.tape)[lane < (int)(sizeof(InplaceTape) / 4) ? lane : 0];
   TFRT_WAVE_BEGIN;
   unsigned work[2] = {0u, 0u};
+  // (once per launch: no pass begins by waiting for a load, and with it for the stores of the pass
+  // before)
+  const BeamCentre centre = beam_centre(g.c0);
   for (; p < a.P; ++p) {
     if (__ballot(active) == 0ull) break;  // (wave-uniform: every ray of the wavefront has ended)
-    beam_pass<T, RT>(W, g, lane, a.bundle, active, skip, p == 0, /*coherent_only=*/1, TFRT_WI_ARG,
-                     work);
+    beam_pass<T, RT>(W, g, centre, lane, a.bundle, active, skip, p == 0, /*coherent_only=*/1,
+                     TFRT_WI_ARG, work);
     wave_fence();
     TFRT_TICK_INIT;
     // (the struct waits in ONE vector register, a word per lane, and is unpacked here, pass by
@@ -2712,7 +2733,23 @@ __device__ __forceinline__ void trace_inplace(const InplaceArgs<T>& a, const Bea
     if (active) {
       const int bi = W.best_i[lane];
       const double t = dkey_inv(W.best_k[lane]);
-      cls = (bi < 0) ? CLS_DEAD : cat_to_cls(tq.catagory[bi]);
+      // everything the reaction reads of the face depends on bi alone: asked for together, one
+      // wait (a lane that turns out not to be active has loaded 48 bytes of a line its
+      // neighbours read anyway)
+      int cat = 0;
+      double un[3] = {0.0, 0.0, 0.0}, fe[3] = {0.0, 0.0, 0.0};
+      if (bi >= 0) {
+        cat = tq.catagory[bi];
+        const double* fp = tq.fnorm + 3 * (int64_t)bi;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) un[k] = fp[k];
+        if (tq.feta != nullptr) {
+          const double* fq = tq.feta + 4 * (int64_t)bi;
+#pragma unroll
+          for (int k = 0; k < 3; ++k) fe[k] = fq[k];
+        }
+      }
+      cls = (bi < 0) ? CLS_DEAD : cat_to_cls(cat);
       const size_t at = (size_t)p * tq.n + i;
       tq.rec_tri[at] = bi;
       tq.rec_t[at] = t;
@@ -2726,12 +2763,8 @@ __device__ __forceinline__ void trace_inplace(const InplaceArgs<T>& a, const Bea
           e[k] = static_cast<double>(W.rtab[3 + k][lane]);
         }
         hit_point(s, e, t, h);
-        double un[3], n1, n2, n_in;
-        const double* fp = tq.fnorm + 3 * (int64_t)bi;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) un[k] = fp[k];
+        double n1, n2, n_in;
         if (tq.feta != nullptr) {
-          const double* fe = tq.feta + 4 * (int64_t)bi;
           n1 = fe[0];
           n2 = fe[1];
           n_in = fe[2];

@@ -35,8 +35,56 @@ struct TriHit {
   bool valid;
 };
 
+// nr / sd, nu / sd, nv / sd, bit for bit.  On the device an IEEE float64 division is eleven
+// instructions, six of which -- the scaled denominator, its reciprocal estimate and the four
+// multiply-adds that refine it -- depend on the numerator only through the scaling
+// v_div_scale_f64 picks for the denominator.  Where the three scalings agree in a lane (anything
+// but extreme exponents: a subnormal or huge denominator, a tiny numerator) those six are formed
+// once and each numerator takes its own five: the compiler's expansion of the three quotients with
+// the common sub-expression shared -- the same operations in the same order, hence the same bits.
+// A lane where they differ takes the three plain divisions; a wavefront without such a lane
+// branches over them.  On the host (tests/host_math) the plain divisions.
+TFRT_HD void quotients3(double nr, double nu, double nv, double sd, double* qr, double* qu,
+                        double* qv) {
+#pragma clang fp contract(off)
+#if defined(__HIP_DEVICE_COMPILE__)
+  bool fr, fu, fv;
+  const double dr = __builtin_amdgcn_div_scale(nr, sd, false, &fr);
+  const double du = __builtin_amdgcn_div_scale(nu, sd, false, &fu);
+  const double dv = __builtin_amdgcn_div_scale(nv, sd, false, &fv);
+  unsigned long long br, bu, bv;
+  __builtin_memcpy(&br, &dr, 8);
+  __builtin_memcpy(&bu, &du, 8);
+  __builtin_memcpy(&bv, &dv, 8);
+  // (`&`: both comparisons in every lane, one branch -- `&&` made the third scaling a branch of
+  // its own)
+  if ((br == bu) & (br == bv)) {
+    const double nd = -dr;
+    const double r0 = __builtin_amdgcn_rcp(dr);
+    const double r1 = __builtin_fma(r0, __builtin_fma(nd, r0, 1.0), r0);
+    const double r2 = __builtin_fma(r1, __builtin_fma(nd, r1, 1.0), r1);
+    const double num[3] = {nr, nu, nv};
+    double* const out[3] = {qr, qu, qv};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      bool fn;
+      const double ns = __builtin_amdgcn_div_scale(num[k], sd, true, &fn);
+      const double m = ns * r2;
+      const double res = __builtin_fma(nd, m, ns);
+      *out[k] = __builtin_amdgcn_div_fixup(__builtin_amdgcn_div_fmas(res, r2, m, fn), sd, num[k]);
+    }
+    return;
+  }
+#endif
+  *qr = nr / sd;
+  *qu = nu / sd;
+  *qv = nv / sd;
+}
+
 // geometry.py:286-311 + engine.py:1138-1141.  s = ray start (r1), e = ray end (r2),
 // P = {xp,yp,zp, x1,y1,z1, x2,y2,z2}.
+// SHARED_QUOTIENTS: the three quotients through quotients3().
+template <bool SHARED_QUOTIENTS = false>
 TFRT_HD TriHit exact_triangle(const double s[3], const double e[3], const double P[9],
                               double eps_int, double eps_size, double eps_start) {
 #pragma clang fp contract(off)
@@ -53,9 +101,13 @@ TFRT_HD TriHit exact_triangle(const double s[3], const double e[3], const double
   TriHit o;
   bool valid = fabs(den) >= eps_int;
   const double sd = valid ? den : 1.0;
-  o.ray_u = nr / sd;
-  o.trig_u = nu / sd;
-  o.trig_v = nv / sd;
+  if constexpr (SHARED_QUOTIENTS) {
+    quotients3(nr, nu, nv, sd, &o.ray_u, &o.trig_u, &o.trig_v);
+  } else {
+    o.ray_u = nr / sd;
+    o.trig_u = nu / sd;
+    o.trig_v = nv / sd;
+  }
   valid = valid && (o.trig_u >= -eps_size);
   valid = valid && (o.trig_v >= -eps_size);
   valid = valid && (o.trig_u + o.trig_v <= 1.0 + eps_size);

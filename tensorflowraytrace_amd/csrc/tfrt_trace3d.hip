@@ -4009,12 +4009,44 @@ __device__ __forceinline__ U ld_lane(const U* base, uint32_t i) {
   return ld_scalar_base(base, (unsigned long long)(i * (uint32_t)sizeof(U)));
 }
 
+// The goal's rows as a compile-time fact of the sweep (ROWS of chain_goal_pass and
+// k_backward_chain_goal_inplace): bit j set = row j of the ray block (0..5: x_start .. z_end)
+// carries a goal column, for a goal whose rows are strictly ascending; row j's column is then the
+// number of set rows below it.  GOAL_ROWS_RUNTIME: the rows are read from ChainGoalArgs in the
+// pass.  Instantiated: ("y_end", "z_end"), the only rows a 3-D GoalError of bench.py,
+// bench_configs.py or examples/ states; every other goal takes the run-time
+// instantiation.
+constexpr int GOAL_ROWS_RUNTIME = -1;
+constexpr int GOAL_ROWS_YZ_END = 0b110000;
+constexpr __host__ __device__ bool goal_row_set(int rows, int j) { return ((rows >> j) & 1) != 0; }
+constexpr __host__ __device__ int goal_row_column(int rows, int j) {
+  int c = 0;
+  for (int k = 0; k < j; ++k) c += (rows >> k) & 1;
+  return c;
+}
+
+// The instantiated mask of a goal's rows, or GOAL_ROWS_RUNTIME (rows not strictly ascending, or a
+// set of rows that has no instantiation).  The route follows from the goal alone.
+static int goal_rows_instantiated(const GoalFields& gf) {
+  int mask = 0;
+  for (int c = 0; c < gf.n; ++c) {
+    if (gf.row[c] < 0 || gf.row[c] > 5) return GOAL_ROWS_RUNTIME;
+    if (c > 0 && gf.row[c] <= gf.row[c - 1]) return GOAL_ROWS_RUNTIME;
+    mask |= 1 << gf.row[c];
+  }
+  return mask == GOAL_ROWS_YZ_END ? mask : GOAL_ROWS_RUNTIME;
+}
+
 // One pass of one lane of k_backward_chain_goal_inplace (below): `child` is the gradient w.r.t.
 // the lane's ray as the later pass left it and receives this pass's.  FIN / CHILD: false where no
 // lane of the wavefront finishes in this pass / no lane has a child ray in it; then the goal's
 // loads, the finished row, the seed and the columns' loop / the child's arm, the index ratios,
-// Snell's reverse and the normal's way back do not exist.  One source for both roles.
-template <typename T, bool FIN, bool CHILD, int TERMS>
+// Snell's reverse and the normal's way back do not exist.  One source for both roles.  ROWS: the
+// goal's rows (above); known, a goal value and a seed exist for the set rows only, the residuals
+// run over them in ascending order -- the run-time code's order, so the error sum keeps its bits --
+// the seeds of the other rows are literal zeros, and the scalar decisions per register, the packed
+// rows and the loop over the columns are not compiled in.
+template <typename T, bool FIN, bool CHILD, int TERMS, int ROWS>
 __device__ __forceinline__ int chain_goal_pass(const ChainGoalArgs<T>& a, int p, int wave, int lane,
                                                int tape, int face, bool fin_lane, double child[6],
                                                double& err, double gP[9]) {
@@ -4050,13 +4082,24 @@ __device__ __forceinline__ int chain_goal_pass(const ChainGoalArgs<T>& a, int p,
   if (fin_here || on_face) t_rec = ld_lane(a.rec_t + off + w0, lv);
   if (FIN) {
     const int64_t gl = (int64_t)lv * a.goal_ray_stride;
+    if constexpr (ROWS != GOAL_ROWS_RUNTIME) {
 #pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      int cj = a.goal_col[j];
-      __asm__ volatile("" : "+s"(cj));   // (a scalar branch per register, decided in the pass)
-      if (cj >= 0) {
-        const double* gb = a.goal + (int64_t)cj * a.goal_stride + (int64_t)w0 * a.goal_ray_stride;
-        if (fin_here) goal_w[j] = ld_scalar_base(gb, (unsigned long long)gl * sizeof(double));
+      for (int j = 0; j < 6; ++j) {
+        if (goal_row_set(ROWS, j)) {
+          const double* gb = a.goal + (int64_t)goal_row_column(ROWS, j) * a.goal_stride +
+                             (int64_t)w0 * a.goal_ray_stride;
+          if (fin_here) goal_w[j] = ld_scalar_base(gb, (unsigned long long)gl * sizeof(double));
+        }
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        int cj = a.goal_col[j];
+        __asm__ volatile("" : "+s"(cj));   // (a scalar branch per register, decided in the pass)
+        if (cj >= 0) {
+          const double* gb = a.goal + (int64_t)cj * a.goal_stride + (int64_t)w0 * a.goal_ray_stride;
+          if (fin_here) goal_w[j] = ld_scalar_base(gb, (unsigned long long)gl * sizeof(double));
+        }
       }
     }
   }
@@ -4094,7 +4137,16 @@ __device__ __forceinline__ int chain_goal_pass(const ChainGoalArgs<T>& a, int p,
       fin_row[k] = s0[k];
       fin_row[3 + k] = static_cast<double>(static_cast<T>(h0[k]));
     }
-    if (a.rows_ascending) {
+    if constexpr (ROWS != GOAL_ROWS_RUNTIME) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        if (goal_row_set(ROWS, k)) {
+          const double r = fin_row[k] - goal_w[k];
+          seed[k] = 2.0 * r;
+          err += r * r;
+        }
+      }
+    } else if (a.rows_ascending) {
 #pragma unroll
       for (int k = 0; k < 6; ++k) {
         if (a.goal_col[k] >= 0) {   // (scalar)
@@ -4134,7 +4186,7 @@ __device__ __forceinline__ int chain_goal_pass(const ChainGoalArgs<T>& a, int p,
   return tri;
 }
 
-template <typename T, int TERMS>
+template <typename T, int TERMS, int ROWS>
 __global__ __launch_bounds__(64)
 __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_backward_chain_goal_inplace(
     ChainGoalArgs<T> a) {
@@ -4201,9 +4253,9 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
     // runs (chain_goal_pass).  A mixed wavefront runs both, each with its own lanes.
     const bool fin_role = here && fin_m != 0ull && !(p < P - 1 && (tape & 3) == CLS_ACTIVE);
     if (fin_role)
-      tri = chain_goal_pass<T, true, false, TERMS>(a, p, wave, lane, tape, face, fin_here, child, err, gP);
+      tri = chain_goal_pass<T, true, false, TERMS, ROWS>(a, p, wave, lane, tape, face, fin_here, child, err, gP);
     if (here && !fin_role)
-      tri = chain_goal_pass<T, false, true, TERMS>(a, p, wave, lane, tape, face, false, child, err, gP);
+      tri = chain_goal_pass<T, false, true, TERMS, ROWS>(a, p, wave, lane, tape, face, false, child, err, gP);
     n_fin += __popcll(fin_m);
     n_entered += __popcll(__ballot(here));
     wave_face_sums<TERMS>(tri, gP, wacc, wface, a.g_fverts);
@@ -5038,9 +5090,13 @@ static int trace3d_backward_t(const SweepCall3& c) {
     ProfScope prof_bwd(TFRT_PROF_BACKWARD, st);
     if (N > 0 && goal_inplace) {
       using Kernel = void (*)(ChainGoalArgs<T>);
-      const Kernel kernel[2] = {k_backward_chain_goal_inplace<T, 9>,   // [four sums]
-                                k_backward_chain_goal_inplace<T, 4>};
-      hipLaunchKernelGGL(kernel[four_sums], dim3(cdiv(N, 64)), dim3(64),
+      const Kernel kernel[2][2] = {   // [the goal's rows known][four sums]
+          {k_backward_chain_goal_inplace<T, 9, GOAL_ROWS_RUNTIME>,
+           k_backward_chain_goal_inplace<T, 4, GOAL_ROWS_RUNTIME>},
+          {k_backward_chain_goal_inplace<T, 9, GOAL_ROWS_YZ_END>,
+           k_backward_chain_goal_inplace<T, 4, GOAL_ROWS_YZ_END>}};
+      const bool rows_known = goal_rows_instantiated(a.gf) == GOAL_ROWS_YZ_END;
+      hipLaunchKernelGGL(kernel[rows_known][four_sums], dim3(cdiv(N, 64)), dim3(64),
                          (size_t)P * 64 * sizeof(int2), st, chain_goal_args_of(a, sc));
     } else if (N > 0) {
       using Kernel = void (*)(ChainArgs<T>, tfrt_scene3d);

@@ -1768,13 +1768,15 @@ __device__ __forceinline__ void beam_decide(const int nb, const int lane, LdsPtr
 }
 
 // LDS of one wavefront of the beam walk (k_intersect_beam, k_trace_inplace)
-template <typename RT>
+// CHUNK: candidate faces per chunk of beam_pass (64; k_trace_inplace<float> takes 32, whose table
+// leaves room for a sixth wavefront per SIMD in a CU's LDS)
+template <typename RT, int CHUNK = 64>
 struct BeamLds {
   uint16_t slist[BEAM_SLIST];
   uint16_t clist[BEAM_CLIST];
   uint32_t flist[BEAM_FLIST];
   uint32_t x_pair[192];  // face << 6 | lane of the ray (faces < 2^24)
-  float4 ftab[65][4];    // records of a chunk's faces, nearest first (face_frame); a round loads two
+  float4 ftab[CHUNK + 1][4];   // records of a chunk's faces, nearest first (face_frame); a round loads two
                          // (the second, behind the chunk's last face, is read and not used)
   RT rtab[6][64];        // the wave's rays as stored (the exact test reads them by slot)
   unsigned long long best_k[64];
@@ -1823,9 +1825,9 @@ __device__ __forceinline__ BeamCentre beam_centre(const double* __restrict__ c0)
 // W.best_k (order-preserving key of ray_u) / W.best_i (face, -1: none).  Returns false when the
 // wavefront is no (few) narrow bundle(s) and the caller should leave it to the grouped kernel
 // (never with coherent_only).
-template <typename T, typename RT>
-__device__ __forceinline__ bool beam_pass(BeamLds<RT>& W, const BeamScene& g,
-                                          const BeamCentre& ctr, const int lane,
+template <typename T, typename RT, int CHUNK = 64>
+__device__ __forceinline__ bool beam_pass(BeamLds<RT, CHUNK>& W, const BeamScene& g,
+                                          const BeamCentre& ctr, const int lane_in,
                                           const int bundle, const bool live, const int skip,
                                           const bool first_pass, const int coherent_only,
                                           unsigned* _wi, unsigned* work = nullptr) {
@@ -1840,7 +1842,20 @@ __device__ __forceinline__ bool beam_pass(BeamLds<RT>& W, const BeamScene& g,
   const int n_clusters = g.n_clusters, n_super = g.n_super;
   const double eps_int = g.eps_int, eps_size = g.eps_size, eps_start = g.eps_start;
   const float4 never = make_float4(0.f, 0.f, 0.f, -1.f);
-  W.best_k[lane] = dkey(INFINITY);
+  // LATE: the kernel with the short chunks (k_trace_inplace<float>, six wavefronts per SIMD, 80
+  // registers) cannot afford per-lane values that wait through the walk over the faces without
+  // being used in it.  There the lane is made opaque anew for every bundle, so that the node and
+  // list addresses made of it are made per bundle, and so is the "no hit" key per call.  The
+  // other kernels keep their instructions.
+  constexpr bool LATE = CHUNK < 64;
+  int lane = lane_in;
+  unsigned long long no_hit = dkey(INFINITY);
+  if constexpr (LATE) {
+    uint32_t top = (uint32_t)(no_hit >> 32);
+    __asm__ volatile("" : "+s"(top));
+    no_hit = ((unsigned long long)top << 32) | (uint32_t)no_hit;
+  }
+  W.best_k[lane] = no_hit;
   W.best_i[lane] = -1;
   const double cx = ctr.c[0], cy = ctr.c[1], cz = ctr.c[2];
   const float cxf = ctr.cf[0], cyf = ctr.cf[1], czf = ctr.cf[2];
@@ -1877,6 +1892,7 @@ __device__ __forceinline__ bool beam_pass(BeamLds<RT>& W, const BeamScene& g,
   int lo = 0, attempts = 0;
   bool spread = false;
   while (lo < bundle) {
+    if constexpr (LATE) __asm__ volatile("" : "+v"(lane));
     ++attempts;
     TFRT_STAT(30, 1);
     TFRT_WAVE_NOTE(0, 1);
@@ -2074,11 +2090,22 @@ __device__ __forceinline__ bool beam_pass(BeamLds<RT>& W, const BeamScene& g,
           // perpendiculars from the frame origin, plus the directions' difference over that distance
           const float su = sx * ux + sy * uy + sz * uz;
           const float fx = sx - su * ux, fy = sy - su * uy, fz = sz - su * uz;
-          const float gx = fx - __shfl_up(fx, 1, 64), gy = fy - __shfl_up(fy, 1, 64),
-                      gz = fz - __shfl_up(fz, 1, 64);
-          const float hx = ux - __shfl_up(ux, 1, 64), hy = uy - __shfl_up(uy, 1, 64),
-                      hz = uz - __shfl_up(uz, 1, 64);
-          const bool prev_ok = __shfl_up(ok ? 1 : 0, 1, 64) != 0;
+          // (the previous lane's value, lane 0 its own: __shfl_up(v, 1, 64); LATE: the partner's
+          // address from this bundle's lane, not from a lane index kept for all passes)
+          auto up1 = [&](const float v) -> float {
+            if constexpr (LATE)
+              return __int_as_float(
+                  __builtin_amdgcn_ds_bpermute((lane - (lane > 0 ? 1 : 0)) << 2, __float_as_int(v)));
+            else
+              return __shfl_up(v, 1, 64);
+          };
+          const float gx = fx - up1(fx), gy = fy - up1(fy), gz = fz - up1(fz);
+          const float hx = ux - up1(ux), hy = uy - up1(uy), hz = uz - up1(uz);
+          bool prev_ok;
+          if constexpr (LATE)
+            prev_ok = __builtin_amdgcn_ds_bpermute((lane - (lane > 0 ? 1 : 0)) << 2, ok ? 1 : 0) != 0;
+          else
+            prev_ok = __shfl_up(ok ? 1 : 0, 1, 64) != 0;
           gap = 0.f;
           if (ok && prev_ok && lane > 0)
             gap = gx * gx + gy * gy + gz * gz +
@@ -2128,14 +2155,17 @@ __device__ __forceinline__ bool beam_pass(BeamLds<RT>& W, const BeamScene& g,
     };
     float myreach = reach_now();
     bool queued = false;  // a pair of this ray waits for its decision
-    // Chunks of up to 64 candidate faces: the entries of flist -- or, for a single ray whose lists
-    // overflowed, every member slot of the scene.  The LAST chunk of the wavefront's last bundle
-    // also decides what is still queued (one place for all decisions: the float64 test's
-    // registers are not multiplied by the number of places that run it).
+    // Chunks of up to CHUNK candidate faces: the entries of flist -- or, for a single ray whose lists
+    // overflowed, every member slot of the scene.  (A chunk boundary only decides the order in
+    // which the faces are met: every face is still walked or skipped by the same necessary
+    // conditions, and the nearest hit is a minimum with ties to the lower face, whatever the order.)
+    // The LAST chunk of the wavefront's last bundle also decides what is still queued (one place
+    // for all decisions: the float64 test's registers are not multiplied by the number of places
+    // that run it).
     const int n_cand = brute ? n_clusters * CLUSTER : nf;
     int f0 = 0;
     do {
-      const int nb = min(64, n_cand - f0);
+      const int nb = min(CHUNK, n_cand - f0);
       if (work != nullptr) work[1] += (unsigned)nb;
       float4 rec[4] = {never, never, never, never};  // (set: nothing is carried around the loop)
       bool touch = false;
@@ -2159,7 +2189,7 @@ __device__ __forceinline__ bool beam_pass(BeamLds<RT>& W, const BeamScene& g,
         if (tnear != tnear) tnear = -INFINITY;  // (NaN: never skipped)
         rec[0].w = tnear;
       }
-      f0 += 64;
+      f0 += CHUNK;
       const bool closing = f0 >= n_cand && hi == bundle;  // nothing comes after this chunk
       // nearest first: a face's place = the number of faces that begin nearer (ties: lower lane)
       const unsigned long long tm = __ballot(touch);
@@ -2667,20 +2697,36 @@ struct InplaceArgs {
   int32_t ngroups, gshift;
 };
 
-// Wavefronts per SIMD: five for the plain kernel (96 registers, no scratch; with the 8 KB of LDS a
-// wavefront takes, five is also what a CU's LDS holds), 0.244 against 0.250 ms per step with four.
+// Wavefronts per SIMD: five for the plain kernel with 64-face chunks (_Float16 state: 96 registers,
+// no scratch; with the 8 KB of LDS a wavefront takes, five is also what a CU's LDS holds), 0.244
+// against 0.250 ms per step with four.
 // The kernel that also writes the finished rows needs 119 registers: four (pinned -- left to itself
 // the compiler took 162, three wavefronts, and the step 0.270 ms).  float64 state: the LDS (9.7 KB
 // per wavefront) admits four either way.
 #ifndef TFRT_INPLACE_WAVES   // (tuning builds set it: scratch/build_variants.py)
 #define TFRT_INPLACE_WAVES 5
 #endif
-#define TFRT_INPLACE_ATTR __attribute__((amdgpu_waves_per_eu(TFRT_INPLACE_WAVES, TFRT_INPLACE_WAVES)))
+// float32 state, plain kernel: six (80 registers, no scratch, and 32-face chunks in beam_pass: 6 KB
+// of LDS per wavefront, 160 KB / 24 = 6.8 KB being the limit): 108 against 119.5 us per launch of
+// the headline step.  It gets there because no per-lane value waits through the walk unused: the
+// lane is made opaque in place around the walk (below) and per bundle inside it (beam_pass, LATE).
+#ifndef TFRT_INPLACE_F32_WAVES
+#define TFRT_INPLACE_F32_WAVES 6
+#endif
+template <typename T>
+constexpr int inplace_waves() {
+  return std::is_same<T, float>::value ? TFRT_INPLACE_F32_WAVES : TFRT_INPLACE_WAVES;
+}
+template <typename T>
+constexpr int inplace_chunk() {
+  return std::is_same<T, float>::value && TFRT_INPLACE_F32_WAVES > 5 ? 32 : 64;
+}
 // ROWS: tfrt_scene3d.in_place == 2 (the finished rows at the rays' own columns)
-template <typename T, bool ROWS>
+// CHUNK: candidate faces per chunk of the beam walk (BeamLds)
+template <typename T, bool ROWS, int CHUNK>
 __device__ __forceinline__ void trace_inplace(const InplaceArgs<T>& a, const BeamScene& g) {
   using RT = std::conditional_t<sizeof(T) <= 4, float, double>;
-  const int lane = threadIdx.x;
+  int lane = threadIdx.x;   // (made opaque in place, pass by pass: below)
   // (one wave-uniform load at entry: the index lives in a scalar register like blockIdx.x did, and
   // everything indexed by wavefront -- rays, tape, count rows -- follows it)
   int qwave = blockIdx.x;
@@ -2690,14 +2736,21 @@ __device__ __forceinline__ void trace_inplace(const InplaceArgs<T>& a, const Bea
     qwave = (g << a.gshift) + ((int)blockIdx.x & ((1 << a.gshift) - 1));
     if (qwave >= a.nwaves) return;   // (the last group of a 32-ray trace may hold one wavefront)
   }
-  const int q = qwave * a.bundle + lane;
-  const bool has = lane < a.bundle && q < a.N;
-  const int64_t i = has ? q : 0;
-  __shared__ BeamLds<RT> lds;
-  BeamLds<RT>& W = lds;
+  // (the ray's index is made of qwave and the lane wherever it is used: as one value made here,
+  // it -- 64 bits -- and the addresses made of it waited in vector registers through every walk)
+  auto ray_index = [&](bool* has) -> int64_t {
+    const int q = qwave * a.bundle + lane;
+    *has = lane < a.bundle && q < a.N;
+    return *has ? q : 0;
+  };
+  __shared__ BeamLds<RT, CHUNK> lds;
+  BeamLds<RT, CHUNK>& W = lds;
+  bool active;
+  {
+    const int64_t i = ray_index(&active);
 #pragma unroll
-  for (int k = 0; k < 6; ++k) W.rtab[k][lane] = static_cast<RT>(a.src[k * a.src_stride + i]);
-  bool active = has;
+    for (int k = 0; k < 6; ++k) W.rtab[k][lane] = static_cast<RT>(a.src[k * a.src_stride + i]);
+  }
   int skip = -1;
   int p = 0;
   static_assert(sizeof(InplaceTape) % 4 == 0 && sizeof(InplaceTape) / 4 <= 64, "one word per lane");
@@ -2710,8 +2763,13 @@ __device__ __forceinline__ void trace_inplace(const InplaceArgs<T>& a, const Bea
   const BeamCentre centre = beam_centre(g.c0);
   for (; p < a.P; ++p) {
     if (__ballot(active) == 0ull) break;  // (wave-uniform: every ray of the wavefront has ended)
-    beam_pass<T, RT>(W, g, centre, lane, a.bundle, active, skip, p == 0, /*coherent_only=*/1,
-                     TFRT_WI_ARG, work);
+    // (the lane, opaque anew in front of the walk and behind it: what either side makes of it --
+    // node, list and table addresses there, the ray's index and its columns here -- is made in
+    // its pass and on its side, and only the lane itself waits through the other)
+    __asm__ volatile("" : "+v"(lane));
+    beam_pass<T, RT, CHUNK>(W, g, centre, lane, a.bundle, active, skip, p == 0, /*coherent_only=*/1,
+                            TFRT_WI_ARG, work);
+    __asm__ volatile("" : "+v"(lane));
     wave_fence();
     TFRT_TICK_INIT;
     // (the struct waits in ONE vector register, a word per lane, and is unpacked here, pass by
@@ -2731,6 +2789,8 @@ __device__ __forceinline__ void trace_inplace(const InplaceArgs<T>& a, const Bea
     }
     int cls = -1;
     if (active) {
+      bool has;
+      const int64_t i = ray_index(&has);
       const int bi = W.best_i[lane];
       const double t = dkey_inv(W.best_k[lane]);
       // everything the reaction reads of the face depends on bi alone: asked for together, one
@@ -2832,6 +2892,8 @@ __device__ __forceinline__ void trace_inplace(const InplaceArgs<T>& a, const Bea
     __builtin_memcpy(&te, w, sizeof(InplaceTape));
   }
   if (ROWS && active) {   // still active after the last pass: not finished either
+    bool has;
+    const int64_t i = ray_index(&has);
     T* fin_rows = static_cast<T*>(te.fin_rows);
 #pragma unroll
     for (int k = 0; k < 6; ++k) fin_rows[k * te.fin_cap + i] = a.src[k * a.src_stride + i];
@@ -2845,13 +2907,15 @@ __device__ __forceinline__ void trace_inplace(const InplaceArgs<T>& a, const Bea
 }
 
 template <typename T>
-__global__ __launch_bounds__(64) TFRT_INPLACE_ATTR void k_trace_inplace(InplaceArgs<T> a, BeamScene g) {
-  trace_inplace<T, false>(a, g);
+__global__ __launch_bounds__(64)
+__attribute__((amdgpu_waves_per_eu(inplace_waves<T>(), inplace_waves<T>()))) void k_trace_inplace(
+    InplaceArgs<T> a, BeamScene g) {
+  trace_inplace<T, false, inplace_chunk<T>()>(a, g);
 }
 template <typename T>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_trace_inplace_rows(
     InplaceArgs<T> a, BeamScene g) {
-  trace_inplace<T, true>(a, g);
+  trace_inplace<T, true, 64>(a, g);
 }
 
 // The counts of an in-place trace: workgroup p sums the class counts of the passes before its own
@@ -3293,10 +3357,12 @@ __device__ __forceinline__ void wsum_fold(double* wacc, const int32_t* wface, in
     }
   }
 }
+// (`lane`: the caller's lane; a caller that hands in a laundered one has the fold's LDS addresses
+// made in the call, not ahead of its loop)
 template <int TERMS>
 __device__ __forceinline__ void wave_face_sums(int tri, const double gP[9], double* wacc,
-                                               int32_t* wface, double* __restrict__ g_fverts) {
-  const int lane = threadIdx.x & 63;
+                                               int32_t* wface, double* __restrict__ g_fverts,
+                                               int lane) {
   int slot = -1, ns = 0;
   unsigned long long todo = __ballot(tri >= 0);
   if (todo == 0ull) return;  // (wave-uniform)
@@ -3328,6 +3394,11 @@ __device__ __forceinline__ void wave_face_sums(int tri, const double gP[9], doub
   else if (copies == 4) wsum_fold<4, TERMS>(wacc, wface, ns * TERMS, lane, g_fverts);
   else wsum_fold<2, TERMS>(wacc, wface, ns * TERMS, lane, g_fverts);
   wave_fence();  // (the next use of wacc / wface must not overtake these reads and zeros)
+}
+template <int TERMS>
+__device__ __forceinline__ void wave_face_sums(int tri, const double gP[9], double* wacc,
+                                               int32_t* wface, double* __restrict__ g_fverts) {
+  wave_face_sums<TERMS>(tri, gP, wacc, wface, g_fverts, (int)(threadIdx.x & 63));
 }
 
 // BW wavefronts per workgroup (the wavefronts share nothing: see k_intersect_beam)
@@ -4009,6 +4080,16 @@ __device__ __forceinline__ U ld_lane(const U* base, uint32_t i) {
   return ld_scalar_base(base, (unsigned long long)(i * (uint32_t)sizeof(U)));
 }
 
+// __shfl_xor(v, d, 64) of a double with the lane handed in: the partner's address is made of `lane`
+// at the call, so a caller that launders its lane does not share the addresses of an earlier
+// butterfly (and keep them in registers from there to here).  The same two ds_bpermute_b32.
+__device__ __forceinline__ double shfl_xor_lane(double v, int d, uint32_t lane) {
+  const int at = (int)((lane ^ (uint32_t)d) << 2);
+  const int lo = __builtin_amdgcn_ds_bpermute(at, __double2loint(v));
+  const int hi = __builtin_amdgcn_ds_bpermute(at, __double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+
 // The goal's rows as a compile-time fact of the sweep (ROWS of chain_goal_pass and
 // k_backward_chain_goal_inplace): bit j set = row j of the ray block (0..5: x_start .. z_end)
 // carries a goal column, for a goal whose rows are strictly ascending; row j's column is then the
@@ -4186,9 +4267,22 @@ __device__ __forceinline__ int chain_goal_pass(const ChainGoalArgs<T>& a, int p,
   return tri;
 }
 
+// The goal step's sweep keeps five wavefronts per SIMD where 96 vector registers hold it with
+// none spilled: the four sums with the goal's rows compiled in (the per-lane addresses of the
+// epilogue and of the LDS records are formed where they are used, not ahead of the walk back).
+// The nine terms (20 to 38 registers spilled at 96) and the run-time rows (their scalar decisions
+// spill scalar registers into a vector one, and a double of the adjoint goes to scratch inside
+// the walk) keep TFRT_CHAIN_WAVES, as k_backward_chain does.
+#ifndef TFRT_CHAIN_GOAL_WAVES   // (tuning builds set it: scratch/build_variants.py)
+#define TFRT_CHAIN_GOAL_WAVES 5
+#endif
+constexpr int chain_goal_waves(int terms, int rows) {
+  return terms == 4 && rows != GOAL_ROWS_RUNTIME ? TFRT_CHAIN_GOAL_WAVES : TFRT_CHAIN_WAVES;
+}
 template <typename T, int TERMS, int ROWS>
 __global__ __launch_bounds__(64)
-__attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_backward_chain_goal_inplace(
+__attribute__((amdgpu_waves_per_eu(chain_goal_waves(TERMS, ROWS), chain_goal_waves(TERMS, ROWS))))
+void k_backward_chain_goal_inplace(
     ChainGoalArgs<T> a) {
   // the reference's squared_difference and reduce_sum are separate ops: no contraction
 #pragma clang fp contract(off)
@@ -4241,8 +4335,12 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
     int tri = -1;
     const bool here = p <= last;
     int tape = CLS_DEAD, face = -1;
+    // (the lane through an empty statement, pass by pass: the LDS addresses of the record and of
+    // the fold in wave_face_sums are made in the pass, see the epilogue)
+    uint32_t lp = lane;
+    __asm__ volatile("" : "+v"(lp));
     if (here) {
-      const int2 rec = chain[p * 64 + lane];
+      const int2 rec = chain[p * 64 + lp];
       tape = rec.x;
       face = max(rec.y, -1);   // (a record is a face or -1)
     }
@@ -4258,19 +4356,26 @@ __attribute__((amdgpu_waves_per_eu(TFRT_CHAIN_WAVES, TFRT_CHAIN_WAVES))) void k_
       tri = chain_goal_pass<T, false, true, TERMS, ROWS>(a, p, wave, lane, tape, face, false, child, err, gP);
     n_fin += __popcll(fin_m);
     n_entered += __popcll(__ballot(here));
-    wave_face_sums<TERMS>(tri, gP, wacc, wface, a.g_fverts);
+    wave_face_sums<TERMS>(tri, gP, wacc, wface, a.g_fverts, (int)lp);
   }
-  if (a.g_src != nullptr && i0 < n0) {
-    for (int k = 0; k < 6; ++k) a.g_src[k * a.N + i0] = child[k];
+  // (the lane through an empty statement again, as in chain_goal_pass: the ray's index, the
+  // address of its g_src column and the six partner addresses of the butterflies are made here,
+  // behind the walk back, and do not wait in vector registers through it -- they were what kept
+  // the kernel from five wavefronts per SIMD.  partial and partial_cnt follow the scalar `wave`.)
+  uint32_t lv = lane;
+  __asm__ volatile("" : "+v"(lv));
+  const int i1 = wave * 64 + (int)lv;
+  if (a.g_src != nullptr && i1 < n0) {
+    for (int k = 0; k < 6; ++k) a.g_src[k * a.N + i1] = child[k];
   }
   // fixed-shape reduction: xor butterflies inside the wave (k_goal_finish sums the partials)
 #pragma unroll
-  for (int d = 32; d > 0; d >>= 1) err += __shfl_xor(err, d, 64);
-  if (lane == 0) {
-    a.partial[i0 >> 6] = err;
+  for (int d = 32; d > 0; d >>= 1) err += shfl_xor_lane(err, d, lv);
+  if (lv == 0) {
+    a.partial[wave] = err;
     if (a.partial_cnt != nullptr) {
-      a.partial_cnt[2 * (i0 >> 6)] = n_fin;
-      a.partial_cnt[2 * (i0 >> 6) + 1] = n_entered;
+      a.partial_cnt[2 * wave] = n_fin;
+      a.partial_cnt[2 * wave + 1] = n_entered;
     }
   }
 }

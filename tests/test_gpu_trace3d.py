@@ -564,14 +564,17 @@ def test_negative_ray_start_epsilon_keeps_hits_just_behind_the_start():
         assert torch.equal(out[cls], ref[cls]), cls
 
 
-def test_non_finite_ray_gradient_poisons_the_same_entries_as_in_the_oracle():
+@pytest.mark.parametrize("deterministic", [False, True])
+def test_non_finite_ray_gradient_poisons_the_same_entries_as_in_the_oracle(deterministic):
     """optimizer.py:226-229 zeroes non-finite entries of the SUMMED parameter gradient: one ray
     with a NaN gradient must therefore poison every parameter it touches (and only those) -- the
     reverse sweep lets NaN through its sums instead of dropping the ray.  A NaN weight on one
-    finished ray's error term stands in for a degenerate ray."""
+    finished ray's error term stands in for a degenerate ray.  deterministic: the ordered sweep
+    carries the ray's non-finite terms as flag bytes beside its integer sums."""
     from tensorflowraytrace_amd import ops
     scene = scene_util.lens_scene(600, k_front=3, k_back=3)
     src, fv, sc, (p_f, p_b) = _gpu_scene(scene, torch.float64)
+    sc.deterministic = deterministic
     out = ops.trace3d(src, fv, sc, max_passes=4)
     fin, ids = out["finished"], out["finished_id"].long()
     assert fin.shape[1] > 400

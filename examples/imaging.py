@@ -64,6 +64,19 @@ its spot's centroid from the fitted image of its object point.  Every report pri
 magnification and the largest residual.
 
     python examples/imaging.py --distortion scale [--rays 20000] [--steps 30] [--generic]
+
+``--telecentric [WEIGHT]`` asks for an image-side telecentric lens: the MEAN direction of every
+object point's bundle must be the axis, while the cone of each point stays as wide as it is --
+``SumError([SpotError(("y_end", "z_end"), ...), CentroidError(("y_dir", "z_dir"), labels, domain,
+targets=zeros)], weights=[1, WEIGHT], reduce="mean")``.  (A ``SpotError`` on the directions would
+collimate the bundles, which is another objective.)  ``WEIGHT`` balances squared direction cosines
+-- 4e-5 per term for the flat starting lens -- against squared spot radii of order 1: the default
+is 1,000, and the step size is ``min(0.4, 100 / WEIGHT)``, because the term is stiff (at weight
+1,000 and the step 0.4 of the other sums the combined error grows; at weight 100 the step is
+stable, and the spot term wins: the lens focuses and the chief rays tilt).  The run prints the
+largest ``|mean direction cosine|`` over the object points before and after.
+
+    python examples/imaging.py --telecentric [WEIGHT] [--rays 20000] [--steps 30] [--generic]
 """
 import argparse
 import math
@@ -89,7 +102,10 @@ import tfrt.sources as sources                # noqa: E402
 LEARNING_RATE = 2e-5     # at 20,000 rays
 MEAN_LEARNING_RATE = 0.4  # --magnification: LEARNING_RATE * 20,000 rays * 2 terms per ray, halved
                           # because two terms pull
+TELECENTRIC_WEIGHT = 1000.0  # --telecentric: squared direction cosines against squared radii
+TELECENTRIC_STEP = 100.0    # --telecentric: the largest weight * learning rate that is stable
 FLAT_WEIGHT_CONES = 16.0  # --flat-field: the FlatFieldError's weight in units of sin(cone)^2
+HALF_DIRECTION = 0.5     # --telecentric: the (y_dir, z_dir) of a finished ray that counts
 HALF_DOMAIN = 3.0        # the target region: the unfocused cone of a ray bundle has radius ~1.6
 
 
@@ -124,7 +140,7 @@ def focus_spread(term):
 
 def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, target_distance=10.0,
           object_size=0.2, lens_aperature=1.0, apodize=None, magnification=None, focus=False,
-          distortion=None, flat_field=False, flat_weight=None):
+          distortion=None, flat_field=False, flat_weight=None, telecentric=None):
     points = letter_f(object_size)
     P = points.shape[0]
     A = max(ray_count // P, 2)
@@ -203,24 +219,37 @@ def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, target_dis
             ("y_end", "z_end"), labels, points[:, 1:],
             ((-HALF_DOMAIN, HALF_DOMAIN), (-HALF_DOMAIN, HALF_DOMAIN)), fit=distortion)
         error_function = optimizer.SumError([spot, distortion_term], reduce="mean")
+    tele_term = None
+    if telecentric is not None:
+        # one target per label: the mean (y_dir, z_dir) of every object point's bundle is 0
+        tele_term = optimizer.CentroidError(
+            ("y_dir", "z_dir"), labels,
+            ((-HALF_DIRECTION, HALF_DIRECTION), (-HALF_DIRECTION, HALF_DIRECTION)),
+            targets=np.zeros((P, 2)))
+        error_function = optimizer.SumError([spot, tele_term], weights=[1.0, float(telecentric)],
+                                            reduce="mean")
     return dict(engine=trace_engine, system=system, lens=lens, source=source, n_rays=n_rays,
                 n_points=P, error_function=error_function, spot=spot, accumulator=accumulator,
-                distortion=distortion_term, flat_field=flat_term)
+                distortion=distortion_term, flat_field=flat_term, telecentric=tele_term)
 
 
 def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=False, verbose=True,
         learning_rate=None, apodize=None, magnification=None, focus=False, distortion=None,
-        flat_field=False, flat_weight=None):
+        flat_field=False, flat_weight=None, telecentric=None):
     s = build(ray_count, lens_res_scale, apodize=apodize, magnification=magnification, focus=focus,
-              distortion=distortion, flat_field=flat_field, flat_weight=flat_weight)
+              distortion=distortion, flat_field=flat_field, flat_weight=flat_weight,
+              telecentric=telecentric)
     focus = focus or flat_field
     combined, erf = s["error_function"], s["spot"]
     if learning_rate is None:
         # (the error is a sum over the rays: the step size goes with 1 / rays)
         learning_rate = LEARNING_RATE * (20000 / s["n_rays"])
-        if magnification is not None or distortion is not None or flat_field:
+        if magnification is not None or distortion is not None or flat_field \
+                or telecentric is not None:
             # (a mean over two terms per ray: the same step per ray as the sum's)
             learning_rate = MEAN_LEARNING_RATE
+        if telecentric is not None and telecentric > 0.0:
+            learning_rate = min(MEAN_LEARNING_RATE, TELECENTRIC_STEP / telecentric)
     kw = dict(learning_rate=learning_rate, grad_clip=1.0, fused=False if generic else "auto")
     if adam:
         opt = optimizer.Adam_Optimizer(s["engine"], s["lens"].parameters, combined, 3,
@@ -228,8 +257,9 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=Fals
     else:
         opt = optimizer.SGD_Optimizer(s["engine"], s["lens"].parameters, combined, 3, **kw)
     opt.suppress_warnings = True
-    rms, times, errors, place, fits, spreads = [], [], [], [], [], []
-    summed = magnification is not None or distortion is not None or flat_field
+    rms, times, errors, place, fits, spreads, tilts = [], [], [], [], [], [], []
+    summed = magnification is not None or distortion is not None or flat_field \
+        or telecentric is not None
     for step in range(steps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -253,6 +283,10 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=Fals
         if flat_field:
             # (read outside the timed part of the step)
             spreads.append(focus_spread(s["flat_field"]))
+        if telecentric is not None:
+            # (read outside the timed part of the step)
+            c = s["telecentric"].centroids()
+            tilts.append(float(c[torch.isfinite(c).all(dim=1)].abs().max()))
         if verbose and (step % 5 == 0 or step == steps - 1):
             extra = "" if magnification is None else \
                 f"  mean squared image distance {place[-1]:.6g}  combined {mean:.6g}"
@@ -269,11 +303,15 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=Fals
             if flat_field:
                 extra = (f"  mean squared distance to the plane {place[-1]:.6g}  combined "
                          f"{mean:.6g}  spread of the foci {spreads[-1]:.6g}")
+            if telecentric is not None:
+                extra = (f"  mean squared mean direction {place[-1]:.6g}  combined {mean:.6g}  "
+                         f"largest |mean direction cosine| {tilts[-1]:.6g}")
             what = "rms distance to the focus" if focus else "rms spot"
             print(f"step {step:4d}: {what} {rms[-1]:.6g}{extra}  ({inside} rays inside, "
                   f"{1e3 * times[-1]:.2f} ms)")
     fused = opt._fused_step
     s.update(rms=rms, times=times, errors=errors, place=place, fits=fits, spreads=spreads,
+             tilts=tilts,
              graph_replays=0 if fused is None else fused.graph_replays,
              centroids=erf.foci() if focus else erf.centroids())
     return s
@@ -304,6 +342,12 @@ if __name__ == "__main__":
                     choices=("scale", "affine"),
                     help="SumError([SpotError, DistortionError]): an undistorted image at a free "
                          "magnification (scale) or under a free 2 x 2 matrix (affine)")
+    ap.add_argument("--telecentric", nargs="?", type=float, const=TELECENTRIC_WEIGHT, default=None,
+                    metavar="WEIGHT",
+                    help="SumError([SpotError, CentroidError((y_dir, z_dir), targets=0)]): the mean "
+                         "direction of every object point's bundle along the axis (default "
+                         f"WEIGHT {TELECENTRIC_WEIGHT:g}; the step is min({MEAN_LEARNING_RATE}, "
+                         f"{TELECENTRIC_STEP:g} / WEIGHT))")
     a = ap.parse_args()
     if a.focus and (a.apodize is not None or a.magnification is not None):
         ap.error("--focus takes neither --apodize nor --magnification")
@@ -312,9 +356,16 @@ if __name__ == "__main__":
     if a.flat_field and (a.apodize is not None or a.magnification is not None
                          or a.distortion is not None):
         ap.error("--flat-field takes neither --apodize nor --magnification nor --distortion")
+    if a.telecentric is not None:
+        if a.focus or a.flat_field or a.magnification is not None or a.distortion is not None:
+            ap.error("--telecentric takes none of --focus, --flat-field, --magnification and "
+                     "--distortion")
+        if not (a.telecentric >= 0.0 and math.isfinite(a.telecentric)):
+            ap.error("--telecentric WEIGHT must be finite and >= 0")
     out = run(a.rays, a.steps, a.edge, generic=a.generic, adam=a.adam, learning_rate=a.lr,
               apodize=a.apodize, magnification=a.magnification, focus=a.focus,
-              distortion=a.distortion, flat_field=a.flat_field, flat_weight=a.flat_weight)
+              distortion=a.distortion, flat_field=a.flat_field, flat_weight=a.flat_weight,
+              telecentric=a.telecentric)
     tail = sorted(out["times"][len(out["times"]) // 2:])
     print(f"{out['n_points']} object points, {out['n_rays']} rays; steps replayed from the graph: "
           f"{out['graph_replays']} of {a.steps}; median step of the second half: "
@@ -349,3 +400,9 @@ if __name__ == "__main__":
         print(f"mean squared image distance: first {out['place'][0]:.6g} last "
               f"{out['place'][-1]:.6g}")
         print(f"combined error: first {out['errors'][0]:.6g} last {out['errors'][-1]:.6g}")
+    if a.telecentric is not None:
+        print(f"mean squared mean direction: first {out['place'][0]:.6g} last "
+              f"{out['place'][-1]:.6g}")
+        print(f"combined error: first {out['errors'][0]:.6g} last {out['errors'][-1]:.6g}")
+        print(f"largest |mean direction cosine| over {out['n_points']} object points: first "
+              f"{out['tilts'][0]:.6g} last {out['tilts'][-1]:.6g}")

@@ -1012,6 +1012,79 @@ int tfrt_distortion_error(const void* rows, int64_t stride, int64_t n, int32_t s
                           double* residual, int64_t* acc, int32_t variant, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* CentroidError: the CENTROID of every group of rays must lie at a given target, or the centroids
+ * of the groups of one parent must coincide, wherever they do -- telecentricity and prescribed
+ * chief-ray angles, a prescribed image height per object point, registration (lateral colour, the
+ * overlap of several beams).  It does not charge the spread of a group.  The error is the sum over
+ * the rays inside of the squared distance of their GROUP'S CENTROID from its target, plus
+ * tfrt_spot_error's penalty for rays outside the domain.  Four launches with `targets` (clear
+ * `acc`, tfrt_spot_error's unweighted accumulate launch, table, seed), five with `parents` (clear
+ * `acc` and `parent_acc` in one launch, accumulate, the parents' records, table, seed); no host
+ * read, no allocation, no float atomics: captured with the rest of a step.
+ *
+ * The columns, the fields and their codes, the four cases of a counting column in their order, the
+ * out-of-domain penalty and its gradient, the records {count, Sx, Sy, 0} with `qbits` and qsx, qsy,
+ * terms = k * (number of counting columns) and the chain rule of a direction field are exactly
+ * tfrt_spot_error_fields'.  Every operation below is an IEEE f64 operation rounded on its own (no
+ * contraction).  With one field the y component of every centroid and target is 0.0 and the same
+ * expressions run.
+ *
+ * A group g HAS RAYS iff count_g > 0: w_g = (double) count_g,
+ *   cx_g = x0 + ((double) Sx_g / w_g) / qsx,  cy_g = y0 + ((double) Sy_g / w_g) / qsy.
+ * Exactly one of `targets` and `parents` is given (TFRT_E_BADARG otherwise).
+ *   targets   t_g = row g of `targets`; the group HAS A TARGET iff every entry of the row is finite
+ *             (a NaN says "not pinned").
+ *   parents   p = parents[g]; the group HAS A TARGET iff 0 <= p < n_parents.  The record of parent
+ *             p is the INTEGER sum {count, Sx, Sy} of the records of its groups that have rays and
+ *             a target (int64 atomics: integer addition is associative, any order gives the same
+ *             bits; the sums are bounded by those over all n rays, which the records are sized
+ *             for).  C_p is formed from the parent's record by the expression of a centroid, and
+ *             t_g = C_parents[g].
+ * A group is USED iff it has rays and has a target:
+ *   rx = cx_g - tx_g,  ry = cy_g - ty_g,  and it adds  w_g * (rx * rx)  and  w_g * (ry * ry).
+ * The residual table: {rx, ry} of a used group; {0.0, 0.0} for a group with rays that is not used;
+ * {NaN, NaN} for a group without rays (no ray reads it).
+ *   error = (sum w * (rx * rx) + sum w * (ry * ry)) + the sum of the penalties,
+ *   error_out = {error, terms, error / terms (NaN with no counting column)}.
+ * A ray inside gets the gradient 2.0 * rx and 2.0 * ry of its own group (chained onto the start
+ * and end rows with a direction field, as the spot seed; all 2 d rows of every column are then
+ * written); a ray outside the penalty's derivative; every other ray zeros.  That is the exact
+ * gradient up to the quantisation of the records, without a derivative of a centroid: with
+ * d c_g / d x_i = 1 / count_g, d/dx_i of count_g |c_g - t_g|^2 is 2 r_g; and C_p is the weighted
+ * mean of its groups' centroids, which minimises sum_g count_g |c_g - C|^2, so the derivative
+ * through C_p drops out.
+ * Every float sum over the groups has tfrt_distortion_error's fixed shape and order: thread j of
+ * the one workgroup of B = 1,024 threads takes the groups j, j + B, j + 2B, ... in ascending order,
+ * starting from 0.0 and skipping groups that are not used; the threads are combined within each
+ * 64-lane wave by v += v[lane ^ d] for d = 32, 16, 8, 4, 2, 1, then the 16 waves in index order
+ * starting from 0.0.  The penalty and count partials of the accumulate launch are summed the same
+ * way, in index order.  Two runs give the same bits.
+ *
+ *   targets      n_groups rows of k f64 (k = the number of fields), on the device, or NULL; read
+ *                by the table launch, so overwriting it between replays of a captured step is seen
+ *   parents      n_groups int32 on the device, or NULL; read by the launches, overwritable alike
+ *   n_parents    1 .. 2^20 with `parents` (ignored with `targets`)
+ *   parent_acc   n_parents records of four int64 {count, Sx, Sy, 0}, cleared and filled by this
+ *                call; required with `parents` (ignored with `targets`)
+ *   used_out     2 f64 {groups used, parents with rays (0.0 with `targets`)}
+ *   residual     n_groups rows of two f64 {rx, ry}, 16-byte aligned
+ *   acc          n_groups records of four int64 {count, Sx, Sy, 0}, cleared and filled by this call
+ *   variant      tfrt_spot_error's
+ *   workspace    tfrt_centroid_error_workspace_bytes(n, n_groups) bytes (0: bad arguments)
+ * Everything else as for tfrt_spot_error_fields.  Bad arguments are refused with TFRT_E_BADARG /
+ * TFRT_E_WORKSPACE before any launch.
+ */
+size_t tfrt_centroid_error_workspace_bytes(int64_t n, int32_t n_groups);
+int tfrt_centroid_error(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                        int32_t dimension, const int32_t* mask, int32_t field_x, int32_t field_y,
+                        const int32_t* group, int64_t n_source, const int32_t* perm,
+                        int32_t n_groups, const double* targets, const int32_t* parents,
+                        int32_t n_parents, int64_t* parent_acc, double x0, double x1, double qsx,
+                        double y0, double y1, double qsy, int32_t qbits, double oob_weight,
+                        double* grad, int64_t grad_stride, double* error_out, double* used_out,
+                        double* residual, int64_t* acc, int32_t variant, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* FlatFieldError: the foci of all groups must lie in ONE plane with the unit normal a = `axis` --
  * wherever along the normal that plane has to stand.  The error is the sum, over the counting rays
  * of the groups with a focus, of the squared distance of their group's focus from that plane, in

@@ -39,6 +39,32 @@ __device__ __forceinline__ V error_block_sum(V v, V* wsum) {
   return s;
 }
 
+// error_block_sum's sum -- the same butterflies inside the wave, the waves in index order from 0,
+// the same bits -- with the sum over the waves made by thread 0 alone and handed round through
+// `total` (one V in LDS).  Every thread still gets the sum; what changes is where the compiler may
+// put the work.  In a kernel that makes several sums of which only thread 0 uses the result
+// (k_centroid_table: five), error_block_sum's NW loads per sum stayed live in registers until the
+// kernel's last block, because the adds were sunk into it: 126 registers and 276 bytes of scratch
+// there; the store of the total ends every sum where it stands (42 registers, no scratch).  Every
+// thread of the workgroup must call it.  `wsum` and `total` may be reused by the next call: that
+// call writes `wsum` only in front of its first barrier, which every thread reaches after it has
+// read `total` here, and thread 0 writes `total` only behind it.
+template <int NW, typename V>
+__device__ __forceinline__ V error_block_total(V v, V* wsum, V* total) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+  if (lane_id() == 0) wsum[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    V s = 0;
+    for (int w = 0; w < NW; ++w) s += wsum[w];
+    *total = s;
+  }
+  __syncthreads();
+  return *total;
+}
+
 // The table (the histogram, the records of every group), cleared in front of the adds.  A launch,
 // not a memset node: replayed inside a step's graph, a memset node in this place left the 896
 // bytes of the imaging example's 28 records uncleared (every count came back as a stale word plus

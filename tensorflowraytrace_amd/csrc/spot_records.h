@@ -1,8 +1,8 @@
-// The group records of SpotError, shared by the files that fill them (tfrt_spot.hip and
-// tfrt_distortion.hip): the constants of a launch, the layout of a record, the classification of
-// a column and the accumulate launch -- {1, qx, qy} (weighted: the limbs) into the record of the
-// ray's group, the out-of-domain penalty and the number of counting columns as one partial per
-// workgroup.  The definition is in include/tfrt_hip.h at tfrt_spot_error; the launches are
+// The group records of SpotError, shared by the files that fill them (tfrt_spot.hip,
+// tfrt_distortion.hip and tfrt_centroid.hip): the constants of a launch, the layout of a record,
+// the classification of a column and the accumulate launch -- {1, qx, qy} (weighted: the limbs)
+// into the record of the ray's group, the out-of-domain penalty and the number of counting columns
+// as one partial per workgroup.  The definition is in include/tfrt_hip.h at tfrt_spot_error; the launches are
 // described at the top of tfrt_spot.hip.  Templates only, so that each file that launches them
 // carries its own instantiations (as k_error_clear of error_sums.h).
 #pragma once

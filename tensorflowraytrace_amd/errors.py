@@ -17,17 +17,19 @@ space -- ``tfrt_focus_error`` (clear, accumulate, solve, seed, finish); a ``Dist
 the groups' centroids must be a scaled or affine copy of the object points --
 ``tfrt_distortion_error`` (clear, SpotError's accumulate, fit, seed); a ``FlatFieldError`` -- the
 foci of all groups must lie in one plane with a given normal -- ``tfrt_flatfield_error`` (clear,
-FocusError's accumulate, fit, seed).  A ``SumError`` is a
-weighted sum of such terms and of ``GoalError``s: every term's launches into a seed block of its
-own (a ``GoalError`` through ``tfrt_goal_error_columns``), then ONE ``tfrt_error_combine`` for the
-step's seed block and error.
+FocusError's accumulate, fit, seed); a ``CentroidError`` -- every group's centroid must lie at a
+given target, or the centroids of the groups of one parent must coincide --
+``tfrt_centroid_error`` (clear, SpotError's accumulate, with parents their records, table, seed).
+A ``SumError`` is a weighted sum of such terms and of ``GoalError``s: every term's launches into a
+seed block of its own (a ``GoalError`` through ``tfrt_goal_error_columns``), then ONE
+``tfrt_error_combine`` for the step's seed block and error.
 
 Each is an ordinary error function (``__call__(engine)``): the generic path gives the same
 numbers, which is what the parity tests compare.
 
 The protocol between a built-in term (``GoalError``, ``DensityError``, ``SpotError``,
-``TransportError``, ``FocusError``, ``DistortionError``, ``FlatFieldError``) and the fused 3-D
-step:
+``TransportError``, ``FocusError``, ``DistortionError``, ``FlatFieldError``, ``CentroidError``)
+and the fused 3-D step:
 
 * ``rows``, ``fields``, ``rows_for(dimension)``: the rows of the ray block (the field codes) the
   term reads;
@@ -1487,6 +1489,278 @@ class _DistortionTerms(torch.autograd.Function):
         return (upstream[:, 0] * grad).to(ctx.dtype), None, None, None, None, None
 
 
+class CentroidError(_CoupledError):
+    """Where the CENTROID of a group of rays lies, without charging the spread of the group.  A
+    ``GoalError`` pins every ray, so it charges spot size with position; a ``SpotError`` charges
+    the spread alone; a ``DistortionError`` moves centroids towards a fitted copy of the object,
+    scale and offset free.  Here every group's centroid is pinned to a target given in advance
+    (``targets``) -- telecentricity or a prescribed chief-ray angle with direction fields (the
+    MEAN direction of a bundle, its cone as wide as it is), a prescribed image height (f-theta,
+    a fisheye law), a magnification without pulling against the spot term -- or the centroids of
+    several groups are registered onto each other, wherever they meet (``parents``): the lateral
+    colour of an object point (one group per wavelength band), the overlap of several emitters'
+    beams, "all chief rays parallel, whatever the direction".
+
+    ``fields``, ``groups``, ``domain``, ``oob_weight`` and ``n_groups`` are exactly
+    ``DistortionError``'s: one or two fields (positions or direction cosines), one label per
+    SOURCE ray (or a callable with ``n_groups``), kept as int32 on the device and overwritable
+    between replays, the label ``-1`` excludes a ray, rays outside the closed domain take the
+    penalty ``oob_weight * (ex**2 + ey**2)`` and are in no group.  There are no ``weights``.
+    Giving both ``targets`` and ``parents`` is a ``ValueError``.
+
+    * ``targets``: (G, k) floats (or (G,) with one field), kept as float64 on the device
+      (``self.targets``, moved once) and overwritable in place between replayed steps; the
+      buffer's address is part of ``graph_key()``.  A row with a NaN leaves that group unpinned
+      (no error, zero gradient for its rays inside the domain); infinite entries are refused.
+    * ``parents``: (G,) integers, kept as int32 on the device (``self.parents``), overwritable in
+      place, its address in the graph key.  ``n_parents`` defaults to ``max + 1`` (at least 1),
+      read once, 1 .. ``ops.SPOT_MAX_GROUPS``.  A group whose parent label lies outside
+      ``[0, n_parents)`` is left out.
+    * neither: one parent for all groups -- all centroids must coincide.
+
+    For every finished ray, the four cases of ``SpotError`` in its order; a ray inside enters its
+    group's record ``{count, Sx, Sy, 0}`` with the same ``qbits`` and ``qsx``.  Every float64
+    operation is rounded on its own; with one field the y components are 0.0
+    (include/tfrt_hip.h, tfrt_centroid_error):
+
+    * a group with ``count > 0`` has rays: ``w = count``, ``c = x0 + (Sx / count) / qsx`` as
+      ``SpotError`` computes it;
+    * with ``parents`` the record of parent p is the INTEGER sum of the records of its groups
+      that have rays and a legal label, ``C_p`` is formed from it by the same expression, and
+      ``t_g = C_parent(g)``; with ``targets`` ``t_g = targets[g]``;
+    * a group is USED if it has rays and a target (a finite row; a legal label):
+      ``r = c - t``, ``e_g = w * (rx * rx)`` and ``w * (ry * ry)``;
+    * the residual table is ``r`` for a used group, 0.0 for one with rays that is not used, NaN
+      for one without rays;
+    * ``error = (sum w rx**2 + sum w ry**2) + penalties`` over ``len(fields) * n_finished``
+      terms, the sums over the groups in ``DistortionError``'s fixed shape and order: two runs
+      give the same bits;
+    * a ray inside gets the gradient ``2 rx``, ``2 ry`` of its group (chained onto start and end
+      rows with a direction field, as ``SpotError``'s), a ray outside the penalty's derivative,
+      every other ray zeros.  That is the exact gradient up to the quantisation of the records,
+      and no centroid is differentiated: with ``targets``, ``d/dx_i`` of ``count_g |c_g -
+      t_g|**2`` is ``2 r_g`` because ``d c_g / d x_i = 1 / count_g``; with ``parents``, ``C_p``
+      minimises the sum of its groups' terms, so its derivative drops out.
+
+    It is an ordinary ``error_function(engine)`` (the generic path: ``ops.centroid_error`` over
+    the finished rays' columns under a ``torch.autograd.Function`` that returns the (n_finished,
+    k) terms -- a ray inside carries its group's ``rx**2``, ``ry**2``), which also serves sources
+    that are not traced in place, ``deterministic=True``, fewer than 4,096 rays, several ranks
+    and 2-D engines.  Its ``backward`` returns ``upstream * gradient``, exact when ``upstream`` is
+    constant (the optimiser passes ones); with a direction field both fields of a ray must carry
+    the same factor.  On a 3-D engine that traces its source in place the optimiser runs it on
+    the fused, graph-replayed step wherever a ``SpotError`` runs there (``FusedStep._rowwise3d``
+    with ``tfrt_centroid_error``: clear, accumulate, [parents,] table, seed), and it is a legal
+    term of a ``SumError``.
+
+    ``last_acc`` is the (G, 4) int64 record table of the last evaluation, ``centroids()`` the
+    (G, k) centroids made from it, ``residuals()`` the (G, k) residuals, ``parent_centroids()``
+    the (P, k) common centroids (``parents`` mode), ``groups_used`` the number of used groups
+    (read from the device).  ``splat_variant`` is ``SpotError``'s."""
+
+    splat_variant = 0
+
+    def __init__(self, fields, groups, domain, targets=None, parents=None, oob_weight=0.0,
+                 n_groups=None, n_parents=None):
+        from . import config
+        what = "CentroidError"
+        self.fields, self.domain = _fields_and_domain(what, fields, domain)
+        self.rows = [_FIELDS3.index(f) for f in self.fields]
+        self.has_direction = any(f.endswith("_dir") for f in self.fields)
+        self.oob_weight = float(oob_weight)
+        if not (self.oob_weight >= 0.0 and np.isfinite(self.oob_weight)):
+            raise ValueError(f"{what}: oob_weight must be finite and >= 0")
+        if targets is not None and parents is not None:
+            raise ValueError(f"{what}: give targets or parents, not both")
+        _init_groups(self, what, groups, n_groups, ops.SPOT_MAX_GROUPS)
+        G, k = self.n_groups, len(self.fields)
+        dev = config.get_device()
+        self.targets = self.parents = None
+        self.n_parents = 0
+        if targets is not None:
+            if n_parents is not None:
+                raise ValueError(f"{what}: n_parents goes with parents, not with targets")
+            try:
+                t = targets.detach().cpu().numpy() if isinstance(targets, torch.Tensor) \
+                    else np.asarray(targets)
+                t = np.ascontiguousarray(t, dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"{what}: targets must be numbers of shape ({G}, {k})") from e
+            if t.ndim == 1 and k == 1:
+                t = t[:, None]
+            if t.shape != (G, k):
+                raise ValueError(f"{what}: targets must have shape (n_groups, fields) = "
+                                 f"({G}, {k}), got {t.shape}")
+            if np.isinf(t).any():
+                bad = np.nonzero(np.isinf(t).any(axis=1))[0][:5].tolist()
+                raise ValueError(f"{what}: targets must be finite, or NaN for a group that is "
+                                 f"not pinned; rows {bad} are infinite")
+            self.targets = torch.as_tensor(t).to(dev)
+        else:
+            if parents is None:
+                p = torch.zeros(G, dtype=torch.int32)
+            else:
+                p = parents if isinstance(parents, torch.Tensor) \
+                    else torch.as_tensor(np.asarray(parents))
+                if p.dim() != 1 or p.dtype.is_floating_point or p.dtype.is_complex \
+                        or p.dtype == torch.bool or p.shape[0] != G:
+                    raise ValueError(f"{what}: parents must be integers of shape (n_groups,) = "
+                                     f"({G},); got shape {tuple(p.shape)}, {p.dtype}")
+                p = p.detach().to(dtype=torch.int32)
+            if n_parents is None:
+                n_parents = max(int(p.max()) + 1, 1)
+            try:
+                self.n_parents = int(n_parents)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"{what}: n_parents must be an integer, got {n_parents!r}") from e
+            if not 1 <= self.n_parents <= ops.SPOT_MAX_GROUPS:
+                raise ValueError(f"{what}: n_parents must lie in 1 .. {ops.SPOT_MAX_GROUPS}, got "
+                                 f"{n_parents!r}")
+            self.parents = p.to(dev).contiguous()
+        self._grids = {}
+        self.last_acc = self.last_grid = self.last_qbits = None
+        self.last_residual = self.last_used = self.last_parent_acc = None
+
+    def labels_of(self, src):
+        """The int32 label buffer of the source set ``src`` on its device, one label per source
+        ray, given or computed and cached as ``SpotError.labels_of`` does."""
+        return _source_buffer(self, "labels", self.groups,
+                              lambda v, dev: _as_labels("CentroidError", v, dev), src,
+                              "CentroidError", "label")
+
+    grid_for = SpotError.grid_for      # (the records are SpotError's: the same qbits and grid)
+
+    def _mode_on(self, device):
+        """(targets, parents) on ``device`` (moved once; a new buffer re-captures a graph)."""
+        name = "targets" if self.targets is not None else "parents"
+        if getattr(self, name).device != device:
+            setattr(self, name, getattr(self, name).to(device))
+        return self.targets, self.parents
+
+    def graph_key(self):
+        """What a captured step has baked in: the addresses of the label buffer and of the
+        ``targets`` or ``parents`` buffer, and the constants."""
+        lab = self.labels
+        mode = self.targets if self.targets is not None else self.parents
+        return (None if lab is None else (lab.data_ptr(), tuple(lab.shape)), self.n_groups,
+                self.domain, self.oob_weight, self.splat_variant, self.targets is not None,
+                mode.data_ptr(), self.n_parents)
+
+    def evaluate(self, rows, row_x, row_y, labels, mask=None, perm=None, dimension=None,
+                 **buffers):
+        """``ops.centroid_error`` of the columns of ``rows`` with these labels, targets or
+        parents and domain (``dimension`` given: ``rows`` is the geometry block, ``row_x`` /
+        ``row_y`` field codes)."""
+        qbits, grid = self.grid_for(labels.numel())
+        targets, parents = self._mode_on(rows.device)
+        out = ops.centroid_error(rows, row_x, row_y, labels, self.n_groups, grid, targets=targets,
+                                 parents=parents,
+                                 n_parents=None if parents is None else self.n_parents,
+                                 oob_weight=self.oob_weight, mask=mask, perm=perm,
+                                 variant=self.splat_variant, qbits=qbits, dimension=dimension,
+                                 **buffers)
+        self.last_acc, self.last_grid, self.last_qbits = out[2], grid, qbits
+        self.last_residual, self.last_used, self.last_parent_acc = out[3], out[4], out[5]
+        return out
+
+    def seed_columns(self, cols, hold):
+        """tfrt_centroid_error on the step's columns: labels through the trace's order inside the
+        kernels, as a SpotError; the records go into ``hold.buffers["acc"]``, (G, 4), the residual
+        table into ``["residual"]``, (G, 2), the counts into ``["used_out"]``, (2,), and with
+        parents their records into ``["parent_acc"]``, (P, 4)."""
+        labels = self.labels_of(cols.src)
+        G, P = self.n_groups, self.n_parents
+        dev = cols.rows.device
+        held = self._held(hold, "acc", (G, 4), torch.int64, dev,
+                          lambda: _lib.lib().tfrt_centroid_error_workspace_bytes(cols.n, G))
+        by_parent = self.parents is not None
+        if "residual" not in held or ("parent_acc" in held) != by_parent \
+                or (by_parent and held["parent_acc"].shape[0] != P):
+            held.pop("parent_acc", None)
+            held["residual"] = torch.zeros((G, 2), dtype=torch.float64, device=dev)
+            held["used_out"] = torch.zeros(2, dtype=torch.float64, device=dev)
+            if by_parent:
+                held["parent_acc"] = torch.zeros((P, 4), dtype=torch.int64, device=dev)
+        self.evaluate(cols.rows, *_xy(self.rows), labels, mask=cols.mask, perm=cols.perm,
+                      dimension=3, grad=hold.g_fin, err=hold.err, **held)
+
+    def _last(self, name):
+        value = getattr(self, name)
+        if value is None:
+            raise RuntimeError("CentroidError: no evaluation yet")
+        return value
+
+    def centroids(self):
+        """(G, k) float64 centroids of the last evaluation, NaN for a group without rays."""
+        return ops.spot_centroids(self._last("last_acc"), self.last_grid, len(self.fields),
+                                  self.last_qbits)
+
+    def residuals(self):
+        """(G, k) float64 residuals ``c - t`` of the last evaluation: NaN for a group without
+        rays, zeros for a group with rays and no target."""
+        return self._last("last_residual")[:, :len(self.fields)]
+
+    def parent_centroids(self):
+        """(P, k) float64 common centroids of the last evaluation (``parents`` mode), NaN for a
+        parent without rays."""
+        if self.parents is None:
+            raise RuntimeError("CentroidError: parent_centroids() needs parents, not targets")
+        return ops.centroid_parent_centroids(self._last("last_parent_acc"), self.last_grid,
+                                             len(self.fields))
+
+    @property
+    def groups_used(self):
+        """The number of used groups of the last evaluation, read from the device."""
+        return int(self._last("last_used")[0])
+
+    def __call__(self, engine):
+        """The (n_finished, k) error terms through the generic path; the gradient rows come back
+        in ``backward``."""
+        codes = self.rows_for(engine.dimension)
+        fin = engine.finished_rays
+        if not bool(fin):
+            return torch.zeros((0, len(self.fields)), dtype=torch.float64)
+        labels = self.labels_of(engine._trace_src)
+        block, _, ids, dim, codes = self._finished_block(engine, fin, codes, ids=True)
+        return _CentroidTerms.apply(block, self, labels, ids, dim, codes)
+
+
+class _CentroidTerms(torch.autograd.Function):
+    """CentroidError over the finished rays, no mask; ``ids``: the source ray of every column;
+    ``block``, ``dimension`` and ``codes`` as for ``_SpotTerms``.  Returns the (n, k) terms: a
+    penalised ray's ``oob_weight * ex**2`` per field, an inside ray's squared residuals of its
+    GROUP (their sum over the rays is the groups' ``w * r**2``), zeros for the rest."""
+
+    @staticmethod
+    def forward(ctx, block, erf, labels, ids, dimension=None, codes=None):
+        rows = block.detach().contiguous()
+        ctx.chained = codes is not None
+        if codes is None:
+            codes = (0, 1)[:rows.shape[0]]
+        _, grad, acc, residual = erf.evaluate(rows, *_xy(codes), labels, perm=ids,
+                                              dimension=dimension)[:4]
+        ctx.save_for_backward(grad)
+        ctx.dtype = block.dtype
+        if ctx.chained:
+            link = ops._link_torch(rows, dimension)
+            v = torch.stack([ops._link_field_torch(link, c, dimension) for c in codes], dim=0)
+        else:
+            v = rows.double()
+        s = ids.long().clamp(0, labels.numel() - 1)
+        r = residual[labels[s].long().clamp(0, erf.n_groups - 1), :v.shape[0]].t()
+        return _spot_terms(erf, v, labels, ids, acc, None, inside=r * r)
+
+    @staticmethod
+    def backward(ctx, upstream):
+        grad, = ctx.saved_tensors
+        if not ctx.chained:
+            return (upstream.t() * grad).to(ctx.dtype), None, None, None, None, None
+        if upstream.shape[1] == 2 and not torch.equal(upstream[:, 0], upstream[:, 1]):
+            raise ValueError("CentroidError with a direction field: the upstream gradient must "
+                             "weigh both fields of a ray alike")
+        return (upstream[:, 0] * grad).to(ctx.dtype), None, None, None, None, None
+
+
 class FlatFieldError(FocusError):
     """The foci of all groups must lie in ONE plane with the normal ``axis`` -- a flat field --,
     wherever along the normal that plane has to stand: the sum, over the finished rays that count,
@@ -1644,7 +1918,8 @@ class _FlatFieldTerms(torch.autograd.Function):
 
 
 # the coupled errors: all finished rays of a step enter one evaluation (one process)
-_COUPLED = (DensityError, SpotError, TransportError, FocusError, DistortionError, FlatFieldError)
+_COUPLED = (DensityError, SpotError, TransportError, FocusError, DistortionError, FlatFieldError,
+            CentroidError)
 
 
 class SumError:
@@ -1655,8 +1930,8 @@ class SumError:
     step is one trace, K error evaluations, one combination and one reverse sweep.
 
     ``terms``: 1 to 8 distinct instances of ``GoalError``, ``DensityError``, ``SpotError``,
-    ``TransportError``, ``FocusError``, ``DistortionError`` or ``FlatFieldError``; a
-    ``RowwiseError``, a nested ``SumError`` or the same object twice is a ValueError.  ``weights``: K finite values >= 0, default all ones, kept as the (K,) float64
+    ``TransportError``, ``FocusError``, ``DistortionError``, ``FlatFieldError`` or
+    ``CentroidError``; a ``RowwiseError``, a nested ``SumError`` or the same object twice is a ValueError.  ``weights``: K finite values >= 0, default all ones, kept as the (K,) float64
     device tensor ``weights``; ``set_weights(values)`` validates on the host and overwrites that
     buffer in place, so a replayed graph sees the new values without a re-capture (as
     ``TransportError.set_goal``).  A weight of 0 switches a term off for a phase; the term is
@@ -1699,8 +1974,8 @@ class SumError:
                                  "code of its own); state it as a GoalError")
             if not isinstance(t, (GoalError,) + _COUPLED):
                 raise ValueError("SumError: terms must be GoalError, DensityError, SpotError, "
-                                 "TransportError, FocusError, DistortionError or FlatFieldError "
-                                 "instances, got "
+                                 "TransportError, FocusError, DistortionError, FlatFieldError or "
+                                 "CentroidError instances, got "
                                  f"{type(t).__name__}")
         if len(set(id(t) for t in terms)) != len(terms):
             raise ValueError("SumError: the same term object is listed twice (a term keeps the "

@@ -1818,6 +1818,9 @@ def _transport_error_cpu(rows, row_x, row_y, tables, grid, angles, mask, grad, e
 
 SPOT_MAX_GROUPS = 1 << 20
 SPOT_LDS_GROUPS = 1024
+SPOT_MAX_GRID = 512                # workgroups of the accumulate launch (spot_records.h) ...
+SPOT_RAYS_PER_BLOCK = 4 * 256      # ... one per that many columns
+DISTORTION_SEED_MAX_GRID = 2048    # workgroups of 256 lanes of k_distortion_seed (residual_seed.h)
 SPOT_WEIGHTED_LDS_GROUPS = 512     # tfrt_spot_error_weighted: six planes, the same 24 KiB
 SPOT_MAX_WBITS = 20
 
@@ -2207,6 +2210,194 @@ def _distortion_error_cpu(rows, row_x, row_y, group, n_groups, points, grid, fit
     fit, res, e_inside = _distortion_fit_cpu(acc, points, grid, two, fit_kind, min_cond)
     fit_out.copy_(fit)
     residual.copy_(res)
+    gx[inside] = 2.0 * res[li, 0]
+    if two:
+        gy[inside] = 2.0 * res[li, 1]
+    _write_grad_cpu(grad, n, dimension, row_x, row_y, gx, gy, link, spot)
+    e = e_inside + pen
+    n_terms = float(int(counting.sum()) * (2 if two else 1))
+    err[0], err[1] = e, n_terms
+    err[2] = e / n_terms if n_terms > 0 else float("nan")
+
+
+# ----------------------------------------- group centroids at targets, or registered by parent
+def centroid_error(rows, row_x, row_y, group, n_groups, grid, targets=None, parents=None,
+                   n_parents=None, oob_weight=0.0, mask=None, perm=None, grad=None, err=None,
+                   acc=None, residual=None, used_out=None, parent_acc=None, variant=0,
+                   workspace=None, qbits=None, dimension=None):
+    """tfrt_centroid_error: the CentroidError of the columns of ``rows`` -- the centroid of every
+    group must lie at its row of ``targets`` (G, k) float64 (a row with a non-finite entry: not
+    pinned), or the centroids of the groups with the same entry of ``parents`` (G,) int32 must
+    coincide (an entry outside ``[0, n_parents)``: left out).  Exactly one of the two is given.
+    The columns, ``row_x`` / ``row_y``, ``group``, ``perm``, ``n_groups``, ``grid``
+    (``spot_grid``), ``qbits``, ``mask``, ``oob_weight``, ``variant`` and ``dimension`` are
+    ``spot_error``'s.  Returns (err {sum, terms, mean}, grad, acc (G, 4) int64 {count, Sx, Sy, 0},
+    residual (G, 2) float64 -- ``c - t`` of a used group, 0 for a group with rays and no target,
+    NaN for a group without rays --, used_out (2,) float64 {groups used, parents with rays},
+    parent_acc (P, 4) int64, the parents' records (None with ``targets``)).  ``grad``, ``err``,
+    ``acc``, ``residual``, ``used_out``, ``parent_acc``, ``workspace`` (uint8): buffers to reuse
+    -- with all of them given a CUDA call allocates nothing.
+
+    CUDA tensors run the kernels.  CPU tensors run a torch restatement with the same int64 fixed
+    point, the same operations per group and the same order of the sums over the groups (``acc``,
+    ``parent_acc``, ``residual`` and the gradient rows agree bit for bit; the penalty sum is
+    torch's and agrees to rounding)."""
+    what = "centroid_error"
+    n_groups = int(n_groups)
+    if group.dtype != torch.int32 or group.dim() != 1 or not group.is_contiguous():
+        raise ValueError(f"{what}: group must be a contiguous int32 vector, one label per "
+                         "source ray")
+    if not 1 <= n_groups <= SPOT_MAX_GROUPS:
+        raise ValueError(f"{what}: n_groups must lie in 1 .. {SPOT_MAX_GROUPS}")
+    if (targets is None) == (parents is None):
+        raise ValueError(f"{what}: exactly one of targets and parents must be given")
+    n = rows.shape[1]
+    _check_field_codes(what, rows, row_x, row_y, dimension)
+    k = 2 if row_y >= 0 else 1
+    if targets is not None:
+        if targets.dtype != torch.float64 or tuple(targets.shape) != (n_groups, k) \
+                or not targets.is_contiguous() or targets.device != rows.device:
+            raise ValueError(f"{what}: targets must be contiguous float64 of shape (n_groups, "
+                             f"{k}) on the rows' device")
+        n_parents = 0
+    else:
+        if parents.dtype != torch.int32 or tuple(parents.shape) != (n_groups,) \
+                or not parents.is_contiguous() or parents.device != rows.device:
+            raise ValueError(f"{what}: parents must be contiguous int32 of shape (n_groups,) on "
+                             "the rows' device")
+        if n_parents is None:
+            raise ValueError(f"{what}: parents need n_parents")
+        n_parents = int(n_parents)
+        if not 1 <= n_parents <= SPOT_MAX_GROUPS:
+            raise ValueError(f"{what}: n_parents must lie in 1 .. {SPOT_MAX_GROUPS}")
+    if variant not in (0, 1, 2) or (variant == 1 and n_groups > SPOT_LDS_GROUPS):
+        raise ValueError(f"{what}: variant must be 0, 1 (up to {SPOT_LDS_GROUPS} groups) or 2")
+    if qbits is None:
+        qbits = spot_qbits(group.numel())
+    if not 1 <= qbits <= 52 or n >= 1 << (62 - qbits):
+        raise ValueError(f"{what}: qbits must lie in 1 .. 52 with n < 2^(62 - qbits)")
+    grad, err = _column_buffers(what, rows, grad, err, mask, perm)
+    dev = rows.device
+    made = dict(acc=((n_groups, 4), torch.int64), residual=((n_groups, 2), torch.float64),
+                used_out=((2,), torch.float64))
+    given = dict(acc=acc, residual=residual, used_out=used_out)
+    if parents is not None:
+        made["parent_acc"] = ((n_parents, 4), torch.int64)
+        given["parent_acc"] = parent_acc
+    for name, (shape, dtype) in made.items():
+        if given[name] is None:
+            given[name] = torch.empty(shape, dtype=dtype, device=dev)
+        b = given[name]
+        if tuple(b.shape) != shape or b.dtype != dtype or not b.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous {dtype} of shape {shape}")
+    acc, residual, used_out = given["acc"], given["residual"], given["used_out"]
+    parent_acc = given.get("parent_acc")
+    if not rows.is_cuda:
+        _centroid_error_cpu(rows, row_x, row_y, group, n_groups, grid, targets, parents,
+                            n_parents, float(oob_weight), mask, perm, grad, err, acc, residual,
+                            used_out, parent_acc, int(qbits), dimension)
+        return err, grad, acc, residual, used_out, parent_acc
+    L = _lib.lib()
+    workspace = _column_workspace(
+        what, rows, grad, workspace,
+        lambda: L.tfrt_centroid_error_workspace_bytes(n, n_groups), group, mask, perm, err, acc,
+        residual, used_out, targets, parents, parent_acc)
+    x0, x1, qsx, y0, y1, qsy = grid
+    # (the field-code form covers plain rows: codes below 2 * dimension are rows of the block)
+    check(L.tfrt_centroid_error(
+        _p(rows), rows.stride(0), n, _DT[rows.dtype], 3 if dimension is None else int(dimension),
+        _p(mask), row_x, row_y, _p(group), group.numel(), _p(perm), n_groups, _p(targets),
+        _p(parents), n_parents, _p(parent_acc), x0, x1, qsx, y0, y1, qsy, int(qbits),
+        float(oob_weight), _p(grad), grad.stride(0), _p(err), _p(used_out), _p(residual), _p(acc),
+        int(variant), _p(workspace), workspace.numel(), _stream(rows)), "tfrt_centroid_error")
+    return err, grad, acc, residual, used_out, parent_acc
+
+
+def centroid_parent_centroids(parent_acc, grid, fields=2):
+    """The (P, fields) float64 centroids of the parents' records of ``centroid_error``, NaN for a
+    parent without rays: ``x0 + (Sx / count) / qsx``, the expression the table launch forms its
+    targets by, bit for bit on either device.  (``spot_centroids`` divides by the Python number
+    ``qsx``, which torch on the device turns into a product with its reciprocal; here the divisor
+    is a tensor and the device divides.)"""
+    x0, _, qsx, y0, _, qsy = grid
+    cnt = parent_acc[:, 0].double()
+    cnt = torch.where(cnt > 0, cnt, torch.full_like(cnt, float("nan")))
+    cols = [x0 + (parent_acc[:, 1].double() / cnt) / torch.full_like(cnt, qsx)]
+    if fields == 2:
+        cols.append(y0 + (parent_acc[:, 2].double() / cnt) / torch.full_like(cnt, qsy))
+    return torch.stack(cols, dim=1)
+
+
+def _centroid_table_cpu(acc, grid, two, targets, parents, n_parents, parent_acc):
+    """(residual (G, 2), used (G,) bool, inside error) of a record table: centroid_math.h,
+    operation by operation, over all groups at once (CPU tensors); ``parent_acc`` is filled."""
+    x0, _, qsx, y0, _, qsy = grid
+    G = acc.shape[0]
+    rays = acc[:, 0] > 0
+    zeros = torch.zeros(G, dtype=torch.float64)
+
+    def centroid(table):
+        w = table[:, 0].double()
+        safe = torch.where(table[:, 0] > 0, w, torch.ones_like(w))
+        cx = x0 + (table[:, 1].double() / safe) / qsx
+        cy = y0 + (table[:, 2].double() / safe) / qsy if two else torch.zeros_like(w)
+        return cx, cy
+
+    w = acc[:, 0].double()
+    cx, cy = centroid(acc)
+    if targets is not None:
+        tx = targets[:, 0]
+        ty = targets[:, 1] if two else zeros
+        has = torch.isfinite(tx) & torch.isfinite(ty)
+    else:
+        p = parents.long()
+        has = (p >= 0) & (p < n_parents)
+        parent_acc.zero_()
+        sel = rays & has
+        parent_acc.index_add_(0, p[sel], acc[sel])
+        Cx, Cy = centroid(parent_acc)
+        at = p.clamp(0, n_parents - 1)
+        tx, ty = Cx[at], Cy[at]
+    used = rays & has
+    nan = float("nan")
+    residual = torch.full((G, 2), nan, dtype=torch.float64)
+    residual[:, 0] = torch.where(used, cx - tx, torch.where(rays, zeros, residual[:, 0]))
+    residual[:, 1] = torch.where(used, cy - ty, torch.where(rays, zeros, residual[:, 1]))
+    rx = torch.where(used, residual[:, 0], zeros)
+    ry = torch.where(used, residual[:, 1], zeros)
+    inside = distortion_group_sum(w * (rx * rx), used) + distortion_group_sum(w * (ry * ry), used)
+    return residual, used, inside
+
+
+def _centroid_error_cpu(rows, row_x, row_y, group, n_groups, grid, targets, parents, n_parents,
+                        oob, mask, perm, grad, err, acc, residual, used_out, parent_acc, qbits,
+                        dimension):
+    """The CPU path of ``centroid_error`` (every torch op rounds on its own, as the kernels
+    do)."""
+    x0, x1, qsx, y0, y1, qsy = grid
+    two = row_y >= 0
+    n = rows.shape[1]
+    qmax = float(np.ldexp(1.0, qbits))
+    x, y, link = _fields_cpu(rows, row_x, row_y, dimension)
+    counting = torch.ones(n, dtype=torch.bool) if mask is None else (mask[:n] >= 0)
+    finite = torch.isfinite(x) & torch.isfinite(y)
+    s = torch.arange(n, dtype=torch.int64) if perm is None else perm[:n].long()
+    s_ok = (s >= 0) & (s < group.numel())
+    label = torch.full((n,), -1, dtype=torch.int64)
+    label[s_ok] = group[s[s_ok]].long()
+    spot = counting & finite & s_ok & (label >= 0) & (label < n_groups)
+    inside, pen, gx, gy = _outside_cpu(x, y, two, grid, oob, spot, None)
+    xi, yi, li = x[inside], y[inside], label[inside]
+    acc.zero_()
+    acc[:, 0].index_add_(0, li, torch.ones_like(li))
+    acc[:, 1].index_add_(0, li, torch.round((xi - x0) * qsx).clamp(0.0, qmax).long())
+    if two:
+        acc[:, 2].index_add_(0, li, torch.round((yi - y0) * qsy).clamp(0.0, qmax).long())
+    res, used, e_inside = _centroid_table_cpu(acc, grid, two, targets, parents, n_parents,
+                                              parent_acc)
+    residual.copy_(res)
+    used_out[0] = float(int(used.sum()))
+    used_out[1] = 0.0 if parent_acc is None else float(int((parent_acc[:, 0] > 0).sum()))
     gx[inside] = 2.0 * res[li, 0]
     if two:
         gy[inside] = 2.0 * res[li, 1]

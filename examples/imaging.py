@@ -77,6 +77,18 @@ stable, and the spot term wins: the lens focuses and the chief rays tilt).  The 
 largest ``|mean direction cosine|`` over the object points before and after.
 
     python examples/imaging.py --telecentric [WEIGHT] [--rays 20000] [--steps 30] [--generic]
+
+``--round-spots [WEIGHT]`` adds the astigmatism term of an imaging merit function: the spot of
+every object point must be ROUND -- equal and uncorrelated widths along y and z --, at whatever
+size the ``SpotError`` beside it reaches:
+``SumError([SpotError, MomentError(("y_end", "z_end"), labels, domain, shape="round")],
+weights=[1, WEIGHT], reduce="mean")``.  The ``MomentError`` charges every ray the squared
+anisotropic part of its spot's covariance, ``(Cxx - Cyy)**2 / 2 + 2 * Cxy**2``; the run prints the
+largest anisotropy ``sqrt((Cxx - Cyy)**2 + 4 * Cxy**2) / (Cxx + Cyy)`` over the object points
+before and after.  The term is stiff beside the spot term: at the step 0.4 of the other sums weight
+10 is stable and weight 100 diverges, so the step is ``min(0.4, 4 / WEIGHT)``.
+
+    python examples/imaging.py --round-spots [WEIGHT] [--rays 20000] [--steps 30] [--generic]
 """
 import argparse
 import math
@@ -105,6 +117,8 @@ MEAN_LEARNING_RATE = 0.4  # --magnification: LEARNING_RATE * 20,000 rays * 2 ter
 TELECENTRIC_WEIGHT = 1000.0  # --telecentric: squared direction cosines against squared radii
 TELECENTRIC_STEP = 100.0    # --telecentric: the largest weight * learning rate that is stable
 FLAT_WEIGHT_CONES = 16.0  # --flat-field: the FlatFieldError's weight in units of sin(cone)^2
+ROUND_WEIGHT = 1.0       # --round-spots: squared covariance residuals against squared radii
+ROUND_STEP = 4.0         # --round-spots: the largest weight * learning rate that was stable
 HALF_DIRECTION = 0.5     # --telecentric: the (y_dir, z_dir) of a finished ray that counts
 HALF_DOMAIN = 3.0        # the target region: the unfocused cone of a ray bundle has radius ~1.6
 
@@ -138,9 +152,19 @@ def focus_spread(term):
     return float(h.max() - h.min())
 
 
+def anisotropy(term):
+    """The largest ``sqrt((Cxx - Cyy)**2 + 4 * Cxy**2) / (Cxx + Cyy)`` over the groups of
+    ``term``'s last evaluation: 0 for a round spot, 1 for a line."""
+    C = term.covariances()
+    C = C[torch.isfinite(C).all(dim=1) & (C[:, 0] + C[:, 2] > 0)]
+    d = C[:, 0] - C[:, 2]
+    return float((torch.sqrt(d * d + 4.0 * C[:, 1] * C[:, 1]) / (C[:, 0] + C[:, 2])).max())
+
+
 def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, target_distance=10.0,
           object_size=0.2, lens_aperature=1.0, apodize=None, magnification=None, focus=False,
-          distortion=None, flat_field=False, flat_weight=None, telecentric=None):
+          distortion=None, flat_field=False, flat_weight=None, telecentric=None,
+          round_spots=None):
     points = letter_f(object_size)
     P = points.shape[0]
     A = max(ray_count // P, 2)
@@ -228,28 +252,38 @@ def build(ray_count=20000, lens_res_scale=0.12, source_distance=10.0, target_dis
             targets=np.zeros((P, 2)))
         error_function = optimizer.SumError([spot, tele_term], weights=[1.0, float(telecentric)],
                                             reduce="mean")
+    round_term = None
+    if round_spots is not None:
+        round_term = optimizer.MomentError(
+            ("y_end", "z_end"), labels,
+            ((-HALF_DOMAIN, HALF_DOMAIN), (-HALF_DOMAIN, HALF_DOMAIN)), shape="round")
+        error_function = optimizer.SumError([spot, round_term], weights=[1.0, float(round_spots)],
+                                            reduce="mean")
     return dict(engine=trace_engine, system=system, lens=lens, source=source, n_rays=n_rays,
                 n_points=P, error_function=error_function, spot=spot, accumulator=accumulator,
-                distortion=distortion_term, flat_field=flat_term, telecentric=tele_term)
+                distortion=distortion_term, flat_field=flat_term, telecentric=tele_term,
+                round_spots=round_term)
 
 
 def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=False, verbose=True,
         learning_rate=None, apodize=None, magnification=None, focus=False, distortion=None,
-        flat_field=False, flat_weight=None, telecentric=None):
+        flat_field=False, flat_weight=None, telecentric=None, round_spots=None):
     s = build(ray_count, lens_res_scale, apodize=apodize, magnification=magnification, focus=focus,
               distortion=distortion, flat_field=flat_field, flat_weight=flat_weight,
-              telecentric=telecentric)
+              telecentric=telecentric, round_spots=round_spots)
     focus = focus or flat_field
     combined, erf = s["error_function"], s["spot"]
     if learning_rate is None:
         # (the error is a sum over the rays: the step size goes with 1 / rays)
         learning_rate = LEARNING_RATE * (20000 / s["n_rays"])
         if magnification is not None or distortion is not None or flat_field \
-                or telecentric is not None:
+                or telecentric is not None or round_spots is not None:
             # (a mean over two terms per ray: the same step per ray as the sum's)
             learning_rate = MEAN_LEARNING_RATE
         if telecentric is not None and telecentric > 0.0:
             learning_rate = min(MEAN_LEARNING_RATE, TELECENTRIC_STEP / telecentric)
+        if round_spots is not None and round_spots > 0.0:
+            learning_rate = min(MEAN_LEARNING_RATE, ROUND_STEP / round_spots)
     kw = dict(learning_rate=learning_rate, grad_clip=1.0, fused=False if generic else "auto")
     if adam:
         opt = optimizer.Adam_Optimizer(s["engine"], s["lens"].parameters, combined, 3,
@@ -257,9 +291,9 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=Fals
     else:
         opt = optimizer.SGD_Optimizer(s["engine"], s["lens"].parameters, combined, 3, **kw)
     opt.suppress_warnings = True
-    rms, times, errors, place, fits, spreads, tilts = [], [], [], [], [], [], []
+    rms, times, errors, place, fits, spreads, tilts, shapes = [], [], [], [], [], [], [], []
     summed = magnification is not None or distortion is not None or flat_field \
-        or telecentric is not None
+        or telecentric is not None or round_spots is not None
     for step in range(steps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -287,6 +321,9 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=Fals
             # (read outside the timed part of the step)
             c = s["telecentric"].centroids()
             tilts.append(float(c[torch.isfinite(c).all(dim=1)].abs().max()))
+        if round_spots is not None:
+            # (read outside the timed part of the step)
+            shapes.append(anisotropy(s["round_spots"]))
         if verbose and (step % 5 == 0 or step == steps - 1):
             extra = "" if magnification is None else \
                 f"  mean squared image distance {place[-1]:.6g}  combined {mean:.6g}"
@@ -306,12 +343,15 @@ def run(ray_count=20000, steps=30, lens_res_scale=0.12, generic=False, adam=Fals
             if telecentric is not None:
                 extra = (f"  mean squared mean direction {place[-1]:.6g}  combined {mean:.6g}  "
                          f"largest |mean direction cosine| {tilts[-1]:.6g}")
+            if round_spots is not None:
+                extra = (f"  mean squared covariance residual {place[-1]:.6g}  combined "
+                         f"{mean:.6g}  largest anisotropy {shapes[-1]:.6g}")
             what = "rms distance to the focus" if focus else "rms spot"
             print(f"step {step:4d}: {what} {rms[-1]:.6g}{extra}  ({inside} rays inside, "
                   f"{1e3 * times[-1]:.2f} ms)")
     fused = opt._fused_step
     s.update(rms=rms, times=times, errors=errors, place=place, fits=fits, spreads=spreads,
-             tilts=tilts,
+             tilts=tilts, shapes=shapes,
              graph_replays=0 if fused is None else fused.graph_replays,
              centroids=erf.foci() if focus else erf.centroids())
     return s
@@ -348,6 +388,12 @@ if __name__ == "__main__":
                          "direction of every object point's bundle along the axis (default "
                          f"WEIGHT {TELECENTRIC_WEIGHT:g}; the step is min({MEAN_LEARNING_RATE}, "
                          f"{TELECENTRIC_STEP:g} / WEIGHT))")
+    ap.add_argument("--round-spots", nargs="?", type=float, const=ROUND_WEIGHT, default=None,
+                    metavar="WEIGHT",
+                    help="SumError([SpotError, MomentError((y_end, z_end), shape='round')]): every "
+                         f"object point's spot round at whatever size (default WEIGHT "
+                         f"{ROUND_WEIGHT:g}; the step is min({MEAN_LEARNING_RATE}, "
+                         f"{ROUND_STEP:g} / WEIGHT))")
     a = ap.parse_args()
     if a.focus and (a.apodize is not None or a.magnification is not None):
         ap.error("--focus takes neither --apodize nor --magnification")
@@ -362,10 +408,17 @@ if __name__ == "__main__":
                      "--distortion")
         if not (a.telecentric >= 0.0 and math.isfinite(a.telecentric)):
             ap.error("--telecentric WEIGHT must be finite and >= 0")
+    if a.round_spots is not None:
+        if a.focus or a.flat_field or a.magnification is not None or a.distortion is not None \
+                or a.telecentric is not None or a.apodize is not None:
+            ap.error("--round-spots takes none of --focus, --flat-field, --magnification, "
+                     "--distortion, --telecentric and --apodize")
+        if not (a.round_spots >= 0.0 and math.isfinite(a.round_spots)):
+            ap.error("--round-spots WEIGHT must be finite and >= 0")
     out = run(a.rays, a.steps, a.edge, generic=a.generic, adam=a.adam, learning_rate=a.lr,
               apodize=a.apodize, magnification=a.magnification, focus=a.focus,
               distortion=a.distortion, flat_field=a.flat_field, flat_weight=a.flat_weight,
-              telecentric=a.telecentric)
+              telecentric=a.telecentric, round_spots=a.round_spots)
     tail = sorted(out["times"][len(out["times"]) // 2:])
     print(f"{out['n_points']} object points, {out['n_rays']} rays; steps replayed from the graph: "
           f"{out['graph_replays']} of {a.steps}; median step of the second half: "
@@ -406,3 +459,9 @@ if __name__ == "__main__":
         print(f"combined error: first {out['errors'][0]:.6g} last {out['errors'][-1]:.6g}")
         print(f"largest |mean direction cosine| over {out['n_points']} object points: first "
               f"{out['tilts'][0]:.6g} last {out['tilts'][-1]:.6g}")
+    if a.round_spots is not None:
+        print(f"mean squared covariance residual: first {out['place'][0]:.6g} last "
+              f"{out['place'][-1]:.6g}")
+        print(f"combined error: first {out['errors'][0]:.6g} last {out['errors'][-1]:.6g}")
+        print(f"largest anisotropy over {out['n_points']} object points: first "
+              f"{out['shapes'][0]:.6g} last {out['shapes'][-1]:.6g}")

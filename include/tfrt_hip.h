@@ -1085,6 +1085,79 @@ int tfrt_centroid_error(const void* rows, int64_t stride, int64_t n, int32_t sta
                         double* residual, int64_t* acc, int32_t variant, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* MomentError: the COVARIANCE of every group of rays -- the size and the shape of its spot -- must
+ * be a given matrix (mode 0, `covariance`), or must be round at whatever size (mode 1): a spot of
+ * a prescribed width, an anamorphic spot, the astigmatism term of an imaging merit function, a
+ * beam matrix in phase space.  The error is the sum over the used groups of n |D|_F^2 with D the
+ * residual of the group's covariance, plus tfrt_spot_error's penalty for rays outside the domain.
+ * Six launches (clear `acc` and `mom`, tfrt_spot_error's unweighted accumulate launch, the centres,
+ * pass 2, table, seed); no host read, no allocation, no float atomics: captured with the rest of a
+ * step.
+ *
+ * The columns, the fields and their codes, the four cases of a counting column in their order, the
+ * out-of-domain penalty and its gradient, terms = k * (number of counting columns) and the chain
+ * rule of a direction field are exactly tfrt_spot_error_fields'.  Every operation below is an IEEE
+ * f64 operation rounded on its own (no contraction); integers are exact.  With one field every xy
+ * and yy component and cy are 0.0.
+ *
+ * Grid.  `mbits` is even, 2 .. 40 (ops.moment_mbits(N) = min(40, 2 * ((61 - bit_length(N)) / 2))
+ * for a source of N rays), h = mbits / 2, msx = 2^mbits / (x1 - x0) and msy alike, computed once
+ * by the caller; n < 2^(61 - mbits).  A ray inside has
+ *   mx = min(max(rint((x - x0) * msx), 0), 2^mbits)   (tfrt_spot_error's fixed point on this grid).
+ * Pass 1.  {1, mx, my} is added to the record {n, Sx, Sy, 0} of the ray's group in `acc`.
+ * Centre.  A group is USED iff n >= 2.  kx = (2 Sx + n) / (2 n) (integer division), ky alike;
+ *   cx = x0 + (double) kx / msx,  cy = y0 + (double) ky / msy   (also formed for n = 1).
+ * Pass 2.  A ray inside a used group: dx = mx - kx, dxl = dx & (2^h - 1), dxh = dx >> h (arithmetic),
+ * dy alike; for (a, b) = (x, x), (x, y), (y, y) the group's record in `mom` -- nine int64
+ * {xxHH, xxHL, xxLL, xyHH, xyHL, xyLL, yyHH, yyHL, yyLL} -- receives
+ *   HH += ah * bh,  HL += ah * bl + al * bh,  LL += al * bl.
+ * |dx| <= 2^mbits, so a term is at most 2^(mbits + 1) in magnitude and a sum stays below 2^62.
+ * HH 2^mbits + HL 2^h + LL is the exact integer sum(da * db).
+ * Covariance.  Mf = (ldexp((double) HH, mbits) + ldexp((double) HL, h)) + (double) LL,
+ *   C_ab = (Mf_ab / (double) n) / (ms_a * ms_b):
+ * the second moment about the centre in scene units squared (the centre lies within half a grid
+ * step of the centroid; the (c - k)^2 correction is dropped by definition).
+ * Residual.  mode 0: t = row g of `covariance`, {txx, txy, tyy} (one field: {txx});
+ *   D_ab = C_ab - t_ab, or 0.0 where t_ab is NaN (a free component).
+ * mode 1 (two fields):  s = (Cxx + Cyy) / 2.0,  Dxx = Cxx - s,  Dxy = Cxy,  Dyy = Cyy - s.
+ * Error.  e_g = n * ((Dxx * Dxx + 2.0 * (Dxy * Dxy)) + Dyy * Dyy),
+ *   error = (sum of e_g over the used groups) + the sum of the penalties,
+ *   error_out = {error, terms, error / terms (NaN with no counting column)}.
+ * The sum over the groups has tfrt_centroid_error's fixed shape and order, the partials of the
+ * accumulate launch likewise.  Two runs give the same bits.
+ * Gradient.  With F = 4.0 * D (exact), a ray inside a used group gets
+ *   gx = Fxx * (x - cx) + Fxy * (y - cy),  gy = Fxy * (x - cx) + Fyy * (y - cy)
+ * (one field: gx = Fxx * (x - cx)) from its own f64 coordinates, chained onto the start and end
+ * rows with a direction field; a ray outside the penalty's derivative; every other ray zeros.
+ * That is the gradient of the error without a derivative of the centre (the residuals of a group
+ * sum to zero) or of s (which minimises the error), up to the grid.
+ *
+ *   mode         0: target covariance; 1: round
+ *   covariance   mode 0: n_groups rows of 3 f64 (one field: of 1) on the device, read by the table
+ *                launch, so overwriting it between replays of a captured step is seen; mode 1: NULL
+ *   used_out     2 f64 {groups used, groups with rays}
+ *   group_rows   n_groups rows of eight f64 {cx, cy, Fxx, Fxy, Fyy, used (1.0 / 0.0), 0, 0},
+ *                16-byte aligned; c is NaN for a group without rays, F is 0.0 for one not used
+ *   cov_out      n_groups rows of six f64 {Cxx, Cxy, Cyy, Dxx, Dxy, Dyy}, NaN for a group not used
+ *   acc          n_groups records of four int64, mom: n_groups records of nine int64; both cleared
+ *                and filled by this call
+ *   variant      0: by n_groups; 1: the tables of both passes in LDS (up to 256 groups); 2: global
+ *                atomics
+ *   workspace    tfrt_moment_error_workspace_bytes(n, n_groups) bytes (0: bad arguments)
+ * Everything else as for tfrt_spot_error_fields.  Bad arguments are refused with TFRT_E_BADARG /
+ * TFRT_E_WORKSPACE before any launch.
+ */
+size_t tfrt_moment_error_workspace_bytes(int64_t n, int32_t n_groups);
+int tfrt_moment_error(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                      int32_t dimension, const int32_t* mask, int32_t field_x, int32_t field_y,
+                      const int32_t* group, int64_t n_source, const int32_t* perm,
+                      int32_t n_groups, int32_t mode, const double* covariance, double x0,
+                      double x1, double msx, double y0, double y1, double msy, int32_t mbits,
+                      double oob_weight, double* grad, int64_t grad_stride, double* error_out,
+                      double* used_out, double* group_rows, double* cov_out, int64_t* acc,
+                      int64_t* mom, int32_t variant, void* workspace, size_t workspace_bytes,
+                      void* stream);
+
 /* FlatFieldError: the foci of all groups must lie in ONE plane with the unit normal a = `axis` --
  * wherever along the normal that plane has to stand.  The error is the sum, over the counting rays
  * of the groups with a focus, of the squared distance of their group's focus from that plane, in

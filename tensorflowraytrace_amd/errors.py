@@ -19,7 +19,10 @@ the groups' centroids must be a scaled or affine copy of the object points --
 foci of all groups must lie in one plane with a given normal -- ``tfrt_flatfield_error`` (clear,
 FocusError's accumulate, fit, seed); a ``CentroidError`` -- every group's centroid must lie at a
 given target, or the centroids of the groups of one parent must coincide --
-``tfrt_centroid_error`` (clear, SpotError's accumulate, with parents their records, table, seed).
+``tfrt_centroid_error`` (clear, SpotError's accumulate, with parents their records, table, seed);
+a ``MomentError`` -- the covariance of every group's rays, the size and the shape of its spot, must
+be a given matrix, or must be round -- ``tfrt_moment_error`` (clear, SpotError's accumulate on a
+finer grid, the integer centres, the limb products about them, table, seed).
 A ``SumError`` is a weighted sum of such terms and of ``GoalError``s: every term's launches into a
 seed block of its own (a ``GoalError`` through ``tfrt_goal_error_columns``), then ONE
 ``tfrt_error_combine`` for the step's seed block and error.
@@ -28,8 +31,8 @@ Each is an ordinary error function (``__call__(engine)``): the generic path give
 numbers, which is what the parity tests compare.
 
 The protocol between a built-in term (``GoalError``, ``DensityError``, ``SpotError``,
-``TransportError``, ``FocusError``, ``DistortionError``, ``FlatFieldError``, ``CentroidError``)
-and the fused 3-D step:
+``TransportError``, ``FocusError``, ``DistortionError``, ``FlatFieldError``, ``CentroidError``,
+``MomentError``) and the fused 3-D step:
 
 * ``rows``, ``fields``, ``rows_for(dimension)``: the rows of the ray block (the field codes) the
   term reads;
@@ -1761,6 +1764,272 @@ class _CentroidTerms(torch.autograd.Function):
         return (upstream[:, 0] * grad).to(ctx.dtype), None, None, None, None, None
 
 
+class MomentError(_CoupledError):
+    """What the spot of a group of rays LOOKS like: the covariance of the group's finished rays
+    -- the size and the shape of its spot -- must be a given matrix, or must be round.  A
+    ``SpotError`` pulls the second moment of every group to zero, alike on both axes; a
+    ``CentroidError`` says where the spot lies.  Here a spot gets a prescribed size (an
+    illumination patch of a given width, a detector under-filled by a margin, a beam of a given
+    divergence with ``("y_dir", "z_dir")``), an anamorphic shape (a line generator, a diode beam
+    to be circularised), a waist at the target plane (``("y_end", "y_dir")`` with ``txy = 0``: a
+    beam matrix in phase space) -- or, with ``shape="round"``, equal and uncorrelated widths on
+    both axes at whatever size: the astigmatism term of an imaging merit function, beside the
+    ``SpotError`` that sets the size.
+
+    ``fields``, ``groups``, ``domain``, ``oob_weight`` and ``n_groups`` are exactly
+    ``SpotError``'s: one or two fields (positions or direction cosines), one label per SOURCE ray
+    (or a callable with ``n_groups``), kept as int32 on the device and overwritable between
+    replays, the label ``-1`` excludes a ray, rays outside the closed domain take the penalty
+    ``oob_weight * (ex**2 + ey**2)`` and are in no group.  There are no ``weights``.  Exactly one
+    of ``covariance`` and ``shape`` is given (``ValueError`` otherwise):
+
+    * ``covariance``: (G, 3) floats ``{txx, txy, tyy}`` in scene units squared -- (G, 1) or (G,)
+      with one field; a single row serves every group --, kept as (G, 3) float64 on the device
+      (``self.covariance``, moved once) and overwritable in place between replayed steps; the
+      buffer's address is part of ``graph_key()``.  A NaN component is free (no error, no
+      gradient from it); finite ``txx < 0``, ``tyy < 0`` or ``txy**2 > txx * tyy`` are refused.
+    * ``shape="round"`` (two fields): ``s = (Cxx + Cyy) / 2`` is free.
+
+    For every finished ray, the four cases of ``SpotError`` in its order.  Float64, every
+    operation rounded on its own, integers exact (include/tfrt_hip.h, tfrt_moment_error); N is
+    the source's ray count:
+
+    * the grid: ``mbits = min(40, 2 * ((61 - bit_length(N)) // 2))`` (``ops.moment_mbits(N)``),
+      ``h = mbits // 2``, ``ms = 2**mbits / (x1 - x0)`` per axis,
+      ``m = min(max(rint((x - x0) * ms), 0), 2**mbits)``;
+    * pass 1: a ray inside adds ``{1, mx, my}`` to its group's int64 record ``{n, Sx, Sy, 0}``;
+    * a group with ``n >= 2`` is USED; its integer centre is ``kx = (2 * Sx + n) // (2 * n)``,
+      ``cx = x0 + kx / ms``: within half a grid step of the centroid;
+    * pass 2: a ray inside a used group has ``dx = mx - kx``, split as ``dxl = dx & (2**h - 1)``,
+      ``dxh = dx >> h``; for (a, b) in xx, xy, yy the group's second record of nine int64 takes
+      ``HH += ah * bh``, ``HL += ah * bl + al * bh``, ``LL += al * bl`` -- below ``2**62`` for any
+      N, and ``HH * 2**mbits + HL * 2**h + LL`` is the exact ``sum(da * db)``;
+    * ``Mf = (ldexp(HH, mbits) + ldexp(HL, h)) + LL``, ``C_ab = (Mf / n) / (ms_a * ms_b)``: the
+      covariance about the centre (the ``(c - k)**2`` correction, below a quarter of a grid step
+      squared, is dropped by definition);
+    * the residual: ``D_ab = C_ab - t_ab`` (0 where ``t_ab`` is NaN); round: ``Dxx = Cxx - s``,
+      ``Dyy = Cyy - s``, ``Dxy = Cxy``;
+    * ``error = sum over used groups of n * ((Dxx**2 + 2 * Dxy**2) + Dyy**2) + penalties`` over
+      ``len(fields) * n_finished`` terms, the sum over the groups in ``CentroidError``'s fixed
+      shape and order: two runs give the same bits;
+    * a ray inside a used group gets ``gx = Fxx * (x - cx) + Fxy * (y - cy)``,
+      ``gy = Fxy * (x - cx) + Fyy * (y - cy)`` with ``F = 4 * D`` and its own float64 ``x``
+      (chained onto start and end rows with a direction field), a ray outside the penalty's
+      derivative, every other ray zeros.  No centre is differentiated, because the residuals of a
+      group sum to zero, and ``s`` is not, because it minimises the error.
+
+    It is an ordinary ``error_function(engine)`` (the generic path: ``ops.moment_error`` over the
+    finished rays' columns under a ``torch.autograd.Function`` that returns the (n_finished, k)
+    terms -- a ray inside a used group carries ``(Dxx**2 + Dxy**2, Dxy**2 + Dyy**2)`` of its
+    group, ``(Dxx**2)`` with one field), which also serves sources that are not traced in place,
+    ``deterministic=True``, fewer than 4,096 rays, several ranks and 2-D engines.  Its
+    ``backward`` returns ``upstream * gradient``, exact when ``upstream`` is constant; with a
+    direction field both fields of a ray must carry the same factor.  On a 3-D engine that traces
+    its source in place the optimiser runs it on the fused, graph-replayed step wherever a
+    ``CentroidError`` runs there (``FusedStep._rowwise3d`` with ``tfrt_moment_error``: clear,
+    accumulate, centres, pass 2, table, seed), and it is a legal term of a ``SumError``.
+
+    ``last_acc`` / ``last_mom`` are the (G, 4) and (G, 9) int64 record tables of the last
+    evaluation, ``centroids()`` the (G, k) centres, ``covariances()`` the (G, 3) ``{Cxx, Cxy,
+    Cyy}`` ((G, 1) with one field), ``residuals()`` the ``D`` alike -- NaN for a group that is
+    not used --, ``groups_used`` the number of used groups (read from the device).
+    ``splat_variant`` is ``ops.moment_error``'s ``variant``."""
+
+    splat_variant = 0
+
+    def __init__(self, fields, groups, domain, covariance=None, shape=None, oob_weight=0.0,
+                 n_groups=None):
+        from . import config
+        what = "MomentError"
+        self.fields, self.domain = _fields_and_domain(what, fields, domain)
+        self.rows = [_FIELDS3.index(f) for f in self.fields]
+        self.has_direction = any(f.endswith("_dir") for f in self.fields)
+        self.oob_weight = float(oob_weight)
+        if not (self.oob_weight >= 0.0 and np.isfinite(self.oob_weight)):
+            raise ValueError(f"{what}: oob_weight must be finite and >= 0")
+        if (covariance is None) == (shape is None):
+            raise ValueError(f"{what}: give exactly one of covariance and shape")
+        _init_groups(self, what, groups, n_groups, ops.SPOT_MAX_GROUPS)
+        G, k = self.n_groups, len(self.fields)
+        k3 = 3 if k == 2 else 1
+        self.shape, self.covariance = shape, None
+        if shape is not None:
+            if shape != "round":
+                raise ValueError(f"{what}: shape must be 'round', got {shape!r}")
+            if k != 2:
+                raise ValueError(f"{what}: shape='round' needs two fields")
+        else:
+            try:
+                t = covariance.detach().cpu().numpy() if isinstance(covariance, torch.Tensor) \
+                    else np.asarray(covariance)
+                t = np.array(t, dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"{what}: covariance must be numbers of shape ({G}, {k3})") from e
+            if k3 == 1 and t.ndim <= 1 and t.size in (1, G):
+                t = t.reshape(-1, 1)
+            if t.ndim == 1 and t.shape[0] == k3:
+                t = t[None, :]
+            if t.ndim != 2 or t.shape[1] != k3 or t.shape[0] not in (1, G):
+                raise ValueError(f"{what}: covariance must have shape (n_groups, {k3}) = "
+                                 f"({G}, {k3}) or one such row, got {t.shape}")
+            t = np.broadcast_to(t, (G, k3)).copy()
+            if np.isinf(t).any():
+                raise ValueError(f"{what}: covariance must be finite, or NaN for a free component")
+            with np.errstate(invalid="ignore"):
+                bad = t[:, 0] < 0
+                if k3 == 3:
+                    bad |= (t[:, 2] < 0) | (t[:, 1] * t[:, 1] > t[:, 0] * t[:, 2])
+            if bad.any():
+                raise ValueError(f"{what}: covariance rows {np.nonzero(bad)[0][:5].tolist()} are "
+                                 "not positive semi-definite (txx >= 0, tyy >= 0, "
+                                 "txy**2 <= txx * tyy)")
+            self.covariance = torch.as_tensor(t).to(config.get_device())
+        self._grids = {}
+        self.last_acc = self.last_mom = self.last_grid = self.last_mbits = None
+        self.last_rows = self.last_cov = self.last_used = None
+
+    def labels_of(self, src):
+        """The int32 label buffer of the source set ``src`` on its device, one label per source
+        ray, given or computed and cached as ``SpotError.labels_of`` does."""
+        return _source_buffer(self, "labels", self.groups,
+                              lambda v, dev: _as_labels("MomentError", v, dev), src,
+                              "MomentError", "label")
+
+    def grid_for(self, n_source):
+        """(mbits, grid constants) for a source of ``n_source`` rays: both paths of a step use
+        the source's ray count, so the fused and the generic step quantise alike."""
+        hit = self._grids.get(n_source)
+        if hit is None:
+            mbits = ops.moment_mbits(n_source)
+            hit = self._grids[n_source] = (mbits, ops.spot_grid(self.domain, mbits))
+        return hit
+
+    def covariance_on(self, device):
+        """The target buffer on ``device`` (moved once; a new buffer re-captures a graph); None
+        with ``shape``."""
+        if self.covariance is not None and self.covariance.device != device:
+            self.covariance = self.covariance.to(device)
+        return self.covariance
+
+    def graph_key(self):
+        """What a captured step has baked in: the addresses of the label buffer and of the
+        target buffer, the mode and the constants."""
+        lab, t = self.labels, self.covariance
+        return (None if lab is None else (lab.data_ptr(), tuple(lab.shape)), self.n_groups,
+                self.domain, self.oob_weight, self.splat_variant, self.shape,
+                None if t is None else t.data_ptr())
+
+    def evaluate(self, rows, row_x, row_y, labels, mask=None, perm=None, dimension=None,
+                 **buffers):
+        """``ops.moment_error`` of the columns of ``rows`` with these labels, target and domain
+        (``dimension`` given: ``rows`` is the geometry block, ``row_x`` / ``row_y`` field
+        codes)."""
+        mbits, grid = self.grid_for(labels.numel())
+        out = ops.moment_error(rows, row_x, row_y, labels, self.n_groups, grid,
+                               covariance=self.covariance_on(rows.device), shape=self.shape,
+                               oob_weight=self.oob_weight, mask=mask, perm=perm,
+                               variant=self.splat_variant, mbits=mbits, dimension=dimension,
+                               **buffers)
+        self.last_acc, self.last_mom, self.last_grid, self.last_mbits = out[2], out[3], grid, mbits
+        self.last_rows, self.last_cov, self.last_used = out[4], out[5], out[6]
+        return out
+
+    def seed_columns(self, cols, hold):
+        """tfrt_moment_error on the step's columns: labels through the trace's order inside the
+        kernels, as a SpotError; the records go into ``hold.buffers["acc"]``, (G, 4), and
+        ``["mom"]``, (G, 9), the per-group rows into ``["group_rows"]``, (G, 8), covariances and
+        residuals into ``["cov"]``, (G, 6), the counts into ``["used_out"]``, (2,)."""
+        labels = self.labels_of(cols.src)
+        G = self.n_groups
+        dev = cols.rows.device
+        held = self._held(hold, "acc", (G, 4), torch.int64, dev,
+                          lambda: _lib.lib().tfrt_moment_error_workspace_bytes(cols.n, G))
+        if "mom" not in held:
+            held["mom"] = torch.zeros((G, 9), dtype=torch.int64, device=dev)
+            held["group_rows"] = torch.zeros((G, 8), dtype=torch.float64, device=dev)
+            held["cov"] = torch.zeros((G, 6), dtype=torch.float64, device=dev)
+            held["used_out"] = torch.zeros(2, dtype=torch.float64, device=dev)
+        self.evaluate(cols.rows, *_xy(self.rows), labels, mask=cols.mask, perm=cols.perm,
+                      dimension=3, grad=hold.g_fin, err=hold.err, **held)
+
+    def _last(self, name):
+        value = getattr(self, name)
+        if value is None:
+            raise RuntimeError("MomentError: no evaluation yet")
+        return value
+
+    def centroids(self):
+        """(G, k) float64 centres of the last evaluation -- the grid point nearest to each
+        group's centroid --, NaN for a group without rays."""
+        return self._last("last_rows")[:, :len(self.fields)]
+
+    def covariances(self):
+        """(G, 3) float64 ``{Cxx, Cxy, Cyy}`` of the last evaluation ((G, 1) with one field), NaN
+        for a group of fewer than two rays."""
+        return ops.moment_covariances(self._last("last_cov"), len(self.fields))
+
+    def residuals(self):
+        """(G, 3) float64 ``{Dxx, Dxy, Dyy}`` of the last evaluation ((G, 1) with one field), NaN
+        for a group of fewer than two rays."""
+        return self._last("last_cov")[:, 3:(6 if len(self.fields) == 2 else 4)]
+
+    @property
+    def groups_used(self):
+        """The number of used groups of the last evaluation, read from the device."""
+        return int(self._last("last_used")[0])
+
+    def __call__(self, engine):
+        """The (n_finished, k) error terms through the generic path; the gradient rows come back
+        in ``backward``."""
+        codes = self.rows_for(engine.dimension)
+        fin = engine.finished_rays
+        if not bool(fin):
+            return torch.zeros((0, len(self.fields)), dtype=torch.float64)
+        labels = self.labels_of(engine._trace_src)
+        block, _, ids, dim, codes = self._finished_block(engine, fin, codes, ids=True)
+        return _MomentTerms.apply(block, self, labels, ids, dim, codes)
+
+
+class _MomentTerms(torch.autograd.Function):
+    """MomentError over the finished rays, no mask; ``ids``: the source ray of every column;
+    ``block``, ``dimension`` and ``codes`` as for ``_SpotTerms``.  Returns the (n, k) terms: a
+    penalised ray's ``oob_weight * ex**2`` per field, for an inside ray of a used group
+    ``(Dxx**2 + Dxy**2, Dxy**2 + Dyy**2)`` of its GROUP (their sum over the rays is the groups'
+    ``n * |D|**2``), zeros for the rest."""
+
+    @staticmethod
+    def forward(ctx, block, erf, labels, ids, dimension=None, codes=None):
+        rows = block.detach().contiguous()
+        ctx.chained = codes is not None
+        if codes is None:
+            codes = (0, 1)[:rows.shape[0]]
+        out = erf.evaluate(rows, *_xy(codes), labels, perm=ids, dimension=dimension)
+        grad, acc, cov = out[1], out[2], out[5]
+        ctx.save_for_backward(grad)
+        ctx.dtype = block.dtype
+        if ctx.chained:
+            link = ops._link_torch(rows, dimension)
+            v = torch.stack([ops._link_field_torch(link, c, dimension) for c in codes], dim=0)
+        else:
+            v = rows.double()
+        s = ids.long().clamp(0, labels.numel() - 1)
+        D = cov[labels[s].long().clamp(0, erf.n_groups - 1), 3:]
+        D = torch.where(torch.isnan(D), torch.zeros_like(D), D)      # (a group that is not used)
+        cross = D[:, 1] * D[:, 1]
+        inside = torch.stack([D[:, 0] * D[:, 0] + cross, cross + D[:, 2] * D[:, 2]], dim=0)
+        return _spot_terms(erf, v, labels, ids, acc, None, inside=inside[:v.shape[0]])
+
+    @staticmethod
+    def backward(ctx, upstream):
+        grad, = ctx.saved_tensors
+        if not ctx.chained:
+            return (upstream.t() * grad).to(ctx.dtype), None, None, None, None, None
+        if upstream.shape[1] == 2 and not torch.equal(upstream[:, 0], upstream[:, 1]):
+            raise ValueError("MomentError with a direction field: the upstream gradient must "
+                             "weigh both fields of a ray alike")
+        return (upstream[:, 0] * grad).to(ctx.dtype), None, None, None, None, None
+
+
 class FlatFieldError(FocusError):
     """The foci of all groups must lie in ONE plane with the normal ``axis`` -- a flat field --,
     wherever along the normal that plane has to stand: the sum, over the finished rays that count,
@@ -1919,7 +2188,7 @@ class _FlatFieldTerms(torch.autograd.Function):
 
 # the coupled errors: all finished rays of a step enter one evaluation (one process)
 _COUPLED = (DensityError, SpotError, TransportError, FocusError, DistortionError, FlatFieldError,
-            CentroidError)
+            CentroidError, MomentError)
 
 
 class SumError:
@@ -1930,8 +2199,8 @@ class SumError:
     step is one trace, K error evaluations, one combination and one reverse sweep.
 
     ``terms``: 1 to 8 distinct instances of ``GoalError``, ``DensityError``, ``SpotError``,
-    ``TransportError``, ``FocusError``, ``DistortionError``, ``FlatFieldError`` or
-    ``CentroidError``; a ``RowwiseError``, a nested ``SumError`` or the same object twice is a ValueError.  ``weights``: K finite values >= 0, default all ones, kept as the (K,) float64
+    ``TransportError``, ``FocusError``, ``DistortionError``, ``FlatFieldError``,
+    ``CentroidError`` or ``MomentError``; a ``RowwiseError``, a nested ``SumError`` or the same object twice is a ValueError.  ``weights``: K finite values >= 0, default all ones, kept as the (K,) float64
     device tensor ``weights``; ``set_weights(values)`` validates on the host and overwrites that
     buffer in place, so a replayed graph sees the new values without a re-capture (as
     ``TransportError.set_goal``).  A weight of 0 switches a term off for a phase; the term is
@@ -1975,7 +2244,7 @@ class SumError:
             if not isinstance(t, (GoalError,) + _COUPLED):
                 raise ValueError("SumError: terms must be GoalError, DensityError, SpotError, "
                                  "TransportError, FocusError, DistortionError, FlatFieldError or "
-                                 "CentroidError instances, got "
+                                 "CentroidError instances, or MomentError ones; got "
                                  f"{type(t).__name__}")
         if len(set(id(t) for t in terms)) != len(terms):
             raise ValueError("SumError: the same term object is listed twice (a term keeps the "

@@ -2408,6 +2408,256 @@ def _centroid_error_cpu(rows, row_x, row_y, group, n_groups, grid, targets, pare
     err[2] = e / n_terms if n_terms > 0 else float("nan")
 
 
+# ------------------------------------------------- the covariance of every group: size and shape
+MOMENT_LDS_GROUPS = 256            # tfrt_moment_error: 9 planes of sums, 2 of centres in LDS, 22 KiB
+MOMENT_MAX_MBITS = 40
+MOMENT_MODES = {"covariance": 0, "round": 1}
+MOMENT_SEED_MAX_GRID = 2048        # workgroups of 256 lanes of k_moment_seed
+
+
+def moment_mbits(n_source):
+    """Fraction bits of tfrt_moment_error's grid for a source of ``n_source`` rays: even, at most
+    40, with ``n_source * 2^(mbits + 1) < 2^62`` -- every limb sum of pass 2 fits an int64."""
+    return min(MOMENT_MAX_MBITS, 2 * ((61 - int(n_source).bit_length()) // 2))
+
+
+def penalty_sum_fixed(pens, outside):
+    """The sum of ``pens[outside]`` over the n columns in the shape and order of the kernels, as
+    float64 torch ops on the CPU: the accumulate launch's ``B = min(512, ceil(n / 1024))``
+    workgroups of 256 threads, thread t of workgroup b adds its columns ``256 b + t``,
+    ``+ 256 B``, ... onto 0.0, a wave's 64 lanes by ``v += v[lane ^ d]`` for d = 32 .. 1, a
+    workgroup's 4 waves in index order; then the partials as ``distortion_group_sum`` adds the
+    groups."""
+    n = pens.numel()
+    if n == 0:
+        return torch.zeros((), dtype=torch.float64)
+    B = min(SPOT_MAX_GRID, (n + SPOT_RAYS_PER_BLOCK - 1) // SPOT_RAYS_PER_BLOCK)
+    stride = B * 256
+    trips = (n + stride - 1) // stride
+    v = torch.zeros(trips * stride, dtype=torch.float64)
+    v[:n] = torch.where(outside, pens, torch.zeros_like(pens))
+    lanes = torch.zeros(stride, dtype=torch.float64)
+    for trip in v.view(trips, stride):
+        lanes = lanes + trip                   # (penalties are >= 0: adding 0.0 changes no bit)
+    w = lanes.view(B * 4, 64)
+    for d in (32, 16, 8, 4, 2, 1):
+        w = w[:, :d] + w[:, d:2 * d]
+    waves = w[:, 0].reshape(B, 4)
+    partial = torch.zeros(B, dtype=torch.float64)
+    for k in range(4):
+        partial = partial + waves[:, k]
+    return distortion_group_sum(partial, torch.ones(B, dtype=torch.bool))
+
+
+def moment_error(rows, row_x, row_y, group, n_groups, grid, covariance=None, shape=None,
+                 oob_weight=0.0, mask=None, perm=None, grad=None, err=None, acc=None, mom=None,
+                 group_rows=None, cov=None, used_out=None, variant=0, workspace=None, mbits=None,
+                 dimension=None):
+    """tfrt_moment_error: the MomentError of the columns of ``rows`` -- the covariance of every
+    group's rays must be its row of ``covariance`` (G, 3) float64 ``{txx, txy, tyy}`` ((G, 1) with
+    one field; a NaN component is free), or, with ``shape="round"`` (two fields), isotropic at
+    whatever size.  Exactly one of the two is given.  The columns, ``row_x`` / ``row_y``,
+    ``group``, ``perm``, ``n_groups``, ``mask``, ``oob_weight`` and ``dimension`` are
+    ``spot_error``'s; ``grid`` is ``spot_grid(domain, mbits)`` with ``mbits`` (None:
+    ``moment_mbits(group.numel())``) even, 2 .. 40.  ``variant``: 0 by G, 1 tables in LDS (up to
+    ``MOMENT_LDS_GROUPS`` groups), 2 global atomics.  Returns (err {sum, terms, mean}, grad, acc (G, 4) int64 {n, Sx,
+    Sy, 0}, mom (G, 9) int64 {xx, xy, yy} x {HH, HL, LL}, group_rows (G, 8) float64 {cx, cy, 4Dxx,
+    4Dxy, 4Dyy, used, 0, 0}, cov (G, 6) float64 {Cxx, Cxy, Cyy, Dxx, Dxy, Dyy} -- NaN for a group
+    of fewer than two rays --, used_out (2,) float64 {groups used, groups with rays}).  ``grad``,
+    ``err``, ``acc``, ``mom``, ``group_rows``, ``cov``, ``used_out``, ``workspace`` (uint8):
+    buffers to reuse -- with all of them given a CUDA call allocates nothing.
+
+    CUDA tensors run the kernels.  CPU tensors run a torch restatement with the same int64
+    records, the same operations per group and per ray and the same order of every sum: every
+    output agrees bit for bit."""
+    what = "moment_error"
+    n_groups = int(n_groups)
+    if group.dtype != torch.int32 or group.dim() != 1 or not group.is_contiguous():
+        raise ValueError(f"{what}: group must be a contiguous int32 vector, one label per "
+                         "source ray")
+    if not 1 <= n_groups <= SPOT_MAX_GROUPS:
+        raise ValueError(f"{what}: n_groups must lie in 1 .. {SPOT_MAX_GROUPS}")
+    if (covariance is None) == (shape is None):
+        raise ValueError(f"{what}: exactly one of covariance and shape must be given")
+    if shape is not None and shape != "round":
+        raise ValueError(f"{what}: shape must be 'round', got {shape!r}")
+    n = rows.shape[1]
+    _check_field_codes(what, rows, row_x, row_y, dimension)
+    two = row_y >= 0
+    k3 = 3 if two else 1
+    if shape is not None and not two:
+        raise ValueError(f"{what}: shape='round' needs two fields")
+    if covariance is not None and (
+            covariance.dtype != torch.float64 or tuple(covariance.shape) != (n_groups, k3)
+            or not covariance.is_contiguous() or covariance.device != rows.device):
+        raise ValueError(f"{what}: covariance must be contiguous float64 of shape (n_groups, "
+                         f"{k3}) on the rows' device")
+    if variant not in (0, 1, 2) or (variant == 1 and n_groups > MOMENT_LDS_GROUPS):
+        raise ValueError(f"{what}: variant must be 0, 1 (up to {MOMENT_LDS_GROUPS} groups) or 2")
+    if mbits is None:
+        mbits = moment_mbits(group.numel())
+    mbits = int(mbits)
+    if not 2 <= mbits <= MOMENT_MAX_MBITS or mbits % 2 or n >= 1 << (61 - mbits):
+        raise ValueError(f"{what}: mbits must be even and lie in 2 .. {MOMENT_MAX_MBITS} with "
+                         "n < 2^(61 - mbits)")
+    grad, err = _column_buffers(what, rows, grad, err, mask, perm)
+    dev = rows.device
+    made = dict(acc=((n_groups, 4), torch.int64), mom=((n_groups, 9), torch.int64),
+                group_rows=((n_groups, 8), torch.float64), cov=((n_groups, 6), torch.float64),
+                used_out=((2,), torch.float64))
+    given = dict(acc=acc, mom=mom, group_rows=group_rows, cov=cov, used_out=used_out)
+    for name, (shp, dtype) in made.items():
+        if given[name] is None:
+            given[name] = torch.empty(shp, dtype=dtype, device=dev)
+        b = given[name]
+        if tuple(b.shape) != shp or b.dtype != dtype or not b.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous {dtype} of shape {shp}")
+    acc, mom, group_rows = given["acc"], given["mom"], given["group_rows"]
+    cov, used_out = given["cov"], given["used_out"]
+    mode = MOMENT_MODES["round" if shape is not None else "covariance"]
+    if not rows.is_cuda:
+        _moment_error_cpu(rows, row_x, row_y, group, n_groups, grid, mode, covariance,
+                          float(oob_weight), mask, perm, grad, err, acc, mom, group_rows, cov,
+                          used_out, mbits, dimension)
+        return err, grad, acc, mom, group_rows, cov, used_out
+    L = _lib.lib()
+    workspace = _column_workspace(
+        what, rows, grad, workspace,
+        lambda: L.tfrt_moment_error_workspace_bytes(n, n_groups), group, mask, perm, err, acc,
+        mom, group_rows, cov, used_out, covariance)
+    x0, x1, msx, y0, y1, msy = grid
+    # (the field-code form covers plain rows: codes below 2 * dimension are rows of the block)
+    check(L.tfrt_moment_error(
+        _p(rows), rows.stride(0), n, _DT[rows.dtype], 3 if dimension is None else int(dimension),
+        _p(mask), row_x, row_y, _p(group), group.numel(), _p(perm), n_groups, mode,
+        _p(covariance), x0, x1, msx, y0, y1, msy, mbits, float(oob_weight), _p(grad),
+        grad.stride(0), _p(err), _p(used_out), _p(group_rows), _p(cov), _p(acc), _p(mom),
+        int(variant), _p(workspace), workspace.numel(), _stream(rows)), "tfrt_moment_error")
+    return err, grad, acc, mom, group_rows, cov, used_out
+
+
+def moment_covariances(cov, fields=2):
+    """The (G, 3) float64 covariances ``{Cxx, Cxy, Cyy}`` of a ``moment_error`` evaluation, (G, 1)
+    with one field: the second moments of every group's rays about its centre, in scene units
+    squared, NaN for a group of fewer than two rays."""
+    return cov[:, :3 if fields == 2 else 1]
+
+
+def _moment_table_cpu(acc, mom, grid, two, mode, covariance, mbits):
+    """(group_rows (G, 8), cov (G, 6), used (G,) bool, rays (G,) bool, inside error) of the two
+    record tables: moment_math.h, operation by operation, over all groups at once (CPU)."""
+    x0, _, msx, y0, _, msy = grid
+    G = acc.shape[0]
+    h = mbits // 2
+    cnt = acc[:, 0]
+    rays, used = cnt > 0, cnt >= 2
+    nan = float("nan")
+    zeros = torch.zeros(G, dtype=torch.float64)
+    nans = torch.full((G,), nan, dtype=torch.float64)
+    safe = torch.where(rays, cnt, torch.ones_like(cnt))
+    nf = safe.double()
+    kx = torch.div(2 * acc[:, 1] + safe, 2 * safe, rounding_mode="floor")
+    ky = torch.div(2 * acc[:, 2] + safe, 2 * safe, rounding_mode="floor")
+    cx = torch.where(rays, x0 + kx.double() / msx, nans)
+    cy = torch.where(rays, y0 + ky.double() / msy, nans) if two else torch.where(rays, zeros, nans)
+    hi, mid = float(np.ldexp(1.0, mbits)), float(np.ldexp(1.0, h))      # (times 2^k: exact)
+
+    def value(first):
+        m = mom[:, first:first + 3].double()
+        return (m[:, 0] * hi + m[:, 1] * mid) + m[:, 2]
+
+    C = [(value(0) / nf) / (msx * msx),
+         (value(3) / nf) / (msx * msy) if two else zeros,
+         (value(6) / nf) / (msy * msy) if two else zeros]
+    if mode == MOMENT_MODES["round"]:
+        s = (C[0] + C[2]) / 2.0
+        D = [C[0] - s, C[1], C[2] - s]
+    else:
+        t = [covariance[:, 0], covariance[:, 1] if two else nans,
+             covariance[:, 2] if two else nans]
+        D = [torch.where(torch.isnan(t[c]), zeros, C[c] - t[c]) for c in range(3)]
+    e = nf * ((D[0] * D[0] + 2.0 * (D[1] * D[1])) + D[2] * D[2])
+    group_rows = torch.zeros((G, 8), dtype=torch.float64)
+    group_rows[:, 0], group_rows[:, 1] = cx, cy
+    cov = torch.full((G, 6), nan, dtype=torch.float64)
+    for c in range(3):
+        group_rows[:, 2 + c] = torch.where(used, 4.0 * D[c], zeros)
+        cov[:, c] = torch.where(used, C[c], nans)
+        cov[:, 3 + c] = torch.where(used, D[c], nans)
+    group_rows[:, 5] = used.double()
+    inside = distortion_group_sum(torch.where(used, e, zeros), used)
+    return group_rows, cov, used, rays, inside, kx, ky
+
+
+def _moment_error_cpu(rows, row_x, row_y, group, n_groups, grid, mode, covariance, oob, mask,
+                      perm, grad, err, acc, mom, group_rows, cov, used_out, mbits, dimension):
+    """The CPU path of ``moment_error`` (every torch op rounds on its own, as the kernels do)."""
+    x0, x1, msx, y0, y1, msy = grid
+    two = row_y >= 0
+    n = rows.shape[1]
+    h = mbits // 2
+    low = (1 << h) - 1
+    mmax = float(np.ldexp(1.0, mbits))
+    x, y, link = _fields_cpu(rows, row_x, row_y, dimension)
+    counting = torch.ones(n, dtype=torch.bool) if mask is None else (mask[:n] >= 0)
+    finite = torch.isfinite(x) & torch.isfinite(y)
+    s = torch.arange(n, dtype=torch.int64) if perm is None else perm[:n].long()
+    s_ok = (s >= 0) & (s < group.numel())
+    label = torch.full((n,), -1, dtype=torch.int64)
+    label[s_ok] = group[s[s_ok]].long()
+    spot = counting & finite & s_ok & (label >= 0) & (label < n_groups)
+    inside, _, gx, gy = _outside_cpu(x, y, two, grid, oob, spot, None)
+    zero = torch.zeros((), dtype=torch.float64)
+    ex = torch.maximum(x0 - x, zero) + torch.maximum(x - x1, zero)
+    ey = (torch.maximum(y0 - y, zero) + torch.maximum(y - y1, zero)) if two \
+        else torch.zeros_like(x)
+    pen = penalty_sum_fixed(oob * (ex * ex + ey * ey), spot & ~inside)
+    xi, yi, li = x[inside], y[inside], label[inside]
+    mx = torch.round((xi - x0) * msx).clamp(0.0, mmax).long()
+    my = torch.round((yi - y0) * msy).clamp(0.0, mmax).long() if two else torch.zeros_like(mx)
+    acc.zero_()
+    acc[:, 0].index_add_(0, li, torch.ones_like(li))
+    acc[:, 1].index_add_(0, li, mx)
+    if two:
+        acc[:, 2].index_add_(0, li, my)
+    # pass 2: the limb products about the integer centres of the used groups
+    cnt = acc[:, 0]
+    safe = torch.where(cnt > 0, cnt, torch.ones_like(cnt))
+    kx = torch.div(2 * acc[:, 1] + safe, 2 * safe, rounding_mode="floor")
+    ky = torch.div(2 * acc[:, 2] + safe, 2 * safe, rounding_mode="floor")
+    in_used = (cnt >= 2)[li]
+    lu = li[in_used]
+    dx, dy = (mx - kx[li])[in_used], (my - ky[li])[in_used]
+    xl, xh, yl, yh = dx & low, dx >> h, dy & low, dy >> h
+    mom.zero_()
+    sums = [xh * xh, 2 * (xh * xl), xl * xl]
+    if two:
+        sums += [xh * yh, xh * yl + xl * yh, xl * yl, yh * yh, 2 * (yh * yl), yl * yl]
+    for p, v in enumerate(sums):
+        mom[:, p].index_add_(0, lu, v)
+    rows_g, cov_g, used, rays, e_inside = _moment_table_cpu(acc, mom, grid, two, mode,
+                                                            covariance, mbits)[:5]
+    group_rows.copy_(rows_g)
+    cov.copy_(cov_g)
+    used_out[0], used_out[1] = float(int(used.sum())), float(int(rays.sum()))
+    row = rows_g[li]
+    ux = xi - row[:, 0]
+    if two:
+        uy = yi - row[:, 1]
+        gxi, gyi = row[:, 2] * ux + row[:, 3] * uy, row[:, 3] * ux + row[:, 4] * uy
+    else:
+        gxi = row[:, 2] * ux
+    live = row[:, 5] != 0.0
+    gx[inside] = torch.where(live, gxi, torch.zeros_like(gxi))
+    if two:
+        gy[inside] = torch.where(live, gyi, torch.zeros_like(gyi))
+    _write_grad_cpu(grad, n, dimension, row_x, row_y, gx, gy, link, spot)
+    e = e_inside + pen
+    n_terms = float(int(counting.sum()) * (2 if two else 1))
+    err[0], err[1] = e, n_terms
+    err[2] = e / n_terms if n_terms > 0 else float("nan")
+
+
 # ------------------------------------------------------- rays of a group through one point
 FOCUS_MAX_GROUPS = 1 << 20
 FOCUS_LDS_GROUPS = 256             # tfrt_focus_error: ten planes of G int64 in LDS, 20 KiB

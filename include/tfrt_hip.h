@@ -1158,6 +1158,74 @@ int tfrt_moment_error(const void* rows, int64_t stride, int64_t n, int32_t state
                       int64_t* mom, int32_t variant, void* workspace, size_t workspace_bytes,
                       void* stream);
 
+/* MixingError: every group of rays must land with the SAME density on the target, whatever that
+ * density is (the dies of an LED behind a mixing rod, the input zones of a homogeniser, the beams
+ * of a combiner).  The error is the mass-weighted mean over the groups of the mean squared
+ * difference of the group's density from the pooled one, in units of the uniform density, plus
+ * tfrt_density_error's penalty for rays outside the domain.  Six launches (clear `hq`, splat,
+ * margins, pulls, finish, seed); no host read, no allocation, no float atomics: captured with the
+ * rest of a step.
+ *
+ * The columns, the fields and their codes, the domain constants sx = nx / (x1 - x0) and sy, the
+ * bilinear splat with its clamped indices, the out-of-domain penalty and its gradient and the
+ * chain rule of a direction field are exactly tfrt_density_error_fields'; with `weight` the
+ * weight w of a column's source ray and every place it enters are tfrt_density_error_weighted's.
+ * Column i is source ray s = perm[i] (perm NULL: i).  Every operation below is an IEEE f64
+ * operation rounded on its own (no contraction); integers are exact.
+ *
+ * Classification.  tfrt_density_error's (weighted: tfrt_density_error_weighted's), then: a column
+ * that counts without a source ray (s outside [0, n_source)) or whose label group[s] lies outside
+ * [0, G) does not count -- no error, zero gradient, no penalty.  A column outside the closed domain
+ * adds oob_weight * (ex^2 + ey^2) (times w last) and gets the derivative of that.
+ * Histogram.  A column inside adds rint(b * 2^32) (weighted: rint((b * w) * 2^32), half to even)
+ * for each of its two or four bilinear weights b to the cell of its bin in plane group[s] of the
+ * int64 table Hq[G][ny][nx].
+ * Margins (integer sums, free of order; no overflow for n < 2^31).  With B = nx * ny:
+ *   nq_g = sum_b Hq_gb,  Pq_b = sum_g Hq_gb,  Nq = sum_g nq_g.
+ * Error.  A group is USED iff nq_g > 0.  For a cell of a used group
+ *   p = (double) Hq_gb / (double) nq_g,  m = (double) Pq_b / (double) Nq,  d = p - m,
+ *   e_g = (double) B * sum_b (d * d),   E_mix = sum over the used groups of
+ *   ((double) nq_g / (double) Nq) * e_g,   error = E_mix + the sum of the penalties,
+ *   error_out = {error, 1, error}  (ONE error term, as tfrt_density_error).
+ * Nq == 0: E_mix = 0.0 and every pull is 0.0.
+ * Pull.  N = (double) Nq * 2^-32,  D_gb = ((2.0 * (double) B) / N) * d; 0.0 in a group not used.
+ * Gradient.  A column inside gets tfrt_density_error's expressions on plane group[s] of D,
+ *   gx = sx * ((1 - ty) * (D[j0][i1] - D[j0][i0]) + ty * (D[j1][i1] - D[j1][i0])),
+ *   gy = sy * ((1 - tx) * (D[j1][i0] - D[j0][i0]) + tx * (D[j1][i1] - D[j0][i1]))
+ * (one field: gx = sx * (D[i1] - D[i0])), times w last, chained onto the start and end rows with a
+ * direction field.  That is the gradient of the error without a derivative of m, nq_g or Nq: m is
+ * the mass-weighted mean of the p_g and so minimises the error, and a column inside carries total
+ * weight 1 (w) wherever it stands.
+ * Orders.  Thread t of 1,024 adds the d * d of the bins t, t + 1024, ... of its group in ascending
+ * order onto 0.0; within each wave of 64 threads v[lane] += v[lane ^ s] for s = 32 .. 1; then the
+ * 16 waves in index order onto 0.0.  The sum over the groups has the same shape with the groups in
+ * the bins' place (tfrt_centroid_error's), the penalties that of tfrt_centroid_error's: two runs
+ * give the same bits.
+ *
+ *   group        n_source int32 labels of the SOURCE rays; n_groups = G, 1 .. 1,024;
+ *                G * nx * ny <= 2^20, nx * ny <= 65,536
+ *   weight       NULL, or n_source f64 in [0, 1] (a column whose weight is not in [0, 1] does not
+ *                count)
+ *   used_out     2 f64 {groups used, N}
+ *   group_errors G f64: e_g, NaN for a group not used
+ *   pull         G * ny * nx f64: D
+ *   hq           G * ny * nx int64, cleared and filled by this call
+ *   variant      0: by the number of cells; 1: the table in LDS (G * nx * ny <= 4,096); 2: global
+ *                atomics
+ *   workspace    tfrt_mixing_error_workspace_bytes(n, n_groups, nx, ny) bytes (0: bad arguments)
+ * Rows of `grad` other than those named are not written.  Bad arguments are refused with
+ * TFRT_E_BADARG / TFRT_E_WORKSPACE before any launch.
+ */
+size_t tfrt_mixing_error_workspace_bytes(int64_t n, int32_t n_groups, int32_t nx, int32_t ny);
+int tfrt_mixing_error(const void* rows, int64_t stride, int64_t n, int32_t state_dtype,
+                      int32_t dimension, const int32_t* mask, int32_t field_x, int32_t field_y,
+                      const int32_t* group, int64_t n_source, const int32_t* perm,
+                      int32_t n_groups, const double* weight, int32_t nx, int32_t ny, double x0,
+                      double x1, double sx, double y0, double y1, double sy, double oob_weight,
+                      double* grad, int64_t grad_stride, double* error_out, double* used_out,
+                      double* group_errors, double* pull, int64_t* hq, int32_t variant,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* FlatFieldError: the foci of all groups must lie in ONE plane with the unit normal a = `axis` --
  * wherever along the normal that plane has to stand.  The error is the sum, over the counting rays
  * of the groups with a focus, of the squared distance of their group's focus from that plane, in

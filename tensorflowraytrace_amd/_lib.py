@@ -261,6 +261,12 @@ SIGNATURES = {
         c_i32, c_vp,                                                          # mode, covariance
         c_f64, c_f64, c_f64, c_f64, c_f64, c_f64, c_i32, c_f64,               # domain, mbits, oob_weight
         c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]),
+    "tfrt_mixing_error_workspace_bytes": (c_sz, [c_i64, c_i32, c_i32, c_i32]),
+    "tfrt_mixing_error": (c_i32, [
+        c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_i32, c_i32,                 # columns, mask, fields
+        c_vp, c_i64, c_vp, c_i32, c_vp,                                       # group, perm, G, weight
+        c_i32, c_i32, c_f64, c_f64, c_f64, c_f64, c_f64, c_f64, c_f64,        # nx, ny, domain, oob_weight
+        c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]),
     "tfrt_flatfield_error_workspace_bytes": (c_sz, [c_i64, c_i32]),
     "tfrt_flatfield_error": (c_i32, [
         c_vp, c_i64, c_i64, c_i32, c_i32, c_vp,                               # columns, dimension, mask

@@ -22,7 +22,13 @@ given target, or the centroids of the groups of one parent must coincide --
 ``tfrt_centroid_error`` (clear, SpotError's accumulate, with parents their records, table, seed);
 a ``MomentError`` -- the covariance of every group's rays, the size and the shape of its spot, must
 be a given matrix, or must be round -- ``tfrt_moment_error`` (clear, SpotError's accumulate on a
-finer grid, the integer centres, the limb products about them, table, seed).
+finer grid, the integer centres, the limb products about them, table, seed); a ``MixingError``
+-- every group of rays must land with the same density, whatever that density is: with ``Hq`` the
+int64 bilinear histogram of ``DensityError`` kept per group, ``p_gb = Hq_gb / nq_g`` a group's
+density and ``m_b = Pq_b / Nq`` the pooled one (``nq``, ``Pq``, ``Nq``: the integer margins), the
+error is ``sum_g (nq_g / Nq) * B * sum_b (p_gb - m_b)**2`` plus ``DensityError``'s penalties and
+the pull on a cell ``D_gb = (2 * B / N) * (p_gb - m_b)``, ``N = Nq * 2**-32`` --
+``tfrt_mixing_error`` (clear, splat, margins, pulls, finish, seed).
 A ``SumError`` is a weighted sum of such terms and of ``GoalError``s: every term's launches into a
 seed block of its own (a ``GoalError`` through ``tfrt_goal_error_columns``), then ONE
 ``tfrt_error_combine`` for the step's seed block and error.
@@ -32,7 +38,7 @@ numbers, which is what the parity tests compare.
 
 The protocol between a built-in term (``GoalError``, ``DensityError``, ``SpotError``,
 ``TransportError``, ``FocusError``, ``DistortionError``, ``FlatFieldError``, ``CentroidError``,
-``MomentError``) and the fused 3-D step:
+``MomentError``, ``MixingError``) and the fused 3-D step:
 
 * ``rows``, ``fields``, ``rows_for(dimension)``: the rows of the ray block (the field codes) the
   term reads;
@@ -2186,9 +2192,212 @@ class _FlatFieldTerms(torch.autograd.Function):
         return (upstream[:, 0] * grad).to(ctx.dtype), None, None, None
 
 
+class MixingError(_CoupledError):
+    """Every group of rays must land with the SAME density on the target -- whatever that density
+    is: the R, G, B and W dies of an LED behind a mixing rod or a collimator (colour uniformity in
+    the near field with ``("y_end", "z_end")``, in the far field with ``("y_dir", "z_dir")``), an
+    emitter array that must survive a dead die, a homogeniser whose output must not depend on
+    where the light entered (the groups are the input zones), a beam combiner.  A ``DensityError``
+    per group needs a goal in advance and pins every group to it; here the pooled shape stays
+    free -- a ``DensityError`` beside it in a ``SumError`` states that one.
+
+    ``fields``, ``domain``, ``oob_weight``, ``weights`` and the bilinear splat are exactly
+    ``DensityError``'s; ``bins`` is ``nx`` or ``(nx, ny)``, at most 65,536 bins.  ``groups`` and
+    ``n_groups`` are ``SpotError``'s: one label per SOURCE ray (a tensor, or a callable with
+    ``n_groups``), kept as int32 on the device (``labels``) and overwritable in place between
+    replays, looked up through the trace's order inside the kernel; ``n_groups`` (G) at most 1,024
+    and ``n_groups * bins`` at most ``2**20``.
+
+    For every finished ray, float64 and int64, every operation rounded on its own
+    (include/tfrt_hip.h, tfrt_mixing_error), B the number of bins:
+
+    * the classification of ``DensityError`` (with ``weights``: the weighted one), then: a ray
+      without a source ray, or whose label lies outside ``[0, G)``, counts as one with a
+      non-finite coordinate -- nothing, zero gradient, no penalty;
+    * a ray outside the closed domain adds ``oob_weight * (ex**2 + ey**2)``, times ``w`` last
+      with weights; its gradient is the derivative of that;
+    * a ray inside adds ``rint(b * 2**32)`` (``rint((b * w) * 2**32)`` with weights) to its two
+      or four bins of ITS OWN GROUP's plane of the int64 histogram ``Hq[G, ny, nx]``;
+    * the margins are integer sums, free of order: ``nq_g = sum_b Hq[g, b]``,
+      ``Pq_b = sum_g Hq[g, b]``, ``Nq = sum_g nq_g``;
+    * ``p_gb = Hq_gb / nq_g`` is the group's density, ``m_b = Pq_b / Nq`` the pooled one,
+      ``e_g = B * sum_b (p_gb - m_b)**2`` the mean squared difference in units of the uniform
+      density, ``E_mix = sum_g (nq_g / Nq) * e_g`` and ``error = E_mix + penalties``: ONE error
+      term, ``{error, 1, error}``, as ``DensityError``.  A group with ``nq_g == 0`` is unused: it
+      adds nothing, pulls nothing and its ``e_g`` reads as NaN; with ``Nq == 0`` everything is 0;
+    * the pull ``D_gb = (2 * B / N) * (p_gb - m_b)`` with ``N = Nq * 2**-32``; a ray inside gets
+      ``DensityError``'s gradient expression on its own group's plane of ``D``, times ``w`` last,
+      chained onto start and end rows with a direction field.  No ``m``, ``n_g`` or ``N`` is
+      differentiated: ``m`` is the mass-weighted mean of the ``p_g`` and so minimises the error,
+      and a ray inside carries total weight 1 wherever it stands.
+    * every float sum has a fixed shape and order -- over the bins of a group the fixed-shape
+      workgroup sum, over the groups ``CentroidError``'s --: two runs give the same bits.
+
+    It is an ordinary ``error_function(engine)`` (the generic path: ``ops.mixing_error`` over the
+    finished rays' columns under a ``torch.autograd.Function``), which also serves sources that
+    are not traced in place, ``deterministic=True``, fewer than 4,096 rays, several ranks and 2-D
+    engines.  On a 3-D engine that traces its source in place the optimiser runs it on the fused,
+    graph-replayed step exactly where a ``DensityError`` runs (``FusedStep._rowwise3d`` with
+    ``tfrt_mixing_error``: clear, splat, margins, pulls, finish, seed), and it is a legal term of
+    a ``SumError``.
+
+    ``last_hq`` is the (G, ny, nx) int64 histogram of the last evaluation ((G, nx) with one
+    field), ``shares()`` the densities ``p`` of that shape (NaN for an unused group), ``pooled()``
+    the pooled density ``m``, ``group_errors()`` the (G,) ``e_g``, ``groups_used`` the number of
+    used groups (read from the device).  ``splat_variant`` (0: by the number of cells; 1: table in
+    LDS; 2: global atomics) is tfrt_mixing_error's, for measuring."""
+
+    splat_variant = 0
+
+    def __init__(self, fields, groups, domain, bins, oob_weight=0.0, n_groups=None, weights=None):
+        what = "MixingError"
+        self.fields, self.domain = _fields_and_domain(what, fields, domain)
+        self.rows = [_FIELDS3.index(f) for f in self.fields]
+        self.has_direction = any(f.endswith("_dir") for f in self.fields)
+        k = len(self.fields)
+        try:
+            self.oob_weight = float(oob_weight)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"{what}: oob_weight must be finite and >= 0") from e
+        if not (self.oob_weight >= 0.0 and np.isfinite(self.oob_weight)):
+            raise ValueError(f"{what}: oob_weight must be finite and >= 0")
+        try:
+            counts = (int(bins),) * k if np.ndim(bins) == 0 else tuple(int(b) for b in bins)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"{what}: bins must be nx or (nx, ny), got {bins!r}") from e
+        if len(counts) != k or any(c < 1 for c in counts) \
+                or int(np.prod(counts, dtype=np.int64)) > ops.DENSITY_MAX_BINS:
+            raise ValueError(f"{what}: bins must give one count >= 1 per field and at most "
+                             f"{ops.DENSITY_MAX_BINS} bins, got {bins!r}")
+        self.bins = counts
+        _init_groups(self, what, groups, n_groups, ops.MIXING_MAX_GROUPS)
+        if self.n_groups * int(np.prod(counts, dtype=np.int64)) > ops.MIXING_MAX_CELLS:
+            raise ValueError(f"{what}: n_groups * bins must not exceed {ops.MIXING_MAX_CELLS}, "
+                             f"got {self.n_groups} groups of {bins!r} bins")
+        self.grid = ops.density_grid(self.domain, counts[0], counts[1] if k == 2 else None)
+        self.last_hq = self.last_pull = self.last_group_errors = self.last_used = None
+        _init_weights(self, what, weights)
+        if self.weights is not None and self.labels is not None \
+                and self.weights.numel() != self.labels.numel():
+            raise ValueError(f"{what}: {self.weights.numel()} weights for "
+                             f"{self.labels.numel()} labels -- one of each per source ray")
+
+    def labels_of(self, src):
+        """The int32 label buffer of the source set ``src`` on its device, one label per source
+        ray, given or computed and cached as ``SpotError.labels_of`` does."""
+        return _source_buffer(self, "labels", self.groups,
+                              lambda v, dev: _as_labels("MixingError", v, dev), src,
+                              "MixingError", "label")
+
+    def graph_key(self):
+        """What a captured step has baked in: the addresses of the label buffer and of the weight
+        buffer, the grid, ``n_groups`` and the constants."""
+        lab = self.labels
+        return (None if lab is None else (lab.data_ptr(), tuple(lab.shape)), self.n_groups,
+                self.bins, self.grid, self.oob_weight, self.splat_variant) + _weights_key(self)
+
+    def evaluate(self, rows, row_x, row_y, labels, mask=None, perm=None, dimension=None,
+                 weights=None, **buffers):
+        """``ops.mixing_error`` of the columns of ``rows`` with these labels, bins, domain and
+        weight (``dimension`` given: ``rows`` is the geometry block, ``row_x`` / ``row_y`` field
+        codes; ``weights``: the buffer of ``weights_of``)."""
+        if weights is not None and weights.numel() != labels.numel():
+            raise ValueError(f"MixingError: {weights.numel()} weights for {labels.numel()} "
+                             "labels -- one of each per source ray")
+        out = ops.mixing_error(rows, row_x, row_y, labels, self.n_groups, self.bins, self.grid,
+                               self.oob_weight, mask=mask, perm=perm, variant=self.splat_variant,
+                               dimension=dimension, weights=weights, **buffers)
+        self.last_hq, self.last_pull = out[2], out[3]
+        self.last_group_errors, self.last_used = out[4], out[5]
+        return out
+
+    def seed_columns(self, cols, hold):
+        """tfrt_mixing_error on the step's columns: labels and weights through the trace's order
+        ``cols.perm`` inside the kernels, as a SpotError; the histogram goes into
+        ``hold.buffers["hq"]``, (G, ny, nx), the pulls into ``["pull"]``, the groups' errors into
+        ``["group_errors"]``, (G,), and the counts into ``["used_out"]``, (2,)."""
+        labels, weights = self.labels_of(cols.src), self.weights_of(cols.src)
+        G = self.n_groups
+        dev = cols.rows.device
+        shape = (G,) + tuple(reversed(self.bins))
+        nx, ny = self.bins[0], (self.bins[1] if len(self.bins) == 2 else 1)
+        held = self._held(hold, "hq", shape, torch.int64, dev,
+                          lambda: _lib.lib().tfrt_mixing_error_workspace_bytes(cols.n, G, nx, ny))
+        if "pull" not in held:
+            held["pull"] = torch.zeros(shape, dtype=torch.float64, device=dev)
+            held["group_errors"] = torch.zeros(G, dtype=torch.float64, device=dev)
+            held["used_out"] = torch.zeros(2, dtype=torch.float64, device=dev)
+        self.evaluate(cols.rows, *_xy(self.rows), labels, mask=cols.mask, perm=cols.perm,
+                      dimension=3, weights=weights, grad=hold.g_fin, err=hold.err, **held)
+
+    def _last(self, name):
+        value = getattr(self, name)
+        if value is None:
+            raise RuntimeError("MixingError: no evaluation yet")
+        return value
+
+    def shares(self):
+        """(G, ny, nx) float64 densities ``p_gb = Hq_gb / nq_g`` of the last evaluation ((G, nx)
+        with one field), NaN for a group without mass."""
+        hq = self._last("last_hq")
+        flat = hq.reshape(hq.shape[0], -1)
+        nq = flat.sum(dim=1)
+        p = flat.double() / torch.where(nq > 0, nq, torch.ones_like(nq)).double()[:, None]
+        p = torch.where((nq > 0)[:, None], p, torch.full_like(p, float("nan")))
+        return p.reshape(hq.shape)
+
+    def pooled(self):
+        """(ny, nx) float64 pooled density ``m_b = Pq_b / Nq`` of the last evaluation ((nx,) with
+        one field), NaN when nothing landed."""
+        hq = self._last("last_hq")
+        pq = hq.sum(dim=0)
+        return pq.double() / pq.sum().double()
+
+    def group_errors(self):
+        """(G,) float64 ``e_g`` of the last evaluation, NaN for a group without mass."""
+        return self._last("last_group_errors")
+
+    @property
+    def groups_used(self):
+        """The number of groups with mass in the last evaluation, read from the device."""
+        return int(self._last("last_used")[0])
+
+    def __call__(self, engine):
+        """The error as a (1,) tensor through the generic path; the gradient rows come back in
+        ``backward``."""
+        codes = self.rows_for(engine.dimension)
+        fin = engine.finished_rays
+        if not bool(fin):
+            return torch.zeros(1, dtype=torch.float64)
+        labels = self.labels_of(engine._trace_src)
+        block, weights, ids, dim, codes = self._finished_block(engine, fin, codes, ids=True)
+        return _MixingTerms.apply(block, self, labels, ids, weights, dim, codes)
+
+
+class _MixingTerms(torch.autograd.Function):
+    """MixingError over the finished rays, no mask; ``ids``: the source ray of every column;
+    ``block``, ``dimension`` and ``codes`` as for ``_DensityTerms``; ``weights`` or None."""
+
+    @staticmethod
+    def forward(ctx, block, erf, labels, ids, weights=None, dimension=None, codes=None):
+        rows = block.detach().contiguous()
+        if codes is None:
+            codes = (0, 1)[:rows.shape[0]]
+        out = erf.evaluate(rows, *_xy(codes), labels, perm=ids, dimension=dimension,
+                           weights=weights)
+        ctx.save_for_backward(out[1])
+        ctx.dtype = block.dtype
+        return out[0][:1].clone()
+
+    @staticmethod
+    def backward(ctx, upstream):
+        grad, = ctx.saved_tensors
+        return (upstream * grad).to(ctx.dtype), None, None, None, None, None, None
+
+
 # the coupled errors: all finished rays of a step enter one evaluation (one process)
 _COUPLED = (DensityError, SpotError, TransportError, FocusError, DistortionError, FlatFieldError,
-            CentroidError, MomentError)
+            CentroidError, MomentError, MixingError)
 
 
 class SumError:
@@ -2200,7 +2409,7 @@ class SumError:
 
     ``terms``: 1 to 8 distinct instances of ``GoalError``, ``DensityError``, ``SpotError``,
     ``TransportError``, ``FocusError``, ``DistortionError``, ``FlatFieldError``,
-    ``CentroidError`` or ``MomentError``; a ``RowwiseError``, a nested ``SumError`` or the same object twice is a ValueError.  ``weights``: K finite values >= 0, default all ones, kept as the (K,) float64
+    ``CentroidError``, ``MomentError`` or ``MixingError``; a ``RowwiseError``, a nested ``SumError`` or the same object twice is a ValueError.  ``weights``: K finite values >= 0, default all ones, kept as the (K,) float64
     device tensor ``weights``; ``set_weights(values)`` validates on the host and overwrites that
     buffer in place, so a replayed graph sees the new values without a re-capture (as
     ``TransportError.set_goal``).  A weight of 0 switches a term off for a phase; the term is
@@ -2244,7 +2453,8 @@ class SumError:
             if not isinstance(t, (GoalError,) + _COUPLED):
                 raise ValueError("SumError: terms must be GoalError, DensityError, SpotError, "
                                  "TransportError, FocusError, DistortionError, FlatFieldError or "
-                                 "CentroidError instances, or MomentError ones; got "
+                                 "CentroidError instances, or MomentError or MixingError ones; "
+                                 "got "
                                  f"{type(t).__name__}")
         if len(set(id(t) for t in terms)) != len(terms):
             raise ValueError("SumError: the same term object is listed twice (a term keeps the "

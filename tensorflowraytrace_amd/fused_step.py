@@ -33,7 +33,7 @@ fixed-shape column), ``fn`` and its autograd, and ``tfrt_trace2d_backward_rows``
 gradient; ``_rowwise3d`` does the same on a 3-D engine with an in-place trace that leaves the
 finished rows at the rays' own columns.  A coupled error (``DensityError``, ``SpotError``,
 ``TransportError``, ``FocusError``, ``DistortionError``, ``FlatFieldError``, ``CentroidError``,
-``MomentError``) takes ``_rowwise3d`` too, with the term's own launches
+``MomentError``, ``MixingError``) takes ``_rowwise3d`` too, with the term's own launches
 (``term.seed_columns``, errors.py) in the place of ``fn`` and its autograd.  A ``SumError`` takes
 ``_rowwise3d`` as well (``_sum_seeds3d``): every term's ``seed_columns`` into a seed block of its
 own, then ONE ``tfrt_error_combine`` for the step's seed block and error.
@@ -58,8 +58,8 @@ from ._lib import RayOut, check
 
 # (the error terms are reached through this module too: optimizer.py and the tests import them here)
 from .errors import (_COUPLED, _GEO2, _GEO3, _Columns, CentroidError, DensityError,  # noqa: F401
-                     DistortionError, FlatFieldError, FocusError, GoalError, MomentError,
-                     RowwiseError, SpotError, SumError, TransportError)
+                     DistortionError, FlatFieldError, FocusError, GoalError, MixingError,
+                     MomentError, RowwiseError, SpotError, SumError, TransportError)
 
 _CLASS_FLAGS = (("finished", _lib.COMPILE_FINISHED), ("active", _lib.COMPILE_ACTIVE),
                 ("stopped", _lib.COMPILE_STOPPED), ("dead", _lib.COMPILE_DEAD))
@@ -217,8 +217,8 @@ class FusedStep:
     """Runs ``SGD_Optimizer.single_step`` for a ``GoalError`` or a ``RowwiseError`` as a fixed
     launch sequence, on 3-D engines and on 2-D ones (one process), and for a ``DensityError``, a
     ``SpotError``, a ``TransportError``, a ``FocusError``, a ``DistortionError``, a
-    ``FlatFieldError``, a ``CentroidError``, a ``MomentError`` or a ``SumError`` of them on 3-D
-    engines;
+    ``FlatFieldError``, a ``CentroidError``, a ``MomentError``, a ``MixingError`` or a ``SumError``
+    of them on 3-D engines;
     see the module docstring.
     One instance per optimizer."""
 

@@ -2658,6 +2658,212 @@ def _moment_error_cpu(rows, row_x, row_y, group, n_groups, grid, mode, covarianc
     err[2] = e / n_terms if n_terms > 0 else float("nan")
 
 
+# ------------------------------------------------------- every group with the same density
+MIXING_MAX_GROUPS = 1024
+MIXING_MAX_CELLS = 1 << 20         # n_groups * bins
+MIXING_LDS_CELLS = 4096            # tfrt_mixing_error: the whole table as int64 in LDS, 32 KiB
+
+
+def mixing_error(rows, row_x, row_y, group, n_groups, bins, grid, oob_weight=0.0, mask=None,
+                 perm=None, grad=None, err=None, hq=None, pull=None, group_errors=None,
+                 used_out=None, workspace=None, variant=0, dimension=None, weights=None):
+    """tfrt_mixing_error: the MixingError of the columns of ``rows`` -- every group of rays must
+    land with the same density on the (ny, nx) bins, whatever that density is.  The columns,
+    ``row_x`` / ``row_y`` (-1: one field), ``mask``, ``oob_weight``, ``dimension`` and ``weights``
+    are ``density_error``'s, ``grid`` is ``density_grid(domain, nx, ny)``; ``bins`` is ``(nx, ny)``
+    (``(nx,)`` or ``nx`` with one field).  ``group``: contiguous int32, one label per SOURCE ray;
+    ``perm``: optional int32 (n,), the source ray of column i (None: column i is source ray i);
+    ``n_groups``: G, at most ``MIXING_MAX_GROUPS`` with ``G * nx * ny <= MIXING_MAX_CELLS``.  A
+    column without a source ray, with a label outside ``[0, G)`` or -- with ``weights`` -- with a
+    weight that is not in [0, 1] does not count.  ``variant``: 0 by the number of cells, 1 the
+    table in LDS (up to ``MIXING_LDS_CELLS`` cells), 2 global atomics.
+
+    Returns (err {sum, 1, mean}, grad, hq (G, ny, nx) int64 -- (G, nx) with one field --, pull of
+    hq's shape float64: D, group_errors (G,) float64: e_g, NaN for a group without mass, used_out
+    (2,) float64 {groups used, N}).  ``grad``, ``err``, ``hq``, ``pull``, ``group_errors``,
+    ``used_out``, ``workspace`` (uint8): buffers to reuse -- with all of them given a CUDA call
+    allocates nothing.  Rows of ``grad`` other than the fields' own (all of them with a direction
+    field) are written only when ``grad`` is made here (zeros).
+
+    CUDA tensors run the kernels.  CPU tensors run a torch restatement with the same int64
+    histogram, the same operations per cell and per ray and the same order of every sum: every
+    output agrees bit for bit."""
+    what = "mixing_error"
+    n_groups = int(n_groups)
+    two = row_y >= 0
+    counts = (int(bins),) if np.ndim(bins) == 0 else tuple(int(b) for b in bins)
+    if len(counts) != (2 if two else 1) or any(c < 1 for c in counts):
+        raise ValueError(f"{what}: bins must give one count >= 1 per field, got {bins!r}")
+    nx, ny = counts[0], (counts[1] if two else 1)
+    if group.dtype != torch.int32 or group.dim() != 1 or not group.is_contiguous():
+        raise ValueError(f"{what}: group must be a contiguous int32 vector, one label per "
+                         "source ray")
+    if not 1 <= n_groups <= MIXING_MAX_GROUPS:
+        raise ValueError(f"{what}: n_groups must lie in 1 .. {MIXING_MAX_GROUPS}")
+    if nx * ny > DENSITY_MAX_BINS or n_groups * nx * ny > MIXING_MAX_CELLS:
+        raise ValueError(f"{what}: at most {DENSITY_MAX_BINS} bins and {MIXING_MAX_CELLS} cells "
+                         "(n_groups * bins)")
+    if variant not in (0, 1, 2) or (variant == 1 and n_groups * nx * ny > MIXING_LDS_CELLS):
+        raise ValueError(f"{what}: variant must be 0, 1 (up to {MIXING_LDS_CELLS} cells) or 2")
+    n = rows.shape[1]
+    _check_field_codes(what, rows, row_x, row_y, dimension)
+    if weights is not None:
+        _check_weights(what, weights)
+        if weights.numel() != group.numel():
+            raise ValueError(f"{what}: {weights.numel()} weights for {group.numel()} labels -- "
+                             "one of each per source ray")
+    grad, err = _column_buffers(what, rows, grad, err, mask, perm)
+    dev = rows.device
+    shape = (n_groups, ny, nx) if two else (n_groups, nx)
+    made = dict(hq=(shape, torch.int64), pull=(shape, torch.float64),
+                group_errors=((n_groups,), torch.float64), used_out=((2,), torch.float64))
+    given = dict(hq=hq, pull=pull, group_errors=group_errors, used_out=used_out)
+    for name, (shp, dtype) in made.items():
+        if given[name] is None:
+            given[name] = torch.empty(shp, dtype=dtype, device=dev)
+        b = given[name]
+        if tuple(b.shape) != shp or b.dtype != dtype or not b.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous {dtype} of shape {shp}")
+    hq, pull = given["hq"], given["pull"]
+    group_errors, used_out = given["group_errors"], given["used_out"]
+    if not rows.is_cuda:
+        _mixing_error_cpu(rows, row_x, row_y, group, n_groups, nx, ny, grid, float(oob_weight),
+                          mask, perm, grad, err, hq, pull, group_errors, used_out, dimension,
+                          weights)
+        return err, grad, hq, pull, group_errors, used_out
+    L = _lib.lib()
+    workspace = _column_workspace(
+        what, rows, grad, workspace,
+        lambda: L.tfrt_mixing_error_workspace_bytes(n, n_groups, nx, ny), group, mask, perm, err,
+        hq, pull, group_errors, used_out, weights)
+    x0, x1, sx, y0, y1, sy = grid
+    # (the field-code form covers plain rows: codes below 2 * dimension are rows of the block)
+    check(L.tfrt_mixing_error(
+        _p(rows), rows.stride(0), n, _DT[rows.dtype], 3 if dimension is None else int(dimension),
+        _p(mask), row_x, row_y, _p(group), group.numel(), _p(perm), n_groups, _p(weights), nx, ny,
+        x0, x1, sx, y0, y1, sy, float(oob_weight), _p(grad), grad.stride(0), _p(err),
+        _p(used_out), _p(group_errors), _p(pull), _p(hq), int(variant), _p(workspace),
+        workspace.numel(), _stream(rows)), "tfrt_mixing_error")
+    return err, grad, hq, pull, group_errors, used_out
+
+
+def mixing_bins_sum(values):
+    """The sums of the rows of ``values`` (G, B) in the fixed shape and order of k_mixing_pulls,
+    as float64 torch ops on the CPU: thread j of 1,024 takes the bins j, j + 1024, ... of its
+    group in ascending order from 0.0, the 64 lanes of a wave are combined by ``v += v[lane ^ d]``
+    for d = 32 .. 1, then the 16 waves in index order from 0.0."""
+    T = DISTORTION_BLOCK
+    G, B = values.shape
+    trips = max((B + T - 1) // T, 1)
+    v = torch.zeros((G, trips * T), dtype=torch.float64)
+    v[:, :B] = values
+    s = torch.zeros((G, T), dtype=torch.float64)
+    for trip in range(trips):
+        s = s + v[:, trip * T:(trip + 1) * T]   # (squares are >= 0: adding 0.0 changes no bit)
+    w = s.view(G, T // 64, 64)
+    for d in (32, 16, 8, 4, 2, 1):
+        w = w[:, :, :d] + w[:, :, d:2 * d]
+    total = torch.zeros(G, dtype=torch.float64)
+    for wave in range(T // 64):
+        total = total + w[:, wave, 0]
+    return total
+
+
+def _mixing_tables_cpu(hq2):
+    """(pull (G, B), group_errors (G,), used (G,) bool, E_mix, N) of the int64 histogram ``hq2``
+    (G, B): mixing_math.h, operation by operation, over all cells at once (CPU)."""
+    G, B = hq2.shape
+    nq = hq2.sum(dim=1)
+    pq = hq2.sum(dim=0)
+    Nq = int(nq.sum())
+    used = nq > 0
+    nan = torch.full((G,), float("nan"), dtype=torch.float64)
+    if Nq <= 0:
+        return (torch.zeros((G, B), dtype=torch.float64), nan, used,
+                torch.zeros((), dtype=torch.float64), 0.0)
+    Nf = torch.tensor(float(Nq), dtype=torch.float64)       # (int -> double: to nearest, even)
+    N = Nf * 2.3283064365386963e-10
+    # (a tensor over a tensor: torch turns ``number / tensor`` into a reciprocal and a product)
+    scale = torch.tensor(2.0 * float(B), dtype=torch.float64) / N
+    safe = torch.where(used, nq, torch.ones_like(nq)).double()
+    d = hq2.double() / safe[:, None] - (pq.double() / Nf)[None, :]
+    zero = torch.zeros((), dtype=torch.float64)
+    pull = torch.where(used[:, None], scale * d, zero)
+    e_g = float(B) * mixing_bins_sum(torch.where(used[:, None], d * d, zero))
+    term = (safe / Nf) * e_g
+    e_mix = distortion_group_sum(torch.where(used, term, torch.zeros_like(term)), used)
+    return pull, torch.where(used, e_g, nan), used, e_mix, float(N)
+
+
+def _mixing_error_cpu(rows, row_x, row_y, group, n_groups, nx, ny, grid, oob, mask, perm, grad,
+                      err, hq, pull, group_errors, used_out, dimension, weights):
+    """The CPU path of ``mixing_error`` (every torch op rounds on its own, as the kernels do)."""
+    x0, x1, sx, y0, y1, sy = grid
+    two = row_y >= 0
+    n = rows.shape[1]
+    bins = nx * ny
+    x, y, link = _fields_cpu(rows, row_x, row_y, dimension)
+    counts = torch.isfinite(x) & torch.isfinite(y)
+    if mask is not None:
+        counts &= mask[:n] >= 0
+    w = None
+    if weights is not None:
+        w, w_ok = _source_weights(weights, perm, n)
+        counts &= w_ok
+    s = torch.arange(n, dtype=torch.int64) if perm is None else perm[:n].long()
+    s_ok = (s >= 0) & (s < group.numel())
+    label = torch.full((n,), -1, dtype=torch.int64)
+    label[s_ok] = group[s[s_ok]].long()
+    counts &= s_ok & (label >= 0) & (label < n_groups)
+    inside, _, gx, gy = _outside_cpu(x, y, two, grid, oob, counts, w)
+    zero = torch.zeros((), dtype=torch.float64)
+    ex = torch.maximum(x0 - x, zero) + torch.maximum(x - x1, zero)
+    ey = (torch.maximum(y0 - y, zero) + torch.maximum(y - y1, zero)) if two \
+        else torch.zeros_like(x)
+    pens = oob * (ex * ex + ey * ey)
+    if w is not None:
+        pens = pens * w
+    pen = penalty_sum_fixed(pens, counts & ~inside)
+    xi, yi, li = x[inside], y[inside], label[inside]
+    wi = w[inside] if w is not None else None
+    ia, ib, tx = _density_axis(xi, x0, sx, nx)
+    flat = hq.view(-1)
+    flat.zero_()
+    base = li * bins
+
+    def splat(index, b):
+        if wi is not None:
+            b = b * wi
+        flat.index_add_(0, base + index, torch.round(b * DENSITY_FIXED_ONE).long())
+    if two:
+        ja, jb, ty = _density_axis(yi, y0, sy, ny)
+        wx0, wx1, wy0, wy1 = 1.0 - tx, tx, 1.0 - ty, ty
+        splat(ja * nx + ia, wy0 * wx0)
+        splat(ja * nx + ib, wy0 * wx1)
+        splat(jb * nx + ia, wy1 * wx0)
+        splat(jb * nx + ib, wy1 * wx1)
+    else:
+        splat(ia, 1.0 - tx)
+        splat(ib, tx)
+    D2, e_g, used, e_mix, N = _mixing_tables_cpu(hq.view(n_groups, bins))
+    pull.view(n_groups, bins).copy_(D2)
+    group_errors.copy_(e_g)
+    used_out[0], used_out[1] = float(int(used.sum())), N
+    D = D2.reshape(-1)
+    if two:
+        d00, d01 = D[base + ja * nx + ia], D[base + ja * nx + ib]
+        d10, d11 = D[base + jb * nx + ia], D[base + jb * nx + ib]
+        gxi = sx * ((1.0 - ty) * (d01 - d00) + ty * (d11 - d10))
+        gyi = sy * ((1.0 - tx) * (d10 - d00) + tx * (d11 - d01))
+        gy[inside] = gyi if wi is None else gyi * wi
+    else:
+        gxi = sx * (D[base + ib] - D[base + ia])
+    gx[inside] = gxi if wi is None else gxi * wi
+    _write_grad_cpu(grad, n, dimension, row_x, row_y, gx, gy, link, counts)
+    e = e_mix + pen
+    err[0], err[1], err[2] = e, 1.0, e
+
+
 # ------------------------------------------------------- rays of a group through one point
 FOCUS_MAX_GROUPS = 1 << 20
 FOCUS_LDS_GROUPS = 256             # tfrt_focus_error: ten planes of G int64 in LDS, 20 KiB

@@ -30,10 +30,10 @@ import torch
 from . import distributed as tdist
 from . import _lib, ops
 # (GoalError, RowwiseError, DensityError, SpotError, TransportError, FocusError, DistortionError,
-# FlatFieldError, CentroidError, MomentError, SumError: public API)
+# FlatFieldError, CentroidError, MomentError, MixingError, SumError: public API)
 from .fused_step import (FusedStep, GoalError, RowwiseError, DensityError, SpotError,  # noqa: F401
                          TransportError, FocusError, DistortionError, FlatFieldError, CentroidError,
-                         MomentError, SumError, _NotInPlace)
+                         MomentError, MixingError, SumError, _NotInPlace)
 
 
 class DeferredScalar:
